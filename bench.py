@@ -1,12 +1,20 @@
 #!/usr/bin/env python3
 """bench.py -- Msamples/s of the hot path render -> ray_color -> hit/scatter on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--dtype f32|f64] [--width 1920|3840]
+  python bench.py --gpus N --steps K --warmup W [--dtype f32|f64] [--width 1920|3840] [--dump-outputs DIR] [--full]
 
 One "step" = one full render of the workload.  Default = BASELINE.json's headline, configs[2]:
 scene_random_spheres (reseed!(); 485 spheres), camera t_cam1, 1920x1080, 1000 spp, depth 50,
-Float32.  `--dtype f64 --width 3840` is the single-GPU share of configs[4] (3840x2160, Float64); the
-default run also times it (2 steps) and reports it as `f64_4k`.
+Float32.  `--dtype f64 --width 3840` is the single-GPU share of configs[4] (3840x2160, Float64); a
+`--full` run also times it (2 steps) and reports it as `f64_4k`.
+
+A plain run sets up, warms up (W steps), times the K steps and prints the line: the headline and what follows from
+its own steps (kernel time, frame hash, segments, the roofline in the fixed yard-sticks with the committed traffic figures).
+Every other leg below (CPU baseline, accelerated / scan_valu / depth16 / numerics legs, end_to_end, in_library_devices,
+small_frames, the live PMC passes, f64_4k, f64_1080p_d16) runs only with `--full`; without it those keys are null.
+`--dump-outputs DIR` writes the image of the last timed step as DIR/image.npy (what `render()` returns: H x W x 3, row,
+column, RGB, the run's element type) right after the timed steps; an image over 64 MB is replaced by a fixed, seeded
+sample of its pixels (DIR/image_sample.npy, N x 3, and their flat row-major pixel indices DIR/image_sample_pixel.npy).
 The scene is already resident in HBM when the timed region starts and the image is left in HBM
 on rank 0.  With N > 1 ranks the SAME image is tile-sharded over the ranks (strong scaling) and
 the zero-padded shard framebuffers are summed onto rank 0 with one RCCL reduce over xGMI inside
@@ -20,7 +28,7 @@ observed, the backend, every rank's device and mean kernel time, and the SHA-256
 RTW_BENCH_ONE_DEVICE=1 (test aid for one-GPU boxes): every rank uses cuda:0 and the collective runs over
 gloo -- exercises the N > 1 control flow (sharding, collective, max-over-ranks timing), not RCCL itself.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects (all but `roofline`, `value` and the N > 1 figures need `--full`):
   roofline     -- roofline of the only kernel (rtw::trace_kernel), against FIXED hardware yard-sticks (round 4: the definitions no
                   longer follow the kernel's formulation; DESIGN.md section 7 re-expresses rounds 1-3 in them):
                     bound "mfma": `achieved` = EXECUTED matrix-pipe flops (counted ray-sphere tests x 64 flop: two chained
@@ -33,7 +41,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with extra objec
                       v_alignbit_b32 per 64 tests, the alignbit charged 2 cycles (the guide's FMA class) -> 445.6 algorithmic TF, or
                       4.3 cycles (measured slow class, tools/ubench_rates.hip) -> 322.3 TF;
                     `issue_busy`: (MFMA-busy + 2 x VALU instructions) / SIMD-cycles, and `traffic`: HBM bytes per launch (FETCH_SIZE x 2 +
-                      WRITE_SIZE) -- MEASURED IN THIS RUN by three `rocprofv3 --pmc` passes of this script that the default run spawns (one
+                      WRITE_SIZE) -- MEASURED IN THIS RUN by three `rocprofv3 --pmc` passes of this script that a `--full` run spawns (one
                       launch each, ~12 s each; `traffic_static` false); when rocprofv3 is missing or a pass fails, the committed figures of
                       profiles/ (`traffic_static` true).  Plus the algorithmic HBM figure.
   value        -- device-resident rate (scene in HBM, image left in HBM), as the task's bench contract prescribes;
@@ -110,8 +118,13 @@ def parse_args(argv=None):
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--spp", type=int, default=1000)
     ap.add_argument("--depth", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the accelerated / scan_valu / ray_pool / end_to_end (value_end_to_end) / depth16 / f64_4k / f64_1080p_d16 legs: ONE kind of launch, for profiling passes")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other leg (CPU baseline, accelerated / scan_valu / depth16 / numerics legs, end_to_end, "
+                         "in_library_devices, small_frames, live PMC passes, f64_4k, f64_1080p_d16); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the image of the last timed step as DIR/image.npy (a fixed, seeded pixel sample when it exceeds 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline legs")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the accelerated / scan_valu / ray_pool / end_to_end (value_end_to_end) / depth16 / f64_4k / f64_1080p_d16 legs: ONE kind of launch, for profiling passes")
     ap.add_argument("--group-cull", action="store_true", help="time the opt-in accelerated scan instead of the plain one")
     ap.add_argument("--scan-valu", action="store_true", help="time the all-VALU plain scan (RTW_FLAG_SCAN_VALU) instead of the matrix-pipe filter")
     ap.add_argument("--ray-pool", action="store_true", help="time the opt-in ray-pool kernel (RTW_FLAG_RAY_POOL) instead of the lane-loop kernel")
@@ -119,7 +132,7 @@ def parse_args(argv=None):
     ap.add_argument("--chunks", type=int, default=0, help="sample chunks per pixel (0 = library default rule)")
     ap.add_argument("--numerics", choices=["reference", "contract", "reference_fma2"], default="reference",
                     help="the deciding arithmetic of the ray-sphere test (include/rtw_hip.h RTW_FLAG_NUMERICS_*): reference = src/hit.jl:16-18 as the reference "
-                         "evaluates it (the default of the library); the default run also times the other two as `numerics_legs`")
+                         "evaluates it (the default of the library); a --full run also times the other two as `numerics_legs`")
     ap.add_argument("--in-library-devices", type=int, default=0, metavar="N",
                     help="time ONLY the in-library device list (what a Julia caller gets with devices=...): rtw_render_* on host buffers with N devices, "
                          "gathered by peer copies and by the in-library RCCL reduce; N > the visible devices: ordinals repeat (emulation, labelled so)")
@@ -134,6 +147,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.emulate_shard_of > 1 and (args.collective == "gather" or args.gpus > 1):
         ap.error("--emulate-shard-of is a one-rank, reduce-layout analysis mode")
     return args
@@ -295,11 +310,32 @@ class Workload:
         fence(c)
         return time.perf_counter() - t0, first_ms, k_ms[-n_steps:]
 
-    def frame_sha256(self):
+    def frame_host(self):
+        """The assembled frame of the last step on the host, flat H*W*3 in Matrix{RGB{T}} layout (rank 0; outside every timed region)."""
+        return self.frame.reshape(-1)[:self.H * self.W * 3].cpu().numpy()
+
+    def frame_sha256(self, host=None):
         """SHA-256 of the assembled H x W x 3 frame of the last step (rank 0; outside every timed region)."""
-        n = self.H * self.W * 3
-        host = self.frame.reshape(-1)[:n].cpu().numpy()
+        host = self.frame_host() if host is None else host
         return hashlib.sha256(host.tobytes()).hexdigest()
+
+
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(np, host, W, H, out_dir):
+    """--dump-outputs: the frame of the last timed step as a caller of render() receives it (H x W x 3, the run's element type) in
+    out_dir/image.npy.  Over 64 MB (Float64 at 3840 x 2160): a fixed sample of pixels drawn with seed 0 instead, in out_dir/image_sample.npy
+    (N x 3, ascending pixel order) with the pixels' flat row-major indices (i * W + j, as float64) in out_dir/image_sample_pixel.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = host.reshape(W, H, 3).transpose(1, 0, 2)
+    if img.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "image.npy"), np.ascontiguousarray(img))
+        return
+    k = DUMP_LIMIT_BYTES // 2 // (3 * img.itemsize)
+    pix = np.sort(np.random.default_rng(0).choice(H * W, size=k, replace=False))
+    np.save(os.path.join(out_dir, "image_sample.npy"), np.ascontiguousarray(img.reshape(H * W, 3)[pix]))
+    np.save(os.path.join(out_dir, "image_sample_pixel.npy"), pix.astype(np.float64))
 
 
 def issue_busy_from_pmc(key):
@@ -690,7 +726,13 @@ def main():
         return
     stats, coll = [], []
     dt = wl.timed(args.steps, args.warmup, cull=args.group_cull, depth=depth, record=stats, valu=args.scan_valu, coll_ms=coll)
-    sha = wl.frame_sha256() if rank == 0 else None
+    sha = None
+    if rank == 0:
+        host = wl.frame_host()
+        sha = wl.frame_sha256(host)
+        if args.dump_outputs:
+            dump_outputs(np, host, W, H, args.dump_outputs)
+        host = None
     kernel_ms = [s["kernel_ms"] for s in stats]
     tests = [s["sphere_tests"] for s in stats]
     segments = [s["segments"] for s in stats]
@@ -711,7 +753,7 @@ def main():
     samples_per_step = W * H * spp / shard_div
     value = samples_per_step * args.steps / dt / 1e6
 
-    extras = not args.no_extras and args.emulate_shard_of <= 1
+    extras = args.full and not args.no_extras and args.emulate_shard_of <= 1
     accel = depth16 = scan_valu = end_to_end = f64_4k = f64_pub = None
     if extras and not args.group_cull:
         # the opt-in accelerated scan (RTW_FLAG_GROUP_CULL, bit-identical image), timed the same way, reported
@@ -799,7 +841,7 @@ def main():
                 roofline["issue_busy"] = pm["issue_busy"]
         cpu = cpu16 = None
         legs = []
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             legs, cpu16 = cpu_legs(wl, args.cpu_seconds)
             cpu = max(legs, key=lambda d: d["value"])
             cpu_counts_short = sorted({cpu["cores"]} | ({16} if cpu16 else set()))       # the Float64 legs: 16 threads and the best count of this curve
@@ -855,7 +897,7 @@ def main():
             line["gpu_over_cpu_16t"] = round(value / cpu16["value"], 1)
     wl.close()
 
-    # configs[4]'s single-GPU share, in the default run only (the headline stays configs[2])
+    # configs[4]'s single-GPU share, in the --full run of the headline workload only (the headline stays configs[2])
     if extras and world == 1 and (args.dtype, W, spp, depth) == ("f32", 1920, 1000, 50) and not (args.group_cull or args.scan_valu):
         w4 = Workload(c, "f64", 3840, 1000, 50)
         st4 = []

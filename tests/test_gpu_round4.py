@@ -223,11 +223,11 @@ def test_huge_sphere_path_off_gives_the_same_frame():
 
 # ---- the bench line -----------------------------------------------------------------------------------------------------------
 def test_bench_line_contract_and_live_counters():
-    """`python bench.py` (small spp): every key of the bench contract, the roofline object in the fixed yard-sticks, HBM traffic and issue-busy
+    """`python bench.py --full` (small spp): every key of the bench contract, the roofline object in the fixed yard-sticks, HBM traffic and issue-busy
     MEASURED by the run itself (rocprofv3 --pmc passes it spawns; `traffic_static` false), the ray-pool leg with the same frame hash, the
     end-to-end value next to the device-resident one, and the reference's published configuration as its own leg."""
     from test_gpu_round3 import _bench
-    p, d = _bench(["--steps", "1", "--warmup", "1", "--spp", "16", "--cpu-seconds", "0.5"], timeout=900)
+    p, d = _bench(["--full", "--steps", "1", "--warmup", "1", "--spp", "16", "--cpu-seconds", "0.5"], timeout=900)
     assert p.returncode == 0 and d is not None, p.stderr[-3000:]
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
         assert k in d, k

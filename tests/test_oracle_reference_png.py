@@ -1,7 +1,7 @@
-"""The ONLY image the reference holds: /root/reference/img/scene_random_spheres_1920x1080.png -- a 961 x 541 screenshot of
-scene_random_spheres through t_cam1 (unknown code version, seed and spp).  SURVEY.md section 8(c): statistical sanity only.  CPU test, build
-container only (the reference is not on the GPU box): the oracle's render of the same camera at 960 x 540 (Float64, depth 16) against
-region statistics of the screenshot.
+"""The ONLY image the reference holds: its img/scene_random_spheres_1920x1080.png (MIT licence), kept byte for byte as the fixture
+tests/golden/reference_screenshot_scene_random_spheres_961x541.png -- a 961 x 541 screenshot of scene_random_spheres through t_cam1
+(unknown code version, seed and spp).  SURVEY.md section 8(c): statistical sanity only.  CPU test: the oracle's render of the same camera
+at 960 x 540 (Float64, depth 16) against region statistics of the screenshot.
 
 What the screenshot PINS (8-bit agreement): the sky gradient (src/ray_color.jl:1-6 + gamma 2, src/vec.jl:22), the camera (src/camera.jl:18-36,
 proto.jl:19: the three unit spheres sit where the oracle puts them), the mirror of the big Metal sphere (reflect, src/light.jl:6: its upper
@@ -15,9 +15,10 @@ import os
 import numpy as np
 import pytest
 
-PNG = "/root/reference/img/scene_random_spheres_1920x1080.png"
+from conftest import GOLDEN
+
+PNG = os.path.join(GOLDEN, "reference_screenshot_scene_random_spheres_961x541.png")
 PIL = pytest.importorskip("PIL.Image")
-pytestmark = pytest.mark.skipif(not os.path.exists(PNG), reason="the reference checkout is not on this box (build container only)")
 
 #: name -> ((row0, row1, col0, col1) in the 540 x 960 frame, tolerance on the per-channel mean)
 REGIONS = {

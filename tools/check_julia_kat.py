@@ -17,6 +17,7 @@ src/hit.jl:16-18 the Julia build emits -- the oracle's `reference` (default of t
 """
 import os
 import sys
+import tempfile
 
 import numpy as np
 
@@ -262,7 +263,9 @@ def check(path):
             print(f"  {os.path.basename(ll)}: fmul {txt.count('fmul')}, fadd {txt.count('fadd')}, fsub {txt.count('fsub')}, llvm.fmuladd {txt.count('llvm.fmuladd')}, "
                   f"llvm.fma {txt.count('llvm.fma.')}, `contract`/`fast` flags {txt.count(' contract ') + txt.count(' fast ')}, llvm.powi {txt.count('llvm.powi')}")
     want = {}
-    for line in predicted_lines("/tmp", mode):
+    with tempfile.TemporaryDirectory() as tmpdir:           # (the predicted render dumps are not compared: a private directory)
+        predicted = predicted_lines(tmpdir, mode)
+    for line in predicted:
         k, v = line.split(":", 1)
         want[k.strip()] = v.strip()
     items = [(f"numerics mode of hit(::Sphere) identified ({mode})", f32 is None or len(f32) == 1, "src/hit.jl:16-18", [], [])]

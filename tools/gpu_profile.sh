@@ -37,8 +37,8 @@ python3 $R/tools/pmc_summarise.py $O
 # committed as profiles/r06_hbm_traffic.json (likewise r06_pmc_summary.json: `roofline.issue_busy`) -- `traffic_static` in the line says that the figure is not measured by bench.py itself)
 cp $O/hbm_traffic.json $R/profiles/r06_hbm_traffic.json; cp $O/pmc_summary.json $R/profiles/r06_pmc_summary.json
 cd $R
-python bench.py > $O/bench_f32.json 2> $O/bench_f32.err; cut -c1-400 $O/bench_f32.json
-python bench.py --dtype f64 --width 3840 --steps 2 --warmup 1 --no-extras > $O/bench_f64_4k.json 2> $O/bench_f64_4k.err; cut -c1-300 $O/bench_f64_4k.json
+python bench.py --full > $O/bench_f32.json 2> $O/bench_f32.err; cut -c1-400 $O/bench_f32.json
+python bench.py --full --dtype f64 --width 3840 --steps 2 --warmup 1 --no-extras > $O/bench_f64_4k.json 2> $O/bench_f64_4k.err; cut -c1-300 $O/bench_f64_4k.json
 python bench.py --emulate-shard-of 8 --steps 3 --no-cpu-baseline > $O/bench_f32_shard8.json 2>/dev/null; cut -c1-300 $O/bench_f32_shard8.json
 RTW_BENCH_ONE_DEVICE=1 python bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline --no-extras 2>/dev/null | grep "^{" > $O/bench_f32_2ranks_one_device.json; cut -c1-300 $O/bench_f32_2ranks_one_device.json
 python tools/kernel_resources.py > $O/kernel_resources.txt 2>&1; tail -12 $O/kernel_resources.txt

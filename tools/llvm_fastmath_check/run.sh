@@ -12,8 +12,9 @@
 # reach inside dot.  The real answer is tools/julia_kat.jl on a Julia box; this narrows what to expect.
 cd "$(dirname "$0")"
 CLANG=${CLANG:-/opt/rocm/lib/llvm/bin/clang}
-$CLANG -O2 -S -march=znver2 hit_sphere_julia_ir.ll -o /tmp/hit_sphere_julia_ir.s 2>/dev/null || exit 1
-awk '/^disc_/ {f=$1} /vfm|vfnm/ {n[f]++} /^disc_/ {n[$1]+=0} END {for (k in n) print k, "fused multiply-adds:", n[k]}' /tmp/hit_sphere_julia_ir.s | sort
-grep -E "^disc_|vfm|vfnm" /tmp/hit_sphere_julia_ir.s
+S=$(mktemp -d)/hit_sphere_julia_ir.s; trap 'rm -rf "$(dirname "$S")"' EXIT
+$CLANG -O2 -S -march=znver2 hit_sphere_julia_ir.ll -o "$S" 2>/dev/null || exit 1
+awk '/^disc_/ {f=$1} /vfm|vfnm/ {n[f]++} /^disc_/ {n[$1]+=0} END {for (k in n) print k, "fused multiply-adds:", n[k]}' "$S" | sort
+grep -E "^disc_|vfm|vfnm" "$S"
 # the fast square root of line 20 stays the IEEE instruction (no reciprocal-square-root estimate for a scalar sqrt on x86), the division by a = 1 folds away
-awk '/^root_julia:/ {f=1} f && /vsqrtss|vrsqrt|vdivss/ {print "root_julia:", $1} f && /retq/ {f=0}' /tmp/hit_sphere_julia_ir.s
+awk '/^root_julia:/ {f=1} f && /vsqrtss|vrsqrt|vdivss/ {print "root_julia:", $1} f && /retq/ {f=0}' "$S"
