@@ -146,6 +146,10 @@ int rtwo_hit_sphere_f32(const float c[3], float r, const float o[3], const float
                         float tmin, float tmax, float rec[8]);
 int rtwo_hit_sphere_f64(const double c[3], double r, const double o[3], const double d[3],
                         double tmin, double tmax, double rec[8]);
+/* the deciding discriminant of hit(::Sphere) (src/hit.jl:13-18) in the unit numerics mode: rows = n x {c[3], r, o[3], d[3]};
+ * half_b (NULL: not wanted) receives the half_b of each row */
+void rtwo_sphere_disc_f32(const float *rows, long n, float *disc, float *half_b);
+void rtwo_sphere_disc_f64(const double *rows, long n, double *disc, double *half_b);
 /* hit(::HittableList): returns index of the closest sphere or -1 */
 /* n rays at once (rays = n x {o[3], d[3]}): idx[i] = -1 on a miss, t[i] = the hit distance */
 void rtwo_hit_world_batch_f32(const rtwo_scene_f32 *, const float *rays, long n, float tmin, float tmax,

@@ -279,6 +279,27 @@ def hit_sphere(c, r, o, d, tmin, tmax, T=np.float64):
     return dict(t=rec[0], p=rec[1:4].copy(), n=rec[4:7].copy(), front=bool(rec[7]))
 
 
+def sphere_disc(c, r, o, d, T=np.float64, half_b=False):
+    """The deciding discriminant of hit_sphere (src/hit.jl:13-18) in the unit numerics mode (set_numerics), batched:
+    c [n, 3], r [n], o [n, 3], d [n, 3] (broadcast) -> disc [n] of dtype T, exactly the binary32 / binary64 value the
+    oracle tests with `disc < 0` (the sign of a zero kept); with half_b=True -> (disc, half_b)."""
+    c, o, d = (np.asarray(a, dtype=T).reshape(-1, 3) for a in (c, o, d))
+    r = np.asarray(r, dtype=T).reshape(-1)
+    n = max(len(c), len(r), len(o), len(d))
+    rows = np.empty((n, 10), T)
+    rows[:, 0:3] = c
+    rows[:, 3] = r
+    rows[:, 4:7] = o
+    rows[:, 7:10] = d
+    out = np.zeros(n, T)
+    hb = np.zeros(n, T)
+    fn = getattr(lib(), "rtwo_sphere_disc_f64" if _is64(T) else "rtwo_sphere_disc_f32")
+    fn.restype = None
+    fn.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p]
+    fn(_p(rows), n, _p(out), _p(hb))
+    return (out, hb) if half_b else out
+
+
 def hit_world(flat_scene, o, d, tmin, tmax, T=np.float64):
     S, keep = make_scene(flat_scene, T)
     rec = np.zeros(8, T)

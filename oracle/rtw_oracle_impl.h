@@ -77,7 +77,7 @@ typedef struct { T t; V3 p, n; int front; } FN(hitrec_);
  *                               on an FMA target if the square does carry the `contract` flag
  *   RTW_NUMERICS_REFERENCE_FMA2 ... and c = fma(-r, r, oc.oc) as well (both fsub-of-a-square sites contracted)
  *   RTW_NUMERICS_CONTRACT       rounds 1-4: three FMA chains (a legal @fastmath contraction only if @fastmath reached into dot) */
-static inline __attribute__((always_inline)) int FN(sphere_test_)(int numerics, V3 c, T r, V3 o, V3 d, T tmin, T tmax, T *t_out) {
+static inline __attribute__((always_inline)) T FN(sphere_disc_)(int numerics, V3 c, T r, V3 o, V3 d, T *half_b_out, T *nc_out) {
     V3 oc = FN(vsub_)(o, c);                                            /* :13 */
     T half_b, disc, nc;
     if (numerics == RTW_NUMERICS_CONTRACT) {
@@ -91,6 +91,13 @@ static inline __attribute__((always_inline)) int FN(sphere_test_)(int numerics, 
         disc = numerics == RTW_NUMERICS_REFERENCE ? half_b * half_b - cc : FMA_T(half_b, half_b, -cc);   /* :18 (a == 1: a*c == c) */
         nc = -cc;
     }
+    *half_b_out = half_b;
+    *nc_out = nc;
+    return disc;
+}
+static inline __attribute__((always_inline)) int FN(sphere_test_)(int numerics, V3 c, T r, V3 o, V3 d, T tmin, T tmax, T *t_out) {
+    T half_b, nc;
+    const T disc = FN(sphere_disc_)(numerics, c, r, o, d, &half_b, &nc);
     if (disc < (T)0) return 0;                                          /* :19 */
     g_cand_disc++;                       /* workload statistics only */
     if (half_b < (T)0 || nc > (T)0) g_cand_fwd++;
@@ -491,6 +498,17 @@ void FN(rtwo_skycolor_)(const T dir[3], double out[3]) {
 }
 static inline void FN(rec_out_)(const HREC *h, T rec[8]) {
     rec[0] = h->t; FN(st3_)(rec + 1, h->p); FN(st3_)(rec + 4, h->n); rec[7] = (T)h->front;
+}
+/* the deciding discriminant of sphere_test_ (src/hit.jl:13-18) in the unit numerics mode, for n (c, r, o, d) rows of 10 values;
+ * half_b (may be NULL): the half_b that goes with it */
+void FN(rtwo_sphere_disc_)(const T *rows, long n, T *disc, T *half_b_out) {
+    for (long i = 0; i < n; ++i) {
+        const T *q = rows + 10 * i;
+        const V3 c = {q[0], q[1], q[2]}, o = {q[4], q[5], q[6]}, d = {q[7], q[8], q[9]};
+        T half_b, nc;
+        disc[i] = FN(sphere_disc_)(g_unit_numerics, c, q[3], o, d, &half_b, &nc);
+        if (half_b_out) half_b_out[i] = half_b;
+    }
 }
 int FN(rtwo_hit_sphere_)(const T c[3], T r, const T o[3], const T d[3], T tmin, T tmax, T rec[8]) {
     HREC h;

@@ -65,13 +65,24 @@ template <> struct ScanGroup<float> { static constexpr int N = 4; };    // 4 x 1
 template <> struct ScanGroup<double> { static constexpr int N = 4; };   // 4 x 8 floats = 2 x s_load_dwordx16
 
 struct NoClock { static constexpr bool on() { return false; } __device__ __forceinline__ void lap(int) {} __device__ __forceinline__ void count(int, unsigned) {} };
+// Pass-1 candidate sink: what pass 1 of a scan hands pass 2, per ray (the unit ops U_SINK_*, rtw_units.hpp).  The scans call it only
+// under `if constexpr (SINK::on())`: with this default nothing is compiled in, the trace kernels' instantiations are unchanged.
+//   ray(lane, ok, sc)   the lane's ray used the filter (ok) / the matrix-pipe scale;  cand(lane, i) / inlane(lane, i): sphere i (the
+//   caller's index) was listed for pass 2 / tested by the lane itself.  `lane` is the lane whose ray it is (hit_world_mfma: the owner).
+struct NoSink {
+    static constexpr bool on() { return false; }
+    unsigned self = 0;
+    __device__ __forceinline__ void ray(unsigned, bool, float) {}
+    __device__ __forceinline__ void cand(unsigned, int) {}
+    __device__ __forceinline__ void inlane(unsigned, int) {}
+};
 
 // src/hit.jl:38-50 -- closest hit by linear scan over ALL spheres; `closest` shrinks; a later
 // sphere wins an exact tie.  Same results as the plain loop, organised for the wave:
 //   pass 1  (branch-free, every lane, every sphere): the discriminant of src/hit.jl:13-18 from
 //           wave-uniform sphere data held in SGPRs (scalar loads, prefetched one group ahead);
 //           its sign bit is shifted into a 32-sphere mask word with ONE v_alignbit per sphere.
-//           disc >= 0  <=>  sign bit clear (disc is never -0: hb*hb >= +0; NaN cannot occur for
+//           disc >= 0  <=>  sign bit clear (-0 only in the contract form: cleared there; NaN cannot occur for
 //           finite scenes).  After each word the few candidate indices go to the lane's LDS list.
 //   pass 2  (every lane walks its own list, ascending sphere index): the exact root selection
 //           of src/hit.jl:19-29 against the shrinking `closest`.  Sphere order is preserved, so
@@ -111,9 +122,9 @@ __device__ __forceinline__ void resolve_candidates(int num, SRC src, const typen
     else resolve_candidates_n<T, STRIDE, NUM_REFERENCE_FMA2>(src, rad, o, d, tmin, closest, idx, list, cnt);
 }
 
-template <typename T, int STRIDE, typename SRC, typename CLK = NoClock>
+template <typename T, int STRIDE, typename SRC, typename CLK = NoClock, typename SINK = NoSink>
 __device__ __forceinline__ int hit_world(const DevScene<T> &w, SRC src, V3<T> o, V3<T> d, T tmin, T tmax, T &t_hit,
-                                         unsigned short *list, CLK &&clk = NoClock()) {
+                                         unsigned short *list, CLK &&clk = NoClock(), SINK sink = SINK()) {
     constexpr int G = ScanGroup<T>::N;
     constexpr bool F64 = sizeof(T) == 8;
     constexpr int SW = F64 ? 8 : 4;                              // floats per sphere in the scan array
@@ -154,6 +165,7 @@ __device__ __forceinline__ int hit_world(const DevScene<T> &w, SRC src, V3<T> o,
         of = {(float)o.x, (float)o.y, (float)o.z};
         df = {(float)d.x, (float)d.y, (float)d.z};
     }
+    if constexpr (SINK::on()) sink.ray(sink.self, lane_ok, 0.0f);
     auto test1 = [&](auto tag, const Unit &sp, uint32_t &mask) {
         if constexpr (F64) {
             const float ocx = of.x - sp.v[0], ocy = of.y - sp.v[1], ocz = of.z - sp.v[2];
@@ -176,7 +188,16 @@ __device__ __forceinline__ int hit_world(const DevScene<T> &w, SRC src, V3<T> o,
             } else {
                 sphere_disc_n<T, decltype(tag)::value>(sp.v[0], sp.v[1], sp.v[2], sp.v[3], T(0), o, d, hb, disc);
             }
-            mask = __builtin_amdgcn_alignbit(mask, sign_word(disc), 31);
+            // (contract: fma(half_b, half_b, nc) rounds a tiny negative exact value (|x| <= 2^-150) to -0, which src/hit.jl:19 (`disc < 0`)
+            //  accepts.  u - (u >> 31) clears the sign bit of -0 (0x80000000) and of no other value.  `disc + 0` would do the same, but the
+            //  compiler folds it away: it takes an fma of a square for one that cannot round to -0.  The reference form cannot produce -0
+            //  (half_b * half_b - c), the fma2 filter adds a positive margin.)
+            if constexpr (decltype(tag)::value == NUM_CONTRACT) {
+                const uint32_t u = sign_word(disc);
+                mask = __builtin_amdgcn_alignbit(mask, u - (u >> 31), 31);
+            } else {
+                mask = __builtin_amdgcn_alignbit(mask, sign_word(disc), 31);
+            }
         }
     };
     // (the whole scan loop once per numerics mode: the mode is decided outside the loop, not per sphere)
@@ -217,6 +238,7 @@ __device__ __forceinline__ int hit_world(const DevScene<T> &w, SRC src, V3<T> o,
         uint32_t m = ~mask;                       // bit 31 = sphere `base`, bit 0 = sphere base+31
         if constexpr (F64) { if (!lane_ok) m = 0xffffffffu; }                // no filter for this ray: every sphere
         if (left < RTW_SPHERE_WORD) m <<= (RTW_SPHERE_WORD - ngroups * G);   // partial word: align to bit 31
+        if constexpr (SINK::on()) for (uint32_t s_ = m; s_ != 0u; s_ &= s_ - 1u) sink.cand(sink.self, base + 31 - (int)__builtin_ctz(s_));
         auto push_first = [&]() {                 // append the lane's first remaining candidate of this word
             const int b = __clz((int)m);
             list[cnt * STRIDE] = (unsigned short)(base + b);

@@ -93,9 +93,9 @@ __device__ __forceinline__ void resolve_candidates_anyorder(int num, SRC src, co
     }
 }
 
-template <typename T, int STRIDE, typename SRC, typename ORIG, typename CLK = NoClock>
+template <typename T, int STRIDE, typename SRC, typename ORIG, typename CLK = NoClock, typename SINK = NoSink>
 __device__ __forceinline__ int hit_world_cull(const CullScene<T> &w, SRC src, ORIG orig, V3<T> o, V3<T> d, T tmin, T tmax,
-                                              T &t_hit, unsigned short *list, CLK &&clk = NoClock()) {
+                                              T &t_hit, unsigned short *list, CLK &&clk = NoClock(), SINK sink = SINK()) {
     using V4 = typename Vec4<T>::type;
     constexpr int G = RTW_CULL_BG;
     constexpr int GS = RTW_CULL_GS;
@@ -110,7 +110,9 @@ __device__ __forceinline__ int hit_world_cull(const CullScene<T> &w, SRC src, OR
         }
         list[cnt * STRIDE] = (unsigned short)i;
         cnt += 1;
+        if constexpr (SINK::on()) sink.cand(sink.self, (int)orig[i]);
     };
+    if constexpr (SINK::on()) sink.ray(sink.self, true, 0.0f);
     // A root >= tmin > 0 needs half_b <= 0 or disc > half_b^2 (else -half_b + sqrt(disc) <= 0):
     // spheres entirely behind the ray are not even listed.
     auto member = [&](const V4 &sp, int i) {

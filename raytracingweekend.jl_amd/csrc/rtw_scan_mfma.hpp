@@ -155,8 +155,8 @@ __device__ __forceinline__ double lane_get(double v, unsigned src_lane) {
 // the lane that holds it was measured too: 3.3 rounds of exact tests at 33 % lane utilisation per scan instead of 1.5 -- candidates of one ray in
 // one block come in runs, the list order of the reference's scene is a row of the lattice.)
 struct NoOrig {};
-template <typename T, bool WITH_R, typename SRC, typename ORIG = NoOrig>
-__device__ __forceinline__ void test_singles(int num, SRC src, [[maybe_unused]] const typename Vec4<T>::type *rad, V3<T> o, V3<T> d, T tmin, const WaveScratch &ws, const unsigned *singles, unsigned n, unsigned lane, ORIG orig, unsigned *prof) {
+template <typename T, bool WITH_R, typename SRC, typename ORIG = NoOrig, typename SINK = NoSink>
+__device__ __forceinline__ void test_singles(int num, SRC src, [[maybe_unused]] const typename Vec4<T>::type *rad, V3<T> o, V3<T> d, T tmin, const WaveScratch &ws, const unsigned *singles, unsigned n, unsigned lane, ORIG orig, unsigned *prof, [[maybe_unused]] SINK sink = SINK()) {
     constexpr bool CULLED = !__is_same(ORIG, NoOrig);      // device order != the caller's order: ties go by orig[], the key carries both
     using V4 = typename Vec4<T>::type;
     for (unsigned p0 = 0; p0 < n; p0 += 64u) {
@@ -169,6 +169,7 @@ __device__ __forceinline__ void test_singles(int num, SRC src, [[maybe_unused]] 
         const V3<T> po = {lane_get(o.x, owner), lane_get(o.y, owner), lane_get(o.z, owner)};
         const V3<T> pd = {lane_get(d.x, owner), lane_get(d.y, owner), lane_get(d.z, owner)};
         const V4 s = src[sph];
+        if constexpr (SINK::on()) { if (valid) { if constexpr (CULLED) sink.cand(owner, (int)orig[sph]); else sink.cand(owner, (int)sph); } }
         T hb, disc, root = 0;
         if constexpr (WITH_R) sphere_disc_n<T, NUM_REFERENCE_FMA2>(s.x, s.y, s.z, s.w, rad[sph].x, po, pd, hb, disc);   // (mat0: the radius itself; the LDS copy holds r^2)
         else sphere_disc<T>(num, s.x, s.y, s.z, s.w, T(0), po, pd, hb, disc);
@@ -194,8 +195,8 @@ __device__ __forceinline__ void test_singles(int num, SRC src, [[maybe_unused]] 
         }
     }
 }
-template <typename T, bool WITH_R, typename SRC, typename ORIG = NoOrig>
-__device__ __forceinline__ void resolve_pairs_impl(int num, SRC src, [[maybe_unused]] const typename Vec4<T>::type *rad, V3<T> o, V3<T> d, T tmin, const WaveScratch &ws, unsigned n, unsigned lane, ORIG orig = ORIG(), unsigned *prof = nullptr) {
+template <typename T, bool WITH_R, typename SRC, typename ORIG = NoOrig, typename SINK = NoSink>
+__device__ __forceinline__ void resolve_pairs_impl(int num, SRC src, [[maybe_unused]] const typename Vec4<T>::type *rad, V3<T> o, V3<T> d, T tmin, const WaveScratch &ws, unsigned n, unsigned lane, ORIG orig = ORIG(), unsigned *prof = nullptr, SINK sink = SINK()) {
     __builtin_amdgcn_wave_barrier();
     const uint2 *list = reinterpret_cast<const uint2 *>(ws.pairs);
     unsigned *singles = ws.pairs + 2u * ws.cap;            // ws.cap2 words behind the ws.cap entries
@@ -211,7 +212,7 @@ __device__ __forceinline__ void resolve_pairs_impl(int num, SRC src, [[maybe_unu
             if (!act) break;
             if (total + 64u > ws.cap2) {
                 __builtin_amdgcn_wave_barrier();
-                test_singles<T, WITH_R>(num, src, rad, o, d, tmin, ws, singles, total, lane, orig, prof);
+                test_singles<T, WITH_R>(num, src, rad, o, d, tmin, ws, singles, total, lane, orig, prof, sink);
                 __builtin_amdgcn_wave_barrier();
                 total = 0;
             }
@@ -224,25 +225,25 @@ __device__ __forceinline__ void resolve_pairs_impl(int num, SRC src, [[maybe_unu
         }
     }
     __builtin_amdgcn_wave_barrier();
-    test_singles<T, WITH_R>(num, src, rad, o, d, tmin, ws, singles, total, lane, orig, prof);
+    test_singles<T, WITH_R>(num, src, rad, o, d, tmin, ws, singles, total, lane, orig, prof, sink);
     __builtin_amdgcn_wave_barrier();
 }
 
 // (NUM_REFERENCE_FMA2 reads the radius from mat0: its own copy of the loop, so that the other modes keep their registers)
-template <typename T, typename SRC, typename RAD, typename ORIG = NoOrig>
-__device__ __forceinline__ void resolve_pairs(int num, SRC src, RAD rad, V3<T> o, V3<T> d, T tmin, const WaveScratch &ws, unsigned n, unsigned lane, ORIG orig = ORIG(), unsigned *prof = nullptr) {
-    if (num == NUM_REFERENCE_FMA2) resolve_pairs_impl<T, true>(num, src, rad(), o, d, tmin, ws, n, lane, orig, prof);
-    else resolve_pairs_impl<T, false>(num, src, nullptr, o, d, tmin, ws, n, lane, orig, prof);
+template <typename T, typename SRC, typename RAD, typename ORIG = NoOrig, typename SINK = NoSink>
+__device__ __forceinline__ void resolve_pairs(int num, SRC src, RAD rad, V3<T> o, V3<T> d, T tmin, const WaveScratch &ws, unsigned n, unsigned lane, ORIG orig = ORIG(), unsigned *prof = nullptr, SINK sink = SINK()) {
+    if (num == NUM_REFERENCE_FMA2) resolve_pairs_impl<T, true>(num, src, rad(), o, d, tmin, ws, n, lane, orig, prof, sink);
+    else resolve_pairs_impl<T, false>(num, src, nullptr, o, d, tmin, ws, n, lane, orig, prof, sink);
 }
 
 // Closest hit for the rays of a whole wave (every lane calls it, convergently; has_ray = this lane has a ray).
 // With `mc` (group cull, RTW_FLAG_GROUP_CULL): the spheres come in the cull layout's device order (src, orig), and a block of
 // 32 is visited only when some ray of the half wave can touch its box (the conservative margin of hit_world_cull, in binary32 with
 // the Float32 kappa for both precisions): the table vote of CullGrid, once per scan.  Returns the DEVICE index.
-template <typename T, typename SRC, typename ORIG = NoOrig, typename CLK = NoClock>
+template <typename T, typename SRC, typename ORIG = NoOrig, typename CLK = NoClock, typename SINK = NoSink>
 __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<T> o, V3<T> d, bool has_ray, T tmin, T &t_hit,
                                               const WaveScratch &ws, unsigned lane, CLK &&clk = NoClock(),
-                                              const MfmaCull *mc = nullptr, ORIG orig = ORIG()) {
+                                              const MfmaCull *mc = nullptr, ORIG orig = ORIG(), SINK sink = SINK()) {
     constexpr bool CULLED = !__is_same(ORIG, NoOrig);
     // radii (mat0[i].x) in the order of `src`: read by NUM_REFERENCE_FMA2 only -- fetched from the kernel arguments where that mode needs them, not held across the scan
     auto rad = [&]() -> const typename Vec4<T>::type * { if constexpr (CULLED) return (const typename Vec4<T>::type *)mc->mat0; else return w.mat0; };
@@ -251,6 +252,7 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
     const float s2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
     const float oinf = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(ox), __builtin_fabsf(oy)), __builtin_fabsf(oz));
     const bool ok = has_ray && s2 <= 1.0009f && oinf <= w.mf_o_max;                  // (false for NaN)
+    if constexpr (SINK::on()) { if (has_ray) sink.ray(lane, ok, w.mf_sc); }
     const float q = __builtin_fmaf(oz, dz, __builtin_fmaf(oy, dy, ox * dx));          // d.o
     const float oo = __builtin_fmaf(oz, oz, __builtin_fmaf(oy, oy, ox * ox));
     const float o1 = (__builtin_fabsf(ox) + __builtin_fabsf(oy)) + __builtin_fabsf(oz);
@@ -393,6 +395,7 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
             if constexpr (CULLED) si = __builtin_amdgcn_readfirstlane((int)mc->tab[6 * RTW_CULL_BINS + 4 + hgi]);      // (the list lies with the vote's tables)
             else si = hgi == 0 ? w.huge[0] : w.huge[1];                  // (no dynamic indexing of a by-value struct: that would live in scratch)
             const V4 sg = src[si];
+            if constexpr (SINK::on()) { if (has_ray) { if constexpr (CULLED) sink.inlane(lane, (int)orig[si]); else sink.inlane(lane, si); } }
             T hb_, disc_, root_ = 0;
             T rr_ = T(0);
             if (w.numerics == NUM_REFERENCE_FMA2) rr_ = rad()[si].x;
@@ -422,6 +425,7 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
         for (int hgi = mc->n_exact; hgi < mc->n_huge; ++hgi) {
             const int si = __builtin_amdgcn_readfirstlane((int)mc->tab[6 * RTW_CULL_BINS + 4 + hgi]);
             const V4 sg = src[si];
+            if constexpr (SINK::on()) { if (has_ray) sink.inlane(lane, (int)orig[si]); }
             T hb_, disc_;
             T rr_ = T(0);
             if (w.numerics == NUM_REFERENCE_FMA2) rr_ = rad()[si].x;
@@ -429,7 +433,7 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
             const bool cand = has_ray && !(disc_ < T(0));
             const unsigned long long cm = __ballot(cand);
             if (cm) {
-                if (total + 64u > ws.cap) { resolve_pairs<T>(w.numerics, src, rad, o, d, tmin, ws, total, lane, orig); total = 0; }
+                if (total + 64u > ws.cap) { resolve_pairs<T>(w.numerics, src, rad, o, d, tmin, ws, total, lane, orig, nullptr, sink); total = 0; }
                 if (cand) {
                     // the entry a recording lane (H, j) would write for ray j + 32 half and sphere 32 block + 16 H + register: H, block, register from
                     // the sphere, j and the half from this lane
@@ -564,7 +568,7 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
         clk.count(27, 1u);                                                             // blocks that record entries
         if (total + 64u > ws.cap) {
             clk.lap(4);
-            { unsigned pr[3] = {0u, 0u, 0u}; resolve_pairs<T>(w.numerics, src, rad, o, d, tmin, ws, total, lane, orig, clk.on() ? pr : nullptr); clk.count(13, total); clk.count(14, pr[0]); clk.count(15, pr[1]); clk.count(28, pr[2]); }
+            { unsigned pr[3] = {0u, 0u, 0u}; resolve_pairs<T>(w.numerics, src, rad, o, d, tmin, ws, total, lane, orig, clk.on() ? pr : nullptr, sink); clk.count(13, total); clk.count(14, pr[0]); clk.count(15, pr[1]); clk.count(28, pr[2]); }
             total = 0;
             clk.lap(5);
         }
@@ -578,7 +582,7 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
     }
     }
     if (use_prio) __builtin_amdgcn_s_setprio(sizeof(T) == 4 ? 1 : 0);
-    { unsigned pr[3] = {0u, 0u, 0u}; resolve_pairs<T>(w.numerics, src, rad, o, d, tmin, ws, total, lane, orig, clk.on() ? pr : nullptr); clk.count(13, total); clk.count(14, pr[0]); clk.count(15, pr[1]); clk.count(28, pr[2]); }
+    { unsigned pr[3] = {0u, 0u, 0u}; resolve_pairs<T>(w.numerics, src, rad, o, d, tmin, ws, total, lane, orig, clk.on() ? pr : nullptr, sink); clk.count(13, total); clk.count(14, pr[0]); clk.count(15, pr[1]); clk.count(28, pr[2]); }
     RTW_PROBE_RESOLVE_TWICE();
     clk.lap(5);
     int idx;

@@ -12,8 +12,10 @@ int run_unit(int op_arg, int count, const void *in, void *out, const SceneT *sce
     if (numerics == 2) return fail(-2, "unknown numerics mode %d (unit op %d)", numerics, op_arg);
     if (count < 0 || (count > 0 && (!in || !out))) return fail(-1, "null argument");
     if (count == 0) return 0;
-    const bool needs_scene = op == rtw::U_HIT_WORLD || op == rtw::U_RAY_COLOR || op == rtw::U_HIT_WORLD_LDS || op == rtw::U_HIT_WORLD_CULL || op == rtw::U_HIT_WORLD_MFMA || op == rtw::U_HIT_WORLD_MFMA_CULL;
+    const bool sink = rtw::unit_is_sink(op);
+    const bool needs_scene = op == rtw::U_HIT_WORLD || op == rtw::U_RAY_COLOR || op == rtw::U_HIT_WORLD_LDS || op == rtw::U_HIT_WORLD_CULL || op == rtw::U_HIT_WORLD_MFMA || op == rtw::U_HIT_WORLD_MFMA_CULL || sink;
     if (needs_scene && !scene) return fail(-1, "op %d needs a scene", op);
+    if (sink && scene->n > RTW_SINK_SPHERES) return fail(-5, "unit op %d: the candidate sets hold %d spheres, the scene has %d", op, RTW_SINK_SPHERES, scene->n);
     if (op == rtw::U_GET_RAY && !cam) return fail(-1, "op %d needs a camera", op);
     DeviceGuard guard;
     int dev;
@@ -45,10 +47,10 @@ int run_unit(int op_arg, int count, const void *in, void *out, const SceneT *sce
     }
     using V4 = typename rtw::Vec4<T>::type;
     size_t lds_bytes = 0;
-    if (op == rtw::U_HIT_WORLD_LDS || op == rtw::U_HIT_WORLD_MFMA) lds_bytes = (size_t)rtw::scene_geom_alloc(S.n, S.n_pad) * sizeof(V4);
-    if (op == rtw::U_HIT_WORLD_MFMA && !S.mf_ops) return fail(-5, "the scene has no matrix-pipe scan operands (unit op %d)", op);
-    if (op == rtw::U_HIT_WORLD_MFMA_CULL && !CS.mf_ops) return fail(-5, "the scene has no matrix-pipe cull operands (unit op %d)", op);
-    if (op == rtw::U_HIT_WORLD_CULL || op == rtw::U_HIT_WORLD_MFMA_CULL) {
+    if (op == rtw::U_HIT_WORLD_LDS || op == rtw::U_HIT_WORLD_MFMA || op == rtw::U_SINK_LDS || op == rtw::U_SINK_MFMA) lds_bytes = (size_t)rtw::scene_geom_alloc(S.n, S.n_pad) * sizeof(V4);
+    if ((op == rtw::U_HIT_WORLD_MFMA || op == rtw::U_SINK_MFMA) && !S.mf_ops) return fail(-5, "the scene has no matrix-pipe scan operands (unit op %d)", op);
+    if ((op == rtw::U_HIT_WORLD_MFMA_CULL || op == rtw::U_SINK_MFMA_CULL) && !CS.mf_ops) return fail(-5, "the scene has no matrix-pipe cull operands (unit op %d)", op);
+    if (op == rtw::U_HIT_WORLD_CULL || op == rtw::U_HIT_WORLD_MFMA_CULL || op == rtw::U_SINK_CULL || op == rtw::U_SINK_MFMA_CULL) {
         const size_t n_cull = (size_t)rtw::cull_exact_count(CS);
         lds_bytes = n_cull * sizeof(V4) + ((n_cull * sizeof(unsigned short) + 15) / 16) * 16;
     }
@@ -58,7 +60,7 @@ int run_unit(int op_arg, int count, const void *in, void *out, const SceneT *sce
     int rc = 0;
     hipError_t e;
     if ((e = hipMalloc(&d_in, in_b)) != hipSuccess || (e = hipMalloc(&d_out, out_b)) != hipSuccess ||
-        (e = hipMemcpy(d_in, in, in_b, hipMemcpyHostToDevice)) != hipSuccess) {
+        (e = hipMemcpy(d_in, in, in_b, hipMemcpyHostToDevice)) != hipSuccess || (sink && (e = hipMemset(d_out, 0, out_b)) != hipSuccess)) {
         rc = fail((int)e, "unit buffers: %s", hipGetErrorString(e));
     } else {
         (void)hipGetLastError();

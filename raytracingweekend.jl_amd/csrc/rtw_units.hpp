@@ -17,8 +17,13 @@ enum UnitOp {
     U_HIT_WORLD_MFMA_CULL = 14,   // hit_world_mfma with block culling (RTW_FLAG_GROUP_CULL on the matrix pipe), cull layout staged in LDS
     U_NEAR_ZERO = 15,        // near_zero(v) (src/vec.jl:20): squared length against the Float64 literal 1e-5
     U_EXACT_MATH = 16,       // t_sqrt / t_rcp against the compiler's IEEE sqrt / division on a RANGE of binary32 bit patterns (Float32 only)
-    U_NUM_OPS = 17
+    // pass-1 candidate sinks: the scans of ops 10, 11, 13, 14 with a CandSink -- per ray what pass 2 was handed instead of the hit (scenes of <= 512 spheres)
+    U_SINK_LDS = 17, U_SINK_CULL = 18, U_SINK_MFMA = 19, U_SINK_MFMA_CULL = 20,
+    U_NUM_OPS = 21
 };
+__host__ __device__ inline bool unit_is_sink(int op) { return op >= U_SINK_LDS && op <= U_SINK_MFMA_CULL; }
+#define RTW_SINK_SPHERES 512
+#define RTW_SINK_SLOTS 18
 
 __host__ __device__ inline int unit_in_slots(int op) {
     switch (op) {
@@ -33,6 +38,7 @@ __host__ __device__ inline int unit_in_slots(int op) {
         case U_NEAR_ZERO: return 3;     // v[3]
         case U_EXACT_MATH: return 2;    // first bit pattern, number of consecutive patterns
         case U_HIT_WORLD: case U_HIT_WORLD_LDS: case U_HIT_WORLD_CULL: case U_HIT_WORLD_MFMA: case U_HIT_WORLD_MFMA_CULL: return 8;     // o[3], d[3], tmin, tmax
+        case U_SINK_LDS: case U_SINK_CULL: case U_SINK_MFMA: case U_SINK_MFMA_CULL: return 8;                                         // (the same)
         case U_RAY_COLOR: return 9;     // state[2], o[3], d[3], depth
         case U_FX_SUM: return 8;        // 8 binary64 values
     }
@@ -51,6 +57,7 @@ __host__ __device__ inline int unit_out_slots(int op) {
         case U_NEAR_ZERO: return 2;     // near_zero(v), squared_length(v) (src/vec.jl:19-20)
         case U_EXACT_MATH: return 4;    // mismatches of t_sqrt, of t_rcp, first bad pattern of each (or -1)
         case U_HIT_WORLD: case U_HIT_WORLD_LDS: case U_HIT_WORLD_CULL: case U_HIT_WORLD_MFMA: case U_HIT_WORLD_MFMA_CULL: return 9;     // idx, t, p[3], n[3], front
+        case U_SINK_LDS: case U_SINK_CULL: case U_SINK_MFMA: case U_SINK_MFMA_CULL: return RTW_SINK_SLOTS;   // ok, mf_sc, cand bits[8], in-lane bits[8] (raw uint64)
         case U_RAY_COLOR: return 6;     // state[2], colour[3], segments
         case U_FX_SUM: return 2;        // sum, poisoned
     }
@@ -64,6 +71,25 @@ __device__ __forceinline__ void st3(double *p, V3<T> v) { p[0] = (double)v.x; p[
 __device__ __forceinline__ uint64_t as_u64(double d) { return (uint64_t)__double_as_longlong(d); }
 __device__ __forceinline__ double as_f64(uint64_t u) { return __longlong_as_double((long long)u); }
 
+// The sink of ops 17-20 (rtw_scan.hpp NoSink): rows of RTW_SINK_SLOTS 8-byte slots, one per ray of the wave, zeroed by the host.  Bit i & 63 of
+// slot 2 + (i >> 6) / 10 + (i >> 6): sphere i of the caller's list.  A row belongs to the lane's ray but any lane may record into it (hit_world_mfma:
+// the lane that runs a candidate's exact test is not its owner): global atomic ORs.
+struct CandSink {
+    double *rows;          // the wave's first row
+    unsigned n_live;       // rows of the wave (lanes beyond have no ray and no row)
+    unsigned self;         // this lane
+    static constexpr bool on() { return true; }
+    __device__ void ray(unsigned lane, bool ok, float sc) {
+        if (lane < n_live) { rows[lane * RTW_SINK_SLOTS] = ok ? 1.0 : 0.0; rows[lane * RTW_SINK_SLOTS + 1] = (double)sc; }
+    }
+    __device__ void bit(unsigned lane, int slot0, int i) {
+        if (lane < n_live && (unsigned)i < (unsigned)RTW_SINK_SPHERES)
+            atomicOr(reinterpret_cast<unsigned long long *>(rows + lane * RTW_SINK_SLOTS + slot0 + (i >> 6)), 1ull << (i & 63));
+    }
+    __device__ void cand(unsigned lane, int i) { bit(lane, 2, i); }
+    __device__ void inlane(unsigned lane, int i) { bit(lane, 10, i); }
+};
+
 template <typename T>
 __global__ void unit_kernel(int op, int count, const double *__restrict__ in, double *__restrict__ out,
                             DevScene<T> scene, CullScene<T> cull, Camera<T> cam) {
@@ -75,7 +101,9 @@ __global__ void unit_kernel(int op, int count, const double *__restrict__ in, do
     const bool live = gid < count;                          // no early return: the scan is wave-cooperative
     const double *x = in + (size_t)gid * unit_in_slots(op);
     double *y = out + (size_t)gid * unit_out_slots(op);
-    const bool coop = op == U_HIT_WORLD || op == U_RAY_COLOR || op == U_HIT_WORLD_LDS || op == U_HIT_WORLD_CULL || op == U_HIT_WORLD_MFMA || op == U_HIT_WORLD_MFMA_CULL;
+    const bool coop = op == U_HIT_WORLD || op == U_RAY_COLOR || op == U_HIT_WORLD_LDS || op == U_HIT_WORLD_CULL || op == U_HIT_WORLD_MFMA || op == U_HIT_WORLD_MFMA_CULL || unit_is_sink(op);
+    const int wave0 = gid - (int)(threadIdx.x & 63u);
+    const CandSink sink = {out + (size_t)wave0 * RTW_SINK_SLOTS, (unsigned)(count - wave0 < 64 ? count - wave0 : 64), threadIdx.x & 63u};   // (ops 17-20)
     if (!coop && !live) return;
     switch (op) {
         case U_HIT_SPHERE: {
@@ -233,6 +261,40 @@ __global__ void unit_kernel(int op, int count, const double *__restrict__ in, do
                 HitRec<T> rec;
                 make_hitrec<T>({g.x, g.y, g.z}, m0.x, o, d, t_hit, rec);
                 y[1] = (double)rec.t; st3(y + 2, rec.p); st3(y + 5, rec.n); y[8] = rec.front ? 1.0 : 0.0;
+            }
+        } break;
+        case U_SINK_LDS: case U_SINK_CULL: {
+            V4 *lds_geom = reinterpret_cast<V4 *>(u_smem);
+            unsigned short *lds_orig = reinterpret_cast<unsigned short *>(lds_geom + (op == U_SINK_CULL ? cull_exact_count(cull) : 0));
+            if (op == U_SINK_CULL) stage_cull_scene<T>(cull, lds_geom, lds_orig); else stage_scene<T>(scene, lds_geom);
+            __syncthreads();
+            V3<T> o = {0, 0, 0}, d = {0, 0, 1};
+            T tmn = 0, tmx = 0;
+            if (live) { o = ld3<T>(x); d = ld3<T>(x + 3); tmn = (T)x[6]; tmx = (T)x[7]; }
+            T t_hit;
+            if (op == U_SINK_CULL)
+                hit_world_cull<T, 64>(cull, (const V4 *)lds_geom, (const unsigned short *)lds_orig, o, d, tmn, tmx, t_hit, my_list, NoClock(), sink);
+            else
+                hit_world<T, 64>(scene, (const V4 *)lds_geom, o, d, tmn, tmx, t_hit, my_list, NoClock(), sink);
+        } break;
+        case U_SINK_MFMA: case U_SINK_MFMA_CULL: {
+            __shared__ __attribute__((aligned(8))) unsigned k_pairs[RTW_PAIR_CAP];
+            __shared__ unsigned long long k_keys[64];
+            __shared__ unsigned k_kidx[64];
+            V4 *lds_geom = reinterpret_cast<V4 *>(u_smem);
+            unsigned short *lds_orig = reinterpret_cast<unsigned short *>(lds_geom + (op == U_SINK_MFMA_CULL ? cull_exact_count(cull) : 0));
+            if (op == U_SINK_MFMA_CULL) stage_cull_scene<T>(cull, lds_geom, lds_orig); else stage_scene<T>(scene, lds_geom);
+            __syncthreads();
+            V3<T> o = {0, 0, 0}, d = {0, 0, 1};
+            if (live) { o = ld3<T>(x); d = ld3<T>(x + 3); }
+            const T tmn = (T)in[6];
+            T t_hit;
+            const WaveScratch ws = {k_pairs, k_keys, k_kidx};
+            if (op == U_SINK_MFMA_CULL) {
+                const MfmaCull mc = mfma_cull_of(cull);
+                hit_world_mfma<T>(scene, (const V4 *)lds_geom, o, d, live, tmn, t_hit, ws, threadIdx.x & 63u, NoClock(), &mc, (const unsigned short *)lds_orig, sink);
+            } else {
+                hit_world_mfma<T>(scene, (const V4 *)lds_geom, o, d, live, tmn, t_hit, ws, threadIdx.x & 63u, NoClock(), nullptr, NoOrig(), sink);
             }
         } break;
         case U_FX_SUM: {
