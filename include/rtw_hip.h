@@ -192,6 +192,24 @@ int rtw_render_device_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, con
 int rtw_render_device_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p,
                           void *d_out, void *hip_stream);
 
+/* Batched render: N views of ONE scene -- same size, spp, depth, flags -- in one kernel launch (turntables, animation frames,
+ * multi-view datasets).  View v is bit-identical to rtw_render_* with cams[v] and seed seeds[v] (seeds == NULL: p->seed for every
+ * view) in every mode.  `cams` is a HOST array of n_views cameras; `out` / `d_out` hold n_views consecutive frames of the layout above:
+ * pixel (i, j) of view v at ((v*width + j-1)*height + i-1)*3 (Julia's Array{RGB{T},3} of size (height, width, n_views)).  The host
+ * variant keeps the same per-device cache as rtw_render_f32 and does one D2H; the device variant is asynchronous like
+ * rtw_render_device_*.  rtw_stats() afterwards reports the batch: samples = N*W*H*spp, the summed segments, one kernel time.
+ * One device and whole frames only: shard_count != 1, RTW_FLAG_COMPACT_TILES, RTW_FLAG_RCCL_REDUCE, RTW_FLAG_RAY_POOL, n_devices > 1 or
+ * device_ids -> -2; n_views < 1 -> -2; a null cams / out -> -1; a batch whose jobs the queues cannot number -> -5 (all decided before any
+ * HIP call).  Additive to ABI 4: callers detect it by symbol lookup. */
+int rtw_render_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views,
+                         const uint64_t *seeds, const rtw_params *p, float *out);
+int rtw_render_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views,
+                         const uint64_t *seeds, const rtw_params *p, double *out);
+int rtw_render_batch_device_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views,
+                                const uint64_t *seeds, const rtw_params *p, void *d_out, void *hip_stream);
+int rtw_render_batch_device_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views,
+                                const uint64_t *seeds, const rtw_params *p, void *d_out, void *hip_stream);
+
 /* Counters/timings of the last render issued from this thread (waits for it to finish). */
 int rtw_stats(rtw_stats_t *out);
 

@@ -116,4 +116,52 @@ function render(scene::HittableList, cam::Camera{T}, image_width=400, n_samples=
     img
 end
 
+"""
+    render(scene, cams::AbstractVector{Camera{T}}, image_width=400, n_samples=1; depth=16, seed=1, n_chunks=0, device=-1, numerics=:reference, group_cull=false, scan_valu=false)
+
+Batched render (rtw_render_batch_f32/_f64): every camera of `cams` in ONE kernel launch on one device.  Returns an
+`Array{RGB{T},3}` of size (image_height, image_width, length(cams)); `img[:, :, v]` is bit-identical to
+`render(scene, cams[v], image_width, n_samples; seed=seeds[v])`.  `seed`: one integer for every view or a vector of `length(cams)`.
+(Not executed in this repository: there is no `julia` in its build image; tests/test_gpu_batch.py drives the same entry point.)
+"""
+function render(scene::HittableList, cams::AbstractVector{Camera{T}}, image_width=400, n_samples=1;
+                depth=16, seed=1, n_chunks=0, device=-1, numerics=:reference, group_cull=false, scan_valu=false) where T <: Union{Float32,Float64}
+    isempty(cams) && throw(ArgumentError("cams is empty"))
+    numerics in (:reference, :contract, :reference_fma2) || throw(ArgumentError("numerics must be :reference, :contract or :reference_fma2"))
+    nflags = numerics === :contract ? 32 : numerics === :reference_fma2 ? 128 : 0
+    nv = length(cams)
+    seeds = seed isa Integer ? fill(UInt64(seed), nv) : UInt64.(seed)
+    length(seeds) == nv || throw(ArgumentError("$(length(seeds)) seeds for $nv views"))
+    image_height = image_width ÷ (16//9)
+    n = length(scene)
+    cx = Vector{T}(undef, n); cy = similar(cx); cz = similar(cx); r = similar(cx)
+    ar = similar(cx); ag = similar(cx); ab = similar(cx); param = similar(cx)
+    kind = Vector{Int32}(undef, n)
+    for (i, h) in enumerate(scene)
+        h isa Sphere{T} || throw(ArgumentError("scene[$i] is $(typeof(h)); the HIP path takes Sphere{$T} only"))
+        cx[i], cy[i], cz[i] = h.center
+        r[i] = h.radius
+        kind[i] = matkind(h.mat)
+        ar[i], ag[i], ab[i] = albedo(h.mat)
+        param[i] = matparam(h.mat)
+    end
+    img = Array{RGB{T},3}(undef, image_height, image_width, nv)     # view v = the v-th consecutive Matrix{RGB{T}}
+    ccams = [CCamera(c) for c in cams]
+    rc = GC.@preserve cx cy cz r kind ar ag ab param img ccams seeds begin
+        params = Ref(CParams(image_width, image_height, n_samples, depth, seeds[1], n_chunks, 0, 1, device, 1,
+                             (group_cull ? 1 : 0) | (scan_valu ? 4 : 0) | nflags, 0, 0, Ptr{Int32}(C_NULL)))
+        cscene = Ref(CScene{T}(n, pointer(cx), pointer(cy), pointer(cz), pointer(r), pointer(kind),
+                               pointer(ar), pointer(ag), pointer(ab), pointer(param)))
+        if T === Float32
+            ccall((:rtw_render_batch_f32, LIB), Cint, (Ref{CScene{Float32}}, Ptr{CCamera{Float32}}, Int32, Ptr{UInt64}, Ref{CParams}, Ptr{Float32}),
+                  cscene, pointer(ccams), nv, pointer(seeds), params, pointer(reinterpret(Float32, vec(img))))
+        else
+            ccall((:rtw_render_batch_f64, LIB), Cint, (Ref{CScene{Float64}}, Ptr{CCamera{Float64}}, Int32, Ptr{UInt64}, Ref{CParams}, Ptr{Float64}),
+                  cscene, pointer(ccams), nv, pointer(seeds), params, pointer(reinterpret(Float64, vec(img))))
+        end
+    end
+    rc == 0 || error("librtw_hip: error $rc: $(last_error())")
+    img
+end
+
 end # module

@@ -12,6 +12,7 @@ SYMBOLS = [
     "rtw_abi_version", "rtw_device_count", "rtw_last_error", "rtw_render_f32", "rtw_render_f64",
     "rtw_scene_upload_f32", "rtw_scene_upload_f64", "rtw_scene_free", "rtw_render_device_f32",
     "rtw_render_device_f64", "rtw_stats", "rtw_stats_devices", "rtw_unit_f32", "rtw_unit_f64", "rtw_shutdown",
+    "rtw_render_batch_f32", "rtw_render_batch_f64", "rtw_render_batch_device_f32", "rtw_render_batch_device_f64",
 ]
 
 
@@ -76,6 +77,12 @@ def lib():
     L.rtw_render_device_f64.argtypes = [C.c_void_p, C.POINTER(CameraF64), C.POINTER(Params), C.c_void_p, C.c_void_p]
     L.rtw_render_f32.argtypes = [C.POINTER(SceneF32), C.POINTER(CameraF32), C.POINTER(Params), C.c_void_p]
     L.rtw_render_f64.argtypes = [C.POINTER(SceneF64), C.POINTER(CameraF64), C.POINTER(Params), C.c_void_p]
+    L.rtw_render_batch_f32.argtypes = [C.POINTER(SceneF32), C.POINTER(CameraF32), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(Params), C.c_void_p]
+    L.rtw_render_batch_f64.argtypes = [C.POINTER(SceneF64), C.POINTER(CameraF64), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(Params), C.c_void_p]
+    L.rtw_render_batch_device_f32.argtypes = [C.c_void_p, C.POINTER(CameraF32), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(Params),
+                                              C.c_void_p, C.c_void_p]
+    L.rtw_render_batch_device_f64.argtypes = [C.c_void_p, C.POINTER(CameraF64), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(Params),
+                                              C.c_void_p, C.c_void_p]
     L.rtw_stats.argtypes = [C.POINTER(Stats)]
     L.rtw_stats_devices.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
     L.rtw_unit_f32.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SceneF32), C.POINTER(CameraF32)]
@@ -116,6 +123,25 @@ def make_camera(cam, T):
         setattr(Cm, k, (ct * 3)(*[float(x) for x in np.asarray(getattr(cam, k), dtype=T)]))
     Cm.lens_radius = float(np.dtype(T).type(cam.lens_radius))
     return Cm
+
+
+def make_cameras(cams, T):
+    """sequence of Camera -> ctypes array of n camera structs (the ``cams`` of rtw_render_batch_*)"""
+    arr = ((CameraF64 if is_f64(T) else CameraF32) * len(cams))()
+    for k, cam in enumerate(cams):
+        arr[k] = make_camera(cam, T)
+    return arr
+
+
+def make_seeds(seed, n):
+    """int or sequence of n ints -> ctypes array of n uint64 seeds (the ``seeds`` of rtw_render_batch_*)"""
+    if isinstance(seed, (int, np.integer)):
+        seeds = [int(seed)] * n
+    else:
+        seeds = [int(s) for s in seed]
+        if len(seeds) != n:
+            raise ValueError(f"{len(seeds)} seeds for {n} views")
+    return (C.c_uint64 * n)(*seeds)
 
 
 FLAG_GROUP_CULL = 1      # include/rtw_hip.h RTW_FLAG_GROUP_CULL

@@ -142,6 +142,41 @@ long long local_tiles(const rtw_params *p) {
     return n_tiles > p->shard_index ? (n_tiles - p->shard_index + p->shard_count - 1) / p->shard_count : 0;
 }
 
+// Everything about a batched render that can be decided without a device (include/rtw_hip.h rtw_render_batch_f32): one device, whole
+// frames, the lane-loop kernel, and a job count the queue positions can hold for at least one job shape (the largest jobs, 16 pixels;
+// launch_render repeats the check for the shape it picks).
+int validate_batch(const void *cams, int32_t n_views, const rtw_params *p, const void *out) {
+    if (!p) return fail(-1, "null params");
+    if (!cams || !out) return fail(-1, "null argument");
+    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
+    int nch, cs;
+    if (int rc = validate_params(p, &nch, &cs)) return rc;
+    if (p->shard_count != 1) return fail(-2, "a batched render renders whole frames (shard_count = %d)", p->shard_count);
+    if (p->flags & RTW_FLAG_COMPACT_TILES) return fail(-2, "a batched render writes whole frames (RTW_FLAG_COMPACT_TILES is a per-shard layout)");
+    if (p->flags & RTW_FLAG_RCCL_REDUCE) return fail(-2, "a batched render runs on one device (RTW_FLAG_RCCL_REDUCE)");
+    if (p->n_devices > 1 || p->n_devices < 0 || p->device_ids)
+        return fail(-2, "a batched render runs on one device (n_devices = %d%s)", p->n_devices, p->device_ids ? ", device_ids given" : "");
+    if (p->flags & RTW_FLAG_RAY_POOL) return fail(-2, "a batched render runs the lane-loop kernel (RTW_FLAG_RAY_POOL)");
+    const long long tiles_i = (p->height + 7) / 8, tiles_j = (p->width + 7) / 8;
+    const double cols = (double)tiles_j * (double)n_views;
+    if (cols * (double)tiles_i * 4.0 >= (double)(1ll << 30) || (cols + 7.0) / 8.0 * (double)tiles_i * 4.0 >= (double)(1ll << 28))
+        return fail(-5, "batch too large for one call: %d views of %lld x %lld tiles", n_views, tiles_i, tiles_j);
+    return 0;
+}
+
+template <typename CamT>
+int render_device_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, void *stream_v) {
+    if (int rc = validate_batch(cams, n_views, p, d_out)) return rc;
+    if (!scene) return fail(-1, "null scene handle");
+    DeviceGuard guard;
+    RenderRec *rec = nullptr;
+    CtxPtr ctx;
+    release_last();
+    int rc = launch_batch_t(scene, cams, n_views, seeds, p, d_out, (hipStream_t)stream_v, &rec, &ctx);
+    if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); }       // (also on a late error: released by the next call)
+    return rc;
+}
+
 template <typename CamT>
 int render_device(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, void *d_out, void *stream_v) {
     DeviceGuard guard;
@@ -197,6 +232,18 @@ int rtw_render_f32(const rtw_scene_f32 *s, const rtw_camera_f32 *c, const rtw_pa
 }
 int rtw_render_f64(const rtw_scene_f64 *s, const rtw_camera_f64 *c, const rtw_params *p, double *out) {
     return render_host_f64(s, c, p, out);
+}
+int rtw_render_batch_f32(const rtw_scene_f32 *s, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, float *out) {
+    return render_host_batch_f32(s, cams, n_views, seeds, p, out);
+}
+int rtw_render_batch_f64(const rtw_scene_f64 *s, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, double *out) {
+    return render_host_batch_f64(s, cams, n_views, seeds, p, out);
+}
+int rtw_render_batch_device_f32(rtw_scene_handle s, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, void *stream) {
+    return render_device_batch(s, cams, n_views, seeds, p, d_out, stream);
+}
+int rtw_render_batch_device_f64(rtw_scene_handle s, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, void *stream) {
+    return render_device_batch(s, cams, n_views, seeds, p, d_out, stream);
 }
 
 int rtw_stats(rtw_stats_t *out) {

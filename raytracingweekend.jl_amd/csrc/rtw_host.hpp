@@ -107,9 +107,13 @@ struct RenderRec {
     bool owned = false;                  // referenced by some thread's "last render"
     bool fresh = true;                   // the device counters have never been cleared as a whole
     int n_spheres = 0, n_chunks = 0, grid = 0, block = 256;
+    void *d_views = nullptr, *h_views = nullptr;  // batched renders: the views' cameras + seeds (device copy; pinned staging for its H2D)
+    size_t views_cap = 0;
     ~RenderRec() {
         if (ctr) HIP_IGNORE(hipFree(ctr));
         if (h_ctr) HIP_IGNORE(hipHostFree(h_ctr));
+        if (d_views) HIP_IGNORE(hipFree(d_views));
+        if (h_views) HIP_IGNORE(hipHostFree(h_views));
         if (ev2) HIP_IGNORE(hipEventDestroy(ev2));
         if (ev0) HIP_IGNORE(hipEventDestroy(ev0));
         if (ev1) HIP_IGNORE(hipEventDestroy(ev1));
@@ -191,10 +195,19 @@ int launch_render_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const r
 inline int launch_render_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_render_f32(s, c, p, d, st, r, x); }
 inline int launch_render_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_render_f64(s, c, p, d, st, r, x); }
 int resolve_rec(RenderRec *r, rtw_stats_t *agg);            // wait for a record's kernel and add its counters to `agg`
+// ... a batch of n_views >= 1 views (validate_batch first): `cams` / `seeds` (null: p->seed) hold n_views entries, `d_out` n_views frames
+int launch_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
+int launch_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
+inline int launch_batch_t(rtw_scene_handle s, const rtw_camera_f32 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_batch_f32(s, c, n, sd, p, d, st, r, x); }
+inline int launch_batch_t(rtw_scene_handle s, const rtw_camera_f64 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_batch_f64(s, c, n, sd, p, d, st, r, x); }
+// rtw_abi.hip: the checks of a batched render that need no device (include/rtw_hip.h rtw_render_batch_f32)
+int validate_batch(const void *cams, int32_t n_views, const rtw_params *p, const void *out);
 
 // rtw_render_host.hip
 int render_host_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, float *out);
 int render_host_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, double *out);
+int render_host_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, float *out);
+int render_host_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, double *out);
 
 // rtw_multi.hip
 int ensure_peer(const CtxPtr &ctx, int dev, int root, bool *direct);

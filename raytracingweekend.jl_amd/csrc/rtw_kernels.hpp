@@ -85,6 +85,17 @@ struct JobSlot {
     __device__ __forceinline__ const unsigned long long *acc(unsigned px) const { return reinterpret_cast<const unsigned long long *>(this + 1) + 8u * px; }
 };
 static_assert(sizeof(JobSlot) == 128, "JobSlot header is 128 bytes (16-byte aligned accumulators follow)");
+// Batched render (rtw_render_batch_*; the BATCH instances of trace_kernel): N views of one scene, same size / spp / depth, one launch.
+// View v owns the tile columns v * tiles_jv .. v * tiles_jv + tiles_jv - 1 of a frame N views wide (KParams::tiles_j = N * tiles_jv):
+// the job queues, static first claims and guided claims run unchanged over all of them.  open_job splits the column into (view, column)
+// and records the view in the slot header (JobSlot::pad); the view then picks the item's RNG seed, camera and output frame.
+template <typename T> struct BatchArgs {
+    const Camera<T> *cams;              // device array of N cameras (read per lane at the start of a sample: a hit in the L2)
+    const unsigned long long *seeds;    // device array of N render seeds (read per wave batch)
+    unsigned tiles_jv;                  // tile columns of one view
+    unsigned div_tjv_m, div_tjv_s;      // exact division by tiles_jv (make_udiv)
+    unsigned long long view_elems;      // W * H * 3: elements of one output frame
+};
 struct JobCache { unsigned long long jc; unsigned jc_lock; unsigned queue_off; unsigned last_g; unsigned static_used; };       // see claim_job
 template <typename T> struct WgShared {
     unsigned char slots[RTW_SLOT_BYTES];      // n_slots x (128-byte JobSlot + 64 bytes per job pixel)
@@ -322,9 +333,12 @@ __device__ __forceinline__ int claim_job(const KParams &P, DevCounters *ctr, Job
 // image (or every queue is exhausted), zero its accumulators and fill in the block's header.
 // S->job: the job's queue position, RTW_JOB_EOF (every queue is exhausted for good) or -- WITH_RETRY only -- RTW_JOB_RETRY (claim_job's "try again";
 // without WITH_RETRY the claim is repeated here until it is decided).
-template <bool WITH_RETRY = false>
-__device__ RTW_RARE_ATTR void open_job(const KParams &P, JobSlot *S, unsigned lane, DevCounters *ctr, JobCache *jcache) {
+// BATCH: the tile column tj of the queues is view v's column tj - v * tiles_jv (BatchArgs); v goes to S->pad.
+template <bool WITH_RETRY = false, bool BATCH = false>
+__device__ RTW_RARE_ATTR void open_job(const KParams &P, JobSlot *S, unsigned lane, DevCounters *ctr, JobCache *jcache,
+                                       unsigned tiles_jv = 0u, unsigned div_tjv_m = 0u, unsigned div_tjv_s = 0u) {
     unsigned g = RTW_JOB_EOF, valid = 0, k = 0;
+    [[maybe_unused]] unsigned view = 0;
     int i_base = 0, j_base = 0;
     const unsigned rs = P.rows_shift, cs = P.job_shift - rs, sub_shift = 6u - P.job_shift, bps_shift = 3u - rs;
     const unsigned xcd = xcd_id();
@@ -341,6 +355,7 @@ __device__ RTW_RARE_ATTR void open_job(const KParams &P, JobSlot *S, unsigned la
             const unsigned tjq = udiv_magic(qt, P.div_tiles_m, P.div_tiles_s);
             ti = qt - tjq * (unsigned)P.tiles_i; tj = xq + 8u * tjq;
             k = tj * (unsigned)P.tiles_i + ti;
+            if constexpr (BATCH) { view = udiv_magic(tj, div_tjv_m, div_tjv_s); tj -= view * tiles_jv; }
         } else {
             k = xq + 8u * qt;
             const unsigned t = k * (unsigned)P.shard_count + (unsigned)P.shard_index;
@@ -363,6 +378,7 @@ __device__ RTW_RARE_ATTR void open_job(const KParams &P, JobSlot *S, unsigned la
         if (lane == 0) {
             S->remaining = (int)((unsigned)__popc(valid) * (unsigned)P.n_chunks);
             S->valid = valid; S->i_base = i_base; S->j_base = j_base; S->k_tile = k;
+            if constexpr (BATCH) S->pad = view;
         }
     }
     if (lane == 0) S->job = g;
@@ -370,9 +386,10 @@ __device__ RTW_RARE_ATTR void open_job(const KParams &P, JobSlot *S, unsigned la
 
 // NUMK >= 0: the numerics mode is fixed at compile time (the launcher picks such an instance for the default mode of the headline
 // variants: the other modes' code and their scalar state are then not in the kernel at all); NUMK < 0: the mode of the arguments.
-template <typename T, bool PROFILE, bool LDS_SCENE, bool CULL, bool MFMA = false, int NUMK = -1>
+// BATCH: a batched render (BatchArgs; `cam_arg` and P.seed are unused, `out` holds N frames); otherwise `batch` is unused.
+template <typename T, bool PROFILE, bool LDS_SCENE, bool CULL, bool MFMA = false, int NUMK = -1, bool BATCH = false>
 __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void trace_kernel(KParams P_arg, Camera<T> cam_arg, DevScene<T> scene,
-                                                   CullScene<T> cull, T *__restrict__ out, DevCounters *ctr) {
+                                                   CullScene<T> cull, T *__restrict__ out, DevCounters *ctr, BatchArgs<T> batch) {
     using V4 = typename Vec4<T>::type;
     if constexpr (NUMK >= 0) { scene.numerics = NUMK; cull.numerics = NUMK; }
     const unsigned lane = lane_id();
@@ -523,7 +540,8 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                 const int L = __builtin_ctzll(fin);
                 fin &= fin - 1ull;
                 JobSlot *S = sh->slot(uniform((unsigned)__shfl((int)((ref_depth & RTW_REF_MASK) >> 4), L)), P.slot_stride);
-                store_job<T>(P, S, lane, out);
+                if constexpr (BATCH) store_job<T>(P, S, lane, out + (size_t)uniform(S->pad) * batch.view_elems);
+                else store_job<T>(P, S, lane, out);
                 clk.count(21, 1u);                                                                        // jobs stored
                 __hip_atomic_store(&S->ready_seq, RTW_SLOT_FREE, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
@@ -570,7 +588,8 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                                                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) ? 1u : 0u;
                         }
                         if (uniform(won)) {
-                            open_job<RTW_OPEN_RETRY != 0>(P, S, lane, ctr, &sh->jobs);
+                            if constexpr (BATCH) open_job<RTW_OPEN_RETRY != 0, true>(P, S, lane, ctr, &sh->jobs, batch.tiles_jv, batch.div_tjv_m, batch.div_tjv_s);
+                            else open_job<RTW_OPEN_RETRY != 0>(P, S, lane, ctr, &sh->jobs);
                             const unsigned opened = uniform(S->job);
                             if (opened >= RTW_JOB_RETRY) {
                                 if (opened == RTW_JOB_EOF && lane == 0) __hip_atomic_store(&sh->eof, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -604,7 +623,8 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                         const unsigned rsh = P.rows_shift;
                         const int i0 = S->i_base + (int)(px & ((1u << rsh) - 1u)), j0 = S->j_base + (int)(px >> rsh);
                         Rng r0;
-                        rng_stream(P.seed, (unsigned long long)j0 * (unsigned)P.height + (unsigned)i0, chunk, r0);
+                        if constexpr (BATCH) rng_stream(batch.seeds[uniform(S->pad)], (unsigned long long)j0 * (unsigned)P.height + (unsigned)i0, chunk, r0);
+                        else rng_stream(P.seed, (unsigned long long)j0 * (unsigned)P.height + (unsigned)i0, chunk, r0);
                         __builtin_amdgcn_wave_barrier();                      // (the previous batch's states have all been read)
                         pool_rng[lane] = ulonglong2{r0.x, r0.y};
                         pool_valid = __ballot((int)chunk < P.n_chunks && ((S->valid >> px) & 1u));
@@ -628,7 +648,8 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                             const unsigned rsh = P.rows_shift;
                             const int i0 = S->i_base + (int)(px & ((1u << rsh) - 1u)), j0 = S->j_base + (int)(px >> rsh);
                             const unsigned long long pix = (unsigned long long)j0 * (unsigned)P.height + (unsigned)i0;
-                            rng_stream(P.seed, pix, chunk, rng);
+                            if constexpr (BATCH) rng_stream(batch.seeds[uniform(S->pad)], pix, chunk, rng);
+                            else rng_stream(P.seed, pix, chunk, rng);
                         }
                         const int s0 = (int)chunk * P.chunk_spp;
                         samples_left = min(P.spp, s0 + P.chunk_spp) - s0;
@@ -737,8 +758,14 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
         }
         if (new_sample) {
             __asm__ volatile("" ::: "memory");                    // (keeps the camera loads inside this branch)
-            const Camera<T> cam = sh->cam;
-            camera_ray_raw<T>(cam, su, sv, rp.x, rp.y, ro, vec);   // src/camera.jl:43-48
+            if constexpr (BATCH) {
+                // the camera of this lane's view (lanes of one wave may hold items of different views)
+                const Camera<T> cam = batch.cams[sh->slot((ref_depth & RTW_REF_MASK) >> 4, P.slot_stride)->pad];
+                camera_ray_raw<T>(cam, su, sv, rp.x, rp.y, ro, vec);
+            } else {
+                const Camera<T> cam = sh->cam;
+                camera_ray_raw<T>(cam, su, sv, rp.x, rp.y, ro, vec);   // src/camera.jl:43-48
+            }
             todo = PATH_NORM;
             thr_r = thr_g = thr_b = 1.0;
             ref_depth = (ref_depth & RTW_REF_MASK) | ((unsigned)P.max_depth << RTW_REF_BITS);

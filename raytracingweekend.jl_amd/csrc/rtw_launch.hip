@@ -19,12 +19,17 @@ void make_udiv(unsigned d, unsigned *m, unsigned *s) {
 }
 
 // Enqueue one render (this shard's tiles) on `stream`; `rec` receives the counters and the kernel's events.
+// n_views >= 1: a batch (validate_batch has accepted it): `cam` points to n_views cameras, `seeds` to n_views seeds (null: p->seed for
+// every view), `d_out` to n_views frames.  The views' tile columns are laid side by side (rtw::BatchArgs), so the job shape, the grid and
+// the queues see the batch's total tile count.  n_views == 0: one render of `cam`.
 template <typename T, typename CamT>
-int launch_render(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out) {
+int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
+                  RenderRec **rec_out, CtxPtr *ctx_out) {
     if (!scene || !cam || !d_out) return fail(-1, "null argument");
     if (scene->is_f64 != (sizeof(T) == 8)) return fail(-4, "scene handle precision does not match the call");
     int nch, cs;
     if (int rc = validate_params(p, &nch, &cs)) return rc;
+    const bool batch = n_views > 0;
     if (p->device >= 0 && p->device != scene->device)
         return fail(-4, "params.device %d != scene device %d", p->device, scene->device);
     CtxPtr ctx;
@@ -38,7 +43,15 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, 
     K.seed = p->seed; K.n_chunks = nch; K.chunk_spp = cs;
     K.shard_index = p->shard_index; K.shard_count = p->shard_count;
     K.tiles_i = (p->height + 7) / 8; K.tiles_j = (p->width + 7) / 8;
-    const long long n_local = local_tiles(p);
+    rtw::BatchArgs<T> B;
+    memset(&B, 0, sizeof B);
+    if (batch) {
+        B.tiles_jv = (unsigned)K.tiles_j;
+        make_udiv(B.tiles_jv, &B.div_tjv_m, &B.div_tjv_s);
+        B.view_elems = (unsigned long long)p->width * (unsigned long long)p->height * 3ull;
+        K.tiles_j *= n_views;                   // (validate_batch: N x tiles_j fits the queue positions)
+    }
+    const long long n_local = batch ? (long long)K.tiles_i * K.tiles_j : local_tiles(p);
     K.gamma = p->gamma;
     K.out_layout = (p->flags & RTW_FLAG_COMPACT_TILES) ? 1 : 0;
     make_udiv((unsigned)K.tiles_i, &K.div_tiles_m, &K.div_tiles_s);
@@ -73,7 +86,7 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, 
                                    : (size_t)rtw::scene_geom_alloc(scene->n, scene->n_pad) * sizeof(V4);
     const bool lds_scene = geom_bytes <= RTW_LDS_SCENE_MAX_BYTES;
     const size_t lds_bytes = list_bytes + shared_bytes + (mfma ? rtw::mfma_cell_bytes<T>() : 0) + (lds_scene ? geom_bytes : 0);
-    typedef void (*kern_t)(rtw::KParams, rtw::Camera<T>, rtw::DevScene<T>, rtw::CullScene<T>, T *, rtw::DevCounters *);
+    typedef void (*kern_t)(rtw::KParams, rtw::Camera<T>, rtw::DevScene<T>, rtw::CullScene<T>, T *, rtw::DevCounters *, rtw::BatchArgs<T>);
     kern_t kern;
     if (cull && mfma && phase_profile) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, true, true, true, true> : (kern_t)rtw::trace_kernel<T, false, false, true, true>;
     else if (cull && mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true, true> : (kern_t)rtw::trace_kernel<T, false, false, true, true>;
@@ -86,6 +99,15 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, 
     // the default numerics mode of the headline variants (scene in LDS, matrix pipe): an instance with the mode fixed at compile time
     if (S.numerics == rtw::NUM_REFERENCE && lds_scene && mfma && !phase_profile)
         kern = cull ? (kern_t)rtw::trace_kernel<T, false, true, true, true, rtw::NUM_REFERENCE> : (kern_t)rtw::trace_kernel<T, false, true, false, true, rtw::NUM_REFERENCE>;
+    // a batch: the same choice among the BATCH instances (no phase profile)
+    if (batch) {
+        if (cull && mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true, true, -1, true> : (kern_t)rtw::trace_kernel<T, false, false, true, true, -1, true>;
+        else if (cull) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true, false, -1, true> : (kern_t)rtw::trace_kernel<T, false, false, true, false, -1, true>;
+        else if (mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false, true, -1, true> : (kern_t)rtw::trace_kernel<T, false, false, false, true, -1, true>;
+        else kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false, false, -1, true> : (kern_t)rtw::trace_kernel<T, false, false, false, false, -1, true>;
+        if (S.numerics == rtw::NUM_REFERENCE && lds_scene && mfma)
+            kern = cull ? (kern_t)rtw::trace_kernel<T, false, true, true, true, rtw::NUM_REFERENCE, true> : (kern_t)rtw::trace_kernel<T, false, true, false, true, rtw::NUM_REFERENCE, true>;
+    }
     // The ray-pool kernel (rtw_pool.hpp; opt-in: RTW_FLAG_RAY_POOL, or RTW_POOL=1 in the environment for A/B runs) exists in `make POOL=1`
     // builds only: Float32 plain scans on the matrix pipe, when the pool, the rings and the scene copy fit the 160 KB of LDS of a CU (one
     // workgroup of RTW_POOL_W waves per CU); everything else runs the lane-loop kernel above.  The default library refuses the flag.
@@ -99,7 +121,7 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, 
     pool_kern_t pool_kern = nullptr;
     if constexpr (sizeof(T) == 4) {
         pool_lds = rtw::pool_fixed_lds_bytes<T, RTW_POOL_W, RTW_POOL_R>() + rtw::pool_scene_lds_bytes<T>(scene->n, scene->n_pad);
-        pool = mfma && !cull && (env_pool || (p->flags & RTW_FLAG_RAY_POOL)) && pool_lds <= ctx->lds_per_cu &&
+        pool = !batch && mfma && !cull && (env_pool || (p->flags & RTW_FLAG_RAY_POOL)) && pool_lds <= ctx->lds_per_cu &&
                cs <= RTW_POOL_MAX_CHUNK_SPP;
         pool_kern = phase_profile ? (pool_kern_t)rtw::trace_pool_kernel<T, RTW_POOL_W, RTW_POOL_R, true> : (pool_kern_t)rtw::trace_pool_kernel<T, RTW_POOL_W, RTW_POOL_R, false>;
     }
@@ -187,6 +209,33 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, 
     HIP_TRY(hipMemsetAsync(rec->ctr, 0, rec->fresh ? sizeof(rtw::DevCounters) : rec->ctr_bytes, stream));
     rec->fresh = false;
     if (drain_profile) HIP_TRY(hipMemsetAsync(&rec->ctr->t_first, 0xff, sizeof(unsigned long long), stream));
+    if (batch) {
+        // the views' cameras and seeds: into the record's pinned buffer, then ONE asynchronous H2D on the render's stream (the record is
+        // handed out again only after ev2, behind this copy, so the pinned buffer is free whenever a render holds the record)
+        const size_t cam_bytes = (size_t)n_views * sizeof(rtw::Camera<T>), bytes = cam_bytes + (size_t)n_views * sizeof(unsigned long long);
+        if (rec->views_cap < bytes) {
+            if (rec->d_views) { HIP_IGNORE(hipFree(rec->d_views)); rec->d_views = nullptr; }
+            if (rec->h_views) { HIP_IGNORE(hipHostFree(rec->h_views)); rec->h_views = nullptr; }
+            rec->views_cap = 0;
+            HIP_TRY(hipMalloc(&rec->d_views, bytes));
+            HIP_TRY(hipHostMalloc(&rec->h_views, bytes, hipHostMallocDefault));
+            rec->views_cap = bytes;
+        }
+        rtw::Camera<T> *hc = reinterpret_cast<rtw::Camera<T> *>(rec->h_views);
+        unsigned long long *hs = reinterpret_cast<unsigned long long *>(static_cast<char *>(rec->h_views) + cam_bytes);
+        for (int v = 0; v < n_views; ++v) {
+            for (int k = 0; k < 3; ++k) {
+                hc[v].origin[k] = cam[v].origin[k]; hc[v].llc[k] = cam[v].lower_left_corner[k];
+                hc[v].horizontal[k] = cam[v].horizontal[k]; hc[v].vertical[k] = cam[v].vertical[k];
+                hc[v].u[k] = cam[v].u[k]; hc[v].v[k] = cam[v].v[k]; hc[v].w[k] = cam[v].w[k];
+            }
+            hc[v].lens_radius = cam[v].lens_radius;
+            hs[v] = seeds ? seeds[v] : p->seed;
+        }
+        HIP_TRY(hipMemcpyAsync(rec->d_views, rec->h_views, bytes, hipMemcpyHostToDevice, stream));
+        B.cams = reinterpret_cast<const rtw::Camera<T> *>(rec->d_views);
+        B.seeds = reinterpret_cast<const unsigned long long *>(static_cast<const char *>(rec->d_views) + cam_bytes);
+    }
     // pixels of other shards read 0 in the full-frame layout (the sum over the shards is the image)
     if (K.out_layout == 0 && p->shard_count > 1)
         HIP_TRY(hipMemsetAsync(d_out, 0, (size_t)p->width * p->height * 3 * sizeof(T), stream));
@@ -197,7 +246,7 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, 
         if (pool) hipLaunchKernelGGL(pool_kern, dim3((unsigned)grid), dim3((unsigned)block_threads), pool_lds, stream, K, C, S, (T *)d_out, rec->ctr);
         else
 #endif
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds_bytes, stream, K, C, S, CS, (T *)d_out, rec->ctr);
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds_bytes, stream, K, C, S, CS, (T *)d_out, rec->ctr, B);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(rec->ev1, stream));
@@ -283,10 +332,18 @@ int resolve_rec(RenderRec *r, rtw_stats_t *agg) {
 }
 
 int launch_render_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out) {
-    return launch_render<float>(scene, cam, p, d_out, stream, rec_out, ctx_out);
+    return launch_render<float>(scene, cam, 0, nullptr, p, d_out, stream, rec_out, ctx_out);
 }
 int launch_render_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out) {
-    return launch_render<double>(scene, cam, p, d_out, stream, rec_out, ctx_out);
+    return launch_render<double>(scene, cam, 0, nullptr, p, d_out, stream, rec_out, ctx_out);
+}
+int launch_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
+                     RenderRec **rec_out, CtxPtr *ctx_out) {
+    return launch_render<float>(scene, cams, n_views, seeds, p, d_out, stream, rec_out, ctx_out);
+}
+int launch_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
+                     RenderRec **rec_out, CtxPtr *ctx_out) {
+    return launch_render<double>(scene, cams, n_views, seeds, p, d_out, stream, rec_out, ctx_out);
 }
 
 }  // namespace rtwh

@@ -292,7 +292,43 @@ int render_host(const SceneT *scene, const CamT *cam, const rtw_params *p, T *ou
     return rc;
 }
 
+// N views of one scene (rtw_render_batch_f32/_f64): the one-device path above with a device image of N frames, ONE launch, ONE D2H.
+template <typename T, typename SceneT, typename CamT>
+int render_host_batch(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, T *out) {
+    if (int rc = validate_batch(cams, n_views, p, out)) return rc;
+    if (!scene) return fail(-1, "null argument");
+    DeviceGuard guard;
+    release_last();
+    if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
+    std::vector<unsigned char> key;
+    scene_key_of(scene, sizeof(T) == 8, key);
+    HostLease L;
+    if (int rc = acquire_host(p->device, key, &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_scene<T>(hc, scene, key)) return rc;
+    rtw_params q = *p;
+    q.device = hc->device; q.n_devices = 0; q.device_ids = nullptr;
+    const size_t elems = (size_t)n_views * (size_t)q.width * (size_t)q.height * 3;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, elems * sizeof(T))) return rc;
+    RenderRec *rec = nullptr;
+    CtxPtr rctx;
+    int rc = launch_batch_t(hc->scene, cams, n_views, seeds, &q, hc->d_img, hc->stream, &rec, &rctx);
+    if (!rc) rc = copy_out(hc, hc->d_img, out, elems * sizeof(T));
+    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    if (!rc) rc = resolve_rec(rec, &g_last.agg);
+    if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
+    if (rec) release_rec(rctx, rec, rc == 0);
+    g_last.resolved = rc == 0;
+    return rc;
+}
+
 int render_host_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, float *out) { return render_host<float>(scene, cam, p, out); }
 int render_host_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, double *out) { return render_host<double>(scene, cam, p, out); }
+int render_host_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, float *out) {
+    return render_host_batch<float>(scene, cams, n_views, seeds, p, out);
+}
+int render_host_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, double *out) {
+    return render_host_batch<double>(scene, cams, n_views, seeds, p, out);
+}
 
 }  // namespace rtwh

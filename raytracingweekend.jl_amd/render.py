@@ -64,6 +64,50 @@ def render(scene, cam, image_width=400, n_samples=1, *, depth=16, seed=1, n_chun
     return _as_image(out, height, int(image_width))
 
 
+def _batch_cameras(cams):
+    """-> (list of Camera, elem_type): a non-empty sequence of cameras of one element type"""
+    cams = list(cams)
+    if not cams:
+        raise ValueError("cams is empty: a batch needs at least one camera")
+    for c in cams:
+        if not isinstance(c, Camera):
+            raise TypeError("every entry of cams must be a Camera")
+    T = cams[0].elem_type
+    if any(np.dtype(c.elem_type) != np.dtype(T) for c in cams):
+        raise TypeError("the cameras of a batch must share one elem_type")
+    return cams, T
+
+
+def render_batch(scene, cams, image_width=400, n_samples=1, *, depth=16, seed=1, n_chunks=0, device=-1, gamma=True,
+                 group_cull=False, scan_valu=False, numerics=None):
+    """Render ``scene`` through each camera of ``cams`` in ONE kernel launch (rtw_render_batch_f32/_f64); returns
+    ``img[v, i, j, :]``.  View ``v`` is bit-identical to ``render(scene, cams[v], ..., seed=seeds[v])``.  ``seed``: one int for every
+    view or a sequence of ``len(cams)`` ints.  Same size, spp, depth and mode for every view; one device."""
+    cams, T = _batch_cameras(cams)
+    n = len(cams)
+    seeds = _capi.make_seeds(seed, n)
+    L = _capi.lib()
+    height = image_height(image_width)
+    if int(image_width) <= 0 or height <= 0:
+        raise ValueError(f"image_width={image_width} gives an empty {height} x {image_width} image")
+    if int(n_samples) <= 0:
+        raise ValueError("n_samples must be >= 1")
+    flat = flatten_scene(scene, T)
+    S, keep = _capi.make_scene(flat, T)
+    Cm = _capi.make_cameras(cams, T)
+    P = _capi.make_params(image_width, height, n_samples, depth, seeds[0], n_chunks, 0, 1, device, 1 if gamma else 0,
+                          (_capi.FLAG_GROUP_CULL if group_cull else 0) | (_capi.FLAG_SCAN_VALU if scan_valu else 0), numerics=numerics)
+    out = np.empty(n * height * int(image_width) * 3, dtype=T)
+    fn = L.rtw_render_batch_f64 if _capi.is_f64(T) else L.rtw_render_batch_f32
+    _capi.check(fn(C.byref(S), Cm, n, seeds, C.byref(P), out.ctypes.data_as(C.c_void_p)))
+    st = _capi.Stats()
+    _capi.check(L.rtw_stats(C.byref(st)))
+    _tls.stats = {k: getattr(st, k) for k, _ in st._fields_}
+    _tls.stats["per_device"] = _stats_devices(L)
+    del keep
+    return out.reshape(n, int(image_width), height, 3).transpose(0, 2, 1, 3)
+
+
 def _stats_devices(L, cap=64):
     """[(HIP ordinal, kernel ms)] of the shards of the calling thread's last render (rtw_stats_devices)"""
     n = C.c_int32(0)
@@ -114,6 +158,27 @@ class DeviceRenderer:
         fn = self.L.rtw_render_device_f64 if _capi.is_f64(self.T) else self.L.rtw_render_device_f32
         _capi.check(fn(self.handle, C.byref(self.cam), C.byref(P), C.c_void_p(int(d_out_ptr)),
                        C.c_void_p(int(stream))))
+        return height
+
+    def render_batch_into(self, d_out_ptr, cams, image_width, n_samples, *, seeds=None, n_elems=None, stream=0, depth=16, seed=1,
+                          n_chunks=0, gamma=True, group_cull=False, scan_valu=False, job_pixels=0, numerics=None):
+        """Enqueue one batched render (rtw_render_batch_device_f32/_f64) of ``cams`` into device memory at ``d_out_ptr``:
+        len(cams) consecutive frames of H*W*3 elements.  ``seeds``: a sequence of len(cams) ints (None: ``seed`` for every view).
+        ``n_elems``: the buffer's length in elements; checked when given."""
+        cams, T = _batch_cameras(cams)
+        if np.dtype(T) != np.dtype(self.T):
+            raise TypeError("the cameras' elem_type differs from the scene's")
+        n = len(cams)
+        height = image_height(image_width)
+        if n_elems is not None and int(n_elems) < n * height * int(image_width) * 3:
+            raise ValueError(f"output buffer holds {n_elems} elements, this batch writes {n * height * int(image_width) * 3}")
+        sd = _capi.make_seeds(seed if seeds is None else seeds, n)
+        Cm = _capi.make_cameras(cams, T)
+        flags = (_capi.FLAG_GROUP_CULL if group_cull else 0) | (_capi.FLAG_SCAN_VALU if scan_valu else 0)
+        P = _capi.make_params(image_width, height, n_samples, depth, seed, n_chunks, 0, 1, -1, 1 if gamma else 0, flags,
+                              job_pixels=job_pixels, numerics=numerics)
+        fn = self.L.rtw_render_batch_device_f64 if _capi.is_f64(T) else self.L.rtw_render_batch_device_f32
+        _capi.check(fn(self.handle, Cm, n, sd, C.byref(P), C.c_void_p(int(d_out_ptr)), C.c_void_p(int(stream))))
         return height
 
     def stats(self):
