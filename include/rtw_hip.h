@@ -210,6 +210,79 @@ int rtw_render_batch_device_f32(rtw_scene_handle scene, const rtw_camera_f32 *ca
 int rtw_render_batch_device_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views,
                                 const uint64_t *seeds, const rtw_params *p, void *d_out, void *hip_stream);
 
+/* Progressive render: a render added up pass by pass in an EXACT accumulator -- a picture that sharpens while it is watched, a render
+ * that stops at a time budget, survives a restart (export / import) or has its samples split over streams, devices or processes.
+ *
+ * The contract: samples are grouped in chunks whose random streams depend on (seed, pixel, chunk) only, and every sample is added as a
+ * signed 64.64 fixed-point integer, so ANY partition of a render's chunks into passes -- in any order, in any mix of RTW_FLAG_GROUP_CULL /
+ * RTW_FLAG_SCAN_VALU / job_pixels, on one accumulator or merged from several -- resolves to the image of the single rtw_render_* call,
+ * bit for bit.  Every prefix is itself a render: after the chunks [0, C) of a render (spp = S, chunk size s) the image equals rtw_render_*
+ * with spp = min(S, C*s), n_chunks = C.
+ *
+ * The accumulator: width*height pixels x 8 uint64_t in device memory, pixel (i, j) (1-based row, column) at word ((j-1)*height + (i-1))*8:
+ *     r_lo, r_hi, g_lo, g_hi, b_lo, b_hi, poison, 0
+ * (lo, hi) = the channel's sum of radiances as a two's-complement 128-bit integer in units of 2^-64, each radiance truncated towards zero
+ * at 2^-64; poison = the number of channel values that were not finite or beyond 2^31 (such a pixel resolves to NaN, as in rtw_render_*).
+ *
+ * rtw_render_accum_*: `p` describes the WHOLE render (spp, n_chunks with the default rule of rtw_params, seed, max_depth, numerics bits);
+ * the call renders the chunks [chunk_begin, chunk_begin + chunk_count) of it -- in units of the effective chunks, rtw_stats_t.n_chunks of
+ * the whole render = rtw_accum_info_t.n_chunks -- and adds them to `a`.  d_out != NULL: the running image (layout of rtw_render_device_*,
+ * p->gamma) is written from the new sums, divided by the samples the accumulator holds INCLUDING this pass.  Asynchronous like
+ * rtw_render_device_*; rtw_stats() afterwards reports this pass alone.  Operations on one accumulator are ordered by the library in the
+ * order of the calls whatever their streams (each waits for the previous one on the device); the calls themselves must not run
+ * concurrently on one accumulator.  Two streams that should overlap -> two accumulators -> rtw_accum_merge.
+ *   The first pass BINDS the accumulator to its render: size, precision, seed, spp, chunk size, n_chunks, max_depth, numerics bits, the
+ * camera's bytes and a 64-bit hash of the scene's arrays taken at upload.  The host keeps the chunk ranges already added.  A later pass,
+ * or a merge, of another render -> -4; a range that overlaps what is there -> -2; both before any HIP call, the accumulator untouched.
+ * RTW_FLAG_GROUP_CULL, RTW_FLAG_SCAN_VALU, job_pixels and gamma may differ from pass to pass.  rtw_accum_reset zeroes and unbinds.
+ *   Whole frames on one device: shard_count != 1, RTW_FLAG_COMPACT_TILES, RTW_FLAG_RCCL_REDUCE, RTW_FLAG_RAY_POOL, n_devices > 1 or
+ * device_ids -> -2; chunk_begin < 0, chunk_count < 1 or a range beyond the effective n_chunks -> -2; a null cam / p / accumulator /
+ * scene -> -1 (these, in this order, before the handles are looked at); a scene of the other precision, an accumulator of another size
+ * or device than the call -> -4.  All decided before any HIP call.
+ *   rtw_accum_resolve_*: accumulator -> image (sum / samples held, sqrt if gamma, rounded to T) into DEVICE memory, asynchronous;
+ * _host_: into HOST memory, blocking.  An accumulator without samples -> -2; the other precision than its render's -> -4.
+ *   rtw_accum_merge: dst += src (same size and device, else -4; disjoint chunk ranges of the same render, else -4 / -2, dst untouched;
+ * an unbound dst takes src's binding; an unbound src is a no-op).  Asynchronous on `hip_stream`, ordered behind both accumulators' work.
+ *   rtw_accum_ranges: the chunk ranges held, sorted, disjoint and coalesced: *count receives their number, at most `capacity` pairs
+ * (begin, end), end exclusive, are written to begin_end.
+ *   rtw_accum_read_pixels: blocking copy of the words (layout above) to the host, behind everything enqueued on the accumulator.
+ *   rtw_accum_export: blocking; writes a self-describing, versioned blob -- the bound render, the chunk ranges, the words -- of *size
+ * bytes (buf == NULL: only reports *size; capacity < *size -> -2).  rtw_accum_import recreates the accumulator from it on any device:
+ * the checkpoint, and the way partial sums travel between devices or processes (there is no cross-device merge in the library).  A
+ * truncated blob, one of another version or a corrupt one -> -2, before any HIP call.  Blobs are little-endian like the device.
+ *   Accumulators own their device memory: rtw_shutdown() does NOT invalidate them.  Additive to ABI 4: detected by symbol lookup. */
+typedef struct rtw_accum *rtw_accum_handle;
+typedef struct {
+    int32_t width, height, device;
+    int32_t bound;          /* 0: no pass yet (the fields below are 0)                        */
+    int32_t precision;      /* 32 or 64                                                       */
+    int32_t spp, chunk_spp; /* of the whole render; chunk_spp = samples per chunk             */
+    int32_t n_chunks;       /* effective chunks of the whole render                           */
+    int32_t max_depth;
+    int32_t numerics_flags; /* the RTW_FLAG_NUMERICS_* bits of the render                     */
+    int32_t chunks_done;    /* chunks held                                                    */
+    int32_t samples_done;   /* samples per pixel held: the divisor of resolve                 */
+    int32_t complete;       /* chunks_done == n_chunks                                        */
+    uint64_t seed;
+} rtw_accum_info_t;
+int rtw_accum_create(int device, int32_t width, int32_t height, rtw_accum_handle *out);   /* zeroed */
+int rtw_accum_reset(rtw_accum_handle a, void *hip_stream);
+int rtw_accum_free(rtw_accum_handle a);
+int rtw_render_accum_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p,
+                         int32_t chunk_begin, int32_t chunk_count, rtw_accum_handle a, void *d_out, void *hip_stream);
+int rtw_render_accum_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p,
+                         int32_t chunk_begin, int32_t chunk_count, rtw_accum_handle a, void *d_out, void *hip_stream);
+int rtw_accum_resolve_f32(rtw_accum_handle a, int32_t gamma, void *d_out, void *hip_stream);
+int rtw_accum_resolve_f64(rtw_accum_handle a, int32_t gamma, void *d_out, void *hip_stream);
+int rtw_accum_resolve_host_f32(rtw_accum_handle a, int32_t gamma, float *out);
+int rtw_accum_resolve_host_f64(rtw_accum_handle a, int32_t gamma, double *out);
+int rtw_accum_merge(rtw_accum_handle dst, rtw_accum_handle src, void *hip_stream);
+int rtw_accum_info(rtw_accum_handle a, rtw_accum_info_t *out);
+int rtw_accum_ranges(rtw_accum_handle a, int32_t capacity, int32_t *count, int32_t *begin_end);
+int rtw_accum_read_pixels(rtw_accum_handle a, uint64_t *host_words);
+int rtw_accum_export(rtw_accum_handle a, void *buf, uint64_t capacity, uint64_t *size);
+int rtw_accum_import(int device, const void *buf, uint64_t size, rtw_accum_handle *out);
+
 /* Counters/timings of the last render issued from this thread (waits for it to finish). */
 int rtw_stats(rtw_stats_t *out);
 

@@ -164,4 +164,84 @@ function render(scene::HittableList, cams::AbstractVector{Camera{T}}, image_widt
     img
 end
 
+"""
+    render_progressive(scene, cam, image_width=400, n_samples=1; passes=4, callback=nothing, depth=16, seed=1, n_chunks=0, device=-1, numerics=:reference, group_cull=false, scan_valu=false)
+
+Progressive render (rtw_render_accum_f32/_f64 into an rtw_accum): the render's chunks in `passes` passes of (nearly) equal chunk counts
+on one device.  The returned `Matrix{RGB{T}}` is bit-identical to `render(scene, cam, image_width, n_samples; ...)` with the same keywords.
+`callback(img, samples_done)` runs after every pass with the image of the samples added so far (rtw_accum_resolve_host_*: it waits for
+the pass); a `true` return value stops the render and that image is returned.  `n_chunks` keeps `render`'s default (min(n_samples, 256)
+chunks); refinement in 1-sample steps beyond 256 samples: `n_chunks = n_samples`.
+(Not executed in this repository: there is no `julia` in its build image; tests/test_gpu_accum.py drives the same entry points.)
+"""
+function render_progressive(scene::HittableList, cam::Camera{T}, image_width=400, n_samples=1;
+                            passes=4, callback=nothing, depth=16, seed=1, n_chunks=0, device=-1, numerics=:reference, group_cull=false, scan_valu=false) where T <: Union{Float32,Float64}
+    passes >= 1 || throw(ArgumentError("passes must be >= 1"))
+    n_samples >= 1 || throw(ArgumentError("n_samples must be >= 1"))
+    numerics in (:reference, :contract, :reference_fma2) || throw(ArgumentError("numerics must be :reference, :contract or :reference_fma2"))
+    nflags = numerics === :contract ? 32 : numerics === :reference_fma2 ? 128 : 0
+    image_height = image_width ÷ (16//9)
+    # the effective chunks of the render (include/rtw_hip.h rtw_params.n_chunks): what chunk_begin / chunk_count count
+    nch = min(n_chunks > 0 ? n_chunks : min(n_samples, 256), n_samples)
+    cs = cld(n_samples, nch)
+    nch = cld(n_samples, cs)
+    passes = min(passes, nch)
+    n = length(scene)
+    cx = Vector{T}(undef, n); cy = similar(cx); cz = similar(cx); r = similar(cx)
+    ar = similar(cx); ag = similar(cx); ab = similar(cx); param = similar(cx)
+    kind = Vector{Int32}(undef, n)
+    for (i, h) in enumerate(scene)
+        h isa Sphere{T} || throw(ArgumentError("scene[$i] is $(typeof(h)); the HIP path takes Sphere{$T} only"))
+        cx[i], cy[i], cz[i] = h.center
+        r[i] = h.radius
+        kind[i] = matkind(h.mat)
+        ar[i], ag[i], ab[i] = albedo(h.mat)
+        param[i] = matparam(h.mat)
+    end
+    img = Matrix{RGB{T}}(undef, image_height, image_width)
+    ccam = Ref(CCamera(cam))
+    check(rc) = rc == 0 || error("librtw_hip: error $rc: $(last_error())")
+    hscene = Ref{Ptr{Cvoid}}(C_NULL)
+    hacc = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve cx cy cz r kind ar ag ab param img begin
+        cscene = Ref(CScene{T}(n, pointer(cx), pointer(cy), pointer(cz), pointer(r), pointer(kind),
+                               pointer(ar), pointer(ag), pointer(ab), pointer(param)))
+        params = Ref(CParams(image_width, image_height, n_samples, depth, seed, n_chunks, 0, 1, -1, 1,
+                             (group_cull ? 1 : 0) | (scan_valu ? 4 : 0) | nflags, 0, 0, Ptr{Int32}(C_NULL)))
+        out = pointer(reinterpret(T, vec(img)))
+        try
+            if T === Float32
+                check(ccall((:rtw_scene_upload_f32, LIB), Cint, (Ref{CScene{Float32}}, Cint, Ref{Ptr{Cvoid}}), cscene, device, hscene))
+            else
+                check(ccall((:rtw_scene_upload_f64, LIB), Cint, (Ref{CScene{Float64}}, Cint, Ref{Ptr{Cvoid}}), cscene, device, hscene))
+            end
+            check(ccall((:rtw_accum_create, LIB), Cint, (Cint, Int32, Int32, Ref{Ptr{Cvoid}}), device, image_width, image_height, hacc))
+            done = 0
+            for k in 0:passes-1
+                b, e = k * nch ÷ passes, (k + 1) * nch ÷ passes
+                if T === Float32
+                    check(ccall((:rtw_render_accum_f32, LIB), Cint, (Ptr{Cvoid}, Ref{CCamera{Float32}}, Ref{CParams}, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                                hscene[], ccam, params, b, e - b, hacc[], C_NULL, C_NULL))
+                else
+                    check(ccall((:rtw_render_accum_f64, LIB), Cint, (Ptr{Cvoid}, Ref{CCamera{Float64}}, Ref{CParams}, Int32, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                                hscene[], ccam, params, b, e - b, hacc[], C_NULL, C_NULL))
+                end
+                done = min(n_samples, e * cs)                  # samples per pixel in the chunks [0, e)
+                if callback !== nothing || k == passes - 1
+                    if T === Float32
+                        check(ccall((:rtw_accum_resolve_host_f32, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float32}), hacc[], 1, out))
+                    else
+                        check(ccall((:rtw_accum_resolve_host_f64, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), hacc[], 1, out))
+                    end
+                    callback !== nothing && callback(img, done) === true && break
+                end
+            end
+        finally
+            ccall((:rtw_accum_free, LIB), Cint, (Ptr{Cvoid},), hacc[])        # (NULL handles are accepted)
+            ccall((:rtw_scene_free, LIB), Cint, (Ptr{Cvoid},), hscene[])
+        end
+    end
+    img
+end
+
 end # module

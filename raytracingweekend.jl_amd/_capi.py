@@ -13,6 +13,9 @@ SYMBOLS = [
     "rtw_scene_upload_f32", "rtw_scene_upload_f64", "rtw_scene_free", "rtw_render_device_f32",
     "rtw_render_device_f64", "rtw_stats", "rtw_stats_devices", "rtw_unit_f32", "rtw_unit_f64", "rtw_shutdown",
     "rtw_render_batch_f32", "rtw_render_batch_f64", "rtw_render_batch_device_f32", "rtw_render_batch_device_f64",
+    "rtw_accum_create", "rtw_accum_reset", "rtw_accum_free", "rtw_render_accum_f32", "rtw_render_accum_f64",
+    "rtw_accum_resolve_f32", "rtw_accum_resolve_f64", "rtw_accum_resolve_host_f32", "rtw_accum_resolve_host_f64",
+    "rtw_accum_merge", "rtw_accum_info", "rtw_accum_ranges", "rtw_accum_read_pixels", "rtw_accum_export", "rtw_accum_import",
 ]
 
 
@@ -45,6 +48,11 @@ class Stats(C.Structure):
     _fields_ = [("samples", C.c_uint64), ("segments", C.c_uint64), ("sphere_tests", C.c_uint64),
                 ("kernel_ms", C.c_double), ("total_ms", C.c_double), ("n_chunks", C.c_int32),
                 ("grid_blocks", C.c_int32), ("block_threads", C.c_int32), ("gather_path", C.c_int32)]
+
+
+class AccumInfo(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("width", "height", "device", "bound", "precision", "spp", "chunk_spp", "n_chunks", "max_depth",
+                                          "numerics_flags", "chunks_done", "samples_done", "complete")] + [("seed", C.c_uint64)]
 
 
 _lib = None
@@ -83,6 +91,19 @@ def lib():
                                               C.c_void_p, C.c_void_p]
     L.rtw_render_batch_device_f64.argtypes = [C.c_void_p, C.POINTER(CameraF64), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(Params),
                                               C.c_void_p, C.c_void_p]
+    for name, CamT in (("rtw_render_accum_f32", CameraF32), ("rtw_render_accum_f64", CameraF64)):
+        getattr(L, name).argtypes = [C.c_void_p, C.POINTER(CamT), C.POINTER(Params), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtw_accum_create.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.rtw_accum_reset.argtypes = [C.c_void_p, C.c_void_p]
+    L.rtw_accum_free.argtypes = [C.c_void_p]
+    L.rtw_accum_resolve_f32.argtypes = L.rtw_accum_resolve_f64.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.rtw_accum_resolve_host_f32.argtypes = L.rtw_accum_resolve_host_f64.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+    L.rtw_accum_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtw_accum_info.argtypes = [C.c_void_p, C.POINTER(AccumInfo)]
+    L.rtw_accum_ranges.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.rtw_accum_read_pixels.argtypes = [C.c_void_p, C.c_void_p]
+    L.rtw_accum_export.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+    L.rtw_accum_import.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
     L.rtw_stats.argtypes = [C.POINTER(Stats)]
     L.rtw_stats_devices.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double)]
     L.rtw_unit_f32.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SceneF32), C.POINTER(CameraF32)]

@@ -5,6 +5,7 @@
 //   rtw_launch.hip       one render = one launch of the trace kernel (rtw_kernels.hpp / rtw_pool.hpp): geometry, job shape, counters
 //   rtw_render_host.hip  the host-buffer entry points: cached per-device context (scene, stream, image), one device or a device list
 //   rtw_multi.hip        what a device list needs: peer access, the on-demand RCCL binding, the un-tile kernel
+//   rtw_accum.hip        progressive render: the accumulator object, its passes, merge / resolve kernels, export / import
 //   rtw_unit.hip         the T0 unit entry points (rtw_units.hpp)
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
 #pragma once
@@ -57,6 +58,7 @@ struct rtw_scene_dev {
     unsigned short *c_orig;
     int c_groups_pad, c_big;
     double c_cs[3], c_rs;
+    uint64_t content_hash;   // FNV-1a over the precision tag, n and the nine host arrays at upload: what binds a progressive accumulator to its scene
 };
 
 namespace rtwh {
@@ -200,6 +202,14 @@ int launch_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_v
 int launch_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
 inline int launch_batch_t(rtw_scene_handle s, const rtw_camera_f32 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_batch_f32(s, c, n, sd, p, d, st, r, x); }
 inline int launch_batch_t(rtw_scene_handle s, const rtw_camera_f64 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_batch_f64(s, c, n, sd, p, d, st, r, x); }
+// ... one pass of a progressive render (rtw_accum.hip has validated it): the chunks [chunk_begin, chunk_begin + chunk_count) of the render
+// `p` describes are added to `words` (layout: include/rtw_hip.h rtw_accum_read_pixels); `samples` = the samples the accumulator holds
+// after this pass, the divisor of the running image written to `d_out` (null: none)
+struct AccumPass { unsigned long long *words; int chunk_begin, chunk_count, samples; };
+int launch_accum_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const AccumPass &pass, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
+int launch_accum_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const AccumPass &pass, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
+inline int launch_accum_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, const AccumPass &a, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_accum_f32(s, c, p, a, d, st, r, x); }
+inline int launch_accum_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, const AccumPass &a, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_accum_f64(s, c, p, a, d, st, r, x); }
 // rtw_abi.hip: the checks of a batched render that need no device (include/rtw_hip.h rtw_render_batch_f32)
 int validate_batch(const void *cams, int32_t n_views, const rtw_params *p, const void *out);
 

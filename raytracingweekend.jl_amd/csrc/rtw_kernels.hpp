@@ -96,6 +96,17 @@ template <typename T> struct BatchArgs {
     unsigned div_tjv_m, div_tjv_s;      // exact division by tiles_jv (make_udiv)
     unsigned long long view_elems;      // W * H * 3: elements of one output frame
 };
+// Progressive render (rtw_render_accum_*; the ACCUM instances of trace_kernel): a launch renders the chunks
+// [chunk_begin, chunk_begin + KParams::n_chunks) of the render KParams::spp / chunk_spp describe and ADDS every finished job to the
+// pixel's running sums in HBM instead of ending them (store_job_accum).  Accumulator layout (include/rtw_hip.h rtw_accum_read_pixels):
+// width x height pixels x 8 uint64, pixel (i, j) (1-based) at word ((j-1) * height + (i-1)) * 8: r.lo r.hi g.lo g.hi b.lo b.hi poison 0
+// -- the LDS slot's own layout.  A job is owned by one workgroup within a launch and the passes into one accumulator are ordered on the
+// device (rtw_accum.hip: every operation waits for the accumulator's event): the read-add-write needs no atomics.
+struct AccumArgs {
+    unsigned long long *words;      // the accumulator
+    int chunk_begin;                // global index of this pass's chunk 0: what the item's RNG stream and sample indices are made from
+    int samples;                    // samples in the accumulator INCLUDING this pass: the divisor of the running image
+};
 struct JobCache { unsigned long long jc; unsigned jc_lock; unsigned queue_off; unsigned last_g; unsigned static_used; };       // see claim_job
 template <typename T> struct WgShared {
     unsigned char slots[RTW_SLOT_BYTES];      // n_slots x (128-byte JobSlot + 64 bytes per job pixel)
@@ -213,6 +224,37 @@ __device__ RTW_RARE_ATTR void store_job(const KParams &P, const JobSlot *S, unsi
             const size_t pix = P.out_layout == 0 ? (size_t)j0 * (size_t)P.height + (size_t)i0
                                                  : (size_t)S->k_tile * 64u + (size_t)((i0 & 7) + 8 * (j0 & 7));
             out[pix * 3 + ch] = (T)v;
+        }
+    }
+}
+
+// The end of a job of an ACCUM launch: lane = (pixel, channel) reads the channel's running 128-bit sum (one 16-byte load), adds the job's
+// sum with carry and writes it back; the poison count (word 6) is read by the pixel's three lanes and written by its channel-0 lane.  `out`
+// non-null: the running image, from the NEW totals -- store_job's formula with the divisor A.samples.
+template <typename T>
+__device__ RTW_RARE_ATTR void store_job_accum(const KParams &P, const JobSlot *S, unsigned lane, T *__restrict__ out, const AccumArgs &A) {
+    const unsigned px = lane / 3u, ch = lane - 3u * px, rs = P.rows_shift;
+    if (px < (1u << P.job_shift)) {
+        if ((S->valid >> px) & 1u) {
+            const int i0 = S->i_base + (int)(px & ((1u << rs) - 1u)), j0 = S->j_base + (int)(px >> rs);
+            const size_t pix = (size_t)j0 * (size_t)P.height + (size_t)i0;
+            const unsigned long long *a = S->acc(px);
+            ulonglong2 *g = reinterpret_cast<ulonglong2 *>(A.words + pix * 8u);
+            // (the poison count first, then the channel: fewer values alive at once)
+            const unsigned long long poison = reinterpret_cast<const unsigned long long *>(g)[6] + a[6];
+            const bool poisoned = poison != 0ull;
+            if (ch == 0u) g[3] = ulonglong2{poison, 0ull};
+            const ulonglong2 old = g[ch];
+            const unsigned long long lo = old.x + a[2 * ch];
+            const unsigned long long hi = old.y + a[2 * ch + 1] + (lo < old.x ? 1ull : 0ull);
+            g[ch] = ulonglong2{lo, hi};
+            if (out) {
+                double v = fx_to_double(lo, hi);
+                if (poisoned) v = __builtin_nan("");
+                v = v / (double)A.samples;
+                if (P.gamma) v = __builtin_sqrt(v);
+                out[pix * 3 + ch] = (T)v;
+            }
         }
     }
 }
@@ -387,9 +429,13 @@ __device__ RTW_RARE_ATTR void open_job(const KParams &P, JobSlot *S, unsigned la
 // NUMK >= 0: the numerics mode is fixed at compile time (the launcher picks such an instance for the default mode of the headline
 // variants: the other modes' code and their scalar state are then not in the kernel at all); NUMK < 0: the mode of the arguments.
 // BATCH: a batched render (BatchArgs; `cam_arg` and P.seed are unused, `out` holds N frames); otherwise `batch` is unused.
-template <typename T, bool PROFILE, bool LDS_SCENE, bool CULL, bool MFMA = false, int NUMK = -1, bool BATCH = false>
+// ACCUM: one pass of a progressive render (AccumArgs): P.n_chunks / bpj count the pass's own chunks, so the scheduling sees an ordinary
+// small render; the item's chunk is accum.chunk_begin + its local chunk wherever it has a meaning (RNG stream, sample indices); `out`
+// may be null (no running image); otherwise `accum` is unused.
+template <typename T, bool PROFILE, bool LDS_SCENE, bool CULL, bool MFMA = false, int NUMK = -1, bool BATCH = false, bool ACCUM = false>
 __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void trace_kernel(KParams P_arg, Camera<T> cam_arg, DevScene<T> scene,
-                                                   CullScene<T> cull, T *__restrict__ out, DevCounters *ctr, BatchArgs<T> batch) {
+                                                   CullScene<T> cull, T *__restrict__ out, DevCounters *ctr, BatchArgs<T> batch, AccumArgs accum) {
+    static_assert(!(BATCH && ACCUM) && !(PROFILE && ACCUM), "no batched and no phase-profile ACCUM instances");
     using V4 = typename Vec4<T>::type;
     if constexpr (NUMK >= 0) { scene.numerics = NUMK; cull.numerics = NUMK; }
     const unsigned lane = lane_id();
@@ -541,6 +587,7 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                 fin &= fin - 1ull;
                 JobSlot *S = sh->slot(uniform((unsigned)__shfl((int)((ref_depth & RTW_REF_MASK) >> 4), L)), P.slot_stride);
                 if constexpr (BATCH) store_job<T>(P, S, lane, out + (size_t)uniform(S->pad) * batch.view_elems);
+                else if constexpr (ACCUM) store_job_accum<T>(P, S, lane, out, accum);
                 else store_job<T>(P, S, lane, out);
                 clk.count(21, 1u);                                                                        // jobs stored
                 __hip_atomic_store(&S->ready_seq, RTW_SLOT_FREE, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -624,6 +671,7 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                         const int i0 = S->i_base + (int)(px & ((1u << rsh) - 1u)), j0 = S->j_base + (int)(px >> rsh);
                         Rng r0;
                         if constexpr (BATCH) rng_stream(batch.seeds[uniform(S->pad)], (unsigned long long)j0 * (unsigned)P.height + (unsigned)i0, chunk, r0);
+                        else if constexpr (ACCUM) rng_stream(P.seed, (unsigned long long)j0 * (unsigned)P.height + (unsigned)i0, chunk + (unsigned)accum.chunk_begin, r0);
                         else rng_stream(P.seed, (unsigned long long)j0 * (unsigned)P.height + (unsigned)i0, chunk, r0);
                         __builtin_amdgcn_wave_barrier();                      // (the previous batch's states have all been read)
                         pool_rng[lane] = ulonglong2{r0.x, r0.y};
@@ -649,9 +697,11 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                             const int i0 = S->i_base + (int)(px & ((1u << rsh) - 1u)), j0 = S->j_base + (int)(px >> rsh);
                             const unsigned long long pix = (unsigned long long)j0 * (unsigned)P.height + (unsigned)i0;
                             if constexpr (BATCH) rng_stream(batch.seeds[uniform(S->pad)], pix, chunk, rng);
+                            else if constexpr (ACCUM) rng_stream(P.seed, pix, chunk + (unsigned)accum.chunk_begin, rng);
                             else rng_stream(P.seed, pix, chunk, rng);
                         }
-                        const int s0 = (int)chunk * P.chunk_spp;
+                        int s0 = (int)chunk * P.chunk_spp;
+                        if constexpr (ACCUM) s0 = (int)(chunk + (unsigned)accum.chunk_begin) * P.chunk_spp;     // the GLOBAL sample index
                         samples_left = min(P.spp, s0 + P.chunk_spp) - s0;
                         jitter = s0 != 0;                                             // sample 1 of the pixel is centred
                         ref_depth = pool_slot * 16u + px;

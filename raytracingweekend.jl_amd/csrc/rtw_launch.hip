@@ -22,13 +22,17 @@ void make_udiv(unsigned d, unsigned *m, unsigned *s) {
 // n_views >= 1: a batch (validate_batch has accepted it): `cam` points to n_views cameras, `seeds` to n_views seeds (null: p->seed for
 // every view), `d_out` to n_views frames.  The views' tile columns are laid side by side (rtw::BatchArgs), so the job shape, the grid and
 // the queues see the batch's total tile count.  n_views == 0: one render of `cam`.
+// `pass` non-null (n_views == 0; validate_accum has accepted it): one pass of a progressive render -- the chunks [chunk_begin, chunk_begin +
+// chunk_count) of the render `p` describes, added to pass->words (rtw::AccumArgs); the job shape, the grid and the batches are those of a
+// render of chunk_count chunks; `d_out` may be null.
 template <typename T, typename CamT>
 int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
-                  RenderRec **rec_out, CtxPtr *ctx_out) {
-    if (!scene || !cam || !d_out) return fail(-1, "null argument");
+                  RenderRec **rec_out, CtxPtr *ctx_out, const AccumPass *pass = nullptr) {
+    if (!scene || !cam || (!d_out && !pass)) return fail(-1, "null argument");
     if (scene->is_f64 != (sizeof(T) == 8)) return fail(-4, "scene handle precision does not match the call");
     int nch, cs;
     if (int rc = validate_params(p, &nch, &cs)) return rc;
+    if (pass) nch = pass->chunk_count;          // (what the scheduling sees; K.spp and K.chunk_spp stay the whole render's)
     const bool batch = n_views > 0;
     if (p->device >= 0 && p->device != scene->device)
         return fail(-4, "params.device %d != scene device %d", p->device, scene->device);
@@ -51,6 +55,9 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
         B.view_elems = (unsigned long long)p->width * (unsigned long long)p->height * 3ull;
         K.tiles_j *= n_views;                   // (validate_batch: N x tiles_j fits the queue positions)
     }
+    rtw::AccumArgs A;
+    memset(&A, 0, sizeof A);
+    if (pass) { A.words = pass->words; A.chunk_begin = pass->chunk_begin; A.samples = pass->samples; }
     const long long n_local = batch ? (long long)K.tiles_i * K.tiles_j : local_tiles(p);
     K.gamma = p->gamma;
     K.out_layout = (p->flags & RTW_FLAG_COMPACT_TILES) ? 1 : 0;
@@ -86,7 +93,7 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
                                    : (size_t)rtw::scene_geom_alloc(scene->n, scene->n_pad) * sizeof(V4);
     const bool lds_scene = geom_bytes <= RTW_LDS_SCENE_MAX_BYTES;
     const size_t lds_bytes = list_bytes + shared_bytes + (mfma ? rtw::mfma_cell_bytes<T>() : 0) + (lds_scene ? geom_bytes : 0);
-    typedef void (*kern_t)(rtw::KParams, rtw::Camera<T>, rtw::DevScene<T>, rtw::CullScene<T>, T *, rtw::DevCounters *, rtw::BatchArgs<T>);
+    typedef void (*kern_t)(rtw::KParams, rtw::Camera<T>, rtw::DevScene<T>, rtw::CullScene<T>, T *, rtw::DevCounters *, rtw::BatchArgs<T>, rtw::AccumArgs);
     kern_t kern;
     if (cull && mfma && phase_profile) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, true, true, true, true> : (kern_t)rtw::trace_kernel<T, false, false, true, true>;
     else if (cull && mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true, true> : (kern_t)rtw::trace_kernel<T, false, false, true, true>;
@@ -108,6 +115,15 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
         if (S.numerics == rtw::NUM_REFERENCE && lds_scene && mfma)
             kern = cull ? (kern_t)rtw::trace_kernel<T, false, true, true, true, rtw::NUM_REFERENCE, true> : (kern_t)rtw::trace_kernel<T, false, true, false, true, rtw::NUM_REFERENCE, true>;
     }
+    // a pass of a progressive render: the same choice among the ACCUM instances (no phase profile)
+    if (pass) {
+        if (cull && mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true, true, -1, false, true> : (kern_t)rtw::trace_kernel<T, false, false, true, true, -1, false, true>;
+        else if (cull) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true, false, -1, false, true> : (kern_t)rtw::trace_kernel<T, false, false, true, false, -1, false, true>;
+        else if (mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false, true, -1, false, true> : (kern_t)rtw::trace_kernel<T, false, false, false, true, -1, false, true>;
+        else kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false, false, -1, false, true> : (kern_t)rtw::trace_kernel<T, false, false, false, false, -1, false, true>;
+        if (S.numerics == rtw::NUM_REFERENCE && lds_scene && mfma)
+            kern = cull ? (kern_t)rtw::trace_kernel<T, false, true, true, true, rtw::NUM_REFERENCE, false, true> : (kern_t)rtw::trace_kernel<T, false, true, false, true, rtw::NUM_REFERENCE, false, true>;
+    }
     // The ray-pool kernel (rtw_pool.hpp; opt-in: RTW_FLAG_RAY_POOL, or RTW_POOL=1 in the environment for A/B runs) exists in `make POOL=1`
     // builds only: Float32 plain scans on the matrix pipe, when the pool, the rings and the scene copy fit the 160 KB of LDS of a CU (one
     // workgroup of RTW_POOL_W waves per CU); everything else runs the lane-loop kernel above.  The default library refuses the flag.
@@ -121,7 +137,7 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
     pool_kern_t pool_kern = nullptr;
     if constexpr (sizeof(T) == 4) {
         pool_lds = rtw::pool_fixed_lds_bytes<T, RTW_POOL_W, RTW_POOL_R>() + rtw::pool_scene_lds_bytes<T>(scene->n, scene->n_pad);
-        pool = !batch && mfma && !cull && (env_pool || (p->flags & RTW_FLAG_RAY_POOL)) && pool_lds <= ctx->lds_per_cu &&
+        pool = !batch && !pass && mfma && !cull && (env_pool || (p->flags & RTW_FLAG_RAY_POOL)) && pool_lds <= ctx->lds_per_cu &&
                cs <= RTW_POOL_MAX_CHUNK_SPP;
         pool_kern = phase_profile ? (pool_kern_t)rtw::trace_pool_kernel<T, RTW_POOL_W, RTW_POOL_R, true> : (pool_kern_t)rtw::trace_pool_kernel<T, RTW_POOL_W, RTW_POOL_R, false>;
     }
@@ -237,7 +253,7 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
         B.seeds = reinterpret_cast<const unsigned long long *>(static_cast<const char *>(rec->d_views) + cam_bytes);
     }
     // pixels of other shards read 0 in the full-frame layout (the sum over the shards is the image)
-    if (K.out_layout == 0 && p->shard_count > 1)
+    if (K.out_layout == 0 && p->shard_count > 1 && d_out)
         HIP_TRY(hipMemsetAsync(d_out, 0, (size_t)p->width * p->height * 3 * sizeof(T), stream));
     HIP_TRY(hipEventRecord(rec->ev0, stream));
     if (total_jobs > 0) {
@@ -246,7 +262,7 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
         if (pool) hipLaunchKernelGGL(pool_kern, dim3((unsigned)grid), dim3((unsigned)block_threads), pool_lds, stream, K, C, S, (T *)d_out, rec->ctr);
         else
 #endif
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds_bytes, stream, K, C, S, CS, (T *)d_out, rec->ctr, B);
+        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds_bytes, stream, K, C, S, CS, (T *)d_out, rec->ctr, B, A);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(rec->ev1, stream));
@@ -344,6 +360,14 @@ int launch_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_v
 int launch_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
                      RenderRec **rec_out, CtxPtr *ctx_out) {
     return launch_render<double>(scene, cams, n_views, seeds, p, d_out, stream, rec_out, ctx_out);
+}
+int launch_accum_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const AccumPass &pass, void *d_out, hipStream_t stream,
+                     RenderRec **rec_out, CtxPtr *ctx_out) {
+    return launch_render<float>(scene, cam, 0, nullptr, p, d_out, stream, rec_out, ctx_out, &pass);
+}
+int launch_accum_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const AccumPass &pass, void *d_out, hipStream_t stream,
+                     RenderRec **rec_out, CtxPtr *ctx_out) {
+    return launch_render<double>(scene, cam, 0, nullptr, p, d_out, stream, rec_out, ctx_out, &pass);
 }
 
 }  // namespace rtwh

@@ -332,6 +332,15 @@ int upload_scene(const SceneT *s, int device, rtw_scene_handle *out) {
     ScenePtr h(new rtw_scene_dev());                      // freed on every error path below
     memset(h.get(), 0, sizeof(rtw_scene_dev));
     h->device = dev; h->is_f64 = sizeof(T) == 8; h->n = n; h->n_pad = n_pad;
+    {
+        uint64_t hsh = 0xcbf29ce484222325ull;
+        auto mix = [&hsh](const void *q, size_t nb) { const unsigned char *b = static_cast<const unsigned char *>(q); for (size_t k = 0; k < nb; ++k) { hsh ^= b[k]; hsh *= 0x100000001b3ull; } };
+        const int32_t tag[2] = {(int32_t)sizeof(T), (int32_t)n};
+        mix(tag, sizeof tag);
+        for (const T *arr : {s->cx, s->cy, s->cz, s->r, s->ar, s->ag, s->ab, s->param}) mix(arr, sizeof(T) * (size_t)n);
+        mix(s->kind, sizeof(int32_t) * (size_t)n);
+        h->content_hash = hsh;
+    }
     const size_t bytes = sizeof(V4) * (size_t)n_alloc;
     HIP_TRY(hipMalloc(&h->geom, bytes));
     HIP_TRY(hipMalloc(&h->mat0, bytes));
