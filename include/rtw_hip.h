@@ -220,7 +220,7 @@ int rtw_render_batch_device_f64(rtw_scene_handle scene, const rtw_camera_f64 *ca
  * with spp = min(S, C*s), n_chunks = C.
  *
  * The accumulator: width*height pixels x 8 uint64_t in device memory, pixel (i, j) (1-based row, column) at word ((j-1)*height + (i-1))*8:
- *     r_lo, r_hi, g_lo, g_hi, b_lo, b_hi, poison, 0
+ *     r_lo, r_hi, g_lo, g_hi, b_lo, b_hi, poison, 0          (word 7: the half difference of an ADAPTIVE accumulator, see below)
  * (lo, hi) = the channel's sum of radiances as a two's-complement 128-bit integer in units of 2^-64, each radiance truncated towards zero
  * at 2^-64; poison = the number of channel values that were not finite or beyond 2^31 (such a pixel resolves to NaN, as in rtw_render_*).
  *
@@ -282,6 +282,75 @@ int rtw_accum_ranges(rtw_accum_handle a, int32_t capacity, int32_t *count, int32
 int rtw_accum_read_pixels(rtw_accum_handle a, uint64_t *host_words);
 int rtw_accum_export(rtw_accum_handle a, void *buf, uint64_t capacity, uint64_t *size);
 int rtw_accum_import(int device, const void *buf, uint64_t size, rtw_accum_handle *out);
+
+/* Adaptive sampling: a progressive render that stops each 8x8 tile as soon as an EXACT noise estimate says it is good enough.
+ *
+ * The definition.  An adaptive render is a progressive render (spp = S, effective n_chunks = N, chunk size s) in which every 8x8 tile t
+ * ends up holding a prefix [0, C_t) of the chunks.  Tiles are numbered column-major like the image, t = tj*tiles_i + ti (tiles_i =
+ * ceil(height / 8) tiles down a column); ragged tiles at the frame's edges count their valid pixels only.
+ *   Checkpoints: the chunk counts c = min_chunks, min_chunks + check_chunks, ... below N.  min_chunks and check_chunks are even and >= 2
+ * (the two halves below then hold equally many FULL chunks at every checkpoint); 0 = the default, the smallest even number >=
+ * max(16, N/8) (passes of fewer than 16 chunks are in the launcher's bad regime).
+ *   Noise statistic: for every sample and channel q = min(fx >> 40, 2^30 - 1), fx = the channel's 64.64 fixed-point radiance exactly as
+ * it is added to the sums (so q is in units of 2^-24 and capped at 64); q = 0 for a negative or a poisoning value.  The pixel's HALF
+ * DIFFERENCE H_p is the signed 64-bit sum of +q over the samples of even global chunks and -q over the samples of odd global chunks
+ * (|H_p| < 2^63 for any int32 sample count).  It lives in word 7 of the pixel's record -- 0 in every other accumulator -- and, being an
+ * integer sum, does not depend on order, scan mode, job size or pass structure.
+ *   Stopping rule: at checkpoint c a tile with C_t == c holds n = c*s samples per pixel and has npix valid pixels; it is CONVERGED iff
+ *         D <= tol * max(Y, floor * n * npix)
+ *     D = sum_p (double)|H_p| * 2^-24,   Y = sum_p max(y_p, 0),   y_p = (double(R) + double(G)) + double(B)
+ * (double(.) = the channel's 128-bit sum rounded once to binary64, as resolve does), both sums over the tile's valid, unpoisoned pixels in
+ * the tile-local order (i mod 8) + 8 (j mod 8) -- a poisoned pixel adds 0 to both.  Everything in binary64, every operation rounded once,
+ * no FMA, the sums sequential in that order; the right-hand side is ((floor * (double)n) * (double)npix), then max, then * tol.
+ *   C_t = the first checkpoint at which tile t is converged, else N.
+ *   (Approximately -- not part of the contract: D / Y = 1/2 sum|mean_even - mean_odd| / sum mean, so for a tile of pixels of similar
+ * noise `tolerance` is roughly 0.8 x the tile's relative standard error; dark_floor keeps near-black tiles from never stopping: it is
+ * the radiance per sample and pixel, summed over the channels, below which the tile is judged as if it were that bright.)
+ *   Consequences (tests/test_gpu_adaptive.py): tile t of the adaptive image equals, bit for bit, tile t of rtw_render_* with spp =
+ * min(S, C_t*s), n_chunks = C_t; image and C_t are identical in every mix of RTW_FLAG_GROUP_CULL, RTW_FLAG_SCAN_VALU and job_pixels;
+ * REFINEMENT is exact: continuing an adaptive accumulator with a tolerance <= the previous one, all else equal, gives the words and C_t
+ * of a fresh run at the new tolerance (a tile that passes the tighter test passed the looser one no later).
+ *
+ * rtw_render_adaptive_*: `p` describes the whole render as for rtw_render_accum_*.  The call runs the whole loop -- a pass over the chunks
+ * [0, min_chunks) of all tiles, a check, a pass over the tiles still active, ... until no tile is active or the chunks run out -- and is
+ * BLOCKING: it returns when the image is complete (each round reads the number of active tiles back: one 4-byte copy).  d_out != NULL
+ * (device memory, layout of rtw_render_device_*, p->gamma) receives the final image, each pixel divided by the samples its tile holds.
+ * rtw_stats() afterwards reports the sums over all rounds (kernel_ms: the sum of the passes' kernels).  The accumulator must be unbound,
+ * or an adaptive accumulator of the same render with the same dark_floor, min_chunks and check_chunks and a `tolerance` <= its last one:
+ * that is refinement.  rtw_accum_resolve_*, rtw_accum_read_pixels, rtw_accum_info and rtw_accum_ranges work on an adaptive accumulator:
+ * resolve divides per tile; chunks_done, samples_done and the range report the LEAST sampled tile; complete = no tile is active under
+ * the last tolerance.  rtw_accum_reset clears the adaptive state with everything else.
+ *   Refusals, all decided before any HIP call, the accumulator untouched: a null scene / cam / p / adaptive / accumulator -> -1;
+ * tolerance not finite or <= 0, dark_floor not finite or < 0, min_chunks or check_chunks odd or < 0 -> -2; the whole-frame, one-device
+ * restrictions of rtw_render_accum_* -> -2; an accumulator bound by plain passes, by another render or other dark_floor / min_chunks /
+ * check_chunks, or a looser tolerance than its last -> -4.  rtw_render_accum_*, rtw_accum_merge (either side) and rtw_accum_export on
+ * an adaptive accumulator -> -2: per-tile chunk ranges in passes, merges and blobs are out of scope.
+ *   rtw_accum_adaptive_info: the state of an adaptive accumulator (-2 for any other).  rtw_accum_tile_chunks: *count receives the number
+ * of tiles, at most `capacity` values C_t are written to `chunks` in tile order (an accumulator that is not adaptive reports its
+ * chunks_done for every tile when its ranges are one prefix [0, C), else -2).  Additive to ABI 4: detected by symbol lookup. */
+typedef struct {
+    double tolerance;       /* > 0; smaller = more samples                                                      */
+    double dark_floor;      /* >= 0; radiance per sample and pixel (R + G + B) below which a tile counts as that bright */
+    int32_t min_chunks;     /* first checkpoint: even, 0 = default                                                */
+    int32_t check_chunks;   /* distance of the checkpoints: even, 0 = default                                     */
+    int32_t reserved[2];    /* 0                                                                                  */
+} rtw_adaptive_t;
+typedef struct {
+    int32_t n_tiles;          /* tiles of the frame                                                               */
+    int32_t tiles_converged;  /* tiles that stopped by the rule (C_t < N)                                         */
+    int32_t tiles_at_cap;     /* tiles that hold all N chunks                                                     */
+    int32_t rounds;           /* passes of the last call                                                          */
+    int32_t min_chunks_held;  /* min C_t                                                                          */
+    int32_t max_chunks_held;  /* max C_t                                                                          */
+    uint64_t samples;         /* sum over the tiles of valid pixels x min(S, C_t*s): every sample in the accumulator */
+    double tolerance;         /* of the last call                                                                 */
+} rtw_adaptive_info_t;
+int rtw_render_adaptive_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_adaptive_t *adaptive,
+                            rtw_accum_handle a, void *d_out, void *hip_stream);
+int rtw_render_adaptive_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_adaptive_t *adaptive,
+                            rtw_accum_handle a, void *d_out, void *hip_stream);
+int rtw_accum_adaptive_info(rtw_accum_handle a, rtw_adaptive_info_t *out);
+int rtw_accum_tile_chunks(rtw_accum_handle a, int32_t capacity, int32_t *count, int32_t *chunks);
 
 /* Counters/timings of the last render issued from this thread (waits for it to finish). */
 int rtw_stats(rtw_stats_t *out);

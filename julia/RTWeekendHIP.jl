@@ -244,4 +244,79 @@ function render_progressive(scene::HittableList, cam::Camera{T}, image_width=400
     img
 end
 
+struct CAdaptive
+    tolerance::Float64; dark_floor::Float64
+    min_chunks::Int32; check_chunks::Int32
+    reserved::NTuple{2,Int32}
+end
+
+"""
+    render_adaptive(scene, cam, image_width=400, n_samples=1; tolerance, dark_floor=0.03, min_chunks=0, check_chunks=0, depth=16, seed=1, n_chunks=0, device=-1, numerics=:reference, group_cull=false, scan_valu=false)
+
+Adaptive sampling (rtw_render_adaptive_f32/_f64): at most `n_samples` samples per pixel; every 8x8 tile stops at the first checkpoint at
+which it is converged under `tolerance` (roughly 0.8 x the tile's relative standard error; the exact rule is in include/rtw_hip.h).
+Returns `(img, tile_chunks)`: the `Matrix{RGB{T}}`, each pixel divided by the samples its tile holds, and the `tiles_i x tiles_j` matrix
+of the chunk counts C_t -- tile (ti, tj) of `img` is bit-identical to `render(...; n_chunks=C_t)` with `min(n_samples, C_t * chunk size)`
+samples.  `dark_floor` (default 0.03 = 1 % of white: a choice, not a measurement) keeps near-black tiles from never stopping.
+(Not executed in this repository: there is no `julia` in its build image; tests/test_gpu_adaptive.py drives the same entry points.)
+"""
+function render_adaptive(scene::HittableList, cam::Camera{T}, image_width=400, n_samples=1;
+                         tolerance, dark_floor=0.03, min_chunks=0, check_chunks=0, depth=16, seed=1, n_chunks=0, device=-1,
+                         numerics=:reference, group_cull=false, scan_valu=false) where T <: Union{Float32,Float64}
+    n_samples >= 1 || throw(ArgumentError("n_samples must be >= 1"))
+    numerics in (:reference, :contract, :reference_fma2) || throw(ArgumentError("numerics must be :reference, :contract or :reference_fma2"))
+    nflags = numerics === :contract ? 32 : numerics === :reference_fma2 ? 128 : 0
+    image_height = image_width ÷ (16//9)
+    n = length(scene)
+    cx = Vector{T}(undef, n); cy = similar(cx); cz = similar(cx); r = similar(cx)
+    ar = similar(cx); ag = similar(cx); ab = similar(cx); param = similar(cx)
+    kind = Vector{Int32}(undef, n)
+    for (i, h) in enumerate(scene)
+        h isa Sphere{T} || throw(ArgumentError("scene[$i] is $(typeof(h)); the HIP path takes Sphere{$T} only"))
+        cx[i], cy[i], cz[i] = h.center
+        r[i] = h.radius
+        kind[i] = matkind(h.mat)
+        ar[i], ag[i], ab[i] = albedo(h.mat)
+        param[i] = matparam(h.mat)
+    end
+    img = Matrix{RGB{T}}(undef, image_height, image_width)
+    tiles_i, tiles_j = cld(image_height, 8), cld(image_width, 8)
+    chunks = Matrix{Int32}(undef, tiles_i, tiles_j)             # column-major like the tile numbering t = tj * tiles_i + ti
+    ccam = Ref(CCamera(cam))
+    check(rc) = rc == 0 || error("librtw_hip: error $rc: $(last_error())")
+    hscene = Ref{Ptr{Cvoid}}(C_NULL)
+    hacc = Ref{Ptr{Cvoid}}(C_NULL)
+    GC.@preserve cx cy cz r kind ar ag ab param img chunks begin
+        cscene = Ref(CScene{T}(n, pointer(cx), pointer(cy), pointer(cz), pointer(r), pointer(kind),
+                               pointer(ar), pointer(ag), pointer(ab), pointer(param)))
+        params = Ref(CParams(image_width, image_height, n_samples, depth, seed, n_chunks, 0, 1, -1, 1,
+                             (group_cull ? 1 : 0) | (scan_valu ? 4 : 0) | nflags, 0, 0, Ptr{Int32}(C_NULL)))
+        adaptive = Ref(CAdaptive(tolerance, dark_floor, min_chunks, check_chunks, (Int32(0), Int32(0))))
+        out = pointer(reinterpret(T, vec(img)))
+        try
+            if T === Float32
+                check(ccall((:rtw_scene_upload_f32, LIB), Cint, (Ref{CScene{Float32}}, Cint, Ref{Ptr{Cvoid}}), cscene, device, hscene))
+            else
+                check(ccall((:rtw_scene_upload_f64, LIB), Cint, (Ref{CScene{Float64}}, Cint, Ref{Ptr{Cvoid}}), cscene, device, hscene))
+            end
+            check(ccall((:rtw_accum_create, LIB), Cint, (Cint, Int32, Int32, Ref{Ptr{Cvoid}}), device, image_width, image_height, hacc))
+            if T === Float32
+                check(ccall((:rtw_render_adaptive_f32, LIB), Cint, (Ptr{Cvoid}, Ref{CCamera{Float32}}, Ref{CParams}, Ref{CAdaptive}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                            hscene[], ccam, params, adaptive, hacc[], C_NULL, C_NULL))
+                check(ccall((:rtw_accum_resolve_host_f32, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float32}), hacc[], 1, out))
+            else
+                check(ccall((:rtw_render_adaptive_f64, LIB), Cint, (Ptr{Cvoid}, Ref{CCamera{Float64}}, Ref{CParams}, Ref{CAdaptive}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                            hscene[], ccam, params, adaptive, hacc[], C_NULL, C_NULL))
+                check(ccall((:rtw_accum_resolve_host_f64, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), hacc[], 1, out))
+            end
+            count = Ref{Int32}(0)
+            check(ccall((:rtw_accum_tile_chunks, LIB), Cint, (Ptr{Cvoid}, Int32, Ref{Int32}, Ptr{Int32}), hacc[], length(chunks), count, pointer(chunks)))
+        finally
+            ccall((:rtw_accum_free, LIB), Cint, (Ptr{Cvoid},), hacc[])        # (NULL handles are accepted)
+            ccall((:rtw_scene_free, LIB), Cint, (Ptr{Cvoid},), hscene[])
+        end
+    end
+    img, chunks
+end
+
 end # module

@@ -21,6 +21,7 @@ from .scenes import (  # noqa: F401
 )
 from .render import DeviceRenderer, render, render_batch, last_stats  # noqa: F401
 from .progressive import ProgressiveRenderer, render_progressive, samples_in_chunks  # noqa: F401
+from .adaptive import AdaptiveRenderer, reference_decisions, render_adaptive  # noqa: F401
 from .shard import compact_elems, compact_to_frame_index, local_tile_count, owned_pixel_mask, render_sharded  # noqa: F401
 from . import imageio  # noqa: F401
 
@@ -30,6 +31,7 @@ __all__ = [
     "default_camera", "flatten_scene", "image_height",
     "scene_2_spheres", "scene_4_spheres", "scene_blue_red_spheres", "scene_diel_spheres",
     "scene_random_spheres", "t_cam1", "t_cam2", "t_default_cam",
-    "DeviceRenderer", "render", "render_batch", "last_stats", "ProgressiveRenderer", "render_progressive", "samples_in_chunks", "owned_pixel_mask", "render_sharded", "compact_elems",
+    "DeviceRenderer", "render", "render_batch", "last_stats", "ProgressiveRenderer", "render_progressive", "samples_in_chunks",
+    "AdaptiveRenderer", "render_adaptive", "reference_decisions", "owned_pixel_mask", "render_sharded", "compact_elems",
     "compact_to_frame_index", "local_tile_count",
 ]

@@ -16,6 +16,7 @@ SYMBOLS = [
     "rtw_accum_create", "rtw_accum_reset", "rtw_accum_free", "rtw_render_accum_f32", "rtw_render_accum_f64",
     "rtw_accum_resolve_f32", "rtw_accum_resolve_f64", "rtw_accum_resolve_host_f32", "rtw_accum_resolve_host_f64",
     "rtw_accum_merge", "rtw_accum_info", "rtw_accum_ranges", "rtw_accum_read_pixels", "rtw_accum_export", "rtw_accum_import",
+    "rtw_render_adaptive_f32", "rtw_render_adaptive_f64", "rtw_accum_adaptive_info", "rtw_accum_tile_chunks",
 ]
 
 
@@ -53,6 +54,18 @@ class Stats(C.Structure):
 class AccumInfo(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("width", "height", "device", "bound", "precision", "spp", "chunk_spp", "n_chunks", "max_depth",
                                           "numerics_flags", "chunks_done", "samples_done", "complete")] + [("seed", C.c_uint64)]
+
+
+class Adaptive(C.Structure):
+    """rtw_adaptive_t"""
+    _fields_ = [("tolerance", C.c_double), ("dark_floor", C.c_double), ("min_chunks", C.c_int32), ("check_chunks", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+class AdaptiveInfo(C.Structure):
+    """rtw_adaptive_info_t"""
+    _fields_ = [(k, C.c_int32) for k in ("n_tiles", "tiles_converged", "tiles_at_cap", "rounds", "min_chunks_held", "max_chunks_held")] + \
+               [("samples", C.c_uint64), ("tolerance", C.c_double)]
 
 
 _lib = None
@@ -93,6 +106,10 @@ def lib():
                                               C.c_void_p, C.c_void_p]
     for name, CamT in (("rtw_render_accum_f32", CameraF32), ("rtw_render_accum_f64", CameraF64)):
         getattr(L, name).argtypes = [C.c_void_p, C.POINTER(CamT), C.POINTER(Params), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    for name, CamT in (("rtw_render_adaptive_f32", CameraF32), ("rtw_render_adaptive_f64", CameraF64)):
+        getattr(L, name).argtypes = [C.c_void_p, C.POINTER(CamT), C.POINTER(Params), C.POINTER(Adaptive), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rtw_accum_adaptive_info.argtypes = [C.c_void_p, C.POINTER(AdaptiveInfo)]
+    L.rtw_accum_tile_chunks.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rtw_accum_create.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
     L.rtw_accum_reset.argtypes = [C.c_void_p, C.c_void_p]
     L.rtw_accum_free.argtypes = [C.c_void_p]

@@ -1,5 +1,6 @@
 // rtw_accum.hip -- progressive render (include/rtw_hip.h rtw_accum_*, rtw_render_accum_*): the accumulator object, the checks of a
-// pass, the merge and resolve kernels, and the export / import blob.
+// pass, the merge and resolve kernels, the export / import blob, and the adaptive render (rtw_render_adaptive_*): the tile kernels that
+// evaluate the stopping rule from the accumulator words and the host loop of passes over the tiles still active.
 //
 // An accumulator is W x H pixels x 8 uint64 in HBM (the job slot's own layout, rtw_kernels.hpp AccumArgs) plus, on the host, the render it
 // is bound to and the chunk ranges it already holds.  Every sample is a signed 64.64 integer and integer addition is associative, so ANY
@@ -25,6 +26,14 @@ struct rtw_accum {
     bool bound = false;
     AccumBind bind;
     std::vector<std::pair<int32_t, int32_t>> ranges;    // chunk ranges [begin, end) already added: sorted, disjoint, coalesced
+                                                        // (adaptive: the one prefix [0, min C_t) -- what the least sampled tile holds)
+    // ---- adaptive accumulators (rtw_render_adaptive_*): tile t holds the chunks [0, C_t) ----
+    bool adaptive = false;
+    bool ad_complete = false;                      // no tile is active under ad.tolerance (false only after a call that failed half way)
+    rtw_adaptive_t ad;                             // the last call's, min_chunks / check_chunks as their effective values
+    int32_t ad_rounds = 0;                         // passes of the last call
+    int32_t *d_tiles = nullptr;                    // device memory, 3 n_tiles + 4 int32: C_t | active flags | active list | count (made by the first adaptive call)
+    std::vector<int32_t> tile_chunks;              // host copy of C_t, read back at the end of every call
 };
 
 namespace rtwh {
@@ -59,6 +68,91 @@ __global__ __launch_bounds__(256) void accum_resolve_kernel(const unsigned long 
     if (k >= n_elems) return;
     const size_t pix = k / 3u;
     const unsigned ch = (unsigned)(k - pix * 3u);
+    const unsigned long long *a = words + pix * 8u;
+    double v = rtw::fx_to_double(a[2 * ch], a[2 * ch + 1]);
+    if (a[6] != 0ull) v = __builtin_nan("");
+    v = v / (double)samples;
+    if (gamma) v = __builtin_sqrt(v);
+    out[k] = (T)v;
+}
+
+// ---- adaptive render: the tile kernels (plain vector loads, stores and shuffles; tiles are numbered t = tj * tiles_i + ti) ----
+// The stopping rule of include/rtw_hip.h at checkpoint `c`, one wave per tile, lane = the pixel (i mod 8) + 8 (j mod 8): flags[t] = 1 for
+// a tile that holds exactly c chunks and is NOT converged (it stays active), 0 for every other tile.  D and Y are summed sequentially in
+// lane order by every lane (64 shuffles each): the written rule's own order, so the result does not depend on how a reduction would
+// associate.  n = (double)(c * chunk_spp).  (-ffp-contract=off: no FMA anywhere in this library unless the source writes one.)
+__global__ __launch_bounds__(256) void accum_tile_check_kernel(const unsigned long long *__restrict__ words, const int *__restrict__ chunks, int *__restrict__ flags,
+                                                               int n_tiles, int tiles_i, int width, int height, int c, double n, double tol, double floor) {
+    const unsigned lane = threadIdx.x & 63u;
+    const int t = (int)(blockIdx.x * 4u + (threadIdx.x >> 6));
+    if (t >= n_tiles) return;                         // (whole waves: no barrier below)
+    if (chunks[t] != c) { if (lane == 0) flags[t] = 0; return; }
+    const int tj = t / tiles_i, ti = t - tj * tiles_i;
+    const int i = ti * 8 + (int)(lane & 7u), j = tj * 8 + (int)(lane >> 3);
+    const bool valid = i < height && j < width;
+    double d = 0.0, y = 0.0;
+    if (valid) {
+        const unsigned long long *a = words + ((size_t)j * (size_t)height + (size_t)i) * 8u;
+        if (a[6] == 0ull) {
+            const long long h = (long long)a[7];
+            const unsigned long long m = h < 0 ? 0ull - (unsigned long long)h : (unsigned long long)h;
+            d = (double)m * 0x1p-24;                  // (exact scaling)
+            y = (rtw::fx_to_double(a[0], a[1]) + rtw::fx_to_double(a[2], a[3])) + rtw::fx_to_double(a[4], a[5]);
+            y = y > 0.0 ? y : 0.0;
+        }
+    }
+    const double npix = (double)__popcll(__ballot(valid));
+    double D = 0.0, Y = 0.0;
+    for (int k = 0; k < 64; ++k) { D = D + __shfl(d, k); Y = Y + __shfl(y, k); }
+    const double dark = (floor * n) * npix;
+    const double M = Y > dark ? Y : dark;
+    if (lane == 0) flags[t] = D <= tol * M ? 0 : 1;
+}
+
+// flags -> the SORTED list of the active tiles + its length, one workgroup: ascending tile numbers keep what the sharded path's queues
+// give a shard -- consecutive list entries are neighbours in the frame, local tile k goes to die k mod 8, and a die works through its
+// part of the list in frame order -- and make the list, like everything else here, the same from run to run (an atomic append would
+// finish a few microseconds sooner and order the list by arrival).
+__global__ __launch_bounds__(1024) void accum_tile_compact_kernel(const int *__restrict__ flags, int *__restrict__ list, int *__restrict__ count, int n_tiles) {
+    __shared__ int wave_n[16];
+    __shared__ int base;
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) base = 0;
+    __syncthreads();
+    for (int t0 = 0; t0 < n_tiles; t0 += 1024) {
+        const int t = t0 + (int)threadIdx.x;
+        const bool f = t < n_tiles && flags[t] != 0;
+        const unsigned long long m = __ballot(f);
+        if (lane == 0) wave_n[wave] = (int)__popcll(m);
+        __syncthreads();
+        int off = base;
+        for (unsigned k = 0; k < wave; ++k) off += wave_n[k];
+        if (f) list[off + (int)__popcll(m & ((1ull << lane) - 1ull))] = t;
+        __syncthreads();
+        if (threadIdx.x == 0) { int n = 0; for (int k = 0; k < 16; ++k) n += wave_n[k]; base += n; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *count = base;
+}
+
+// after a pass of `add` chunks: C_t += add for the tiles of the list (list == null: for all n tiles)
+__global__ __launch_bounds__(256) void accum_tile_advance_kernel(const int *__restrict__ list, int n, int *__restrict__ chunks, int add) {
+    const int k = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (k >= n) return;
+    chunks[list ? list[k] : k] += add;
+}
+
+// accum_resolve_kernel for an adaptive accumulator: a pixel is divided by the samples ITS TILE holds, min(spp, C_t * chunk_spp)
+template <typename T>
+__global__ __launch_bounds__(256) void accum_resolve_tiles_kernel(const unsigned long long *__restrict__ words, T *__restrict__ out, size_t n_elems, const int *__restrict__ chunks,
+                                                                  int height, int tiles_i, int spp, int chunk_spp, int gamma) {
+    const size_t k = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (k >= n_elems) return;
+    const size_t pix = k / 3u;
+    const unsigned ch = (unsigned)(k - pix * 3u);
+    const size_t j = pix / (size_t)height, i = pix - j * (size_t)height;
+    const long long held = (long long)chunks[(j >> 3) * (size_t)tiles_i + (i >> 3)] * chunk_spp;
+    const int samples = held < spp ? (int)held : spp;
     const unsigned long long *a = words + pix * 8u;
     double v = rtw::fx_to_double(a[2 * ch], a[2 * ch + 1]);
     if (a[6] != 0ull) v = __builtin_nan("");
@@ -157,6 +251,10 @@ int resolve_dev(rtw_accum *a, int32_t gamma, void *d_out, hipStream_t stream) {
     if (int rc = wait_for(a, stream)) return rc;
     const size_t n = n_pixels(a) * 3u;
     (void)hipGetLastError();
+    if (a->adaptive)
+        hipLaunchKernelGGL(accum_resolve_tiles_kernel<T>, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, a->words, (T *)d_out, n, a->d_tiles, (int)a->height,
+                           (int)((a->height + 7) / 8), (int)a->bind.spp, (int)a->bind.chunk_spp, (int)gamma);
+    else
     hipLaunchKernelGGL(accum_resolve_kernel<T>, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, a->words, (T *)d_out, n, (int)s, (int)gamma);
     HIP_TRY(hipGetLastError());
     return mark(a, stream);
@@ -178,10 +276,8 @@ int resolve_host(rtw_accum *a, int32_t gamma, T *out) {
 
 // Everything about a pass that is decided without a device, in the header's order: nulls, the render's own checks, whole frames on one
 // device, the chunk range; then the handles (precision, size, device), the binding, the overlap.  On success *nch / *cs: the effective chunks.
-template <typename CamT>
-int validate_accum(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, rtw_accum_handle a, int *nch_out, int *cs_out) {
-    if (!p) return fail(-1, "null params");
-    if (!cam || !a || !scene) return fail(-1, "null argument");
+// (validate_frame: the render's own checks and whole frames on one device; validate_handles: precision, size, device)
+int validate_frame(const rtw_params *p, int *nch_out, int *cs_out) {
     int nch, cs;
     if (int rc = validate_params(p, &nch, &cs)) return rc;
     if (p->shard_count != 1) return fail(-2, "a progressive render renders whole frames (shard_count = %d)", p->shard_count);
@@ -190,13 +286,27 @@ int validate_accum(rtw_scene_handle scene, const CamT *cam, const rtw_params *p,
     if (p->flags & RTW_FLAG_RAY_POOL) return fail(-2, "a progressive render runs the lane-loop kernel (RTW_FLAG_RAY_POOL)");
     if (p->n_devices > 1 || p->n_devices < 0 || p->device_ids)
         return fail(-2, "a progressive render runs on one device (n_devices = %d%s)", p->n_devices, p->device_ids ? ", device_ids given" : "");
-    if (chunk_begin < 0 || chunk_count < 1 || (long long)chunk_begin + chunk_count > nch)
-        return fail(-2, "chunk range [%d, %lld) is not inside the render's %d chunks", chunk_begin, (long long)chunk_begin + chunk_count, nch);
-    if (scene->is_f64 != (sizeof(CamT) == sizeof(rtw_camera_f64))) return fail(-4, "scene handle precision does not match the call");
+    *nch_out = nch; *cs_out = cs;
+    return 0;
+}
+int validate_handles(bool call_f64, rtw_scene_handle scene, const rtw_params *p, rtw_accum_handle a) {
+    if (scene->is_f64 != call_f64) return fail(-4, "scene handle precision does not match the call");
     if (a->width != p->width || a->height != p->height)
         return fail(-4, "the accumulator is %d x %d, the render %d x %d", a->width, a->height, p->width, p->height);
     if (a->device != scene->device) return fail(-4, "accumulator on device %d, scene on device %d", a->device, scene->device);
     if (p->device >= 0 && p->device != scene->device) return fail(-4, "params.device %d != scene device %d", p->device, scene->device);
+    return 0;
+}
+template <typename CamT>
+int validate_accum(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, rtw_accum_handle a, int *nch_out, int *cs_out) {
+    if (!p) return fail(-1, "null params");
+    if (!cam || !a || !scene) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = validate_frame(p, &nch, &cs)) return rc;
+    if (chunk_begin < 0 || chunk_count < 1 || (long long)chunk_begin + chunk_count > nch)
+        return fail(-2, "chunk range [%d, %lld) is not inside the render's %d chunks", chunk_begin, (long long)chunk_begin + chunk_count, nch);
+    if (int rc = validate_handles(sizeof(CamT) == sizeof(rtw_camera_f64), scene, p, a)) return rc;
+    if (a->adaptive) return fail(-2, "the accumulator is adaptive (its tiles hold different chunk counts): rtw_render_adaptive_* continues it, rtw_accum_reset() makes it a plain one");
     if (a->bound) {
         AccumBind b;
         make_bind(&b, scene, cam, p, nch, cs);
@@ -232,6 +342,165 @@ int render_accum(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, i
     return mark(a, stream);
 }
 
+// ---- adaptive render ----
+int n_tiles_of(const rtw_accum *a) { return ((a->height + 7) / 8) * ((a->width + 7) / 8); }
+int default_check_chunks(int nch) { int m = std::max(16, (nch + 7) / 8); return m + (m & 1); }      // the smallest even number >= max(16, N / 8)
+
+// everything about an adaptive call that is decided without a device: nulls, the render, whole frames on one device, the adaptive
+// parameters; then the handles and the binding.  *eff: the parameters with min_chunks / check_chunks as their effective values.
+template <typename CamT>
+int validate_adaptive(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, const rtw_adaptive_t *ad, rtw_accum_handle a, int *nch_out, int *cs_out, rtw_adaptive_t *eff) {
+    if (!p) return fail(-1, "null params");
+    if (!cam || !a || !scene || !ad) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = validate_frame(p, &nch, &cs)) return rc;
+    if (!std::isfinite(ad->tolerance) || !(ad->tolerance > 0.0)) return fail(-2, "tolerance must be finite and > 0 (got %g)", ad->tolerance);
+    if (!std::isfinite(ad->dark_floor) || ad->dark_floor < 0.0) return fail(-2, "dark_floor must be finite and >= 0 (got %g)", ad->dark_floor);
+    if (ad->min_chunks < 0 || (ad->min_chunks & 1)) return fail(-2, "min_chunks must be even and >= 2, or 0 for the default (got %d)", ad->min_chunks);
+    if (ad->check_chunks < 0 || (ad->check_chunks & 1)) return fail(-2, "check_chunks must be even and >= 2, or 0 for the default (got %d)", ad->check_chunks);
+    if (int rc = validate_handles(sizeof(CamT) == sizeof(rtw_camera_f64), scene, p, a)) return rc;
+    memset(eff, 0, sizeof *eff);
+    eff->tolerance = ad->tolerance; eff->dark_floor = ad->dark_floor;
+    eff->min_chunks = ad->min_chunks ? ad->min_chunks : default_check_chunks(nch);
+    eff->check_chunks = ad->check_chunks ? ad->check_chunks : default_check_chunks(nch);
+    if (a->bound) {
+        if (!a->adaptive) return fail(-4, "the accumulator is bound by plain passes (rtw_render_accum_* / merge / import); rtw_accum_reset() unbinds it");
+        AccumBind b;
+        make_bind(&b, scene, cam, p, nch, cs);
+        if (!same_render(a->bind, b)) return fail(-4, "the accumulator is bound to another render (size, precision, seed, spp, chunks, depth, numerics, camera or scene differ); rtw_accum_reset() unbinds it");
+        if (a->ad.dark_floor != eff->dark_floor || a->ad.min_chunks != eff->min_chunks || a->ad.check_chunks != eff->check_chunks)
+            return fail(-4, "the accumulator's adaptive render has dark_floor %g, min_chunks %d, check_chunks %d: a refinement keeps them", a->ad.dark_floor, a->ad.min_chunks, a->ad.check_chunks);
+        if (eff->tolerance > a->ad.tolerance)
+            return fail(-4, "tolerance %g is looser than the accumulator's last (%g): refinement only tightens", eff->tolerance, a->ad.tolerance);
+    }
+    *nch_out = nch; *cs_out = cs;
+    return 0;
+}
+
+// The loop: [0, min_chunks) on all tiles, then per checkpoint c: check the tiles that hold exactly c chunks, list the ones not converged,
+// read the list's length back (the round's one host wait), render [c, c + check_chunks) for the list.  A refinement walks the same
+// checkpoints: a tile that stopped at c under the looser tolerance is looked at again at c, where a fresh run would have decided it.
+template <typename CamT>
+int render_adaptive(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, const rtw_adaptive_t *ad, rtw_accum_handle a, void *d_out, void *stream_v) {
+    using T = typename std::conditional<sizeof(CamT) == sizeof(rtw_camera_f64), double, float>::type;
+    int nch, cs;
+    rtw_adaptive_t eff;
+    if (int rc = validate_adaptive(scene, cam, p, ad, a, &nch, &cs, &eff)) return rc;
+    AccumBind b;
+    make_bind(&b, scene, cam, p, nch, cs);
+    DeviceGuard guard;
+    hipStream_t stream = (hipStream_t)stream_v;
+    HIP_TRY(hipSetDevice(a->device));
+    const int n_tiles = n_tiles_of(a), tiles_i = (a->height + 7) / 8;
+    if (!a->d_tiles) HIP_TRY(hipMalloc((void **)&a->d_tiles, ((size_t)n_tiles * 3u + 4u) * sizeof(int32_t)));
+    int32_t *d_chunks = a->d_tiles, *d_flags = d_chunks + n_tiles, *d_list = d_flags + n_tiles, *d_count = d_list + n_tiles;
+    if (int rc = wait_for(a, stream)) return rc;
+    const bool fresh = !a->bound;
+    const bool settled = !fresh && a->ad_complete && eff.tolerance == a->ad.tolerance;     // (the same tolerance again: nothing to decide)
+    int later_max = 0;                       // refinement: the last checkpoint some tile stopped at
+    if (!fresh) for (int32_t c : a->tile_chunks) if (c < nch) later_max = std::max(later_max, (int)c);
+    if (fresh) HIP_TRY(hipMemsetAsync(d_chunks, 0, (size_t)n_tiles * sizeof(int32_t), stream));
+
+    release_last();
+    rtw_stats_t agg;
+    memset(&agg, 0, sizeof agg);
+    RenderRec *rec = nullptr;
+    CtxPtr ctx;
+    int rounds = 0;
+    // one pass: launch, C_t += count; the caller synchronises the stream before `finish` reads the pass's counters
+    auto pass = [&](int begin, int count, const int32_t *list, int n_list) -> int {
+        AccumPass ps;
+        ps.words = a->words; ps.chunk_begin = begin; ps.chunk_count = count; ps.samples = 1;      // (no running image: the divisor is unused)
+        ps.adapt = true; ps.tile_list = list; ps.list_tiles = n_list;
+        int rc = launch_accum_t(scene, cam, p, ps, nullptr, stream, &rec, &ctx);
+        if (rc) { if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); rec = nullptr; } return rc; }     // (released by the next call)
+        (void)hipGetLastError();
+        hipLaunchKernelGGL(accum_tile_advance_kernel, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, stream, list, n_list, d_chunks, count);
+        HIP_TRY(hipGetLastError());
+        ++rounds;
+        return 0;
+    };
+    auto finish = [&]() -> int {              // (behind a stream synchronisation) the last pass's counters -> agg; its record goes back to the pool
+        if (!rec) return 0;
+        rtw_stats_t one;
+        memset(&one, 0, sizeof one);
+        int rc = resolve_rec(rec, &one);
+        release_rec(ctx, rec, rc == 0);
+        rec = nullptr;
+        if (rc) return rc;
+        agg.samples += one.samples; agg.segments += one.segments; agg.sphere_tests += one.sphere_tests;
+        agg.kernel_ms += one.kernel_ms; agg.total_ms += one.total_ms;
+        agg.grid_blocks = std::max(agg.grid_blocks, one.grid_blocks); agg.block_threads = std::max(agg.block_threads, one.block_threads);
+        return 0;
+    };
+    auto run = [&]() -> int {
+        const int first = std::min((int)eff.min_chunks, nch);
+        int moved = 0;                          // tiles the last pass brought to the checkpoint at hand
+        if (fresh) {
+            if (int rc = pass(0, first, nullptr, n_tiles)) return rc;
+            a->bind = b; a->bound = true; a->adaptive = true; a->ad = eff; a->ad_complete = false;
+            moved = n_tiles;
+        }
+        a->ad.tolerance = eff.tolerance;
+        a->ad_complete = false;
+        for (int c = first; c < nch && !settled; c += eff.check_chunks) {
+            if (moved == 0 && c > later_max) break;
+            (void)hipGetLastError();
+            hipLaunchKernelGGL(accum_tile_check_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, stream, a->words, d_chunks, d_flags, n_tiles, tiles_i,
+                               (int)a->width, (int)a->height, c, (double)((long long)c * cs), eff.tolerance, eff.dark_floor);
+            hipLaunchKernelGGL(accum_tile_compact_kernel, dim3(1), dim3(1024), 0, stream, d_flags, d_list, d_count, n_tiles);
+            HIP_TRY(hipGetLastError());
+            int32_t n_active = 0;
+            HIP_TRY(hipMemcpyAsync(&n_active, d_count, sizeof n_active, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (int rc = finish()) return rc;
+            if (n_active < 0 || n_active > n_tiles) return fail(-3, "adaptive render: %d active tiles of %d", n_active, n_tiles);
+            moved = n_active;
+            if (n_active == 0) continue;
+            if (int rc = pass(c, std::min((int)eff.check_chunks, nch - c), d_list, n_active)) return rc;
+        }
+        a->tile_chunks.resize((size_t)n_tiles);
+        HIP_TRY(hipMemcpyAsync(a->tile_chunks.data(), d_chunks, (size_t)n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (int rc = finish()) return rc;
+        int min_c = nch;
+        for (int32_t c : a->tile_chunks) min_c = std::min(min_c, (int)c);
+        a->ranges.clear();
+        a->ranges.emplace_back(0, min_c);
+        a->ad_complete = true;
+        a->ad_rounds = rounds;
+        if (d_out) {
+            if (int rc = resolve_dev<T>(a, p->gamma, d_out, stream)) return rc;
+            HIP_TRY(hipStreamSynchronize(stream));
+        }
+        return 0;
+    };
+    const int rc = run();
+    if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); }       // (a failure between a pass and its wait)
+    if (rc) { if (a->bound) HIP_IGNORE(hipEventRecord(a->ev, stream)); return rc; }
+    agg.n_chunks = nch;
+    g_last.agg = agg;
+    g_last.resolved = true;
+    g_last.per_device.emplace_back(a->device, agg.kernel_ms);
+    return mark(a, stream);
+}
+
+int adaptive_info(const rtw_accum *a, rtw_adaptive_info_t *out) {
+    memset(out, 0, sizeof *out);
+    const int tiles_i = (a->height + 7) / 8, tiles_j = (a->width + 7) / 8, nch = a->bind.n_chunks;
+    out->n_tiles = tiles_i * tiles_j; out->rounds = a->ad_rounds; out->tolerance = a->ad.tolerance;
+    out->min_chunks_held = nch; out->max_chunks_held = 0;
+    for (int tj = 0; tj < tiles_j; ++tj)
+        for (int ti = 0; ti < tiles_i; ++ti) {
+            const int c = a->tile_chunks[(size_t)tj * (size_t)tiles_i + (size_t)ti];
+            const long long npix = (long long)std::min(8, a->height - 8 * ti) * std::min(8, a->width - 8 * tj);
+            out->samples += (uint64_t)(npix * samples_in(a->bind, 0, c));
+            if (c < nch) ++out->tiles_converged; else ++out->tiles_at_cap;
+            out->min_chunks_held = std::min(out->min_chunks_held, c); out->max_chunks_held = std::max(out->max_chunks_held, c);
+        }
+    return 0;
+}
+
 }  // namespace
 
 }  // namespace rtwh
@@ -257,6 +526,8 @@ int rtw_accum_reset(rtw_accum_handle a, void *stream_v) {
     a->bound = false;
     a->ranges.clear();
     memset(&a->bind, 0, sizeof a->bind);
+    a->adaptive = false; a->ad_complete = false; a->ad_rounds = 0; a->tile_chunks.clear();      // (the tile counts are zeroed by the next adaptive call)
+    memset(&a->ad, 0, sizeof a->ad);
     return mark(a, stream);
 }
 
@@ -266,6 +537,7 @@ int rtw_accum_free(rtw_accum_handle a) {
     HIP_IGNORE(hipSetDevice(a->device));
     if (a->ev) { HIP_IGNORE(hipEventSynchronize(a->ev)); HIP_IGNORE(hipEventDestroy(a->ev)); }
     if (a->words) HIP_IGNORE(hipFree(a->words));
+    if (a->d_tiles) HIP_IGNORE(hipFree(a->d_tiles));
     delete a;
     return 0;
 }
@@ -277,6 +549,32 @@ int rtw_render_accum_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, cons
 int rtw_render_accum_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count,
                          rtw_accum_handle a, void *d_out, void *stream) {
     return render_accum(scene, cam, p, chunk_begin, chunk_count, a, d_out, stream);
+}
+
+int rtw_render_adaptive_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_adaptive_t *adaptive,
+                            rtw_accum_handle a, void *d_out, void *stream) {
+    return render_adaptive(scene, cam, p, adaptive, a, d_out, stream);
+}
+int rtw_render_adaptive_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_adaptive_t *adaptive,
+                            rtw_accum_handle a, void *d_out, void *stream) {
+    return render_adaptive(scene, cam, p, adaptive, a, d_out, stream);
+}
+
+int rtw_accum_adaptive_info(rtw_accum_handle a, rtw_adaptive_info_t *out) {
+    if (!a || !out) return fail(-1, "null argument");
+    if (!a->adaptive || a->tile_chunks.empty()) return fail(-2, "the accumulator is not adaptive");
+    return adaptive_info(a, out);
+}
+
+int rtw_accum_tile_chunks(rtw_accum_handle a, int32_t capacity, int32_t *count, int32_t *chunks) {
+    if (!a || !count || capacity < 0 || (capacity > 0 && !chunks)) return fail(-1, "null argument");
+    const int n = n_tiles_of(a);
+    if (!a->adaptive && a->ranges.size() > 1) return fail(-2, "the accumulator's chunks are not one prefix: its tiles have no chunk count");
+    if (!a->adaptive && a->ranges.size() == 1 && a->ranges[0].first != 0) return fail(-2, "the accumulator's chunks are not one prefix: its tiles have no chunk count");
+    *count = n;
+    const int32_t uniform = a->ranges.empty() ? 0 : a->ranges[0].second;
+    for (int32_t k = 0; k < capacity && k < n; ++k) chunks[k] = a->adaptive && !a->tile_chunks.empty() ? a->tile_chunks[(size_t)k] : uniform;
+    return 0;
 }
 
 int rtw_accum_resolve_f32(rtw_accum_handle a, int32_t gamma, void *d_out, void *stream) {
@@ -295,6 +593,7 @@ int rtw_accum_resolve_host_f64(rtw_accum_handle a, int32_t gamma, double *out) {
 int rtw_accum_merge(rtw_accum_handle dst, rtw_accum_handle src, void *stream_v) {
     if (!dst || !src) return fail(-1, "null argument");
     if (dst == src) return fail(-2, "an accumulator cannot be merged into itself");
+    if (dst->adaptive || src->adaptive) return fail(-2, "adaptive accumulators (tiles with different chunk counts) cannot be merged");
     if (dst->width != src->width || dst->height != src->height)
         return fail(-4, "accumulators of different sizes (%d x %d, %d x %d)", dst->width, dst->height, src->width, src->height);
     if (dst->device != src->device)
@@ -332,7 +631,7 @@ int rtw_accum_info(rtw_accum_handle a, rtw_accum_info_t *out) {
         out->seed = b.seed; out->numerics_flags = b.numerics;
         out->chunks_done = chunks_done(a);
         out->samples_done = (int32_t)samples_done(a);
-        out->complete = out->chunks_done == b.n_chunks;
+        out->complete = a->adaptive ? (a->ad_complete ? 1 : 0) : out->chunks_done == b.n_chunks;
     }
     return 0;
 }
@@ -352,6 +651,7 @@ int rtw_accum_read_pixels(rtw_accum_handle a, uint64_t *host_words) {
 
 int rtw_accum_export(rtw_accum_handle a, void *buf, uint64_t capacity, uint64_t *size) {
     if (!a || !size) return fail(-1, "null argument");
+    if (a->adaptive) return fail(-2, "adaptive accumulators (tiles with different chunk counts) cannot be exported");
     const size_t head = sizeof(BlobHeader) + a->ranges.size() * 8u, total = head + n_pixels(a) * 64u;
     *size = total;
     if (!buf) return 0;                         // (a size query)

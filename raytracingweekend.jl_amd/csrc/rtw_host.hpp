@@ -204,8 +204,9 @@ inline int launch_batch_t(rtw_scene_handle s, const rtw_camera_f32 *c, int n, co
 inline int launch_batch_t(rtw_scene_handle s, const rtw_camera_f64 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_batch_f64(s, c, n, sd, p, d, st, r, x); }
 // ... one pass of a progressive render (rtw_accum.hip has validated it): the chunks [chunk_begin, chunk_begin + chunk_count) of the render
 // `p` describes are added to `words` (layout: include/rtw_hip.h rtw_accum_read_pixels); `samples` = the samples the accumulator holds
-// after this pass, the divisor of the running image written to `d_out` (null: none)
-struct AccumPass { unsigned long long *words; int chunk_begin, chunk_count, samples; };
+// after this pass, the divisor of the running image written to `d_out` (null: none).  `adapt`: a pass of an adaptive render (the ADAPT
+// kernels: half differences in word 7); `tile_list` non-null: only the `list_tiles` tiles of that device-resident list
+struct AccumPass { unsigned long long *words; int chunk_begin, chunk_count, samples; bool adapt = false; const int *tile_list = nullptr; int list_tiles = 0; };
 int launch_accum_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const AccumPass &pass, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
 int launch_accum_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const AccumPass &pass, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
 inline int launch_accum_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, const AccumPass &a, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_accum_f32(s, c, p, a, d, st, r, x); }

@@ -106,7 +106,13 @@ struct AccumArgs {
     unsigned long long *words;      // the accumulator
     int chunk_begin;                // global index of this pass's chunk 0: what the item's RNG stream and sample indices are made from
     int samples;                    // samples in the accumulator INCLUDING this pass: the divisor of the running image
+    const int *tile_list;           // ADAPT instances, KParams::shard_count == 0: local tile k is global tile tile_list[k] (local_tiles entries)
 };
+// Adaptive render (rtw_render_adaptive_*; the ADAPT instances of trace_kernel, all of them ACCUM instances): a pass renders its chunks
+// for the tiles of a device-resident list only (open_job), and every sample also adds its noise statistic to word 7 of the pixel's slot --
+// +q for a sample of an even GLOBAL chunk, -q for one of an odd chunk, q = min(fx >> 40, 2^30 - 1) per channel (fx_noise_q) -- so the
+// record's spare word ends up holding the pixel's half difference H_p (include/rtw_hip.h), an integer sum like the others: independent
+// of order, scan mode, job size and pass structure.
 struct JobCache { unsigned long long jc; unsigned jc_lock; unsigned queue_off; unsigned last_g; unsigned static_used; };       // see claim_job
 template <typename T> struct WgShared {
     unsigned char slots[RTW_SLOT_BYTES];      // n_slots x (128-byte JobSlot + 64 bytes per job pixel)
@@ -179,14 +185,29 @@ template <typename T> __host__ __device__ constexpr size_t mfma_cell_bytes() { r
 #define RTW_RARE_ATTR __forceinline__
 #endif
 
+// The noise statistic of one channel value in 64.64 fixed point (hi:lo as fx_from_double made it): min(fx >> 40, 2^30 - 1) -- units of
+// 2^-24, capped at 64 -- and 0 for a negative value.
+__device__ __forceinline__ unsigned long long fx_noise_q(unsigned long long lo, unsigned long long hi) {
+    if (hi >> 63) return 0ull;
+    return hi >= 64ull ? (1ull << 30) - 1ull : (hi << 24) | (lo >> 40);
+}
+// ADAPT: +-q into word 7 of the pixel's slot: ONE 64-bit LDS atomic per channel value (two's complement: adding 0 - q subtracts q)
+__device__ __forceinline__ void fx_noise_add(unsigned long long *a, unsigned long long lo, unsigned long long hi, bool odd) {
+    const unsigned long long q = fx_noise_q(lo, hi);
+    __hip_atomic_fetch_add(&a[7], odd ? 0ull - q : q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 // Exact accumulation of one sample's radiance into pixel `a` of a job slot.
-__device__ __forceinline__ void fx_accumulate(unsigned long long *a, double r, double g, double b) {
+// ADAPT: the sample's noise statistic goes to a[7] (`odd`: the parity of the item's global chunk).
+template <bool ADAPT = false>
+__device__ __forceinline__ void fx_accumulate(unsigned long long *a, double r, double g, double b, [[maybe_unused]] bool odd = false) {
     const double cs[3] = {r, g, b};
 #pragma unroll 1
     for (int c = 0; c < 3; ++c) {        // not unrolled: one channel's temporaries at a time
 
         unsigned long long lo, hi;
         if (fx_from_double(cs[c], lo, hi)) {
+            if constexpr (ADAPT) fx_noise_add(a, lo, hi, odd);
             const unsigned long long old = __hip_atomic_fetch_add(&a[2 * c], lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             hi += (old + lo < old) ? 1ull : 0ull;
             if (hi) __hip_atomic_fetch_add(&a[2 * c + 1], hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -197,9 +218,11 @@ __device__ __forceinline__ void fx_accumulate(unsigned long long *a, double r, d
 }
 
 // One channel of one sample: `acc` = the pixel's accumulators (a[2c], a[2c+1] per channel, a[6] = poison count).
-__device__ __forceinline__ void fx_accumulate_channel(unsigned long long *acc, unsigned c, double v) {
+template <bool ADAPT = false>
+__device__ __forceinline__ void fx_accumulate_channel(unsigned long long *acc, unsigned c, double v, [[maybe_unused]] bool odd = false) {
     unsigned long long lo, hi;
     if (fx_from_double(v, lo, hi)) {
+        if constexpr (ADAPT) fx_noise_add(acc, lo, hi, odd);
         const unsigned long long old = __hip_atomic_fetch_add(&acc[2 * c], lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         hi += (old + lo < old) ? 1ull : 0ull;
         if (hi) __hip_atomic_fetch_add(&acc[2 * c + 1], hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -231,7 +254,8 @@ __device__ RTW_RARE_ATTR void store_job(const KParams &P, const JobSlot *S, unsi
 // The end of a job of an ACCUM launch: lane = (pixel, channel) reads the channel's running 128-bit sum (one 16-byte load), adds the job's
 // sum with carry and writes it back; the poison count (word 6) is read by the pixel's three lanes and written by its channel-0 lane.  `out`
 // non-null: the running image, from the NEW totals -- store_job's formula with the divisor A.samples.
-template <typename T>
+// ADAPT: the record's fourth pair is {poison, H_old + H_job} (the job's half differences, word 7 of the slot) instead of {poison, 0}.
+template <typename T, bool ADAPT = false>
 __device__ RTW_RARE_ATTR void store_job_accum(const KParams &P, const JobSlot *S, unsigned lane, T *__restrict__ out, const AccumArgs &A) {
     const unsigned px = lane / 3u, ch = lane - 3u * px, rs = P.rows_shift;
     if (px < (1u << P.job_shift)) {
@@ -241,9 +265,16 @@ __device__ RTW_RARE_ATTR void store_job_accum(const KParams &P, const JobSlot *S
             const unsigned long long *a = S->acc(px);
             ulonglong2 *g = reinterpret_cast<ulonglong2 *>(A.words + pix * 8u);
             // (the poison count first, then the channel: fewer values alive at once)
-            const unsigned long long poison = reinterpret_cast<const unsigned long long *>(g)[6] + a[6];
+            unsigned long long poison;
+            if constexpr (ADAPT) {
+                const ulonglong2 pz = g[3];
+                poison = pz.x + a[6];
+                if (ch == 0u) g[3] = ulonglong2{poison, pz.y + a[7]};
+            } else {
+                poison = reinterpret_cast<const unsigned long long *>(g)[6] + a[6];
+                if (ch == 0u) g[3] = ulonglong2{poison, 0ull};
+            }
             const bool poisoned = poison != 0ull;
-            if (ch == 0u) g[3] = ulonglong2{poison, 0ull};
             const ulonglong2 old = g[ch];
             const unsigned long long lo = old.x + a[2 * ch];
             const unsigned long long hi = old.y + a[2 * ch + 1] + (lo < old.x ? 1ull : 0ull);
@@ -376,9 +407,11 @@ __device__ __forceinline__ int claim_job(const KParams &P, DevCounters *ctr, Job
 // S->job: the job's queue position, RTW_JOB_EOF (every queue is exhausted for good) or -- WITH_RETRY only -- RTW_JOB_RETRY (claim_job's "try again";
 // without WITH_RETRY the claim is repeated here until it is decided).
 // BATCH: the tile column tj of the queues is view v's column tj - v * tiles_jv (BatchArgs); v goes to S->pad.
-template <bool WITH_RETRY = false, bool BATCH = false>
+// ADAPT: outside a full frame (P.shard_count == 0) local tile k is global tile tile_list[k] -- the sharded render's hook with a list in
+// the place of k * shard_count + shard_index; the queues, the claims and the scheduling see a shard of P.local_tiles tiles.
+template <bool WITH_RETRY = false, bool BATCH = false, bool ADAPT = false>
 __device__ RTW_RARE_ATTR void open_job(const KParams &P, JobSlot *S, unsigned lane, DevCounters *ctr, JobCache *jcache,
-                                       unsigned tiles_jv = 0u, unsigned div_tjv_m = 0u, unsigned div_tjv_s = 0u) {
+                                       unsigned tiles_jv = 0u, unsigned div_tjv_m = 0u, unsigned div_tjv_s = 0u, [[maybe_unused]] const int *tile_list = nullptr) {
     unsigned g = RTW_JOB_EOF, valid = 0, k = 0;
     [[maybe_unused]] unsigned view = 0;
     int i_base = 0, j_base = 0;
@@ -400,7 +433,9 @@ __device__ RTW_RARE_ATTR void open_job(const KParams &P, JobSlot *S, unsigned la
             if constexpr (BATCH) { view = udiv_magic(tj, div_tjv_m, div_tjv_s); tj -= view * tiles_jv; }
         } else {
             k = xq + 8u * qt;
-            const unsigned t = k * (unsigned)P.shard_count + (unsigned)P.shard_index;
+            unsigned t;
+            if constexpr (ADAPT) t = uniform((unsigned)tile_list[k]);
+            else t = k * (unsigned)P.shard_count + (unsigned)P.shard_index;
             tj = udiv_magic(t, P.div_tiles_m, P.div_tiles_s); ti = t - tj * (unsigned)P.tiles_i;
         }
         i_base = (int)(ti * 8u + ((q & ((1u << bps_shift) - 1u)) << rs));
@@ -432,10 +467,12 @@ __device__ RTW_RARE_ATTR void open_job(const KParams &P, JobSlot *S, unsigned la
 // ACCUM: one pass of a progressive render (AccumArgs): P.n_chunks / bpj count the pass's own chunks, so the scheduling sees an ordinary
 // small render; the item's chunk is accum.chunk_begin + its local chunk wherever it has a meaning (RNG stream, sample indices); `out`
 // may be null (no running image); otherwise `accum` is unused.
-template <typename T, bool PROFILE, bool LDS_SCENE, bool CULL, bool MFMA = false, int NUMK = -1, bool BATCH = false, bool ACCUM = false>
+// ADAPT (with ACCUM): a pass of an adaptive render (AccumArgs::tile_list): the tiles of a list, and the half difference in word 7.
+template <typename T, bool PROFILE, bool LDS_SCENE, bool CULL, bool MFMA = false, int NUMK = -1, bool BATCH = false, bool ACCUM = false, bool ADAPT = false>
 __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void trace_kernel(KParams P_arg, Camera<T> cam_arg, DevScene<T> scene,
                                                    CullScene<T> cull, T *__restrict__ out, DevCounters *ctr, BatchArgs<T> batch, AccumArgs accum) {
     static_assert(!(BATCH && ACCUM) && !(PROFILE && ACCUM), "no batched and no phase-profile ACCUM instances");
+    static_assert(!ADAPT || ACCUM, "an ADAPT instance is an ACCUM instance");
     using V4 = typename Vec4<T>::type;
     if constexpr (NUMK >= 0) { scene.numerics = NUMK; cull.numerics = NUMK; }
     const unsigned lane = lane_id();
@@ -491,6 +528,7 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
     unsigned ref_depth = 0;   // (bounces left << 9) | item_ref, item_ref = slot * 16 + pixel of the owned item
     int samples_left = 0;
     bool jitter = false;      // false only for sample 1 of the pixel (src/render.jl:30-31)
+    [[maybe_unused]] bool odd_chunk = false;   // ADAPT: the owned item's global chunk is odd (the sign of its samples in the half difference)
     Rng rng = {1, 2};
     V3<T> ro = {0, 0, 0}, rd = {0, 0, 1};
     double thr_r = 1, thr_g = 1, thr_b = 1;
@@ -548,8 +586,9 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                     const C3 sky = skycolor(rd);
                     const unsigned k3 = 3u * __builtin_amdgcn_mbcnt_hi((unsigned)(miss_mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)miss_mask, 0u));
                     const unsigned item_ref = ref_depth & RTW_REF_MASK;
-                    const unsigned a0 = (unsigned)(reinterpret_cast<unsigned char *>(sh->slot(item_ref >> 4, P.slot_stride)->acc(item_ref & 15u)) - smem);
+                    unsigned a0 = (unsigned)(reinterpret_cast<unsigned char *>(sh->slot(item_ref >> 4, P.slot_stride)->acc(item_ref & 15u)) - smem);
                     task_val[k3] = thr_r * sky.r; task_val[k3 + 1u] = thr_g * sky.g; task_val[k3 + 2u] = thr_b * sky.b;
+                    if constexpr (ADAPT) a0 |= odd_chunk ? 4u : 0u;     // (the accumulators are 8-byte aligned: bit 2 carries the parity to the task's lane)
                     task_acc[k3] = (unsigned short)a0; task_acc[k3 + 1u] = (unsigned short)(a0 | 1u); task_acc[k3 + 2u] = (unsigned short)(a0 | 2u);
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -558,7 +597,8 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                     const unsigned t = t0 + lane;
                     if (t < n3) {
                         const unsigned ac = task_acc[t];
-                        fx_accumulate_channel(reinterpret_cast<unsigned long long *>(smem + (ac & 0xfff8u)), ac & 7u, task_val[t]);
+                        if constexpr (ADAPT) fx_accumulate_channel<true>(reinterpret_cast<unsigned long long *>(smem + (ac & 0xfff8u)), ac & 3u, task_val[t], (ac & 4u) != 0u);
+                        else fx_accumulate_channel(reinterpret_cast<unsigned long long *>(smem + (ac & 0xfff8u)), ac & 7u, task_val[t]);
                     }
                 }
                 __builtin_amdgcn_wave_barrier();
@@ -566,7 +606,8 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
         } else if (has_ray && idx < 0) {
             const C3 sky = skycolor(rd);
             const unsigned item_ref = ref_depth & RTW_REF_MASK;
-            fx_accumulate(sh->slot(item_ref >> 4, P.slot_stride)->acc(item_ref & 15u), thr_r * sky.r, thr_g * sky.g, thr_b * sky.b);
+            if constexpr (ADAPT) fx_accumulate<true>(sh->slot(item_ref >> 4, P.slot_stride)->acc(item_ref & 15u), thr_r * sky.r, thr_g * sky.g, thr_b * sky.b, odd_chunk);
+            else fx_accumulate(sh->slot(item_ref >> 4, P.slot_stride)->acc(item_ref & 15u), thr_r * sky.r, thr_g * sky.g, thr_b * sky.b);
         }
         has_ray = false;
 
@@ -587,6 +628,7 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                 fin &= fin - 1ull;
                 JobSlot *S = sh->slot(uniform((unsigned)__shfl((int)((ref_depth & RTW_REF_MASK) >> 4), L)), P.slot_stride);
                 if constexpr (BATCH) store_job<T>(P, S, lane, out + (size_t)uniform(S->pad) * batch.view_elems);
+                else if constexpr (ADAPT) store_job_accum<T, true>(P, S, lane, out, accum);
                 else if constexpr (ACCUM) store_job_accum<T>(P, S, lane, out, accum);
                 else store_job<T>(P, S, lane, out);
                 clk.count(21, 1u);                                                                        // jobs stored
@@ -636,6 +678,7 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                         }
                         if (uniform(won)) {
                             if constexpr (BATCH) open_job<RTW_OPEN_RETRY != 0, true>(P, S, lane, ctr, &sh->jobs, batch.tiles_jv, batch.div_tjv_m, batch.div_tjv_s);
+                            else if constexpr (ADAPT) open_job<RTW_OPEN_RETRY != 0, false, true>(P, S, lane, ctr, &sh->jobs, 0u, 0u, 0u, accum.tile_list);
                             else open_job<RTW_OPEN_RETRY != 0>(P, S, lane, ctr, &sh->jobs);
                             const unsigned opened = uniform(S->job);
                             if (opened >= RTW_JOB_RETRY) {
@@ -702,6 +745,7 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                         }
                         int s0 = (int)chunk * P.chunk_spp;
                         if constexpr (ACCUM) s0 = (int)(chunk + (unsigned)accum.chunk_begin) * P.chunk_spp;     // the GLOBAL sample index
+                        if constexpr (ADAPT) odd_chunk = ((chunk + (unsigned)accum.chunk_begin) & 1u) != 0u;
                         samples_left = min(P.spp, s0 + P.chunk_spp) - s0;
                         jitter = s0 != 0;                                             // sample 1 of the pixel is centred
                         ref_depth = pool_slot * 16u + px;

@@ -24,7 +24,9 @@ void make_udiv(unsigned d, unsigned *m, unsigned *s) {
 // the queues see the batch's total tile count.  n_views == 0: one render of `cam`.
 // `pass` non-null (n_views == 0; validate_accum has accepted it): one pass of a progressive render -- the chunks [chunk_begin, chunk_begin +
 // chunk_count) of the render `p` describes, added to pass->words (rtw::AccumArgs); the job shape, the grid and the batches are those of a
-// render of chunk_count chunks; `d_out` may be null.
+// render of chunk_count chunks; `d_out` may be null.  pass->adapt: a pass of an adaptive render (the ADAPT instances: the half difference
+// in word 7); with pass->tile_list also a pass over the pass->list_tiles tiles of that device-resident list only -- scheduled like a shard
+// of that many tiles (K.shard_count = 0 marks it).
 template <typename T, typename CamT>
 int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
                   RenderRec **rec_out, CtxPtr *ctx_out, const AccumPass *pass = nullptr) {
@@ -46,6 +48,8 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
     K.width = p->width; K.height = p->height; K.spp = p->spp; K.max_depth = p->max_depth;
     K.seed = p->seed; K.n_chunks = nch; K.chunk_spp = cs;
     K.shard_index = p->shard_index; K.shard_count = p->shard_count;
+    const bool listed = pass && pass->adapt && pass->tile_list;
+    if (listed) { K.shard_index = 0; K.shard_count = 0; }
     K.tiles_i = (p->height + 7) / 8; K.tiles_j = (p->width + 7) / 8;
     rtw::BatchArgs<T> B;
     memset(&B, 0, sizeof B);
@@ -57,8 +61,9 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
     }
     rtw::AccumArgs A;
     memset(&A, 0, sizeof A);
-    if (pass) { A.words = pass->words; A.chunk_begin = pass->chunk_begin; A.samples = pass->samples; }
-    const long long n_local = batch ? (long long)K.tiles_i * K.tiles_j : local_tiles(p);
+    if (pass) { A.words = pass->words; A.chunk_begin = pass->chunk_begin; A.samples = pass->samples; A.tile_list = pass->adapt ? pass->tile_list : nullptr; }
+    if (listed && (pass->list_tiles < 0 || pass->list_tiles > (long long)K.tiles_i * K.tiles_j)) return fail(-2, "tile list of %d entries", pass->list_tiles);
+    const long long n_local = batch ? (long long)K.tiles_i * K.tiles_j : listed ? (long long)pass->list_tiles : local_tiles(p);
     K.gamma = p->gamma;
     K.out_layout = (p->flags & RTW_FLAG_COMPACT_TILES) ? 1 : 0;
     make_udiv((unsigned)K.tiles_i, &K.div_tiles_m, &K.div_tiles_s);
@@ -123,6 +128,15 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
         else kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false, false, -1, false, true> : (kern_t)rtw::trace_kernel<T, false, false, false, false, -1, false, true>;
         if (S.numerics == rtw::NUM_REFERENCE && lds_scene && mfma)
             kern = cull ? (kern_t)rtw::trace_kernel<T, false, true, true, true, rtw::NUM_REFERENCE, false, true> : (kern_t)rtw::trace_kernel<T, false, true, false, true, rtw::NUM_REFERENCE, false, true>;
+    }
+    // a pass of an adaptive render: the same choice among the ADAPT instances
+    if (pass && pass->adapt) {
+        if (cull && mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true, true, -1, false, true, true> : (kern_t)rtw::trace_kernel<T, false, false, true, true, -1, false, true, true>;
+        else if (cull) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true, false, -1, false, true, true> : (kern_t)rtw::trace_kernel<T, false, false, true, false, -1, false, true, true>;
+        else if (mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false, true, -1, false, true, true> : (kern_t)rtw::trace_kernel<T, false, false, false, true, -1, false, true, true>;
+        else kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false, false, -1, false, true, true> : (kern_t)rtw::trace_kernel<T, false, false, false, false, -1, false, true, true>;
+        if (S.numerics == rtw::NUM_REFERENCE && lds_scene && mfma)
+            kern = cull ? (kern_t)rtw::trace_kernel<T, false, true, true, true, rtw::NUM_REFERENCE, false, true, true> : (kern_t)rtw::trace_kernel<T, false, true, false, true, rtw::NUM_REFERENCE, false, true, true>;
     }
     // The ray-pool kernel (rtw_pool.hpp; opt-in: RTW_FLAG_RAY_POOL, or RTW_POOL=1 in the environment for A/B runs) exists in `make POOL=1`
     // builds only: Float32 plain scans on the matrix pipe, when the pool, the rings and the scene copy fit the 160 KB of LDS of a CU (one
@@ -193,7 +207,7 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
     const long long cpb = 64 >> job_shift;
     const long long bpj = (nch + cpb - 1) / cpb;
     // (claim_job packs a queue position into 28 bits; queue 0 is the longest: every 8th tile column, or every 8th tile of a shard)
-    const long long queue0_jobs = (p->shard_count == 1 ? (long long)((K.tiles_j + 7) / 8) * K.tiles_i : (n_local + 7) / 8) * (64 >> job_shift);
+    const long long queue0_jobs = (K.shard_count == 1 ? (long long)((K.tiles_j + 7) / 8) * K.tiles_i : (n_local + 7) / 8) * (64 >> job_shift);
     if (total_jobs >= (1ll << 30) || queue0_jobs >= (1ll << 28) || total_jobs * bpj >= (1ll << 40))
         return fail(-5, "render too large for one call: %lld pixel-block jobs", total_jobs);
     K.total_jobs = (unsigned)total_jobs; K.local_tiles = (unsigned)n_local; K.bpj = (unsigned)bpj; K.job_shift = (unsigned)job_shift;

@@ -18,9 +18,9 @@ for line in out.splitlines():
 print(f"{'kernel':52s} {'VGPR':>5s} {'SGPR':>5s} {'waves':>5s} {'scratch B':>9s} {'vspill':>6s} {'sspill':>6s}")
 for r in rows:
     n = r["name"]
-    m = re.match(r"_ZN3rtw12trace_kernelI([fd])Lb([01])ELb([01])ELb([01])ELb([01])ELi(n?\d+)ELb([01])ELb([01])E", n)
+    m = re.match(r"_ZN3rtw12trace_kernelI([fd])Lb([01])ELb([01])ELb([01])ELb([01])ELi(n?\d+)ELb([01])ELb([01])ELb([01])E", n)
     if m:
-        label = f"trace<{'f32' if m.group(1) == 'f' else 'f64'}{', profile' if m.group(2) == '1' else ''}{', lds-scene' if m.group(3) == '1' else ', global-scene'}{', cull' if m.group(4) == '1' else ''}{', mfma' if m.group(5) == '1' else ''}{', numerics fixed' if not m.group(6).startswith('n') else ''}{', batch' if m.group(7) == '1' else ''}{', accum' if m.group(8) == '1' else ''}>"
+        label = f"trace<{'f32' if m.group(1) == 'f' else 'f64'}{', profile' if m.group(2) == '1' else ''}{', lds-scene' if m.group(3) == '1' else ', global-scene'}{', cull' if m.group(4) == '1' else ''}{', mfma' if m.group(5) == '1' else ''}{', numerics fixed' if not m.group(6).startswith('n') else ''}{', batch' if m.group(7) == '1' else ''}{', accum' if m.group(8) == '1' else ''}{', adapt' if m.group(9) == '1' else ''}>"
     elif "unit_kernel" in n:
         label = "unit_kernel<%s>" % ("f32" if "IfE" in n else "f64")
     else:
