@@ -352,6 +352,48 @@ int rtw_render_adaptive_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, c
 int rtw_accum_adaptive_info(rtw_accum_handle a, rtw_adaptive_info_t *out);
 int rtw_accum_tile_chunks(rtw_accum_handle a, int32_t capacity, int32_t *count, int32_t *chunks);
 
+/* Batched progressive and adaptive renders: N views of ONE scene -- same size, spp, chunks, depth, flags -- each with its own accumulator,
+ * every pass ONE kernel launch for all of them (an adaptive turntable or animation: `rounds` launches and host waits instead of
+ * N x rounds, and late passes N times as full).
+ *
+ * The contract: accumulator v after a batched call is indistinguishable from the same accumulator after the single-view call with cams[v],
+ * seed seeds[v] (seeds == NULL: p->seed for every view) and the same p / adaptive -- the same words (word 7 included), the same C_t, the same
+ * binding, the same answer from every query, all on the bits.  Each accumulator is afterwards an ordinary progressive or adaptive
+ * accumulator: it can be continued alone or in another batch, in any mix.
+ *   `cams`, `seeds` and `accums` are HOST arrays of n_views entries.  d_out != NULL receives n_views frames in the layout of
+ * rtw_render_batch_device_*.  The calls are ordered on EVERY accumulator of the array (they wait for all n_views accumulators' previous
+ * operations and are waited for by all their next ones).  rtw_stats() afterwards reports the sums over the views (and, adaptive, over
+ * the rounds).
+ *   rtw_render_accum_batch_*: the chunks [chunk_begin, chunk_begin + chunk_count) of every view's render in ONE launch, added to
+ * accums[v]; asynchronous like rtw_render_accum_*.  Every accumulator is validated on its own exactly as rtw_render_accum_* validates it:
+ * unbound or bound to its own view's render, the range not overlapping what IT holds; the accumulators may hold different ranges before
+ * the call.  Frame v of d_out is divided by the samples accums[v] holds including this pass.  The first pass binds accums[v] to
+ * (cams[v], seeds[v], p).  rtw_accum_merge / export / import / resolve / info / ranges work on each accumulator as ever.
+ *   rtw_render_adaptive_batch_*: blocking like rtw_render_adaptive_*; ONE loop for all views: a pass over [0, min_chunks) of all tiles of
+ * all views; at each checkpoint ONE check over the n_views x n_tiles tiles, ONE sorted list of the active batch-global tiles
+ * (v * n_tiles + t), ONE 4-byte read-back and ONE pass over that list; until no view has an active tile or the chunks run out.  The
+ * accumulators are all unbound, or all adaptive accumulators of their own views' renders with the call's dark_floor / min_chunks /
+ * check_chunks and a last tolerance >= the call's (refinement).  rtw_accum_adaptive_info(accums[v]).rounds is what the single call
+ * reports: the passes of this call that held at least one tile of view v.
+ *   Refusals, all decided before any HIP call with NO accumulator of the array touched: a null scene / cams / p / adaptive / accums or a
+ * null entry of accums -> -1; n_views < 1, the whole-frame one-device restrictions of rtw_render_batch_* and rtw_render_accum_*, a bad
+ * chunk range, bad adaptive parameters, one accumulator twice in the array, a range overlapping what some accumulator holds,
+ * rtw_render_accum_batch_* on an adaptive accumulator -> -2; a batch whose jobs the queues cannot number (rtw_render_batch_*) -> -5; an
+ * accumulator of another size, device or precision, one bound to another render than its view's, a mix of unbound and bound accumulators
+ * in the adaptive call, a looser tolerance than some accumulator's last -> -4.  Additive to ABI 4: detected by symbol lookup. */
+int rtw_render_accum_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds,
+                               const rtw_params *p, int32_t chunk_begin, int32_t chunk_count,
+                               const rtw_accum_handle *accums, void *d_out, void *hip_stream);
+int rtw_render_accum_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds,
+                               const rtw_params *p, int32_t chunk_begin, int32_t chunk_count,
+                               const rtw_accum_handle *accums, void *d_out, void *hip_stream);
+int rtw_render_adaptive_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds,
+                                  const rtw_params *p, const rtw_adaptive_t *adaptive,
+                                  const rtw_accum_handle *accums, void *d_out, void *hip_stream);
+int rtw_render_adaptive_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds,
+                                  const rtw_params *p, const rtw_adaptive_t *adaptive,
+                                  const rtw_accum_handle *accums, void *d_out, void *hip_stream);
+
 /* Counters/timings of the last render issued from this thread (waits for it to finish). */
 int rtw_stats(rtw_stats_t *out);
 

@@ -319,4 +319,143 @@ function render_adaptive(scene::HittableList, cam::Camera{T}, image_width=400, n
     img, chunks
 end
 
+# what the two batched methods below share: the scene uploaded once, one accumulator per camera, `body(hscene, haccs, params, ccams, seeds, check)`,
+# and the handles freed whatever happens
+function with_batch(body, scene::HittableList, cams::AbstractVector{Camera{T}}, image_width, n_samples, depth, seed, n_chunks, device,
+                    numerics, group_cull, scan_valu) where T <: Union{Float32,Float64}
+    isempty(cams) && throw(ArgumentError("cams is empty"))
+    n_samples >= 1 || throw(ArgumentError("n_samples must be >= 1"))
+    numerics in (:reference, :contract, :reference_fma2) || throw(ArgumentError("numerics must be :reference, :contract or :reference_fma2"))
+    nflags = numerics === :contract ? 32 : numerics === :reference_fma2 ? 128 : 0
+    nv = length(cams)
+    seeds = seed isa Integer ? fill(UInt64(seed), nv) : UInt64.(seed)
+    length(seeds) == nv || throw(ArgumentError("$(length(seeds)) seeds for $nv views"))
+    image_height = image_width ÷ (16//9)
+    n = length(scene)
+    cx = Vector{T}(undef, n); cy = similar(cx); cz = similar(cx); r = similar(cx)
+    ar = similar(cx); ag = similar(cx); ab = similar(cx); param = similar(cx)
+    kind = Vector{Int32}(undef, n)
+    for (i, h) in enumerate(scene)
+        h isa Sphere{T} || throw(ArgumentError("scene[$i] is $(typeof(h)); the HIP path takes Sphere{$T} only"))
+        cx[i], cy[i], cz[i] = h.center
+        r[i] = h.radius
+        kind[i] = matkind(h.mat)
+        ar[i], ag[i], ab[i] = albedo(h.mat)
+        param[i] = matparam(h.mat)
+    end
+    ccams = [CCamera(c) for c in cams]
+    check(rc) = rc == 0 || error("librtw_hip: error $rc: $(last_error())")
+    hscene = Ref{Ptr{Cvoid}}(C_NULL)
+    haccs = fill(Ptr{Cvoid}(C_NULL), nv)
+    GC.@preserve cx cy cz r kind ar ag ab param ccams seeds haccs begin
+        cscene = Ref(CScene{T}(n, pointer(cx), pointer(cy), pointer(cz), pointer(r), pointer(kind),
+                               pointer(ar), pointer(ag), pointer(ab), pointer(param)))
+        params = Ref(CParams(image_width, image_height, n_samples, depth, seeds[1], n_chunks, 0, 1, -1, 1,
+                             (group_cull ? 1 : 0) | (scan_valu ? 4 : 0) | nflags, 0, 0, Ptr{Int32}(C_NULL)))
+        try
+            if T === Float32
+                check(ccall((:rtw_scene_upload_f32, LIB), Cint, (Ref{CScene{Float32}}, Cint, Ref{Ptr{Cvoid}}), cscene, device, hscene))
+            else
+                check(ccall((:rtw_scene_upload_f64, LIB), Cint, (Ref{CScene{Float64}}, Cint, Ref{Ptr{Cvoid}}), cscene, device, hscene))
+            end
+            for v in 1:nv
+                h = Ref{Ptr{Cvoid}}(C_NULL)
+                check(ccall((:rtw_accum_create, LIB), Cint, (Cint, Int32, Int32, Ref{Ptr{Cvoid}}), device, image_width, image_height, h))
+                haccs[v] = h[]
+            end
+            body(hscene[], haccs, params, ccams, seeds, check)
+        finally
+            for h in haccs
+                ccall((:rtw_accum_free, LIB), Cint, (Ptr{Cvoid},), h)          # (NULL handles are accepted)
+            end
+            ccall((:rtw_scene_free, LIB), Cint, (Ptr{Cvoid},), hscene[])
+        end
+    end
+end
+
+"""
+    render_progressive(scene, cams::AbstractVector{Camera{T}}, image_width=400, n_samples=1; passes=4, depth=16, seed=1, n_chunks=0, device=-1, numerics=:reference, group_cull=false, scan_valu=false)
+
+Batched progressive render (rtw_render_accum_batch_f32/_f64): every camera of `cams` with an accumulator of its own, each of the `passes`
+passes ONE kernel launch for all of them.  Returns an `Array{RGB{T},3}` of size (image_height, image_width, length(cams)); `img[:, :, v]`
+is bit-identical to `render(scene, cams[v], image_width, n_samples; seed=seeds[v])`.  `seed`: one integer for every view or a vector.
+(tests/test_gpu_accum_batch.py drives the same entry points through ctypes.)
+"""
+function render_progressive(scene::HittableList, cams::AbstractVector{Camera{T}}, image_width=400, n_samples=1;
+                            passes=4, depth=16, seed=1, n_chunks=0, device=-1, numerics=:reference, group_cull=false, scan_valu=false) where T <: Union{Float32,Float64}
+    passes >= 1 || throw(ArgumentError("passes must be >= 1"))
+    nv = length(cams)
+    image_height = image_width ÷ (16//9)
+    nch = min(n_chunks > 0 ? n_chunks : min(n_samples, 256), n_samples)      # the effective chunks (include/rtw_hip.h rtw_params.n_chunks)
+    nch = cld(n_samples, cld(n_samples, nch))
+    passes = min(passes, nch)
+    img = Array{RGB{T},3}(undef, image_height, image_width, nv)
+    with_batch(scene, cams, image_width, n_samples, depth, seed, n_chunks, device, numerics, group_cull, scan_valu) do hscene, haccs, params, ccams, seeds, check
+        GC.@preserve img begin
+            for k in 0:passes-1
+                b, e = k * nch ÷ passes, (k + 1) * nch ÷ passes
+                if T === Float32
+                    check(ccall((:rtw_render_accum_batch_f32, LIB), Cint, (Ptr{Cvoid}, Ptr{CCamera{Float32}}, Int32, Ptr{UInt64}, Ref{CParams}, Int32, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Cvoid}),
+                                hscene, pointer(ccams), nv, pointer(seeds), params, b, e - b, pointer(haccs), C_NULL, C_NULL))
+                else
+                    check(ccall((:rtw_render_accum_batch_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{CCamera{Float64}}, Int32, Ptr{UInt64}, Ref{CParams}, Int32, Int32, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Cvoid}),
+                                hscene, pointer(ccams), nv, pointer(seeds), params, b, e - b, pointer(haccs), C_NULL, C_NULL))
+                end
+            end
+            for v in 1:nv
+                out = pointer(reinterpret(T, vec(img))) + (v - 1) * image_height * image_width * 3 * sizeof(T)
+                if T === Float32
+                    check(ccall((:rtw_accum_resolve_host_f32, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float32}), haccs[v], 1, out))
+                else
+                    check(ccall((:rtw_accum_resolve_host_f64, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), haccs[v], 1, out))
+                end
+            end
+        end
+    end
+    img
+end
+
+"""
+    render_adaptive(scene, cams::AbstractVector{Camera{T}}, image_width=400, n_samples=1; tolerance, dark_floor=0.03, min_chunks=0, check_chunks=0, depth=16, seed=1, n_chunks=0, device=-1, numerics=:reference, group_cull=false, scan_valu=false)
+
+Batched adaptive sampling (rtw_render_adaptive_batch_f32/_f64): every camera of `cams` in ONE loop of passes -- per checkpoint one check,
+one list of the active tiles of all views, one host wait, one launch.  Returns `(img, tile_chunks)`: an `Array{RGB{T},3}` of size
+(image_height, image_width, length(cams)) and an `Array{Int32,3}` of size (tiles_i, tiles_j, length(cams)); view `v` of both is
+bit-identical to `render_adaptive(scene, cams[v], ...; seed=seeds[v])`.  `seed`: one integer for every view or a vector.
+(tests/test_gpu_accum_batch.py drives the same entry points through ctypes.)
+"""
+function render_adaptive(scene::HittableList, cams::AbstractVector{Camera{T}}, image_width=400, n_samples=1;
+                         tolerance, dark_floor=0.03, min_chunks=0, check_chunks=0, depth=16, seed=1, n_chunks=0, device=-1,
+                         numerics=:reference, group_cull=false, scan_valu=false) where T <: Union{Float32,Float64}
+    nv = length(cams)
+    image_height = image_width ÷ (16//9)
+    tiles_i, tiles_j = cld(image_height, 8), cld(image_width, 8)
+    img = Array{RGB{T},3}(undef, image_height, image_width, nv)
+    chunks = Array{Int32,3}(undef, tiles_i, tiles_j, nv)          # view v: column-major like the tile numbering t = tj * tiles_i + ti
+    with_batch(scene, cams, image_width, n_samples, depth, seed, n_chunks, device, numerics, group_cull, scan_valu) do hscene, haccs, params, ccams, seeds, check
+        adaptive = Ref(CAdaptive(tolerance, dark_floor, min_chunks, check_chunks, (Int32(0), Int32(0))))
+        GC.@preserve img chunks begin
+            if T === Float32
+                check(ccall((:rtw_render_adaptive_batch_f32, LIB), Cint, (Ptr{Cvoid}, Ptr{CCamera{Float32}}, Int32, Ptr{UInt64}, Ref{CParams}, Ref{CAdaptive}, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Cvoid}),
+                            hscene, pointer(ccams), nv, pointer(seeds), params, adaptive, pointer(haccs), C_NULL, C_NULL))
+            else
+                check(ccall((:rtw_render_adaptive_batch_f64, LIB), Cint, (Ptr{Cvoid}, Ptr{CCamera{Float64}}, Int32, Ptr{UInt64}, Ref{CParams}, Ref{CAdaptive}, Ptr{Ptr{Cvoid}}, Ptr{Cvoid}, Ptr{Cvoid}),
+                            hscene, pointer(ccams), nv, pointer(seeds), params, adaptive, pointer(haccs), C_NULL, C_NULL))
+            end
+            count = Ref{Int32}(0)
+            for v in 1:nv
+                out = pointer(reinterpret(T, vec(img))) + (v - 1) * image_height * image_width * 3 * sizeof(T)
+                if T === Float32
+                    check(ccall((:rtw_accum_resolve_host_f32, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float32}), haccs[v], 1, out))
+                else
+                    check(ccall((:rtw_accum_resolve_host_f64, LIB), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}), haccs[v], 1, out))
+                end
+                check(ccall((:rtw_accum_tile_chunks, LIB), Cint, (Ptr{Cvoid}, Int32, Ref{Int32}, Ptr{Int32}), haccs[v], tiles_i * tiles_j, count,
+                            pointer(chunks) + (v - 1) * tiles_i * tiles_j * sizeof(Int32)))
+            end
+        end
+    end
+    img, chunks
+end
+
 end # module

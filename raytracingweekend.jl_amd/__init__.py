@@ -20,8 +20,8 @@ from .scenes import (  # noqa: F401
     scene_random_spheres, t_cam1, t_cam2, t_default_cam,
 )
 from .render import DeviceRenderer, render, render_batch, last_stats  # noqa: F401
-from .progressive import ProgressiveRenderer, render_progressive, samples_in_chunks  # noqa: F401
-from .adaptive import AdaptiveRenderer, reference_decisions, render_adaptive  # noqa: F401
+from .progressive import ProgressiveBatchRenderer, ProgressiveRenderer, render_progressive, samples_in_chunks  # noqa: F401
+from .adaptive import AdaptiveBatchRenderer, AdaptiveRenderer, reference_decisions, render_adaptive, render_adaptive_batch  # noqa: F401
 from .shard import compact_elems, compact_to_frame_index, local_tile_count, owned_pixel_mask, render_sharded  # noqa: F401
 from . import imageio  # noqa: F401
 
@@ -33,5 +33,5 @@ __all__ = [
     "scene_random_spheres", "t_cam1", "t_cam2", "t_default_cam",
     "DeviceRenderer", "render", "render_batch", "last_stats", "ProgressiveRenderer", "render_progressive", "samples_in_chunks",
     "AdaptiveRenderer", "render_adaptive", "reference_decisions", "owned_pixel_mask", "render_sharded", "compact_elems",
-    "compact_to_frame_index", "local_tile_count",
+    "compact_to_frame_index", "local_tile_count", "ProgressiveBatchRenderer", "AdaptiveBatchRenderer", "render_adaptive_batch",
 ]

@@ -17,6 +17,7 @@ SYMBOLS = [
     "rtw_accum_resolve_f32", "rtw_accum_resolve_f64", "rtw_accum_resolve_host_f32", "rtw_accum_resolve_host_f64",
     "rtw_accum_merge", "rtw_accum_info", "rtw_accum_ranges", "rtw_accum_read_pixels", "rtw_accum_export", "rtw_accum_import",
     "rtw_render_adaptive_f32", "rtw_render_adaptive_f64", "rtw_accum_adaptive_info", "rtw_accum_tile_chunks",
+    "rtw_render_accum_batch_f32", "rtw_render_accum_batch_f64", "rtw_render_adaptive_batch_f32", "rtw_render_adaptive_batch_f64",
 ]
 
 
@@ -108,6 +109,12 @@ def lib():
         getattr(L, name).argtypes = [C.c_void_p, C.POINTER(CamT), C.POINTER(Params), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     for name, CamT in (("rtw_render_adaptive_f32", CameraF32), ("rtw_render_adaptive_f64", CameraF64)):
         getattr(L, name).argtypes = [C.c_void_p, C.POINTER(CamT), C.POINTER(Params), C.POINTER(Adaptive), C.c_void_p, C.c_void_p, C.c_void_p]
+    for name, CamT in (("rtw_render_accum_batch_f32", CameraF32), ("rtw_render_accum_batch_f64", CameraF64)):
+        getattr(L, name).argtypes = [C.c_void_p, C.POINTER(CamT), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(Params), C.c_int32, C.c_int32,
+                                     C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
+    for name, CamT in (("rtw_render_adaptive_batch_f32", CameraF32), ("rtw_render_adaptive_batch_f64", CameraF64)):
+        getattr(L, name).argtypes = [C.c_void_p, C.POINTER(CamT), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(Params), C.POINTER(Adaptive),
+                                     C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
     L.rtw_accum_adaptive_info.argtypes = [C.c_void_p, C.POINTER(AdaptiveInfo)]
     L.rtw_accum_tile_chunks.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rtw_accum_create.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
@@ -180,6 +187,11 @@ def make_seeds(seed, n):
         if len(seeds) != n:
             raise ValueError(f"{len(seeds)} seeds for {n} views")
     return (C.c_uint64 * n)(*seeds)
+
+
+def make_handles(handles):
+    """sequence of accumulator handles (c_void_p or int) -> ctypes array (the ``accums`` of rtw_render_accum_batch_* / _adaptive_batch_*)"""
+    return (C.c_void_p * len(handles))(*[h.value if isinstance(h, C.c_void_p) else h for h in handles])
 
 
 FLAG_GROUP_CULL = 1      # include/rtw_hip.h RTW_FLAG_GROUP_CULL

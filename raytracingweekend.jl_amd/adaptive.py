@@ -11,7 +11,7 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from .progressive import ProgressiveRenderer
+from .progressive import ProgressiveBatchRenderer, ProgressiveRenderer
 
 #: Default ``dark_floor``: 1 % of a white pixel (R + G + B = 3 per sample).  A CHOICE, not a measurement: it says below which
 #: brightness a tile's relative error stops mattering, and a caller who cares about deep shadows lowers it.
@@ -153,3 +153,68 @@ def render_adaptive(scene, cam, image_width=400, n_samples=1, *, tolerance, dark
                           depth=depth, seed=seed, n_chunks=n_chunks, device=device, numerics=numerics) as ar:
         info = ar.run(tolerance, group_cull=group_cull, scan_valu=scan_valu)
         return ar.image(gamma=gamma), ar.samples_per_pixel(), info
+
+
+class AdaptiveBatchRenderer(ProgressiveBatchRenderer):
+    """N adaptive renders of ONE scene (a camera and a seed per view) run as one loop (``rtw_render_adaptive_batch_*``): per checkpoint
+    one check, one list of the active tiles of all views, one host wait and one pass -- ``rounds`` launches and waits instead of
+    N x ``rounds``.  View ``v`` is, bit for bit, the ``AdaptiveRenderer`` of ``cams[v]`` and ``seeds[v]``.  ``run`` again with a smaller
+    tolerance refines every view."""
+
+    def __init__(self, scene, cams, image_width=400, n_samples=1, *, dark_floor=DEFAULT_DARK_FLOOR, min_chunks=0, check_chunks=0,
+                 depth=16, seeds=1, n_chunks=0, device=-1, numerics=None):
+        super().__init__(scene, cams, image_width, n_samples, depth=depth, seeds=seeds, n_chunks=n_chunks, device=device, numerics=numerics)
+        self.dark_floor, self.min_chunks, self.check_chunks = float(dark_floor), int(min_chunks), int(check_chunks)
+
+    @property
+    def tiles(self):
+        """(tiles down a column, tiles along a row) of one view"""
+        return (self.height + 7) // 8, (self.width + 7) // 8
+
+    def run(self, tolerance, *, group_cull=False, scan_valu=False, job_pixels=0, d_out=None, gamma=True, stream=0):
+        """Render every view to ``tolerance`` (blocking).  ``d_out``: a device pointer that receives the N final images.  Returns the
+        list of ``info(v)``."""
+        P = self._params(group_cull, scan_valu, job_pixels, gamma)
+        A = _capi.Adaptive(float(tolerance), self.dark_floor, self.min_chunks, self.check_chunks)
+        fn = self.L.rtw_render_adaptive_batch_f64 if _capi.is_f64(self.T) else self.L.rtw_render_adaptive_batch_f32
+        _capi.check(fn(self.handle, self.cams, self.n_views, self.seeds, C.byref(P), C.byref(A), self._handles,
+                       C.c_void_p(int(d_out)) if d_out else None, C.c_void_p(int(stream))))
+        return [self.info(v) for v in range(self.n_views)]
+
+    def tile_chunks(self):
+        """``C_t`` as an int32 array of shape (N, tiles_i, tiles_j): ``[v, ti, tj]`` = the chunks tile ``tj * tiles_i + ti`` of view
+        ``v`` holds"""
+        ti, tj = self.tiles
+        out = np.zeros((self.n_views, ti, tj), dtype=np.int32)
+        for v, acc in enumerate(self.accums):
+            buf = np.zeros(ti * tj, dtype=np.int32)
+            n = C.c_int32(0)
+            _capi.check(self.L.rtw_accum_tile_chunks(acc, buf.size, C.byref(n), buf.ctypes.data_as(C.POINTER(C.c_int32))))
+            assert n.value == buf.size
+            out[v] = buf.reshape(tj, ti).T
+        return out
+
+    def samples_per_pixel(self):
+        """int32 ``N x H x W``: the samples each pixel of each view holds"""
+        spp = np.minimum(self.n_samples, self.tile_chunks().astype(np.int64) * self.chunk_spp).astype(np.int32)
+        return np.repeat(np.repeat(spp, 8, axis=1), 8, axis=2)[:, :self.height, :self.width]
+
+    def info(self, v):
+        """view ``v``'s accumulator info and, once a run has finished, the fields of ``rtw_adaptive_info_t``"""
+        out = super().info(v)
+        st = _capi.AdaptiveInfo()
+        if self.L.rtw_accum_adaptive_info(self.accums[v], C.byref(st)) == 0:
+            out.update({k: getattr(st, k) for k, _ in st._fields_})
+        return out
+
+
+def render_adaptive_batch(scene, cams, image_width=400, n_samples=1, *, tolerance, seeds=None, dark_floor=DEFAULT_DARK_FLOOR, depth=16,
+                          n_chunks=0, min_chunks=0, check_chunks=0, group_cull=False, scan_valu=False, numerics=None, gamma=True, device=-1):
+    """``render_adaptive`` for N cameras of one scene in one loop of batched passes; view ``v`` equals ``render_adaptive(scene, cams[v],
+    ..., seed=seeds[v])`` bit for bit.  ``seeds``: None (seed 1 for every view, ``render_adaptive``'s default), one int, or N ints.
+
+    Returns ``(images, samples_per_pixel, infos)``: ``N x H x W x 3``, int32 ``N x H x W``, and the list of the views' info dicts."""
+    with AdaptiveBatchRenderer(scene, cams, image_width, n_samples, dark_floor=dark_floor, min_chunks=min_chunks, check_chunks=check_chunks,
+                               depth=depth, seeds=1 if seeds is None else seeds, n_chunks=n_chunks, device=device, numerics=numerics) as ar:
+        infos = ar.run(tolerance, group_cull=group_cull, scan_valu=scan_valu)
+        return ar.images(gamma=gamma), ar.samples_per_pixel(), infos

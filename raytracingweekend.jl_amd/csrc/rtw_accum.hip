@@ -81,12 +81,8 @@ __global__ __launch_bounds__(256) void accum_resolve_kernel(const unsigned long 
 // a tile that holds exactly c chunks and is NOT converged (it stays active), 0 for every other tile.  D and Y are summed sequentially in
 // lane order by every lane (64 shuffles each): the written rule's own order, so the result does not depend on how a reduction would
 // associate.  n = (double)(c * chunk_spp).  (-ffp-contract=off: no FMA anywhere in this library unless the source writes one.)
-__global__ __launch_bounds__(256) void accum_tile_check_kernel(const unsigned long long *__restrict__ words, const int *__restrict__ chunks, int *__restrict__ flags,
-                                                               int n_tiles, int tiles_i, int width, int height, int c, double n, double tol, double floor) {
-    const unsigned lane = threadIdx.x & 63u;
-    const int t = (int)(blockIdx.x * 4u + (threadIdx.x >> 6));
-    if (t >= n_tiles) return;                         // (whole waves: no barrier below)
-    if (chunks[t] != c) { if (lane == 0) flags[t] = 0; return; }
+// (tile_not_converged: the rule itself for tile t of one frame, whole wave, the same value in every lane -- shared with the batched check)
+__device__ __forceinline__ int tile_not_converged(const unsigned long long *__restrict__ words, int t, unsigned lane, int tiles_i, int width, int height, double n, double tol, double floor) {
     const int tj = t / tiles_i, ti = t - tj * tiles_i;
     const int i = ti * 8 + (int)(lane & 7u), j = tj * 8 + (int)(lane >> 3);
     const bool valid = i < height && j < width;
@@ -106,7 +102,88 @@ __global__ __launch_bounds__(256) void accum_tile_check_kernel(const unsigned lo
     for (int k = 0; k < 64; ++k) { D = D + __shfl(d, k); Y = Y + __shfl(y, k); }
     const double dark = (floor * n) * npix;
     const double M = Y > dark ? Y : dark;
-    if (lane == 0) flags[t] = D <= tol * M ? 0 : 1;
+    return D <= tol * M ? 0 : 1;
+}
+__global__ __launch_bounds__(256) void accum_tile_check_kernel(const unsigned long long *__restrict__ words, const int *__restrict__ chunks, int *__restrict__ flags,
+                                                               int n_tiles, int tiles_i, int width, int height, int c, double n, double tol, double floor) {
+    const unsigned lane = threadIdx.x & 63u;
+    const int t = (int)(blockIdx.x * 4u + (threadIdx.x >> 6));
+    if (t >= n_tiles) return;                         // (whole waves: no barrier below)
+    if (chunks[t] != c) { if (lane == 0) flags[t] = 0; return; }
+    const int f = tile_not_converged(words, t, lane, tiles_i, width, height, n, tol, floor);
+    if (lane == 0) flags[t] = f;
+}
+
+// ---- the same for a batch of N views (rtw_render_adaptive_batch_*): batch-global tile g = v * n_tiles + t, view v's words and C_t ----
+struct TileView { const unsigned long long *words; int *chunks; };
+// one wave per (view, tile): tile_not_converged on view v's words -- the single check's arithmetic in the single check's order
+__global__ __launch_bounds__(256) void accum_tile_check_batch_kernel(const TileView *__restrict__ views, int *__restrict__ flags, int n_views, int n_tiles, int tiles_i,
+                                                                     int width, int height, int c, double n, double tol, double floor) {
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned g = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (g >= (unsigned)n_views * (unsigned)n_tiles) return;      // (whole waves: no barrier below)
+    const unsigned v = g / (unsigned)n_tiles;
+    const int t = (int)(g - v * (unsigned)n_tiles);
+    const TileView V = views[v];
+    if (V.chunks[t] != c) { if (lane == 0) flags[g] = 0; return; }
+    const int f = tile_not_converged(V.words, t, lane, tiles_i, width, height, n, tol, floor);
+    if (lane == 0) flags[g] = f;
+}
+// The batch's list in three small launches instead of one workgroup's loop over N * n_tiles flags (accum_tile_compact_kernel: a chain of
+// n / 1024 dependent steps): blocks of 256 flags are counted, ONE workgroup turns the counts into offsets (and the total into *count), the
+// blocks write their tiles behind their offsets.  The order is the flags' order, so the list is the one the loop makes: sorted.
+__global__ __launch_bounds__(256) void accum_tile_count_kernel(const int *__restrict__ flags, int *__restrict__ block_n, int n) {
+    __shared__ int wave_n[4];
+    const int t = (int)(blockIdx.x * 256u + threadIdx.x);
+    const bool f = t < n && flags[t] != 0;
+    const unsigned long long m = __ballot(f);
+    if ((threadIdx.x & 63u) == 0u) wave_n[threadIdx.x >> 6] = (int)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) block_n[blockIdx.x] = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
+}
+// counts -> exclusive prefix sums, in place; one workgroup, 1024 counts per step
+__global__ __launch_bounds__(1024) void accum_tile_scan_kernel(int *__restrict__ block_n, int *__restrict__ count, int nb) {
+    __shared__ int wave_s[16];
+    __shared__ int base;
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) base = 0;
+    __syncthreads();
+    for (int b0 = 0; b0 < nb; b0 += 1024) {
+        const int b = b0 + (int)threadIdx.x;
+        const int v = b < nb ? block_n[b] : 0;
+        int x = v;                                    // inclusive sums within the wave
+        for (unsigned d = 1; d < 64u; d <<= 1) { const int y = __shfl_up(x, d); if (lane >= d) x += y; }
+        if (lane == 63u) wave_s[wave] = x;
+        __syncthreads();
+        int off = base;
+        for (unsigned k = 0; k < wave; ++k) off += wave_s[k];
+        if (b < nb) block_n[b] = off + x - v;
+        __syncthreads();
+        if (threadIdx.x == 0) { int s = 0; for (int k = 0; k < 16; ++k) s += wave_s[k]; base += s; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *count = base;
+}
+__global__ __launch_bounds__(256) void accum_tile_scatter_kernel(const int *__restrict__ flags, const int *__restrict__ block_off, int *__restrict__ list, int n) {
+    __shared__ int wave_n[4];
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const int t = (int)(blockIdx.x * 256u + threadIdx.x);
+    const bool f = t < n && flags[t] != 0;
+    const unsigned long long m = __ballot(f);
+    if (lane == 0u) wave_n[wave] = (int)__popcll(m);
+    __syncthreads();
+    if (f) {
+        int off = block_off[blockIdx.x];
+        for (unsigned k = 0; k < wave; ++k) off += wave_n[k];
+        list[off + (int)__popcll(m & ((1ull << lane) - 1ull))] = t;
+    }
+}
+// after a pass of `add` chunks: C_t += add in each listed tile's OWN view (list == null: for all n = N * n_tiles tiles)
+__global__ __launch_bounds__(256) void accum_tile_advance_batch_kernel(const int *__restrict__ list, int n, const TileView *__restrict__ views, int n_tiles, int add) {
+    const int k = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (k >= n) return;
+    const unsigned g = (unsigned)(list ? list[k] : k), v = g / (unsigned)n_tiles;
+    views[v].chunks[g - v * (unsigned)n_tiles] += add;
 }
 
 // flags -> the SORTED list of the active tiles + its length, one workgroup: ascending tile numbers keep what the sharded path's queues
@@ -348,21 +425,25 @@ int default_check_chunks(int nch) { int m = std::max(16, (nch + 7) / 8); return 
 
 // everything about an adaptive call that is decided without a device: nulls, the render, whole frames on one device, the adaptive
 // parameters; then the handles and the binding.  *eff: the parameters with min_chunks / check_chunks as their effective values.
+int validate_adaptive_params(const rtw_adaptive_t *ad, int nch, rtw_adaptive_t *eff) {
+    if (!std::isfinite(ad->tolerance) || !(ad->tolerance > 0.0)) return fail(-2, "tolerance must be finite and > 0 (got %g)", ad->tolerance);
+    if (!std::isfinite(ad->dark_floor) || ad->dark_floor < 0.0) return fail(-2, "dark_floor must be finite and >= 0 (got %g)", ad->dark_floor);
+    if (ad->min_chunks < 0 || (ad->min_chunks & 1)) return fail(-2, "min_chunks must be even and >= 2, or 0 for the default (got %d)", ad->min_chunks);
+    if (ad->check_chunks < 0 || (ad->check_chunks & 1)) return fail(-2, "check_chunks must be even and >= 2, or 0 for the default (got %d)", ad->check_chunks);
+    memset(eff, 0, sizeof *eff);
+    eff->tolerance = ad->tolerance; eff->dark_floor = ad->dark_floor;
+    eff->min_chunks = ad->min_chunks ? ad->min_chunks : default_check_chunks(nch);
+    eff->check_chunks = ad->check_chunks ? ad->check_chunks : default_check_chunks(nch);
+    return 0;
+}
 template <typename CamT>
 int validate_adaptive(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, const rtw_adaptive_t *ad, rtw_accum_handle a, int *nch_out, int *cs_out, rtw_adaptive_t *eff) {
     if (!p) return fail(-1, "null params");
     if (!cam || !a || !scene || !ad) return fail(-1, "null argument");
     int nch, cs;
     if (int rc = validate_frame(p, &nch, &cs)) return rc;
-    if (!std::isfinite(ad->tolerance) || !(ad->tolerance > 0.0)) return fail(-2, "tolerance must be finite and > 0 (got %g)", ad->tolerance);
-    if (!std::isfinite(ad->dark_floor) || ad->dark_floor < 0.0) return fail(-2, "dark_floor must be finite and >= 0 (got %g)", ad->dark_floor);
-    if (ad->min_chunks < 0 || (ad->min_chunks & 1)) return fail(-2, "min_chunks must be even and >= 2, or 0 for the default (got %d)", ad->min_chunks);
-    if (ad->check_chunks < 0 || (ad->check_chunks & 1)) return fail(-2, "check_chunks must be even and >= 2, or 0 for the default (got %d)", ad->check_chunks);
+    if (int rc = validate_adaptive_params(ad, nch, eff)) return rc;
     if (int rc = validate_handles(sizeof(CamT) == sizeof(rtw_camera_f64), scene, p, a)) return rc;
-    memset(eff, 0, sizeof *eff);
-    eff->tolerance = ad->tolerance; eff->dark_floor = ad->dark_floor;
-    eff->min_chunks = ad->min_chunks ? ad->min_chunks : default_check_chunks(nch);
-    eff->check_chunks = ad->check_chunks ? ad->check_chunks : default_check_chunks(nch);
     if (a->bound) {
         if (!a->adaptive) return fail(-4, "the accumulator is bound by plain passes (rtw_render_accum_* / merge / import); rtw_accum_reset() unbinds it");
         AccumBind b;
@@ -485,6 +566,240 @@ int render_adaptive(rtw_scene_handle scene, const CamT *cam, const rtw_params *p
     return mark(a, stream);
 }
 
+// ---- batched passes (rtw_render_accum_batch_*, rtw_render_adaptive_batch_*): N views of one scene, each with its own accumulator ----
+// what both batched calls decide before they look at a handle: nulls, n_views, the frame (validate_frame), the queue limit of a batch
+int validate_views(rtw_scene_handle scene, const void *cams, int32_t n_views, const rtw_params *p, const rtw_accum_handle *accums, int *nch_out, int *cs_out) {
+    if (!p) return fail(-1, "null params");
+    if (!cams || !accums || !scene) return fail(-1, "null argument");
+    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
+    for (int32_t v = 0; v < n_views; ++v) if (!accums[v]) return fail(-1, "null accumulator (view %d)", v);
+    if (int rc = validate_frame(p, nch_out, cs_out)) return rc;
+    return validate_batch(cams, n_views, p, cams);       // (what is left of it: -5 for a batch whose jobs the queues cannot number)
+}
+int validate_distinct(int32_t n_views, const rtw_accum_handle *accums) {
+    std::vector<rtw_accum_handle> sorted(accums, accums + n_views);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end()) return fail(-2, "one accumulator is given for two views");
+    return 0;
+}
+rtw_params view_params(const rtw_params *p, const uint64_t *seeds, int v) { rtw_params q = *p; if (seeds) q.seed = seeds[v]; return q; }
+
+template <typename CamT>
+int render_accum_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count,
+                       const rtw_accum_handle *accums, void *d_out, void *stream_v) {
+    int nch, cs;
+    if (int rc = validate_views(scene, cams, n_views, p, accums, &nch, &cs)) return rc;
+    if (chunk_begin < 0 || chunk_count < 1 || (long long)chunk_begin + chunk_count > nch)
+        return fail(-2, "chunk range [%d, %lld) is not inside the render's %d chunks", chunk_begin, (long long)chunk_begin + chunk_count, nch);
+    if (int rc = validate_distinct(n_views, accums)) return rc;
+    // every accumulator on its own, as rtw_render_accum_* validates it -- all of them before anything is touched
+    std::vector<AccumBind> binds((size_t)n_views);
+    for (int32_t v = 0; v < n_views; ++v) {
+        const rtw_params q = view_params(p, seeds, v);
+        int nv, cv;
+        if (int rc = validate_accum(scene, cams + v, &q, chunk_begin, chunk_count, accums[v], &nv, &cv)) return fail(rc, "view %d: %s", v, std::string(g_err).c_str());
+        make_bind(&binds[(size_t)v], scene, cams + v, &q, nch, cs);
+    }
+    DeviceGuard guard;
+    hipStream_t stream = (hipStream_t)stream_v;
+    HIP_TRY(hipSetDevice(scene->device));
+    std::vector<AccumViewPass> views((size_t)n_views);
+    for (int32_t v = 0; v < n_views; ++v) {
+        if (int rc = wait_for(accums[v], stream)) return rc;
+        views[(size_t)v].words = accums[v]->words;
+        views[(size_t)v].samples = (int)(samples_done(accums[v]) + samples_in(binds[(size_t)v], chunk_begin, (long long)chunk_begin + chunk_count));
+    }
+    AccumPass pass;
+    pass.words = nullptr; pass.chunk_begin = chunk_begin; pass.chunk_count = chunk_count; pass.samples = 1;
+    pass.views = views.data();
+    RenderRec *rec = nullptr;
+    CtxPtr ctx;
+    release_last();
+    int rc = launch_accum_batch_t(scene, cams, n_views, seeds, p, pass, d_out, stream, &rec, &ctx);
+    if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); }       // (also on a late error: released by the next call)
+    if (rc) return rc;
+    for (int32_t v = 0; v < n_views; ++v) {
+        rtw_accum *a = accums[v];
+        a->bind = binds[(size_t)v]; a->bound = true;
+        add_range(a->ranges, chunk_begin, chunk_begin + chunk_count);
+        if (int rc2 = mark(a, stream)) return rc2;
+    }
+    return 0;
+}
+
+// The single call's loop (render_adaptive) for all views at once: per checkpoint ONE check over the N * n_tiles tiles, ONE compaction into
+// the sorted list of batch-global tiles, ONE read-back, ONE pass over the list.  A tile's history does not depend on its neighbours', so
+// every view ends with the words and C_t of its own single call; its `rounds` -- the passes that held one of ITS tiles -- follows on the
+// host from C_t before and after: a pass at checkpoint c held tile t iff old C_t <= c < new C_t (a fresh run's first pass: c = 0).
+template <typename CamT>
+int render_adaptive_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_adaptive_t *ad,
+                          const rtw_accum_handle *accums, void *d_out, void *stream_v) {
+    using T = typename std::conditional<sizeof(CamT) == sizeof(rtw_camera_f64), double, float>::type;
+    if (!p) return fail(-1, "null params");
+    if (!ad) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = validate_views(scene, cams, n_views, p, accums, &nch, &cs)) return rc;
+    rtw_adaptive_t eff;
+    if (int rc = validate_adaptive_params(ad, nch, &eff)) return rc;
+    if (int rc = validate_distinct(n_views, accums)) return rc;
+    std::vector<AccumBind> binds((size_t)n_views);
+    // (a mixed array is refused at its first view that fails either test, so WHICH -4 message it gets -- "bound by plain passes", "another
+    //  render", "all unbound or all adaptive" -- depends on the order of the views; the code does not)
+    for (int32_t v = 0; v < n_views; ++v) {          // every accumulator on its own, as rtw_render_adaptive_* validates it -- all before anything is touched
+        const rtw_params q = view_params(p, seeds, v);
+        int nv, cv;
+        if (int rc = validate_adaptive(scene, cams + v, &q, ad, accums[v], &nv, &cv, &eff)) return fail(rc, "view %d: %s", v, std::string(g_err).c_str());
+        make_bind(&binds[(size_t)v], scene, cams + v, &q, nch, cs);
+        if (accums[v]->bound != accums[0]->bound) return fail(-4, "view %d: the accumulators of a batch are all unbound or all adaptive accumulators of their views' renders", v);
+    }
+    DeviceGuard guard;
+    hipStream_t stream = (hipStream_t)stream_v;
+    HIP_TRY(hipSetDevice(scene->device));
+    const rtw_accum *a0 = accums[0];
+    const int n_tiles = n_tiles_of(a0), tiles_i = (a0->height + 7) / 8;
+    const long long n_all = (long long)n_views * n_tiles;            // (validate_batch: fits an int with room to spare)
+    const bool fresh = !a0->bound;
+    // (from here on a HIP failure can leave an unbound accumulator with its tile array allocated and cleared: nothing a caller can see --
+    //  words, binding and ranges are touched only behind a pass that was launched -- and what the next adaptive call expects to find or make)
+    for (int32_t v = 0; v < n_views; ++v) {
+        rtw_accum *a = accums[v];
+        if (!a->d_tiles) HIP_TRY(hipMalloc((void **)&a->d_tiles, ((size_t)n_tiles * 3u + 4u) * sizeof(int32_t)));
+        if (int rc = wait_for(a, stream)) return rc;
+        if (fresh) HIP_TRY(hipMemsetAsync(a->d_tiles, 0, (size_t)n_tiles * sizeof(int32_t), stream));
+        else if (!a->ad_complete || a->tile_chunks.size() != (size_t)n_tiles) {      // (after a call that failed half way: what the device holds)
+            a->tile_chunks.resize((size_t)n_tiles);
+            HIP_TRY(hipMemcpyAsync(a->tile_chunks.data(), a->d_tiles, (size_t)n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+        }
+    }
+    // the call's scratch, made once: the views' table | flags | list | count | the compaction's block offsets
+    struct Scratch { void *p = nullptr; ~Scratch() { if (p) HIP_IGNORE(hipFree(p)); } } scratch;
+    const size_t tab_bytes = ((size_t)n_views * sizeof(TileView) + 15u) / 16u * 16u;
+    const int n_blocks = (int)((n_all + 255) / 256);
+    HIP_TRY(hipMalloc(&scratch.p, tab_bytes + ((size_t)n_all * 2u + 4u + (size_t)n_blocks) * sizeof(int32_t)));
+    TileView *d_views = static_cast<TileView *>(scratch.p);
+    int32_t *d_flags = reinterpret_cast<int32_t *>(static_cast<char *>(scratch.p) + tab_bytes), *d_list = d_flags + n_all, *d_count = d_list + n_all, *d_blocks = d_count + 4;
+    // (measurement aid: RTW_BATCH_COMPACT=loop makes the list with the single call's one-workgroup loop -- the same list)
+    static const bool compact_loop = aid_env("RTW_BATCH_COMPACT") != nullptr && strcmp(aid_env("RTW_BATCH_COMPACT"), "loop") == 0;
+    std::vector<TileView> h_views((size_t)n_views);
+    std::vector<AccumViewPass> views((size_t)n_views);
+    std::vector<std::vector<int32_t>> old_chunks((size_t)n_views);
+    bool settled = !fresh;
+    int later_max = 0;                       // refinement: the last checkpoint some tile of some view stopped at
+    for (int32_t v = 0; v < n_views; ++v) {
+        rtw_accum *a = accums[v];
+        h_views[(size_t)v] = TileView{a->words, a->d_tiles};
+        views[(size_t)v] = AccumViewPass{a->words, 1};                // (no running image: the divisor is unused)
+        old_chunks[(size_t)v] = fresh ? std::vector<int32_t>((size_t)n_tiles, 0) : a->tile_chunks;
+        if (!fresh) for (int32_t c : a->tile_chunks) if (c < nch) later_max = std::max(later_max, (int)c);
+        settled = settled && a->ad_complete && eff.tolerance == a->ad.tolerance;
+    }
+    HIP_TRY(hipMemcpyAsync(d_views, h_views.data(), (size_t)n_views * sizeof(TileView), hipMemcpyHostToDevice, stream));    // (h_views outlives the call's last synchronisation)
+
+    release_last();
+    rtw_stats_t agg;
+    memset(&agg, 0, sizeof agg);
+    RenderRec *rec = nullptr;
+    CtxPtr ctx;
+    std::vector<int> pass_at;                // the checkpoints of this call's passes (0: a fresh run's first)
+    auto pass = [&](int begin, int count, const int32_t *list, int n_list) -> int {
+        AccumPass ps;
+        ps.words = nullptr; ps.chunk_begin = begin; ps.chunk_count = count; ps.samples = 1;
+        ps.adapt = true; ps.tile_list = list; ps.list_tiles = n_list; ps.views = views.data();
+        int rc = launch_accum_batch_t(scene, cams, n_views, seeds, p, ps, nullptr, stream, &rec, &ctx);
+        if (rc) { if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); rec = nullptr; } return rc; }     // (released by the next call)
+        (void)hipGetLastError();
+        hipLaunchKernelGGL(accum_tile_advance_batch_kernel, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, stream, list, n_list, d_views, n_tiles, count);
+        HIP_TRY(hipGetLastError());
+        pass_at.push_back(begin);
+        return 0;
+    };
+    auto finish = [&]() -> int {              // (behind a stream synchronisation) the last pass's counters -> agg; its record goes back to the pool
+        if (!rec) return 0;
+        rtw_stats_t one;
+        memset(&one, 0, sizeof one);
+        int rc = resolve_rec(rec, &one);
+        release_rec(ctx, rec, rc == 0);
+        rec = nullptr;
+        if (rc) return rc;
+        agg.samples += one.samples; agg.segments += one.segments; agg.sphere_tests += one.sphere_tests;
+        agg.kernel_ms += one.kernel_ms; agg.total_ms += one.total_ms;
+        agg.grid_blocks = std::max(agg.grid_blocks, one.grid_blocks); agg.block_threads = std::max(agg.block_threads, one.block_threads);
+        return 0;
+    };
+    auto run = [&]() -> int {
+        const int first = std::min((int)eff.min_chunks, nch);
+        long long moved = 0;                    // tiles the last pass brought to the checkpoint at hand
+        if (fresh) {
+            if (int rc = pass(0, first, nullptr, (int)n_all)) return rc;
+            for (int32_t v = 0; v < n_views; ++v) { rtw_accum *a = accums[v]; a->bind = binds[(size_t)v]; a->bound = true; a->adaptive = true; a->ad = eff; }
+            moved = n_all;
+        }
+        for (int32_t v = 0; v < n_views; ++v) { accums[v]->ad.tolerance = eff.tolerance; accums[v]->ad_complete = false; }
+        for (int c = first; c < nch && !settled; c += eff.check_chunks) {
+            if (moved == 0 && c > later_max) break;
+            (void)hipGetLastError();
+            hipLaunchKernelGGL(accum_tile_check_batch_kernel, dim3((unsigned)((n_all + 3) / 4)), dim3(256), 0, stream, d_views, d_flags, (int)n_views, n_tiles, tiles_i,
+                               (int)a0->width, (int)a0->height, c, (double)((long long)c * cs), eff.tolerance, eff.dark_floor);
+            if (compact_loop) {
+                hipLaunchKernelGGL(accum_tile_compact_kernel, dim3(1), dim3(1024), 0, stream, d_flags, d_list, d_count, (int)n_all);
+            } else {
+                hipLaunchKernelGGL(accum_tile_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, d_flags, d_blocks, (int)n_all);
+                hipLaunchKernelGGL(accum_tile_scan_kernel, dim3(1), dim3(1024), 0, stream, d_blocks, d_count, n_blocks);
+                hipLaunchKernelGGL(accum_tile_scatter_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, d_flags, d_blocks, d_list, (int)n_all);
+            }
+            HIP_TRY(hipGetLastError());
+            int32_t n_active = 0;
+            HIP_TRY(hipMemcpyAsync(&n_active, d_count, sizeof n_active, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (int rc = finish()) return rc;
+            if (n_active < 0 || n_active > n_all) return fail(-3, "adaptive batch: %d active tiles of %lld", n_active, n_all);
+            moved = n_active;
+            if (n_active == 0) continue;
+            if (int rc = pass(c, std::min((int)eff.check_chunks, nch - c), d_list, n_active)) return rc;
+        }
+        for (int32_t v = 0; v < n_views; ++v) {
+            rtw_accum *a = accums[v];
+            a->tile_chunks.resize((size_t)n_tiles);
+            HIP_TRY(hipMemcpyAsync(a->tile_chunks.data(), a->d_tiles, (size_t)n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        }
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (int rc = finish()) return rc;
+        for (int32_t v = 0; v < n_views; ++v) {
+            rtw_accum *a = accums[v];
+            const std::vector<int32_t> &was = old_chunks[(size_t)v];
+            int min_c = nch, rounds = 0;
+            for (int32_t c : a->tile_chunks) min_c = std::min(min_c, (int)c);
+            for (int at : pass_at) {
+                bool held = false;
+                for (int t = 0; t < n_tiles && !held; ++t) held = was[(size_t)t] <= at && at < a->tile_chunks[(size_t)t];
+                rounds += held ? 1 : 0;
+            }
+            a->ranges.clear();
+            a->ranges.emplace_back(0, min_c);
+            a->ad_complete = true;
+            a->ad_rounds = rounds;
+            if (d_out)
+                if (int rc = resolve_dev<T>(a, p->gamma, static_cast<T *>(d_out) + (size_t)v * n_pixels(a) * 3u, stream)) return rc;
+        }
+        if (d_out) HIP_TRY(hipStreamSynchronize(stream));
+        return 0;
+    };
+    const int rc = run();
+    if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); }       // (a failure between a pass and its wait)
+    if (rc) {
+        for (int32_t v = 0; v < n_views; ++v) if (accums[v]->bound) HIP_IGNORE(hipEventRecord(accums[v]->ev, stream));
+        HIP_IGNORE(hipStreamSynchronize(stream));                               // (the scratch is freed on return)
+        return rc;
+    }
+    agg.n_chunks = nch;
+    g_last.agg = agg;
+    g_last.resolved = true;
+    g_last.per_device.emplace_back(scene->device, agg.kernel_ms);
+    for (int32_t v = 0; v < n_views; ++v) if (int rc2 = mark(accums[v], stream)) return rc2;
+    return 0;
+}
+
 int adaptive_info(const rtw_accum *a, rtw_adaptive_info_t *out) {
     memset(out, 0, sizeof *out);
     const int tiles_i = (a->height + 7) / 8, tiles_j = (a->width + 7) / 8, nch = a->bind.n_chunks;
@@ -558,6 +873,23 @@ int rtw_render_adaptive_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, c
 int rtw_render_adaptive_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_adaptive_t *adaptive,
                             rtw_accum_handle a, void *d_out, void *stream) {
     return render_adaptive(scene, cam, p, adaptive, a, d_out, stream);
+}
+
+int rtw_render_accum_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin,
+                               int32_t chunk_count, const rtw_accum_handle *accums, void *d_out, void *stream) {
+    return render_accum_batch(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, accums, d_out, stream);
+}
+int rtw_render_accum_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin,
+                               int32_t chunk_count, const rtw_accum_handle *accums, void *d_out, void *stream) {
+    return render_accum_batch(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, accums, d_out, stream);
+}
+int rtw_render_adaptive_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
+                                  const rtw_adaptive_t *adaptive, const rtw_accum_handle *accums, void *d_out, void *stream) {
+    return render_adaptive_batch(scene, cams, n_views, seeds, p, adaptive, accums, d_out, stream);
+}
+int rtw_render_adaptive_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
+                                  const rtw_adaptive_t *adaptive, const rtw_accum_handle *accums, void *d_out, void *stream) {
+    return render_adaptive_batch(scene, cams, n_views, seeds, p, adaptive, accums, d_out, stream);
 }
 
 int rtw_accum_adaptive_info(rtw_accum_handle a, rtw_adaptive_info_t *out) {

@@ -107,6 +107,16 @@ struct AccumArgs {
     int chunk_begin;                // global index of this pass's chunk 0: what the item's RNG stream and sample indices are made from
     int samples;                    // samples in the accumulator INCLUDING this pass: the divisor of the running image
     const int *tile_list;           // ADAPT instances, KParams::shard_count == 0: local tile k is global tile tile_list[k] (local_tiles entries)
+    const struct AccumView *views;  // BATCH && ACCUM instances: one entry per view (`words` and `samples` above are then unused)
+};
+// Batched progressive / adaptive render (rtw_render_accum_batch_*, rtw_render_adaptive_batch_*; the BATCH && ACCUM instances): view v of
+// the batch (BatchArgs, JobSlot::pad) adds its jobs to its OWN accumulator and divides its running image by its OWN sample count.  A
+// listed pass (ADAPT) numbers the tiles batch-globally, v * tiles_i * tiles_jv + t: tile t of view v is tile column v * tiles_jv + tj of
+// the frame N views wide, so the list entry splits into (ti, tj) and tj into (view, column) exactly as a full-frame batch job does.
+struct AccumView {
+    unsigned long long *words;      // view v's accumulator
+    int samples;                    // samples it holds INCLUDING this pass
+    int pad;
 };
 // Adaptive render (rtw_render_adaptive_*; the ADAPT instances of trace_kernel, all of them ACCUM instances): a pass renders its chunks
 // for the tiles of a device-resident list only (open_job), and every sample also adds its noise statistic to word 7 of the pixel's slot --
@@ -406,7 +416,8 @@ __device__ __forceinline__ int claim_job(const KParams &P, DevCounters *ctr, Job
 // image (or every queue is exhausted), zero its accumulators and fill in the block's header.
 // S->job: the job's queue position, RTW_JOB_EOF (every queue is exhausted for good) or -- WITH_RETRY only -- RTW_JOB_RETRY (claim_job's "try again";
 // without WITH_RETRY the claim is repeated here until it is decided).
-// BATCH: the tile column tj of the queues is view v's column tj - v * tiles_jv (BatchArgs); v goes to S->pad.
+// BATCH: the tile column tj of the queues is view v's column tj - v * tiles_jv (BatchArgs); v goes to S->pad.  With ADAPT the list's
+// tiles are batch-global and split the same way.
 // ADAPT: outside a full frame (P.shard_count == 0) local tile k is global tile tile_list[k] -- the sharded render's hook with a list in
 // the place of k * shard_count + shard_index; the queues, the claims and the scheduling see a shard of P.local_tiles tiles.
 template <bool WITH_RETRY = false, bool BATCH = false, bool ADAPT = false>
@@ -437,6 +448,7 @@ __device__ RTW_RARE_ATTR void open_job(const KParams &P, JobSlot *S, unsigned la
             if constexpr (ADAPT) t = uniform((unsigned)tile_list[k]);
             else t = k * (unsigned)P.shard_count + (unsigned)P.shard_index;
             tj = udiv_magic(t, P.div_tiles_m, P.div_tiles_s); ti = t - tj * (unsigned)P.tiles_i;
+            if constexpr (BATCH && ADAPT) { view = udiv_magic(tj, div_tjv_m, div_tjv_s); tj -= view * tiles_jv; }      // (a batch-global tile: AccumView)
         }
         i_base = (int)(ti * 8u + ((q & ((1u << bps_shift) - 1u)) << rs));
         j_base = (int)(tj * 8u + ((q >> bps_shift) << cs));
@@ -468,10 +480,12 @@ __device__ RTW_RARE_ATTR void open_job(const KParams &P, JobSlot *S, unsigned la
 // small render; the item's chunk is accum.chunk_begin + its local chunk wherever it has a meaning (RNG stream, sample indices); `out`
 // may be null (no running image); otherwise `accum` is unused.
 // ADAPT (with ACCUM): a pass of an adaptive render (AccumArgs::tile_list): the tiles of a list, and the half difference in word 7.
+// BATCH && ACCUM (&& ADAPT): a pass of N views' progressive (adaptive) renders: the view picks camera and seed as in a batch, the
+// accumulator and the divisor from AccumArgs::views; chunks and parity are global as in every ACCUM instance.
 template <typename T, bool PROFILE, bool LDS_SCENE, bool CULL, bool MFMA = false, int NUMK = -1, bool BATCH = false, bool ACCUM = false, bool ADAPT = false>
 __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void trace_kernel(KParams P_arg, Camera<T> cam_arg, DevScene<T> scene,
                                                    CullScene<T> cull, T *__restrict__ out, DevCounters *ctr, BatchArgs<T> batch, AccumArgs accum) {
-    static_assert(!(BATCH && ACCUM) && !(PROFILE && ACCUM), "no batched and no phase-profile ACCUM instances");
+    static_assert(!(PROFILE && ACCUM), "no phase-profile ACCUM instances");
     static_assert(!ADAPT || ACCUM, "an ADAPT instance is an ACCUM instance");
     using V4 = typename Vec4<T>::type;
     if constexpr (NUMK >= 0) { scene.numerics = NUMK; cull.numerics = NUMK; }
@@ -627,7 +641,14 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                 const int L = __builtin_ctzll(fin);
                 fin &= fin - 1ull;
                 JobSlot *S = sh->slot(uniform((unsigned)__shfl((int)((ref_depth & RTW_REF_MASK) >> 4), L)), P.slot_stride);
-                if constexpr (BATCH) store_job<T>(P, S, lane, out + (size_t)uniform(S->pad) * batch.view_elems);
+                if constexpr (BATCH && ACCUM) {
+                    // the view's own accumulator and divisor; its frame of the running image
+                    const unsigned v = uniform(S->pad);
+                    AccumArgs av = accum;
+                    av.words = accum.views[v].words; av.samples = accum.views[v].samples;
+                    store_job_accum<T, ADAPT>(P, S, lane, out ? out + (size_t)v * batch.view_elems : out, av);
+                }
+                else if constexpr (BATCH) store_job<T>(P, S, lane, out + (size_t)uniform(S->pad) * batch.view_elems);
                 else if constexpr (ADAPT) store_job_accum<T, true>(P, S, lane, out, accum);
                 else if constexpr (ACCUM) store_job_accum<T>(P, S, lane, out, accum);
                 else store_job<T>(P, S, lane, out);
@@ -677,7 +698,8 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                                                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) ? 1u : 0u;
                         }
                         if (uniform(won)) {
-                            if constexpr (BATCH) open_job<RTW_OPEN_RETRY != 0, true>(P, S, lane, ctr, &sh->jobs, batch.tiles_jv, batch.div_tjv_m, batch.div_tjv_s);
+                            if constexpr (BATCH && ADAPT) open_job<RTW_OPEN_RETRY != 0, true, true>(P, S, lane, ctr, &sh->jobs, batch.tiles_jv, batch.div_tjv_m, batch.div_tjv_s, accum.tile_list);
+                            else if constexpr (BATCH) open_job<RTW_OPEN_RETRY != 0, true>(P, S, lane, ctr, &sh->jobs, batch.tiles_jv, batch.div_tjv_m, batch.div_tjv_s);
                             else if constexpr (ADAPT) open_job<RTW_OPEN_RETRY != 0, false, true>(P, S, lane, ctr, &sh->jobs, 0u, 0u, 0u, accum.tile_list);
                             else open_job<RTW_OPEN_RETRY != 0>(P, S, lane, ctr, &sh->jobs);
                             const unsigned opened = uniform(S->job);
@@ -713,7 +735,8 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                         const unsigned rsh = P.rows_shift;
                         const int i0 = S->i_base + (int)(px & ((1u << rsh) - 1u)), j0 = S->j_base + (int)(px >> rsh);
                         Rng r0;
-                        if constexpr (BATCH) rng_stream(batch.seeds[uniform(S->pad)], (unsigned long long)j0 * (unsigned)P.height + (unsigned)i0, chunk, r0);
+                        if constexpr (BATCH && ACCUM) rng_stream(batch.seeds[uniform(S->pad)], (unsigned long long)j0 * (unsigned)P.height + (unsigned)i0, chunk + (unsigned)accum.chunk_begin, r0);
+                        else if constexpr (BATCH) rng_stream(batch.seeds[uniform(S->pad)], (unsigned long long)j0 * (unsigned)P.height + (unsigned)i0, chunk, r0);
                         else if constexpr (ACCUM) rng_stream(P.seed, (unsigned long long)j0 * (unsigned)P.height + (unsigned)i0, chunk + (unsigned)accum.chunk_begin, r0);
                         else rng_stream(P.seed, (unsigned long long)j0 * (unsigned)P.height + (unsigned)i0, chunk, r0);
                         __builtin_amdgcn_wave_barrier();                      // (the previous batch's states have all been read)
@@ -739,7 +762,8 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
                             const unsigned rsh = P.rows_shift;
                             const int i0 = S->i_base + (int)(px & ((1u << rsh) - 1u)), j0 = S->j_base + (int)(px >> rsh);
                             const unsigned long long pix = (unsigned long long)j0 * (unsigned)P.height + (unsigned)i0;
-                            if constexpr (BATCH) rng_stream(batch.seeds[uniform(S->pad)], pix, chunk, rng);
+                            if constexpr (BATCH && ACCUM) rng_stream(batch.seeds[uniform(S->pad)], pix, chunk + (unsigned)accum.chunk_begin, rng);
+                            else if constexpr (BATCH) rng_stream(batch.seeds[uniform(S->pad)], pix, chunk, rng);
                             else if constexpr (ACCUM) rng_stream(P.seed, pix, chunk + (unsigned)accum.chunk_begin, rng);
                             else rng_stream(P.seed, pix, chunk, rng);
                         }

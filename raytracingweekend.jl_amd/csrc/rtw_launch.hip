@@ -27,6 +27,8 @@ void make_udiv(unsigned d, unsigned *m, unsigned *s) {
 // render of chunk_count chunks; `d_out` may be null.  pass->adapt: a pass of an adaptive render (the ADAPT instances: the half difference
 // in word 7); with pass->tile_list also a pass over the pass->list_tiles tiles of that device-resident list only -- scheduled like a shard
 // of that many tiles (K.shard_count = 0 marks it).
+// n_views >= 1 AND `pass`: one pass of n_views progressive (adaptive) renders (the BATCH && ACCUM instances, rtw_batch_accum.hpp):
+// pass->views holds every view's accumulator and divisor, a tile list numbers the tiles batch-globally (v * n_tiles + t).
 template <typename T, typename CamT>
 int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
                   RenderRec **rec_out, CtxPtr *ctx_out, const AccumPass *pass = nullptr) {
@@ -62,8 +64,9 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
     rtw::AccumArgs A;
     memset(&A, 0, sizeof A);
     if (pass) { A.words = pass->words; A.chunk_begin = pass->chunk_begin; A.samples = pass->samples; A.tile_list = pass->adapt ? pass->tile_list : nullptr; }
+    if (batch && pass && !pass->views) return fail(-1, "null argument");
     if (listed && (pass->list_tiles < 0 || pass->list_tiles > (long long)K.tiles_i * K.tiles_j)) return fail(-2, "tile list of %d entries", pass->list_tiles);
-    const long long n_local = batch ? (long long)K.tiles_i * K.tiles_j : listed ? (long long)pass->list_tiles : local_tiles(p);
+    const long long n_local = listed ? (long long)pass->list_tiles : batch ? (long long)K.tiles_i * K.tiles_j : local_tiles(p);
     K.gamma = p->gamma;
     K.out_layout = (p->flags & RTW_FLAG_COMPACT_TILES) ? 1 : 0;
     make_udiv((unsigned)K.tiles_i, &K.div_tiles_m, &K.div_tiles_s);
@@ -137,6 +140,11 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
         else kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false, false, -1, false, true, true> : (kern_t)rtw::trace_kernel<T, false, false, false, false, -1, false, true, true>;
         if (S.numerics == rtw::NUM_REFERENCE && lds_scene && mfma)
             kern = cull ? (kern_t)rtw::trace_kernel<T, false, true, true, true, rtw::NUM_REFERENCE, false, true, true> : (kern_t)rtw::trace_kernel<T, false, true, false, true, rtw::NUM_REFERENCE, false, true, true>;
+    }
+    // a pass of a batch of progressive / adaptive renders: the same choice among the BATCH && ACCUM instances (a translation unit per precision)
+    if (batch && pass) {
+        const bool fixed = S.numerics == rtw::NUM_REFERENCE && lds_scene && mfma;
+        kern = (kern_t)(sizeof(T) == 8 ? batch_accum_kernel_f64(cull, mfma, lds_scene, fixed, pass->adapt) : batch_accum_kernel_f32(cull, mfma, lds_scene, fixed, pass->adapt));
     }
     // The ray-pool kernel (rtw_pool.hpp; opt-in: RTW_FLAG_RAY_POOL, or RTW_POOL=1 in the environment for A/B runs) exists in `make POOL=1`
     // builds only: Float32 plain scans on the matrix pipe, when the pool, the rings and the scene copy fit the 160 KB of LDS of a CU (one
@@ -242,7 +250,10 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
     if (batch) {
         // the views' cameras and seeds: into the record's pinned buffer, then ONE asynchronous H2D on the render's stream (the record is
         // handed out again only after ev2, behind this copy, so the pinned buffer is free whenever a render holds the record)
-        const size_t cam_bytes = (size_t)n_views * sizeof(rtw::Camera<T>), bytes = cam_bytes + (size_t)n_views * sizeof(unsigned long long);
+        // (a batched pass: behind them the views' accumulators and divisors, rtw::AccumView)
+        const size_t cam_bytes = (size_t)n_views * sizeof(rtw::Camera<T>), seed_bytes = (size_t)n_views * sizeof(unsigned long long);
+        static_assert(sizeof(rtw::Camera<T>) % 8 == 0, "the seeds and the view table behind the cameras are 8-byte aligned");
+        const size_t bytes = cam_bytes + seed_bytes + (pass ? (size_t)n_views * sizeof(rtw::AccumView) : 0);
         if (rec->views_cap < bytes) {
             if (rec->d_views) { HIP_IGNORE(hipFree(rec->d_views)); rec->d_views = nullptr; }
             if (rec->h_views) { HIP_IGNORE(hipHostFree(rec->h_views)); rec->h_views = nullptr; }
@@ -261,6 +272,11 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
             }
             hc[v].lens_radius = cam[v].lens_radius;
             hs[v] = seeds ? seeds[v] : p->seed;
+        }
+        if (pass) {
+            rtw::AccumView *hv = reinterpret_cast<rtw::AccumView *>(static_cast<char *>(rec->h_views) + cam_bytes + seed_bytes);
+            for (int v = 0; v < n_views; ++v) { hv[v].words = pass->views[v].words; hv[v].samples = pass->views[v].samples; hv[v].pad = 0; }
+            A.views = reinterpret_cast<const rtw::AccumView *>(static_cast<const char *>(rec->d_views) + cam_bytes + seed_bytes);
         }
         HIP_TRY(hipMemcpyAsync(rec->d_views, rec->h_views, bytes, hipMemcpyHostToDevice, stream));
         B.cams = reinterpret_cast<const rtw::Camera<T> *>(rec->d_views);
@@ -374,6 +390,14 @@ int launch_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_v
 int launch_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
                      RenderRec **rec_out, CtxPtr *ctx_out) {
     return launch_render<double>(scene, cams, n_views, seeds, p, d_out, stream, rec_out, ctx_out);
+}
+int launch_accum_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, const AccumPass &pass, void *d_out,
+                           hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out) {
+    return launch_render<float>(scene, cams, n_views, seeds, p, d_out, stream, rec_out, ctx_out, &pass);
+}
+int launch_accum_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, const AccumPass &pass, void *d_out,
+                           hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out) {
+    return launch_render<double>(scene, cams, n_views, seeds, p, d_out, stream, rec_out, ctx_out, &pass);
 }
 int launch_accum_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const AccumPass &pass, void *d_out, hipStream_t stream,
                      RenderRec **rec_out, CtxPtr *ctx_out) {

@@ -224,6 +224,117 @@ class ProgressiveRenderer:
             pass
 
 
+class ProgressiveBatchRenderer:
+    """N views of ONE scene -- same size, samples, chunks and depth; a camera and a seed per view -- each with its own exact accumulator,
+    every pass ONE kernel launch for all of them (``rtw_render_accum_batch_*``).  View ``v`` is, bit for bit, the
+    ``ProgressiveRenderer`` of ``cams[v]`` and ``seeds[v]``: the same words, ranges and image after the same chunks.
+
+    ``seeds``: one int for every view, or a sequence of N.  ``add_range`` enqueues the chunks ``[begin, begin + count)`` of every view
+    (asynchronous on ``stream``); ``images()`` resolves what has been added so far; ``read_pixels(v)`` / ``info(v)`` / ``ranges(v)``
+    look at one view."""
+
+    def __init__(self, scene, cams, image_width=400, n_samples=1, *, depth=16, seeds=1, n_chunks=0, device=-1, numerics=None):
+        cams = list(cams)
+        if not cams or not all(isinstance(c, Camera) for c in cams):
+            raise TypeError("cams must be a non-empty sequence of Camera")
+        self.T = cams[0].elem_type
+        if any(np.dtype(c.elem_type) != np.dtype(self.T) for c in cams):
+            raise TypeError("the cameras of a batch share one element type")
+        self.n_views = len(cams)
+        self.width, self.height = int(image_width), image_height(image_width)
+        if self.width <= 0 or self.height <= 0:
+            raise ValueError(f"image_width={image_width} gives an empty {self.height} x {image_width} image")
+        self.n_samples, self.depth = int(n_samples), int(depth)
+        self.n_chunks, self.chunk_spp = effective_chunks(n_samples, n_chunks)          # (ValueError for n_samples < 1)
+        self._n_chunks_arg = int(n_chunks)
+        self.numerics = _capi.numerics_name(numerics)
+        self.seeds = _capi.make_seeds(seeds, self.n_views)                           # (ValueError for a wrong count)
+        self.cams = _capi.make_cameras(cams, self.T)
+        self.L = _capi.lib()
+        self.handle, self.accums = C.c_void_p(), []
+        flat = flatten_scene(scene, self.T)
+        S, keep = _capi.make_scene(flat, self.T)
+        up = self.L.rtw_scene_upload_f64 if _capi.is_f64(self.T) else self.L.rtw_scene_upload_f32
+        _capi.check(up(C.byref(S), int(device), C.byref(self.handle)))
+        del keep
+        try:
+            for _ in range(self.n_views):
+                acc = C.c_void_p()
+                _capi.check(self.L.rtw_accum_create(int(device), self.width, self.height, C.byref(acc)))
+                self.accums.append(acc)
+        except Exception:
+            self.close()
+            raise
+        self._handles = _capi.make_handles(self.accums)
+
+    def _params(self, group_cull, scan_valu, job_pixels, gamma):
+        flags = (_capi.FLAG_GROUP_CULL if group_cull else 0) | (_capi.FLAG_SCAN_VALU if scan_valu else 0)
+        return _capi.make_params(self.width, self.height, self.n_samples, self.depth, 0, self._n_chunks_arg, 0, 1, -1,
+                                 1 if gamma else 0, flags, job_pixels=job_pixels, numerics=self.numerics)
+
+    def add_range(self, begin, count, *, group_cull=False, scan_valu=False, job_pixels=0, d_out=None, gamma=True, stream=0):
+        """Enqueue the chunks ``[begin, begin + count)`` of every view in one launch; ``d_out``: a device pointer that receives the N
+        running images (N*H*W*3 elements, frame after frame)."""
+        P = self._params(group_cull, scan_valu, job_pixels, gamma)
+        fn = self.L.rtw_render_accum_batch_f64 if _capi.is_f64(self.T) else self.L.rtw_render_accum_batch_f32
+        _capi.check(fn(self.handle, self.cams, self.n_views, self.seeds, C.byref(P), int(begin), int(count), self._handles,
+                       C.c_void_p(int(d_out)) if d_out else None, C.c_void_p(int(stream))))
+
+    def images(self, gamma=True):
+        """The images of the samples added so far (blocking): ``imgs[v, i, j, :]``, view ``v`` like ``render``'s image."""
+        out = np.empty((self.n_views, self.height * self.width * 3), dtype=self.T)
+        fn = self.L.rtw_accum_resolve_host_f64 if _capi.is_f64(self.T) else self.L.rtw_accum_resolve_host_f32
+        for v, acc in enumerate(self.accums):
+            _capi.check(fn(acc, 1 if gamma else 0, out[v].ctypes.data_as(C.c_void_p)))
+        return np.stack([_as_image(out[v], self.height, self.width) for v in range(self.n_views)])
+
+    def read_pixels(self, v):
+        """View ``v``'s accumulator (blocking): ``words[i, j, :]`` as ``ProgressiveRenderer.read_pixels``."""
+        out = np.empty(self.height * self.width * 8, dtype=np.uint64)
+        _capi.check(self.L.rtw_accum_read_pixels(self.accums[v], out.ctypes.data_as(C.c_void_p)))
+        return out.reshape(self.width, self.height, 8).transpose(1, 0, 2)
+
+    def info(self, v):
+        st = _capi.AccumInfo()
+        _capi.check(self.L.rtw_accum_info(self.accums[v], C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def ranges(self, v):
+        """the chunk ranges view ``v`` holds: sorted list of ``(begin, end)``, end exclusive"""
+        n = C.c_int32(0)
+        _capi.check(self.L.rtw_accum_ranges(self.accums[v], 0, C.byref(n), None))
+        buf = (C.c_int32 * (2 * max(n.value, 1)))()
+        _capi.check(self.L.rtw_accum_ranges(self.accums[v], n.value, C.byref(n), buf))
+        return [(int(buf[2 * k]), int(buf[2 * k + 1])) for k in range(n.value)]
+
+    def stats(self):
+        """Counters / kernel time of the calling thread's last call (waits for it): the sums over the views."""
+        st = _capi.Stats()
+        _capi.check(self.L.rtw_stats(C.byref(st)))
+        return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def close(self):
+        for acc in getattr(self, "accums", []):
+            if acc:
+                self.L.rtw_accum_free(acc)
+        self.accums = []
+        if getattr(self, "handle", None):
+            self.L.rtw_scene_free(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def render_progressive(scene, cam, image_width=400, n_samples=1, *, passes=4, callback=None, depth=16, seed=1, n_chunks=0, device=-1,
                        gamma=True, group_cull=False, scan_valu=False, numerics=None):
     """``render(...)`` in ``passes`` passes of (nearly) equal chunk counts; the return value equals ``render``'s with the same

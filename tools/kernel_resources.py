@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Register / scratch / occupancy table of every trace_kernel instantiation (hipcc -Rpass-analysis=kernel-resource-usage).
-usage: python tools/kernel_resources.py [extra hipcc flags]   (cross-compiles for gfx950, no GPU needed)"""
+usage: python tools/kernel_resources.py [extra hipcc flags]   (cross-compiles for gfx950, no GPU needed)
+The instances live in rtw_launch.hip and, the BATCH && ACCUM ones, in rtw_batch_accum_f32.hip / _f64.hip: one table over all three."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-src = os.path.join(ROOT, "raytracingweekend.jl_amd", "csrc", "rtw_launch.hip")
-cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form",
-       "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/dev/null"] + sys.argv[1:]
-out = subprocess.run(cmd, capture_output=True, text=True).stderr
+out = ""
+for unit in ("rtw_launch.hip", "rtw_batch_accum_f32.hip", "rtw_batch_accum_f64.hip"):
+    src = os.path.join(ROOT, "raytracingweekend.jl_amd", "csrc", unit)
+    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form",
+           "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/dev/null"] + sys.argv[1:]
+    out += subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], None
 for line in out.splitlines():
     m = re.search(r"Function Name: (\S+)", line)
