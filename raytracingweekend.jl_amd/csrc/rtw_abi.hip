@@ -172,7 +172,7 @@ int render_device_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_view
     RenderRec *rec = nullptr;
     CtxPtr ctx;
     release_last();
-    int rc = launch_batch_t(scene, cams, n_views, seeds, p, d_out, (hipStream_t)stream_v, &rec, &ctx);
+    int rc = launch_render_t(scene, cams, n_views, seeds, p, d_out, (hipStream_t)stream_v, &rec, &ctx);
     if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); }       // (also on a late error: released by the next call)
     return rc;
 }
@@ -184,7 +184,7 @@ int render_device(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, 
     RenderRec *rec = nullptr;
     CtxPtr ctx;
     release_last();
-    int rc = launch_render_t(scene, cam, p, d_out, (hipStream_t)stream_v, &rec, &ctx);
+    int rc = launch_render_t(scene, cam, 0, nullptr, p, d_out, (hipStream_t)stream_v, &rec, &ctx);
     if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); }       // (also on a late error: released by the next call)
     return rc;
 }

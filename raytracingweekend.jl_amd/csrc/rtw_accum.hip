@@ -31,7 +31,7 @@ struct rtw_accum {
     bool adaptive = false;
     bool ad_complete = false;                      // no tile is active under ad.tolerance (false only after a call that failed half way)
     rtw_adaptive_t ad;                             // the last call's, min_chunks / check_chunks as their effective values
-    int32_t ad_rounds = 0;                         // passes of the last call
+    int32_t ad_rounds = 0;                         // passes of the last call that held one of its tiles
     int32_t *d_tiles = nullptr;                    // device memory, 3 n_tiles + 4 int32: C_t | active flags | active list | count (made by the first adaptive call)
     std::vector<int32_t> tile_chunks;              // host copy of C_t, read back at the end of every call
 };
@@ -395,28 +395,46 @@ int validate_accum(rtw_scene_handle scene, const CamT *cam, const rtw_params *p,
     return 0;
 }
 
+// One pass after its validation, for the n_views >= 1 accumulators of a call (`binds`: what each is, or will be, bound to): wait for their
+// events, launch, bind, add the range, mark.  `single`: the call came in through rtw_render_accum_* -- the one view's words and divisor
+// travel in the pass itself and the non-BATCH instance runs; otherwise the view array and the BATCH instance.
+template <typename CamT>
+int accum_pass(bool single, rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count,
+               const rtw_accum_handle *accums, const AccumBind *binds, void *d_out, void *stream_v) {
+    DeviceGuard guard;
+    hipStream_t stream = (hipStream_t)stream_v;
+    HIP_TRY(hipSetDevice(scene->device));
+    std::vector<AccumViewPass> views((size_t)n_views);
+    for (int32_t v = 0; v < n_views; ++v) {
+        if (int rc = wait_for(accums[v], stream)) return rc;
+        views[(size_t)v].words = accums[v]->words;
+        views[(size_t)v].samples = (int)(samples_done(accums[v]) + samples_in(binds[v], chunk_begin, (long long)chunk_begin + chunk_count));
+    }
+    AccumPass pass;
+    pass.words = single ? views[0].words : nullptr; pass.chunk_begin = chunk_begin; pass.chunk_count = chunk_count; pass.samples = single ? views[0].samples : 1;
+    pass.views = single ? nullptr : views.data();
+    RenderRec *rec = nullptr;
+    CtxPtr ctx;
+    release_last();
+    int rc = launch_render_t(scene, cams, single ? 0 : n_views, seeds, p, d_out, stream, &rec, &ctx, &pass);
+    if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); }       // (also on a late error: released by the next call)
+    if (rc) return rc;
+    for (int32_t v = 0; v < n_views; ++v) {
+        rtw_accum *a = accums[v];
+        a->bind = binds[v]; a->bound = true;
+        add_range(a->ranges, chunk_begin, chunk_begin + chunk_count);
+        if (int rc2 = mark(a, stream)) return rc2;
+    }
+    return 0;
+}
+
 template <typename CamT>
 int render_accum(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, rtw_accum_handle a, void *d_out, void *stream_v) {
     int nch, cs;
     if (int rc = validate_accum(scene, cam, p, chunk_begin, chunk_count, a, &nch, &cs)) return rc;
     AccumBind b;
     make_bind(&b, scene, cam, p, nch, cs);
-    DeviceGuard guard;
-    hipStream_t stream = (hipStream_t)stream_v;
-    HIP_TRY(hipSetDevice(a->device));
-    if (int rc = wait_for(a, stream)) return rc;
-    AccumPass pass;
-    pass.words = a->words; pass.chunk_begin = chunk_begin; pass.chunk_count = chunk_count;
-    pass.samples = (int)(samples_done(a) + samples_in(b, chunk_begin, (long long)chunk_begin + chunk_count));
-    RenderRec *rec = nullptr;
-    CtxPtr ctx;
-    release_last();
-    int rc = launch_accum_t(scene, cam, p, pass, d_out, stream, &rec, &ctx);
-    if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); }       // (also on a late error: released by the next call)
-    if (rc) return rc;
-    a->bind = b; a->bound = true;
-    add_range(a->ranges, chunk_begin, chunk_begin + chunk_count);
-    return mark(a, stream);
+    return accum_pass(true, scene, cam, 1, nullptr, p, chunk_begin, chunk_count, &a, &b, d_out, stream_v);
 }
 
 // ---- adaptive render ----
@@ -458,47 +476,86 @@ int validate_adaptive(rtw_scene_handle scene, const CamT *cam, const rtw_params 
     return 0;
 }
 
-// The loop: [0, min_chunks) on all tiles, then per checkpoint c: check the tiles that hold exactly c chunks, list the ones not converged,
-// read the list's length back (the round's one host wait), render [c, c + check_chunks) for the list.  A refinement walks the same
-// checkpoints: a tile that stopped at c under the looser tolerance is looked at again at c, where a fresh run would have decided it.
+// The loop, after the validation, for the n_views >= 1 accumulators of a call: [0, min_chunks) on all tiles, then per checkpoint c: check
+// the tiles that hold exactly c chunks, list the ones not converged, read the list's length back (the round's one host wait), render
+// [c, c + check_chunks) for the list.  A refinement walks the same checkpoints: a tile that stopped at c under the looser tolerance is
+// looked at again at c, where a fresh run would have decided it.  For a batch that is ONE check over the N * n_tiles tiles, ONE compaction
+// into the sorted list of batch-global tiles, ONE read-back and ONE pass over the list per checkpoint; a tile's history does not depend on
+// its neighbours', so every view ends with the words and C_t of its own single call.  A view's `rounds` -- the passes that held one of ITS
+// tiles -- follows on the host from C_t before and after: a pass at checkpoint c held tile t iff old C_t <= c < new C_t (a fresh run's
+// first pass: c = 0); every pass of a single call holds one of its tiles, so there it is the number of passes.
+// `single`: the call came in through rtw_render_adaptive_*.  It decides the three launch sites of a round and nothing else: the check
+// (accum_tile_check_kernel on the accumulator's own flags / list / count in d_tiles, or accum_tile_check_batch_kernel on the call's
+// scratch and view table), the compaction (one workgroup's loop, or count / scan / scatter) and the pass (the ACCUM && ADAPT instance
+// with accum_tile_advance_kernel, or the BATCH one with accum_tile_advance_batch_kernel) -- a batch of one view runs the BATCH kernels.
 template <typename CamT>
-int render_adaptive(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, const rtw_adaptive_t *ad, rtw_accum_handle a, void *d_out, void *stream_v) {
+int adaptive_loop(bool single, rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_adaptive_t &eff, int nch, int cs,
+                  const rtw_accum_handle *accums, const AccumBind *binds, void *d_out, void *stream_v) {
     using T = typename std::conditional<sizeof(CamT) == sizeof(rtw_camera_f64), double, float>::type;
-    int nch, cs;
-    rtw_adaptive_t eff;
-    if (int rc = validate_adaptive(scene, cam, p, ad, a, &nch, &cs, &eff)) return rc;
-    AccumBind b;
-    make_bind(&b, scene, cam, p, nch, cs);
     DeviceGuard guard;
     hipStream_t stream = (hipStream_t)stream_v;
-    HIP_TRY(hipSetDevice(a->device));
-    const int n_tiles = n_tiles_of(a), tiles_i = (a->height + 7) / 8;
-    if (!a->d_tiles) HIP_TRY(hipMalloc((void **)&a->d_tiles, ((size_t)n_tiles * 3u + 4u) * sizeof(int32_t)));
-    int32_t *d_chunks = a->d_tiles, *d_flags = d_chunks + n_tiles, *d_list = d_flags + n_tiles, *d_count = d_list + n_tiles;
-    if (int rc = wait_for(a, stream)) return rc;
-    const bool fresh = !a->bound;
-    const bool settled = !fresh && a->ad_complete && eff.tolerance == a->ad.tolerance;     // (the same tolerance again: nothing to decide)
-    int later_max = 0;                       // refinement: the last checkpoint some tile stopped at
-    if (!fresh) for (int32_t c : a->tile_chunks) if (c < nch) later_max = std::max(later_max, (int)c);
-    if (fresh) HIP_TRY(hipMemsetAsync(d_chunks, 0, (size_t)n_tiles * sizeof(int32_t), stream));
+    HIP_TRY(hipSetDevice(scene->device));
+    rtw_accum *a0 = accums[0];
+    const int n_tiles = n_tiles_of(a0), tiles_i = (a0->height + 7) / 8;
+    const long long n_all = (long long)n_views * n_tiles;            // (validate_batch: fits an int with room to spare)
+    const bool fresh = !a0->bound;
+    // (from here on a HIP failure can leave an unbound accumulator with its tile array allocated and cleared: nothing a caller can see --
+    //  words, binding and ranges are touched only behind a pass that was launched -- and what the next adaptive call expects to find or make)
+    for (int32_t v = 0; v < n_views; ++v) {
+        rtw_accum *a = accums[v];
+        if (!a->d_tiles) HIP_TRY(hipMalloc((void **)&a->d_tiles, ((size_t)n_tiles * 3u + 4u) * sizeof(int32_t)));
+        if (int rc = wait_for(a, stream)) return rc;
+        if (fresh) HIP_TRY(hipMemsetAsync(a->d_tiles, 0, (size_t)n_tiles * sizeof(int32_t), stream));
+        else if (!a->ad_complete || a->tile_chunks.size() != (size_t)n_tiles) {      // (after a call that failed half way: what the device holds)
+            a->tile_chunks.resize((size_t)n_tiles);
+            HIP_TRY(hipMemcpyAsync(a->tile_chunks.data(), a->d_tiles, (size_t)n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+        }
+    }
+    // flags | list | count: the single call's lie behind C_t in its accumulator's d_tiles; a batch's in the call's scratch, made once:
+    // the views' table | flags | list | count | the compaction's block offsets
+    struct Scratch { void *p = nullptr; ~Scratch() { if (p) HIP_IGNORE(hipFree(p)); } } scratch;
+    const size_t tab_bytes = ((size_t)n_views * sizeof(TileView) + 15u) / 16u * 16u;
+    const int n_blocks = (int)((n_all + 255) / 256);
+    if (!single) HIP_TRY(hipMalloc(&scratch.p, tab_bytes + ((size_t)n_all * 2u + 4u + (size_t)n_blocks) * sizeof(int32_t)));
+    TileView *d_views = static_cast<TileView *>(scratch.p);
+    int32_t *d_flags = single ? a0->d_tiles + n_tiles : reinterpret_cast<int32_t *>(static_cast<char *>(scratch.p) + tab_bytes);
+    int32_t *d_list = d_flags + n_all, *d_count = d_list + n_all, *d_blocks = d_count + 4;
+    // (measurement aid: RTW_BATCH_COMPACT=loop makes a batch's list with the single call's one-workgroup loop -- the same list)
+    static const bool compact_loop = aid_env("RTW_BATCH_COMPACT") != nullptr && strcmp(aid_env("RTW_BATCH_COMPACT"), "loop") == 0;
+    std::vector<TileView> h_views((size_t)n_views);
+    std::vector<AccumViewPass> views((size_t)n_views);
+    std::vector<std::vector<int32_t>> old_chunks((size_t)n_views);
+    bool settled = !fresh;                   // (the same tolerance again: nothing to decide)
+    int later_max = 0;                       // refinement: the last checkpoint some tile of some view stopped at
+    for (int32_t v = 0; v < n_views; ++v) {
+        rtw_accum *a = accums[v];
+        h_views[(size_t)v] = TileView{a->words, a->d_tiles};
+        views[(size_t)v] = AccumViewPass{a->words, 1};                // (no running image: the divisor is unused)
+        old_chunks[(size_t)v] = fresh ? std::vector<int32_t>((size_t)n_tiles, 0) : a->tile_chunks;
+        if (!fresh) for (int32_t c : a->tile_chunks) if (c < nch) later_max = std::max(later_max, (int)c);
+        settled = settled && a->ad_complete && eff.tolerance == a->ad.tolerance;
+    }
+    if (!single) HIP_TRY(hipMemcpyAsync(d_views, h_views.data(), (size_t)n_views * sizeof(TileView), hipMemcpyHostToDevice, stream));    // (h_views outlives the call's last synchronisation)
 
     release_last();
     rtw_stats_t agg;
     memset(&agg, 0, sizeof agg);
     RenderRec *rec = nullptr;
     CtxPtr ctx;
-    int rounds = 0;
+    std::vector<int> pass_at;                // the checkpoints of this call's passes (0: a fresh run's first)
     // one pass: launch, C_t += count; the caller synchronises the stream before `finish` reads the pass's counters
     auto pass = [&](int begin, int count, const int32_t *list, int n_list) -> int {
         AccumPass ps;
-        ps.words = a->words; ps.chunk_begin = begin; ps.chunk_count = count; ps.samples = 1;      // (no running image: the divisor is unused)
-        ps.adapt = true; ps.tile_list = list; ps.list_tiles = n_list;
-        int rc = launch_accum_t(scene, cam, p, ps, nullptr, stream, &rec, &ctx);
+        ps.words = single ? a0->words : nullptr; ps.chunk_begin = begin; ps.chunk_count = count; ps.samples = 1;
+        ps.adapt = true; ps.tile_list = list; ps.list_tiles = n_list; ps.views = single ? nullptr : views.data();
+        int rc = launch_render_t(scene, cams, single ? 0 : n_views, seeds, p, nullptr, stream, &rec, &ctx, &ps);
         if (rc) { if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); rec = nullptr; } return rc; }     // (released by the next call)
         (void)hipGetLastError();
-        hipLaunchKernelGGL(accum_tile_advance_kernel, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, stream, list, n_list, d_chunks, count);
+        if (single) hipLaunchKernelGGL(accum_tile_advance_kernel, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, stream, list, n_list, a0->d_tiles, count);
+        else hipLaunchKernelGGL(accum_tile_advance_batch_kernel, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, stream, list, n_list, d_views, n_tiles, count);
         HIP_TRY(hipGetLastError());
-        ++rounds;
+        pass_at.push_back(begin);
         return 0;
     };
     auto finish = [&]() -> int {              // (behind a stream synchronisation) the last pass's counters -> agg; its record goes back to the pool
@@ -516,54 +573,89 @@ int render_adaptive(rtw_scene_handle scene, const CamT *cam, const rtw_params *p
     };
     auto run = [&]() -> int {
         const int first = std::min((int)eff.min_chunks, nch);
-        int moved = 0;                          // tiles the last pass brought to the checkpoint at hand
+        long long moved = 0;                    // tiles the last pass brought to the checkpoint at hand
         if (fresh) {
-            if (int rc = pass(0, first, nullptr, n_tiles)) return rc;
-            a->bind = b; a->bound = true; a->adaptive = true; a->ad = eff; a->ad_complete = false;
-            moved = n_tiles;
+            if (int rc = pass(0, first, nullptr, (int)n_all)) return rc;
+            for (int32_t v = 0; v < n_views; ++v) { rtw_accum *a = accums[v]; a->bind = binds[v]; a->bound = true; a->adaptive = true; a->ad = eff; }
+            moved = n_all;
         }
-        a->ad.tolerance = eff.tolerance;
-        a->ad_complete = false;
+        for (int32_t v = 0; v < n_views; ++v) { accums[v]->ad.tolerance = eff.tolerance; accums[v]->ad_complete = false; }
         for (int c = first; c < nch && !settled; c += eff.check_chunks) {
             if (moved == 0 && c > later_max) break;
             (void)hipGetLastError();
-            hipLaunchKernelGGL(accum_tile_check_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, stream, a->words, d_chunks, d_flags, n_tiles, tiles_i,
-                               (int)a->width, (int)a->height, c, (double)((long long)c * cs), eff.tolerance, eff.dark_floor);
-            hipLaunchKernelGGL(accum_tile_compact_kernel, dim3(1), dim3(1024), 0, stream, d_flags, d_list, d_count, n_tiles);
+            if (single)
+                hipLaunchKernelGGL(accum_tile_check_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, stream, a0->words, a0->d_tiles, d_flags, n_tiles, tiles_i,
+                                   (int)a0->width, (int)a0->height, c, (double)((long long)c * cs), eff.tolerance, eff.dark_floor);
+            else
+                hipLaunchKernelGGL(accum_tile_check_batch_kernel, dim3((unsigned)((n_all + 3) / 4)), dim3(256), 0, stream, d_views, d_flags, (int)n_views, n_tiles, tiles_i,
+                                   (int)a0->width, (int)a0->height, c, (double)((long long)c * cs), eff.tolerance, eff.dark_floor);
+            if (single || compact_loop) {
+                hipLaunchKernelGGL(accum_tile_compact_kernel, dim3(1), dim3(1024), 0, stream, d_flags, d_list, d_count, (int)n_all);
+            } else {
+                hipLaunchKernelGGL(accum_tile_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, d_flags, d_blocks, (int)n_all);
+                hipLaunchKernelGGL(accum_tile_scan_kernel, dim3(1), dim3(1024), 0, stream, d_blocks, d_count, n_blocks);
+                hipLaunchKernelGGL(accum_tile_scatter_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, d_flags, d_blocks, d_list, (int)n_all);
+            }
             HIP_TRY(hipGetLastError());
             int32_t n_active = 0;
             HIP_TRY(hipMemcpyAsync(&n_active, d_count, sizeof n_active, hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipStreamSynchronize(stream));
             if (int rc = finish()) return rc;
-            if (n_active < 0 || n_active > n_tiles) return fail(-3, "adaptive render: %d active tiles of %d", n_active, n_tiles);
+            if (n_active < 0 || n_active > n_all) return fail(-3, "adaptive render: %d active tiles of %lld", n_active, n_all);
             moved = n_active;
             if (n_active == 0) continue;
             if (int rc = pass(c, std::min((int)eff.check_chunks, nch - c), d_list, n_active)) return rc;
         }
-        a->tile_chunks.resize((size_t)n_tiles);
-        HIP_TRY(hipMemcpyAsync(a->tile_chunks.data(), d_chunks, (size_t)n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        for (int32_t v = 0; v < n_views; ++v) {
+            rtw_accum *a = accums[v];
+            a->tile_chunks.resize((size_t)n_tiles);
+            HIP_TRY(hipMemcpyAsync(a->tile_chunks.data(), a->d_tiles, (size_t)n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        }
         HIP_TRY(hipStreamSynchronize(stream));
         if (int rc = finish()) return rc;
-        int min_c = nch;
-        for (int32_t c : a->tile_chunks) min_c = std::min(min_c, (int)c);
-        a->ranges.clear();
-        a->ranges.emplace_back(0, min_c);
-        a->ad_complete = true;
-        a->ad_rounds = rounds;
-        if (d_out) {
-            if (int rc = resolve_dev<T>(a, p->gamma, d_out, stream)) return rc;
-            HIP_TRY(hipStreamSynchronize(stream));
+        for (int32_t v = 0; v < n_views; ++v) {
+            rtw_accum *a = accums[v];
+            const std::vector<int32_t> &was = old_chunks[(size_t)v];
+            int min_c = nch, rounds = 0;
+            for (int32_t c : a->tile_chunks) min_c = std::min(min_c, (int)c);
+            for (int at : pass_at) {
+                bool held = false;
+                for (int t = 0; t < n_tiles && !held; ++t) held = was[(size_t)t] <= at && at < a->tile_chunks[(size_t)t];
+                rounds += held ? 1 : 0;
+            }
+            a->ranges.clear();
+            a->ranges.emplace_back(0, min_c);
+            a->ad_complete = true;
+            a->ad_rounds = rounds;
+            if (d_out)
+                if (int rc = resolve_dev<T>(a, p->gamma, static_cast<T *>(d_out) + (size_t)v * n_pixels(a) * 3u, stream)) return rc;
         }
+        if (d_out) HIP_TRY(hipStreamSynchronize(stream));
         return 0;
     };
     const int rc = run();
     if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); }       // (a failure between a pass and its wait)
-    if (rc) { if (a->bound) HIP_IGNORE(hipEventRecord(a->ev, stream)); return rc; }
+    if (rc) {
+        for (int32_t v = 0; v < n_views; ++v) if (accums[v]->bound) HIP_IGNORE(hipEventRecord(accums[v]->ev, stream));
+        if (scratch.p) HIP_IGNORE(hipStreamSynchronize(stream));               // (the scratch is freed on return)
+        return rc;
+    }
     agg.n_chunks = nch;
     g_last.agg = agg;
     g_last.resolved = true;
-    g_last.per_device.emplace_back(a->device, agg.kernel_ms);
-    return mark(a, stream);
+    g_last.per_device.emplace_back(scene->device, agg.kernel_ms);
+    for (int32_t v = 0; v < n_views; ++v) if (int rc2 = mark(accums[v], stream)) return rc2;
+    return 0;
+}
+
+template <typename CamT>
+int render_adaptive(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, const rtw_adaptive_t *ad, rtw_accum_handle a, void *d_out, void *stream_v) {
+    int nch, cs;
+    rtw_adaptive_t eff;
+    if (int rc = validate_adaptive(scene, cam, p, ad, a, &nch, &cs, &eff)) return rc;
+    AccumBind b;
+    make_bind(&b, scene, cam, p, nch, cs);
+    return adaptive_loop(true, scene, cam, 1, nullptr, p, eff, nch, cs, &a, &b, d_out, stream_v);
 }
 
 // ---- batched passes (rtw_render_accum_batch_*, rtw_render_adaptive_batch_*): N views of one scene, each with its own accumulator ----
@@ -600,41 +692,12 @@ int render_accum_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_views
         if (int rc = validate_accum(scene, cams + v, &q, chunk_begin, chunk_count, accums[v], &nv, &cv)) return fail(rc, "view %d: %s", v, std::string(g_err).c_str());
         make_bind(&binds[(size_t)v], scene, cams + v, &q, nch, cs);
     }
-    DeviceGuard guard;
-    hipStream_t stream = (hipStream_t)stream_v;
-    HIP_TRY(hipSetDevice(scene->device));
-    std::vector<AccumViewPass> views((size_t)n_views);
-    for (int32_t v = 0; v < n_views; ++v) {
-        if (int rc = wait_for(accums[v], stream)) return rc;
-        views[(size_t)v].words = accums[v]->words;
-        views[(size_t)v].samples = (int)(samples_done(accums[v]) + samples_in(binds[(size_t)v], chunk_begin, (long long)chunk_begin + chunk_count));
-    }
-    AccumPass pass;
-    pass.words = nullptr; pass.chunk_begin = chunk_begin; pass.chunk_count = chunk_count; pass.samples = 1;
-    pass.views = views.data();
-    RenderRec *rec = nullptr;
-    CtxPtr ctx;
-    release_last();
-    int rc = launch_accum_batch_t(scene, cams, n_views, seeds, p, pass, d_out, stream, &rec, &ctx);
-    if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); }       // (also on a late error: released by the next call)
-    if (rc) return rc;
-    for (int32_t v = 0; v < n_views; ++v) {
-        rtw_accum *a = accums[v];
-        a->bind = binds[(size_t)v]; a->bound = true;
-        add_range(a->ranges, chunk_begin, chunk_begin + chunk_count);
-        if (int rc2 = mark(a, stream)) return rc2;
-    }
-    return 0;
+    return accum_pass(false, scene, cams, n_views, seeds, p, chunk_begin, chunk_count, accums, binds.data(), d_out, stream_v);
 }
 
-// The single call's loop (render_adaptive) for all views at once: per checkpoint ONE check over the N * n_tiles tiles, ONE compaction into
-// the sorted list of batch-global tiles, ONE read-back, ONE pass over the list.  A tile's history does not depend on its neighbours', so
-// every view ends with the words and C_t of its own single call; its `rounds` -- the passes that held one of ITS tiles -- follows on the
-// host from C_t before and after: a pass at checkpoint c held tile t iff old C_t <= c < new C_t (a fresh run's first pass: c = 0).
 template <typename CamT>
 int render_adaptive_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_adaptive_t *ad,
                           const rtw_accum_handle *accums, void *d_out, void *stream_v) {
-    using T = typename std::conditional<sizeof(CamT) == sizeof(rtw_camera_f64), double, float>::type;
     if (!p) return fail(-1, "null params");
     if (!ad) return fail(-1, "null argument");
     int nch, cs;
@@ -652,152 +715,7 @@ int render_adaptive_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_vi
         make_bind(&binds[(size_t)v], scene, cams + v, &q, nch, cs);
         if (accums[v]->bound != accums[0]->bound) return fail(-4, "view %d: the accumulators of a batch are all unbound or all adaptive accumulators of their views' renders", v);
     }
-    DeviceGuard guard;
-    hipStream_t stream = (hipStream_t)stream_v;
-    HIP_TRY(hipSetDevice(scene->device));
-    const rtw_accum *a0 = accums[0];
-    const int n_tiles = n_tiles_of(a0), tiles_i = (a0->height + 7) / 8;
-    const long long n_all = (long long)n_views * n_tiles;            // (validate_batch: fits an int with room to spare)
-    const bool fresh = !a0->bound;
-    // (from here on a HIP failure can leave an unbound accumulator with its tile array allocated and cleared: nothing a caller can see --
-    //  words, binding and ranges are touched only behind a pass that was launched -- and what the next adaptive call expects to find or make)
-    for (int32_t v = 0; v < n_views; ++v) {
-        rtw_accum *a = accums[v];
-        if (!a->d_tiles) HIP_TRY(hipMalloc((void **)&a->d_tiles, ((size_t)n_tiles * 3u + 4u) * sizeof(int32_t)));
-        if (int rc = wait_for(a, stream)) return rc;
-        if (fresh) HIP_TRY(hipMemsetAsync(a->d_tiles, 0, (size_t)n_tiles * sizeof(int32_t), stream));
-        else if (!a->ad_complete || a->tile_chunks.size() != (size_t)n_tiles) {      // (after a call that failed half way: what the device holds)
-            a->tile_chunks.resize((size_t)n_tiles);
-            HIP_TRY(hipMemcpyAsync(a->tile_chunks.data(), a->d_tiles, (size_t)n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-        }
-    }
-    // the call's scratch, made once: the views' table | flags | list | count | the compaction's block offsets
-    struct Scratch { void *p = nullptr; ~Scratch() { if (p) HIP_IGNORE(hipFree(p)); } } scratch;
-    const size_t tab_bytes = ((size_t)n_views * sizeof(TileView) + 15u) / 16u * 16u;
-    const int n_blocks = (int)((n_all + 255) / 256);
-    HIP_TRY(hipMalloc(&scratch.p, tab_bytes + ((size_t)n_all * 2u + 4u + (size_t)n_blocks) * sizeof(int32_t)));
-    TileView *d_views = static_cast<TileView *>(scratch.p);
-    int32_t *d_flags = reinterpret_cast<int32_t *>(static_cast<char *>(scratch.p) + tab_bytes), *d_list = d_flags + n_all, *d_count = d_list + n_all, *d_blocks = d_count + 4;
-    // (measurement aid: RTW_BATCH_COMPACT=loop makes the list with the single call's one-workgroup loop -- the same list)
-    static const bool compact_loop = aid_env("RTW_BATCH_COMPACT") != nullptr && strcmp(aid_env("RTW_BATCH_COMPACT"), "loop") == 0;
-    std::vector<TileView> h_views((size_t)n_views);
-    std::vector<AccumViewPass> views((size_t)n_views);
-    std::vector<std::vector<int32_t>> old_chunks((size_t)n_views);
-    bool settled = !fresh;
-    int later_max = 0;                       // refinement: the last checkpoint some tile of some view stopped at
-    for (int32_t v = 0; v < n_views; ++v) {
-        rtw_accum *a = accums[v];
-        h_views[(size_t)v] = TileView{a->words, a->d_tiles};
-        views[(size_t)v] = AccumViewPass{a->words, 1};                // (no running image: the divisor is unused)
-        old_chunks[(size_t)v] = fresh ? std::vector<int32_t>((size_t)n_tiles, 0) : a->tile_chunks;
-        if (!fresh) for (int32_t c : a->tile_chunks) if (c < nch) later_max = std::max(later_max, (int)c);
-        settled = settled && a->ad_complete && eff.tolerance == a->ad.tolerance;
-    }
-    HIP_TRY(hipMemcpyAsync(d_views, h_views.data(), (size_t)n_views * sizeof(TileView), hipMemcpyHostToDevice, stream));    // (h_views outlives the call's last synchronisation)
-
-    release_last();
-    rtw_stats_t agg;
-    memset(&agg, 0, sizeof agg);
-    RenderRec *rec = nullptr;
-    CtxPtr ctx;
-    std::vector<int> pass_at;                // the checkpoints of this call's passes (0: a fresh run's first)
-    auto pass = [&](int begin, int count, const int32_t *list, int n_list) -> int {
-        AccumPass ps;
-        ps.words = nullptr; ps.chunk_begin = begin; ps.chunk_count = count; ps.samples = 1;
-        ps.adapt = true; ps.tile_list = list; ps.list_tiles = n_list; ps.views = views.data();
-        int rc = launch_accum_batch_t(scene, cams, n_views, seeds, p, ps, nullptr, stream, &rec, &ctx);
-        if (rc) { if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); rec = nullptr; } return rc; }     // (released by the next call)
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(accum_tile_advance_batch_kernel, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, stream, list, n_list, d_views, n_tiles, count);
-        HIP_TRY(hipGetLastError());
-        pass_at.push_back(begin);
-        return 0;
-    };
-    auto finish = [&]() -> int {              // (behind a stream synchronisation) the last pass's counters -> agg; its record goes back to the pool
-        if (!rec) return 0;
-        rtw_stats_t one;
-        memset(&one, 0, sizeof one);
-        int rc = resolve_rec(rec, &one);
-        release_rec(ctx, rec, rc == 0);
-        rec = nullptr;
-        if (rc) return rc;
-        agg.samples += one.samples; agg.segments += one.segments; agg.sphere_tests += one.sphere_tests;
-        agg.kernel_ms += one.kernel_ms; agg.total_ms += one.total_ms;
-        agg.grid_blocks = std::max(agg.grid_blocks, one.grid_blocks); agg.block_threads = std::max(agg.block_threads, one.block_threads);
-        return 0;
-    };
-    auto run = [&]() -> int {
-        const int first = std::min((int)eff.min_chunks, nch);
-        long long moved = 0;                    // tiles the last pass brought to the checkpoint at hand
-        if (fresh) {
-            if (int rc = pass(0, first, nullptr, (int)n_all)) return rc;
-            for (int32_t v = 0; v < n_views; ++v) { rtw_accum *a = accums[v]; a->bind = binds[(size_t)v]; a->bound = true; a->adaptive = true; a->ad = eff; }
-            moved = n_all;
-        }
-        for (int32_t v = 0; v < n_views; ++v) { accums[v]->ad.tolerance = eff.tolerance; accums[v]->ad_complete = false; }
-        for (int c = first; c < nch && !settled; c += eff.check_chunks) {
-            if (moved == 0 && c > later_max) break;
-            (void)hipGetLastError();
-            hipLaunchKernelGGL(accum_tile_check_batch_kernel, dim3((unsigned)((n_all + 3) / 4)), dim3(256), 0, stream, d_views, d_flags, (int)n_views, n_tiles, tiles_i,
-                               (int)a0->width, (int)a0->height, c, (double)((long long)c * cs), eff.tolerance, eff.dark_floor);
-            if (compact_loop) {
-                hipLaunchKernelGGL(accum_tile_compact_kernel, dim3(1), dim3(1024), 0, stream, d_flags, d_list, d_count, (int)n_all);
-            } else {
-                hipLaunchKernelGGL(accum_tile_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, d_flags, d_blocks, (int)n_all);
-                hipLaunchKernelGGL(accum_tile_scan_kernel, dim3(1), dim3(1024), 0, stream, d_blocks, d_count, n_blocks);
-                hipLaunchKernelGGL(accum_tile_scatter_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, d_flags, d_blocks, d_list, (int)n_all);
-            }
-            HIP_TRY(hipGetLastError());
-            int32_t n_active = 0;
-            HIP_TRY(hipMemcpyAsync(&n_active, d_count, sizeof n_active, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            if (int rc = finish()) return rc;
-            if (n_active < 0 || n_active > n_all) return fail(-3, "adaptive batch: %d active tiles of %lld", n_active, n_all);
-            moved = n_active;
-            if (n_active == 0) continue;
-            if (int rc = pass(c, std::min((int)eff.check_chunks, nch - c), d_list, n_active)) return rc;
-        }
-        for (int32_t v = 0; v < n_views; ++v) {
-            rtw_accum *a = accums[v];
-            a->tile_chunks.resize((size_t)n_tiles);
-            HIP_TRY(hipMemcpyAsync(a->tile_chunks.data(), a->d_tiles, (size_t)n_tiles * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-        }
-        HIP_TRY(hipStreamSynchronize(stream));
-        if (int rc = finish()) return rc;
-        for (int32_t v = 0; v < n_views; ++v) {
-            rtw_accum *a = accums[v];
-            const std::vector<int32_t> &was = old_chunks[(size_t)v];
-            int min_c = nch, rounds = 0;
-            for (int32_t c : a->tile_chunks) min_c = std::min(min_c, (int)c);
-            for (int at : pass_at) {
-                bool held = false;
-                for (int t = 0; t < n_tiles && !held; ++t) held = was[(size_t)t] <= at && at < a->tile_chunks[(size_t)t];
-                rounds += held ? 1 : 0;
-            }
-            a->ranges.clear();
-            a->ranges.emplace_back(0, min_c);
-            a->ad_complete = true;
-            a->ad_rounds = rounds;
-            if (d_out)
-                if (int rc = resolve_dev<T>(a, p->gamma, static_cast<T *>(d_out) + (size_t)v * n_pixels(a) * 3u, stream)) return rc;
-        }
-        if (d_out) HIP_TRY(hipStreamSynchronize(stream));
-        return 0;
-    };
-    const int rc = run();
-    if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); }       // (a failure between a pass and its wait)
-    if (rc) {
-        for (int32_t v = 0; v < n_views; ++v) if (accums[v]->bound) HIP_IGNORE(hipEventRecord(accums[v]->ev, stream));
-        HIP_IGNORE(hipStreamSynchronize(stream));                               // (the scratch is freed on return)
-        return rc;
-    }
-    agg.n_chunks = nch;
-    g_last.agg = agg;
-    g_last.resolved = true;
-    g_last.per_device.emplace_back(scene->device, agg.kernel_ms);
-    for (int32_t v = 0; v < n_views; ++v) if (int rc2 = mark(accums[v], stream)) return rc2;
-    return 0;
+    return adaptive_loop(false, scene, cams, n_views, seeds, p, eff, nch, cs, accums, binds.data(), d_out, stream_v);
 }
 
 int adaptive_info(const rtw_accum *a, rtw_adaptive_info_t *out) {

@@ -5,7 +5,7 @@
 //   rtw_launch.hip       one render = one launch of the trace kernel (rtw_kernels.hpp / rtw_pool.hpp): geometry, job shape, counters
 //   rtw_render_host.hip  the host-buffer entry points: cached per-device context (scene, stream, image), one device or a device list
 //   rtw_multi.hip        what a device list needs: peer access, the on-demand RCCL binding, the un-tile kernel
-//   rtw_batch_accum_f32.hip / _f64.hip  the BATCH && ACCUM instances of the trace kernel (rtw_batch_accum.hpp), a unit per precision
+//   rtw_batch_accum_f32.hip / _f64.hip  the BATCH && ACCUM instances of the trace kernel (rtw_instances.hpp: the kernel-instance table), a unit per precision
 //   rtw_accum.hip        progressive render: the accumulator object, its passes, merge / resolve kernels, export / import
 //   rtw_unit.hip         the T0 unit entry points (rtw_units.hpp)
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
@@ -192,35 +192,24 @@ int upload_scene_f64(const rtw_scene_f64 *s, int device, rtw_scene_handle *out);
 inline int upload_scene_t(const rtw_scene_f32 *s, int device, rtw_scene_handle *out) { return upload_scene_f32(s, device, out); }
 inline int upload_scene_t(const rtw_scene_f64 *s, int device, rtw_scene_handle *out) { return upload_scene_f64(s, device, out); }
 
-// rtw_launch.hip -- enqueue one render (this shard's tiles) on `stream`; `rec` receives the counters and the kernel's events
-int launch_render_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
-int launch_render_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
-inline int launch_render_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_render_f32(s, c, p, d, st, r, x); }
-inline int launch_render_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_render_f64(s, c, p, d, st, r, x); }
-int resolve_rec(RenderRec *r, rtw_stats_t *agg);            // wait for a record's kernel and add its counters to `agg`
-// ... a batch of n_views >= 1 views (validate_batch first): `cams` / `seeds` (null: p->seed) hold n_views entries, `d_out` n_views frames
-int launch_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
-int launch_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
-inline int launch_batch_t(rtw_scene_handle s, const rtw_camera_f32 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_batch_f32(s, c, n, sd, p, d, st, r, x); }
-inline int launch_batch_t(rtw_scene_handle s, const rtw_camera_f64 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_batch_f64(s, c, n, sd, p, d, st, r, x); }
-// ... one pass of a progressive render (rtw_accum.hip has validated it): the chunks [chunk_begin, chunk_begin + chunk_count) of the render
+// rtw_launch.hip -- enqueue one render (this shard's tiles) on `stream`; `rec` receives the counters and the kernel's events.
+// n_views == 0: one render of the camera `cams` points to.  n_views >= 1: a batch of that many views (validate_batch first): `cams` /
+// `seeds` (null: p->seed) hold n_views entries, `d_out` n_views frames.
+// `pass`: one pass of a progressive render (rtw_accum.hip has validated it): the chunks [chunk_begin, chunk_begin + chunk_count) of the render
 // `p` describes are added to `words` (layout: include/rtw_hip.h rtw_accum_read_pixels); `samples` = the samples the accumulator holds
 // after this pass, the divisor of the running image written to `d_out` (null: none).  `adapt`: a pass of an adaptive render (the ADAPT
 // kernels: half differences in word 7); `tile_list` non-null: only the `list_tiles` tiles of that device-resident list
-// A pass of a BATCH of such renders (launch_accum_batch_*): `views` holds every view's accumulator and divisor (`words` / `samples` of the
+// A pass of a BATCH of such renders (n_views >= 1): `views` holds every view's accumulator and divisor (`words` / `samples` of the
 // pass itself are unused), `tile_list` numbers the tiles batch-globally, v * n_tiles + t
 struct AccumViewPass { unsigned long long *words; int samples; };
 struct AccumPass { unsigned long long *words; int chunk_begin, chunk_count, samples; bool adapt = false; const int *tile_list = nullptr; int list_tiles = 0; const AccumViewPass *views = nullptr; };
-int launch_accum_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const AccumPass &pass, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
-int launch_accum_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const AccumPass &pass, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
-inline int launch_accum_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, const AccumPass &a, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_accum_f32(s, c, p, a, d, st, r, x); }
-inline int launch_accum_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, const AccumPass &a, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_accum_f64(s, c, p, a, d, st, r, x); }
-int launch_accum_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, const AccumPass &pass, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
-int launch_accum_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, const AccumPass &pass, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
-inline int launch_accum_batch_t(rtw_scene_handle s, const rtw_camera_f32 *c, int n, const uint64_t *sd, const rtw_params *p, const AccumPass &a, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_accum_batch_f32(s, c, n, sd, p, a, d, st, r, x); }
-inline int launch_accum_batch_t(rtw_scene_handle s, const rtw_camera_f64 *c, int n, const uint64_t *sd, const rtw_params *p, const AccumPass &a, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_accum_batch_f64(s, c, n, sd, p, a, d, st, r, x); }
+int launch_render_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const AccumPass *pass = nullptr);
+int launch_render_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const AccumPass *pass = nullptr);
+inline int launch_render_t(rtw_scene_handle s, const rtw_camera_f32 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const AccumPass *a = nullptr) { return launch_render_f32(s, c, n, sd, p, d, st, r, x, a); }
+inline int launch_render_t(rtw_scene_handle s, const rtw_camera_f64 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const AccumPass *a = nullptr) { return launch_render_f64(s, c, n, sd, p, d, st, r, x, a); }
+int resolve_rec(RenderRec *r, rtw_stats_t *agg);            // wait for a record's kernel and add its counters to `agg`
 // rtw_batch_accum_f32.hip / _f64.hip: the BATCH && ACCUM (&& ADAPT) instance of the trace kernel for a scan variant, as launch_render chooses
-// among the other instances (`fixed`: the instance with the default numerics mode compiled in)
+// among the other instances (rtw_instances.hpp; `fixed`: the numerics mode is the default one, which the headline variants have compiled in)
 const void *batch_accum_kernel_f32(bool cull, bool mfma, bool lds_scene, bool fixed, bool adapt);
 const void *batch_accum_kernel_f64(bool cull, bool mfma, bool lds_scene, bool fixed, bool adapt);
 // rtw_abi.hip: the checks of a batched render that need no device (include/rtw_hip.h rtw_render_batch_f32)

@@ -2,6 +2,7 @@
 // instantiation, the persistent grid, the job shape, the per-render counters and events, and what rtw_stats() reads back.
 #include "rtw_scene_view.hpp"
 #include "rtw_kernels.hpp"
+#include "rtw_instances.hpp"
 #ifdef RTW_WITH_POOL          // `make POOL=1`: the ray-pool kernel (a measured 16 - 19 % LOSS on this chip, DESIGN_LOG R4) is not in the default library
 #include "rtw_pool.hpp"
 #endif
@@ -27,7 +28,7 @@ void make_udiv(unsigned d, unsigned *m, unsigned *s) {
 // render of chunk_count chunks; `d_out` may be null.  pass->adapt: a pass of an adaptive render (the ADAPT instances: the half difference
 // in word 7); with pass->tile_list also a pass over the pass->list_tiles tiles of that device-resident list only -- scheduled like a shard
 // of that many tiles (K.shard_count = 0 marks it).
-// n_views >= 1 AND `pass`: one pass of n_views progressive (adaptive) renders (the BATCH && ACCUM instances, rtw_batch_accum.hpp):
+// n_views >= 1 AND `pass`: one pass of n_views progressive (adaptive) renders (the BATCH && ACCUM instances, rtw_batch_accum_f32.hip / _f64.hip):
 // pass->views holds every view's accumulator and divisor, a tile list numbers the tiles batch-globally (v * n_tiles + t).
 template <typename T, typename CamT>
 int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
@@ -114,38 +115,14 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
     // the default numerics mode of the headline variants (scene in LDS, matrix pipe): an instance with the mode fixed at compile time
     if (S.numerics == rtw::NUM_REFERENCE && lds_scene && mfma && !phase_profile)
         kern = cull ? (kern_t)rtw::trace_kernel<T, false, true, true, true, rtw::NUM_REFERENCE> : (kern_t)rtw::trace_kernel<T, false, true, false, true, rtw::NUM_REFERENCE>;
-    // a batch: the same choice among the BATCH instances (no phase profile)
-    if (batch) {
-        if (cull && mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true, true, -1, true> : (kern_t)rtw::trace_kernel<T, false, false, true, true, -1, true>;
-        else if (cull) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true, false, -1, true> : (kern_t)rtw::trace_kernel<T, false, false, true, false, -1, true>;
-        else if (mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false, true, -1, true> : (kern_t)rtw::trace_kernel<T, false, false, false, true, -1, true>;
-        else kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false, false, -1, true> : (kern_t)rtw::trace_kernel<T, false, false, false, false, -1, true>;
-        if (S.numerics == rtw::NUM_REFERENCE && lds_scene && mfma)
-            kern = cull ? (kern_t)rtw::trace_kernel<T, false, true, true, true, rtw::NUM_REFERENCE, true> : (kern_t)rtw::trace_kernel<T, false, true, false, true, rtw::NUM_REFERENCE, true>;
-    }
-    // a pass of a progressive render: the same choice among the ACCUM instances (no phase profile)
-    if (pass) {
-        if (cull && mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true, true, -1, false, true> : (kern_t)rtw::trace_kernel<T, false, false, true, true, -1, false, true>;
-        else if (cull) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true, false, -1, false, true> : (kern_t)rtw::trace_kernel<T, false, false, true, false, -1, false, true>;
-        else if (mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false, true, -1, false, true> : (kern_t)rtw::trace_kernel<T, false, false, false, true, -1, false, true>;
-        else kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false, false, -1, false, true> : (kern_t)rtw::trace_kernel<T, false, false, false, false, -1, false, true>;
-        if (S.numerics == rtw::NUM_REFERENCE && lds_scene && mfma)
-            kern = cull ? (kern_t)rtw::trace_kernel<T, false, true, true, true, rtw::NUM_REFERENCE, false, true> : (kern_t)rtw::trace_kernel<T, false, true, false, true, rtw::NUM_REFERENCE, false, true>;
-    }
-    // a pass of an adaptive render: the same choice among the ADAPT instances
-    if (pass && pass->adapt) {
-        if (cull && mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true, true, -1, false, true, true> : (kern_t)rtw::trace_kernel<T, false, false, true, true, -1, false, true, true>;
-        else if (cull) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true, false, -1, false, true, true> : (kern_t)rtw::trace_kernel<T, false, false, true, false, -1, false, true, true>;
-        else if (mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false, true, -1, false, true, true> : (kern_t)rtw::trace_kernel<T, false, false, false, true, -1, false, true, true>;
-        else kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false, false, -1, false, true, true> : (kern_t)rtw::trace_kernel<T, false, false, false, false, -1, false, true, true>;
-        if (S.numerics == rtw::NUM_REFERENCE && lds_scene && mfma)
-            kern = cull ? (kern_t)rtw::trace_kernel<T, false, true, true, true, rtw::NUM_REFERENCE, false, true, true> : (kern_t)rtw::trace_kernel<T, false, true, false, true, rtw::NUM_REFERENCE, false, true, true>;
-    }
-    // a pass of a batch of progressive / adaptive renders: the same choice among the BATCH && ACCUM instances (a translation unit per precision)
-    if (batch && pass) {
-        const bool fixed = S.numerics == rtw::NUM_REFERENCE && lds_scene && mfma;
-        kern = (kern_t)(sizeof(T) == 8 ? batch_accum_kernel_f64(cull, mfma, lds_scene, fixed, pass->adapt) : batch_accum_kernel_f32(cull, mfma, lds_scene, fixed, pass->adapt));
-    }
+    // a batch, a pass of a progressive render, a pass of an adaptive one: the same choice among the BATCH, the ACCUM and the ACCUM && ADAPT
+    // instances (rtw_instances.hpp; no phase profile); a pass of a batch of such renders: among the BATCH && ACCUM instances (a translation
+    // unit per precision)
+    const bool fixed = S.numerics == rtw::NUM_REFERENCE;
+    if (batch && pass) kern = (kern_t)(sizeof(T) == 8 ? batch_accum_kernel_f64(cull, mfma, lds_scene, fixed, pass->adapt) : batch_accum_kernel_f32(cull, mfma, lds_scene, fixed, pass->adapt));
+    else if (batch) kern = (kern_t)trace_instance_of<T, true, false, false>(cull, mfma, lds_scene, fixed);
+    else if (pass && !pass->adapt) kern = (kern_t)trace_instance_of<T, false, true, false>(cull, mfma, lds_scene, fixed);
+    else if (pass) kern = (kern_t)trace_instance_of<T, false, true, true>(cull, mfma, lds_scene, fixed);
     // The ray-pool kernel (rtw_pool.hpp; opt-in: RTW_FLAG_RAY_POOL, or RTW_POOL=1 in the environment for A/B runs) exists in `make POOL=1`
     // builds only: Float32 plain scans on the matrix pipe, when the pool, the rings and the scene copy fit the 160 KB of LDS of a CU (one
     // workgroup of RTW_POOL_W waves per CU); everything else runs the lane-loop kernel above.  The default library refuses the flag.
@@ -377,35 +354,13 @@ int resolve_rec(RenderRec *r, rtw_stats_t *agg) {
     return 0;
 }
 
-int launch_render_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out) {
-    return launch_render<float>(scene, cam, 0, nullptr, p, d_out, stream, rec_out, ctx_out);
+int launch_render_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
+                      RenderRec **rec_out, CtxPtr *ctx_out, const AccumPass *pass) {
+    return launch_render<float>(scene, cams, n_views, seeds, p, d_out, stream, rec_out, ctx_out, pass);
 }
-int launch_render_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out) {
-    return launch_render<double>(scene, cam, 0, nullptr, p, d_out, stream, rec_out, ctx_out);
-}
-int launch_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
-                     RenderRec **rec_out, CtxPtr *ctx_out) {
-    return launch_render<float>(scene, cams, n_views, seeds, p, d_out, stream, rec_out, ctx_out);
-}
-int launch_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
-                     RenderRec **rec_out, CtxPtr *ctx_out) {
-    return launch_render<double>(scene, cams, n_views, seeds, p, d_out, stream, rec_out, ctx_out);
-}
-int launch_accum_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, const AccumPass &pass, void *d_out,
-                           hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out) {
-    return launch_render<float>(scene, cams, n_views, seeds, p, d_out, stream, rec_out, ctx_out, &pass);
-}
-int launch_accum_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, const AccumPass &pass, void *d_out,
-                           hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out) {
-    return launch_render<double>(scene, cams, n_views, seeds, p, d_out, stream, rec_out, ctx_out, &pass);
-}
-int launch_accum_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const AccumPass &pass, void *d_out, hipStream_t stream,
-                     RenderRec **rec_out, CtxPtr *ctx_out) {
-    return launch_render<float>(scene, cam, 0, nullptr, p, d_out, stream, rec_out, ctx_out, &pass);
-}
-int launch_accum_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const AccumPass &pass, void *d_out, hipStream_t stream,
-                     RenderRec **rec_out, CtxPtr *ctx_out) {
-    return launch_render<double>(scene, cam, 0, nullptr, p, d_out, stream, rec_out, ctx_out, &pass);
+int launch_render_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
+                      RenderRec **rec_out, CtxPtr *ctx_out, const AccumPass *pass) {
+    return launch_render<double>(scene, cams, n_views, seeds, p, d_out, stream, rec_out, ctx_out, pass);
 }
 
 }  // namespace rtwh

@@ -145,7 +145,7 @@ int render_host(const SceneT *scene, const CamT *cam, const rtw_params *p, T *ou
         if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, elems * sizeof(T))) return rc;
         RenderRec *rec = nullptr;
         CtxPtr rctx;
-        int rc = launch_render_t(hc->scene, cam, &q, hc->d_img, hc->stream, &rec, &rctx);
+        int rc = launch_render_t(hc->scene, cam, 0, nullptr, &q, hc->d_img, hc->stream, &rec, &rctx);
         if (!rc) rc = copy_out(hc, hc->d_img, out, elems * sizeof(T));
         if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
         if (!rc) rc = resolve_rec(rec, &g_last.agg);
@@ -207,7 +207,7 @@ int render_host(const SceneT *scene, const CamT *cam, const rtw_params *p, T *ou
         if (use_rccl) {
             // this shard's tiles in the full-frame layout, zero elsewhere (launch_render clears the frame of a sharded render first)
             if ((rc = ensure_dev(&hc->d_img, &hc->d_cap, frame_bytes))) break;
-            rc = launch_render_t(hc->scene, cam, &q, hc->d_img, hc->stream, &recs[r], &rctx[r]);
+            rc = launch_render_t(hc->scene, cam, 0, nullptr, &q, hc->d_img, hc->stream, &recs[r], &rctx[r]);
             continue;
         }
         q.flags |= RTW_FLAG_COMPACT_TILES;
@@ -220,7 +220,7 @@ int render_host(const SceneT *scene, const CamT *cam, const rtw_params *p, T *ou
             if ((rc = ensure_dev(&hc->d_img, &hc->d_cap, my_bytes))) break;        // (the shard buffer belongs to ITS device)
             d_out = hc->d_img;
         }
-        if ((rc = launch_render_t(hc->scene, cam, &q, d_out, hc->stream, &recs[r], &rctx[r]))) break;
+        if ((rc = launch_render_t(hc->scene, cam, 0, nullptr, &q, d_out, hc->stream, &recs[r], &rctx[r]))) break;
         hipError_t e = hipSuccess;
         bool staged = false;
         if (remote) {
@@ -312,7 +312,7 @@ int render_host_batch(const SceneT *scene, const CamT *cams, int32_t n_views, co
     if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, elems * sizeof(T))) return rc;
     RenderRec *rec = nullptr;
     CtxPtr rctx;
-    int rc = launch_batch_t(hc->scene, cams, n_views, seeds, &q, hc->d_img, hc->stream, &rec, &rctx);
+    int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, hc->d_img, hc->stream, &rec, &rctx);
     if (!rc) rc = copy_out(hc, hc->d_img, out, elems * sizeof(T));
     if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
     if (!rc) rc = resolve_rec(rec, &g_last.agg);
