@@ -106,7 +106,7 @@ typedef struct {
 /* (64 was RTW_FLAG_NUMERICS_REFERENCE_FMA in ABI 3 -- only the last step contracted: removed in ABI 4, neither LLVM experiment of
  *  tools/llvm_fastmath_check/ emits it; the bit is rejected as unknown) */
 #define RTW_FLAG_NUMERICS_REFERENCE_FMA2 128
-/* Measurement / test switches of the ENVIRONMENT (RTW_SCAN, RTW_POOL, RTW_JOB_PIXELS, RTW_ROWS_SHIFT, RTW_NO_HUGE,
+/* Measurement / test switches of the ENVIRONMENT (RTW_SCAN, RTW_POOL, RTW_JOB_PIXELS, RTW_ROWS_SHIFT, RTW_NO_HUGE, RTW_PLAIN_ORDER,
  * RTW_DEBUG_REMOTE_SHARDS, RTW_DEBUG_NO_PEER, RTW_PHASE_PROFILE, RTW_DRAIN_PROFILE, RTW_DEBUG) are honoured only when the master switch
  * RTW_ENABLE_TEST_AIDS=1 is set too (read once per process).  Without it a stray variable changes nothing: a render's kernel choice, launch
  * geometry and gather path depend on rtw_params alone. */

@@ -217,6 +217,8 @@ int rtw_scene_free(rtw_scene_handle h) {
     HIP_IGNORE(hipSetDevice(h->device));
     void *ptrs[] = {h->geom, h->mat0, h->mat1, h->scan, h->mf_ops, h->c_mf_ops, h->c_mf_box, h->c_bound, h->c_exact, h->c_mat0, h->c_mat1, h->c_orig};
     for (void *q : ptrs) if (q) HIP_IGNORE(hipFree(q));
+    if (h->p_orig) HIP_IGNORE(hipFree(h->p_orig));
+    if (!h->p_alias) for (void *q : {h->p_mf_ops, h->p_geom, h->p_mat0, h->p_mat1}) if (q) HIP_IGNORE(hipFree(q));      // (the plain scan's own order)
     delete h;
     return 0;
 }

@@ -48,6 +48,12 @@ struct rtw_scene_dev {
     int mf_blocks;
     float mf_sc, mf_sigma2, mf_oo_keep, mf_o1_coef, mf_o_max;
     int n_huge, huge[2];   // spheres that pass the filter for nearly every ray (a ground sphere): tested exactly by every lane, their filter rows disabled
+    // the plain matrix-pipe scan of the trace kernel runs over its OWN order (rtw_plain_layout.hpp: spatially sorted, evenly filled blocks; the
+    // huge spheres behind the blocks): operands, geom / mat0 / mat1 rows and the caller's index of every row.  Set whenever mf_ops is.
+    // (p_alias: the caller's order is kept -- at most one block, or the A/B aid -- and geom / mat0 / mat1 / mf_ops are the arrays above)
+    void *p_mf_ops, *p_geom, *p_mat0, *p_mat1;
+    unsigned short *p_orig;
+    int p_alias, p_n, p_n_pad, p_mf_blocks, p_huge[2];
     // group-cull mode on the matrix pipe: the same operands in the cluster-major order + one box per block of 32
     void *c_mf_ops, *c_mf_box;
     float c_glo[3], c_ghi[3];   // the box of the whole small class (union of the block boxes): the ray is clipped against it once per scan

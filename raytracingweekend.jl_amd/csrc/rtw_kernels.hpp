@@ -510,7 +510,8 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
         ws.kidx = reinterpret_cast<unsigned *>(cells + 4 * 64 * sizeof(unsigned long long)) + wv * 64;
         pool_rng = reinterpret_cast<ulonglong2 *>(cells + mfma_cell_bytes<T>() - 4 * 64 * 16) + wv * 64;
     }
-    unsigned short *lds_orig = reinterpret_cast<unsigned short *>(lds_geom + (CULL ? cull_exact_count(cull) : 0));
+    // (the plain scan on the matrix pipe: the caller's index of every entry of its own order, DevScene::orig, behind the scene copy)
+    unsigned short *lds_orig = reinterpret_cast<unsigned short *>(lds_geom + (CULL ? cull_exact_count(cull) : MFMA ? scene_geom_alloc(scene.n, scene.n_pad) : 0));
     // (CULL on the matrix pipe: the tables of the block vote behind the index list)
     [[maybe_unused]] unsigned *lds_tab = reinterpret_cast<unsigned *>(reinterpret_cast<unsigned char *>(lds_orig) + (CULL ? ((size_t)cull_exact_count(cull) * sizeof(unsigned short) + 15) / 16 * 16 : 0));
     if (threadIdx.x < P_arg.n_slots) { JobSlot *S0 = sh->slot(threadIdx.x, P_arg.slot_stride); S0->ready_seq = RTW_SLOT_FREE; S0->job = 0u; }
@@ -519,6 +520,7 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
     if (LDS_SCENE) {
         if (CULL) stage_cull_scene<T>(cull, lds_geom, lds_orig);
         else stage_scene<T>(scene, lds_geom);
+        if constexpr (!CULL && MFMA) { for (int i = threadIdx.x; i < scene_geom_alloc(scene.n, scene.n_pad); i += blockDim.x) lds_orig[i] = scene.orig[i]; }
         if constexpr (CULL && MFMA) {
             const unsigned *gt = reinterpret_cast<const unsigned *>(cull.mf_box + 8 * (cull.mf_blocks + 1));
             for (int i = threadIdx.x; i < cull_tab_words(cull.mf_blocks); i += blockDim.x) lds_tab[i] = gt[i];
@@ -564,8 +566,9 @@ __global__ __launch_bounds__(256, (TraceWavesOf<T, CULL, MFMA>::value)) void tra
             }
         } else if constexpr (MFMA) {
             if (__any(has_ray)) {
-                if (LDS_SCENE) idx = hit_world_mfma<T>(scene, (const V4 *)lds_geom, ro, rd, has_ray, (T)1e-4, t_hit, ws, lane, clk);
-                else idx = hit_world_mfma<T>(scene, scene.geom, ro, rd, has_ray, (T)1e-4, t_hit, ws, lane, clk);
+                // (the scan's own sphere order: ties go by the caller's index, idx is the DEVICE index -- scene.geom / mat0 / mat1 are in that order)
+                if (LDS_SCENE) idx = hit_world_mfma<T, const V4 *, const unsigned short *, PhaseClock<PROFILE> &, NoSink, false>(scene, (const V4 *)lds_geom, ro, rd, has_ray, (T)1e-4, t_hit, ws, lane, clk, nullptr, (const unsigned short *)lds_orig);
+                else idx = hit_world_mfma<T, const V4 *, const unsigned short *, PhaseClock<PROFILE> &, NoSink, false>(scene, scene.geom, ro, rd, has_ray, (T)1e-4, t_hit, ws, lane, clk, nullptr, scene.orig);
             }
         } else if (has_ray) {
             if (CULL && LDS_SCENE)

@@ -101,7 +101,22 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
                                          (mfma ? (size_t)rtw::cull_tab_words(scene->c_mf_blocks) * sizeof(unsigned) : 0)
                                    : (size_t)rtw::scene_geom_alloc(scene->n, scene->n_pad) * sizeof(V4);
     const bool lds_scene = geom_bytes <= RTW_LDS_SCENE_MAX_BYTES;
-    const size_t lds_bytes = list_bytes + shared_bytes + (mfma ? rtw::mfma_cell_bytes<T>() : 0) + (lds_scene ? geom_bytes : 0);
+    // the plain scan on the matrix pipe reads the scene in its own order (rtw_scene.hip build_plain); its index array travels with the scene copy.
+    // (lds_scene is decided by the caller-order bytes above, so a scene takes the same instance whatever the layout; what is then asked for
+    //  is plain_bytes: up to 31 dead rows + the huge spheres more, and 2 B per entry for the index -- at most 24 KB x 18 / 16 + 1.2 KB.  The
+    //  grid follows the runtime's occupancy answer for the bytes really requested.)
+    const bool plain_order = mfma && !cull;
+    [[maybe_unused]] const rtw::DevScene<T> S_caller = S;
+    size_t plain_bytes = 0;
+    if (plain_order) {
+        if (!scene->p_mf_ops || !scene->p_orig) return fail(-9, "internal: the scene has no arrays in the plain scan's order");
+        const int num = S.numerics;
+        S = dev_scene_plain_of<T>(scene);
+        S.numerics = num;
+        const size_t na = (size_t)rtw::scene_geom_alloc(S.n, S.n_pad);
+        plain_bytes = na * sizeof(V4) + ((na * sizeof(unsigned short) + 15) / 16) * 16;
+    }
+    const size_t lds_bytes = list_bytes + shared_bytes + (mfma ? rtw::mfma_cell_bytes<T>() : 0) + (lds_scene ? (plain_order ? plain_bytes : geom_bytes) : 0);
     typedef void (*kern_t)(rtw::KParams, rtw::Camera<T>, rtw::DevScene<T>, rtw::CullScene<T>, T *, rtw::DevCounters *, rtw::BatchArgs<T>, rtw::AccumArgs);
     kern_t kern;
     if (cull && mfma && phase_profile) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, true, true, true, true> : (kern_t)rtw::trace_kernel<T, false, false, true, true>;
@@ -266,7 +281,7 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
     if (total_jobs > 0) {
         (void)hipGetLastError();           // (hipEventQuery's hipErrorNotReady in acquire_rec must not be mistaken for a launch failure)
 #ifdef RTW_WITH_POOL
-        if (pool) hipLaunchKernelGGL(pool_kern, dim3((unsigned)grid), dim3((unsigned)block_threads), pool_lds, stream, K, C, S, (T *)d_out, rec->ctr);
+        if (pool) hipLaunchKernelGGL(pool_kern, dim3((unsigned)grid), dim3((unsigned)block_threads), pool_lds, stream, K, C, S_caller, (T *)d_out, rec->ctr);      // (the caller's order)
         else
 #endif
         hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds_bytes, stream, K, C, S, CS, (T *)d_out, rec->ctr, B, A);

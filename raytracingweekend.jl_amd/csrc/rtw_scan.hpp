@@ -39,6 +39,8 @@ template <typename T> struct DevScene {
     float mf_o_max;         // rays with a larger |o_k| (or non-unit, non-finite ones) take every sphere as a candidate
     int n_huge, huge[2];    // spheres tested exactly by every lane instead of through the filter (a ground sphere: candidate of nearly every ray)
     int numerics;           // NUM_*: the deciding arithmetic of sphere_disc for this render (set per launch, not per upload)
+    const unsigned short *orig;   // the plain matrix-pipe scan of the trace kernel (its own sphere order: geom / mat0 / mat1 / mf_ops / huge above are
+                                  // in it): the caller's index of every entry, what ties go by; null: the arrays are in the caller's order
 };
 
 // Candidate lists: pass 1 of the scan appends the indices of the spheres whose discriminant is

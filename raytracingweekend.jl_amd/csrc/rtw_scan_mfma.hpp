@@ -240,11 +240,16 @@ __device__ __forceinline__ void resolve_pairs(int num, SRC src, RAD rad, V3<T> o
 // With `mc` (group cull, RTW_FLAG_GROUP_CULL): the spheres come in the cull layout's device order (src, orig), and a block of
 // 32 is visited only when some ray of the half wave can touch its box (the conservative margin of hit_world_cull, in binary32 with
 // the Float32 kappa for both precisions): the table vote of CullGrid, once per scan.  Returns the DEVICE index.
-template <typename T, typename SRC, typename ORIG = NoOrig, typename CLK = NoClock, typename SINK = NoSink>
+// `orig` without `mc` (VOTE = false: the trace kernel's plain scan): the spheres come in the plain scan's own order (rtw_plain_layout.hpp) -- w.geom,
+// w.mat0, w.mf_ops, w.huge are in it -- and every block is visited; orig[] serves the one thing the order must not change, which of two
+// spheres with the same root wins: the low word of the key.  Returns the DEVICE index there too.
+template <typename T, typename SRC, typename ORIG = NoOrig, typename CLK = NoClock, typename SINK = NoSink, bool VOTE = !__is_same(ORIG, NoOrig)>
 __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<T> o, V3<T> d, bool has_ray, T tmin, T &t_hit,
                                               const WaveScratch &ws, unsigned lane, CLK &&clk = NoClock(),
                                               const MfmaCull *mc = nullptr, ORIG orig = ORIG(), SINK sink = SINK()) {
-    constexpr bool CULLED = !__is_same(ORIG, NoOrig);
+    constexpr bool HAS_ORIG = !__is_same(ORIG, NoOrig);      // device order != the caller's order: ties go by orig[]
+    constexpr bool CULLED = VOTE;                            // the group cull: operands, tables and the in-lane list of `mc`, the block vote
+    static_assert(HAS_ORIG || !VOTE, "the group cull's order comes with its index array");
     // radii (mat0[i].x) in the order of `src`: read by NUM_REFERENCE_FMA2 only -- fetched from the kernel arguments where that mode needs them, not held across the scan
     auto rad = [&]() -> const typename Vec4<T>::type * { if constexpr (CULLED) return (const typename Vec4<T>::type *)mc->mat0; else return w.mat0; };
     // ---- ray features (binary32) ----
@@ -395,16 +400,16 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
             if constexpr (CULLED) si = __builtin_amdgcn_readfirstlane((int)mc->tab[6 * RTW_CULL_BINS + 4 + hgi]);      // (the list lies with the vote's tables)
             else si = hgi == 0 ? w.huge[0] : w.huge[1];                  // (no dynamic indexing of a by-value struct: that would live in scratch)
             const V4 sg = src[si];
-            if constexpr (SINK::on()) { if (has_ray) { if constexpr (CULLED) sink.inlane(lane, (int)orig[si]); else sink.inlane(lane, si); } }
+            if constexpr (SINK::on()) { if (has_ray) { if constexpr (HAS_ORIG) sink.inlane(lane, (int)orig[si]); else sink.inlane(lane, si); } }
             T hb_, disc_, root_ = 0;
             T rr_ = T(0);
             if (w.numerics == NUM_REFERENCE_FMA2) rr_ = rad()[si].x;
             sphere_disc<T>(w.numerics, sg.x, sg.y, sg.z, sg.w, rr_, o, d, hb_, disc_);
             if (has_ray && sphere_root<T>(hb_, disc_, tmin, (T)__builtin_huge_val(), root_)) {
                 unsigned tie = (unsigned)si;                       // larger = later in the caller's list (resolve_pairs)
-                if constexpr (CULLED) tie = ((unsigned)orig[si] << 16) | (unsigned)si;
+                if constexpr (HAS_ORIG) tie = ((unsigned)orig[si] << 16) | (unsigned)si;
                 if constexpr (sizeof(T) == 4) {
-                    const unsigned low = CULLED ? ((0xffffu - (tie >> 16)) << 16) | (tie & 0xffffu) : 0xffffffffu - tie;
+                    const unsigned low = HAS_ORIG ? ((0xffffu - (tie >> 16)) << 16) | (tie & 0xffffu) : 0xffffffffu - tie;
                     const unsigned long long k = ((unsigned long long)__float_as_uint((float)root_) << 32) | (unsigned long long)low;
                     key0 = k < key0 ? k : key0;
                 } else {
@@ -588,12 +593,12 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
     int idx;
     if constexpr (sizeof(T) == 4) {
         const unsigned long long k = ws.keys[lane];
-        idx = k == ~0ull ? -1 : (CULLED ? (int)((unsigned)k & 0xffffu) : (int)(0xffffffffu - (unsigned)k));
+        idx = k == ~0ull ? -1 : (HAS_ORIG ? (int)((unsigned)k & 0xffffu) : (int)(0xffffffffu - (unsigned)k));
         t_hit = __uint_as_float((unsigned)(k >> 32));
     } else {
         const unsigned long long k = ws.keys[lane];
         const unsigned ki = ws.kidx[lane];
-        idx = ki == 0u ? -1 : (CULLED ? (int)((ki - 1u) & 0xffffu) : (int)ki - 1);
+        idx = ki == 0u ? -1 : (HAS_ORIG ? (int)((ki - 1u) & 0xffffu) : (int)ki - 1);
         t_hit = __longlong_as_double((long long)k);
     }
     if (!has_ray) idx = -1;

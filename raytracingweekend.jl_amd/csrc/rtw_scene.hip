@@ -3,6 +3,7 @@
 // (hit_world_mfma, rtw_device.hpp) with their error-margin constants.  Host code only; -ffp-contract=off like the kernels.
 #include "rtw_scene_view.hpp"
 #include "rtw_cull_tables.hpp"
+#include "rtw_plain_layout.hpp"
 
 namespace rtwh {
 
@@ -47,7 +48,7 @@ void material_rows(const SceneT *s, int i, V4 &m0, V4 &m1) {
 
 // cluster-major arrays for the opt-in group-cull scan (rtw_device.hpp, "opt-in accelerated scan")
 template <typename T, typename V4>
-int build_mfma_operands(const std::vector<V4> &geom, int n, rtw_scene_dev *h, void **ops_out, int *blocks_out, int n_skip = 0, const int *skip = nullptr);
+int build_mfma_operands(const std::vector<V4> &geom, int n, rtw_scene_dev *h, void **ops_out, int *blocks_out, int n_skip = 0, const int *skip = nullptr, int n_rows = -1);
 
 template <typename T, typename SceneT>
 int build_cull(const SceneT *s, rtw_scene_dev *h) {
@@ -204,15 +205,18 @@ int build_cull(const SceneT *s, rtw_scene_dev *h) {
 // every feature split into two f16 pieces, in the slot order documented there.  Row i of the instruction holds sphere
 // 16 ((i >> 2) & 1) + (((i >> 3) << 2) | (i & 3)) of the block, so that result register r of lane (H, j) is sphere 16 H + r.
 // `geom`: n entries; entries with r^2 < -1e29 are padding (never a candidate).  *ops_out / *blocks_out receive the device
-// array; the scale constants in `h` depend on the set of spheres only, so both orders of a scene get the same ones.
+// array; the scale constants in `h` depend on the set of spheres only, so every order of a scene gets the same ones.
+// n_rows >= 0: only the first n_rows entries get rows (the plain scan's order keeps its huge spheres behind the blocks: they count for the
+// scales like everything else).
 template <typename T, typename V4>
-int build_mfma_operands(const std::vector<V4> &geom, int n, rtw_scene_dev *h, void **ops_out, int *blocks_out, int n_skip, const int *skip) {
+int build_mfma_operands(const std::vector<V4> &geom, int n, rtw_scene_dev *h, void **ops_out, int *blocks_out, int n_skip, const int *skip, int n_rows) {
     *ops_out = nullptr; *blocks_out = 0;
     if (n <= 0) return 0;
     auto live = [&](int i) { return i < n && (double)geom[i].w > -1e29; };
     // `skip`: spheres whose filter ROW is disabled (written like a padding row: never flagged for a ray that uses the filter) because
     // every lane tests them exactly by itself (DevScene::huge).  They still count for the scales: both orders of a scene share those.
-    auto in_filter = [&](int i) { if (!live(i)) return false; for (int k = 0; k < n_skip; ++k) if (skip[k] == i) return false; return true; };
+    if (n_rows < 0) n_rows = n;
+    auto in_filter = [&](int i) { if (!live(i) || i >= n_rows) return false; for (int k = 0; k < n_skip; ++k) if (skip[k] == i) return false; return true; };
     double emax = 0;
     for (int i = 0; i < n; ++i) {
         if (!live(i)) continue;
@@ -239,7 +243,7 @@ int build_mfma_operands(const std::vector<V4> &geom, int n, rtw_scene_dev *h, vo
         memcpy(&b1, &h1, 2); memcpy(&b2, &h2, 2);
         p1 = b1; p2 = b2;
     };
-    const int nb = (n + 31) / 32;
+    const int nb = (n_rows + 31) / 32;
     std::vector<uint4> ops((size_t)(nb + 1) * 128);
     for (int blk = 0; blk <= nb; ++blk)
         for (int lane = 0; lane < 64; ++lane) {
@@ -290,6 +294,59 @@ int build_mfma_operands(const std::vector<V4> &geom, int n, rtw_scene_dev *h, vo
     if ((double)coef < 1.02 * 9 * phi_c) coef = std::nextafter(coef, INFINITY);
     h->mf_o1_coef = coef;
     h->mf_o_max = (float)(std::ldexp(1.0, 13) / sc);
+    return 0;
+}
+
+// The plain matrix-pipe scan's own order (rtw_plain_layout.hpp): the spheres that go through the filter in spatially sorted, evenly filled
+// blocks of 32, unused rows dead, the huge spheres (tested in-lane, no row) behind the blocks; operands, geom / mat0 / mat1 in that order
+// and the caller's index of every entry -- what "the later sphere wins a tie" is decided by (hit_world_mfma).  Uploaded once with the scene.
+// At most one block, or more entries than a 16-bit index holds: the caller's arrays themselves, with the identity for the index array.
+template <typename T, typename V4>
+int build_plain(const std::vector<V4> &geom, const std::vector<V4> &mat0, const std::vector<V4> &mat1, int n, rtw_scene_dev *h) {
+    if (!h->mf_ops) return 0;
+    static const bool keep_env = aid_env("RTW_PLAIN_ORDER") != nullptr && strcmp(aid_env("RTW_PLAIN_ORDER"), "caller") == 0;      // A/B aid: the caller's order in the new code path
+    auto is_huge = [&](int i) { for (int k = 0; k < h->n_huge; ++k) if (h->huge[k] == i) return true; return false; };
+    std::vector<int> filt;
+    std::vector<double> cx, cy, cz;
+    for (int i = 0; i < n; ++i) {
+        if (is_huge(i)) continue;
+        filt.push_back(i);
+        cx.push_back((double)geom[i].x); cy.push_back((double)geom[i].y); cz.push_back((double)geom[i].z);
+    }
+    PlainLayout L;
+    build_plain_layout(cx.data(), cy.data(), cz.data(), (int)filt.size(), &L);
+    constexpr int grp = rtw::ScanGroup<T>::N;
+    const int n_rows = L.blocks * RTW_PLAIN_BLOCK, np = n_rows + h->n_huge, np_pad = ((np + grp - 1) / grp) * grp;
+    const int np_alloc = rtw::scene_geom_alloc(np, np_pad);
+    std::vector<unsigned short> orig;
+    if (keep_env || L.blocks <= 1 || np_alloc >= 65536) {
+        h->p_alias = 1;
+        h->p_mf_ops = h->mf_ops; h->p_geom = h->geom; h->p_mat0 = h->mat0; h->p_mat1 = h->mat1;
+        h->p_n = n; h->p_n_pad = h->n_pad; h->p_mf_blocks = h->mf_blocks; h->p_huge[0] = h->huge[0]; h->p_huge[1] = h->huge[1];
+        orig.resize((size_t)rtw::scene_geom_alloc(n, h->n_pad));
+        for (size_t i = 0; i < orig.size(); ++i) orig[i] = (unsigned short)i;
+    } else {
+        std::vector<V4> g(np_alloc, V4{(T)0, (T)0, (T)0, (T)-1e30}), m0(np_alloc, V4{(T)1, (T)0, (T)0, (T)0}), m1(np_alloc, V4{(T)0, (T)0, (T)0, (T)0});
+        orig.assign((size_t)np_alloc, 0);
+        auto put = [&](int k, int i) { g[k] = geom[i]; m0[k] = mat0[i]; m1[k] = mat1[i]; orig[k] = (unsigned short)i; };
+        for (int k = 0; k < n_rows; ++k) if (L.slot[k] >= 0) put(k, filt[L.slot[k]]);
+        for (int k = 0; k < h->n_huge; ++k) { put(n_rows + k, h->huge[k]); h->p_huge[k] = n_rows + k; }
+        h->p_n = np; h->p_n_pad = np_pad;
+        const size_t bytes = sizeof(V4) * (size_t)np_alloc;
+        HIP_TRY(hipMalloc(&h->p_geom, bytes));
+        HIP_TRY(hipMalloc(&h->p_mat0, bytes));
+        HIP_TRY(hipMalloc(&h->p_mat1, bytes));
+        HIP_TRY(hipMemcpy(h->p_geom, g.data(), bytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(h->p_mat0, m0.data(), bytes, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(h->p_mat1, m1.data(), bytes, hipMemcpyHostToDevice));
+        if (int rc = build_mfma_operands<T>(g, np, h, &h->p_mf_ops, &h->p_mf_blocks, h->n_huge, h->p_huge, n_rows)) return rc;
+        if (!h->p_mf_ops) return fail(-9, "internal: no matrix-pipe operands for the plain scan's order");
+    }
+    if (aid_env("RTW_DEBUG"))
+        fprintf(stderr, "[rtw debug] plain scan layout: %d spheres through the filter, %d blocks, %s\n", (int)filt.size(), h->p_mf_blocks,
+                h->p_alias ? "the caller's order" : "its own order");
+    HIP_TRY(hipMalloc((void **)&h->p_orig, orig.size() * sizeof(unsigned short)));
+    HIP_TRY(hipMemcpy(h->p_orig, orig.data(), orig.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -392,6 +449,7 @@ int upload_scene(const SceneT *s, int device, rtw_scene_handle *out) {
     static const bool env_no_huge = aid_flag("RTW_NO_HUGE");      // A/B aid
     if (env_no_huge) h->n_huge = 0;
     if (int rc = build_mfma_operands<T>(geom, n, h.get(), &h->mf_ops, &h->mf_blocks, h->n_huge, h->huge)) return rc;
+    if (int rc = build_plain<T>(geom, mat0, mat1, n, h.get())) return rc;
     if (int rc = build_cull<T>(s, h.get())) return rc;
     *out = h.release();
     return 0;

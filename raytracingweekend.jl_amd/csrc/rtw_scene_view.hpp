@@ -38,4 +38,17 @@ rtw::DevScene<T> dev_scene_of(const rtw_scene_dev *h) {
     return S;
 }
 
+// the scene as the trace kernel's plain matrix-pipe scan reads it: its own sphere order (rtw_scene.hip build_plain) and the index array
+template <typename T>
+rtw::DevScene<T> dev_scene_plain_of(const rtw_scene_dev *h) {
+    using V4 = typename rtw::Vec4<T>::type;
+    rtw::DevScene<T> S = dev_scene_of<T>(h);
+    S.geom = (const V4 *)h->p_geom; S.mat0 = (const V4 *)h->p_mat0; S.mat1 = (const V4 *)h->p_mat1;
+    S.n = h->p_n; S.n_pad = h->p_n_pad;
+    S.mf_ops = (const uint4 *)h->p_mf_ops; S.mf_blocks = h->p_mf_blocks;
+    S.huge[0] = h->p_huge[0]; S.huge[1] = h->p_huge[1];
+    S.orig = h->p_orig;
+    return S;
+}
+
 }  // namespace rtwh
