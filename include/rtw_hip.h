@@ -415,6 +415,23 @@ int rtw_stats_devices(int32_t capacity, int32_t *count, int32_t *devices, double
  *       15 near_zero(v) (src/vec.jl:19-20)
  *       16 (Float32) the kernels' short correctly-rounded sqrt / reciprocal against the compiler's IEEE sequences on a range of binary32 bit patterns:
  *          in = (first pattern, count) per item, out = (mismatches sqrt, mismatches 1/x, first bad pattern of each or -1)
+ *       17 - 20 the scans of ops 10, 11, 13, 14 with a candidate sink: what pass 1 hands pass 2 (tests/test_gpu_filters.py)
+ *   Ops 21 - 23 run the accumulator's tile kernels (the adaptive render's stopping rule, its tile lists, its per-tile resolve) on words
+ *   the caller makes up, with the launch geometry of rtw_render_adaptive_*.  Their layouts belong to the whole call, not to an item, in
+ *   8-byte slots: "value" slots hold a binary64 number (integers as such), "raw" slots a uint64 / int64.  Tiles are 8 x 8 pixels,
+ *   n_tiles = ceil(height / 8) * ceil(width / 8), tile t = (j / 8) * ceil(height / 8) + i / 8 for row i, column j; the words of a frame
+ *   are rtw_accum_read_pixels' (pixel (i, j) at (j * height + i) * 8).  Nulls -> -1; a size or value outside the layout, a frame of more
+ *   than 16384 on a side or 2^20 pixels, or more than 2^24 input slots -> -2; all before any HIP call.  Ops 21 and 22 are on rtw_unit_f64 only.
+ *       21 the tile check.  count = n_views >= 1.  in: 8 value slots width, height, c, chunk_spp, tolerance, dark_floor, 0, 0; then per
+ *          view n_tiles value slots C_t and width * height * 8 raw words.  out (raw int64): per view the n_tiles flags of the single
+ *          call's check kernel, launched view by view; then the n_views * n_tiles flags of ONE launch of the batch's check kernel.  A
+ *          flag is 1 for a tile with C_t == c that is NOT converged under the rule with n = c * chunk_spp, 0 for every other tile.
+ *       22 the tile lists.  count = n >= 1 flags.  in: n raw slots, the low 32 bits of each are the flag (set: non-zero).  out (raw
+ *          int64): the count and the n list slots of the single call's one-workgroup compaction, then the same of the batch's count /
+ *          scan / scatter.  A list holds the indices of the set flags in ascending order; the slots behind the count hold -1.
+ *       23 the per-tile resolve (also on rtw_unit_f32: T = float).  count = 1.  in: 8 value slots width, height, spp, chunk_spp, gamma
+ *          (0 / 1), 0, 0, 0; n_tiles value slots C_t >= 1; width * height * 8 raw words.  out: width * height * 3 value slots, element
+ *          (j * height + i) * 3 + channel: the sum over min(spp, C_t * chunk_spp) samples of the pixel's tile, rounded to T, widened.
  *   bits 8-9 of `op`: the numerics mode of the ray-sphere test for ops 0, 8 - 11, 13, 14 (0 reference, 1 contract, 3 reference_fma2; 2 is rejected)  */
 int rtw_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene,
                  const rtw_camera_f32 *cam);

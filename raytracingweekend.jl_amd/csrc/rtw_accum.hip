@@ -238,6 +238,42 @@ __global__ __launch_bounds__(256) void accum_resolve_tiles_kernel(const unsigned
     out[k] = (T)v;
 }
 
+// ---- the launches of the tile kernels: adaptive_loop / resolve_dev and the unit ops 21-23 (accum_unit) all go through these, so the test
+// seam runs the product's kernels with the product's grids.  (enqueue only: the caller clears and reads hipGetLastError around them) ----
+int tiles_down(int height) { return (height + 7) / 8; }
+int tiles_of(int width, int height) { return tiles_down(height) * ((width + 7) / 8); }
+// the check at checkpoint `c` of ONE frame: flags[t] for its tiles (n handed to the rule: the samples of c chunks of `cs`)
+void launch_tile_check(hipStream_t stream, const unsigned long long *words, const int *chunks, int *flags, int width, int height, int c, int cs, double tol, double floor) {
+    const int n_tiles = tiles_of(width, height);
+    hipLaunchKernelGGL(accum_tile_check_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, stream, words, chunks, flags, n_tiles, tiles_down(height),
+                       width, height, c, (double)((long long)c * cs), tol, floor);
+}
+// ... of the n_views frames of a device-resident view table: flags[v * n_tiles + t]
+void launch_tile_check_batch(hipStream_t stream, const TileView *d_views, int *flags, int n_views, int width, int height, int c, int cs, double tol, double floor) {
+    const int n_tiles = tiles_of(width, height);
+    const long long n_all = (long long)n_views * n_tiles;
+    hipLaunchKernelGGL(accum_tile_check_batch_kernel, dim3((unsigned)((n_all + 3) / 4)), dim3(256), 0, stream, d_views, flags, n_views, n_tiles, tiles_down(height),
+                       width, height, c, (double)((long long)c * cs), tol, floor);
+}
+// n flags -> the sorted list + its length: one workgroup's loop, or count / scan / scatter over compact_blocks(n) ints of scratch
+void launch_compact_loop(hipStream_t stream, const int *flags, int *list, int *count, int n) {
+    hipLaunchKernelGGL(accum_tile_compact_kernel, dim3(1), dim3(1024), 0, stream, flags, list, count, n);
+}
+int compact_blocks(long long n) { return (int)((n + 255) / 256); }
+void launch_compact_blocks(hipStream_t stream, const int *flags, int *blocks, int *list, int *count, int n) {
+    const int n_blocks = compact_blocks(n);
+    hipLaunchKernelGGL(accum_tile_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, flags, blocks, n);
+    hipLaunchKernelGGL(accum_tile_scan_kernel, dim3(1), dim3(1024), 0, stream, blocks, count, n_blocks);
+    hipLaunchKernelGGL(accum_tile_scatter_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, flags, blocks, list, n);
+}
+// the frame of an adaptive accumulator: every pixel over the samples its tile holds
+template <typename T>
+void launch_resolve_tiles(hipStream_t stream, const unsigned long long *words, T *d_out, const int *chunks, int width, int height, int spp, int chunk_spp, int gamma) {
+    const size_t n = (size_t)width * (size_t)height * 3u;
+    hipLaunchKernelGGL(accum_resolve_tiles_kernel<T>, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, words, d_out, n, chunks, height, tiles_down(height),
+                       spp, chunk_spp, gamma);
+}
+
 size_t n_pixels(const rtw_accum *a) { return (size_t)a->width * (size_t)a->height; }
 
 long long samples_in(const AccumBind &b, long long begin, long long end) {
@@ -329,8 +365,7 @@ int resolve_dev(rtw_accum *a, int32_t gamma, void *d_out, hipStream_t stream) {
     const size_t n = n_pixels(a) * 3u;
     (void)hipGetLastError();
     if (a->adaptive)
-        hipLaunchKernelGGL(accum_resolve_tiles_kernel<T>, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, a->words, (T *)d_out, n, a->d_tiles, (int)a->height,
-                           (int)((a->height + 7) / 8), (int)a->bind.spp, (int)a->bind.chunk_spp, (int)gamma);
+        launch_resolve_tiles<T>(stream, a->words, (T *)d_out, a->d_tiles, (int)a->width, (int)a->height, (int)a->bind.spp, (int)a->bind.chunk_spp, (int)gamma);
     else
     hipLaunchKernelGGL(accum_resolve_kernel<T>, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, a->words, (T *)d_out, n, (int)s, (int)gamma);
     HIP_TRY(hipGetLastError());
@@ -438,7 +473,7 @@ int render_accum(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, i
 }
 
 // ---- adaptive render ----
-int n_tiles_of(const rtw_accum *a) { return ((a->height + 7) / 8) * ((a->width + 7) / 8); }
+int n_tiles_of(const rtw_accum *a) { return tiles_of(a->width, a->height); }
 int default_check_chunks(int nch) { int m = std::max(16, (nch + 7) / 8); return m + (m & 1); }      // the smallest even number >= max(16, N / 8)
 
 // everything about an adaptive call that is decided without a device: nulls, the render, whole frames on one device, the adaptive
@@ -496,7 +531,7 @@ int adaptive_loop(bool single, rtw_scene_handle scene, const CamT *cams, int32_t
     hipStream_t stream = (hipStream_t)stream_v;
     HIP_TRY(hipSetDevice(scene->device));
     rtw_accum *a0 = accums[0];
-    const int n_tiles = n_tiles_of(a0), tiles_i = (a0->height + 7) / 8;
+    const int n_tiles = n_tiles_of(a0);
     const long long n_all = (long long)n_views * n_tiles;            // (validate_batch: fits an int with room to spare)
     const bool fresh = !a0->bound;
     // (from here on a HIP failure can leave an unbound accumulator with its tile array allocated and cleared: nothing a caller can see --
@@ -516,7 +551,7 @@ int adaptive_loop(bool single, rtw_scene_handle scene, const CamT *cams, int32_t
     // the views' table | flags | list | count | the compaction's block offsets
     struct Scratch { void *p = nullptr; ~Scratch() { if (p) HIP_IGNORE(hipFree(p)); } } scratch;
     const size_t tab_bytes = ((size_t)n_views * sizeof(TileView) + 15u) / 16u * 16u;
-    const int n_blocks = (int)((n_all + 255) / 256);
+    const int n_blocks = compact_blocks(n_all);
     if (!single) HIP_TRY(hipMalloc(&scratch.p, tab_bytes + ((size_t)n_all * 2u + 4u + (size_t)n_blocks) * sizeof(int32_t)));
     TileView *d_views = static_cast<TileView *>(scratch.p);
     int32_t *d_flags = single ? a0->d_tiles + n_tiles : reinterpret_cast<int32_t *>(static_cast<char *>(scratch.p) + tab_bytes);
@@ -583,19 +618,10 @@ int adaptive_loop(bool single, rtw_scene_handle scene, const CamT *cams, int32_t
         for (int c = first; c < nch && !settled; c += eff.check_chunks) {
             if (moved == 0 && c > later_max) break;
             (void)hipGetLastError();
-            if (single)
-                hipLaunchKernelGGL(accum_tile_check_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, stream, a0->words, a0->d_tiles, d_flags, n_tiles, tiles_i,
-                                   (int)a0->width, (int)a0->height, c, (double)((long long)c * cs), eff.tolerance, eff.dark_floor);
-            else
-                hipLaunchKernelGGL(accum_tile_check_batch_kernel, dim3((unsigned)((n_all + 3) / 4)), dim3(256), 0, stream, d_views, d_flags, (int)n_views, n_tiles, tiles_i,
-                                   (int)a0->width, (int)a0->height, c, (double)((long long)c * cs), eff.tolerance, eff.dark_floor);
-            if (single || compact_loop) {
-                hipLaunchKernelGGL(accum_tile_compact_kernel, dim3(1), dim3(1024), 0, stream, d_flags, d_list, d_count, (int)n_all);
-            } else {
-                hipLaunchKernelGGL(accum_tile_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, d_flags, d_blocks, (int)n_all);
-                hipLaunchKernelGGL(accum_tile_scan_kernel, dim3(1), dim3(1024), 0, stream, d_blocks, d_count, n_blocks);
-                hipLaunchKernelGGL(accum_tile_scatter_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, d_flags, d_blocks, d_list, (int)n_all);
-            }
+            if (single) launch_tile_check(stream, a0->words, a0->d_tiles, d_flags, (int)a0->width, (int)a0->height, c, cs, eff.tolerance, eff.dark_floor);
+            else launch_tile_check_batch(stream, d_views, d_flags, (int)n_views, (int)a0->width, (int)a0->height, c, cs, eff.tolerance, eff.dark_floor);
+            if (single || compact_loop) launch_compact_loop(stream, d_flags, d_list, d_count, (int)n_all);
+            else launch_compact_blocks(stream, d_flags, d_blocks, d_list, d_count, (int)n_all);
             HIP_TRY(hipGetLastError());
             int32_t n_active = 0;
             HIP_TRY(hipMemcpyAsync(&n_active, d_count, sizeof n_active, hipMemcpyDeviceToHost, stream));
@@ -734,7 +760,159 @@ int adaptive_info(const rtw_accum *a, rtw_adaptive_info_t *out) {
     return 0;
 }
 
+// ---- the unit ops 21-23 (include/rtw_hip.h rtw_unit_f64; tests/test_gpu_accum_kernels.py): the tile kernels on the caller's words ----
+// A test seam like the other rtw_unit ops: host slots in, host slots out, the null stream, blocking copies, one device allocation that is
+// freed on return.  Everything is validated before the first HIP call: nulls -1; a size or a value the layout does not hold, or a call
+// of more than RTW_ACCUM_UNIT_SLOTS input slots, -2.  The kernels run through the launch helpers of the adaptive loop.
+#define RTW_ACCUM_UNIT_SLOTS (1ll << 24)         // 128 MiB of 8-byte slots
+#define RTW_ACCUM_UNIT_PIXELS (1ll << 20)        // ... and frames of at most this many pixels, 16384 on a side
+struct DevBuf { void *p = nullptr; ~DevBuf() { if (p) HIP_IGNORE(hipFree(p)); } };
+size_t up16(size_t b) { return (b + 15u) / 16u * 16u; }
+// a slot that holds an integer of [lo, hi] as a binary64 value
+bool slot_int(double d, long long lo, long long hi, int *out) {
+    if (!(d >= (double)lo && d <= (double)hi) || d != std::floor(d)) return false;
+    *out = (int)d;
+    return true;
+}
+int unit_frame(const double *in, int *W, int *H) {
+    if (!slot_int(in[0], 1, 1 << 14, W) || !slot_int(in[1], 1, 1 << 14, H) || (long long)*W * *H > RTW_ACCUM_UNIT_PIXELS)
+        return fail(-2, "accumulator unit op: a frame of %g x %g (at most 16384 on a side, %lld pixels)", in[0], in[1], RTW_ACCUM_UNIT_PIXELS);
+    return 0;
+}
+int unit_chunks(const double *slots, long long n, int lowest, std::vector<int32_t> *out) {
+    out->resize((size_t)n);
+    for (long long k = 0; k < n; ++k) {
+        int c;
+        if (!slot_int(slots[k], lowest, 0x7fffffff, &c)) return fail(-2, "accumulator unit op: tile chunk count %g (slot %lld)", slots[k], k);
+        (*out)[(size_t)k] = c;
+    }
+    return 0;
+}
+int unit_device() {
+    int dev;
+    if (int rc = resolve_device(-1, &dev)) return rc;
+    HIP_TRY(hipSetDevice(dev));
+    return 0;
+}
+
+// op 21: in = width, height, c, chunk_spp, tol, floor, 0, 0 | per view: n_tiles x C_t, W * H * 8 raw words; out (raw int64) = per view the
+// n_tiles flags of accum_tile_check_kernel, launched view by view | the n_views * n_tiles flags of ONE accum_tile_check_batch_kernel launch
+int unit_tile_check(int n_views, const double *in, long long *out) {
+    int W, H, c, cs;
+    if (n_views < 1) return fail(-2, "unit op 21: count is the number of views (got %d)", n_views);
+    if (int rc = unit_frame(in, &W, &H)) return rc;
+    if (!slot_int(in[2], 0, 0x7fffffff, &c) || !slot_int(in[3], 1, 0x7fffffff, &cs)) return fail(-2, "unit op 21: checkpoint %g, chunk_spp %g", in[2], in[3]);
+    const double tol = in[4], floor = in[5];
+    if (!std::isfinite(tol) || !(tol > 0.0) || !std::isfinite(floor) || floor < 0.0) return fail(-2, "unit op 21: tolerance %g, dark_floor %g", tol, floor);
+    if (in[6] != 0.0 || in[7] != 0.0) return fail(-2, "unit op 21: header slots 6 and 7 must be 0");
+    const long long n_tiles = tiles_of(W, H), n_words = (long long)W * H * 8, stride = n_tiles + n_words, n_all = (long long)n_views * n_tiles;
+    if (8 + (long long)n_views * stride > RTW_ACCUM_UNIT_SLOTS) return fail(-2, "unit op 21: %d views of %d x %d exceed %lld slots", n_views, W, H, RTW_ACCUM_UNIT_SLOTS);
+    std::vector<int32_t> chunks, one;
+    for (int v = 0; v < n_views; ++v) {
+        if (int rc = unit_chunks(in + 8 + (size_t)v * (size_t)stride, n_tiles, 0, &one)) return rc;
+        chunks.insert(chunks.end(), one.begin(), one.end());
+    }
+    DeviceGuard guard;
+    if (int rc = unit_device()) return rc;
+    const size_t words_b = (size_t)n_views * (size_t)n_words * 8u, tab_b = up16((size_t)n_views * sizeof(TileView)), ints_b = (size_t)n_all * sizeof(int32_t);
+    DevBuf buf;
+    HIP_TRY(hipMalloc(&buf.p, words_b + tab_b + 3u * ints_b));
+    unsigned long long *d_words = static_cast<unsigned long long *>(buf.p);
+    TileView *d_views = reinterpret_cast<TileView *>(static_cast<char *>(buf.p) + words_b);
+    int32_t *d_chunks = reinterpret_cast<int32_t *>(static_cast<char *>(buf.p) + words_b + tab_b), *d_flags = d_chunks + n_all;
+    std::vector<TileView> h_views((size_t)n_views);
+    for (int v = 0; v < n_views; ++v) {
+        HIP_TRY(hipMemcpy(d_words + (size_t)v * (size_t)n_words, in + 8 + (size_t)v * (size_t)stride + (size_t)n_tiles, (size_t)n_words * 8u, hipMemcpyHostToDevice));
+        h_views[(size_t)v] = TileView{d_words + (size_t)v * (size_t)n_words, d_chunks + (size_t)v * (size_t)n_tiles};
+    }
+    HIP_TRY(hipMemcpy(d_views, h_views.data(), (size_t)n_views * sizeof(TileView), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_chunks, chunks.data(), ints_b, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_flags, 0xff, 2u * ints_b));                  // (a flag nobody wrote reads -1)
+    (void)hipGetLastError();
+    for (int v = 0; v < n_views; ++v) launch_tile_check(nullptr, h_views[(size_t)v].words, h_views[(size_t)v].chunks, d_flags + (size_t)v * (size_t)n_tiles, W, H, c, cs, tol, floor);
+    launch_tile_check_batch(nullptr, d_views, d_flags + n_all, n_views, W, H, c, cs, tol, floor);
+    HIP_TRY(hipGetLastError());
+    std::vector<int32_t> h((size_t)n_all * 2u);
+    HIP_TRY(hipMemcpy(h.data(), d_flags, 2u * ints_b, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < h.size(); ++k) out[k] = h[k];
+    return 0;
+}
+
+// op 22: in = n slots whose low 32 bits are the flags; out (raw int64) = count, list[n] of accum_tile_compact_kernel | the same of count /
+// scan / scatter.  Both lists are prefilled with -1: the slots behind the count read -1.
+int unit_compact(int n, const unsigned long long *in, long long *out) {
+    if (n < 1 || n > RTW_ACCUM_UNIT_SLOTS) return fail(-2, "unit op 22: count is the number of flags, 1 .. %lld (got %d)", RTW_ACCUM_UNIT_SLOTS, n);
+    std::vector<int32_t> flags((size_t)n);
+    for (int k = 0; k < n; ++k) flags[(size_t)k] = (int32_t)(uint32_t)in[k];
+    DeviceGuard guard;
+    if (int rc = unit_device()) return rc;
+    const int n_blocks = compact_blocks(n);
+    const size_t res = (size_t)n + 4u;                               // one result: list | count (+ 3 unused)
+    DevBuf buf;
+    HIP_TRY(hipMalloc(&buf.p, ((size_t)n + 2u * res + (size_t)n_blocks) * sizeof(int32_t)));
+    int32_t *d_flags = static_cast<int32_t *>(buf.p), *d_res = d_flags + n, *d_blocks = d_res + 2u * res;
+    HIP_TRY(hipMemcpy(d_flags, flags.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_res, 0xff, 2u * res * sizeof(int32_t)));
+    (void)hipGetLastError();
+    launch_compact_loop(nullptr, d_flags, d_res, d_res + n, n);
+    launch_compact_blocks(nullptr, d_flags, d_blocks, d_res + res, d_res + res + n, n);
+    HIP_TRY(hipGetLastError());
+    std::vector<int32_t> h(2u * res);
+    HIP_TRY(hipMemcpy(h.data(), d_res, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int r = 0; r < 2; ++r) {
+        long long *o = out + (size_t)r * ((size_t)n + 1u);
+        const int32_t *s = h.data() + (size_t)r * res;
+        o[0] = s[n];
+        for (int k = 0; k < n; ++k) o[1 + k] = s[k];
+    }
+    return 0;
+}
+
+// op 23: in = width, height, spp, chunk_spp, gamma, 0, 0, 0 | n_tiles x C_t | W * H * 8 raw words; out = the W * H * 3 values of
+// accum_resolve_tiles_kernel<T>, each widened to binary64
+template <typename T>
+int unit_resolve_tiles(int count, const double *in, double *out) {
+    int W, H, spp, cs, gamma;
+    if (count != 1) return fail(-2, "unit op 23: count must be 1 (got %d)", count);
+    if (int rc = unit_frame(in, &W, &H)) return rc;
+    if (!slot_int(in[2], 1, 0x7fffffff, &spp) || !slot_int(in[3], 1, 0x7fffffff, &cs) || !slot_int(in[4], 0, 1, &gamma))
+        return fail(-2, "unit op 23: spp %g, chunk_spp %g, gamma %g", in[2], in[3], in[4]);
+    if (in[5] != 0.0 || in[6] != 0.0 || in[7] != 0.0) return fail(-2, "unit op 23: header slots 5 to 7 must be 0");
+    const long long n_tiles = tiles_of(W, H), n_words = (long long)W * H * 8;
+    std::vector<int32_t> chunks;
+    if (int rc = unit_chunks(in + 8, n_tiles, 1, &chunks)) return rc;
+    DeviceGuard guard;
+    if (int rc = unit_device()) return rc;
+    const size_t n_out = (size_t)W * (size_t)H * 3u, words_b = (size_t)n_words * 8u, out_b = up16(n_out * sizeof(T));
+    DevBuf buf;
+    HIP_TRY(hipMalloc(&buf.p, words_b + out_b + (size_t)n_tiles * sizeof(int32_t)));
+    unsigned long long *d_words = static_cast<unsigned long long *>(buf.p);
+    T *d_out = reinterpret_cast<T *>(static_cast<char *>(buf.p) + words_b);
+    int32_t *d_chunks = reinterpret_cast<int32_t *>(static_cast<char *>(buf.p) + words_b + out_b);
+    HIP_TRY(hipMemcpy(d_words, in + 8 + (size_t)n_tiles, words_b, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_chunks, chunks.data(), (size_t)n_tiles * sizeof(int32_t), hipMemcpyHostToDevice));
+    (void)hipGetLastError();
+    launch_resolve_tiles<T>(nullptr, d_words, d_out, d_chunks, W, H, spp, cs, gamma);
+    HIP_TRY(hipGetLastError());
+    std::vector<T> h(n_out);
+    HIP_TRY(hipMemcpy(h.data(), d_out, n_out * sizeof(T), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n_out; ++k) out[k] = (double)h[k];
+    return 0;
+}
+
 }  // namespace
+
+int accum_unit(int op, bool f64, int count, const void *in, void *out) {
+    if (!in || !out) return fail(-1, "null argument");
+    if (op != 23 && !f64) return fail(-2, "unit op %d is an op of rtw_unit_f64", op);
+    switch (op) {
+        case 21: return unit_tile_check(count, static_cast<const double *>(in), static_cast<long long *>(out));
+        case 22: return unit_compact(count, static_cast<const unsigned long long *>(in), static_cast<long long *>(out));
+        case 23: return f64 ? unit_resolve_tiles<double>(count, static_cast<const double *>(in), static_cast<double *>(out))
+                            : unit_resolve_tiles<float>(count, static_cast<const double *>(in), static_cast<double *>(out));
+    }
+    return fail(-2, "unknown unit op %d", op);
+}
 
 }  // namespace rtwh
 

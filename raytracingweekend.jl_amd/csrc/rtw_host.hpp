@@ -235,6 +235,10 @@ int rccl_reduce_frames(RcclSet &set, const std::vector<const void *> &send, void
 void rccl_shutdown();
 int launch_untile(bool f64, const void *gather, void *frame, int W, int H, long n_tiles, int n_shards, long pad_tiles, hipStream_t stream);
 
+// rtw_accum.hip: the unit ops 21-23 (include/rtw_hip.h rtw_unit_f64): the tile check, the compactions and the per-tile resolve on the
+// caller's words, through the launch helpers the adaptive loop itself uses
+int accum_unit(int op, bool f64, int count, const void *in, void *out);
+
 // rtw_unit.hip
 int run_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene, const rtw_camera_f32 *cam);
 int run_unit_f64(int op, int count, const void *in, void *out, const rtw_scene_f64 *scene, const rtw_camera_f64 *cam);

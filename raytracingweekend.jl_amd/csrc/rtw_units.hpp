@@ -19,8 +19,12 @@ enum UnitOp {
     U_EXACT_MATH = 16,       // t_sqrt / t_rcp against the compiler's IEEE sqrt / division on a RANGE of binary32 bit patterns (Float32 only)
     // pass-1 candidate sinks: the scans of ops 10, 11, 13, 14 with a CandSink -- per ray what pass 2 was handed instead of the hit (scenes of <= 512 spheres)
     U_SINK_LDS = 17, U_SINK_CULL = 18, U_SINK_MFMA = 19, U_SINK_MFMA_CULL = 20,
-    U_NUM_OPS = 21
+    // the accumulator's tile kernels on hand-made words (rtw_accum.hip accum_unit; whole-call layouts, not per item: include/rtw_hip.h): the
+    // stopping rule's two check kernels, the two compactions, the per-tile resolve.  rtw_unit.hip hands them over before its per-item path.
+    U_ACCUM_TILE_CHECK = 21, U_ACCUM_COMPACT = 22, U_ACCUM_RESOLVE_TILES = 23,
+    U_NUM_OPS = 24
 };
+__host__ __device__ inline bool unit_is_accum(int op) { return op >= U_ACCUM_TILE_CHECK && op <= U_ACCUM_RESOLVE_TILES; }
 __host__ __device__ inline bool unit_is_sink(int op) { return op >= U_SINK_LDS && op <= U_SINK_MFMA_CULL; }
 #define RTW_SINK_SPHERES 512
 #define RTW_SINK_SLOTS 18
