@@ -394,6 +394,51 @@ int rtw_render_adaptive_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *
                                   const rtw_params *p, const rtw_adaptive_t *adaptive,
                                   const rtw_accum_handle *accums, void *d_out, void *hip_stream);
 
+/* First-hit feature buffers: per pixel the surface colour, normal and depth of what the camera sees first, and how much of the pixel is
+ * covered -- the guides that denoisers, edge-aware upsamplers and compositing steps want next to a low-sample-count image (a progressive
+ * prefix, an adaptive render).  Defined on the render's own primary rays, exact like the image itself.
+ *
+ * The definition.  A render `p` (width W, height H, spp = S, seed, numerics bits, camera) has N effective chunks of s = ceil(S / n_chunks)
+ * samples under the default rule of rtw_params.n_chunks (N = rtw_stats_t.n_chunks of the render).  Chunk c of pixel (i, j) (1-based row,
+ * column) starts with the random stream of (seed, pix, c), pix = (j-1)*H + (i-1), and its first sample has the global index c*s.  The
+ * FEATURE SAMPLE of (pixel, chunk c) is the primary ray of that first sample, built exactly as the render builds it: the jitter is drawn
+ * iff c*s != 0 -- du = rand / T(Float32(W)), then dv = rand / T(Float32(H)) --, then get_ray(cam, T(j/W) + du, T((H-i)/H) + dv) with its
+ * lens-disk rejection drawn from the same stream (src/render.jl:26-37, src/camera.jl:43-48), then hit(world, ray, T(1e-4), typemax(T)) in
+ * the render's numerics mode, ties resolved as the render's scans resolve them (the later sphere of the caller's list).  With s == 1 these
+ * are all the primary rays of the image, otherwise every s-th.  Each feature sample contributes 8 binary64 values:
+ *     slot 0-2  albedo    hit: the attenuation of scatter() (src/material.jl: the albedo of a Lambertian / Metal, (1, 1, 1) for a Dielectric), widened
+ *                         miss: skycolor(ray) as the render adds it (src/ray_color.jl:1-6, binary64)
+ *     slot 3-5  normal    hit: HitRecord.n, the face-forwarded normal (src/hit.jl:6-10; a negative radius flips the outward normal), widened; miss: 0
+ *     slot 6    depth     hit: HitRecord.t, widened; miss: 0
+ *     slot 7    coverage  hit: 1; miss: 0
+ * The values of the chunks [chunk_begin, chunk_begin + chunk_count) are summed per slot as signed 64.64 fixed-point integers, exactly as the
+ * render sums radiances (each value truncated towards zero at 2^-64; a value that is not finite or beyond 2^31 poisons the pixel); each sum
+ * is rounded once to binary64, divided by (double)chunk_count and the quotient rounded to T.  No gamma.  Normals are NOT renormalised and
+ * depth is averaged over ALL samples of the range, hits or not: the caller divides both by coverage.  A poisoned pixel is NaN in all 8 slots.
+ * Layout: pixel-interleaved, pixel (i, j) at ((j-1)*H + (i-1)) * RTW_FEATURE_CHANNELS -- Julia's Array{T,3} of size (8, H, W).
+ *   The result depends on p (size, spp, n_chunks, seed, numerics bits), the camera, the scene and the chunk range only: RTW_FLAG_GROUP_CULL,
+ * RTW_FLAG_SCAN_VALU and every legal job_pixels are accepted and give identical words; max_depth and gamma are ignored (but validated).
+ *
+ * rtw_render_features_device_*: `d_out` is a DEVICE pointer, 16-byte aligned, to height*width*8 elements; asynchronous like
+ * rtw_render_device_*.  rtw_render_features_*: `out` is a HOST buffer of that size; blocking; the per-device scene, stream and buffer cache
+ * of rtw_render_f32.  rtw_stats() afterwards reports this call: samples = segments = W*H*chunk_count (one scan per pixel and chunk),
+ * sphere_tests = segments * n, n_chunks = N, the kernel's HIP-event time.
+ *   Refusals, all decided before any HIP call and before a handle is looked at: a null scene / cam / p / output -> -1; the usual validation of
+ * rtw_params -- sizes, unknown flags, both numerics bits, job_pixels -> -2; chunk_begin < 0, chunk_count < 1 or a range beyond N -> -2;
+ * shard_count != 1, RTW_FLAG_COMPACT_TILES, RTW_FLAG_RCCL_REDUCE, RTW_FLAG_RAY_POOL, n_devices > 1 or device_ids -> -2; a d_out that is not
+ * 16-byte aligned -> -2; a frame of 2^31 tiles or more -> -5.  Then: a scene handle of the other precision, or on another device than
+ * p->device names -> -4.  Batched views, feature sums in accumulators, per-tile chunk prefixes of adaptive renders and device lists are
+ * out of scope.  Additive to ABI 4: detected by symbol lookup. */
+#define RTW_FEATURE_CHANNELS 8
+int rtw_render_features_device_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p,
+                                   int32_t chunk_begin, int32_t chunk_count, void *d_out, void *hip_stream);
+int rtw_render_features_device_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p,
+                                   int32_t chunk_begin, int32_t chunk_count, void *d_out, void *hip_stream);
+int rtw_render_features_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p,
+                            int32_t chunk_begin, int32_t chunk_count, float *out);
+int rtw_render_features_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p,
+                            int32_t chunk_begin, int32_t chunk_count, double *out);
+
 /* Counters/timings of the last render issued from this thread (waits for it to finish). */
 int rtw_stats(rtw_stats_t *out);
 

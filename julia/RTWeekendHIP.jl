@@ -458,4 +458,54 @@ function render_adaptive(scene::HittableList, cams::AbstractVector{Camera{T}}, i
     img, chunks
 end
 
+"""
+    render_features(scene, cam, image_width=400, n_samples=1; seed=1, n_chunks=0, chunks=nothing, device=-1, numerics=:reference, group_cull=false, scan_valu=false)
+
+First-hit feature buffers (rtw_render_features_f32/_f64) of the render `render(scene, cam, image_width, n_samples; seed, n_chunks)`: an
+`Array{T,3}` of size (8, image_height, image_width) -- per pixel `[1:3]` albedo (the sky colour where nothing is hit), `[4:6]` the
+face-forwarded normal, `[7]` depth (t), `[8]` coverage, each the mean over the primary rays of the chunks' first samples (normals are not
+renormalised, depth is averaged over hits and misses alike: divide both by the coverage).  `chunks=nothing`: the whole render;
+`chunks=(begin, count)`: that range of its effective chunks (0-based, as in `render_progressive`).  A poisoned pixel is NaN in all 8 slots.
+(Not executed in this repository: there is no `julia` in its build image; tests/test_gpu_features.py drives the same entry point.)
+"""
+function render_features(scene::HittableList, cam::Camera{T}, image_width=400, n_samples=1;
+                         seed=1, n_chunks=0, chunks=nothing, device=-1, numerics=:reference, group_cull=false, scan_valu=false) where T <: Union{Float32,Float64}
+    numerics in (:reference, :contract, :reference_fma2) || throw(ArgumentError("numerics must be :reference, :contract or :reference_fma2"))
+    nflags = numerics === :contract ? 32 : numerics === :reference_fma2 ? 128 : 0
+    image_height = image_width ÷ (16//9)
+    # the effective chunks of the render under the default rule of rtw_params.n_chunks
+    nch = min(n_chunks > 0 ? n_chunks : min(n_samples, 256), n_samples)
+    chunk_spp = cld(n_samples, nch)
+    chunk_begin, chunk_count = chunks === nothing ? (0, cld(n_samples, chunk_spp)) : chunks
+    n = length(scene)
+    cx = Vector{T}(undef, n); cy = similar(cx); cz = similar(cx); r = similar(cx)
+    ar = similar(cx); ag = similar(cx); ab = similar(cx); param = similar(cx)
+    kind = Vector{Int32}(undef, n)
+    for (i, h) in enumerate(scene)
+        h isa Sphere{T} || throw(ArgumentError("scene[$i] is $(typeof(h)); the HIP path takes Sphere{$T} only"))
+        cx[i], cy[i], cz[i] = h.center
+        r[i] = h.radius
+        kind[i] = matkind(h.mat)
+        ar[i], ag[i], ab[i] = albedo(h.mat)
+        param[i] = matparam(h.mat)
+    end
+    out = Array{T,3}(undef, 8, image_height, image_width)       # RTW_FEATURE_CHANNELS values per pixel, pixels column-major
+    ccam = Ref(CCamera(cam))
+    rc = GC.@preserve cx cy cz r kind ar ag ab param out begin
+        params = Ref(CParams(image_width, image_height, n_samples, 16, seed, n_chunks, 0, 1, device, 1,
+                             (group_cull ? 1 : 0) | (scan_valu ? 4 : 0) | nflags, 0, 0, Ptr{Int32}(C_NULL)))
+        cscene = Ref(CScene{T}(n, pointer(cx), pointer(cy), pointer(cz), pointer(r), pointer(kind),
+                               pointer(ar), pointer(ag), pointer(ab), pointer(param)))
+        if T === Float32
+            ccall((:rtw_render_features_f32, LIB), Cint, (Ref{CScene{Float32}}, Ref{CCamera{Float32}}, Ref{CParams}, Int32, Int32, Ptr{Float32}),
+                  cscene, ccam, params, chunk_begin, chunk_count, pointer(out))
+        else
+            ccall((:rtw_render_features_f64, LIB), Cint, (Ref{CScene{Float64}}, Ref{CCamera{Float64}}, Ref{CParams}, Int32, Int32, Ptr{Float64}),
+                  cscene, ccam, params, chunk_begin, chunk_count, pointer(out))
+        end
+    end
+    rc == 0 || error("librtw_hip: error $rc: $(last_error())")
+    out
+end
+
 end # module

@@ -18,6 +18,7 @@ SYMBOLS = [
     "rtw_accum_merge", "rtw_accum_info", "rtw_accum_ranges", "rtw_accum_read_pixels", "rtw_accum_export", "rtw_accum_import",
     "rtw_render_adaptive_f32", "rtw_render_adaptive_f64", "rtw_accum_adaptive_info", "rtw_accum_tile_chunks",
     "rtw_render_accum_batch_f32", "rtw_render_accum_batch_f64", "rtw_render_adaptive_batch_f32", "rtw_render_adaptive_batch_f64",
+    "rtw_render_features_device_f32", "rtw_render_features_device_f64", "rtw_render_features_f32", "rtw_render_features_f64",
 ]
 
 
@@ -115,6 +116,9 @@ def lib():
     for name, CamT in (("rtw_render_adaptive_batch_f32", CameraF32), ("rtw_render_adaptive_batch_f64", CameraF64)):
         getattr(L, name).argtypes = [C.c_void_p, C.POINTER(CamT), C.c_int32, C.POINTER(C.c_uint64), C.POINTER(Params), C.POINTER(Adaptive),
                                      C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]
+    for sfx, SceneT, CamT in (("f32", SceneF32, CameraF32), ("f64", SceneF64, CameraF64)):
+        getattr(L, "rtw_render_features_device_" + sfx).argtypes = [C.c_void_p, C.POINTER(CamT), C.POINTER(Params), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        getattr(L, "rtw_render_features_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), C.POINTER(Params), C.c_int32, C.c_int32, C.c_void_p]
     L.rtw_accum_adaptive_info.argtypes = [C.c_void_p, C.POINTER(AdaptiveInfo)]
     L.rtw_accum_tile_chunks.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rtw_accum_create.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]

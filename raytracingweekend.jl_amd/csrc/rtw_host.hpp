@@ -8,6 +8,7 @@
 //   rtw_batch_accum_f32.hip / _f64.hip  the BATCH && ACCUM instances of the trace kernel (rtw_instances.hpp: the kernel-instance table), a unit per precision
 //   rtw_accum.hip        progressive render: the accumulator object, its passes, merge / resolve kernels, export / import
 //   rtw_unit.hip         the T0 unit entry points (rtw_units.hpp)
+//   rtw_features.hip     first-hit feature buffers: one launch of the feature kernel (rtw_features.hpp), the device-resident entry points
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
 #pragma once
 #pragma GCC visibility push(default)
@@ -226,6 +227,8 @@ int render_host_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const
 int render_host_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, double *out);
 int render_host_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, float *out);
 int render_host_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, double *out);
+int render_host_features_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, float *out);
+int render_host_features_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, double *out);
 
 // rtw_multi.hip
 int ensure_peer(const CtxPtr &ctx, int dev, int root, bool *direct);
@@ -238,6 +241,15 @@ int launch_untile(bool f64, const void *gather, void *frame, int W, int H, long 
 // rtw_accum.hip: the unit ops 21-23 (include/rtw_hip.h rtw_unit_f64): the tile check, the compactions and the per-tile resolve on the
 // caller's words, through the launch helpers the adaptive loop itself uses
 int accum_unit(int op, bool f64, int count, const void *in, void *out);
+
+// rtw_features.hip -- first-hit feature buffers (include/rtw_hip.h rtw_render_features_*).  validate_features: the checks that need no device
+// (the render, whole frames on one device, the chunk range); launch_features: enqueue the feature kernel for the chunks [chunk_begin,
+// chunk_begin + chunk_count) on `stream`, `rec` receives the counters and the kernel's events like a render's.
+int validate_features(const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, int *n_chunks, int *chunk_spp);
+int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
+int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
+inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_features_f32(s, c, p, b, n, d, st, r, x); }
+inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_features_f64(s, c, p, b, n, d, st, r, x); }
 
 // rtw_unit.hip
 int run_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene, const rtw_camera_f32 *cam);

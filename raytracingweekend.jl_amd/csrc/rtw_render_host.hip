@@ -322,6 +322,39 @@ int render_host_batch(const SceneT *scene, const CamT *cams, int32_t n_views, co
     return rc;
 }
 
+// First-hit feature buffers (rtw_render_features_f32/_f64): the one-device path above with a device buffer of W x H x 8 elements, ONE launch of
+// the feature kernel (rtw_features.hip), ONE D2H.
+template <typename T, typename SceneT, typename CamT>
+int render_host_features(const SceneT *scene, const CamT *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, T *out) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !cam || !out) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = validate_features(p, chunk_begin, chunk_count, &nch, &cs)) return rc;
+    DeviceGuard guard;
+    release_last();
+    if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
+    std::vector<unsigned char> key;
+    scene_key_of(scene, sizeof(T) == 8, key);
+    HostLease L;
+    if (int rc = acquire_host(p->device, key, &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_scene<T>(hc, scene, key)) return rc;
+    rtw_params q = *p;
+    q.device = hc->device; q.n_devices = 0; q.device_ids = nullptr;
+    const size_t elems = (size_t)q.width * (size_t)q.height * RTW_FEATURE_CHANNELS;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, elems * sizeof(T))) return rc;
+    RenderRec *rec = nullptr;
+    CtxPtr rctx;
+    int rc = launch_features_t(hc->scene, cam, &q, chunk_begin, chunk_count, hc->d_img, hc->stream, &rec, &rctx);
+    if (!rc) rc = copy_out(hc, hc->d_img, out, elems * sizeof(T));
+    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    if (!rc) rc = resolve_rec(rec, &g_last.agg);
+    if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
+    if (rec) release_rec(rctx, rec, rc == 0);
+    g_last.resolved = rc == 0;
+    return rc;
+}
+
 int render_host_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, float *out) { return render_host<float>(scene, cam, p, out); }
 int render_host_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, double *out) { return render_host<double>(scene, cam, p, out); }
 int render_host_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, float *out) {
@@ -329,6 +362,12 @@ int render_host_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams
 }
 int render_host_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, double *out) {
     return render_host_batch<double>(scene, cams, n_views, seeds, p, out);
+}
+int render_host_features_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, float *out) {
+    return render_host_features<float>(scene, cam, p, chunk_begin, chunk_count, out);
+}
+int render_host_features_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, double *out) {
+    return render_host_features<double>(scene, cam, p, chunk_begin, chunk_count, out);
 }
 
 }  // namespace rtwh

@@ -181,6 +181,12 @@ class DeviceRenderer:
         _capi.check(fn(self.handle, Cm, n, sd, C.byref(P), C.c_void_p(int(d_out_ptr)), C.c_void_p(int(stream))))
         return height
 
+    def features_into(self, d_out_ptr, image_width, n_samples, **kw):
+        """Enqueue the first-hit feature pass (rtw_render_features_device_f32/_f64) of this scene and camera into device memory at
+        ``d_out_ptr``: H*W*8 elements, 16-byte aligned.  Keywords: ``features.features_into``."""
+        from .features import features_into
+        return features_into(self, d_out_ptr, image_width, n_samples, **kw)
+
     def stats(self):
         st = _capi.Stats()
         _capi.check(self.L.rtw_stats(C.byref(st)))

@@ -1,11 +1,15 @@
 #!/usr/bin/env python3
 """Register / scratch / occupancy table of every trace_kernel instantiation (hipcc -Rpass-analysis=kernel-resource-usage).
-usage: python tools/kernel_resources.py [extra hipcc flags]   (cross-compiles for gfx950, no GPU needed)
-The instances live in rtw_launch.hip and, the BATCH && ACCUM ones, in rtw_batch_accum_f32.hip / _f64.hip: one table over all three."""
+usage: python tools/kernel_resources.py [--unit NAME.hip ...] [extra hipcc flags]   (cross-compiles for gfx950, no GPU needed)
+The instances live in rtw_launch.hip and, the BATCH && ACCUM ones, in rtw_batch_accum_f32.hip / _f64.hip: one table over all three.
+--unit names other translation units instead (rtw_features.hip: the instances of the feature kernel)."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = ""
-for unit in ("rtw_launch.hip", "rtw_batch_accum_f32.hip", "rtw_batch_accum_f64.hip"):
+units = []
+while len(sys.argv) > 2 and sys.argv[1] == "--unit":
+    units.append(sys.argv[2]); del sys.argv[1:3]
+for unit in units or ("rtw_launch.hip", "rtw_batch_accum_f32.hip", "rtw_batch_accum_f64.hip"):
     src = os.path.join(ROOT, "raytracingweekend.jl_amd", "csrc", unit)
     cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-fno-fast-math", "-fno-slp-vectorize", "-mllvm", "-amdgpu-mfma-vgpr-form",
            "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/dev/null"] + sys.argv[1:]
@@ -24,6 +28,9 @@ for r in rows:
     m = re.match(r"_ZN3rtw12trace_kernelI([fd])Lb([01])ELb([01])ELb([01])ELb([01])ELi(n?\d+)ELb([01])ELb([01])ELb([01])E", n)
     if m:
         label = f"trace<{'f32' if m.group(1) == 'f' else 'f64'}{', profile' if m.group(2) == '1' else ''}{', lds-scene' if m.group(3) == '1' else ', global-scene'}{', cull' if m.group(4) == '1' else ''}{', mfma' if m.group(5) == '1' else ''}{', numerics fixed' if not m.group(6).startswith('n') else ''}{', batch' if m.group(7) == '1' else ''}{', accum' if m.group(8) == '1' else ''}{', adapt' if m.group(9) == '1' else ''}>"
+    elif re.match(r"_ZN3rtw15features_kernelI([fd])Lb([01])ELb([01])ELi(n?\d+)E", n):
+        m = re.match(r"_ZN3rtw15features_kernelI([fd])Lb([01])ELb([01])ELi(n?\d+)E", n)
+        label = f"features<{'f32' if m.group(1) == 'f' else 'f64'}{', mfma' if m.group(2) == '1' else ', valu'}{', lds-scene' if m.group(3) == '1' else ', global-scene'}{', numerics fixed' if not m.group(4).startswith('n') else ''}>"
     elif "unit_kernel" in n:
         label = "unit_kernel<%s>" % ("f32" if "IfE" in n else "f64")
     else:
