@@ -83,6 +83,12 @@ int launch_features(rtw_scene_handle scene, const CamT *cam, const rtw_params *p
     // the default numerics mode of the headline variant (scene in LDS, matrix pipe): the mode fixed at compile time
     if (mfma && lds_scene && numerics == rtw::NUM_REFERENCE) kern = (kern_t)rtw::features_kernel<T, true, true, rtw::NUM_REFERENCE>;
     const unsigned grid = (K.n_tiles + RTW_FEATURE_WAVES - 1u) / RTW_FEATURE_WAVES;
+    // (test aid: which instance the rules above picked, in the form of the trace kernel's line -- rtw_launch.hip; the grid is one workgroup
+    //  per RTW_FEATURE_WAVES tiles, no occupancy question is asked: blocks_per_cu=0)
+    static const bool debug = aid_env("RTW_DEBUG") != nullptr;
+    if (debug)
+        fprintf(stderr, "[rtw debug] features instance: %s lds_scene=%d cull=0 mfma=%d fixed=%d batch=0 accum=0 adapt=0 lds_bytes=%zu blocks_per_cu=0\n", sizeof(T) == 8 ? "f64" : "f32",
+                (int)lds_scene, (int)mfma, (int)(mfma && lds_scene && numerics == rtw::NUM_REFERENCE), lds_bytes);
 
     RenderRec *rec;
     if (int rc = acquire_rec(ctx.get(), &rec)) return rc;

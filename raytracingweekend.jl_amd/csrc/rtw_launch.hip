@@ -176,6 +176,12 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
         }
     }
     if (blocks_per_cu < 1) blocks_per_cu = 1;
+    // (test aid: which instance the rules above picked -- `fixed`: the one with the default numerics mode compiled in)
+    static const bool debug = aid_env("RTW_DEBUG") != nullptr;
+    if (debug && !pool)
+        fprintf(stderr, "[rtw debug] trace instance: %s lds_scene=%d cull=%d mfma=%d fixed=%d batch=%d accum=%d adapt=%d lds_bytes=%zu blocks_per_cu=%d\n", sizeof(T) == 8 ? "f64" : "f32",
+                (int)lds_scene, (int)cull, (int)mfma, (int)(fixed && lds_scene && mfma && !(phase_profile && !batch && !pass)), (int)batch, (int)(pass != nullptr), (int)(pass && pass->adapt),
+                lds_bytes, blocks_per_cu);
     long long grid = (long long)ctx->num_cus * blocks_per_cu;
     // Job size.  A job is owned by one workgroup, so its size sets the end-of-queue drain; smaller jobs also store the
     // image in smaller pieces (more partial-line writes).  2x2 pixels (a batch = 4 pixels x 16 chunks) when the chunks

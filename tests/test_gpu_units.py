@@ -126,7 +126,7 @@ def test_scatter(oracle, T):
     kind = rng.integers(0, 3, n)
     albedo = rng.uniform(0, 1, (n, 3)).astype(T).astype(np.float64)
     param = np.where(kind == 1, rng.uniform(0, 5, n), 1.5).astype(T).astype(np.float64)
-    param[kind == 1][:8] = 0.0
+    param[np.flatnonzero(kind == 1)[:8]] = 0.0
     d, nrm = unit_dirs(rng, n, T), unit_dirs(rng, n, T)
     flip = np.sum(d * nrm, 1) > 0
     nrm[flip] *= -1                                            # the hit normal faces the incoming ray
