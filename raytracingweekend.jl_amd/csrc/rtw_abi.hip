@@ -80,6 +80,15 @@ int acquire_rec(DeviceCtx *ctx, RenderRec **out) {
     return 0;
 }
 
+int begin_record(DeviceCtx *ctx, const rtw_scene_dev *scene, int n_chunks, int grid, int block, size_t ctr_bytes, hipStream_t stream, RenderRec **rec_out) {
+    if (int rc = acquire_rec(ctx, rec_out)) return rc;
+    RenderRec *rec = *rec_out;
+    rec->n_spheres = scene->n; rec->n_chunks = n_chunks; rec->grid = grid; rec->block = block; rec->ctr_bytes = ctr_bytes;
+    HIP_TRY(hipMemsetAsync(rec->ctr, 0, rec->fresh ? sizeof(rtw::DevCounters) : rec->ctr_bytes, stream));
+    rec->fresh = false;
+    return 0;
+}
+
 void release_rec(const CtxPtr &ctx, RenderRec *r, bool finished) {
     std::lock_guard<std::mutex> lk(ctx->mu);
     if (finished) r->done = true;
@@ -96,6 +105,7 @@ void release_last() {
     memset(&g_last.agg, 0, sizeof g_last.agg);
     g_last.per_device.clear();
 }
+void hold_last(RenderRec *rec, const CtxPtr &ctx) { if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); } }
 LastRender::~LastRender() {
     if (generation == g_generation.load())
         for (size_t k = 0; k < recs.size(); ++k) release_rec(ctxs[k], recs[k], false);
@@ -137,6 +147,11 @@ int validate_params(const rtw_params *p, int *n_chunks, int *chunk_spp) {
     return 0;
 }
 
+int check_chunk_range(int32_t begin, int32_t count, int nch) {
+    if (begin >= 0 && count >= 1 && (long long)begin + count <= nch) return 0;
+    return fail(-2, "chunk range [%d, %lld) is not inside the render's %d chunks", begin, (long long)begin + count, nch);
+}
+
 long long local_tiles(const rtw_params *p) {
     const long long n_tiles = (long long)((p->height + 7) / 8) * ((p->width + 7) / 8);
     return n_tiles > p->shard_index ? (n_tiles - p->shard_index + p->shard_count - 1) / p->shard_count : 0;
@@ -173,7 +188,7 @@ int render_device_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_view
     CtxPtr ctx;
     release_last();
     int rc = launch_render_t(scene, cams, n_views, seeds, p, d_out, (hipStream_t)stream_v, &rec, &ctx);
-    if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); }       // (also on a late error: released by the next call)
+    hold_last(rec, ctx);               // (also on a late error: released by the next call)
     return rc;
 }
 
@@ -185,7 +200,7 @@ int render_device(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, 
     CtxPtr ctx;
     release_last();
     int rc = launch_render_t(scene, cam, 0, nullptr, p, d_out, (hipStream_t)stream_v, &rec, &ctx);
-    if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); }       // (also on a late error: released by the next call)
+    hold_last(rec, ctx);               // (also on a late error: released by the next call)
     return rc;
 }
 

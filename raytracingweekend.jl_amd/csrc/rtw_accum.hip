@@ -415,8 +415,7 @@ int validate_accum(rtw_scene_handle scene, const CamT *cam, const rtw_params *p,
     if (!cam || !a || !scene) return fail(-1, "null argument");
     int nch, cs;
     if (int rc = validate_frame(p, &nch, &cs)) return rc;
-    if (chunk_begin < 0 || chunk_count < 1 || (long long)chunk_begin + chunk_count > nch)
-        return fail(-2, "chunk range [%d, %lld) is not inside the render's %d chunks", chunk_begin, (long long)chunk_begin + chunk_count, nch);
+    if (int rc = check_chunk_range(chunk_begin, chunk_count, nch)) return rc;
     if (int rc = validate_handles(sizeof(CamT) == sizeof(rtw_camera_f64), scene, p, a)) return rc;
     if (a->adaptive) return fail(-2, "the accumulator is adaptive (its tiles hold different chunk counts): rtw_render_adaptive_* continues it, rtw_accum_reset() makes it a plain one");
     if (a->bound) {
@@ -452,7 +451,7 @@ int accum_pass(bool single, rtw_scene_handle scene, const CamT *cams, int32_t n_
     CtxPtr ctx;
     release_last();
     int rc = launch_render_t(scene, cams, single ? 0 : n_views, seeds, p, d_out, stream, &rec, &ctx, &pass);
-    if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); }       // (also on a late error: released by the next call)
+    hold_last(rec, ctx);               // (also on a late error: released by the next call)
     if (rc) return rc;
     for (int32_t v = 0; v < n_views; ++v) {
         rtw_accum *a = accums[v];
@@ -585,7 +584,7 @@ int adaptive_loop(bool single, rtw_scene_handle scene, const CamT *cams, int32_t
         ps.words = single ? a0->words : nullptr; ps.chunk_begin = begin; ps.chunk_count = count; ps.samples = 1;
         ps.adapt = true; ps.tile_list = list; ps.list_tiles = n_list; ps.views = single ? nullptr : views.data();
         int rc = launch_render_t(scene, cams, single ? 0 : n_views, seeds, p, nullptr, stream, &rec, &ctx, &ps);
-        if (rc) { if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); rec = nullptr; } return rc; }     // (released by the next call)
+        if (rc) { hold_last(rec, ctx); rec = nullptr; return rc; }     // (released by the next call)
         (void)hipGetLastError();
         if (single) hipLaunchKernelGGL(accum_tile_advance_kernel, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, stream, list, n_list, a0->d_tiles, count);
         else hipLaunchKernelGGL(accum_tile_advance_batch_kernel, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, stream, list, n_list, d_views, n_tiles, count);
@@ -660,7 +659,7 @@ int adaptive_loop(bool single, rtw_scene_handle scene, const CamT *cams, int32_t
         return 0;
     };
     const int rc = run();
-    if (rec) { g_last.recs.push_back(rec); g_last.ctxs.push_back(ctx); }       // (a failure between a pass and its wait)
+    hold_last(rec, ctx);               // (a failure between a pass and its wait)
     if (rc) {
         for (int32_t v = 0; v < n_views; ++v) if (accums[v]->bound) HIP_IGNORE(hipEventRecord(accums[v]->ev, stream));
         if (scratch.p) HIP_IGNORE(hipStreamSynchronize(stream));               // (the scratch is freed on return)
@@ -707,8 +706,7 @@ int render_accum_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_views
                        const rtw_accum_handle *accums, void *d_out, void *stream_v) {
     int nch, cs;
     if (int rc = validate_views(scene, cams, n_views, p, accums, &nch, &cs)) return rc;
-    if (chunk_begin < 0 || chunk_count < 1 || (long long)chunk_begin + chunk_count > nch)
-        return fail(-2, "chunk range [%d, %lld) is not inside the render's %d chunks", chunk_begin, (long long)chunk_begin + chunk_count, nch);
+    if (int rc = check_chunk_range(chunk_begin, chunk_count, nch)) return rc;
     if (int rc = validate_distinct(n_views, accums)) return rc;
     // every accumulator on its own, as rtw_render_accum_* validates it -- all of them before anything is touched
     std::vector<AccumBind> binds((size_t)n_views);

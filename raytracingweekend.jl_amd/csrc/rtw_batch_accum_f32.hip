@@ -3,8 +3,8 @@
 
 namespace rtwh {
 
-const void *batch_accum_kernel_f32(bool cull, bool mfma, bool lds_scene, bool fixed, bool adapt) {
-    return adapt ? trace_instance_of<float, true, true, true>(cull, mfma, lds_scene, fixed) : trace_instance_of<float, true, true, false>(cull, mfma, lds_scene, fixed);
+TraceInstance batch_accum_kernel_f32(bool cull, bool mfma, bool lds_scene, bool fixed, bool adapt) {
+    return adapt ? trace_instance_of<float, true, true, true>(cull, mfma, lds_scene, fixed, false) : trace_instance_of<float, true, true, false>(cull, mfma, lds_scene, fixed, false);
 }
 
 }  // namespace rtwh

@@ -1,14 +1,15 @@
 // rtw_host.hpp -- host-side internals of librtw_hip.so shared by its translation units (nothing here is part of the C ABI):
 //   rtw_abi.hip          the extern "C" entry points (include/rtw_hip.h), argument validation, the per-device contexts and the per-render
-//                        records behind rtw_stats()
+//                        records behind rtw_stats(): begin_record / run_record, the one sequence around every launch that has a record
 //   rtw_scene.hip        scene upload: SoA rows, kd split of the group-cull layout, the f16-split operands of the matrix-pipe filter
-//   rtw_launch.hip       one render = one launch of the trace kernel (rtw_kernels.hpp / rtw_pool.hpp): geometry, job shape, counters
-//   rtw_render_host.hip  the host-buffer entry points: cached per-device context (scene, stream, image), one device or a device list
+//   rtw_launch.hip       one render = one launch of the trace kernel (rtw_kernels.hpp / rtw_pool.hpp): geometry, occupancy, job shape, views
+//   rtw_render_host.hip  the host-buffer entry points: cached per-device context (scene, stream, image), ONE one-device path (render_one_device) or a device list
 //   rtw_multi.hip        what a device list needs: peer access, the on-demand RCCL binding, the un-tile kernel
 //   rtw_batch_accum_f32.hip / _f64.hip  the BATCH && ACCUM instances of the trace kernel (rtw_instances.hpp: the kernel-instance table), a unit per precision
 //   rtw_accum.hip        progressive render: the accumulator object, its passes, merge / resolve kernels, export / import
 //   rtw_unit.hip         the T0 unit entry points (rtw_units.hpp)
 //   rtw_features.hip     first-hit feature buffers: one launch of the feature kernel (rtw_features.hpp), the device-resident entry points
+//   (rtw_scene_view.hpp: what both launch functions derive from their arguments; rtw_instances.hpp: the one table of the trace kernel's instances)
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
 #pragma once
 #pragma GCC visibility push(default)
@@ -178,12 +179,30 @@ struct LastRender {
     ~LastRender();                          // a thread that exits hands its records back
 };
 extern thread_local LastRender g_last;
+void hold_last(RenderRec *rec, const CtxPtr &ctx);       // the record of a device-resident call (null: none) stays with this thread for rtw_stats()
 
 int get_ctx(int device, CtxPtr *out);
 int acquire_rec(DeviceCtx *ctx, RenderRec **out);           // a record nobody references whose previous kernel (if any) has finished; the device must be current
 void release_rec(const CtxPtr &ctx, RenderRec *r, bool finished);
+// The sequence around every launch that has a record.  begin_record: a record (acquire_rec) that describes the launch, the first `ctr_bytes`
+// of its counters -- what comes back to the host -- cleared on `stream`; *rec_out is set as soon as a record exists, so the caller can hold
+// it after a late error.  run_record: ev0, `launch()` (it enqueues the kernel and nothing else), ev1, the counters' copy, ev2.
+int begin_record(DeviceCtx *ctx, const rtw_scene_dev *scene, int n_chunks, int grid, int block, size_t ctr_bytes, hipStream_t stream, RenderRec **rec_out);
+template <typename Launch>
+int run_record(RenderRec *rec, hipStream_t stream, Launch launch) {
+    HIP_TRY(hipEventRecord(rec->ev0, stream));
+    (void)hipGetLastError();           // (hipEventQuery's hipErrorNotReady in acquire_rec must not be mistaken for a launch failure)
+    launch();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(rec->ev1, stream));
+    HIP_TRY(hipMemcpyAsync(rec->h_ctr, rec->ctr, rec->ctr_bytes, hipMemcpyDeviceToHost, stream));     // (into pinned memory: truly asynchronous)
+    HIP_TRY(hipEventRecord(rec->ev2, stream));
+    rec->used = true; rec->done = false;
+    return 0;
+}
 int resolve_device(int device, int *out);
 int validate_params(const rtw_params *p, int *n_chunks, int *chunk_spp);
+int check_chunk_range(int32_t begin, int32_t count, int nch);     // [begin, begin + count) lies inside a render's `nch` effective chunks
 long long local_tiles(const rtw_params *p);
 
 template <typename SceneT> bool s_has_bad_scene(const SceneT *s) {
@@ -215,10 +234,12 @@ int launch_render_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_
 inline int launch_render_t(rtw_scene_handle s, const rtw_camera_f32 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const AccumPass *a = nullptr) { return launch_render_f32(s, c, n, sd, p, d, st, r, x, a); }
 inline int launch_render_t(rtw_scene_handle s, const rtw_camera_f64 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const AccumPass *a = nullptr) { return launch_render_f64(s, c, n, sd, p, d, st, r, x, a); }
 int resolve_rec(RenderRec *r, rtw_stats_t *agg);            // wait for a record's kernel and add its counters to `agg`
+// what the kernel-instance table answers (rtw_instances.hpp): the kernel, and whether it has the default numerics mode compiled in
+struct TraceInstance { const void *kern; bool fixed; };
 // rtw_batch_accum_f32.hip / _f64.hip: the BATCH && ACCUM (&& ADAPT) instance of the trace kernel for a scan variant, as launch_render chooses
-// among the other instances (rtw_instances.hpp; `fixed`: the numerics mode is the default one, which the headline variants have compiled in)
-const void *batch_accum_kernel_f32(bool cull, bool mfma, bool lds_scene, bool fixed, bool adapt);
-const void *batch_accum_kernel_f64(bool cull, bool mfma, bool lds_scene, bool fixed, bool adapt);
+// among the other instances (`fixed`: the numerics mode is the default one, which the headline variants have compiled in)
+TraceInstance batch_accum_kernel_f32(bool cull, bool mfma, bool lds_scene, bool fixed, bool adapt);
+TraceInstance batch_accum_kernel_f64(bool cull, bool mfma, bool lds_scene, bool fixed, bool adapt);
 // rtw_abi.hip: the checks of a batched render that need no device (include/rtw_hip.h rtw_render_batch_f32)
 int validate_batch(const void *cams, int32_t n_views, const rtw_params *p, const void *out);
 

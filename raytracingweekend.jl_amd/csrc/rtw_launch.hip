@@ -1,10 +1,12 @@
-// rtw_launch.hip -- one render = ONE launch of the trace kernel (rtw_kernels.hpp; opt-in: the ray-pool kernel of rtw_pool.hpp): which
-// instantiation, the persistent grid, the job shape, the per-render counters and events, and what rtw_stats() reads back.
+// rtw_launch.hip -- one render = ONE launch of the trace kernel (rtw_kernels.hpp; opt-in: the ray-pool kernel of rtw_pool.hpp).  launch_render
+// reads top to bottom: validate, parameters, scene view (rtw_scene_view.hpp), instance (rtw_instances.hpp), occupancy, job shape, record
+// (rtw_host.hpp begin_record / run_record), views, launch; its own steps are the static functions in front of it.  Behind it: resolve_rec.
 #include "rtw_scene_view.hpp"
 #include "rtw_kernels.hpp"
 #include "rtw_instances.hpp"
 #ifdef RTW_WITH_POOL          // `make POOL=1`: the ray-pool kernel (a measured 16 - 19 % LOSS on this chip, DESIGN_LOG R4) is not in the default library
 #include "rtw_pool.hpp"
+template <typename T> using pool_kern_t = void (*)(rtw::KParams, rtw::Camera<T>, rtw::DevScene<T>, T *, rtw::DevCounters *);
 #endif
 
 namespace rtwh {
@@ -17,6 +19,115 @@ void make_udiv(unsigned d, unsigned *m, unsigned *s) {
     while ((1ull << l) < d) ++l;                        // l = ceil(log2 d) >= 1
     *m = (unsigned)((((1ull << l) - d) << 32) / d + 1);
     *s = l - 1;
+}
+
+// The ray-pool kernel (rtw_pool.hpp; opt-in: RTW_FLAG_RAY_POOL, or RTW_POOL=1 in the environment for A/B runs) exists in `make POOL=1`
+// builds only: `eligible` launches (Float32 plain scans on the matrix pipe, no batch, no pass), when the pool, the rings and the scene copy fit the
+// 160 KB of LDS of a CU (one workgroup of RTW_POOL_W waves per CU); everything else runs the lane-loop kernel.  The default library refuses the flag.
+struct PoolChoice { bool use = false; const void *kern = nullptr; size_t lds = 0; int block_threads = 256, blocks_per_cu = 0; };
+template <typename T>
+static int choose_pool(const DeviceCtx *ctx, const rtw_scene_dev *scene, const rtw_params *p, int cs, bool eligible, bool phase_profile, PoolChoice *pool) {
+#ifdef RTW_WITH_POOL
+    static const bool env_pool = aid_flag("RTW_POOL");
+    if constexpr (sizeof(T) == 4) {
+        pool->lds = rtw::pool_fixed_lds_bytes<T, RTW_POOL_W, RTW_POOL_R>() + rtw::pool_scene_lds_bytes<T>(scene->n, scene->n_pad);
+        pool->use = eligible && (env_pool || (p->flags & RTW_FLAG_RAY_POOL)) && pool->lds <= ctx->lds_per_cu && cs <= RTW_POOL_MAX_CHUNK_SPP;
+        pool->kern = phase_profile ? (const void *)rtw::trace_pool_kernel<T, RTW_POOL_W, RTW_POOL_R, true> : (const void *)rtw::trace_pool_kernel<T, RTW_POOL_W, RTW_POOL_R, false>;
+    }
+    if (pool->use) {
+        pool->block_threads = RTW_POOL_W * 64;
+        // "everything else runs the lane-loop kernel": also a device (or a runtime) that refuses this much dynamic LDS
+        hipError_t e = hipFuncSetAttribute(pool->kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pool->lds);
+        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&pool->blocks_per_cu, pool->kern, pool->block_threads, pool->lds);
+        if (e != hipSuccess || pool->blocks_per_cu < 1) { (void)hipGetLastError(); pool->use = false; pool->block_threads = 256; pool->blocks_per_cu = 0; }
+    }
+#else
+    if (p->flags & RTW_FLAG_RAY_POOL)
+        return fail(-7, "RTW_FLAG_RAY_POOL: this build of librtw_hip has no ray-pool kernel (a measured loss on MI355X; `make POOL=1` builds it in)");
+#endif
+    return 0;
+}
+
+// The job shape of a launch over `n_local` tiles and `nch` chunks with `grid` workgroups at full occupancy (tiles_i x tiles_j, shard_count: as
+// the kernel sees them -- a batch's columns side by side, 0 shards for a tile list): a pure function of its arguments.  (ShapeAids: the aids of A/B
+// runs, tools/gpu_ab.sh -- RTW_JOB_PIXELS = 1, 4, 8 or 16, else ignored; RTW_ROWS_SHIFT; RTW_GRID_BLOCKS caps the persistent grid: fewer waves per SIMD)
+struct ShapeAids { int job_pixels, rows_shift; long long grid_blocks; };
+struct JobShape { int job_shift, rows_shift; unsigned slot_stride, n_slots; long long total_jobs, bpj, grid; };
+static int job_shape(int nch, long long n_local, int tiles_i, int tiles_j, int shard_count, long long grid, int job_pixels, bool pool, const ShapeAids &aids, JobShape *out) {
+    // Job size.  A job is owned by one workgroup, so its size sets the end-of-queue drain; smaller jobs also store the
+    // image in smaller pieces (more partial-line writes).  2x2 pixels (a batch = 4 pixels x 16 chunks) when the chunks
+    // fill such batches, else 4x4 (x 4 chunks); ONE pixel (x 64 chunks) when a workgroup would otherwise see fewer than
+    // 150 jobs (small frames, shards of a multi-GPU render).  Measured at 1080p x 1000 spp / 250 chunks
+    // (tools/gpu_drain.py): drain 4.4 / 9.7 / 30 ms of idle wave slots for 1 / 4 / 16-pixel jobs; full frame 859 / 859 /
+    // 871 ms; a 1/8 shard 115.6 / 119.8 / 137.7 ms; HBM writes 148 / 72 / 45 MB per frame.
+    // (Slots per workgroup: 24 / 12 / 4 -- one-pixel jobs need many slots in flight; with 6 they ran 33 % slower.)
+    // Round 6, with out-of-order job slots and static first claims (tools/gpu_small_sweep.sh, kernel us for 1 / 4 / 8 / 16 pixels):
+    //   1/8 shard of 1080p x 1000 spp (250 chunks)   51.1 / 53.0 / -- / 73.8 ms      one-pixel jobs: the shortest drain
+    //   1/8 shard of 1080p x 64 spp (64 chunks)      4.28 / 4.08 / -- / 5.22 ms      (1 pixel x 64 chunks = ONE batch per job: every batch opens a job)
+    //   320 x 180 x 64 spp (64 chunks; 11 jobs of 4 pixels per workgroup)            1008 / 838 / 1002 / 997 us
+    //   200 x 112 x 32 spp Float64 (32 chunks; 5 per workgroup)                      572 / 377 / 419 / 334 us
+    //   96 x 54 x 16 spp (16 chunks; 1 per workgroup)                                527 / 155 / 91 / 58 us
+    // -> one pixel only when its batches are many (>= 2 per job); the LARGEST jobs when a workgroup sees only a handful (a frame of
+    //    a few hundred microseconds is a latency chain per wave: the fewest job openings win).
+    int job_shift = nch >= 16 ? 2 : 4;
+    if (nch >= 128 && n_local * 16 < 150 * grid) job_shift = 0;
+    else if (n_local * 16 < 8 * grid) job_shift = 4;
+    if (!job_pixels) job_pixels = aids.job_pixels;
+    if (job_pixels == 16 || job_pixels == 8 || job_pixels == 4 || job_pixels == 1) {
+        job_shift = job_pixels == 16 ? 4 : job_pixels == 8 ? 3 : job_pixels == 4 ? 2 : 0;
+    } else if (job_pixels != 0) {
+        return fail(-2, "job_pixels must be 0 (automatic), 1, 4, 8 or 16");
+    }
+    const long long total_jobs = n_local * (64 >> job_shift);
+    const long long cpb = 64 >> job_shift;
+    const long long bpj = (nch + cpb - 1) / cpb;
+    // (claim_job packs a queue position into 28 bits; queue 0 is the longest: every 8th tile column, or every 8th tile of a shard)
+    const long long queue0_jobs = (shard_count == 1 ? (long long)((tiles_j + 7) / 8) * tiles_i : (n_local + 7) / 8) * (64 >> job_shift);
+    if (total_jobs >= (1ll << 30) || queue0_jobs >= (1ll << 28) || total_jobs * bpj >= (1ll << 40))
+        return fail(-5, "render too large for one call: %lld pixel-block jobs", total_jobs);
+    out->total_jobs = total_jobs; out->bpj = bpj; out->job_shift = job_shift;
+    out->rows_shift = std::min(job_shift, 3);       // 4 x 1, 8 x 1, 8 x 2 pixels: whole column strips
+    if (aids.rows_shift >= 0 && aids.rows_shift <= job_shift && aids.rows_shift <= 3 && job_shift - aids.rows_shift <= 2) out->rows_shift = aids.rows_shift;
+    out->slot_stride = (unsigned)(sizeof(rtw::JobSlot) + 64u * (1u << job_shift));
+    out->n_slots = std::min(24u, (unsigned)RTW_SLOT_BYTES / out->slot_stride);             // 24 / 12 / 7 / 4 slots of 1 / 4 / 8 / 16 pixels
+    long long max_useful = (total_jobs * bpj + 3) / 4;                                             // one batch per wave, 4 waves per block
+#ifdef RTW_WITH_POOL
+    if (pool) max_useful = (total_jobs * bpj * 64 + RTW_POOL_R - 1) / RTW_POOL_R;                  // one item per slot of the pool
+#endif
+    if (grid > max_useful) grid = max_useful;
+    if (aids.grid_blocks > 0 && grid > aids.grid_blocks) grid = aids.grid_blocks;
+    out->grid = grid < 1 ? 1 : grid;
+    return 0;
+}
+
+// A batch's views: the cameras and seeds go into the record's pinned buffer, then ONE asynchronous H2D on the render's stream (the record
+// is handed out again only after ev2, behind this copy, so the pinned buffer is free whenever a render holds the record).
+// (a batched pass: behind them the views' accumulators and divisors, rtw::AccumView)
+template <typename T, typename CamT>
+static int upload_views(RenderRec *rec, const CamT *cam, int n_views, const uint64_t *seeds, uint64_t seed, const AccumPass *pass, hipStream_t stream, rtw::BatchArgs<T> *B, rtw::AccumArgs *A) {
+    const size_t cam_bytes = (size_t)n_views * sizeof(rtw::Camera<T>), seed_bytes = (size_t)n_views * sizeof(unsigned long long);
+    static_assert(sizeof(rtw::Camera<T>) % 8 == 0, "the seeds and the view table behind the cameras are 8-byte aligned");
+    const size_t bytes = cam_bytes + seed_bytes + (pass ? (size_t)n_views * sizeof(rtw::AccumView) : 0);
+    if (rec->views_cap < bytes) {
+        if (rec->d_views) { HIP_IGNORE(hipFree(rec->d_views)); rec->d_views = nullptr; }
+        if (rec->h_views) { HIP_IGNORE(hipHostFree(rec->h_views)); rec->h_views = nullptr; }
+        rec->views_cap = 0;
+        HIP_TRY(hipMalloc(&rec->d_views, bytes));
+        HIP_TRY(hipHostMalloc(&rec->h_views, bytes, hipHostMallocDefault));
+        rec->views_cap = bytes;
+    }
+    rtw::Camera<T> *hc = reinterpret_cast<rtw::Camera<T> *>(rec->h_views);
+    unsigned long long *hs = reinterpret_cast<unsigned long long *>(static_cast<char *>(rec->h_views) + cam_bytes);
+    for (int v = 0; v < n_views; ++v) { hc[v] = device_camera<T>(cam[v]); hs[v] = seeds ? seeds[v] : seed; }
+    if (pass) {
+        rtw::AccumView *hv = reinterpret_cast<rtw::AccumView *>(static_cast<char *>(rec->h_views) + cam_bytes + seed_bytes);
+        for (int v = 0; v < n_views; ++v) { hv[v].words = pass->views[v].words; hv[v].samples = pass->views[v].samples; hv[v].pad = 0; }
+        A->views = reinterpret_cast<const rtw::AccumView *>(static_cast<const char *>(rec->d_views) + cam_bytes + seed_bytes);
+    }
+    HIP_TRY(hipMemcpyAsync(rec->d_views, rec->h_views, bytes, hipMemcpyHostToDevice, stream));
+    B->cams = reinterpret_cast<const rtw::Camera<T> *>(rec->d_views);
+    B->seeds = reinterpret_cast<const unsigned long long *>(static_cast<const char *>(rec->d_views) + cam_bytes);
+    return 0;
 }
 
 // Enqueue one render (this shard's tiles) on `stream`; `rec` receives the counters and the kernel's events.
@@ -71,233 +182,93 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
     K.gamma = p->gamma;
     K.out_layout = (p->flags & RTW_FLAG_COMPACT_TILES) ? 1 : 0;
     make_udiv((unsigned)K.tiles_i, &K.div_tiles_m, &K.div_tiles_s);
-
-    rtw::Camera<T> C;
-    for (int k = 0; k < 3; ++k) {
-        C.origin[k] = cam->origin[k]; C.llc[k] = cam->lower_left_corner[k];
-        C.horizontal[k] = cam->horizontal[k]; C.vertical[k] = cam->vertical[k];
-        C.u[k] = cam->u[k]; C.v[k] = cam->v[k]; C.w[k] = cam->w[k];
-    }
-    C.lens_radius = cam->lens_radius;
+    const rtw::Camera<T> C = device_camera<T>(*cam);
+    // ---- scene view: group cull reads the caller's order beside the cull layout, whose exact rows and index are what is staged in LDS ----
     using V4 = typename rtw::Vec4<T>::type;
-    rtw::DevScene<T> S = dev_scene_of<T>(scene);
-    // the deciding arithmetic of the ray-sphere test (include/rtw_hip.h RTW_FLAG_NUMERICS_*): a property of the render, not of the upload
-    S.numerics = (p->flags & RTW_FLAG_NUMERICS_CONTRACT) ? rtw::NUM_CONTRACT : (p->flags & RTW_FLAG_NUMERICS_REFERENCE_FMA2) ? rtw::NUM_REFERENCE_FMA2 : rtw::NUM_REFERENCE;
-
-    // persistent grid: enough 256-thread blocks to fill every CU at the kernel's occupancy
+    const int numerics = numerics_of(p->flags);
     static const bool phase_profile = aid_env("RTW_PHASE_PROFILE") != nullptr;   // debugging aid, not for timed runs
     const size_t list_bytes = (size_t)RTW_LIST_CAP * 256 * sizeof(unsigned short);
     const size_t shared_bytes = (sizeof(rtw::WgShared<T>) + 15) / 16 * 16;
     const bool cull = (p->flags & RTW_FLAG_GROUP_CULL) != 0;
     rtw::CullScene<T> CS = cull_scene_of<T>(scene);
-    CS.numerics = S.numerics;
-    const size_t n_cull = (size_t)rtw::cull_exact_count(CS);
+    CS.numerics = numerics;
     // the plain scan runs pass 1 on the matrix pipe (RTW_SCAN=valu: the all-VALU scan, for A/B measurements)
     static const bool force_valu = aid_env("RTW_SCAN") != nullptr && strcmp(aid_env("RTW_SCAN"), "valu") == 0;
     // (group cull: on the matrix pipe too when the scene has the operands; RTW_FLAG_SCAN_VALU selects the all-VALU cull scan)
     const bool mfma = (cull ? scene->c_mf_ops != nullptr : scene->mf_ops != nullptr) && !force_valu && !(p->flags & RTW_FLAG_SCAN_VALU);
-    // (group cull on the matrix pipe: the tables of the block vote travel with the scene copy)
-    const size_t geom_bytes = cull ? n_cull * sizeof(V4) + ((n_cull * sizeof(unsigned short) + 15) / 16) * 16 +
-                                         (mfma ? (size_t)rtw::cull_tab_words(scene->c_mf_blocks) * sizeof(unsigned) : 0)
-                                   : (size_t)rtw::scene_geom_alloc(scene->n, scene->n_pad) * sizeof(V4);
-    const bool lds_scene = geom_bytes <= RTW_LDS_SCENE_MAX_BYTES;
-    // the plain scan on the matrix pipe reads the scene in its own order (rtw_scene.hip build_plain); its index array travels with the scene copy.
-    // (lds_scene is decided by the caller-order bytes above, so a scene takes the same instance whatever the layout; what is then asked for
-    //  is plain_bytes: up to 31 dead rows + the huge spheres more, and 2 B per entry for the index -- at most 24 KB x 18 / 16 + 1.2 KB.  The
-    //  grid follows the runtime's occupancy answer for the bytes really requested.)
-    const bool plain_order = mfma && !cull;
-    [[maybe_unused]] const rtw::DevScene<T> S_caller = S;
-    size_t plain_bytes = 0;
-    if (plain_order) {
-        if (!scene->p_mf_ops || !scene->p_orig) return fail(-9, "internal: the scene has no arrays in the plain scan's order");
-        const int num = S.numerics;
-        S = dev_scene_plain_of<T>(scene);
-        S.numerics = num;
-        const size_t na = (size_t)rtw::scene_geom_alloc(S.n, S.n_pad);
-        plain_bytes = na * sizeof(V4) + ((na * sizeof(unsigned short) + 15) / 16) * 16;
-    }
-    const size_t lds_bytes = list_bytes + shared_bytes + (mfma ? rtw::mfma_cell_bytes<T>() : 0) + (lds_scene ? (plain_order ? plain_bytes : geom_bytes) : 0);
-    typedef void (*kern_t)(rtw::KParams, rtw::Camera<T>, rtw::DevScene<T>, rtw::CullScene<T>, T *, rtw::DevCounters *, rtw::BatchArgs<T>, rtw::AccumArgs);
-    kern_t kern;
-    if (cull && mfma && phase_profile) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, true, true, true, true> : (kern_t)rtw::trace_kernel<T, false, false, true, true>;
-    else if (cull && mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true, true> : (kern_t)rtw::trace_kernel<T, false, false, true, true>;
-    else if (cull && phase_profile) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, true, true, true> : (kern_t)rtw::trace_kernel<T, false, false, true>;
-    else if (cull) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, true> : (kern_t)rtw::trace_kernel<T, false, false, true>;
-    else if (mfma && phase_profile) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, true, true, false, true> : (kern_t)rtw::trace_kernel<T, true, false, false, true>;
-    else if (mfma) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false, true> : (kern_t)rtw::trace_kernel<T, false, false, false, true>;
-    else if (phase_profile) kern = lds_scene ? (kern_t)rtw::trace_kernel<T, true, true, false> : (kern_t)rtw::trace_kernel<T, true, false, false>;
-    else kern = lds_scene ? (kern_t)rtw::trace_kernel<T, false, true, false> : (kern_t)rtw::trace_kernel<T, false, false, false>;
-    // the default numerics mode of the headline variants (scene in LDS, matrix pipe): an instance with the mode fixed at compile time
-    if (S.numerics == rtw::NUM_REFERENCE && lds_scene && mfma && !phase_profile)
-        kern = cull ? (kern_t)rtw::trace_kernel<T, false, true, true, true, rtw::NUM_REFERENCE> : (kern_t)rtw::trace_kernel<T, false, true, false, true, rtw::NUM_REFERENCE>;
-    // a batch, a pass of a progressive render, a pass of an adaptive one: the same choice among the BATCH, the ACCUM and the ACCUM && ADAPT
-    // instances (rtw_instances.hpp; no phase profile); a pass of a batch of such renders: among the BATCH && ACCUM instances (a translation
-    // unit per precision)
-    const bool fixed = S.numerics == rtw::NUM_REFERENCE;
-    if (batch && pass) kern = (kern_t)(sizeof(T) == 8 ? batch_accum_kernel_f64(cull, mfma, lds_scene, fixed, pass->adapt) : batch_accum_kernel_f32(cull, mfma, lds_scene, fixed, pass->adapt));
-    else if (batch) kern = (kern_t)trace_instance_of<T, true, false, false>(cull, mfma, lds_scene, fixed);
-    else if (pass && !pass->adapt) kern = (kern_t)trace_instance_of<T, false, true, false>(cull, mfma, lds_scene, fixed);
-    else if (pass) kern = (kern_t)trace_instance_of<T, false, true, true>(cull, mfma, lds_scene, fixed);
-    // The ray-pool kernel (rtw_pool.hpp; opt-in: RTW_FLAG_RAY_POOL, or RTW_POOL=1 in the environment for A/B runs) exists in `make POOL=1`
-    // builds only: Float32 plain scans on the matrix pipe, when the pool, the rings and the scene copy fit the 160 KB of LDS of a CU (one
-    // workgroup of RTW_POOL_W waves per CU); everything else runs the lane-loop kernel above.  The default library refuses the flag.
-    [[maybe_unused]] size_t pool_lds = 0;
-    bool pool = false;
-    int block_threads = 256;
-    int blocks_per_cu = 0;
-#ifdef RTW_WITH_POOL
-    static const bool env_pool = aid_flag("RTW_POOL");
-    typedef void (*pool_kern_t)(rtw::KParams, rtw::Camera<T>, rtw::DevScene<T>, T *, rtw::DevCounters *);
-    pool_kern_t pool_kern = nullptr;
-    if constexpr (sizeof(T) == 4) {
-        pool_lds = rtw::pool_fixed_lds_bytes<T, RTW_POOL_W, RTW_POOL_R>() + rtw::pool_scene_lds_bytes<T>(scene->n, scene->n_pad);
-        pool = !batch && !pass && mfma && !cull && (env_pool || (p->flags & RTW_FLAG_RAY_POOL)) && pool_lds <= ctx->lds_per_cu &&
-               cs <= RTW_POOL_MAX_CHUNK_SPP;
-        pool_kern = phase_profile ? (pool_kern_t)rtw::trace_pool_kernel<T, RTW_POOL_W, RTW_POOL_R, true> : (pool_kern_t)rtw::trace_pool_kernel<T, RTW_POOL_W, RTW_POOL_R, false>;
-    }
-    if (pool) {
-        block_threads = RTW_POOL_W * 64;
-        // "everything else runs the lane-loop kernel": also a device (or a runtime) that refuses this much dynamic LDS
-        hipError_t e = hipFuncSetAttribute((const void *)pool_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pool_lds);
-        if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, pool_kern, block_threads, pool_lds);
-        if (e != hipSuccess || blocks_per_cu < 1) { (void)hipGetLastError(); pool = false; block_threads = 256; blocks_per_cu = 0; }
-    }
-#else
-    if (p->flags & RTW_FLAG_RAY_POOL)
-        return fail(-7, "RTW_FLAG_RAY_POOL: this build of librtw_hip has no ray-pool kernel (a measured loss on MI355X; `make POOL=1` builds it in)");
-#endif
-    if (!pool) {
+    PlainView<T> V;
+    if (cull) {
+        const size_t n_cull = (size_t)rtw::cull_exact_count(CS);
+        V.scene = dev_scene_of<T>(scene);
+        V.scene.numerics = numerics;
+        // (on the matrix pipe the tables of the block vote travel with the scene copy)
+        V.scene_bytes = n_cull * sizeof(V4) + ((n_cull * sizeof(unsigned short) + 15) / 16) * 16 + (mfma ? (size_t)rtw::cull_tab_words(scene->c_mf_blocks) * sizeof(unsigned) : 0);
+        V.lds_scene = V.scene_bytes <= RTW_LDS_SCENE_MAX_BYTES;
+    } else if (int rc = plain_scene_view<T>(scene, mfma, numerics, &V)) return rc;
+    const bool lds_scene = V.lds_scene;
+    const size_t lds_bytes = list_bytes + shared_bytes + (mfma ? rtw::mfma_cell_bytes<T>() : 0) + (lds_scene ? V.scene_bytes : 0);
+    // ---- instance (rtw_instances.hpp; a pass of a batch of renders: the BATCH && ACCUM instances, a translation unit per precision) ----
+    const bool fixed = numerics == rtw::NUM_REFERENCE;
+    TraceInstance inst;
+    if (!batch && !pass) inst = trace_instance_of<T, false, false, false>(cull, mfma, lds_scene, fixed, phase_profile);
+    else if (batch && pass) inst = sizeof(T) == 8 ? batch_accum_kernel_f64(cull, mfma, lds_scene, fixed, pass->adapt) : batch_accum_kernel_f32(cull, mfma, lds_scene, fixed, pass->adapt);
+    else if (batch) inst = trace_instance_of<T, true, false, false>(cull, mfma, lds_scene, fixed, phase_profile);
+    else if (!pass->adapt) inst = trace_instance_of<T, false, true, false>(cull, mfma, lds_scene, fixed, phase_profile);
+    else inst = trace_instance_of<T, false, true, true>(cull, mfma, lds_scene, fixed, phase_profile);
+    const trace_kern_t<T> kern = (trace_kern_t<T>)inst.kern;
+    // ---- occupancy: the persistent grid is enough 256-thread blocks to fill every CU at the kernel's occupancy ----
+    PoolChoice pool;
+    if (int rc = choose_pool<T>(ctx.get(), scene, p, cs, !batch && !pass && mfma && !cull, phase_profile, &pool)) return rc;
+    int blocks_per_cu = pool.blocks_per_cu;
+    if (!pool.use) {
         // (the runtime's answer for a (kernel, LDS size) pair does not change: asked once per device context -- 4 us per render otherwise)
         std::lock_guard<std::mutex> lk(ctx->mu);
-        for (auto &o : ctx->occupancy) if (o.first.first == (const void *)kern && o.first.second == lds_bytes) blocks_per_cu = o.second;
+        for (auto &o : ctx->occupancy) if (o.first.first == inst.kern && o.first.second == lds_bytes) blocks_per_cu = o.second;
         if (blocks_per_cu < 1) {
             HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, kern, 256, lds_bytes));
-            ctx->occupancy.push_back({{(const void *)kern, lds_bytes}, blocks_per_cu});
+            ctx->occupancy.push_back({{inst.kern, lds_bytes}, blocks_per_cu});
         }
     }
     if (blocks_per_cu < 1) blocks_per_cu = 1;
-    // (test aid: which instance the rules above picked -- `fixed`: the one with the default numerics mode compiled in)
+    // (test aid: which instance the table picked -- `fixed`: the one with the default numerics mode compiled in)
     static const bool debug = aid_env("RTW_DEBUG") != nullptr;
-    if (debug && !pool)
+    if (debug && !pool.use)
         fprintf(stderr, "[rtw debug] trace instance: %s lds_scene=%d cull=%d mfma=%d fixed=%d batch=%d accum=%d adapt=%d lds_bytes=%zu blocks_per_cu=%d\n", sizeof(T) == 8 ? "f64" : "f32",
-                (int)lds_scene, (int)cull, (int)mfma, (int)(fixed && lds_scene && mfma && !(phase_profile && !batch && !pass)), (int)batch, (int)(pass != nullptr), (int)(pass && pass->adapt),
-                lds_bytes, blocks_per_cu);
-    long long grid = (long long)ctx->num_cus * blocks_per_cu;
-    // Job size.  A job is owned by one workgroup, so its size sets the end-of-queue drain; smaller jobs also store the
-    // image in smaller pieces (more partial-line writes).  2x2 pixels (a batch = 4 pixels x 16 chunks) when the chunks
-    // fill such batches, else 4x4 (x 4 chunks); ONE pixel (x 64 chunks) when a workgroup would otherwise see fewer than
-    // 150 jobs (small frames, shards of a multi-GPU render).  Measured at 1080p x 1000 spp / 250 chunks
-    // (tools/gpu_drain.py): drain 4.4 / 9.7 / 30 ms of idle wave slots for 1 / 4 / 16-pixel jobs; full frame 859 / 859 /
-    // 871 ms; a 1/8 shard 115.6 / 119.8 / 137.7 ms; HBM writes 148 / 72 / 45 MB per frame.
-    // (Slots per workgroup: 24 / 12 / 4 -- one-pixel jobs need many slots in flight; with 6 they ran 33 % slower.)
-    // Round 6, with out-of-order job slots and static first claims (tools/gpu_small_sweep.sh, kernel us for 1 / 4 / 8 / 16 pixels):
-    //   1/8 shard of 1080p x 1000 spp (250 chunks)   51.1 / 53.0 / -- / 73.8 ms      one-pixel jobs: the shortest drain
-    //   1/8 shard of 1080p x 64 spp (64 chunks)      4.28 / 4.08 / -- / 5.22 ms      (1 pixel x 64 chunks = ONE batch per job: every batch opens a job)
-    //   320 x 180 x 64 spp (64 chunks; 11 jobs of 4 pixels per workgroup)            1008 / 838 / 1002 / 997 us
-    //   200 x 112 x 32 spp Float64 (32 chunks; 5 per workgroup)                      572 / 377 / 419 / 334 us
-    //   96 x 54 x 16 spp (16 chunks; 1 per workgroup)                                527 / 155 / 91 / 58 us
-    // -> one pixel only when its batches are many (>= 2 per job); the LARGEST jobs when a workgroup sees only a handful (a frame of
-    //    a few hundred microseconds is a latency chain per wave: the fewest job openings win).
-    int job_shift = nch >= 16 ? 2 : 4;
-    if (nch >= 128 && n_local * 16 < 150 * grid) job_shift = 0;
-    else if (n_local * 16 < 8 * grid) job_shift = 4;
-    // (measurement aid for A/B runs, tools/gpu_ab.sh: RTW_JOB_PIXELS = 1, 4, 8 or 16; any other value is ignored)
-    static const int env_job_pixels = [] { const char *e = aid_env("RTW_JOB_PIXELS"); const int v = e ? atoi(e) : 0; return (v == 1 || v == 4 || v == 8 || v == 16) ? v : 0; }();
-    const int job_pixels = p->job_pixels ? p->job_pixels : env_job_pixels;
-    if (job_pixels == 16 || job_pixels == 8 || job_pixels == 4 || job_pixels == 1) {
-        job_shift = job_pixels == 16 ? 4 : job_pixels == 8 ? 3 : job_pixels == 4 ? 2 : 0;
-    } else if (job_pixels != 0) {
-        return fail(-2, "job_pixels must be 0 (automatic), 1, 4, 8 or 16");
-    }
-    const long long total_jobs = n_local * (64 >> job_shift);
-    const long long cpb = 64 >> job_shift;
-    const long long bpj = (nch + cpb - 1) / cpb;
-    // (claim_job packs a queue position into 28 bits; queue 0 is the longest: every 8th tile column, or every 8th tile of a shard)
-    const long long queue0_jobs = (K.shard_count == 1 ? (long long)((K.tiles_j + 7) / 8) * K.tiles_i : (n_local + 7) / 8) * (64 >> job_shift);
-    if (total_jobs >= (1ll << 30) || queue0_jobs >= (1ll << 28) || total_jobs * bpj >= (1ll << 40))
-        return fail(-5, "render too large for one call: %lld pixel-block jobs", total_jobs);
-    K.total_jobs = (unsigned)total_jobs; K.local_tiles = (unsigned)n_local; K.bpj = (unsigned)bpj; K.job_shift = (unsigned)job_shift;
-    K.rows_shift = (unsigned)std::min(job_shift, 3);       // 4 x 1, 8 x 1, 8 x 2 pixels: whole column strips
-    static const int env_rows_shift = aid_env("RTW_ROWS_SHIFT") ? atoi(aid_env("RTW_ROWS_SHIFT")) : -1;             // measurement aid: job shape
-    if (env_rows_shift >= 0 && env_rows_shift <= job_shift && env_rows_shift <= 3 && job_shift - env_rows_shift <= 2) K.rows_shift = (unsigned)env_rows_shift;
-    K.slot_stride = (unsigned)(sizeof(rtw::JobSlot) + 64u * (1u << job_shift));
-    K.n_slots = std::min(24u, (unsigned)RTW_SLOT_BYTES / K.slot_stride);             // 24 / 12 / 7 / 4 slots of 1 / 4 / 8 / 16 pixels
-    make_udiv((unsigned)bpj, &K.div_bpj_m, &K.div_bpj_s);
-    long long max_useful = (total_jobs * bpj + 3) / 4;                                             // one batch per wave, 4 waves per block
-#ifdef RTW_WITH_POOL
-    if (pool) max_useful = (total_jobs * bpj * 64 + RTW_POOL_R - 1) / RTW_POOL_R;                  // one item per slot of the pool
-#endif
-    if (grid > max_useful) grid = max_useful;
-    // (measurement aid: RTW_GRID_BLOCKS caps the persistent grid -- fewer waves per SIMD, same image)
-    static const long long env_grid = aid_env("RTW_GRID_BLOCKS") ? atoll(aid_env("RTW_GRID_BLOCKS")) : 0;
-    if (env_grid > 0 && grid > env_grid) grid = env_grid;
-    if (grid < 1) grid = 1;
-
-    RenderRec *rec;
-    if (int rc = acquire_rec(ctx.get(), &rec)) return rc;
-    *rec_out = rec;
-    rec->n_spheres = scene->n; rec->n_chunks = nch; rec->grid = (int)grid; rec->block = block_threads;
-    // the counters: queue heads + segment / sample counts (+ the phase cells) are cleared per render; the drain clocks and their 16 KB
-    // histogram only when the drain is profiled (the kernel touches them only then)
+                (int)lds_scene, (int)cull, (int)mfma, (int)inst.fixed, (int)batch, (int)(pass != nullptr), (int)(pass && pass->adapt), lds_bytes, blocks_per_cu);
+    // ---- job shape ----
+    static const ShapeAids aids = {[] { const char *e = aid_env("RTW_JOB_PIXELS"); const int v = e ? atoi(e) : 0; return (v == 1 || v == 4 || v == 8 || v == 16) ? v : 0; }(),
+                                   aid_env("RTW_ROWS_SHIFT") ? atoi(aid_env("RTW_ROWS_SHIFT")) : -1, aid_env("RTW_GRID_BLOCKS") ? atoll(aid_env("RTW_GRID_BLOCKS")) : 0};
+    JobShape J;
+    if (int rc = job_shape(nch, n_local, K.tiles_i, K.tiles_j, K.shard_count, (long long)ctx->num_cus * blocks_per_cu, p->job_pixels, pool.use, aids, &J)) return rc;
+    K.total_jobs = (unsigned)J.total_jobs; K.local_tiles = (unsigned)n_local; K.bpj = (unsigned)J.bpj; K.job_shift = (unsigned)J.job_shift;
+    K.rows_shift = (unsigned)J.rows_shift; K.slot_stride = J.slot_stride; K.n_slots = J.n_slots;
+    make_udiv((unsigned)J.bpj, &K.div_bpj_m, &K.div_bpj_s);
+    // ---- record.  The counters: queue heads + segment / sample counts (+ the phase cells) are cleared per render; the drain clocks and
+    // their 16 KB histogram only when the drain is profiled (the kernel touches them only then) ----
     static const bool drain_profile = aid_env("RTW_DRAIN_PROFILE") != nullptr;
     K.drain_profile = drain_profile ? 1 : 0;
-    rec->ctr_bytes = (drain_profile || phase_profile || pool) ? sizeof(rtw::DevCounters) : offsetof(rtw::DevCounters, t_first);    // (the ray-pool kernel keeps its stage profile / watchdog state in the histogram cells)
-    HIP_TRY(hipMemsetAsync(rec->ctr, 0, rec->fresh ? sizeof(rtw::DevCounters) : rec->ctr_bytes, stream));
-    rec->fresh = false;
+    const size_t ctr_bytes = (drain_profile || phase_profile || pool.use) ? sizeof(rtw::DevCounters) : offsetof(rtw::DevCounters, t_first);    // (the ray-pool kernel keeps its stage profile / watchdog state in the histogram cells)
+    if (int rc = begin_record(ctx.get(), scene, nch, (int)J.grid, pool.block_threads, ctr_bytes, stream, rec_out)) return rc;
+    RenderRec *rec = *rec_out;
     if (drain_profile) HIP_TRY(hipMemsetAsync(&rec->ctr->t_first, 0xff, sizeof(unsigned long long), stream));
-    if (batch) {
-        // the views' cameras and seeds: into the record's pinned buffer, then ONE asynchronous H2D on the render's stream (the record is
-        // handed out again only after ev2, behind this copy, so the pinned buffer is free whenever a render holds the record)
-        // (a batched pass: behind them the views' accumulators and divisors, rtw::AccumView)
-        const size_t cam_bytes = (size_t)n_views * sizeof(rtw::Camera<T>), seed_bytes = (size_t)n_views * sizeof(unsigned long long);
-        static_assert(sizeof(rtw::Camera<T>) % 8 == 0, "the seeds and the view table behind the cameras are 8-byte aligned");
-        const size_t bytes = cam_bytes + seed_bytes + (pass ? (size_t)n_views * sizeof(rtw::AccumView) : 0);
-        if (rec->views_cap < bytes) {
-            if (rec->d_views) { HIP_IGNORE(hipFree(rec->d_views)); rec->d_views = nullptr; }
-            if (rec->h_views) { HIP_IGNORE(hipHostFree(rec->h_views)); rec->h_views = nullptr; }
-            rec->views_cap = 0;
-            HIP_TRY(hipMalloc(&rec->d_views, bytes));
-            HIP_TRY(hipHostMalloc(&rec->h_views, bytes, hipHostMallocDefault));
-            rec->views_cap = bytes;
-        }
-        rtw::Camera<T> *hc = reinterpret_cast<rtw::Camera<T> *>(rec->h_views);
-        unsigned long long *hs = reinterpret_cast<unsigned long long *>(static_cast<char *>(rec->h_views) + cam_bytes);
-        for (int v = 0; v < n_views; ++v) {
-            for (int k = 0; k < 3; ++k) {
-                hc[v].origin[k] = cam[v].origin[k]; hc[v].llc[k] = cam[v].lower_left_corner[k];
-                hc[v].horizontal[k] = cam[v].horizontal[k]; hc[v].vertical[k] = cam[v].vertical[k];
-                hc[v].u[k] = cam[v].u[k]; hc[v].v[k] = cam[v].v[k]; hc[v].w[k] = cam[v].w[k];
-            }
-            hc[v].lens_radius = cam[v].lens_radius;
-            hs[v] = seeds ? seeds[v] : p->seed;
-        }
-        if (pass) {
-            rtw::AccumView *hv = reinterpret_cast<rtw::AccumView *>(static_cast<char *>(rec->h_views) + cam_bytes + seed_bytes);
-            for (int v = 0; v < n_views; ++v) { hv[v].words = pass->views[v].words; hv[v].samples = pass->views[v].samples; hv[v].pad = 0; }
-            A.views = reinterpret_cast<const rtw::AccumView *>(static_cast<const char *>(rec->d_views) + cam_bytes + seed_bytes);
-        }
-        HIP_TRY(hipMemcpyAsync(rec->d_views, rec->h_views, bytes, hipMemcpyHostToDevice, stream));
-        B.cams = reinterpret_cast<const rtw::Camera<T> *>(rec->d_views);
-        B.seeds = reinterpret_cast<const unsigned long long *>(static_cast<const char *>(rec->d_views) + cam_bytes);
-    }
+    // ---- views ----
+    if (batch) if (int rc = upload_views<T>(rec, cam, n_views, seeds, p->seed, pass, stream, &B, &A)) return rc;
     // pixels of other shards read 0 in the full-frame layout (the sum over the shards is the image)
     if (K.out_layout == 0 && p->shard_count > 1 && d_out)
         HIP_TRY(hipMemsetAsync(d_out, 0, (size_t)p->width * p->height * 3 * sizeof(T), stream));
-    HIP_TRY(hipEventRecord(rec->ev0, stream));
-    if (total_jobs > 0) {
-        (void)hipGetLastError();           // (hipEventQuery's hipErrorNotReady in acquire_rec must not be mistaken for a launch failure)
+    // ---- launch ----
+    return run_record(rec, stream, [&] {
+        if (J.total_jobs <= 0) return;
 #ifdef RTW_WITH_POOL
-        if (pool) hipLaunchKernelGGL(pool_kern, dim3((unsigned)grid), dim3((unsigned)block_threads), pool_lds, stream, K, C, S_caller, (T *)d_out, rec->ctr);      // (the caller's order)
-        else
+        if (pool.use) {
+            rtw::DevScene<T> S_caller = dev_scene_of<T>(scene);      // (the caller's order)
+            S_caller.numerics = numerics;
+            hipLaunchKernelGGL((pool_kern_t<T>)pool.kern, dim3((unsigned)J.grid), dim3((unsigned)pool.block_threads), pool.lds, stream, K, C, S_caller, (T *)d_out, rec->ctr);
+            return;
+        }
 #endif
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), lds_bytes, stream, K, C, S, CS, (T *)d_out, rec->ctr, B, A);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(rec->ev1, stream));
-    HIP_TRY(hipMemcpyAsync(rec->h_ctr, rec->ctr, rec->ctr_bytes, hipMemcpyDeviceToHost, stream));     // (into pinned memory: truly asynchronous)
-    HIP_TRY(hipEventRecord(rec->ev2, stream));
-    rec->used = true; rec->done = false;
-    return 0;
+        hipLaunchKernelGGL(kern, dim3((unsigned)J.grid), dim3(256), lds_bytes, stream, K, C, V.scene, CS, (T *)d_out, rec->ctr, B, A);
+    });
 }
 
 // wait for a record's kernel and add its counters to `agg`

@@ -1,6 +1,7 @@
 // rtw_render_host.hip -- the host-buffer entry points rtw_render_f32/_f64 (what the Julia ccall binds; replaces src/render.jl:8-44):
-// a cached per-device context (uploaded scene, stream, device image), one device or a device list (tiles dealt round-robin, shards
-// gathered on the first device by peer copies or ONE RCCL reduce: rtw_multi.hip), one D2H of the frame.
+// a cached per-device context (uploaded scene, stream, device image), one device (render_one_device: the path the batched and the
+// feature entry points share) or a device list (tiles dealt round-robin, shards gathered on the first device by peer copies or ONE RCCL
+// reduce: rtw_multi.hip), one D2H of the frame.
 #include "rtw_host.hpp"
 
 namespace rtwh {
@@ -104,6 +105,34 @@ int copy_out(HostCtx *hc, const void *d_src, void *out, size_t bytes) {
 }
 
 
+// The one-device host path of every host-buffer entry point: a leased context of `device` (negative: the current device) with the scene uploaded,
+// `elems` elements of device image, ONE launch -- launch(hc, q, &rec, &ctx) enqueues it on hc->stream into hc->d_img, q: the caller's params bound
+// to the lease's device --, ONE D2H into `out`, the counters into this thread's last render.  (elems == 0, render_host's alone: a compact shard that owns no tile)
+template <typename T, typename SceneT, typename Launch>
+int render_one_device(int device, const SceneT *scene, const rtw_params *p, size_t elems, T *out, Launch launch) {
+    if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
+    std::vector<unsigned char> key;
+    scene_key_of(scene, sizeof(T) == 8, key);
+    HostLease L;
+    if (int rc = acquire_host(device, key, &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_scene<T>(hc, scene, key)) return rc;
+    rtw_params q = *p;
+    q.device = hc->device; q.n_devices = 0; q.device_ids = nullptr;
+    if (elems == 0) { g_last.resolved = true; return 0; }
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, elems * sizeof(T))) return rc;
+    RenderRec *rec = nullptr;
+    CtxPtr rctx;
+    int rc = launch(hc, q, &rec, &rctx);
+    if (!rc) rc = copy_out(hc, hc->d_img, out, elems * sizeof(T));
+    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    if (!rc) rc = resolve_rec(rec, &g_last.agg);
+    if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
+    if (rec) release_rec(rctx, rec, rc == 0);
+    g_last.resolved = rc == 0;
+    return rc;
+}
+
 template <typename T, typename SceneT, typename CamT>
 int render_host(const SceneT *scene, const CamT *cam, const rtw_params *p, T *out) {
     if (!scene || !cam || !p || !out) return fail(-1, "null argument");
@@ -126,34 +155,17 @@ int render_host(const SceneT *scene, const CamT *cam, const rtw_params *p, T *ou
     } else if (p->n_devices < -1) {
         return fail(-2, "bad n_devices %d", p->n_devices);
     }
+    if (devs.size() <= 1 && !((p->flags & RTW_FLAG_RCCL_REDUCE) && devs.size() == 1)) {
+        // ---- one device: render into the cached device image, one D2H ----
+        const size_t elems = (p->flags & RTW_FLAG_COMPACT_TILES) ? (size_t)local_tiles(p) * 64 * 3 : (size_t)p->width * (size_t)p->height * 3;
+        return render_one_device(devs.size() == 1 ? devs[0] : p->device, scene, p, elems, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+            q.flags &= ~RTW_FLAG_RCCL_REDUCE;              // (one device: nothing to reduce)
+            return launch_render_t(hc->scene, cam, 0, nullptr, &q, hc->d_img, hc->stream, rec, rctx);
+        });
+    }
     if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
     std::vector<unsigned char> key;
     scene_key_of(scene, sizeof(T) == 8, key);
-
-    if (devs.size() <= 1 && !((p->flags & RTW_FLAG_RCCL_REDUCE) && devs.size() == 1)) {
-        // ---- one device: render into the cached device image, one D2H ----
-        HostLease L;
-        if (int rc = acquire_host(devs.size() == 1 ? devs[0] : p->device, key, &L)) return rc;
-        HostCtx *hc = L.hc;
-        if (int rc = ensure_scene<T>(hc, scene, key)) return rc;
-        rtw_params q = *p;
-        q.device = hc->device; q.n_devices = 0; q.device_ids = nullptr;
-        q.flags &= ~RTW_FLAG_RCCL_REDUCE;              // (one device: nothing to reduce)
-        const bool compact = (q.flags & RTW_FLAG_COMPACT_TILES) != 0;
-        const size_t elems = compact ? (size_t)local_tiles(&q) * 64 * 3 : (size_t)q.width * (size_t)q.height * 3;
-        if (elems == 0) { g_last.resolved = true; return 0; }
-        if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, elems * sizeof(T))) return rc;
-        RenderRec *rec = nullptr;
-        CtxPtr rctx;
-        int rc = launch_render_t(hc->scene, cam, 0, nullptr, &q, hc->d_img, hc->stream, &rec, &rctx);
-        if (!rc) rc = copy_out(hc, hc->d_img, out, elems * sizeof(T));
-        if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
-        if (!rc) rc = resolve_rec(rec, &g_last.agg);
-        if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
-        if (rec) release_rec(rctx, rec, rc == 0);
-        g_last.resolved = rc == 0;
-        return rc;
-    }
 
     // ---- several devices: shard r renders tiles t = r (mod N) on its own device and stream, then ONE of
     //   (default)             compact tile-major shards gathered in HBM of the first device -- peer copies over xGMI with peer access
@@ -299,27 +311,9 @@ int render_host_batch(const SceneT *scene, const CamT *cams, int32_t n_views, co
     if (!scene) return fail(-1, "null argument");
     DeviceGuard guard;
     release_last();
-    if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
-    std::vector<unsigned char> key;
-    scene_key_of(scene, sizeof(T) == 8, key);
-    HostLease L;
-    if (int rc = acquire_host(p->device, key, &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_scene<T>(hc, scene, key)) return rc;
-    rtw_params q = *p;
-    q.device = hc->device; q.n_devices = 0; q.device_ids = nullptr;
-    const size_t elems = (size_t)n_views * (size_t)q.width * (size_t)q.height * 3;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, elems * sizeof(T))) return rc;
-    RenderRec *rec = nullptr;
-    CtxPtr rctx;
-    int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, hc->d_img, hc->stream, &rec, &rctx);
-    if (!rc) rc = copy_out(hc, hc->d_img, out, elems * sizeof(T));
-    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
-    if (!rc) rc = resolve_rec(rec, &g_last.agg);
-    if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
-    if (rec) release_rec(rctx, rec, rc == 0);
-    g_last.resolved = rc == 0;
-    return rc;
+    return render_one_device(p->device, scene, p, (size_t)n_views * (size_t)p->width * (size_t)p->height * 3, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+        return launch_render_t(hc->scene, cams, n_views, seeds, &q, hc->d_img, hc->stream, rec, rctx);
+    });
 }
 
 // First-hit feature buffers (rtw_render_features_f32/_f64): the one-device path above with a device buffer of W x H x 8 elements, ONE launch of
@@ -332,27 +326,9 @@ int render_host_features(const SceneT *scene, const CamT *cam, const rtw_params 
     if (int rc = validate_features(p, chunk_begin, chunk_count, &nch, &cs)) return rc;
     DeviceGuard guard;
     release_last();
-    if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
-    std::vector<unsigned char> key;
-    scene_key_of(scene, sizeof(T) == 8, key);
-    HostLease L;
-    if (int rc = acquire_host(p->device, key, &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_scene<T>(hc, scene, key)) return rc;
-    rtw_params q = *p;
-    q.device = hc->device; q.n_devices = 0; q.device_ids = nullptr;
-    const size_t elems = (size_t)q.width * (size_t)q.height * RTW_FEATURE_CHANNELS;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, elems * sizeof(T))) return rc;
-    RenderRec *rec = nullptr;
-    CtxPtr rctx;
-    int rc = launch_features_t(hc->scene, cam, &q, chunk_begin, chunk_count, hc->d_img, hc->stream, &rec, &rctx);
-    if (!rc) rc = copy_out(hc, hc->d_img, out, elems * sizeof(T));
-    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
-    if (!rc) rc = resolve_rec(rec, &g_last.agg);
-    if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
-    if (rec) release_rec(rctx, rec, rc == 0);
-    g_last.resolved = rc == 0;
-    return rc;
+    return render_one_device(p->device, scene, p, (size_t)p->width * (size_t)p->height * RTW_FEATURE_CHANNELS, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+        return launch_features_t(hc->scene, cam, &q, chunk_begin, chunk_count, hc->d_img, hc->stream, rec, rctx);
+    });
 }
 
 int render_host_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, float *out) { return render_host<float>(scene, cam, p, out); }

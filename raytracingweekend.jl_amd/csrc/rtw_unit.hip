@@ -38,14 +38,7 @@ int run_unit(int op_arg, int count, const void *in, void *out, const SceneT *sce
     HIP_TRY(hipSetDevice(dev));
     rtw::Camera<T> C;
     memset(&C, 0, sizeof C);
-    if (cam) {
-        for (int k = 0; k < 3; ++k) {
-            C.origin[k] = cam->origin[k]; C.llc[k] = cam->lower_left_corner[k];
-            C.horizontal[k] = cam->horizontal[k]; C.vertical[k] = cam->vertical[k];
-            C.u[k] = cam->u[k]; C.v[k] = cam->v[k]; C.w[k] = cam->w[k];
-        }
-        C.lens_radius = cam->lens_radius;
-    }
+    if (cam) C = device_camera<T>(*cam);
     using V4 = typename rtw::Vec4<T>::type;
     size_t lds_bytes = 0;
     if (op == rtw::U_HIT_WORLD_LDS || op == rtw::U_HIT_WORLD_MFMA || op == rtw::U_SINK_LDS || op == rtw::U_SINK_MFMA) lds_bytes = (size_t)rtw::scene_geom_alloc(S.n, S.n_pad) * sizeof(V4);

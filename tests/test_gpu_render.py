@@ -296,3 +296,86 @@ def test_large_and_degenerate_scenes_in_every_scan_mode(oracle, T):
         for flags in (1, 5, 0, 4):           # group cull on the matrix pipe / on the VALU, plain scan on the matrix pipe / on the VALU
             img, st = gpu_render(g, width=64, height=36, spp=2, n_chunks=2, max_depth=6, flags=flags)
             assert np.array_equal(img, ref) and st.segments == ost["segments"], (n, flags)
+
+
+# ---- the phase-profile instances of the kernel-instance table (csrc/rtw_instances.hpp) ------------------------------------------------------
+_PROFILE_SCANS = (0, 4, 1, 5)     # plain, RTW_FLAG_SCAN_VALU, RTW_FLAG_GROUP_CULL, RTW_FLAG_GROUP_CULL | RTW_FLAG_SCAN_VALU
+_PROFILE_CHILD = """
+import sys
+sys.path[:0] = [{tests!r}, {root!r}, {oracle!r}]
+import torch
+torch.cuda.init()                       # (two HIP runtimes in one process: torch's goes first, tests/conftest.py)
+import ctypes as C
+import numpy as np
+import rtw_amd as R
+from rtw_amd import _capi
+T = np.float32
+L = _capi.lib()
+S, keep = _capi.make_scene(R.flatten_scene(R.scene_2_spheres(elem_type=T), T), T)
+h = C.c_void_p()
+_capi.check(L.rtw_scene_upload_f32(C.byref(S), 0, C.byref(h)))
+Cm = _capi.make_camera(R.t_default_cam(elem_type=T), T)
+for mode in {modes!r}:
+    for flags in {scans!r}:
+        print("@render", mode, flags, file=sys.stderr, flush=True)
+        P = _capi.make_params(width=8, height=5, spp=2, max_depth=4, flags=flags, numerics=mode)
+        d = torch.full((8 * 5 * 3,), -1.0, dtype=torch.float32, device="cuda:0")
+        _capi.check(L.rtw_render_device_f32(h, C.byref(Cm), C.byref(P), C.c_void_p(d.data_ptr()), None))
+        st = _capi.Stats()
+        _capi.check(L.rtw_stats(C.byref(st)))
+        torch.cuda.synchronize()
+        print("frame", mode, flags, d.cpu().numpy().tobytes().hex())
+L.rtw_scene_free(h)
+"""
+_profile_runs = {}
+
+
+def _profile_child(profile):
+    """The 2-sphere smoke scene at 8 x 5, 2 spp, depth 4, Float32 through rtw_render_device_f32 + rtw_stats in a fresh process (the
+    environment aids are read once per process), in every numerics mode x the four scan modes; run once, shared by the test's cases.
+    -> ({(mode, flags): frame bytes}, {(mode, flags): that render's stderr})"""
+    import os
+    import subprocess
+    import sys
+    from conftest import NUMERICS_MODES
+    if profile not in _profile_runs:
+        tests = os.path.dirname(os.path.abspath(__file__))
+        root = os.path.dirname(tests)
+        code = _PROFILE_CHILD.format(tests=tests, root=root, oracle=os.path.join(root, "oracle"), modes=tuple(NUMERICS_MODES), scans=_PROFILE_SCANS)
+        env = {k: v for k, v in os.environ.items() if k not in ("RTW_PHASE_PROFILE", "RTW_DEBUG", "RTW_DRAIN_PROFILE")}
+        env["RTW_ENABLE_TEST_AIDS"] = "1"
+        if profile:
+            env["RTW_PHASE_PROFILE"] = "1"
+        r = subprocess.run(["timeout", "-k", "10", "120", sys.executable, "-c", code], capture_output=True, text=True, env=env, timeout=150)
+        assert r.returncode == 0, r.stderr[-3000:]
+        frames = {}
+        for ln in r.stdout.splitlines():
+            if ln.startswith("frame "):
+                _, mode, flags, hexed = ln.split()
+                frames[(mode, int(flags))] = bytes.fromhex(hexed)
+        logs = {}
+        for section in r.stderr.split("@render ")[1:]:
+            mode, flags = section.split()[:2]
+            logs[(mode, int(flags))] = section
+        _profile_runs[profile] = (frames, logs)
+    return _profile_runs[profile]
+
+
+def test_phase_profile_instances_render_the_same_frames():
+    """RTW_PHASE_PROFILE selects the PROFILE instances of the plain render (nothing else reaches that part of the instance table): the
+    frames are the frames without the switch bit for bit, and every render's counters hold the wave-cycles only a PROFILE instance
+    writes (one `[rtw phase profile] wave-cycles:` line per render, total > 0; none without the switch)."""
+    import re
+    from conftest import current_numerics
+    mode = current_numerics()
+    frames, logs = _profile_child(True)
+    plain_frames, plain_logs = _profile_child(False)
+    pat = re.compile(r"^\[rtw phase profile\] wave-cycles: .*\(total ([0-9.eE+]+)\)\s*$", re.M)
+    for flags in _PROFILE_SCANS:
+        k = (mode, flags)
+        assert len(frames[k]) == 8 * 5 * 3 * 4 and frames[k] == plain_frames[k], k
+        img = np.frombuffer(frames[k], np.float32)
+        assert np.isfinite(img).all() and (img >= 0).all() and img.any(), k         # (rendered: not the -1 the buffer was filled with)
+        totals = pat.findall(logs[k])
+        assert len(totals) == 1 and float(totals[0]) > 0, (k, logs[k][-600:])
+        assert not pat.findall(plain_logs[k]), k
