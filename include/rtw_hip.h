@@ -439,6 +439,70 @@ int rtw_render_features_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *ca
 int rtw_render_features_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p,
                             int32_t chunk_begin, int32_t chunk_count, double *out);
 
+/* Feature-guided denoiser: an edge-avoiding a-trous filter of a low-sample-count image, guided by the first-hit feature buffers above.
+ *
+ * The definition.  Everything is computed in the element type T (binary32 or binary64); every operation is rounded once, no FMA, no
+ * reassociation; quotients and the final sqrt are the correctly rounded IEEE ones.  Inputs: `image`, H*W*3 in the layout of the render
+ * entry points (normally a gamma = 0 image), and `features`, H*W*8 in the layout of the feature entry points; pixel (i, j) (0-based row,
+ * column) at j*H + i.  Call the pixel's colour c[0..2] and its feature slots f[0..7].
+ *   Prepare, per pixel p.  valid(p): all 3 + 8 inputs are finite.  cov = f[7]; has(p) = valid and cov > 0.  If has: n = f[3..5] / cov
+ * (three quotients) and z = f[6] / cov, otherwise n = 0 and z = 0.  With RTW_DENOISE_DEMODULATE: a[k] = max(f[k], T(2^-6)) and
+ * e[k] = c[k] / a[k], k = 0..2; otherwise a = 1 and e = c.
+ *   Level k = 0 .. levels-1, step s = 2^k.  The host computes in binary64 sc = sigma_color * 2^-k, inv_sc = T(1.0 / (sc*sc)) and
+ * inv_sz = T(1.0 / (sigma_depth*sigma_depth)).  For every valid p: sum_w = +0, sum_e = (+0, +0, +0); the taps are visited with dj = -2..2
+ * as the outer and di = -2..2 as the inner loop; the tap pixel is q = p + s*(di, dj); h = K[|di|] * K[|dj|] with K = (3/8, 1/4, 1/16)
+ * (exact products).  The centre tap (di = dj = 0) has w = h = 9/64 and e_q = e_p.  A tap outside the frame, or whose q is not valid, is
+ * skipped.  Any other tap:
+ *       d = e_p - e_q;  dc = (d0*d0 + d1*d1) + d2*d2;  w_c = 1 / (1 + dc*inv_sc)
+ *       t_v = 1 - |cov_p - cov_q|;  w_v = t_v > 0 ? t_v : +0
+ *       w = (h*w_c)*w_v
+ *       if has(p) and has(q):
+ *           dot = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z;  t = dot > 0 ? dot : +0, then t = t*t repeated m = normal_power_log2 times
+ *           zs = z_p + z_q;  r = (z_p - z_q) / (zs > 0 ? zs : 1);  w_z = 1 / (1 + (r*r)*inv_sz)
+ *           w = (w*t)*w_z
+ * Every visited tap accumulates sum_w = sum_w + w and sum_e[k] = sum_e[k] + w*e_q[k].  After the 25 taps e'_p[k] = sum_e[k] / sum_w
+ * (sum_w >= 9/64).  All pixels of a level read the previous level's e; the guides n, z, cov and a never change.
+ *   End.  out[k] = e[k] * a[k] with RTW_DENOISE_DEMODULATE, else e[k]; then sqrt if gamma = 1.  A pixel that is not valid is a quiet NaN
+ * in all three channels, and it is never a neighbour.
+ *   The weights are rational, not exponential, so that a CPU restatement agrees on the bits (tests/denoise_ref.py); the depth difference is
+ * relative (the scenes have a ground sphere of radius 1000); the coverage term needs no parameter.
+ *
+ * The device form is asynchronous on `hip_stream` (a hipStream_t as void*; NULL = the null stream) of the device d->device (-1: the current
+ * one).  The caller owns `d_work`: as many bytes as the work-bytes call below returns for the frame (a multiple of 16, monotone in the size;
+ * < 0: an error code), 16-byte aligned; there is no shared device workspace, so any number of calls may be in flight with a workspace each.
+ * `d_features` is 16-byte aligned, `d_image` and `d_out` are aligned to T; `d_out` may not alias an input or the workspace.  The host form
+ * is blocking and uses the per-device stream and buffer cache of rtw_render_f32.  Neither changes what rtw_stats() reports: time them with
+ * stream events.
+ *   The render-and-denoise call renders `p` with gamma = 0, runs the feature pass over all N effective chunks of that render and the
+ * denoiser with d->gamma replaced by p->gamma (and d->device by p->device), all on the cached context's stream, and copies the result to
+ * `out` once.  rtw_stats() afterwards reports the render's record.
+ *   Refusals, all decided before any HIP call: a null argument -> -1; levels outside 1..8, normal_power_log2 outside 0..7, unknown flag
+ * bits, gamma other than 0 or 1, reserved != 0, device < -1, a sigma that is not finite and positive, width or height < 1, misaligned or
+ * aliasing pointers, elem_bytes other than 4 or 8 -> -2; a frame of 2^31 8x8 tiles or more -> -5; the render-and-denoise call additionally
+ * refuses everything a feature render of `p` refuses.  Variance-guided weights, temporal reuse across the views of a batch, compact or
+ * sharded frames, device lists and progressive / adaptive accumulators are out of scope.  Additive to ABI 4:
+ * detected by symbol lookup. */
+#define RTW_DENOISE_DEMODULATE 1   /* filter image / albedo, multiply back at the end */
+typedef struct {
+    int32_t levels;             /* 1..8 a-trous passes; pass k has step 2^k */
+    int32_t normal_power_log2;  /* 0..7: m, normal weight = max(0, n.n')^(2^m) */
+    int32_t flags;              /* RTW_DENOISE_* */
+    int32_t gamma;              /* 1 = sqrt per channel at the end, 0 = linear */
+    int32_t device;             /* -1 = current */
+    int32_t reserved;           /* 0 */
+    double  sigma_color;        /* > 0, finite */
+    double  sigma_depth;        /* > 0, finite */
+} rtw_denoise_t;                /* 40 bytes */
+int64_t rtw_denoise_work_bytes(int32_t width, int32_t height, int32_t elem_bytes);
+int rtw_denoise_device_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features,
+                           void *d_out, void *d_work, void *hip_stream);
+int rtw_denoise_device_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features,
+                           void *d_out, void *d_work, void *hip_stream);
+int rtw_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const float *image, const float *features, float *out);
+int rtw_denoise_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const double *image, const double *features, double *out);
+int rtw_render_denoised_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, float *out);
+int rtw_render_denoised_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, double *out);
+
 /* Counters/timings of the last render issued from this thread (waits for it to finish). */
 int rtw_stats(rtw_stats_t *out);
 

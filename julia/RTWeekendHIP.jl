@@ -508,4 +508,58 @@ function render_features(scene::HittableList, cam::Camera{T}, image_width=400, n
     out
 end
 
+# rtw_denoise_t (include/rtw_hip.h): 40 bytes
+struct CDenoise
+    levels::Int32; normal_power_log2::Int32; flags::Int32; gamma::Int32; device::Int32; reserved::Int32
+    sigma_color::Float64; sigma_depth::Float64
+end
+
+"""
+    render_denoised(scene, cam, image_width=400, n_samples=1; depth=16, seed=1, n_chunks=0, device=-1, numerics=:reference, group_cull=false, scan_valu=false,
+                    levels=3, normal_power_log2=1, sigma_color=0.5, sigma_depth=0.1, demodulate=true)
+
+`render` at a low sample count through the feature-guided denoiser (rtw_render_denoised_f32/_f64): the linear image, the first-hit feature
+pass over all of its chunks and an edge-avoiding à-trous filter (`levels` passes with steps 1, 2, 4, ...; colour, normal, relative-depth
+and coverage weights; the definition is in include/rtw_hip.h) run on the device, gamma is applied at the end and the `Matrix{RGB{T}}`
+comes back once.  `demodulate=true` filters image / albedo and multiplies the albedo back (RTW_DENOISE_DEMODULATE).
+(Not executed in this repository: there is no `julia` in its build image; tests/test_gpu_denoise.py drives the same entry point.)
+"""
+function render_denoised(scene::HittableList, cam::Camera{T}, image_width=400, n_samples=1;
+                         depth=16, seed=1, n_chunks=0, device=-1, numerics=:reference, group_cull=false, scan_valu=false,
+                         levels=3, normal_power_log2=1, sigma_color=0.5, sigma_depth=0.1, demodulate=true) where T <: Union{Float32,Float64}
+    numerics in (:reference, :contract, :reference_fma2) || throw(ArgumentError("numerics must be :reference, :contract or :reference_fma2"))
+    nflags = numerics === :contract ? 32 : numerics === :reference_fma2 ? 128 : 0
+    image_height = image_width ÷ (16//9)
+    n = length(scene)
+    cx = Vector{T}(undef, n); cy = similar(cx); cz = similar(cx); r = similar(cx)
+    ar = similar(cx); ag = similar(cx); ab = similar(cx); param = similar(cx)
+    kind = Vector{Int32}(undef, n)
+    for (i, h) in enumerate(scene)
+        h isa Sphere{T} || throw(ArgumentError("scene[$i] is $(typeof(h)); the HIP path takes Sphere{$T} only"))
+        cx[i], cy[i], cz[i] = h.center
+        r[i] = h.radius
+        kind[i] = matkind(h.mat)
+        ar[i], ag[i], ab[i] = albedo(h.mat)
+        param[i] = matparam(h.mat)
+    end
+    img = Matrix{RGB{T}}(undef, image_height, image_width)
+    ccam = Ref(CCamera(cam))
+    den = Ref(CDenoise(levels, normal_power_log2, demodulate ? 1 : 0, 1, -1, 0, sigma_color, sigma_depth))
+    rc = GC.@preserve cx cy cz r kind ar ag ab param img begin
+        params = Ref(CParams(image_width, image_height, n_samples, depth, seed, n_chunks, 0, 1, device, 1,
+                             (group_cull ? 1 : 0) | (scan_valu ? 4 : 0) | nflags, 0, 0, Ptr{Int32}(C_NULL)))
+        cscene = Ref(CScene{T}(n, pointer(cx), pointer(cy), pointer(cz), pointer(r), pointer(kind),
+                               pointer(ar), pointer(ag), pointer(ab), pointer(param)))
+        if T === Float32
+            ccall((:rtw_render_denoised_f32, LIB), Cint, (Ref{CScene{Float32}}, Ref{CCamera{Float32}}, Ref{CParams}, Ref{CDenoise}, Ptr{Float32}),
+                  cscene, ccam, params, den, pointer(reinterpret(Float32, vec(img))))
+        else
+            ccall((:rtw_render_denoised_f64, LIB), Cint, (Ref{CScene{Float64}}, Ref{CCamera{Float64}}, Ref{CParams}, Ref{CDenoise}, Ptr{Float64}),
+                  cscene, ccam, params, den, pointer(reinterpret(Float64, vec(img))))
+        end
+    end
+    rc == 0 || error("librtw_hip: error $rc: $(last_error())")
+    img
+end
+
 end # module

@@ -24,6 +24,7 @@ from .progressive import ProgressiveBatchRenderer, ProgressiveRenderer, render_p
 from .adaptive import AdaptiveBatchRenderer, AdaptiveRenderer, reference_decisions, render_adaptive, render_adaptive_batch  # noqa: F401
 from .shard import compact_elems, compact_to_frame_index, local_tile_count, owned_pixel_mask, render_sharded  # noqa: F401
 from .features import features_into, render_features  # noqa: F401
+from .denoise import denoise, denoise_into, denoise_work_bytes, render_denoised  # noqa: F401
 from . import imageio  # noqa: F401
 
 __all__ = [
@@ -35,5 +36,5 @@ __all__ = [
     "DeviceRenderer", "render", "render_batch", "last_stats", "ProgressiveRenderer", "render_progressive", "samples_in_chunks",
     "AdaptiveRenderer", "render_adaptive", "reference_decisions", "owned_pixel_mask", "render_sharded", "compact_elems",
     "compact_to_frame_index", "local_tile_count", "ProgressiveBatchRenderer", "AdaptiveBatchRenderer", "render_adaptive_batch",
-    "render_features", "features_into",
+    "render_features", "features_into", "denoise", "denoise_into", "denoise_work_bytes", "render_denoised",
 ]

@@ -19,6 +19,8 @@ SYMBOLS = [
     "rtw_render_adaptive_f32", "rtw_render_adaptive_f64", "rtw_accum_adaptive_info", "rtw_accum_tile_chunks",
     "rtw_render_accum_batch_f32", "rtw_render_accum_batch_f64", "rtw_render_adaptive_batch_f32", "rtw_render_adaptive_batch_f64",
     "rtw_render_features_device_f32", "rtw_render_features_device_f64", "rtw_render_features_f32", "rtw_render_features_f64",
+    "rtw_denoise_work_bytes", "rtw_denoise_device_f32", "rtw_denoise_device_f64", "rtw_denoise_f32", "rtw_denoise_f64",
+    "rtw_render_denoised_f32", "rtw_render_denoised_f64",
 ]
 
 
@@ -70,6 +72,12 @@ class AdaptiveInfo(C.Structure):
                [("samples", C.c_uint64), ("tolerance", C.c_double)]
 
 
+class Denoise(C.Structure):
+    """rtw_denoise_t"""
+    _fields_ = [(k, C.c_int32) for k in ("levels", "normal_power_log2", "flags", "gamma", "device", "reserved")] + \
+               [("sigma_color", C.c_double), ("sigma_depth", C.c_double)]
+
+
 _lib = None
 
 
@@ -119,6 +127,11 @@ def lib():
     for sfx, SceneT, CamT in (("f32", SceneF32, CameraF32), ("f64", SceneF64, CameraF64)):
         getattr(L, "rtw_render_features_device_" + sfx).argtypes = [C.c_void_p, C.POINTER(CamT), C.POINTER(Params), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         getattr(L, "rtw_render_features_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), C.POINTER(Params), C.c_int32, C.c_int32, C.c_void_p]
+        getattr(L, "rtw_denoise_device_" + sfx).argtypes = [C.POINTER(Denoise), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        getattr(L, "rtw_denoise_" + sfx).argtypes = [C.POINTER(Denoise), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        getattr(L, "rtw_render_denoised_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), C.POINTER(Params), C.POINTER(Denoise), C.c_void_p]
+    L.rtw_denoise_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.rtw_denoise_work_bytes.restype = C.c_int64
     L.rtw_accum_adaptive_info.argtypes = [C.c_void_p, C.POINTER(AdaptiveInfo)]
     L.rtw_accum_tile_chunks.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.rtw_accum_create.argtypes = [C.c_int, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
@@ -205,6 +218,7 @@ FLAG_RAY_POOL = 8        # include/rtw_hip.h RTW_FLAG_RAY_POOL
 FLAG_RCCL_REDUCE = 16    # include/rtw_hip.h RTW_FLAG_RCCL_REDUCE
 FLAG_NUMERICS_CONTRACT = 32        # include/rtw_hip.h RTW_FLAG_NUMERICS_CONTRACT
 FLAG_NUMERICS_REFERENCE_FMA2 = 128  # include/rtw_hip.h RTW_FLAG_NUMERICS_REFERENCE_FMA2
+DENOISE_DEMODULATE = 1   # include/rtw_hip.h RTW_DENOISE_DEMODULATE
 GATHER_PEER, GATHER_HOST_STAGED, GATHER_RCCL, GATHER_SAME_DEVICE = 1, 2, 4, 8    # rtw_stats_t.gather_path bits
 ABI_VERSION = 4
 

@@ -1,0 +1,136 @@
+// rtw_denoise.hip -- the feature-guided denoiser (include/rtw_hip.h rtw_denoise_*): the checks that need no device, the launch sequence of
+// its kernels (rtw_denoise.hpp: prepare, then the level kernel once per a-trous pass, the last one writing the image) and the device-resident
+// entry points.  (The host-buffer entry points and rtw_render_denoised_* live with the other cached-context paths in rtw_render_host.hip.)
+#include "rtw_host.hpp"
+#include "rtw_denoise.hpp"
+
+namespace rtwh {
+
+// Everything about a denoiser call that is decided without a device.
+int validate_denoise(const rtw_denoise_t *d, int32_t width, int32_t height) {
+    if (!d) return fail(-1, "null denoiser parameters");
+    if (d->levels < 1 || d->levels > 8) return fail(-2, "levels must be in 1..8 (got %d)", d->levels);
+    if (d->normal_power_log2 < 0 || d->normal_power_log2 > 7) return fail(-2, "normal_power_log2 must be in 0..7 (got %d)", d->normal_power_log2);
+    if (d->flags & ~(RTW_DENOISE_DEMODULATE)) return fail(-2, "unknown denoiser flags 0x%x", d->flags);
+    if (d->gamma != 0 && d->gamma != 1) return fail(-2, "gamma must be 0 or 1 (got %d)", d->gamma);
+    if (d->reserved != 0) return fail(-2, "reserved must be 0");
+    if (d->device < -1) return fail(-2, "bad device %d", d->device);
+    if (!(d->sigma_color > 0) || !std::isfinite(d->sigma_color)) return fail(-2, "sigma_color must be finite and positive");
+    if (!(d->sigma_depth > 0) || !std::isfinite(d->sigma_depth)) return fail(-2, "sigma_depth must be finite and positive");
+    if (width < 1 || height < 1) return fail(-2, "width/height must be positive (got %d x %d)", width, height);
+    const long long n_tiles = (long long)((height + 7) / 8) * ((width + 7) / 8);         // the feature pass's own limit (validate_features)
+    if (n_tiles >= (1ll << 31)) return fail(-5, "frame too large for one call: %lld tiles", n_tiles);
+    return 0;
+}
+
+// the workspace: the planes E, E', G and A of rtw_denoise.hpp, 4 elements per pixel each
+static long long plane_bytes(int32_t width, int32_t height, int elem_bytes) { return (long long)width * height * 4 * elem_bytes; }
+
+static bool overlap(const void *a, long long na, const void *b, long long nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
+}
+
+// Enqueue the denoiser on `stream` of the current device (validate_denoise has accepted the call).
+template <typename T>
+int launch_denoise(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream) {
+    using V = typename rtw::DnVec<T>::type;
+    const long long n_pix = (long long)width * height;
+    char *w = (char *)d_work;
+    const long long pb = plane_bytes(width, height, sizeof(T));
+    V *E[2] = {(V *)w, (V *)(w + pb)};
+    V *G = (V *)(w + 2 * pb), *A = (V *)(w + 3 * pb);
+    const bool demod = (d->flags & RTW_DENOISE_DEMODULATE) != 0;
+    const unsigned grid = (unsigned)((n_pix + 255) / 256);
+    // (measurement aid, tools/gpu_denoise.py: events around every kernel, reported on stderr -- this one blocks)
+    static const bool profile = aid_flag("RTW_DENOISE_PROFILE");
+    struct Events { hipEvent_t e[10] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
+    hipEvent_t *ev = events.e;
+    if (profile) for (int k = 0; k <= d->levels + 1; ++k) HIP_TRY(hipEventCreate(&ev[k]));
+    if (profile) HIP_TRY(hipEventRecord(ev[0], stream));
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(rtw::dn_prepare<T>, dim3(grid), dim3(256), 0, stream, (const T *)d_image, (const V *)d_features, E[0], G, A, n_pix, demod ? 1 : 0);
+    HIP_TRY(hipGetLastError());
+    if (profile) HIP_TRY(hipEventRecord(ev[1], stream));
+    for (int k = 0; k < d->levels; ++k) {
+        rtw::DnLevel<T> L;
+        const double sc = d->sigma_color * std::ldexp(1.0, -k);
+        L.inv_sc = (T)(1.0 / (sc * sc));
+        L.inv_sz = (T)(1.0 / (d->sigma_depth * d->sigma_depth));
+        L.step = 1 << k; L.m = d->normal_power_log2;
+        L.mode = k == d->levels - 1 ? (RTW_DN_FINAL | (demod ? RTW_DN_DEMOD : 0) | (d->gamma ? RTW_DN_GAMMA : 0)) : 0;
+        L.W = width; L.H = height;
+        const V *in = E[k & 1];
+        V *next = E[(k & 1) ^ 1];
+        hipLaunchKernelGGL(rtw::dn_level<T>, dim3(grid), dim3(256), 0, stream, L, in, (const V *)G, (const V *)A, next, (T *)d_out);
+        HIP_TRY(hipGetLastError());
+        if (profile) HIP_TRY(hipEventRecord(ev[k + 2], stream));
+    }
+    if (profile) {
+        HIP_TRY(hipEventSynchronize(ev[d->levels + 1]));
+        for (int k = 0; k <= d->levels; ++k) {
+            float ms = 0;
+            HIP_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+            if (k == 0) fprintf(stderr, "[rtw denoise] %s %dx%d prepare ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, ms);
+            else fprintf(stderr, "[rtw denoise] %s %dx%d level step=%d final=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, 1 << (k - 1),
+                         (int)(k == d->levels), ms);
+        }
+        float all_ms = 0;
+        HIP_TRY(hipEventElapsedTime(&all_ms, ev[0], ev[d->levels + 1]));
+        fprintf(stderr, "[rtw denoise] %s %dx%d total levels=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, d->levels, all_ms);
+    }
+    return 0;
+}
+
+int launch_denoise_f32(const rtw_denoise_t *d, int32_t w, int32_t h, const void *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_denoise<float>(d, w, h, img, feat, out, work, st); }
+int launch_denoise_f64(const rtw_denoise_t *d, int32_t w, int32_t h, const void *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_denoise<double>(d, w, h, img, feat, out, work, st); }
+
+template <typename T>
+int denoise_device(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, void *stream_v) {
+    if (!d || !d_image || !d_features || !d_out || !d_work) return fail(-1, "null argument");
+    if (int rc = validate_denoise(d, width, height)) return rc;
+    if (((uintptr_t)d_work & 15u) || ((uintptr_t)d_features & 15u)) return fail(-2, "the workspace and the feature buffer must be 16-byte aligned");
+    if (((uintptr_t)d_image & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
+    const long long n_pix = (long long)width * height, img_b = n_pix * 3 * (long long)sizeof(T), feat_b = n_pix * 8 * (long long)sizeof(T);
+    const long long work_b = 4 * plane_bytes(width, height, sizeof(T));
+    if (overlap(d_out, img_b, d_image, img_b) || overlap(d_out, img_b, d_features, feat_b) || overlap(d_out, img_b, d_work, work_b))
+        return fail(-2, "d_out may not alias an input or the workspace");
+    if (overlap(d_work, work_b, d_image, img_b) || overlap(d_work, work_b, d_features, feat_b)) return fail(-2, "the workspace may not alias an input");
+    DeviceGuard guard;
+    if (d->device >= 0) HIP_TRY(hipSetDevice(d->device));
+    return launch_denoise<T>(d, width, height, d_image, d_features, d_out, d_work, (hipStream_t)stream_v);
+}
+
+}  // namespace rtwh
+
+using namespace rtwh;
+
+extern "C" {
+
+int64_t rtw_denoise_work_bytes(int32_t width, int32_t height, int32_t elem_bytes) {
+    if (elem_bytes != 4 && elem_bytes != 8) return fail(-2, "elem_bytes must be 4 or 8 (got %d)", elem_bytes);
+    if (width < 1 || height < 1) return fail(-2, "width/height must be positive (got %d x %d)", width, height);
+    const long long n_tiles = (long long)((height + 7) / 8) * ((width + 7) / 8);
+    if (n_tiles >= (1ll << 31)) return fail(-5, "frame too large for one call: %lld tiles", n_tiles);
+    return 4 * plane_bytes(width, height, elem_bytes);
+}
+int rtw_denoise_device_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, void *hip_stream) {
+    return denoise_device<float>(d, width, height, d_image, d_features, d_out, d_work, hip_stream);
+}
+int rtw_denoise_device_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, void *hip_stream) {
+    return denoise_device<double>(d, width, height, d_image, d_features, d_out, d_work, hip_stream);
+}
+int rtw_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const float *image, const float *features, float *out) {
+    return denoise_host_f32(d, width, height, image, features, out);
+}
+int rtw_denoise_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const double *image, const double *features, double *out) {
+    return denoise_host_f64(d, width, height, image, features, out);
+}
+int rtw_render_denoised_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, float *out) {
+    return render_host_denoised_f32(scene, cam, p, d, out);
+}
+int rtw_render_denoised_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, double *out) {
+    return render_host_denoised_f64(scene, cam, p, d, out);
+}
+
+}  // extern "C"

@@ -1,0 +1,143 @@
+// rtw_denoise.hpp -- the kernels of the feature-guided denoiser (include/rtw_hip.h rtw_denoise_*: an edge-avoiding a-trous filter, the
+// definition is there): prepare, and the level kernel.
+//   prepare        one pixel per lane: validity, the guides n = f[3..5] / cov, z = f[6] / cov, the (de)modulated colour e = c / a.  Three planes of
+//                  4-element slots (16 bytes in Float32, 32 in Float64), pixel p at slot p:  E = (e0, e1, e2, z)   G = (n.x, n.y, n.z, cov)
+//                  A = (a0, a1, a2, 0).  A pixel that is not valid has cov = NaN in G (a valid pixel's cov is finite): never a neighbour.
+//   level          one pixel per lane, lanes along i, the 24 neighbours read from global memory (L1 / L2)
+// The colour plane ping-pongs between two E planes; the last level multiplies the albedo back, applies gamma and the NaN rule and writes the
+// image.  No atomics, no cross-lane operation; the trip count over the taps is uniform, skipped taps are predicated by selects.
+// Every operation is rounded once (the Makefile's -ffp-contract=off -fno-fast-math); divisions and sqrt are the compiler's IEEE ones.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace rtw {
+
+template <typename T> struct DnVec;
+template <> struct DnVec<float> { using type = float4; };
+// (not double4: its natural alignment is 32 bytes, and the contract of the buffers and of the workspace is 16)
+struct alignas(16) DnDouble4 { double x, y, z, w; };
+template <> struct DnVec<double> { using type = DnDouble4; };
+
+#define RTW_DN_FINAL 1      // DnLevel::mode: the last level (writes the image)
+#define RTW_DN_DEMOD 2      //   ... multiplies the albedo back
+#define RTW_DN_GAMMA 4      //   ... sqrt per channel
+
+template <typename T> struct DnLevel {
+    T inv_sc, inv_sz;       // 1 / (sigma_color 2^-k)^2 and 1 / sigma_depth^2, computed in binary64 and rounded to T by the host
+    int step, m, mode;      // 2^k; normal_power_log2; RTW_DN_*
+    int W, H;
+};
+
+__device__ __forceinline__ float dn_abs(float x) { return __builtin_fabsf(x); }
+__device__ __forceinline__ double dn_abs(double x) { return __builtin_fabs(x); }
+__device__ __forceinline__ float dn_sqrt(float x) { return __builtin_sqrtf(x); }
+__device__ __forceinline__ double dn_sqrt(double x) { return __builtin_sqrt(x); }
+template <typename T> __device__ __forceinline__ T dn_nan() { return (T)__builtin_nanf(""); }
+template <typename T> __device__ __forceinline__ bool dn_finite(T x) { return dn_abs(x) < (T)__builtin_inff(); }   // (false for NaN)
+
+template <typename T> struct DnSum { T w, e0, e1, e2; };
+
+// one tap that is not the centre; `ok`: inside the frame and valid.  The data of a tap that is not ok may be anything: selects, not weights, drop it.
+template <typename T, typename V>
+__device__ __forceinline__ void dn_tap(DnSum<T> &a, const V &ep, const V &gp, const V &eq, const V &gq, T h, bool ok, const DnLevel<T> &L) {
+    const T d0 = ep.x - eq.x, d1 = ep.y - eq.y, d2 = ep.z - eq.z;
+    const T dc = (d0 * d0 + d1 * d1) + d2 * d2;
+    const T wc = T(1) / (T(1) + dc * L.inv_sc);
+    const T tv = T(1) - dn_abs(gp.w - gq.w);
+    const T wv = tv > T(0) ? tv : T(0);
+    T w = (h * wc) * wv;
+    const T dot = (gp.x * gq.x + gp.y * gq.y) + gp.z * gq.z;
+    T t = dot > T(0) ? dot : T(0);
+    for (int r = 0; r < L.m; ++r) t = t * t;
+    const T zs = ep.w + eq.w;
+    const T rz = (ep.w - eq.w) / (zs > T(0) ? zs : T(1));
+    const T wz = T(1) / (T(1) + (rz * rz) * L.inv_sz);
+    const T wg = (w * t) * wz;
+    w = (gp.w > T(0) && gq.w > T(0)) ? wg : w;         // has(p) && has(q)  (cov = NaN: not valid, so not has)
+    a.w = a.w + (ok ? w : T(0));
+    a.e0 = a.e0 + (ok ? w * eq.x : T(0));
+    a.e1 = a.e1 + (ok ? w * eq.y : T(0));
+    a.e2 = a.e2 + (ok ? w * eq.z : T(0));
+}
+template <typename T, typename V>
+__device__ __forceinline__ void dn_centre(DnSum<T> &a, const V &ep) {
+    const T h = T(9) / T(64);
+    a.w = a.w + h;
+    a.e0 = a.e0 + h * ep.x; a.e1 = a.e1 + h * ep.y; a.e2 = a.e2 + h * ep.z;
+}
+__device__ constexpr double dn_k(int d) { return d == 0 ? 0.375 : (d == 1 || d == -1) ? 0.25 : 0.0625; }
+
+// after the 25 taps: the quotients, and either the next level's colour slot or the image's pixel
+template <typename T, typename V>
+__device__ __forceinline__ void dn_store(const DnSum<T> &a, const V &ep, const V &gp, long long p, const DnLevel<T> &L, const V *__restrict__ A, V *__restrict__ Eout, T *__restrict__ out) {
+    T e0 = a.e0 / a.w, e1 = a.e1 / a.w, e2 = a.e2 / a.w;
+    if (!(L.mode & RTW_DN_FINAL)) {
+        V o; o.x = e0; o.y = e1; o.z = e2; o.w = ep.w;
+        Eout[p] = o;
+        return;
+    }
+    if (L.mode & RTW_DN_DEMOD) { const V al = A[p]; e0 = e0 * al.x; e1 = e1 * al.y; e2 = e2 * al.z; }
+    if (L.mode & RTW_DN_GAMMA) { e0 = dn_sqrt(e0); e1 = dn_sqrt(e1); e2 = dn_sqrt(e2); }
+    const bool valid = gp.w == gp.w;
+    out[p * 3 + 0] = valid ? e0 : dn_nan<T>();
+    out[p * 3 + 1] = valid ? e1 : dn_nan<T>();
+    out[p * 3 + 2] = valid ? e2 : dn_nan<T>();
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void dn_prepare(const T *__restrict__ image, const typename DnVec<T>::type *__restrict__ feat, typename DnVec<T>::type *__restrict__ E,
+                                                  typename DnVec<T>::type *__restrict__ G, typename DnVec<T>::type *__restrict__ A, long long n_pix, int demod) {
+    using V = typename DnVec<T>::type;
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= n_pix) return;
+    const T c0 = image[p * 3 + 0], c1 = image[p * 3 + 1], c2 = image[p * 3 + 2];
+    const V f0 = feat[p * 2 + 0], f1 = feat[p * 2 + 1];        // albedo, n.x | n.y, n.z, depth, coverage
+    const bool valid = dn_finite(c0) && dn_finite(c1) && dn_finite(c2) && dn_finite(f0.x) && dn_finite(f0.y) && dn_finite(f0.z) && dn_finite(f0.w) &&
+                       dn_finite(f1.x) && dn_finite(f1.y) && dn_finite(f1.z) && dn_finite(f1.w);
+    const T cov = f1.w;
+    const bool has = valid && cov > T(0);
+    const T dv = has ? cov : T(1);
+    const T nx = f0.w / dv, ny = f1.x / dv, nz = f1.y / dv, z = f1.z / dv;
+    V e, g, a;
+    a.x = a.y = a.z = T(1); a.w = T(0);
+    if (demod) {
+        const T floor_ = T(0.015625);               // 2^-6
+        a.x = f0.x > floor_ ? f0.x : floor_; a.y = f0.y > floor_ ? f0.y : floor_; a.z = f0.z > floor_ ? f0.z : floor_;
+        e.x = c0 / a.x; e.y = c1 / a.y; e.z = c2 / a.z;
+    } else {
+        e.x = c0; e.y = c1; e.z = c2;
+    }
+    e.w = has ? z : T(0);
+    g.x = has ? nx : T(0); g.y = has ? ny : T(0); g.z = has ? nz : T(0);
+    g.w = valid ? cov : dn_nan<T>();
+    if (!valid) { e.x = e.y = e.z = T(0); a.x = a.y = a.z = T(1); }
+    E[p] = e; G[p] = g; A[p] = a;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void dn_level(DnLevel<T> L, const typename DnVec<T>::type *__restrict__ Ein, const typename DnVec<T>::type *__restrict__ G,
+                                                       const typename DnVec<T>::type *__restrict__ A, typename DnVec<T>::type *__restrict__ Eout, T *__restrict__ out) {
+    using V = typename DnVec<T>::type;
+    const long long H = L.H, W = L.W, s = L.step;
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= W * H) return;
+    // (a 32-bit division whenever the frame allows it)
+    const long long j = W * H < (1ll << 31) ? (long long)((unsigned)p / (unsigned)H) : p / H, i = p - j * H;
+    const V ep = Ein[p], gp = G[p];
+    DnSum<T> a = {T(0), T(0), T(0), T(0)};
+#pragma unroll
+    for (int dj = -2; dj <= 2; ++dj) {
+#pragma unroll
+        for (int di = -2; di <= 2; ++di) {
+            if (di == 0 && dj == 0) { dn_centre<T>(a, ep); continue; }
+            const long long qi = i + s * di, qj = j + s * dj;
+            const bool in = qi >= 0 && qi < H && qj >= 0 && qj < W;
+            const long long q = in ? qj * H + qi : p;
+            const V eq = Ein[q], gq = G[q];
+            dn_tap<T>(a, ep, gp, eq, gq, (T)(dn_k(di) * dn_k(dj)), in && gq.w == gq.w, L);
+        }
+    }
+    dn_store<T>(a, ep, gp, p, L, A, Eout, out);
+}
+
+}  // namespace rtw

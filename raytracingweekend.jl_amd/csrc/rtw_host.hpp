@@ -9,6 +9,7 @@
 //   rtw_accum.hip        progressive render: the accumulator object, its passes, merge / resolve kernels, export / import
 //   rtw_unit.hip         the T0 unit entry points (rtw_units.hpp)
 //   rtw_features.hip     first-hit feature buffers: one launch of the feature kernel (rtw_features.hpp), the device-resident entry points
+//   rtw_denoise.hip      the feature-guided denoiser: its checks, the launch sequence of its kernels (rtw_denoise.hpp), the device-resident entry points
 //   (rtw_scene_view.hpp: what both launch functions derive from their arguments; rtw_instances.hpp: the one table of the trace kernel's instances)
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
 #pragma once
@@ -271,6 +272,17 @@ int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const
 int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
 inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_features_f32(s, c, p, b, n, d, st, r, x); }
 inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_features_f64(s, c, p, b, n, d, st, r, x); }
+
+// rtw_denoise.hip -- the feature-guided denoiser (include/rtw_hip.h rtw_denoise_*).  validate_denoise: the checks that need no device;
+// launch_denoise: enqueue its kernels on `stream` of the current device (d_work: rtw_denoise_work_bytes bytes, 16-byte aligned).
+int validate_denoise(const rtw_denoise_t *d, int32_t width, int32_t height);
+int launch_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream);
+int launch_denoise_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream);
+// rtw_render_host.hip: its host-buffer entry points
+int denoise_host_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const float *image, const float *features, float *out);
+int denoise_host_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const double *image, const double *features, double *out);
+int render_host_denoised_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, float *out);
+int render_host_denoised_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, double *out);
 
 // rtw_unit.hip
 int run_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene, const rtw_camera_f32 *cam);

@@ -53,7 +53,11 @@ int acquire_host(int device, const std::vector<unsigned char> &key, HostLease *o
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
         HostCtx *pick = nullptr;
-        for (auto &h : ctx->host) if (!h->busy && h->scene_key == key) { pick = h.get(); break; }     // same scene: nothing to upload
+        if (key.empty()) {                                                                             // no scene wanted (the denoiser): the idle entry used last, whatever it holds
+            for (auto &h : ctx->host) if (!h->busy && (!pick || h->last_use > pick->last_use)) pick = h.get();
+        } else {
+            for (auto &h : ctx->host) if (!h->busy && h->scene_key == key) { pick = h.get(); break; }     // same scene: nothing to upload
+        }
         size_t idle = 0;
         for (auto &h : ctx->host) if (!h->busy) ++idle;
         if (!pick && ctx->host.size() < RTW_HOST_CTX_POOL && idle < RTW_HOST_CTX_IDLE_KEEP) {
@@ -330,6 +334,91 @@ int render_host_features(const SceneT *scene, const CamT *cam, const rtw_params 
         return launch_features_t(hc->scene, cam, &q, chunk_begin, chunk_count, hc->d_img, hc->stream, rec, rctx);
     });
 }
+
+inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, const float *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_denoise_f32(d, w, h, img, feat, out, work, st); }
+inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, const double *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_denoise_f64(d, w, h, img, feat, out, work, st); }
+
+// The denoiser's regions inside a context's device buffer: image, features, output, workspace -- each starts on a 16-byte boundary.
+template <typename T> struct DenoiseRegions {
+    size_t img_b, feat_b, off_feat, off_out, off_work, total;
+    DenoiseRegions(int32_t width, int32_t height) {
+        const size_t n = (size_t)width * (size_t)height;
+        auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
+        img_b = n * 3 * sizeof(T); feat_b = n * RTW_FEATURE_CHANNELS * sizeof(T);
+        off_feat = up(img_b); off_out = off_feat + up(feat_b); off_work = off_out + up(img_b);
+        total = off_work + (size_t)rtw_denoise_work_bytes(width, height, (int32_t)sizeof(T));
+    }
+};
+
+// The denoiser on host buffers (rtw_denoise_f32/_f64): a leased context of the device (its stream and buffer; the scene it may hold is left
+// alone), two H2D, the kernels, ONE D2H.  This thread's last render (rtw_stats) is not touched.
+template <typename T>
+int denoise_host(const rtw_denoise_t *d, int32_t width, int32_t height, const T *image, const T *features, T *out) {
+    if (!d || !image || !features || !out) return fail(-1, "null argument");
+    if (int rc = validate_denoise(d, width, height)) return rc;
+    const DenoiseRegions<T> R(width, height);
+    auto hits = [](const void *a, size_t na, const void *b, size_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; };
+    if (hits(out, R.img_b, image, R.img_b) || hits(out, R.img_b, features, R.feat_b)) return fail(-2, "out may not alias an input");
+    DeviceGuard guard;
+    HostLease L;
+    if (int rc = acquire_host(d->device, std::vector<unsigned char>(), &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total)) return rc;
+    char *base = (char *)hc->d_img;
+    int rc = 0;
+    hipError_t e = hipMemcpyAsync(base, image, R.img_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_feat, features, R.feat_b, hipMemcpyHostToDevice, hc->stream);
+    if (e != hipSuccess) rc = fail((int)e, "upload of the denoiser's inputs failed: %s", hipGetErrorString(e));
+    if (!rc) rc = launch_denoise_t(d, width, height, (const T *)base, base + R.off_feat, base + R.off_out, base + R.off_work, hc->stream);
+    if (!rc) rc = copy_out(hc, base + R.off_out, out, R.img_b);
+    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    return rc;
+}
+
+// Render, feature pass over all N effective chunks and denoiser in one call (rtw_render_denoised_f32/_f64): the one-device path with a device
+// buffer that holds the linear image, the features, the result and the denoiser's workspace; everything on the context's stream, ONE D2H.
+// rtw_stats() reports the render's record.
+template <typename T, typename SceneT, typename CamT>
+int render_host_denoised(const SceneT *scene, const CamT *cam, const rtw_params *p, const rtw_denoise_t *d, T *out) {
+    if (!scene || !cam || !p || !d || !out) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = validate_features(p, 0, 1, &nch, &cs)) return rc;
+    if (int rc = validate_denoise(d, p->width, p->height)) return rc;
+    if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
+    DeviceGuard guard;
+    release_last();
+    std::vector<unsigned char> key;
+    scene_key_of(scene, sizeof(T) == 8, key);
+    HostLease L;
+    if (int rc = acquire_host(p->device, key, &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_scene<T>(hc, scene, key)) return rc;
+    const DenoiseRegions<T> R(p->width, p->height);
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total)) return rc;
+    char *base = (char *)hc->d_img;
+    rtw_params q = *p;
+    q.device = hc->device; q.n_devices = 0; q.device_ids = nullptr; q.gamma = 0;
+    rtw_denoise_t dd = *d;
+    dd.gamma = p->gamma != 0; dd.device = hc->device;
+    RenderRec *rec = nullptr, *frec = nullptr;
+    CtxPtr rctx, fctx;
+    int rc = launch_render_t(hc->scene, cam, 0, nullptr, &q, base, hc->stream, &rec, &rctx);
+    if (!rc) rc = launch_features_t(hc->scene, cam, &q, 0, nch, base + R.off_feat, hc->stream, &frec, &fctx);
+    if (!rc) rc = launch_denoise_t(&dd, p->width, p->height, (const T *)base, base + R.off_feat, base + R.off_out, base + R.off_work, hc->stream);
+    if (!rc) rc = copy_out(hc, base + R.off_out, out, R.img_b);
+    if (rc) (void)hipStreamSynchronize(hc->stream);
+    if (!rc) rc = resolve_rec(rec, &g_last.agg);
+    if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
+    if (rec) release_rec(rctx, rec, rc == 0);
+    if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
+    g_last.resolved = rc == 0;
+    return rc;
+}
+
+int denoise_host_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const float *image, const float *features, float *out) { return denoise_host<float>(d, width, height, image, features, out); }
+int denoise_host_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const double *image, const double *features, double *out) { return denoise_host<double>(d, width, height, image, features, out); }
+int render_host_denoised_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, float *out) { return render_host_denoised<float>(scene, cam, p, d, out); }
+int render_host_denoised_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, double *out) { return render_host_denoised<double>(scene, cam, p, d, out); }
 
 int render_host_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, float *out) { return render_host<float>(scene, cam, p, out); }
 int render_host_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, double *out) { return render_host<double>(scene, cam, p, out); }

@@ -1,0 +1,99 @@
+"""Feature-guided denoiser (include/rtw_hip.h ``rtw_denoise_*``): an edge-avoiding a-trous filter of a low-sample-count image -- a
+progressive prefix, an adaptive render that stopped early, a 1-4 spp preview -- guided by the first-hit feature buffers of
+``render_features``.  The definition is in the header; tests/denoise_ref.py restates it on the CPU and the device agrees on the bits.
+All compute happens in librtw_hip.so; there is no CPU fallback.
+
+Defaults: ``levels=3, normal_power_log2=1, sigma_color=0.5, sigma_depth=0.1, demodulate=True, gamma=True``.  The image handed in is
+normally a LINEAR one (``render(..., gamma=False)``): the denoiser applies gamma itself at the end.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from .render import _tls as _render_tls
+from .structs import Camera, flatten_scene, image_height
+
+
+def make_denoise(levels=3, normal_power_log2=1, sigma_color=0.5, sigma_depth=0.1, demodulate=True, gamma=True, device=-1):
+    """-> the ``rtw_denoise_t`` of these keywords"""
+    flags = _capi.DENOISE_DEMODULATE if demodulate else 0
+    return _capi.Denoise(int(levels), int(normal_power_log2), flags, 1 if gamma else 0, int(device), 0, float(sigma_color), float(sigma_depth))
+
+
+def denoise_work_bytes(image_width, image_height, elem_type=np.float32):
+    """bytes of device workspace ``denoise_into`` needs for one frame (16-byte aligned, owned by the caller)"""
+    n = _capi.lib().rtw_denoise_work_bytes(int(image_width), int(image_height), np.dtype(elem_type).itemsize)
+    if n < 0:
+        _capi.check(int(n))
+    return int(n)
+
+
+def denoise(image, features, **params):
+    """``image`` [H, W, 3] and ``features`` [H, W, 8] -- or the dict ``render_features`` returns -- host arrays of one element type
+    (float32 / float64) -> the denoised image [H, W, 3].  Keywords: ``make_denoise``.  Blocking; ``last_stats()`` is left as it was."""
+    if isinstance(features, dict):
+        features = features["raw"]
+    image, features = np.asarray(image), np.asarray(features)
+    T = image.dtype
+    if T not in (np.dtype(np.float32), np.dtype(np.float64)) or features.dtype != T:
+        raise TypeError("image and features must both be float32 or both float64")
+    if image.ndim != 3 or image.shape[2] != 3 or features.shape != image.shape[:2] + (8,):
+        raise ValueError(f"expected image [H, W, 3] and features [H, W, 8], got {image.shape} and {features.shape}")
+    H, W = image.shape[:2]
+    if H < 1 or W < 1:
+        raise ValueError("empty image")
+    D = make_denoise(**params)
+    img = np.ascontiguousarray(image.transpose(1, 0, 2))           # the library's layout: pixel (i, j) at j*H + i
+    feat = np.ascontiguousarray(features.transpose(1, 0, 2))
+    out = np.empty(W * H * 3, dtype=T)
+    L = _capi.lib()
+    fn = L.rtw_denoise_f64 if _capi.is_f64(T) else L.rtw_denoise_f32
+    _capi.check(fn(C.byref(D), W, H, img.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out.reshape(W, H, 3).transpose(1, 0, 2)
+
+
+def denoise_into(d_out_ptr, d_image_ptr, d_features_ptr, d_work_ptr, image_width, image_height, *, elem_type=np.float32, stream=0,
+                 work_bytes=None, **params):
+    """The device-resident form (rtw_denoise_device_*): enqueue the denoiser on ``stream``.  All four are DEVICE pointers (a torch
+    tensor's ``data_ptr()``): the image and the result hold H*W*3 elements, the features H*W*8 (16-byte aligned), the workspace
+    ``denoise_work_bytes(...)`` bytes (16-byte aligned; ``work_bytes``: its size, checked when given).  The result may not alias an
+    input or the workspace; concurrent calls need a workspace each.  Keywords: ``make_denoise``."""
+    need = denoise_work_bytes(image_width, image_height, elem_type)
+    if work_bytes is not None and int(work_bytes) < need:
+        raise ValueError(f"workspace holds {work_bytes} bytes, the denoiser needs {need}")
+    D = make_denoise(**params)
+    L = _capi.lib()
+    fn = L.rtw_denoise_device_f64 if _capi.is_f64(elem_type) else L.rtw_denoise_device_f32
+    _capi.check(fn(C.byref(D), int(image_width), int(image_height), C.c_void_p(int(d_image_ptr)), C.c_void_p(int(d_features_ptr)),
+                   C.c_void_p(int(d_out_ptr)), C.c_void_p(int(d_work_ptr)), C.c_void_p(int(stream))))
+
+
+def render_denoised(scene, cam, image_width=400, n_samples=1, *, depth=16, seed=1, n_chunks=0, device=-1, gamma=True, group_cull=False,
+                    scan_valu=False, numerics=None, levels=3, normal_power_log2=1, sigma_color=0.5, sigma_depth=0.1, demodulate=True):
+    """``render`` + ``render_features`` + ``denoise`` in one call on the device (rtw_render_denoised_*): the linear image, the feature
+    pass over all of its chunks and the filter stay in HBM, the result comes back once.  Returns ``img[i, j, :]``; ``last_stats()``
+    reports the render."""
+    if not isinstance(cam, Camera):
+        raise TypeError("cam must be a Camera")
+    T = cam.elem_type
+    height = image_height(image_width)
+    if int(image_width) <= 0 or height <= 0:
+        raise ValueError(f"image_width={image_width} gives an empty {height} x {image_width} image")
+    if int(n_samples) <= 0:
+        raise ValueError("n_samples must be >= 1")
+    L = _capi.lib()
+    flat = scene if isinstance(scene, dict) else flatten_scene(scene, T)
+    S, keep = _capi.make_scene(flat, T)
+    Cm = _capi.make_camera(cam, T)
+    P = _capi.make_params(image_width, height, n_samples, depth, seed, n_chunks, 0, 1, device, 1 if gamma else 0,
+                          (_capi.FLAG_GROUP_CULL if group_cull else 0) | (_capi.FLAG_SCAN_VALU if scan_valu else 0), numerics=numerics)
+    D = make_denoise(levels, normal_power_log2, sigma_color, sigma_depth, demodulate, gamma)
+    out = np.empty(height * int(image_width) * 3, dtype=T)
+    fn = L.rtw_render_denoised_f64 if _capi.is_f64(T) else L.rtw_render_denoised_f32
+    _capi.check(fn(C.byref(S), C.byref(Cm), C.byref(P), C.byref(D), out.ctypes.data_as(C.c_void_p)))
+    del keep
+    st = _capi.Stats()
+    _capi.check(L.rtw_stats(C.byref(st)))
+    _render_tls.stats = {k: getattr(st, k) for k, _ in st._fields_}
+    return out.reshape(int(image_width), height, 3).transpose(1, 0, 2)
