@@ -427,8 +427,8 @@ int rtw_render_adaptive_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *
  * rtw_params -- sizes, unknown flags, both numerics bits, job_pixels -> -2; chunk_begin < 0, chunk_count < 1 or a range beyond N -> -2;
  * shard_count != 1, RTW_FLAG_COMPACT_TILES, RTW_FLAG_RCCL_REDUCE, RTW_FLAG_RAY_POOL, n_devices > 1 or device_ids -> -2; a d_out that is not
  * 16-byte aligned -> -2; a frame of 2^31 tiles or more -> -5.  Then: a scene handle of the other precision, or on another device than
- * p->device names -> -4.  Batched views, feature sums in accumulators, per-tile chunk prefixes of adaptive renders and device lists are
- * out of scope.  Additive to ABI 4: detected by symbol lookup. */
+ * p->device names -> -4.  Batched views, feature sums in accumulators and device lists are out of scope; the
+ * per-tile chunk prefixes of an adaptive accumulator: rtw_accum_features_* below.  Additive to ABI 4: detected by symbol lookup. */
 #define RTW_FEATURE_CHANNELS 8
 int rtw_render_features_device_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p,
                                    int32_t chunk_begin, int32_t chunk_count, void *d_out, void *hip_stream);
@@ -479,9 +479,9 @@ int rtw_render_features_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *ca
  *   Refusals, all decided before any HIP call: a null argument -> -1; levels outside 1..8, normal_power_log2 outside 0..7, unknown flag
  * bits, gamma other than 0 or 1, reserved != 0, device < -1, a sigma that is not finite and positive, width or height < 1, misaligned or
  * aliasing pointers, elem_bytes other than 4 or 8 -> -2; a frame of 2^31 8x8 tiles or more -> -5; the render-and-denoise call additionally
- * refuses everything a feature render of `p` refuses.  Variance-guided weights, temporal reuse across the views of a batch, compact or
- * sharded frames, device lists and progressive / adaptive accumulators are out of scope.  Additive to ABI 4:
- * detected by symbol lookup. */
+ * refuses everything a feature render of `p` refuses.  Temporal reuse across the views of a batch, compact or sharded frames and device
+ * lists are out of scope; noise-guided weights and accumulators as the input: the block behind these declarations.
+ * Additive to ABI 4: detected by symbol lookup. */
 #define RTW_DENOISE_DEMODULATE 1   /* filter image / albedo, multiply back at the end */
 typedef struct {
     int32_t levels;             /* 1..8 a-trous passes; pass k has step 2^k */
@@ -502,6 +502,72 @@ int rtw_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const
 int rtw_denoise_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const double *image, const double *features, double *out);
 int rtw_render_denoised_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, float *out);
 int rtw_render_denoised_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, double *out);
+
+/* Accumulators as the input of the filter above: the feature buffers of exactly the samples a progressive or adaptive accumulator holds,
+ * a per-pixel noise map from the half differences of an adaptive accumulator, a form of the filter whose colour weight is scaled by that
+ * map, and one call that strings them together.  Everything here only READS the accumulator's words and C_t; every call waits for the
+ * accumulator's event on its stream and records it afterwards, like a resolve, so a later pass cannot overwrite them under a running kernel.
+ *
+ * rtw_accum_features_*: asynchronous like the device form of the feature pass above; `d_out` is a DEVICE pointer, 16-byte aligned, to
+ * height*width*8 elements in the layout of the feature entry points.  `scene`, `cam` and `p` are the accumulator's render.
+ *   Adaptive accumulator: tile t = tj*tiles_i + ti (the numbering of the adaptive render) receives the feature sums of the chunks
+ * [0, C_t), every sum rounded once to binary64, divided by (double)C_t and rounded to T: the definition above with the tile's own range.
+ * The kernel reads C_t from the accumulator's device array; its counters add valid pixels x C_t per tile (rtw_stats: samples = segments =
+ * the sum over the tiles).  Consequence (tests/test_gpu_accum_denoise.py): the tiles with C_t == c equal, bit for bit, those tiles of
+ * the device form of the feature pass above over [0, c).
+ *   Uniform accumulator: it must hold exactly ONE chunk interval [b, b + C); the call is the feature pass above over it.
+ *   Refusals, all before any HIP call: a null scene / cam / p / accumulator / d_out -> -1; everything the device form of the feature pass
+ * refuses for `p` -> its code; a scene of the other precision, an accumulator of another size or device -> -4; an accumulator that holds
+ * nothing -> -2; a scene, camera or parameter set that is not the accumulator's binding (the comparison a pass makes: size, precision,
+ * seed, spp, chunk size, n_chunks, max_depth, numerics bits, the camera's bytes, the scene's hash) -> -4; RTW_FLAG_GROUP_CULL, RTW_FLAG_SCAN_VALU,
+ * job_pixels and gamma may differ from the binding's (they do not change the words); a uniform accumulator that holds several intervals
+ * -> -2; an adaptive accumulator whose last adaptive call did not finish -> -2.
+ *
+ * rtw_accum_noise_*: asynchronous; `d_out` is a DEVICE pointer to height*width elements of T, pixel (i, j) (0-based row, column) at
+ * j*height + i.  Adaptive accumulators only (a uniform accumulator's word 7 is 0 by contract: -2; the other precision than its render's:
+ * -4; a last adaptive call that did not finish: -2; nulls: -1; a misaligned d_out: -2).
+ *   The definition, in binary64, one rounding per operation, no FMA.  For a pixel p in tile t whose poison word is 0, with the
+ * accumulator's bound dark_floor, spp = S and chunk size s:
+ *       n = min(S, C_t*s);   D = (double)|H_p| * 2^-24  (the magnitude as an unsigned value: INT64_MIN is 2^63);
+ *       y = (double(R) + double(G)) + double(B)  as the stopping rule computes it;   M = max(max(y, 0), dark_floor * (double)n);
+ *       rho_p = M > 0 ? D / M : 0.
+ * The map is the 3 x 3 binomial mean of rho:  num = +0, den = +0; for dj = -1..1 (outer), di = -1..1 (inner), q = p + (di, dj) inside the
+ * frame and not poisoned, b = (2 - |di|) * (2 - |dj|):  num = num + b*rho_q, den = den + b;  the result is num / den rounded to T.  A
+ * poisoned pixel p is a quiet NaN (and never a neighbour).  rho is relative to the pixel's OWN sample count, so the mean may cross tile
+ * borders; one |H_p| is an estimate with one degree of freedom, hence the mean (3 x 3 was chosen over 5 x 5 on the sweep of DESIGN.md 7.11).
+ *
+ * rtw_guided_filter_device_*: the device form of the filter above with one more input, `d_noise`: a DEVICE pointer, aligned to T, to
+ * height*width elements (the map above, or any per-pixel relative noise the caller has).  rtw_denoise_t is unchanged and there is no flag
+ * for it: the entry point is what makes the call guided.  Workspace, alignment, aliasing rules (d_noise is an input) and refusals are
+ * those of the device form above; a null d_noise -> -1.  The definition differs from the one above in two places:
+ *   Prepare.  valid(p) additionally needs a finite noise[p] = rho.  L = (e[0] + e[1]) + e[2];  s = rho * max(L, T(2^-6));
+ *       v_p = min(max(s*s, V_MIN), V_MAX),  max(x, c) = x > c ? x : c,  min(x, c) = x < c ? x : c  (so a NaN s*s becomes V_MIN),
+ *       V_MIN = 2^-40, V_MAX = 2^40: powers of two, normal numbers in binary32, so v_p is positive and finite and dc / v_p is never 0/0 or
+ *       inf/inf.  v_p is kept for all levels.
+ *   Level k.  The colour weight is  w_c = 1 / (1 + (dc / v_p)*inv_sc)  with the CENTRE pixel's v_p; inv_sc = T(1 / (sc*sc)), sc =
+ *       sigma_color * 2^-k as above.  sigma_color thus counts estimated standard deviations of the pixel instead of colour units.
+ * Everything else -- tap order, skipped taps, coverage, normal and depth terms, the end step -- is the definition above, bit for bit.
+ *
+ * rtw_accum_filtered_*: `out` is a HOST buffer of height*width*3 elements; blocking.  It runs, on the accumulator's device in a cached
+ * context (the stream and buffer of the host forms), the resolve with gamma = 0 (per tile for an adaptive accumulator), the feature pass
+ * rtw_accum_features_*, with guided = 1 the map rtw_accum_noise_* and the guided filter, with guided = 0 the filter above; d->gamma is
+ * replaced by p->gamma and d->device by the accumulator's device; the result is copied to `out` once.  rtw_stats() afterwards reports
+ * the feature pass's record.  Refusals, before any HIP call: nulls -> -1; guided other than 0 / 1 -> -2; everything rtw_accum_features_*
+ * and the filter's own checks refuse; guided = 1 on a uniform accumulator -> -2.
+ *   Out of scope: batched launches of these passes, temporal reuse across views, device lists, compact or sharded
+ * frames.  Additive to ABI 4: detected by symbol lookup. */
+int rtw_accum_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, rtw_accum_handle accum, void *d_out, void *hip_stream);
+int rtw_accum_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, rtw_accum_handle accum, void *d_out, void *hip_stream);
+int rtw_accum_noise_f32(rtw_accum_handle accum, void *d_out, void *hip_stream);
+int rtw_accum_noise_f64(rtw_accum_handle accum, void *d_out, void *hip_stream);
+int rtw_guided_filter_device_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_noise,
+                                 void *d_out, void *d_work, void *hip_stream);
+int rtw_guided_filter_device_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_noise,
+                                 void *d_out, void *d_work, void *hip_stream);
+int rtw_accum_filtered_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle accum, int32_t guided,
+                           float *out);
+int rtw_accum_filtered_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle accum, int32_t guided,
+                           double *out);
 
 /* Counters/timings of the last render issued from this thread (waits for it to finish). */
 int rtw_stats(rtw_stats_t *out);
@@ -541,6 +607,9 @@ int rtw_stats_devices(int32_t capacity, int32_t *count, int32_t *devices, double
  *       23 the per-tile resolve (also on rtw_unit_f32: T = float).  count = 1.  in: 8 value slots width, height, spp, chunk_spp, gamma
  *          (0 / 1), 0, 0, 0; n_tiles value slots C_t >= 1; width * height * 8 raw words.  out: width * height * 3 value slots, element
  *          (j * height + i) * 3 + channel: the sum over min(spp, C_t * chunk_spp) samples of the pixel's tile, rounded to T, widened.
+ *   Op 25 runs the noise map kernel of rtw_accum_noise_* the same way (24 is not an op; also on rtw_unit_f32: T = float).  count = 1.  in: 8 value
+ *          slots width, height, spp, chunk_spp, dark_floor (finite, >= 0), 0, 0, 0; n_tiles value slots C_t >= 1; width * height * 8 raw words.
+ *          out: width * height value slots, element j * height + i: the map's value of type T, widened (NaN for a poisoned pixel).
  *   bits 8-9 of `op`: the numerics mode of the ray-sphere test for ops 0, 8 - 11, 13, 14 (0 reference, 1 contract, 3 reference_fma2; 2 is rejected)  */
 int rtw_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene,
                  const rtw_camera_f32 *cam);

@@ -21,10 +21,12 @@ from .scenes import (  # noqa: F401
 )
 from .render import DeviceRenderer, render, render_batch, last_stats  # noqa: F401
 from .progressive import ProgressiveBatchRenderer, ProgressiveRenderer, render_progressive, samples_in_chunks  # noqa: F401
-from .adaptive import AdaptiveBatchRenderer, AdaptiveRenderer, reference_decisions, render_adaptive, render_adaptive_batch  # noqa: F401
+from .adaptive import (  # noqa: F401
+    AdaptiveBatchRenderer, AdaptiveRenderer, reference_decisions, render_adaptive, render_adaptive_batch, render_adaptive_denoised,
+)
 from .shard import compact_elems, compact_to_frame_index, local_tile_count, owned_pixel_mask, render_sharded  # noqa: F401
 from .features import features_into, render_features  # noqa: F401
-from .denoise import denoise, denoise_into, denoise_work_bytes, render_denoised  # noqa: F401
+from .denoise import denoise, denoise_guided_into, denoise_into, denoise_work_bytes, render_denoised  # noqa: F401
 from . import imageio  # noqa: F401
 
 __all__ = [
@@ -37,4 +39,5 @@ __all__ = [
     "AdaptiveRenderer", "render_adaptive", "reference_decisions", "owned_pixel_mask", "render_sharded", "compact_elems",
     "compact_to_frame_index", "local_tile_count", "ProgressiveBatchRenderer", "AdaptiveBatchRenderer", "render_adaptive_batch",
     "render_features", "features_into", "denoise", "denoise_into", "denoise_work_bytes", "render_denoised",
+    "denoise_guided_into", "render_adaptive_denoised",
 ]

@@ -21,6 +21,8 @@ SYMBOLS = [
     "rtw_render_features_device_f32", "rtw_render_features_device_f64", "rtw_render_features_f32", "rtw_render_features_f64",
     "rtw_denoise_work_bytes", "rtw_denoise_device_f32", "rtw_denoise_device_f64", "rtw_denoise_f32", "rtw_denoise_f64",
     "rtw_render_denoised_f32", "rtw_render_denoised_f64",
+    "rtw_accum_features_f32", "rtw_accum_features_f64", "rtw_accum_noise_f32", "rtw_accum_noise_f64",
+    "rtw_guided_filter_device_f32", "rtw_guided_filter_device_f64", "rtw_accum_filtered_f32", "rtw_accum_filtered_f64",
 ]
 
 
@@ -130,6 +132,11 @@ def lib():
         getattr(L, "rtw_denoise_device_" + sfx).argtypes = [C.POINTER(Denoise), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         getattr(L, "rtw_denoise_" + sfx).argtypes = [C.POINTER(Denoise), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         getattr(L, "rtw_render_denoised_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), C.POINTER(Params), C.POINTER(Denoise), C.c_void_p]
+        getattr(L, "rtw_accum_features_" + sfx).argtypes = [C.c_void_p, C.POINTER(CamT), C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p]
+        getattr(L, "rtw_accum_noise_" + sfx).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        getattr(L, "rtw_guided_filter_device_" + sfx).argtypes = [C.POINTER(Denoise), C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                 C.c_void_p]
+        getattr(L, "rtw_accum_filtered_" + sfx).argtypes = [C.c_void_p, C.POINTER(CamT), C.POINTER(Params), C.POINTER(Denoise), C.c_void_p, C.c_int32, C.c_void_p]
     L.rtw_denoise_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_denoise_work_bytes.restype = C.c_int64
     L.rtw_accum_adaptive_info.argtypes = [C.c_void_p, C.POINTER(AdaptiveInfo)]

@@ -130,6 +130,28 @@ class AdaptiveRenderer(ProgressiveRenderer):
         spp = np.minimum(self.n_samples, self.tile_chunks().astype(np.int64) * self.chunk_spp).astype(np.int32)
         return np.repeat(np.repeat(spp, 8, axis=0), 8, axis=1)[:self.height, :self.width]
 
+    def noise_into(self, d_out_ptr, stream=0):
+        """Enqueue the noise map (rtw_accum_noise_*) into device memory at ``d_out_ptr``: H*W elements, pixel (i, j) at ``j*H + i``."""
+        fn = self.L.rtw_accum_noise_f64 if _capi.is_f64(self.T) else self.L.rtw_accum_noise_f32
+        _capi.check(fn(self.accum, C.c_void_p(int(d_out_ptr)), C.c_void_p(int(stream))))
+
+    def noise(self):
+        """``H x W``: the per-pixel relative noise of the render so far -- the 3x3 binomial mean of ``|H_p| 2^-24 / max(y_p, dark_floor
+        n)``, the stopping rule's own quantities for one pixel; NaN for a poisoned pixel (blocking)."""
+        import torch
+        buf = self._device_buffer(self.height * self.width)
+        self.noise_into(buf.data_ptr(), stream=torch.cuda.current_stream(buf.device).cuda_stream)
+        return buf.cpu().numpy().reshape(self.width, self.height).T
+
+    def denoised(self, guided=True, gamma=True, **params):
+        """The adaptive image filtered with the features of exactly the samples each tile holds (rtw_accum_filtered_*, blocking).
+        ``guided`` (default): the colour weight of every pixel is scaled by its own noise estimate (``noise()``), so ``sigma_color``
+        counts standard deviations (default ``GUIDED_SIGMA_COLOR``); ``guided=False``: the plain filter.  Keywords: ``make_denoise``."""
+        if guided:
+            from .denoise import GUIDED_SIGMA_COLOR
+            params.setdefault("sigma_color", GUIDED_SIGMA_COLOR)
+        return self._filtered(bool(guided), gamma, params)
+
     def info(self):
         """the accumulator's info (``samples_done`` / ``chunks_done``: the least sampled tile) and, once a run has finished, the
         fields of ``rtw_adaptive_info_t``"""
@@ -138,6 +160,18 @@ class AdaptiveRenderer(ProgressiveRenderer):
         if self.L.rtw_accum_adaptive_info(self.accum, C.byref(st)) == 0:
             out.update({k: getattr(st, k) for k, _ in st._fields_})
         return out
+
+
+def render_adaptive_denoised(scene, cam, image_width=400, n_samples=1, *, tolerance, guided=True, dark_floor=DEFAULT_DARK_FLOOR, depth=16, seed=1,
+                             n_chunks=0, min_chunks=0, check_chunks=0, group_cull=False, scan_valu=False, numerics=None, gamma=True, device=-1,
+                             **denoise_params):
+    """``render_adaptive`` followed by ``AdaptiveRenderer.denoised`` on the device: every tile is filtered with the features of the
+    chunks it holds and, with ``guided`` (default), with a colour weight scaled by each pixel's own noise estimate.  ``denoise_params``:
+    the keywords of ``make_denoise`` but ``gamma`` / ``device``.  Returns ``(image, samples_per_pixel, info)`` like ``render_adaptive``."""
+    with AdaptiveRenderer(scene, cam, image_width, n_samples, dark_floor=dark_floor, min_chunks=min_chunks, check_chunks=check_chunks,
+                          depth=depth, seed=seed, n_chunks=n_chunks, device=device, numerics=numerics) as ar:
+        info = ar.run(tolerance, group_cull=group_cull, scan_valu=scan_valu)
+        return ar.denoised(guided=guided, gamma=gamma, **denoise_params), ar.samples_per_pixel(), info
 
 
 def render_adaptive(scene, cam, image_width=400, n_samples=1, *, tolerance, dark_floor=DEFAULT_DARK_FLOOR, depth=16, seed=1, n_chunks=0,
@@ -198,6 +232,13 @@ class AdaptiveBatchRenderer(ProgressiveBatchRenderer):
         """int32 ``N x H x W``: the samples each pixel of each view holds"""
         spp = np.minimum(self.n_samples, self.tile_chunks().astype(np.int64) * self.chunk_spp).astype(np.int32)
         return np.repeat(np.repeat(spp, 8, axis=1), 8, axis=2)[:, :self.height, :self.width]
+
+    def denoised(self, v, guided=True, gamma=True, **params):
+        """View ``v``'s adaptive image, filtered like ``AdaptiveRenderer.denoised``"""
+        if guided:
+            from .denoise import GUIDED_SIGMA_COLOR
+            params.setdefault("sigma_color", GUIDED_SIGMA_COLOR)
+        return self._filtered(v, bool(guided), gamma, params)
 
     def info(self, v):
         """view ``v``'s accumulator info and, once a run has finished, the fields of ``rtw_adaptive_info_t``"""

@@ -238,6 +238,48 @@ __global__ __launch_bounds__(256) void accum_resolve_tiles_kernel(const unsigned
     out[k] = (T)v;
 }
 
+// ---- the noise map of an adaptive accumulator (include/rtw_hip.h rtw_accum_noise_*) ----
+// rho of one pixel: the stopping rule's D / M for the pixel alone, n = the samples ITS tile holds.  false: the pixel is poisoned.
+__device__ __forceinline__ bool pixel_rho(const unsigned long long *__restrict__ words, const int *__restrict__ chunks, size_t i, size_t j, int height, int tiles_i, int spp,
+                                          int chunk_spp, double floor, double *rho) {
+    const unsigned long long *a = words + (j * (size_t)height + i) * 8u;
+    if (a[6] != 0ull) return false;
+    const long long held = (long long)chunks[(j >> 3) * (size_t)tiles_i + (i >> 3)] * chunk_spp;
+    const double n = (double)(held < spp ? held : (long long)spp);
+    const long long h = (long long)a[7];
+    const unsigned long long m = h < 0 ? 0ull - (unsigned long long)h : (unsigned long long)h;
+    const double D = (double)m * 0x1p-24;                  // (exact scaling)
+    double y = (rtw::fx_to_double(a[0], a[1]) + rtw::fx_to_double(a[2], a[3])) + rtw::fx_to_double(a[4], a[5]);
+    y = y > 0.0 ? y : 0.0;
+    const double dark = floor * n;
+    const double M = y > dark ? y : dark;
+    *rho = M > 0.0 ? D / M : 0.0;
+    return true;
+}
+// one pixel per lane, lanes along i: the 3 x 3 binomial mean of rho over the neighbours inside the frame that are not poisoned, dj outer,
+// di inner, both sums sequential; a poisoned centre is a quiet NaN.  Reads only; no LDS, no atomics, no cross-lane operation.
+template <typename T>
+__global__ __launch_bounds__(256) void accum_noise_kernel(const unsigned long long *__restrict__ words, const int *__restrict__ chunks, T *__restrict__ out, int width, int height,
+                                                          int tiles_i, int spp, int chunk_spp, double floor) {
+    const size_t p = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (p >= (size_t)width * (size_t)height) return;
+    const size_t j = p / (size_t)height, i = p - j * (size_t)height;
+    double rho;
+    if (!pixel_rho(words, chunks, i, j, height, tiles_i, spp, chunk_spp, floor, &rho)) { out[p] = (T)__builtin_nan(""); return; }
+    double num = 0.0, den = 0.0;
+    for (int dj = -1; dj <= 1; ++dj)
+        for (int di = -1; di <= 1; ++di) {
+            const long long qi = (long long)i + di, qj = (long long)j + dj;
+            if (qi < 0 || qi >= height || qj < 0 || qj >= width) continue;
+            double r;
+            if (!pixel_rho(words, chunks, (size_t)qi, (size_t)qj, height, tiles_i, spp, chunk_spp, floor, &r)) continue;
+            const double b = (double)((di == 0 ? 2 : 1) * (dj == 0 ? 2 : 1));
+            num = num + b * r;
+            den = den + b;
+        }
+    out[p] = (T)(num / den);
+}
+
 // ---- the launches of the tile kernels: adaptive_loop / resolve_dev and the unit ops 21-23 (accum_unit) all go through these, so the test
 // seam runs the product's kernels with the product's grids.  (enqueue only: the caller clears and reads hipGetLastError around them) ----
 int tiles_down(int height) { return (height + 7) / 8; }
@@ -272,6 +314,13 @@ void launch_resolve_tiles(hipStream_t stream, const unsigned long long *words, T
     const size_t n = (size_t)width * (size_t)height * 3u;
     hipLaunchKernelGGL(accum_resolve_tiles_kernel<T>, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, words, d_out, n, chunks, height, tiles_down(height),
                        spp, chunk_spp, gamma);
+}
+
+// the noise map of a frame whose tile t holds C_t = chunks[t] >= 1 chunks (rtw_accum_noise_* and the unit op 25)
+template <typename T>
+void launch_noise(hipStream_t stream, const unsigned long long *words, T *d_out, const int *chunks, int width, int height, int spp, int chunk_spp, double floor) {
+    const size_t n = (size_t)width * (size_t)height;
+    hipLaunchKernelGGL(accum_noise_kernel<T>, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, words, chunks, d_out, width, height, tiles_down(height), spp, chunk_spp, floor);
 }
 
 size_t n_pixels(const rtw_accum *a) { return (size_t)a->width * (size_t)a->height; }
@@ -898,16 +947,132 @@ int unit_resolve_tiles(int count, const double *in, double *out) {
     return 0;
 }
 
+// op 25: in = width, height, spp, chunk_spp, dark_floor, 0, 0, 0 | n_tiles x C_t | W * H * 8 raw words; out = the W * H values of
+// accum_noise_kernel<T>, each widened to binary64
+template <typename T>
+int unit_noise(int count, const double *in, double *out) {
+    int W, H, spp, cs;
+    if (count != 1) return fail(-2, "unit op 25: count must be 1 (got %d)", count);
+    if (int rc = unit_frame(in, &W, &H)) return rc;
+    if (!slot_int(in[2], 1, 0x7fffffff, &spp) || !slot_int(in[3], 1, 0x7fffffff, &cs)) return fail(-2, "unit op 25: spp %g, chunk_spp %g", in[2], in[3]);
+    const double floor = in[4];
+    if (!std::isfinite(floor) || floor < 0.0) return fail(-2, "unit op 25: dark_floor %g", floor);
+    if (in[5] != 0.0 || in[6] != 0.0 || in[7] != 0.0) return fail(-2, "unit op 25: header slots 5 to 7 must be 0");
+    const long long n_tiles = tiles_of(W, H), n_words = (long long)W * H * 8;
+    std::vector<int32_t> chunks;
+    if (int rc = unit_chunks(in + 8, n_tiles, 1, &chunks)) return rc;
+    DeviceGuard guard;
+    if (int rc = unit_device()) return rc;
+    const size_t n_out = (size_t)W * (size_t)H, words_b = (size_t)n_words * 8u, out_b = up16(n_out * sizeof(T));
+    DevBuf buf;
+    HIP_TRY(hipMalloc(&buf.p, words_b + out_b + (size_t)n_tiles * sizeof(int32_t)));
+    unsigned long long *d_words = static_cast<unsigned long long *>(buf.p);
+    T *d_out = reinterpret_cast<T *>(static_cast<char *>(buf.p) + words_b);
+    int32_t *d_chunks = reinterpret_cast<int32_t *>(static_cast<char *>(buf.p) + words_b + out_b);
+    HIP_TRY(hipMemcpy(d_words, in + 8 + (size_t)n_tiles, words_b, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_chunks, chunks.data(), (size_t)n_tiles * sizeof(int32_t), hipMemcpyHostToDevice));
+    (void)hipGetLastError();
+    launch_noise<T>(nullptr, d_words, d_out, d_chunks, W, H, spp, cs, floor);
+    HIP_TRY(hipGetLastError());
+    std::vector<T> h(n_out);
+    HIP_TRY(hipMemcpy(h.data(), d_out, n_out * sizeof(T), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n_out; ++k) out[k] = (double)h[k];
+    return 0;
+}
+
+// ---- an accumulator as the denoiser's input (include/rtw_hip.h rtw_accum_features_*, rtw_accum_noise_*): everything here READS the words and
+// C_t; the calls wait for the accumulator's event and record it afterwards, so a later pass cannot overwrite them under a running kernel ----
+// an adaptive accumulator whose last call finished: C_t on the device is what the host copy says
+int check_adaptive_complete(const rtw_accum *a) {
+    if (!a->ad_complete || !a->d_tiles || a->tile_chunks.size() != (size_t)n_tiles_of(a))
+        return fail(-2, "the accumulator's last adaptive call did not finish: its tiles' chunk counts are not settled");
+    return 0;
+}
+template <typename CamT>
+int validate_accum_features(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, rtw_accum_handle a) {
+    if (!p) return fail(-1, "null params");
+    if (!cam || !a || !scene) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = validate_features(p, 0, 1, &nch, &cs)) return rc;
+    if (int rc = validate_handles(sizeof(CamT) == sizeof(rtw_camera_f64), scene, p, a)) return rc;
+    if (!a->bound) return fail(-2, "the accumulator holds no chunk interval: there is nothing to take features of");
+    AccumBind b;
+    make_bind(&b, scene, cam, p, nch, cs);
+    if (!same_render(a->bind, b)) return fail(-4, "the accumulator is bound to another render (size, precision, seed, spp, chunks, depth, numerics, camera or scene differ)");
+    if (a->adaptive) return check_adaptive_complete(a);
+    if (a->ranges.size() != 1) return fail(-2, "the accumulator holds %d chunk intervals: a feature pass covers exactly one", (int)a->ranges.size());
+    return 0;
+}
+template <typename CamT>
+int enqueue_accum_features(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, rtw_accum_handle a, void *d_out, hipStream_t stream, RenderRec **rec, CtxPtr *ctx) {
+    HIP_TRY(hipSetDevice(a->device));
+    if (int rc = wait_for(a, stream)) return rc;
+    int rc;
+    if (a->adaptive) rc = launch_features_t(scene, cam, p, 0, 1, d_out, stream, rec, ctx, a->d_tiles);
+    else rc = launch_features_t(scene, cam, p, a->ranges[0].first, a->ranges[0].second - a->ranges[0].first, d_out, stream, rec, ctx);
+    if (rc) return rc;
+    return mark(a, stream);
+}
+template <typename CamT>
+int accum_features(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, rtw_accum_handle a, void *d_out, void *stream_v) {
+    // (nulls, the render's own checks and the buffer before a handle is looked at, like the device form of the feature pass)
+    if (!p) return fail(-1, "null params");
+    if (!cam || !a || !scene || !d_out) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = validate_features(p, 0, 1, &nch, &cs)) return rc;
+    if (((uintptr_t)d_out & 15u) != 0) return fail(-2, "the feature buffer must be 16-byte aligned");
+    if (int rc = validate_accum_features(scene, cam, p, a)) return rc;
+    DeviceGuard guard;
+    RenderRec *rec = nullptr;
+    CtxPtr ctx;
+    release_last();
+    const int rc = enqueue_accum_features(scene, cam, p, a, d_out, (hipStream_t)stream_v, &rec, &ctx);
+    hold_last(rec, ctx);               // (also on a late error: released by the next call)
+    return rc;
+}
+
 }  // namespace
+
+int validate_accum_features_f32(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, rtw_accum_handle a) { return validate_accum_features(s, c, p, a); }
+int validate_accum_features_f64(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, rtw_accum_handle a) { return validate_accum_features(s, c, p, a); }
+int enqueue_accum_features_f32(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, rtw_accum_handle a, void *d_out, hipStream_t st, RenderRec **rec, CtxPtr *ctx) {
+    return enqueue_accum_features(s, c, p, a, d_out, st, rec, ctx);
+}
+int enqueue_accum_features_f64(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, rtw_accum_handle a, void *d_out, hipStream_t st, RenderRec **rec, CtxPtr *ctx) {
+    return enqueue_accum_features(s, c, p, a, d_out, st, rec, ctx);
+}
+int accum_device_of(rtw_accum_handle a) { return a->device; }
+bool accum_is_adaptive(rtw_accum_handle a) { return a->adaptive; }
+int validate_accum_noise(rtw_accum_handle a, bool f64) {
+    if (!a) return fail(-1, "null argument");
+    if (!a->adaptive) return fail(-2, "the accumulator is not adaptive: word 7 of its pixels is 0 by contract, it carries no noise measurement");
+    if (int rc = check_adaptive_complete(a)) return rc;
+    if ((a->bind.is_f64 != 0) != f64) return fail(-4, "accumulator precision does not match the call");
+    return 0;
+}
+int enqueue_accum_noise(rtw_accum_handle a, bool f64, void *d_out, hipStream_t stream) {
+    HIP_TRY(hipSetDevice(a->device));
+    if (int rc = wait_for(a, stream)) return rc;
+    (void)hipGetLastError();
+    if (f64) launch_noise<double>(stream, a->words, (double *)d_out, a->d_tiles, (int)a->width, (int)a->height, (int)a->bind.spp, (int)a->bind.chunk_spp, a->ad.dark_floor);
+    else launch_noise<float>(stream, a->words, (float *)d_out, a->d_tiles, (int)a->width, (int)a->height, (int)a->bind.spp, (int)a->bind.chunk_spp, a->ad.dark_floor);
+    HIP_TRY(hipGetLastError());
+    return mark(a, stream);
+}
+int enqueue_accum_resolve(rtw_accum_handle a, bool f64, int32_t gamma, void *d_out, hipStream_t stream) {
+    return f64 ? resolve_dev<double>(a, gamma, d_out, stream) : resolve_dev<float>(a, gamma, d_out, stream);
+}
 
 int accum_unit(int op, bool f64, int count, const void *in, void *out) {
     if (!in || !out) return fail(-1, "null argument");
-    if (op != 23 && !f64) return fail(-2, "unit op %d is an op of rtw_unit_f64", op);
+    if (op != 23 && op != 25 && !f64) return fail(-2, "unit op %d is an op of rtw_unit_f64", op);
     switch (op) {
         case 21: return unit_tile_check(count, static_cast<const double *>(in), static_cast<long long *>(out));
         case 22: return unit_compact(count, static_cast<const unsigned long long *>(in), static_cast<long long *>(out));
         case 23: return f64 ? unit_resolve_tiles<double>(count, static_cast<const double *>(in), static_cast<double *>(out))
                             : unit_resolve_tiles<float>(count, static_cast<const double *>(in), static_cast<double *>(out));
+        case 25: return f64 ? unit_noise<double>(count, static_cast<const double *>(in), static_cast<double *>(out))
+                            : unit_noise<float>(count, static_cast<const double *>(in), static_cast<double *>(out));
     }
     return fail(-2, "unknown unit op %d", op);
 }
@@ -1002,6 +1167,22 @@ int rtw_accum_tile_chunks(rtw_accum_handle a, int32_t capacity, int32_t *count, 
     for (int32_t k = 0; k < capacity && k < n; ++k) chunks[k] = a->adaptive && !a->tile_chunks.empty() ? a->tile_chunks[(size_t)k] : uniform;
     return 0;
 }
+
+int rtw_accum_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, rtw_accum_handle a, void *d_out, void *stream) {
+    return accum_features(scene, cam, p, a, d_out, stream);
+}
+int rtw_accum_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, rtw_accum_handle a, void *d_out, void *stream) {
+    return accum_features(scene, cam, p, a, d_out, stream);
+}
+static int accum_noise(rtw_accum_handle a, bool f64, void *d_out, void *stream) {
+    if (!a || !d_out) return fail(-1, "null argument");
+    if (int rc = validate_accum_noise(a, f64)) return rc;
+    if ((uintptr_t)d_out & (f64 ? 7u : 3u)) return fail(-2, "the noise map must be aligned to its element type");
+    DeviceGuard guard;
+    return enqueue_accum_noise(a, f64, d_out, (hipStream_t)stream);
+}
+int rtw_accum_noise_f32(rtw_accum_handle a, void *d_out, void *stream) { return accum_noise(a, false, d_out, stream); }
+int rtw_accum_noise_f64(rtw_accum_handle a, void *d_out, void *stream) { return accum_noise(a, true, d_out, stream); }
 
 int rtw_accum_resolve_f32(rtw_accum_handle a, int32_t gamma, void *d_out, void *stream) {
     if (!a || !d_out) return fail(-1, "null argument");

@@ -31,9 +31,11 @@ static bool overlap(const void *a, long long na, const void *b, long long nb) {
     return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
 }
 
-// Enqueue the denoiser on `stream` of the current device (validate_denoise has accepted the call).
+// Enqueue the denoiser on `stream` of the current device (validate_denoise has accepted the call).  d_noise non-null: the noise-guided
+// form -- the GUIDED instances of both kernels, the same launch sequence and workspace (the variance lives in the A plane's fourth slot).
 template <typename T>
-int launch_denoise(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream) {
+int launch_denoise(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream,
+                   const void *d_noise) {
     using V = typename rtw::DnVec<T>::type;
     const long long n_pix = (long long)width * height;
     char *w = (char *)d_work;
@@ -49,7 +51,9 @@ int launch_denoise(const rtw_denoise_t *d, int32_t width, int32_t height, const 
     if (profile) for (int k = 0; k <= d->levels + 1; ++k) HIP_TRY(hipEventCreate(&ev[k]));
     if (profile) HIP_TRY(hipEventRecord(ev[0], stream));
     (void)hipGetLastError();
-    hipLaunchKernelGGL(rtw::dn_prepare<T>, dim3(grid), dim3(256), 0, stream, (const T *)d_image, (const V *)d_features, E[0], G, A, n_pix, demod ? 1 : 0);
+    const bool guided = d_noise != nullptr;
+    if (guided) hipLaunchKernelGGL((rtw::dn_prepare<T, true>), dim3(grid), dim3(256), 0, stream, (const T *)d_image, (const V *)d_features, E[0], G, A, n_pix, demod ? 1 : 0, (const T *)d_noise);
+    else hipLaunchKernelGGL((rtw::dn_prepare<T, false>), dim3(grid), dim3(256), 0, stream, (const T *)d_image, (const V *)d_features, E[0], G, A, n_pix, demod ? 1 : 0, (const T *)nullptr);
     HIP_TRY(hipGetLastError());
     if (profile) HIP_TRY(hipEventRecord(ev[1], stream));
     for (int k = 0; k < d->levels; ++k) {
@@ -62,32 +66,35 @@ int launch_denoise(const rtw_denoise_t *d, int32_t width, int32_t height, const 
         L.W = width; L.H = height;
         const V *in = E[k & 1];
         V *next = E[(k & 1) ^ 1];
-        hipLaunchKernelGGL(rtw::dn_level<T>, dim3(grid), dim3(256), 0, stream, L, in, (const V *)G, (const V *)A, next, (T *)d_out);
+        if (guided) hipLaunchKernelGGL((rtw::dn_level<T, true>), dim3(grid), dim3(256), 0, stream, L, in, (const V *)G, (const V *)A, next, (T *)d_out);
+        else hipLaunchKernelGGL((rtw::dn_level<T, false>), dim3(grid), dim3(256), 0, stream, L, in, (const V *)G, (const V *)A, next, (T *)d_out);
         HIP_TRY(hipGetLastError());
         if (profile) HIP_TRY(hipEventRecord(ev[k + 2], stream));
     }
     if (profile) {
+        const char *tag = guided ? "rtw denoise guided" : "rtw denoise";       // (tools/gpu_accum_denoise.py tells the two forms apart by it)
         HIP_TRY(hipEventSynchronize(ev[d->levels + 1]));
         for (int k = 0; k <= d->levels; ++k) {
             float ms = 0;
             HIP_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-            if (k == 0) fprintf(stderr, "[rtw denoise] %s %dx%d prepare ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, ms);
-            else fprintf(stderr, "[rtw denoise] %s %dx%d level step=%d final=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, 1 << (k - 1),
+            if (k == 0) fprintf(stderr, "[%s] %s %dx%d prepare ms=%.5f\n", tag, sizeof(T) == 8 ? "f64" : "f32", width, height, ms);
+            else fprintf(stderr, "[%s] %s %dx%d level step=%d final=%d ms=%.5f\n", tag, sizeof(T) == 8 ? "f64" : "f32", width, height, 1 << (k - 1),
                          (int)(k == d->levels), ms);
         }
         float all_ms = 0;
         HIP_TRY(hipEventElapsedTime(&all_ms, ev[0], ev[d->levels + 1]));
-        fprintf(stderr, "[rtw denoise] %s %dx%d total levels=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, d->levels, all_ms);
+        fprintf(stderr, "[%s] %s %dx%d total levels=%d ms=%.5f\n", tag, sizeof(T) == 8 ? "f64" : "f32", width, height, d->levels, all_ms);
     }
     return 0;
 }
 
-int launch_denoise_f32(const rtw_denoise_t *d, int32_t w, int32_t h, const void *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_denoise<float>(d, w, h, img, feat, out, work, st); }
-int launch_denoise_f64(const rtw_denoise_t *d, int32_t w, int32_t h, const void *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_denoise<double>(d, w, h, img, feat, out, work, st); }
+int launch_denoise_f32(const rtw_denoise_t *d, int32_t w, int32_t h, const void *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise) { return launch_denoise<float>(d, w, h, img, feat, out, work, st, noise); }
+int launch_denoise_f64(const rtw_denoise_t *d, int32_t w, int32_t h, const void *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise) { return launch_denoise<double>(d, w, h, img, feat, out, work, st, noise); }
 
+// the device-resident entry points; `guided`: rtw_guided_filter_device_* (d_noise: H*W elements of T), else d_noise is null
 template <typename T>
-int denoise_device(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, void *stream_v) {
-    if (!d || !d_image || !d_features || !d_out || !d_work) return fail(-1, "null argument");
+int denoise_device(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_noise, bool guided, void *d_out, void *d_work, void *stream_v) {
+    if (!d || !d_image || !d_features || !d_out || !d_work || (guided && !d_noise)) return fail(-1, "null argument");
     if (int rc = validate_denoise(d, width, height)) return rc;
     if (((uintptr_t)d_work & 15u) || ((uintptr_t)d_features & 15u)) return fail(-2, "the workspace and the feature buffer must be 16-byte aligned");
     if (((uintptr_t)d_image & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
@@ -96,9 +103,15 @@ int denoise_device(const rtw_denoise_t *d, int32_t width, int32_t height, const 
     if (overlap(d_out, img_b, d_image, img_b) || overlap(d_out, img_b, d_features, feat_b) || overlap(d_out, img_b, d_work, work_b))
         return fail(-2, "d_out may not alias an input or the workspace");
     if (overlap(d_work, work_b, d_image, img_b) || overlap(d_work, work_b, d_features, feat_b)) return fail(-2, "the workspace may not alias an input");
+    if (guided) {
+        const long long noise_b = n_pix * (long long)sizeof(T);
+        if ((uintptr_t)d_noise & (sizeof(T) - 1)) return fail(-2, "the noise map must be aligned to its element type");
+        if (overlap(d_out, img_b, d_noise, noise_b)) return fail(-2, "d_out may not alias an input or the workspace");
+        if (overlap(d_work, work_b, d_noise, noise_b)) return fail(-2, "the workspace may not alias an input");
+    }
     DeviceGuard guard;
     if (d->device >= 0) HIP_TRY(hipSetDevice(d->device));
-    return launch_denoise<T>(d, width, height, d_image, d_features, d_out, d_work, (hipStream_t)stream_v);
+    return launch_denoise<T>(d, width, height, d_image, d_features, d_out, d_work, (hipStream_t)stream_v, guided ? d_noise : nullptr);
 }
 
 }  // namespace rtwh
@@ -115,10 +128,18 @@ int64_t rtw_denoise_work_bytes(int32_t width, int32_t height, int32_t elem_bytes
     return 4 * plane_bytes(width, height, elem_bytes);
 }
 int rtw_denoise_device_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, void *hip_stream) {
-    return denoise_device<float>(d, width, height, d_image, d_features, d_out, d_work, hip_stream);
+    return denoise_device<float>(d, width, height, d_image, d_features, nullptr, false, d_out, d_work, hip_stream);
 }
 int rtw_denoise_device_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, void *hip_stream) {
-    return denoise_device<double>(d, width, height, d_image, d_features, d_out, d_work, hip_stream);
+    return denoise_device<double>(d, width, height, d_image, d_features, nullptr, false, d_out, d_work, hip_stream);
+}
+int rtw_guided_filter_device_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_noise, void *d_out, void *d_work,
+                                 void *hip_stream) {
+    return denoise_device<float>(d, width, height, d_image, d_features, d_noise, true, d_out, d_work, hip_stream);
+}
+int rtw_guided_filter_device_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_noise, void *d_out, void *d_work,
+                                 void *hip_stream) {
+    return denoise_device<double>(d, width, height, d_image, d_features, d_noise, true, d_out, d_work, hip_stream);
 }
 int rtw_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const float *image, const float *features, float *out) {
     return denoise_host_f32(d, width, height, image, features, out);
@@ -131,6 +152,12 @@ int rtw_render_denoised_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *ca
 }
 int rtw_render_denoised_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, double *out) {
     return render_host_denoised_f64(scene, cam, p, d, out);
+}
+int rtw_accum_filtered_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle accum, int32_t guided, float *out) {
+    return accum_filtered_host_f32(scene, cam, p, d, accum, guided, out);
+}
+int rtw_accum_filtered_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle accum, int32_t guided, double *out) {
+    return accum_filtered_host_f64(scene, cam, p, d, accum, guided, out);
 }
 
 }  // extern "C"

@@ -7,6 +7,10 @@
 // The colour plane ping-pongs between two E planes; the last level multiplies the albedo back, applies gamma and the NaN rule and writes the
 // image.  No atomics, no cross-lane operation; the trip count over the taps is uniform, skipped taps are predicated by selects.
 // Every operation is rounded once (the Makefile's -ffp-contract=off -fno-fast-math); divisions and sqrt are the compiler's IEEE ones.
+//   GUIDED         the noise-guided form (include/rtw_hip.h rtw_guided_filter_device_*): prepare also reads the caller's noise map, treats a
+//                  pixel whose entry is not finite as not valid and stores the pixel's colour variance v in A.w (the slot the plain form
+//                  leaves 0); the level kernel divides a tap's colour distance by the CENTRE pixel's v.  Nothing else differs, and the
+//                  instances with GUIDED = false are the plain form's code.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,11 +41,17 @@ template <typename T> __device__ __forceinline__ bool dn_finite(T x) { return dn
 
 template <typename T> struct DnSum { T w, e0, e1, e2; };
 
+// the bounds of the guided form's variance: powers of two (the clamps and a division by them are exact), normal numbers in binary32
+#define RTW_DN_V_MIN 0x1p-40
+#define RTW_DN_V_MAX 0x1p40
+
 // one tap that is not the centre; `ok`: inside the frame and valid.  The data of a tap that is not ok may be anything: selects, not weights, drop it.
-template <typename T, typename V>
-__device__ __forceinline__ void dn_tap(DnSum<T> &a, const V &ep, const V &gp, const V &eq, const V &gq, T h, bool ok, const DnLevel<T> &L) {
+// GUIDED: `vp` is the centre pixel's variance (RTW_DN_V_MIN <= vp <= RTW_DN_V_MAX), the colour distance is measured in units of it.
+template <typename T, bool GUIDED, typename V>
+__device__ __forceinline__ void dn_tap(DnSum<T> &a, const V &ep, const V &gp, const V &eq, const V &gq, T h, bool ok, const DnLevel<T> &L, [[maybe_unused]] T vp) {
     const T d0 = ep.x - eq.x, d1 = ep.y - eq.y, d2 = ep.z - eq.z;
-    const T dc = (d0 * d0 + d1 * d1) + d2 * d2;
+    T dc = (d0 * d0 + d1 * d1) + d2 * d2;
+    if constexpr (GUIDED) dc = dc / vp;
     const T wc = T(1) / (T(1) + dc * L.inv_sc);
     const T tv = T(1) - dn_abs(gp.w - gq.w);
     const T wv = tv > T(0) ? tv : T(0);
@@ -84,16 +94,19 @@ __device__ __forceinline__ void dn_store(const DnSum<T> &a, const V &ep, const V
     out[p * 3 + 2] = valid ? e2 : dn_nan<T>();
 }
 
-template <typename T>
+template <typename T, bool GUIDED = false>
 __global__ __launch_bounds__(256) void dn_prepare(const T *__restrict__ image, const typename DnVec<T>::type *__restrict__ feat, typename DnVec<T>::type *__restrict__ E,
-                                                  typename DnVec<T>::type *__restrict__ G, typename DnVec<T>::type *__restrict__ A, long long n_pix, int demod) {
+                                                  typename DnVec<T>::type *__restrict__ G, typename DnVec<T>::type *__restrict__ A, long long n_pix, int demod,
+                                                  [[maybe_unused]] const T *__restrict__ noise) {
     using V = typename DnVec<T>::type;
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
     if (p >= n_pix) return;
     const T c0 = image[p * 3 + 0], c1 = image[p * 3 + 1], c2 = image[p * 3 + 2];
     const V f0 = feat[p * 2 + 0], f1 = feat[p * 2 + 1];        // albedo, n.x | n.y, n.z, depth, coverage
-    const bool valid = dn_finite(c0) && dn_finite(c1) && dn_finite(c2) && dn_finite(f0.x) && dn_finite(f0.y) && dn_finite(f0.z) && dn_finite(f0.w) &&
-                       dn_finite(f1.x) && dn_finite(f1.y) && dn_finite(f1.z) && dn_finite(f1.w);
+    bool valid = dn_finite(c0) && dn_finite(c1) && dn_finite(c2) && dn_finite(f0.x) && dn_finite(f0.y) && dn_finite(f0.z) && dn_finite(f0.w) &&
+                 dn_finite(f1.x) && dn_finite(f1.y) && dn_finite(f1.z) && dn_finite(f1.w);
+    [[maybe_unused]] T rho = T(0);
+    if constexpr (GUIDED) { rho = noise[p]; valid = valid && dn_finite(rho); }
     const T cov = f1.w;
     const bool has = valid && cov > T(0);
     const T dv = has ? cov : T(1);
@@ -110,11 +123,21 @@ __global__ __launch_bounds__(256) void dn_prepare(const T *__restrict__ image, c
     e.w = has ? z : T(0);
     g.x = has ? nx : T(0); g.y = has ? ny : T(0); g.z = has ? nz : T(0);
     g.w = valid ? cov : dn_nan<T>();
+    if constexpr (GUIDED) {
+        // the pixel's own standard deviation estimate: the relative noise times its (demodulated) brightness, floored like the albedo
+        const T floor_ = T(0.015625);
+        const T L = (e.x + e.y) + e.z;
+        const T s = rho * (L > floor_ ? L : floor_);
+        T v = s * s;
+        v = v > T(RTW_DN_V_MIN) ? v : T(RTW_DN_V_MIN);
+        v = v < T(RTW_DN_V_MAX) ? v : T(RTW_DN_V_MAX);
+        a.w = valid ? v : T(1);
+    }
     if (!valid) { e.x = e.y = e.z = T(0); a.x = a.y = a.z = T(1); }
     E[p] = e; G[p] = g; A[p] = a;
 }
 
-template <typename T>
+template <typename T, bool GUIDED = false>
 __global__ __launch_bounds__(256) void dn_level(DnLevel<T> L, const typename DnVec<T>::type *__restrict__ Ein, const typename DnVec<T>::type *__restrict__ G,
                                                        const typename DnVec<T>::type *__restrict__ A, typename DnVec<T>::type *__restrict__ Eout, T *__restrict__ out) {
     using V = typename DnVec<T>::type;
@@ -124,6 +147,8 @@ __global__ __launch_bounds__(256) void dn_level(DnLevel<T> L, const typename DnV
     // (a 32-bit division whenever the frame allows it)
     const long long j = W * H < (1ll << 31) ? (long long)((unsigned)p / (unsigned)H) : p / H, i = p - j * H;
     const V ep = Ein[p], gp = G[p];
+    [[maybe_unused]] T vp = T(1);
+    if constexpr (GUIDED) vp = A[p].w;
     DnSum<T> a = {T(0), T(0), T(0), T(0)};
 #pragma unroll
     for (int dj = -2; dj <= 2; ++dj) {
@@ -134,7 +159,7 @@ __global__ __launch_bounds__(256) void dn_level(DnLevel<T> L, const typename DnV
             const bool in = qi >= 0 && qi < H && qj >= 0 && qj < W;
             const long long q = in ? qj * H + qi : p;
             const V eq = Ein[q], gq = G[q];
-            dn_tap<T>(a, ep, gp, eq, gq, (T)(dn_k(di) * dn_k(dj)), in && gq.w == gq.w, L);
+            dn_tap<T, GUIDED>(a, ep, gp, eq, gq, (T)(dn_k(di) * dn_k(dj)), in && gq.w == gq.w, L, vp);
         }
     }
     dn_store<T>(a, ep, gp, p, L, A, Eout, out);

@@ -29,9 +29,11 @@ int validate_features(const rtw_params *p, int32_t chunk_begin, int32_t chunk_co
 
 // Enqueue the feature kernel for the chunks [chunk_begin, chunk_begin + chunk_count) of the render `p` describes (validate_features has
 // accepted them) on `stream`; `rec` receives the counters and the kernel's events like a render's.
+// d_tile_chunks non-null (rtw_accum_features_* on an adaptive accumulator, rtw_accum.hip): the TILED instances -- tile t gets the chunks
+// [0, d_tile_chunks[t]) instead of the call's range (which the caller passes as [0, 1): validated, not looked at by the kernel).
 template <typename T, typename CamT>
 int launch_features(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream,
-                    RenderRec **rec_out, CtxPtr *ctx_out) {
+                    RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks) {
     if (!scene || !cam || !p || !d_out) return fail(-1, "null argument");
     int nch, cs;
     if (int rc = validate_features(p, chunk_begin, chunk_count, &nch, &cs)) return rc;
@@ -60,32 +62,38 @@ int launch_features(rtw_scene_handle scene, const CamT *cam, const rtw_params *p
     PlainView<T> V;
     if (int rc = plain_scene_view<T>(scene, mfma, numerics, &V)) return rc;
     const size_t lds_bytes = rtw::feat_fixed_lds_bytes<T>() + (V.lds_scene ? V.scene_bytes : 0);
-    typedef void (*kern_t)(rtw::FeatParams, rtw::Camera<T>, rtw::DevScene<T>, T *, rtw::DevCounters *);
+    typedef void (*kern_t)(rtw::FeatParams, rtw::Camera<T>, rtw::DevScene<T>, T *, rtw::DevCounters *, const int *);
+    const bool tiled = d_tile_chunks != nullptr;
     kern_t kern;
-    if (mfma) kern = V.lds_scene ? (kern_t)rtw::features_kernel<T, true, true> : (kern_t)rtw::features_kernel<T, true, false>;
-    else kern = V.lds_scene ? (kern_t)rtw::features_kernel<T, false, true> : (kern_t)rtw::features_kernel<T, false, false>;
+    if (!tiled) {
+        if (mfma) kern = V.lds_scene ? (kern_t)rtw::features_kernel<T, true, true> : (kern_t)rtw::features_kernel<T, true, false>;
+        else kern = V.lds_scene ? (kern_t)rtw::features_kernel<T, false, true> : (kern_t)rtw::features_kernel<T, false, false>;
+    } else {
+        if (mfma) kern = V.lds_scene ? (kern_t)rtw::features_kernel<T, true, true, -1, true> : (kern_t)rtw::features_kernel<T, true, false, -1, true>;
+        else kern = V.lds_scene ? (kern_t)rtw::features_kernel<T, false, true, -1, true> : (kern_t)rtw::features_kernel<T, false, false, -1, true>;
+    }
     // the default numerics mode of the headline variant (scene in LDS, matrix pipe): the mode fixed at compile time
     const bool fixed = mfma && V.lds_scene && numerics == rtw::NUM_REFERENCE;
-    if (fixed) kern = (kern_t)rtw::features_kernel<T, true, true, rtw::NUM_REFERENCE>;
+    if (fixed) kern = tiled ? (kern_t)rtw::features_kernel<T, true, true, rtw::NUM_REFERENCE, true> : (kern_t)rtw::features_kernel<T, true, true, rtw::NUM_REFERENCE>;
     const unsigned grid = (K.n_tiles + RTW_FEATURE_WAVES - 1u) / RTW_FEATURE_WAVES;
     // (test aid: which instance the rules above picked, in the form of the trace kernel's line -- rtw_launch.hip; the grid is one workgroup
     //  per RTW_FEATURE_WAVES tiles, no occupancy question is asked: blocks_per_cu=0)
     static const bool debug = aid_env("RTW_DEBUG") != nullptr;
     if (debug)
-        fprintf(stderr, "[rtw debug] features instance: %s lds_scene=%d cull=0 mfma=%d fixed=%d batch=0 accum=0 adapt=0 lds_bytes=%zu blocks_per_cu=0\n", sizeof(T) == 8 ? "f64" : "f32",
-                (int)V.lds_scene, (int)mfma, (int)fixed, lds_bytes);
+        fprintf(stderr, "[rtw debug] features instance: %s lds_scene=%d cull=0 mfma=%d fixed=%d batch=0 accum=%d adapt=%d lds_bytes=%zu blocks_per_cu=0\n", sizeof(T) == 8 ? "f64" : "f32",
+                (int)V.lds_scene, (int)mfma, (int)fixed, (int)tiled, (int)tiled, lds_bytes);
 
     if (int rc = begin_record(ctx.get(), scene, nch, (int)grid, 64 * RTW_FEATURE_WAVES, offsetof(rtw::DevCounters, t_first), stream, rec_out)) return rc;
-    return run_record(*rec_out, stream, [&] { hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * RTW_FEATURE_WAVES), lds_bytes, stream, K, C, V.scene, (T *)d_out, (*rec_out)->ctr); });
+    return run_record(*rec_out, stream, [&] { hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * RTW_FEATURE_WAVES), lds_bytes, stream, K, C, V.scene, (T *)d_out, (*rec_out)->ctr, d_tile_chunks); });
 }
 
 int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream,
-                        RenderRec **rec_out, CtxPtr *ctx_out) {
-    return launch_features<float>(scene, cam, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out);
+                        RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks) {
+    return launch_features<float>(scene, cam, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks);
 }
 int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream,
-                        RenderRec **rec_out, CtxPtr *ctx_out) {
-    return launch_features<double>(scene, cam, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out);
+                        RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks) {
+    return launch_features<double>(scene, cam, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks);
 }
 
 template <typename CamT>

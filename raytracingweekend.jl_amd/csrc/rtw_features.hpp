@@ -62,9 +62,11 @@ template <> __device__ __forceinline__ void feat_store8<double>(double *o, const
 // MFMA: hit_world_mfma over the plain scan's own sphere order (scene.orig: ties by the caller's index); otherwise hit_world over the
 // caller's order.  Either way `scene`'s geom / mat0 / mat1 are the arrays the scan's index refers to.
 // NUMK >= 0: the numerics mode fixed at compile time (the default mode of the headline variant), NUMK < 0: the mode of the arguments.
-template <typename T, bool MFMA, bool LDS_SCENE, int NUMK = -1>
+// TILED: the pass over what an adaptive accumulator holds (rtw_accum_features_*): the wave's tile t gets the chunks [0, C_t) with C_t =
+// tile_chunks[t] (the accumulator's device array, >= 1), read once and made wave-uniform; P.chunk_begin / chunk_count are not looked at.
+template <typename T, bool MFMA, bool LDS_SCENE, int NUMK = -1, bool TILED = false>
 __global__ __launch_bounds__(64 * RTW_FEATURE_WAVES, (FeatWaves<T>::value)) void features_kernel(FeatParams P, Camera<T> cam_arg, DevScene<T> scene,
-                                                                                             T *__restrict__ out, DevCounters *ctr) {
+                                                                                             T *__restrict__ out, DevCounters *ctr, const int *__restrict__ tile_chunks) {
     using V4 = typename Vec4<T>::type;
     if constexpr (NUMK >= 0) scene.numerics = NUMK;
     const unsigned lane = lane_id(), wv = threadIdx.x >> 6;
@@ -98,6 +100,9 @@ __global__ __launch_bounds__(64 * RTW_FEATURE_WAVES, (FeatWaves<T>::value)) void
     const T u0 = (T)((double)(j0 + 1) / (double)P.width);                               // T(j / W),       src/render.jl:26
     const T v0 = (T)((double)(P.height - (i0 + 1)) / (double)P.height);                 // T((H - i) / H), src/render.jl:27
 
+    int chunk_begin = P.chunk_begin, chunk_count = P.chunk_count;
+    if constexpr (TILED) { chunk_begin = 0; chunk_count = __builtin_amdgcn_readfirstlane(tile_chunks[tile]); }
+
     unsigned long long lo[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hi[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned poison = 0;
     auto add = [&](int k, double v) {
@@ -106,8 +111,8 @@ __global__ __launch_bounds__(64 * RTW_FEATURE_WAVES, (FeatWaves<T>::value)) void
         else poison += 1u;
     };
 #pragma unroll 1
-    for (int c = 0; c < P.chunk_count; ++c) {
-        const unsigned chunk = (unsigned)(P.chunk_begin + c);
+    for (int c = 0; c < chunk_count; ++c) {
+        const unsigned chunk = (unsigned)(chunk_begin + c);
         Rng rng;
         rng_stream(P.seed, pix, chunk, rng);
         T du = 0, dv = 0;
@@ -158,12 +163,12 @@ __global__ __launch_bounds__(64 * RTW_FEATURE_WAVES, (FeatWaves<T>::value)) void
         for (int k = 0; k < 8; ++k) {
             double v = fx_to_double(lo[k], hi[k]);
             if (poison != 0u) v = __builtin_nan("");
-            r[k] = (T)(v / (double)P.chunk_count);
+            r[k] = (T)(v / (double)chunk_count);
         }
         feat_store8<T>(out + pix * 8u, r);
     }
     // what rtw_stats() reports: one scan per pixel inside the frame and chunk (two adds per wave)
-    const unsigned long long n = (unsigned long long)__popcll(__ballot(valid)) * (unsigned long long)P.chunk_count;
+    const unsigned long long n = (unsigned long long)__popcll(__ballot(valid)) * (unsigned long long)chunk_count;
     if (lane == 0) {
         atomicAdd(&ctr->segments, n);
         atomicAdd(&ctr->samples, n);

@@ -263,21 +263,42 @@ int launch_untile(bool f64, const void *gather, void *frame, int W, int H, long 
 // rtw_accum.hip: the unit ops 21-23 (include/rtw_hip.h rtw_unit_f64): the tile check, the compactions and the per-tile resolve on the
 // caller's words, through the launch helpers the adaptive loop itself uses
 int accum_unit(int op, bool f64, int count, const void *in, void *out);
+// rtw_accum.hip: an accumulator as the denoiser's input -- what rtw_accum_features_* / rtw_accum_noise_* run and what rtw_accum_filtered_*
+// (rtw_render_host.hip) strings together.  validate_*: every refusal, before any HIP call; enqueue_*: wait for the accumulator's event,
+// launch on `stream`, record the event (everything reads the words and C_t only).
+int validate_accum_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, rtw_accum_handle a);
+int validate_accum_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, rtw_accum_handle a);
+int enqueue_accum_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, rtw_accum_handle a, void *d_out, hipStream_t stream, RenderRec **rec, CtxPtr *ctx);
+int enqueue_accum_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, rtw_accum_handle a, void *d_out, hipStream_t stream, RenderRec **rec, CtxPtr *ctx);
+inline int validate_accum_features_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, rtw_accum_handle a) { return validate_accum_features_f32(s, c, p, a); }
+inline int validate_accum_features_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, rtw_accum_handle a) { return validate_accum_features_f64(s, c, p, a); }
+inline int enqueue_accum_features_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, rtw_accum_handle a, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return enqueue_accum_features_f32(s, c, p, a, d, st, r, x); }
+inline int enqueue_accum_features_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, rtw_accum_handle a, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return enqueue_accum_features_f64(s, c, p, a, d, st, r, x); }
+int accum_device_of(rtw_accum_handle a);
+bool accum_is_adaptive(rtw_accum_handle a);
+int validate_accum_noise(rtw_accum_handle a, bool f64);                                             // adaptive, its last call finished, the call's precision
+int enqueue_accum_noise(rtw_accum_handle a, bool f64, void *d_out, hipStream_t stream);               // H*W elements of T
+int enqueue_accum_resolve(rtw_accum_handle a, bool f64, int32_t gamma, void *d_out, hipStream_t stream);   // rtw_accum_resolve_*'s own path
+int accum_filtered_host_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle a, int32_t guided, float *out);    // rtw_render_host.hip
+int accum_filtered_host_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle a, int32_t guided, double *out);
 
 // rtw_features.hip -- first-hit feature buffers (include/rtw_hip.h rtw_render_features_*).  validate_features: the checks that need no device
 // (the render, whole frames on one device, the chunk range); launch_features: enqueue the feature kernel for the chunks [chunk_begin,
 // chunk_begin + chunk_count) on `stream`, `rec` receives the counters and the kernel's events like a render's.
 int validate_features(const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, int *n_chunks, int *chunk_spp);
-int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
-int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
-inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_features_f32(s, c, p, b, n, d, st, r, x); }
-inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_features_f64(s, c, p, b, n, d, st, r, x); }
+// d_tile_chunks non-null: the pass over what an adaptive accumulator holds -- tile t gets the chunks [0, d_tile_chunks[t]) (device memory, the
+// accumulator's C_t array), the call's own range is validated and otherwise unused.
+int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks = nullptr);
+int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks = nullptr);
+inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const int *tc = nullptr) { return launch_features_f32(s, c, p, b, n, d, st, r, x, tc); }
+inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const int *tc = nullptr) { return launch_features_f64(s, c, p, b, n, d, st, r, x, tc); }
 
 // rtw_denoise.hip -- the feature-guided denoiser (include/rtw_hip.h rtw_denoise_*).  validate_denoise: the checks that need no device;
 // launch_denoise: enqueue its kernels on `stream` of the current device (d_work: rtw_denoise_work_bytes bytes, 16-byte aligned).
 int validate_denoise(const rtw_denoise_t *d, int32_t width, int32_t height);
-int launch_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream);
-int launch_denoise_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream);
+// d_noise non-null: the noise-guided form (rtw_guided_filter_device_*): H*W elements of T, the per-pixel relative noise.
+int launch_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream, const void *d_noise = nullptr);
+int launch_denoise_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream, const void *d_noise = nullptr);
 // rtw_render_host.hip: its host-buffer entry points
 int denoise_host_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const float *image, const float *features, float *out);
 int denoise_host_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const double *image, const double *features, double *out);

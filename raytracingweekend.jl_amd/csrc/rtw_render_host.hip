@@ -335,8 +335,8 @@ int render_host_features(const SceneT *scene, const CamT *cam, const rtw_params 
     });
 }
 
-inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, const float *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_denoise_f32(d, w, h, img, feat, out, work, st); }
-inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, const double *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_denoise_f64(d, w, h, img, feat, out, work, st); }
+inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, const float *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise = nullptr) { return launch_denoise_f32(d, w, h, img, feat, out, work, st, noise); }
+inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, const double *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise = nullptr) { return launch_denoise_f64(d, w, h, img, feat, out, work, st, noise); }
 
 // The denoiser's regions inside a context's device buffer: image, features, output, workspace -- each starts on a 16-byte boundary.
 template <typename T> struct DenoiseRegions {
@@ -413,6 +413,52 @@ int render_host_denoised(const SceneT *scene, const CamT *cam, const rtw_params 
     if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
     g_last.resolved = rc == 0;
     return rc;
+}
+
+// What an accumulator holds, denoised (rtw_accum_filtered_f32/_f64): the gamma-0 resolve (per tile for an adaptive accumulator), the feature
+// pass over exactly the samples it holds, with `guided` its noise map and the noise-guided filter (else the plain one), all on the
+// accumulator's device in a leased context's buffer and stream, ONE D2H.  The accumulator is only read; every step orders itself behind
+// its event.  rtw_stats() reports the feature pass's record.
+template <typename T, typename CamT>
+int accum_filtered_host(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle a, int32_t guided, T *out) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !cam || !d || !a || !out) return fail(-1, "null argument");
+    if (guided != 0 && guided != 1) return fail(-2, "guided must be 0 or 1 (got %d)", guided);
+    int nch, cs;                                                   // (the render's and the filter's own checks before a handle is looked at)
+    if (int rc = validate_features(p, 0, 1, &nch, &cs)) return rc;
+    if (int rc = validate_denoise(d, p->width, p->height)) return rc;
+    if (int rc = validate_accum_features_t(scene, cam, p, a)) return rc;
+    if (guided) if (int rc = validate_accum_noise(a, sizeof(T) == 8)) return rc;
+    DeviceGuard guard;
+    release_last();
+    HostLease L;
+    if (int rc = acquire_host(accum_device_of(a), std::vector<unsigned char>(), &L)) return rc;
+    HostCtx *hc = L.hc;
+    const DenoiseRegions<T> R(p->width, p->height);
+    const size_t off_noise = (R.total + 15) & ~(size_t)15;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, off_noise + (size_t)p->width * (size_t)p->height * sizeof(T))) return rc;
+    char *base = (char *)hc->d_img;
+    rtw_denoise_t dd = *d;
+    dd.gamma = p->gamma != 0; dd.device = hc->device;
+    RenderRec *frec = nullptr;
+    CtxPtr fctx;
+    int rc = enqueue_accum_resolve(a, sizeof(T) == 8, 0, base, hc->stream);
+    if (!rc) rc = enqueue_accum_features_t(scene, cam, p, a, base + R.off_feat, hc->stream, &frec, &fctx);
+    if (!rc && guided) rc = enqueue_accum_noise(a, sizeof(T) == 8, base + off_noise, hc->stream);
+    if (!rc) rc = launch_denoise_t(&dd, p->width, p->height, (const T *)base, base + R.off_feat, base + R.off_out, base + R.off_work, hc->stream, guided ? base + off_noise : nullptr);
+    if (!rc) rc = copy_out(hc, base + R.off_out, out, R.img_b);
+    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    if (!rc) rc = resolve_rec(frec, &g_last.agg);
+    if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
+    if (frec) release_rec(fctx, frec, rc == 0);
+    g_last.resolved = rc == 0;
+    return rc;
+}
+int accum_filtered_host_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle a, int32_t guided, float *out) {
+    return accum_filtered_host<float>(scene, cam, p, d, a, guided, out);
+}
+int accum_filtered_host_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle a, int32_t guided, double *out) {
+    return accum_filtered_host<double>(scene, cam, p, d, a, guided, out);
 }
 
 int denoise_host_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const float *image, const float *features, float *out) { return denoise_host<float>(d, width, height, image, features, out); }

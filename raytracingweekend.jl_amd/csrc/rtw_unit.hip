@@ -8,9 +8,9 @@ namespace rtwh {
 template <typename T, typename SceneT, typename CamT>
 int run_unit(int op_arg, int count, const void *in, void *out, const SceneT *scene, const CamT *cam) {
     const int op = op_arg & 0xff, numerics = (op_arg >> 8) & 3;      // bits 8-9: the numerics mode of the ray-sphere test
-    if (op_arg < 0 || (op_arg >> 10) != 0 || op >= rtw::U_NUM_OPS) return fail(-2, "unknown unit op %d", op_arg);
+    if (op_arg < 0 || (op_arg >> 10) != 0 || op >= rtw::U_NUM_OPS || op == 24) return fail(-2, "unknown unit op %d", op_arg);
     if (numerics == 2) return fail(-2, "unknown numerics mode %d (unit op %d)", numerics, op_arg);
-    if (rtw::unit_is_accum(op)) return accum_unit(op, sizeof(T) == 8, count, in, out);      // (ops 21-23: layouts of their own, no scene, no numerics mode)
+    if (rtw::unit_is_accum(op)) return accum_unit(op, sizeof(T) == 8, count, in, out);      // (ops 21-23 and 25: layouts of their own, no scene, no numerics mode)
     if (count < 0 || (count > 0 && (!in || !out))) return fail(-1, "null argument");
     if (count == 0) return 0;
     const bool sink = rtw::unit_is_sink(op);

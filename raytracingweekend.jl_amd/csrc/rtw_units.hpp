@@ -22,9 +22,11 @@ enum UnitOp {
     // the accumulator's tile kernels on hand-made words (rtw_accum.hip accum_unit; whole-call layouts, not per item: include/rtw_hip.h): the
     // stopping rule's two check kernels, the two compactions, the per-tile resolve.  rtw_unit.hip hands them over before its per-item path.
     U_ACCUM_TILE_CHECK = 21, U_ACCUM_COMPACT = 22, U_ACCUM_RESOLVE_TILES = 23,
-    U_NUM_OPS = 24
+    // (24 is not an op: callers probe it as the first unknown number)
+    U_ACCUM_NOISE = 25,      // the noise map kernel of an adaptive accumulator on hand-made words and C_t (rtw_accum.hip accum_unit)
+    U_NUM_OPS = 26
 };
-__host__ __device__ inline bool unit_is_accum(int op) { return op >= U_ACCUM_TILE_CHECK && op <= U_ACCUM_RESOLVE_TILES; }
+__host__ __device__ inline bool unit_is_accum(int op) { return (op >= U_ACCUM_TILE_CHECK && op <= U_ACCUM_RESOLVE_TILES) || op == U_ACCUM_NOISE; }
 __host__ __device__ inline bool unit_is_sink(int op) { return op >= U_SINK_LDS && op <= U_SINK_MFMA_CULL; }
 #define RTW_SINK_SPHERES 512
 #define RTW_SINK_SLOTS 18

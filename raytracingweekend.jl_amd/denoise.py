@@ -15,6 +15,11 @@ from .render import _tls as _render_tls
 from .structs import Camera, flatten_scene, image_height
 
 
+#: Default ``sigma_color`` of the noise-guided form (``AdaptiveRenderer.denoised``, ``denoise_guided_into``): there it counts estimated
+#: standard deviations of the pixel.  Measured on the CPU witness (the power of two with the lowest MSE).
+GUIDED_SIGMA_COLOR = 1.0
+
+
 def make_denoise(levels=3, normal_power_log2=1, sigma_color=0.5, sigma_depth=0.1, demodulate=True, gamma=True, device=-1):
     """-> the ``rtw_denoise_t`` of these keywords"""
     flags = _capi.DENOISE_DEMODULATE if demodulate else 0
@@ -67,6 +72,21 @@ def denoise_into(d_out_ptr, d_image_ptr, d_features_ptr, d_work_ptr, image_width
     fn = L.rtw_denoise_device_f64 if _capi.is_f64(elem_type) else L.rtw_denoise_device_f32
     _capi.check(fn(C.byref(D), int(image_width), int(image_height), C.c_void_p(int(d_image_ptr)), C.c_void_p(int(d_features_ptr)),
                    C.c_void_p(int(d_out_ptr)), C.c_void_p(int(d_work_ptr)), C.c_void_p(int(stream))))
+
+
+def denoise_guided_into(d_out_ptr, d_image_ptr, d_features_ptr, d_noise_ptr, d_work_ptr, image_width, image_height, *, elem_type=np.float32,
+                        stream=0, work_bytes=None, **params):
+    """The noise-guided device form (rtw_guided_filter_device_*): ``denoise_into`` with one more input, ``d_noise_ptr``: H*W elements,
+    the per-pixel relative noise (``AdaptiveRenderer.noise_into``).  ``sigma_color`` defaults to ``GUIDED_SIGMA_COLOR``."""
+    need = denoise_work_bytes(image_width, image_height, elem_type)
+    if work_bytes is not None and int(work_bytes) < need:
+        raise ValueError(f"workspace holds {work_bytes} bytes, the denoiser needs {need}")
+    params.setdefault("sigma_color", GUIDED_SIGMA_COLOR)
+    D = make_denoise(**params)
+    L = _capi.lib()
+    fn = L.rtw_guided_filter_device_f64 if _capi.is_f64(elem_type) else L.rtw_guided_filter_device_f32
+    _capi.check(fn(C.byref(D), int(image_width), int(image_height), C.c_void_p(int(d_image_ptr)), C.c_void_p(int(d_features_ptr)),
+                   C.c_void_p(int(d_noise_ptr)), C.c_void_p(int(d_out_ptr)), C.c_void_p(int(d_work_ptr)), C.c_void_p(int(stream))))
 
 
 def render_denoised(scene, cam, image_width=400, n_samples=1, *, depth=16, seed=1, n_chunks=0, device=-1, gamma=True, group_cull=False,

@@ -132,6 +132,52 @@ class ProgressiveRenderer:
         _capi.check(self.L.rtw_accum_read_pixels(self.accum, out.ctypes.data_as(C.c_void_p)))
         return out.reshape(self.width, self.height, 8).transpose(1, 0, 2)
 
+    # ---- the accumulator as the denoiser's input (include/rtw_hip.h rtw_accum_features_*, rtw_accum_filtered_*) ----
+    def _render_params(self, gamma=True, group_cull=False, scan_valu=False, job_pixels=0):
+        flags = (_capi.FLAG_GROUP_CULL if group_cull else 0) | (_capi.FLAG_SCAN_VALU if scan_valu else 0)
+        return _capi.make_params(self.width, self.height, self.n_samples, self.depth, self.seed, self._n_chunks_arg, 0, 1, -1,
+                                 1 if gamma else 0, flags, job_pixels=job_pixels, numerics=self.numerics)
+
+    def _device_buffer(self, n_elems):
+        """a torch tensor on the accumulator's device (torch is the package's plumbing for device memory; it must have initialised
+        the GPU before the library did)"""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("torch sees no GPU: a host copy of a device-resident result needs torch for its device buffer")
+        dev = self.info()["device"]
+        return torch.empty(int(n_elems), dtype=torch.float64 if _capi.is_f64(self.T) else torch.float32, device=f"cuda:{dev}")
+
+    def features_into(self, d_out_ptr, *, scan_valu=False, group_cull=False, job_pixels=0, stream=0):
+        """Enqueue the feature pass over exactly the samples the accumulator holds (rtw_accum_features_*) into device memory at
+        ``d_out_ptr``: H*W*8 elements, 16-byte aligned, the layout of ``features_into``.  A uniform accumulator must hold ONE chunk
+        interval; an adaptive one gets, per tile, the features of the chunks ``[0, C_t)``."""
+        P = self._render_params(True, group_cull, scan_valu, job_pixels)
+        fn = self.L.rtw_accum_features_f64 if _capi.is_f64(self.T) else self.L.rtw_accum_features_f32
+        _capi.check(fn(self.handle, C.byref(self.cam), C.byref(P), self.accum, C.c_void_p(int(d_out_ptr)), C.c_void_p(int(stream))))
+
+    def features(self, **kw):
+        """The first-hit features of the samples added so far (blocking): the dict of ``render_features``."""
+        import torch
+        from .features import FEATURE_CHANNELS, split
+        buf = self._device_buffer(self.height * self.width * FEATURE_CHANNELS)
+        self.features_into(buf.data_ptr(), stream=torch.cuda.current_stream(buf.device).cuda_stream, **kw)
+        raw = buf.cpu().numpy()
+        return split(raw.reshape(self.width, self.height, FEATURE_CHANNELS).transpose(1, 0, 2))
+
+    def _filtered(self, guided, gamma, kw):
+        from .denoise import make_denoise
+        D = make_denoise(gamma=gamma, **kw)
+        P = self._render_params(gamma)
+        out = np.empty(self.height * self.width * 3, dtype=self.T)
+        fn = self.L.rtw_accum_filtered_f64 if _capi.is_f64(self.T) else self.L.rtw_accum_filtered_f32
+        _capi.check(fn(self.handle, C.byref(self.cam), C.byref(P), C.byref(D), self.accum, 1 if guided else 0, out.ctypes.data_as(C.c_void_p)))
+        return _as_image(out, self.height, self.width)
+
+    def denoised(self, gamma=True, **params):
+        """The image of the samples added so far, filtered with the features of exactly those samples (rtw_accum_filtered_*, blocking):
+        resolve, feature pass and filter stay on the device, the result comes back once.  Keywords: ``make_denoise``."""
+        return self._filtered(False, gamma, params)
+
     def info(self):
         st = _capi.AccumInfo()
         _capi.check(self.L.rtw_accum_info(self.accum, C.byref(st)))
@@ -298,6 +344,20 @@ class ProgressiveBatchRenderer:
         st = _capi.AccumInfo()
         _capi.check(self.L.rtw_accum_info(self.accums[v], C.byref(st)))
         return {k: getattr(st, k) for k, _ in st._fields_}
+
+    def _filtered(self, v, guided, gamma, kw):
+        from .denoise import make_denoise
+        D = make_denoise(gamma=gamma, **kw)
+        P = self._params(False, False, 0, gamma)
+        P.seed = int(self.seeds[v])
+        out = np.empty(self.height * self.width * 3, dtype=self.T)
+        fn = self.L.rtw_accum_filtered_f64 if _capi.is_f64(self.T) else self.L.rtw_accum_filtered_f32
+        _capi.check(fn(self.handle, C.byref(self.cams[v]), C.byref(P), C.byref(D), self.accums[v], 1 if guided else 0, out.ctypes.data_as(C.c_void_p)))
+        return _as_image(out, self.height, self.width)
+
+    def denoised(self, v, gamma=True, **params):
+        """View ``v``'s image so far, filtered with the features of exactly the samples it holds (``ProgressiveRenderer.denoised``)."""
+        return self._filtered(v, False, gamma, params)
 
     def ranges(self, v):
         """the chunk ranges view ``v`` holds: sorted list of ``(begin, end)``, end exclusive"""
