@@ -427,7 +427,8 @@ int rtw_render_adaptive_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *
  * rtw_params -- sizes, unknown flags, both numerics bits, job_pixels -> -2; chunk_begin < 0, chunk_count < 1 or a range beyond N -> -2;
  * shard_count != 1, RTW_FLAG_COMPACT_TILES, RTW_FLAG_RCCL_REDUCE, RTW_FLAG_RAY_POOL, n_devices > 1 or device_ids -> -2; a d_out that is not
  * 16-byte aligned -> -2; a frame of 2^31 tiles or more -> -5.  Then: a scene handle of the other precision, or on another device than
- * p->device names -> -4.  Batched views, feature sums in accumulators and device lists are out of scope; the
+ * p->device names -> -4.  Feature sums in accumulators and device lists are out of scope; N views in one launch:
+ * rtw_render_features_batch_* below; the
  * per-tile chunk prefixes of an adaptive accumulator: rtw_accum_features_* below.  Additive to ABI 4: detected by symbol lookup. */
 #define RTW_FEATURE_CHANNELS 8
 int rtw_render_features_device_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p,
@@ -480,7 +481,7 @@ int rtw_render_features_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *ca
  * bits, gamma other than 0 or 1, reserved != 0, device < -1, a sigma that is not finite and positive, width or height < 1, misaligned or
  * aliasing pointers, elem_bytes other than 4 or 8 -> -2; a frame of 2^31 8x8 tiles or more -> -5; the render-and-denoise call additionally
  * refuses everything a feature render of `p` refuses.  Temporal reuse across the views of a batch, compact or sharded frames and device
- * lists are out of scope; noise-guided weights and accumulators as the input: the block behind these declarations.
+ * lists are out of scope; N frames in each launch: rtw_filter_batch_* below; noise-guided weights and accumulators as the input: the block behind these declarations.
  * Additive to ABI 4: detected by symbol lookup. */
 #define RTW_DENOISE_DEMODULATE 1   /* filter image / albedo, multiply back at the end */
 typedef struct {
@@ -554,7 +555,7 @@ int rtw_render_denoised_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *ca
  * replaced by p->gamma and d->device by the accumulator's device; the result is copied to `out` once.  rtw_stats() afterwards reports
  * the feature pass's record.  Refusals, before any HIP call: nulls -> -1; guided other than 0 / 1 -> -2; everything rtw_accum_features_*
  * and the filter's own checks refuse; guided = 1 on a uniform accumulator -> -2.
- *   Out of scope: batched launches of these passes, temporal reuse across views, device lists, compact or sharded
+ *   Out of scope: batched launches of the passes over accumulators, temporal reuse across views, device lists, compact or sharded
  * frames.  Additive to ABI 4: detected by symbol lookup. */
 int rtw_accum_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, rtw_accum_handle accum, void *d_out, void *hip_stream);
 int rtw_accum_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, rtw_accum_handle accum, void *d_out, void *hip_stream);
@@ -568,6 +569,55 @@ int rtw_accum_filtered_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, co
                            float *out);
 int rtw_accum_filtered_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle accum, int32_t guided,
                            double *out);
+
+/* Batched feature and filter passes: N views of one scene, of one size, in each launch -- what rtw_render_batch_* is to the render.  A
+ * turntable of N previews is then 2 + 1 + levels launches (render: views' upload + kernel; feature pass; prepare + levels) for any N,
+ * instead of N times 2 + levels behind the one batched render.  No new arithmetic is defined:
+ *   View v of a batched feature call is, bit for bit, rtw_render_features_* with cams[v] and seeds[v] (`seeds` == NULL: p->seed for every
+ * view), in every scan mode, numerics mode and precision; view v writes W*H*8 elements at out + v*W*H*8.
+ *   View v of a batched filter call is, bit for bit, the single-frame filter above (device or host form) on (image v, features v): images
+ * and results hold the views one behind the other, view v at v*W*H*3 elements, the features at v*W*H*8; no tap ever reads another view.
+ *   View v of rtw_render_filtered_batch_* is the render-and-denoise call above with cams[v] / seeds[v].
+ *
+ * rtw_render_features_batch_device_*: ONE launch; `d_out` is a DEVICE pointer, 16-byte aligned, to n_views*height*width*8 elements;
+ * asynchronous like the single-view device form, the same render records: rtw_stats() afterwards reports samples = segments =
+ * n_views*W*H*chunk_count, sphere_tests = segments * n, n_chunks = N, ONE kernel time.  rtw_render_features_batch_*: HOST buffers, blocking,
+ * the cached per-device context of rtw_render_f32, one D2H.
+ *   rtw_filter_batch_device_*: prepare + `levels` launches for all views, asynchronous on `hip_stream` of d->device.  The caller owns
+ * `d_work`: n_views times the bytes the work-bytes call above returns for ONE frame, 16-byte aligned; its four planes (E, E', G, A) are
+ * batch-major -- each holds n_views*W*H slots of 4 elements, view v at slot offset v*W*H --, so it is NOT n_views single-frame workspaces
+ * side by side.  Alignment and aliasing rules are those of the single-frame device form, applied to the whole batch's extents.
+ * rtw_filter_batch_*: HOST buffers, blocking, a leased context like the single-frame host form.  Neither changes what rtw_stats() reports.
+ *   rtw_render_filtered_batch_*: the batched render of `p` with gamma = 0, the batched feature pass over all N effective chunks and the
+ * batched filter with d->gamma replaced by p->gamma (d->device by p->device), in one device buffer on the cached context's stream; `out`
+ * (HOST, n_views*height*width*3 elements) is written by one D2H; rtw_stats() afterwards reports the render's record.
+ *   Refusals, all before any HIP call and before a handle is looked at.  Feature calls: the rules of rtw_render_batch_* together with
+ * those of the feature pass -- null scene / cams / p / output -> -1; n_views < 1 -> -2; everything either refuses for `p`, the chunk range,
+ * a misaligned d_out -> -2; a batch whose jobs the render's queues cannot number (which bounds the tiles of the feature launch too) -> -5.
+ * Filter calls: nulls -> -1; everything the single-frame filter refuses, n_views < 1 -> -2; a batch of 2^39 pixels or more -> -5.
+ * rtw_render_filtered_batch_*: both sets.  Then: a scene handle of the other precision -> -4.
+ *   Out of scope: accumulators as the input of a batch (the tiled feature pass, the noise-guided filter,
+ * rtw_accum_*), device lists, temporal reuse across the views.  Additive to ABI 4: detected by symbol lookup. */
+int rtw_render_features_batch_device_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds,
+                                         const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, void *hip_stream);
+int rtw_render_features_batch_device_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds,
+                                         const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, void *hip_stream);
+int rtw_render_features_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds,
+                                  const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, float *out);
+int rtw_render_features_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds,
+                                  const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, double *out);
+int rtw_filter_batch_device_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_images,
+                                const void *d_features, void *d_out, void *d_work, void *hip_stream);
+int rtw_filter_batch_device_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_images,
+                                const void *d_features, void *d_out, void *d_work, void *hip_stream);
+int rtw_filter_batch_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const float *images, const float *features,
+                         float *out);
+int rtw_filter_batch_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const double *images, const double *features,
+                         double *out);
+int rtw_render_filtered_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds,
+                                  const rtw_params *p, const rtw_denoise_t *d, float *out);
+int rtw_render_filtered_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds,
+                                  const rtw_params *p, const rtw_denoise_t *d, double *out);
 
 /* Counters/timings of the last render issued from this thread (waits for it to finish). */
 int rtw_stats(rtw_stats_t *out);

@@ -1,6 +1,6 @@
 // rtw_denoise.hip -- the feature-guided denoiser (include/rtw_hip.h rtw_denoise_*): the checks that need no device, the launch sequence of
 // its kernels (rtw_denoise.hpp: prepare, then the level kernel once per a-trous pass, the last one writing the image) and the device-resident
-// entry points.  (The host-buffer entry points and rtw_render_denoised_* live with the other cached-context paths in rtw_render_host.hip.)
+// entry points; rtw_filter_batch_*: the same sequence once for N frames (the batched level kernel).  (The host-buffer entry points and rtw_render_denoised_* live with the other cached-context paths in rtw_render_host.hip.)
 #include "rtw_host.hpp"
 #include "rtw_denoise.hpp"
 
@@ -33,13 +33,18 @@ static bool overlap(const void *a, long long na, const void *b, long long nb) {
 
 // Enqueue the denoiser on `stream` of the current device (validate_denoise has accepted the call).  d_noise non-null: the noise-guided
 // form -- the GUIDED instances of both kernels, the same launch sequence and workspace (the variance lives in the A plane's fourth slot).
+// n_views >= 1 (rtw_filter_batch_*; plain form only, validate_filter_batch has accepted it): the same sequence ONCE for n_views frames --
+// every buffer and every plane of the workspace holds the views one behind the other, so prepare (which looks at its own pixel only) runs
+// over all N*W*H pixels and the level kernel is the batched one, which bounds the taps by each view's own frame.  n_views == 0: one frame.
 template <typename T>
-int launch_denoise(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream,
+int launch_denoise(const rtw_denoise_t *d, int32_t width, int32_t height, int n_views, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream,
                    const void *d_noise) {
     using V = typename rtw::DnVec<T>::type;
-    const long long n_pix = (long long)width * height;
+    const bool batch = n_views > 0;
+    if (batch && d_noise) return fail(-9, "internal: the noise-guided filter has no batched form");
+    const long long n_pix = (long long)width * height * (batch ? n_views : 1);
     char *w = (char *)d_work;
-    const long long pb = plane_bytes(width, height, sizeof(T));
+    const long long pb = plane_bytes(width, height, sizeof(T)) * (batch ? n_views : 1);
     V *E[2] = {(V *)w, (V *)(w + pb)};
     V *G = (V *)(w + 2 * pb), *A = (V *)(w + 3 * pb);
     const bool demod = (d->flags & RTW_DENOISE_DEMODULATE) != 0;
@@ -66,40 +71,59 @@ int launch_denoise(const rtw_denoise_t *d, int32_t width, int32_t height, const 
         L.W = width; L.H = height;
         const V *in = E[k & 1];
         V *next = E[(k & 1) ^ 1];
-        if (guided) hipLaunchKernelGGL((rtw::dn_level<T, true>), dim3(grid), dim3(256), 0, stream, L, in, (const V *)G, (const V *)A, next, (T *)d_out);
+        if (batch) {
+            rtw::DnLevelBatch<T> LB;
+            LB.L = L; LB.n_all = n_pix;
+            hipLaunchKernelGGL((rtw::dn_level_batch<T>), dim3(grid), dim3(256), 0, stream, LB, in, (const V *)G, (const V *)A, next, (T *)d_out);
+        } else if (guided) hipLaunchKernelGGL((rtw::dn_level<T, true>), dim3(grid), dim3(256), 0, stream, L, in, (const V *)G, (const V *)A, next, (T *)d_out);
         else hipLaunchKernelGGL((rtw::dn_level<T, false>), dim3(grid), dim3(256), 0, stream, L, in, (const V *)G, (const V *)A, next, (T *)d_out);
         HIP_TRY(hipGetLastError());
         if (profile) HIP_TRY(hipEventRecord(ev[k + 2], stream));
     }
     if (profile) {
         const char *tag = guided ? "rtw denoise guided" : "rtw denoise";       // (tools/gpu_accum_denoise.py tells the two forms apart by it)
+        char views[32] = "";                                                    // (a batched filter: " views=N" behind the frame's size)
+        if (batch) snprintf(views, sizeof views, " views=%d", n_views);
         HIP_TRY(hipEventSynchronize(ev[d->levels + 1]));
         for (int k = 0; k <= d->levels; ++k) {
             float ms = 0;
             HIP_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-            if (k == 0) fprintf(stderr, "[%s] %s %dx%d prepare ms=%.5f\n", tag, sizeof(T) == 8 ? "f64" : "f32", width, height, ms);
-            else fprintf(stderr, "[%s] %s %dx%d level step=%d final=%d ms=%.5f\n", tag, sizeof(T) == 8 ? "f64" : "f32", width, height, 1 << (k - 1),
+            if (k == 0) fprintf(stderr, "[%s] %s %dx%d%s prepare ms=%.5f\n", tag, sizeof(T) == 8 ? "f64" : "f32", width, height, views, ms);
+            else fprintf(stderr, "[%s] %s %dx%d%s level step=%d final=%d ms=%.5f\n", tag, sizeof(T) == 8 ? "f64" : "f32", width, height, views, 1 << (k - 1),
                          (int)(k == d->levels), ms);
         }
         float all_ms = 0;
         HIP_TRY(hipEventElapsedTime(&all_ms, ev[0], ev[d->levels + 1]));
-        fprintf(stderr, "[%s] %s %dx%d total levels=%d ms=%.5f\n", tag, sizeof(T) == 8 ? "f64" : "f32", width, height, d->levels, all_ms);
+        fprintf(stderr, "[%s] %s %dx%d%s total levels=%d ms=%.5f\n", tag, sizeof(T) == 8 ? "f64" : "f32", width, height, views, d->levels, all_ms);
     }
     return 0;
 }
 
-int launch_denoise_f32(const rtw_denoise_t *d, int32_t w, int32_t h, const void *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise) { return launch_denoise<float>(d, w, h, img, feat, out, work, st, noise); }
-int launch_denoise_f64(const rtw_denoise_t *d, int32_t w, int32_t h, const void *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise) { return launch_denoise<double>(d, w, h, img, feat, out, work, st, noise); }
+int launch_denoise_f32(const rtw_denoise_t *d, int32_t w, int32_t h, const void *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise) { return launch_denoise<float>(d, w, h, 0, img, feat, out, work, st, noise); }
+int launch_denoise_f64(const rtw_denoise_t *d, int32_t w, int32_t h, const void *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise) { return launch_denoise<double>(d, w, h, 0, img, feat, out, work, st, noise); }
+int launch_filter_batch_f32(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t n_views, const void *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_denoise<float>(d, w, h, n_views, img, feat, out, work, st, nullptr); }
+int launch_filter_batch_f64(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t n_views, const void *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_denoise<double>(d, w, h, n_views, img, feat, out, work, st, nullptr); }
+
+// A batched filter call (rtw_filter_batch_*): validate_denoise for the frame, and a batch whose pixels the launches can number (256 per workgroup)
+int validate_filter_batch(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views) {
+    if (int rc = validate_denoise(d, width, height)) return rc;
+    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
+    if ((double)width * (double)height * (double)n_views >= (double)(1ll << 39)) return fail(-5, "batch too large for one call: %d views of %d x %d pixels", n_views, width, height);
+    return 0;
+}
 
 // the device-resident entry points; `guided`: rtw_guided_filter_device_* (d_noise: H*W elements of T), else d_noise is null
+// `batch`: rtw_filter_batch_device_* (not guided) -- n_views frames; the alignment and aliasing checks cover the whole batch's extents
 template <typename T>
-int denoise_device(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_noise, bool guided, void *d_out, void *d_work, void *stream_v) {
+int denoise_device(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_noise, bool guided, void *d_out, void *d_work, void *stream_v,
+                   bool batch = false, int32_t n_views = 0) {
     if (!d || !d_image || !d_features || !d_out || !d_work || (guided && !d_noise)) return fail(-1, "null argument");
-    if (int rc = validate_denoise(d, width, height)) return rc;
+    if (batch) { if (int rc = validate_filter_batch(d, width, height, n_views)) return rc; }
+    else if (int rc = validate_denoise(d, width, height)) return rc;
     if (((uintptr_t)d_work & 15u) || ((uintptr_t)d_features & 15u)) return fail(-2, "the workspace and the feature buffer must be 16-byte aligned");
     if (((uintptr_t)d_image & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
-    const long long n_pix = (long long)width * height, img_b = n_pix * 3 * (long long)sizeof(T), feat_b = n_pix * 8 * (long long)sizeof(T);
-    const long long work_b = 4 * plane_bytes(width, height, sizeof(T));
+    const long long n_pix = (long long)width * height * (batch ? n_views : 1), img_b = n_pix * 3 * (long long)sizeof(T), feat_b = n_pix * 8 * (long long)sizeof(T);
+    const long long work_b = 4 * plane_bytes(width, height, sizeof(T)) * (batch ? n_views : 1);
     if (overlap(d_out, img_b, d_image, img_b) || overlap(d_out, img_b, d_features, feat_b) || overlap(d_out, img_b, d_work, work_b))
         return fail(-2, "d_out may not alias an input or the workspace");
     if (overlap(d_work, work_b, d_image, img_b) || overlap(d_work, work_b, d_features, feat_b)) return fail(-2, "the workspace may not alias an input");
@@ -111,7 +135,7 @@ int denoise_device(const rtw_denoise_t *d, int32_t width, int32_t height, const 
     }
     DeviceGuard guard;
     if (d->device >= 0) HIP_TRY(hipSetDevice(d->device));
-    return launch_denoise<T>(d, width, height, d_image, d_features, d_out, d_work, (hipStream_t)stream_v, guided ? d_noise : nullptr);
+    return launch_denoise<T>(d, width, height, batch ? n_views : 0, d_image, d_features, d_out, d_work, (hipStream_t)stream_v, guided ? d_noise : nullptr);
 }
 
 }  // namespace rtwh
@@ -140,6 +164,28 @@ int rtw_guided_filter_device_f32(const rtw_denoise_t *d, int32_t width, int32_t 
 int rtw_guided_filter_device_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_noise, void *d_out, void *d_work,
                                  void *hip_stream) {
     return denoise_device<double>(d, width, height, d_image, d_features, d_noise, true, d_out, d_work, hip_stream);
+}
+int rtw_filter_batch_device_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_images, const void *d_features, void *d_out, void *d_work,
+                                void *hip_stream) {
+    return denoise_device<float>(d, width, height, d_images, d_features, nullptr, false, d_out, d_work, hip_stream, true, n_views);
+}
+int rtw_filter_batch_device_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_images, const void *d_features, void *d_out, void *d_work,
+                                void *hip_stream) {
+    return denoise_device<double>(d, width, height, d_images, d_features, nullptr, false, d_out, d_work, hip_stream, true, n_views);
+}
+int rtw_filter_batch_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const float *images, const float *features, float *out) {
+    return filter_batch_host_f32(d, width, height, n_views, images, features, out);
+}
+int rtw_filter_batch_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const double *images, const double *features, double *out) {
+    return filter_batch_host_f64(d, width, height, n_views, images, features, out);
+}
+int rtw_render_filtered_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d,
+                                  float *out) {
+    return render_host_filtered_batch_f32(scene, cams, n_views, seeds, p, d, out);
+}
+int rtw_render_filtered_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d,
+                                  double *out) {
+    return render_host_filtered_batch_f64(scene, cams, n_views, seeds, p, d, out);
 }
 int rtw_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const float *image, const float *features, float *out) {
     return denoise_host_f32(d, width, height, image, features, out);

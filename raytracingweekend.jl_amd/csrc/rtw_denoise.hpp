@@ -11,6 +11,11 @@
 //                  pixel whose entry is not finite as not valid and stores the pixel's colour variance v in A.w (the slot the plain form
 //                  leaves 0); the level kernel divides a tap's colour distance by the CENTRE pixel's v.  Nothing else differs, and the
 //                  instances with GUIDED = false are the plain form's code.
+//   BATCH          N frames of one size in each launch (include/rtw_hip.h rtw_filter_batch_*), plain form only: every plane holds N*W*H slots,
+//                  view v at slot offset v*W*H; the image and the result at v*W*H*3 elements, the features at v*W*H*2 vectors.  Prepare
+//                  looks at its own pixel only, so the batch runs the plain prepare over N*W*H pixels; the level kernel's batched twin, dn_level_batch,
+//                  splits its flat pixel into (view, j, i) and bounds every tap by the view's own frame -- the arithmetic of a pixel is
+//                  dn_tap / dn_centre / dn_store as everywhere.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -137,6 +142,9 @@ __global__ __launch_bounds__(256) void dn_prepare(const T *__restrict__ image, c
     E[p] = e; G[p] = g; A[p] = a;
 }
 
+// the batched level kernel's first argument: DnLevel of ONE frame with the batch's pixel count behind it
+template <typename T> struct DnLevelBatch { DnLevel<T> L; long long n_all; };       // n_all = N * W * H
+
 template <typename T, bool GUIDED = false>
 __global__ __launch_bounds__(256) void dn_level(DnLevel<T> L, const typename DnVec<T>::type *__restrict__ Ein, const typename DnVec<T>::type *__restrict__ G,
                                                        const typename DnVec<T>::type *__restrict__ A, typename DnVec<T>::type *__restrict__ Eout, T *__restrict__ out) {
@@ -160,6 +168,41 @@ __global__ __launch_bounds__(256) void dn_level(DnLevel<T> L, const typename DnV
             const long long q = in ? qj * H + qi : p;
             const V eq = Ein[q], gq = G[q];
             dn_tap<T, GUIDED>(a, ep, gp, eq, gq, (T)(dn_k(di) * dn_k(dj)), in && gq.w == gq.w, L, vp);
+        }
+    }
+    dn_store<T>(a, ep, gp, p, L, A, Eout, out);
+}
+
+// BATCH (plain form): lane = flat pixel p of the batch = view * W*H + j*H + i; `base` is the view's first slot, every tap stays in [base, base + W*H)
+template <typename T>
+__global__ __launch_bounds__(256) void dn_level_batch(DnLevelBatch<T> B, const typename DnVec<T>::type *__restrict__ Ein, const typename DnVec<T>::type *__restrict__ G,
+                                                             const typename DnVec<T>::type *__restrict__ A, typename DnVec<T>::type *__restrict__ Eout, T *__restrict__ out) {
+    using V = typename DnVec<T>::type;
+    const DnLevel<T> &L = B.L;
+    const long long H = L.H, W = L.W, s = L.step, WH = W * H;
+    const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (p >= B.n_all) return;
+    // (32-bit divisions whenever the batch allows it)
+    long long base, j, i;
+    if (B.n_all < (1ll << 31)) {
+        const unsigned v = (unsigned)p / (unsigned)WH, r = (unsigned)p - v * (unsigned)WH, jj = r / (unsigned)H;
+        base = (long long)v * WH; j = jj; i = r - jj * (unsigned)H;
+    } else {
+        const long long v = p / WH, r = p - v * WH;
+        base = v * WH; j = r / H; i = r - j * H;
+    }
+    const V ep = Ein[p], gp = G[p];
+    DnSum<T> a = {T(0), T(0), T(0), T(0)};
+#pragma unroll
+    for (int dj = -2; dj <= 2; ++dj) {
+#pragma unroll
+        for (int di = -2; di <= 2; ++di) {
+            if (di == 0 && dj == 0) { dn_centre<T>(a, ep); continue; }
+            const long long qi = i + s * di, qj = j + s * dj;
+            const bool in = qi >= 0 && qi < H && qj >= 0 && qj < W;
+            const long long q = in ? base + qj * H + qi : p;
+            const V eq = Ein[q], gq = G[q];
+            dn_tap<T, false>(a, ep, gp, eq, gq, (T)(dn_k(di) * dn_k(dj)), in && gq.w == gq.w, L, T(1));
         }
     }
     dn_store<T>(a, ep, gp, p, L, A, Eout, out);

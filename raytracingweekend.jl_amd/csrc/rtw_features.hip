@@ -1,6 +1,7 @@
 // rtw_features.hip -- first-hit feature buffers (include/rtw_hip.h rtw_render_features_*): the checks that need no device, ONE launch of the
 // feature kernel (rtw_features.hpp) per call -- its own parameters, instance and grid; camera, numerics mode and scene view (rtw_scene_view.hpp) and the
 // record sequence (rtw_host.hpp begin_record / run_record) are the ones launch_render (rtw_launch.hip) uses --, and the device-resident entry points.
+// rtw_render_features_batch_*: the same launch with a BATCH instance over N views, whose cameras and seeds go up with the record (upload_views, rtw_launch.hip).
 // (The host-buffer entry points live with the other cached-context paths in rtw_render_host.hip.)
 #include "rtw_scene_view.hpp"
 #include "rtw_features.hpp"
@@ -27,16 +28,35 @@ int validate_features(const rtw_params *p, int32_t chunk_begin, int32_t chunk_co
     return 0;
 }
 
+// A batched feature render (rtw_render_features_batch_*): validate_batch's rules together with validate_features'.  What the one launch
+// must be able to number -- the batch's tiles (flat, v * n_tiles + t) and its workgroups -- is inside validate_batch's bound for the render's
+// queues (n_views x tiles < 2^28); the check below states it for this launch.
+int validate_features_batch(const void *cams, int32_t n_views, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, const void *out, int *n_chunks, int *chunk_spp) {
+    if (int rc = validate_batch(cams, n_views, p, out)) return rc;
+    if (int rc = validate_features(p, chunk_begin, chunk_count, n_chunks, chunk_spp)) return rc;
+    const long long n_tiles = (long long)((p->height + 7) / 8) * ((p->width + 7) / 8);
+    if ((double)n_tiles * (double)n_views >= (double)(1ll << 31)) return fail(-5, "batch too large for one call: %d views of %lld tiles", n_views, n_tiles);
+    return 0;
+}
+
 // Enqueue the feature kernel for the chunks [chunk_begin, chunk_begin + chunk_count) of the render `p` describes (validate_features has
 // accepted them) on `stream`; `rec` receives the counters and the kernel's events like a render's.
 // d_tile_chunks non-null (rtw_accum_features_* on an adaptive accumulator, rtw_accum.hip): the TILED instances -- tile t gets the chunks
 // [0, d_tile_chunks[t]) instead of the call's range (which the caller passes as [0, 1): validated, not looked at by the kernel).
+// n_views >= 1 (validate_features_batch has accepted it; no d_tile_chunks): ONE launch of a BATCH instance over the n_views cameras `cam`
+// points to, `seeds` (null: p->seed for every view) and n_views buffers behind d_out; the views go up with the record (upload_views).
+inline int upload_views_t(RenderRec *r, const rtw_camera_f32 *c, int n, const uint64_t *sd, uint64_t s, hipStream_t st, const void **dc, const unsigned long long **ds) { return upload_views_f32(r, c, n, sd, s, st, dc, ds); }
+inline int upload_views_t(RenderRec *r, const rtw_camera_f64 *c, int n, const uint64_t *sd, uint64_t s, hipStream_t st, const void **dc, const unsigned long long **ds) { return upload_views_f64(r, c, n, sd, s, st, dc, ds); }
+
 template <typename T, typename CamT>
-int launch_features(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream,
-                    RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks) {
+int launch_features(rtw_scene_handle scene, const CamT *cam, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out,
+                    hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks) {
     if (!scene || !cam || !p || !d_out) return fail(-1, "null argument");
+    const bool batch = n_views > 0;
+    if (batch && d_tile_chunks) return fail(-9, "internal: the tiled feature pass has no batched form");
     int nch, cs;
-    if (int rc = validate_features(p, chunk_begin, chunk_count, &nch, &cs)) return rc;
+    if (batch) { if (int rc = validate_features_batch(cam, n_views, p, chunk_begin, chunk_count, d_out, &nch, &cs)) return rc; }
+    else if (int rc = validate_features(p, chunk_begin, chunk_count, &nch, &cs)) return rc;
     if (((uintptr_t)d_out & 15u) != 0) return fail(-2, "the feature buffer must be 16-byte aligned");
     if (scene->is_f64 != (sizeof(T) == 8)) return fail(-4, "scene handle precision does not match the call");
     if (p->device >= 0 && p->device != scene->device)
@@ -61,11 +81,16 @@ int launch_features(rtw_scene_handle scene, const CamT *cam, const rtw_params *p
     const bool mfma = scene->mf_ops != nullptr && !(p->flags & RTW_FLAG_SCAN_VALU);
     PlainView<T> V;
     if (int rc = plain_scene_view<T>(scene, mfma, numerics, &V)) return rc;
-    const size_t lds_bytes = rtw::feat_fixed_lds_bytes<T>() + (V.lds_scene ? V.scene_bytes : 0);
+    const size_t lds_bytes = (batch ? rtw::feat_fixed_lds_bytes<T, true>() : rtw::feat_fixed_lds_bytes<T>()) + (V.lds_scene ? V.scene_bytes : 0);
     typedef void (*kern_t)(rtw::FeatParams, rtw::Camera<T>, rtw::DevScene<T>, T *, rtw::DevCounters *, const int *);
+    typedef void (*bkern_t)(rtw::FeatParams, rtw::Camera<T>, rtw::DevScene<T>, T *, rtw::DevCounters *, rtw::FeatViews<T>);
     const bool tiled = d_tile_chunks != nullptr;
-    kern_t kern;
-    if (!tiled) {
+    kern_t kern = nullptr;
+    bkern_t bkern = nullptr;
+    if (batch) {
+        if (mfma) bkern = V.lds_scene ? (bkern_t)rtw::features_kernel<T, true, true, -1, false, true> : (bkern_t)rtw::features_kernel<T, true, false, -1, false, true>;
+        else bkern = V.lds_scene ? (bkern_t)rtw::features_kernel<T, false, true, -1, false, true> : (bkern_t)rtw::features_kernel<T, false, false, -1, false, true>;
+    } else if (!tiled) {
         if (mfma) kern = V.lds_scene ? (kern_t)rtw::features_kernel<T, true, true> : (kern_t)rtw::features_kernel<T, true, false>;
         else kern = V.lds_scene ? (kern_t)rtw::features_kernel<T, false, true> : (kern_t)rtw::features_kernel<T, false, false>;
     } else {
@@ -74,26 +99,49 @@ int launch_features(rtw_scene_handle scene, const CamT *cam, const rtw_params *p
     }
     // the default numerics mode of the headline variant (scene in LDS, matrix pipe): the mode fixed at compile time
     const bool fixed = mfma && V.lds_scene && numerics == rtw::NUM_REFERENCE;
-    if (fixed) kern = tiled ? (kern_t)rtw::features_kernel<T, true, true, rtw::NUM_REFERENCE, true> : (kern_t)rtw::features_kernel<T, true, true, rtw::NUM_REFERENCE>;
-    const unsigned grid = (K.n_tiles + RTW_FEATURE_WAVES - 1u) / RTW_FEATURE_WAVES;
+    if (fixed && batch) bkern = (bkern_t)rtw::features_kernel<T, true, true, rtw::NUM_REFERENCE, false, true>;
+    else if (fixed) kern = tiled ? (kern_t)rtw::features_kernel<T, true, true, rtw::NUM_REFERENCE, true> : (kern_t)rtw::features_kernel<T, true, true, rtw::NUM_REFERENCE>;
+    // (a batch: its tiles numbered flat, v * n_tiles + t -- validate_features_batch: fewer than 2^31)
+    const unsigned total_tiles = batch ? K.n_tiles * (unsigned)n_views : K.n_tiles;
+    const unsigned grid = (total_tiles + RTW_FEATURE_WAVES - 1u) / RTW_FEATURE_WAVES;
     // (test aid: which instance the rules above picked, in the form of the trace kernel's line -- rtw_launch.hip; the grid is one workgroup
     //  per RTW_FEATURE_WAVES tiles, no occupancy question is asked: blocks_per_cu=0)
     static const bool debug = aid_env("RTW_DEBUG") != nullptr;
     if (debug)
-        fprintf(stderr, "[rtw debug] features instance: %s lds_scene=%d cull=0 mfma=%d fixed=%d batch=0 accum=%d adapt=%d lds_bytes=%zu blocks_per_cu=0\n", sizeof(T) == 8 ? "f64" : "f32",
-                (int)V.lds_scene, (int)mfma, (int)fixed, (int)tiled, (int)tiled, lds_bytes);
+        fprintf(stderr, "[rtw debug] features instance: %s lds_scene=%d cull=0 mfma=%d fixed=%d batch=%d accum=%d adapt=%d lds_bytes=%zu blocks_per_cu=0\n", sizeof(T) == 8 ? "f64" : "f32",
+                (int)V.lds_scene, (int)mfma, (int)fixed, (int)batch, (int)tiled, (int)tiled, lds_bytes);
 
     if (int rc = begin_record(ctx.get(), scene, nch, (int)grid, 64 * RTW_FEATURE_WAVES, offsetof(rtw::DevCounters, t_first), stream, rec_out)) return rc;
+    if (batch) {
+        rtw::FeatViews<T> FV;
+        memset(&FV, 0, sizeof FV);
+        const void *d_cams = nullptr;
+        if (int rc = upload_views_t(*rec_out, cam, n_views, seeds, p->seed, stream, &d_cams, &FV.seeds)) return rc;
+        FV.cams = (const rtw::Camera<T> *)d_cams;
+        FV.total_tiles = total_tiles;
+        FV.view_elems = (unsigned long long)p->width * (unsigned long long)p->height * RTW_FEATURE_CHANNELS;
+        return run_record(*rec_out, stream, [&] { hipLaunchKernelGGL(bkern, dim3(grid), dim3(64 * RTW_FEATURE_WAVES), lds_bytes, stream, K, C, V.scene, (T *)d_out, (*rec_out)->ctr, FV); });
+    }
     return run_record(*rec_out, stream, [&] { hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * RTW_FEATURE_WAVES), lds_bytes, stream, K, C, V.scene, (T *)d_out, (*rec_out)->ctr, d_tile_chunks); });
 }
 
 int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream,
                         RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks) {
-    return launch_features<float>(scene, cam, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks);
+    return launch_features<float>(scene, cam, 0, nullptr, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks);
+}
+int launch_features_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count,
+                              void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out) {
+    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
+    return launch_features<float>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, nullptr);
+}
+int launch_features_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count,
+                              void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out) {
+    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
+    return launch_features<double>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, nullptr);
 }
 int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream,
                         RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks) {
-    return launch_features<double>(scene, cam, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks);
+    return launch_features<double>(scene, cam, 0, nullptr, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks);
 }
 
 template <typename CamT>
@@ -108,6 +156,24 @@ int features_device(rtw_scene_handle scene, const CamT *cam, const rtw_params *p
     CtxPtr ctx;
     release_last();
     int rc = launch_features_t(scene, cam, p, chunk_begin, chunk_count, d_out, (hipStream_t)stream_v, &rec, &ctx);
+    hold_last(rec, ctx);               // (also on a late error: released by the next call)
+    return rc;
+}
+
+// rtw_render_features_batch_device_*
+template <typename CamT>
+int features_batch_device(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out,
+                          void *stream_v) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !cams || !d_out) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = validate_features_batch(cams, n_views, p, chunk_begin, chunk_count, d_out, &nch, &cs)) return rc;
+    if (((uintptr_t)d_out & 15u) != 0) return fail(-2, "the feature buffer must be 16-byte aligned");
+    DeviceGuard guard;
+    RenderRec *rec = nullptr;
+    CtxPtr ctx;
+    release_last();
+    int rc = launch_features_batch_t(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, (hipStream_t)stream_v, &rec, &ctx);
     hold_last(rec, ctx);               // (also on a late error: released by the next call)
     return rc;
 }
@@ -129,6 +195,23 @@ int rtw_render_features_f32(const rtw_scene_f32 *s, const rtw_camera_f32 *c, con
 }
 int rtw_render_features_f64(const rtw_scene_f64 *s, const rtw_camera_f64 *c, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, double *out) {
     return render_host_features_f64(s, c, p, chunk_begin, chunk_count, out);
+}
+
+int rtw_render_features_batch_device_f32(rtw_scene_handle s, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin,
+                                         int32_t chunk_count, void *d_out, void *stream) {
+    return features_batch_device(s, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream);
+}
+int rtw_render_features_batch_device_f64(rtw_scene_handle s, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin,
+                                         int32_t chunk_count, void *d_out, void *stream) {
+    return features_batch_device(s, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream);
+}
+int rtw_render_features_batch_f32(const rtw_scene_f32 *s, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin,
+                                  int32_t chunk_count, float *out) {
+    return render_host_features_batch_f32(s, cams, n_views, seeds, p, chunk_begin, chunk_count, out);
+}
+int rtw_render_features_batch_f64(const rtw_scene_f64 *s, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin,
+                                  int32_t chunk_count, double *out) {
+    return render_host_features_batch_f64(s, cams, n_views, seeds, p, chunk_begin, chunk_count, out);
 }
 
 }  // extern "C"

@@ -34,8 +34,22 @@ struct FeatParams {
 // matrix-pipe scan: keys, kidx][camera][scene copy + (matrix pipe) its index array: LDS_SCENE only]; every offset a multiple of 16
 template <typename T> __host__ __device__ constexpr size_t feat_list_bytes() { return (size_t)RTW_LIST_CAP * 64 * RTW_FEATURE_WAVES * sizeof(unsigned short); }
 template <typename T> __host__ __device__ constexpr size_t feat_cell_bytes() { return (size_t)RTW_FEATURE_WAVES * 64 * (sizeof(unsigned long long) + sizeof(unsigned)); }
-template <typename T> __host__ __device__ constexpr size_t feat_cam_bytes() { return (sizeof(Camera<T>) + 15) / 16 * 16; }
-template <typename T> __host__ __device__ constexpr size_t feat_fixed_lds_bytes() { return feat_list_bytes<T>() + feat_cell_bytes<T>() + feat_cam_bytes<T>(); }
+// (BATCH: one camera per wave -- a workgroup's waves may belong to different views)
+template <typename T, bool BATCH = false> __host__ __device__ constexpr size_t feat_cam_bytes() { return (sizeof(Camera<T>) * (BATCH ? RTW_FEATURE_WAVES : 1) + 15) / 16 * 16; }
+template <typename T, bool BATCH = false> __host__ __device__ constexpr size_t feat_fixed_lds_bytes() { return feat_list_bytes<T>() + feat_cell_bytes<T>() + feat_cam_bytes<T, BATCH>(); }
+
+// The views of a batched launch (rtw_render_features_batch_*; the BATCH instances): the device arrays upload_views (rtw_launch.hip) fills.
+// The batch's tiles are numbered flat, g = v * n_tiles + t, so a workgroup's waves may belong to different views: a frame of one tile
+// still fills all RTW_FEATURE_WAVES waves.  View v writes at out + v * view_elems.
+template <typename T> struct FeatViews {
+    const Camera<T> *cams;              // N cameras
+    const unsigned long long *seeds;    // N render seeds
+    unsigned total_tiles;               // N * FeatParams::n_tiles (< 2^31)
+    unsigned long long view_elems;      // W * H * 8: elements of one view's buffer
+};
+// the kernel's last argument: the tile-chunk array of the TILED instances (every instance that is not BATCH keeps its signature), the views of a BATCH instance
+template <typename T, bool BATCH> struct FeatLastArg { using type = const int *__restrict__; };
+template <typename T> struct FeatLastArg<T, true> { using type = FeatViews<T>; };
 
 // waves per SIMD the kernel is compiled for: 32 registers of sums next to the scan's own
 template <typename T> struct FeatWaves { static constexpr int value = 4; };
@@ -64,9 +78,14 @@ template <> __device__ __forceinline__ void feat_store8<double>(double *o, const
 // NUMK >= 0: the numerics mode fixed at compile time (the default mode of the headline variant), NUMK < 0: the mode of the arguments.
 // TILED: the pass over what an adaptive accumulator holds (rtw_accum_features_*): the wave's tile t gets the chunks [0, C_t) with C_t =
 // tile_chunks[t] (the accumulator's device array, >= 1), read once and made wave-uniform; P.chunk_begin / chunk_count are not looked at.
-template <typename T, bool MFMA, bool LDS_SCENE, int NUMK = -1, bool TILED = false>
+// BATCH: N views in one launch (FeatViews, the last argument): the wave's flat tile g = v * n_tiles + t is tile t of view v, whose camera the
+// wave stages in its own LDS cell, whose seed is seeds[v] and whose buffer starts at out + v * view_elems; cam_arg and P.seed are not looked
+// at.  Everything behind the tile's coordinates is the code of the other instances.  (TILED && BATCH is not built; the last argument keeps
+// its name `tile_chunks` in both forms: FeatLastArg says what it is.)
+template <typename T, bool MFMA, bool LDS_SCENE, int NUMK = -1, bool TILED = false, bool BATCH = false>
 __global__ __launch_bounds__(64 * RTW_FEATURE_WAVES, (FeatWaves<T>::value)) void features_kernel(FeatParams P, Camera<T> cam_arg, DevScene<T> scene,
-                                                                                             T *__restrict__ out, DevCounters *ctr, const int *__restrict__ tile_chunks) {
+                                                                                             T *__restrict__ out, DevCounters *ctr, typename FeatLastArg<T, BATCH>::type tile_chunks) {
+    static_assert(!(TILED && BATCH), "the tiled pass has no batched form");
     using V4 = typename Vec4<T>::type;
     if constexpr (NUMK >= 0) scene.numerics = NUMK;
     const unsigned lane = lane_id(), wv = threadIdx.x >> 6;
@@ -74,7 +93,7 @@ __global__ __launch_bounds__(64 * RTW_FEATURE_WAVES, (FeatWaves<T>::value)) void
     [[maybe_unused]] unsigned short *my_list = reinterpret_cast<unsigned short *>(smem) + threadIdx.x;
     unsigned char *cells = smem + feat_list_bytes<T>();
     Camera<T> *sh_cam = reinterpret_cast<Camera<T> *>(cells + feat_cell_bytes<T>());
-    V4 *lds_geom = reinterpret_cast<V4 *>(smem + feat_fixed_lds_bytes<T>());
+    V4 *lds_geom = reinterpret_cast<V4 *>(smem + feat_fixed_lds_bytes<T, BATCH>());
     [[maybe_unused]] unsigned short *lds_orig = reinterpret_cast<unsigned short *>(lds_geom + scene_geom_alloc(scene.n, scene.n_pad));
     [[maybe_unused]] WaveScratch ws = {nullptr, nullptr, nullptr};
     if constexpr (MFMA) {
@@ -83,15 +102,36 @@ __global__ __launch_bounds__(64 * RTW_FEATURE_WAVES, (FeatWaves<T>::value)) void
         ws.keys = reinterpret_cast<unsigned long long *>(cells) + wv * 64;
         ws.kidx = reinterpret_cast<unsigned *>(cells + RTW_FEATURE_WAVES * 64 * sizeof(unsigned long long)) + wv * 64;
     }
-    if (threadIdx.x == 0) *sh_cam = cam_arg;
+    // BATCH: the wave's view and its tile in it, wave-uniform; a wave behind the batch's last tile stages no camera but still helps with the scene
+    [[maybe_unused]] unsigned view = 0, tile_b = 0;
+    [[maybe_unused]] bool has_tile = true;
+    if constexpr (BATCH) {
+        const unsigned g = __builtin_amdgcn_readfirstlane(blockIdx.x * RTW_FEATURE_WAVES + wv);
+        has_tile = g < tile_chunks.total_tiles;
+        view = has_tile ? g / P.n_tiles : 0u;
+        tile_b = g - view * P.n_tiles;
+        sh_cam += wv;
+        if (lane == 0 && has_tile) *sh_cam = tile_chunks.cams[view];
+    } else {
+        if (threadIdx.x == 0) *sh_cam = cam_arg;
+    }
     if constexpr (LDS_SCENE) {
         stage_scene<T>(scene, lds_geom);
         if constexpr (MFMA) { for (int i = threadIdx.x; i < scene_geom_alloc(scene.n, scene.n_pad); i += blockDim.x) lds_orig[i] = scene.orig[i]; }
     }
     __syncthreads();
     // (no workgroup barrier from here on: a wave without a tile may leave)
-    const unsigned tile = blockIdx.x * RTW_FEATURE_WAVES + wv;
-    if (tile >= P.n_tiles) return;
+    unsigned tile;
+    [[maybe_unused]] unsigned long long seed = P.seed;
+    if constexpr (BATCH) {
+        if (!has_tile) return;
+        tile = tile_b;
+        seed = tile_chunks.seeds[view];
+        out += (unsigned long long)view * tile_chunks.view_elems;
+    } else {
+        tile = blockIdx.x * RTW_FEATURE_WAVES + wv;
+        if (tile >= P.n_tiles) return;
+    }
     const unsigned tj = tile / (unsigned)P.tiles_i, ti = tile - tj * (unsigned)P.tiles_i;
     const int i0 = (int)(ti * 8u + (lane & 7u)), j0 = (int)(tj * 8u + (lane >> 3));       // 0-based row, column
     const bool valid = i0 < P.height && j0 < P.width;
@@ -114,7 +154,7 @@ __global__ __launch_bounds__(64 * RTW_FEATURE_WAVES, (FeatWaves<T>::value)) void
     for (int c = 0; c < chunk_count; ++c) {
         const unsigned chunk = (unsigned)(chunk_begin + c);
         Rng rng;
-        rng_stream(P.seed, pix, chunk, rng);
+        rng_stream(BATCH ? seed : P.seed, pix, chunk, rng);
         T du = 0, dv = 0;
         if ((long long)chunk * P.chunk_spp != 0) {                 // the chunk's first sample is not sample 1 of the pixel (src/render.jl:30-31)
             T r1, r2;

@@ -8,8 +8,8 @@
 //   rtw_batch_accum_f32.hip / _f64.hip  the BATCH && ACCUM instances of the trace kernel (rtw_instances.hpp: the kernel-instance table), a unit per precision
 //   rtw_accum.hip        progressive render: the accumulator object, its passes, merge / resolve kernels, export / import
 //   rtw_unit.hip         the T0 unit entry points (rtw_units.hpp)
-//   rtw_features.hip     first-hit feature buffers: one launch of the feature kernel (rtw_features.hpp), the device-resident entry points
-//   rtw_denoise.hip      the feature-guided denoiser: its checks, the launch sequence of its kernels (rtw_denoise.hpp), the device-resident entry points
+//   rtw_features.hip     first-hit feature buffers: one launch of the feature kernel (rtw_features.hpp) for one view or a batch of views, the device-resident entry points
+//   rtw_denoise.hip      the feature-guided denoiser: its checks, the launch sequence of its kernels (rtw_denoise.hpp) for one frame or a batch of frames, the device-resident entry points
 //   (rtw_scene_view.hpp: what both launch functions derive from their arguments; rtw_instances.hpp: the one table of the trace kernel's instances)
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
 #pragma once
@@ -234,6 +234,10 @@ int launch_render_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_
 int launch_render_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const AccumPass *pass = nullptr);
 inline int launch_render_t(rtw_scene_handle s, const rtw_camera_f32 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const AccumPass *a = nullptr) { return launch_render_f32(s, c, n, sd, p, d, st, r, x, a); }
 inline int launch_render_t(rtw_scene_handle s, const rtw_camera_f64 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const AccumPass *a = nullptr) { return launch_render_f64(s, c, n, sd, p, d, st, r, x, a); }
+// a batch's cameras and seeds (null: `seed` for every view) into the record's pinned buffer and, by ONE asynchronous H2D on `stream`, into its
+// device buffer (the upload of launch_render's batches): *d_cams receives the device array of n_views rtw::Camera<T>, *d_seeds that of the seeds
+int upload_views_f32(RenderRec *rec, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds);
+int upload_views_f64(RenderRec *rec, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds);
 int resolve_rec(RenderRec *r, rtw_stats_t *agg);            // wait for a record's kernel and add its counters to `agg`
 // what the kernel-instance table answers (rtw_instances.hpp): the kernel, and whether it has the default numerics mode compiled in
 struct TraceInstance { const void *kern; bool fixed; };
@@ -292,6 +296,14 @@ int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const
 int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks = nullptr);
 inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const int *tc = nullptr) { return launch_features_f32(s, c, p, b, n, d, st, r, x, tc); }
 inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const int *tc = nullptr) { return launch_features_f64(s, c, p, b, n, d, st, r, x, tc); }
+// The batched feature pass (include/rtw_hip.h rtw_render_features_batch_*): validate_features_batch = validate_batch's rules together with
+// validate_features' and a tile count the one launch can number; launch_features_batch: ONE launch of a BATCH instance for n_views >= 1
+// cameras, seeds (null: p->seed) and buffers of W*H*8 elements behind d_out.
+int validate_features_batch(const void *cams, int32_t n_views, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, const void *out, int *n_chunks, int *chunk_spp);
+int launch_features_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
+int launch_features_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
+inline int launch_features_batch_t(rtw_scene_handle s, const rtw_camera_f32 *c, int nv, const uint64_t *sd, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_features_batch_f32(s, c, nv, sd, p, b, n, d, st, r, x); }
+inline int launch_features_batch_t(rtw_scene_handle s, const rtw_camera_f64 *c, int nv, const uint64_t *sd, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_features_batch_f64(s, c, nv, sd, p, b, n, d, st, r, x); }
 
 // rtw_denoise.hip -- the feature-guided denoiser (include/rtw_hip.h rtw_denoise_*).  validate_denoise: the checks that need no device;
 // launch_denoise: enqueue its kernels on `stream` of the current device (d_work: rtw_denoise_work_bytes bytes, 16-byte aligned).
@@ -299,7 +311,18 @@ int validate_denoise(const rtw_denoise_t *d, int32_t width, int32_t height);
 // d_noise non-null: the noise-guided form (rtw_guided_filter_device_*): H*W elements of T, the per-pixel relative noise.
 int launch_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream, const void *d_noise = nullptr);
 int launch_denoise_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream, const void *d_noise = nullptr);
+// The batched filter (rtw_filter_batch_*): n_views frames of one size in prepare + `levels` launches; every buffer and every plane of the
+// workspace (n_views * rtw_denoise_work_bytes bytes) holds the views one behind the other.  validate_filter_batch: validate_denoise, n_views, the batch's size.
+int validate_filter_batch(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views);
+int launch_filter_batch_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_images, const void *d_features, void *d_out, void *d_work, hipStream_t stream);
+int launch_filter_batch_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_images, const void *d_features, void *d_out, void *d_work, hipStream_t stream);
 // rtw_render_host.hip: its host-buffer entry points
+int render_host_features_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, float *out);
+int render_host_features_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, double *out);
+int filter_batch_host_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const float *images, const float *features, float *out);
+int filter_batch_host_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const double *images, const double *features, double *out);
+int render_host_filtered_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, float *out);
+int render_host_filtered_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, double *out);
 int denoise_host_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const float *image, const float *features, float *out);
 int denoise_host_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const double *image, const double *features, double *out);
 int render_host_denoised_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, float *out);

@@ -130,6 +130,23 @@ static int upload_views(RenderRec *rec, const CamT *cam, int n_views, const uint
     return 0;
 }
 
+// the same upload for a launch that is not the trace kernel's (the batched feature pass, rtw_features.hip): the device arrays of the
+// cameras and of the seeds in the record's buffer
+template <typename T, typename CamT>
+static int upload_views_plain(RenderRec *rec, const CamT *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds) {
+    rtw::BatchArgs<T> B;
+    memset(&B, 0, sizeof B);
+    if (int rc = upload_views<T>(rec, cams, n_views, seeds, seed, nullptr, stream, &B, nullptr)) return rc;
+    *d_cams = B.cams; *d_seeds = B.seeds;
+    return 0;
+}
+int upload_views_f32(RenderRec *rec, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds) {
+    return upload_views_plain<float>(rec, cams, n_views, seeds, seed, stream, d_cams, d_seeds);
+}
+int upload_views_f64(RenderRec *rec, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds) {
+    return upload_views_plain<double>(rec, cams, n_views, seeds, seed, stream, d_cams, d_seeds);
+}
+
 // Enqueue one render (this shard's tiles) on `stream`; `rec` receives the counters and the kernel's events.
 // n_views >= 1: a batch (validate_batch has accepted it): `cam` points to n_views cameras, `seeds` to n_views seeds (null: p->seed for
 // every view), `d_out` to n_views frames.  The views' tile columns are laid side by side (rtw::BatchArgs), so the job shape, the grid and

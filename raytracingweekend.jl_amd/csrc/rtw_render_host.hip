@@ -335,18 +335,36 @@ int render_host_features(const SceneT *scene, const CamT *cam, const rtw_params 
     });
 }
 
+// N views' feature buffers (rtw_render_features_batch_f32/_f64): the one-device path with a device buffer of N x W x H x 8 elements, ONE
+// launch of a BATCH instance of the feature kernel, ONE D2H.
+template <typename T, typename SceneT, typename CamT>
+int render_host_features_batch(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, T *out) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !cams || !out) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = validate_features_batch(cams, n_views, p, chunk_begin, chunk_count, out, &nch, &cs)) return rc;
+    DeviceGuard guard;
+    release_last();
+    return render_one_device(p->device, scene, p, (size_t)n_views * (size_t)p->width * (size_t)p->height * RTW_FEATURE_CHANNELS, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+        return launch_features_batch_t(hc->scene, cams, n_views, seeds, &q, chunk_begin, chunk_count, hc->d_img, hc->stream, rec, rctx);
+    });
+}
+
+inline int launch_filter_batch_t(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t n, const float *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_filter_batch_f32(d, w, h, n, img, feat, out, work, st); }
+inline int launch_filter_batch_t(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t n, const double *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_filter_batch_f64(d, w, h, n, img, feat, out, work, st); }
 inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, const float *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise = nullptr) { return launch_denoise_f32(d, w, h, img, feat, out, work, st, noise); }
 inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, const double *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise = nullptr) { return launch_denoise_f64(d, w, h, img, feat, out, work, st, noise); }
 
 // The denoiser's regions inside a context's device buffer: image, features, output, workspace -- each starts on a 16-byte boundary.
+// (n_views > 1: a batch -- every region holds the views one behind the other)
 template <typename T> struct DenoiseRegions {
     size_t img_b, feat_b, off_feat, off_out, off_work, total;
-    DenoiseRegions(int32_t width, int32_t height) {
-        const size_t n = (size_t)width * (size_t)height;
+    DenoiseRegions(int32_t width, int32_t height, int32_t n_views = 1) {
+        const size_t n = (size_t)width * (size_t)height * (size_t)n_views;
         auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
         img_b = n * 3 * sizeof(T); feat_b = n * RTW_FEATURE_CHANNELS * sizeof(T);
         off_feat = up(img_b); off_out = off_feat + up(feat_b); off_work = off_out + up(img_b);
-        total = off_work + (size_t)rtw_denoise_work_bytes(width, height, (int32_t)sizeof(T));
+        total = off_work + (size_t)rtw_denoise_work_bytes(width, height, (int32_t)sizeof(T)) * (size_t)n_views;
     }
 };
 
@@ -372,6 +390,71 @@ int denoise_host(const rtw_denoise_t *d, int32_t width, int32_t height, const T 
     if (!rc) rc = launch_denoise_t(d, width, height, (const T *)base, base + R.off_feat, base + R.off_out, base + R.off_work, hc->stream);
     if (!rc) rc = copy_out(hc, base + R.off_out, out, R.img_b);
     if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    return rc;
+}
+
+// The batched filter on host buffers (rtw_filter_batch_f32/_f64): denoise_host for n_views frames -- two H2D, prepare + `levels` launches, ONE D2H.
+template <typename T>
+int filter_batch_host(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const T *images, const T *features, T *out) {
+    if (!d || !images || !features || !out) return fail(-1, "null argument");
+    if (int rc = validate_filter_batch(d, width, height, n_views)) return rc;
+    const DenoiseRegions<T> R(width, height, n_views);
+    auto hits = [](const void *a, size_t na, const void *b, size_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; };
+    if (hits(out, R.img_b, images, R.img_b) || hits(out, R.img_b, features, R.feat_b)) return fail(-2, "out may not alias an input");
+    DeviceGuard guard;
+    HostLease L;
+    if (int rc = acquire_host(d->device, std::vector<unsigned char>(), &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total)) return rc;
+    char *base = (char *)hc->d_img;
+    int rc = 0;
+    hipError_t e = hipMemcpyAsync(base, images, R.img_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_feat, features, R.feat_b, hipMemcpyHostToDevice, hc->stream);
+    if (e != hipSuccess) rc = fail((int)e, "upload of the filter's inputs failed: %s", hipGetErrorString(e));
+    if (!rc) rc = launch_filter_batch_t(d, width, height, n_views, (const T *)base, base + R.off_feat, base + R.off_out, base + R.off_work, hc->stream);
+    if (!rc) rc = copy_out(hc, base + R.off_out, out, R.img_b);
+    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    return rc;
+}
+
+// N views rendered, their feature passes and the filter in one call (rtw_render_filtered_batch_f32/_f64): render_host_denoised as a batch --
+// the batched render with gamma 0, the batched feature pass over all chunks, the batched filter with p->gamma, 2 + 1 + levels launches for
+// any N, one device buffer, ONE D2H.  rtw_stats() reports the render's record.
+template <typename T, typename SceneT, typename CamT>
+int render_host_filtered_batch(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, T *out) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !cams || !d || !out) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = validate_features_batch(cams, n_views, p, 0, 1, out, &nch, &cs)) return rc;
+    if (int rc = validate_filter_batch(d, p->width, p->height, n_views)) return rc;
+    if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
+    DeviceGuard guard;
+    release_last();
+    std::vector<unsigned char> key;
+    scene_key_of(scene, sizeof(T) == 8, key);
+    HostLease L;
+    if (int rc = acquire_host(p->device, key, &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_scene<T>(hc, scene, key)) return rc;
+    const DenoiseRegions<T> R(p->width, p->height, n_views);
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total)) return rc;
+    char *base = (char *)hc->d_img;
+    rtw_params q = *p;
+    q.device = hc->device; q.n_devices = 0; q.device_ids = nullptr; q.gamma = 0;
+    rtw_denoise_t dd = *d;
+    dd.gamma = p->gamma != 0; dd.device = hc->device;
+    RenderRec *rec = nullptr, *frec = nullptr;
+    CtxPtr rctx, fctx;
+    int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, &rec, &rctx);
+    if (!rc) rc = launch_features_batch_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec, &fctx);
+    if (!rc) rc = launch_filter_batch_t(&dd, p->width, p->height, n_views, (const T *)base, base + R.off_feat, base + R.off_out, base + R.off_work, hc->stream);
+    if (!rc) rc = copy_out(hc, base + R.off_out, out, R.img_b);
+    if (rc) (void)hipStreamSynchronize(hc->stream);
+    if (!rc) rc = resolve_rec(rec, &g_last.agg);
+    if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
+    if (rec) release_rec(rctx, rec, rc == 0);
+    if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
+    g_last.resolved = rc == 0;
     return rc;
 }
 
@@ -465,6 +548,21 @@ int denoise_host_f32(const rtw_denoise_t *d, int32_t width, int32_t height, cons
 int denoise_host_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const double *image, const double *features, double *out) { return denoise_host<double>(d, width, height, image, features, out); }
 int render_host_denoised_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, float *out) { return render_host_denoised<float>(scene, cam, p, d, out); }
 int render_host_denoised_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, double *out) { return render_host_denoised<double>(scene, cam, p, d, out); }
+
+int render_host_features_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, float *out) {
+    return render_host_features_batch<float>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, out);
+}
+int render_host_features_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, double *out) {
+    return render_host_features_batch<double>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, out);
+}
+int filter_batch_host_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const float *images, const float *features, float *out) { return filter_batch_host<float>(d, width, height, n_views, images, features, out); }
+int filter_batch_host_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const double *images, const double *features, double *out) { return filter_batch_host<double>(d, width, height, n_views, images, features, out); }
+int render_host_filtered_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, float *out) {
+    return render_host_filtered_batch<float>(scene, cams, n_views, seeds, p, d, out);
+}
+int render_host_filtered_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, double *out) {
+    return render_host_filtered_batch<double>(scene, cams, n_views, seeds, p, d, out);
+}
 
 int render_host_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, float *out) { return render_host<float>(scene, cam, p, out); }
 int render_host_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, double *out) { return render_host<double>(scene, cam, p, out); }

@@ -117,3 +117,78 @@ def render_denoised(scene, cam, image_width=400, n_samples=1, *, depth=16, seed=
     _capi.check(L.rtw_stats(C.byref(st)))
     _render_tls.stats = {k: getattr(st, k) for k, _ in st._fields_}
     return out.reshape(int(image_width), height, 3).transpose(1, 0, 2)
+
+
+def denoise_batch(images, features, **params):
+    """``images`` [N, H, W, 3] and ``features`` [N, H, W, 8] -- or the dict ``render_features_batch`` returns -- -> the N denoised images
+    [N, H, W, 3] in prepare + ``levels`` launches for all views (rtw_filter_batch_*).  View ``v`` is bit for bit
+    ``denoise(images[v], features[v], ...)``.  Keywords: ``make_denoise``.  Blocking; ``last_stats()`` is left as it was."""
+    if isinstance(features, dict):
+        features = features["raw"]
+    images, features = np.asarray(images), np.asarray(features)
+    T = images.dtype
+    if T not in (np.dtype(np.float32), np.dtype(np.float64)) or features.dtype != T:
+        raise TypeError("images and features must both be float32 or both float64")
+    if images.ndim != 4 or images.shape[3] != 3 or features.shape != images.shape[:3] + (8,):
+        raise ValueError(f"expected images [N, H, W, 3] and features [N, H, W, 8], got {images.shape} and {features.shape}")
+    N, H, W = images.shape[:3]
+    if N < 1 or H < 1 or W < 1:
+        raise ValueError("empty batch")
+    D = make_denoise(**params)
+    img = np.ascontiguousarray(images.transpose(0, 2, 1, 3))          # the library's layout: view v, pixel (i, j) at v*W*H + j*H + i
+    feat = np.ascontiguousarray(features.transpose(0, 2, 1, 3))
+    out = np.empty(N * W * H * 3, dtype=T)
+    L = _capi.lib()
+    fn = L.rtw_filter_batch_f64 if _capi.is_f64(T) else L.rtw_filter_batch_f32
+    _capi.check(fn(C.byref(D), W, H, N, img.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
+    return out.reshape(N, W, H, 3).transpose(0, 2, 1, 3)
+
+
+def denoise_batch_into(d_out_ptr, d_images_ptr, d_features_ptr, d_work_ptr, image_width, image_height, n_views, *, elem_type=np.float32,
+                       stream=0, work_bytes=None, **params):
+    """The device-resident batched form (rtw_filter_batch_device_*): ``denoise_into`` for ``n_views`` frames one behind the other in
+    every buffer.  The workspace holds ``n_views * denoise_work_bytes(...)`` bytes (``work_bytes``: its size, checked when given); its
+    planes are batch-major, so it is one workspace, not ``n_views`` single-frame ones.  Keywords: ``make_denoise``."""
+    need = int(n_views) * denoise_work_bytes(image_width, image_height, elem_type)
+    if int(n_views) < 1:
+        raise ValueError("n_views must be >= 1")
+    if work_bytes is not None and int(work_bytes) < need:
+        raise ValueError(f"workspace holds {work_bytes} bytes, the batched filter needs {need}")
+    D = make_denoise(**params)
+    L = _capi.lib()
+    fn = L.rtw_filter_batch_device_f64 if _capi.is_f64(elem_type) else L.rtw_filter_batch_device_f32
+    _capi.check(fn(C.byref(D), int(image_width), int(image_height), int(n_views), C.c_void_p(int(d_images_ptr)), C.c_void_p(int(d_features_ptr)),
+                   C.c_void_p(int(d_out_ptr)), C.c_void_p(int(d_work_ptr)), C.c_void_p(int(stream))))
+
+
+def render_denoised_batch(scene, cams, image_width=400, n_samples=1, *, seeds=None, depth=16, seed=1, n_chunks=0, device=-1, gamma=True,
+                          group_cull=False, scan_valu=False, numerics=None, levels=3, normal_power_log2=1, sigma_color=0.5, sigma_depth=0.1,
+                          demodulate=True):
+    """``render_batch`` + ``render_features_batch`` + ``denoise_batch`` in one call on the device (rtw_render_filtered_batch_*):
+    2 + 1 + ``levels`` launches for any number of views, the result comes back once.  Returns ``img[v, i, j, :]``; view ``v`` is bit for
+    bit ``render_denoised(scene, cams[v], ..., seed=seeds[v])``.  ``seeds``: a sequence of ``len(cams)`` ints (None: ``seed`` for every
+    view).  ``last_stats()`` reports the render."""
+    from .render import _batch_cameras
+    cams, T = _batch_cameras(cams)
+    n = len(cams)
+    sd = _capi.make_seeds(seed if seeds is None else seeds, n)
+    height = image_height(image_width)
+    if int(image_width) <= 0 or height <= 0:
+        raise ValueError(f"image_width={image_width} gives an empty {height} x {image_width} image")
+    if int(n_samples) <= 0:
+        raise ValueError("n_samples must be >= 1")
+    L = _capi.lib()
+    flat = scene if isinstance(scene, dict) else flatten_scene(scene, T)
+    S, keep = _capi.make_scene(flat, T)
+    Cm = _capi.make_cameras(cams, T)
+    P = _capi.make_params(image_width, height, n_samples, depth, seed, n_chunks, 0, 1, device, 1 if gamma else 0,
+                          (_capi.FLAG_GROUP_CULL if group_cull else 0) | (_capi.FLAG_SCAN_VALU if scan_valu else 0), numerics=numerics)
+    D = make_denoise(levels, normal_power_log2, sigma_color, sigma_depth, demodulate, gamma)
+    out = np.empty(n * height * int(image_width) * 3, dtype=T)
+    fn = L.rtw_render_filtered_batch_f64 if _capi.is_f64(T) else L.rtw_render_filtered_batch_f32
+    _capi.check(fn(C.byref(S), Cm, n, sd, C.byref(P), C.byref(D), out.ctypes.data_as(C.c_void_p)))
+    del keep
+    st = _capi.Stats()
+    _capi.check(L.rtw_stats(C.byref(st)))
+    _render_tls.stats = {k: getattr(st, k) for k, _ in st._fields_}
+    return out.reshape(n, int(image_width), height, 3).transpose(0, 2, 1, 3)

@@ -95,3 +95,52 @@ def features_into(renderer, d_out_ptr, image_width, n_samples, *, seed=1, n_chun
     fn = L.rtw_render_features_device_f64 if _capi.is_f64(renderer.T) else L.rtw_render_features_device_f32
     _capi.check(fn(renderer.handle, C.byref(renderer.cam), C.byref(P), begin, count, C.c_void_p(int(d_out_ptr)), C.c_void_p(int(stream))))
     return height
+
+
+def render_features_batch(scene, cams, image_width=400, n_samples=1, *, seeds=None, seed=1, n_chunks=0, chunks=None, device=-1, numerics=None,
+                          flags=0):
+    """The feature buffers of N views of ``scene`` in ONE launch (rtw_render_features_batch_*): the dict of ``render_features`` with a
+    leading view axis -- ``raw`` [N, H, W, 8], ``albedo`` [N, H, W, 3], ... -- the way ``render_batch`` stacks its frames.  View ``v`` is
+    bit for bit ``render_features(scene, cams[v], ..., seed=seeds[v])``.  ``seeds``: a sequence of ``len(cams)`` ints (None: ``seed`` for
+    every view).  Same size, spp, chunks and mode for every view; one device."""
+    from .render import _batch_cameras
+    cams, T = _batch_cameras(cams)
+    n = len(cams)
+    sd = _capi.make_seeds(seed if seeds is None else seeds, n)
+    L = _capi.lib()
+    height, P = _params(image_width, n_samples, seed, n_chunks, device, numerics, flags)
+    begin, count = _range(chunks, n_samples, n_chunks)
+    flat = scene if isinstance(scene, dict) else flatten_scene(scene, T)
+    S, keep = _capi.make_scene(flat, T)
+    Cm = _capi.make_cameras(cams, T)
+    out = np.empty(n * height * int(image_width) * FEATURE_CHANNELS, dtype=T)
+    fn = L.rtw_render_features_batch_f64 if _capi.is_f64(T) else L.rtw_render_features_batch_f32
+    _capi.check(fn(C.byref(S), Cm, n, sd, C.byref(P), begin, count, out.ctypes.data_as(C.c_void_p)))
+    del keep
+    st = _capi.Stats()
+    _capi.check(L.rtw_stats(C.byref(st)))
+    _render_tls.stats = {k: getattr(st, k) for k, _ in st._fields_}
+    return split(out.reshape(n, int(image_width), height, FEATURE_CHANNELS).transpose(0, 2, 1, 3))
+
+
+def features_batch_into(renderer, d_out_ptr, cams, image_width, n_samples, *, seeds=None, seed=1, n_chunks=0, chunks=None, stream=0, flags=0,
+                        job_pixels=0, numerics=None, n_elems=None):
+    """The device-resident batched form (rtw_render_features_batch_device_*; ``DeviceRenderer.features_batch_into``): enqueue ONE feature
+    launch of ``renderer``'s scene through ``cams`` into device memory at ``d_out_ptr`` -- len(cams) consecutive buffers of H*W*8
+    elements, 16-byte aligned -- on ``stream``.  ``n_elems``: the buffer's length in elements; checked when given.  Returns H."""
+    from .render import _batch_cameras
+    cams, T = _batch_cameras(cams)
+    if np.dtype(T) != np.dtype(renderer.T):
+        raise TypeError("the cameras' elem_type differs from the scene's")
+    n = len(cams)
+    height, P = _params(image_width, n_samples, seed, n_chunks, -1, numerics, flags, job_pixels)
+    need = n * height * int(image_width) * FEATURE_CHANNELS
+    if n_elems is not None and int(n_elems) < need:
+        raise ValueError(f"output buffer holds {n_elems} elements, the batched feature pass writes {need}")
+    begin, count = _range(chunks, n_samples, n_chunks)
+    sd = _capi.make_seeds(seed if seeds is None else seeds, n)
+    Cm = _capi.make_cameras(cams, T)
+    L = renderer.L
+    fn = L.rtw_render_features_batch_device_f64 if _capi.is_f64(T) else L.rtw_render_features_batch_device_f32
+    _capi.check(fn(renderer.handle, Cm, n, sd, C.byref(P), begin, count, C.c_void_p(int(d_out_ptr)), C.c_void_p(int(stream))))
+    return height

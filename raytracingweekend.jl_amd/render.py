@@ -187,6 +187,12 @@ class DeviceRenderer:
         from .features import features_into
         return features_into(self, d_out_ptr, image_width, n_samples, **kw)
 
+    def features_batch_into(self, d_out_ptr, cams, image_width, n_samples, **kw):
+        """Enqueue ONE feature launch (rtw_render_features_batch_device_f32/_f64) of this scene through ``cams`` into device memory at
+        ``d_out_ptr``: len(cams) consecutive buffers of H*W*8 elements, 16-byte aligned.  Keywords: ``features.features_batch_into``."""
+        from .features import features_batch_into
+        return features_batch_into(self, d_out_ptr, cams, image_width, n_samples, **kw)
+
     def stats(self):
         st = _capi.Stats()
         _capi.check(self.L.rtw_stats(C.byref(st)))

@@ -2,7 +2,7 @@
 """Register / scratch / occupancy table of every trace_kernel instantiation (hipcc -Rpass-analysis=kernel-resource-usage).
 usage: python tools/kernel_resources.py [--unit NAME.hip ...] [extra hipcc flags]   (cross-compiles for gfx950, no GPU needed)
 The instances live in rtw_launch.hip and, the BATCH && ACCUM ones, in rtw_batch_accum_f32.hip / _f64.hip: one table over all three.
---unit names other translation units instead (rtw_features.hip: the instances of the feature kernel; rtw_denoise.hip: the denoiser's kernels;
+--unit names other translation units instead (rtw_features.hip: the instances of the feature kernel, the batched ones among them; rtw_denoise.hip: the denoiser's kernels and the batched level kernel;
 rtw_accum.hip: the accumulator's kernels, the noise map among them)."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,8 +30,10 @@ for r in rows:
     if m:
         label = f"trace<{'f32' if m.group(1) == 'f' else 'f64'}{', profile' if m.group(2) == '1' else ''}{', lds-scene' if m.group(3) == '1' else ', global-scene'}{', cull' if m.group(4) == '1' else ''}{', mfma' if m.group(5) == '1' else ''}{', numerics fixed' if not m.group(6).startswith('n') else ''}{', batch' if m.group(7) == '1' else ''}{', accum' if m.group(8) == '1' else ''}{', adapt' if m.group(9) == '1' else ''}>"
     elif re.match(r"_ZN3rtw15features_kernelI([fd])Lb([01])ELb([01])ELi(n?\d+)E", n):
-        m = re.match(r"_ZN3rtw15features_kernelI([fd])Lb([01])ELb([01])ELi(n?\d+)E(?:Lb([01])E)?", n)
-        label = f"features<{'f32' if m.group(1) == 'f' else 'f64'}{', mfma' if m.group(2) == '1' else ', valu'}{', lds-scene' if m.group(3) == '1' else ', global-scene'}{', numerics fixed' if not m.group(4).startswith('n') else ''}{', tiled' if m.group(5) == '1' else ''}>"
+        m = re.match(r"_ZN3rtw15features_kernelI([fd])Lb([01])ELb([01])ELi(n?\d+)E(?:Lb([01])E)?(?:Lb([01])E)?", n)
+        label = f"features<{'f32' if m.group(1) == 'f' else 'f64'}{', mfma' if m.group(2) == '1' else ', valu'}{', lds-scene' if m.group(3) == '1' else ', global-scene'}{', numerics fixed' if not m.group(4).startswith('n') else ''}{', tiled' if m.group(5) == '1' else ''}{', batch' if m.group(6) == '1' else ''}>"
+    elif re.match(r"_ZN3rtw\d+dn_level_batchI([fd])", n):
+        label = "denoise level<%s, batch>" % ("f32" if re.match(r"_ZN3rtw\d+dn_level_batchI([fd])", n).group(1) == "f" else "f64")
     elif re.match(r"_ZN3rtw\d+dn_(prepare|level)I([fd])", n):
         m = re.match(r"_ZN3rtw\d+dn_(prepare|level)I([fd])(?:Lb([01])E)?", n)
         label = f"denoise {m.group(1)}<{'f32' if m.group(2) == 'f' else 'f64'}{', guided' if m.group(3) == '1' else ''}>"
