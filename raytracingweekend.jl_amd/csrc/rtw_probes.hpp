@@ -71,7 +71,7 @@
 #endif
 
 #ifdef RTW_DUP_EVAL      // (no CSE with the real one)
-#define RTW_PROBE_EVAL_TWICE(Wv) { unsigned keep = mask; eval(Wv); __asm__ volatile("" :: "v"(mask)); mask = keep; __asm__ volatile("" : "+v"(Wv)); }
+#define RTW_PROBE_EVAL_TWICE(Wv) { unsigned extra = 0u; eval(Wv, extra); __asm__ volatile("" :: "v"(extra)); __asm__ volatile("" : "+v"(Wv)); }
 #else
 #define RTW_PROBE_EVAL_TWICE(Wv)
 #endif

@@ -348,7 +348,16 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
     // (measured: running the first group's vote and the first operand fetch HERE, in front of the ray operands and the huge-sphere tests,
     //  changes nothing -- 293.1 against 293.2 ms -- and costs a spilled register: the vote stays in the block loop's prologue)
     uint4 A1 = {0u, 0u, 0u, 0u}, A2 = {0u, 0u, 0u, 0u};
-    if constexpr (!CULLED) { A1 = pa_of(0)[lane]; A2 = pa_of(0)[lane + 64u]; }
+    // both operand rows of a block through ONE lane offset: base[lane] and the same address + 1 KiB (written base[lane + 64u] the second index is a 32-bit
+    // sum of its own, and the loop rebuilt a `lane << 4` per block).  The block's base stays a scalar the compiler cannot look through: folded into the
+    // lane's pointer it becomes a 64-bit vector address, one v_lshl_add_u64 per block.
+    auto fetch = [&](int b) {
+        typedef unsigned u4 __attribute__((ext_vector_type(4)));
+        const __attribute__((address_space(1))) u4 *q = (const __attribute__((address_space(1))) u4 *)pa_of(b);      // (global memory, said so: the asm hides where it came from)
+        __asm__("" : "+s"(q));
+        A1 = __builtin_bit_cast(uint4, q[(size_t)lane]); A2 = __builtin_bit_cast(uint4, q[(size_t)lane + 64u]);
+    };
+    if constexpr (!CULLED) fetch(0);
     // Lane (H, j) supplies slots 8H .. 8H + 7 of both MFMAs for ray j (first half wave: h = 0) / ray 32 + j (h = 1).  Every
     // lane makes, for ITS ray, the operand words of both lane groups; one v_permlane32_swap per word then hands each lane
     // group its words for both half waves:
@@ -472,8 +481,13 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
         if (!todo) continue;
         blk = base + (int)__builtin_ctz(todo);
         todo &= todo - 1u;
-        A1 = pa_of(blk)[lane]; A2 = pa_of(blk)[lane + 64u];
+        fetch(blk);
     }
+    // (`bits`, the sign bits of the block at hand: all ones between blocks, in a register the compiler takes for a variable -- as a constant
+    //  it is written again for every block whose half 0 is skipped, and a block without a candidate should write nothing; set again by the
+    //  blocks that record, behind the record)
+    auto all_ones = [] { unsigned v; __asm__("v_mov_b32 %0, -1" : "=v"(v)); return v; };
+    unsigned bits = all_ones();
     for (bool more = true; more;) {
         const int cur = blk;                                   // (this iteration's block; `blk` becomes the next one)
         [[maybe_unused]] bool do_half0 = true, do_half1 = true;          // (wave-uniform) group cull: which ray halves of the wave can touch this block
@@ -488,16 +502,18 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
             blk = cur + 1;
             more = blk < n_blocks;
         }
-        unsigned mask = 0;
-        bool any_cand = false;                               // (wave-uniform)
         const rtw_f16v zero = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        // Sign collection of one half block's 16 filter values: one slow-class v_alignbit_b32 per value.  Most (wave, half block)
-        // evaluations find no candidate in ANY lane (rays of a wave are neighbours), so the sign bits of a GROUP of values are ANDed first
-        // (FMA-class v_bitop3_b32 / v_and_b32, one per two values) and the alignbits of the group run only when some lane has a
-        // non-negative value in it.  RTW_PRECHECK_GROUPS groups per half block: 1 = all 16 values at once (rounds 3 - 5), 2 = two groups of 8.
+        // Sign collection of one half block's 16 filter values: one slow-class v_alignbit_b32 per value, each shifting a sign bit into `bits`.
+        // Most (wave, half block) evaluations find no candidate in ANY lane (rays of a wave are neighbours), so the sign bits of a GROUP of
+        // values are ANDed first (FMA-class v_bitop3_b32 / v_and_b32, one per two values) and the alignbits run only when some lane has a
+        // non-negative value.  RTW_PRECHECK_GROUPS groups per half block: 1 = all 16 values at once (rounds 3 - 5), 2 = two groups of 8.
         // (Left to the compiler the skip is if-converted -- both sides executed -- and gains nothing: the collecting side is fenced by an asm.)
-        auto collect = [&](rtw_f16v &Wv) {
+        // Returns the ballot of the pre-check (wave-uniform; 0: nothing collected).  A half that does not collect leaves NOTHING behind -- `bits`
+        // is untouched, no per-lane mask is written and no flag is set: what a skipped half contributes to the block's mask (all ones: no
+        // candidate) is settled where the block records, so a block without a candidate issues the two pre-checks (2 x 9 VALU) and nothing else.
+        auto collect = [&](rtw_f16v &Wv, unsigned &bits) -> unsigned long long {
             constexpr int NG = RTW_PRECHECK_GROUPS, GS = 16 / NG;
+            unsigned long long some[NG], any = 0ull;
 #pragma unroll
             for (int g = 0; g < NG; ++g) {
                 const int r0 = g * GS;
@@ -505,20 +521,26 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
 #pragma unroll
                 for (int r = r0 + 3; r < r0 + GS - 1; r += 2) t = __builtin_amdgcn_bitop3_b32(t, __float_as_uint(Wv[r]), __float_as_uint(Wv[r + 1]), 0x80);
                 t &= __float_as_uint(Wv[r0 + GS - 1]);
-                if (RTW_SCAN_SKIP && !__any((int)t >= 0)) {
-                    mask = (mask << GS) | ((1u << GS) - 1u);                       // all negative: no lane has a candidate in this group
-                } else {
-                    if (RTW_SCAN_SKIP) __asm__ volatile("" : "+v"(Wv));
+                some[g] = RTW_SCAN_SKIP ? __ballot((int)t >= 0) : ~0ull;                // all negative: no lane has a candidate in this group
+                any |= some[g];
+            }
+            if (!any) return 0ull;
+            if (RTW_SCAN_SKIP) __asm__ volatile("" : "+v"(Wv));
 #pragma unroll
-                    for (int r = r0; r < r0 + GS; ++r) mask = __builtin_amdgcn_alignbit(mask, __float_as_uint(Wv[r]), 31);
-                    any_cand = true;
+            for (int g = 0; g < NG; ++g) {
+                if (NG == 1 || some[g]) {
+#pragma unroll
+                    for (int r = g * GS; r < g * GS + GS; ++r) bits = __builtin_amdgcn_alignbit(bits, __float_as_uint(Wv[r]), 31);
                     clk.count(26, 1u);                                                 // sign collections executed (per group)
+                } else {
+                    bits = (bits << GS) | ((1u << GS) - 1u);
                 }
             }
+            return any;
         };
-        [[maybe_unused]] auto eval = [&](const rtw_f16v &Wv) {            // (rtw_probes.hpp)
+        [[maybe_unused]] auto eval = [&](const rtw_f16v &Wv, unsigned &bits) {            // (rtw_probes.hpp)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) mask = __builtin_amdgcn_alignbit(mask, __float_as_uint(Wv[r]), 31);
+            for (int r = 0; r < 16; ++r) bits = __builtin_amdgcn_alignbit(bits, __float_as_uint(Wv[r]), 31);
         };
         // the filter values of one half block (32 spheres x 32 rays): two chained MFMAs (rtw_probes.hpp: time probes that repeat / replace them)
         auto filter_pair = [&](const uint4 &a1, const uint4 &a2, const rtw_h8 &b1, const rtw_h8 &b2) -> rtw_f16v {
@@ -528,44 +550,45 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
             RTW_PROBE_FILTER_PAIR_AGAIN(Wp, a1, a2, b1, b2);
             return Wp;
         };
-        constexpr unsigned HB = 16u;                          // mask bits per half block
-        {
-            if (!CULLED || do_half0) {
-                rtw_f16v Wv = filter_pair(A1, A2, B1[0], B2[0]);
-                RTW_PROBE_EVAL_TWICE(Wv);
-                collect(Wv);
-            } else {
-                mask = (1u << HB) - 1u;                               // (no ray of this half can touch the block)
-            }
+        // The two ray halves of the block.  Each shifts its 16 sign bits into `bits` and keeps the lanes that made it do so (group cull: a half
+        // that the vote skips is a half that did not collect).
+        unsigned long long some0 = 0ull, some1 = 0ull;
+        if (!CULLED || do_half0) {
+            rtw_f16v Wv = filter_pair(A1, A2, B1[0], B2[0]);
+            RTW_PROBE_EVAL_TWICE(Wv);
+            some0 = collect(Wv, bits);
+        }                                                    // (else: no ray of this half can touch the block)
+        // (plain if / else, the evaluating side first: as lambdas that return early for a skipped half, the structurized group-cull loop keeps the
+        //  old operands alive across the skipped side's prefetch -- the loads land in other registers, are waited for at once and copied: +1 %)
+        // the next block's operands are fetched as soon as this block's last use of each is issued (one block of
+        // padding at the end), so only one set of A registers is live during the evaluation
+        // (two copies of the prefetch: with ONE behind an `if (run) Wv = ...` the skipped side zeroes all 16 result registers -- 16 v_mov per
+        //  skipped ray half in the group cull, measured in the ISA)
+        if (!CULLED || do_half1) {
+            rtw_f16v Wv = filter_pair(A1, A2, B1[1], B2[1]);
+            __builtin_amdgcn_sched_barrier(0);
+            fetch(blk);
+            __builtin_amdgcn_sched_barrier(0);
+            RTW_PROBE_EVAL_TWICE(Wv);
+            some1 = collect(Wv, bits);
+        } else {
+            fetch(blk);
         }
-        {
-            // the next block's operands are fetched as soon as this block's last use of each is issued (one block of
-            // padding at the end), so only one set of A registers is live during the evaluation
-            // (two copies of the prefetch: with ONE behind an `if (run) Wv = ...` the skipped side zeroes all 16 result registers -- 16 v_mov per
-            //  skipped ray half in the group cull, measured in the ISA)
-            if (!CULLED || do_half1) {
-                rtw_f16v Wv = filter_pair(A1, A2, B1[1], B2[1]);
-                __builtin_amdgcn_sched_barrier(0);
-                A1 = pa_of(blk)[lane]; A2 = pa_of(blk)[lane + 64u];
-                __builtin_amdgcn_sched_barrier(0);
-                RTW_PROBE_EVAL_TWICE(Wv);
-                collect(Wv);
-            } else {
-                A1 = pa_of(blk)[lane]; A2 = pa_of(blk)[lane + 64u];
-                mask = (mask << HB) | ((1u << HB) - 1u);
-            }
-        }
+        // The block's candidates m: bit 31 - b, b = ray half << 4 | result register, set where the filter value is NOT negative.  `bits` is all ones
+        // when a block starts, each collecting half shifts its 16 signs in, and a half that is skipped does nothing at all:
+        //     both halves:  ~bits                 half 1 only:  ~bits, the ones of the skipped half 0 have moved to the upper half
+        //     half 0 only:  ~bits << 16           neither:      bits is still all ones -- on to the next block
+        // One if / else, no `continue`: the branches are wave-uniform but the loop holds divergent ones too (the record, the resolve), so the
+        // compiler structurizes it, and every jump out of the middle comes back as scalar flags set and tested on the path of every block.
         clk.lap(2);
-        if (RTW_SCAN_SKIP && !any_cand) {                    // no lane has a candidate in this block: nothing to extract
-            if constexpr (!CULLED) { clk.count(7, 1u); clk.count(6, 1u); }
-            continue;
-        }
-        // (the block's mask: bit 31 - b, b = half wave << 4 | result register)
-        unsigned m = ~mask;
-        if constexpr (!CULLED) {                          // (phase-profile build only: blocks, and blocks without any candidate)
-            clk.count(7, 1u);
-            if (!__any(m != 0u)) clk.count(6, 1u);
-        }
+        if constexpr (!CULLED) clk.count(7, 1u);             // (phase-profile build only: blocks, and blocks without any candidate)
+        if (RTW_SCAN_SKIP && !(some0 | some1)) {             // no lane has a candidate in this block: nothing to extract
+            if constexpr (!CULLED) clk.count(6, 1u);
+        } else {
+        unsigned long long got1 = some1;
+        __asm__("" : "+s"(got1));                            // (tested HERE: as a flag made next to half 1's branch it costs every block two scalar instructions)
+        const unsigned m = ~bits << (got1 ? 0u : 16u);       // (a scalar select of the shift)
+        if constexpr (!CULLED) { if (!__any(m != 0u)) clk.count(6, 1u); }
         // the lanes with a candidate in this block record their bits, ONE entry each: (bits, recording lane << 16 | block << 5) -- pass 2
         // walks the bits.  (Until round 5 every BIT became an entry here: a loop of ballot / ctz / mbcnt / write per candidate of the
         // busiest lane, ~25 - 35 VALU instructions per block with a candidate against 7 now.)
@@ -580,10 +603,12 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
         RTW_PROBE_EXTRACT_TWICE();
         if (m != 0u) {
             const unsigned pos = __builtin_amdgcn_mbcnt_hi((unsigned)(act >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)act, total));
-            reinterpret_cast<uint2 *>(ws.pairs)[pos] = uint2{m, lane_const + (unsigned)cur * 32u};
+            reinterpret_cast<uint2 *>(ws.pairs)[pos] = uint2{m, lane_const + (unsigned)(CULLED ? cur : blk - 1) * 32u};     // (plain: the block at hand is the one in front of `blk`)
         }
         total += (unsigned)__popcll(act);
+        bits = all_ones();                                   // (here, not where m is made: not live across the resolve)
         clk.lap(4);
+        }
     }
     }
     if (use_prio) __builtin_amdgcn_s_setprio(sizeof(T) == 4 ? 1 : 0);

@@ -15,8 +15,8 @@ import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "raytracingweekend.jl_amd", "csrc")
 OUT = os.path.join(ROOT, "build", "asm_g")
-KERNEL = "_ZN3rtw12trace_kernelIfLb0ELb1ELb0ELb1ELi0EEE"
-KERNEL_CULL = "_ZN3rtw12trace_kernelIfLb0ELb1ELb1ELb1ELi0EEE"       # `--cull`: the group-cull instance
+KERNEL = "_ZN3rtw12trace_kernelIfLb0ELb1ELb0ELb1ELi0ELb0ELb0ELb0EEE"
+KERNEL_CULL = "_ZN3rtw12trace_kernelIfLb0ELb1ELb1ELb1ELi0ELb0ELb0ELb0EEE"       # `--cull`: the group-cull instance
 
 # phase = (file, anchor substring of the line where it starts); a phase runs to the next anchor of the same file.  `mult`: counter name(s).
 PHASES = [
@@ -44,9 +44,9 @@ PHASES = [
     ("rtw_scan_mfma.hpp", "// The rest of the in-lane class (group cull", "S   group cull: discriminant of the in-lane class, list entries", "1"),
     ("rtw_scan_mfma.hpp", "// ---- the result cells, initialised with", "S   prologue: in-lane test of the huge spheres", "1"),
     ("rtw_scan_mfma.hpp", "// Wave priority: low inside the block loop", "S   block loop: control, MFMA issue, AND pre-check", "blocks"),
-    ("rtw_scan_mfma.hpp", "for (int r = r0; r < r0 + GS; ++r) mask = __builtin_amdgcn_alignbit", "S   block loop: sign collection (16 v_alignbit)", "sign_collections", "v_alignbit_b32/16"),
-    ("rtw_scan_mfma.hpp", "any_cand = true;", "S   block loop: control, MFMA issue, AND pre-check", "blocks"),
-    ("rtw_scan_mfma.hpp", "// the lanes with a candidate in this block record", "S   block loop: record the block's entries", "blocks_recording"),
+    ("rtw_scan_mfma.hpp", "for (int r = g * GS; r < g * GS + GS; ++r) bits = __builtin_amdgcn_alignbit", "S   block loop: sign collection (16 v_alignbit)", "sign_collections", "v_alignbit_b32/16"),
+    ("rtw_scan_mfma.hpp", "clk.count(26, 1u);", "S   block loop: control, MFMA issue, AND pre-check", "blocks"),
+    ("rtw_scan_mfma.hpp", "unsigned long long got1 = some1;", "S   block loop: record the block's entries", "blocks_recording"),
     ("rtw_scan_mfma.hpp", "if (use_prio) __builtin_amdgcn_s_setprio(sizeof(T) == 4 ? 1 : 0);", "S   epilogue: final pass 2 call, result cells", "1"),
 ]
 
@@ -71,7 +71,7 @@ def phase_table():
             hits = [i + 1 for i, ln in enumerate(lines) if anchor in ln]
             if not hits:
                 raise SystemExit(f"anchor not found in {fname}: {anchor!r}")
-            starts.append((hits[0] if "any_cand = true;" not in anchor else hits[0] + 1, name, mult))
+            starts.append((hits[0], name, mult))
         tab[fname] = sorted(starts)
     return tab
 
