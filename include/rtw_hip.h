@@ -660,7 +660,11 @@ int rtw_stats_devices(int32_t capacity, int32_t *count, int32_t *devices, double
  *   Op 25 runs the noise map kernel of rtw_accum_noise_* the same way (24 is not an op; also on rtw_unit_f32: T = float).  count = 1.  in: 8 value
  *          slots width, height, spp, chunk_spp, dark_floor (finite, >= 0), 0, 0, 0; n_tiles value slots C_t >= 1; width * height * 8 raw words.
  *          out: width * height value slots, element j * height + i: the map's value of type T, widened (NaN for a poisoned pixel).
- *   bits 8-9 of `op`: the numerics mode of the ray-sphere test for ops 0, 8 - 11, 13, 14 (0 reference, 1 contract, 3 reference_fma2; 2 is rejected)  */
+ *       26 one bounce as the trace kernel composes it (needs a scene; per item like ops 0 - 20).  in: state[2] (raw), o[3], d[3].  hit_world as op 8
+ *          with tmin = 1e-4, tmax = +inf, then on the UPLOADED material rows the kernel's own sequence: make_hitrec, the dielectric constants
+ *          1 / ir, r0_front, r0_back the upload stored, scatter_begin with them, attenuation_of, the rejection loop, scatter_finish, the final
+ *          normalize.  out: state[2] (raw), idx, o[3], d[3], att[3]; a miss leaves the state as it came, idx = -1 and zeros.
+ *   bits 8-9 of `op`: the numerics mode of the ray-sphere test for ops 0, 8 - 11, 13, 14, 26 (0 reference, 1 contract, 3 reference_fma2; 2 is rejected)  */
 int rtw_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene,
                  const rtw_camera_f32 *cam);
 int rtw_unit_f64(int op, int count, const void *in, void *out, const rtw_scene_f64 *scene,

@@ -14,7 +14,7 @@ int run_unit(int op_arg, int count, const void *in, void *out, const SceneT *sce
     if (count < 0 || (count > 0 && (!in || !out))) return fail(-1, "null argument");
     if (count == 0) return 0;
     const bool sink = rtw::unit_is_sink(op);
-    const bool needs_scene = op == rtw::U_HIT_WORLD || op == rtw::U_RAY_COLOR || op == rtw::U_HIT_WORLD_LDS || op == rtw::U_HIT_WORLD_CULL || op == rtw::U_HIT_WORLD_MFMA || op == rtw::U_HIT_WORLD_MFMA_CULL || sink;
+    const bool needs_scene = op == rtw::U_HIT_WORLD || op == rtw::U_RAY_COLOR || op == rtw::U_HIT_WORLD_LDS || op == rtw::U_HIT_WORLD_CULL || op == rtw::U_HIT_WORLD_MFMA || op == rtw::U_HIT_WORLD_MFMA_CULL || op == rtw::U_SHADE || sink;
     if (needs_scene && !scene) return fail(-1, "op %d needs a scene", op);
     if (sink && scene->n > RTW_SINK_SPHERES) return fail(-5, "unit op %d: the candidate sets hold %d spheres, the scene has %d", op, RTW_SINK_SPHERES, scene->n);
     if (op == rtw::U_GET_RAY && !cam) return fail(-1, "op %d needs a camera", op);

@@ -24,7 +24,10 @@ enum UnitOp {
     U_ACCUM_TILE_CHECK = 21, U_ACCUM_COMPACT = 22, U_ACCUM_RESOLVE_TILES = 23,
     // (24 is not an op: callers probe it as the first unknown number)
     U_ACCUM_NOISE = 25,      // the noise map kernel of an adaptive accumulator on hand-made words and C_t (rtw_accum.hip accum_unit)
-    U_NUM_OPS = 26
+    // one bounce as the trace kernel composes it (rtw_kernels.hpp phases H2, R, F): hit_world, then make_hitrec, the DielConst of the uploaded cold
+    // rows, scatter_begin(..., &dc), attenuation_of, the rejection loop, scatter_finish, the final normalize
+    U_SHADE = 26,
+    U_NUM_OPS = 27
 };
 __host__ __device__ inline bool unit_is_accum(int op) { return (op >= U_ACCUM_TILE_CHECK && op <= U_ACCUM_RESOLVE_TILES) || op == U_ACCUM_NOISE; }
 __host__ __device__ inline bool unit_is_sink(int op) { return op >= U_SINK_LDS && op <= U_SINK_MFMA_CULL; }
@@ -47,6 +50,7 @@ __host__ __device__ inline int unit_in_slots(int op) {
         case U_SINK_LDS: case U_SINK_CULL: case U_SINK_MFMA: case U_SINK_MFMA_CULL: return 8;                                         // (the same)
         case U_RAY_COLOR: return 9;     // state[2], o[3], d[3], depth
         case U_FX_SUM: return 8;        // 8 binary64 values
+        case U_SHADE: return 8;         // state[2], o[3], d[3]
     }
     return 0;
 }
@@ -66,6 +70,7 @@ __host__ __device__ inline int unit_out_slots(int op) {
         case U_SINK_LDS: case U_SINK_CULL: case U_SINK_MFMA: case U_SINK_MFMA_CULL: return RTW_SINK_SLOTS;   // ok, mf_sc, cand bits[8], in-lane bits[8] (raw uint64)
         case U_RAY_COLOR: return 6;     // state[2], colour[3], segments
         case U_FX_SUM: return 2;        // sum, poisoned
+        case U_SHADE: return 12;        // state[2], idx, o[3], d[3], att[3] (a miss: the state as it came, idx = -1, zeros)
     }
     return 0;
 }
@@ -107,7 +112,7 @@ __global__ void unit_kernel(int op, int count, const double *__restrict__ in, do
     const bool live = gid < count;                          // no early return: the scan is wave-cooperative
     const double *x = in + (size_t)gid * unit_in_slots(op);
     double *y = out + (size_t)gid * unit_out_slots(op);
-    const bool coop = op == U_HIT_WORLD || op == U_RAY_COLOR || op == U_HIT_WORLD_LDS || op == U_HIT_WORLD_CULL || op == U_HIT_WORLD_MFMA || op == U_HIT_WORLD_MFMA_CULL || unit_is_sink(op);
+    const bool coop = op == U_HIT_WORLD || op == U_RAY_COLOR || op == U_HIT_WORLD_LDS || op == U_HIT_WORLD_CULL || op == U_HIT_WORLD_MFMA || op == U_HIT_WORLD_MFMA_CULL || op == U_SHADE || unit_is_sink(op);
     const int wave0 = gid - (int)(threadIdx.x & 63u);
     const CandSink sink = {out + (size_t)wave0 * RTW_SINK_SLOTS, (unsigned)(count - wave0 < 64 ? count - wave0 : 64), threadIdx.x & 63u};   // (ops 17-20)
     if (!coop && !live) return;
@@ -349,6 +354,43 @@ __global__ void unit_kernel(int op, int count, const double *__restrict__ in, do
             if (!live) return;
             y[0] = as_f64(rng.x); y[1] = as_f64(rng.y);
             y[2] = cr; y[3] = cg; y[4] = cb; y[5] = (double)segs;
+        } break;
+        case U_SHADE: {
+            // rtw_kernels.hpp phases H2, R, F for one segment: the calls and their order are the trace kernel's, on the rows the upload made
+            Rng rng = {1, 2};
+            V3<T> o = {0, 0, 0}, d = {0, 0, 1};
+            if (live) { rng = {as_u64(x[0]), as_u64(x[1])}; o = ld3<T>(x + 2); d = ld3<T>(x + 5); }
+            T t_hit;
+            const int idx = hit_world<T, 64>(scene, scene.geom, o, d, (T)1e-4, (T)__builtin_huge_val(), t_hit, my_list);
+            if (!live) return;
+            for (int k = 0; k < 12; ++k) y[k] = 0.0;
+            y[2] = (double)idx;
+            if (idx >= 0) {
+                const V4 g = scene.geom[idx];
+                const V4 m0 = scene.mat0[idx];
+                const V4 m1 = scene.mat1[idx];
+                HitRec<T> rec;
+                make_hitrec<T>({g.x, g.y, g.z}, m0.x, o, d, t_hit, rec);
+                const int kind = (int)m0.z;
+                const DielConst<T> dc = {m0.w, m1.x, m1.y};
+                V3<T> vec = {0, 0, 0};
+                T vs = 1;
+                int todo = scatter_begin<T>(rng, kind, m0.y, d, rec, vec, vs, &dc);
+                const V3<T> att = attenuation_of<T>(kind, {m1.x, m1.y, m1.z});
+                if (todo == PATH_BALL) {
+                    V3<T> rp = {0, 0, 0};
+                    T len2 = 0;
+                    bool pending = true;
+                    while (pending) {
+                        len2 = reject_trial<T>(rng, true, rp);
+                        pending = !(len2 <= T(1));
+                    }
+                    todo = scatter_finish<T>(kind, vec, vs, rp, len2, vec);
+                }
+                if (todo == PATH_NORM) vec = normalize(vec);
+                st3(y + 3, rec.p); st3(y + 6, vec); st3(y + 9, att);
+            }
+            y[0] = as_f64(rng.x); y[1] = as_f64(rng.y);
         } break;
     }
 }

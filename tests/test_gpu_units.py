@@ -13,6 +13,9 @@ Slot layouts (8-byte slots: doubles for reals, raw uint64 for RNG state words), 
   op 7 rng         in  state[2]                            out state[2] u[4]
   op 8 hit_world   in  o[3] d[3] tmin tmax                 out idx t p[3] n[3] front
   op 9 ray_color   in  state[2] o[3] d[3] depth            out state[2] c[3] segments
+  op 26 shade      in  state[2] o[3] d[3]                  out state[2] idx o[3] d[3] att[3]
+                   (one bounce as the trace kernel composes it, on the uploaded material rows; a miss: the state as it
+                   came, idx -1, zeros -- tests/test_gpu_material_sweep.py)
 """
 import ctypes as C
 
