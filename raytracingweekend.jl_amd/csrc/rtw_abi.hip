@@ -163,7 +163,7 @@ long long local_tiles(const rtw_params *p) {
 int validate_batch(const void *cams, int32_t n_views, const rtw_params *p, const void *out) {
     if (!p) return fail(-1, "null params");
     if (!cams || !out) return fail(-1, "null argument");
-    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
+    if (n_views < 1) return fail(-2, "n_views must be >= 1");
     int nch, cs;
     if (int rc = validate_params(p, &nch, &cs)) return rc;
     if (p->shard_count != 1) return fail(-2, "a batched render renders whole frames (shard_count = %d)", p->shard_count);
@@ -243,18 +243,6 @@ int rtw_render_device_f32(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw
 }
 int rtw_render_device_f64(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, void *d_out, void *stream) {
     return render_device(s, c, p, d_out, stream);
-}
-int rtw_render_f32(const rtw_scene_f32 *s, const rtw_camera_f32 *c, const rtw_params *p, float *out) {
-    return render_host_f32(s, c, p, out);
-}
-int rtw_render_f64(const rtw_scene_f64 *s, const rtw_camera_f64 *c, const rtw_params *p, double *out) {
-    return render_host_f64(s, c, p, out);
-}
-int rtw_render_batch_f32(const rtw_scene_f32 *s, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, float *out) {
-    return render_host_batch_f32(s, cams, n_views, seeds, p, out);
-}
-int rtw_render_batch_f64(const rtw_scene_f64 *s, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, double *out) {
-    return render_host_batch_f64(s, cams, n_views, seeds, p, out);
 }
 int rtw_render_batch_device_f32(rtw_scene_handle s, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, void *stream) {
     return render_device_batch(s, cams, n_views, seeds, p, d_out, stream);

@@ -1008,8 +1008,8 @@ int enqueue_accum_features(rtw_scene_handle scene, const CamT *cam, const rtw_pa
     HIP_TRY(hipSetDevice(a->device));
     if (int rc = wait_for(a, stream)) return rc;
     int rc;
-    if (a->adaptive) rc = launch_features_t(scene, cam, p, 0, 1, d_out, stream, rec, ctx, a->d_tiles);
-    else rc = launch_features_t(scene, cam, p, a->ranges[0].first, a->ranges[0].second - a->ranges[0].first, d_out, stream, rec, ctx);
+    if (a->adaptive) rc = launch_features_t(scene, cam, 0, nullptr, p, 0, 1, d_out, stream, rec, ctx, a->d_tiles);
+    else rc = launch_features_t(scene, cam, 0, nullptr, p, a->ranges[0].first, a->ranges[0].second - a->ranges[0].first, d_out, stream, rec, ctx);
     if (rc) return rc;
     return mark(a, stream);
 }

@@ -1,10 +1,19 @@
 // rtw_denoise.hip -- the feature-guided denoiser (include/rtw_hip.h rtw_denoise_*): the checks that need no device, the launch sequence of
 // its kernels (rtw_denoise.hpp: prepare, then the level kernel once per a-trous pass, the last one writing the image) and the device-resident
-// entry points; rtw_filter_batch_*: the same sequence once for N frames (the batched level kernel).  (The host-buffer entry points and rtw_render_denoised_* live with the other cached-context paths in rtw_render_host.hip.)
+// entry points.  n_views == 0 is one frame; n_views >= 1 (rtw_filter_batch_*) the same sequence once for that many frames (the batched level
+// kernel).  (The host-buffer entry points, rtw_render_denoised_* and rtw_render_filtered_batch_* live with the other cached-context paths in rtw_render_host.hip.)
 #include "rtw_host.hpp"
 #include "rtw_denoise.hpp"
 
 namespace rtwh {
+
+// the frame of a denoiser call: a size, and no more tiles than the feature pass numbers (validate_features)
+static int check_frame(int32_t width, int32_t height) {
+    if (width < 1 || height < 1) return fail(-2, "width/height must be positive (got %d x %d)", width, height);
+    const long long n_tiles = (long long)((height + 7) / 8) * ((width + 7) / 8);
+    if (n_tiles >= (1ll << 31)) return fail(-5, "frame too large for one call: %lld tiles", n_tiles);
+    return 0;
+}
 
 // Everything about a denoiser call that is decided without a device.
 int validate_denoise(const rtw_denoise_t *d, int32_t width, int32_t height) {
@@ -17,19 +26,11 @@ int validate_denoise(const rtw_denoise_t *d, int32_t width, int32_t height) {
     if (d->device < -1) return fail(-2, "bad device %d", d->device);
     if (!(d->sigma_color > 0) || !std::isfinite(d->sigma_color)) return fail(-2, "sigma_color must be finite and positive");
     if (!(d->sigma_depth > 0) || !std::isfinite(d->sigma_depth)) return fail(-2, "sigma_depth must be finite and positive");
-    if (width < 1 || height < 1) return fail(-2, "width/height must be positive (got %d x %d)", width, height);
-    const long long n_tiles = (long long)((height + 7) / 8) * ((width + 7) / 8);         // the feature pass's own limit (validate_features)
-    if (n_tiles >= (1ll << 31)) return fail(-5, "frame too large for one call: %lld tiles", n_tiles);
-    return 0;
+    return check_frame(width, height);
 }
 
 // the workspace: the planes E, E', G and A of rtw_denoise.hpp, 4 elements per pixel each
 static long long plane_bytes(int32_t width, int32_t height, int elem_bytes) { return (long long)width * height * 4 * elem_bytes; }
-
-static bool overlap(const void *a, long long na, const void *b, long long nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + (uintptr_t)nb && y < x + (uintptr_t)na;
-}
 
 // Enqueue the denoiser on `stream` of the current device (validate_denoise has accepted the call).  d_noise non-null: the noise-guided
 // form -- the GUIDED instances of both kernels, the same launch sequence and workspace (the variance lives in the A plane's fourth slot).
@@ -40,11 +41,10 @@ template <typename T>
 int launch_denoise(const rtw_denoise_t *d, int32_t width, int32_t height, int n_views, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream,
                    const void *d_noise) {
     using V = typename rtw::DnVec<T>::type;
-    const bool batch = n_views > 0;
+    const bool batch = n_views != 0;
     if (batch && d_noise) return fail(-9, "internal: the noise-guided filter has no batched form");
-    const long long n_pix = (long long)width * height * (batch ? n_views : 1);
+    const long long frames = batch ? n_views : 1, n_pix = (long long)width * height * frames, pb = plane_bytes(width, height, sizeof(T)) * frames;
     char *w = (char *)d_work;
-    const long long pb = plane_bytes(width, height, sizeof(T)) * (batch ? n_views : 1);
     V *E[2] = {(V *)w, (V *)(w + pb)};
     V *G = (V *)(w + 2 * pb), *A = (V *)(w + 3 * pb);
     const bool demod = (d->flags & RTW_DENOISE_DEMODULATE) != 0;
@@ -99,43 +99,39 @@ int launch_denoise(const rtw_denoise_t *d, int32_t width, int32_t height, int n_
     return 0;
 }
 
-int launch_denoise_f32(const rtw_denoise_t *d, int32_t w, int32_t h, const void *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise) { return launch_denoise<float>(d, w, h, 0, img, feat, out, work, st, noise); }
-int launch_denoise_f64(const rtw_denoise_t *d, int32_t w, int32_t h, const void *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise) { return launch_denoise<double>(d, w, h, 0, img, feat, out, work, st, noise); }
-int launch_filter_batch_f32(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t n_views, const void *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_denoise<float>(d, w, h, n_views, img, feat, out, work, st, nullptr); }
-int launch_filter_batch_f64(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t n_views, const void *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_denoise<double>(d, w, h, n_views, img, feat, out, work, st, nullptr); }
+int launch_denoise_f32(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t n_views, const void *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise) { return launch_denoise<float>(d, w, h, n_views, img, feat, out, work, st, noise); }
+int launch_denoise_f64(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t n_views, const void *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise) { return launch_denoise<double>(d, w, h, n_views, img, feat, out, work, st, noise); }
 
 // A batched filter call (rtw_filter_batch_*): validate_denoise for the frame, and a batch whose pixels the launches can number (256 per workgroup)
 int validate_filter_batch(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views) {
     if (int rc = validate_denoise(d, width, height)) return rc;
-    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
+    if (n_views < 1) return fail(-2, "n_views must be >= 1");
     if ((double)width * (double)height * (double)n_views >= (double)(1ll << 39)) return fail(-5, "batch too large for one call: %d views of %d x %d pixels", n_views, width, height);
     return 0;
 }
 
-// the device-resident entry points; `guided`: rtw_guided_filter_device_* (d_noise: H*W elements of T), else d_noise is null
-// `batch`: rtw_filter_batch_device_* (not guided) -- n_views frames; the alignment and aliasing checks cover the whole batch's extents
+// The device-resident entry points.  n_views == 0: one frame, rtw_denoise_device_* or, with d_noise (H*W elements of T), rtw_guided_filter_device_*;
+// n_views != 0: rtw_filter_batch_device_* (no d_noise).  The alignment and aliasing checks cover the extents of all frames.
 template <typename T>
-int denoise_device(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_noise, bool guided, void *d_out, void *d_work, void *stream_v,
-                   bool batch = false, int32_t n_views = 0) {
+int denoise_device(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_image, const void *d_features, const void *d_noise, bool guided, void *d_out,
+                   void *d_work, void *stream_v) {
     if (!d || !d_image || !d_features || !d_out || !d_work || (guided && !d_noise)) return fail(-1, "null argument");
-    if (batch) { if (int rc = validate_filter_batch(d, width, height, n_views)) return rc; }
-    else if (int rc = validate_denoise(d, width, height)) return rc;
+    if (int rc = n_views ? validate_filter_batch(d, width, height, n_views) : validate_denoise(d, width, height)) return rc;
     if (((uintptr_t)d_work & 15u) || ((uintptr_t)d_features & 15u)) return fail(-2, "the workspace and the feature buffer must be 16-byte aligned");
     if (((uintptr_t)d_image & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
-    const long long n_pix = (long long)width * height * (batch ? n_views : 1), img_b = n_pix * 3 * (long long)sizeof(T), feat_b = n_pix * 8 * (long long)sizeof(T);
-    const long long work_b = 4 * plane_bytes(width, height, sizeof(T)) * (batch ? n_views : 1);
-    if (overlap(d_out, img_b, d_image, img_b) || overlap(d_out, img_b, d_features, feat_b) || overlap(d_out, img_b, d_work, work_b))
+    const size_t frames = n_views ? (size_t)n_views : 1, n_pix = (size_t)width * (size_t)height * frames;
+    const size_t img_b = n_pix * 3 * sizeof(T), feat_b = n_pix * 8 * sizeof(T), noise_b = n_pix * sizeof(T), work_b = 4 * (size_t)plane_bytes(width, height, sizeof(T)) * frames;
+    if (ranges_overlap(d_out, img_b, d_image, img_b) || ranges_overlap(d_out, img_b, d_features, feat_b) || ranges_overlap(d_out, img_b, d_work, work_b))
         return fail(-2, "d_out may not alias an input or the workspace");
-    if (overlap(d_work, work_b, d_image, img_b) || overlap(d_work, work_b, d_features, feat_b)) return fail(-2, "the workspace may not alias an input");
+    if (ranges_overlap(d_work, work_b, d_image, img_b) || ranges_overlap(d_work, work_b, d_features, feat_b)) return fail(-2, "the workspace may not alias an input");
     if (guided) {
-        const long long noise_b = n_pix * (long long)sizeof(T);
         if ((uintptr_t)d_noise & (sizeof(T) - 1)) return fail(-2, "the noise map must be aligned to its element type");
-        if (overlap(d_out, img_b, d_noise, noise_b)) return fail(-2, "d_out may not alias an input or the workspace");
-        if (overlap(d_work, work_b, d_noise, noise_b)) return fail(-2, "the workspace may not alias an input");
+        if (ranges_overlap(d_out, img_b, d_noise, noise_b)) return fail(-2, "d_out may not alias an input or the workspace");
+        if (ranges_overlap(d_work, work_b, d_noise, noise_b)) return fail(-2, "the workspace may not alias an input");
     }
     DeviceGuard guard;
     if (d->device >= 0) HIP_TRY(hipSetDevice(d->device));
-    return launch_denoise<T>(d, width, height, batch ? n_views : 0, d_image, d_features, d_out, d_work, (hipStream_t)stream_v, guided ? d_noise : nullptr);
+    return launch_denoise<T>(d, width, height, n_views, d_image, d_features, d_out, d_work, (hipStream_t)stream_v, guided ? d_noise : nullptr);
 }
 
 }  // namespace rtwh
@@ -146,64 +142,30 @@ extern "C" {
 
 int64_t rtw_denoise_work_bytes(int32_t width, int32_t height, int32_t elem_bytes) {
     if (elem_bytes != 4 && elem_bytes != 8) return fail(-2, "elem_bytes must be 4 or 8 (got %d)", elem_bytes);
-    if (width < 1 || height < 1) return fail(-2, "width/height must be positive (got %d x %d)", width, height);
-    const long long n_tiles = (long long)((height + 7) / 8) * ((width + 7) / 8);
-    if (n_tiles >= (1ll << 31)) return fail(-5, "frame too large for one call: %lld tiles", n_tiles);
+    if (int rc = check_frame(width, height)) return rc;
     return 4 * plane_bytes(width, height, elem_bytes);
 }
 int rtw_denoise_device_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, void *hip_stream) {
-    return denoise_device<float>(d, width, height, d_image, d_features, nullptr, false, d_out, d_work, hip_stream);
+    return denoise_device<float>(d, width, height, 0, d_image, d_features, nullptr, false, d_out, d_work, hip_stream);
 }
 int rtw_denoise_device_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, void *hip_stream) {
-    return denoise_device<double>(d, width, height, d_image, d_features, nullptr, false, d_out, d_work, hip_stream);
+    return denoise_device<double>(d, width, height, 0, d_image, d_features, nullptr, false, d_out, d_work, hip_stream);
 }
 int rtw_guided_filter_device_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_noise, void *d_out, void *d_work,
                                  void *hip_stream) {
-    return denoise_device<float>(d, width, height, d_image, d_features, d_noise, true, d_out, d_work, hip_stream);
+    return denoise_device<float>(d, width, height, 0, d_image, d_features, d_noise, true, d_out, d_work, hip_stream);
 }
 int rtw_guided_filter_device_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_noise, void *d_out, void *d_work,
                                  void *hip_stream) {
-    return denoise_device<double>(d, width, height, d_image, d_features, d_noise, true, d_out, d_work, hip_stream);
+    return denoise_device<double>(d, width, height, 0, d_image, d_features, d_noise, true, d_out, d_work, hip_stream);
 }
 int rtw_filter_batch_device_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_images, const void *d_features, void *d_out, void *d_work,
                                 void *hip_stream) {
-    return denoise_device<float>(d, width, height, d_images, d_features, nullptr, false, d_out, d_work, hip_stream, true, n_views);
+    return denoise_device<float>(d, width, height, batch_views(n_views), d_images, d_features, nullptr, false, d_out, d_work, hip_stream);
 }
 int rtw_filter_batch_device_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_images, const void *d_features, void *d_out, void *d_work,
                                 void *hip_stream) {
-    return denoise_device<double>(d, width, height, d_images, d_features, nullptr, false, d_out, d_work, hip_stream, true, n_views);
-}
-int rtw_filter_batch_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const float *images, const float *features, float *out) {
-    return filter_batch_host_f32(d, width, height, n_views, images, features, out);
-}
-int rtw_filter_batch_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const double *images, const double *features, double *out) {
-    return filter_batch_host_f64(d, width, height, n_views, images, features, out);
-}
-int rtw_render_filtered_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d,
-                                  float *out) {
-    return render_host_filtered_batch_f32(scene, cams, n_views, seeds, p, d, out);
-}
-int rtw_render_filtered_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d,
-                                  double *out) {
-    return render_host_filtered_batch_f64(scene, cams, n_views, seeds, p, d, out);
-}
-int rtw_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const float *image, const float *features, float *out) {
-    return denoise_host_f32(d, width, height, image, features, out);
-}
-int rtw_denoise_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const double *image, const double *features, double *out) {
-    return denoise_host_f64(d, width, height, image, features, out);
-}
-int rtw_render_denoised_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, float *out) {
-    return render_host_denoised_f32(scene, cam, p, d, out);
-}
-int rtw_render_denoised_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, double *out) {
-    return render_host_denoised_f64(scene, cam, p, d, out);
-}
-int rtw_accum_filtered_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle accum, int32_t guided, float *out) {
-    return accum_filtered_host_f32(scene, cam, p, d, accum, guided, out);
-}
-int rtw_accum_filtered_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle accum, int32_t guided, double *out) {
-    return accum_filtered_host_f64(scene, cam, p, d, accum, guided, out);
+    return denoise_device<double>(d, width, height, batch_views(n_views), d_images, d_features, nullptr, false, d_out, d_work, hip_stream);
 }
 
 }  // extern "C"

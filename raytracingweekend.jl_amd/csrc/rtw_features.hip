@@ -1,7 +1,8 @@
 // rtw_features.hip -- first-hit feature buffers (include/rtw_hip.h rtw_render_features_*): the checks that need no device, ONE launch of the
 // feature kernel (rtw_features.hpp) per call -- its own parameters, instance and grid; camera, numerics mode and scene view (rtw_scene_view.hpp) and the
 // record sequence (rtw_host.hpp begin_record / run_record) are the ones launch_render (rtw_launch.hip) uses --, and the device-resident entry points.
-// rtw_render_features_batch_*: the same launch with a BATCH instance over N views, whose cameras and seeds go up with the record (upload_views, rtw_launch.hip).
+// n_views == 0 is the single-view call; n_views >= 1 (rtw_render_features_batch_*) the same launch with a BATCH instance over that many views,
+// whose cameras and seeds go up with the record (upload_views, rtw_launch.hip).
 // (The host-buffer entry points live with the other cached-context paths in rtw_render_host.hip.)
 #include "rtw_scene_view.hpp"
 #include "rtw_features.hpp"
@@ -48,11 +49,20 @@ int validate_features_batch(const void *cams, int32_t n_views, const rtw_params 
 inline int upload_views_t(RenderRec *r, const rtw_camera_f32 *c, int n, const uint64_t *sd, uint64_t s, hipStream_t st, const void **dc, const unsigned long long **ds) { return upload_views_f32(r, c, n, sd, s, st, dc, ds); }
 inline int upload_views_t(RenderRec *r, const rtw_camera_f64 *c, int n, const uint64_t *sd, uint64_t s, hipStream_t st, const void **dc, const unsigned long long **ds) { return upload_views_f64(r, c, n, sd, s, st, dc, ds); }
 
+// The feature kernel's instances over the scan (matrix pipe or VALU) and where the scene lives (LDS or global memory), written once for the
+// plain, the TILED and the BATCH form (TILED && BATCH is not built).  FIXED (mfma && lds_scene): the one instance with the default numerics mode compiled in.
+template <typename T, bool TILED, bool BATCH, bool FIXED = false>
+const void *feature_instance(bool mfma, bool lds_scene) {
+    if constexpr (FIXED) return (const void *)rtw::features_kernel<T, true, true, rtw::NUM_REFERENCE, TILED, BATCH>;
+    if (mfma) return lds_scene ? (const void *)rtw::features_kernel<T, true, true, -1, TILED, BATCH> : (const void *)rtw::features_kernel<T, true, false, -1, TILED, BATCH>;
+    return lds_scene ? (const void *)rtw::features_kernel<T, false, true, -1, TILED, BATCH> : (const void *)rtw::features_kernel<T, false, false, -1, TILED, BATCH>;
+}
+
 template <typename T, typename CamT>
 int launch_features(rtw_scene_handle scene, const CamT *cam, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out,
                     hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks) {
     if (!scene || !cam || !p || !d_out) return fail(-1, "null argument");
-    const bool batch = n_views > 0;
+    const bool batch = n_views != 0;
     if (batch && d_tile_chunks) return fail(-9, "internal: the tiled feature pass has no batched form");
     int nch, cs;
     if (batch) { if (int rc = validate_features_batch(cam, n_views, p, chunk_begin, chunk_count, d_out, &nch, &cs)) return rc; }
@@ -82,25 +92,12 @@ int launch_features(rtw_scene_handle scene, const CamT *cam, int n_views, const 
     PlainView<T> V;
     if (int rc = plain_scene_view<T>(scene, mfma, numerics, &V)) return rc;
     const size_t lds_bytes = (batch ? rtw::feat_fixed_lds_bytes<T, true>() : rtw::feat_fixed_lds_bytes<T>()) + (V.lds_scene ? V.scene_bytes : 0);
-    typedef void (*kern_t)(rtw::FeatParams, rtw::Camera<T>, rtw::DevScene<T>, T *, rtw::DevCounters *, const int *);
-    typedef void (*bkern_t)(rtw::FeatParams, rtw::Camera<T>, rtw::DevScene<T>, T *, rtw::DevCounters *, rtw::FeatViews<T>);
     const bool tiled = d_tile_chunks != nullptr;
-    kern_t kern = nullptr;
-    bkern_t bkern = nullptr;
-    if (batch) {
-        if (mfma) bkern = V.lds_scene ? (bkern_t)rtw::features_kernel<T, true, true, -1, false, true> : (bkern_t)rtw::features_kernel<T, true, false, -1, false, true>;
-        else bkern = V.lds_scene ? (bkern_t)rtw::features_kernel<T, false, true, -1, false, true> : (bkern_t)rtw::features_kernel<T, false, false, -1, false, true>;
-    } else if (!tiled) {
-        if (mfma) kern = V.lds_scene ? (kern_t)rtw::features_kernel<T, true, true> : (kern_t)rtw::features_kernel<T, true, false>;
-        else kern = V.lds_scene ? (kern_t)rtw::features_kernel<T, false, true> : (kern_t)rtw::features_kernel<T, false, false>;
-    } else {
-        if (mfma) kern = V.lds_scene ? (kern_t)rtw::features_kernel<T, true, true, -1, true> : (kern_t)rtw::features_kernel<T, true, false, -1, true>;
-        else kern = V.lds_scene ? (kern_t)rtw::features_kernel<T, false, true, -1, true> : (kern_t)rtw::features_kernel<T, false, false, -1, true>;
-    }
     // the default numerics mode of the headline variant (scene in LDS, matrix pipe): the mode fixed at compile time
     const bool fixed = mfma && V.lds_scene && numerics == rtw::NUM_REFERENCE;
-    if (fixed && batch) bkern = (bkern_t)rtw::features_kernel<T, true, true, rtw::NUM_REFERENCE, false, true>;
-    else if (fixed) kern = tiled ? (kern_t)rtw::features_kernel<T, true, true, rtw::NUM_REFERENCE, true> : (kern_t)rtw::features_kernel<T, true, true, rtw::NUM_REFERENCE>;
+    const void *kern = batch ? feature_instance<T, false, true>(mfma, V.lds_scene) : !tiled ? feature_instance<T, false, false>(mfma, V.lds_scene) : feature_instance<T, true, false>(mfma, V.lds_scene);
+    // (asked for after the table, so that the instances are emitted in the order they always were and the object's device code stays the same bytes)
+    if (fixed) kern = batch ? feature_instance<T, false, true, true>(mfma, V.lds_scene) : tiled ? feature_instance<T, true, false, true>(mfma, V.lds_scene) : feature_instance<T, false, false, true>(mfma, V.lds_scene);
     // (a batch: its tiles numbered flat, v * n_tiles + t -- validate_features_batch: fewer than 2^31)
     const unsigned total_tiles = batch ? K.n_tiles * (unsigned)n_views : K.n_tiles;
     const unsigned grid = (total_tiles + RTW_FEATURE_WAVES - 1u) / RTW_FEATURE_WAVES;
@@ -112,68 +109,43 @@ int launch_features(rtw_scene_handle scene, const CamT *cam, int n_views, const 
                 (int)V.lds_scene, (int)mfma, (int)fixed, (int)batch, (int)tiled, (int)tiled, lds_bytes);
 
     if (int rc = begin_record(ctx.get(), scene, nch, (int)grid, 64 * RTW_FEATURE_WAVES, offsetof(rtw::DevCounters, t_first), stream, rec_out)) return rc;
+    rtw::FeatViews<T> FV;
+    memset(&FV, 0, sizeof FV);
     if (batch) {
-        rtw::FeatViews<T> FV;
-        memset(&FV, 0, sizeof FV);
         const void *d_cams = nullptr;
         if (int rc = upload_views_t(*rec_out, cam, n_views, seeds, p->seed, stream, &d_cams, &FV.seeds)) return rc;
         FV.cams = (const rtw::Camera<T> *)d_cams;
         FV.total_tiles = total_tiles;
         FV.view_elems = (unsigned long long)p->width * (unsigned long long)p->height * RTW_FEATURE_CHANNELS;
-        return run_record(*rec_out, stream, [&] { hipLaunchKernelGGL(bkern, dim3(grid), dim3(64 * RTW_FEATURE_WAVES), lds_bytes, stream, K, C, V.scene, (T *)d_out, (*rec_out)->ctr, FV); });
     }
-    return run_record(*rec_out, stream, [&] { hipLaunchKernelGGL(kern, dim3(grid), dim3(64 * RTW_FEATURE_WAVES), lds_bytes, stream, K, C, V.scene, (T *)d_out, (*rec_out)->ctr, d_tile_chunks); });
+    // the kernel's last argument (rtw::FeatLastArg): the views of a BATCH instance, else the tiles' chunk counts (null but for a TILED one)
+    void *args[] = {&K, (void *)&C, &V.scene, &d_out, &(*rec_out)->ctr, batch ? (void *)&FV : (void *)&d_tile_chunks};
+    return run_record(*rec_out, stream, [&] { (void)hipLaunchKernel(kern, dim3(grid), dim3(64 * RTW_FEATURE_WAVES), args, lds_bytes, stream); });
 }
 
-int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream,
-                        RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks) {
-    return launch_features<float>(scene, cam, 0, nullptr, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks);
+int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out,
+                        hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks) {
+    return launch_features<float>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks);
 }
-int launch_features_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count,
-                              void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out) {
-    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
-    return launch_features<float>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, nullptr);
-}
-int launch_features_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count,
-                              void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out) {
-    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
-    return launch_features<double>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, nullptr);
-}
-int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream,
-                        RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks) {
-    return launch_features<double>(scene, cam, 0, nullptr, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks);
+int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out,
+                        hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks) {
+    return launch_features<double>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks);
 }
 
+// The device-resident entry points rtw_render_features_device_* (n_views == 0) and rtw_render_features_batch_device_* (n_views != 0).
 template <typename CamT>
-int features_device(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, void *stream_v) {
-    if (!p) return fail(-1, "null params");
-    if (!scene || !cam || !d_out) return fail(-1, "null argument");
-    int nch, cs;
-    if (int rc = validate_features(p, chunk_begin, chunk_count, &nch, &cs)) return rc;
-    if (((uintptr_t)d_out & 15u) != 0) return fail(-2, "the feature buffer must be 16-byte aligned");
-    DeviceGuard guard;
-    RenderRec *rec = nullptr;
-    CtxPtr ctx;
-    release_last();
-    int rc = launch_features_t(scene, cam, p, chunk_begin, chunk_count, d_out, (hipStream_t)stream_v, &rec, &ctx);
-    hold_last(rec, ctx);               // (also on a late error: released by the next call)
-    return rc;
-}
-
-// rtw_render_features_batch_device_*
-template <typename CamT>
-int features_batch_device(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out,
-                          void *stream_v) {
+int features_device(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out,
+                    void *stream_v) {
     if (!p) return fail(-1, "null params");
     if (!scene || !cams || !d_out) return fail(-1, "null argument");
     int nch, cs;
-    if (int rc = validate_features_batch(cams, n_views, p, chunk_begin, chunk_count, d_out, &nch, &cs)) return rc;
+    if (int rc = n_views ? validate_features_batch(cams, n_views, p, chunk_begin, chunk_count, d_out, &nch, &cs) : validate_features(p, chunk_begin, chunk_count, &nch, &cs)) return rc;
     if (((uintptr_t)d_out & 15u) != 0) return fail(-2, "the feature buffer must be 16-byte aligned");
     DeviceGuard guard;
     RenderRec *rec = nullptr;
     CtxPtr ctx;
     release_last();
-    int rc = launch_features_batch_t(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, (hipStream_t)stream_v, &rec, &ctx);
+    int rc = launch_features_t(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, (hipStream_t)stream_v, &rec, &ctx);
     hold_last(rec, ctx);               // (also on a late error: released by the next call)
     return rc;
 }
@@ -185,33 +157,18 @@ using namespace rtwh;
 extern "C" {
 
 int rtw_render_features_device_f32(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, void *stream) {
-    return features_device(s, c, p, chunk_begin, chunk_count, d_out, stream);
+    return features_device(s, c, 0, nullptr, p, chunk_begin, chunk_count, d_out, stream);
 }
 int rtw_render_features_device_f64(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, void *stream) {
-    return features_device(s, c, p, chunk_begin, chunk_count, d_out, stream);
+    return features_device(s, c, 0, nullptr, p, chunk_begin, chunk_count, d_out, stream);
 }
-int rtw_render_features_f32(const rtw_scene_f32 *s, const rtw_camera_f32 *c, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, float *out) {
-    return render_host_features_f32(s, c, p, chunk_begin, chunk_count, out);
-}
-int rtw_render_features_f64(const rtw_scene_f64 *s, const rtw_camera_f64 *c, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, double *out) {
-    return render_host_features_f64(s, c, p, chunk_begin, chunk_count, out);
-}
-
 int rtw_render_features_batch_device_f32(rtw_scene_handle s, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin,
                                          int32_t chunk_count, void *d_out, void *stream) {
-    return features_batch_device(s, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream);
+    return features_device(s, cams, batch_views(n_views), seeds, p, chunk_begin, chunk_count, d_out, stream);
 }
 int rtw_render_features_batch_device_f64(rtw_scene_handle s, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin,
                                          int32_t chunk_count, void *d_out, void *stream) {
-    return features_batch_device(s, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream);
-}
-int rtw_render_features_batch_f32(const rtw_scene_f32 *s, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin,
-                                  int32_t chunk_count, float *out) {
-    return render_host_features_batch_f32(s, cams, n_views, seeds, p, chunk_begin, chunk_count, out);
-}
-int rtw_render_features_batch_f64(const rtw_scene_f64 *s, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin,
-                                  int32_t chunk_count, double *out) {
-    return render_host_features_batch_f64(s, cams, n_views, seeds, p, chunk_begin, chunk_count, out);
+    return features_device(s, cams, batch_views(n_views), seeds, p, chunk_begin, chunk_count, d_out, stream);
 }
 
 }  // extern "C"

@@ -1,9 +1,10 @@
 // rtw_host.hpp -- host-side internals of librtw_hip.so shared by its translation units (nothing here is part of the C ABI):
-//   rtw_abi.hip          the extern "C" entry points (include/rtw_hip.h), argument validation, the per-device contexts and the per-render
+//   rtw_abi.hip          the extern "C" entry points (include/rtw_hip.h) that no other unit defines, argument validation, the per-device contexts and the per-render
 //                        records behind rtw_stats(): begin_record / run_record, the one sequence around every launch that has a record
 //   rtw_scene.hip        scene upload: SoA rows, kd split of the group-cull layout, the f16-split operands of the matrix-pipe filter
 //   rtw_launch.hip       one render = one launch of the trace kernel (rtw_kernels.hpp / rtw_pool.hpp): geometry, occupancy, job shape, views
-//   rtw_render_host.hip  the host-buffer entry points: cached per-device context (scene, stream, image), ONE one-device path (render_one_device) or a device list
+//   rtw_render_host.hip  every host-buffer entry point: cached per-device context (scene, stream, buffer), ONE one-device path (render_one_device) behind render,
+//                        batch, feature and render + filter calls, the filter on host buffers, or a device list
 //   rtw_multi.hip        what a device list needs: peer access, the on-demand RCCL binding, the un-tile kernel
 //   rtw_batch_accum_f32.hip / _f64.hip  the BATCH && ACCUM instances of the trace kernel (rtw_instances.hpp: the kernel-instance table), a unit per precision
 //   rtw_accum.hip        progressive render: the accumulator object, its passes, merge / resolve kernels, export / import
@@ -247,14 +248,12 @@ TraceInstance batch_accum_kernel_f32(bool cull, bool mfma, bool lds_scene, bool 
 TraceInstance batch_accum_kernel_f64(bool cull, bool mfma, bool lds_scene, bool fixed, bool adapt);
 // rtw_abi.hip: the checks of a batched render that need no device (include/rtw_hip.h rtw_render_batch_f32)
 int validate_batch(const void *cams, int32_t n_views, const rtw_params *p, const void *out);
-
-// rtw_render_host.hip
-int render_host_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, float *out);
-int render_host_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, double *out);
-int render_host_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, float *out);
-int render_host_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, double *out);
-int render_host_features_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, float *out);
-int render_host_features_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, double *out);
+// Below the C ABI n_views == 0 is the single-view call and n_views >= 1 a batch of that many.  A batched entry point hands its caller's count
+// down through batch_views: a count that is no batch stays one the batch's validation refuses (-2) and never selects the single-view path.
+inline int32_t batch_views(int32_t n_views) { return n_views < 1 ? -1 : n_views; }
+// do the byte ranges [a, a + na) and [b, b + nb) share a byte?
+inline bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; }
+// (rtw_render_host.hip defines the host-buffer entry points of the C ABI itself: nothing of it is declared here)
 
 // rtw_multi.hip
 int ensure_peer(const CtxPtr &ctx, int dev, int root, bool *direct);
@@ -283,50 +282,34 @@ bool accum_is_adaptive(rtw_accum_handle a);
 int validate_accum_noise(rtw_accum_handle a, bool f64);                                             // adaptive, its last call finished, the call's precision
 int enqueue_accum_noise(rtw_accum_handle a, bool f64, void *d_out, hipStream_t stream);               // H*W elements of T
 int enqueue_accum_resolve(rtw_accum_handle a, bool f64, int32_t gamma, void *d_out, hipStream_t stream);   // rtw_accum_resolve_*'s own path
-int accum_filtered_host_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle a, int32_t guided, float *out);    // rtw_render_host.hip
-int accum_filtered_host_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle a, int32_t guided, double *out);
 
 // rtw_features.hip -- first-hit feature buffers (include/rtw_hip.h rtw_render_features_*).  validate_features: the checks that need no device
-// (the render, whole frames on one device, the chunk range); launch_features: enqueue the feature kernel for the chunks [chunk_begin,
-// chunk_begin + chunk_count) on `stream`, `rec` receives the counters and the kernel's events like a render's.
+// (the render, whole frames on one device, the chunk range); validate_features_batch: validate_batch's rules together with those and a tile
+// count the one launch can number.
 int validate_features(const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, int *n_chunks, int *chunk_spp);
-// d_tile_chunks non-null: the pass over what an adaptive accumulator holds -- tile t gets the chunks [0, d_tile_chunks[t]) (device memory, the
-// accumulator's C_t array), the call's own range is validated and otherwise unused.
-int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks = nullptr);
-int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks = nullptr);
-inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const int *tc = nullptr) { return launch_features_f32(s, c, p, b, n, d, st, r, x, tc); }
-inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const int *tc = nullptr) { return launch_features_f64(s, c, p, b, n, d, st, r, x, tc); }
-// The batched feature pass (include/rtw_hip.h rtw_render_features_batch_*): validate_features_batch = validate_batch's rules together with
-// validate_features' and a tile count the one launch can number; launch_features_batch: ONE launch of a BATCH instance for n_views >= 1
-// cameras, seeds (null: p->seed) and buffers of W*H*8 elements behind d_out.
 int validate_features_batch(const void *cams, int32_t n_views, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, const void *out, int *n_chunks, int *chunk_spp);
-int launch_features_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
-int launch_features_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
-inline int launch_features_batch_t(rtw_scene_handle s, const rtw_camera_f32 *c, int nv, const uint64_t *sd, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_features_batch_f32(s, c, nv, sd, p, b, n, d, st, r, x); }
-inline int launch_features_batch_t(rtw_scene_handle s, const rtw_camera_f64 *c, int nv, const uint64_t *sd, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return launch_features_batch_f64(s, c, nv, sd, p, b, n, d, st, r, x); }
+// launch_features: enqueue the feature kernel for the chunks [chunk_begin, chunk_begin + chunk_count) on `stream`, `rec` receives the counters
+// and the kernel's events like a render's.  n_views as for launch_render: 0 -- the one camera `cams` points to; >= 1 -- ONE launch of a BATCH
+// instance for that many cameras, seeds (null: p->seed) and buffers of W*H*8 elements behind d_out.
+// d_tile_chunks non-null (n_views == 0 only): the pass over what an adaptive accumulator holds -- tile t gets the chunks [0, d_tile_chunks[t])
+// (device memory, the accumulator's C_t array), the call's own range is validated and otherwise unused.
+int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks = nullptr);
+int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks = nullptr);
+inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f32 *c, int nv, const uint64_t *sd, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const int *tc = nullptr) { return launch_features_f32(s, c, nv, sd, p, b, n, d, st, r, x, tc); }
+inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f64 *c, int nv, const uint64_t *sd, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const int *tc = nullptr) { return launch_features_f64(s, c, nv, sd, p, b, n, d, st, r, x, tc); }
 
-// rtw_denoise.hip -- the feature-guided denoiser (include/rtw_hip.h rtw_denoise_*).  validate_denoise: the checks that need no device;
-// launch_denoise: enqueue its kernels on `stream` of the current device (d_work: rtw_denoise_work_bytes bytes, 16-byte aligned).
+// rtw_denoise.hip -- the feature-guided denoiser (include/rtw_hip.h rtw_denoise_*, rtw_filter_batch_*).  validate_denoise: the checks of one
+// frame that need no device; validate_filter_batch: those, n_views and the batch's size.
 int validate_denoise(const rtw_denoise_t *d, int32_t width, int32_t height);
-// d_noise non-null: the noise-guided form (rtw_guided_filter_device_*): H*W elements of T, the per-pixel relative noise.
-int launch_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream, const void *d_noise = nullptr);
-int launch_denoise_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream, const void *d_noise = nullptr);
-// The batched filter (rtw_filter_batch_*): n_views frames of one size in prepare + `levels` launches; every buffer and every plane of the
-// workspace (n_views * rtw_denoise_work_bytes bytes) holds the views one behind the other.  validate_filter_batch: validate_denoise, n_views, the batch's size.
 int validate_filter_batch(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views);
-int launch_filter_batch_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_images, const void *d_features, void *d_out, void *d_work, hipStream_t stream);
-int launch_filter_batch_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_images, const void *d_features, void *d_out, void *d_work, hipStream_t stream);
-// rtw_render_host.hip: its host-buffer entry points
-int render_host_features_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, float *out);
-int render_host_features_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, double *out);
-int filter_batch_host_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const float *images, const float *features, float *out);
-int filter_batch_host_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const double *images, const double *features, double *out);
-int render_host_filtered_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, float *out);
-int render_host_filtered_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, double *out);
-int denoise_host_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const float *image, const float *features, float *out);
-int denoise_host_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const double *image, const double *features, double *out);
-int render_host_denoised_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, float *out);
-int render_host_denoised_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, double *out);
+// launch_denoise: enqueue its kernels on `stream` of the current device.  n_views == 0: one frame, d_work of rtw_denoise_work_bytes bytes
+// (16-byte aligned); d_noise non-null: the noise-guided form (rtw_guided_filter_device_*), H*W elements of T, the per-pixel relative noise.
+// n_views >= 1 (no d_noise): that many frames of one size in prepare + `levels` launches; every buffer and every plane of the workspace
+// (n_views * rtw_denoise_work_bytes bytes) holds the views one behind the other.
+int launch_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream, const void *d_noise = nullptr);
+int launch_denoise_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream, const void *d_noise = nullptr);
+inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t nv, const float *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise = nullptr) { return launch_denoise_f32(d, w, h, nv, img, feat, out, work, st, noise); }
+inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t nv, const double *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise = nullptr) { return launch_denoise_f64(d, w, h, nv, img, feat, out, work, st, noise); }
 
 // rtw_unit.hip
 int run_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene, const rtw_camera_f32 *cam);

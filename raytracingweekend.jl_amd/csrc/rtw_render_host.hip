@@ -1,7 +1,7 @@
-// rtw_render_host.hip -- the host-buffer entry points rtw_render_f32/_f64 (what the Julia ccall binds; replaces src/render.jl:8-44):
-// a cached per-device context (uploaded scene, stream, device image), one device (render_one_device: the path the batched and the
-// feature entry points share) or a device list (tiles dealt round-robin, shards gathered on the first device by peer copies or ONE RCCL
-// reduce: rtw_multi.hip), one D2H of the frame.
+// rtw_render_host.hip -- the host-buffer entry points of the C ABI (rtw_render_f32/_f64 is what the Julia ccall binds; replaces src/render.jl:8-44):
+// a cached per-device context (uploaded scene, stream, device buffer), one device (render_one_device: the path the plain, the batched, the
+// feature and the render + filter entry points share) or a device list (tiles dealt round-robin, shards gathered on the first device by peer
+// copies or ONE RCCL reduce: rtw_multi.hip), one D2H of the result.  The single and the batched form of a call share one body (n_views == 0: single).
 #include "rtw_host.hpp"
 
 namespace rtwh {
@@ -109,11 +109,13 @@ int copy_out(HostCtx *hc, const void *d_src, void *out, size_t bytes) {
 }
 
 
-// The one-device host path of every host-buffer entry point: a leased context of `device` (negative: the current device) with the scene uploaded,
-// `elems` elements of device image, ONE launch -- launch(hc, q, &rec, &ctx) enqueues it on hc->stream into hc->d_img, q: the caller's params bound
-// to the lease's device --, ONE D2H into `out`, the counters into this thread's last render.  (elems == 0, render_host's alone: a compact shard that owns no tile)
+// The one-device host path of every host-buffer entry point that renders: a leased context of `device` (negative: the current device) with the
+// scene uploaded and `dev_bytes` bytes of device buffer, ONE launch sequence -- launch(hc, q, &rec, &ctx) enqueues it on hc->stream into
+// hc->d_img, q: the caller's params bound to the lease's device --, ONE D2H of the `out_bytes` bytes at `out_off` into `out`, the counters of
+// `rec` into this thread's last render.  The stream has drained when it returns, on success and on an error.
+// (dev_bytes == 0, render_host's alone: a compact shard that owns no tile)
 template <typename T, typename SceneT, typename Launch>
-int render_one_device(int device, const SceneT *scene, const rtw_params *p, size_t elems, T *out, Launch launch) {
+int render_one_device(int device, const SceneT *scene, const rtw_params *p, size_t dev_bytes, size_t out_off, size_t out_bytes, T *out, Launch launch) {
     if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
     std::vector<unsigned char> key;
     scene_key_of(scene, sizeof(T) == 8, key);
@@ -123,12 +125,12 @@ int render_one_device(int device, const SceneT *scene, const rtw_params *p, size
     if (int rc = ensure_scene<T>(hc, scene, key)) return rc;
     rtw_params q = *p;
     q.device = hc->device; q.n_devices = 0; q.device_ids = nullptr;
-    if (elems == 0) { g_last.resolved = true; return 0; }
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, elems * sizeof(T))) return rc;
+    if (dev_bytes == 0) { g_last.resolved = true; return 0; }
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, dev_bytes)) return rc;
     RenderRec *rec = nullptr;
     CtxPtr rctx;
     int rc = launch(hc, q, &rec, &rctx);
-    if (!rc) rc = copy_out(hc, hc->d_img, out, elems * sizeof(T));
+    if (!rc) rc = copy_out(hc, (const char *)hc->d_img + out_off, out, out_bytes);
     if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
     if (!rc) rc = resolve_rec(rec, &g_last.agg);
     if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
@@ -161,8 +163,8 @@ int render_host(const SceneT *scene, const CamT *cam, const rtw_params *p, T *ou
     }
     if (devs.size() <= 1 && !((p->flags & RTW_FLAG_RCCL_REDUCE) && devs.size() == 1)) {
         // ---- one device: render into the cached device image, one D2H ----
-        const size_t elems = (p->flags & RTW_FLAG_COMPACT_TILES) ? (size_t)local_tiles(p) * 64 * 3 : (size_t)p->width * (size_t)p->height * 3;
-        return render_one_device(devs.size() == 1 ? devs[0] : p->device, scene, p, elems, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+        const size_t bytes = ((p->flags & RTW_FLAG_COMPACT_TILES) ? (size_t)local_tiles(p) * 64 * 3 : (size_t)p->width * (size_t)p->height * 3) * sizeof(T);
+        return render_one_device(devs.size() == 1 ? devs[0] : p->device, scene, p, bytes, 0, bytes, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
             q.flags &= ~RTW_FLAG_RCCL_REDUCE;              // (one device: nothing to reduce)
             return launch_render_t(hc->scene, cam, 0, nullptr, &q, hc->d_img, hc->stream, rec, rctx);
         });
@@ -315,92 +317,56 @@ int render_host_batch(const SceneT *scene, const CamT *cams, int32_t n_views, co
     if (!scene) return fail(-1, "null argument");
     DeviceGuard guard;
     release_last();
-    return render_one_device(p->device, scene, p, (size_t)n_views * (size_t)p->width * (size_t)p->height * 3, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+    const size_t bytes = (size_t)n_views * (size_t)p->width * (size_t)p->height * 3 * sizeof(T);
+    return render_one_device(p->device, scene, p, bytes, 0, bytes, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
         return launch_render_t(hc->scene, cams, n_views, seeds, &q, hc->d_img, hc->stream, rec, rctx);
     });
 }
 
-// First-hit feature buffers (rtw_render_features_f32/_f64): the one-device path above with a device buffer of W x H x 8 elements, ONE launch of
-// the feature kernel (rtw_features.hip), ONE D2H.
-template <typename T, typename SceneT, typename CamT>
-int render_host_features(const SceneT *scene, const CamT *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, T *out) {
-    if (!p) return fail(-1, "null params");
-    if (!scene || !cam || !out) return fail(-1, "null argument");
-    int nch, cs;
-    if (int rc = validate_features(p, chunk_begin, chunk_count, &nch, &cs)) return rc;
-    DeviceGuard guard;
-    release_last();
-    return render_one_device(p->device, scene, p, (size_t)p->width * (size_t)p->height * RTW_FEATURE_CHANNELS, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
-        return launch_features_t(hc->scene, cam, &q, chunk_begin, chunk_count, hc->d_img, hc->stream, rec, rctx);
-    });
-}
+// In everything below n_views == 0 is the single-view entry point and n_views != 0 the batched one (rtw_host.hpp batch_views): each keeps its
+// own validation, what follows it is shared.
 
-// N views' feature buffers (rtw_render_features_batch_f32/_f64): the one-device path with a device buffer of N x W x H x 8 elements, ONE
-// launch of a BATCH instance of the feature kernel, ONE D2H.
+// First-hit feature buffers (rtw_render_features_* / rtw_render_features_batch_*): the one-device path above with a device buffer of W x H x 8
+// elements per view, ONE launch of the feature kernel (rtw_features.hip; a BATCH instance for a batch), ONE D2H.
 template <typename T, typename SceneT, typename CamT>
-int render_host_features_batch(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, T *out) {
+int render_host_features(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, T *out) {
     if (!p) return fail(-1, "null params");
     if (!scene || !cams || !out) return fail(-1, "null argument");
     int nch, cs;
-    if (int rc = validate_features_batch(cams, n_views, p, chunk_begin, chunk_count, out, &nch, &cs)) return rc;
+    if (int rc = n_views ? validate_features_batch(cams, n_views, p, chunk_begin, chunk_count, out, &nch, &cs) : validate_features(p, chunk_begin, chunk_count, &nch, &cs)) return rc;
     DeviceGuard guard;
     release_last();
-    return render_one_device(p->device, scene, p, (size_t)n_views * (size_t)p->width * (size_t)p->height * RTW_FEATURE_CHANNELS, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
-        return launch_features_batch_t(hc->scene, cams, n_views, seeds, &q, chunk_begin, chunk_count, hc->d_img, hc->stream, rec, rctx);
+    const size_t bytes = (size_t)(n_views ? n_views : 1) * (size_t)p->width * (size_t)p->height * RTW_FEATURE_CHANNELS * sizeof(T);
+    return render_one_device(p->device, scene, p, bytes, 0, bytes, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+        return launch_features_t(hc->scene, cams, n_views, seeds, &q, chunk_begin, chunk_count, hc->d_img, hc->stream, rec, rctx);
     });
 }
 
-inline int launch_filter_batch_t(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t n, const float *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_filter_batch_f32(d, w, h, n, img, feat, out, work, st); }
-inline int launch_filter_batch_t(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t n, const double *img, const void *feat, void *out, void *work, hipStream_t st) { return launch_filter_batch_f64(d, w, h, n, img, feat, out, work, st); }
-inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, const float *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise = nullptr) { return launch_denoise_f32(d, w, h, img, feat, out, work, st, noise); }
-inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, const double *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise = nullptr) { return launch_denoise_f64(d, w, h, img, feat, out, work, st, noise); }
-
-// The denoiser's regions inside a context's device buffer: image, features, output, workspace -- each starts on a 16-byte boundary.
-// (n_views > 1: a batch -- every region holds the views one behind the other)
+// The denoiser's regions inside a context's device buffer: image, features, output, workspace -- each starts on a 16-byte boundary and holds
+// the frames of a batch one behind the other.
 template <typename T> struct DenoiseRegions {
     size_t img_b, feat_b, off_feat, off_out, off_work, total;
-    DenoiseRegions(int32_t width, int32_t height, int32_t n_views = 1) {
-        const size_t n = (size_t)width * (size_t)height * (size_t)n_views;
+    DenoiseRegions(int32_t width, int32_t height, int32_t n_views) {
+        const size_t frames = n_views ? (size_t)n_views : 1, n = (size_t)width * (size_t)height * frames;
         auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
         img_b = n * 3 * sizeof(T); feat_b = n * RTW_FEATURE_CHANNELS * sizeof(T);
         off_feat = up(img_b); off_out = off_feat + up(feat_b); off_work = off_out + up(img_b);
-        total = off_work + (size_t)rtw_denoise_work_bytes(width, height, (int32_t)sizeof(T)) * (size_t)n_views;
+        total = off_work + (size_t)rtw_denoise_work_bytes(width, height, (int32_t)sizeof(T)) * frames;
+    }
+    // the filter over the regions of `base`, on `stream`
+    int launch(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, char *base, hipStream_t stream, const void *d_noise = nullptr) const {
+        return launch_denoise_t(d, width, height, n_views, (const T *)base, base + off_feat, base + off_out, base + off_work, stream, d_noise);
     }
 };
 
-// The denoiser on host buffers (rtw_denoise_f32/_f64): a leased context of the device (its stream and buffer; the scene it may hold is left
-// alone), two H2D, the kernels, ONE D2H.  This thread's last render (rtw_stats) is not touched.
+// The filter on host buffers (rtw_denoise_* / rtw_filter_batch_*): a leased context of the device (its stream and buffer; the scene it may hold
+// is left alone), two H2D, prepare + `levels` launches for any number of frames, ONE D2H.  This thread's last render (rtw_stats) is not touched.
 template <typename T>
-int denoise_host(const rtw_denoise_t *d, int32_t width, int32_t height, const T *image, const T *features, T *out) {
-    if (!d || !image || !features || !out) return fail(-1, "null argument");
-    if (int rc = validate_denoise(d, width, height)) return rc;
-    const DenoiseRegions<T> R(width, height);
-    auto hits = [](const void *a, size_t na, const void *b, size_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; };
-    if (hits(out, R.img_b, image, R.img_b) || hits(out, R.img_b, features, R.feat_b)) return fail(-2, "out may not alias an input");
-    DeviceGuard guard;
-    HostLease L;
-    if (int rc = acquire_host(d->device, std::vector<unsigned char>(), &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total)) return rc;
-    char *base = (char *)hc->d_img;
-    int rc = 0;
-    hipError_t e = hipMemcpyAsync(base, image, R.img_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_feat, features, R.feat_b, hipMemcpyHostToDevice, hc->stream);
-    if (e != hipSuccess) rc = fail((int)e, "upload of the denoiser's inputs failed: %s", hipGetErrorString(e));
-    if (!rc) rc = launch_denoise_t(d, width, height, (const T *)base, base + R.off_feat, base + R.off_out, base + R.off_work, hc->stream);
-    if (!rc) rc = copy_out(hc, base + R.off_out, out, R.img_b);
-    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
-    return rc;
-}
-
-// The batched filter on host buffers (rtw_filter_batch_f32/_f64): denoise_host for n_views frames -- two H2D, prepare + `levels` launches, ONE D2H.
-template <typename T>
-int filter_batch_host(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const T *images, const T *features, T *out) {
+int filter_host(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const T *images, const T *features, T *out) {
     if (!d || !images || !features || !out) return fail(-1, "null argument");
-    if (int rc = validate_filter_batch(d, width, height, n_views)) return rc;
+    if (int rc = n_views ? validate_filter_batch(d, width, height, n_views) : validate_denoise(d, width, height)) return rc;
     const DenoiseRegions<T> R(width, height, n_views);
-    auto hits = [](const void *a, size_t na, const void *b, size_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; };
-    if (hits(out, R.img_b, images, R.img_b) || hits(out, R.img_b, features, R.feat_b)) return fail(-2, "out may not alias an input");
+    if (ranges_overlap(out, R.img_b, images, R.img_b) || ranges_overlap(out, R.img_b, features, R.feat_b)) return fail(-2, "out may not alias an input");
     DeviceGuard guard;
     HostLease L;
     if (int rc = acquire_host(d->device, std::vector<unsigned char>(), &L)) return rc;
@@ -410,98 +376,46 @@ int filter_batch_host(const rtw_denoise_t *d, int32_t width, int32_t height, int
     int rc = 0;
     hipError_t e = hipMemcpyAsync(base, images, R.img_b, hipMemcpyHostToDevice, hc->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_feat, features, R.feat_b, hipMemcpyHostToDevice, hc->stream);
-    if (e != hipSuccess) rc = fail((int)e, "upload of the filter's inputs failed: %s", hipGetErrorString(e));
-    if (!rc) rc = launch_filter_batch_t(d, width, height, n_views, (const T *)base, base + R.off_feat, base + R.off_out, base + R.off_work, hc->stream);
+    if (e != hipSuccess) rc = fail((int)e, "upload of the %s's inputs failed: %s", n_views ? "filter" : "denoiser", hipGetErrorString(e));
+    if (!rc) rc = R.launch(d, width, height, n_views, base, hc->stream);
     if (!rc) rc = copy_out(hc, base + R.off_out, out, R.img_b);
     if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
     return rc;
 }
 
-// N views rendered, their feature passes and the filter in one call (rtw_render_filtered_batch_f32/_f64): render_host_denoised as a batch --
-// the batched render with gamma 0, the batched feature pass over all chunks, the batched filter with p->gamma, 2 + 1 + levels launches for
-// any N, one device buffer, ONE D2H.  rtw_stats() reports the render's record.
+// Render, feature pass over all N effective chunks and filter in one call (rtw_render_denoised_* / rtw_render_filtered_batch_*): the one-device
+// path above with a device buffer that holds the linear image (the render with gamma 0), the features, the result (the filter with p->gamma) and
+// the filter's workspace; 2 + 1 + levels launches for any number of views on the context's stream, ONE D2H.  rtw_stats() reports the render's record.
 template <typename T, typename SceneT, typename CamT>
-int render_host_filtered_batch(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, T *out) {
+int render_host_filtered(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, T *out) {
     if (!p) return fail(-1, "null params");
     if (!scene || !cams || !d || !out) return fail(-1, "null argument");
     int nch, cs;
-    if (int rc = validate_features_batch(cams, n_views, p, 0, 1, out, &nch, &cs)) return rc;
-    if (int rc = validate_filter_batch(d, p->width, p->height, n_views)) return rc;
-    if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
+    if (int rc = n_views ? validate_features_batch(cams, n_views, p, 0, 1, out, &nch, &cs) : validate_features(p, 0, 1, &nch, &cs)) return rc;
+    if (int rc = n_views ? validate_filter_batch(d, p->width, p->height, n_views) : validate_denoise(d, p->width, p->height)) return rc;
     DeviceGuard guard;
     release_last();
-    std::vector<unsigned char> key;
-    scene_key_of(scene, sizeof(T) == 8, key);
-    HostLease L;
-    if (int rc = acquire_host(p->device, key, &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_scene<T>(hc, scene, key)) return rc;
     const DenoiseRegions<T> R(p->width, p->height, n_views);
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total)) return rc;
-    char *base = (char *)hc->d_img;
-    rtw_params q = *p;
-    q.device = hc->device; q.n_devices = 0; q.device_ids = nullptr; q.gamma = 0;
-    rtw_denoise_t dd = *d;
-    dd.gamma = p->gamma != 0; dd.device = hc->device;
-    RenderRec *rec = nullptr, *frec = nullptr;
-    CtxPtr rctx, fctx;
-    int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, &rec, &rctx);
-    if (!rc) rc = launch_features_batch_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec, &fctx);
-    if (!rc) rc = launch_filter_batch_t(&dd, p->width, p->height, n_views, (const T *)base, base + R.off_feat, base + R.off_out, base + R.off_work, hc->stream);
-    if (!rc) rc = copy_out(hc, base + R.off_out, out, R.img_b);
-    if (rc) (void)hipStreamSynchronize(hc->stream);
-    if (!rc) rc = resolve_rec(rec, &g_last.agg);
-    if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
-    if (rec) release_rec(rctx, rec, rc == 0);
+    RenderRec *frec = nullptr;
+    CtxPtr fctx;
+    const int rc = render_one_device(p->device, scene, p, R.total, R.off_out, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+        char *base = (char *)hc->d_img;
+        q.gamma = 0;
+        rtw_denoise_t dd = *d;
+        dd.gamma = p->gamma != 0; dd.device = hc->device;
+        int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
+        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec, &fctx);
+        if (!rc) rc = R.launch(&dd, p->width, p->height, n_views, base, hc->stream);
+        return rc;
+    });
     if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
-    g_last.resolved = rc == 0;
-    return rc;
-}
-
-// Render, feature pass over all N effective chunks and denoiser in one call (rtw_render_denoised_f32/_f64): the one-device path with a device
-// buffer that holds the linear image, the features, the result and the denoiser's workspace; everything on the context's stream, ONE D2H.
-// rtw_stats() reports the render's record.
-template <typename T, typename SceneT, typename CamT>
-int render_host_denoised(const SceneT *scene, const CamT *cam, const rtw_params *p, const rtw_denoise_t *d, T *out) {
-    if (!scene || !cam || !p || !d || !out) return fail(-1, "null argument");
-    int nch, cs;
-    if (int rc = validate_features(p, 0, 1, &nch, &cs)) return rc;
-    if (int rc = validate_denoise(d, p->width, p->height)) return rc;
-    if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
-    DeviceGuard guard;
-    release_last();
-    std::vector<unsigned char> key;
-    scene_key_of(scene, sizeof(T) == 8, key);
-    HostLease L;
-    if (int rc = acquire_host(p->device, key, &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_scene<T>(hc, scene, key)) return rc;
-    const DenoiseRegions<T> R(p->width, p->height);
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total)) return rc;
-    char *base = (char *)hc->d_img;
-    rtw_params q = *p;
-    q.device = hc->device; q.n_devices = 0; q.device_ids = nullptr; q.gamma = 0;
-    rtw_denoise_t dd = *d;
-    dd.gamma = p->gamma != 0; dd.device = hc->device;
-    RenderRec *rec = nullptr, *frec = nullptr;
-    CtxPtr rctx, fctx;
-    int rc = launch_render_t(hc->scene, cam, 0, nullptr, &q, base, hc->stream, &rec, &rctx);
-    if (!rc) rc = launch_features_t(hc->scene, cam, &q, 0, nch, base + R.off_feat, hc->stream, &frec, &fctx);
-    if (!rc) rc = launch_denoise_t(&dd, p->width, p->height, (const T *)base, base + R.off_feat, base + R.off_out, base + R.off_work, hc->stream);
-    if (!rc) rc = copy_out(hc, base + R.off_out, out, R.img_b);
-    if (rc) (void)hipStreamSynchronize(hc->stream);
-    if (!rc) rc = resolve_rec(rec, &g_last.agg);
-    if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
-    if (rec) release_rec(rctx, rec, rc == 0);
-    if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
-    g_last.resolved = rc == 0;
     return rc;
 }
 
 // What an accumulator holds, denoised (rtw_accum_filtered_f32/_f64): the gamma-0 resolve (per tile for an adaptive accumulator), the feature
 // pass over exactly the samples it holds, with `guided` its noise map and the noise-guided filter (else the plain one), all on the
 // accumulator's device in a leased context's buffer and stream, ONE D2H.  The accumulator is only read; every step orders itself behind
-// its event.  rtw_stats() reports the feature pass's record.
+// its event.  rtw_stats() reports the feature pass's record.  (Not through render_one_device: its lease has no scene to upload.)
 template <typename T, typename CamT>
 int accum_filtered_host(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle a, int32_t guided, T *out) {
     if (!p) return fail(-1, "null params");
@@ -517,7 +431,7 @@ int accum_filtered_host(rtw_scene_handle scene, const CamT *cam, const rtw_param
     HostLease L;
     if (int rc = acquire_host(accum_device_of(a), std::vector<unsigned char>(), &L)) return rc;
     HostCtx *hc = L.hc;
-    const DenoiseRegions<T> R(p->width, p->height);
+    const DenoiseRegions<T> R(p->width, p->height, 0);
     const size_t off_noise = (R.total + 15) & ~(size_t)15;
     if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, off_noise + (size_t)p->width * (size_t)p->height * sizeof(T))) return rc;
     char *base = (char *)hc->d_img;
@@ -528,7 +442,7 @@ int accum_filtered_host(rtw_scene_handle scene, const CamT *cam, const rtw_param
     int rc = enqueue_accum_resolve(a, sizeof(T) == 8, 0, base, hc->stream);
     if (!rc) rc = enqueue_accum_features_t(scene, cam, p, a, base + R.off_feat, hc->stream, &frec, &fctx);
     if (!rc && guided) rc = enqueue_accum_noise(a, sizeof(T) == 8, base + off_noise, hc->stream);
-    if (!rc) rc = launch_denoise_t(&dd, p->width, p->height, (const T *)base, base + R.off_feat, base + R.off_out, base + R.off_work, hc->stream, guided ? base + off_noise : nullptr);
+    if (!rc) rc = R.launch(&dd, p->width, p->height, 0, base, hc->stream, guided ? base + off_noise : nullptr);
     if (!rc) rc = copy_out(hc, base + R.off_out, out, R.img_b);
     if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
     if (!rc) rc = resolve_rec(frec, &g_last.agg);
@@ -537,46 +451,71 @@ int accum_filtered_host(rtw_scene_handle scene, const CamT *cam, const rtw_param
     g_last.resolved = rc == 0;
     return rc;
 }
-int accum_filtered_host_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle a, int32_t guided, float *out) {
-    return accum_filtered_host<float>(scene, cam, p, d, a, guided, out);
-}
-int accum_filtered_host_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle a, int32_t guided, double *out) {
-    return accum_filtered_host<double>(scene, cam, p, d, a, guided, out);
-}
-
-int denoise_host_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const float *image, const float *features, float *out) { return denoise_host<float>(d, width, height, image, features, out); }
-int denoise_host_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const double *image, const double *features, double *out) { return denoise_host<double>(d, width, height, image, features, out); }
-int render_host_denoised_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, float *out) { return render_host_denoised<float>(scene, cam, p, d, out); }
-int render_host_denoised_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, double *out) { return render_host_denoised<double>(scene, cam, p, d, out); }
-
-int render_host_features_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, float *out) {
-    return render_host_features_batch<float>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, out);
-}
-int render_host_features_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, double *out) {
-    return render_host_features_batch<double>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, out);
-}
-int filter_batch_host_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const float *images, const float *features, float *out) { return filter_batch_host<float>(d, width, height, n_views, images, features, out); }
-int filter_batch_host_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const double *images, const double *features, double *out) { return filter_batch_host<double>(d, width, height, n_views, images, features, out); }
-int render_host_filtered_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, float *out) {
-    return render_host_filtered_batch<float>(scene, cams, n_views, seeds, p, d, out);
-}
-int render_host_filtered_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, double *out) {
-    return render_host_filtered_batch<double>(scene, cams, n_views, seeds, p, d, out);
-}
-
-int render_host_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, float *out) { return render_host<float>(scene, cam, p, out); }
-int render_host_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, double *out) { return render_host<double>(scene, cam, p, out); }
-int render_host_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, float *out) {
-    return render_host_batch<float>(scene, cams, n_views, seeds, p, out);
-}
-int render_host_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, double *out) {
-    return render_host_batch<double>(scene, cams, n_views, seeds, p, out);
-}
-int render_host_features_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, float *out) {
-    return render_host_features<float>(scene, cam, p, chunk_begin, chunk_count, out);
-}
-int render_host_features_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, double *out) {
-    return render_host_features<double>(scene, cam, p, chunk_begin, chunk_count, out);
-}
 
 }  // namespace rtwh
+
+using namespace rtwh;
+
+// ---- the host-buffer entry points of the C ABI (include/rtw_hip.h) ------------------------------------------------------
+extern "C" {
+
+int rtw_render_f32(const rtw_scene_f32 *s, const rtw_camera_f32 *c, const rtw_params *p, float *out) { return render_host<float>(s, c, p, out); }
+int rtw_render_f64(const rtw_scene_f64 *s, const rtw_camera_f64 *c, const rtw_params *p, double *out) { return render_host<double>(s, c, p, out); }
+int rtw_render_batch_f32(const rtw_scene_f32 *s, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, float *out) {
+    return render_host_batch<float>(s, cams, n_views, seeds, p, out);
+}
+int rtw_render_batch_f64(const rtw_scene_f64 *s, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, double *out) {
+    return render_host_batch<double>(s, cams, n_views, seeds, p, out);
+}
+
+int rtw_render_features_f32(const rtw_scene_f32 *s, const rtw_camera_f32 *c, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, float *out) {
+    return render_host_features<float>(s, c, 0, nullptr, p, chunk_begin, chunk_count, out);
+}
+int rtw_render_features_f64(const rtw_scene_f64 *s, const rtw_camera_f64 *c, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, double *out) {
+    return render_host_features<double>(s, c, 0, nullptr, p, chunk_begin, chunk_count, out);
+}
+int rtw_render_features_batch_f32(const rtw_scene_f32 *s, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin,
+                                  int32_t chunk_count, float *out) {
+    return render_host_features<float>(s, cams, batch_views(n_views), seeds, p, chunk_begin, chunk_count, out);
+}
+int rtw_render_features_batch_f64(const rtw_scene_f64 *s, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin,
+                                  int32_t chunk_count, double *out) {
+    return render_host_features<double>(s, cams, batch_views(n_views), seeds, p, chunk_begin, chunk_count, out);
+}
+
+int rtw_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const float *image, const float *features, float *out) {
+    return filter_host<float>(d, width, height, 0, image, features, out);
+}
+int rtw_denoise_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const double *image, const double *features, double *out) {
+    return filter_host<double>(d, width, height, 0, image, features, out);
+}
+int rtw_filter_batch_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const float *images, const float *features, float *out) {
+    return filter_host<float>(d, width, height, batch_views(n_views), images, features, out);
+}
+int rtw_filter_batch_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const double *images, const double *features, double *out) {
+    return filter_host<double>(d, width, height, batch_views(n_views), images, features, out);
+}
+
+int rtw_render_denoised_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, float *out) {
+    return render_host_filtered<float>(scene, cam, 0, nullptr, p, d, out);
+}
+int rtw_render_denoised_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, double *out) {
+    return render_host_filtered<double>(scene, cam, 0, nullptr, p, d, out);
+}
+int rtw_render_filtered_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d,
+                                  float *out) {
+    return render_host_filtered<float>(scene, cams, batch_views(n_views), seeds, p, d, out);
+}
+int rtw_render_filtered_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d,
+                                  double *out) {
+    return render_host_filtered<double>(scene, cams, batch_views(n_views), seeds, p, d, out);
+}
+
+int rtw_accum_filtered_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle accum, int32_t guided, float *out) {
+    return accum_filtered_host<float>(scene, cam, p, d, accum, guided, out);
+}
+int rtw_accum_filtered_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle accum, int32_t guided, double *out) {
+    return accum_filtered_host<double>(scene, cam, p, d, accum, guided, out);
+}
+
+}  // extern "C"

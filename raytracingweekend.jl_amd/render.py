@@ -22,6 +22,25 @@ def _as_image(flat, height, width):
     return flat.reshape(width, height, 3).transpose(1, 0, 2)
 
 
+def _frame_height(image_width, n_samples):
+    """H of a frame ``image_width`` wide, after the checks every render makes of its size and sample count"""
+    height = image_height(image_width)
+    if int(image_width) <= 0 or height <= 0:
+        raise ValueError(f"image_width={image_width} gives an empty {height} x {image_width} image")
+    if int(n_samples) <= 0:
+        raise ValueError("n_samples must be >= 1")
+    return height
+
+
+def _record_stats(L, per_device=False):
+    """rtw_stats() of the call this thread has just made -> what ``last_stats()`` reports"""
+    st = _capi.Stats()
+    _capi.check(L.rtw_stats(C.byref(st)))
+    _tls.stats = {k: getattr(st, k) for k, _ in st._fields_}
+    if per_device:
+        _tls.stats["per_device"] = _stats_devices(L)
+
+
 def render(scene, cam, image_width=400, n_samples=1, *, depth=16, seed=1, n_chunks=0, device=-1, gamma=True,
            group_cull=False, devices=None, scan_valu=False, ray_pool=False, rccl_reduce=False, numerics=None):
     """Render ``scene`` through ``cam``; returns ``img[i, j, :]`` (row i, column j, RGB) of the
@@ -41,11 +60,7 @@ def render(scene, cam, image_width=400, n_samples=1, *, depth=16, seed=1, n_chun
         raise TypeError("cam must be a Camera")
     T = cam.elem_type
     L = _capi.lib()
-    height = image_height(image_width)
-    if int(image_width) <= 0 or height <= 0:
-        raise ValueError(f"image_width={image_width} gives an empty {height} x {image_width} image")
-    if int(n_samples) <= 0:
-        raise ValueError("n_samples must be >= 1")
+    height = _frame_height(image_width, n_samples)
     flat = flatten_scene(scene, T)
     S, keep = _capi.make_scene(flat, T)
     Cm = _capi.make_camera(cam, T)
@@ -56,10 +71,7 @@ def render(scene, cam, image_width=400, n_samples=1, *, depth=16, seed=1, n_chun
     out = np.empty(height * int(image_width) * 3, dtype=T)
     fn = L.rtw_render_f64 if _capi.is_f64(T) else L.rtw_render_f32
     _capi.check(fn(C.byref(S), C.byref(Cm), C.byref(P), out.ctypes.data_as(C.c_void_p)))
-    st = _capi.Stats()
-    _capi.check(L.rtw_stats(C.byref(st)))
-    _tls.stats = {k: getattr(st, k) for k, _ in st._fields_}
-    _tls.stats["per_device"] = _stats_devices(L)
+    _record_stats(L, per_device=True)
     del keep
     return _as_image(out, height, int(image_width))
 
@@ -87,11 +99,7 @@ def render_batch(scene, cams, image_width=400, n_samples=1, *, depth=16, seed=1,
     n = len(cams)
     seeds = _capi.make_seeds(seed, n)
     L = _capi.lib()
-    height = image_height(image_width)
-    if int(image_width) <= 0 or height <= 0:
-        raise ValueError(f"image_width={image_width} gives an empty {height} x {image_width} image")
-    if int(n_samples) <= 0:
-        raise ValueError("n_samples must be >= 1")
+    height = _frame_height(image_width, n_samples)
     flat = flatten_scene(scene, T)
     S, keep = _capi.make_scene(flat, T)
     Cm = _capi.make_cameras(cams, T)
@@ -100,10 +108,7 @@ def render_batch(scene, cams, image_width=400, n_samples=1, *, depth=16, seed=1,
     out = np.empty(n * height * int(image_width) * 3, dtype=T)
     fn = L.rtw_render_batch_f64 if _capi.is_f64(T) else L.rtw_render_batch_f32
     _capi.check(fn(C.byref(S), Cm, n, seeds, C.byref(P), out.ctypes.data_as(C.c_void_p)))
-    st = _capi.Stats()
-    _capi.check(L.rtw_stats(C.byref(st)))
-    _tls.stats = {k: getattr(st, k) for k, _ in st._fields_}
-    _tls.stats["per_device"] = _stats_devices(L)
+    _record_stats(L, per_device=True)
     del keep
     return out.reshape(n, int(image_width), height, 3).transpose(0, 2, 1, 3)
 

@@ -412,3 +412,59 @@ def test_python_layer(rtw):
         _assert_same(imgs[v], rtw.render_denoised(scene, cams[v], 48, 4, seed=seeds[v]), f"render_denoised_batch view {v}")
     same_seed = rtw.render_denoised_batch(scene, cams[:2], 48, 4, seed=3)
     _assert_same(same_seed[0], imgs[0], "seed for every view")
+
+
+# ---- the cached context across call kinds: one device buffer, one set of per-thread stats ---------------------------------------------------
+@pytest.mark.parametrize("T", [np.float32, np.float64])
+def test_call_kinds_share_the_cached_context_without_leaking_into_each_other(rtw, T):
+    """Every host-buffer call goes through one cached context per device: ONE device buffer that each call kind sizes and partitions its own
+    way (a frame, N frames, feature buffers, the denoiser's regions for one view or N) and ONE set of per-thread stats.  The eight calls
+    below, made in one order and then in the reverse one, must each return the same bits both times -- so neither the buffer growing and
+    shrinking between callers nor a previous caller's region offsets leak into a result -- and leave in last_stats() what their contract
+    says: the render's record after a render + filter call, nothing new after a filter alone.
+    40 x 22, 2 spp, depth 4, levels 3, 2 views: H is no multiple of 8 (partial tiles), 880 pixels are no multiple of 256, and the step 4
+    taps cross the frame border.  Tolerance: NONE."""
+    W, H, spp, n = 40, 22, 2, 2
+    scene = rtw.scene_2_spheres(elem_type=T)
+    cams = [rtw.t_default_cam(elem_type=T), rtw.t_cam2(elem_type=T)]
+    seeds = [1, 9]
+    kw = dict(depth=4)
+    # the filter's inputs are the same arrays in both orders (made before either)
+    image = np.ascontiguousarray(rtw.render(scene, cams[0], W, spp, gamma=False, **kw))
+    feat = np.ascontiguousarray(rtw.render_features(scene, cams[0], W, spp)["raw"])
+    images = np.ascontiguousarray(rtw.render_batch(scene, cams, W, spp, seed=seeds, gamma=False, **kw))
+    feats = np.ascontiguousarray(rtw.render_features_batch(scene, cams, W, spp, seeds=seeds)["raw"])
+    assert image.shape == (H, W, 3) and feats.shape == (n, H, W, 8)
+    calls = [
+        ("render", lambda: rtw.render(scene, cams[0], W, spp, **kw)),
+        ("render_denoised_batch", lambda: rtw.render_denoised_batch(scene, cams, W, spp, seeds=seeds, levels=3, **kw)),
+        ("render_features", lambda: rtw.render_features(scene, cams[1], W, spp, seed=9)["raw"]),
+        ("denoise", lambda: rtw.denoise(image, feat, levels=3)),
+        ("render_features_batch", lambda: rtw.render_features_batch(scene, cams, W, spp, seeds=seeds)["raw"]),
+        ("denoise_batch", lambda: rtw.denoise_batch(images, feats, levels=3)),
+        ("render_denoised", lambda: rtw.render_denoised(scene, cams[1], W, spp, seed=9, levels=3, **kw)),
+        ("render (again)", lambda: rtw.render(scene, cams[0], W, spp, **kw)),
+    ]
+    shapes = {"render": (H, W, 3), "render_denoised_batch": (n, H, W, 3), "render_features": (H, W, 8), "denoise": (H, W, 3),
+              "render_features_batch": (n, H, W, 8), "denoise_batch": (n, H, W, 3), "render_denoised": (H, W, 3), "render (again)": (H, W, 3)}
+
+    def run(order):
+        got = {}
+        for name, call in order:
+            before = dict(rtw.last_stats())
+            res = call()
+            st = rtw.last_stats()
+            assert res.shape == shapes[name] and res.dtype == T, (name, res.shape, res.dtype)
+            if name == "render_denoised":
+                assert st["samples"] == W * H * spp, (name, st["samples"])
+            elif name == "render_denoised_batch":
+                assert st["samples"] == n * W * H * spp, (name, st["samples"])
+            elif name in ("denoise", "denoise_batch"):
+                assert st == before, f"{name} changed last_stats(): {before} -> {st}"
+            got[name] = np.ascontiguousarray(res).tobytes()
+        return got
+
+    forward, backward = run(calls), run(calls[::-1])
+    for name, _ in calls:
+        assert forward[name] == backward[name], f"{name}: the result depends on the calls made before it"
+    assert forward["render"] == forward["render (again)"] == backward["render (again)"]
