@@ -664,7 +664,16 @@ int rtw_stats_devices(int32_t capacity, int32_t *count, int32_t *devices, double
  *          with tmin = 1e-4, tmax = +inf, then on the UPLOADED material rows the kernel's own sequence: make_hitrec, the dielectric constants
  *          1 / ir, r0_front, r0_back the upload stored, scatter_begin with them, attenuation_of, the rejection loop, scatter_finish, the final
  *          normalize.  out: state[2] (raw), idx, o[3], d[3], att[3]; a miss leaves the state as it came, idx = -1 and zeros.
- *   bits 8-9 of `op`: the numerics mode of the ray-sphere test for ops 0, 8 - 11, 13, 14, 26 (0 reference, 1 contract, 3 reference_fma2; 2 is rejected)  */
+ *       27 op 20's scan with a sink that also records the block vote of the group cull (needs a scene of at most 512 spheres with matrix-pipe
+ *          cull operands; per item like ops 17 - 20).  in: o[3], d[3], tmin, tmax.  out: the 18 slots of op 20 -- ok, mf_sc, candidate bits
+ *          [8 raw uint64], in-lane bits [8 raw uint64], bit i = sphere i of the caller's list -- and one raw uint64: bit b is set when block b
+ *          of the cull layout's device order was voted for by the half wave of this ray (item i runs in lane i % 64 of wave i / 64; lanes
+ *          behind `count` have no ray).  tests/test_gpu_cull_vote.py
+ *       28 the cull layout (needs a scene with matrix-pipe cull operands).  Item p is device position p, its block is p / 32.  in: one slot,
+ *          ignored.  out: the caller's index of the sphere at that position, or -1 for a dead or padding slot and for p beyond the layout;
+ *          1 if the position is in the in-lane list (tested by every lane itself, its filter row disabled), else 0; the number of positions;
+ *          the number of blocks.
+ *   bits 8-9 of `op`: the numerics mode of the ray-sphere test for ops 0, 8 - 11, 13, 14, 17 - 20, 26, 27 (0 reference, 1 contract, 3 reference_fma2; 2 is rejected)  */
 int rtw_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene,
                  const rtw_camera_f32 *cam);
 int rtw_unit_f64(int op, int count, const void *in, void *out, const rtw_scene_f64 *scene,

@@ -71,12 +71,15 @@ struct NoClock { static constexpr bool on() { return false; } __device__ __force
 // under `if constexpr (SINK::on())`: with this default nothing is compiled in, the trace kernels' instantiations are unchanged.
 //   ray(lane, ok, sc)   the lane's ray used the filter (ok) / the matrix-pipe scale;  cand(lane, i) / inlane(lane, i): sphere i (the
 //   caller's index) was listed for pass 2 / tested by the lane itself.  `lane` is the lane whose ray it is (hit_world_mfma: the owner).
+//   blocks(lane, base, v0, v1)   group cull on the matrix pipe: the vote of the group of 32 blocks that starts at block `base` -- v0 / v1: the
+//   sets the first / second half wave voted for (bit b: block base + b); every lane calls it once per group, right behind the vote.
 struct NoSink {
     static constexpr bool on() { return false; }
     unsigned self = 0;
     __device__ __forceinline__ void ray(unsigned, bool, float) {}
     __device__ __forceinline__ void cand(unsigned, int) {}
     __device__ __forceinline__ void inlane(unsigned, int) {}
+    __device__ __forceinline__ void blocks(unsigned, int, unsigned, unsigned) {}
 };
 
 // src/hit.jl:38-50 -- closest hit by linear scan over ALL spheres; `closest` shrinks; a later

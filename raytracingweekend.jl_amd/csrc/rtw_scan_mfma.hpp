@@ -475,6 +475,7 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
     int blk = base;
     if constexpr (CULLED) {
         block_sets(base, vote0, vote1);
+        if constexpr (SINK::on()) sink.blocks(lane, base, vote0, vote1);
         todo = vote0 | vote1;
         clk.count(7, (unsigned)(n_blocks - base < 32 ? n_blocks - base : 32));
         clk.count(6, (unsigned)((n_blocks - base < 32 ? n_blocks - base : 32) - __popc(todo)));

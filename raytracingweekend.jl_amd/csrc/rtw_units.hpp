@@ -27,12 +27,19 @@ enum UnitOp {
     // one bounce as the trace kernel composes it (rtw_kernels.hpp phases H2, R, F): hit_world, then make_hitrec, the DielConst of the uploaded cold
     // rows, scatter_begin(..., &dc), attenuation_of, the rejection loop, scatter_finish, the final normalize
     U_SHADE = 26,
-    U_NUM_OPS = 27
+    // op 20's scan with a sink that also records the block vote: RTW_SINK_SLOTS slots as op 20, then one raw uint64 -- bit b: block b of the cull
+    // layout's device order was voted for by the half wave of this ray (the first group of 32 blocks: all there is within RTW_SINK_SPHERES)
+    U_SINK_MFMA_CULL_VOTE = 27,
+    // the cull layout itself: item p is device position p (block p / 32).  out: the caller's index of the sphere there (-1: a dead or padding slot, or
+    // p beyond the layout), 1 if that position is in the in-lane list, the number of positions, the number of blocks
+    U_CULL_LAYOUT = 28,
+    U_NUM_OPS = 29
 };
 __host__ __device__ inline bool unit_is_accum(int op) { return (op >= U_ACCUM_TILE_CHECK && op <= U_ACCUM_RESOLVE_TILES) || op == U_ACCUM_NOISE; }
-__host__ __device__ inline bool unit_is_sink(int op) { return op >= U_SINK_LDS && op <= U_SINK_MFMA_CULL; }
+__host__ __device__ inline bool unit_is_sink(int op) { return (op >= U_SINK_LDS && op <= U_SINK_MFMA_CULL) || op == U_SINK_MFMA_CULL_VOTE; }
 #define RTW_SINK_SPHERES 512
 #define RTW_SINK_SLOTS 18
+#define RTW_VOTE_SLOTS (RTW_SINK_SLOTS + 1)
 
 __host__ __device__ inline int unit_in_slots(int op) {
     switch (op) {
@@ -47,7 +54,8 @@ __host__ __device__ inline int unit_in_slots(int op) {
         case U_NEAR_ZERO: return 3;     // v[3]
         case U_EXACT_MATH: return 2;    // first bit pattern, number of consecutive patterns
         case U_HIT_WORLD: case U_HIT_WORLD_LDS: case U_HIT_WORLD_CULL: case U_HIT_WORLD_MFMA: case U_HIT_WORLD_MFMA_CULL: return 8;     // o[3], d[3], tmin, tmax
-        case U_SINK_LDS: case U_SINK_CULL: case U_SINK_MFMA: case U_SINK_MFMA_CULL: return 8;                                         // (the same)
+        case U_SINK_LDS: case U_SINK_CULL: case U_SINK_MFMA: case U_SINK_MFMA_CULL: case U_SINK_MFMA_CULL_VOTE: return 8;             // (the same)
+        case U_CULL_LAYOUT: return 1;   // (ignored)
         case U_RAY_COLOR: return 9;     // state[2], o[3], d[3], depth
         case U_FX_SUM: return 8;        // 8 binary64 values
         case U_SHADE: return 8;         // state[2], o[3], d[3]
@@ -68,6 +76,8 @@ __host__ __device__ inline int unit_out_slots(int op) {
         case U_EXACT_MATH: return 4;    // mismatches of t_sqrt, of t_rcp, first bad pattern of each (or -1)
         case U_HIT_WORLD: case U_HIT_WORLD_LDS: case U_HIT_WORLD_CULL: case U_HIT_WORLD_MFMA: case U_HIT_WORLD_MFMA_CULL: return 9;     // idx, t, p[3], n[3], front
         case U_SINK_LDS: case U_SINK_CULL: case U_SINK_MFMA: case U_SINK_MFMA_CULL: return RTW_SINK_SLOTS;   // ok, mf_sc, cand bits[8], in-lane bits[8] (raw uint64)
+        case U_SINK_MFMA_CULL_VOTE: return RTW_VOTE_SLOTS;   // op 20's slots, voted blocks (raw uint64)
+        case U_CULL_LAYOUT: return 4;   // the caller's index or -1, in-lane, positions, blocks
         case U_RAY_COLOR: return 6;     // state[2], colour[3], segments
         case U_FX_SUM: return 2;        // sum, poisoned
         case U_SHADE: return 12;        // state[2], idx, o[3], d[3], att[3] (a miss: the state as it came, idx = -1, zeros)
@@ -85,21 +95,32 @@ __device__ __forceinline__ double as_f64(uint64_t u) { return __longlong_as_doub
 // The sink of ops 17-20 (rtw_scan.hpp NoSink): rows of RTW_SINK_SLOTS 8-byte slots, one per ray of the wave, zeroed by the host.  Bit i & 63 of
 // slot 2 + (i >> 6) / 10 + (i >> 6): sphere i of the caller's list.  A row belongs to the lane's ray but any lane may record into it (hit_world_mfma:
 // the lane that runs a candidate's exact test is not its owner): global atomic ORs.
-struct CandSink {
+// Op 27 (SLOTS = RTW_VOTE_SLOTS): the same rows with one more slot, the blocks the ray's half wave voted for (blocks(): every lane records into its
+// OWN row what its half of the wave-uniform vote words says).
+template <int SLOTS>
+struct CandSinkT {
     double *rows;          // the wave's first row
     unsigned n_live;       // rows of the wave (lanes beyond have no ray and no row)
     unsigned self;         // this lane
     static constexpr bool on() { return true; }
     __device__ void ray(unsigned lane, bool ok, float sc) {
-        if (lane < n_live) { rows[lane * RTW_SINK_SLOTS] = ok ? 1.0 : 0.0; rows[lane * RTW_SINK_SLOTS + 1] = (double)sc; }
+        if (lane < n_live) { rows[lane * SLOTS] = ok ? 1.0 : 0.0; rows[lane * SLOTS + 1] = (double)sc; }
     }
     __device__ void bit(unsigned lane, int slot0, int i) {
         if (lane < n_live && (unsigned)i < (unsigned)RTW_SINK_SPHERES)
-            atomicOr(reinterpret_cast<unsigned long long *>(rows + lane * RTW_SINK_SLOTS + slot0 + (i >> 6)), 1ull << (i & 63));
+            atomicOr(reinterpret_cast<unsigned long long *>(rows + lane * SLOTS + slot0 + (i >> 6)), 1ull << (i & 63));
     }
     __device__ void cand(unsigned lane, int i) { bit(lane, 2, i); }
     __device__ void inlane(unsigned lane, int i) { bit(lane, 10, i); }
+    __device__ void blocks(unsigned lane, int base, unsigned v0, unsigned v1) {
+        if constexpr (SLOTS > RTW_SINK_SLOTS) {
+            if (lane < n_live && (unsigned)base < 64u)
+                atomicOr(reinterpret_cast<unsigned long long *>(rows + lane * SLOTS + RTW_SINK_SLOTS), (unsigned long long)(lane < 32u ? v0 : v1) << base);
+        }
+    }
 };
+using CandSink = CandSinkT<RTW_SINK_SLOTS>;
+using VoteSink = CandSinkT<RTW_VOTE_SLOTS>;
 
 template <typename T>
 __global__ void unit_kernel(int op, int count, const double *__restrict__ in, double *__restrict__ out,
@@ -115,6 +136,7 @@ __global__ void unit_kernel(int op, int count, const double *__restrict__ in, do
     const bool coop = op == U_HIT_WORLD || op == U_RAY_COLOR || op == U_HIT_WORLD_LDS || op == U_HIT_WORLD_CULL || op == U_HIT_WORLD_MFMA || op == U_HIT_WORLD_MFMA_CULL || op == U_SHADE || unit_is_sink(op);
     const int wave0 = gid - (int)(threadIdx.x & 63u);
     const CandSink sink = {out + (size_t)wave0 * RTW_SINK_SLOTS, (unsigned)(count - wave0 < 64 ? count - wave0 : 64), threadIdx.x & 63u};   // (ops 17-20)
+    const VoteSink vsink = {out + (size_t)wave0 * RTW_VOTE_SLOTS, sink.n_live, sink.self};                                                   // (op 27)
     if (!coop && !live) return;
     switch (op) {
         case U_HIT_SPHERE: {
@@ -288,25 +310,41 @@ __global__ void unit_kernel(int op, int count, const double *__restrict__ in, do
             else
                 hit_world<T, 64>(scene, (const V4 *)lds_geom, o, d, tmn, tmx, t_hit, my_list, NoClock(), sink);
         } break;
-        case U_SINK_MFMA: case U_SINK_MFMA_CULL: {
+        case U_SINK_MFMA: case U_SINK_MFMA_CULL: case U_SINK_MFMA_CULL_VOTE: {
             __shared__ __attribute__((aligned(8))) unsigned k_pairs[RTW_PAIR_CAP];
             __shared__ unsigned long long k_keys[64];
             __shared__ unsigned k_kidx[64];
             V4 *lds_geom = reinterpret_cast<V4 *>(u_smem);
-            unsigned short *lds_orig = reinterpret_cast<unsigned short *>(lds_geom + (op == U_SINK_MFMA_CULL ? cull_exact_count(cull) : 0));
-            if (op == U_SINK_MFMA_CULL) stage_cull_scene<T>(cull, lds_geom, lds_orig); else stage_scene<T>(scene, lds_geom);
+            const bool culled = op != U_SINK_MFMA;
+            unsigned short *lds_orig = reinterpret_cast<unsigned short *>(lds_geom + (culled ? cull_exact_count(cull) : 0));
+            if (culled) stage_cull_scene<T>(cull, lds_geom, lds_orig); else stage_scene<T>(scene, lds_geom);
             __syncthreads();
             V3<T> o = {0, 0, 0}, d = {0, 0, 1};
             if (live) { o = ld3<T>(x); d = ld3<T>(x + 3); }
             const T tmn = (T)in[6];
             T t_hit;
             const WaveScratch ws = {k_pairs, k_keys, k_kidx};
-            if (op == U_SINK_MFMA_CULL) {
+            if (op == U_SINK_MFMA_CULL_VOTE) {
+                const MfmaCull mc = mfma_cull_of(cull);
+                hit_world_mfma<T>(scene, (const V4 *)lds_geom, o, d, live, tmn, t_hit, ws, threadIdx.x & 63u, NoClock(), &mc, (const unsigned short *)lds_orig, vsink);
+            } else if (op == U_SINK_MFMA_CULL) {
                 const MfmaCull mc = mfma_cull_of(cull);
                 hit_world_mfma<T>(scene, (const V4 *)lds_geom, o, d, live, tmn, t_hit, ws, threadIdx.x & 63u, NoClock(), &mc, (const unsigned short *)lds_orig, sink);
             } else {
                 hit_world_mfma<T>(scene, (const V4 *)lds_geom, o, d, live, tmn, t_hit, ws, threadIdx.x & 63u, NoClock(), nullptr, NoOrig(), sink);
             }
+        } break;
+        case U_CULL_LAYOUT: {
+            // (the host refuses a scene without matrix-pipe cull operands: the tables, with the in-lane list, lie behind the block boxes)
+            const int n_pos = cull_exact_count(cull);
+            const MfmaCull mc = mfma_cull_of(cull);
+            int idx = -1;
+            bool inl = false;
+            if (gid < n_pos && !((double)cull.exact[gid].w < -1e29)) {
+                idx = (int)cull.orig[gid];
+                for (int k = 0; k < mc.n_huge && k < RTW_CULL_INLANE_MAX; ++k) inl = inl || (int)mc.tab[6 * RTW_CULL_BINS + 4 + k] == gid;
+            }
+            y[0] = (double)idx; y[1] = inl ? 1.0 : 0.0; y[2] = (double)n_pos; y[3] = (double)mc.blocks;
         } break;
         case U_FX_SUM: {
             // the trace kernel's pixel accumulation: fx_from_double -> 128-bit adds -> fx_to_double

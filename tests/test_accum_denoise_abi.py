@@ -173,7 +173,7 @@ def test_unit_op_25_validates_before_any_hip_call(lib):
 
     assert unit(25, 1, None, out) == -1 and unit(25, 1, head, None, f32=True) == -1
     assert unit(24, 1, head, out) == -2 and b"unknown unit op" in lib.rtw_last_error()
-    assert unit(27, 1, head, out) == -2 and b"unknown unit op" in lib.rtw_last_error()
+    assert unit(29, 1, head, out) == -2 and b"unknown unit op" in lib.rtw_last_error()      # (the first number behind the last op)
     for bad in (dict(count=0), dict(count=2), dict(width=0), dict(height=2 ** 15), dict(width=2048, height=1024), dict(spp=0), dict(cs=0), dict(cs=1.5),
                 dict(floor=-1.0), dict(floor=float("nan")), dict(floor=float("inf")), dict(pad=1), dict(chunks=0), dict(chunks=1.25)):
         assert noise(**bad) == -2 and noise(f32=True, **bad) == -2, bad

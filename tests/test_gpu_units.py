@@ -16,6 +16,12 @@ Slot layouts (8-byte slots: doubles for reals, raw uint64 for RNG state words), 
   op 26 shade      in  state[2] o[3] d[3]                  out state[2] idx o[3] d[3] att[3]
                    (one bounce as the trace kernel composes it, on the uploaded material rows; a miss: the state as it
                    came, idx -1, zeros -- tests/test_gpu_material_sweep.py)
+  op 27 vote sink  in  o[3] d[3] tmin tmax                 out ok mf_sc cand[8] inlane[8] blocks
+                   (op 20's scan and its 18 slots -- raw uint64 bit sets, bit i = sphere i -- plus one raw uint64: bit b = block b of
+                   the cull layout's device order was voted for by this ray's half wave -- tests/test_gpu_cull_vote.py)
+  op 28 cull layout in (ignored)                           out idx inlane positions blocks
+                   (item p = device position p, block p / 32: the caller's index of the sphere there or -1, whether the position is
+                   in the in-lane list, the layout's number of positions and of blocks)
 """
 import ctypes as C
 
