@@ -555,8 +555,8 @@ int rtw_render_denoised_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *ca
  * replaced by p->gamma and d->device by the accumulator's device; the result is copied to `out` once.  rtw_stats() afterwards reports
  * the feature pass's record.  Refusals, before any HIP call: nulls -> -1; guided other than 0 / 1 -> -2; everything rtw_accum_features_*
  * and the filter's own checks refuse; guided = 1 on a uniform accumulator -> -2.
- *   Out of scope: batched launches of the passes over accumulators, temporal reuse across views, device lists, compact or sharded
- * frames.  Additive to ABI 4: detected by symbol lookup. */
+ *   N accumulators in each launch: rtw_accum_*_batch_* below.  Out of scope: temporal reuse across views, device lists,
+ * compact or sharded frames.  Additive to ABI 4: detected by symbol lookup. */
 int rtw_accum_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, rtw_accum_handle accum, void *d_out, void *hip_stream);
 int rtw_accum_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, rtw_accum_handle accum, void *d_out, void *hip_stream);
 int rtw_accum_noise_f32(rtw_accum_handle accum, void *d_out, void *hip_stream);
@@ -596,8 +596,8 @@ int rtw_accum_filtered_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, co
  * a misaligned d_out -> -2; a batch whose jobs the render's queues cannot number (which bounds the tiles of the feature launch too) -> -5.
  * Filter calls: nulls -> -1; everything the single-frame filter refuses, n_views < 1 -> -2; a batch of 2^39 pixels or more -> -5.
  * rtw_render_filtered_batch_*: both sets.  Then: a scene handle of the other precision -> -4.
- *   Out of scope: accumulators as the input of a batch (the tiled feature pass, the noise-guided filter,
- * rtw_accum_*), device lists, temporal reuse across the views.  Additive to ABI 4: detected by symbol lookup. */
+ *   Accumulators as the input of a batch (the tiled feature pass, the noise-guided filter): the block behind these declarations.  Out of
+ * scope: device lists, temporal reuse across the views.  Additive to ABI 4: detected by symbol lookup. */
 int rtw_render_features_batch_device_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds,
                                          const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, void *hip_stream);
 int rtw_render_features_batch_device_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds,
@@ -618,6 +618,54 @@ int rtw_render_filtered_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f
                                   const rtw_params *p, const rtw_denoise_t *d, float *out);
 int rtw_render_filtered_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds,
                                   const rtw_params *p, const rtw_denoise_t *d, double *out);
+
+/* Batched passes over accumulators: the N accumulators a batched progressive or adaptive render (rtw_render_accum_batch_*,
+ * rtw_render_adaptive_batch_*) filled go through ONE resolve launch, ONE feature launch, ONE noise launch and prepare + `levels` filter
+ * launches -- 4 + levels launches and one D2H for any N, instead of N times that.  `accums`, `cams` and `seeds` are HOST arrays of n_views
+ * entries as in rtw_render_accum_batch_* (`seeds` == NULL: p->seed for every view).  No new arithmetic is defined:
+ *   View v of each call equals, bit for bit, the single-view entry point -- rtw_accum_resolve_*, rtw_accum_features_*, rtw_accum_noise_*,
+ * rtw_guided_filter_device_*, rtw_accum_filtered_* -- called with accums[v], cams[v], seeds[v].
+ *   Layouts.  Frames are view-major: view v at v*W*H*3 elements (images), v*W*H*8 (features), v*W*H (noise maps).  The filter's workspace is
+ * n_views times the single-frame bytes and batch-major, as rtw_filter_batch_device_* defines it; the guided form keeps v_p in the A plane's
+ * fourth slot.
+ *   Every call is asynchronous on `hip_stream` except rtw_accum_filtered_batch_*, which is blocking with one D2H (`out`: a HOST buffer of
+ * n_views*height*width*3 elements; the cached context of the accumulators' device, as rtw_accum_filtered_*).  Every call only reads the
+ * accumulators; it waits for EVERY accumulator's event and records it on every one afterwards, like a batched pass.  The resolve and the
+ * noise call read a small device table of the views that is kept with accums[0]: a call whose table is the one staged last (the same
+ * accumulators in the same order, holding the same samples -- a resolve followed by the noise map, a batch read again) enqueues and returns;
+ * a call with ANOTHER table first waits on the host until the copy of the previous one has left its staging buffer, i.e. until the work
+ * queued in front of that copy has run.
+ *   rtw_stats() after rtw_accum_features_batch_* and after rtw_accum_filtered_batch_* reports the ONE feature launch: samples = segments =
+ * the sum over views and tiles of valid pixels x chunks held, ONE kernel time.  The other calls leave rtw_stats() alone.
+ *   rtw_accum_features_batch_* takes accumulators that are all adaptive -- every one settled; the feature kernel's tiled batched instance
+ * reads C_t of tile t of view v from the view's own device array -- or all uniform: each holds exactly one chunk interval and it is the SAME
+ * [b, b + C) in every view, the batched feature pass above runs over it.  A mix of the two kinds, or uniform accumulators with different
+ * intervals -> -2.  rtw_accum_resolve_batch_* takes either kind in any mix.
+ *   Refusals, all before any HIP call and with no accumulator touched.  Nulls, including a null entry of `accums` -> -1.  n_views < 1; one
+ * accumulator given twice; everything the single-view call refuses for `p`, `d`, alignment or aliasing (applied to the batch's extents);
+ * guided other than 0 / 1; guided = 1 or a noise call on a uniform accumulator; an accumulator that holds nothing; an adaptive one whose
+ * last adaptive call did not finish -> -2.  An accumulator of another size, device or precision; one not bound to (cams[v], seeds[v], p);
+ * for the noise call, accumulators whose spp, chunk size or dark_floor differ from accums[0]'s (the kernel takes one set) -> -4.  A batch
+ * the feature launch's tile numbering or the filter's 2^39-pixel rule cannot hold -> -5; rtw_accum_resolve_batch_*, whose one launch numbers
+ * three elements per pixel: n_views * width * height >= 2^37 -> -5.
+ *   Out of scope: temporal reuse across the views, device lists, compact or sharded frames.  Additive to ABI 4:
+ * detected by symbol lookup. */
+int rtw_accum_resolve_batch_f32(const rtw_accum_handle *accums, int32_t n_views, int32_t gamma, void *d_out, void *hip_stream);
+int rtw_accum_resolve_batch_f64(const rtw_accum_handle *accums, int32_t n_views, int32_t gamma, void *d_out, void *hip_stream);
+int rtw_accum_features_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
+                                 const rtw_accum_handle *accums, void *d_out, void *hip_stream);
+int rtw_accum_features_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
+                                 const rtw_accum_handle *accums, void *d_out, void *hip_stream);
+int rtw_accum_noise_batch_f32(const rtw_accum_handle *accums, int32_t n_views, void *d_out, void *hip_stream);
+int rtw_accum_noise_batch_f64(const rtw_accum_handle *accums, int32_t n_views, void *d_out, void *hip_stream);
+int rtw_guided_filter_batch_device_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_images,
+                                       const void *d_features, const void *d_noise, void *d_out, void *d_work, void *hip_stream);
+int rtw_guided_filter_batch_device_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_images,
+                                       const void *d_features, const void *d_noise, void *d_out, void *d_work, void *hip_stream);
+int rtw_accum_filtered_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
+                                 const rtw_denoise_t *d, const rtw_accum_handle *accums, int32_t guided, float *out);
+int rtw_accum_filtered_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
+                                 const rtw_denoise_t *d, const rtw_accum_handle *accums, int32_t guided, double *out);
 
 /* Counters/timings of the last render issued from this thread (waits for it to finish). */
 int rtw_stats(rtw_stats_t *out);
@@ -673,6 +721,12 @@ int rtw_stats_devices(int32_t capacity, int32_t *count, int32_t *devices, double
  *          ignored.  out: the caller's index of the sphere at that position, or -1 for a dead or padding slot and for p beyond the layout;
  *          1 if the position is in the in-lane list (tested by every lane itself, its filter row disabled), else 0; the number of positions;
  *          the number of blocks.
+ *   Ops 30 and 31 run the batched per-tile resolve and the batched noise map of rtw_accum_resolve_batch_* / rtw_accum_noise_batch_* the same
+ *          way (29 is not an op, like 24; both also on rtw_unit_f32: T = float).  count = n_views >= 1.  in: the 8 header slots of op 23 (30:
+ *          width, height, spp, chunk_spp, gamma, 0, 0, 0) or of op 25 (31: ..., dark_floor, 0, 0, 0); then per view n_tiles value slots C_t >= 1
+ *          and width * height * 8 raw words.  With E = width * height * 3 (30) or width * height (31): out = per view the E value slots of the
+ *          single kernel of op 23 / op 25, launched view by view; then the n_views * E value slots of ONE launch of the batch kernel, view v
+ *          at v * E.  tests/test_gpu_accum_filter_batch.py
  *   bits 8-9 of `op`: the numerics mode of the ray-sphere test for ops 0, 8 - 11, 13, 14, 17 - 20, 26, 27 (0 reference, 1 contract, 3 reference_fma2; 2 is rejected)  */
 int rtw_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene,
                  const rtw_camera_f32 *cam);

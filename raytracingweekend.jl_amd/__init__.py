@@ -23,11 +23,13 @@ from .render import DeviceRenderer, render, render_batch, last_stats  # noqa: F4
 from .progressive import ProgressiveBatchRenderer, ProgressiveRenderer, render_progressive, samples_in_chunks  # noqa: F401
 from .adaptive import (  # noqa: F401
     AdaptiveBatchRenderer, AdaptiveRenderer, reference_decisions, render_adaptive, render_adaptive_batch, render_adaptive_denoised,
+    render_adaptive_denoised_batch,
 )
 from .shard import compact_elems, compact_to_frame_index, local_tile_count, owned_pixel_mask, render_sharded  # noqa: F401
 from .features import features_batch_into, features_into, render_features, render_features_batch  # noqa: F401
 from .denoise import (  # noqa: F401
-    denoise, denoise_batch, denoise_batch_into, denoise_guided_into, denoise_into, denoise_work_bytes, render_denoised, render_denoised_batch,
+    denoise, denoise_batch, denoise_batch_into, denoise_guided_batch_into, denoise_guided_into, denoise_into, denoise_work_bytes, render_denoised,
+    render_denoised_batch,
 )
 from . import imageio  # noqa: F401
 
@@ -43,4 +45,5 @@ __all__ = [
     "render_features", "features_into", "denoise", "denoise_into", "denoise_work_bytes", "render_denoised",
     "denoise_guided_into", "render_adaptive_denoised",
     "render_features_batch", "features_batch_into", "denoise_batch", "denoise_batch_into", "render_denoised_batch",
+    "denoise_guided_batch_into", "render_adaptive_denoised_batch",
 ]

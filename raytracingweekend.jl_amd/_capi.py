@@ -26,6 +26,9 @@ SYMBOLS = [
     "rtw_render_features_batch_device_f32", "rtw_render_features_batch_device_f64", "rtw_render_features_batch_f32", "rtw_render_features_batch_f64",
     "rtw_filter_batch_device_f32", "rtw_filter_batch_device_f64", "rtw_filter_batch_f32", "rtw_filter_batch_f64",
     "rtw_render_filtered_batch_f32", "rtw_render_filtered_batch_f64",
+    "rtw_accum_resolve_batch_f32", "rtw_accum_resolve_batch_f64", "rtw_accum_features_batch_f32", "rtw_accum_features_batch_f64",
+    "rtw_accum_noise_batch_f32", "rtw_accum_noise_batch_f64", "rtw_guided_filter_batch_device_f32", "rtw_guided_filter_batch_device_f64",
+    "rtw_accum_filtered_batch_f32", "rtw_accum_filtered_batch_f64",
 ]
 
 
@@ -147,6 +150,14 @@ def lib():
         getattr(L, "rtw_filter_batch_device_" + sfx).argtypes = [C.POINTER(Denoise), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         getattr(L, "rtw_filter_batch_" + sfx).argtypes = [C.POINTER(Denoise), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         getattr(L, "rtw_render_filtered_batch_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), C.c_int32, seeds, C.POINTER(Params), C.POINTER(Denoise), C.c_void_p]
+        accums = C.POINTER(C.c_void_p)
+        getattr(L, "rtw_accum_resolve_batch_" + sfx).argtypes = [accums, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+        getattr(L, "rtw_accum_features_batch_" + sfx).argtypes = [C.c_void_p, C.POINTER(CamT), C.c_int32, seeds, C.POINTER(Params), accums, C.c_void_p, C.c_void_p]
+        getattr(L, "rtw_accum_noise_batch_" + sfx).argtypes = [accums, C.c_int32, C.c_void_p, C.c_void_p]
+        getattr(L, "rtw_guided_filter_batch_device_" + sfx).argtypes = [C.POINTER(Denoise), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                                       C.c_void_p, C.c_void_p]
+        getattr(L, "rtw_accum_filtered_batch_" + sfx).argtypes = [C.c_void_p, C.POINTER(CamT), C.c_int32, seeds, C.POINTER(Params), C.POINTER(Denoise), accums, C.c_int32,
+                                                                 C.c_void_p]
     L.rtw_denoise_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_denoise_work_bytes.restype = C.c_int64
     L.rtw_accum_adaptive_info.argtypes = [C.c_void_p, C.POINTER(AdaptiveInfo)]

@@ -240,6 +240,26 @@ class AdaptiveBatchRenderer(ProgressiveBatchRenderer):
             params.setdefault("sigma_color", GUIDED_SIGMA_COLOR)
         return self._filtered(v, bool(guided), gamma, params)
 
+    def noise_all_into(self, d_out_ptr, stream=0):
+        """Enqueue ONE noise-map launch for all views (rtw_accum_noise_batch_*) into device memory at ``d_out_ptr``: N*H*W elements, view
+        ``v``'s map at ``v*H*W``, pixel (i, j) at ``j*H + i``."""
+        fn = getattr(self.L, "rtw_accum_noise_batch_" + self._sfx())
+        _capi.check(fn(self._handles, self.n_views, C.c_void_p(int(d_out_ptr)), C.c_void_p(int(stream))))
+
+    def noise_all(self):
+        """``N x H x W``: ``AdaptiveRenderer.noise()`` of every view (blocking)"""
+        import torch
+        buf = self._device_buffer(self.n_views * self.height * self.width)
+        self.noise_all_into(buf.data_ptr(), stream=torch.cuda.current_stream(buf.device).cuda_stream)
+        return buf.cpu().numpy().reshape(self.n_views, self.width, self.height).transpose(0, 2, 1)
+
+    def denoised_all(self, guided=True, gamma=True, **params):
+        """``denoised(v)`` of every view, ``[N, H, W, 3]``, in 4 + ``levels`` launches and one copy for any N (rtw_accum_filtered_batch_*, blocking)."""
+        if guided:
+            from .denoise import GUIDED_SIGMA_COLOR
+            params.setdefault("sigma_color", GUIDED_SIGMA_COLOR)
+        return self._filtered_all(bool(guided), gamma, params)
+
     def info(self, v):
         """view ``v``'s accumulator info and, once a run has finished, the fields of ``rtw_adaptive_info_t``"""
         out = super().info(v)
@@ -259,3 +279,15 @@ def render_adaptive_batch(scene, cams, image_width=400, n_samples=1, *, toleranc
                                depth=depth, seeds=1 if seeds is None else seeds, n_chunks=n_chunks, device=device, numerics=numerics) as ar:
         infos = ar.run(tolerance, group_cull=group_cull, scan_valu=scan_valu)
         return ar.images(gamma=gamma), ar.samples_per_pixel(), infos
+
+
+def render_adaptive_denoised_batch(scene, cams, image_width=400, n_samples=1, *, tolerance, guided=True, seeds=None, dark_floor=DEFAULT_DARK_FLOOR,
+                                   depth=16, n_chunks=0, min_chunks=0, check_chunks=0, group_cull=False, scan_valu=False, numerics=None, gamma=True,
+                                   device=-1, **denoise_params):
+    """``render_adaptive_batch`` followed by ``AdaptiveBatchRenderer.denoised_all`` on the device; view ``v`` equals
+    ``render_adaptive_denoised(scene, cams[v], ..., seed=seeds[v])`` bit for bit.  Returns ``(images, samples_per_pixel, infos)`` like
+    ``render_adaptive_batch``."""
+    with AdaptiveBatchRenderer(scene, cams, image_width, n_samples, dark_floor=dark_floor, min_chunks=min_chunks, check_chunks=check_chunks,
+                               depth=depth, seeds=1 if seeds is None else seeds, n_chunks=n_chunks, device=device, numerics=numerics) as ar:
+        infos = ar.run(tolerance, group_cull=group_cull, scan_valu=scan_valu)
+        return ar.denoised_all(guided=guided, gamma=gamma, **denoise_params), ar.samples_per_pixel(), infos

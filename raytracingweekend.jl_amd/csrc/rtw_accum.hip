@@ -34,6 +34,10 @@ struct rtw_accum {
     int32_t ad_rounds = 0;                         // passes of the last call that held one of its tiles
     int32_t *d_tiles = nullptr;                    // device memory, 3 n_tiles + 4 int32: C_t | active flags | active list | count (made by the first adaptive call)
     std::vector<int32_t> tile_chunks;              // host copy of C_t, read back at the end of every call
+    // ---- the view table of a batched read-only pass (rtw_accum_resolve_batch_* / rtw_accum_noise_batch_*) whose FIRST accumulator this is ----
+    void *d_tab = nullptr, *h_tab = nullptr;       // device table; pinned staging of its H2D
+    size_t tab_cap = 0, tab_bytes = 0;             // tab_bytes: how much of h_tab the device table is known to hold (0: nothing -- stage it)
+    hipEvent_t tab_ev = nullptr;                   // behind the last H2D out of h_tab
 };
 
 namespace rtwh {
@@ -280,6 +284,59 @@ __global__ __launch_bounds__(256) void accum_noise_kernel(const unsigned long lo
     out[p] = (T)(num / den);
 }
 
+// ---- the read-only passes over a batch of N accumulators of one size (rtw_accum_resolve_batch_*, rtw_accum_noise_batch_*): ONE launch over
+// the views' elements, flat element g = v * (elements of a view) + k; view v is read through a device table and written at out + v * (elements
+// of a view).  The arithmetic of an element is the single kernel's, operation for operation, so view v is the single call on the bits. ----
+// chunks null: a uniform accumulator, `samples` is its divisor; else an adaptive one, its C_t array and its render's spp / chunk size
+struct ReadView { const unsigned long long *words; const int *chunks; int samples, spp, chunk_spp, pad; };
+// element k of view v = accum_resolve_tiles_kernel's (adaptive) or accum_resolve_kernel's (uniform) of that view
+template <typename T>
+__global__ __launch_bounds__(256) void accum_resolve_batch_kernel(const ReadView *__restrict__ views, T *__restrict__ out, size_t view_elems, size_t n_elems, int height, int tiles_i, int gamma) {
+    const size_t g = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (g >= n_elems) return;
+    const size_t view = g / view_elems, k = g - view * view_elems;
+    const ReadView V = views[view];
+    const size_t pix = k / 3u;
+    const unsigned ch = (unsigned)(k - pix * 3u);
+    int samples = V.samples;
+    if (V.chunks) {
+        const size_t j = pix / (size_t)height, i = pix - j * (size_t)height;
+        const long long held = (long long)V.chunks[(j >> 3) * (size_t)tiles_i + (i >> 3)] * V.chunk_spp;
+        samples = held < V.spp ? (int)held : V.spp;
+    }
+    const unsigned long long *a = V.words + pix * 8u;
+    double v = rtw::fx_to_double(a[2 * ch], a[2 * ch + 1]);
+    if (a[6] != 0ull) v = __builtin_nan("");
+    v = v / (double)samples;
+    if (gamma) v = __builtin_sqrt(v);
+    out[g] = (T)v;
+}
+// pixel p of view v = accum_noise_kernel's of that view: pixel_rho and the 3 x 3 binomial mean, every neighbour bounded by the view's own frame
+template <typename T>
+__global__ __launch_bounds__(256) void accum_noise_batch_kernel(const ReadView *__restrict__ views, T *__restrict__ out, size_t n_pix, int width, int height, int tiles_i, int spp,
+                                                                int chunk_spp, double floor) {
+    const size_t g = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (g >= n_pix) return;
+    const size_t view_pix = (size_t)width * (size_t)height, view = g / view_pix, p = g - view * view_pix;
+    const unsigned long long *words = views[view].words;
+    const int *chunks = views[view].chunks;
+    const size_t j = p / (size_t)height, i = p - j * (size_t)height;
+    double rho;
+    if (!pixel_rho(words, chunks, i, j, height, tiles_i, spp, chunk_spp, floor, &rho)) { out[g] = (T)__builtin_nan(""); return; }
+    double num = 0.0, den = 0.0;
+    for (int dj = -1; dj <= 1; ++dj)
+        for (int di = -1; di <= 1; ++di) {
+            const long long qi = (long long)i + di, qj = (long long)j + dj;
+            if (qi < 0 || qi >= height || qj < 0 || qj >= width) continue;
+            double r;
+            if (!pixel_rho(words, chunks, (size_t)qi, (size_t)qj, height, tiles_i, spp, chunk_spp, floor, &r)) continue;
+            const double b = (double)((di == 0 ? 2 : 1) * (dj == 0 ? 2 : 1));
+            num = num + b * r;
+            den = den + b;
+        }
+    out[g] = (T)(num / den);
+}
+
 // ---- the launches of the tile kernels: adaptive_loop / resolve_dev and the unit ops 21-23 (accum_unit) all go through these, so the test
 // seam runs the product's kernels with the product's grids.  (enqueue only: the caller clears and reads hipGetLastError around them) ----
 int tiles_down(int height) { return (height + 7) / 8; }
@@ -321,6 +378,18 @@ template <typename T>
 void launch_noise(hipStream_t stream, const unsigned long long *words, T *d_out, const int *chunks, int width, int height, int spp, int chunk_spp, double floor) {
     const size_t n = (size_t)width * (size_t)height;
     hipLaunchKernelGGL(accum_noise_kernel<T>, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, words, chunks, d_out, width, height, tiles_down(height), spp, chunk_spp, floor);
+}
+
+// ... of the n_views frames of a device-resident view table, view v at d_out + v * W * H * 3 (resolve) / v * W * H (noise)
+template <typename T>
+void launch_resolve_batch(hipStream_t stream, const ReadView *d_views, T *d_out, int n_views, int width, int height, int gamma) {
+    const size_t view_elems = (size_t)width * (size_t)height * 3u, n = view_elems * (size_t)n_views;
+    hipLaunchKernelGGL(accum_resolve_batch_kernel<T>, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, d_views, d_out, view_elems, n, height, tiles_down(height), gamma);
+}
+template <typename T>
+void launch_noise_batch(hipStream_t stream, const ReadView *d_views, T *d_out, int n_views, int width, int height, int spp, int chunk_spp, double floor) {
+    const size_t n = (size_t)width * (size_t)height * (size_t)n_views;
+    hipLaunchKernelGGL(accum_noise_batch_kernel<T>, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, d_views, d_out, n, width, height, tiles_down(height), spp, chunk_spp, floor);
 }
 
 size_t n_pixels(const rtw_accum *a) { return (size_t)a->width * (size_t)a->height; }
@@ -980,6 +1049,60 @@ int unit_noise(int count, const double *in, double *out) {
     return 0;
 }
 
+// ops 30 / 31: the batched per-tile resolve / the batched noise map.  count = n_views.  in = the header of op 23 / op 25 (width, height, spp,
+// chunk_spp, gamma / dark_floor, 0, 0, 0) | per view: n_tiles x C_t >= 1, W * H * 8 raw words.  With E = W * H * 3 (30) or W * H (31): out = per
+// view the E values of the single kernel (accum_resolve_tiles_kernel / accum_noise_kernel), launched view by view | the n_views * E values of ONE
+// launch of the batch kernel; each of type T, widened.  An element nobody wrote reads -7.
+template <typename T>
+int unit_read_batch(int op, int n_views, const double *in, double *out) {
+    const bool noise = op == 31;
+    int W, H, spp, cs, gamma = 0;
+    if (n_views < 1) return fail(-2, "unit op %d: count is the number of views (got %d)", op, n_views);
+    if (int rc = unit_frame(in, &W, &H)) return rc;
+    if (!slot_int(in[2], 1, 0x7fffffff, &spp) || !slot_int(in[3], 1, 0x7fffffff, &cs)) return fail(-2, "unit op %d: spp %g, chunk_spp %g", op, in[2], in[3]);
+    const double floor = in[4];
+    if (noise ? (!std::isfinite(floor) || floor < 0.0) : !slot_int(in[4], 0, 1, &gamma)) return fail(-2, "unit op %d: %s %g", op, noise ? "dark_floor" : "gamma", in[4]);
+    if (in[5] != 0.0 || in[6] != 0.0 || in[7] != 0.0) return fail(-2, "unit op %d: header slots 5 to 7 must be 0", op);
+    const long long n_tiles = tiles_of(W, H), n_words = (long long)W * H * 8, stride = n_tiles + n_words, n_all = (long long)n_views * n_tiles;
+    if (8 + (long long)n_views * stride > RTW_ACCUM_UNIT_SLOTS) return fail(-2, "unit op %d: %d views of %d x %d exceed %lld slots", op, n_views, W, H, RTW_ACCUM_UNIT_SLOTS);
+    std::vector<int32_t> chunks, one;
+    for (int v = 0; v < n_views; ++v) {
+        if (int rc = unit_chunks(in + 8 + (size_t)v * (size_t)stride, n_tiles, 1, &one)) return rc;
+        chunks.insert(chunks.end(), one.begin(), one.end());
+    }
+    DeviceGuard guard;
+    if (int rc = unit_device()) return rc;
+    const size_t per = (size_t)W * (size_t)H * (noise ? 1u : 3u), n_out = 2u * (size_t)n_views * per;
+    const size_t words_b = (size_t)n_views * (size_t)n_words * 8u, tab_b = up16((size_t)n_views * sizeof(ReadView)), out_b = up16(n_out * sizeof(T));
+    DevBuf buf;
+    HIP_TRY(hipMalloc(&buf.p, words_b + tab_b + out_b + (size_t)n_all * sizeof(int32_t)));
+    unsigned long long *d_words = static_cast<unsigned long long *>(buf.p);
+    ReadView *d_views = reinterpret_cast<ReadView *>(static_cast<char *>(buf.p) + words_b);
+    T *d_out = reinterpret_cast<T *>(static_cast<char *>(buf.p) + words_b + tab_b);
+    int32_t *d_chunks = reinterpret_cast<int32_t *>(static_cast<char *>(buf.p) + words_b + tab_b + out_b);
+    std::vector<ReadView> h_views((size_t)n_views);
+    for (int v = 0; v < n_views; ++v) {
+        HIP_TRY(hipMemcpy(d_words + (size_t)v * (size_t)n_words, in + 8 + (size_t)v * (size_t)stride + (size_t)n_tiles, (size_t)n_words * 8u, hipMemcpyHostToDevice));
+        h_views[(size_t)v] = ReadView{d_words + (size_t)v * (size_t)n_words, d_chunks + (size_t)v * (size_t)n_tiles, 0, spp, cs, 0};
+    }
+    std::vector<T> h(n_out, (T)-7);
+    HIP_TRY(hipMemcpy(d_views, h_views.data(), (size_t)n_views * sizeof(ReadView), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_chunks, chunks.data(), (size_t)n_all * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_out, h.data(), n_out * sizeof(T), hipMemcpyHostToDevice));
+    (void)hipGetLastError();
+    for (int v = 0; v < n_views; ++v) {
+        const ReadView &V = h_views[(size_t)v];
+        if (noise) launch_noise<T>(nullptr, V.words, d_out + (size_t)v * per, V.chunks, W, H, spp, cs, floor);
+        else launch_resolve_tiles<T>(nullptr, V.words, d_out + (size_t)v * per, V.chunks, W, H, spp, cs, gamma);
+    }
+    if (noise) launch_noise_batch<T>(nullptr, d_views, d_out + (size_t)n_views * per, n_views, W, H, spp, cs, floor);
+    else launch_resolve_batch<T>(nullptr, d_views, d_out + (size_t)n_views * per, n_views, W, H, gamma);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(h.data(), d_out, n_out * sizeof(T), hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n_out; ++k) out[k] = (double)h[k];
+    return 0;
+}
+
 // ---- an accumulator as the denoiser's input (include/rtw_hip.h rtw_accum_features_*, rtw_accum_noise_*): everything here READS the words and
 // C_t; the calls wait for the accumulator's event and record it afterwards, so a later pass cannot overwrite them under a running kernel ----
 // an adaptive accumulator whose last call finished: C_t on the device is what the host copy says
@@ -1031,8 +1154,164 @@ int accum_features(rtw_scene_handle scene, const CamT *cam, const rtw_params *p,
     return rc;
 }
 
+// ---- the same for a batch (rtw_accum_resolve_batch_*, rtw_accum_features_batch_*, rtw_accum_noise_batch_*): N accumulators of one size on one
+// device, ONE launch per pass; every call waits for EVERY accumulator's event and records it on every one afterwards ----
+// (validate_accum_array, rtw_host.hpp: a null array or entry, the count -- every batched entry point calls it once, before anything looks at an entry)
+// accumulators of ONE size on ONE device: what the one launch's geometry and the one output buffer need
+int validate_same_frame(const rtw_accum_handle *accums, int32_t n_views) {
+    const rtw_accum *a0 = accums[0];
+    for (int32_t v = 1; v < n_views; ++v) {
+        const rtw_accum *a = accums[v];
+        if (a->width != a0->width || a->height != a0->height) return fail(-4, "view %d: the accumulator is %d x %d, view 0's %d x %d", v, a->width, a->height, a0->width, a0->height);
+        if (a->device != a0->device) return fail(-4, "view %d: accumulator on device %d, view 0's on device %d", v, a->device, a0->device);
+    }
+    return 0;
+}
+int wait_for_all(const rtw_accum_handle *accums, int32_t n_views, hipStream_t stream) {
+    for (int32_t v = 0; v < n_views; ++v) if (int rc = wait_for(accums[v], stream)) return rc;
+    return 0;
+}
+int mark_all(const rtw_accum_handle *accums, int32_t n_views, hipStream_t stream) {
+    for (int32_t v = 0; v < n_views; ++v) if (int rc = mark(accums[v], stream)) return rc;
+    return 0;
+}
+// The views' table {words, C_t or null, divisor, spp, chunk size} on the device, by ONE H2D on `stream` (which already waits for the accumulators'
+// events).  It lives with the FIRST accumulator: whatever read the table before is ordered in front of that accumulator's event, hence in
+// front of this copy.  A call whose table is the one the device already holds -- the resolve and the noise map of one batch, a turntable
+// read again -- uploads nothing and does not wait; only a DIFFERENT table waits on the host until the previous copy has left the pinned
+// staging buffer (tab_ev).  (forget_views: after a failure behind the copy the device table counts as unknown.)
+void forget_views(rtw_accum *a0) { a0->tab_bytes = 0; }
+int stage_views(const rtw_accum_handle *accums, int32_t n_views, hipStream_t stream, const ReadView **d_views) {
+    rtw_accum *a0 = accums[0];
+    const size_t bytes = (size_t)n_views * sizeof(ReadView);
+    std::vector<ReadView> tab((size_t)n_views);
+    for (int32_t v = 0; v < n_views; ++v) {
+        const rtw_accum *a = accums[v];
+        tab[(size_t)v] = ReadView{a->words, a->adaptive ? a->d_tiles : nullptr, (int)samples_done(a), (int)a->bind.spp, (int)a->bind.chunk_spp, 0};
+    }
+    *d_views = static_cast<const ReadView *>(a0->d_tab);
+    if (a0->tab_bytes == bytes && memcmp(a0->h_tab, tab.data(), bytes) == 0) return 0;
+    forget_views(a0);
+    if (a0->tab_ev) HIP_TRY(hipEventSynchronize(a0->tab_ev));
+    else HIP_TRY(hipEventCreateWithFlags(&a0->tab_ev, hipEventDisableTiming));
+    if (a0->tab_cap < bytes) {
+        if (a0->d_tab) { HIP_IGNORE(hipFree(a0->d_tab)); a0->d_tab = nullptr; }            // (hipFree waits for the device: nothing reads the old table)
+        if (a0->h_tab) { HIP_IGNORE(hipHostFree(a0->h_tab)); a0->h_tab = nullptr; }
+        a0->tab_cap = 0;
+        HIP_TRY(hipMalloc(&a0->d_tab, bytes));
+        HIP_TRY(hipHostMalloc(&a0->h_tab, bytes, hipHostMallocDefault));
+        a0->tab_cap = bytes;
+    }
+    memcpy(a0->h_tab, tab.data(), bytes);
+    HIP_TRY(hipMemcpyAsync(a0->d_tab, a0->h_tab, bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(a0->tab_ev, stream));
+    a0->tab_bytes = bytes;
+    *d_views = static_cast<const ReadView *>(a0->d_tab);
+    return 0;
+}
+// what follows the table in both read-only passes: the launch's error, then every accumulator's event; a failure forgets the table
+int finish_read_batch(const rtw_accum_handle *accums, int32_t n_views, hipStream_t stream) {
+    const hipError_t e = hipGetLastError();
+    int rc = e == hipSuccess ? mark_all(accums, n_views, stream) : fail((int)e, "batched pass over %d accumulators: %s", n_views, hipGetErrorString(e));
+    if (rc) forget_views(accums[0]);
+    return rc;
+}
+
+// rtw_accum_resolve_batch_*: what rtw_accum_resolve_* refuses, for every view, and the batch's own rules
+int validate_resolve_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64) {
+    if (int rc = validate_distinct(n_views, accums)) return rc;
+    for (int32_t v = 0; v < n_views; ++v) {
+        const rtw_accum *a = accums[v];
+        if (samples_done(a) < 1) return fail(-2, "view %d: the accumulator holds no samples: nothing to resolve", v);
+        if (a->adaptive) if (int rc = check_adaptive_complete(a)) return fail(rc, "view %d: %s", v, std::string(g_err).c_str());
+        if ((a->bind.is_f64 != 0) != f64) return fail(-4, "view %d: accumulator precision does not match the call", v);
+    }
+    if (int rc = validate_same_frame(accums, n_views)) return rc;
+    if ((double)n_pixels(accums[0]) * (double)n_views >= (double)(1ll << 37)) return fail(-5, "batch too large for one call: %d views of %d x %d pixels", n_views, accums[0]->width, accums[0]->height);
+    return 0;
+}
+template <typename T>
+int resolve_batch_dev(const rtw_accum_handle *accums, int32_t n_views, int32_t gamma, void *d_out, hipStream_t stream) {
+    rtw_accum *a0 = accums[0];
+    HIP_TRY(hipSetDevice(a0->device));
+    if (int rc = wait_for_all(accums, n_views, stream)) return rc;
+    const ReadView *d_views = nullptr;
+    if (int rc = stage_views(accums, n_views, stream, &d_views)) return rc;
+    (void)hipGetLastError();
+    launch_resolve_batch<T>(stream, d_views, (T *)d_out, (int)n_views, (int)a0->width, (int)a0->height, (int)gamma);
+    return finish_read_batch(accums, n_views, stream);
+}
+template <typename T>
+int resolve_batch(const rtw_accum_handle *accums, int32_t n_views, int32_t gamma, void *d_out, void *stream_v) {
+    if (!d_out) return fail(-1, "null argument");
+    if (int rc = validate_accum_array(accums, n_views)) return rc;
+    if ((uintptr_t)d_out & (sizeof(T) - 1)) return fail(-2, "the frames must be aligned to their element type");
+    if (int rc = validate_resolve_batch(accums, n_views, sizeof(T) == 8)) return rc;
+    DeviceGuard guard;
+    return resolve_batch_dev<T>(accums, n_views, gamma, d_out, (hipStream_t)stream_v);
+}
+
+// rtw_accum_features_batch_*: the handles of a batched feature pass, after the checks that look at no handle -- every view as
+// rtw_accum_features_* validates it (with its own camera and seed), then the batch's rule: all adaptive, or all uniform with ONE interval
+template <typename CamT>
+int validate_accum_features_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums) {
+    if (int rc = validate_distinct(n_views, accums)) return rc;
+    for (int32_t v = 0; v < n_views; ++v) {
+        const rtw_params q = view_params(p, seeds, v);
+        if (int rc = validate_accum_features(scene, cams + v, &q, accums[v])) return fail(rc, "view %d: %s", v, std::string(g_err).c_str());
+    }
+    const rtw_accum *a0 = accums[0];
+    for (int32_t v = 1; v < n_views; ++v) {
+        const rtw_accum *a = accums[v];
+        if (a->adaptive != a0->adaptive) return fail(-2, "view %d: the accumulators of a batched feature pass are all adaptive or all uniform", v);
+        if (!a->adaptive && a->ranges[0] != a0->ranges[0])
+            return fail(-2, "view %d holds the chunks [%d, %d), view 0 [%d, %d): uniform accumulators of a batched feature pass hold ONE interval", v, a->ranges[0].first,
+                        a->ranges[0].second, a0->ranges[0].first, a0->ranges[0].second);
+    }
+    return 0;
+}
+template <typename CamT>
+int enqueue_accum_features_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums, void *d_out,
+                                 hipStream_t stream, RenderRec **rec, CtxPtr *ctx) {
+    const rtw_accum *a0 = accums[0];
+    HIP_TRY(hipSetDevice(a0->device));
+    if (int rc = wait_for_all(accums, n_views, stream)) return rc;
+    int rc;
+    if (a0->adaptive) {
+        std::vector<const int *> tiles((size_t)n_views);
+        for (int32_t v = 0; v < n_views; ++v) tiles[(size_t)v] = accums[v]->d_tiles;
+        rc = launch_features_t(scene, cams, n_views, seeds, p, 0, 1, d_out, stream, rec, ctx, nullptr, tiles.data());
+    } else rc = launch_features_t(scene, cams, n_views, seeds, p, a0->ranges[0].first, a0->ranges[0].second - a0->ranges[0].first, d_out, stream, rec, ctx);
+    if (rc) return rc;
+    return mark_all(accums, n_views, stream);
+}
+template <typename CamT>
+int accum_features_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums, void *d_out, void *stream_v) {
+    if (!p) return fail(-1, "null params");
+    if (!cams || !accums || !scene || !d_out) return fail(-1, "null argument");
+    if (int rc = validate_accum_array(accums, n_views)) return rc;
+    int nch, cs;
+    if (int rc = validate_features_batch(cams, n_views, p, 0, 1, d_out, &nch, &cs)) return rc;
+    if (((uintptr_t)d_out & 15u) != 0) return fail(-2, "the feature buffer must be 16-byte aligned");
+    if (int rc = validate_accum_features_batch(scene, cams, n_views, seeds, p, accums)) return rc;
+    DeviceGuard guard;
+    RenderRec *rec = nullptr;
+    CtxPtr ctx;
+    release_last();
+    const int rc = enqueue_accum_features_batch(scene, cams, n_views, seeds, p, accums, d_out, (hipStream_t)stream_v, &rec, &ctx);
+    hold_last(rec, ctx);               // (also on a late error: released by the next call)
+    return rc;
+}
+
 }  // namespace
 
+// the array of a batched call itself: a null array or entry, the count
+int validate_accum_array(const rtw_accum_handle *accums, int32_t n_views) {
+    if (!accums) return fail(-1, "null argument");
+    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
+    for (int32_t v = 0; v < n_views; ++v) if (!accums[v]) return fail(-1, "null accumulator (view %d)", v);
+    return 0;
+}
 int validate_accum_features_f32(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, rtw_accum_handle a) { return validate_accum_features(s, c, p, a); }
 int validate_accum_features_f64(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, rtw_accum_handle a) { return validate_accum_features(s, c, p, a); }
 int enqueue_accum_features_f32(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, rtw_accum_handle a, void *d_out, hipStream_t st, RenderRec **rec, CtxPtr *ctx) {
@@ -1062,10 +1341,56 @@ int enqueue_accum_noise(rtw_accum_handle a, bool f64, void *d_out, hipStream_t s
 int enqueue_accum_resolve(rtw_accum_handle a, bool f64, int32_t gamma, void *d_out, hipStream_t stream) {
     return f64 ? resolve_dev<double>(a, gamma, d_out, stream) : resolve_dev<float>(a, gamma, d_out, stream);
 }
+// the batched forms (rtw_accum_filtered_batch_* strings them together as the single call strings the ones above)
+int validate_accum_features_batch_f32(rtw_scene_handle s, const rtw_camera_f32 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a) {
+    return validate_accum_features_batch(s, c, n, sd, p, a);
+}
+int validate_accum_features_batch_f64(rtw_scene_handle s, const rtw_camera_f64 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a) {
+    return validate_accum_features_batch(s, c, n, sd, p, a);
+}
+int enqueue_accum_features_batch_f32(rtw_scene_handle s, const rtw_camera_f32 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a, void *d_out, hipStream_t st,
+                                     RenderRec **rec, CtxPtr *ctx) {
+    return enqueue_accum_features_batch(s, c, n, sd, p, a, d_out, st, rec, ctx);
+}
+int enqueue_accum_features_batch_f64(rtw_scene_handle s, const rtw_camera_f64 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a, void *d_out, hipStream_t st,
+                                     RenderRec **rec, CtxPtr *ctx) {
+    return enqueue_accum_features_batch(s, c, n, sd, p, a, d_out, st, rec, ctx);
+}
+// every view as rtw_accum_noise_* validates it; one frame size and device; ONE spp, chunk size and dark_floor -- the kernel takes one set
+int validate_accum_noise_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64) {
+    if (int rc = validate_distinct(n_views, accums)) return rc;
+    for (int32_t v = 0; v < n_views; ++v)
+        if (int rc = validate_accum_noise(accums[v], f64)) return fail(rc, "view %d: %s", v, std::string(g_err).c_str());
+    if (int rc = validate_same_frame(accums, n_views)) return rc;
+    const rtw_accum *a0 = accums[0];
+    for (int32_t v = 1; v < n_views; ++v) {
+        const rtw_accum *a = accums[v];
+        if (a->bind.spp != a0->bind.spp || a->bind.chunk_spp != a0->bind.chunk_spp || a->ad.dark_floor != a0->ad.dark_floor)
+            return fail(-4, "view %d: spp %d, chunk size %d, dark_floor %g; view 0: %d, %d, %g -- the noise maps of a batch share them", v, a->bind.spp, a->bind.chunk_spp, a->ad.dark_floor,
+                        a0->bind.spp, a0->bind.chunk_spp, a0->ad.dark_floor);
+    }
+    if ((double)n_pixels(a0) * (double)n_views >= (double)(1ll << 39)) return fail(-5, "batch too large for one call: %d views of %d x %d pixels", n_views, a0->width, a0->height);
+    return 0;
+}
+int enqueue_accum_noise_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64, void *d_out, hipStream_t stream) {
+    rtw_accum *a0 = accums[0];
+    HIP_TRY(hipSetDevice(a0->device));
+    if (int rc = wait_for_all(accums, n_views, stream)) return rc;
+    const ReadView *d_views = nullptr;
+    if (int rc = stage_views(accums, n_views, stream, &d_views)) return rc;
+    (void)hipGetLastError();
+    if (f64) launch_noise_batch<double>(stream, d_views, (double *)d_out, (int)n_views, (int)a0->width, (int)a0->height, (int)a0->bind.spp, (int)a0->bind.chunk_spp, a0->ad.dark_floor);
+    else launch_noise_batch<float>(stream, d_views, (float *)d_out, (int)n_views, (int)a0->width, (int)a0->height, (int)a0->bind.spp, (int)a0->bind.chunk_spp, a0->ad.dark_floor);
+    return finish_read_batch(accums, n_views, stream);
+}
+int validate_accum_resolve_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64) { return validate_resolve_batch(accums, n_views, f64); }
+int enqueue_accum_resolve_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64, int32_t gamma, void *d_out, hipStream_t stream) {
+    return f64 ? resolve_batch_dev<double>(accums, n_views, gamma, d_out, stream) : resolve_batch_dev<float>(accums, n_views, gamma, d_out, stream);
+}
 
 int accum_unit(int op, bool f64, int count, const void *in, void *out) {
     if (!in || !out) return fail(-1, "null argument");
-    if (op != 23 && op != 25 && !f64) return fail(-2, "unit op %d is an op of rtw_unit_f64", op);
+    if (op != 23 && op != 25 && op != 30 && op != 31 && !f64) return fail(-2, "unit op %d is an op of rtw_unit_f64", op);
     switch (op) {
         case 21: return unit_tile_check(count, static_cast<const double *>(in), static_cast<long long *>(out));
         case 22: return unit_compact(count, static_cast<const unsigned long long *>(in), static_cast<long long *>(out));
@@ -1073,6 +1398,8 @@ int accum_unit(int op, bool f64, int count, const void *in, void *out) {
                             : unit_resolve_tiles<float>(count, static_cast<const double *>(in), static_cast<double *>(out));
         case 25: return f64 ? unit_noise<double>(count, static_cast<const double *>(in), static_cast<double *>(out))
                             : unit_noise<float>(count, static_cast<const double *>(in), static_cast<double *>(out));
+        case 30: case 31: return f64 ? unit_read_batch<double>(op, count, static_cast<const double *>(in), static_cast<double *>(out))
+                                     : unit_read_batch<float>(op, count, static_cast<const double *>(in), static_cast<double *>(out));
     }
     return fail(-2, "unknown unit op %d", op);
 }
@@ -1112,6 +1439,9 @@ int rtw_accum_free(rtw_accum_handle a) {
     if (a->ev) { HIP_IGNORE(hipEventSynchronize(a->ev)); HIP_IGNORE(hipEventDestroy(a->ev)); }
     if (a->words) HIP_IGNORE(hipFree(a->words));
     if (a->d_tiles) HIP_IGNORE(hipFree(a->d_tiles));
+    if (a->tab_ev) { HIP_IGNORE(hipEventSynchronize(a->tab_ev)); HIP_IGNORE(hipEventDestroy(a->tab_ev)); }
+    if (a->d_tab) HIP_IGNORE(hipFree(a->d_tab));
+    if (a->h_tab) HIP_IGNORE(hipHostFree(a->h_tab));
     delete a;
     return 0;
 }
@@ -1194,6 +1524,27 @@ int rtw_accum_resolve_f64(rtw_accum_handle a, int32_t gamma, void *d_out, void *
     DeviceGuard guard;
     return resolve_dev<double>(a, gamma, d_out, (hipStream_t)stream);
 }
+int rtw_accum_resolve_batch_f32(const rtw_accum_handle *accums, int32_t n_views, int32_t gamma, void *d_out, void *stream) { return resolve_batch<float>(accums, n_views, gamma, d_out, stream); }
+int rtw_accum_resolve_batch_f64(const rtw_accum_handle *accums, int32_t n_views, int32_t gamma, void *d_out, void *stream) { return resolve_batch<double>(accums, n_views, gamma, d_out, stream); }
+int rtw_accum_features_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums,
+                                 void *d_out, void *stream) {
+    return accum_features_batch(scene, cams, n_views, seeds, p, accums, d_out, stream);
+}
+int rtw_accum_features_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums,
+                                 void *d_out, void *stream) {
+    return accum_features_batch(scene, cams, n_views, seeds, p, accums, d_out, stream);
+}
+static int accum_noise_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64, void *d_out, void *stream) {
+    if (!d_out) return fail(-1, "null argument");
+    if (int rc = validate_accum_array(accums, n_views)) return rc;
+    if ((uintptr_t)d_out & (f64 ? 7u : 3u)) return fail(-2, "the noise maps must be aligned to their element type");
+    if (int rc = validate_accum_noise_batch(accums, n_views, f64)) return rc;
+    DeviceGuard guard;
+    return enqueue_accum_noise_batch(accums, n_views, f64, d_out, (hipStream_t)stream);
+}
+int rtw_accum_noise_batch_f32(const rtw_accum_handle *accums, int32_t n_views, void *d_out, void *stream) { return accum_noise_batch(accums, n_views, false, d_out, stream); }
+int rtw_accum_noise_batch_f64(const rtw_accum_handle *accums, int32_t n_views, void *d_out, void *stream) { return accum_noise_batch(accums, n_views, true, d_out, stream); }
+
 int rtw_accum_resolve_host_f32(rtw_accum_handle a, int32_t gamma, float *out) { return resolve_host<float>(a, gamma, out); }
 int rtw_accum_resolve_host_f64(rtw_accum_handle a, int32_t gamma, double *out) { return resolve_host<double>(a, gamma, out); }
 

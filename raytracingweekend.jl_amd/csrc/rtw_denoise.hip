@@ -34,15 +34,15 @@ static long long plane_bytes(int32_t width, int32_t height, int elem_bytes) { re
 
 // Enqueue the denoiser on `stream` of the current device (validate_denoise has accepted the call).  d_noise non-null: the noise-guided
 // form -- the GUIDED instances of both kernels, the same launch sequence and workspace (the variance lives in the A plane's fourth slot).
-// n_views >= 1 (rtw_filter_batch_*; plain form only, validate_filter_batch has accepted it): the same sequence ONCE for n_views frames --
+// n_views >= 1 (rtw_filter_batch_*, rtw_guided_filter_batch_device_*; validate_filter_batch has accepted it): the same sequence ONCE for n_views frames --
 // every buffer and every plane of the workspace holds the views one behind the other, so prepare (which looks at its own pixel only) runs
-// over all N*W*H pixels and the level kernel is the batched one, which bounds the taps by each view's own frame.  n_views == 0: one frame.
+// over all N*W*H pixels (the guided one with a noise map of N*W*H elements) and the level kernel is the batched one, which bounds the taps by
+// each view's own frame.  n_views == 0: one frame.
 template <typename T>
 int launch_denoise(const rtw_denoise_t *d, int32_t width, int32_t height, int n_views, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream,
                    const void *d_noise) {
     using V = typename rtw::DnVec<T>::type;
     const bool batch = n_views != 0;
-    if (batch && d_noise) return fail(-9, "internal: the noise-guided filter has no batched form");
     const long long frames = batch ? n_views : 1, n_pix = (long long)width * height * frames, pb = plane_bytes(width, height, sizeof(T)) * frames;
     char *w = (char *)d_work;
     V *E[2] = {(V *)w, (V *)(w + pb)};
@@ -74,7 +74,8 @@ int launch_denoise(const rtw_denoise_t *d, int32_t width, int32_t height, int n_
         if (batch) {
             rtw::DnLevelBatch<T> LB;
             LB.L = L; LB.n_all = n_pix;
-            hipLaunchKernelGGL((rtw::dn_level_batch<T>), dim3(grid), dim3(256), 0, stream, LB, in, (const V *)G, (const V *)A, next, (T *)d_out);
+            if (guided) hipLaunchKernelGGL((rtw::dn_level_batch<T, true>), dim3(grid), dim3(256), 0, stream, LB, in, (const V *)G, (const V *)A, next, (T *)d_out);
+            else hipLaunchKernelGGL((rtw::dn_level_batch<T, false>), dim3(grid), dim3(256), 0, stream, LB, in, (const V *)G, (const V *)A, next, (T *)d_out);
         } else if (guided) hipLaunchKernelGGL((rtw::dn_level<T, true>), dim3(grid), dim3(256), 0, stream, L, in, (const V *)G, (const V *)A, next, (T *)d_out);
         else hipLaunchKernelGGL((rtw::dn_level<T, false>), dim3(grid), dim3(256), 0, stream, L, in, (const V *)G, (const V *)A, next, (T *)d_out);
         HIP_TRY(hipGetLastError());
@@ -111,7 +112,7 @@ int validate_filter_batch(const rtw_denoise_t *d, int32_t width, int32_t height,
 }
 
 // The device-resident entry points.  n_views == 0: one frame, rtw_denoise_device_* or, with d_noise (H*W elements of T), rtw_guided_filter_device_*;
-// n_views != 0: rtw_filter_batch_device_* (no d_noise).  The alignment and aliasing checks cover the extents of all frames.
+// n_views != 0: rtw_filter_batch_device_* or, with d_noise (n_views*H*W elements), rtw_guided_filter_batch_device_*.  The alignment and aliasing checks cover the extents of all frames.
 template <typename T>
 int denoise_device(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_image, const void *d_features, const void *d_noise, bool guided, void *d_out,
                    void *d_work, void *stream_v) {
@@ -166,6 +167,14 @@ int rtw_filter_batch_device_f32(const rtw_denoise_t *d, int32_t width, int32_t h
 int rtw_filter_batch_device_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_images, const void *d_features, void *d_out, void *d_work,
                                 void *hip_stream) {
     return denoise_device<double>(d, width, height, batch_views(n_views), d_images, d_features, nullptr, false, d_out, d_work, hip_stream);
+}
+int rtw_guided_filter_batch_device_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_images, const void *d_features, const void *d_noise,
+                                       void *d_out, void *d_work, void *hip_stream) {
+    return denoise_device<float>(d, width, height, batch_views(n_views), d_images, d_features, d_noise, true, d_out, d_work, hip_stream);
+}
+int rtw_guided_filter_batch_device_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_images, const void *d_features, const void *d_noise,
+                                       void *d_out, void *d_work, void *hip_stream) {
+    return denoise_device<double>(d, width, height, batch_views(n_views), d_images, d_features, d_noise, true, d_out, d_work, hip_stream);
 }
 
 }  // extern "C"

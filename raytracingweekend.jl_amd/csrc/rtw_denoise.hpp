@@ -11,11 +11,12 @@
 //                  pixel whose entry is not finite as not valid and stores the pixel's colour variance v in A.w (the slot the plain form
 //                  leaves 0); the level kernel divides a tap's colour distance by the CENTRE pixel's v.  Nothing else differs, and the
 //                  instances with GUIDED = false are the plain form's code.
-//   BATCH          N frames of one size in each launch (include/rtw_hip.h rtw_filter_batch_*), plain form only: every plane holds N*W*H slots,
+//   BATCH          N frames of one size in each launch (include/rtw_hip.h rtw_filter_batch_*, rtw_guided_filter_batch_device_*): every plane holds N*W*H slots,
 //                  view v at slot offset v*W*H; the image and the result at v*W*H*3 elements, the features at v*W*H*2 vectors.  Prepare
 //                  looks at its own pixel only, so the batch runs the plain prepare over N*W*H pixels; the level kernel's batched twin, dn_level_batch,
 //                  splits its flat pixel into (view, j, i) and bounds every tap by the view's own frame -- the arithmetic of a pixel is
-//                  dn_tap / dn_centre / dn_store as everywhere.
+//                  dn_tap / dn_centre / dn_store as everywhere.  GUIDED: the noise map holds N*W*H elements, view v at v*W*H; the centre pixel's
+//                  variance is A[p].w as in dn_level<T, true>; the instance with GUIDED = false is the plain batched form's code.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -173,8 +174,8 @@ __global__ __launch_bounds__(256) void dn_level(DnLevel<T> L, const typename DnV
     dn_store<T>(a, ep, gp, p, L, A, Eout, out);
 }
 
-// BATCH (plain form): lane = flat pixel p of the batch = view * W*H + j*H + i; `base` is the view's first slot, every tap stays in [base, base + W*H)
-template <typename T>
+// BATCH: lane = flat pixel p of the batch = view * W*H + j*H + i; `base` is the view's first slot, every tap stays in [base, base + W*H)
+template <typename T, bool GUIDED = false>
 __global__ __launch_bounds__(256) void dn_level_batch(DnLevelBatch<T> B, const typename DnVec<T>::type *__restrict__ Ein, const typename DnVec<T>::type *__restrict__ G,
                                                              const typename DnVec<T>::type *__restrict__ A, typename DnVec<T>::type *__restrict__ Eout, T *__restrict__ out) {
     using V = typename DnVec<T>::type;
@@ -192,6 +193,8 @@ __global__ __launch_bounds__(256) void dn_level_batch(DnLevelBatch<T> B, const t
         base = v * WH; j = r / H; i = r - j * H;
     }
     const V ep = Ein[p], gp = G[p];
+    [[maybe_unused]] T vp = T(1);
+    if constexpr (GUIDED) vp = A[p].w;
     DnSum<T> a = {T(0), T(0), T(0), T(0)};
 #pragma unroll
     for (int dj = -2; dj <= 2; ++dj) {
@@ -202,7 +205,7 @@ __global__ __launch_bounds__(256) void dn_level_batch(DnLevelBatch<T> B, const t
             const bool in = qi >= 0 && qi < H && qj >= 0 && qj < W;
             const long long q = in ? base + qj * H + qi : p;
             const V eq = Ein[q], gq = G[q];
-            dn_tap<T, false>(a, ep, gp, eq, gq, (T)(dn_k(di) * dn_k(dj)), in && gq.w == gq.w, L, T(1));
+            dn_tap<T, GUIDED>(a, ep, gp, eq, gq, (T)(dn_k(di) * dn_k(dj)), in && gq.w == gq.w, L, vp);
         }
     }
     dn_store<T>(a, ep, gp, p, L, A, Eout, out);

@@ -46,11 +46,16 @@ int validate_features_batch(const void *cams, int32_t n_views, const rtw_params 
 // [0, d_tile_chunks[t]) instead of the call's range (which the caller passes as [0, 1): validated, not looked at by the kernel).
 // n_views >= 1 (validate_features_batch has accepted it; no d_tile_chunks): ONE launch of a BATCH instance over the n_views cameras `cam`
 // points to, `seeds` (null: p->seed for every view) and n_views buffers behind d_out; the views go up with the record (upload_views).
-inline int upload_views_t(RenderRec *r, const rtw_camera_f32 *c, int n, const uint64_t *sd, uint64_t s, hipStream_t st, const void **dc, const unsigned long long **ds) { return upload_views_f32(r, c, n, sd, s, st, dc, ds); }
-inline int upload_views_t(RenderRec *r, const rtw_camera_f64 *c, int n, const uint64_t *sd, uint64_t s, hipStream_t st, const void **dc, const unsigned long long **ds) { return upload_views_f64(r, c, n, sd, s, st, dc, ds); }
+// view_tiles non-null (n_views >= 1 only; rtw_accum_features_batch_* on adaptive accumulators): a HOST array of n_views device pointers, the
+// accumulators' tile-chunk arrays -- ONE launch of a TILED && BATCH instance (rtw_features_accum_batch_f32.hip / _f64.hip), the table goes up with the views.
+inline int upload_views_t(RenderRec *r, const rtw_camera_f32 *c, int n, const uint64_t *sd, uint64_t s, hipStream_t st, const void **dc, const unsigned long long **ds, const int *const *t, const int *const **dt) { return upload_views_f32(r, c, n, sd, s, st, dc, ds, t, dt); }
+inline int upload_views_t(RenderRec *r, const rtw_camera_f64 *c, int n, const uint64_t *sd, uint64_t s, hipStream_t st, const void **dc, const unsigned long long **ds, const int *const *t, const int *const **dt) { return upload_views_f64(r, c, n, sd, s, st, dc, ds, t, dt); }
+template <typename T> const void *features_tiled_batch_kernel(bool mfma, bool lds_scene, bool fixed);
+template <> const void *features_tiled_batch_kernel<float>(bool mfma, bool lds_scene, bool fixed) { return features_tiled_batch_kernel_f32(mfma, lds_scene, fixed); }
+template <> const void *features_tiled_batch_kernel<double>(bool mfma, bool lds_scene, bool fixed) { return features_tiled_batch_kernel_f64(mfma, lds_scene, fixed); }
 
 // The feature kernel's instances over the scan (matrix pipe or VALU) and where the scene lives (LDS or global memory), written once for the
-// plain, the TILED and the BATCH form (TILED && BATCH is not built).  FIXED (mfma && lds_scene): the one instance with the default numerics mode compiled in.
+// plain, the TILED and the BATCH form (TILED && BATCH: the same table in a unit per precision, rtw_features_accum_batch_f32.hip / _f64.hip).  FIXED (mfma && lds_scene): the one instance with the default numerics mode compiled in.
 template <typename T, bool TILED, bool BATCH, bool FIXED = false>
 const void *feature_instance(bool mfma, bool lds_scene) {
     if constexpr (FIXED) return (const void *)rtw::features_kernel<T, true, true, rtw::NUM_REFERENCE, TILED, BATCH>;
@@ -60,10 +65,10 @@ const void *feature_instance(bool mfma, bool lds_scene) {
 
 template <typename T, typename CamT>
 int launch_features(rtw_scene_handle scene, const CamT *cam, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out,
-                    hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks) {
+                    hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks, const int *const *view_tiles) {
     if (!scene || !cam || !p || !d_out) return fail(-1, "null argument");
     const bool batch = n_views != 0;
-    if (batch && d_tile_chunks) return fail(-9, "internal: the tiled feature pass has no batched form");
+    if (batch ? d_tile_chunks != nullptr : view_tiles != nullptr) return fail(-9, "internal: a batch takes its tile-chunk arrays as a table, a single view as one array");
     int nch, cs;
     if (batch) { if (int rc = validate_features_batch(cam, n_views, p, chunk_begin, chunk_count, d_out, &nch, &cs)) return rc; }
     else if (int rc = validate_features(p, chunk_begin, chunk_count, &nch, &cs)) return rc;
@@ -92,28 +97,32 @@ int launch_features(rtw_scene_handle scene, const CamT *cam, int n_views, const 
     PlainView<T> V;
     if (int rc = plain_scene_view<T>(scene, mfma, numerics, &V)) return rc;
     const size_t lds_bytes = (batch ? rtw::feat_fixed_lds_bytes<T, true>() : rtw::feat_fixed_lds_bytes<T>()) + (V.lds_scene ? V.scene_bytes : 0);
-    const bool tiled = d_tile_chunks != nullptr;
+    const bool tiled = d_tile_chunks != nullptr || view_tiles != nullptr;
     // the default numerics mode of the headline variant (scene in LDS, matrix pipe): the mode fixed at compile time
     const bool fixed = mfma && V.lds_scene && numerics == rtw::NUM_REFERENCE;
     const void *kern = batch ? feature_instance<T, false, true>(mfma, V.lds_scene) : !tiled ? feature_instance<T, false, false>(mfma, V.lds_scene) : feature_instance<T, true, false>(mfma, V.lds_scene);
     // (asked for after the table, so that the instances are emitted in the order they always were and the object's device code stays the same bytes)
     if (fixed) kern = batch ? feature_instance<T, false, true, true>(mfma, V.lds_scene) : tiled ? feature_instance<T, true, false, true>(mfma, V.lds_scene) : feature_instance<T, false, false, true>(mfma, V.lds_scene);
+    if (batch && tiled) kern = features_tiled_batch_kernel<T>(mfma, V.lds_scene, fixed);
     // (a batch: its tiles numbered flat, v * n_tiles + t -- validate_features_batch: fewer than 2^31)
     const unsigned total_tiles = batch ? K.n_tiles * (unsigned)n_views : K.n_tiles;
     const unsigned grid = (total_tiles + RTW_FEATURE_WAVES - 1u) / RTW_FEATURE_WAVES;
     // (test aid: which instance the rules above picked, in the form of the trace kernel's line -- rtw_launch.hip; the grid is one workgroup
     //  per RTW_FEATURE_WAVES tiles, no occupancy question is asked: blocks_per_cu=0)
     static const bool debug = aid_env("RTW_DEBUG") != nullptr;
-    if (debug)
-        fprintf(stderr, "[rtw debug] features instance: %s lds_scene=%d cull=0 mfma=%d fixed=%d batch=%d accum=%d adapt=%d lds_bytes=%zu blocks_per_cu=0\n", sizeof(T) == 8 ? "f64" : "f32",
-                (int)V.lds_scene, (int)mfma, (int)fixed, (int)batch, (int)tiled, (int)tiled, lds_bytes);
+    if (debug) {
+        char views[32] = "";                                                    // (the TILED && BATCH instance alone: " views=N" at the end of the line)
+        if (batch && tiled) snprintf(views, sizeof views, " views=%d", n_views);
+        fprintf(stderr, "[rtw debug] features instance: %s lds_scene=%d cull=0 mfma=%d fixed=%d batch=%d accum=%d adapt=%d lds_bytes=%zu blocks_per_cu=0%s\n", sizeof(T) == 8 ? "f64" : "f32",
+                (int)V.lds_scene, (int)mfma, (int)fixed, (int)batch, (int)tiled, (int)tiled, lds_bytes, views);
+    }
 
     if (int rc = begin_record(ctx.get(), scene, nch, (int)grid, 64 * RTW_FEATURE_WAVES, offsetof(rtw::DevCounters, t_first), stream, rec_out)) return rc;
-    rtw::FeatViews<T> FV;
+    rtw::FeatTiledViews<T> FV;          // (a BATCH instance that is not TILED takes its base, rtw::FeatViews<T>: the same bytes in front)
     memset(&FV, 0, sizeof FV);
     if (batch) {
         const void *d_cams = nullptr;
-        if (int rc = upload_views_t(*rec_out, cam, n_views, seeds, p->seed, stream, &d_cams, &FV.seeds)) return rc;
+        if (int rc = upload_views_t(*rec_out, cam, n_views, seeds, p->seed, stream, &d_cams, &FV.seeds, view_tiles, &FV.chunks)) return rc;
         FV.cams = (const rtw::Camera<T> *)d_cams;
         FV.total_tiles = total_tiles;
         FV.view_elems = (unsigned long long)p->width * (unsigned long long)p->height * RTW_FEATURE_CHANNELS;
@@ -124,12 +133,12 @@ int launch_features(rtw_scene_handle scene, const CamT *cam, int n_views, const 
 }
 
 int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out,
-                        hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks) {
-    return launch_features<float>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks);
+                        hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks, const int *const *view_tiles) {
+    return launch_features<float>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks, view_tiles);
 }
 int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out,
-                        hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks) {
-    return launch_features<double>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks);
+                        hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks, const int *const *view_tiles) {
+    return launch_features<double>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks, view_tiles);
 }
 
 // The device-resident entry points rtw_render_features_device_* (n_views == 0) and rtw_render_features_batch_device_* (n_views != 0).

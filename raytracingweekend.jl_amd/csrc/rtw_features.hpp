@@ -47,9 +47,16 @@ template <typename T> struct FeatViews {
     unsigned total_tiles;               // N * FeatParams::n_tiles (< 2^31)
     unsigned long long view_elems;      // W * H * 8: elements of one view's buffer
 };
-// the kernel's last argument: the tile-chunk array of the TILED instances (every instance that is not BATCH keeps its signature), the views of a BATCH instance
-template <typename T, bool BATCH> struct FeatLastArg { using type = const int *__restrict__; };
-template <typename T> struct FeatLastArg<T, true> { using type = FeatViews<T>; };
+// ... of a TILED && BATCH launch (rtw_accum_features_batch_* over adaptive accumulators): the same views and, behind them, the device table of
+// the N accumulators' tile-chunk arrays (chunks[v][t] = C_t of view v), staged in the buffer the cameras and seeds go up in
+template <typename T> struct FeatTiledViews : FeatViews<T> {
+    const int *const *chunks;           // N device pointers
+};
+// the kernel's last argument: the tile-chunk array of the TILED instances (every instance that is not BATCH keeps its signature), the views of a
+// BATCH instance, the views and their tile-chunk arrays of a TILED && BATCH one
+template <typename T, bool BATCH, bool TILED = false> struct FeatLastArg { using type = const int *__restrict__; };
+template <typename T> struct FeatLastArg<T, true, false> { using type = FeatViews<T>; };
+template <typename T> struct FeatLastArg<T, true, true> { using type = FeatTiledViews<T>; };
 
 // waves per SIMD the kernel is compiled for: 32 registers of sums next to the scan's own
 template <typename T> struct FeatWaves { static constexpr int value = 4; };
@@ -80,12 +87,14 @@ template <> __device__ __forceinline__ void feat_store8<double>(double *o, const
 // tile_chunks[t] (the accumulator's device array, >= 1), read once and made wave-uniform; P.chunk_begin / chunk_count are not looked at.
 // BATCH: N views in one launch (FeatViews, the last argument): the wave's flat tile g = v * n_tiles + t is tile t of view v, whose camera the
 // wave stages in its own LDS cell, whose seed is seeds[v] and whose buffer starts at out + v * view_elems; cam_arg and P.seed are not looked
-// at.  Everything behind the tile's coordinates is the code of the other instances.  (TILED && BATCH is not built; the last argument keeps
-// its name `tile_chunks` in both forms: FeatLastArg says what it is.)
+// at.  Everything behind the tile's coordinates is the code of the other instances.  (The last argument keeps its name `tile_chunks` in
+// every form: FeatLastArg says what it is.)
+// TILED && BATCH: both -- tile t of view v gets the chunks [0, C) with C = chunks[v][t] of the view's own accumulator, read once and made
+// wave-uniform, so the waves of one workgroup may belong to different views AND run different trip counts; like BATCH it has no workgroup
+// barrier behind the staging of the scene, and a wave behind the last tile leaves without touching a view.
 template <typename T, bool MFMA, bool LDS_SCENE, int NUMK = -1, bool TILED = false, bool BATCH = false>
 __global__ __launch_bounds__(64 * RTW_FEATURE_WAVES, (FeatWaves<T>::value)) void features_kernel(FeatParams P, Camera<T> cam_arg, DevScene<T> scene,
-                                                                                             T *__restrict__ out, DevCounters *ctr, typename FeatLastArg<T, BATCH>::type tile_chunks) {
-    static_assert(!(TILED && BATCH), "the tiled pass has no batched form");
+                                                                                             T *__restrict__ out, DevCounters *ctr, typename FeatLastArg<T, BATCH, TILED>::type tile_chunks) {
     using V4 = typename Vec4<T>::type;
     if constexpr (NUMK >= 0) scene.numerics = NUMK;
     const unsigned lane = lane_id(), wv = threadIdx.x >> 6;
@@ -141,7 +150,11 @@ __global__ __launch_bounds__(64 * RTW_FEATURE_WAVES, (FeatWaves<T>::value)) void
     const T v0 = (T)((double)(P.height - (i0 + 1)) / (double)P.height);                 // T((H - i) / H), src/render.jl:27
 
     int chunk_begin = P.chunk_begin, chunk_count = P.chunk_count;
-    if constexpr (TILED) { chunk_begin = 0; chunk_count = __builtin_amdgcn_readfirstlane(tile_chunks[tile]); }
+    if constexpr (TILED) {
+        chunk_begin = 0;
+        if constexpr (BATCH) chunk_count = __builtin_amdgcn_readfirstlane(tile_chunks.chunks[view][tile]);
+        else chunk_count = __builtin_amdgcn_readfirstlane(tile_chunks[tile]);
+    }
 
     unsigned long long lo[8] = {0, 0, 0, 0, 0, 0, 0, 0}, hi[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned poison = 0;

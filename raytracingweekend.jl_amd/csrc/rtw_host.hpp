@@ -7,6 +7,7 @@
 //                        batch, feature and render + filter calls, the filter on host buffers, or a device list
 //   rtw_multi.hip        what a device list needs: peer access, the on-demand RCCL binding, the un-tile kernel
 //   rtw_batch_accum_f32.hip / _f64.hip  the BATCH && ACCUM instances of the trace kernel (rtw_instances.hpp: the kernel-instance table), a unit per precision
+//   rtw_features_accum_batch_f32.hip / _f64.hip  the TILED && BATCH instances of the feature kernel (rtw_features.hpp), a unit per precision
 //   rtw_accum.hip        progressive render: the accumulator object, its passes, merge / resolve kernels, export / import
 //   rtw_unit.hip         the T0 unit entry points (rtw_units.hpp)
 //   rtw_features.hip     first-hit feature buffers: one launch of the feature kernel (rtw_features.hpp) for one view or a batch of views, the device-resident entry points
@@ -236,9 +237,12 @@ int launch_render_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_
 inline int launch_render_t(rtw_scene_handle s, const rtw_camera_f32 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const AccumPass *a = nullptr) { return launch_render_f32(s, c, n, sd, p, d, st, r, x, a); }
 inline int launch_render_t(rtw_scene_handle s, const rtw_camera_f64 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const AccumPass *a = nullptr) { return launch_render_f64(s, c, n, sd, p, d, st, r, x, a); }
 // a batch's cameras and seeds (null: `seed` for every view) into the record's pinned buffer and, by ONE asynchronous H2D on `stream`, into its
-// device buffer (the upload of launch_render's batches): *d_cams receives the device array of n_views rtw::Camera<T>, *d_seeds that of the seeds
-int upload_views_f32(RenderRec *rec, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds);
-int upload_views_f64(RenderRec *rec, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds);
+// device buffer (the upload of launch_render's batches): *d_cams receives the device array of n_views rtw::Camera<T>, *d_seeds that of the seeds.
+// `tiles` non-null: n_views device pointers (the tile-chunk arrays of adaptive accumulators) travel behind them, *d_tiles receives the table's device address
+int upload_views_f32(RenderRec *rec, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds,
+                     const int *const *tiles = nullptr, const int *const **d_tiles = nullptr);
+int upload_views_f64(RenderRec *rec, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds,
+                     const int *const *tiles = nullptr, const int *const **d_tiles = nullptr);
 int resolve_rec(RenderRec *r, rtw_stats_t *agg);            // wait for a record's kernel and add its counters to `agg`
 // what the kernel-instance table answers (rtw_instances.hpp): the kernel, and whether it has the default numerics mode compiled in
 struct TraceInstance { const void *kern; bool fixed; };
@@ -282,6 +286,24 @@ bool accum_is_adaptive(rtw_accum_handle a);
 int validate_accum_noise(rtw_accum_handle a, bool f64);                                             // adaptive, its last call finished, the call's precision
 int enqueue_accum_noise(rtw_accum_handle a, bool f64, void *d_out, hipStream_t stream);               // H*W elements of T
 int enqueue_accum_resolve(rtw_accum_handle a, bool f64, int32_t gamma, void *d_out, hipStream_t stream);   // rtw_accum_resolve_*'s own path
+// ... and the batched forms (rtw_accum_resolve_batch_* / _features_batch_* / _noise_batch_*, strung together by rtw_accum_filtered_batch_*): n_views >= 1
+// accumulators of one size on one device, ONE launch per pass.  validate_accum_array: a null array or entry, the count -- an entry point calls
+// it once, first.  validate_*_batch: every refusal that looks at a handle (a handle given twice, every view as the single call validates it,
+// the batch's own rules), before any HIP call; enqueue_*: wait for EVERY accumulator's
+// event, launch on `stream`, record every event.  Frames lie view-major behind d_out.
+int validate_accum_array(const rtw_accum_handle *accums, int32_t n_views);
+int validate_accum_features_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums);
+int validate_accum_features_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums);
+int enqueue_accum_features_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums, void *d_out, hipStream_t stream, RenderRec **rec, CtxPtr *ctx);
+int enqueue_accum_features_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums, void *d_out, hipStream_t stream, RenderRec **rec, CtxPtr *ctx);
+inline int validate_accum_features_batch_t(rtw_scene_handle s, const rtw_camera_f32 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a) { return validate_accum_features_batch_f32(s, c, n, sd, p, a); }
+inline int validate_accum_features_batch_t(rtw_scene_handle s, const rtw_camera_f64 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a) { return validate_accum_features_batch_f64(s, c, n, sd, p, a); }
+inline int enqueue_accum_features_batch_t(rtw_scene_handle s, const rtw_camera_f32 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return enqueue_accum_features_batch_f32(s, c, n, sd, p, a, d, st, r, x); }
+inline int enqueue_accum_features_batch_t(rtw_scene_handle s, const rtw_camera_f64 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return enqueue_accum_features_batch_f64(s, c, n, sd, p, a, d, st, r, x); }
+int validate_accum_noise_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64);
+int enqueue_accum_noise_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64, void *d_out, hipStream_t stream);
+int validate_accum_resolve_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64);
+int enqueue_accum_resolve_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64, int32_t gamma, void *d_out, hipStream_t stream);
 
 // rtw_features.hip -- first-hit feature buffers (include/rtw_hip.h rtw_render_features_*).  validate_features: the checks that need no device
 // (the render, whole frames on one device, the chunk range); validate_features_batch: validate_batch's rules together with those and a tile
@@ -293,10 +315,16 @@ int validate_features_batch(const void *cams, int32_t n_views, const rtw_params 
 // instance for that many cameras, seeds (null: p->seed) and buffers of W*H*8 elements behind d_out.
 // d_tile_chunks non-null (n_views == 0 only): the pass over what an adaptive accumulator holds -- tile t gets the chunks [0, d_tile_chunks[t])
 // (device memory, the accumulator's C_t array), the call's own range is validated and otherwise unused.
-int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks = nullptr);
-int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks = nullptr);
-inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f32 *c, int nv, const uint64_t *sd, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const int *tc = nullptr) { return launch_features_f32(s, c, nv, sd, p, b, n, d, st, r, x, tc); }
-inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f64 *c, int nv, const uint64_t *sd, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const int *tc = nullptr) { return launch_features_f64(s, c, nv, sd, p, b, n, d, st, r, x, tc); }
+// view_tiles non-null (n_views >= 1 only): the same pass for a batch of adaptive accumulators in ONE launch of a TILED && BATCH instance -- a HOST
+// array of n_views such device arrays, tile t of view v gets the chunks [0, view_tiles[v][t]).
+int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks = nullptr, const int *const *view_tiles = nullptr);
+int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks = nullptr, const int *const *view_tiles = nullptr);
+inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f32 *c, int nv, const uint64_t *sd, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const int *tc = nullptr, const int *const *vt = nullptr) { return launch_features_f32(s, c, nv, sd, p, b, n, d, st, r, x, tc, vt); }
+inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f64 *c, int nv, const uint64_t *sd, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const int *tc = nullptr, const int *const *vt = nullptr) { return launch_features_f64(s, c, nv, sd, p, b, n, d, st, r, x, tc, vt); }
+// rtw_features_accum_batch_f32.hip / _f64.hip: the TILED && BATCH instance of the feature kernel for a scan variant, as launch_features chooses
+// among the other instances (`fixed`: the headline variant with the default numerics mode compiled in)
+const void *features_tiled_batch_kernel_f32(bool mfma, bool lds_scene, bool fixed);
+const void *features_tiled_batch_kernel_f64(bool mfma, bool lds_scene, bool fixed);
 
 // rtw_denoise.hip -- the feature-guided denoiser (include/rtw_hip.h rtw_denoise_*, rtw_filter_batch_*).  validate_denoise: the checks of one
 // frame that need no device; validate_filter_batch: those, n_views and the batch's size.
@@ -304,8 +332,8 @@ int validate_denoise(const rtw_denoise_t *d, int32_t width, int32_t height);
 int validate_filter_batch(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views);
 // launch_denoise: enqueue its kernels on `stream` of the current device.  n_views == 0: one frame, d_work of rtw_denoise_work_bytes bytes
 // (16-byte aligned); d_noise non-null: the noise-guided form (rtw_guided_filter_device_*), H*W elements of T, the per-pixel relative noise.
-// n_views >= 1 (no d_noise): that many frames of one size in prepare + `levels` launches; every buffer and every plane of the workspace
-// (n_views * rtw_denoise_work_bytes bytes) holds the views one behind the other.
+// n_views >= 1: that many frames of one size in prepare + `levels` launches; every buffer (d_noise: n_views*H*W elements) and every plane of the
+// workspace (n_views * rtw_denoise_work_bytes bytes) holds the views one behind the other.
 int launch_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream, const void *d_noise = nullptr);
 int launch_denoise_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream, const void *d_noise = nullptr);
 inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t nv, const float *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise = nullptr) { return launch_denoise_f32(d, w, h, nv, img, feat, out, work, st, noise); }

@@ -102,12 +102,15 @@ static int job_shape(int nch, long long n_local, int tiles_i, int tiles_j, int s
 
 // A batch's views: the cameras and seeds go into the record's pinned buffer, then ONE asynchronous H2D on the render's stream (the record
 // is handed out again only after ev2, behind this copy, so the pinned buffer is free whenever a render holds the record).
-// (a batched pass: behind them the views' accumulators and divisors, rtw::AccumView)
+// (a batched pass: behind them the views' accumulators and divisors, rtw::AccumView; the batched feature pass over adaptive accumulators:
+//  behind them `tiles`, the n_views device pointers of the accumulators' tile-chunk arrays -- *d_tiles receives the table's device address)
 template <typename T, typename CamT>
-static int upload_views(RenderRec *rec, const CamT *cam, int n_views, const uint64_t *seeds, uint64_t seed, const AccumPass *pass, hipStream_t stream, rtw::BatchArgs<T> *B, rtw::AccumArgs *A) {
+static int upload_views(RenderRec *rec, const CamT *cam, int n_views, const uint64_t *seeds, uint64_t seed, const AccumPass *pass, hipStream_t stream, rtw::BatchArgs<T> *B, rtw::AccumArgs *A,
+                        const int *const *tiles = nullptr, const int *const **d_tiles = nullptr) {
     const size_t cam_bytes = (size_t)n_views * sizeof(rtw::Camera<T>), seed_bytes = (size_t)n_views * sizeof(unsigned long long);
     static_assert(sizeof(rtw::Camera<T>) % 8 == 0, "the seeds and the view table behind the cameras are 8-byte aligned");
-    const size_t bytes = cam_bytes + seed_bytes + (pass ? (size_t)n_views * sizeof(rtw::AccumView) : 0);
+    const size_t tiles_off = cam_bytes + seed_bytes + (pass ? (size_t)n_views * sizeof(rtw::AccumView) : 0);
+    const size_t bytes = tiles_off + (tiles ? (size_t)n_views * sizeof(const int *) : 0);
     if (rec->views_cap < bytes) {
         if (rec->d_views) { HIP_IGNORE(hipFree(rec->d_views)); rec->d_views = nullptr; }
         if (rec->h_views) { HIP_IGNORE(hipHostFree(rec->h_views)); rec->h_views = nullptr; }
@@ -124,6 +127,10 @@ static int upload_views(RenderRec *rec, const CamT *cam, int n_views, const uint
         for (int v = 0; v < n_views; ++v) { hv[v].words = pass->views[v].words; hv[v].samples = pass->views[v].samples; hv[v].pad = 0; }
         A->views = reinterpret_cast<const rtw::AccumView *>(static_cast<const char *>(rec->d_views) + cam_bytes + seed_bytes);
     }
+    if (tiles) {
+        memcpy(static_cast<char *>(rec->h_views) + tiles_off, tiles, (size_t)n_views * sizeof(const int *));
+        *d_tiles = reinterpret_cast<const int *const *>(static_cast<const char *>(rec->d_views) + tiles_off);
+    }
     HIP_TRY(hipMemcpyAsync(rec->d_views, rec->h_views, bytes, hipMemcpyHostToDevice, stream));
     B->cams = reinterpret_cast<const rtw::Camera<T> *>(rec->d_views);
     B->seeds = reinterpret_cast<const unsigned long long *>(static_cast<const char *>(rec->d_views) + cam_bytes);
@@ -133,18 +140,21 @@ static int upload_views(RenderRec *rec, const CamT *cam, int n_views, const uint
 // the same upload for a launch that is not the trace kernel's (the batched feature pass, rtw_features.hip): the device arrays of the
 // cameras and of the seeds in the record's buffer
 template <typename T, typename CamT>
-static int upload_views_plain(RenderRec *rec, const CamT *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds) {
+static int upload_views_plain(RenderRec *rec, const CamT *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds,
+                              const int *const *tiles, const int *const **d_tiles) {
     rtw::BatchArgs<T> B;
     memset(&B, 0, sizeof B);
-    if (int rc = upload_views<T>(rec, cams, n_views, seeds, seed, nullptr, stream, &B, nullptr)) return rc;
+    if (int rc = upload_views<T>(rec, cams, n_views, seeds, seed, nullptr, stream, &B, nullptr, tiles, d_tiles)) return rc;
     *d_cams = B.cams; *d_seeds = B.seeds;
     return 0;
 }
-int upload_views_f32(RenderRec *rec, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds) {
-    return upload_views_plain<float>(rec, cams, n_views, seeds, seed, stream, d_cams, d_seeds);
+int upload_views_f32(RenderRec *rec, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds,
+                     const int *const *tiles, const int *const **d_tiles) {
+    return upload_views_plain<float>(rec, cams, n_views, seeds, seed, stream, d_cams, d_seeds, tiles, d_tiles);
 }
-int upload_views_f64(RenderRec *rec, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds) {
-    return upload_views_plain<double>(rec, cams, n_views, seeds, seed, stream, d_cams, d_seeds);
+int upload_views_f64(RenderRec *rec, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds,
+                     const int *const *tiles, const int *const **d_tiles) {
+    return upload_views_plain<double>(rec, cams, n_views, seeds, seed, stream, d_cams, d_seeds, tiles, d_tiles);
 }
 
 // Enqueue one render (this shard's tiles) on `stream`; `rec` receives the counters and the kernel's events.

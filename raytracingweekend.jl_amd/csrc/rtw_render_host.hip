@@ -416,33 +416,47 @@ int render_host_filtered(const SceneT *scene, const CamT *cams, int32_t n_views,
 // pass over exactly the samples it holds, with `guided` its noise map and the noise-guided filter (else the plain one), all on the
 // accumulator's device in a leased context's buffer and stream, ONE D2H.  The accumulator is only read; every step orders itself behind
 // its event.  rtw_stats() reports the feature pass's record.  (Not through render_one_device: its lease has no scene to upload.)
+// n_views != 0 (rtw_accum_filtered_batch_*): the same for the n_views accumulators behind `accums` with cams[v] / seeds[v] -- ONE batched
+// resolve, ONE batched feature launch, ONE batched noise launch and the batched filter, 4 + levels launches and ONE D2H for any number of views.
 template <typename T, typename CamT>
-int accum_filtered_host(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle a, int32_t guided, T *out) {
+int accum_filtered_host(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, const rtw_accum_handle *accums,
+                        int32_t guided, T *out) {
+    constexpr bool f64 = sizeof(T) == 8;
     if (!p) return fail(-1, "null params");
-    if (!scene || !cam || !d || !a || !out) return fail(-1, "null argument");
+    if (!scene || !cams || !d || !accums || !out) return fail(-1, "null argument");
+    if (n_views) { if (int rc = validate_accum_array(accums, n_views)) return rc; }
+    else if (!accums[0]) return fail(-1, "null argument");
     if (guided != 0 && guided != 1) return fail(-2, "guided must be 0 or 1 (got %d)", guided);
     int nch, cs;                                                   // (the render's and the filter's own checks before a handle is looked at)
-    if (int rc = validate_features(p, 0, 1, &nch, &cs)) return rc;
-    if (int rc = validate_denoise(d, p->width, p->height)) return rc;
-    if (int rc = validate_accum_features_t(scene, cam, p, a)) return rc;
-    if (guided) if (int rc = validate_accum_noise(a, sizeof(T) == 8)) return rc;
+    if (int rc = n_views ? validate_features_batch(cams, n_views, p, 0, 1, out, &nch, &cs) : validate_features(p, 0, 1, &nch, &cs)) return rc;
+    if (int rc = n_views ? validate_filter_batch(d, p->width, p->height, n_views) : validate_denoise(d, p->width, p->height)) return rc;
+    if (int rc = n_views ? validate_accum_features_batch_t(scene, cams, n_views, seeds, p, accums) : validate_accum_features_t(scene, cams, p, accums[0])) return rc;
+    if (n_views) if (int rc = validate_accum_resolve_batch(accums, n_views, f64)) return rc;
+    if (guided) if (int rc = n_views ? validate_accum_noise_batch(accums, n_views, f64) : validate_accum_noise(accums[0], f64)) return rc;
     DeviceGuard guard;
     release_last();
     HostLease L;
-    if (int rc = acquire_host(accum_device_of(a), std::vector<unsigned char>(), &L)) return rc;
+    if (int rc = acquire_host(accum_device_of(accums[0]), std::vector<unsigned char>(), &L)) return rc;
     HostCtx *hc = L.hc;
-    const DenoiseRegions<T> R(p->width, p->height, 0);
+    const DenoiseRegions<T> R(p->width, p->height, n_views);
     const size_t off_noise = (R.total + 15) & ~(size_t)15;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, off_noise + (size_t)p->width * (size_t)p->height * sizeof(T))) return rc;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, off_noise + (size_t)std::max(n_views, 1) * (size_t)p->width * (size_t)p->height * sizeof(T))) return rc;
     char *base = (char *)hc->d_img;
     rtw_denoise_t dd = *d;
     dd.gamma = p->gamma != 0; dd.device = hc->device;
     RenderRec *frec = nullptr;
     CtxPtr fctx;
-    int rc = enqueue_accum_resolve(a, sizeof(T) == 8, 0, base, hc->stream);
-    if (!rc) rc = enqueue_accum_features_t(scene, cam, p, a, base + R.off_feat, hc->stream, &frec, &fctx);
-    if (!rc && guided) rc = enqueue_accum_noise(a, sizeof(T) == 8, base + off_noise, hc->stream);
-    if (!rc) rc = R.launch(&dd, p->width, p->height, 0, base, hc->stream, guided ? base + off_noise : nullptr);
+    int rc;
+    if (n_views) {
+        rc = enqueue_accum_resolve_batch(accums, n_views, f64, 0, base, hc->stream);
+        if (!rc) rc = enqueue_accum_features_batch_t(scene, cams, n_views, seeds, p, accums, base + R.off_feat, hc->stream, &frec, &fctx);
+        if (!rc && guided) rc = enqueue_accum_noise_batch(accums, n_views, f64, base + off_noise, hc->stream);
+    } else {
+        rc = enqueue_accum_resolve(accums[0], f64, 0, base, hc->stream);
+        if (!rc) rc = enqueue_accum_features_t(scene, cams, p, accums[0], base + R.off_feat, hc->stream, &frec, &fctx);
+        if (!rc && guided) rc = enqueue_accum_noise(accums[0], f64, base + off_noise, hc->stream);
+    }
+    if (!rc) rc = R.launch(&dd, p->width, p->height, n_views, base, hc->stream, guided ? base + off_noise : nullptr);
     if (!rc) rc = copy_out(hc, base + R.off_out, out, R.img_b);
     if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
     if (!rc) rc = resolve_rec(frec, &g_last.agg);
@@ -512,10 +526,18 @@ int rtw_render_filtered_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f
 }
 
 int rtw_accum_filtered_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle accum, int32_t guided, float *out) {
-    return accum_filtered_host<float>(scene, cam, p, d, accum, guided, out);
+    return accum_filtered_host<float>(scene, cam, 0, nullptr, p, d, &accum, guided, out);
 }
 int rtw_accum_filtered_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle accum, int32_t guided, double *out) {
-    return accum_filtered_host<double>(scene, cam, p, d, accum, guided, out);
+    return accum_filtered_host<double>(scene, cam, 0, nullptr, p, d, &accum, guided, out);
+}
+int rtw_accum_filtered_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d,
+                                 const rtw_accum_handle *accums, int32_t guided, float *out) {
+    return accum_filtered_host<float>(scene, cams, batch_views(n_views), seeds, p, d, accums, guided, out);
+}
+int rtw_accum_filtered_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d,
+                                 const rtw_accum_handle *accums, int32_t guided, double *out) {
+    return accum_filtered_host<double>(scene, cams, batch_views(n_views), seeds, p, d, accums, guided, out);
 }
 
 }  // extern "C"

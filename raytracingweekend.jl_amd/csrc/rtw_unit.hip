@@ -1,7 +1,7 @@
 // rtw_unit.hip -- the T0 unit entry points (rtw_unit_f32/_f64): host slots -> device -> unit_kernel (rtw_units.hpp) -> host slots
 // Per-item ops with a scene: 8 - 11, 13, 14, 26 (scans and the bounce), 17 - 20 (candidate sinks, rows of RTW_SINK_SLOTS slots, scenes of at most
 // RTW_SINK_SPHERES spheres), 27 (op 20's sink plus the block vote: rows of RTW_VOTE_SLOTS slots), 28 (the cull layout: item p = device position p;
-// the caller's index or -1, in-lane, positions, blocks).  24 is not an op.
+// the caller's index or -1, in-lane, positions, blocks).  24 and 29 are not ops.
 #include "rtw_scene_view.hpp"
 #include "rtw_units.hpp"
 
@@ -11,9 +11,9 @@ namespace rtwh {
 template <typename T, typename SceneT, typename CamT>
 int run_unit(int op_arg, int count, const void *in, void *out, const SceneT *scene, const CamT *cam) {
     const int op = op_arg & 0xff, numerics = (op_arg >> 8) & 3;      // bits 8-9: the numerics mode of the ray-sphere test
-    if (op_arg < 0 || (op_arg >> 10) != 0 || op >= rtw::U_NUM_OPS || op == 24) return fail(-2, "unknown unit op %d", op_arg);
+    if (op_arg < 0 || (op_arg >> 10) != 0 || op >= rtw::U_NUM_OPS || op == 24 || op == 29) return fail(-2, "unknown unit op %d", op_arg);
     if (numerics == 2) return fail(-2, "unknown numerics mode %d (unit op %d)", numerics, op_arg);
-    if (rtw::unit_is_accum(op)) return accum_unit(op, sizeof(T) == 8, count, in, out);      // (ops 21-23 and 25: layouts of their own, no scene, no numerics mode)
+    if (rtw::unit_is_accum(op)) return accum_unit(op, sizeof(T) == 8, count, in, out);      // (ops 21-23, 25, 30 and 31: layouts of their own, no scene, no numerics mode)
     if (count < 0 || (count > 0 && (!in || !out))) return fail(-1, "null argument");
     if (count == 0) return 0;
     const bool sink = rtw::unit_is_sink(op);

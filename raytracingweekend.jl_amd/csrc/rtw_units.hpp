@@ -33,9 +33,14 @@ enum UnitOp {
     // the cull layout itself: item p is device position p (block p / 32).  out: the caller's index of the sphere there (-1: a dead or padding slot, or
     // p beyond the layout), 1 if that position is in the in-lane list, the number of positions, the number of blocks
     U_CULL_LAYOUT = 28,
-    U_NUM_OPS = 29
+    // (29 is not an op either: the first number behind op 28 stays the unknown one callers probe)
+    // the batched per-tile resolve and the batched noise map on hand-made words and C_t, N views in ONE launch next to the single kernels view by view (rtw_accum.hip accum_unit)
+    U_ACCUM_RESOLVE_BATCH = 30, U_ACCUM_NOISE_BATCH = 31,
+    U_NUM_OPS = 32
 };
-__host__ __device__ inline bool unit_is_accum(int op) { return (op >= U_ACCUM_TILE_CHECK && op <= U_ACCUM_RESOLVE_TILES) || op == U_ACCUM_NOISE; }
+__host__ __device__ inline bool unit_is_accum(int op) {
+    return (op >= U_ACCUM_TILE_CHECK && op <= U_ACCUM_RESOLVE_TILES) || op == U_ACCUM_NOISE || op == U_ACCUM_RESOLVE_BATCH || op == U_ACCUM_NOISE_BATCH;
+}
 __host__ __device__ inline bool unit_is_sink(int op) { return (op >= U_SINK_LDS && op <= U_SINK_MFMA_CULL) || op == U_SINK_MFMA_CULL_VOTE; }
 #define RTW_SINK_SPHERES 512
 #define RTW_SINK_SLOTS 18

@@ -149,6 +149,18 @@ def denoise_batch_into(d_out_ptr, d_images_ptr, d_features_ptr, d_work_ptr, imag
                  elem_type, stream, work_bytes, params, n_views=(int(n_views),))
 
 
+def denoise_guided_batch_into(d_out_ptr, d_images_ptr, d_features_ptr, d_noise_ptr, d_work_ptr, image_width, image_height, n_views, *,
+                              elem_type=np.float32, stream=0, work_bytes=None, **params):
+    """The noise-guided batched device form (rtw_guided_filter_batch_device_*): ``denoise_batch_into`` with one more input,
+    ``d_noise_ptr``: n_views*H*W elements, view ``v``'s map at ``v*H*W`` (``AdaptiveBatchRenderer.noise_all_into``).  View ``v`` is bit for
+    bit ``denoise_guided_into`` on frame ``v``.  ``sigma_color`` defaults to ``GUIDED_SIGMA_COLOR``."""
+    if int(n_views) < 1:
+        raise ValueError("n_views must be >= 1")
+    params.setdefault("sigma_color", GUIDED_SIGMA_COLOR)
+    _filter_into("rtw_guided_filter_batch_device_", int(n_views), "batched filter", (d_images_ptr, d_features_ptr, d_noise_ptr, d_out_ptr, d_work_ptr),
+                 image_width, image_height, elem_type, stream, work_bytes, params, n_views=(int(n_views),))
+
+
 def render_denoised_batch(scene, cams, image_width=400, n_samples=1, *, seeds=None, depth=16, seed=1, n_chunks=0, device=-1, gamma=True,
                           group_cull=False, scan_valu=False, numerics=None, levels=3, normal_power_log2=1, sigma_color=0.5, sigma_depth=0.1,
                           demodulate=True):

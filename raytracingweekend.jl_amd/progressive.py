@@ -327,12 +327,14 @@ class ProgressiveBatchRenderer:
                        C.c_void_p(int(d_out)) if d_out else None, C.c_void_p(int(stream))))
 
     def images(self, gamma=True):
-        """The images of the samples added so far (blocking): ``imgs[v, i, j, :]``, view ``v`` like ``render``'s image."""
-        out = np.empty((self.n_views, self.height * self.width * 3), dtype=self.T)
-        fn = self.L.rtw_accum_resolve_host_f64 if _capi.is_f64(self.T) else self.L.rtw_accum_resolve_host_f32
-        for v, acc in enumerate(self.accums):
-            _capi.check(fn(acc, 1 if gamma else 0, out[v].ctypes.data_as(C.c_void_p)))
-        return np.stack([_as_image(out[v], self.height, self.width) for v in range(self.n_views)])
+        """The images of the samples added so far (blocking): ``imgs[v, i, j, :]``, view ``v`` like ``render``'s image.  ONE resolve launch
+        for all views (``images_into``) and one copy back; view ``v`` is bit for bit ``ProgressiveRenderer.image()``.  Like ``features()``
+        it takes its device buffer from torch (RuntimeError without a GPU torch sees; torch must have initialised the GPU first,
+        INTEGRATION.md section 5).  An adaptive view whose last ``run`` failed half way is refused (RtwError -2) until a ``run`` finishes."""
+        import torch
+        buf = self._device_buffer(self.n_views * self.height * self.width * 3)
+        self.images_into(buf.data_ptr(), gamma, stream=torch.cuda.current_stream(buf.device).cuda_stream)
+        return buf.cpu().numpy().reshape(self.n_views, self.width, self.height, 3).transpose(0, 2, 1, 3)
 
     def read_pixels(self, v):
         """View ``v``'s accumulator (blocking): ``words[i, j, :]`` as ``ProgressiveRenderer.read_pixels``."""
@@ -358,6 +360,54 @@ class ProgressiveBatchRenderer:
     def denoised(self, v, gamma=True, **params):
         """View ``v``'s image so far, filtered with the features of exactly the samples it holds (``ProgressiveRenderer.denoised``)."""
         return self._filtered(v, False, gamma, params)
+
+    # ---- all views in each launch (rtw_accum_*_batch_*): view v is, bit for bit, the per-view method ----
+    def _device_buffer(self, n_elems):
+        """a torch tensor on the accumulators' device (``ProgressiveRenderer._device_buffer``)"""
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("torch sees no GPU: a host copy of a device-resident result needs torch for its device buffer")
+        dev = self.info(0)["device"]
+        return torch.empty(int(n_elems), dtype=torch.float64 if _capi.is_f64(self.T) else torch.float32, device=f"cuda:{dev}")
+
+    def _sfx(self):
+        return "f64" if _capi.is_f64(self.T) else "f32"
+
+    def images_into(self, d_out_ptr, gamma=True, stream=0):
+        """Enqueue ONE resolve launch for all views (rtw_accum_resolve_batch_*) into device memory at ``d_out_ptr``: N*H*W*3 elements,
+        view ``v`` at ``v*H*W*3`` in the layout of ``ProgressiveRenderer.image_into``."""
+        fn = getattr(self.L, "rtw_accum_resolve_batch_" + self._sfx())
+        _capi.check(fn(self._handles, self.n_views, 1 if gamma else 0, C.c_void_p(int(d_out_ptr)), C.c_void_p(int(stream))))
+
+    def features_all_into(self, d_out_ptr, *, scan_valu=False, group_cull=False, job_pixels=0, stream=0):
+        """Enqueue ONE feature launch over exactly the samples every view holds (rtw_accum_features_batch_*) into device memory at
+        ``d_out_ptr``: N*H*W*8 elements, 16-byte aligned, view ``v`` at ``v*H*W*8``.  Uniform accumulators must all hold the same single
+        chunk interval; adaptive ones get, per tile, the features of the chunks ``[0, C_t)`` of their own view."""
+        P = self._params(group_cull, scan_valu, job_pixels, True)
+        fn = getattr(self.L, "rtw_accum_features_batch_" + self._sfx())
+        _capi.check(fn(self.handle, self.cams, self.n_views, self.seeds, C.byref(P), self._handles, C.c_void_p(int(d_out_ptr)), C.c_void_p(int(stream))))
+
+    def features_all(self, **kw):
+        """The first-hit features of the samples every view holds (blocking): the dict of ``render_features_batch``, arrays ``[N, H, W, ...]``."""
+        import torch
+        from .features import FEATURE_CHANNELS, split
+        buf = self._device_buffer(self.n_views * self.height * self.width * FEATURE_CHANNELS)
+        self.features_all_into(buf.data_ptr(), stream=torch.cuda.current_stream(buf.device).cuda_stream, **kw)
+        raw = buf.cpu().numpy()
+        return split(raw.reshape(self.n_views, self.width, self.height, FEATURE_CHANNELS).transpose(0, 2, 1, 3))
+
+    def _filtered_all(self, guided, gamma, kw):
+        from .denoise import make_denoise
+        D = make_denoise(gamma=gamma, **kw)
+        P = self._params(False, False, 0, gamma)
+        out = np.empty(self.n_views * self.height * self.width * 3, dtype=self.T)
+        fn = getattr(self.L, "rtw_accum_filtered_batch_" + self._sfx())
+        _capi.check(fn(self.handle, self.cams, self.n_views, self.seeds, C.byref(P), C.byref(D), self._handles, 1 if guided else 0, out.ctypes.data_as(C.c_void_p)))
+        return out.reshape(self.n_views, self.width, self.height, 3).transpose(0, 2, 1, 3)
+
+    def denoised_all(self, gamma=True, **params):
+        """``denoised(v)`` of every view, ``[N, H, W, 3]``, in 3 + ``levels`` launches and one copy for any N (rtw_accum_filtered_batch_*, blocking)."""
+        return self._filtered_all(False, gamma, params)
 
     def ranges(self, v):
         """the chunk ranges view ``v`` holds: sorted list of ``(begin, end)``, end exclusive"""

@@ -2,8 +2,9 @@
 """Register / scratch / occupancy table of every trace_kernel instantiation (hipcc -Rpass-analysis=kernel-resource-usage).
 usage: python tools/kernel_resources.py [--unit NAME.hip ...] [extra hipcc flags]   (cross-compiles for gfx950, no GPU needed)
 The instances live in rtw_launch.hip and, the BATCH && ACCUM ones, in rtw_batch_accum_f32.hip / _f64.hip: one table over all three.
---unit names other translation units instead (rtw_features.hip: the instances of the feature kernel, the batched ones among them; rtw_denoise.hip: the denoiser's kernels and the batched level kernel;
-rtw_accum.hip: the accumulator's kernels, the noise map among them)."""
+--unit names other translation units instead (rtw_features.hip: the instances of the feature kernel, the batched ones among them; rtw_features_accum_batch_f32.hip /
+_f64.hip: its tiled batched instances; rtw_denoise.hip: the denoiser's kernels and the batched level kernels; rtw_accum.hip: the accumulator's kernels, the noise map and the
+batched resolve and noise map among them)."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = ""
@@ -33,10 +34,17 @@ for r in rows:
         m = re.match(r"_ZN3rtw15features_kernelI([fd])Lb([01])ELb([01])ELi(n?\d+)E(?:Lb([01])E)?(?:Lb([01])E)?", n)
         label = f"features<{'f32' if m.group(1) == 'f' else 'f64'}{', mfma' if m.group(2) == '1' else ', valu'}{', lds-scene' if m.group(3) == '1' else ', global-scene'}{', numerics fixed' if not m.group(4).startswith('n') else ''}{', tiled' if m.group(5) == '1' else ''}{', batch' if m.group(6) == '1' else ''}>"
     elif re.match(r"_ZN3rtw\d+dn_level_batchI([fd])", n):
-        label = "denoise level<%s, batch>" % ("f32" if re.match(r"_ZN3rtw\d+dn_level_batchI([fd])", n).group(1) == "f" else "f64")
+        m = re.match(r"_ZN3rtw\d+dn_level_batchI([fd])(?:Lb([01])E)?", n)
+        label = f"denoise level<{'f32' if m.group(1) == 'f' else 'f64'}{', guided' if m.group(2) == '1' else ''}, batch>"
     elif re.match(r"_ZN3rtw\d+dn_(prepare|level)I([fd])", n):
         m = re.match(r"_ZN3rtw\d+dn_(prepare|level)I([fd])(?:Lb([01])E)?", n)
         label = f"denoise {m.group(1)}<{'f32' if m.group(2) == 'f' else 'f64'}{', guided' if m.group(3) == '1' else ''}>"
+    elif re.search(r"accum_(noise|resolve)_batch_kernelI([fd])", n):
+        m = re.search(r"accum_(noise|resolve)_batch_kernelI([fd])", n)
+        label = f"accum {m.group(1)}<{'f32' if m.group(2) == 'f' else 'f64'}, batch>"
+    elif re.search(r"accum_resolve(_tiles)?_kernelI([fd])", n):
+        m = re.search(r"accum_resolve(_tiles)?_kernelI([fd])", n)
+        label = f"accum resolve<{'f32' if m.group(2) == 'f' else 'f64'}{', tiles' if m.group(1) else ''}>"
     elif re.search(r"accum_noise_kernelI([fd])", n):
         label = "accum noise<%s>" % ("f32" if re.search(r"accum_noise_kernelI([fd])", n).group(1) == "f" else "f64")
     elif "unit_kernel" in n:
