@@ -1,6 +1,7 @@
-// rtw_accum.hip -- progressive render (include/rtw_hip.h rtw_accum_*, rtw_render_accum_*): the accumulator object, the checks of a
-// pass, the merge and resolve kernels, the export / import blob, and the adaptive render (rtw_render_adaptive_*): the tile kernels that
-// evaluate the stopping rule from the accumulator words and the host loop of passes over the tiles still active.
+// rtw_accum.hip -- progressive render (include/rtw_hip.h rtw_accum_*, rtw_render_accum_*): the accumulator object (rtw_accum.hpp), the
+// checks of a pass, merge and resolve, the export / import blob, the adaptive render (rtw_render_adaptive_*): the host loop of passes over
+// the tiles still active, and the read-only passes that make an accumulator the denoiser's input.  Host code only: every kernel and its
+// launch is in rtw_accum_kernels.hip.
 //
 // An accumulator is W x H pixels x 8 uint64 in HBM (the job slot's own layout, rtw_kernels.hpp AccumArgs) plus, on the host, the render it
 // is bound to and the chunk ranges it already holds.  Every sample is a signed 64.64 integer and integer addition is associative, so ANY
@@ -8,37 +9,7 @@
 // several -- resolves to the bits of the single render.  Nothing here needs an atomic: within a launch one workgroup owns a pixel, and
 // everything that touches an accumulator is ordered behind its event (`ev`: recorded after every pass / merge / reset, waited for by
 // whatever comes next on whichever stream).
-#include "rtw_host.hpp"
-#include "rtw_path.hpp"         // fx_to_double
-
-// what an accumulator is bound to by its first pass: everything that decides the value of a sample
-struct AccumBind {
-    int32_t is_f64, spp, chunk_spp, n_chunks, max_depth, numerics;
-    uint64_t seed, scene_hash;
-    unsigned char cam[sizeof(rtw_camera_f64)];     // the camera's bytes (Float32: the first half, the rest 0)
-};
-
-struct rtw_accum {
-    int device = -1;
-    int32_t width = 0, height = 0;
-    unsigned long long *words = nullptr;           // device memory: width * height * 8
-    hipEvent_t ev = nullptr;                       // behind the last operation enqueued on `words`
-    bool bound = false;
-    AccumBind bind;
-    std::vector<std::pair<int32_t, int32_t>> ranges;    // chunk ranges [begin, end) already added: sorted, disjoint, coalesced
-                                                        // (adaptive: the one prefix [0, min C_t) -- what the least sampled tile holds)
-    // ---- adaptive accumulators (rtw_render_adaptive_*): tile t holds the chunks [0, C_t) ----
-    bool adaptive = false;
-    bool ad_complete = false;                      // no tile is active under ad.tolerance (false only after a call that failed half way)
-    rtw_adaptive_t ad;                             // the last call's, min_chunks / check_chunks as their effective values
-    int32_t ad_rounds = 0;                         // passes of the last call that held one of its tiles
-    int32_t *d_tiles = nullptr;                    // device memory, 3 n_tiles + 4 int32: C_t | active flags | active list | count (made by the first adaptive call)
-    std::vector<int32_t> tile_chunks;              // host copy of C_t, read back at the end of every call
-    // ---- the view table of a batched read-only pass (rtw_accum_resolve_batch_* / rtw_accum_noise_batch_*) whose FIRST accumulator this is ----
-    void *d_tab = nullptr, *h_tab = nullptr;       // device table; pinned staging of its H2D
-    size_t tab_cap = 0, tab_bytes = 0;             // tab_bytes: how much of h_tab the device table is known to hold (0: nothing -- stage it)
-    hipEvent_t tab_ev = nullptr;                   // behind the last H2D out of h_tab
-};
+#include "rtw_accum.hpp"
 
 namespace rtwh {
 
@@ -53,344 +24,6 @@ struct BlobHeader {
 };
 static_assert(sizeof(BlobHeader) == 248, "the blob header is part of the file format");
 // followed by n_ranges x (int32 begin, int32 end), then width * height * 8 uint64 (little endian, like the device)
-
-// dst += src: lane = one 16-byte pair of one pixel -- a channel's (lo, hi) (128-bit add with carry) or (poison, 0) (plain add)
-__global__ __launch_bounds__(256) void accum_merge_kernel(ulonglong2 *__restrict__ dst, const ulonglong2 *__restrict__ src, size_t n_pairs) {
-    const size_t k = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (k >= n_pairs) return;
-    const ulonglong2 a = dst[k], b = src[k];
-    ulonglong2 r;
-    r.x = a.x + b.x;
-    r.y = a.y + b.y + (((k & 3u) != 3u && r.x < a.x) ? 1ull : 0ull);
-    dst[k] = r;
-}
-
-// accumulator -> RGB{T} frame: store_job's formula (rtw_kernels.hpp) with the divisor `samples`; lane = (pixel, channel)
-template <typename T>
-__global__ __launch_bounds__(256) void accum_resolve_kernel(const unsigned long long *__restrict__ words, T *__restrict__ out, size_t n_elems, int samples, int gamma) {
-    const size_t k = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (k >= n_elems) return;
-    const size_t pix = k / 3u;
-    const unsigned ch = (unsigned)(k - pix * 3u);
-    const unsigned long long *a = words + pix * 8u;
-    double v = rtw::fx_to_double(a[2 * ch], a[2 * ch + 1]);
-    if (a[6] != 0ull) v = __builtin_nan("");
-    v = v / (double)samples;
-    if (gamma) v = __builtin_sqrt(v);
-    out[k] = (T)v;
-}
-
-// ---- adaptive render: the tile kernels (plain vector loads, stores and shuffles; tiles are numbered t = tj * tiles_i + ti) ----
-// The stopping rule of include/rtw_hip.h at checkpoint `c`, one wave per tile, lane = the pixel (i mod 8) + 8 (j mod 8): flags[t] = 1 for
-// a tile that holds exactly c chunks and is NOT converged (it stays active), 0 for every other tile.  D and Y are summed sequentially in
-// lane order by every lane (64 shuffles each): the written rule's own order, so the result does not depend on how a reduction would
-// associate.  n = (double)(c * chunk_spp).  (-ffp-contract=off: no FMA anywhere in this library unless the source writes one.)
-// (tile_not_converged: the rule itself for tile t of one frame, whole wave, the same value in every lane -- shared with the batched check)
-__device__ __forceinline__ int tile_not_converged(const unsigned long long *__restrict__ words, int t, unsigned lane, int tiles_i, int width, int height, double n, double tol, double floor) {
-    const int tj = t / tiles_i, ti = t - tj * tiles_i;
-    const int i = ti * 8 + (int)(lane & 7u), j = tj * 8 + (int)(lane >> 3);
-    const bool valid = i < height && j < width;
-    double d = 0.0, y = 0.0;
-    if (valid) {
-        const unsigned long long *a = words + ((size_t)j * (size_t)height + (size_t)i) * 8u;
-        if (a[6] == 0ull) {
-            const long long h = (long long)a[7];
-            const unsigned long long m = h < 0 ? 0ull - (unsigned long long)h : (unsigned long long)h;
-            d = (double)m * 0x1p-24;                  // (exact scaling)
-            y = (rtw::fx_to_double(a[0], a[1]) + rtw::fx_to_double(a[2], a[3])) + rtw::fx_to_double(a[4], a[5]);
-            y = y > 0.0 ? y : 0.0;
-        }
-    }
-    const double npix = (double)__popcll(__ballot(valid));
-    double D = 0.0, Y = 0.0;
-    for (int k = 0; k < 64; ++k) { D = D + __shfl(d, k); Y = Y + __shfl(y, k); }
-    const double dark = (floor * n) * npix;
-    const double M = Y > dark ? Y : dark;
-    return D <= tol * M ? 0 : 1;
-}
-__global__ __launch_bounds__(256) void accum_tile_check_kernel(const unsigned long long *__restrict__ words, const int *__restrict__ chunks, int *__restrict__ flags,
-                                                               int n_tiles, int tiles_i, int width, int height, int c, double n, double tol, double floor) {
-    const unsigned lane = threadIdx.x & 63u;
-    const int t = (int)(blockIdx.x * 4u + (threadIdx.x >> 6));
-    if (t >= n_tiles) return;                         // (whole waves: no barrier below)
-    if (chunks[t] != c) { if (lane == 0) flags[t] = 0; return; }
-    const int f = tile_not_converged(words, t, lane, tiles_i, width, height, n, tol, floor);
-    if (lane == 0) flags[t] = f;
-}
-
-// ---- the same for a batch of N views (rtw_render_adaptive_batch_*): batch-global tile g = v * n_tiles + t, view v's words and C_t ----
-struct TileView { const unsigned long long *words; int *chunks; };
-// one wave per (view, tile): tile_not_converged on view v's words -- the single check's arithmetic in the single check's order
-__global__ __launch_bounds__(256) void accum_tile_check_batch_kernel(const TileView *__restrict__ views, int *__restrict__ flags, int n_views, int n_tiles, int tiles_i,
-                                                                     int width, int height, int c, double n, double tol, double floor) {
-    const unsigned lane = threadIdx.x & 63u;
-    const unsigned g = blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (g >= (unsigned)n_views * (unsigned)n_tiles) return;      // (whole waves: no barrier below)
-    const unsigned v = g / (unsigned)n_tiles;
-    const int t = (int)(g - v * (unsigned)n_tiles);
-    const TileView V = views[v];
-    if (V.chunks[t] != c) { if (lane == 0) flags[g] = 0; return; }
-    const int f = tile_not_converged(V.words, t, lane, tiles_i, width, height, n, tol, floor);
-    if (lane == 0) flags[g] = f;
-}
-// The batch's list in three small launches instead of one workgroup's loop over N * n_tiles flags (accum_tile_compact_kernel: a chain of
-// n / 1024 dependent steps): blocks of 256 flags are counted, ONE workgroup turns the counts into offsets (and the total into *count), the
-// blocks write their tiles behind their offsets.  The order is the flags' order, so the list is the one the loop makes: sorted.
-__global__ __launch_bounds__(256) void accum_tile_count_kernel(const int *__restrict__ flags, int *__restrict__ block_n, int n) {
-    __shared__ int wave_n[4];
-    const int t = (int)(blockIdx.x * 256u + threadIdx.x);
-    const bool f = t < n && flags[t] != 0;
-    const unsigned long long m = __ballot(f);
-    if ((threadIdx.x & 63u) == 0u) wave_n[threadIdx.x >> 6] = (int)__popcll(m);
-    __syncthreads();
-    if (threadIdx.x == 0) block_n[blockIdx.x] = (wave_n[0] + wave_n[1]) + (wave_n[2] + wave_n[3]);
-}
-// counts -> exclusive prefix sums, in place; one workgroup, 1024 counts per step
-__global__ __launch_bounds__(1024) void accum_tile_scan_kernel(int *__restrict__ block_n, int *__restrict__ count, int nb) {
-    __shared__ int wave_s[16];
-    __shared__ int base;
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) base = 0;
-    __syncthreads();
-    for (int b0 = 0; b0 < nb; b0 += 1024) {
-        const int b = b0 + (int)threadIdx.x;
-        const int v = b < nb ? block_n[b] : 0;
-        int x = v;                                    // inclusive sums within the wave
-        for (unsigned d = 1; d < 64u; d <<= 1) { const int y = __shfl_up(x, d); if (lane >= d) x += y; }
-        if (lane == 63u) wave_s[wave] = x;
-        __syncthreads();
-        int off = base;
-        for (unsigned k = 0; k < wave; ++k) off += wave_s[k];
-        if (b < nb) block_n[b] = off + x - v;
-        __syncthreads();
-        if (threadIdx.x == 0) { int s = 0; for (int k = 0; k < 16; ++k) s += wave_s[k]; base += s; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *count = base;
-}
-__global__ __launch_bounds__(256) void accum_tile_scatter_kernel(const int *__restrict__ flags, const int *__restrict__ block_off, int *__restrict__ list, int n) {
-    __shared__ int wave_n[4];
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const int t = (int)(blockIdx.x * 256u + threadIdx.x);
-    const bool f = t < n && flags[t] != 0;
-    const unsigned long long m = __ballot(f);
-    if (lane == 0u) wave_n[wave] = (int)__popcll(m);
-    __syncthreads();
-    if (f) {
-        int off = block_off[blockIdx.x];
-        for (unsigned k = 0; k < wave; ++k) off += wave_n[k];
-        list[off + (int)__popcll(m & ((1ull << lane) - 1ull))] = t;
-    }
-}
-// after a pass of `add` chunks: C_t += add in each listed tile's OWN view (list == null: for all n = N * n_tiles tiles)
-__global__ __launch_bounds__(256) void accum_tile_advance_batch_kernel(const int *__restrict__ list, int n, const TileView *__restrict__ views, int n_tiles, int add) {
-    const int k = (int)(blockIdx.x * 256u + threadIdx.x);
-    if (k >= n) return;
-    const unsigned g = (unsigned)(list ? list[k] : k), v = g / (unsigned)n_tiles;
-    views[v].chunks[g - v * (unsigned)n_tiles] += add;
-}
-
-// flags -> the SORTED list of the active tiles + its length, one workgroup: ascending tile numbers keep what the sharded path's queues
-// give a shard -- consecutive list entries are neighbours in the frame, local tile k goes to die k mod 8, and a die works through its
-// part of the list in frame order -- and make the list, like everything else here, the same from run to run (an atomic append would
-// finish a few microseconds sooner and order the list by arrival).
-__global__ __launch_bounds__(1024) void accum_tile_compact_kernel(const int *__restrict__ flags, int *__restrict__ list, int *__restrict__ count, int n_tiles) {
-    __shared__ int wave_n[16];
-    __shared__ int base;
-    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) base = 0;
-    __syncthreads();
-    for (int t0 = 0; t0 < n_tiles; t0 += 1024) {
-        const int t = t0 + (int)threadIdx.x;
-        const bool f = t < n_tiles && flags[t] != 0;
-        const unsigned long long m = __ballot(f);
-        if (lane == 0) wave_n[wave] = (int)__popcll(m);
-        __syncthreads();
-        int off = base;
-        for (unsigned k = 0; k < wave; ++k) off += wave_n[k];
-        if (f) list[off + (int)__popcll(m & ((1ull << lane) - 1ull))] = t;
-        __syncthreads();
-        if (threadIdx.x == 0) { int n = 0; for (int k = 0; k < 16; ++k) n += wave_n[k]; base += n; }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *count = base;
-}
-
-// after a pass of `add` chunks: C_t += add for the tiles of the list (list == null: for all n tiles)
-__global__ __launch_bounds__(256) void accum_tile_advance_kernel(const int *__restrict__ list, int n, int *__restrict__ chunks, int add) {
-    const int k = (int)(blockIdx.x * 256u + threadIdx.x);
-    if (k >= n) return;
-    chunks[list ? list[k] : k] += add;
-}
-
-// accum_resolve_kernel for an adaptive accumulator: a pixel is divided by the samples ITS TILE holds, min(spp, C_t * chunk_spp)
-template <typename T>
-__global__ __launch_bounds__(256) void accum_resolve_tiles_kernel(const unsigned long long *__restrict__ words, T *__restrict__ out, size_t n_elems, const int *__restrict__ chunks,
-                                                                  int height, int tiles_i, int spp, int chunk_spp, int gamma) {
-    const size_t k = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (k >= n_elems) return;
-    const size_t pix = k / 3u;
-    const unsigned ch = (unsigned)(k - pix * 3u);
-    const size_t j = pix / (size_t)height, i = pix - j * (size_t)height;
-    const long long held = (long long)chunks[(j >> 3) * (size_t)tiles_i + (i >> 3)] * chunk_spp;
-    const int samples = held < spp ? (int)held : spp;
-    const unsigned long long *a = words + pix * 8u;
-    double v = rtw::fx_to_double(a[2 * ch], a[2 * ch + 1]);
-    if (a[6] != 0ull) v = __builtin_nan("");
-    v = v / (double)samples;
-    if (gamma) v = __builtin_sqrt(v);
-    out[k] = (T)v;
-}
-
-// ---- the noise map of an adaptive accumulator (include/rtw_hip.h rtw_accum_noise_*) ----
-// rho of one pixel: the stopping rule's D / M for the pixel alone, n = the samples ITS tile holds.  false: the pixel is poisoned.
-__device__ __forceinline__ bool pixel_rho(const unsigned long long *__restrict__ words, const int *__restrict__ chunks, size_t i, size_t j, int height, int tiles_i, int spp,
-                                          int chunk_spp, double floor, double *rho) {
-    const unsigned long long *a = words + (j * (size_t)height + i) * 8u;
-    if (a[6] != 0ull) return false;
-    const long long held = (long long)chunks[(j >> 3) * (size_t)tiles_i + (i >> 3)] * chunk_spp;
-    const double n = (double)(held < spp ? held : (long long)spp);
-    const long long h = (long long)a[7];
-    const unsigned long long m = h < 0 ? 0ull - (unsigned long long)h : (unsigned long long)h;
-    const double D = (double)m * 0x1p-24;                  // (exact scaling)
-    double y = (rtw::fx_to_double(a[0], a[1]) + rtw::fx_to_double(a[2], a[3])) + rtw::fx_to_double(a[4], a[5]);
-    y = y > 0.0 ? y : 0.0;
-    const double dark = floor * n;
-    const double M = y > dark ? y : dark;
-    *rho = M > 0.0 ? D / M : 0.0;
-    return true;
-}
-// one pixel per lane, lanes along i: the 3 x 3 binomial mean of rho over the neighbours inside the frame that are not poisoned, dj outer,
-// di inner, both sums sequential; a poisoned centre is a quiet NaN.  Reads only; no LDS, no atomics, no cross-lane operation.
-template <typename T>
-__global__ __launch_bounds__(256) void accum_noise_kernel(const unsigned long long *__restrict__ words, const int *__restrict__ chunks, T *__restrict__ out, int width, int height,
-                                                          int tiles_i, int spp, int chunk_spp, double floor) {
-    const size_t p = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (p >= (size_t)width * (size_t)height) return;
-    const size_t j = p / (size_t)height, i = p - j * (size_t)height;
-    double rho;
-    if (!pixel_rho(words, chunks, i, j, height, tiles_i, spp, chunk_spp, floor, &rho)) { out[p] = (T)__builtin_nan(""); return; }
-    double num = 0.0, den = 0.0;
-    for (int dj = -1; dj <= 1; ++dj)
-        for (int di = -1; di <= 1; ++di) {
-            const long long qi = (long long)i + di, qj = (long long)j + dj;
-            if (qi < 0 || qi >= height || qj < 0 || qj >= width) continue;
-            double r;
-            if (!pixel_rho(words, chunks, (size_t)qi, (size_t)qj, height, tiles_i, spp, chunk_spp, floor, &r)) continue;
-            const double b = (double)((di == 0 ? 2 : 1) * (dj == 0 ? 2 : 1));
-            num = num + b * r;
-            den = den + b;
-        }
-    out[p] = (T)(num / den);
-}
-
-// ---- the read-only passes over a batch of N accumulators of one size (rtw_accum_resolve_batch_*, rtw_accum_noise_batch_*): ONE launch over
-// the views' elements, flat element g = v * (elements of a view) + k; view v is read through a device table and written at out + v * (elements
-// of a view).  The arithmetic of an element is the single kernel's, operation for operation, so view v is the single call on the bits. ----
-// chunks null: a uniform accumulator, `samples` is its divisor; else an adaptive one, its C_t array and its render's spp / chunk size
-struct ReadView { const unsigned long long *words; const int *chunks; int samples, spp, chunk_spp, pad; };
-// element k of view v = accum_resolve_tiles_kernel's (adaptive) or accum_resolve_kernel's (uniform) of that view
-template <typename T>
-__global__ __launch_bounds__(256) void accum_resolve_batch_kernel(const ReadView *__restrict__ views, T *__restrict__ out, size_t view_elems, size_t n_elems, int height, int tiles_i, int gamma) {
-    const size_t g = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (g >= n_elems) return;
-    const size_t view = g / view_elems, k = g - view * view_elems;
-    const ReadView V = views[view];
-    const size_t pix = k / 3u;
-    const unsigned ch = (unsigned)(k - pix * 3u);
-    int samples = V.samples;
-    if (V.chunks) {
-        const size_t j = pix / (size_t)height, i = pix - j * (size_t)height;
-        const long long held = (long long)V.chunks[(j >> 3) * (size_t)tiles_i + (i >> 3)] * V.chunk_spp;
-        samples = held < V.spp ? (int)held : V.spp;
-    }
-    const unsigned long long *a = V.words + pix * 8u;
-    double v = rtw::fx_to_double(a[2 * ch], a[2 * ch + 1]);
-    if (a[6] != 0ull) v = __builtin_nan("");
-    v = v / (double)samples;
-    if (gamma) v = __builtin_sqrt(v);
-    out[g] = (T)v;
-}
-// pixel p of view v = accum_noise_kernel's of that view: pixel_rho and the 3 x 3 binomial mean, every neighbour bounded by the view's own frame
-template <typename T>
-__global__ __launch_bounds__(256) void accum_noise_batch_kernel(const ReadView *__restrict__ views, T *__restrict__ out, size_t n_pix, int width, int height, int tiles_i, int spp,
-                                                                int chunk_spp, double floor) {
-    const size_t g = (size_t)blockIdx.x * 256u + threadIdx.x;
-    if (g >= n_pix) return;
-    const size_t view_pix = (size_t)width * (size_t)height, view = g / view_pix, p = g - view * view_pix;
-    const unsigned long long *words = views[view].words;
-    const int *chunks = views[view].chunks;
-    const size_t j = p / (size_t)height, i = p - j * (size_t)height;
-    double rho;
-    if (!pixel_rho(words, chunks, i, j, height, tiles_i, spp, chunk_spp, floor, &rho)) { out[g] = (T)__builtin_nan(""); return; }
-    double num = 0.0, den = 0.0;
-    for (int dj = -1; dj <= 1; ++dj)
-        for (int di = -1; di <= 1; ++di) {
-            const long long qi = (long long)i + di, qj = (long long)j + dj;
-            if (qi < 0 || qi >= height || qj < 0 || qj >= width) continue;
-            double r;
-            if (!pixel_rho(words, chunks, (size_t)qi, (size_t)qj, height, tiles_i, spp, chunk_spp, floor, &r)) continue;
-            const double b = (double)((di == 0 ? 2 : 1) * (dj == 0 ? 2 : 1));
-            num = num + b * r;
-            den = den + b;
-        }
-    out[g] = (T)(num / den);
-}
-
-// ---- the launches of the tile kernels: adaptive_loop / resolve_dev and the unit ops 21-23 (accum_unit) all go through these, so the test
-// seam runs the product's kernels with the product's grids.  (enqueue only: the caller clears and reads hipGetLastError around them) ----
-int tiles_down(int height) { return (height + 7) / 8; }
-int tiles_of(int width, int height) { return tiles_down(height) * ((width + 7) / 8); }
-// the check at checkpoint `c` of ONE frame: flags[t] for its tiles (n handed to the rule: the samples of c chunks of `cs`)
-void launch_tile_check(hipStream_t stream, const unsigned long long *words, const int *chunks, int *flags, int width, int height, int c, int cs, double tol, double floor) {
-    const int n_tiles = tiles_of(width, height);
-    hipLaunchKernelGGL(accum_tile_check_kernel, dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, stream, words, chunks, flags, n_tiles, tiles_down(height),
-                       width, height, c, (double)((long long)c * cs), tol, floor);
-}
-// ... of the n_views frames of a device-resident view table: flags[v * n_tiles + t]
-void launch_tile_check_batch(hipStream_t stream, const TileView *d_views, int *flags, int n_views, int width, int height, int c, int cs, double tol, double floor) {
-    const int n_tiles = tiles_of(width, height);
-    const long long n_all = (long long)n_views * n_tiles;
-    hipLaunchKernelGGL(accum_tile_check_batch_kernel, dim3((unsigned)((n_all + 3) / 4)), dim3(256), 0, stream, d_views, flags, n_views, n_tiles, tiles_down(height),
-                       width, height, c, (double)((long long)c * cs), tol, floor);
-}
-// n flags -> the sorted list + its length: one workgroup's loop, or count / scan / scatter over compact_blocks(n) ints of scratch
-void launch_compact_loop(hipStream_t stream, const int *flags, int *list, int *count, int n) {
-    hipLaunchKernelGGL(accum_tile_compact_kernel, dim3(1), dim3(1024), 0, stream, flags, list, count, n);
-}
-int compact_blocks(long long n) { return (int)((n + 255) / 256); }
-void launch_compact_blocks(hipStream_t stream, const int *flags, int *blocks, int *list, int *count, int n) {
-    const int n_blocks = compact_blocks(n);
-    hipLaunchKernelGGL(accum_tile_count_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, flags, blocks, n);
-    hipLaunchKernelGGL(accum_tile_scan_kernel, dim3(1), dim3(1024), 0, stream, blocks, count, n_blocks);
-    hipLaunchKernelGGL(accum_tile_scatter_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, flags, blocks, list, n);
-}
-// the frame of an adaptive accumulator: every pixel over the samples its tile holds
-template <typename T>
-void launch_resolve_tiles(hipStream_t stream, const unsigned long long *words, T *d_out, const int *chunks, int width, int height, int spp, int chunk_spp, int gamma) {
-    const size_t n = (size_t)width * (size_t)height * 3u;
-    hipLaunchKernelGGL(accum_resolve_tiles_kernel<T>, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, words, d_out, n, chunks, height, tiles_down(height),
-                       spp, chunk_spp, gamma);
-}
-
-// the noise map of a frame whose tile t holds C_t = chunks[t] >= 1 chunks (rtw_accum_noise_* and the unit op 25)
-template <typename T>
-void launch_noise(hipStream_t stream, const unsigned long long *words, T *d_out, const int *chunks, int width, int height, int spp, int chunk_spp, double floor) {
-    const size_t n = (size_t)width * (size_t)height;
-    hipLaunchKernelGGL(accum_noise_kernel<T>, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, words, chunks, d_out, width, height, tiles_down(height), spp, chunk_spp, floor);
-}
-
-// ... of the n_views frames of a device-resident view table, view v at d_out + v * W * H * 3 (resolve) / v * W * H (noise)
-template <typename T>
-void launch_resolve_batch(hipStream_t stream, const ReadView *d_views, T *d_out, int n_views, int width, int height, int gamma) {
-    const size_t view_elems = (size_t)width * (size_t)height * 3u, n = view_elems * (size_t)n_views;
-    hipLaunchKernelGGL(accum_resolve_batch_kernel<T>, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, d_views, d_out, view_elems, n, height, tiles_down(height), gamma);
-}
-template <typename T>
-void launch_noise_batch(hipStream_t stream, const ReadView *d_views, T *d_out, int n_views, int width, int height, int spp, int chunk_spp, double floor) {
-    const size_t n = (size_t)width * (size_t)height * (size_t)n_views;
-    hipLaunchKernelGGL(accum_noise_batch_kernel<T>, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, d_views, d_out, n, width, height, tiles_down(height), spp, chunk_spp, floor);
-}
 
 size_t n_pixels(const rtw_accum *a) { return (size_t)a->width * (size_t)a->height; }
 
@@ -480,12 +113,9 @@ int resolve_dev(rtw_accum *a, int32_t gamma, void *d_out, hipStream_t stream) {
     if (a->bind.is_f64 != (sizeof(T) == 8)) return fail(-4, "accumulator precision does not match the call");
     HIP_TRY(hipSetDevice(a->device));
     if (int rc = wait_for(a, stream)) return rc;
-    const size_t n = n_pixels(a) * 3u;
     (void)hipGetLastError();
-    if (a->adaptive)
-        launch_resolve_tiles<T>(stream, a->words, (T *)d_out, a->d_tiles, (int)a->width, (int)a->height, (int)a->bind.spp, (int)a->bind.chunk_spp, (int)gamma);
-    else
-    hipLaunchKernelGGL(accum_resolve_kernel<T>, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, a->words, (T *)d_out, n, (int)s, (int)gamma);
+    if (a->adaptive) launch_resolve_tiles<T>(stream, a->words, (T *)d_out, a->d_tiles, (int)a->width, (int)a->height, (int)a->bind.spp, (int)a->bind.chunk_spp, (int)gamma);
+    else launch_resolve<T>(stream, a->words, (T *)d_out, (int)a->width, (int)a->height, (int)s, (int)gamma);
     HIP_TRY(hipGetLastError());
     return mark(a, stream);
 }
@@ -704,8 +334,8 @@ int adaptive_loop(bool single, rtw_scene_handle scene, const CamT *cams, int32_t
         int rc = launch_render_t(scene, cams, single ? 0 : n_views, seeds, p, nullptr, stream, &rec, &ctx, &ps);
         if (rc) { hold_last(rec, ctx); rec = nullptr; return rc; }     // (released by the next call)
         (void)hipGetLastError();
-        if (single) hipLaunchKernelGGL(accum_tile_advance_kernel, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, stream, list, n_list, a0->d_tiles, count);
-        else hipLaunchKernelGGL(accum_tile_advance_batch_kernel, dim3((unsigned)((n_list + 255) / 256)), dim3(256), 0, stream, list, n_list, d_views, n_tiles, count);
+        if (single) launch_tile_advance(stream, list, n_list, a0->d_tiles, count);
+        else launch_tile_advance_batch(stream, list, n_list, d_views, n_tiles, count);
         HIP_TRY(hipGetLastError());
         pass_at.push_back(begin);
         return 0;
@@ -876,233 +506,6 @@ int adaptive_info(const rtw_accum *a, rtw_adaptive_info_t *out) {
     return 0;
 }
 
-// ---- the unit ops 21-23 (include/rtw_hip.h rtw_unit_f64; tests/test_gpu_accum_kernels.py): the tile kernels on the caller's words ----
-// A test seam like the other rtw_unit ops: host slots in, host slots out, the null stream, blocking copies, one device allocation that is
-// freed on return.  Everything is validated before the first HIP call: nulls -1; a size or a value the layout does not hold, or a call
-// of more than RTW_ACCUM_UNIT_SLOTS input slots, -2.  The kernels run through the launch helpers of the adaptive loop.
-#define RTW_ACCUM_UNIT_SLOTS (1ll << 24)         // 128 MiB of 8-byte slots
-#define RTW_ACCUM_UNIT_PIXELS (1ll << 20)        // ... and frames of at most this many pixels, 16384 on a side
-struct DevBuf { void *p = nullptr; ~DevBuf() { if (p) HIP_IGNORE(hipFree(p)); } };
-size_t up16(size_t b) { return (b + 15u) / 16u * 16u; }
-// a slot that holds an integer of [lo, hi] as a binary64 value
-bool slot_int(double d, long long lo, long long hi, int *out) {
-    if (!(d >= (double)lo && d <= (double)hi) || d != std::floor(d)) return false;
-    *out = (int)d;
-    return true;
-}
-int unit_frame(const double *in, int *W, int *H) {
-    if (!slot_int(in[0], 1, 1 << 14, W) || !slot_int(in[1], 1, 1 << 14, H) || (long long)*W * *H > RTW_ACCUM_UNIT_PIXELS)
-        return fail(-2, "accumulator unit op: a frame of %g x %g (at most 16384 on a side, %lld pixels)", in[0], in[1], RTW_ACCUM_UNIT_PIXELS);
-    return 0;
-}
-int unit_chunks(const double *slots, long long n, int lowest, std::vector<int32_t> *out) {
-    out->resize((size_t)n);
-    for (long long k = 0; k < n; ++k) {
-        int c;
-        if (!slot_int(slots[k], lowest, 0x7fffffff, &c)) return fail(-2, "accumulator unit op: tile chunk count %g (slot %lld)", slots[k], k);
-        (*out)[(size_t)k] = c;
-    }
-    return 0;
-}
-int unit_device() {
-    int dev;
-    if (int rc = resolve_device(-1, &dev)) return rc;
-    HIP_TRY(hipSetDevice(dev));
-    return 0;
-}
-
-// op 21: in = width, height, c, chunk_spp, tol, floor, 0, 0 | per view: n_tiles x C_t, W * H * 8 raw words; out (raw int64) = per view the
-// n_tiles flags of accum_tile_check_kernel, launched view by view | the n_views * n_tiles flags of ONE accum_tile_check_batch_kernel launch
-int unit_tile_check(int n_views, const double *in, long long *out) {
-    int W, H, c, cs;
-    if (n_views < 1) return fail(-2, "unit op 21: count is the number of views (got %d)", n_views);
-    if (int rc = unit_frame(in, &W, &H)) return rc;
-    if (!slot_int(in[2], 0, 0x7fffffff, &c) || !slot_int(in[3], 1, 0x7fffffff, &cs)) return fail(-2, "unit op 21: checkpoint %g, chunk_spp %g", in[2], in[3]);
-    const double tol = in[4], floor = in[5];
-    if (!std::isfinite(tol) || !(tol > 0.0) || !std::isfinite(floor) || floor < 0.0) return fail(-2, "unit op 21: tolerance %g, dark_floor %g", tol, floor);
-    if (in[6] != 0.0 || in[7] != 0.0) return fail(-2, "unit op 21: header slots 6 and 7 must be 0");
-    const long long n_tiles = tiles_of(W, H), n_words = (long long)W * H * 8, stride = n_tiles + n_words, n_all = (long long)n_views * n_tiles;
-    if (8 + (long long)n_views * stride > RTW_ACCUM_UNIT_SLOTS) return fail(-2, "unit op 21: %d views of %d x %d exceed %lld slots", n_views, W, H, RTW_ACCUM_UNIT_SLOTS);
-    std::vector<int32_t> chunks, one;
-    for (int v = 0; v < n_views; ++v) {
-        if (int rc = unit_chunks(in + 8 + (size_t)v * (size_t)stride, n_tiles, 0, &one)) return rc;
-        chunks.insert(chunks.end(), one.begin(), one.end());
-    }
-    DeviceGuard guard;
-    if (int rc = unit_device()) return rc;
-    const size_t words_b = (size_t)n_views * (size_t)n_words * 8u, tab_b = up16((size_t)n_views * sizeof(TileView)), ints_b = (size_t)n_all * sizeof(int32_t);
-    DevBuf buf;
-    HIP_TRY(hipMalloc(&buf.p, words_b + tab_b + 3u * ints_b));
-    unsigned long long *d_words = static_cast<unsigned long long *>(buf.p);
-    TileView *d_views = reinterpret_cast<TileView *>(static_cast<char *>(buf.p) + words_b);
-    int32_t *d_chunks = reinterpret_cast<int32_t *>(static_cast<char *>(buf.p) + words_b + tab_b), *d_flags = d_chunks + n_all;
-    std::vector<TileView> h_views((size_t)n_views);
-    for (int v = 0; v < n_views; ++v) {
-        HIP_TRY(hipMemcpy(d_words + (size_t)v * (size_t)n_words, in + 8 + (size_t)v * (size_t)stride + (size_t)n_tiles, (size_t)n_words * 8u, hipMemcpyHostToDevice));
-        h_views[(size_t)v] = TileView{d_words + (size_t)v * (size_t)n_words, d_chunks + (size_t)v * (size_t)n_tiles};
-    }
-    HIP_TRY(hipMemcpy(d_views, h_views.data(), (size_t)n_views * sizeof(TileView), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_chunks, chunks.data(), ints_b, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_flags, 0xff, 2u * ints_b));                  // (a flag nobody wrote reads -1)
-    (void)hipGetLastError();
-    for (int v = 0; v < n_views; ++v) launch_tile_check(nullptr, h_views[(size_t)v].words, h_views[(size_t)v].chunks, d_flags + (size_t)v * (size_t)n_tiles, W, H, c, cs, tol, floor);
-    launch_tile_check_batch(nullptr, d_views, d_flags + n_all, n_views, W, H, c, cs, tol, floor);
-    HIP_TRY(hipGetLastError());
-    std::vector<int32_t> h((size_t)n_all * 2u);
-    HIP_TRY(hipMemcpy(h.data(), d_flags, 2u * ints_b, hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < h.size(); ++k) out[k] = h[k];
-    return 0;
-}
-
-// op 22: in = n slots whose low 32 bits are the flags; out (raw int64) = count, list[n] of accum_tile_compact_kernel | the same of count /
-// scan / scatter.  Both lists are prefilled with -1: the slots behind the count read -1.
-int unit_compact(int n, const unsigned long long *in, long long *out) {
-    if (n < 1 || n > RTW_ACCUM_UNIT_SLOTS) return fail(-2, "unit op 22: count is the number of flags, 1 .. %lld (got %d)", RTW_ACCUM_UNIT_SLOTS, n);
-    std::vector<int32_t> flags((size_t)n);
-    for (int k = 0; k < n; ++k) flags[(size_t)k] = (int32_t)(uint32_t)in[k];
-    DeviceGuard guard;
-    if (int rc = unit_device()) return rc;
-    const int n_blocks = compact_blocks(n);
-    const size_t res = (size_t)n + 4u;                               // one result: list | count (+ 3 unused)
-    DevBuf buf;
-    HIP_TRY(hipMalloc(&buf.p, ((size_t)n + 2u * res + (size_t)n_blocks) * sizeof(int32_t)));
-    int32_t *d_flags = static_cast<int32_t *>(buf.p), *d_res = d_flags + n, *d_blocks = d_res + 2u * res;
-    HIP_TRY(hipMemcpy(d_flags, flags.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d_res, 0xff, 2u * res * sizeof(int32_t)));
-    (void)hipGetLastError();
-    launch_compact_loop(nullptr, d_flags, d_res, d_res + n, n);
-    launch_compact_blocks(nullptr, d_flags, d_blocks, d_res + res, d_res + res + n, n);
-    HIP_TRY(hipGetLastError());
-    std::vector<int32_t> h(2u * res);
-    HIP_TRY(hipMemcpy(h.data(), d_res, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (int r = 0; r < 2; ++r) {
-        long long *o = out + (size_t)r * ((size_t)n + 1u);
-        const int32_t *s = h.data() + (size_t)r * res;
-        o[0] = s[n];
-        for (int k = 0; k < n; ++k) o[1 + k] = s[k];
-    }
-    return 0;
-}
-
-// op 23: in = width, height, spp, chunk_spp, gamma, 0, 0, 0 | n_tiles x C_t | W * H * 8 raw words; out = the W * H * 3 values of
-// accum_resolve_tiles_kernel<T>, each widened to binary64
-template <typename T>
-int unit_resolve_tiles(int count, const double *in, double *out) {
-    int W, H, spp, cs, gamma;
-    if (count != 1) return fail(-2, "unit op 23: count must be 1 (got %d)", count);
-    if (int rc = unit_frame(in, &W, &H)) return rc;
-    if (!slot_int(in[2], 1, 0x7fffffff, &spp) || !slot_int(in[3], 1, 0x7fffffff, &cs) || !slot_int(in[4], 0, 1, &gamma))
-        return fail(-2, "unit op 23: spp %g, chunk_spp %g, gamma %g", in[2], in[3], in[4]);
-    if (in[5] != 0.0 || in[6] != 0.0 || in[7] != 0.0) return fail(-2, "unit op 23: header slots 5 to 7 must be 0");
-    const long long n_tiles = tiles_of(W, H), n_words = (long long)W * H * 8;
-    std::vector<int32_t> chunks;
-    if (int rc = unit_chunks(in + 8, n_tiles, 1, &chunks)) return rc;
-    DeviceGuard guard;
-    if (int rc = unit_device()) return rc;
-    const size_t n_out = (size_t)W * (size_t)H * 3u, words_b = (size_t)n_words * 8u, out_b = up16(n_out * sizeof(T));
-    DevBuf buf;
-    HIP_TRY(hipMalloc(&buf.p, words_b + out_b + (size_t)n_tiles * sizeof(int32_t)));
-    unsigned long long *d_words = static_cast<unsigned long long *>(buf.p);
-    T *d_out = reinterpret_cast<T *>(static_cast<char *>(buf.p) + words_b);
-    int32_t *d_chunks = reinterpret_cast<int32_t *>(static_cast<char *>(buf.p) + words_b + out_b);
-    HIP_TRY(hipMemcpy(d_words, in + 8 + (size_t)n_tiles, words_b, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_chunks, chunks.data(), (size_t)n_tiles * sizeof(int32_t), hipMemcpyHostToDevice));
-    (void)hipGetLastError();
-    launch_resolve_tiles<T>(nullptr, d_words, d_out, d_chunks, W, H, spp, cs, gamma);
-    HIP_TRY(hipGetLastError());
-    std::vector<T> h(n_out);
-    HIP_TRY(hipMemcpy(h.data(), d_out, n_out * sizeof(T), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < n_out; ++k) out[k] = (double)h[k];
-    return 0;
-}
-
-// op 25: in = width, height, spp, chunk_spp, dark_floor, 0, 0, 0 | n_tiles x C_t | W * H * 8 raw words; out = the W * H values of
-// accum_noise_kernel<T>, each widened to binary64
-template <typename T>
-int unit_noise(int count, const double *in, double *out) {
-    int W, H, spp, cs;
-    if (count != 1) return fail(-2, "unit op 25: count must be 1 (got %d)", count);
-    if (int rc = unit_frame(in, &W, &H)) return rc;
-    if (!slot_int(in[2], 1, 0x7fffffff, &spp) || !slot_int(in[3], 1, 0x7fffffff, &cs)) return fail(-2, "unit op 25: spp %g, chunk_spp %g", in[2], in[3]);
-    const double floor = in[4];
-    if (!std::isfinite(floor) || floor < 0.0) return fail(-2, "unit op 25: dark_floor %g", floor);
-    if (in[5] != 0.0 || in[6] != 0.0 || in[7] != 0.0) return fail(-2, "unit op 25: header slots 5 to 7 must be 0");
-    const long long n_tiles = tiles_of(W, H), n_words = (long long)W * H * 8;
-    std::vector<int32_t> chunks;
-    if (int rc = unit_chunks(in + 8, n_tiles, 1, &chunks)) return rc;
-    DeviceGuard guard;
-    if (int rc = unit_device()) return rc;
-    const size_t n_out = (size_t)W * (size_t)H, words_b = (size_t)n_words * 8u, out_b = up16(n_out * sizeof(T));
-    DevBuf buf;
-    HIP_TRY(hipMalloc(&buf.p, words_b + out_b + (size_t)n_tiles * sizeof(int32_t)));
-    unsigned long long *d_words = static_cast<unsigned long long *>(buf.p);
-    T *d_out = reinterpret_cast<T *>(static_cast<char *>(buf.p) + words_b);
-    int32_t *d_chunks = reinterpret_cast<int32_t *>(static_cast<char *>(buf.p) + words_b + out_b);
-    HIP_TRY(hipMemcpy(d_words, in + 8 + (size_t)n_tiles, words_b, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_chunks, chunks.data(), (size_t)n_tiles * sizeof(int32_t), hipMemcpyHostToDevice));
-    (void)hipGetLastError();
-    launch_noise<T>(nullptr, d_words, d_out, d_chunks, W, H, spp, cs, floor);
-    HIP_TRY(hipGetLastError());
-    std::vector<T> h(n_out);
-    HIP_TRY(hipMemcpy(h.data(), d_out, n_out * sizeof(T), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < n_out; ++k) out[k] = (double)h[k];
-    return 0;
-}
-
-// ops 30 / 31: the batched per-tile resolve / the batched noise map.  count = n_views.  in = the header of op 23 / op 25 (width, height, spp,
-// chunk_spp, gamma / dark_floor, 0, 0, 0) | per view: n_tiles x C_t >= 1, W * H * 8 raw words.  With E = W * H * 3 (30) or W * H (31): out = per
-// view the E values of the single kernel (accum_resolve_tiles_kernel / accum_noise_kernel), launched view by view | the n_views * E values of ONE
-// launch of the batch kernel; each of type T, widened.  An element nobody wrote reads -7.
-template <typename T>
-int unit_read_batch(int op, int n_views, const double *in, double *out) {
-    const bool noise = op == 31;
-    int W, H, spp, cs, gamma = 0;
-    if (n_views < 1) return fail(-2, "unit op %d: count is the number of views (got %d)", op, n_views);
-    if (int rc = unit_frame(in, &W, &H)) return rc;
-    if (!slot_int(in[2], 1, 0x7fffffff, &spp) || !slot_int(in[3], 1, 0x7fffffff, &cs)) return fail(-2, "unit op %d: spp %g, chunk_spp %g", op, in[2], in[3]);
-    const double floor = in[4];
-    if (noise ? (!std::isfinite(floor) || floor < 0.0) : !slot_int(in[4], 0, 1, &gamma)) return fail(-2, "unit op %d: %s %g", op, noise ? "dark_floor" : "gamma", in[4]);
-    if (in[5] != 0.0 || in[6] != 0.0 || in[7] != 0.0) return fail(-2, "unit op %d: header slots 5 to 7 must be 0", op);
-    const long long n_tiles = tiles_of(W, H), n_words = (long long)W * H * 8, stride = n_tiles + n_words, n_all = (long long)n_views * n_tiles;
-    if (8 + (long long)n_views * stride > RTW_ACCUM_UNIT_SLOTS) return fail(-2, "unit op %d: %d views of %d x %d exceed %lld slots", op, n_views, W, H, RTW_ACCUM_UNIT_SLOTS);
-    std::vector<int32_t> chunks, one;
-    for (int v = 0; v < n_views; ++v) {
-        if (int rc = unit_chunks(in + 8 + (size_t)v * (size_t)stride, n_tiles, 1, &one)) return rc;
-        chunks.insert(chunks.end(), one.begin(), one.end());
-    }
-    DeviceGuard guard;
-    if (int rc = unit_device()) return rc;
-    const size_t per = (size_t)W * (size_t)H * (noise ? 1u : 3u), n_out = 2u * (size_t)n_views * per;
-    const size_t words_b = (size_t)n_views * (size_t)n_words * 8u, tab_b = up16((size_t)n_views * sizeof(ReadView)), out_b = up16(n_out * sizeof(T));
-    DevBuf buf;
-    HIP_TRY(hipMalloc(&buf.p, words_b + tab_b + out_b + (size_t)n_all * sizeof(int32_t)));
-    unsigned long long *d_words = static_cast<unsigned long long *>(buf.p);
-    ReadView *d_views = reinterpret_cast<ReadView *>(static_cast<char *>(buf.p) + words_b);
-    T *d_out = reinterpret_cast<T *>(static_cast<char *>(buf.p) + words_b + tab_b);
-    int32_t *d_chunks = reinterpret_cast<int32_t *>(static_cast<char *>(buf.p) + words_b + tab_b + out_b);
-    std::vector<ReadView> h_views((size_t)n_views);
-    for (int v = 0; v < n_views; ++v) {
-        HIP_TRY(hipMemcpy(d_words + (size_t)v * (size_t)n_words, in + 8 + (size_t)v * (size_t)stride + (size_t)n_tiles, (size_t)n_words * 8u, hipMemcpyHostToDevice));
-        h_views[(size_t)v] = ReadView{d_words + (size_t)v * (size_t)n_words, d_chunks + (size_t)v * (size_t)n_tiles, 0, spp, cs, 0};
-    }
-    std::vector<T> h(n_out, (T)-7);
-    HIP_TRY(hipMemcpy(d_views, h_views.data(), (size_t)n_views * sizeof(ReadView), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_chunks, chunks.data(), (size_t)n_all * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_out, h.data(), n_out * sizeof(T), hipMemcpyHostToDevice));
-    (void)hipGetLastError();
-    for (int v = 0; v < n_views; ++v) {
-        const ReadView &V = h_views[(size_t)v];
-        if (noise) launch_noise<T>(nullptr, V.words, d_out + (size_t)v * per, V.chunks, W, H, spp, cs, floor);
-        else launch_resolve_tiles<T>(nullptr, V.words, d_out + (size_t)v * per, V.chunks, W, H, spp, cs, gamma);
-    }
-    if (noise) launch_noise_batch<T>(nullptr, d_views, d_out + (size_t)n_views * per, n_views, W, H, spp, cs, floor);
-    else launch_resolve_batch<T>(nullptr, d_views, d_out + (size_t)n_views * per, n_views, W, H, gamma);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(h.data(), d_out, n_out * sizeof(T), hipMemcpyDeviceToHost));
-    for (size_t k = 0; k < n_out; ++k) out[k] = (double)h[k];
-    return 0;
-}
-
 // ---- an accumulator as the denoiser's input (include/rtw_hip.h rtw_accum_features_*, rtw_accum_noise_*): everything here READS the words and
 // C_t; the calls wait for the accumulator's event and record it afterwards, so a later pass cannot overwrite them under a running kernel ----
 // an adaptive accumulator whose last call finished: C_t on the device is what the host copy says
@@ -1111,6 +514,8 @@ int check_adaptive_complete(const rtw_accum *a) {
         return fail(-2, "the accumulator's last adaptive call did not finish: its tiles' chunk counts are not settled");
     return 0;
 }
+}  // namespace
+// (validate_ / enqueue_accum_features: declared in rtw_host.hpp, rtw_accum_filtered_* runs them too)
 template <typename CamT>
 int validate_accum_features(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, rtw_accum_handle a) {
     if (!p) return fail(-1, "null params");
@@ -1136,6 +541,11 @@ int enqueue_accum_features(rtw_scene_handle scene, const CamT *cam, const rtw_pa
     if (rc) return rc;
     return mark(a, stream);
 }
+template int validate_accum_features(rtw_scene_handle, const rtw_camera_f32 *, const rtw_params *, rtw_accum_handle);
+template int validate_accum_features(rtw_scene_handle, const rtw_camera_f64 *, const rtw_params *, rtw_accum_handle);
+template int enqueue_accum_features(rtw_scene_handle, const rtw_camera_f32 *, const rtw_params *, rtw_accum_handle, void *, hipStream_t, RenderRec **, CtxPtr *);
+template int enqueue_accum_features(rtw_scene_handle, const rtw_camera_f64 *, const rtw_params *, rtw_accum_handle, void *, hipStream_t, RenderRec **, CtxPtr *);
+namespace {
 template <typename CamT>
 int accum_features(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, rtw_accum_handle a, void *d_out, void *stream_v) {
     // (nulls, the render's own checks and the buffer before a handle is looked at, like the device form of the feature pass)
@@ -1251,6 +661,7 @@ int resolve_batch(const rtw_accum_handle *accums, int32_t n_views, int32_t gamma
     return resolve_batch_dev<T>(accums, n_views, gamma, d_out, (hipStream_t)stream_v);
 }
 
+}  // namespace
 // rtw_accum_features_batch_*: the handles of a batched feature pass, after the checks that look at no handle -- every view as
 // rtw_accum_features_* validates it (with its own camera and seed), then the batch's rule: all adaptive, or all uniform with ONE interval
 template <typename CamT>
@@ -1285,6 +696,11 @@ int enqueue_accum_features_batch(rtw_scene_handle scene, const CamT *cams, int32
     if (rc) return rc;
     return mark_all(accums, n_views, stream);
 }
+template int validate_accum_features_batch(rtw_scene_handle, const rtw_camera_f32 *, int32_t, const uint64_t *, const rtw_params *, const rtw_accum_handle *);
+template int validate_accum_features_batch(rtw_scene_handle, const rtw_camera_f64 *, int32_t, const uint64_t *, const rtw_params *, const rtw_accum_handle *);
+template int enqueue_accum_features_batch(rtw_scene_handle, const rtw_camera_f32 *, int32_t, const uint64_t *, const rtw_params *, const rtw_accum_handle *, void *, hipStream_t, RenderRec **, CtxPtr *);
+template int enqueue_accum_features_batch(rtw_scene_handle, const rtw_camera_f64 *, int32_t, const uint64_t *, const rtw_params *, const rtw_accum_handle *, void *, hipStream_t, RenderRec **, CtxPtr *);
+namespace {
 template <typename CamT>
 int accum_features_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums, void *d_out, void *stream_v) {
     if (!p) return fail(-1, "null params");
@@ -1312,14 +728,6 @@ int validate_accum_array(const rtw_accum_handle *accums, int32_t n_views) {
     for (int32_t v = 0; v < n_views; ++v) if (!accums[v]) return fail(-1, "null accumulator (view %d)", v);
     return 0;
 }
-int validate_accum_features_f32(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, rtw_accum_handle a) { return validate_accum_features(s, c, p, a); }
-int validate_accum_features_f64(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, rtw_accum_handle a) { return validate_accum_features(s, c, p, a); }
-int enqueue_accum_features_f32(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, rtw_accum_handle a, void *d_out, hipStream_t st, RenderRec **rec, CtxPtr *ctx) {
-    return enqueue_accum_features(s, c, p, a, d_out, st, rec, ctx);
-}
-int enqueue_accum_features_f64(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, rtw_accum_handle a, void *d_out, hipStream_t st, RenderRec **rec, CtxPtr *ctx) {
-    return enqueue_accum_features(s, c, p, a, d_out, st, rec, ctx);
-}
 int accum_device_of(rtw_accum_handle a) { return a->device; }
 bool accum_is_adaptive(rtw_accum_handle a) { return a->adaptive; }
 int validate_accum_noise(rtw_accum_handle a, bool f64) {
@@ -1342,20 +750,6 @@ int enqueue_accum_resolve(rtw_accum_handle a, bool f64, int32_t gamma, void *d_o
     return f64 ? resolve_dev<double>(a, gamma, d_out, stream) : resolve_dev<float>(a, gamma, d_out, stream);
 }
 // the batched forms (rtw_accum_filtered_batch_* strings them together as the single call strings the ones above)
-int validate_accum_features_batch_f32(rtw_scene_handle s, const rtw_camera_f32 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a) {
-    return validate_accum_features_batch(s, c, n, sd, p, a);
-}
-int validate_accum_features_batch_f64(rtw_scene_handle s, const rtw_camera_f64 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a) {
-    return validate_accum_features_batch(s, c, n, sd, p, a);
-}
-int enqueue_accum_features_batch_f32(rtw_scene_handle s, const rtw_camera_f32 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a, void *d_out, hipStream_t st,
-                                     RenderRec **rec, CtxPtr *ctx) {
-    return enqueue_accum_features_batch(s, c, n, sd, p, a, d_out, st, rec, ctx);
-}
-int enqueue_accum_features_batch_f64(rtw_scene_handle s, const rtw_camera_f64 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a, void *d_out, hipStream_t st,
-                                     RenderRec **rec, CtxPtr *ctx) {
-    return enqueue_accum_features_batch(s, c, n, sd, p, a, d_out, st, rec, ctx);
-}
 // every view as rtw_accum_noise_* validates it; one frame size and device; ONE spp, chunk size and dark_floor -- the kernel takes one set
 int validate_accum_noise_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64) {
     if (int rc = validate_distinct(n_views, accums)) return rc;
@@ -1386,22 +780,6 @@ int enqueue_accum_noise_batch(const rtw_accum_handle *accums, int32_t n_views, b
 int validate_accum_resolve_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64) { return validate_resolve_batch(accums, n_views, f64); }
 int enqueue_accum_resolve_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64, int32_t gamma, void *d_out, hipStream_t stream) {
     return f64 ? resolve_batch_dev<double>(accums, n_views, gamma, d_out, stream) : resolve_batch_dev<float>(accums, n_views, gamma, d_out, stream);
-}
-
-int accum_unit(int op, bool f64, int count, const void *in, void *out) {
-    if (!in || !out) return fail(-1, "null argument");
-    if (op != 23 && op != 25 && op != 30 && op != 31 && !f64) return fail(-2, "unit op %d is an op of rtw_unit_f64", op);
-    switch (op) {
-        case 21: return unit_tile_check(count, static_cast<const double *>(in), static_cast<long long *>(out));
-        case 22: return unit_compact(count, static_cast<const unsigned long long *>(in), static_cast<long long *>(out));
-        case 23: return f64 ? unit_resolve_tiles<double>(count, static_cast<const double *>(in), static_cast<double *>(out))
-                            : unit_resolve_tiles<float>(count, static_cast<const double *>(in), static_cast<double *>(out));
-        case 25: return f64 ? unit_noise<double>(count, static_cast<const double *>(in), static_cast<double *>(out))
-                            : unit_noise<float>(count, static_cast<const double *>(in), static_cast<double *>(out));
-        case 30: case 31: return f64 ? unit_read_batch<double>(op, count, static_cast<const double *>(in), static_cast<double *>(out))
-                                     : unit_read_batch<float>(op, count, static_cast<const double *>(in), static_cast<double *>(out));
-    }
-    return fail(-2, "unknown unit op %d", op);
 }
 
 }  // namespace rtwh
@@ -1567,10 +945,8 @@ int rtw_accum_merge(rtw_accum_handle dst, rtw_accum_handle src, void *stream_v) 
     HIP_TRY(hipSetDevice(dst->device));
     if (int rc = wait_for(dst, stream)) return rc;
     if (int rc = wait_for(src, stream)) return rc;
-    const size_t n = n_pixels(dst) * 4u;
     (void)hipGetLastError();
-    hipLaunchKernelGGL(accum_merge_kernel, dim3((unsigned)((n + 255u) / 256u)), dim3(256), 0, stream, reinterpret_cast<ulonglong2 *>(dst->words),
-                       reinterpret_cast<const ulonglong2 *>(src->words), n);
+    launch_merge(stream, dst->words, src->words, n_pixels(dst));
     HIP_TRY(hipGetLastError());
     dst->bind = src->bind; dst->bound = true;
     for (auto &r : src->ranges) add_range(dst->ranges, r.first, r.second);

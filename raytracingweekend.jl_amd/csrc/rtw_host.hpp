@@ -8,7 +8,8 @@
 //   rtw_multi.hip        what a device list needs: peer access, the on-demand RCCL binding, the un-tile kernel
 //   rtw_batch_accum_f32.hip / _f64.hip  the BATCH && ACCUM instances of the trace kernel (rtw_instances.hpp: the kernel-instance table), a unit per precision
 //   rtw_features_accum_batch_f32.hip / _f64.hip  the TILED && BATCH instances of the feature kernel (rtw_features.hpp), a unit per precision
-//   rtw_accum.hip        progressive render: the accumulator object, its passes, merge / resolve kernels, export / import
+//   rtw_accum.hip        progressive and adaptive render: the accumulator object (rtw_accum.hpp), its passes, the adaptive loop, the read-only passes, export / import
+//   rtw_accum_kernels.hip  the accumulator's kernels (merge, resolve, tile check / compaction, noise map; single and batched), their launches and the unit ops on them
 //   rtw_unit.hip         the T0 unit entry points (rtw_units.hpp)
 //   rtw_features.hip     first-hit feature buffers: one launch of the feature kernel (rtw_features.hpp) for one view or a batch of views, the device-resident entry points
 //   rtw_denoise.hip      the feature-guided denoiser: its checks, the launch sequence of its kernels (rtw_denoise.hpp) for one frame or a batch of frames, the device-resident entry points
@@ -267,20 +268,15 @@ int rccl_reduce_frames(RcclSet &set, const std::vector<const void *> &send, void
 void rccl_shutdown();
 int launch_untile(bool f64, const void *gather, void *frame, int W, int H, long n_tiles, int n_shards, long pad_tiles, hipStream_t stream);
 
-// rtw_accum.hip: the unit ops 21-23 (include/rtw_hip.h rtw_unit_f64): the tile check, the compactions and the per-tile resolve on the
-// caller's words, through the launch helpers the adaptive loop itself uses
+// rtw_accum_kernels.hip: the unit ops 21-23, 25, 30, 31 (include/rtw_hip.h rtw_unit_f32 / _f64): the accumulator's kernels on the caller's
+// words, through the launches the host paths themselves use
 int accum_unit(int op, bool f64, int count, const void *in, void *out);
 // rtw_accum.hip: an accumulator as the denoiser's input -- what rtw_accum_features_* / rtw_accum_noise_* run and what rtw_accum_filtered_*
 // (rtw_render_host.hip) strings together.  validate_*: every refusal, before any HIP call; enqueue_*: wait for the accumulator's event,
 // launch on `stream`, record the event (everything reads the words and C_t only).
-int validate_accum_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, rtw_accum_handle a);
-int validate_accum_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, rtw_accum_handle a);
-int enqueue_accum_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, rtw_accum_handle a, void *d_out, hipStream_t stream, RenderRec **rec, CtxPtr *ctx);
-int enqueue_accum_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, rtw_accum_handle a, void *d_out, hipStream_t stream, RenderRec **rec, CtxPtr *ctx);
-inline int validate_accum_features_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, rtw_accum_handle a) { return validate_accum_features_f32(s, c, p, a); }
-inline int validate_accum_features_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, rtw_accum_handle a) { return validate_accum_features_f64(s, c, p, a); }
-inline int enqueue_accum_features_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, rtw_accum_handle a, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return enqueue_accum_features_f32(s, c, p, a, d, st, r, x); }
-inline int enqueue_accum_features_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, rtw_accum_handle a, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return enqueue_accum_features_f64(s, c, p, a, d, st, r, x); }
+// (the templates on CamT: rtw_camera_f32 or rtw_camera_f64, instantiated for both in rtw_accum.hip)
+template <typename CamT> int validate_accum_features(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, rtw_accum_handle a);
+template <typename CamT> int enqueue_accum_features(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, rtw_accum_handle a, void *d_out, hipStream_t stream, RenderRec **rec, CtxPtr *ctx);
 int accum_device_of(rtw_accum_handle a);
 bool accum_is_adaptive(rtw_accum_handle a);
 int validate_accum_noise(rtw_accum_handle a, bool f64);                                             // adaptive, its last call finished, the call's precision
@@ -292,14 +288,8 @@ int enqueue_accum_resolve(rtw_accum_handle a, bool f64, int32_t gamma, void *d_o
 // the batch's own rules), before any HIP call; enqueue_*: wait for EVERY accumulator's
 // event, launch on `stream`, record every event.  Frames lie view-major behind d_out.
 int validate_accum_array(const rtw_accum_handle *accums, int32_t n_views);
-int validate_accum_features_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums);
-int validate_accum_features_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums);
-int enqueue_accum_features_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums, void *d_out, hipStream_t stream, RenderRec **rec, CtxPtr *ctx);
-int enqueue_accum_features_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums, void *d_out, hipStream_t stream, RenderRec **rec, CtxPtr *ctx);
-inline int validate_accum_features_batch_t(rtw_scene_handle s, const rtw_camera_f32 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a) { return validate_accum_features_batch_f32(s, c, n, sd, p, a); }
-inline int validate_accum_features_batch_t(rtw_scene_handle s, const rtw_camera_f64 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a) { return validate_accum_features_batch_f64(s, c, n, sd, p, a); }
-inline int enqueue_accum_features_batch_t(rtw_scene_handle s, const rtw_camera_f32 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return enqueue_accum_features_batch_f32(s, c, n, sd, p, a, d, st, r, x); }
-inline int enqueue_accum_features_batch_t(rtw_scene_handle s, const rtw_camera_f64 *c, int32_t n, const uint64_t *sd, const rtw_params *p, const rtw_accum_handle *a, void *d, hipStream_t st, RenderRec **r, CtxPtr *x) { return enqueue_accum_features_batch_f64(s, c, n, sd, p, a, d, st, r, x); }
+template <typename CamT> int validate_accum_features_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums);
+template <typename CamT> int enqueue_accum_features_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_accum_handle *accums, void *d_out, hipStream_t stream, RenderRec **rec, CtxPtr *ctx);
 int validate_accum_noise_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64);
 int enqueue_accum_noise_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64, void *d_out, hipStream_t stream);
 int validate_accum_resolve_batch(const rtw_accum_handle *accums, int32_t n_views, bool f64);

@@ -430,7 +430,7 @@ int accum_filtered_host(rtw_scene_handle scene, const CamT *cams, int32_t n_view
     int nch, cs;                                                   // (the render's and the filter's own checks before a handle is looked at)
     if (int rc = n_views ? validate_features_batch(cams, n_views, p, 0, 1, out, &nch, &cs) : validate_features(p, 0, 1, &nch, &cs)) return rc;
     if (int rc = n_views ? validate_filter_batch(d, p->width, p->height, n_views) : validate_denoise(d, p->width, p->height)) return rc;
-    if (int rc = n_views ? validate_accum_features_batch_t(scene, cams, n_views, seeds, p, accums) : validate_accum_features_t(scene, cams, p, accums[0])) return rc;
+    if (int rc = n_views ? validate_accum_features_batch(scene, cams, n_views, seeds, p, accums) : validate_accum_features(scene, cams, p, accums[0])) return rc;
     if (n_views) if (int rc = validate_accum_resolve_batch(accums, n_views, f64)) return rc;
     if (guided) if (int rc = n_views ? validate_accum_noise_batch(accums, n_views, f64) : validate_accum_noise(accums[0], f64)) return rc;
     DeviceGuard guard;
@@ -449,11 +449,11 @@ int accum_filtered_host(rtw_scene_handle scene, const CamT *cams, int32_t n_view
     int rc;
     if (n_views) {
         rc = enqueue_accum_resolve_batch(accums, n_views, f64, 0, base, hc->stream);
-        if (!rc) rc = enqueue_accum_features_batch_t(scene, cams, n_views, seeds, p, accums, base + R.off_feat, hc->stream, &frec, &fctx);
+        if (!rc) rc = enqueue_accum_features_batch(scene, cams, n_views, seeds, p, accums, base + R.off_feat, hc->stream, &frec, &fctx);
         if (!rc && guided) rc = enqueue_accum_noise_batch(accums, n_views, f64, base + off_noise, hc->stream);
     } else {
         rc = enqueue_accum_resolve(accums[0], f64, 0, base, hc->stream);
-        if (!rc) rc = enqueue_accum_features_t(scene, cams, p, accums[0], base + R.off_feat, hc->stream, &frec, &fctx);
+        if (!rc) rc = enqueue_accum_features(scene, cams, p, accums[0], base + R.off_feat, hc->stream, &frec, &fctx);
         if (!rc && guided) rc = enqueue_accum_noise(accums[0], f64, base + off_noise, hc->stream);
     }
     if (!rc) rc = R.launch(&dd, p->width, p->height, n_views, base, hc->stream, guided ? base + off_noise : nullptr);

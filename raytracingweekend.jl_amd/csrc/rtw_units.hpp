@@ -19,11 +19,11 @@ enum UnitOp {
     U_EXACT_MATH = 16,       // t_sqrt / t_rcp against the compiler's IEEE sqrt / division on a RANGE of binary32 bit patterns (Float32 only)
     // pass-1 candidate sinks: the scans of ops 10, 11, 13, 14 with a CandSink -- per ray what pass 2 was handed instead of the hit (scenes of <= 512 spheres)
     U_SINK_LDS = 17, U_SINK_CULL = 18, U_SINK_MFMA = 19, U_SINK_MFMA_CULL = 20,
-    // the accumulator's tile kernels on hand-made words (rtw_accum.hip accum_unit; whole-call layouts, not per item: include/rtw_hip.h): the
+    // the accumulator's tile kernels on hand-made words (rtw_accum_kernels.hip accum_unit; whole-call layouts, not per item: include/rtw_hip.h): the
     // stopping rule's two check kernels, the two compactions, the per-tile resolve.  rtw_unit.hip hands them over before its per-item path.
     U_ACCUM_TILE_CHECK = 21, U_ACCUM_COMPACT = 22, U_ACCUM_RESOLVE_TILES = 23,
     // (24 is not an op: callers probe it as the first unknown number)
-    U_ACCUM_NOISE = 25,      // the noise map kernel of an adaptive accumulator on hand-made words and C_t (rtw_accum.hip accum_unit)
+    U_ACCUM_NOISE = 25,      // the noise map kernel of an adaptive accumulator on hand-made words and C_t (rtw_accum_kernels.hip accum_unit)
     // one bounce as the trace kernel composes it (rtw_kernels.hpp phases H2, R, F): hit_world, then make_hitrec, the DielConst of the uploaded cold
     // rows, scatter_begin(..., &dc), attenuation_of, the rejection loop, scatter_finish, the final normalize
     U_SHADE = 26,
@@ -34,7 +34,7 @@ enum UnitOp {
     // p beyond the layout), 1 if that position is in the in-lane list, the number of positions, the number of blocks
     U_CULL_LAYOUT = 28,
     // (29 is not an op either: the first number behind op 28 stays the unknown one callers probe)
-    // the batched per-tile resolve and the batched noise map on hand-made words and C_t, N views in ONE launch next to the single kernels view by view (rtw_accum.hip accum_unit)
+    // the batched per-tile resolve and the batched noise map on hand-made words and C_t, N views in ONE launch next to the single kernels view by view (rtw_accum_kernels.hip accum_unit)
     U_ACCUM_RESOLVE_BATCH = 30, U_ACCUM_NOISE_BATCH = 31,
     U_NUM_OPS = 32
 };

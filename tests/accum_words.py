@@ -1,4 +1,4 @@
-"""Exact reference for the arithmetic of accumulator words (raytracingweekend.jl_amd/csrc/rtw_accum.hip; include/rtw_hip.h "Progressive
+"""Exact reference for the arithmetic of accumulator words (raytracingweekend.jl_amd/csrc/rtw_accum_kernels.hip; include/rtw_hip.h "Progressive
 render", "Adaptive sampling"), in plain Python integers, Fractions and single binary64 operations.
 
 An accumulator is 8 uint64 per pixel: (lo, hi) of the signed 64.64 sum of R, G and B, the poison count (word 6) and the signed half
@@ -74,7 +74,7 @@ def from_device_order(flat, width, height, per_pixel):
     return np.asarray(flat).reshape(width, height, per_pixel).transpose(1, 0, 2)
 
 
-# ---- the export blob (rtw_accum.hip BlobHeader / AccumBind) -------------------------------------------------------------------------
+# ---- the export blob (rtw_accum.hip BlobHeader / rtw_accum.hpp AccumBind) -------------------------------------------------------------------------
 #   char magic[8]; uint32 version, header_bytes; int32 width, height, bound, n_ranges;                     32 bytes
 #   AccumBind: int32 is_f64, spp, chunk_spp, n_chunks, max_depth, numerics; uint64 seed, scene_hash;       40 bytes
 #              unsigned char cam[sizeof(rtw_camera_f64)] (22 doubles; Float32: the first half, the rest 0) 176 bytes

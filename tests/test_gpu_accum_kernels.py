@@ -1,4 +1,4 @@
-"""The tile kernels of the adaptive render on hand-made words (rtw_accum.hip: tile_not_converged behind accum_tile_check_kernel and
+"""The tile kernels of the adaptive render on hand-made words (rtw_accum_kernels.hip: tile_not_converged behind accum_tile_check_kernel and
 accum_tile_check_batch_kernel; accum_tile_compact_kernel and the count / scan / scatter trio; accum_resolve_tiles_kernel), through
 the unit ops 21-23 of rtw_unit_f64 -- adaptive accumulators can be neither exported nor imported, so these three have a seam.  The ops
 launch the product's kernels through the launch helpers of the adaptive loop itself: the same grids.

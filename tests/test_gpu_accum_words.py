@@ -1,4 +1,4 @@
-"""Resolve and merge on hand-made accumulator words (rtw_accum.hip accum_resolve_kernel, accum_merge_kernel, fx_to_double), reached with
+"""Resolve and merge on hand-made accumulator words (rtw_accum_kernels.hip accum_resolve_kernel, accum_merge_kernel, fx_to_double), reached with
 no seam at all: rtw_accum_import takes a blob without a checksum, so tests/accum_words.py writes the header, the ranges and any words it
 likes, and the imported accumulator is resolved, merged, read and exported like any other.  The words a render leaves are benign (small
 positive sums, no ties, no carries between the halves); these are not: every shift count of the normalisation, exact ties and their

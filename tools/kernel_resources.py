@@ -3,7 +3,7 @@
 usage: python tools/kernel_resources.py [--unit NAME.hip ...] [extra hipcc flags]   (cross-compiles for gfx950, no GPU needed)
 The instances live in rtw_launch.hip and, the BATCH && ACCUM ones, in rtw_batch_accum_f32.hip / _f64.hip: one table over all three.
 --unit names other translation units instead (rtw_features.hip: the instances of the feature kernel, the batched ones among them; rtw_features_accum_batch_f32.hip /
-_f64.hip: its tiled batched instances; rtw_denoise.hip: the denoiser's kernels and the batched level kernels; rtw_accum.hip: the accumulator's kernels, the noise map and the
+_f64.hip: its tiled batched instances; rtw_denoise.hip: the denoiser's kernels and the batched level kernels; rtw_accum_kernels.hip: the accumulator's kernels, the noise map and the
 batched resolve and noise map among them)."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
