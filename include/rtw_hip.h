@@ -667,6 +667,101 @@ int rtw_accum_filtered_batch_f32(rtw_scene_handle scene, const rtw_camera_f32 *c
 int rtw_accum_filtered_batch_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
                                  const rtw_denoise_t *d, const rtw_accum_handle *accums, int32_t guided, double *out);
 
+/* Feature-guided upsampler: a full-size image from a small render, guided by a full-size feature pass.  A feature pass traces one primary
+ * scan per pixel and chunk, a render about 2.7 segments per sample: a frame path-traced at half width (a quarter of the samples) takes
+ * its silhouettes, normals and albedo detail from the feature buffers of the full frame.
+ *
+ * The definition.  Everything is computed in the element type T (binary32 or binary64); every operation is rounded once, no FMA, no
+ * reassociation; quotients and the final sqrt are the correctly rounded IEEE ones; subnormals are kept, as in the denoiser.
+ *   Inputs.  The small frame is w x h: `image_lo` (h*w*3, normally a gamma = 0 image) and `features_lo` (h*w*8).  The full frame is W x H:
+ * `features_hi` (H*W*8); the result holds H*W*3 elements.  Layouts are those of the render and feature entry points: pixel (i, j) (0-based
+ * row, column) at j*rows + i.  1 <= w <= W and 1 <= h <= H.
+ *   Small frame.  It is prepared exactly as the denoiser above prepares a frame: valid(q), has(q), n_q, z_q, cov_q, a_q and e_q (with
+ * RTW_UPSAMPLE_DEMODULATE a = max(f, T(2^-6)) and e = c / a, otherwise a = 1 and e = c).  Then `levels` (0..8) passes of the denoiser's level
+ * definition run on e at the small size, with the steps 2^k and the same inv_sc(k) and inv_sz; no pass is a final one -- nothing is
+ * multiplied back and no gamma is applied.  With levels = 0, e is prepare's e.
+ *   Full-size pixel P = (i, j), its feature slots F[0..7].  valid(P): all eight are finite.  cov_P = F[7]; has(P) = valid(P) and cov_P > 0.
+ * If has(P): n_P = F[3..5] / cov_P and z_P = F[6] / cov_P, otherwise both are 0.  a_P[k] = max(F[k], T(2^-6)) with
+ * RTW_UPSAMPLE_DEMODULATE, else 1.
+ *   Position in the small frame (pixel centres coincide), in exact integers:  num_x = (2j + 3)*w - 3W;  x0 = floor(num_x / 2W);
+ * r_x = num_x - x0*2W, in [0, 2W);  fx = T(r_x) / T(2W) -- each conversion rounded to nearest even, one quotient.  Rows likewise: (i, h, H)
+ * give y0 and fy.  x0 lies in [-2, w-1], and every full-size pixel has a tap inside the small frame with a positive spatial weight
+ * (tests/test_upsample_ref.py checks both for every 1 <= w <= W <= 64): that is why w > W is refused.
+ *   Taps.  16 of them: the column offset b = -1..2 is the outer, the row offset a = -1..2 the inner loop; the tap is q = (y0 + a, x0 + b).
+ * kx = 1 - |T(b) - fx| * T(0.5), ky likewise with a and fy (each subtraction rounded once, the product by 0.5 exact, both >= 0); s = ky*kx.
+ * A tap outside the small frame, or whose q is not valid, is skipped.  Any other tap:
+ *       da[k] = a_P[k] - a_q[k];  dA = (da0*da0 + da1*da1) + da2*da2;  w_a = 1 / (1 + dA*inv_sa)
+ *       t_v = 1 - |cov_P - cov_q|;  w_v = t_v > 0 ? t_v : +0
+ *       w = (s*w_a)*w_v
+ *       if has(P) and has(q):
+ *           dot = (n_P.x*n_q.x + n_P.y*n_q.y) + n_P.z*n_q.z;  t = dot > 0 ? dot : +0, then t = t*t repeated m = normal_power_log2 times
+ *           zs = z_P + z_q;  r = (z_P - z_q) / (zs > 0 ? zs : 1);  w_z = 1 / (1 + (r*r)*inv_sz)
+ *           w = (w*t)*w_z
+ *       sum_w = sum_w + w;  sum_e[k] = sum_e[k] + w*e_q[k];  sum_s = sum_s + s;  sum_se[k] = sum_se[k] + s*e_q[k]
+ * All four sums start at +0.  inv_sa = T(1.0 / (sigma_albedo*sigma_albedo)), computed by the host in binary64.
+ *   End.  If sum_w > 0: e[k] = sum_e[k] / sum_w.  Otherwise, if sum_s > 0: e[k] = sum_se[k] / sum_s -- the purely spatial fallback: every
+ * guide rejected every tap.  Otherwise the pixel is not valid.  out[k] = e[k] * a_P[k] with RTW_UPSAMPLE_DEMODULATE, else e[k]; then sqrt per
+ * channel if gamma = 1.  A pixel that is not valid, or whose valid(P) is false, is a quiet NaN in all three channels.  Without
+ * RTW_UPSAMPLE_DEMODULATE a = 1 on both sides, so dA = 0 and w_a = 1 exactly: there is no special case.  (tests/upsample_ref.py restates all
+ * of this on the CPU and the device agrees on the bits.)
+ *
+ * The device forms are asynchronous on `hip_stream` of the device u->device (-1: the current one).  The caller owns `d_work`: the bytes the
+ * work-bytes call below returns for the SMALL frame (the denoiser's), times n_views for a batch, 16-byte aligned; no device workspace is
+ * shared, so any number of calls may be in flight with a workspace each.  Both feature buffers are 16-byte aligned, the images aligned
+ * to T; `d_out` aliases nothing, the workspace aliases no input.  Launches: prepare + `levels` + 1, for any number of views.
+ *   Batches are batch-major as rtw_filter_batch_device_* defines it: view v's planes follow view v-1's, each at its own frame size -- the
+ * small images at v*w*h*3 elements, the small features at v*w*h*8, the full features at v*W*H*8, the results at v*W*H*3; view v is, bit
+ * for bit, the single call on its frames.
+ *   The host forms are blocking, lease a cached context like rtw_denoise_f32 and copy the result back once.  Neither the host nor the device
+ * forms change what rtw_stats() reports.
+ *   The render-and-upsample call: let q = *p with the small width and height and gamma 0.  It renders q, runs the feature pass over all
+ * N_q effective chunks of q, runs the feature pass of `p` at full size over the chunks [0, hi_chunks) (hi_chunks = 0: all N_p), and
+ * upsamples with u->gamma replaced by p->gamma and u->device by p->device -- all on the cached context's stream, with one D2H of the
+ * full-size result: 5 + `levels` launches for any number of views.  rtw_stats() afterwards reports the small render's record.
+ *   Refusals, all decided before any HIP call: a null argument -> -1; levels outside 0..8, normal_power_log2 outside 0..7, unknown flag
+ * bits, gamma other than 0 or 1, device < -1, hi_chunks < 0, a sigma that is not finite and positive (sigma_color also with levels = 0),
+ * a width or height < 1, a small frame larger than the full one in either direction, misaligned or aliasing pointers, elem_bytes other
+ * than 4 or 8, n_views < 1 -> -2; hi_chunks beyond N_p -> -2; a full frame of 2^31 8x8 tiles or more, a batch of 2^39 full-size pixels
+ * or more -> -5; the render calls additionally refuse everything a feature render of `p` and of q refuses.  Out of scope (DESIGN.md
+ * section 9): accumulators as the input, a noise-guided form, device lists, an LDS-tiled kernel.  Additive to ABI 4: detected by symbol lookup. */
+#define RTW_UPSAMPLE_DEMODULATE 1  /* filter and interpolate image / albedo, multiply the full-size albedo back at the end */
+typedef struct {
+    int32_t levels;             /* 0..8 a-trous passes at the small size before the upsampling */
+    int32_t normal_power_log2;  /* 0..7: m, normal weight = max(0, n.n')^(2^m) */
+    int32_t flags;              /* RTW_UPSAMPLE_* */
+    int32_t gamma;              /* 1 = sqrt per channel at the end, 0 = linear */
+    int32_t device;             /* -1 = current */
+    int32_t hi_chunks;          /* render-and-upsample calls: chunks [0, hi_chunks) of the full-size feature pass; 0 = all N; >= 0 everywhere */
+    double  sigma_color;        /* the levels' colour sigma; > 0, finite (validated even with levels = 0) */
+    double  sigma_depth;        /* levels and taps; > 0, finite */
+    double  sigma_albedo;       /* taps; > 0, finite */
+} rtw_upsample_t;               /* 48 bytes */
+int64_t rtw_upsample_work_bytes(int32_t lo_width, int32_t lo_height, int32_t elem_bytes);
+int rtw_upsample_device_f32(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, const void *d_image_lo,
+                            const void *d_features_lo, const void *d_features_hi, void *d_out, void *d_work, void *hip_stream);
+int rtw_upsample_device_f64(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, const void *d_image_lo,
+                            const void *d_features_lo, const void *d_features_hi, void *d_out, void *d_work, void *hip_stream);
+int rtw_upsample_f32(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, const float *image_lo,
+                     const float *features_lo, const float *features_hi, float *out);
+int rtw_upsample_f64(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, const double *image_lo,
+                     const double *features_lo, const double *features_hi, double *out);
+int rtw_upsample_batch_device_f32(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views,
+                                  const void *d_images_lo, const void *d_features_lo, const void *d_features_hi, void *d_out, void *d_work, void *hip_stream);
+int rtw_upsample_batch_device_f64(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views,
+                                  const void *d_images_lo, const void *d_features_lo, const void *d_features_hi, void *d_out, void *d_work, void *hip_stream);
+int rtw_upsample_batch_f32(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views,
+                           const float *images_lo, const float *features_lo, const float *features_hi, float *out);
+int rtw_upsample_batch_f64(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views,
+                           const double *images_lo, const double *features_lo, const double *features_hi, double *out);
+int rtw_render_upsampled_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, int32_t lo_width, int32_t lo_height,
+                             const rtw_upsample_t *u, float *out);
+int rtw_render_upsampled_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t lo_width, int32_t lo_height,
+                             const rtw_upsample_t *u, double *out);
+int rtw_render_upsampled_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
+                                   int32_t lo_width, int32_t lo_height, const rtw_upsample_t *u, float *out);
+int rtw_render_upsampled_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
+                                   int32_t lo_width, int32_t lo_height, const rtw_upsample_t *u, double *out);
+
 /* Counters/timings of the last render issued from this thread (waits for it to finish). */
 int rtw_stats(rtw_stats_t *out);
 

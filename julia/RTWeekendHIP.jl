@@ -562,4 +562,60 @@ function render_denoised(scene::HittableList, cam::Camera{T}, image_width=400, n
     img
 end
 
+# rtw_upsample_t (include/rtw_hip.h): 48 bytes
+struct CUpsample
+    levels::Int32; normal_power_log2::Int32; flags::Int32; gamma::Int32; device::Int32; hi_chunks::Int32
+    sigma_color::Float64; sigma_depth::Float64; sigma_albedo::Float64
+end
+
+"""
+    render_upsampled(scene, cam, image_width=400, n_samples=1; lo_width=cld(image_width, 2), hi_chunks=0, depth=16, seed=1, n_chunks=0, device=-1,
+                     numerics=:reference, group_cull=false, scan_valu=false, levels=2, normal_power_log2=1, sigma_color=0.5, sigma_depth=0.1,
+                     sigma_albedo=0.2, demodulate=true)
+
+A full-size frame from a render at `lo_width` (rtw_render_upsampled_f32/_f64): the small linear image, its feature pass, the feature pass
+of the full frame over its first `hi_chunks` chunks (0: all) and the feature-guided upsampler (the definition is in include/rtw_hip.h) run
+on the device, gamma is applied at the end and the full-size `Matrix{RGB{T}}` comes back once.  The filter's defaults are untuned.
+(Not executed in this repository: there is no `julia` in its build image; tests/test_gpu_upsample.py drives the same entry point.)
+"""
+function render_upsampled(scene::HittableList, cam::Camera{T}, image_width=400, n_samples=1;
+                          lo_width=cld(image_width, 2), hi_chunks=0, depth=16, seed=1, n_chunks=0, device=-1, numerics=:reference,
+                          group_cull=false, scan_valu=false, levels=2, normal_power_log2=1, sigma_color=0.5, sigma_depth=0.1,
+                          sigma_albedo=0.2, demodulate=true) where T <: Union{Float32,Float64}
+    numerics in (:reference, :contract, :reference_fma2) || throw(ArgumentError("numerics must be :reference, :contract or :reference_fma2"))
+    nflags = numerics === :contract ? 32 : numerics === :reference_fma2 ? 128 : 0
+    image_height = image_width ÷ (16//9)
+    lo_height = lo_width ÷ (16//9)
+    n = length(scene)
+    cx = Vector{T}(undef, n); cy = similar(cx); cz = similar(cx); r = similar(cx)
+    ar = similar(cx); ag = similar(cx); ab = similar(cx); param = similar(cx)
+    kind = Vector{Int32}(undef, n)
+    for (i, h) in enumerate(scene)
+        h isa Sphere{T} || throw(ArgumentError("scene[$i] is $(typeof(h)); the HIP path takes Sphere{$T} only"))
+        cx[i], cy[i], cz[i] = h.center
+        r[i] = h.radius
+        kind[i] = matkind(h.mat)
+        ar[i], ag[i], ab[i] = albedo(h.mat)
+        param[i] = matparam(h.mat)
+    end
+    img = Matrix{RGB{T}}(undef, image_height, image_width)
+    ccam = Ref(CCamera(cam))
+    up = Ref(CUpsample(levels, normal_power_log2, demodulate ? 1 : 0, 1, -1, hi_chunks, sigma_color, sigma_depth, sigma_albedo))
+    rc = GC.@preserve cx cy cz r kind ar ag ab param img begin
+        params = Ref(CParams(image_width, image_height, n_samples, depth, seed, n_chunks, 0, 1, device, 1,
+                             (group_cull ? 1 : 0) | (scan_valu ? 4 : 0) | nflags, 0, 0, Ptr{Int32}(C_NULL)))
+        cscene = Ref(CScene{T}(n, pointer(cx), pointer(cy), pointer(cz), pointer(r), pointer(kind),
+                               pointer(ar), pointer(ag), pointer(ab), pointer(param)))
+        if T === Float32
+            ccall((:rtw_render_upsampled_f32, LIB), Cint, (Ref{CScene{Float32}}, Ref{CCamera{Float32}}, Ref{CParams}, Int32, Int32, Ref{CUpsample}, Ptr{Float32}),
+                  cscene, ccam, params, lo_width, lo_height, up, pointer(reinterpret(Float32, vec(img))))
+        else
+            ccall((:rtw_render_upsampled_f64, LIB), Cint, (Ref{CScene{Float64}}, Ref{CCamera{Float64}}, Ref{CParams}, Int32, Int32, Ref{CUpsample}, Ptr{Float64}),
+                  cscene, ccam, params, lo_width, lo_height, up, pointer(reinterpret(Float64, vec(img))))
+        end
+    end
+    rc == 0 || error("librtw_hip: error $rc: $(last_error())")
+    img
+end
+
 end # module

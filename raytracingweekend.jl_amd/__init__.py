@@ -31,6 +31,9 @@ from .denoise import (  # noqa: F401
     denoise, denoise_batch, denoise_batch_into, denoise_guided_batch_into, denoise_guided_into, denoise_into, denoise_work_bytes, render_denoised,
     render_denoised_batch,
 )
+from .upsample import (  # noqa: F401
+    make_upsample, render_upsampled, render_upsampled_batch, upsample, upsample_batch, upsample_batch_into, upsample_into, upsample_work_bytes,
+)
 from . import imageio  # noqa: F401
 
 __all__ = [
@@ -46,4 +49,6 @@ __all__ = [
     "denoise_guided_into", "render_adaptive_denoised",
     "render_features_batch", "features_batch_into", "denoise_batch", "denoise_batch_into", "render_denoised_batch",
     "denoise_guided_batch_into", "render_adaptive_denoised_batch",
+    "make_upsample", "upsample_work_bytes", "upsample", "upsample_into", "upsample_batch", "upsample_batch_into", "render_upsampled",
+    "render_upsampled_batch",
 ]

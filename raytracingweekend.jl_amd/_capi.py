@@ -29,6 +29,9 @@ SYMBOLS = [
     "rtw_accum_resolve_batch_f32", "rtw_accum_resolve_batch_f64", "rtw_accum_features_batch_f32", "rtw_accum_features_batch_f64",
     "rtw_accum_noise_batch_f32", "rtw_accum_noise_batch_f64", "rtw_guided_filter_batch_device_f32", "rtw_guided_filter_batch_device_f64",
     "rtw_accum_filtered_batch_f32", "rtw_accum_filtered_batch_f64",
+    "rtw_upsample_work_bytes", "rtw_upsample_device_f32", "rtw_upsample_device_f64", "rtw_upsample_f32", "rtw_upsample_f64",
+    "rtw_upsample_batch_device_f32", "rtw_upsample_batch_device_f64", "rtw_upsample_batch_f32", "rtw_upsample_batch_f64",
+    "rtw_render_upsampled_f32", "rtw_render_upsampled_f64", "rtw_render_upsampled_batch_f32", "rtw_render_upsampled_batch_f64",
 ]
 
 
@@ -84,6 +87,12 @@ class Denoise(C.Structure):
     """rtw_denoise_t"""
     _fields_ = [(k, C.c_int32) for k in ("levels", "normal_power_log2", "flags", "gamma", "device", "reserved")] + \
                [("sigma_color", C.c_double), ("sigma_depth", C.c_double)]
+
+
+class Upsample(C.Structure):
+    """rtw_upsample_t"""
+    _fields_ = [(k, C.c_int32) for k in ("levels", "normal_power_log2", "flags", "gamma", "device", "hi_chunks")] + \
+               [("sigma_color", C.c_double), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double)]
 
 
 _lib = None
@@ -158,6 +167,15 @@ def lib():
                                                                        C.c_void_p, C.c_void_p]
         getattr(L, "rtw_accum_filtered_batch_" + sfx).argtypes = [C.c_void_p, C.POINTER(CamT), C.c_int32, seeds, C.POINTER(Params), C.POINTER(Denoise), accums, C.c_int32,
                                                                  C.c_void_p]
+        up, i32, ptr = C.POINTER(Upsample), C.c_int32, C.c_void_p
+        getattr(L, "rtw_upsample_device_" + sfx).argtypes = [up, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_upsample_" + sfx).argtypes = [up, i32, i32, i32, i32, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_upsample_batch_device_" + sfx).argtypes = [up, i32, i32, i32, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_upsample_batch_" + sfx).argtypes = [up, i32, i32, i32, i32, i32, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_render_upsampled_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), C.POINTER(Params), i32, i32, up, ptr]
+        getattr(L, "rtw_render_upsampled_batch_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), i32, i32, up, ptr]
+    L.rtw_upsample_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.rtw_upsample_work_bytes.restype = C.c_int64
     L.rtw_denoise_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_denoise_work_bytes.restype = C.c_int64
     L.rtw_accum_adaptive_info.argtypes = [C.c_void_p, C.POINTER(AdaptiveInfo)]
@@ -247,6 +265,7 @@ FLAG_RCCL_REDUCE = 16    # include/rtw_hip.h RTW_FLAG_RCCL_REDUCE
 FLAG_NUMERICS_CONTRACT = 32        # include/rtw_hip.h RTW_FLAG_NUMERICS_CONTRACT
 FLAG_NUMERICS_REFERENCE_FMA2 = 128  # include/rtw_hip.h RTW_FLAG_NUMERICS_REFERENCE_FMA2
 DENOISE_DEMODULATE = 1   # include/rtw_hip.h RTW_DENOISE_DEMODULATE
+UPSAMPLE_DEMODULATE = 1  # include/rtw_hip.h RTW_UPSAMPLE_DEMODULATE
 GATHER_PEER, GATHER_HOST_STAGED, GATHER_RCCL, GATHER_SAME_DEVICE = 1, 2, 4, 8    # rtw_stats_t.gather_path bits
 ABI_VERSION = 4
 

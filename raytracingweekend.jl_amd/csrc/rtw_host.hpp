@@ -4,7 +4,7 @@
 //   rtw_scene.hip        scene upload: SoA rows, kd split of the group-cull layout, the f16-split operands of the matrix-pipe filter
 //   rtw_launch.hip       one render = one launch of the trace kernel (rtw_kernels.hpp / rtw_pool.hpp): geometry, occupancy, job shape, views
 //   rtw_render_host.hip  every host-buffer entry point: cached per-device context (scene, stream, buffer), ONE one-device path (render_one_device) behind render,
-//                        batch, feature and render + filter calls, the filter on host buffers, or a device list
+//                        batch, feature, render + filter and render + upsample calls, the filter and the upsampler on host buffers, or a device list
 //   rtw_multi.hip        what a device list needs: peer access, the on-demand RCCL binding, the un-tile kernel
 //   rtw_batch_accum_f32.hip / _f64.hip  the BATCH && ACCUM instances of the trace kernel (rtw_instances.hpp: the kernel-instance table), a unit per precision
 //   rtw_features_accum_batch_f32.hip / _f64.hip  the TILED && BATCH instances of the feature kernel (rtw_features.hpp), a unit per precision
@@ -13,6 +13,7 @@
 //   rtw_unit.hip         the T0 unit entry points (rtw_units.hpp)
 //   rtw_features.hip     first-hit feature buffers: one launch of the feature kernel (rtw_features.hpp) for one view or a batch of views, the device-resident entry points
 //   rtw_denoise.hip      the feature-guided denoiser: its checks, the launch sequence of its kernels (rtw_denoise.hpp) for one frame or a batch of frames, the device-resident entry points
+//   rtw_upsample.hip     the feature-guided upsampler: its checks, the launch sequence (the denoiser's prepare and level kernels at the small size, then rtw_upsample.hpp at the full size), the device-resident entry points
 //   (rtw_scene_view.hpp: what both launch functions derive from their arguments; rtw_instances.hpp: the one table of the trace kernel's instances)
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
 #pragma once
@@ -328,6 +329,17 @@ int launch_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, in
 int launch_denoise_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream, const void *d_noise = nullptr);
 inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t nv, const float *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise = nullptr) { return launch_denoise_f32(d, w, h, nv, img, feat, out, work, st, noise); }
 inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t nv, const double *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise = nullptr) { return launch_denoise_f64(d, w, h, nv, img, feat, out, work, st, noise); }
+
+// rtw_upsample.hip -- the feature-guided upsampler (include/rtw_hip.h rtw_upsample_*).  validate_upsample: every check of a call that needs no
+// device -- the parameters, both frame sizes, n_views (0: one frame) and the batch's size.
+int validate_upsample(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, int elem_bytes);
+// launch_upsample: enqueue prepare + `levels` level passes at the small size and the upsampling kernel at the full size on `stream` of the current
+// device.  n_views == 0: one frame, d_work of rtw_upsample_work_bytes bytes (16-byte aligned); n_views >= 1: that many views in the same number
+// of launches, every buffer and every plane of the workspace (n_views times the bytes) holds the views one behind the other, each at its own size.
+int launch_upsample_f32(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, const void *d_image_lo, const void *d_features_lo, const void *d_features_hi, void *d_out, void *d_work, hipStream_t stream);
+int launch_upsample_f64(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, const void *d_image_lo, const void *d_features_lo, const void *d_features_hi, void *d_out, void *d_work, hipStream_t stream);
+inline int launch_upsample_t(const rtw_upsample_t *u, int32_t lw, int32_t lh, int32_t w, int32_t h, int32_t nv, const float *img, const void *flo, const void *fhi, void *out, void *work, hipStream_t st) { return launch_upsample_f32(u, lw, lh, w, h, nv, img, flo, fhi, out, work, st); }
+inline int launch_upsample_t(const rtw_upsample_t *u, int32_t lw, int32_t lh, int32_t w, int32_t h, int32_t nv, const double *img, const void *flo, const void *fhi, void *out, void *work, hipStream_t st) { return launch_upsample_f64(u, lw, lh, w, h, nv, img, flo, fhi, out, work, st); }
 
 // rtw_unit.hip
 int run_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene, const rtw_camera_f32 *cam);

@@ -1,6 +1,6 @@
 // rtw_render_host.hip -- the host-buffer entry points of the C ABI (rtw_render_f32/_f64 is what the Julia ccall binds; replaces src/render.jl:8-44):
 // a cached per-device context (uploaded scene, stream, device buffer), one device (render_one_device: the path the plain, the batched, the
-// feature and the render + filter entry points share) or a device list (tiles dealt round-robin, shards gathered on the first device by peer
+// feature, the render + filter and the render + upsample entry points share) or a device list (tiles dealt round-robin, shards gathered on the first device by peer
 // copies or ONE RCCL reduce: rtw_multi.hip), one D2H of the result.  The single and the batched form of a call share one body (n_views == 0: single).
 #include "rtw_host.hpp"
 
@@ -412,6 +412,88 @@ int render_host_filtered(const SceneT *scene, const CamT *cams, int32_t n_views,
     return rc;
 }
 
+// The upsampler's regions inside a context's device buffer: small image, small features, full features, output, workspace -- each starts on a
+// 16-byte boundary and holds the frames of a batch one behind the other.
+template <typename T> struct UpsampleRegions {
+    size_t img_b, flo_b, fhi_b, out_b, off_flo, off_fhi, off_out, off_work, total;
+    UpsampleRegions(int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views) {
+        const size_t frames = n_views ? (size_t)n_views : 1, n_lo = (size_t)lo_width * (size_t)lo_height * frames, n_hi = (size_t)width * (size_t)height * frames;
+        auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
+        img_b = n_lo * 3 * sizeof(T); flo_b = n_lo * RTW_FEATURE_CHANNELS * sizeof(T); fhi_b = n_hi * RTW_FEATURE_CHANNELS * sizeof(T); out_b = n_hi * 3 * sizeof(T);
+        off_flo = up(img_b); off_fhi = off_flo + up(flo_b); off_out = off_fhi + up(fhi_b); off_work = off_out + up(out_b);
+        total = off_work + (size_t)rtw_upsample_work_bytes(lo_width, lo_height, (int32_t)sizeof(T)) * frames;
+    }
+    // the upsampler over the regions of `base`, on `stream`
+    int launch(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, char *base, hipStream_t stream) const {
+        return launch_upsample_t(u, lo_width, lo_height, width, height, n_views, (const T *)base, base + off_flo, base + off_fhi, base + off_out, base + off_work, stream);
+    }
+};
+
+// The upsampler on host buffers (rtw_upsample_* / rtw_upsample_batch_*): a leased context of the device like filter_host's, three H2D,
+// prepare + `levels` + 1 launches for any number of views, ONE D2H.  This thread's last render (rtw_stats) is not touched.
+template <typename T>
+int upsample_host(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, const T *images_lo, const T *features_lo,
+                  const T *features_hi, T *out) {
+    if (!u || !images_lo || !features_lo || !features_hi || !out) return fail(-1, "null argument");
+    if (int rc = validate_upsample(u, lo_width, lo_height, width, height, n_views, (int)sizeof(T))) return rc;
+    const UpsampleRegions<T> R(lo_width, lo_height, width, height, n_views);
+    if (ranges_overlap(out, R.out_b, images_lo, R.img_b) || ranges_overlap(out, R.out_b, features_lo, R.flo_b) || ranges_overlap(out, R.out_b, features_hi, R.fhi_b))
+        return fail(-2, "out may not alias an input");
+    DeviceGuard guard;
+    HostLease L;
+    if (int rc = acquire_host(u->device, std::vector<unsigned char>(), &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total)) return rc;
+    char *base = (char *)hc->d_img;
+    int rc = 0;
+    hipError_t e = hipMemcpyAsync(base, images_lo, R.img_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_flo, features_lo, R.flo_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_fhi, features_hi, R.fhi_b, hipMemcpyHostToDevice, hc->stream);
+    if (e != hipSuccess) rc = fail((int)e, "upload of the upsampler's inputs failed: %s", hipGetErrorString(e));
+    if (!rc) rc = R.launch(u, lo_width, lo_height, width, height, n_views, base, hc->stream);
+    if (!rc) rc = copy_out(hc, base + R.off_out, out, R.out_b);
+    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    return rc;
+}
+
+// A small render, its feature pass, the full-size feature pass and the upsampler in one call (rtw_render_upsampled_* / rtw_render_upsampled_batch_*):
+// the one-device path above with a device buffer that holds the small linear image (the render of q = p at the small size with gamma 0), the
+// features of q over all of its chunks, the features of p over [0, hi_chunks), the result (the upsampler with p->gamma) and the workspace;
+// 5 + levels launches for any number of views on the context's stream, ONE D2H.  rtw_stats() reports the small render's record.
+template <typename T, typename SceneT, typename CamT>
+int render_host_upsampled(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t lo_width, int32_t lo_height,
+                          const rtw_upsample_t *u, T *out) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !cams || !u || !out) return fail(-1, "null argument");
+    rtw_params q = *p;
+    q.width = lo_width; q.height = lo_height; q.gamma = 0;
+    int nch_p, nch_q, cs;
+    if (int rc = n_views ? validate_features_batch(cams, n_views, p, 0, 1, out, &nch_p, &cs) : validate_features(p, 0, 1, &nch_p, &cs)) return rc;
+    if (int rc = n_views ? validate_features_batch(cams, n_views, &q, 0, 1, out, &nch_q, &cs) : validate_features(&q, 0, 1, &nch_q, &cs)) return rc;
+    if (int rc = validate_upsample(u, lo_width, lo_height, p->width, p->height, n_views, (int)sizeof(T))) return rc;
+    const int hi_chunks = u->hi_chunks ? u->hi_chunks : nch_p;
+    if (int rc = check_chunk_range(0, hi_chunks, nch_p)) return rc;
+    DeviceGuard guard;
+    release_last();
+    const UpsampleRegions<T> R(lo_width, lo_height, p->width, p->height, n_views);
+    RenderRec *frec[2] = {nullptr, nullptr};
+    CtxPtr fctx[2];
+    const int rc = render_one_device(p->device, scene, p, R.total, R.off_out, R.out_b, out, [&](HostCtx *hc, rtw_params &pd, RenderRec **rec, CtxPtr *rctx) {
+        char *base = (char *)hc->d_img;
+        rtw_params qd = pd;
+        qd.width = lo_width; qd.height = lo_height; qd.gamma = 0;
+        rtw_upsample_t uu = *u;
+        uu.gamma = p->gamma != 0; uu.device = hc->device;
+        int rc = launch_render_t(hc->scene, cams, n_views, seeds, &qd, base, hc->stream, rec, rctx);
+        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &qd, 0, nch_q, base + R.off_flo, hc->stream, &frec[0], &fctx[0]);
+        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &pd, 0, hi_chunks, base + R.off_fhi, hc->stream, &frec[1], &fctx[1]);
+        if (!rc) rc = R.launch(&uu, lo_width, lo_height, p->width, p->height, n_views, base, hc->stream);
+        return rc;
+    });
+    for (int k = 0; k < 2; ++k) if (frec[k]) release_rec(fctx[k], frec[k], true);        // (the stream has drained either way)
+    return rc;
+}
+
 // What an accumulator holds, denoised (rtw_accum_filtered_f32/_f64): the gamma-0 resolve (per tile for an adaptive accumulator), the feature
 // pass over exactly the samples it holds, with `guided` its noise map and the noise-guided filter (else the plain one), all on the
 // accumulator's device in a leased context's buffer and stream, ONE D2H.  The accumulator is only read; every step orders itself behind
@@ -523,6 +605,37 @@ int rtw_render_filtered_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f
 int rtw_render_filtered_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d,
                                   double *out) {
     return render_host_filtered<double>(scene, cams, batch_views(n_views), seeds, p, d, out);
+}
+
+int rtw_upsample_f32(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, const float *image_lo, const float *features_lo,
+                     const float *features_hi, float *out) {
+    return upsample_host<float>(u, lo_width, lo_height, width, height, 0, image_lo, features_lo, features_hi, out);
+}
+int rtw_upsample_f64(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, const double *image_lo, const double *features_lo,
+                     const double *features_hi, double *out) {
+    return upsample_host<double>(u, lo_width, lo_height, width, height, 0, image_lo, features_lo, features_hi, out);
+}
+int rtw_upsample_batch_f32(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, const float *images_lo,
+                           const float *features_lo, const float *features_hi, float *out) {
+    return upsample_host<float>(u, lo_width, lo_height, width, height, batch_views(n_views), images_lo, features_lo, features_hi, out);
+}
+int rtw_upsample_batch_f64(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, const double *images_lo,
+                           const double *features_lo, const double *features_hi, double *out) {
+    return upsample_host<double>(u, lo_width, lo_height, width, height, batch_views(n_views), images_lo, features_lo, features_hi, out);
+}
+int rtw_render_upsampled_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, int32_t lo_width, int32_t lo_height, const rtw_upsample_t *u, float *out) {
+    return render_host_upsampled<float>(scene, cam, 0, nullptr, p, lo_width, lo_height, u, out);
+}
+int rtw_render_upsampled_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, int32_t lo_width, int32_t lo_height, const rtw_upsample_t *u, double *out) {
+    return render_host_upsampled<double>(scene, cam, 0, nullptr, p, lo_width, lo_height, u, out);
+}
+int rtw_render_upsampled_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t lo_width,
+                                   int32_t lo_height, const rtw_upsample_t *u, float *out) {
+    return render_host_upsampled<float>(scene, cams, batch_views(n_views), seeds, p, lo_width, lo_height, u, out);
+}
+int rtw_render_upsampled_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t lo_width,
+                                   int32_t lo_height, const rtw_upsample_t *u, double *out) {
+    return render_host_upsampled<double>(scene, cams, batch_views(n_views), seeds, p, lo_width, lo_height, u, out);
 }
 
 int rtw_accum_filtered_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle accum, int32_t guided, float *out) {
