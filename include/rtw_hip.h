@@ -480,8 +480,8 @@ int rtw_render_features_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *ca
  *   Refusals, all decided before any HIP call: a null argument -> -1; levels outside 1..8, normal_power_log2 outside 0..7, unknown flag
  * bits, gamma other than 0 or 1, reserved != 0, device < -1, a sigma that is not finite and positive, width or height < 1, misaligned or
  * aliasing pointers, elem_bytes other than 4 or 8 -> -2; a frame of 2^31 8x8 tiles or more -> -5; the render-and-denoise call additionally
- * refuses everything a feature render of `p` refuses.  Temporal reuse across the views of a batch, compact or sharded frames and device
- * lists are out of scope; N frames in each launch: rtw_filter_batch_* below; noise-guided weights and accumulators as the input: the block behind these declarations.
+ * refuses everything a feature render of `p` refuses.  Compact or sharded frames and device lists are out of scope (DESIGN.md
+ * section 9); history reuse across the views of a camera path: the rtw_temporal_* block further down; N frames in each launch: rtw_filter_batch_* below; noise-guided weights and accumulators as the input: the block behind these declarations.
  * Additive to ABI 4: detected by symbol lookup. */
 #define RTW_DENOISE_DEMODULATE 1   /* filter image / albedo, multiply back at the end */
 typedef struct {
@@ -597,7 +597,8 @@ int rtw_accum_filtered_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, co
  * Filter calls: nulls -> -1; everything the single-frame filter refuses, n_views < 1 -> -2; a batch of 2^39 pixels or more -> -5.
  * rtw_render_filtered_batch_*: both sets.  Then: a scene handle of the other precision -> -4.
  *   Accumulators as the input of a batch (the tiled feature pass, the noise-guided filter): the block behind these declarations.  Out of
- * scope: device lists, temporal reuse across the views.  Additive to ABI 4: detected by symbol lookup. */
+ * scope: device lists.  History reuse across the views: rtw_render_sequence_* (the rtw_temporal_* block further down).
+ * Additive to ABI 4: detected by symbol lookup. */
 int rtw_render_features_batch_device_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds,
                                          const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, void *hip_stream);
 int rtw_render_features_batch_device_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds,
@@ -761,6 +762,104 @@ int rtw_render_upsampled_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_
                                    int32_t lo_width, int32_t lo_height, const rtw_upsample_t *u, float *out);
 int rtw_render_upsampled_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
                                    int32_t lo_width, int32_t lo_height, const rtw_upsample_t *u, double *out);
+
+/* Temporal reprojection: history reuse along a camera path.  N cameras along a path over one static scene at 1-4 spp each see mostly what
+ * the previous camera saw: a temporal step blends a frame with the accumulated history of the previous frame, gathered where the pixel's
+ * first-hit point lay in the previous view.  One new kernel, a small state, and the host paths; everything else (the linear image, the
+ * feature buffers) is what the passes above leave in HBM.
+ *
+ * The definition.  Everything is computed in the element type T (binary32 or binary64); every operation is rounded once, no FMA, no
+ * reassociation; quotients and sqrt are the correctly rounded IEEE ones; subnormals are kept; weights are rational; a tap that does not take
+ * part is dropped by a select, never by a zero weight.  A temporal step takes the parameters rtw_temporal_t, the current camera `cam` and
+ * the previous one `cam_prev`, the current linear image (H*W*3, the render entry points' layout, normally gamma = 0), the current features
+ * (H*W*8, the feature entry points' layout) and the previous STATE, which may be absent (the first frame: then cam_prev is absent too);
+ * it produces an image (H*W*3) and the next state.  Pixel (i, j) (0-based row, column) is slot p = j*H + i.
+ *   State.  Three planes, one behind the other, each starting on a 16-byte boundary: E = (e0, e1, e2, z), a 4-element slot per pixel, at
+ * byte 0; G = (n.x, n.y, n.z, cov), a 4-element slot per pixel, at byte 4*W*H*sizeof(T) -- cov = NaN marks a pixel that is not valid --;
+ * L = len, one element per pixel, at byte 8*W*H*sizeof(T).  rtw_temporal_state_bytes returns the size: 9*W*H elements rounded up to a
+ * multiple of 16 bytes (monotone in the size; < 0: an error code).  The layout is public.
+ *   Prepare, per pixel, exactly the denoiser's: valid = all 3 + 8 inputs are finite; cov = f[7]; has = valid and cov > 0; if has:
+ * n = f[3..5] / cov (three quotients) and z = f[6] / cov, otherwise n = 0 and z = 0.  With RTW_TEMPORAL_DEMODULATE a[k] = max(f[k], T(2^-6))
+ * and e[k] = c[k] / a[k], otherwise a = 1 and e = c.
+ *   The pixel's own ray in the current camera.  The trace kernel samples column j at (j+1)/W + [0,1)/W and rows likewise; the centre of
+ * those samples is  su = (T(j) + T(1.5)) / T(W),  tv = (T(H - i) - T(0.5)) / T(H)  (integers converted to T, one quotient each).  Per
+ * component  D = ((llc + su*hor) + tv*ver) - origin;  l2 = (D.x*D.x + D.y*D.y) + D.z*D.z;  nD = D / sqrt(l2) (three quotients by the one
+ * square root).  The lens is ignored: a stated approximation (lens_radius is not read).
+ *   The point to reproject, relative to the previous origin.  If has: Pw = origin + z*nD and d = Pw - origin_prev (per component, in this
+ * order).  Else, for a sky pixel, the point at infinity: d = nD.
+ *   Projection into the previous camera.  The host computes in binary64 from the previous camera's fields (converted to binary64 exactly):
+ * q = llc - origin, Kw = q.w, Qh = q.hor, Qv = q.ver, ih = 1/(hor.hor), iv = 1/(ver.ver), and rounds each to T once; likewise
+ * inv_sz = T(1/(sigma_depth*sigma_depth)), w_min = T(min_weight), n_max = T(history_max).  Every three-term dot product, on the host and on
+ * the device, is grouped (x + y) + z.  The device computes
+ *       dw = d.w_prev;  front = dw < 0;  lam = Kw / dw
+ *       s = (lam*(d.hor_prev) - Qh)*ih;  t = (lam*(d.ver_prev) - Qv)*iv
+ *       x = s*T(W) - T(1.5);  y = (T(H) - T(0.5)) - t*T(H)
+ *       inr = x > -1 and x < W and y > -1 and y < H   (a NaN fails)
+ *       x0 = floor(x), fx = x - T(x0);  y0 = floor(y), fy = y - T(y0)
+ * A position with inr false decides nothing (the pixel resets below), so x0, fx, y0, fy are only defined under inr.  The depth the point
+ * is expected to have in the previous view is zexp = sqrt((d.x*d.x + d.y*d.y) + d.z*d.z), used for has pixels only.
+ *   Taps.  b = 0, 1 is the outer and c = 0, 1 the inner loop; the tap pixel q is column x0 + b, row y0 + c; kx = b ? fx : 1 - fx,
+ * ky = c ? fy : 1 - fy, sb = ky*kx.  A tap outside the frame, or whose state slot is not valid (G.w is NaN), is skipped.  Any other tap:
+ *       t_v = 1 - |cov_p - cov_q|;  w_v = t_v > 0 ? t_v : +0
+ *       w = sb*w_v
+ *       if has(p) and cov_q > 0:
+ *           dot = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z;  t = dot > 0 ? dot : +0, then t = t*t repeated m = normal_power_log2 times
+ *           zs = zexp + z_q;  r = (zexp - z_q) / (zs > 0 ? zs : 1);  w_z = 1 / (1 + (r*r)*inv_sz)
+ *           w = (w*t)*w_z
+ *       sum_w = sum_w + w;  sum_e[k] = sum_e[k] + w*e_q[k];  sum_l = sum_l + w*len_q
+ * All sums start at +0; n_q, z_q, cov_q, e_q and len_q are the state's.
+ *   Blend.  accept = the previous state is present and front and inr and sum_w >= w_min (a NaN fails).  If accepted:
+ *       eh[k] = sum_e[k] / sum_w;  lh = sum_l / sum_w;  l1 = lh + 1;  n' = l1 < n_max ? l1 : n_max;  alpha = 1 / n'
+ *       e'[k] = eh[k] + alpha*(e[k] - eh[k]);  len' = n'
+ * Otherwise the pixel RESETS: e' = e and len' = 1.
+ *   End.  out[k] = e'[k]*a[k] with RTW_TEMPORAL_DEMODULATE, else e'[k]; then sqrt per channel if gamma = 1.  The next state is E = (e', z),
+ * G = (n, cov), L = len'.  A pixel that is not valid is a quiet NaN in all three `out` channels, has G.w = NaN and zeros in the rest of its
+ * state; it is never a tap.  (tests/temporal_ref.py restates all of this on the CPU and the device agrees on the bits.)
+ *
+ * rtw_temporal_device_*: asynchronous on `hip_stream` of the device t->device (-1: the current one); rtw_stats() is left alone.
+ * d_state_prev == NULL together with cam_prev == NULL is the first frame: every pixel resets.  `d_features` and both states are 16-byte
+ * aligned, `d_image` and `d_out` aligned to T; `d_out` and `d_state_next` alias neither each other nor any input.  One launch.
+ *   rtw_temporal_*: the host-buffer form, blocking, through the cached per-device context like rtw_denoise_f32; `state_prev` (with
+ * `cam_prev`) may be NULL: the first frame; `state_next` receives rtw_temporal_state_bytes bytes.  rtw_stats() is left alone.
+ *   rtw_render_sequence_*: n_views cameras along a path, all on the cached context's stream -- one batched render of `p` with gamma = 0,
+ * one batched feature pass over all N effective chunks, n_views temporal steps in view order (view 0 is the first frame, view v uses
+ * cams[v-1] and the state view v-1 left; two states ping-pong), and, if `d` is not NULL, one batched filter pass (rtw_filter_batch_*'s
+ * launch sequence) over the n_views accumulated LINEAR images and their features -- then one D2H of n_views*H*W*3 elements.  p->gamma is
+ * applied exactly once, by the last stage that runs: with `d` the steps run with gamma = 0 and the filter with p->gamma, without it the steps
+ * run with p->gamma (t->gamma and d->gamma are replaced, t->device and d->device by p->device).  `seeds`: n_views of them, or NULL (p->seed).
+ * View v equals, bit for bit, the chain of the single calls.  rtw_stats() afterwards reports the render's record.
+ *   Refusals, all decided before any HIP call: a null argument -> -1; unknown flag bits, gamma other than 0 or 1, reserved != 0,
+ * device < -1, normal_power_log2 outside 0..7, a sigma_depth that is not finite and positive, min_weight outside (0, 1], history_max not
+ * finite or < 1, width or height < 1, elem_bytes other than 4 or 8, misaligned or aliasing pointers, exactly one of cam_prev /
+ * d_state_prev (state_prev) null -> -2; a frame of 2^31 8x8 tiles or more (the denoiser's frame rule) -> -5; the sequence call additionally
+ * refuses everything rtw_render_filtered_batch_* refuses for its arguments (with `d` NULL: everything a batched feature render refuses).
+ *   Left out on purpose: N independent sequences in one launch, accumulators or the upsampler as the step's input,
+ * device lists, moving spheres (the scene is static: there are no motion vectors beyond the camera's), a variance-guided alpha,
+ * neighbourhood colour clamping.  Additive to ABI 4: detected by symbol lookup. */
+#define RTW_TEMPORAL_DEMODULATE 1  /* accumulate image / albedo, multiply the current albedo back at the end */
+typedef struct {
+    int32_t normal_power_log2;  /* 0..7: m, normal weight = max(0, n.n')^(2^m) */
+    int32_t flags;              /* RTW_TEMPORAL_* */
+    int32_t gamma;              /* 1 = sqrt per channel at the end, 0 = linear */
+    int32_t device;             /* -1 = current */
+    int32_t reserved[2];        /* 0 */
+    double  sigma_depth;        /* > 0, finite */
+    double  min_weight;         /* in (0, 1]: the least sum of tap weights a history is accepted with */
+    double  history_max;        /* >= 1, finite: where len saturates (alpha never falls below 1 / history_max) */
+} rtw_temporal_t;               /* 48 bytes */
+int64_t rtw_temporal_state_bytes(int32_t width, int32_t height, int32_t elem_bytes);
+int rtw_temporal_device_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height,
+                            const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, void *hip_stream);
+int rtw_temporal_device_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
+                            const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, void *hip_stream);
+int rtw_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height,
+                     const float *image, const float *features, const void *state_prev, void *state_next, float *out);
+int rtw_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
+                     const double *image, const double *features, const void *state_prev, void *state_next, double *out);
+int rtw_render_sequence_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
+                            const rtw_temporal_t *t, const rtw_denoise_t *d /* may be NULL */, float *out);
+int rtw_render_sequence_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
+                            const rtw_temporal_t *t, const rtw_denoise_t *d /* may be NULL */, double *out);
 
 /* Counters/timings of the last render issued from this thread (waits for it to finish). */
 int rtw_stats(rtw_stats_t *out);

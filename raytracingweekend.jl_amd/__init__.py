@@ -34,6 +34,9 @@ from .denoise import (  # noqa: F401
 from .upsample import (  # noqa: F401
     make_upsample, render_upsampled, render_upsampled_batch, upsample, upsample_batch, upsample_batch_into, upsample_into, upsample_work_bytes,
 )
+from .temporal import (  # noqa: F401
+    TemporalAccumulator, make_temporal, render_sequence, temporal_state_bytes, temporal_step, temporal_step_into,
+)
 from . import imageio  # noqa: F401
 
 __all__ = [
@@ -51,4 +54,5 @@ __all__ = [
     "denoise_guided_batch_into", "render_adaptive_denoised_batch",
     "make_upsample", "upsample_work_bytes", "upsample", "upsample_into", "upsample_batch", "upsample_batch_into", "render_upsampled",
     "render_upsampled_batch",
+    "make_temporal", "temporal_state_bytes", "temporal_step", "temporal_step_into", "TemporalAccumulator", "render_sequence",
 ]

@@ -32,6 +32,8 @@ SYMBOLS = [
     "rtw_upsample_work_bytes", "rtw_upsample_device_f32", "rtw_upsample_device_f64", "rtw_upsample_f32", "rtw_upsample_f64",
     "rtw_upsample_batch_device_f32", "rtw_upsample_batch_device_f64", "rtw_upsample_batch_f32", "rtw_upsample_batch_f64",
     "rtw_render_upsampled_f32", "rtw_render_upsampled_f64", "rtw_render_upsampled_batch_f32", "rtw_render_upsampled_batch_f64",
+    "rtw_temporal_state_bytes", "rtw_temporal_device_f32", "rtw_temporal_device_f64", "rtw_temporal_f32", "rtw_temporal_f64",
+    "rtw_render_sequence_f32", "rtw_render_sequence_f64",
 ]
 
 
@@ -94,6 +96,14 @@ class Upsample(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("levels", "normal_power_log2", "flags", "gamma", "device", "hi_chunks")] + \
                [("sigma_color", C.c_double), ("sigma_depth", C.c_double), ("sigma_albedo", C.c_double)]
 
+
+class Temporal(C.Structure):
+    """rtw_temporal_t"""
+    _fields_ = [(k, C.c_int32) for k in ("normal_power_log2", "flags", "gamma", "device")] + [("reserved", C.c_int32 * 2)] + \
+               [("sigma_depth", C.c_double), ("min_weight", C.c_double), ("history_max", C.c_double)]
+
+
+assert C.sizeof(Temporal) == 48
 
 _lib = None
 
@@ -174,6 +184,12 @@ def lib():
         getattr(L, "rtw_upsample_batch_" + sfx).argtypes = [up, i32, i32, i32, i32, i32, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_render_upsampled_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), C.POINTER(Params), i32, i32, up, ptr]
         getattr(L, "rtw_render_upsampled_batch_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), i32, i32, up, ptr]
+        tp = C.POINTER(Temporal)
+        getattr(L, "rtw_temporal_device_" + sfx).argtypes = [tp, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_temporal_" + sfx).argtypes = [tp, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_render_sequence_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), tp, C.POINTER(Denoise), ptr]
+    L.rtw_temporal_state_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.rtw_temporal_state_bytes.restype = C.c_int64
     L.rtw_upsample_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_upsample_work_bytes.restype = C.c_int64
     L.rtw_denoise_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
@@ -266,6 +282,7 @@ FLAG_NUMERICS_CONTRACT = 32        # include/rtw_hip.h RTW_FLAG_NUMERICS_CONTRAC
 FLAG_NUMERICS_REFERENCE_FMA2 = 128  # include/rtw_hip.h RTW_FLAG_NUMERICS_REFERENCE_FMA2
 DENOISE_DEMODULATE = 1   # include/rtw_hip.h RTW_DENOISE_DEMODULATE
 UPSAMPLE_DEMODULATE = 1  # include/rtw_hip.h RTW_UPSAMPLE_DEMODULATE
+TEMPORAL_DEMODULATE = 1  # include/rtw_hip.h RTW_TEMPORAL_DEMODULATE
 GATHER_PEER, GATHER_HOST_STAGED, GATHER_RCCL, GATHER_SAME_DEVICE = 1, 2, 4, 8    # rtw_stats_t.gather_path bits
 ABI_VERSION = 4
 

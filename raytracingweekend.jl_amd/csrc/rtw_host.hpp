@@ -14,6 +14,7 @@
 //   rtw_features.hip     first-hit feature buffers: one launch of the feature kernel (rtw_features.hpp) for one view or a batch of views, the device-resident entry points
 //   rtw_denoise.hip      the feature-guided denoiser: its checks, the launch sequence of its kernels (rtw_denoise.hpp) for one frame or a batch of frames, the device-resident entry points
 //   rtw_upsample.hip     the feature-guided upsampler: its checks, the launch sequence (the denoiser's prepare and level kernels at the small size, then rtw_upsample.hpp at the full size), the device-resident entry points
+//   rtw_temporal.hip     temporal reprojection: its checks, the host constants and the one launch of a step (rtw_temporal.hpp), the device-resident entry points
 //   (rtw_scene_view.hpp: what both launch functions derive from their arguments; rtw_instances.hpp: the one table of the trace kernel's instances)
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
 #pragma once
@@ -340,6 +341,16 @@ int launch_upsample_f32(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_he
 int launch_upsample_f64(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, const void *d_image_lo, const void *d_features_lo, const void *d_features_hi, void *d_out, void *d_work, hipStream_t stream);
 inline int launch_upsample_t(const rtw_upsample_t *u, int32_t lw, int32_t lh, int32_t w, int32_t h, int32_t nv, const float *img, const void *flo, const void *fhi, void *out, void *work, hipStream_t st) { return launch_upsample_f32(u, lw, lh, w, h, nv, img, flo, fhi, out, work, st); }
 inline int launch_upsample_t(const rtw_upsample_t *u, int32_t lw, int32_t lh, int32_t w, int32_t h, int32_t nv, const double *img, const void *flo, const void *fhi, void *out, void *work, hipStream_t st) { return launch_upsample_f64(u, lw, lh, w, h, nv, img, flo, fhi, out, work, st); }
+
+// rtw_temporal.hip -- temporal reprojection (include/rtw_hip.h rtw_temporal_*).  validate_temporal: every check of a step that needs neither a
+// device nor a pointer -- the parameters and the frame.
+int validate_temporal(const rtw_temporal_t *t, int32_t width, int32_t height, int elem_bytes);
+// launch_temporal: enqueue ONE step (one launch) on `stream` of the current device.  cam_prev and d_state_prev are both null (the first frame)
+// or both given; the states hold rtw_temporal_state_bytes bytes each (16-byte aligned).
+int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream);
+int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream);
+inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f32 *c, const rtw_camera_f32 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st) { return launch_temporal_f32(t, c, cp, w, h, img, feat, sp, sn, out, st); }
+inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f64 *c, const rtw_camera_f64 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st) { return launch_temporal_f64(t, c, cp, w, h, img, feat, sp, sn, out, st); }
 
 // rtw_unit.hip
 int run_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene, const rtw_camera_f32 *cam);

@@ -1,6 +1,6 @@
 // rtw_render_host.hip -- the host-buffer entry points of the C ABI (rtw_render_f32/_f64 is what the Julia ccall binds; replaces src/render.jl:8-44):
 // a cached per-device context (uploaded scene, stream, device buffer), one device (render_one_device: the path the plain, the batched, the
-// feature, the render + filter and the render + upsample entry points share) or a device list (tiles dealt round-robin, shards gathered on the first device by peer
+// feature, the render + filter, the render + upsample and the sequence entry points share) or a device list (tiles dealt round-robin, shards gathered on the first device by peer
 // copies or ONE RCCL reduce: rtw_multi.hip), one D2H of the result.  The single and the batched form of a call share one body (n_views == 0: single).
 #include "rtw_host.hpp"
 
@@ -494,6 +494,95 @@ int render_host_upsampled(const SceneT *scene, const CamT *cams, int32_t n_views
     return rc;
 }
 
+// The regions of the temporal paths inside a context's device buffer: the linear images and the features of `frames` views, the accumulated
+// images, (filter: the filtered images,) two states, (filter: the denoiser's workspace) -- each starts on a 16-byte boundary.
+template <typename T> struct TemporalRegions {
+    size_t frame_b, img_b, feat_b, st_b, off_feat, off_acc, off_flt, off_st[2], off_work, total;
+    TemporalRegions(int32_t width, int32_t height, size_t frames, bool filter) {
+        const size_t n = (size_t)width * (size_t)height;
+        auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
+        frame_b = n * 3 * sizeof(T); img_b = frame_b * frames; feat_b = n * RTW_FEATURE_CHANNELS * sizeof(T) * frames;
+        st_b = (size_t)rtw_temporal_state_bytes(width, height, (int32_t)sizeof(T));
+        off_feat = up(img_b); off_acc = off_feat + up(feat_b); off_flt = off_acc + up(img_b);
+        off_st[0] = off_flt + (filter ? up(img_b) : 0); off_st[1] = off_st[0] + st_b; off_work = off_st[1] + st_b;
+        total = off_work + (filter ? (size_t)rtw_denoise_work_bytes(width, height, (int32_t)sizeof(T)) * frames : 0);
+    }
+};
+
+// One temporal step on host buffers (rtw_temporal_*): a leased context of the device like filter_host's, two or three H2D, ONE launch, two D2H
+// (the next state, the image).  This thread's last render (rtw_stats) is not touched.
+template <typename T, typename CamT>
+int temporal_host(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const T *image, const T *features, const void *state_prev,
+                  void *state_next, T *out) {
+    if (!t || !cam || !image || !features || !state_next || !out) return fail(-1, "null argument");
+    if (int rc = validate_temporal(t, width, height, (int)sizeof(T))) return rc;
+    if ((cam_prev == nullptr) != (state_prev == nullptr)) return fail(-2, "cam_prev and state_prev must both be given or both be null (the first frame)");
+    const TemporalRegions<T> R(width, height, 1, false);
+    const size_t feat_b = R.feat_b, img_b = R.img_b, st_b = R.st_b;
+    if (ranges_overlap(out, img_b, state_next, st_b)) return fail(-2, "out and state_next may not alias each other");
+    if (ranges_overlap(out, img_b, image, img_b) || ranges_overlap(out, img_b, features, feat_b) || (state_prev && ranges_overlap(out, img_b, state_prev, st_b)))
+        return fail(-2, "out may not alias an input");
+    if (ranges_overlap(state_next, st_b, image, img_b) || ranges_overlap(state_next, st_b, features, feat_b) || (state_prev && ranges_overlap(state_next, st_b, state_prev, st_b)))
+        return fail(-2, "state_next may not alias an input");
+    DeviceGuard guard;
+    HostLease L;
+    if (int rc = acquire_host(t->device, std::vector<unsigned char>(), &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total)) return rc;
+    char *base = (char *)hc->d_img;
+    int rc = 0;
+    hipError_t e = hipMemcpyAsync(base, image, img_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_feat, features, feat_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess && state_prev) e = hipMemcpyAsync(base + R.off_st[0], state_prev, st_b, hipMemcpyHostToDevice, hc->stream);
+    if (e != hipSuccess) rc = fail((int)e, "upload of the temporal step's inputs failed: %s", hipGetErrorString(e));
+    if (!rc) rc = launch_temporal_t(t, cam, cam_prev, width, height, base, base + R.off_feat, state_prev ? base + R.off_st[0] : nullptr, base + R.off_st[1], base + R.off_acc, hc->stream);
+    if (!rc) {
+        e = hipMemcpyAsync(state_next, base + R.off_st[1], st_b, hipMemcpyDeviceToHost, hc->stream);
+        if (e != hipSuccess) rc = fail((int)e, "download of the next state failed: %s", hipGetErrorString(e));
+    }
+    if (!rc) rc = copy_out(hc, base + R.off_acc, out, img_b);
+    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    return rc;
+}
+
+// N cameras along a path with history reuse (rtw_render_sequence_*): the one-device path above with a device buffer that holds the linear images
+// (ONE batched render with gamma 0), the features (ONE batched pass over all chunks), the accumulated images (n_views temporal steps in view
+// order, two states ping-pong) and, with `d`, the filtered images and the filter's workspace (ONE batched filter pass); 2 + n_views (+ 1 + levels)
+// launches on the context's stream, ONE D2H.  p->gamma is applied by the last stage that runs.  rtw_stats() reports the render's record.
+template <typename T, typename SceneT, typename CamT>
+int render_host_sequence(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t, const rtw_denoise_t *d, T *out) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !cams || !t || !out) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = validate_features_batch(cams, n_views, p, 0, 1, out, &nch, &cs)) return rc;
+    if (d) if (int rc = validate_filter_batch(d, p->width, p->height, n_views)) return rc;
+    if (int rc = validate_temporal(t, p->width, p->height, (int)sizeof(T))) return rc;
+    DeviceGuard guard;
+    release_last();
+    const TemporalRegions<T> R(p->width, p->height, (size_t)n_views, d != nullptr);
+    RenderRec *frec = nullptr;
+    CtxPtr fctx;
+    const int rc = render_one_device(p->device, scene, p, R.total, d ? R.off_flt : R.off_acc, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+        char *base = (char *)hc->d_img;
+        q.gamma = 0;
+        rtw_temporal_t tt = *t;
+        tt.gamma = d ? 0 : (p->gamma != 0); tt.device = hc->device;
+        int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
+        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec, &fctx);
+        for (int v = 0; v < n_views && !rc; ++v)
+            rc = launch_temporal_t(&tt, cams + v, v ? cams + (v - 1) : nullptr, p->width, p->height, base + (size_t)v * R.frame_b, base + R.off_feat + (size_t)v * (R.feat_b / (size_t)n_views),
+                                   v ? base + R.off_st[(v & 1) ^ 1] : nullptr, base + R.off_st[v & 1], base + R.off_acc + (size_t)v * R.frame_b, hc->stream);
+        if (!rc && d) {
+            rtw_denoise_t dd = *d;
+            dd.gamma = p->gamma != 0; dd.device = hc->device;
+            rc = launch_denoise_t(&dd, p->width, p->height, n_views, (const T *)(base + R.off_acc), base + R.off_feat, base + R.off_flt, base + R.off_work, hc->stream);
+        }
+        return rc;
+    });
+    if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
+    return rc;
+}
+
 // What an accumulator holds, denoised (rtw_accum_filtered_f32/_f64): the gamma-0 resolve (per tile for an adaptive accumulator), the feature
 // pass over exactly the samples it holds, with `guided` its noise map and the noise-guided filter (else the plain one), all on the
 // accumulator's device in a leased context's buffer and stream, ONE D2H.  The accumulator is only read; every step orders itself behind
@@ -636,6 +725,23 @@ int rtw_render_upsampled_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_
 int rtw_render_upsampled_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t lo_width,
                                    int32_t lo_height, const rtw_upsample_t *u, double *out) {
     return render_host_upsampled<double>(scene, cams, batch_views(n_views), seeds, p, lo_width, lo_height, u, out);
+}
+
+int rtw_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height, const float *image, const float *features,
+                     const void *state_prev, void *state_next, float *out) {
+    return temporal_host<float>(t, cam, cam_prev, width, height, image, features, state_prev, state_next, out);
+}
+int rtw_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const double *image, const double *features,
+                     const void *state_prev, void *state_next, double *out) {
+    return temporal_host<double>(t, cam, cam_prev, width, height, image, features, state_prev, state_next, out);
+}
+int rtw_render_sequence_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
+                            const rtw_denoise_t *d, float *out) {
+    return render_host_sequence<float>(scene, cams, batch_views(n_views), seeds, p, t, d, out);
+}
+int rtw_render_sequence_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
+                            const rtw_denoise_t *d, double *out) {
+    return render_host_sequence<double>(scene, cams, batch_views(n_views), seeds, p, t, d, out);
 }
 
 int rtw_accum_filtered_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle accum, int32_t guided, float *out) {

@@ -1,0 +1,122 @@
+// rtw_temporal.hip -- temporal reprojection (include/rtw_hip.h rtw_temporal_*): the checks that need no device, the host constants of a step,
+// the one launch of its kernel (rtw_temporal.hpp) and the device-resident entry points.
+// (The host-buffer entry points, rtw_temporal_* and rtw_render_sequence_*, live with the other cached-context paths in rtw_render_host.hip.)
+#include "rtw_host.hpp"
+#include "rtw_temporal.hpp"
+
+namespace rtwh {
+
+// Everything about a temporal step that is decided without a device and without a pointer.
+int validate_temporal(const rtw_temporal_t *t, int32_t width, int32_t height, int elem_bytes) {
+    if (!t) return fail(-1, "null temporal parameters");
+    if (t->normal_power_log2 < 0 || t->normal_power_log2 > 7) return fail(-2, "normal_power_log2 must be in 0..7 (got %d)", t->normal_power_log2);
+    if (t->flags & ~(RTW_TEMPORAL_DEMODULATE)) return fail(-2, "unknown temporal flags 0x%x", t->flags);
+    if (t->gamma != 0 && t->gamma != 1) return fail(-2, "gamma must be 0 or 1 (got %d)", t->gamma);
+    if (t->device < -1) return fail(-2, "bad device %d", t->device);
+    if (t->reserved[0] != 0 || t->reserved[1] != 0) return fail(-2, "reserved must be 0");
+    if (!(t->sigma_depth > 0) || !std::isfinite(t->sigma_depth)) return fail(-2, "sigma_depth must be finite and positive");
+    if (!(t->min_weight > 0) || !(t->min_weight <= 1)) return fail(-2, "min_weight must be in (0, 1]");
+    if (!(t->history_max >= 1) || !std::isfinite(t->history_max)) return fail(-2, "history_max must be finite and >= 1");
+    if (width < 1 || height < 1) return fail(-2, "width/height must be positive (got %d x %d)", width, height);
+    if (const int64_t rc = rtw_denoise_work_bytes(width, height, elem_bytes); rc < 0) return (int)rc;         // (the denoiser's frame rule)
+    return 0;
+}
+
+// the state: the planes E and G of 4 elements per pixel and L of one, one behind the other (each starts on a 16-byte boundary)
+static long long state_bytes(int32_t width, int32_t height, int elem_bytes) { return ((long long)width * height * 9 * elem_bytes + 15) & ~15ll; }
+
+// Enqueue one step on `stream` of the current device (validate_temporal has accepted the call).  cam_prev and d_state_prev are both null
+// (the first frame) or both given.
+template <typename T, typename CamT>
+int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features,
+                    const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream) {
+    using V = typename rtw::DnVec<T>::type;
+    const long long n_pix = (long long)width * height;
+    rtw::TpParams<T> U;
+    memset(&U, 0, sizeof U);
+    for (int k = 0; k < 3; ++k) { U.o[k] = cam->origin[k]; U.llc[k] = cam->lower_left_corner[k]; U.hor[k] = cam->horizontal[k]; U.ver[k] = cam->vertical[k]; }
+    if (cam_prev) {
+        // the projection's constants: binary64 from the previous camera's fields, every dot product (x + y) + z, each rounded to T once
+        double q[3], w[3], h[3], v[3];
+        for (int k = 0; k < 3; ++k) {
+            U.po[k] = cam_prev->origin[k]; U.pw[k] = cam_prev->w[k]; U.ph[k] = cam_prev->horizontal[k]; U.pv[k] = cam_prev->vertical[k];
+            q[k] = (double)cam_prev->lower_left_corner[k] - (double)cam_prev->origin[k];
+            w[k] = cam_prev->w[k]; h[k] = cam_prev->horizontal[k]; v[k] = cam_prev->vertical[k];
+        }
+        auto dot = [](const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+        U.Kw = (T)dot(q, w); U.Qh = (T)dot(q, h); U.Qv = (T)dot(q, v);
+        U.ih = (T)(1.0 / dot(h, h)); U.iv = (T)(1.0 / dot(v, v));
+    }
+    U.inv_sz = (T)(1.0 / (t->sigma_depth * t->sigma_depth));
+    U.w_min = (T)t->min_weight; U.n_max = (T)t->history_max;
+    U.m = t->normal_power_log2;
+    U.mode = ((t->flags & RTW_TEMPORAL_DEMODULATE) ? RTW_DN_DEMOD : 0) | (t->gamma ? RTW_DN_GAMMA : 0);
+    U.W = width; U.H = height;
+    const long long pb = n_pix * 4 * (long long)sizeof(T);
+    const char *sp = (const char *)d_state_prev;
+    char *sn = (char *)d_state_next;
+    const unsigned grid = (unsigned)((n_pix + 255) / 256);
+    // (measurement aid, tools/gpu_temporal.py: events around the kernel, reported on stderr -- this one blocks)
+    static const bool profile = aid_flag("RTW_TEMPORAL_PROFILE");
+    struct Events { hipEvent_t e[2] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
+    if (profile) { for (hipEvent_t &x : events.e) HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventRecord(events.e[0], stream)); }
+    (void)hipGetLastError();
+    if (sp) hipLaunchKernelGGL((rtw::tp_step<T, true>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, (const V *)sp, (const V *)(sp + pb),
+                               (const T *)(sp + 2 * pb), (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out);
+    else hipLaunchKernelGGL((rtw::tp_step<T, false>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, (const V *)nullptr, (const V *)nullptr,
+                            (const T *)nullptr, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out);
+    HIP_TRY(hipGetLastError());
+    if (profile) {
+        float ms = 0;
+        HIP_TRY(hipEventRecord(events.e[1], stream));
+        HIP_TRY(hipEventSynchronize(events.e[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, events.e[0], events.e[1]));
+        fprintf(stderr, "[rtw temporal] %s %dx%d step prev=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, sp ? 1 : 0, ms);
+    }
+    return 0;
+}
+
+int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st) { return launch_temporal<float>(t, cam, cam_prev, w, h, img, feat, sp, sn, out, st); }
+int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st) { return launch_temporal<double>(t, cam, cam_prev, w, h, img, feat, sp, sn, out, st); }
+
+// The device-resident entry point: nulls, the parameters, then the pointers' alignment and aliasing.
+template <typename T, typename CamT>
+int temporal_device(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev,
+                    void *d_state_next, void *d_out, void *stream_v) {
+    if (!t || !cam || !d_image || !d_features || !d_state_next || !d_out) return fail(-1, "null argument");
+    if (int rc = validate_temporal(t, width, height, (int)sizeof(T))) return rc;
+    if ((cam_prev == nullptr) != (d_state_prev == nullptr)) return fail(-2, "cam_prev and d_state_prev must both be given or both be null (the first frame)");
+    if (((uintptr_t)d_features & 15u) || ((uintptr_t)d_state_prev & 15u) || ((uintptr_t)d_state_next & 15u)) return fail(-2, "the feature buffer and both states must be 16-byte aligned");
+    if (((uintptr_t)d_image & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
+    const size_t n_pix = (size_t)width * (size_t)height;
+    const size_t img_b = n_pix * 3 * sizeof(T), feat_b = n_pix * 8 * sizeof(T), st_b = (size_t)state_bytes(width, height, sizeof(T));
+    if (ranges_overlap(d_out, img_b, d_state_next, st_b)) return fail(-2, "d_out and d_state_next may not alias each other");
+    if (ranges_overlap(d_out, img_b, d_image, img_b) || ranges_overlap(d_out, img_b, d_features, feat_b) || (d_state_prev && ranges_overlap(d_out, img_b, d_state_prev, st_b)))
+        return fail(-2, "d_out may not alias an input");
+    if (ranges_overlap(d_state_next, st_b, d_image, img_b) || ranges_overlap(d_state_next, st_b, d_features, feat_b) || (d_state_prev && ranges_overlap(d_state_next, st_b, d_state_prev, st_b)))
+        return fail(-2, "d_state_next may not alias an input");
+    DeviceGuard guard;
+    if (t->device >= 0) HIP_TRY(hipSetDevice(t->device));
+    return launch_temporal<T>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, (hipStream_t)stream_v);
+}
+
+}  // namespace rtwh
+
+using namespace rtwh;
+
+extern "C" {
+
+int64_t rtw_temporal_state_bytes(int32_t width, int32_t height, int32_t elem_bytes) {
+    if (const int64_t rc = rtw_denoise_work_bytes(width, height, elem_bytes); rc < 0) return rc;             // (elem_bytes, the sizes, the denoiser's frame rule)
+    return state_bytes(width, height, elem_bytes);
+}
+int rtw_temporal_device_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height, const void *d_image,
+                            const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, void *hip_stream) {
+    return temporal_device<float>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, hip_stream);
+}
+int rtw_temporal_device_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const void *d_image,
+                            const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, void *hip_stream) {
+    return temporal_device<double>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, hip_stream);
+}
+
+}  // extern "C"

@@ -1,0 +1,157 @@
+// rtw_temporal.hpp -- the kernel of the temporal reprojection (include/rtw_hip.h rtw_temporal_*: the definition is there): one step of history
+// reuse along a camera path.
+//   tp_step        one pixel per lane, lanes along i.  The pixel is prepared inline exactly as dn_prepare prepares it (validity, n, z, cov, the
+//                  (de)modulated colour e); its own ray in the current camera gives the world point (or, for a sky pixel, the direction) that is
+//                  projected into the PREVIOUS camera; the 2 x 2 taps around that position gather one E slot, one G slot and one L element each
+//                  from the previous state in global memory (L1 / L2); the blend and the next state follow.  State planes, pixel p at slot p:
+//                  E = (e0, e1, e2, z)   G = (n.x, n.y, n.z, cov; cov = NaN: not valid)   L = len.
+//   HAS_PREV       false: the first frame -- no camera, no state, every pixel resets; the instance reads neither.
+// No LDS, no atomics, no cross-lane operation; the trip count over the 4 taps is uniform, skipped taps are dropped by selects, as in dn_tap.
+// Every operation is rounded once (the Makefile's -ffp-contract=off -fno-fast-math); divisions and sqrt are the compiler's IEEE ones.
+#pragma once
+#include "rtw_denoise.hpp"
+
+namespace rtw {
+
+// the two cameras and what the host derives from them and from rtw_temporal_t, by value
+template <typename T> struct TpParams {
+    T o[3], llc[3], hor[3], ver[3];     // the current camera: origin, lower_left_corner, horizontal, vertical
+    T po[3], pw[3], ph[3], pv[3];       // the previous camera: origin, w, horizontal, vertical  (HAS_PREV = false: unused)
+    T Kw, Qh, Qv, ih, iv;               // q = llc - origin of the previous camera: q.w, q.hor, q.ver, 1 / hor.hor, 1 / ver.ver (binary64, rounded to T)
+    T inv_sz, w_min, n_max;             // 1 / sigma_depth^2, min_weight, history_max (binary64, rounded to T)
+    int m, mode;                        // normal_power_log2; RTW_DN_DEMOD | RTW_DN_GAMMA
+    int W, H;
+};
+
+__device__ __forceinline__ float tp_floor(float x) { return __builtin_floorf(x); }
+__device__ __forceinline__ double tp_floor(double x) { return __builtin_floor(x); }
+template <typename T> __device__ __forceinline__ T tp_dot(T ax, T ay, T az, const T *b) { return (ax * b[0] + ay * b[1]) + az * b[2]; }
+
+template <typename T> struct TpSum { T w, e0, e1, e2, l; };
+
+// one tap of the previous state; `ok`: inside the frame and valid.  The data of a tap that is not ok may be anything: selects, not weights, drop it.
+// (g: the pixel's own guides (n, cov); hasP: it is covered; zexp: the depth its point has in the previous view)
+template <typename T, typename V>
+__device__ __forceinline__ void tp_tap(TpSum<T> &a, const V &g, bool hasP, T zexp, const V &eq, const V &gq, T lq, T sb, bool ok, const TpParams<T> &U) {
+    const T tv = T(1) - dn_abs(g.w - gq.w);
+    const T wv = tv > T(0) ? tv : T(0);
+    T w = sb * wv;
+    const T dot = (g.x * gq.x + g.y * gq.y) + g.z * gq.z;
+    T t = dot > T(0) ? dot : T(0);
+    for (int r = 0; r < U.m; ++r) t = t * t;
+    const T zs = zexp + eq.w;
+    const T rz = (zexp - eq.w) / (zs > T(0) ? zs : T(1));
+    const T wz = T(1) / (T(1) + (rz * rz) * U.inv_sz);
+    const T wg = (w * t) * wz;
+    w = (hasP && gq.w > T(0)) ? wg : w;                 // has(p) && has(q)  (cov_q = NaN: not valid, so not has)
+    a.w = a.w + (ok ? w : T(0));
+    a.e0 = a.e0 + (ok ? w * eq.x : T(0));
+    a.e1 = a.e1 + (ok ? w * eq.y : T(0));
+    a.e2 = a.e2 + (ok ? w * eq.z : T(0));
+    a.l = a.l + (ok ? w * lq : T(0));
+}
+
+// lane = flat pixel P = j*H + i
+template <typename T, bool HAS_PREV>
+__global__ __launch_bounds__(256) void tp_step(TpParams<T> U, const T *__restrict__ image, const typename DnVec<T>::type *__restrict__ feat,
+                                               const typename DnVec<T>::type *__restrict__ Ep, const typename DnVec<T>::type *__restrict__ Gp, const T *__restrict__ Lp,
+                                               typename DnVec<T>::type *__restrict__ En, typename DnVec<T>::type *__restrict__ Gn, T *__restrict__ Ln, T *__restrict__ out) {
+    using V = typename DnVec<T>::type;
+    const long long H = U.H, W = U.W, n_pix = W * H;
+    const long long P = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (P >= n_pix) return;
+    // (a 32-bit division whenever the frame allows it)
+    long long j, i;
+    if (n_pix < (1ll << 31)) {
+        const unsigned jj = (unsigned)P / (unsigned)H;
+        j = jj; i = (unsigned)P - jj * (unsigned)H;
+    } else {
+        j = P / H; i = P - j * H;
+    }
+    // ---- prepare: dn_prepare's arithmetic on this pixel
+    const T c0 = image[P * 3 + 0], c1 = image[P * 3 + 1], c2 = image[P * 3 + 2];
+    const V f0 = feat[P * 2 + 0], f1 = feat[P * 2 + 1];        // albedo, n.x | n.y, n.z, depth, coverage
+    const bool valid = dn_finite(c0) && dn_finite(c1) && dn_finite(c2) && dn_finite(f0.x) && dn_finite(f0.y) && dn_finite(f0.z) && dn_finite(f0.w) &&
+                       dn_finite(f1.x) && dn_finite(f1.y) && dn_finite(f1.z) && dn_finite(f1.w);
+    const T cov = f1.w;
+    const bool has = valid && cov > T(0);
+    const T dv = has ? cov : T(1);
+    const T nx = f0.w / dv, ny = f1.x / dv, nz = f1.y / dv, zq = f1.z / dv;
+    V g;
+    g.x = has ? nx : T(0); g.y = has ? ny : T(0); g.z = has ? nz : T(0); g.w = cov;
+    const T z = has ? zq : T(0);
+    T a0 = T(1), a1 = T(1), a2 = T(1), e0 = c0, e1 = c1, e2 = c2;
+    if (U.mode & RTW_DN_DEMOD) {
+        const T floor_ = T(0.015625);               // 2^-6
+        a0 = f0.x > floor_ ? f0.x : floor_; a1 = f0.y > floor_ ? f0.y : floor_; a2 = f0.z > floor_ ? f0.z : floor_;
+        e0 = c0 / a0; e1 = c1 / a1; e2 = c2 / a2;
+    }
+    T r0 = e0, r1 = e1, r2 = e2, len = T(1);        // a reset
+    if constexpr (HAS_PREV) {
+        // ---- the pixel's own ray in the current camera (the centre of the trace kernel's samples; the lens is ignored)
+        const T su = (T((int)j) + T(1.5)) / T((int)W);
+        const T tv = (T((int)(H - i)) - T(0.5)) / T((int)H);
+        const T D0 = ((U.llc[0] + su * U.hor[0]) + tv * U.ver[0]) - U.o[0];
+        const T D1 = ((U.llc[1] + su * U.hor[1]) + tv * U.ver[1]) - U.o[1];
+        const T D2 = ((U.llc[2] + su * U.hor[2]) + tv * U.ver[2]) - U.o[2];
+        const T sl = dn_sqrt((D0 * D0 + D1 * D1) + D2 * D2);
+        const T n0 = D0 / sl, n1 = D1 / sl, n2 = D2 / sl;
+        // ---- the point to reproject (a sky pixel: the point at infinity), relative to the previous origin
+        const T d0 = has ? (U.o[0] + z * n0) - U.po[0] : n0;
+        const T d1 = has ? (U.o[1] + z * n1) - U.po[1] : n1;
+        const T d2 = has ? (U.o[2] + z * n2) - U.po[2] : n2;
+        // ---- projection into the previous camera
+        const T dw = tp_dot<T>(d0, d1, d2, U.pw);
+        const bool front = dw < T(0);
+        const T lam = U.Kw / dw;
+        const T s = (lam * tp_dot<T>(d0, d1, d2, U.ph) - U.Qh) * U.ih;
+        const T t = (lam * tp_dot<T>(d0, d1, d2, U.pv) - U.Qv) * U.iv;
+        const T x = s * T((int)W) - T(1.5);
+        const T y = (T((int)H) - T(0.5)) - t * T((int)H);
+        const bool inr = x > T(-1) && x < T((int)W) && y > T(-1) && y < T((int)H);       // (a NaN fails)
+        // (a position that is not in range decides nothing: its taps are gathered around (0, 0) and thrown away)
+        const T xs = inr ? x : T(0), ys = inr ? y : T(0);
+        const T xf = tp_floor(xs), yf = tp_floor(ys);
+        const long long x0 = (int)xf, y0 = (int)yf;             // -1 .. W-1, -1 .. H-1
+        const T fx = xs - xf, fy = ys - yf;
+        const T zexp = dn_sqrt((d0 * d0 + d1 * d1) + d2 * d2);
+        TpSum<T> a = {T(0), T(0), T(0), T(0), T(0)};
+#pragma unroll
+        for (int b = 0; b <= 1; ++b) {
+            const T kx = b ? fx : T(1) - fx;
+#pragma unroll
+            for (int c = 0; c <= 1; ++c) {
+                const T ky = c ? fy : T(1) - fy;
+                const long long qi = y0 + c, qj = x0 + b;
+                const bool in = qi >= 0 && qi < H && qj >= 0 && qj < W;
+                const long long q = in ? qj * H + qi : P;
+                const V eq = Ep[q], gq = Gp[q];
+                const T lq = Lp[q];
+                tp_tap<T>(a, g, has, zexp, eq, gq, lq, ky * kx, in && gq.w == gq.w, U);
+            }
+        }
+        // ---- blend
+        const bool accept = front && inr && a.w >= U.w_min;      // (a NaN sum fails)
+        const T h0 = a.e0 / a.w, h1 = a.e1 / a.w, h2 = a.e2 / a.w, lh = a.l / a.w;
+        const T l1 = lh + T(1);
+        const T nn = l1 < U.n_max ? l1 : U.n_max;
+        const T alpha = T(1) / nn;
+        const T b0 = h0 + alpha * (e0 - h0), b1 = h1 + alpha * (e1 - h1), b2 = h2 + alpha * (e2 - h2);
+        r0 = accept ? b0 : e0; r1 = accept ? b1 : e1; r2 = accept ? b2 : e2;
+        len = accept ? nn : T(1);
+    }
+    // ---- end: the image and the next state
+    T o0 = r0, o1 = r1, o2 = r2;
+    if (U.mode & RTW_DN_DEMOD) { o0 = r0 * a0; o1 = r1 * a1; o2 = r2 * a2; }
+    if (U.mode & RTW_DN_GAMMA) { o0 = dn_sqrt(o0); o1 = dn_sqrt(o1); o2 = dn_sqrt(o2); }
+    out[P * 3 + 0] = valid ? o0 : dn_nan<T>();
+    out[P * 3 + 1] = valid ? o1 : dn_nan<T>();
+    out[P * 3 + 2] = valid ? o2 : dn_nan<T>();
+    V en;
+    en.x = valid ? r0 : T(0); en.y = valid ? r1 : T(0); en.z = valid ? r2 : T(0); en.w = z;
+    g.w = valid ? cov : dn_nan<T>();
+    En[P] = en; Gn[P] = g;
+    Ln[P] = valid ? len : T(0);
+}
+
+}  // namespace rtw
