@@ -835,7 +835,8 @@ int rtw_render_upsampled_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_
  * refuses everything rtw_render_filtered_batch_* refuses for its arguments (with `d` NULL: everything a batched feature render refuses).
  *   Left out on purpose: N independent sequences in one launch, accumulators or the upsampler as the step's input,
  * device lists, moving spheres (the scene is static: there are no motion vectors beyond the camera's), a variance-guided alpha,
- * neighbourhood colour clamping.  Additive to ABI 4: detected by symbol lookup. */
+ * neighbourhood colour clamping.  (A per-pixel noise map from the history's second moments, and the sequence call that feeds it to the
+ * noise-guided filter: the block behind these declarations.)  Additive to ABI 4: detected by symbol lookup. */
 #define RTW_TEMPORAL_DEMODULATE 1  /* accumulate image / albedo, multiply the current albedo back at the end */
 typedef struct {
     int32_t normal_power_log2;  /* 0..7: m, normal weight = max(0, n.n')^(2^m) */
@@ -860,6 +861,94 @@ int rtw_render_sequence_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *ca
                             const rtw_temporal_t *t, const rtw_denoise_t *d /* may be NULL */, float *out);
 int rtw_render_sequence_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
                             const rtw_temporal_t *t, const rtw_denoise_t *d /* may be NULL */, double *out);
+
+/* Temporal moments: a per-pixel noise estimate from the history, for the noise-guided filter (rtw_guided_filter_device_*,
+ * rtw_guided_filter_batch_device_*).  A pixel with a long history has seen many independent samples of its radiance, a pixel that has just
+ * been disoccluded one; the step above can carry the second moment of what it accumulates, and a second pass turns state and moments into
+ * the relative-noise map the guided filter already takes.  Where the history is short a spatial estimate stands in.  Nothing above changes:
+ * the 9-element state keeps its layout and size, the moments live in a buffer of their own, and the step's image and state are the same bits.
+ * (The entry points are named rtw_history_* and rtw_render_path_guided_*: the names of the block above are a closed set.)
+ *
+ * The definition, in the arithmetic of the block above (T, one rounding per operation, no FMA, IEEE quotients and sqrt, rational weights,
+ * a tap that takes no part is dropped by a select).
+ *   Moment plane.  M holds one element per pixel at slot p = j*H + i: the running second moment of the pixel's (de)modulated luminance; a
+ * pixel that is not valid stores 0.  rtw_history_moment_bytes returns its size: W*H elements rounded up to a multiple of 16 bytes (the error
+ * codes are those of rtw_temporal_state_bytes).
+ *   Step with moments.  rtw_temporal_device_* with two more pointers, the previous and the next moment plane.  The image and all three state
+ * planes are those of rtw_temporal_device_* on the bits.  In addition, with e the pixel's (de)modulated colour of Prepare:
+ *       y = (e[0] + e[1]) + e[2];  y2 = y*y
+ * every tap that contributes (the same taps, the same w, the same order) adds  sum_m = sum_m + w*M_q  (sum_m starts at +0), and
+ *       accepted:  mh = sum_m / sum_w;  M' = mh + alpha*(y2 - mh)          reset, or the first frame:  M' = y2
+ * M' is stored for a valid pixel, 0 for any other.
+ *   Noise map.  A second pass over the NEXT state (E, G, L) and its moment plane M; `d_noise` receives height*width elements, pixel (i, j) at
+ * j*height + i (the layout rtw_guided_filter_device_* reads).  A pixel whose slot is not valid (G.w is NaN) is a quiet NaN.  Any other pixel p,
+ * with inv_sz = T(1/(sigma_depth*sigma_depth)) and ml = T(min_len) rounded on the host as above, m = normal_power_log2, r = radius:
+ *       Lm = (E[0] + E[1]) + E[2];  vt = M - Lm*Lm;  var = vt > 0 ? vt : +0
+ *       if not (len >= ml), the spatial estimate: S0 = S1 = S2 = +0; dj = -r..r is the outer and di = -r..r the inner loop; the tap q is row
+ *       i + di, column j + dj; a tap outside the frame or whose slot is not valid is skipped; any other tap (the centre among them):
+ *           t_v = 1 - |cov_p - cov_q|;  w = t_v > 0 ? t_v : +0                                   (the step's tap weight with sb = 1)
+ *           if cov_p > 0 and cov_q > 0:
+ *               dot = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z;  t = dot > 0 ? dot : +0, then t = t*t repeated m times
+ *               zs = z_p + z_q;  rz = (z_p - z_q) / (zs > 0 ? zs : 1);  w_z = 1 / (1 + (rz*rz)*inv_sz)          (zexp = z_p)
+ *               w = (w*t)*w_z
+ *           Lm_q = (E_q[0] + E_q[1]) + E_q[2];  S0 = S0 + w;  S1 = S1 + w*Lm_q;  S2 = S2 + w*M_q
+ *       then  mu = S1 / S0;  vs = S2 / S0 - mu*mu;  var = vs > 0 ? vs : +0
+ *       v = var / len;  rho = sqrt(v) / (Lm > T(2^-6) ? Lm : T(2^-6))
+ * The centre tap has t_v = 1, so S0 > 0 unless a covered pixel's normal is the zero vector (then 0 / 0: the map is NaN there, which the
+ * guided filter treats as a pixel that is not valid).  rho is relative to the luminance of the accumulated, (de)modulated colour: the
+ * guided filter's prepare multiplies it back when it runs with the same demodulation as the step.  (tests/temporal_noise_ref.py restates
+ * all of this on the CPU, twice, and the device agrees on the bits.)
+ *
+ * rtw_history_moments_device_*: rtw_temporal_device_* with `d_moment_prev` / `d_moment_next`, DEVICE pointers to rtw_history_moment_bytes
+ * bytes, 16-byte aligned; d_moment_prev is NULL exactly when d_state_prev is; the three outputs alias neither each other nor an input.  One
+ * launch, asynchronous.
+ *   rtw_history_noise_device_*: the map of `d_state` and `d_moment` into `d_noise` (aligned to T, aliasing neither input), one launch,
+ * asynchronous on `hip_stream` of the device n->device (-1: the current one).
+ *   rtw_history_moments_*: the host-buffer form, blocking, through the cached context like rtw_temporal_f32: the step, then the map of what
+ * it left; `state_prev`, `moment_prev` and `cam_prev` are NULL together (the first frame); it returns the image, the next state, the next
+ * moment plane and the noise map (n->device is replaced by t->device).  rtw_stats() is left alone.
+ *   rtw_render_path_guided_*: rtw_render_sequence_* with `d` required.  The steps are the steps with moments; after step v one noise
+ * launch writes view v of an N-view noise region (before the ping-pong reuses that state: stream order); then ONE noise-guided batched
+ * filter pass (rtw_guided_filter_batch_device_*'s launch sequence) over the N accumulated LINEAR images, their features and the N maps;
+ * one D2H.  p->gamma is applied once, by the filter.  View v equals the chain of the single device calls on the bits; rtw_stats() reports
+ * the render's record.
+ *   Refusals, all decided before any HIP call: a null argument -> -1; everything rtw_temporal_device_* refuses, its alignment and aliasing
+ * rules extended to the moment planes, exactly one of d_state_prev / d_moment_prev null -> -2; radius outside 1..3, normal_power_log2
+ * outside 0..7, device < -1, reserved != 0, a sigma_depth that is not finite and positive, min_len not finite or < 1, a misaligned or
+ * aliasing pointer -> -2; the frame rule -> -5; the sequence call refuses everything rtw_render_sequence_* refuses and, with -2, a `t` and
+ * a `d` whose DEMODULATE flags differ (the map is relative to the state's luminance).
+ *   The defaults (radius 2, normal_power_log2 1, sigma_depth 0.1, min_len 4) are UNTUNED beyond the record of DESIGN.md 7.19.  Left out on
+ * purpose: a variance-driven alpha, neighbourhood colour clamping, smoothing of the map, moments for accumulators or
+ * the upsampler, N sequences per launch, device lists, an LDS-tiled window.  Additive to ABI 4: detected by symbol lookup. */
+typedef struct {
+    int32_t radius;             /* 1..3: the spatial estimate's window is (2*radius + 1)^2 */
+    int32_t normal_power_log2;  /* 0..7: m of the window's normal weight */
+    int32_t device;             /* -1 = current */
+    int32_t reserved[3];        /* 0 */
+    double  sigma_depth;        /* > 0, finite: the window's relative-depth weight */
+    double  min_len;            /* >= 1, finite: a history at least this long uses its own moments */
+} rtw_temporal_noise_t;         /* 40 bytes */
+int64_t rtw_history_moment_bytes(int32_t width, int32_t height, int32_t elem_bytes);
+int rtw_history_moments_device_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height,
+                                    const void *d_image, const void *d_features, const void *d_state_prev, const void *d_moment_prev, void *d_state_next,
+                                    void *d_moment_next, void *d_out, void *hip_stream);
+int rtw_history_moments_device_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
+                                    const void *d_image, const void *d_features, const void *d_state_prev, const void *d_moment_prev, void *d_state_next,
+                                    void *d_moment_next, void *d_out, void *hip_stream);
+int rtw_history_noise_device_f32(const rtw_temporal_noise_t *n, int32_t width, int32_t height, const void *d_state, const void *d_moment, void *d_noise,
+                                  void *hip_stream);
+int rtw_history_noise_device_f64(const rtw_temporal_noise_t *n, int32_t width, int32_t height, const void *d_state, const void *d_moment, void *d_noise,
+                                  void *hip_stream);
+int rtw_history_moments_f32(const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width,
+                             int32_t height, const float *image, const float *features, const void *state_prev, const void *moment_prev, void *state_next,
+                             void *moment_next, float *out, float *noise);
+int rtw_history_moments_f64(const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width,
+                             int32_t height, const double *image, const double *features, const void *state_prev, const void *moment_prev, void *state_next,
+                             void *moment_next, double *out, double *noise);
+int rtw_render_path_guided_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
+                                   const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, float *out);
+int rtw_render_path_guided_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
+                                   const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, double *out);
 
 /* Counters/timings of the last render issued from this thread (waits for it to finish). */
 int rtw_stats(rtw_stats_t *out);

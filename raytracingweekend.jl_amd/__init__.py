@@ -35,7 +35,8 @@ from .upsample import (  # noqa: F401
     make_upsample, render_upsampled, render_upsampled_batch, upsample, upsample_batch, upsample_batch_into, upsample_into, upsample_work_bytes,
 )
 from .temporal import (  # noqa: F401
-    TemporalAccumulator, make_temporal, render_sequence, temporal_state_bytes, temporal_step, temporal_step_into,
+    TemporalAccumulator, make_temporal, make_temporal_noise, render_sequence, temporal_moment_bytes, temporal_noise_into, temporal_state_bytes, temporal_step,
+    temporal_step_into, temporal_step_moments, temporal_step_moments_into,
 )
 from . import imageio  # noqa: F401
 
@@ -55,4 +56,5 @@ __all__ = [
     "make_upsample", "upsample_work_bytes", "upsample", "upsample_into", "upsample_batch", "upsample_batch_into", "render_upsampled",
     "render_upsampled_batch",
     "make_temporal", "temporal_state_bytes", "temporal_step", "temporal_step_into", "TemporalAccumulator", "render_sequence",
+    "make_temporal_noise", "temporal_moment_bytes", "temporal_step_moments", "temporal_step_moments_into", "temporal_noise_into",
 ]

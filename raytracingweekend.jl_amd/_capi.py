@@ -34,6 +34,8 @@ SYMBOLS = [
     "rtw_render_upsampled_f32", "rtw_render_upsampled_f64", "rtw_render_upsampled_batch_f32", "rtw_render_upsampled_batch_f64",
     "rtw_temporal_state_bytes", "rtw_temporal_device_f32", "rtw_temporal_device_f64", "rtw_temporal_f32", "rtw_temporal_f64",
     "rtw_render_sequence_f32", "rtw_render_sequence_f64",
+    "rtw_history_moment_bytes", "rtw_history_moments_device_f32", "rtw_history_moments_device_f64", "rtw_history_noise_device_f32", "rtw_history_noise_device_f64",
+    "rtw_history_moments_f32", "rtw_history_moments_f64", "rtw_render_path_guided_f32", "rtw_render_path_guided_f64",
 ]
 
 
@@ -104,6 +106,15 @@ class Temporal(C.Structure):
 
 
 assert C.sizeof(Temporal) == 48
+
+
+class TemporalNoise(C.Structure):
+    """rtw_temporal_noise_t"""
+    _fields_ = [(k, C.c_int32) for k in ("radius", "normal_power_log2", "device")] + [("reserved", C.c_int32 * 3)] + \
+               [("sigma_depth", C.c_double), ("min_len", C.c_double)]
+
+
+assert C.sizeof(TemporalNoise) == 40
 
 _lib = None
 
@@ -188,8 +199,15 @@ def lib():
         getattr(L, "rtw_temporal_device_" + sfx).argtypes = [tp, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_temporal_" + sfx).argtypes = [tp, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_render_sequence_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), tp, C.POINTER(Denoise), ptr]
+        tn = C.POINTER(TemporalNoise)
+        getattr(L, "rtw_history_moments_device_" + sfx).argtypes = [tp, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_history_noise_device_" + sfx).argtypes = [tn, i32, i32, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_history_moments_" + sfx).argtypes = [tp, tn, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_render_path_guided_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), tp, tn, C.POINTER(Denoise), ptr]
     L.rtw_temporal_state_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_temporal_state_bytes.restype = C.c_int64
+    L.rtw_history_moment_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.rtw_history_moment_bytes.restype = C.c_int64
     L.rtw_upsample_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_upsample_work_bytes.restype = C.c_int64
     L.rtw_denoise_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]

@@ -346,11 +346,19 @@ inline int launch_upsample_t(const rtw_upsample_t *u, int32_t lw, int32_t lh, in
 // device nor a pointer -- the parameters and the frame.
 int validate_temporal(const rtw_temporal_t *t, int32_t width, int32_t height, int elem_bytes);
 // launch_temporal: enqueue ONE step (one launch) on `stream` of the current device.  cam_prev and d_state_prev are both null (the first frame)
-// or both given; the states hold rtw_temporal_state_bytes bytes each (16-byte aligned).
-int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream);
-int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream);
-inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f32 *c, const rtw_camera_f32 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st) { return launch_temporal_f32(t, c, cp, w, h, img, feat, sp, sn, out, st); }
-inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f64 *c, const rtw_camera_f64 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st) { return launch_temporal_f64(t, c, cp, w, h, img, feat, sp, sn, out, st); }
+// or both given; the states hold rtw_temporal_state_bytes bytes each (16-byte aligned).  d_moment_next non-null: the step with moments
+// (rtw_history_moments_*), planes of rtw_history_moment_bytes bytes, d_moment_prev null exactly when d_state_prev is.
+int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr);
+int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr);
+inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f32 *c, const rtw_camera_f32 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp = nullptr, void *mn = nullptr) { return launch_temporal_f32(t, c, cp, w, h, img, feat, sp, sn, out, st, mp, mn); }
+inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f64 *c, const rtw_camera_f64 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp = nullptr, void *mn = nullptr) { return launch_temporal_f64(t, c, cp, w, h, img, feat, sp, sn, out, st, mp, mn); }
+// validate_temporal_noise: every check of a noise map (rtw_history_noise_device_*) that needs neither a device nor a pointer.  launch_temporal_noise:
+// enqueue the map (ONE launch) of a state and its moment plane on `stream` of the current device; d_noise: width*height elements of T.
+int validate_temporal_noise(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int elem_bytes);
+int launch_temporal_noise_f32(const rtw_temporal_noise_t *n, int32_t width, int32_t height, const void *d_state, const void *d_moment, void *d_noise, hipStream_t stream);
+int launch_temporal_noise_f64(const rtw_temporal_noise_t *n, int32_t width, int32_t height, const void *d_state, const void *d_moment, void *d_noise, hipStream_t stream);
+inline int launch_temporal_noise_t(const rtw_temporal_noise_t *n, int32_t w, int32_t h, const void *st, const void *mo, float *noise, hipStream_t s) { return launch_temporal_noise_f32(n, w, h, st, mo, noise, s); }
+inline int launch_temporal_noise_t(const rtw_temporal_noise_t *n, int32_t w, int32_t h, const void *st, const void *mo, double *noise, hipStream_t s) { return launch_temporal_noise_f64(n, w, h, st, mo, noise, s); }
 
 // rtw_unit.hip
 int run_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene, const rtw_camera_f32 *cam);

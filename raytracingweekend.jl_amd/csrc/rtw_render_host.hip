@@ -583,6 +583,114 @@ int render_host_sequence(const SceneT *scene, const CamT *cams, int32_t n_views,
     return rc;
 }
 
+// The regions of the temporal paths with moments: TemporalRegions (always with the filter's regions when `filter`), then two moment planes and
+// the noise maps of `frames` views -- each starts on a 16-byte boundary.
+template <typename T> struct MomentRegions : TemporalRegions<T> {
+    size_t mo_b, noise_b, off_mo[2], off_noise, total_m;
+    MomentRegions(int32_t width, int32_t height, size_t frames, bool filter) : TemporalRegions<T>(width, height, frames, filter) {
+        auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
+        mo_b = (size_t)rtw_history_moment_bytes(width, height, (int32_t)sizeof(T));
+        noise_b = (size_t)width * (size_t)height * sizeof(T);
+        off_mo[0] = up(this->total); off_mo[1] = off_mo[0] + mo_b; off_noise = off_mo[1] + mo_b;
+        total_m = off_noise + up(noise_b * frames);
+    }
+};
+
+// One temporal step with moments and the noise map of what it leaves, on host buffers (rtw_history_moments_*): temporal_host's path with two more
+// buffers each way -- two to four H2D, TWO launches (the step, the map), four D2H.  This thread's last render (rtw_stats) is not touched.
+template <typename T, typename CamT>
+int temporal_moments_host(const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const T *image, const T *features,
+                          const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, T *out, T *noise) {
+    if (!t || !n || !cam || !image || !features || !state_next || !moment_next || !out || !noise) return fail(-1, "null argument");
+    if (int rc = validate_temporal(t, width, height, (int)sizeof(T))) return rc;
+    if (int rc = validate_temporal_noise(n, width, height, (int)sizeof(T))) return rc;
+    if ((cam_prev == nullptr) != (state_prev == nullptr)) return fail(-2, "cam_prev and state_prev must both be given or both be null (the first frame)");
+    if ((moment_prev == nullptr) != (state_prev == nullptr)) return fail(-2, "moment_prev and state_prev must both be given or both be null (the first frame)");
+    const MomentRegions<T> R(width, height, 1, false);
+    // the four outputs against each other and against every input
+    const void *outs[4] = {out, state_next, moment_next, noise}, *ins[4] = {image, features, state_prev, moment_prev};
+    const size_t out_b[4] = {R.img_b, R.st_b, R.mo_b, R.noise_b}, in_b[4] = {R.img_b, R.feat_b, R.st_b, R.mo_b};
+    static const char *const names[4] = {"out", "state_next", "moment_next", "noise"};
+    for (int a = 0; a < 4; ++a) {
+        for (int b = a + 1; b < 4; ++b)
+            if (ranges_overlap(outs[a], out_b[a], outs[b], out_b[b])) return fail(-2, "%s and %s may not alias each other", names[a], names[b]);
+        for (int b = 0; b < 4; ++b)
+            if (ins[b] && ranges_overlap(outs[a], out_b[a], ins[b], in_b[b])) return fail(-2, "%s may not alias an input", names[a]);
+    }
+    DeviceGuard guard;
+    HostLease L;
+    if (int rc = acquire_host(t->device, std::vector<unsigned char>(), &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total_m)) return rc;
+    char *base = (char *)hc->d_img;
+    int rc = 0;
+    hipError_t e = hipMemcpyAsync(base, image, R.img_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_feat, features, R.feat_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess && state_prev) e = hipMemcpyAsync(base + R.off_st[0], state_prev, R.st_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess && state_prev) e = hipMemcpyAsync(base + R.off_mo[0], moment_prev, R.mo_b, hipMemcpyHostToDevice, hc->stream);
+    if (e != hipSuccess) rc = fail((int)e, "upload of the temporal step's inputs failed: %s", hipGetErrorString(e));
+    rtw_temporal_noise_t nn = *n;
+    nn.device = hc->device;
+    if (!rc) rc = launch_temporal_t(t, cam, cam_prev, width, height, base, base + R.off_feat, state_prev ? base + R.off_st[0] : nullptr, base + R.off_st[1], base + R.off_acc, hc->stream,
+                                    state_prev ? base + R.off_mo[0] : nullptr, base + R.off_mo[1]);
+    if (!rc) rc = launch_temporal_noise_t(&nn, width, height, base + R.off_st[1], base + R.off_mo[1], (T *)(base + R.off_noise), hc->stream);
+    if (!rc) {
+        e = hipMemcpyAsync(state_next, base + R.off_st[1], R.st_b, hipMemcpyDeviceToHost, hc->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(moment_next, base + R.off_mo[1], R.mo_b, hipMemcpyDeviceToHost, hc->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(noise, base + R.off_noise, R.noise_b, hipMemcpyDeviceToHost, hc->stream);
+        if (e != hipSuccess) rc = fail((int)e, "download of the next state, its moments or the noise map failed: %s", hipGetErrorString(e));
+    }
+    if (!rc) rc = copy_out(hc, base + R.off_acc, out, R.img_b);
+    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    return rc;
+}
+
+// rtw_render_path_guided_*: render_host_sequence with the filter required, the steps with moments, one noise launch behind each step (into
+// view v of the noise region, before the ping-pong reuses that state: stream order) and the NOISE-GUIDED batched filter pass over the N maps;
+// 2 + 2*n_views + 1 + levels launches on the context's stream, ONE D2H.  p->gamma is applied by the filter.  rtw_stats() reports the render's record.
+template <typename T, typename SceneT, typename CamT>
+int render_host_sequence_guided(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t, const rtw_temporal_noise_t *n,
+                                const rtw_denoise_t *d, T *out) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !cams || !t || !n || !d || !out) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = validate_features_batch(cams, n_views, p, 0, 1, out, &nch, &cs)) return rc;
+    if (int rc = validate_filter_batch(d, p->width, p->height, n_views)) return rc;
+    if (int rc = validate_temporal(t, p->width, p->height, (int)sizeof(T))) return rc;
+    if (int rc = validate_temporal_noise(n, p->width, p->height, (int)sizeof(T))) return rc;
+    if (((t->flags & RTW_TEMPORAL_DEMODULATE) != 0) != ((d->flags & RTW_DENOISE_DEMODULATE) != 0))
+        return fail(-2, "the DEMODULATE flags of t and d must agree (the noise map is relative to the state's luminance)");
+    DeviceGuard guard;
+    release_last();
+    const MomentRegions<T> R(p->width, p->height, (size_t)n_views, true);
+    RenderRec *frec = nullptr;
+    CtxPtr fctx;
+    const int rc = render_one_device(p->device, scene, p, R.total_m, R.off_flt, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+        char *base = (char *)hc->d_img;
+        q.gamma = 0;
+        rtw_temporal_t tt = *t;
+        tt.gamma = 0; tt.device = hc->device;
+        rtw_temporal_noise_t nn = *n;
+        nn.device = hc->device;
+        int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
+        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec, &fctx);
+        for (int v = 0; v < n_views && !rc; ++v) {
+            rc = launch_temporal_t(&tt, cams + v, v ? cams + (v - 1) : nullptr, p->width, p->height, base + (size_t)v * R.frame_b, base + R.off_feat + (size_t)v * (R.feat_b / (size_t)n_views),
+                                   v ? base + R.off_st[(v & 1) ^ 1] : nullptr, base + R.off_st[v & 1], base + R.off_acc + (size_t)v * R.frame_b, hc->stream,
+                                   v ? base + R.off_mo[(v & 1) ^ 1] : nullptr, base + R.off_mo[v & 1]);
+            if (!rc) rc = launch_temporal_noise_t(&nn, p->width, p->height, base + R.off_st[v & 1], base + R.off_mo[v & 1], (T *)(base + R.off_noise + (size_t)v * R.noise_b), hc->stream);
+        }
+        if (!rc) {
+            rtw_denoise_t dd = *d;
+            dd.gamma = p->gamma != 0; dd.device = hc->device;
+            rc = launch_denoise_t(&dd, p->width, p->height, n_views, (const T *)(base + R.off_acc), base + R.off_feat, base + R.off_flt, base + R.off_work, hc->stream, base + R.off_noise);
+        }
+        return rc;
+    });
+    if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
+    return rc;
+}
+
 // What an accumulator holds, denoised (rtw_accum_filtered_f32/_f64): the gamma-0 resolve (per tile for an adaptive accumulator), the feature
 // pass over exactly the samples it holds, with `guided` its noise map and the noise-guided filter (else the plain one), all on the
 // accumulator's device in a leased context's buffer and stream, ONE D2H.  The accumulator is only read; every step orders itself behind
@@ -734,6 +842,22 @@ int rtw_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const r
 int rtw_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const double *image, const double *features,
                      const void *state_prev, void *state_next, double *out) {
     return temporal_host<double>(t, cam, cam_prev, width, height, image, features, state_prev, state_next, out);
+}
+int rtw_history_moments_f32(const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height,
+                             const float *image, const float *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, float *out, float *noise) {
+    return temporal_moments_host<float>(t, n, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, noise);
+}
+int rtw_history_moments_f64(const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
+                             const double *image, const double *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, double *out, double *noise) {
+    return temporal_moments_host<double>(t, n, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, noise);
+}
+int rtw_render_path_guided_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
+                                   const rtw_temporal_noise_t *n, const rtw_denoise_t *d, float *out) {
+    return render_host_sequence_guided<float>(scene, cams, batch_views(n_views), seeds, p, t, n, d, out);
+}
+int rtw_render_path_guided_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
+                                   const rtw_temporal_noise_t *n, const rtw_denoise_t *d, double *out) {
+    return render_host_sequence_guided<double>(scene, cams, batch_views(n_views), seeds, p, t, n, d, out);
 }
 int rtw_render_sequence_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                             const rtw_denoise_t *d, float *out) {

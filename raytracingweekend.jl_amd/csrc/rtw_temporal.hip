@@ -1,6 +1,7 @@
 // rtw_temporal.hip -- temporal reprojection (include/rtw_hip.h rtw_temporal_*): the checks that need no device, the host constants of a step,
-// the one launch of its kernel (rtw_temporal.hpp) and the device-resident entry points.
-// (The host-buffer entry points, rtw_temporal_* and rtw_render_sequence_*, live with the other cached-context paths in rtw_render_host.hip.)
+// the one launch of its kernel (rtw_temporal.hpp), the step with moments and the noise map (rtw_history_moments_*, rtw_history_noise_device_*) and the
+// device-resident entry points.
+// (The host-buffer entry points, rtw_temporal_*, rtw_history_moments_* and rtw_render_sequence_*, live with the other cached-context paths in rtw_render_host.hip.)
 #include "rtw_host.hpp"
 #include "rtw_temporal.hpp"
 
@@ -25,11 +26,29 @@ int validate_temporal(const rtw_temporal_t *t, int32_t width, int32_t height, in
 // the state: the planes E and G of 4 elements per pixel and L of one, one behind the other (each starts on a 16-byte boundary)
 static long long state_bytes(int32_t width, int32_t height, int elem_bytes) { return ((long long)width * height * 9 * elem_bytes + 15) & ~15ll; }
 
+// the moment plane: one element per pixel (it starts on a 16-byte boundary like a state)
+static long long moment_bytes(int32_t width, int32_t height, int elem_bytes) { return ((long long)width * height * elem_bytes + 15) & ~15ll; }
+
+// Everything about a noise map (rtw_history_noise_device_*) that is decided without a device and without a pointer.
+int validate_temporal_noise(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int elem_bytes) {
+    if (!n) return fail(-1, "null temporal noise parameters");
+    if (n->radius < 1 || n->radius > 3) return fail(-2, "radius must be in 1..3 (got %d)", n->radius);
+    if (n->normal_power_log2 < 0 || n->normal_power_log2 > 7) return fail(-2, "normal_power_log2 must be in 0..7 (got %d)", n->normal_power_log2);
+    if (n->device < -1) return fail(-2, "bad device %d", n->device);
+    if (n->reserved[0] != 0 || n->reserved[1] != 0 || n->reserved[2] != 0) return fail(-2, "reserved must be 0");
+    if (!(n->sigma_depth > 0) || !std::isfinite(n->sigma_depth)) return fail(-2, "sigma_depth must be finite and positive");
+    if (!(n->min_len >= 1) || !std::isfinite(n->min_len)) return fail(-2, "min_len must be finite and >= 1");
+    if (width < 1 || height < 1) return fail(-2, "width/height must be positive (got %d x %d)", width, height);
+    if (const int64_t rc = rtw_denoise_work_bytes(width, height, elem_bytes); rc < 0) return (int)rc;         // (the denoiser's frame rule)
+    return 0;
+}
+
 // Enqueue one step on `stream` of the current device (validate_temporal has accepted the call).  cam_prev and d_state_prev are both null
-// (the first frame) or both given.
+// (the first frame) or both given.  d_moment_next non-null: the step with moments (rtw_history_moments_*), d_moment_prev null exactly when
+// d_state_prev is.
 template <typename T, typename CamT>
 int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features,
-                    const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream) {
+                    const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev, void *d_moment_next) {
     using V = typename rtw::DnVec<T>::type;
     const long long n_pix = (long long)width * height;
     rtw::TpParams<T> U;
@@ -61,31 +80,75 @@ int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
     struct Events { hipEvent_t e[2] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
     if (profile) { for (hipEvent_t &x : events.e) HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventRecord(events.e[0], stream)); }
     (void)hipGetLastError();
-    if (sp) hipLaunchKernelGGL((rtw::tp_step<T, true>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, (const V *)sp, (const V *)(sp + pb),
-                               (const T *)(sp + 2 * pb), (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out);
+    const T *mp = (const T *)d_moment_prev;
+    T *mn = (T *)d_moment_next;
+    if (mn) {
+        if (sp) hipLaunchKernelGGL((rtw::tp_step<T, true, true>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, (const V *)sp, (const V *)(sp + pb),
+                                   (const T *)(sp + 2 * pb), (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn);
+        else hipLaunchKernelGGL((rtw::tp_step<T, false, true>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, (const V *)nullptr, (const V *)nullptr,
+                                (const T *)nullptr, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, (const T *)nullptr, mn);
+    } else if (sp) hipLaunchKernelGGL((rtw::tp_step<T, true>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, (const V *)sp, (const V *)(sp + pb),
+                                      (const T *)(sp + 2 * pb), (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, (const T *)nullptr, (T *)nullptr);
     else hipLaunchKernelGGL((rtw::tp_step<T, false>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, (const V *)nullptr, (const V *)nullptr,
-                            (const T *)nullptr, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out);
+                            (const T *)nullptr, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, (const T *)nullptr, (T *)nullptr);
     HIP_TRY(hipGetLastError());
     if (profile) {
         float ms = 0;
         HIP_TRY(hipEventRecord(events.e[1], stream));
         HIP_TRY(hipEventSynchronize(events.e[1]));
         HIP_TRY(hipEventElapsedTime(&ms, events.e[0], events.e[1]));
-        fprintf(stderr, "[rtw temporal] %s %dx%d step prev=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, sp ? 1 : 0, ms);
+        fprintf(stderr, "[rtw temporal] %s %dx%d %s prev=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, mn ? "step+moments" : "step", sp ? 1 : 0, ms);
     }
     return 0;
 }
 
-int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st) { return launch_temporal<float>(t, cam, cam_prev, w, h, img, feat, sp, sn, out, st); }
-int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st) { return launch_temporal<double>(t, cam, cam_prev, w, h, img, feat, sp, sn, out, st); }
+int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn) { return launch_temporal<float>(t, cam, cam_prev, w, h, img, feat, sp, sn, out, st, mp, mn); }
+int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn) { return launch_temporal<double>(t, cam, cam_prev, w, h, img, feat, sp, sn, out, st, mp, mn); }
 
-// The device-resident entry point: nulls, the parameters, then the pointers' alignment and aliasing.
+// Enqueue the noise map of a state and its moment plane on `stream` of the current device (validate_temporal_noise has accepted the call): ONE launch.
+template <typename T>
+int launch_temporal_noise(const rtw_temporal_noise_t *n, int32_t width, int32_t height, const void *d_state, const void *d_moment, void *d_noise, hipStream_t stream) {
+    using V = typename rtw::DnVec<T>::type;
+    const long long n_pix = (long long)width * height;
+    rtw::TpNoiseParams<T> U;
+    memset(&U, 0, sizeof U);
+    U.inv_sz = (T)(1.0 / (n->sigma_depth * n->sigma_depth));
+    U.min_len = (T)n->min_len;
+    U.m = n->normal_power_log2; U.r = n->radius;
+    U.W = width; U.H = height;
+    const long long pb = n_pix * 4 * (long long)sizeof(T);
+    const char *sp = (const char *)d_state;
+    const unsigned grid = (unsigned)((n_pix + 255) / 256);
+    // (measurement aid, tools/gpu_temporal_noise.py: events around the kernel, reported on stderr -- this one blocks)
+    static const bool profile = aid_flag("RTW_TEMPORAL_PROFILE");
+    struct Events { hipEvent_t e[2] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
+    if (profile) { for (hipEvent_t &x : events.e) HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventRecord(events.e[0], stream)); }
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((rtw::tp_noise<T>), dim3(grid), dim3(256), 0, stream, U, (const V *)sp, (const V *)(sp + pb), (const T *)(sp + 2 * pb), (const T *)d_moment, (T *)d_noise);
+    HIP_TRY(hipGetLastError());
+    if (profile) {
+        float ms = 0;
+        HIP_TRY(hipEventRecord(events.e[1], stream));
+        HIP_TRY(hipEventSynchronize(events.e[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, events.e[0], events.e[1]));
+        fprintf(stderr, "[rtw temporal] %s %dx%d noise r=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, n->radius, ms);
+    }
+    return 0;
+}
+
+int launch_temporal_noise_f32(const rtw_temporal_noise_t *n, int32_t w, int32_t h, const void *st, const void *mo, void *noise, hipStream_t s) { return launch_temporal_noise<float>(n, w, h, st, mo, noise, s); }
+int launch_temporal_noise_f64(const rtw_temporal_noise_t *n, int32_t w, int32_t h, const void *st, const void *mo, void *noise, hipStream_t s) { return launch_temporal_noise<double>(n, w, h, st, mo, noise, s); }
+
+// The device-resident entry points of a step: nulls, the parameters, then the pointers' alignment and aliasing.  `moments`:
+// rtw_history_moments_device_*, the same with the two moment planes (d_moment_prev null exactly when d_state_prev is).
 template <typename T, typename CamT>
 int temporal_device(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev,
-                    void *d_state_next, void *d_out, void *stream_v) {
-    if (!t || !cam || !d_image || !d_features || !d_state_next || !d_out) return fail(-1, "null argument");
+                    void *d_state_next, void *d_out, void *stream_v, bool moments = false, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr) {
+    if (!t || !cam || !d_image || !d_features || !d_state_next || !d_out || (moments && !d_moment_next)) return fail(-1, "null argument");
     if (int rc = validate_temporal(t, width, height, (int)sizeof(T))) return rc;
     if ((cam_prev == nullptr) != (d_state_prev == nullptr)) return fail(-2, "cam_prev and d_state_prev must both be given or both be null (the first frame)");
+    if (moments && (d_moment_prev == nullptr) != (d_state_prev == nullptr)) return fail(-2, "d_moment_prev and d_state_prev must both be given or both be null (the first frame)");
+    if (moments && (((uintptr_t)d_moment_prev & 15u) || ((uintptr_t)d_moment_next & 15u))) return fail(-2, "both moment planes must be 16-byte aligned");
     if (((uintptr_t)d_features & 15u) || ((uintptr_t)d_state_prev & 15u) || ((uintptr_t)d_state_next & 15u)) return fail(-2, "the feature buffer and both states must be 16-byte aligned");
     if (((uintptr_t)d_image & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
     const size_t n_pix = (size_t)width * (size_t)height;
@@ -95,9 +158,35 @@ int temporal_device(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
         return fail(-2, "d_out may not alias an input");
     if (ranges_overlap(d_state_next, st_b, d_image, img_b) || ranges_overlap(d_state_next, st_b, d_features, feat_b) || (d_state_prev && ranges_overlap(d_state_next, st_b, d_state_prev, st_b)))
         return fail(-2, "d_state_next may not alias an input");
+    if (moments) {
+        const size_t mo_b = (size_t)moment_bytes(width, height, sizeof(T));
+        if (ranges_overlap(d_moment_next, mo_b, d_out, img_b) || ranges_overlap(d_moment_next, mo_b, d_state_next, st_b)) return fail(-2, "d_moment_next may not alias another output");
+        if (ranges_overlap(d_moment_next, mo_b, d_image, img_b) || ranges_overlap(d_moment_next, mo_b, d_features, feat_b) ||
+            (d_state_prev && (ranges_overlap(d_moment_next, mo_b, d_state_prev, st_b) || ranges_overlap(d_moment_next, mo_b, d_moment_prev, mo_b))))
+            return fail(-2, "d_moment_next may not alias an input");
+        if (d_moment_prev && (ranges_overlap(d_moment_prev, mo_b, d_out, img_b) || ranges_overlap(d_moment_prev, mo_b, d_state_next, st_b)))
+            return fail(-2, "d_moment_prev may not alias an output");
+    }
     DeviceGuard guard;
     if (t->device >= 0) HIP_TRY(hipSetDevice(t->device));
-    return launch_temporal<T>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, (hipStream_t)stream_v);
+    return launch_temporal<T>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, (hipStream_t)stream_v, moments ? d_moment_prev : nullptr,
+                              moments ? d_moment_next : nullptr);
+}
+
+// The device-resident entry point of the noise map: nulls, the parameters, then the pointers' alignment and aliasing.
+template <typename T>
+int temporal_noise_device(const rtw_temporal_noise_t *n, int32_t width, int32_t height, const void *d_state, const void *d_moment, void *d_noise, void *stream_v) {
+    if (!n || !d_state || !d_moment || !d_noise) return fail(-1, "null argument");
+    if (int rc = validate_temporal_noise(n, width, height, (int)sizeof(T))) return rc;
+    if (((uintptr_t)d_state & 15u) || ((uintptr_t)d_moment & 15u)) return fail(-2, "the state and the moment plane must be 16-byte aligned");
+    if ((uintptr_t)d_noise & (sizeof(T) - 1)) return fail(-2, "the noise map must be aligned to its element type");
+    const size_t n_pix = (size_t)width * (size_t)height;
+    if (ranges_overlap(d_noise, n_pix * sizeof(T), d_state, (size_t)state_bytes(width, height, sizeof(T))) ||
+        ranges_overlap(d_noise, n_pix * sizeof(T), d_moment, (size_t)moment_bytes(width, height, sizeof(T))))
+        return fail(-2, "d_noise may not alias an input");
+    DeviceGuard guard;
+    if (n->device >= 0) HIP_TRY(hipSetDevice(n->device));
+    return launch_temporal_noise<T>(n, width, height, d_state, d_moment, d_noise, (hipStream_t)stream_v);
 }
 
 }  // namespace rtwh
@@ -110,6 +199,10 @@ int64_t rtw_temporal_state_bytes(int32_t width, int32_t height, int32_t elem_byt
     if (const int64_t rc = rtw_denoise_work_bytes(width, height, elem_bytes); rc < 0) return rc;             // (elem_bytes, the sizes, the denoiser's frame rule)
     return state_bytes(width, height, elem_bytes);
 }
+int64_t rtw_history_moment_bytes(int32_t width, int32_t height, int32_t elem_bytes) {
+    if (const int64_t rc = rtw_denoise_work_bytes(width, height, elem_bytes); rc < 0) return rc;             // (the same checks and codes)
+    return moment_bytes(width, height, elem_bytes);
+}
 int rtw_temporal_device_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height, const void *d_image,
                             const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, void *hip_stream) {
     return temporal_device<float>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, hip_stream);
@@ -117,6 +210,20 @@ int rtw_temporal_device_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, 
 int rtw_temporal_device_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const void *d_image,
                             const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, void *hip_stream) {
     return temporal_device<double>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, hip_stream);
+}
+int rtw_history_moments_device_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height, const void *d_image,
+                                    const void *d_features, const void *d_state_prev, const void *d_moment_prev, void *d_state_next, void *d_moment_next, void *d_out, void *hip_stream) {
+    return temporal_device<float>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, hip_stream, true, d_moment_prev, d_moment_next);
+}
+int rtw_history_moments_device_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const void *d_image,
+                                    const void *d_features, const void *d_state_prev, const void *d_moment_prev, void *d_state_next, void *d_moment_next, void *d_out, void *hip_stream) {
+    return temporal_device<double>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, hip_stream, true, d_moment_prev, d_moment_next);
+}
+int rtw_history_noise_device_f32(const rtw_temporal_noise_t *n, int32_t width, int32_t height, const void *d_state, const void *d_moment, void *d_noise, void *hip_stream) {
+    return temporal_noise_device<float>(n, width, height, d_state, d_moment, d_noise, hip_stream);
+}
+int rtw_history_noise_device_f64(const rtw_temporal_noise_t *n, int32_t width, int32_t height, const void *d_state, const void *d_moment, void *d_noise, void *hip_stream) {
+    return temporal_noise_device<double>(n, width, height, d_state, d_moment, d_noise, hip_stream);
 }
 
 }  // extern "C"

@@ -6,7 +6,15 @@
 //                  from the previous state in global memory (L1 / L2); the blend and the next state follow.  State planes, pixel p at slot p:
 //                  E = (e0, e1, e2, z)   G = (n.x, n.y, n.z, cov; cov = NaN: not valid)   L = len.
 //   HAS_PREV       false: the first frame -- no camera, no state, every pixel resets; the instance reads neither.
+//   MOMENTS        true (rtw_history_moments_*): the step also carries the moment plane M, one element per pixel at slot p -- the running second
+//                  moment of the pixel's (de)modulated luminance: one more element gathered per tap, one more stored.  The image and the three
+//                  state planes are those of the MOMENTS = false instance on the bits; that instance never looks at the two moment pointers.
+//   tp_noise       the per-pixel relative-noise map (rtw_history_noise_device_*) from a state and its moment plane: one pixel per lane, lanes along
+//                  i.  A pixel whose history is at least min_len long divides its temporal variance M - Lm^2 by len; any other pixel estimates
+//                  the variance over its (2r+1)^2 window under tp_tap's weights (sb = 1, zexp = z_p), taps from global memory: the E and the G
+//                  slot, one element of M (Lm_q comes from the E slot) -- two 16-byte slots and one element per tap; len is the centre's alone.
 // No LDS, no atomics, no cross-lane operation; the trip count over the 4 taps is uniform, skipped taps are dropped by selects, as in dn_tap.
+// (tp_noise: lanes with a long history skip the window by a branch of their own; the window's trip count is the radius', uniform.)
 // Every operation is rounded once (the Makefile's -ffp-contract=off -fno-fast-math); divisions and sqrt are the compiler's IEEE ones.
 #pragma once
 #include "rtw_denoise.hpp"
@@ -31,8 +39,9 @@ template <typename T> struct TpSum { T w, e0, e1, e2, l; };
 
 // one tap of the previous state; `ok`: inside the frame and valid.  The data of a tap that is not ok may be anything: selects, not weights, drop it.
 // (g: the pixel's own guides (n, cov); hasP: it is covered; zexp: the depth its point has in the previous view)
-template <typename T, typename V>
-__device__ __forceinline__ void tp_tap(TpSum<T> &a, const V &g, bool hasP, T zexp, const V &eq, const V &gq, T lq, T sb, bool ok, const TpParams<T> &U) {
+// -> the tap's weight w (meaningful only where ok).  U: anything with m and inv_sz (TpParams, TpNoiseParams)
+template <typename T, typename V, typename P>
+__device__ __forceinline__ T tp_tap(TpSum<T> &a, const V &g, bool hasP, T zexp, const V &eq, const V &gq, T lq, T sb, bool ok, const P &U) {
     const T tv = T(1) - dn_abs(g.w - gq.w);
     const T wv = tv > T(0) ? tv : T(0);
     T w = sb * wv;
@@ -49,13 +58,15 @@ __device__ __forceinline__ void tp_tap(TpSum<T> &a, const V &g, bool hasP, T zex
     a.e1 = a.e1 + (ok ? w * eq.y : T(0));
     a.e2 = a.e2 + (ok ? w * eq.z : T(0));
     a.l = a.l + (ok ? w * lq : T(0));
+    return w;
 }
 
 // lane = flat pixel P = j*H + i
-template <typename T, bool HAS_PREV>
+template <typename T, bool HAS_PREV, bool MOMENTS = false>
 __global__ __launch_bounds__(256) void tp_step(TpParams<T> U, const T *__restrict__ image, const typename DnVec<T>::type *__restrict__ feat,
                                                const typename DnVec<T>::type *__restrict__ Ep, const typename DnVec<T>::type *__restrict__ Gp, const T *__restrict__ Lp,
-                                               typename DnVec<T>::type *__restrict__ En, typename DnVec<T>::type *__restrict__ Gn, T *__restrict__ Ln, T *__restrict__ out) {
+                                               typename DnVec<T>::type *__restrict__ En, typename DnVec<T>::type *__restrict__ Gn, T *__restrict__ Ln, T *__restrict__ out,
+                                               const T *__restrict__ Mp, T *__restrict__ Mn) {
     using V = typename DnVec<T>::type;
     const long long H = U.H, W = U.W, n_pix = W * H;
     const long long P = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -87,6 +98,11 @@ __global__ __launch_bounds__(256) void tp_step(TpParams<T> U, const T *__restric
         e0 = c0 / a0; e1 = c1 / a1; e2 = c2 / a2;
     }
     T r0 = e0, r1 = e1, r2 = e2, len = T(1);        // a reset
+    [[maybe_unused]] T y2 = T(0), mom = T(0);       // (MOMENTS) the luminance's square; a reset stores it
+    if constexpr (MOMENTS) {
+        const T y = (e0 + e1) + e2;
+        y2 = y * y; mom = y2;
+    }
     if constexpr (HAS_PREV) {
         // ---- the pixel's own ray in the current camera (the centre of the trace kernel's samples; the lens is ignored)
         const T su = (T((int)j) + T(1.5)) / T((int)W);
@@ -116,6 +132,7 @@ __global__ __launch_bounds__(256) void tp_step(TpParams<T> U, const T *__restric
         const T fx = xs - xf, fy = ys - yf;
         const T zexp = dn_sqrt((d0 * d0 + d1 * d1) + d2 * d2);
         TpSum<T> a = {T(0), T(0), T(0), T(0), T(0)};
+        [[maybe_unused]] T sum_m = T(0);
 #pragma unroll
         for (int b = 0; b <= 1; ++b) {
             const T kx = b ? fx : T(1) - fx;
@@ -127,7 +144,12 @@ __global__ __launch_bounds__(256) void tp_step(TpParams<T> U, const T *__restric
                 const long long q = in ? qj * H + qi : P;
                 const V eq = Ep[q], gq = Gp[q];
                 const T lq = Lp[q];
-                tp_tap<T>(a, g, has, zexp, eq, gq, lq, ky * kx, in && gq.w == gq.w, U);
+                const bool ok = in && gq.w == gq.w;
+                const T w = tp_tap<T>(a, g, has, zexp, eq, gq, lq, ky * kx, ok, U);
+                if constexpr (MOMENTS) {
+                    const T mq = Mp[q];
+                    sum_m = sum_m + (ok ? w * mq : T(0));
+                }
             }
         }
         // ---- blend
@@ -139,6 +161,11 @@ __global__ __launch_bounds__(256) void tp_step(TpParams<T> U, const T *__restric
         const T b0 = h0 + alpha * (e0 - h0), b1 = h1 + alpha * (e1 - h1), b2 = h2 + alpha * (e2 - h2);
         r0 = accept ? b0 : e0; r1 = accept ? b1 : e1; r2 = accept ? b2 : e2;
         len = accept ? nn : T(1);
+        if constexpr (MOMENTS) {
+            const T mh = sum_m / a.w;
+            const T mb = mh + alpha * (y2 - mh);
+            mom = accept ? mb : y2;
+        }
     }
     // ---- end: the image and the next state
     T o0 = r0, o1 = r1, o2 = r2;
@@ -152,6 +179,63 @@ __global__ __launch_bounds__(256) void tp_step(TpParams<T> U, const T *__restric
     g.w = valid ? cov : dn_nan<T>();
     En[P] = en; Gn[P] = g;
     Ln[P] = valid ? len : T(0);
+    if constexpr (MOMENTS) Mn[P] = valid ? mom : T(0);
+}
+
+// what the host derives from rtw_temporal_noise_t, by value
+template <typename T> struct TpNoiseParams {
+    T inv_sz, min_len;                  // 1 / sigma_depth^2, min_len (binary64, rounded to T)
+    int m, r;                           // normal_power_log2, radius
+    int W, H;
+};
+
+// lane = flat pixel P = j*H + i of the state (E, G, L) and the moment plane M -> noise[P]
+template <typename T>
+__global__ __launch_bounds__(256) void tp_noise(TpNoiseParams<T> U, const typename DnVec<T>::type *__restrict__ E, const typename DnVec<T>::type *__restrict__ G, const T *__restrict__ L,
+                                                const T *__restrict__ M, T *__restrict__ noise) {
+    using V = typename DnVec<T>::type;
+    const long long H = U.H, W = U.W, n_pix = W * H;
+    const long long P = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (P >= n_pix) return;
+    long long j, i;
+    if (n_pix < (1ll << 31)) {
+        const unsigned jj = (unsigned)P / (unsigned)H;
+        j = jj; i = (unsigned)P - jj * (unsigned)H;
+    } else {
+        j = P / H; i = P - j * H;
+    }
+    const V e = E[P], g = G[P];
+    const T len = L[P], mp = M[P];
+    const bool valid = g.w == g.w;
+    const T lm = (e.x + e.y) + e.z;
+    const T vt = mp - lm * lm;
+    T var = vt > T(0) ? vt : T(0);
+    if (valid && !(len >= U.min_len)) {
+        // ---- a short history: the variance over the window, tp_tap's weights with sb = 1 and zexp = z_p (the centre tap is one of them)
+        const bool has = g.w > T(0);
+        TpSum<T> a = {T(0), T(0), T(0), T(0), T(0)};       // (a.w = S0; a.l = S1, fed Lm_q in len's place)
+        T s2 = T(0);
+        for (int dj = -U.r; dj <= U.r; ++dj) {
+            for (int di = -U.r; di <= U.r; ++di) {
+                const long long qi = i + di, qj = j + dj;
+                const bool in = qi >= 0 && qi < H && qj >= 0 && qj < W;
+                const long long q = in ? qj * H + qi : P;
+                const V eq = E[q], gq = G[q];
+                const T mq = M[q];
+                const bool ok = in && gq.w == gq.w;
+                const T lq = (eq.x + eq.y) + eq.z;
+                const T w = tp_tap<T>(a, g, has, e.w, eq, gq, lq, T(1), ok, U);
+                s2 = s2 + (ok ? w * mq : T(0));
+            }
+        }
+        const T mu = a.l / a.w;
+        const T vs = s2 / a.w - mu * mu;
+        var = vs > T(0) ? vs : T(0);
+    }
+    const T v = var / len;
+    const T floor_ = T(0.015625);                          // 2^-6
+    const T rho = dn_sqrt(v) / (lm > floor_ ? lm : floor_);
+    noise[P] = valid ? rho : dn_nan<T>();
 }
 
 }  // namespace rtw

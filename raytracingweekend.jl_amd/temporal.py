@@ -7,13 +7,20 @@ in librtw_hip.so; there is no CPU fallback.
 Defaults: ``normal_power_log2=1, sigma_depth=0.1, min_weight=0.25, history_max=16, demodulate=True, gamma=True``.  They are UNTUNED beyond a
 small grid on the CPU witness.  The image handed to a step is a LINEAR one (``render(..., gamma=False)``): the step
 applies gamma itself at the end, and the state stays linear.
+
+Temporal moments (``rtw_history_moments_*``, ``rtw_history_noise_device_*``, ``rtw_render_path_guided_*``): the step can carry the
+second moment of the luminance it accumulates in a plane of its own, and a second kernel turns state and moments into the per-pixel
+relative-noise map the noise-guided filter takes -- a long history uses its own variance, a short one its neighbourhood's
+(``temporal_step_moments``, ``temporal_step_moments_into``, ``temporal_noise_into``, ``TemporalAccumulator(moments=True)``,
+``render_sequence(..., guided=True)``; witness: tests/temporal_noise_ref.py).  Its defaults ``radius=2, normal_power_log2=1,
+sigma_depth=0.1, min_len=4`` are UNTUNED.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _capi
-from .denoise import make_denoise
+from .denoise import GUIDED_SIGMA_COLOR, make_denoise
 from .render import _batch_cameras, _frame_height, _record_stats
 from .structs import Camera
 
@@ -98,21 +105,124 @@ def temporal_step_into(d_out_ptr, d_state_next_ptr, d_image_ptr, d_features_ptr,
                    C.c_void_p(int(stream))))
 
 
+_NOISE_KEYS = ("radius", "normal_power_log2", "sigma_depth", "min_len")
+
+
+def make_temporal_noise(radius=2, normal_power_log2=1, sigma_depth=0.1, min_len=4.0, device=-1):
+    """-> the ``rtw_temporal_noise_t`` of these keywords: the window of the spatial estimate and the history length from which a pixel's own
+    moments are used.  The defaults are untuned beyond the record of DESIGN.md section 7.19."""
+    return _capi.TemporalNoise(int(radius), int(normal_power_log2), int(device), (C.c_int32 * 3)(0, 0, 0), float(sigma_depth), float(min_len))
+
+
+def _noise_arg(noise):
+    """None / True / a dict of ``make_temporal_noise``'s keywords -> the keywords"""
+    nk = {} if noise is None or noise is True else dict(noise)
+    if set(nk) - set(_NOISE_KEYS):
+        raise ValueError(f"noise takes the keywords {_NOISE_KEYS}, got {sorted(set(nk) - set(_NOISE_KEYS))}")
+    return nk
+
+
+def temporal_moment_bytes(image_width, image_height, elem_type=np.float32):
+    """bytes of one moment plane: W*H elements rounded up to 16 bytes"""
+    n = _capi.lib().rtw_history_moment_bytes(int(image_width), int(image_height), np.dtype(elem_type).itemsize)
+    if n < 0:
+        _capi.check(int(n))
+    return int(n)
+
+
+def temporal_step_moments(image, features, cam, state=None, moment=None, cam_prev=None, *, noise=None, **params):
+    """``temporal_step`` with second moments and the noise map of what it leaves (rtw_history_moments_*): ``state``, ``moment`` and
+    ``cam_prev`` are what the previous call returned and its camera (all None: the first frame).  -> ``(out [H, W, 3], next_state,
+    next_moment, noise_map [H, W])``; a moment plane is a flat array of ``temporal_moment_bytes`` bytes, pixel (i, j) at j*H + i; the map is
+    the per-pixel relative noise ``denoise``'s guided form takes (NaN where the pixel is not valid).  ``noise``: a dict of
+    ``make_temporal_noise``'s keywords ``radius, normal_power_log2, sigma_depth, min_len`` (the defaults are untuned); other keywords:
+    ``make_temporal``.  Blocking; ``last_stats()`` is left as it was."""
+    if isinstance(features, dict):
+        features = features["raw"]
+    image, features = np.asarray(image), np.asarray(features)
+    T = image.dtype
+    if T not in (np.dtype(np.float32), np.dtype(np.float64)) or features.dtype != T:
+        raise TypeError("image and features must both be float32 or both float64")
+    if image.ndim != 3 or image.shape[-1] != 3 or features.shape != image.shape[:-1] + (8,):
+        raise ValueError(f"expected image [H, W, 3] and features [H, W, 8], got {image.shape} and {features.shape}")
+    if 0 in image.shape:
+        raise ValueError("empty image")
+    if not ((state is None) == (cam_prev is None) == (moment is None)):
+        raise ValueError("state, moment and cam_prev must all be given or all be None (the first frame)")
+    H, W = image.shape[:2]
+    n_state = temporal_state_bytes(W, H, T) // T.itemsize
+    n_mom = temporal_moment_bytes(W, H, T) // T.itemsize
+    Cm = _camera_arg(cam, T.type, "cam")
+    Cp = None
+    if state is not None:
+        state, moment = np.ascontiguousarray(state), np.ascontiguousarray(moment)
+        if state.dtype != T or state.shape != (n_state,):
+            raise ValueError(f"state must be a flat {T.name} array of {n_state} elements, got {state.dtype.name} {state.shape}")
+        if moment.dtype != T or moment.shape != (n_mom,):
+            raise ValueError(f"moment must be a flat {T.name} array of {n_mom} elements, got {moment.dtype.name} {moment.shape}")
+        Cp = C.byref(_camera_arg(cam_prev, T.type, "cam_prev"))
+    tp = make_temporal(**params)
+    tn = make_temporal_noise(**_noise_arg(noise))
+    img = np.ascontiguousarray(np.swapaxes(image, 0, 1))             # the library's layout: pixel (i, j) at j*H + i
+    feat = np.ascontiguousarray(np.swapaxes(features, 0, 1))
+    out = np.empty((W, H, 3), dtype=T)
+    nxt, mom, rho = np.zeros(n_state, dtype=T), np.zeros(n_mom, dtype=T), np.empty((W, H), dtype=T)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    fn = getattr(_capi.lib(), "rtw_history_moments_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(C.byref(tp), C.byref(tn), C.byref(Cm), Cp, W, H, ptr(img), ptr(feat), ptr(state), ptr(moment), ptr(nxt), ptr(mom), ptr(out), ptr(rho)))
+    return np.swapaxes(out, 0, 1), nxt, mom, np.swapaxes(rho, 0, 1)
+
+
+def temporal_step_moments_into(d_out_ptr, d_state_next_ptr, d_moment_next_ptr, d_image_ptr, d_features_ptr, cam, image_width, image_height, *, d_state_prev_ptr=None,
+                               d_moment_prev_ptr=None, cam_prev=None, elem_type=np.float32, stream=0, **params):
+    """The device-resident step with moments (rtw_history_moments_device_*): ``temporal_step_into`` with the two moment planes, DEVICE
+    pointers to ``temporal_moment_bytes`` bytes (16-byte aligned).  ``d_state_prev_ptr``, ``d_moment_prev_ptr`` and ``cam_prev`` all None:
+    the first frame.  Keywords: ``make_temporal``."""
+    if not ((d_state_prev_ptr is None) == (cam_prev is None) == (d_moment_prev_ptr is None)):
+        raise ValueError("d_state_prev_ptr, d_moment_prev_ptr and cam_prev must all be given or all be None (the first frame)")
+    T = np.dtype(elem_type).type
+    Cm = _camera_arg(cam, T, "cam")
+    Cp = C.byref(_camera_arg(cam_prev, T, "cam_prev")) if cam_prev is not None else None
+    tp = make_temporal(**params)
+    vp = lambda p: C.c_void_p(int(p)) if p is not None else None
+    fn = getattr(_capi.lib(), "rtw_history_moments_device_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(C.byref(tp), C.byref(Cm), Cp, int(image_width), int(image_height), vp(d_image_ptr), vp(d_features_ptr), vp(d_state_prev_ptr), vp(d_moment_prev_ptr),
+                   vp(d_state_next_ptr), vp(d_moment_next_ptr), vp(d_out_ptr), C.c_void_p(int(stream))))
+
+
+def temporal_noise_into(d_noise_ptr, d_state_ptr, d_moment_ptr, image_width, image_height, *, elem_type=np.float32, stream=0, **noise):
+    """The device-resident noise map (rtw_history_noise_device_*): enqueue the map of a state and its moment plane on ``stream``.  All are
+    DEVICE pointers; the map is H*W elements, pixel (i, j) at j*H + i -- what ``guided_filter``'s device forms read.  Keywords:
+    ``make_temporal_noise`` (the defaults are untuned)."""
+    tn = make_temporal_noise(**noise)
+    T = np.dtype(elem_type).type
+    fn = getattr(_capi.lib(), "rtw_history_noise_device_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(C.byref(tn), int(image_width), int(image_height), C.c_void_p(int(d_state_ptr)), C.c_void_p(int(d_moment_ptr)), C.c_void_p(int(d_noise_ptr)),
+                   C.c_void_p(int(stream))))
+
+
 class TemporalAccumulator:
     """The history of one camera path on one device: two device states (torch tensors; torch is the package's plumbing for device memory)
     and the previous frame's camera.  ``step`` enqueues one ``temporal_step_into`` and swaps the states; ``reset`` forgets the history, so
-    the next step is a first frame.  Steps of one accumulator must be ordered on the device (one stream, or events between streams)."""
+    the next step is a first frame.  Steps of one accumulator must be ordered on the device (one stream, or events between streams).
+    ``moments=True``: the steps carry second moments (``temporal_step_moments_into``, two moment planes besides the states) and
+    ``noise_into`` enqueues the noise map of the state the last step left."""
 
-    def __init__(self, image_width, image_height, *, elem_type=np.float32, device=0, **params):
+    def __init__(self, image_width, image_height, *, elem_type=np.float32, device=0, moments=False, **params):
         import torch
         make_temporal(**params)                                    # (the keywords, checked now)
         self.width, self.height, self.elem_type = int(image_width), int(image_height), np.dtype(elem_type).type
         if self.width < 1 or self.height < 1:
             raise ValueError(f"empty frame {self.width} x {self.height}")
         self.params = dict(params, device=int(device))
+        self.moments = bool(moments)
         n = temporal_state_bytes(self.width, self.height, self.elem_type) // np.dtype(self.elem_type).itemsize
         dt = torch.float64 if _capi.is_f64(self.elem_type) else torch.float32
         self._states = [torch.zeros(n, dtype=dt, device=f"cuda:{int(device)}") for _ in range(2)]
+        self._moments = None
+        if self.moments:
+            nm = temporal_moment_bytes(self.width, self.height, self.elem_type) // np.dtype(self.elem_type).itemsize
+            self._moments = [torch.zeros(nm, dtype=dt, device=f"cuda:{int(device)}") for _ in range(2)]
         torch.cuda.synchronize(int(device))
         self._cur = 0                                              # the state the NEXT step writes
         self._cam_prev = None
@@ -131,31 +241,64 @@ class TemporalAccumulator:
         if not isinstance(cam, Camera):
             raise TypeError("cam must be a Camera")
         prev = self._states[self._cur ^ 1].data_ptr() if self._cam_prev is not None else None
-        temporal_step_into(d_out_ptr, self._states[self._cur].data_ptr(), d_image_ptr, d_features_ptr, cam, self.width, self.height, d_state_prev_ptr=prev,
-                           cam_prev=self._cam_prev, elem_type=self.elem_type, stream=stream, **self.params)
+        if self.moments:
+            mprev = self._moments[self._cur ^ 1].data_ptr() if self._cam_prev is not None else None
+            temporal_step_moments_into(d_out_ptr, self._states[self._cur].data_ptr(), self._moments[self._cur].data_ptr(), d_image_ptr, d_features_ptr, cam, self.width,
+                                       self.height, d_state_prev_ptr=prev, d_moment_prev_ptr=mprev, cam_prev=self._cam_prev, elem_type=self.elem_type, stream=stream, **self.params)
+        else:
+            temporal_step_into(d_out_ptr, self._states[self._cur].data_ptr(), d_image_ptr, d_features_ptr, cam, self.width, self.height, d_state_prev_ptr=prev,
+                               cam_prev=self._cam_prev, elem_type=self.elem_type, stream=stream, **self.params)
         self._cur ^= 1
         self._cam_prev = cam
         self.frames += 1
 
+    @property
+    def moment(self):
+        """the torch tensor that holds the moment plane the last step left (None without ``moments=True``, before the first step or after ``reset``)"""
+        return self._moments[self._cur ^ 1] if self.moments and self._cam_prev is not None else None
 
-def render_sequence(scene, cams, image_width=400, n_samples=1, *, seeds=None, denoise=None, depth=16, seed=1, n_chunks=0, device=-1, gamma=True, group_cull=False,
-                    scan_valu=False, numerics=None, normal_power_log2=1, sigma_depth=0.1, min_weight=0.25, history_max=16.0, demodulate=True):
+    def noise_into(self, d_noise_ptr, stream=0, **noise):
+        """enqueue the noise map (``temporal_noise_into``) of the state and moments the last step left; keywords: ``make_temporal_noise``"""
+        if not self.moments:
+            raise ValueError("noise_into needs an accumulator made with moments=True")
+        if self._cam_prev is None:
+            raise ValueError("noise_into before the first step: there is no state yet")
+        temporal_noise_into(d_noise_ptr, self.state.data_ptr(), self.moment.data_ptr(), self.width, self.height, elem_type=self.elem_type, stream=stream,
+                            device=self.params["device"], **noise)
+
+
+def render_sequence(scene, cams, image_width=400, n_samples=1, *, seeds=None, denoise=None, guided=None, depth=16, seed=1, n_chunks=0, device=-1, gamma=True,
+                    group_cull=False, scan_valu=False, numerics=None, normal_power_log2=1, sigma_depth=0.1, min_weight=0.25, history_max=16.0, demodulate=True):
     """N cameras along a path over one scene with history reuse, in one call on the device (rtw_render_sequence_*): one batched render, one
     batched feature pass, ``len(cams)`` temporal steps in order (view 0 is a first frame) and, with ``denoise`` (True, or a dict of
     ``make_denoise``'s keywords ``levels, normal_power_log2, sigma_color, sigma_depth, demodulate``), one batched filter pass over the
-    accumulated images.  ``gamma`` is applied once, by the last stage.  Returns ``img[v, i, j, :]``; ``last_stats()`` reports the render.
+    accumulated images.  ``guided`` (True, or a dict of ``make_temporal_noise``'s keywords ``radius, normal_power_log2, sigma_depth,
+    min_len``; rtw_render_path_guided_*): the steps carry second moments, a noise map follows each step and the filter pass is the
+    noise-guided one over those maps -- ``denoise`` is then required (None: its defaults, ``sigma_color`` defaults to ``GUIDED_SIGMA_COLOR``) and its
+    ``demodulate`` must be the steps'.
+    ``gamma`` is applied once, by the last stage.  Returns ``img[v, i, j, :]``; ``last_stats()`` reports the render.
     ``seeds``: a sequence of ``len(cams)`` ints (None: ``seed`` for every view).  The temporal defaults are untuned (see the module's docstring)."""
     from .structs import flatten_scene
     cams, T = _batch_cameras(cams)
     n = len(cams)
     sd = _capi.make_seeds(seed if seeds is None else seeds, n)
     height = _frame_height(image_width, n_samples)
-    D = None
+    D = N = None
+    if guided:
+        N = make_temporal_noise(**_noise_arg(guided))
+        if denoise is None:
+            denoise = True
+        elif not denoise:
+            raise ValueError("guided=... filters with the noise map: denoise may not be switched off")
     if denoise:
         dk = {} if denoise is True else dict(denoise)
         if set(dk) - set(_DENOISE_KEYS):
             raise ValueError(f"denoise takes the keywords {_DENOISE_KEYS}, got {sorted(set(dk) - set(_DENOISE_KEYS))}")
+        if guided:
+            dk.setdefault("sigma_color", GUIDED_SIGMA_COLOR)       # (there it counts estimated standard deviations: denoise.py)
         D = make_denoise(gamma=gamma, **dk)
+        if guided and bool(dk.get("demodulate", True)) != bool(demodulate):
+            raise ValueError("guided=...: denoise's demodulate must equal the steps' (the noise map is relative to the state's luminance)")
     tp = make_temporal(normal_power_log2, sigma_depth, min_weight, history_max, demodulate, gamma)
     L = _capi.lib()
     flat = scene if isinstance(scene, dict) else flatten_scene(scene, T)
@@ -163,8 +306,13 @@ def render_sequence(scene, cams, image_width=400, n_samples=1, *, seeds=None, de
     P = _capi.make_params(image_width, height, n_samples, depth, seed, n_chunks, 0, 1, device, 1 if gamma else 0,
                           (_capi.FLAG_GROUP_CULL if group_cull else 0) | (_capi.FLAG_SCAN_VALU if scan_valu else 0), numerics=numerics)
     out = np.empty(n * height * int(image_width) * 3, dtype=T)
-    fn = getattr(L, "rtw_render_sequence_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(S), _capi.make_cameras(cams, T), n, sd, C.byref(P), C.byref(tp), C.byref(D) if D is not None else None, out.ctypes.data_as(C.c_void_p)))
+    sfx = "f64" if _capi.is_f64(T) else "f32"
+    if N is not None:
+        _capi.check(getattr(L, "rtw_render_path_guided_" + sfx)(C.byref(S), _capi.make_cameras(cams, T), n, sd, C.byref(P), C.byref(tp), C.byref(N), C.byref(D),
+                                                                    out.ctypes.data_as(C.c_void_p)))
+    else:
+        _capi.check(getattr(L, "rtw_render_sequence_" + sfx)(C.byref(S), _capi.make_cameras(cams, T), n, sd, C.byref(P), C.byref(tp), C.byref(D) if D is not None else None,
+                                                             out.ctypes.data_as(C.c_void_p)))
     del keep
     _record_stats(L)
     return out.reshape(n, int(image_width), height, 3).transpose(0, 2, 1, 3)
