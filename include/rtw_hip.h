@@ -950,6 +950,81 @@ int rtw_render_path_guided_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 
 int rtw_render_path_guided_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
                                    const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, double *out);
 
+/* Present stage: display-ready 8-bit frames from the device.  Every pipeline above ends in T elements in the column-major layout of the
+ * render entry points; a window, a PNG or a video encoder wants 8-bit rows.  One kernel clips, rounds, packs and transposes in HBM, and the
+ * D2H behind it moves 3 or 4 bytes per pixel instead of 12 or 24.
+ *
+ * The definition.  Input: a frame of H*W*3 elements of T in the layout of the render entry points, pixel (i, j) (0-based row, column) at
+ * (j*H + i)*3; a batch is n_views such frames one behind the other.  Output: H*W*C bytes, ROW-major: channel k of pixel (i, j) at
+ * (i*W + j)*C + k, C = channels (3 or 4); rows are tightly packed, row 0 is the row a PNG or PPM writer writes first; a batch is n_views
+ * frames of H*W*C bytes one behind the other, and rtw_present_bytes returns the total (n_views == 0 means one frame; < 0: an error code).
+ *   Per channel k < 3, on the input element x, every operation in binary64 and rounded once (no FMA), whatever T is:
+ *     1. v = (double)x                                  (exact for both T)
+ *     2. if v is NaN the byte is nan_rgb[k] and steps 3 - 7 are skipped   (decided per channel, not per pixel)
+ *     3. v = v * exposure
+ *     4. v = min(max(v, 0), 1)                          (+inf gives 1; -inf and -0.0 give 0)
+ *     5. with RTW_PRESENT_SQRT: v = sqrt(v), the correctly rounded IEEE one   (the reference's gamma 2, for linear inputs such as a temporal state)
+ *     6. y = v * 255.0
+ *     7. without RTW_PRESENT_DITHER: the byte is q = rint(y), ties to even
+ *        with RTW_PRESENT_DITHER:    q = min(floor(y + t), 255),  t = (B(i mod 8, j mod 8) + 0.5) / 64   (exact in binary64)
+ *           B(r, c) = sum over b = 0..2 of  (((r^c)>>b)&1) << (5-2b)  |  ((r>>b)&1) << (4-2b)
+ *        the standard 8 x 8 Bayer index matrix (its first row is 0 32 8 40 2 34 10 42); the same t serves all three channels of a pixel
+ *        and every view of a batch.
+ *   With RTW_PRESENT_BGR channels 0 and 2 of the output are swapped; that applies to nan_rgb too, which is given in R, G, B order.  With
+ * C = 4 byte 3 is 255.
+ *   With exposure = 1, no flags and nan_rgb = {0, 0, 0} the output is imageio.to_u8 -- rint(clip(x, 0, 1) * 255) in binary64, NaN -> 0, the
+ * 8-bit image the project already defines -- of the same frame on the bits.  (tests/present_ref.py restates the definition on the CPU and
+ * the device agrees on the bytes.)
+ *
+ * rtw_present_device_* / rtw_present_batch_device_*: ONE launch, asynchronous on `hip_stream` (a hipStream_t as void*; NULL = the null stream)
+ * of the device p->device (-1: the current one).  `d_image` is aligned to T, `d_out` to 4 bytes; the output may not overlap the input.
+ * Neither changes what rtw_stats() reports.
+ *   rtw_present_*: the host-buffer form of one frame, blocking, on the per-device stream and buffer cache of rtw_render_f32: the frame in,
+ * the kernel, one D2H of the bytes.
+ *   rtw_render_presented_* / rtw_render_presented_batch_*: render and present in one call on the cached context's stream.  `d` NULL: the
+ * render of rtw_render_f32 / rtw_render_batch_f32 with p->gamma as given (whole frames on one device: what a feature render of `params`
+ * refuses is refused).  `d` non-NULL: exactly what rtw_render_denoised_* / rtw_render_filtered_batch_* do, up to their device image.  Then
+ * the present kernel (p->device replaced by params->device) and ONE D2H of rtw_present_bytes bytes: no float frame crosses the bus.
+ * rtw_stats() reports the render as it does after those calls; view v of the batch equals the single call on the bits.
+ *   Refusals, all decided before any HIP call: a null argument -> -1 (`d` may be NULL); channels other than 3 or 4, unknown flag bits,
+ * reserved != 0, an exposure that is not finite and positive, width or height < 1, n_views < 1 on a batch call (< 0 for rtw_present_bytes),
+ * device < -1, a d_out that is not 4-byte aligned, a d_image that is not aligned to T, an output that overlaps the input -> -2; 2^31 tiles
+ * of 64 x 64 pixels or more over all views (what the launch's index arithmetic covers) -> -5; the render-and-present calls additionally
+ * refuse everything their render (and, with `d`, their filter) refuses.
+ *   Left out on purpose: the sRGB transfer curve (its pow is not correctly rounded, so a device and a numpy witness
+ * could not be held to the same bits), a row pitch, a vertical flip, 16-bit output, one-call forms for the accumulator, the upsampler and
+ * the sequences (their device-resident stages compose with rtw_present_device_*), a host-buffer batch form.
+ * Additive to ABI 4: detected by symbol lookup. */
+#define RTW_PRESENT_DITHER 1       /* ordered dither (8 x 8 Bayer) instead of round-to-nearest */
+#define RTW_PRESENT_BGR 2          /* bytes in B, G, R order */
+#define RTW_PRESENT_SQRT 4         /* sqrt per channel after the clamp: gamma 2 for a linear input */
+typedef struct {
+    int32_t channels;           /* 3 or 4: bytes per pixel (byte 3 = 255) */
+    int32_t flags;              /* RTW_PRESENT_* */
+    int32_t device;             /* -1 = current */
+    uint8_t nan_rgb[3];         /* the bytes of a NaN channel, in R, G, B order */
+    uint8_t reserved0;          /* 0 */
+    double  exposure;           /* > 0, finite: multiplies every channel before the clamp */
+    int32_t reserved[2];        /* 0 */
+} rtw_present_t;                /* 32 bytes */
+int64_t rtw_present_bytes(int32_t width, int32_t height, int32_t channels, int32_t n_views);
+int rtw_present_device_f32(const rtw_present_t *p, int32_t width, int32_t height, const void *d_image, void *d_out, void *hip_stream);
+int rtw_present_device_f64(const rtw_present_t *p, int32_t width, int32_t height, const void *d_image, void *d_out, void *hip_stream);
+int rtw_present_batch_device_f32(const rtw_present_t *p, int32_t width, int32_t height, int32_t n_views, const void *d_images, void *d_out,
+                                 void *hip_stream);
+int rtw_present_batch_device_f64(const rtw_present_t *p, int32_t width, int32_t height, int32_t n_views, const void *d_images, void *d_out,
+                                 void *hip_stream);
+int rtw_present_f32(const rtw_present_t *p, int32_t width, int32_t height, const float *image, uint8_t *out);
+int rtw_present_f64(const rtw_present_t *p, int32_t width, int32_t height, const double *image, uint8_t *out);
+int rtw_render_presented_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *params, const rtw_denoise_t *d /* may be NULL */,
+                             const rtw_present_t *p, uint8_t *out);
+int rtw_render_presented_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *params, const rtw_denoise_t *d /* may be NULL */,
+                             const rtw_present_t *p, uint8_t *out);
+int rtw_render_presented_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds,
+                                   const rtw_params *params, const rtw_denoise_t *d /* may be NULL */, const rtw_present_t *p, uint8_t *out);
+int rtw_render_presented_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds,
+                                   const rtw_params *params, const rtw_denoise_t *d /* may be NULL */, const rtw_present_t *p, uint8_t *out);
+
 /* Counters/timings of the last render issued from this thread (waits for it to finish). */
 int rtw_stats(rtw_stats_t *out);
 

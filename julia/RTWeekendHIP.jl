@@ -618,4 +618,66 @@ function render_upsampled(scene::HittableList, cam::Camera{T}, image_width=400, 
     img
 end
 
+# rtw_present_t (include/rtw_hip.h): 32 bytes
+struct CPresent
+    channels::Int32; flags::Int32; device::Int32
+    nan_rgb::NTuple{3,UInt8}; reserved0::UInt8
+    exposure::Float64
+    reserved::NTuple{2,Int32}
+end
+
+"""
+    render_u8(scene, cam, image_width=400, n_samples=1; channels=3, dither=false, bgr=false, sqrt=false, exposure=1.0, nan_rgb=(0, 0, 0),
+              denoise=false, depth=16, seed=1, n_chunks=0, device=-1, numerics=:reference, group_cull=false, scan_valu=false,
+              levels=3, normal_power_log2=1, sigma_color=0.5, sigma_depth=0.1, demodulate=true)
+
+`render` (with `denoise=true`: `render_denoised`) and the present stage in one call (rtw_render_presented_f32/_f64): the float frame stays
+on the device, where it is clipped, rounded in binary64 (ties to even; `dither=true`: an 8 × 8 ordered dither), packed and transposed, and
+only the bytes come back.  Returns an `Array{UInt8,3}` of size `(channels, image_width, image_height)`: its memory is the row-major frame
+a PNG or video writer takes -- channel k of pixel (i, j), 0-based, at `(i*image_width + j)*channels + k`; with the defaults the bytes are
+`round(clamp(x, 0, 1) * 255)` of `render`'s image (the definition is in include/rtw_hip.h).
+(Not executed in this repository: there is no `julia` in its build image; tests/test_gpu_present.py drives the same entry point.)
+"""
+function render_u8(scene::HittableList, cam::Camera{T}, image_width=400, n_samples=1;
+                   channels=3, dither=false, bgr=false, sqrt=false, exposure=1.0, nan_rgb=(0, 0, 0), denoise=false,
+                   depth=16, seed=1, n_chunks=0, device=-1, numerics=:reference, group_cull=false, scan_valu=false,
+                   levels=3, normal_power_log2=1, sigma_color=0.5, sigma_depth=0.1, demodulate=true) where T <: Union{Float32,Float64}
+    numerics in (:reference, :contract, :reference_fma2) || throw(ArgumentError("numerics must be :reference, :contract or :reference_fma2"))
+    channels in (3, 4) || throw(ArgumentError("channels must be 3 or 4"))
+    nflags = numerics === :contract ? 32 : numerics === :reference_fma2 ? 128 : 0
+    image_height = image_width ÷ (16//9)
+    n = length(scene)
+    cx = Vector{T}(undef, n); cy = similar(cx); cz = similar(cx); r = similar(cx)
+    ar = similar(cx); ag = similar(cx); ab = similar(cx); param = similar(cx)
+    kind = Vector{Int32}(undef, n)
+    for (i, h) in enumerate(scene)
+        h isa Sphere{T} || throw(ArgumentError("scene[$i] is $(typeof(h)); the HIP path takes Sphere{$T} only"))
+        cx[i], cy[i], cz[i] = h.center
+        r[i] = h.radius
+        kind[i] = matkind(h.mat)
+        ar[i], ag[i], ab[i] = albedo(h.mat)
+        param[i] = matparam(h.mat)
+    end
+    bytes = Array{UInt8,3}(undef, channels, image_width, image_height)
+    ccam = Ref(CCamera(cam))
+    den = Ref(CDenoise(levels, normal_power_log2, demodulate ? 1 : 0, 1, -1, 0, sigma_color, sigma_depth))
+    pres = Ref(CPresent(channels, (dither ? 1 : 0) | (bgr ? 2 : 0) | (sqrt ? 4 : 0), -1, UInt8.(Tuple(nan_rgb)), 0x00, exposure, (Int32(0), Int32(0))))
+    rc = GC.@preserve cx cy cz r kind ar ag ab param bytes den begin
+        params = Ref(CParams(image_width, image_height, n_samples, depth, seed, n_chunks, 0, 1, device, 1,
+                             (group_cull ? 1 : 0) | (scan_valu ? 4 : 0) | nflags, 0, 0, Ptr{Int32}(C_NULL)))
+        cscene = Ref(CScene{T}(n, pointer(cx), pointer(cy), pointer(cz), pointer(r), pointer(kind),
+                               pointer(ar), pointer(ag), pointer(ab), pointer(param)))
+        pden = denoise ? Base.unsafe_convert(Ptr{CDenoise}, den) : Ptr{CDenoise}(C_NULL)     # NULL: no filter
+        if T === Float32
+            ccall((:rtw_render_presented_f32, LIB), Cint, (Ref{CScene{Float32}}, Ref{CCamera{Float32}}, Ref{CParams}, Ptr{CDenoise}, Ref{CPresent}, Ptr{UInt8}),
+                  cscene, ccam, params, pden, pres, pointer(bytes))
+        else
+            ccall((:rtw_render_presented_f64, LIB), Cint, (Ref{CScene{Float64}}, Ref{CCamera{Float64}}, Ref{CParams}, Ptr{CDenoise}, Ref{CPresent}, Ptr{UInt8}),
+                  cscene, ccam, params, pden, pres, pointer(bytes))
+        end
+    end
+    rc == 0 || error("librtw_hip: error $rc: $(last_error())")
+    bytes
+end
+
 end # module

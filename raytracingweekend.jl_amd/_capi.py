@@ -36,6 +36,9 @@ SYMBOLS = [
     "rtw_render_sequence_f32", "rtw_render_sequence_f64",
     "rtw_history_moment_bytes", "rtw_history_moments_device_f32", "rtw_history_moments_device_f64", "rtw_history_noise_device_f32", "rtw_history_noise_device_f64",
     "rtw_history_moments_f32", "rtw_history_moments_f64", "rtw_render_path_guided_f32", "rtw_render_path_guided_f64",
+    "rtw_present_bytes", "rtw_present_device_f32", "rtw_present_device_f64", "rtw_present_batch_device_f32", "rtw_present_batch_device_f64",
+    "rtw_present_f32", "rtw_present_f64", "rtw_render_presented_f32", "rtw_render_presented_f64", "rtw_render_presented_batch_f32",
+    "rtw_render_presented_batch_f64",
 ]
 
 
@@ -115,6 +118,15 @@ class TemporalNoise(C.Structure):
 
 
 assert C.sizeof(TemporalNoise) == 40
+
+
+class Present(C.Structure):
+    """rtw_present_t"""
+    _fields_ = [(k, C.c_int32) for k in ("channels", "flags", "device")] + [("nan_rgb", C.c_uint8 * 3), ("reserved0", C.c_uint8), ("exposure", C.c_double),
+                                                                            ("reserved", C.c_int32 * 2)]
+
+
+assert C.sizeof(Present) == 32
 
 _lib = None
 
@@ -204,6 +216,14 @@ def lib():
         getattr(L, "rtw_history_noise_device_" + sfx).argtypes = [tn, i32, i32, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_history_moments_" + sfx).argtypes = [tp, tn, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_render_path_guided_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), tp, tn, C.POINTER(Denoise), ptr]
+        pr, dn = C.POINTER(Present), C.POINTER(Denoise)
+        getattr(L, "rtw_present_device_" + sfx).argtypes = [pr, i32, i32, ptr, ptr, ptr]
+        getattr(L, "rtw_present_batch_device_" + sfx).argtypes = [pr, i32, i32, i32, ptr, ptr, ptr]
+        getattr(L, "rtw_present_" + sfx).argtypes = [pr, i32, i32, ptr, ptr]
+        getattr(L, "rtw_render_presented_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), C.POINTER(Params), dn, pr, ptr]
+        getattr(L, "rtw_render_presented_batch_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), dn, pr, ptr]
+    L.rtw_present_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.rtw_present_bytes.restype = C.c_int64
     L.rtw_temporal_state_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_temporal_state_bytes.restype = C.c_int64
     L.rtw_history_moment_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
@@ -301,6 +321,7 @@ FLAG_NUMERICS_REFERENCE_FMA2 = 128  # include/rtw_hip.h RTW_FLAG_NUMERICS_REFERE
 DENOISE_DEMODULATE = 1   # include/rtw_hip.h RTW_DENOISE_DEMODULATE
 UPSAMPLE_DEMODULATE = 1  # include/rtw_hip.h RTW_UPSAMPLE_DEMODULATE
 TEMPORAL_DEMODULATE = 1  # include/rtw_hip.h RTW_TEMPORAL_DEMODULATE
+PRESENT_DITHER, PRESENT_BGR, PRESENT_SQRT = 1, 2, 4     # include/rtw_hip.h RTW_PRESENT_*
 GATHER_PEER, GATHER_HOST_STAGED, GATHER_RCCL, GATHER_SAME_DEVICE = 1, 2, 4, 8    # rtw_stats_t.gather_path bits
 ABI_VERSION = 4
 

@@ -4,7 +4,7 @@
 //   rtw_scene.hip        scene upload: SoA rows, kd split of the group-cull layout, the f16-split operands of the matrix-pipe filter
 //   rtw_launch.hip       one render = one launch of the trace kernel (rtw_kernels.hpp / rtw_pool.hpp): geometry, occupancy, job shape, views
 //   rtw_render_host.hip  every host-buffer entry point: cached per-device context (scene, stream, buffer), ONE one-device path (render_one_device) behind render,
-//                        batch, feature, render + filter and render + upsample calls, the filter and the upsampler on host buffers, or a device list
+//                        batch, feature, render + filter, render + upsample and render + present calls, the filter, the upsampler and the present stage on host buffers, or a device list
 //   rtw_multi.hip        what a device list needs: peer access, the on-demand RCCL binding, the un-tile kernel
 //   rtw_batch_accum_f32.hip / _f64.hip  the BATCH && ACCUM instances of the trace kernel (rtw_instances.hpp: the kernel-instance table), a unit per precision
 //   rtw_features_accum_batch_f32.hip / _f64.hip  the TILED && BATCH instances of the feature kernel (rtw_features.hpp), a unit per precision
@@ -15,6 +15,7 @@
 //   rtw_denoise.hip      the feature-guided denoiser: its checks, the launch sequence of its kernels (rtw_denoise.hpp) for one frame or a batch of frames, the device-resident entry points
 //   rtw_upsample.hip     the feature-guided upsampler: its checks, the launch sequence (the denoiser's prepare and level kernels at the small size, then rtw_upsample.hpp at the full size), the device-resident entry points
 //   rtw_temporal.hip     temporal reprojection: its checks, the host constants and the one launch of a step (rtw_temporal.hpp), the device-resident entry points
+//   rtw_present.hip      the present stage: its checks, the one launch of its kernel (rtw_present.hpp) for one frame or a batch, the device-resident entry points
 //   (rtw_scene_view.hpp: what both launch functions derive from their arguments; rtw_instances.hpp: the one table of the trace kernel's instances)
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
 #pragma once
@@ -359,6 +360,16 @@ int launch_temporal_noise_f32(const rtw_temporal_noise_t *n, int32_t width, int3
 int launch_temporal_noise_f64(const rtw_temporal_noise_t *n, int32_t width, int32_t height, const void *d_state, const void *d_moment, void *d_noise, hipStream_t stream);
 inline int launch_temporal_noise_t(const rtw_temporal_noise_t *n, int32_t w, int32_t h, const void *st, const void *mo, float *noise, hipStream_t s) { return launch_temporal_noise_f32(n, w, h, st, mo, noise, s); }
 inline int launch_temporal_noise_t(const rtw_temporal_noise_t *n, int32_t w, int32_t h, const void *st, const void *mo, double *noise, hipStream_t s) { return launch_temporal_noise_f64(n, w, h, st, mo, noise, s); }
+
+// rtw_present.hip -- the present stage (include/rtw_hip.h rtw_present_*).  validate_present: every check of a call that needs neither a device
+// nor a pointer -- the parameters, the frame, n_views (0: one frame; a batch's count through batch_views) and the size of the launch.
+int validate_present(const rtw_present_t *p, int32_t width, int32_t height, int32_t n_views);
+// launch_present: enqueue ONE launch on `stream` of the current device.  n_views == 0: one frame of width*height*3 elements into
+// width*height*channels bytes (d_out 4-byte aligned); n_views >= 1: that many frames one behind the other in both buffers.
+int launch_present_f32(const rtw_present_t *p, int32_t width, int32_t height, int32_t n_views, const void *d_images, void *d_out, hipStream_t stream);
+int launch_present_f64(const rtw_present_t *p, int32_t width, int32_t height, int32_t n_views, const void *d_images, void *d_out, hipStream_t stream);
+inline int launch_present_t(const rtw_present_t *p, int32_t w, int32_t h, int32_t nv, const float *img, void *out, hipStream_t st) { return launch_present_f32(p, w, h, nv, img, out, st); }
+inline int launch_present_t(const rtw_present_t *p, int32_t w, int32_t h, int32_t nv, const double *img, void *out, hipStream_t st) { return launch_present_f64(p, w, h, nv, img, out, st); }
 
 // rtw_unit.hip
 int run_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene, const rtw_camera_f32 *cam);

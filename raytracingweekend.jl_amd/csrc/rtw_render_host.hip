@@ -1,6 +1,6 @@
 // rtw_render_host.hip -- the host-buffer entry points of the C ABI (rtw_render_f32/_f64 is what the Julia ccall binds; replaces src/render.jl:8-44):
 // a cached per-device context (uploaded scene, stream, device buffer), one device (render_one_device: the path the plain, the batched, the
-// feature, the render + filter, the render + upsample and the sequence entry points share) or a device list (tiles dealt round-robin, shards gathered on the first device by peer
+// feature, the render + filter, the render + upsample, the sequence and the render + present entry points share) or a device list (tiles dealt round-robin, shards gathered on the first device by peer
 // copies or ONE RCCL reduce: rtw_multi.hip), one D2H of the result.  The single and the batched form of a call share one body (n_views == 0: single).
 #include "rtw_host.hpp"
 
@@ -383,6 +383,22 @@ int filter_host(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n
     return rc;
 }
 
+// The launch sequence of render + feature pass + filter on a leased context (render_host_filtered, render_host_presented): the linear image, the
+// features over all `nch` effective chunks and the filter with the caller's gamma into the regions R of hc->d_img.  `q`: the caller's params bound
+// to the lease's device; rec / frec: the render's and the feature pass's records.
+template <typename T, typename CamT>
+int launch_filtered(HostCtx *hc, rtw_params &q, const CamT *cams, int32_t n_views, const uint64_t *seeds, int32_t gamma, const rtw_denoise_t *d, int nch, const DenoiseRegions<T> &R,
+                    RenderRec **rec, CtxPtr *rctx, RenderRec **frec, CtxPtr *fctx) {
+    char *base = (char *)hc->d_img;
+    q.gamma = 0;
+    rtw_denoise_t dd = *d;
+    dd.gamma = gamma != 0; dd.device = hc->device;
+    int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
+    if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, frec, fctx);
+    if (!rc) rc = R.launch(&dd, q.width, q.height, n_views, base, hc->stream);
+    return rc;
+}
+
 // Render, feature pass over all N effective chunks and filter in one call (rtw_render_denoised_* / rtw_render_filtered_batch_*): the one-device
 // path above with a device buffer that holds the linear image (the render with gamma 0), the features, the result (the filter with p->gamma) and
 // the filter's workspace; 2 + 1 + levels launches for any number of views on the context's stream, ONE D2H.  rtw_stats() reports the render's record.
@@ -399,13 +415,62 @@ int render_host_filtered(const SceneT *scene, const CamT *cams, int32_t n_views,
     RenderRec *frec = nullptr;
     CtxPtr fctx;
     const int rc = render_one_device(p->device, scene, p, R.total, R.off_out, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+        return launch_filtered(hc, q, cams, n_views, seeds, p->gamma, d, nch, R, rec, rctx, &frec, &fctx);
+    });
+    if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
+    return rc;
+}
+
+// The present stage on a host buffer (rtw_present_*): a leased context of the device (its stream and buffer; the scene it may hold is left
+// alone), one H2D of the frame, ONE launch, ONE D2H of the bytes.  This thread's last render (rtw_stats) is not touched.
+template <typename T>
+int present_host(const rtw_present_t *p, int32_t width, int32_t height, const T *image, uint8_t *out) {
+    if (!p || !image || !out) return fail(-1, "null argument");
+    if (int rc = validate_present(p, width, height, 0)) return rc;
+    const size_t n_pix = (size_t)width * (size_t)height, img_b = n_pix * 3 * sizeof(T), out_b = n_pix * (size_t)p->channels, off_out = (img_b + 15) & ~(size_t)15;
+    if (ranges_overlap(out, out_b, image, img_b)) return fail(-2, "out may not alias the input");
+    DeviceGuard guard;
+    HostLease L;
+    if (int rc = acquire_host(p->device, std::vector<unsigned char>(), &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, off_out + out_b)) return rc;
+    char *base = (char *)hc->d_img;
+    int rc = 0;
+    const hipError_t e = hipMemcpyAsync(base, image, img_b, hipMemcpyHostToDevice, hc->stream);
+    if (e != hipSuccess) rc = fail((int)e, "upload of the frame failed: %s", hipGetErrorString(e));
+    if (!rc) rc = launch_present_t(p, width, height, 0, (const T *)base, base + off_out, hc->stream);
+    if (!rc) rc = copy_out(hc, base + off_out, out, out_b);
+    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    return rc;
+}
+
+// Render and present in one call (rtw_render_presented_* / rtw_render_presented_batch_*): the one-device path above.  d null: the render with
+// p->gamma as given into the head of the device buffer; d non-null: the launch sequence of render_host_filtered into its regions.  Then ONE
+// launch of the present kernel over the device image of all views into a byte region behind everything else, and ONE D2H of those bytes.
+template <typename T, typename SceneT, typename CamT>
+int render_host_presented(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, const rtw_present_t *pr,
+                          uint8_t *out) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !cams || !pr || !out) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = n_views ? validate_features_batch(cams, n_views, p, 0, 1, out, &nch, &cs) : validate_features(p, 0, 1, &nch, &cs)) return rc;
+    if (d) { if (int rc = n_views ? validate_filter_batch(d, p->width, p->height, n_views) : validate_denoise(d, p->width, p->height)) return rc; }
+    if (int rc = validate_present(pr, p->width, p->height, n_views)) return rc;
+    DeviceGuard guard;
+    release_last();
+    const DenoiseRegions<T> R(p->width, p->height, n_views);
+    const size_t off_img = d ? R.off_out : 0, off_pres = d ? R.total : (R.img_b + 15) & ~(size_t)15;       // (R.total is a multiple of 16)
+    const size_t pres_b = (size_t)rtw_present_bytes(p->width, p->height, pr->channels, n_views);
+    RenderRec *frec = nullptr;
+    CtxPtr fctx;
+    // (render_one_device takes its precision from the type of `out` and hands the pointer to the D2H untyped: the bytes go out as they are)
+    const int rc = render_one_device(p->device, scene, p, off_pres + pres_b, off_pres, pres_b, reinterpret_cast<T *>(out), [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
         char *base = (char *)hc->d_img;
-        q.gamma = 0;
-        rtw_denoise_t dd = *d;
-        dd.gamma = p->gamma != 0; dd.device = hc->device;
-        int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
-        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec, &fctx);
-        if (!rc) rc = R.launch(&dd, p->width, p->height, n_views, base, hc->stream);
+        rtw_present_t pp = *pr;
+        pp.device = hc->device;
+        int rc = d ? launch_filtered(hc, q, cams, n_views, seeds, p->gamma, d, nch, R, rec, rctx, &frec, &fctx)
+                   : launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
+        if (!rc) rc = launch_present_t(&pp, p->width, p->height, n_views, (const T *)(base + off_img), base + off_pres, hc->stream);
         return rc;
     });
     if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
@@ -802,6 +867,23 @@ int rtw_render_filtered_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f
 int rtw_render_filtered_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d,
                                   double *out) {
     return render_host_filtered<double>(scene, cams, batch_views(n_views), seeds, p, d, out);
+}
+
+int rtw_present_f32(const rtw_present_t *p, int32_t width, int32_t height, const float *image, uint8_t *out) { return present_host<float>(p, width, height, image, out); }
+int rtw_present_f64(const rtw_present_t *p, int32_t width, int32_t height, const double *image, uint8_t *out) { return present_host<double>(p, width, height, image, out); }
+int rtw_render_presented_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *params, const rtw_denoise_t *d, const rtw_present_t *p, uint8_t *out) {
+    return render_host_presented<float>(scene, cam, 0, nullptr, params, d, p, out);
+}
+int rtw_render_presented_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *params, const rtw_denoise_t *d, const rtw_present_t *p, uint8_t *out) {
+    return render_host_presented<double>(scene, cam, 0, nullptr, params, d, p, out);
+}
+int rtw_render_presented_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *params, const rtw_denoise_t *d,
+                                   const rtw_present_t *p, uint8_t *out) {
+    return render_host_presented<float>(scene, cams, batch_views(n_views), seeds, params, d, p, out);
+}
+int rtw_render_presented_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *params, const rtw_denoise_t *d,
+                                   const rtw_present_t *p, uint8_t *out) {
+    return render_host_presented<double>(scene, cams, batch_views(n_views), seeds, params, d, p, out);
 }
 
 int rtw_upsample_f32(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, const float *image_lo, const float *features_lo,

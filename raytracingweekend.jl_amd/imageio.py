@@ -9,13 +9,24 @@ import numpy as np
 
 
 def to_u8(img):
-    """float image (gamma already applied by ``render``) -> uint8 [H, W, 3]"""
+    """float image (gamma already applied by ``render``) -> uint8 [H, W, 3]; a uint8 image (``present``, ``render_presented``) is returned
+    as it is"""
+    if isinstance(img, np.ndarray) and img.dtype == np.uint8:
+        return img
     a = np.nan_to_num(np.asarray(img, dtype=np.float64), nan=0.0, posinf=1.0, neginf=0.0)
     return np.rint(np.clip(a, 0.0, 1.0) * 255.0).astype(np.uint8)
 
 
-def save_ppm(img, path):
+def _u8_rgb(img):
+    """what the writers write: ``to_u8`` of a float image, a uint8 [H, W, 3] image as it is (4 channels: present with channels=3)"""
     u = to_u8(img)
+    if u is img and (u.ndim != 3 or u.shape[2] != 3):
+        raise ValueError(f"a uint8 image must be [H, W, 3], got {u.shape}")
+    return u
+
+
+def save_ppm(img, path):
+    u = _u8_rgb(img)
     with open(path, "wb") as f:
         f.write(b"P6\n%d %d\n255\n" % (u.shape[1], u.shape[0]))
         f.write(np.ascontiguousarray(u).tobytes())
@@ -27,7 +38,7 @@ def _chunk(tag, data):
 
 
 def save_png(img, path):
-    u = np.ascontiguousarray(to_u8(img))
+    u = np.ascontiguousarray(_u8_rgb(img))
     h, w, _ = u.shape
     raw = b"".join(b"\x00" + u[i].tobytes() for i in range(h))      # filter type 0 per scanline
     png = b"\x89PNG\r\n\x1a\n" + _chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + \

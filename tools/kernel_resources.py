@@ -4,7 +4,7 @@ usage: python tools/kernel_resources.py [--unit NAME.hip ...] [extra hipcc flags
 The instances live in rtw_launch.hip and, the BATCH && ACCUM ones, in rtw_batch_accum_f32.hip / _f64.hip: one table over all three.
 --unit names other translation units instead (rtw_features.hip: the instances of the feature kernel, the batched ones among them; rtw_features_accum_batch_f32.hip /
 _f64.hip: its tiled batched instances; rtw_denoise.hip: the denoiser's kernels and the batched level kernels; rtw_accum_kernels.hip: the accumulator's kernels, the noise map and the
-batched resolve and noise map among them; rtw_temporal.hip: the instances of the temporal step, with and without moments, and the temporal noise map)."""
+batched resolve and noise map among them; rtw_temporal.hip: the instances of the temporal step, with and without moments, and the temporal noise map; rtw_present.hip: the instances of the present kernel)."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = ""
@@ -21,10 +21,10 @@ for line in out.splitlines():
     m = re.search(r"Function Name: (\S+)", line)
     if m:
         cur = {"name": m.group(1)}; rows.append(cur); continue
-    m = re.search(r"remark:\s+(TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill): (\d+)", line)
+    m = re.search(r"remark:\s+(TotalSGPRs|VGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|SGPRs Spill|VGPRs Spill|LDS Size \[bytes/block\]): (\d+)", line)
     if m and cur is not None:
         cur[m.group(1)] = int(m.group(2))
-print(f"{'kernel':52s} {'VGPR':>5s} {'SGPR':>5s} {'waves':>5s} {'scratch B':>9s} {'vspill':>6s} {'sspill':>6s}")
+print(f"{'kernel':52s} {'VGPR':>5s} {'SGPR':>5s} {'waves':>5s} {'scratch B':>9s} {'vspill':>6s} {'sspill':>6s} {'LDS B':>6s}")
 for r in rows:
     n = r["name"]
     m = re.match(r"_ZN3rtw12trace_kernelI([fd])Lb([01])ELb([01])ELb([01])ELb([01])ELi(n?\d+)ELb([01])ELb([01])ELb([01])E", n)
@@ -52,8 +52,11 @@ for r in rows:
         label = f"temporal tp_step<{'f32' if m.group(1) == 'f' else 'f64'}{', has_prev' if m.group(2) == '1' else ', first frame'}{', moments' if m.group(3) == '1' else ''}>"
     elif re.match(r"_ZN3rtw\d+tp_noiseI([fd])", n):
         label = "temporal tp_noise<%s>" % ("f32" if re.match(r"_ZN3rtw\d+tp_noiseI([fd])", n).group(1) == "f" else "f64")
+    elif re.match(r"_ZN3rtw\d+pr_presentI([fd])Li([34])ELb([01])E", n):
+        m = re.match(r"_ZN3rtw\d+pr_presentI([fd])Li([34])ELb([01])E", n)
+        label = f"present pr_present<{'f32' if m.group(1) == 'f' else 'f64'}, C = {m.group(2)}{'' if m.group(2) == '4' else ', aligned rows' if m.group(3) == '1' else ', unaligned rows'}>"
     elif "unit_kernel" in n:
         label = "unit_kernel<%s>" % ("f32" if "IfE" in n else "f64")
     else:
         label = n[:44]
-    print(f"{label:52s} {r.get('VGPRs', 0):5d} {r.get('TotalSGPRs', 0):5d} {r.get('Occupancy [waves/SIMD]', 0):5d} {r.get('ScratchSize [bytes/lane]', 0):9d} {r.get('VGPRs Spill', 0):6d} {r.get('SGPRs Spill', 0):6d}")
+    print(f"{label:52s} {r.get('VGPRs', 0):5d} {r.get('TotalSGPRs', 0):5d} {r.get('Occupancy [waves/SIMD]', 0):5d} {r.get('ScratchSize [bytes/lane]', 0):9d} {r.get('VGPRs Spill', 0):6d} {r.get('SGPRs Spill', 0):6d} {r.get('LDS Size [bytes/block]', 0):6d}")
