@@ -834,8 +834,8 @@ int rtw_render_upsampled_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_
  * d_state_prev (state_prev) null -> -2; a frame of 2^31 8x8 tiles or more (the denoiser's frame rule) -> -5; the sequence call additionally
  * refuses everything rtw_render_filtered_batch_* refuses for its arguments (with `d` NULL: everything a batched feature render refuses).
  *   Left out on purpose: N independent sequences in one launch, accumulators or the upsampler as the step's input,
- * device lists, moving spheres (the scene is static: there are no motion vectors beyond the camera's), a variance-guided alpha,
- * neighbourhood colour clamping.  (A per-pixel noise map from the history's second moments, and the sequence call that feeds it to the
+ * device lists, moving spheres (the scene is static: there are no motion vectors beyond the camera's), a variance-guided alpha.
+ * (Neighbourhood colour clamping: the rtw_clamped_step_* block further down.  A per-pixel noise map from the history's second moments, and the sequence call that feeds it to the
  * noise-guided filter: the block behind these declarations.)  Additive to ABI 4: detected by symbol lookup. */
 #define RTW_TEMPORAL_DEMODULATE 1  /* accumulate image / albedo, multiply the current albedo back at the end */
 typedef struct {
@@ -918,7 +918,7 @@ int rtw_render_sequence_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *ca
  * aliasing pointer -> -2; the frame rule -> -5; the sequence call refuses everything rtw_render_sequence_* refuses and, with -2, a `t` and
  * a `d` whose DEMODULATE flags differ (the map is relative to the state's luminance).
  *   The defaults (radius 2, normal_power_log2 1, sigma_depth 0.1, min_len 4) are UNTUNED beyond the record of DESIGN.md 7.19.  Left out on
- * purpose: a variance-driven alpha, neighbourhood colour clamping, smoothing of the map, moments for accumulators or
+ * purpose: a variance-driven alpha, smoothing of the map, moments for accumulators or
  * the upsampler, N sequences per launch, device lists, an LDS-tiled window.  Additive to ABI 4: detected by symbol lookup. */
 typedef struct {
     int32_t radius;             /* 1..3: the spatial estimate's window is (2*radius + 1)^2 */
@@ -949,6 +949,82 @@ int rtw_render_path_guided_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 
                                    const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, float *out);
 int rtw_render_path_guided_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
                                    const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, double *out);
+
+/* Temporal clamp: neighbourhood colour clamping of the reprojected history.  The two blocks above trust a history completely once the
+ * geometric tests accept it, and those tests see first-hit geometry only: what is view-dependent behind the first hit (a metal's reflection,
+ * everything seen through a dielectric) and the blur of repeated bilinear resampling are reprojected as if painted on the surface, then
+ * averaged for up to history_max frames.  The clamped step pulls the gathered history into mean +- sigma standard deviations of the CURRENT
+ * frame's (2*radius + 1)^2 window before it blends, and can shorten the history it moved.  Nothing above changes: the step, the state, the
+ * moment plane and every entry point of the two blocks above keep their bits and their layouts; this is one more form of the step.
+ * (The entry points are named rtw_clamped_step_* and rtw_render_path_clamped_*: the names of the two blocks above are closed sets.)
+ *
+ * The definition, in the arithmetic of the temporal block (everything in T, one rounding per operation, no FMA, IEEE quotients and sqrt, a
+ * tap that takes no part is dropped by a select).  The step is rtw_history_moments_device_*'s (rtw_temporal_device_*'s when no moment planes
+ * are given) with one insertion between "Taps" and "Blend".  ks = T(sigma) and ls = T(len_scale) are rounded on the host.
+ *   Window of the current frame.  r = radius; S0 = S1[k] = S2[k] = +0; dj = -r..r is the outer and di = -r..r the inner loop; the tap q is
+ * row i + di, column j + dj.  A tap outside the frame, or whose pixel is not valid by Prepare (any of its 3 + 8 inputs not finite), is
+ * skipped.  Any other tap (the centre among them), with e_q, n_q, z_q, cov_q those of Prepare for pixel q of the current frame:
+ *       with RTW_CLAMP_GUIDES, the noise map's window weight on the current frame's guides (the step's tap weight with sb = 1, zexp = z_p;
+ *       m = t->normal_power_log2 and inv_sz = T(1/(t->sigma_depth*t->sigma_depth)) are the step's):
+ *           t_v = 1 - |cov_p - cov_q|;  w = t_v > 0 ? t_v : +0
+ *           if has(p) and cov_q > 0:
+ *               dot = (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z;  t = dot > 0 ? dot : +0, then t = t*t repeated m times
+ *               zs = z_p + z_q;  rz = (z_p - z_q) / (zs > 0 ? zs : 1);  w_z = 1 / (1 + (rz*rz)*inv_sz);  w = (w*t)*w_z
+ *           S0 = S0 + w;  S1[k] = S1[k] + w*e_q[k];  S2[k] = S2[k] + w*(e_q[k]*e_q[k])
+ *       without it w = 1 and the products by w are not formed:
+ *           S0 = S0 + 1;  S1[k] = S1[k] + e_q[k];    S2[k] = S2[k] + e_q[k]*e_q[k]
+ *   then per channel
+ *       mu = S1/S0;  vt = S2/S0 - mu*mu;  var = vt > 0 ? vt : +0;  sd = sqrt(var);  lo = mu - ks*sd;  hi = mu + ks*sd
+ *   Clamp.  With eh and lh the history of "Blend" (eh[k] = sum_e[k] / sum_w, lh = sum_l / sum_w):
+ *       hc[k] = eh[k] < lo[k] ? lo[k] : (eh[k] > hi[k] ? hi[k] : eh[k])      (a NaN bound -- S0 = 0 -- fails both comparisons: hc = eh)
+ *       moved = some channel has hc[k] != eh[k];  lh' = moved ? lh*ls : lh
+ * and the blend continues with hc and lh' in place of eh and lh: l1 = lh' + 1; n' = l1 < n_max ? l1 : n_max; alpha = 1 / n';
+ * e'[k] = hc[k] + alpha*(e[k] - hc[k]); len' = n'.  With moment planes mh = sum_m / sum_w is blended with the alpha that results,
+ * M' = mh + alpha*(y2 - mh): the second moment itself is not clamped.
+ *   Reset and first frame.  A pixel that resets, and the first frame, are the plain step's: the window decides nothing there (the first
+ * frame runs the plain step's kernel).  A pixel that is not valid is the plain step's as well.
+ *   Equivalence.  Where no pixel is moved the call equals rtw_temporal_device_* / rtw_history_moments_device_* on the bits: image, state and
+ * moment plane.  (tests/temporal_clamp_ref.py restates all of this on the CPU, twice, and the device agrees on the bits.)
+ *
+ * rtw_clamped_step_device_*: rtw_history_moments_device_* with the clamp `c` behind `t`; d_moment_prev and d_moment_next are NULL together
+ * (no moments: rtw_temporal_device_*'s step) or follow rtw_history_moments_device_*'s rule.  One launch, asynchronous; rtw_stats() is left alone.
+ *   rtw_clamped_step_*: the host-buffer form, blocking, through the cached context like rtw_temporal_f32; `moment_prev` / `moment_next` are
+ * optional in the same way; there is no noise map (rtw_history_noise_device_* reads the state and the plane this call returns).
+ *   rtw_render_path_clamped_*: n_views cameras along a path with clamped steps.  `n` and `d` both NULL: rtw_render_sequence_* without a
+ * filter; `d` alone: with the plain filter; `n` and `d`: rtw_render_path_guided_*; `n` without `d` -> -2.  In every case the steps behind
+ * view 0 are clamped steps; view v equals the chain of the single device calls on the bits; rtw_stats() reports the render's record.
+ *   Refusals, all decided before any HIP call: a null `c` (or any other null argument that is not optional) -> -1; radius outside 1..3,
+ * unknown flag bits, reserved != 0, sigma not finite or < 0, len_scale outside [0, 1] or NaN -> -2; everything the underlying temporal,
+ * moments or sequence call refuses, with that call's code.
+ *   The defaults (radius 1, no flags, sigma 1, len_scale 1) are UNTUNED beyond the record of DESIGN.md 7.21.  Left out on purpose (DESIGN.md
+ * section 9): a continuous variance-driven alpha, clamping in another colour space, clamping the second moment, N sequences per launch,
+ * device lists.  Additive to ABI 4: detected by symbol lookup. */
+#define RTW_CLAMP_GUIDES 1      /* weight the window's taps by the current frame's guides (coverage, normal, depth) */
+typedef struct {
+    int32_t radius;             /* 1..3: the window is (2*radius + 1)^2 */
+    int32_t flags;              /* RTW_CLAMP_* */
+    int32_t reserved[2];        /* 0 */
+    double  sigma;              /* finite, >= 0: the bounds are mean -+ sigma standard deviations */
+    double  len_scale;          /* in [0, 1]: the gathered history length of a pixel the clamp moved is multiplied by it */
+} rtw_temporal_clamp_t;         /* 32 bytes */
+int rtw_clamped_step_device_f32(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width,
+                                    int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, const void *d_moment_prev /* may be NULL */,
+                                    void *d_state_next, void *d_moment_next /* may be NULL */, void *d_out, void *hip_stream);
+int rtw_clamped_step_device_f64(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width,
+                                    int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, const void *d_moment_prev /* may be NULL */,
+                                    void *d_state_next, void *d_moment_next /* may be NULL */, void *d_out, void *hip_stream);
+int rtw_clamped_step_f32(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width,
+                             int32_t height, const float *image, const float *features, const void *state_prev, const void *moment_prev /* may be NULL */,
+                             void *state_next, void *moment_next /* may be NULL */, float *out);
+int rtw_clamped_step_f64(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width,
+                             int32_t height, const double *image, const double *features, const void *state_prev, const void *moment_prev /* may be NULL */,
+                             void *state_next, void *moment_next /* may be NULL */, double *out);
+int rtw_render_path_clamped_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
+                                 const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n /* may be NULL */,
+                                 const rtw_denoise_t *d /* may be NULL */, float *out);
+int rtw_render_path_clamped_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
+                                 const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n /* may be NULL */,
+                                 const rtw_denoise_t *d /* may be NULL */, double *out);
 
 /* Present stage: display-ready 8-bit frames from the device.  Every pipeline above ends in T elements in the column-major layout of the
  * render entry points; a window, a PNG or a video encoder wants 8-bit rows.  One kernel clips, rounds, packs and transposes in HBM, and the

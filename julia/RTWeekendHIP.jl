@@ -164,6 +164,64 @@ function render(scene::HittableList, cams::AbstractVector{Camera{T}}, image_widt
     img
 end
 
+# rtw_temporal_t (48 bytes) and rtw_temporal_clamp_t (32 bytes), include/rtw_hip.h
+struct CTemporal
+    normal_power_log2::Int32; flags::Int32; gamma::Int32; device::Int32; reserved::NTuple{2,Int32}
+    sigma_depth::Float64; min_weight::Float64; history_max::Float64
+end
+struct CTemporalClamp
+    radius::Int32; flags::Int32; reserved::NTuple{2,Int32}
+    sigma::Float64; len_scale::Float64
+end
+
+"""
+    render_sequence_clamped(scene, cams, image_width=400, n_samples=1; radius=1, guides=false, sigma=1.0, len_scale=1.0, depth=16, seed=1, device=-1)
+
+A camera path with clamped history reuse (rtw_render_path_clamped_f32/_f64 with `n` and `d` NULL: no noise maps, no filter): one batched
+render, one batched feature pass and `length(cams)` temporal steps whose reprojected history is clamped to mean ± `sigma` standard deviations
+of the current frame's (2·radius+1)² window.  Returns an `Array{RGB{T},3}` like the batched `render`; the temporal step runs at the header's
+defaults, the clamp's defaults are untuned (DESIGN.md 7.21).
+(Not executed in this repository: there is no `julia` in its build image; tests/test_gpu_temporal_clamp.py drives the same entry point.)
+"""
+function render_sequence_clamped(scene::HittableList, cams::AbstractVector{Camera{T}}, image_width=400, n_samples=1;
+                                 radius=1, guides=false, sigma=1.0, len_scale=1.0, depth=16, seed=1, device=-1) where T <: Union{Float32,Float64}
+    isempty(cams) && throw(ArgumentError("cams is empty"))
+    nv = length(cams)
+    seeds = seed isa Integer ? fill(UInt64(seed), nv) : UInt64.(seed)
+    length(seeds) == nv || throw(ArgumentError("$(length(seeds)) seeds for $nv views"))
+    image_height = image_width ÷ (16//9)
+    n = length(scene)
+    cx = Vector{T}(undef, n); cy = similar(cx); cz = similar(cx); r = similar(cx)
+    ar = similar(cx); ag = similar(cx); ab = similar(cx); param = similar(cx)
+    kind = Vector{Int32}(undef, n)
+    for (i, h) in enumerate(scene)
+        h isa Sphere{T} || throw(ArgumentError("scene[$i] is $(typeof(h)); the HIP path takes Sphere{$T} only"))
+        cx[i], cy[i], cz[i] = h.center
+        r[i] = h.radius
+        kind[i] = matkind(h.mat)
+        ar[i], ag[i], ab[i] = albedo(h.mat)
+        param[i] = matparam(h.mat)
+    end
+    img = Array{RGB{T},3}(undef, image_height, image_width, nv)
+    ccams = [CCamera(c) for c in cams]
+    rc = GC.@preserve cx cy cz r kind ar ag ab param img ccams seeds begin
+        params = Ref(CParams(image_width, image_height, n_samples, depth, seeds[1], 0, 0, 1, device, 1, 0, 0, 0, Ptr{Int32}(C_NULL)))
+        cscene = Ref(CScene{T}(n, pointer(cx), pointer(cy), pointer(cz), pointer(r), pointer(kind),
+                               pointer(ar), pointer(ag), pointer(ab), pointer(param)))
+        t = Ref(CTemporal(1, 1, 1, -1, (0, 0), 0.1, 0.25, 16.0))            # the header's defaults; RTW_TEMPORAL_DEMODULATE
+        c = Ref(CTemporalClamp(radius, guides ? 1 : 0, (0, 0), sigma, len_scale))       # RTW_CLAMP_GUIDES
+        if T === Float32
+            ccall((:rtw_render_path_clamped_f32, LIB), Cint, (Ref{CScene{Float32}}, Ptr{CCamera{Float32}}, Int32, Ptr{UInt64}, Ref{CParams}, Ref{CTemporal}, Ref{CTemporalClamp}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float32}),
+                  cscene, pointer(ccams), nv, pointer(seeds), params, t, c, C_NULL, C_NULL, pointer(reinterpret(Float32, vec(img))))
+        else
+            ccall((:rtw_render_path_clamped_f64, LIB), Cint, (Ref{CScene{Float64}}, Ptr{CCamera{Float64}}, Int32, Ptr{UInt64}, Ref{CParams}, Ref{CTemporal}, Ref{CTemporalClamp}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Float64}),
+                  cscene, pointer(ccams), nv, pointer(seeds), params, t, c, C_NULL, C_NULL, pointer(reinterpret(Float64, vec(img))))
+        end
+    end
+    rc == 0 || error("librtw_hip: error $rc: $(last_error())")
+    img
+end
+
 """
     render_progressive(scene, cam, image_width=400, n_samples=1; passes=4, callback=nothing, depth=16, seed=1, n_chunks=0, device=-1, numerics=:reference, group_cull=false, scan_valu=false)
 

@@ -36,6 +36,8 @@ SYMBOLS = [
     "rtw_render_sequence_f32", "rtw_render_sequence_f64",
     "rtw_history_moment_bytes", "rtw_history_moments_device_f32", "rtw_history_moments_device_f64", "rtw_history_noise_device_f32", "rtw_history_noise_device_f64",
     "rtw_history_moments_f32", "rtw_history_moments_f64", "rtw_render_path_guided_f32", "rtw_render_path_guided_f64",
+    "rtw_clamped_step_device_f32", "rtw_clamped_step_device_f64", "rtw_clamped_step_f32", "rtw_clamped_step_f64",
+    "rtw_render_path_clamped_f32", "rtw_render_path_clamped_f64",
     "rtw_present_bytes", "rtw_present_device_f32", "rtw_present_device_f64", "rtw_present_batch_device_f32", "rtw_present_batch_device_f64",
     "rtw_present_f32", "rtw_present_f64", "rtw_render_presented_f32", "rtw_render_presented_f64", "rtw_render_presented_batch_f32",
     "rtw_render_presented_batch_f64",
@@ -118,6 +120,14 @@ class TemporalNoise(C.Structure):
 
 
 assert C.sizeof(TemporalNoise) == 40
+
+
+class TemporalClamp(C.Structure):
+    """rtw_temporal_clamp_t"""
+    _fields_ = [("radius", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32 * 2), ("sigma", C.c_double), ("len_scale", C.c_double)]
+
+
+assert C.sizeof(TemporalClamp) == 32
 
 
 class Present(C.Structure):
@@ -216,6 +226,10 @@ def lib():
         getattr(L, "rtw_history_noise_device_" + sfx).argtypes = [tn, i32, i32, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_history_moments_" + sfx).argtypes = [tp, tn, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_render_path_guided_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), tp, tn, C.POINTER(Denoise), ptr]
+        tc = C.POINTER(TemporalClamp)
+        getattr(L, "rtw_clamped_step_device_" + sfx).argtypes = [tp, tc, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_clamped_step_" + sfx).argtypes = [tp, tc, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_render_path_clamped_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), tp, tc, tn, C.POINTER(Denoise), ptr]
         pr, dn = C.POINTER(Present), C.POINTER(Denoise)
         getattr(L, "rtw_present_device_" + sfx).argtypes = [pr, i32, i32, ptr, ptr, ptr]
         getattr(L, "rtw_present_batch_device_" + sfx).argtypes = [pr, i32, i32, i32, ptr, ptr, ptr]
@@ -321,6 +335,7 @@ FLAG_NUMERICS_REFERENCE_FMA2 = 128  # include/rtw_hip.h RTW_FLAG_NUMERICS_REFERE
 DENOISE_DEMODULATE = 1   # include/rtw_hip.h RTW_DENOISE_DEMODULATE
 UPSAMPLE_DEMODULATE = 1  # include/rtw_hip.h RTW_UPSAMPLE_DEMODULATE
 TEMPORAL_DEMODULATE = 1  # include/rtw_hip.h RTW_TEMPORAL_DEMODULATE
+CLAMP_GUIDES = 1         # include/rtw_hip.h RTW_CLAMP_GUIDES
 PRESENT_DITHER, PRESENT_BGR, PRESENT_SQRT = 1, 2, 4     # include/rtw_hip.h RTW_PRESENT_*
 GATHER_PEER, GATHER_HOST_STAGED, GATHER_RCCL, GATHER_SAME_DEVICE = 1, 2, 4, 8    # rtw_stats_t.gather_path bits
 ABI_VERSION = 4

@@ -614,14 +614,17 @@ int temporal_host(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_prev
 // (ONE batched render with gamma 0), the features (ONE batched pass over all chunks), the accumulated images (n_views temporal steps in view
 // order, two states ping-pong) and, with `d`, the filtered images and the filter's workspace (ONE batched filter pass); 2 + n_views (+ 1 + levels)
 // launches on the context's stream, ONE D2H.  p->gamma is applied by the last stage that runs.  rtw_stats() reports the render's record.
+// `c` non-null (rtw_render_path_clamped_*): the steps behind view 0 are clamped steps, launch for launch.
 template <typename T, typename SceneT, typename CamT>
-int render_host_sequence(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t, const rtw_denoise_t *d, T *out) {
+int render_host_sequence(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t, const rtw_denoise_t *d, T *out,
+                         const rtw_temporal_clamp_t *c = nullptr) {
     if (!p) return fail(-1, "null params");
     if (!scene || !cams || !t || !out) return fail(-1, "null argument");
     int nch, cs;
     if (int rc = validate_features_batch(cams, n_views, p, 0, 1, out, &nch, &cs)) return rc;
     if (d) if (int rc = validate_filter_batch(d, p->width, p->height, n_views)) return rc;
     if (int rc = validate_temporal(t, p->width, p->height, (int)sizeof(T))) return rc;
+    if (c) if (int rc = validate_temporal_clamp(c)) return rc;
     DeviceGuard guard;
     release_last();
     const TemporalRegions<T> R(p->width, p->height, (size_t)n_views, d != nullptr);
@@ -636,7 +639,7 @@ int render_host_sequence(const SceneT *scene, const CamT *cams, int32_t n_views,
         if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec, &fctx);
         for (int v = 0; v < n_views && !rc; ++v)
             rc = launch_temporal_t(&tt, cams + v, v ? cams + (v - 1) : nullptr, p->width, p->height, base + (size_t)v * R.frame_b, base + R.off_feat + (size_t)v * (R.feat_b / (size_t)n_views),
-                                   v ? base + R.off_st[(v & 1) ^ 1] : nullptr, base + R.off_st[v & 1], base + R.off_acc + (size_t)v * R.frame_b, hc->stream);
+                                   v ? base + R.off_st[(v & 1) ^ 1] : nullptr, base + R.off_st[v & 1], base + R.off_acc + (size_t)v * R.frame_b, hc->stream, nullptr, nullptr, c);
         if (!rc && d) {
             rtw_denoise_t dd = *d;
             dd.gamma = p->gamma != 0; dd.device = hc->device;
@@ -710,12 +713,60 @@ int temporal_moments_host(const rtw_temporal_t *t, const rtw_temporal_noise_t *n
     return rc;
 }
 
+// One clamped step on host buffers (rtw_clamped_step_*): temporal_host's path with the clamp `c` and, when moment_next is given, the two moment
+// planes of temporal_moments_host (no noise map) -- two to four H2D, ONE launch, two or three D2H.  This thread's last render (rtw_stats) is not touched.
+template <typename T, typename CamT>
+int temporal_clamped_host(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const T *image, const T *features,
+                          const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, T *out) {
+    const bool moments = moment_prev || moment_next;
+    if (!t || !c || !cam || !image || !features || !state_next || !out || (moments && !moment_next)) return fail(-1, "null argument");
+    if (int rc = validate_temporal(t, width, height, (int)sizeof(T))) return rc;
+    if (int rc = validate_temporal_clamp(c)) return rc;
+    if ((cam_prev == nullptr) != (state_prev == nullptr)) return fail(-2, "cam_prev and state_prev must both be given or both be null (the first frame)");
+    if (moments && (moment_prev == nullptr) != (state_prev == nullptr)) return fail(-2, "moment_prev and state_prev must both be given or both be null (the first frame)");
+    const MomentRegions<T> R(width, height, 1, false);
+    // the outputs against each other and against every input
+    const void *outs[3] = {out, state_next, moment_next}, *ins[4] = {image, features, state_prev, moment_prev};
+    const size_t out_b[3] = {R.img_b, R.st_b, R.mo_b}, in_b[4] = {R.img_b, R.feat_b, R.st_b, R.mo_b};
+    static const char *const names[3] = {"out", "state_next", "moment_next"};
+    for (int a = 0; a < 3; ++a) {
+        if (!outs[a]) continue;
+        for (int b = a + 1; b < 3; ++b)
+            if (outs[b] && ranges_overlap(outs[a], out_b[a], outs[b], out_b[b])) return fail(-2, "%s and %s may not alias each other", names[a], names[b]);
+        for (int b = 0; b < 4; ++b)
+            if (ins[b] && ranges_overlap(outs[a], out_b[a], ins[b], in_b[b])) return fail(-2, "%s may not alias an input", names[a]);
+    }
+    DeviceGuard guard;
+    HostLease L;
+    if (int rc = acquire_host(t->device, std::vector<unsigned char>(), &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total_m)) return rc;
+    char *base = (char *)hc->d_img;
+    int rc = 0;
+    hipError_t e = hipMemcpyAsync(base, image, R.img_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_feat, features, R.feat_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess && state_prev) e = hipMemcpyAsync(base + R.off_st[0], state_prev, R.st_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess && moment_prev) e = hipMemcpyAsync(base + R.off_mo[0], moment_prev, R.mo_b, hipMemcpyHostToDevice, hc->stream);
+    if (e != hipSuccess) rc = fail((int)e, "upload of the temporal step's inputs failed: %s", hipGetErrorString(e));
+    if (!rc) rc = launch_temporal_t(t, cam, cam_prev, width, height, base, base + R.off_feat, state_prev ? base + R.off_st[0] : nullptr, base + R.off_st[1], base + R.off_acc, hc->stream,
+                                    moment_prev ? base + R.off_mo[0] : nullptr, moments ? base + R.off_mo[1] : nullptr, c);
+    if (!rc) {
+        e = hipMemcpyAsync(state_next, base + R.off_st[1], R.st_b, hipMemcpyDeviceToHost, hc->stream);
+        if (e == hipSuccess && moments) e = hipMemcpyAsync(moment_next, base + R.off_mo[1], R.mo_b, hipMemcpyDeviceToHost, hc->stream);
+        if (e != hipSuccess) rc = fail((int)e, "download of the next state or its moments failed: %s", hipGetErrorString(e));
+    }
+    if (!rc) rc = copy_out(hc, base + R.off_acc, out, R.img_b);
+    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    return rc;
+}
+
 // rtw_render_path_guided_*: render_host_sequence with the filter required, the steps with moments, one noise launch behind each step (into
 // view v of the noise region, before the ping-pong reuses that state: stream order) and the NOISE-GUIDED batched filter pass over the N maps;
 // 2 + 2*n_views + 1 + levels launches on the context's stream, ONE D2H.  p->gamma is applied by the filter.  rtw_stats() reports the render's record.
+// `c` non-null (rtw_render_path_clamped_*): the steps behind view 0 are clamped steps, launch for launch.
 template <typename T, typename SceneT, typename CamT>
 int render_host_sequence_guided(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t, const rtw_temporal_noise_t *n,
-                                const rtw_denoise_t *d, T *out) {
+                                const rtw_denoise_t *d, T *out, const rtw_temporal_clamp_t *c = nullptr) {
     if (!p) return fail(-1, "null params");
     if (!scene || !cams || !t || !n || !d || !out) return fail(-1, "null argument");
     int nch, cs;
@@ -723,6 +774,7 @@ int render_host_sequence_guided(const SceneT *scene, const CamT *cams, int32_t n
     if (int rc = validate_filter_batch(d, p->width, p->height, n_views)) return rc;
     if (int rc = validate_temporal(t, p->width, p->height, (int)sizeof(T))) return rc;
     if (int rc = validate_temporal_noise(n, p->width, p->height, (int)sizeof(T))) return rc;
+    if (c) if (int rc = validate_temporal_clamp(c)) return rc;
     if (((t->flags & RTW_TEMPORAL_DEMODULATE) != 0) != ((d->flags & RTW_DENOISE_DEMODULATE) != 0))
         return fail(-2, "the DEMODULATE flags of t and d must agree (the noise map is relative to the state's luminance)");
     DeviceGuard guard;
@@ -742,7 +794,7 @@ int render_host_sequence_guided(const SceneT *scene, const CamT *cams, int32_t n
         for (int v = 0; v < n_views && !rc; ++v) {
             rc = launch_temporal_t(&tt, cams + v, v ? cams + (v - 1) : nullptr, p->width, p->height, base + (size_t)v * R.frame_b, base + R.off_feat + (size_t)v * (R.feat_b / (size_t)n_views),
                                    v ? base + R.off_st[(v & 1) ^ 1] : nullptr, base + R.off_st[v & 1], base + R.off_acc + (size_t)v * R.frame_b, hc->stream,
-                                   v ? base + R.off_mo[(v & 1) ^ 1] : nullptr, base + R.off_mo[v & 1]);
+                                   v ? base + R.off_mo[(v & 1) ^ 1] : nullptr, base + R.off_mo[v & 1], c);
             if (!rc) rc = launch_temporal_noise_t(&nn, p->width, p->height, base + R.off_st[v & 1], base + R.off_mo[v & 1], (T *)(base + R.off_noise + (size_t)v * R.noise_b), hc->stream);
         }
         if (!rc) {
@@ -754,6 +806,16 @@ int render_host_sequence_guided(const SceneT *scene, const CamT *cams, int32_t n
     });
     if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
     return rc;
+}
+
+// rtw_render_path_clamped_*: the sequence (n null; d optional) or the guided sequence (n and d) with clamped steps.
+template <typename T, typename SceneT, typename CamT>
+int render_host_sequence_clamped(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t, const rtw_temporal_clamp_t *c,
+                                 const rtw_temporal_noise_t *n, const rtw_denoise_t *d, T *out) {
+    if (!p) return fail(-1, "null params");
+    if (!c) return fail(-1, "null temporal clamp parameters");
+    if (n && !d) return fail(-2, "a noise map (n) guides the filter: d is required with it");
+    return n ? render_host_sequence_guided<T>(scene, cams, n_views, seeds, p, t, n, d, out, c) : render_host_sequence<T>(scene, cams, n_views, seeds, p, t, d, out, c);
 }
 
 // What an accumulator holds, denoised (rtw_accum_filtered_f32/_f64): the gamma-0 resolve (per tile for an adaptive accumulator), the feature
@@ -932,6 +994,22 @@ int rtw_history_moments_f32(const rtw_temporal_t *t, const rtw_temporal_noise_t 
 int rtw_history_moments_f64(const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
                              const double *image, const double *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, double *out, double *noise) {
     return temporal_moments_host<double>(t, n, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, noise);
+}
+int rtw_clamped_step_f32(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height,
+                             const float *image, const float *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, float *out) {
+    return temporal_clamped_host<float>(t, c, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out);
+}
+int rtw_clamped_step_f64(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
+                             const double *image, const double *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, double *out) {
+    return temporal_clamped_host<double>(t, c, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out);
+}
+int rtw_render_path_clamped_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
+                                 const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, float *out) {
+    return render_host_sequence_clamped<float>(scene, cams, batch_views(n_views), seeds, p, t, c, n, d, out);
+}
+int rtw_render_path_clamped_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
+                                 const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, double *out) {
+    return render_host_sequence_clamped<double>(scene, cams, batch_views(n_views), seeds, p, t, c, n, d, out);
 }
 int rtw_render_path_guided_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                                    const rtw_temporal_noise_t *n, const rtw_denoise_t *d, float *out) {

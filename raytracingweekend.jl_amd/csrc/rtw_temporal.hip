@@ -1,9 +1,12 @@
 // rtw_temporal.hip -- temporal reprojection (include/rtw_hip.h rtw_temporal_*): the checks that need no device, the host constants of a step,
-// the one launch of its kernel (rtw_temporal.hpp), the step with moments and the noise map (rtw_history_moments_*, rtw_history_noise_device_*) and the
+// the one launch of its kernel (rtw_temporal.hpp), the step with moments and the noise map (rtw_history_moments_*, rtw_history_noise_device_*), the
+// clamped step (rtw_clamped_step_device_*: the checks of its clamp and the launch of its own kernel, rtw_temporal_clamp.hpp) and the
 // device-resident entry points.
-// (The host-buffer entry points, rtw_temporal_*, rtw_history_moments_* and rtw_render_sequence_*, live with the other cached-context paths in rtw_render_host.hip.)
+// (The host-buffer entry points, rtw_temporal_*, rtw_history_moments_*, rtw_clamped_step_*, rtw_render_sequence_* and rtw_render_path_*, live with the other
+// cached-context paths in rtw_render_host.hip.)
 #include "rtw_host.hpp"
 #include "rtw_temporal.hpp"
+#include "rtw_temporal_clamp.hpp"
 
 namespace rtwh {
 
@@ -20,6 +23,17 @@ int validate_temporal(const rtw_temporal_t *t, int32_t width, int32_t height, in
     if (!(t->history_max >= 1) || !std::isfinite(t->history_max)) return fail(-2, "history_max must be finite and >= 1");
     if (width < 1 || height < 1) return fail(-2, "width/height must be positive (got %d x %d)", width, height);
     if (const int64_t rc = rtw_denoise_work_bytes(width, height, elem_bytes); rc < 0) return (int)rc;         // (the denoiser's frame rule)
+    return 0;
+}
+
+// Everything about the clamp of a clamped step (rtw_clamped_step_*, rtw_render_path_clamped_*) that is decided without a device and without a pointer.
+int validate_temporal_clamp(const rtw_temporal_clamp_t *c) {
+    if (!c) return fail(-1, "null temporal clamp parameters");
+    if (c->radius < 1 || c->radius > 3) return fail(-2, "clamp radius must be in 1..3 (got %d)", c->radius);
+    if (c->flags & ~(RTW_CLAMP_GUIDES)) return fail(-2, "unknown clamp flags 0x%x", c->flags);
+    if (c->reserved[0] != 0 || c->reserved[1] != 0) return fail(-2, "clamp reserved must be 0");
+    if (!(c->sigma >= 0) || !std::isfinite(c->sigma)) return fail(-2, "clamp sigma must be finite and >= 0");
+    if (!(c->len_scale >= 0) || !(c->len_scale <= 1)) return fail(-2, "clamp len_scale must be in [0, 1]");
     return 0;
 }
 
@@ -45,10 +59,11 @@ int validate_temporal_noise(const rtw_temporal_noise_t *n, int32_t width, int32_
 
 // Enqueue one step on `stream` of the current device (validate_temporal has accepted the call).  cam_prev and d_state_prev are both null
 // (the first frame) or both given.  d_moment_next non-null: the step with moments (rtw_history_moments_*), d_moment_prev null exactly when
-// d_state_prev is.
+// d_state_prev is.  `c` non-null (validate_temporal_clamp has accepted it): the clamped step -- its own kernel (rtw_temporal_clamp.hpp), one workgroup per
+// tile, whenever there is a previous state; the first frame is the plain step's.
 template <typename T, typename CamT>
 int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features,
-                    const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev, void *d_moment_next) {
+                    const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev, void *d_moment_next, const rtw_temporal_clamp_t *c) {
     using V = typename rtw::DnVec<T>::type;
     const long long n_pix = (long long)width * height;
     rtw::TpParams<T> U;
@@ -82,7 +97,20 @@ int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
     (void)hipGetLastError();
     const T *mp = (const T *)d_moment_prev;
     T *mn = (T *)d_moment_next;
-    if (mn) {
+    if (c && sp) {
+        // the tile grid: fewer tiles than the frame rule's 8 x 8 ones, so one 32-bit grid dimension holds them
+        rtw::TpClampParams<T> K;
+        memset(&K, 0, sizeof K);
+        K.ks = (T)c->sigma; K.ls = (T)c->len_scale; K.r = c->radius;
+        K.tiles_i = (unsigned)((height + rtw::TP_TI - 1) / rtw::TP_TI);
+        const unsigned tiles = K.tiles_i * (unsigned)((width + rtw::TP_TJ - 1) / rtw::TP_TJ);
+        const bool gd = (c->flags & RTW_CLAMP_GUIDES) != 0;
+#define RTW_TP_CLAMPED(MO, GD) hipLaunchKernelGGL((rtw::tp_step_clamped<T, MO, GD>), dim3(tiles), dim3(256), 0, stream, U, K, (const T *)d_image, (const V *)d_features, (const V *)sp, \
+                                                  (const V *)(sp + pb), (const T *)(sp + 2 * pb), (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn)
+        if (mn) { if (gd) RTW_TP_CLAMPED(true, true); else RTW_TP_CLAMPED(true, false); }
+        else { if (gd) RTW_TP_CLAMPED(false, true); else RTW_TP_CLAMPED(false, false); }
+#undef RTW_TP_CLAMPED
+    } else if (mn) {
         if (sp) hipLaunchKernelGGL((rtw::tp_step<T, true, true>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, (const V *)sp, (const V *)(sp + pb),
                                    (const T *)(sp + 2 * pb), (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn);
         else hipLaunchKernelGGL((rtw::tp_step<T, false, true>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, (const V *)nullptr, (const V *)nullptr,
@@ -97,13 +125,14 @@ int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
         HIP_TRY(hipEventRecord(events.e[1], stream));
         HIP_TRY(hipEventSynchronize(events.e[1]));
         HIP_TRY(hipEventElapsedTime(&ms, events.e[0], events.e[1]));
-        fprintf(stderr, "[rtw temporal] %s %dx%d %s prev=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, mn ? "step+moments" : "step", sp ? 1 : 0, ms);
+        if (c && sp) fprintf(stderr, "[rtw temporal] %s %dx%d %s r=%d guides=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, mn ? "clamped+moments" : "clamped", c->radius, c->flags & RTW_CLAMP_GUIDES, ms);
+        else fprintf(stderr, "[rtw temporal] %s %dx%d %s prev=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, mn ? "step+moments" : "step", sp ? 1 : 0, ms);
     }
     return 0;
 }
 
-int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn) { return launch_temporal<float>(t, cam, cam_prev, w, h, img, feat, sp, sn, out, st, mp, mn); }
-int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn) { return launch_temporal<double>(t, cam, cam_prev, w, h, img, feat, sp, sn, out, st, mp, mn); }
+int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn, const rtw_temporal_clamp_t *c) { return launch_temporal<float>(t, cam, cam_prev, w, h, img, feat, sp, sn, out, st, mp, mn, c); }
+int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn, const rtw_temporal_clamp_t *c) { return launch_temporal<double>(t, cam, cam_prev, w, h, img, feat, sp, sn, out, st, mp, mn, c); }
 
 // Enqueue the noise map of a state and its moment plane on `stream` of the current device (validate_temporal_noise has accepted the call): ONE launch.
 template <typename T>
@@ -140,12 +169,15 @@ int launch_temporal_noise_f32(const rtw_temporal_noise_t *n, int32_t w, int32_t 
 int launch_temporal_noise_f64(const rtw_temporal_noise_t *n, int32_t w, int32_t h, const void *st, const void *mo, void *noise, hipStream_t s) { return launch_temporal_noise<double>(n, w, h, st, mo, noise, s); }
 
 // The device-resident entry points of a step: nulls, the parameters, then the pointers' alignment and aliasing.  `moments`:
-// rtw_history_moments_device_*, the same with the two moment planes (d_moment_prev null exactly when d_state_prev is).
+// rtw_history_moments_device_*, the same with the two moment planes (d_moment_prev null exactly when d_state_prev is).  `clamped`:
+// rtw_clamped_step_device_*, either of the two with the clamp `c`.
 template <typename T, typename CamT>
 int temporal_device(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev,
-                    void *d_state_next, void *d_out, void *stream_v, bool moments = false, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr) {
-    if (!t || !cam || !d_image || !d_features || !d_state_next || !d_out || (moments && !d_moment_next)) return fail(-1, "null argument");
+                    void *d_state_next, void *d_out, void *stream_v, bool moments = false, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr, bool clamped = false,
+                    const rtw_temporal_clamp_t *c = nullptr) {
+    if (!t || !cam || !d_image || !d_features || !d_state_next || !d_out || (moments && !d_moment_next) || (clamped && !c)) return fail(-1, "null argument");
     if (int rc = validate_temporal(t, width, height, (int)sizeof(T))) return rc;
+    if (clamped) if (int rc = validate_temporal_clamp(c)) return rc;
     if ((cam_prev == nullptr) != (d_state_prev == nullptr)) return fail(-2, "cam_prev and d_state_prev must both be given or both be null (the first frame)");
     if (moments && (d_moment_prev == nullptr) != (d_state_prev == nullptr)) return fail(-2, "d_moment_prev and d_state_prev must both be given or both be null (the first frame)");
     if (moments && (((uintptr_t)d_moment_prev & 15u) || ((uintptr_t)d_moment_next & 15u))) return fail(-2, "both moment planes must be 16-byte aligned");
@@ -170,7 +202,7 @@ int temporal_device(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
     DeviceGuard guard;
     if (t->device >= 0) HIP_TRY(hipSetDevice(t->device));
     return launch_temporal<T>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, (hipStream_t)stream_v, moments ? d_moment_prev : nullptr,
-                              moments ? d_moment_next : nullptr);
+                              moments ? d_moment_next : nullptr, clamped ? c : nullptr);
 }
 
 // The device-resident entry point of the noise map: nulls, the parameters, then the pointers' alignment and aliasing.
@@ -218,6 +250,18 @@ int rtw_history_moments_device_f32(const rtw_temporal_t *t, const rtw_camera_f32
 int rtw_history_moments_device_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const void *d_image,
                                     const void *d_features, const void *d_state_prev, const void *d_moment_prev, void *d_state_next, void *d_moment_next, void *d_out, void *hip_stream) {
     return temporal_device<double>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, hip_stream, true, d_moment_prev, d_moment_next);
+}
+int rtw_clamped_step_device_f32(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height,
+                                    const void *d_image, const void *d_features, const void *d_state_prev, const void *d_moment_prev, void *d_state_next, void *d_moment_next, void *d_out,
+                                    void *hip_stream) {
+    return temporal_device<float>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, hip_stream, d_moment_prev || d_moment_next, d_moment_prev,
+                                  d_moment_next, true, c);
+}
+int rtw_clamped_step_device_f64(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
+                                    const void *d_image, const void *d_features, const void *d_state_prev, const void *d_moment_prev, void *d_state_next, void *d_moment_next, void *d_out,
+                                    void *hip_stream) {
+    return temporal_device<double>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, hip_stream, d_moment_prev || d_moment_next, d_moment_prev,
+                                   d_moment_next, true, c);
 }
 int rtw_history_noise_device_f32(const rtw_temporal_noise_t *n, int32_t width, int32_t height, const void *d_state, const void *d_moment, void *d_noise, void *hip_stream) {
     return temporal_noise_device<float>(n, width, height, d_state, d_moment, d_noise, hip_stream);

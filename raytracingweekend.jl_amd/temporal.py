@@ -14,6 +14,12 @@ relative-noise map the noise-guided filter takes -- a long history uses its own 
 (``temporal_step_moments``, ``temporal_step_moments_into``, ``temporal_noise_into``, ``TemporalAccumulator(moments=True)``,
 ``render_sequence(..., guided=True)``; witness: tests/temporal_noise_ref.py).  Its defaults ``radius=2, normal_power_log2=1,
 sigma_depth=0.1, min_len=4`` are UNTUNED.
+
+Temporal clamp (``rtw_clamped_step_*``, ``rtw_render_path_clamped_*``): the step can clamp the history it gathered to mean +- sigma
+standard deviations of the current frame's window before it blends, and shorten the history it moved (``make_temporal_clamp``,
+``temporal_step_clamped``, ``temporal_step_clamped_into``, ``TemporalAccumulator(clamp=...)``, ``render_sequence(..., clamp=...)``; witness:
+tests/temporal_clamp_ref.py).  Its defaults ``radius=1, guides=False, sigma=1, len_scale=1`` are UNTUNED.  Omitting
+``clamp`` is the plain step, call for call.
 """
 import ctypes as C
 
@@ -201,16 +207,109 @@ def temporal_noise_into(d_noise_ptr, d_state_ptr, d_moment_ptr, image_width, ima
                    C.c_void_p(int(stream))))
 
 
+_CLAMP_KEYS = ("radius", "guides", "sigma", "len_scale")
+
+
+def make_temporal_clamp(radius=1, guides=False, sigma=1.0, len_scale=1.0):
+    """-> the ``rtw_temporal_clamp_t`` of these keywords: the window of the current frame is ``(2*radius + 1)^2``, ``guides`` weights its taps
+    by the frame's coverage, normal and depth (RTW_CLAMP_GUIDES), the bounds are mean -+ ``sigma`` standard deviations, and the gathered
+    history length of a pixel the clamp moved is multiplied by ``len_scale``.  The defaults are untuned beyond the record of DESIGN.md
+    section 7.21."""
+    return _capi.TemporalClamp(int(radius), _capi.CLAMP_GUIDES if guides else 0, (C.c_int32 * 2)(0, 0), float(sigma), float(len_scale))
+
+
+def _clamp_arg(clamp):
+    """True / a dict of ``make_temporal_clamp``'s keywords -> the keywords"""
+    ck = {} if clamp is True else dict(clamp)
+    if set(ck) - set(_CLAMP_KEYS):
+        raise ValueError(f"clamp takes the keywords {_CLAMP_KEYS}, got {sorted(set(ck) - set(_CLAMP_KEYS))}")
+    return ck
+
+
+def temporal_step_clamped(image, features, cam, state=None, moment=None, cam_prev=None, *, clamp=True, moments=None, **params):
+    """``temporal_step`` with the history clamped to the current frame's neighbourhood (rtw_clamped_step_*).  ``clamp``: True, or a dict
+    of ``make_temporal_clamp``'s keywords ``radius, guides, sigma, len_scale`` (the defaults are untuned).  ``moments`` (default: whether
+    ``moment`` is given): carry the second moments as ``temporal_step_moments`` does; ``state``, ``cam_prev`` (and with moments ``moment``)
+    are None together: the first frame, which is the plain step's.  -> ``(out [H, W, 3], next_state)`` or, with moments,
+    ``(out, next_state, next_moment)``.  Other keywords: ``make_temporal``.  Blocking; ``last_stats()`` is left as it was."""
+    if isinstance(features, dict):
+        features = features["raw"]
+    image, features = np.asarray(image), np.asarray(features)
+    T = image.dtype
+    if T not in (np.dtype(np.float32), np.dtype(np.float64)) or features.dtype != T:
+        raise TypeError("image and features must both be float32 or both float64")
+    if image.ndim != 3 or image.shape[-1] != 3 or features.shape != image.shape[:-1] + (8,):
+        raise ValueError(f"expected image [H, W, 3] and features [H, W, 8], got {image.shape} and {features.shape}")
+    if 0 in image.shape:
+        raise ValueError("empty image")
+    if not clamp:
+        raise ValueError("temporal_step_clamped needs clamp=True or a dict (without a clamp: temporal_step, temporal_step_moments)")
+    if moments is None:
+        moments = moment is not None
+    if (state is None) != (cam_prev is None) or (moment is not None and (not moments or state is None)) or (moments and state is not None and moment is None):
+        raise ValueError("state, cam_prev and (with moments) moment must all be given or all be None (the first frame)")
+    H, W = image.shape[:2]
+    n_state = temporal_state_bytes(W, H, T) // T.itemsize
+    n_mom = temporal_moment_bytes(W, H, T) // T.itemsize
+    Cm = _camera_arg(cam, T.type, "cam")
+    Cp = None
+    if state is not None:
+        state = np.ascontiguousarray(state)
+        if state.dtype != T or state.shape != (n_state,):
+            raise ValueError(f"state must be a flat {T.name} array of {n_state} elements, got {state.dtype.name} {state.shape}")
+        if moments:
+            moment = np.ascontiguousarray(moment)
+            if moment.dtype != T or moment.shape != (n_mom,):
+                raise ValueError(f"moment must be a flat {T.name} array of {n_mom} elements, got {moment.dtype.name} {moment.shape}")
+        Cp = C.byref(_camera_arg(cam_prev, T.type, "cam_prev"))
+    tp = make_temporal(**params)
+    tc = make_temporal_clamp(**_clamp_arg(clamp))
+    img = np.ascontiguousarray(np.swapaxes(image, 0, 1))             # the library's layout: pixel (i, j) at j*H + i
+    feat = np.ascontiguousarray(np.swapaxes(features, 0, 1))
+    out = np.empty((W, H, 3), dtype=T)
+    nxt = np.zeros(n_state, dtype=T)
+    mom = np.zeros(n_mom, dtype=T) if moments else None
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+    fn = getattr(_capi.lib(), "rtw_clamped_step_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(C.byref(tp), C.byref(tc), C.byref(Cm), Cp, W, H, ptr(img), ptr(feat), ptr(state), ptr(moment) if moments else None, ptr(nxt), ptr(mom), ptr(out)))
+    return (np.swapaxes(out, 0, 1), nxt, mom) if moments else (np.swapaxes(out, 0, 1), nxt)
+
+
+def temporal_step_clamped_into(d_out_ptr, d_state_next_ptr, d_image_ptr, d_features_ptr, cam, image_width, image_height, *, clamp=True, d_state_prev_ptr=None,
+                               d_moment_prev_ptr=None, d_moment_next_ptr=None, cam_prev=None, elem_type=np.float32, stream=0, **params):
+    """The device-resident clamped step (rtw_clamped_step_device_*): ``temporal_step_into`` -- or, with ``d_moment_next_ptr``,
+    ``temporal_step_moments_into`` -- with ``clamp`` (True, or a dict of ``make_temporal_clamp``'s keywords; the defaults are untuned).
+    ``d_state_prev_ptr``, ``cam_prev`` (and with moments ``d_moment_prev_ptr``) all None: the first frame.  Other keywords: ``make_temporal``."""
+    if not clamp:
+        raise ValueError("temporal_step_clamped_into needs clamp=True or a dict")
+    if (d_state_prev_ptr is None) != (cam_prev is None) or (d_moment_prev_ptr is not None and (d_moment_next_ptr is None or d_state_prev_ptr is None)) or \
+            (d_moment_next_ptr is not None and d_state_prev_ptr is not None and d_moment_prev_ptr is None):
+        raise ValueError("d_state_prev_ptr, cam_prev and (with moments) d_moment_prev_ptr must all be given or all be None (the first frame)")
+    T = np.dtype(elem_type).type
+    Cm = _camera_arg(cam, T, "cam")
+    Cp = C.byref(_camera_arg(cam_prev, T, "cam_prev")) if cam_prev is not None else None
+    tp = make_temporal(**params)
+    tc = make_temporal_clamp(**_clamp_arg(clamp))
+    vp = lambda p: C.c_void_p(int(p)) if p is not None else None
+    fn = getattr(_capi.lib(), "rtw_clamped_step_device_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(C.byref(tp), C.byref(tc), C.byref(Cm), Cp, int(image_width), int(image_height), vp(d_image_ptr), vp(d_features_ptr), vp(d_state_prev_ptr), vp(d_moment_prev_ptr),
+                   vp(d_state_next_ptr), vp(d_moment_next_ptr), vp(d_out_ptr), C.c_void_p(int(stream))))
+
+
 class TemporalAccumulator:
     """The history of one camera path on one device: two device states (torch tensors; torch is the package's plumbing for device memory)
     and the previous frame's camera.  ``step`` enqueues one ``temporal_step_into`` and swaps the states; ``reset`` forgets the history, so
     the next step is a first frame.  Steps of one accumulator must be ordered on the device (one stream, or events between streams).
     ``moments=True``: the steps carry second moments (``temporal_step_moments_into``, two moment planes besides the states) and
-    ``noise_into`` enqueues the noise map of the state the last step left."""
+    ``noise_into`` enqueues the noise map of the state the last step left.  ``clamp`` (True, or a dict of ``make_temporal_clamp``'s keywords):
+    every step is a clamped step (``temporal_step_clamped_into``), with or without moments; None: the plain steps, call for call."""
 
-    def __init__(self, image_width, image_height, *, elem_type=np.float32, device=0, moments=False, **params):
+    def __init__(self, image_width, image_height, *, elem_type=np.float32, device=0, moments=False, clamp=None, **params):
         import torch
         make_temporal(**params)                                    # (the keywords, checked now)
+        self.clamp = _clamp_arg(clamp) if clamp else None
+        if self.clamp is not None:
+            make_temporal_clamp(**self.clamp)
         self.width, self.height, self.elem_type = int(image_width), int(image_height), np.dtype(elem_type).type
         if self.width < 1 or self.height < 1:
             raise ValueError(f"empty frame {self.width} x {self.height}")
@@ -241,7 +340,12 @@ class TemporalAccumulator:
         if not isinstance(cam, Camera):
             raise TypeError("cam must be a Camera")
         prev = self._states[self._cur ^ 1].data_ptr() if self._cam_prev is not None else None
-        if self.moments:
+        if self.clamp is not None:
+            mprev = self._moments[self._cur ^ 1].data_ptr() if self.moments and self._cam_prev is not None else None
+            temporal_step_clamped_into(d_out_ptr, self._states[self._cur].data_ptr(), d_image_ptr, d_features_ptr, cam, self.width, self.height, clamp=self.clamp,
+                                       d_state_prev_ptr=prev, d_moment_prev_ptr=mprev, d_moment_next_ptr=self._moments[self._cur].data_ptr() if self.moments else None,
+                                       cam_prev=self._cam_prev, elem_type=self.elem_type, stream=stream, **self.params)
+        elif self.moments:
             mprev = self._moments[self._cur ^ 1].data_ptr() if self._cam_prev is not None else None
             temporal_step_moments_into(d_out_ptr, self._states[self._cur].data_ptr(), self._moments[self._cur].data_ptr(), d_image_ptr, d_features_ptr, cam, self.width,
                                        self.height, d_state_prev_ptr=prev, d_moment_prev_ptr=mprev, cam_prev=self._cam_prev, elem_type=self.elem_type, stream=stream, **self.params)
@@ -267,7 +371,7 @@ class TemporalAccumulator:
                             device=self.params["device"], **noise)
 
 
-def render_sequence(scene, cams, image_width=400, n_samples=1, *, seeds=None, denoise=None, guided=None, depth=16, seed=1, n_chunks=0, device=-1, gamma=True,
+def render_sequence(scene, cams, image_width=400, n_samples=1, *, seeds=None, denoise=None, guided=None, clamp=None, depth=16, seed=1, n_chunks=0, device=-1, gamma=True,
                     group_cull=False, scan_valu=False, numerics=None, normal_power_log2=1, sigma_depth=0.1, min_weight=0.25, history_max=16.0, demodulate=True):
     """N cameras along a path over one scene with history reuse, in one call on the device (rtw_render_sequence_*): one batched render, one
     batched feature pass, ``len(cams)`` temporal steps in order (view 0 is a first frame) and, with ``denoise`` (True, or a dict of
@@ -275,7 +379,8 @@ def render_sequence(scene, cams, image_width=400, n_samples=1, *, seeds=None, de
     accumulated images.  ``guided`` (True, or a dict of ``make_temporal_noise``'s keywords ``radius, normal_power_log2, sigma_depth,
     min_len``; rtw_render_path_guided_*): the steps carry second moments, a noise map follows each step and the filter pass is the
     noise-guided one over those maps -- ``denoise`` is then required (None: its defaults, ``sigma_color`` defaults to ``GUIDED_SIGMA_COLOR``) and its
-    ``demodulate`` must be the steps'.
+    ``demodulate`` must be the steps'.  ``clamp`` (True, or a dict of ``make_temporal_clamp``'s keywords ``radius, guides, sigma, len_scale``;
+    rtw_render_path_clamped_*): the steps behind view 0 are clamped steps, in any of the three forms above; the clamp's defaults are untuned.
     ``gamma`` is applied once, by the last stage.  Returns ``img[v, i, j, :]``; ``last_stats()`` reports the render.
     ``seeds``: a sequence of ``len(cams)`` ints (None: ``seed`` for every view).  The temporal defaults are untuned (see the module's docstring)."""
     from .structs import flatten_scene
@@ -307,7 +412,12 @@ def render_sequence(scene, cams, image_width=400, n_samples=1, *, seeds=None, de
                           (_capi.FLAG_GROUP_CULL if group_cull else 0) | (_capi.FLAG_SCAN_VALU if scan_valu else 0), numerics=numerics)
     out = np.empty(n * height * int(image_width) * 3, dtype=T)
     sfx = "f64" if _capi.is_f64(T) else "f32"
-    if N is not None:
+    if clamp:
+        K = make_temporal_clamp(**_clamp_arg(clamp))
+        _capi.check(getattr(L, "rtw_render_path_clamped_" + sfx)(C.byref(S), _capi.make_cameras(cams, T), n, sd, C.byref(P), C.byref(tp), C.byref(K),
+                                                                 C.byref(N) if N is not None else None, C.byref(D) if D is not None else None,
+                                                                 out.ctypes.data_as(C.c_void_p)))
+    elif N is not None:
         _capi.check(getattr(L, "rtw_render_path_guided_" + sfx)(C.byref(S), _capi.make_cameras(cams, T), n, sd, C.byref(P), C.byref(tp), C.byref(N), C.byref(D),
                                                                     out.ctypes.data_as(C.c_void_p)))
     else:

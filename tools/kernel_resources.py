@@ -50,6 +50,9 @@ for r in rows:
     elif re.match(r"_ZN3rtw\d+tp_stepI([fd])Lb([01])E", n):
         m = re.match(r"_ZN3rtw\d+tp_stepI([fd])Lb([01])E(?:Lb([01])E)?", n)
         label = f"temporal tp_step<{'f32' if m.group(1) == 'f' else 'f64'}{', has_prev' if m.group(2) == '1' else ', first frame'}{', moments' if m.group(3) == '1' else ''}>"
+    elif re.match(r"_ZN3rtw\d+tp_step_clampedI([fd])Lb([01])ELb([01])E", n):
+        m = re.match(r"_ZN3rtw\d+tp_step_clampedI([fd])Lb([01])ELb([01])E", n)
+        label = f"temporal tp_step_clamped<{'f32' if m.group(1) == 'f' else 'f64'}{', moments' if m.group(2) == '1' else ''}{', guides' if m.group(3) == '1' else ''}>"
     elif re.match(r"_ZN3rtw\d+tp_noiseI([fd])", n):
         label = "temporal tp_noise<%s>" % ("f32" if re.match(r"_ZN3rtw\d+tp_noiseI([fd])", n).group(1) == "f" else "f64")
     elif re.match(r"_ZN3rtw\d+pr_presentI([fd])Li([34])ELb([01])E", n):
