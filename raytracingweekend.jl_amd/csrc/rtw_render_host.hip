@@ -574,83 +574,6 @@ template <typename T> struct TemporalRegions {
     }
 };
 
-// One temporal step on host buffers (rtw_temporal_*): a leased context of the device like filter_host's, two or three H2D, ONE launch, two D2H
-// (the next state, the image).  This thread's last render (rtw_stats) is not touched.
-template <typename T, typename CamT>
-int temporal_host(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const T *image, const T *features, const void *state_prev,
-                  void *state_next, T *out) {
-    if (!t || !cam || !image || !features || !state_next || !out) return fail(-1, "null argument");
-    if (int rc = validate_temporal(t, width, height, (int)sizeof(T))) return rc;
-    if ((cam_prev == nullptr) != (state_prev == nullptr)) return fail(-2, "cam_prev and state_prev must both be given or both be null (the first frame)");
-    const TemporalRegions<T> R(width, height, 1, false);
-    const size_t feat_b = R.feat_b, img_b = R.img_b, st_b = R.st_b;
-    if (ranges_overlap(out, img_b, state_next, st_b)) return fail(-2, "out and state_next may not alias each other");
-    if (ranges_overlap(out, img_b, image, img_b) || ranges_overlap(out, img_b, features, feat_b) || (state_prev && ranges_overlap(out, img_b, state_prev, st_b)))
-        return fail(-2, "out may not alias an input");
-    if (ranges_overlap(state_next, st_b, image, img_b) || ranges_overlap(state_next, st_b, features, feat_b) || (state_prev && ranges_overlap(state_next, st_b, state_prev, st_b)))
-        return fail(-2, "state_next may not alias an input");
-    DeviceGuard guard;
-    HostLease L;
-    if (int rc = acquire_host(t->device, std::vector<unsigned char>(), &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total)) return rc;
-    char *base = (char *)hc->d_img;
-    int rc = 0;
-    hipError_t e = hipMemcpyAsync(base, image, img_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_feat, features, feat_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess && state_prev) e = hipMemcpyAsync(base + R.off_st[0], state_prev, st_b, hipMemcpyHostToDevice, hc->stream);
-    if (e != hipSuccess) rc = fail((int)e, "upload of the temporal step's inputs failed: %s", hipGetErrorString(e));
-    if (!rc) rc = launch_temporal_t(t, cam, cam_prev, width, height, base, base + R.off_feat, state_prev ? base + R.off_st[0] : nullptr, base + R.off_st[1], base + R.off_acc, hc->stream);
-    if (!rc) {
-        e = hipMemcpyAsync(state_next, base + R.off_st[1], st_b, hipMemcpyDeviceToHost, hc->stream);
-        if (e != hipSuccess) rc = fail((int)e, "download of the next state failed: %s", hipGetErrorString(e));
-    }
-    if (!rc) rc = copy_out(hc, base + R.off_acc, out, img_b);
-    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
-    return rc;
-}
-
-// N cameras along a path with history reuse (rtw_render_sequence_*): the one-device path above with a device buffer that holds the linear images
-// (ONE batched render with gamma 0), the features (ONE batched pass over all chunks), the accumulated images (n_views temporal steps in view
-// order, two states ping-pong) and, with `d`, the filtered images and the filter's workspace (ONE batched filter pass); 2 + n_views (+ 1 + levels)
-// launches on the context's stream, ONE D2H.  p->gamma is applied by the last stage that runs.  rtw_stats() reports the render's record.
-// `c` non-null (rtw_render_path_clamped_*): the steps behind view 0 are clamped steps, launch for launch.
-template <typename T, typename SceneT, typename CamT>
-int render_host_sequence(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t, const rtw_denoise_t *d, T *out,
-                         const rtw_temporal_clamp_t *c = nullptr) {
-    if (!p) return fail(-1, "null params");
-    if (!scene || !cams || !t || !out) return fail(-1, "null argument");
-    int nch, cs;
-    if (int rc = validate_features_batch(cams, n_views, p, 0, 1, out, &nch, &cs)) return rc;
-    if (d) if (int rc = validate_filter_batch(d, p->width, p->height, n_views)) return rc;
-    if (int rc = validate_temporal(t, p->width, p->height, (int)sizeof(T))) return rc;
-    if (c) if (int rc = validate_temporal_clamp(c)) return rc;
-    DeviceGuard guard;
-    release_last();
-    const TemporalRegions<T> R(p->width, p->height, (size_t)n_views, d != nullptr);
-    RenderRec *frec = nullptr;
-    CtxPtr fctx;
-    const int rc = render_one_device(p->device, scene, p, R.total, d ? R.off_flt : R.off_acc, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
-        char *base = (char *)hc->d_img;
-        q.gamma = 0;
-        rtw_temporal_t tt = *t;
-        tt.gamma = d ? 0 : (p->gamma != 0); tt.device = hc->device;
-        int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
-        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec, &fctx);
-        for (int v = 0; v < n_views && !rc; ++v)
-            rc = launch_temporal_t(&tt, cams + v, v ? cams + (v - 1) : nullptr, p->width, p->height, base + (size_t)v * R.frame_b, base + R.off_feat + (size_t)v * (R.feat_b / (size_t)n_views),
-                                   v ? base + R.off_st[(v & 1) ^ 1] : nullptr, base + R.off_st[v & 1], base + R.off_acc + (size_t)v * R.frame_b, hc->stream, nullptr, nullptr, c);
-        if (!rc && d) {
-            rtw_denoise_t dd = *d;
-            dd.gamma = p->gamma != 0; dd.device = hc->device;
-            rc = launch_denoise_t(&dd, p->width, p->height, n_views, (const T *)(base + R.off_acc), base + R.off_feat, base + R.off_flt, base + R.off_work, hc->stream);
-        }
-        return rc;
-    });
-    if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
-    return rc;
-}
-
 // The regions of the temporal paths with moments: TemporalRegions (always with the filter's regions when `filter`), then two moment planes and
 // the noise maps of `frames` views -- each starts on a 16-byte boundary.
 template <typename T> struct MomentRegions : TemporalRegions<T> {
@@ -664,74 +587,29 @@ template <typename T> struct MomentRegions : TemporalRegions<T> {
     }
 };
 
-// One temporal step with moments and the noise map of what it leaves, on host buffers (rtw_history_moments_*): temporal_host's path with two more
-// buffers each way -- two to four H2D, TWO launches (the step, the map), four D2H.  This thread's last render (rtw_stats) is not touched.
+// One temporal step on host buffers (rtw_temporal_*, rtw_history_moments_*, rtw_clamped_step_*): a leased context of the device like
+// filter_host's, two to four H2D, the step's launch (`c`: a clamped step) and, with `n`, the launch of the noise map of what it leaves, then
+// two to four D2H (the next state, its moments, the map; the image last).  The moment planes take part when either is given; moment_next
+// must then be.  `form_args`: what the entry point requires beyond that (n, moment_next and noise; or c) is there.  This thread's last
+// render (rtw_stats) is not touched.
 template <typename T, typename CamT>
-int temporal_moments_host(const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const T *image, const T *features,
-                          const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, T *out, T *noise) {
-    if (!t || !n || !cam || !image || !features || !state_next || !moment_next || !out || !noise) return fail(-1, "null argument");
+int temporal_step_host(bool form_args, const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const CamT *cam, const CamT *cam_prev, int32_t width,
+                       int32_t height, const T *image, const T *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, T *out, T *noise) {
+    const bool moments = moment_prev || moment_next;
+    if (!form_args || !t || !cam || !image || !features || !state_next || !out || (moments && !moment_next)) return fail(-1, "null argument");
     if (int rc = validate_temporal(t, width, height, (int)sizeof(T))) return rc;
-    if (int rc = validate_temporal_noise(n, width, height, (int)sizeof(T))) return rc;
+    if (n) if (int rc = validate_temporal_noise(n, width, height, (int)sizeof(T))) return rc;
+    if (c) if (int rc = validate_temporal_clamp(c)) return rc;
     if ((cam_prev == nullptr) != (state_prev == nullptr)) return fail(-2, "cam_prev and state_prev must both be given or both be null (the first frame)");
-    if ((moment_prev == nullptr) != (state_prev == nullptr)) return fail(-2, "moment_prev and state_prev must both be given or both be null (the first frame)");
+    if (moments && (moment_prev == nullptr) != (state_prev == nullptr)) return fail(-2, "moment_prev and state_prev must both be given or both be null (the first frame)");
     const MomentRegions<T> R(width, height, 1, false);
-    // the four outputs against each other and against every input
+    // the outputs that are there against each other and against every input that is
     const void *outs[4] = {out, state_next, moment_next, noise}, *ins[4] = {image, features, state_prev, moment_prev};
     const size_t out_b[4] = {R.img_b, R.st_b, R.mo_b, R.noise_b}, in_b[4] = {R.img_b, R.feat_b, R.st_b, R.mo_b};
     static const char *const names[4] = {"out", "state_next", "moment_next", "noise"};
     for (int a = 0; a < 4; ++a) {
-        for (int b = a + 1; b < 4; ++b)
-            if (ranges_overlap(outs[a], out_b[a], outs[b], out_b[b])) return fail(-2, "%s and %s may not alias each other", names[a], names[b]);
-        for (int b = 0; b < 4; ++b)
-            if (ins[b] && ranges_overlap(outs[a], out_b[a], ins[b], in_b[b])) return fail(-2, "%s may not alias an input", names[a]);
-    }
-    DeviceGuard guard;
-    HostLease L;
-    if (int rc = acquire_host(t->device, std::vector<unsigned char>(), &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total_m)) return rc;
-    char *base = (char *)hc->d_img;
-    int rc = 0;
-    hipError_t e = hipMemcpyAsync(base, image, R.img_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_feat, features, R.feat_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess && state_prev) e = hipMemcpyAsync(base + R.off_st[0], state_prev, R.st_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess && state_prev) e = hipMemcpyAsync(base + R.off_mo[0], moment_prev, R.mo_b, hipMemcpyHostToDevice, hc->stream);
-    if (e != hipSuccess) rc = fail((int)e, "upload of the temporal step's inputs failed: %s", hipGetErrorString(e));
-    rtw_temporal_noise_t nn = *n;
-    nn.device = hc->device;
-    if (!rc) rc = launch_temporal_t(t, cam, cam_prev, width, height, base, base + R.off_feat, state_prev ? base + R.off_st[0] : nullptr, base + R.off_st[1], base + R.off_acc, hc->stream,
-                                    state_prev ? base + R.off_mo[0] : nullptr, base + R.off_mo[1]);
-    if (!rc) rc = launch_temporal_noise_t(&nn, width, height, base + R.off_st[1], base + R.off_mo[1], (T *)(base + R.off_noise), hc->stream);
-    if (!rc) {
-        e = hipMemcpyAsync(state_next, base + R.off_st[1], R.st_b, hipMemcpyDeviceToHost, hc->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(moment_next, base + R.off_mo[1], R.mo_b, hipMemcpyDeviceToHost, hc->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(noise, base + R.off_noise, R.noise_b, hipMemcpyDeviceToHost, hc->stream);
-        if (e != hipSuccess) rc = fail((int)e, "download of the next state, its moments or the noise map failed: %s", hipGetErrorString(e));
-    }
-    if (!rc) rc = copy_out(hc, base + R.off_acc, out, R.img_b);
-    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
-    return rc;
-}
-
-// One clamped step on host buffers (rtw_clamped_step_*): temporal_host's path with the clamp `c` and, when moment_next is given, the two moment
-// planes of temporal_moments_host (no noise map) -- two to four H2D, ONE launch, two or three D2H.  This thread's last render (rtw_stats) is not touched.
-template <typename T, typename CamT>
-int temporal_clamped_host(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const T *image, const T *features,
-                          const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, T *out) {
-    const bool moments = moment_prev || moment_next;
-    if (!t || !c || !cam || !image || !features || !state_next || !out || (moments && !moment_next)) return fail(-1, "null argument");
-    if (int rc = validate_temporal(t, width, height, (int)sizeof(T))) return rc;
-    if (int rc = validate_temporal_clamp(c)) return rc;
-    if ((cam_prev == nullptr) != (state_prev == nullptr)) return fail(-2, "cam_prev and state_prev must both be given or both be null (the first frame)");
-    if (moments && (moment_prev == nullptr) != (state_prev == nullptr)) return fail(-2, "moment_prev and state_prev must both be given or both be null (the first frame)");
-    const MomentRegions<T> R(width, height, 1, false);
-    // the outputs against each other and against every input
-    const void *outs[3] = {out, state_next, moment_next}, *ins[4] = {image, features, state_prev, moment_prev};
-    const size_t out_b[3] = {R.img_b, R.st_b, R.mo_b}, in_b[4] = {R.img_b, R.feat_b, R.st_b, R.mo_b};
-    static const char *const names[3] = {"out", "state_next", "moment_next"};
-    for (int a = 0; a < 3; ++a) {
         if (!outs[a]) continue;
-        for (int b = a + 1; b < 3; ++b)
+        for (int b = a + 1; b < 4; ++b)
             if (outs[b] && ranges_overlap(outs[a], out_b[a], outs[b], out_b[b])) return fail(-2, "%s and %s may not alias each other", names[a], names[b]);
         for (int b = 0; b < 4; ++b)
             if (ins[b] && ranges_overlap(outs[a], out_b[a], ins[b], in_b[b])) return fail(-2, "%s may not alias an input", names[a]);
@@ -750,57 +628,69 @@ int temporal_clamped_host(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c
     if (e != hipSuccess) rc = fail((int)e, "upload of the temporal step's inputs failed: %s", hipGetErrorString(e));
     if (!rc) rc = launch_temporal_t(t, cam, cam_prev, width, height, base, base + R.off_feat, state_prev ? base + R.off_st[0] : nullptr, base + R.off_st[1], base + R.off_acc, hc->stream,
                                     moment_prev ? base + R.off_mo[0] : nullptr, moments ? base + R.off_mo[1] : nullptr, c);
+    if (!rc && n) {
+        rtw_temporal_noise_t nn = *n;
+        nn.device = hc->device;
+        rc = launch_temporal_noise_t(&nn, width, height, base + R.off_st[1], base + R.off_mo[1], (T *)(base + R.off_noise), hc->stream);
+    }
     if (!rc) {
         e = hipMemcpyAsync(state_next, base + R.off_st[1], R.st_b, hipMemcpyDeviceToHost, hc->stream);
         if (e == hipSuccess && moments) e = hipMemcpyAsync(moment_next, base + R.off_mo[1], R.mo_b, hipMemcpyDeviceToHost, hc->stream);
-        if (e != hipSuccess) rc = fail((int)e, "download of the next state or its moments failed: %s", hipGetErrorString(e));
+        if (e == hipSuccess && n) e = hipMemcpyAsync(noise, base + R.off_noise, R.noise_b, hipMemcpyDeviceToHost, hc->stream);
+        if (e != hipSuccess) rc = fail((int)e, "download of the next state, its moments or the noise map failed: %s", hipGetErrorString(e));
     }
     if (!rc) rc = copy_out(hc, base + R.off_acc, out, R.img_b);
     if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
     return rc;
 }
 
-// rtw_render_path_guided_*: render_host_sequence with the filter required, the steps with moments, one noise launch behind each step (into
-// view v of the noise region, before the ping-pong reuses that state: stream order) and the NOISE-GUIDED batched filter pass over the N maps;
-// 2 + 2*n_views + 1 + levels launches on the context's stream, ONE D2H.  p->gamma is applied by the filter.  rtw_stats() reports the render's record.
+// N cameras along a path with history reuse (rtw_render_sequence_*): the one-device path above with a device buffer that holds the linear images
+// (ONE batched render with gamma 0), the features (ONE batched pass over all chunks), the accumulated images (n_views temporal steps in view
+// order, two states ping-pong) and, with `d`, the filtered images and the filter's workspace (ONE batched filter pass); 2 + n_views (+ 1 + levels)
+// launches on the context's stream, ONE D2H.  p->gamma is applied by the last stage that runs.  rtw_stats() reports the render's record.
+// `n` non-null (rtw_render_path_guided_*; d is then there): the steps carry moments (two moment planes ping-pong with the states), one noise
+// launch follows each step (into view v of the noise region, before the ping-pong reuses that state: stream order) and the filter pass is the
+// NOISE-GUIDED one over the N maps: 2 + 2*n_views + 1 + levels launches.  `guided` says only that the ENTRY POINT requires n and d, so that
+// a null one is refused with -1 and not taken for the plain form; what runs is decided by n alone.
 // `c` non-null (rtw_render_path_clamped_*): the steps behind view 0 are clamped steps, launch for launch.
 template <typename T, typename SceneT, typename CamT>
-int render_host_sequence_guided(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t, const rtw_temporal_noise_t *n,
-                                const rtw_denoise_t *d, T *out, const rtw_temporal_clamp_t *c = nullptr) {
+int render_host_sequence(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t, const rtw_temporal_noise_t *n,
+                         const rtw_denoise_t *d, T *out, const rtw_temporal_clamp_t *c = nullptr, bool guided = false) {
     if (!p) return fail(-1, "null params");
-    if (!scene || !cams || !t || !n || !d || !out) return fail(-1, "null argument");
+    if (!scene || !cams || !t || !out || (guided && (!n || !d))) return fail(-1, "null argument");
     int nch, cs;
     if (int rc = validate_features_batch(cams, n_views, p, 0, 1, out, &nch, &cs)) return rc;
-    if (int rc = validate_filter_batch(d, p->width, p->height, n_views)) return rc;
+    if (d) if (int rc = validate_filter_batch(d, p->width, p->height, n_views)) return rc;
     if (int rc = validate_temporal(t, p->width, p->height, (int)sizeof(T))) return rc;
-    if (int rc = validate_temporal_noise(n, p->width, p->height, (int)sizeof(T))) return rc;
+    if (n) if (int rc = validate_temporal_noise(n, p->width, p->height, (int)sizeof(T))) return rc;
     if (c) if (int rc = validate_temporal_clamp(c)) return rc;
-    if (((t->flags & RTW_TEMPORAL_DEMODULATE) != 0) != ((d->flags & RTW_DENOISE_DEMODULATE) != 0))
+    if (n && ((t->flags & RTW_TEMPORAL_DEMODULATE) != 0) != ((d->flags & RTW_DENOISE_DEMODULATE) != 0))
         return fail(-2, "the DEMODULATE flags of t and d must agree (the noise map is relative to the state's luminance)");
     DeviceGuard guard;
     release_last();
-    const MomentRegions<T> R(p->width, p->height, (size_t)n_views, true);
+    const MomentRegions<T> R(p->width, p->height, (size_t)n_views, d != nullptr);
     RenderRec *frec = nullptr;
     CtxPtr fctx;
-    const int rc = render_one_device(p->device, scene, p, R.total_m, R.off_flt, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+    const int rc = render_one_device(p->device, scene, p, n ? R.total_m : R.total, d ? R.off_flt : R.off_acc, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
         char *base = (char *)hc->d_img;
         q.gamma = 0;
         rtw_temporal_t tt = *t;
-        tt.gamma = 0; tt.device = hc->device;
-        rtw_temporal_noise_t nn = *n;
+        tt.gamma = d ? 0 : (p->gamma != 0); tt.device = hc->device;
+        rtw_temporal_noise_t nn = n ? *n : rtw_temporal_noise_t();
         nn.device = hc->device;
         int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
         if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec, &fctx);
         for (int v = 0; v < n_views && !rc; ++v) {
             rc = launch_temporal_t(&tt, cams + v, v ? cams + (v - 1) : nullptr, p->width, p->height, base + (size_t)v * R.frame_b, base + R.off_feat + (size_t)v * (R.feat_b / (size_t)n_views),
                                    v ? base + R.off_st[(v & 1) ^ 1] : nullptr, base + R.off_st[v & 1], base + R.off_acc + (size_t)v * R.frame_b, hc->stream,
-                                   v ? base + R.off_mo[(v & 1) ^ 1] : nullptr, base + R.off_mo[v & 1], c);
-            if (!rc) rc = launch_temporal_noise_t(&nn, p->width, p->height, base + R.off_st[v & 1], base + R.off_mo[v & 1], (T *)(base + R.off_noise + (size_t)v * R.noise_b), hc->stream);
+                                   n && v ? base + R.off_mo[(v & 1) ^ 1] : nullptr, n ? base + R.off_mo[v & 1] : nullptr, c);
+            if (!rc && n) rc = launch_temporal_noise_t(&nn, p->width, p->height, base + R.off_st[v & 1], base + R.off_mo[v & 1], (T *)(base + R.off_noise + (size_t)v * R.noise_b), hc->stream);
         }
-        if (!rc) {
+        if (!rc && d) {
             rtw_denoise_t dd = *d;
             dd.gamma = p->gamma != 0; dd.device = hc->device;
-            rc = launch_denoise_t(&dd, p->width, p->height, n_views, (const T *)(base + R.off_acc), base + R.off_feat, base + R.off_flt, base + R.off_work, hc->stream, base + R.off_noise);
+            rc = launch_denoise_t(&dd, p->width, p->height, n_views, (const T *)(base + R.off_acc), base + R.off_feat, base + R.off_flt, base + R.off_work, hc->stream,
+                                  n ? base + R.off_noise : nullptr);
         }
         return rc;
     });
@@ -815,7 +705,7 @@ int render_host_sequence_clamped(const SceneT *scene, const CamT *cams, int32_t 
     if (!p) return fail(-1, "null params");
     if (!c) return fail(-1, "null temporal clamp parameters");
     if (n && !d) return fail(-2, "a noise map (n) guides the filter: d is required with it");
-    return n ? render_host_sequence_guided<T>(scene, cams, n_views, seeds, p, t, n, d, out, c) : render_host_sequence<T>(scene, cams, n_views, seeds, p, t, d, out, c);
+    return render_host_sequence<T>(scene, cams, n_views, seeds, p, t, n, d, out, c, n != nullptr);
 }
 
 // What an accumulator holds, denoised (rtw_accum_filtered_f32/_f64): the gamma-0 resolve (per tile for an adaptive accumulator), the feature
@@ -981,27 +871,27 @@ int rtw_render_upsampled_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_
 
 int rtw_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height, const float *image, const float *features,
                      const void *state_prev, void *state_next, float *out) {
-    return temporal_host<float>(t, cam, cam_prev, width, height, image, features, state_prev, state_next, out);
+    return temporal_step_host<float>(true, t, nullptr, nullptr, cam, cam_prev, width, height, image, features, state_prev, nullptr, state_next, nullptr, out, nullptr);
 }
 int rtw_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const double *image, const double *features,
                      const void *state_prev, void *state_next, double *out) {
-    return temporal_host<double>(t, cam, cam_prev, width, height, image, features, state_prev, state_next, out);
+    return temporal_step_host<double>(true, t, nullptr, nullptr, cam, cam_prev, width, height, image, features, state_prev, nullptr, state_next, nullptr, out, nullptr);
 }
 int rtw_history_moments_f32(const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height,
                              const float *image, const float *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, float *out, float *noise) {
-    return temporal_moments_host<float>(t, n, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, noise);
+    return temporal_step_host<float>(n && moment_next && noise, t, nullptr, n, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, noise);
 }
 int rtw_history_moments_f64(const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
                              const double *image, const double *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, double *out, double *noise) {
-    return temporal_moments_host<double>(t, n, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, noise);
+    return temporal_step_host<double>(n && moment_next && noise, t, nullptr, n, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, noise);
 }
 int rtw_clamped_step_f32(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height,
                              const float *image, const float *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, float *out) {
-    return temporal_clamped_host<float>(t, c, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out);
+    return temporal_step_host<float>(c != nullptr, t, c, nullptr, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, nullptr);
 }
 int rtw_clamped_step_f64(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
                              const double *image, const double *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, double *out) {
-    return temporal_clamped_host<double>(t, c, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out);
+    return temporal_step_host<double>(c != nullptr, t, c, nullptr, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, nullptr);
 }
 int rtw_render_path_clamped_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                                  const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, float *out) {
@@ -1013,19 +903,19 @@ int rtw_render_path_clamped_f64(const rtw_scene_f64 *scene, const rtw_camera_f64
 }
 int rtw_render_path_guided_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                                    const rtw_temporal_noise_t *n, const rtw_denoise_t *d, float *out) {
-    return render_host_sequence_guided<float>(scene, cams, batch_views(n_views), seeds, p, t, n, d, out);
+    return render_host_sequence<float>(scene, cams, batch_views(n_views), seeds, p, t, n, d, out, nullptr, true);
 }
 int rtw_render_path_guided_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                                    const rtw_temporal_noise_t *n, const rtw_denoise_t *d, double *out) {
-    return render_host_sequence_guided<double>(scene, cams, batch_views(n_views), seeds, p, t, n, d, out);
+    return render_host_sequence<double>(scene, cams, batch_views(n_views), seeds, p, t, n, d, out, nullptr, true);
 }
 int rtw_render_sequence_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                             const rtw_denoise_t *d, float *out) {
-    return render_host_sequence<float>(scene, cams, batch_views(n_views), seeds, p, t, d, out);
+    return render_host_sequence<float>(scene, cams, batch_views(n_views), seeds, p, t, nullptr, d, out);
 }
 int rtw_render_sequence_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                             const rtw_denoise_t *d, double *out) {
-    return render_host_sequence<double>(scene, cams, batch_views(n_views), seeds, p, t, d, out);
+    return render_host_sequence<double>(scene, cams, batch_views(n_views), seeds, p, t, nullptr, d, out);
 }
 
 int rtw_accum_filtered_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, rtw_accum_handle accum, int32_t guided, float *out) {

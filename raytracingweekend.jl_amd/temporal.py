@@ -56,11 +56,11 @@ def _camera_arg(cam, T, what):
     return _capi.make_camera(cam, T)
 
 
-def temporal_step(image, features, cam, state=None, cam_prev=None, **params):
-    """One step on host arrays (rtw_temporal_*): ``image`` [H, W, 3] (linear) and ``features`` [H, W, 8] -- or the dict ``render_features``
-    returns -- of the frame seen through ``cam``; ``state``: what the previous step returned, with ``cam_prev`` the camera of that frame
-    (both None: the first frame).  -> ``(out [H, W, 3], next_state)``; a state is a flat array of ``temporal_state_bytes`` bytes in the
-    public layout of the header.  Keywords: ``make_temporal``.  Blocking; ``last_stats()`` is left as it was."""
+def _host_step(name, image, features, cam, state, moment, cam_prev, params, *, check, head=None, planes=True, moments=False, noise_map=False):
+    """One step on host arrays through the entry point ``name``: the checks of the arrays, then ``check()`` (the caller's own rule about its
+    arguments; it raises), the state's and -- with ``moments`` -- the moment's, the library's layout,
+    ``make_temporal(**params)`` and the struct ``head()`` makes behind it, the call.  ``planes``: the entry point takes the two moment
+    planes (null without ``moments``); ``noise_map``: and the map.  -> ``(out [H, W, 3], next_state, next_moment or None, map [H, W] or None)``."""
     if isinstance(features, dict):
         features = features["raw"]
     image, features = np.asarray(image), np.asarray(features)
@@ -71,26 +71,55 @@ def temporal_step(image, features, cam, state=None, cam_prev=None, **params):
         raise ValueError(f"expected image [H, W, 3] and features [H, W, 8], got {image.shape} and {features.shape}")
     if 0 in image.shape:
         raise ValueError("empty image")
-    if (state is None) != (cam_prev is None):
-        raise ValueError("state and cam_prev must both be given or both be None (the first frame)")
+    check()
     H, W = image.shape[:2]
     n_state = temporal_state_bytes(W, H, T) // T.itemsize
+    n_mom = temporal_moment_bytes(W, H, T) // T.itemsize
     Cm = _camera_arg(cam, T.type, "cam")
     Cp = None
     if state is not None:
         state = np.ascontiguousarray(state)
         if state.dtype != T or state.shape != (n_state,):
             raise ValueError(f"state must be a flat {T.name} array of {n_state} elements, got {state.dtype.name} {state.shape}")
+        if moments:
+            moment = np.ascontiguousarray(moment)
+            if moment.dtype != T or moment.shape != (n_mom,):
+                raise ValueError(f"moment must be a flat {T.name} array of {n_mom} elements, got {moment.dtype.name} {moment.shape}")
         Cp = C.byref(_camera_arg(cam_prev, T.type, "cam_prev"))
-    tp = make_temporal(**params)
+    heads = [C.byref(make_temporal(**params))] + ([C.byref(head())] if head else [])
     img = np.ascontiguousarray(np.swapaxes(image, 0, 1))             # the library's layout: pixel (i, j) at j*H + i
     feat = np.ascontiguousarray(np.swapaxes(features, 0, 1))
-    out = np.empty((W, H, 3), dtype=T)
-    nxt = np.zeros(n_state, dtype=T)
-    fn = getattr(_capi.lib(), "rtw_temporal_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(tp), C.byref(Cm), Cp, W, H, img.ctypes.data_as(C.c_void_p), feat.ctypes.data_as(C.c_void_p),
-                   state.ctypes.data_as(C.c_void_p) if state is not None else None, nxt.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)))
-    return np.swapaxes(out, 0, 1), nxt
+    out, nxt = np.empty((W, H, 3), dtype=T), np.zeros(n_state, dtype=T)
+    mom = np.zeros(n_mom, dtype=T) if moments else None
+    rho = np.empty((W, H), dtype=T) if noise_map else None
+    arrays = [img, feat, state] + ([moment if moments else None] if planes else []) + [nxt] + ([mom] if planes else []) + [out] + ([rho] if noise_map else [])
+    fn = getattr(_capi.lib(), name + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(*heads, C.byref(Cm), Cp, W, H, *(a.ctypes.data_as(C.c_void_p) if a is not None else None for a in arrays)))
+    return np.swapaxes(out, 0, 1), nxt, mom, np.swapaxes(rho, 0, 1) if noise_map else None
+
+
+def _enqueue_step(name, cam, cam_prev, image_width, image_height, elem_type, stream, params, clamp, *ptrs):
+    """A device-resident step: the cameras, ``make_temporal(**params)``, with ``clamp`` its parameters behind them, the frame, the DEVICE
+    pointers in the entry point's order (None: a null pointer) and the stream -> ``name`` + the element type's suffix."""
+    T = np.dtype(elem_type).type
+    Cm = _camera_arg(cam, T, "cam")
+    Cp = C.byref(_camera_arg(cam_prev, T, "cam_prev")) if cam_prev is not None else None
+    heads = [C.byref(make_temporal(**params))]
+    if clamp is not None:
+        heads.append(C.byref(make_temporal_clamp(**_clamp_arg(clamp))))
+    fn = getattr(_capi.lib(), name + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(*heads, C.byref(Cm), Cp, int(image_width), int(image_height), *(C.c_void_p(int(q)) if q is not None else None for q in ptrs), C.c_void_p(int(stream))))
+
+
+def temporal_step(image, features, cam, state=None, cam_prev=None, **params):
+    """One step on host arrays (rtw_temporal_*): ``image`` [H, W, 3] (linear) and ``features`` [H, W, 8] -- or the dict ``render_features``
+    returns -- of the frame seen through ``cam``; ``state``: what the previous step returned, with ``cam_prev`` the camera of that frame
+    (both None: the first frame).  -> ``(out [H, W, 3], next_state)``; a state is a flat array of ``temporal_state_bytes`` bytes in the
+    public layout of the header.  Keywords: ``make_temporal``.  Blocking; ``last_stats()`` is left as it was."""
+    def check():
+        if (state is None) != (cam_prev is None):
+            raise ValueError("state and cam_prev must both be given or both be None (the first frame)")
+    return _host_step("rtw_temporal_", image, features, cam, state, None, cam_prev, params, check=check, planes=False)[:2]
 
 
 def temporal_step_into(d_out_ptr, d_state_next_ptr, d_image_ptr, d_features_ptr, cam, image_width, image_height, *, d_state_prev_ptr=None, cam_prev=None,
@@ -101,14 +130,8 @@ def temporal_step_into(d_out_ptr, d_state_next_ptr, d_image_ptr, d_features_ptr,
     ``make_temporal``."""
     if (d_state_prev_ptr is None) != (cam_prev is None):
         raise ValueError("d_state_prev_ptr and cam_prev must both be given or both be None (the first frame)")
-    T = np.dtype(elem_type).type
-    Cm = _camera_arg(cam, T, "cam")
-    Cp = C.byref(_camera_arg(cam_prev, T, "cam_prev")) if cam_prev is not None else None
-    tp = make_temporal(**params)
-    fn = getattr(_capi.lib(), "rtw_temporal_device_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(tp), C.byref(Cm), Cp, int(image_width), int(image_height), C.c_void_p(int(d_image_ptr)), C.c_void_p(int(d_features_ptr)),
-                   C.c_void_p(int(d_state_prev_ptr)) if d_state_prev_ptr is not None else None, C.c_void_p(int(d_state_next_ptr)), C.c_void_p(int(d_out_ptr)),
-                   C.c_void_p(int(stream))))
+    _enqueue_step("rtw_temporal_device_", cam, cam_prev, image_width, image_height, elem_type, stream, params, None, int(d_image_ptr), int(d_features_ptr), d_state_prev_ptr,
+                  int(d_state_next_ptr), int(d_out_ptr))
 
 
 _NOISE_KEYS = ("radius", "normal_power_log2", "sigma_depth", "min_len")
@@ -143,40 +166,11 @@ def temporal_step_moments(image, features, cam, state=None, moment=None, cam_pre
     the per-pixel relative noise ``denoise``'s guided form takes (NaN where the pixel is not valid).  ``noise``: a dict of
     ``make_temporal_noise``'s keywords ``radius, normal_power_log2, sigma_depth, min_len`` (the defaults are untuned); other keywords:
     ``make_temporal``.  Blocking; ``last_stats()`` is left as it was."""
-    if isinstance(features, dict):
-        features = features["raw"]
-    image, features = np.asarray(image), np.asarray(features)
-    T = image.dtype
-    if T not in (np.dtype(np.float32), np.dtype(np.float64)) or features.dtype != T:
-        raise TypeError("image and features must both be float32 or both float64")
-    if image.ndim != 3 or image.shape[-1] != 3 or features.shape != image.shape[:-1] + (8,):
-        raise ValueError(f"expected image [H, W, 3] and features [H, W, 8], got {image.shape} and {features.shape}")
-    if 0 in image.shape:
-        raise ValueError("empty image")
-    if not ((state is None) == (cam_prev is None) == (moment is None)):
-        raise ValueError("state, moment and cam_prev must all be given or all be None (the first frame)")
-    H, W = image.shape[:2]
-    n_state = temporal_state_bytes(W, H, T) // T.itemsize
-    n_mom = temporal_moment_bytes(W, H, T) // T.itemsize
-    Cm = _camera_arg(cam, T.type, "cam")
-    Cp = None
-    if state is not None:
-        state, moment = np.ascontiguousarray(state), np.ascontiguousarray(moment)
-        if state.dtype != T or state.shape != (n_state,):
-            raise ValueError(f"state must be a flat {T.name} array of {n_state} elements, got {state.dtype.name} {state.shape}")
-        if moment.dtype != T or moment.shape != (n_mom,):
-            raise ValueError(f"moment must be a flat {T.name} array of {n_mom} elements, got {moment.dtype.name} {moment.shape}")
-        Cp = C.byref(_camera_arg(cam_prev, T.type, "cam_prev"))
-    tp = make_temporal(**params)
-    tn = make_temporal_noise(**_noise_arg(noise))
-    img = np.ascontiguousarray(np.swapaxes(image, 0, 1))             # the library's layout: pixel (i, j) at j*H + i
-    feat = np.ascontiguousarray(np.swapaxes(features, 0, 1))
-    out = np.empty((W, H, 3), dtype=T)
-    nxt, mom, rho = np.zeros(n_state, dtype=T), np.zeros(n_mom, dtype=T), np.empty((W, H), dtype=T)
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
-    fn = getattr(_capi.lib(), "rtw_history_moments_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(tp), C.byref(tn), C.byref(Cm), Cp, W, H, ptr(img), ptr(feat), ptr(state), ptr(moment), ptr(nxt), ptr(mom), ptr(out), ptr(rho)))
-    return np.swapaxes(out, 0, 1), nxt, mom, np.swapaxes(rho, 0, 1)
+    def check():
+        if not ((state is None) == (cam_prev is None) == (moment is None)):
+            raise ValueError("state, moment and cam_prev must all be given or all be None (the first frame)")
+    return _host_step("rtw_history_moments_", image, features, cam, state, moment, cam_prev, params, check=check, head=lambda: make_temporal_noise(**_noise_arg(noise)),
+                      moments=True, noise_map=True)
 
 
 def temporal_step_moments_into(d_out_ptr, d_state_next_ptr, d_moment_next_ptr, d_image_ptr, d_features_ptr, cam, image_width, image_height, *, d_state_prev_ptr=None,
@@ -186,14 +180,8 @@ def temporal_step_moments_into(d_out_ptr, d_state_next_ptr, d_moment_next_ptr, d
     the first frame.  Keywords: ``make_temporal``."""
     if not ((d_state_prev_ptr is None) == (cam_prev is None) == (d_moment_prev_ptr is None)):
         raise ValueError("d_state_prev_ptr, d_moment_prev_ptr and cam_prev must all be given or all be None (the first frame)")
-    T = np.dtype(elem_type).type
-    Cm = _camera_arg(cam, T, "cam")
-    Cp = C.byref(_camera_arg(cam_prev, T, "cam_prev")) if cam_prev is not None else None
-    tp = make_temporal(**params)
-    vp = lambda p: C.c_void_p(int(p)) if p is not None else None
-    fn = getattr(_capi.lib(), "rtw_history_moments_device_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(tp), C.byref(Cm), Cp, int(image_width), int(image_height), vp(d_image_ptr), vp(d_features_ptr), vp(d_state_prev_ptr), vp(d_moment_prev_ptr),
-                   vp(d_state_next_ptr), vp(d_moment_next_ptr), vp(d_out_ptr), C.c_void_p(int(stream))))
+    _enqueue_step("rtw_history_moments_device_", cam, cam_prev, image_width, image_height, elem_type, stream, params, None, d_image_ptr, d_features_ptr, d_state_prev_ptr,
+                  d_moment_prev_ptr, d_state_next_ptr, d_moment_next_ptr, d_out_ptr)
 
 
 def temporal_noise_into(d_noise_ptr, d_state_ptr, d_moment_ptr, image_width, image_height, *, elem_type=np.float32, stream=0, **noise):
@@ -232,47 +220,16 @@ def temporal_step_clamped(image, features, cam, state=None, moment=None, cam_pre
     ``moment`` is given): carry the second moments as ``temporal_step_moments`` does; ``state``, ``cam_prev`` (and with moments ``moment``)
     are None together: the first frame, which is the plain step's.  -> ``(out [H, W, 3], next_state)`` or, with moments,
     ``(out, next_state, next_moment)``.  Other keywords: ``make_temporal``.  Blocking; ``last_stats()`` is left as it was."""
-    if isinstance(features, dict):
-        features = features["raw"]
-    image, features = np.asarray(image), np.asarray(features)
-    T = image.dtype
-    if T not in (np.dtype(np.float32), np.dtype(np.float64)) or features.dtype != T:
-        raise TypeError("image and features must both be float32 or both float64")
-    if image.ndim != 3 or image.shape[-1] != 3 or features.shape != image.shape[:-1] + (8,):
-        raise ValueError(f"expected image [H, W, 3] and features [H, W, 8], got {image.shape} and {features.shape}")
-    if 0 in image.shape:
-        raise ValueError("empty image")
-    if not clamp:
-        raise ValueError("temporal_step_clamped needs clamp=True or a dict (without a clamp: temporal_step, temporal_step_moments)")
     if moments is None:
         moments = moment is not None
-    if (state is None) != (cam_prev is None) or (moment is not None and (not moments or state is None)) or (moments and state is not None and moment is None):
-        raise ValueError("state, cam_prev and (with moments) moment must all be given or all be None (the first frame)")
-    H, W = image.shape[:2]
-    n_state = temporal_state_bytes(W, H, T) // T.itemsize
-    n_mom = temporal_moment_bytes(W, H, T) // T.itemsize
-    Cm = _camera_arg(cam, T.type, "cam")
-    Cp = None
-    if state is not None:
-        state = np.ascontiguousarray(state)
-        if state.dtype != T or state.shape != (n_state,):
-            raise ValueError(f"state must be a flat {T.name} array of {n_state} elements, got {state.dtype.name} {state.shape}")
-        if moments:
-            moment = np.ascontiguousarray(moment)
-            if moment.dtype != T or moment.shape != (n_mom,):
-                raise ValueError(f"moment must be a flat {T.name} array of {n_mom} elements, got {moment.dtype.name} {moment.shape}")
-        Cp = C.byref(_camera_arg(cam_prev, T.type, "cam_prev"))
-    tp = make_temporal(**params)
-    tc = make_temporal_clamp(**_clamp_arg(clamp))
-    img = np.ascontiguousarray(np.swapaxes(image, 0, 1))             # the library's layout: pixel (i, j) at j*H + i
-    feat = np.ascontiguousarray(np.swapaxes(features, 0, 1))
-    out = np.empty((W, H, 3), dtype=T)
-    nxt = np.zeros(n_state, dtype=T)
-    mom = np.zeros(n_mom, dtype=T) if moments else None
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
-    fn = getattr(_capi.lib(), "rtw_clamped_step_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(tp), C.byref(tc), C.byref(Cm), Cp, W, H, ptr(img), ptr(feat), ptr(state), ptr(moment) if moments else None, ptr(nxt), ptr(mom), ptr(out)))
-    return (np.swapaxes(out, 0, 1), nxt, mom) if moments else (np.swapaxes(out, 0, 1), nxt)
+    def check():
+        if not clamp:
+            raise ValueError("temporal_step_clamped needs clamp=True or a dict (without a clamp: temporal_step, temporal_step_moments)")
+        if (state is None) != (cam_prev is None) or (moment is not None and (not moments or state is None)) or (moments and state is not None and moment is None):
+            raise ValueError("state, cam_prev and (with moments) moment must all be given or all be None (the first frame)")
+    res = _host_step("rtw_clamped_step_", image, features, cam, state, moment, cam_prev, params, check=check, head=lambda: make_temporal_clamp(**_clamp_arg(clamp)),
+                     moments=moments)
+    return res[:3] if moments else res[:2]
 
 
 def temporal_step_clamped_into(d_out_ptr, d_state_next_ptr, d_image_ptr, d_features_ptr, cam, image_width, image_height, *, clamp=True, d_state_prev_ptr=None,
@@ -285,15 +242,8 @@ def temporal_step_clamped_into(d_out_ptr, d_state_next_ptr, d_image_ptr, d_featu
     if (d_state_prev_ptr is None) != (cam_prev is None) or (d_moment_prev_ptr is not None and (d_moment_next_ptr is None or d_state_prev_ptr is None)) or \
             (d_moment_next_ptr is not None and d_state_prev_ptr is not None and d_moment_prev_ptr is None):
         raise ValueError("d_state_prev_ptr, cam_prev and (with moments) d_moment_prev_ptr must all be given or all be None (the first frame)")
-    T = np.dtype(elem_type).type
-    Cm = _camera_arg(cam, T, "cam")
-    Cp = C.byref(_camera_arg(cam_prev, T, "cam_prev")) if cam_prev is not None else None
-    tp = make_temporal(**params)
-    tc = make_temporal_clamp(**_clamp_arg(clamp))
-    vp = lambda p: C.c_void_p(int(p)) if p is not None else None
-    fn = getattr(_capi.lib(), "rtw_clamped_step_device_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(tp), C.byref(tc), C.byref(Cm), Cp, int(image_width), int(image_height), vp(d_image_ptr), vp(d_features_ptr), vp(d_state_prev_ptr), vp(d_moment_prev_ptr),
-                   vp(d_state_next_ptr), vp(d_moment_next_ptr), vp(d_out_ptr), C.c_void_p(int(stream))))
+    _enqueue_step("rtw_clamped_step_device_", cam, cam_prev, image_width, image_height, elem_type, stream, params, clamp, d_image_ptr, d_features_ptr, d_state_prev_ptr,
+                  d_moment_prev_ptr, d_state_next_ptr, d_moment_next_ptr, d_out_ptr)
 
 
 class TemporalAccumulator:
