@@ -833,7 +833,7 @@ int rtw_render_upsampled_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_
  * finite or < 1, width or height < 1, elem_bytes other than 4 or 8, misaligned or aliasing pointers, exactly one of cam_prev /
  * d_state_prev (state_prev) null -> -2; a frame of 2^31 8x8 tiles or more (the denoiser's frame rule) -> -5; the sequence call additionally
  * refuses everything rtw_render_filtered_batch_* refuses for its arguments (with `d` NULL: everything a batched feature render refuses).
- *   Left out on purpose: N independent sequences in one launch, accumulators or the upsampler as the step's input,
+ *   Left out on purpose: accumulators or the upsampler as the step's input,
  * device lists, moving spheres (the scene is static: there are no motion vectors beyond the camera's), a variance-guided alpha.
  * (Neighbourhood colour clamping: the rtw_clamped_step_* block further down.  A per-pixel noise map from the history's second moments, and the sequence call that feeds it to the
  * noise-guided filter: the block behind these declarations.)  Additive to ABI 4: detected by symbol lookup. */
@@ -919,7 +919,7 @@ int rtw_render_sequence_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *ca
  * a `d` whose DEMODULATE flags differ (the map is relative to the state's luminance).
  *   The defaults (radius 2, normal_power_log2 1, sigma_depth 0.1, min_len 4) are UNTUNED beyond the record of DESIGN.md 7.19.  Left out on
  * purpose: a variance-driven alpha, smoothing of the map, moments for accumulators or
- * the upsampler, N sequences per launch, device lists, an LDS-tiled window.  Additive to ABI 4: detected by symbol lookup. */
+ * the upsampler, device lists, an LDS-tiled window.  Additive to ABI 4: detected by symbol lookup. */
 typedef struct {
     int32_t radius;             /* 1..3: the spatial estimate's window is (2*radius + 1)^2 */
     int32_t normal_power_log2;  /* 0..7: m of the window's normal weight */
@@ -997,7 +997,7 @@ int rtw_render_path_guided_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 
  * unknown flag bits, reserved != 0, sigma not finite or < 0, len_scale outside [0, 1] or NaN -> -2; everything the underlying temporal,
  * moments or sequence call refuses, with that call's code.
  *   The defaults (radius 1, no flags, sigma 1, len_scale 1) are UNTUNED beyond the record of DESIGN.md 7.21.  Left out on purpose (DESIGN.md
- * section 9): a continuous variance-driven alpha, clamping in another colour space, clamping the second moment, N sequences per launch,
+ * section 9): a continuous variance-driven alpha, clamping in another colour space, clamping the second moment,
  * device lists.  Additive to ABI 4: detected by symbol lookup. */
 #define RTW_CLAMP_GUIDES 1      /* weight the window's taps by the current frame's guides (coverage, normal, depth) */
 typedef struct {
@@ -1025,6 +1025,68 @@ int rtw_render_path_clamped_f32(const rtw_scene_f32 *scene, const rtw_camera_f32
 int rtw_render_path_clamped_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p,
                                  const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n /* may be NULL */,
                                  const rtw_denoise_t *d /* may be NULL */, double *out);
+
+/* Batched temporal steps: n_paths independent camera paths over one scene (a stereo pair, several orbiting cameras, candidate camera moves
+ * side by side) advance in each launch.  At preview sizes a step is all launch cost; S paths share it.
+ *
+ * The definition.  There is no new arithmetic.  Path s of a batched step is, bit for bit, the single call for path s -- one of
+ * rtw_temporal_device_*, rtw_history_moments_device_* or rtw_clamped_step_device_*, chosen by the pointer rule of rtw_clamped_step_device_*
+ * extended by `c`: c == NULL is the plain step, both moment pointers NULL is the step without moments.  Path s of the batched noise map is
+ * rtw_history_noise_device_* of path s.  The arrays hold the paths one behind the other: image and out of path s at s*W*H*3 elements,
+ * features at s*W*H*8 elements, the state at byte s * rtw_temporal_state_bytes, the moment plane at byte s * rtw_history_moment_bytes, the
+ * noise map at s*W*H elements.  The padding bytes between states and between moment planes (there whenever W*H is odd) are never written.
+ * All paths of a call share t, c, n, the frame size and first-frame-ness: d_states_prev == NULL means every path resets.
+ *   The table.  A device-resident step stays ONE launch with no hidden copy and no allocation (it can be captured into a graph like its
+ * neighbours), so the per-path camera constants live in a caller-owned DEVICE table of 32 elements of T per path:
+ *     0..2 origin, 3..5 lower_left_corner, 6..8 horizontal, 9..11 vertical of the path's CURRENT camera;
+ *     12..14 origin, 15..17 w, 18..20 horizontal, 21..23 vertical of its PREVIOUS camera;
+ *     24..28 Kw, Qh, Qv, ih, iv: with q = lower_left_corner - origin of the previous camera, q.w, q.horizontal, q.vertical,
+ *     1 / horizontal.horizontal, 1 / vertical.vertical -- binary64 from the previous camera's fields, every dot product grouped
+ *     (x + y) + z, each value rounded to T once (exactly what the single step derives from cam_prev);  29..31: 0.
+ * rtw_reproject_table_* fills a HOST buffer of rtw_reproject_table_bytes bytes (pure host code; the caller uploads it); cams_prev == NULL
+ * (first frames): elements 12..28 are 0.  A step whose d_states_prev is NULL reads no element of the table; any other reads 0..28.
+ *   rtw_reproject_batch_device_*: one launch on `hip_stream`, asynchronous; rtw_stats() is left alone.  All pointers are DEVICE pointers.
+ *   rtw_reproject_noise_batch_device_*: the n_paths maps of n_paths states and their moment planes, one launch.
+ *   rtw_render_paths_*: n_paths paths of n_steps steps each in one call, host buffers, blocking, through the cached context.  The layout
+ * is STEP-major, so that the frames of one step are contiguous: path s at step k is cams[k*n_paths + s], `seeds` holds n_steps*n_paths
+ * values in the same order (or is NULL: p->seed), and frame (k, s) of `out` sits at (k*n_paths + s)*H*W*3.  On the context's stream:
+ * ONE batched render of n_steps*n_paths views with gamma 0, ONE batched feature pass, ONE H2D of the whole table, n_steps batched step
+ * launches (two sets of n_paths states -- with `n`, of moment planes -- ping-pong), with `n` one batched noise launch behind each step,
+ * with `d` ONE plain or (with `n`) noise-guided batched filter pass over all frames, ONE D2H.  p->gamma is applied once, by the last stage
+ * that runs.  `c`, `n`, `d`: the three combinations of rtw_render_path_clamped_* and additionally c == NULL (plain steps).  Path s equals,
+ * on the bits, what rtw_render_sequence_*, rtw_render_path_guided_* or rtw_render_path_clamped_* returns for that path's cameras and
+ * seeds.  rtw_stats() reports the render's record.
+ *   Refusals, all decided before any HIP call: a null argument that is not optional -> -1; n_paths < 1, n_steps < 1 or a product
+ * n_steps*n_paths beyond int32 -> -2; everything the single step, clamp and noise calls refuse, with that call's code; a table, feature
+ * buffer, state or moment plane that is not 16-byte aligned, images, out or noise not aligned to T, outputs that alias each other or an
+ * input over the full n_paths extents, exactly one of d_states_prev / d_moments_prev null when moments are on, `n` without `d`,
+ * DEMODULATE flags of `t` and `d` that differ under `n` -> -2; width*height*frames >= 2^39 (the batched filter's rule) -> -5; the paths
+ * call refuses everything the batched render, feature and filter calls refuse for n_steps*n_paths views, with that call's code.
+ *   Left out on purpose: a host-buffer form of the single batched step (the paths call is the host form), paths of
+ * different frame sizes or different t / c / n in one launch, a path that joins or resets alone mid-batch, device lists, the Julia shim,
+ * one-call forms with the upsampler or the present stage behind them (the device-resident stages compose on the caller's stream).
+ * Additive to ABI 4: detected by symbol lookup. */
+int64_t rtw_reproject_table_bytes(int32_t n_paths, int32_t elem_bytes);
+int rtw_reproject_table_f32(const rtw_camera_f32 *cams, const rtw_camera_f32 *cams_prev /* NULL: first frames */, int32_t n_paths, void *table /* host */);
+int rtw_reproject_table_f64(const rtw_camera_f64 *cams, const rtw_camera_f64 *cams_prev /* NULL: first frames */, int32_t n_paths, void *table /* host */);
+int rtw_reproject_batch_device_f32(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* may be NULL */, int32_t n_paths, const void *d_table, int32_t width,
+                                   int32_t height, const void *d_images, const void *d_features, const void *d_states_prev /* NULL: first frames */,
+                                   const void *d_moments_prev /* may be NULL */, void *d_states_next, void *d_moments_next /* may be NULL */, void *d_out,
+                                   void *hip_stream);
+int rtw_reproject_batch_device_f64(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* may be NULL */, int32_t n_paths, const void *d_table, int32_t width,
+                                   int32_t height, const void *d_images, const void *d_features, const void *d_states_prev /* NULL: first frames */,
+                                   const void *d_moments_prev /* may be NULL */, void *d_states_next, void *d_moments_next /* may be NULL */, void *d_out,
+                                   void *hip_stream);
+int rtw_reproject_noise_batch_device_f32(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int32_t n_paths, const void *d_states, const void *d_moments,
+                                         void *d_noise, void *hip_stream);
+int rtw_reproject_noise_batch_device_f64(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int32_t n_paths, const void *d_states, const void *d_moments,
+                                         void *d_noise, void *hip_stream);
+int rtw_render_paths_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_paths, int32_t n_steps, const uint64_t *seeds, const rtw_params *p,
+                         const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* may be NULL */, const rtw_temporal_noise_t *n /* may be NULL */,
+                         const rtw_denoise_t *d /* may be NULL */, float *out);
+int rtw_render_paths_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_paths, int32_t n_steps, const uint64_t *seeds, const rtw_params *p,
+                         const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* may be NULL */, const rtw_temporal_noise_t *n /* may be NULL */,
+                         const rtw_denoise_t *d /* may be NULL */, double *out);
 
 /* Present stage: display-ready 8-bit frames from the device.  Every pipeline above ends in T elements in the column-major layout of the
  * render entry points; a window, a PNG or a video encoder wants 8-bit rows.  One kernel clips, rounds, packs and transposes in HBM, and the

@@ -37,6 +37,7 @@ from .upsample import (  # noqa: F401
 from .temporal import (  # noqa: F401
     TemporalAccumulator, make_temporal, make_temporal_noise, render_sequence, temporal_moment_bytes, temporal_noise_into, temporal_state_bytes, temporal_step,
     temporal_step_into, temporal_step_moments, temporal_step_moments_into, make_temporal_clamp, temporal_step_clamped, temporal_step_clamped_into,
+    temporal_path_table, temporal_step_batch_into, temporal_noise_batch_into, TemporalBatchAccumulator, render_sequences,
 )
 from .present import (  # noqa: F401
     make_present, present, present_batch_into, present_bytes, present_into, render_presented, render_presented_batch,
@@ -61,5 +62,6 @@ __all__ = [
     "make_temporal", "temporal_state_bytes", "temporal_step", "temporal_step_into", "TemporalAccumulator", "render_sequence",
     "make_temporal_noise", "temporal_moment_bytes", "temporal_step_moments", "temporal_step_moments_into", "temporal_noise_into",
     "make_temporal_clamp", "temporal_step_clamped", "temporal_step_clamped_into",
+    "temporal_path_table", "temporal_step_batch_into", "temporal_noise_batch_into", "TemporalBatchAccumulator", "render_sequences",
     "make_present", "present_bytes", "present", "present_into", "present_batch_into", "render_presented", "render_presented_batch",
 ]

@@ -38,6 +38,8 @@ SYMBOLS = [
     "rtw_history_moments_f32", "rtw_history_moments_f64", "rtw_render_path_guided_f32", "rtw_render_path_guided_f64",
     "rtw_clamped_step_device_f32", "rtw_clamped_step_device_f64", "rtw_clamped_step_f32", "rtw_clamped_step_f64",
     "rtw_render_path_clamped_f32", "rtw_render_path_clamped_f64",
+    "rtw_reproject_table_bytes", "rtw_reproject_table_f32", "rtw_reproject_table_f64", "rtw_reproject_batch_device_f32", "rtw_reproject_batch_device_f64",
+    "rtw_reproject_noise_batch_device_f32", "rtw_reproject_noise_batch_device_f64", "rtw_render_paths_f32", "rtw_render_paths_f64",
     "rtw_present_bytes", "rtw_present_device_f32", "rtw_present_device_f64", "rtw_present_batch_device_f32", "rtw_present_batch_device_f64",
     "rtw_present_f32", "rtw_present_f64", "rtw_render_presented_f32", "rtw_render_presented_f64", "rtw_render_presented_batch_f32",
     "rtw_render_presented_batch_f64",
@@ -230,6 +232,10 @@ def lib():
         getattr(L, "rtw_clamped_step_device_" + sfx).argtypes = [tp, tc, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_clamped_step_" + sfx).argtypes = [tp, tc, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_render_path_clamped_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), tp, tc, tn, C.POINTER(Denoise), ptr]
+        getattr(L, "rtw_reproject_table_" + sfx).argtypes = [C.POINTER(CamT), C.POINTER(CamT), i32, ptr]
+        getattr(L, "rtw_reproject_batch_device_" + sfx).argtypes = [tp, tc, i32, ptr, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_reproject_noise_batch_device_" + sfx).argtypes = [tn, i32, i32, i32, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_render_paths_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, i32, seeds, C.POINTER(Params), tp, tc, tn, C.POINTER(Denoise), ptr]
         pr, dn = C.POINTER(Present), C.POINTER(Denoise)
         getattr(L, "rtw_present_device_" + sfx).argtypes = [pr, i32, i32, ptr, ptr, ptr]
         getattr(L, "rtw_present_batch_device_" + sfx).argtypes = [pr, i32, i32, i32, ptr, ptr, ptr]
@@ -242,6 +248,8 @@ def lib():
     L.rtw_temporal_state_bytes.restype = C.c_int64
     L.rtw_history_moment_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_history_moment_bytes.restype = C.c_int64
+    L.rtw_reproject_table_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.rtw_reproject_table_bytes.restype = C.c_int64
     L.rtw_upsample_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_upsample_work_bytes.restype = C.c_int64
     L.rtw_denoise_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]

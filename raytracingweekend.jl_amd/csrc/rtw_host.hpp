@@ -14,7 +14,7 @@
 //   rtw_features.hip     first-hit feature buffers: one launch of the feature kernel (rtw_features.hpp) for one view or a batch of views, the device-resident entry points
 //   rtw_denoise.hip      the feature-guided denoiser: its checks, the launch sequence of its kernels (rtw_denoise.hpp) for one frame or a batch of frames, the device-resident entry points
 //   rtw_upsample.hip     the feature-guided upsampler: its checks, the launch sequence (the denoiser's prepare and level kernels at the small size, then rtw_upsample.hpp at the full size), the device-resident entry points
-//   rtw_temporal.hip     temporal reprojection: its checks, the host constants and the one launch of a step (rtw_temporal.hpp; clamped: rtw_temporal_clamp.hpp), the device-resident entry points
+//   rtw_temporal.hip     temporal reprojection: its checks, the host constants and the one launch of a step for one path or a batch of paths (rtw_temporal.hpp; clamped: rtw_temporal_clamp.hpp), the device-resident entry points
 //   rtw_present.hip      the present stage: its checks, the one launch of its kernel (rtw_present.hpp) for one frame or a batch, the device-resident entry points
 //   (rtw_scene_view.hpp: what both launch functions derive from their arguments; rtw_instances.hpp: the one table of the trace kernel's instances)
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
@@ -346,22 +346,32 @@ inline int launch_upsample_t(const rtw_upsample_t *u, int32_t lw, int32_t lh, in
 // rtw_temporal.hip -- temporal reprojection (include/rtw_hip.h rtw_temporal_*).  validate_temporal: every check of a step that needs neither a
 // device nor a pointer -- the parameters and the frame.
 int validate_temporal(const rtw_temporal_t *t, int32_t width, int32_t height, int elem_bytes);
-// launch_temporal: enqueue ONE step (one launch) on `stream` of the current device.  cam_prev and d_state_prev are both null (the first frame)
-// or both given; the states hold rtw_temporal_state_bytes bytes each (16-byte aligned).  d_moment_next non-null: the step with moments
+// launch_temporal: enqueue ONE step (one launch) on `stream` of the current device.  n_paths == 0: ONE path -- cam_prev and d_state_prev are
+// both null (the first frame) or both given; the states hold rtw_temporal_state_bytes bytes each (16-byte aligned).  n_paths >= 1
+// (rtw_reproject_batch_device_*): that many paths in the same ONE launch -- cam / cam_prev are unused, path s takes its constants from entry s of
+// the DEVICE table d_table (temporal_table_*: 32 elements of T per path) and every buffer holds the paths one behind the other; d_state_prev
+// null: every path's first frame.  d_moment_next non-null: the step with moments
 // (rtw_history_moments_*), planes of rtw_history_moment_bytes bytes, d_moment_prev null exactly when d_state_prev is.  `c` non-null (accepted by
 // validate_temporal_clamp: every check of a clamp, none needs a device): the clamped step (rtw_clamped_step_*), still one launch.
 int validate_temporal_clamp(const rtw_temporal_clamp_t *c);
-int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr, const rtw_temporal_clamp_t *c = nullptr);
-int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr, const rtw_temporal_clamp_t *c = nullptr);
-inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f32 *c, const rtw_camera_f32 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp = nullptr, void *mn = nullptr, const rtw_temporal_clamp_t *cl = nullptr) { return launch_temporal_f32(t, c, cp, w, h, img, feat, sp, sn, out, st, mp, mn, cl); }
-inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f64 *c, const rtw_camera_f64 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp = nullptr, void *mn = nullptr, const rtw_temporal_clamp_t *cl = nullptr) { return launch_temporal_f64(t, c, cp, w, h, img, feat, sp, sn, out, st, mp, mn, cl); }
+int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t n_paths, const void *d_table, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr, const rtw_temporal_clamp_t *c = nullptr);
+int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t n_paths, const void *d_table, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr, const rtw_temporal_clamp_t *c = nullptr);
+inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f32 *c, const rtw_camera_f32 *cp, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp = nullptr, void *mn = nullptr, const rtw_temporal_clamp_t *cl = nullptr) { return launch_temporal_f32(t, c, cp, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, cl); }
+inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f64 *c, const rtw_camera_f64 *cp, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp = nullptr, void *mn = nullptr, const rtw_temporal_clamp_t *cl = nullptr) { return launch_temporal_f64(t, c, cp, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, cl); }
+// temporal_table_*: the camera constants of n paths into a HOST table, 32 elements per path (include/rtw_hip.h rtw_reproject_table_*; cams_prev null: first
+// frames) -- the one copy of that arithmetic, launch_temporal's own constants included.
+void temporal_table_f32(const rtw_camera_f32 *cams, const rtw_camera_f32 *cams_prev, int64_t n, float *table);
+void temporal_table_f64(const rtw_camera_f64 *cams, const rtw_camera_f64 *cams_prev, int64_t n, double *table);
+inline void temporal_table_t(const rtw_camera_f32 *c, const rtw_camera_f32 *cp, int64_t n, float *tab) { temporal_table_f32(c, cp, n, tab); }
+inline void temporal_table_t(const rtw_camera_f64 *c, const rtw_camera_f64 *cp, int64_t n, double *tab) { temporal_table_f64(c, cp, n, tab); }
 // validate_temporal_noise: every check of a noise map (rtw_history_noise_device_*) that needs neither a device nor a pointer.  launch_temporal_noise:
 // enqueue the map (ONE launch) of a state and its moment plane on `stream` of the current device; d_noise: width*height elements of T.
+// n_paths >= 1 (rtw_reproject_noise_batch_device_*): the maps of that many states and planes, one behind the other, in the same ONE launch.
 int validate_temporal_noise(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int elem_bytes);
-int launch_temporal_noise_f32(const rtw_temporal_noise_t *n, int32_t width, int32_t height, const void *d_state, const void *d_moment, void *d_noise, hipStream_t stream);
-int launch_temporal_noise_f64(const rtw_temporal_noise_t *n, int32_t width, int32_t height, const void *d_state, const void *d_moment, void *d_noise, hipStream_t stream);
-inline int launch_temporal_noise_t(const rtw_temporal_noise_t *n, int32_t w, int32_t h, const void *st, const void *mo, float *noise, hipStream_t s) { return launch_temporal_noise_f32(n, w, h, st, mo, noise, s); }
-inline int launch_temporal_noise_t(const rtw_temporal_noise_t *n, int32_t w, int32_t h, const void *st, const void *mo, double *noise, hipStream_t s) { return launch_temporal_noise_f64(n, w, h, st, mo, noise, s); }
+int launch_temporal_noise_f32(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int32_t n_paths, const void *d_state, const void *d_moment, void *d_noise, hipStream_t stream);
+int launch_temporal_noise_f64(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int32_t n_paths, const void *d_state, const void *d_moment, void *d_noise, hipStream_t stream);
+inline int launch_temporal_noise_t(const rtw_temporal_noise_t *n, int32_t w, int32_t h, int32_t np, const void *st, const void *mo, float *noise, hipStream_t s) { return launch_temporal_noise_f32(n, w, h, np, st, mo, noise, s); }
+inline int launch_temporal_noise_t(const rtw_temporal_noise_t *n, int32_t w, int32_t h, int32_t np, const void *st, const void *mo, double *noise, hipStream_t s) { return launch_temporal_noise_f64(n, w, h, np, st, mo, noise, s); }
 
 // rtw_present.hip -- the present stage (include/rtw_hip.h rtw_present_*).  validate_present: every check of a call that needs neither a device
 // nor a pointer -- the parameters, the frame, n_views (0: one frame; a batch's count through batch_views) and the size of the launch.

@@ -560,14 +560,15 @@ int render_host_upsampled(const SceneT *scene, const CamT *cams, int32_t n_views
 }
 
 // The regions of the temporal paths inside a context's device buffer: the linear images and the features of `frames` views, the accumulated
-// images, (filter: the filtered images,) two states, (filter: the denoiser's workspace) -- each starts on a 16-byte boundary.
+// images, (filter: the filtered images,) two states, (filter: the denoiser's workspace) -- each starts on a 16-byte boundary.  `paths` >= 1
+// (rtw_render_paths_*): each of the two states is a SET of that many, one behind the other.
 template <typename T> struct TemporalRegions {
     size_t frame_b, img_b, feat_b, st_b, off_feat, off_acc, off_flt, off_st[2], off_work, total;
-    TemporalRegions(int32_t width, int32_t height, size_t frames, bool filter) {
+    TemporalRegions(int32_t width, int32_t height, size_t frames, bool filter, size_t paths = 1) {
         const size_t n = (size_t)width * (size_t)height;
         auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
         frame_b = n * 3 * sizeof(T); img_b = frame_b * frames; feat_b = n * RTW_FEATURE_CHANNELS * sizeof(T) * frames;
-        st_b = (size_t)rtw_temporal_state_bytes(width, height, (int32_t)sizeof(T));
+        st_b = (size_t)rtw_temporal_state_bytes(width, height, (int32_t)sizeof(T)) * paths;
         off_feat = up(img_b); off_acc = off_feat + up(feat_b); off_flt = off_acc + up(img_b);
         off_st[0] = off_flt + (filter ? up(img_b) : 0); off_st[1] = off_st[0] + st_b; off_work = off_st[1] + st_b;
         total = off_work + (filter ? (size_t)rtw_denoise_work_bytes(width, height, (int32_t)sizeof(T)) * frames : 0);
@@ -575,15 +576,19 @@ template <typename T> struct TemporalRegions {
 };
 
 // The regions of the temporal paths with moments: TemporalRegions (always with the filter's regions when `filter`), then two moment planes and
-// the noise maps of `frames` views -- each starts on a 16-byte boundary.
+// the noise maps of `frames` views -- each starts on a 16-byte boundary.  `paths` >= 1: each of the two moment planes is a set of that many, and
+// the table of the `frames` steps' camera constants (rtw_reproject_table_*) lies behind everything else: total_p bytes with `moments`' regions
+// or without them.
 template <typename T> struct MomentRegions : TemporalRegions<T> {
-    size_t mo_b, noise_b, off_mo[2], off_noise, total_m;
-    MomentRegions(int32_t width, int32_t height, size_t frames, bool filter) : TemporalRegions<T>(width, height, frames, filter) {
+    size_t mo_b, noise_b, off_mo[2], off_noise, total_m, tab_b, off_tab, total_p;
+    MomentRegions(int32_t width, int32_t height, size_t frames, bool filter, size_t paths = 1, bool moments = true) : TemporalRegions<T>(width, height, frames, filter, paths) {
         auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        mo_b = (size_t)rtw_history_moment_bytes(width, height, (int32_t)sizeof(T));
+        mo_b = (size_t)rtw_history_moment_bytes(width, height, (int32_t)sizeof(T)) * paths;
         noise_b = (size_t)width * (size_t)height * sizeof(T);
         off_mo[0] = up(this->total); off_mo[1] = off_mo[0] + mo_b; off_noise = off_mo[1] + mo_b;
         total_m = off_noise + up(noise_b * frames);
+        tab_b = frames * 32 * sizeof(T);
+        off_tab = moments ? total_m : up(this->total); total_p = off_tab + tab_b;
     }
 };
 
@@ -626,12 +631,12 @@ int temporal_step_host(bool form_args, const rtw_temporal_t *t, const rtw_tempor
     if (e == hipSuccess && state_prev) e = hipMemcpyAsync(base + R.off_st[0], state_prev, R.st_b, hipMemcpyHostToDevice, hc->stream);
     if (e == hipSuccess && moment_prev) e = hipMemcpyAsync(base + R.off_mo[0], moment_prev, R.mo_b, hipMemcpyHostToDevice, hc->stream);
     if (e != hipSuccess) rc = fail((int)e, "upload of the temporal step's inputs failed: %s", hipGetErrorString(e));
-    if (!rc) rc = launch_temporal_t(t, cam, cam_prev, width, height, base, base + R.off_feat, state_prev ? base + R.off_st[0] : nullptr, base + R.off_st[1], base + R.off_acc, hc->stream,
+    if (!rc) rc = launch_temporal_t(t, cam, cam_prev, 0, nullptr, width, height, base, base + R.off_feat, state_prev ? base + R.off_st[0] : nullptr, base + R.off_st[1], base + R.off_acc, hc->stream,
                                     moment_prev ? base + R.off_mo[0] : nullptr, moments ? base + R.off_mo[1] : nullptr, c);
     if (!rc && n) {
         rtw_temporal_noise_t nn = *n;
         nn.device = hc->device;
-        rc = launch_temporal_noise_t(&nn, width, height, base + R.off_st[1], base + R.off_mo[1], (T *)(base + R.off_noise), hc->stream);
+        rc = launch_temporal_noise_t(&nn, width, height, 0, base + R.off_st[1], base + R.off_mo[1], (T *)(base + R.off_noise), hc->stream);
     }
     if (!rc) {
         e = hipMemcpyAsync(state_next, base + R.off_st[1], R.st_b, hipMemcpyDeviceToHost, hc->stream);
@@ -653,9 +658,14 @@ int temporal_step_host(bool form_args, const rtw_temporal_t *t, const rtw_tempor
 // NOISE-GUIDED one over the N maps: 2 + 2*n_views + 1 + levels launches.  `guided` says only that the ENTRY POINT requires n and d, so that
 // a null one is refused with -1 and not taken for the plain form; what runs is decided by n alone.
 // `c` non-null (rtw_render_path_clamped_*): the steps behind view 0 are clamped steps, launch for launch.
+// n_paths >= 1 (rtw_render_paths_*): n_views = n_steps * n_paths frames, step-major -- path s at step k is view k*n_paths + s of cams, seeds and
+// out.  Still ONE render, ONE feature pass and ONE filter pass over all n_views frames; the table of all n_views camera constants
+// (temporal_table_t: step k's previous cameras are step k-1's) goes up by ONE H2D from the context's pinned staging buffer, then n_steps
+// BATCHED step launches (step k reads the table's entries [k*n_paths, (k+1)*n_paths); two sets of n_paths states -- with n, of moment planes
+// -- ping-pong) and, with n, one batched noise launch behind each.  n_paths == 0 is the one path above, call for call.
 template <typename T, typename SceneT, typename CamT>
 int render_host_sequence(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t, const rtw_temporal_noise_t *n,
-                         const rtw_denoise_t *d, T *out, const rtw_temporal_clamp_t *c = nullptr, bool guided = false) {
+                         const rtw_denoise_t *d, T *out, const rtw_temporal_clamp_t *c = nullptr, bool guided = false, int32_t n_paths = 0) {
     if (!p) return fail(-1, "null params");
     if (!scene || !cams || !t || !out || (guided && (!n || !d))) return fail(-1, "null argument");
     int nch, cs;
@@ -666,12 +676,17 @@ int render_host_sequence(const SceneT *scene, const CamT *cams, int32_t n_views,
     if (c) if (int rc = validate_temporal_clamp(c)) return rc;
     if (n && ((t->flags & RTW_TEMPORAL_DEMODULATE) != 0) != ((d->flags & RTW_DENOISE_DEMODULATE) != 0))
         return fail(-2, "the DEMODULATE flags of t and d must agree (the noise map is relative to the state's luminance)");
+    if (n_paths && (double)p->width * (double)p->height * (double)n_views >= (double)(1ll << 39))         // (without d nothing above has applied the batch's size rule)
+        return fail(-5, "batch too large for one call: %d frames of %d x %d pixels", n_views, p->width, p->height);
     DeviceGuard guard;
     release_last();
-    const MomentRegions<T> R(p->width, p->height, (size_t)n_views, d != nullptr);
+    const size_t np = n_paths ? (size_t)n_paths : 1;          // paths per step launch
+    const int32_t n_steps = n_paths ? n_views / n_paths : n_views;
+    const MomentRegions<T> R(p->width, p->height, (size_t)n_views, d != nullptr, np, n != nullptr);
+    const size_t dev_b = n_paths ? R.total_p : n ? R.total_m : R.total;
     RenderRec *frec = nullptr;
     CtxPtr fctx;
-    const int rc = render_one_device(p->device, scene, p, n ? R.total_m : R.total, d ? R.off_flt : R.off_acc, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+    const int rc = render_one_device(p->device, scene, p, dev_b, d ? R.off_flt : R.off_acc, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
         char *base = (char *)hc->d_img;
         q.gamma = 0;
         rtw_temporal_t tt = *t;
@@ -680,11 +695,25 @@ int render_host_sequence(const SceneT *scene, const CamT *cams, int32_t n_views,
         nn.device = hc->device;
         int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
         if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec, &fctx);
-        for (int v = 0; v < n_views && !rc; ++v) {
-            rc = launch_temporal_t(&tt, cams + v, v ? cams + (v - 1) : nullptr, p->width, p->height, base + (size_t)v * R.frame_b, base + R.off_feat + (size_t)v * (R.feat_b / (size_t)n_views),
-                                   v ? base + R.off_st[(v & 1) ^ 1] : nullptr, base + R.off_st[v & 1], base + R.off_acc + (size_t)v * R.frame_b, hc->stream,
-                                   n && v ? base + R.off_mo[(v & 1) ^ 1] : nullptr, n ? base + R.off_mo[v & 1] : nullptr, c);
-            if (!rc && n) rc = launch_temporal_noise_t(&nn, p->width, p->height, base + R.off_st[v & 1], base + R.off_mo[v & 1], (T *)(base + R.off_noise + (size_t)v * R.noise_b), hc->stream);
+        if (!rc && n_paths) {
+            // the whole table: step 0's entries are first frames', step k's previous cameras are step k-1's
+            if (hc->stage_cap < R.tab_b) {
+                if (hc->h_stage) { HIP_IGNORE(hipHostFree(hc->h_stage)); hc->h_stage = nullptr; hc->stage_cap = 0; }
+                HIP_TRY(hipHostMalloc(&hc->h_stage, R.tab_b, hipHostMallocDefault));
+                hc->stage_cap = R.tab_b;
+            }
+            T *tab = (T *)hc->h_stage;
+            temporal_table_t(cams, nullptr, n_paths, tab);
+            if (n_steps > 1) temporal_table_t(cams + n_paths, cams, (int64_t)(n_steps - 1) * n_paths, tab + 32 * np);
+            HIP_TRY(hipMemcpyAsync(base + R.off_tab, tab, R.tab_b, hipMemcpyHostToDevice, hc->stream));
+        }
+        const size_t feat_frame_b = R.feat_b / (size_t)n_views;
+        for (int v = 0; v < n_steps && !rc; ++v) {
+            const size_t f = (size_t)v * np;                  // the step's first frame
+            rc = launch_temporal_t(&tt, n_paths ? nullptr : cams + v, n_paths || !v ? nullptr : cams + (v - 1), n_paths, n_paths ? base + R.off_tab + f * 32 * sizeof(T) : nullptr, p->width,
+                                   p->height, base + f * R.frame_b, base + R.off_feat + f * feat_frame_b, v ? base + R.off_st[(v & 1) ^ 1] : nullptr, base + R.off_st[v & 1],
+                                   base + R.off_acc + f * R.frame_b, hc->stream, n && v ? base + R.off_mo[(v & 1) ^ 1] : nullptr, n ? base + R.off_mo[v & 1] : nullptr, c);
+            if (!rc && n) rc = launch_temporal_noise_t(&nn, p->width, p->height, n_paths, base + R.off_st[v & 1], base + R.off_mo[v & 1], (T *)(base + R.off_noise + f * R.noise_b), hc->stream);
         }
         if (!rc && d) {
             rtw_denoise_t dd = *d;
@@ -696,6 +725,19 @@ int render_host_sequence(const SceneT *scene, const CamT *cams, int32_t n_views,
     });
     if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
     return rc;
+}
+
+// rtw_render_paths_*: n_paths paths x n_steps steps, step-major, in any of the sequence's forms -- c null: plain steps; n (d is then required): the
+// guided form.  The counts and their product first; everything else is the sequence's own check of n_steps*n_paths views.
+template <typename T, typename SceneT, typename CamT>
+int render_host_paths(const SceneT *scene, const CamT *cams, int32_t n_paths, int32_t n_steps, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
+                      const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, T *out) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !cams || !t || !out) return fail(-1, "null argument");
+    if (n_paths < 1 || n_steps < 1) return fail(-2, "n_paths and n_steps must be >= 1 (got %d, %d)", n_paths, n_steps);
+    if ((int64_t)n_paths * n_steps > INT32_MAX) return fail(-2, "n_steps * n_paths must fit in 32 bits (got %d * %d)", n_steps, n_paths);
+    if (n && !d) return fail(-2, "a noise map (n) guides the filter: d is required with it");
+    return render_host_sequence<T>(scene, cams, n_paths * n_steps, seeds, p, t, n, d, out, c, n != nullptr, n_paths);
 }
 
 // rtw_render_path_clamped_*: the sequence (n null; d optional) or the guided sequence (n and d) with clamped steps.
@@ -900,6 +942,14 @@ int rtw_render_path_clamped_f32(const rtw_scene_f32 *scene, const rtw_camera_f32
 int rtw_render_path_clamped_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                                  const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, double *out) {
     return render_host_sequence_clamped<double>(scene, cams, batch_views(n_views), seeds, p, t, c, n, d, out);
+}
+int rtw_render_paths_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_paths, int32_t n_steps, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
+                         const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, float *out) {
+    return render_host_paths<float>(scene, cams, n_paths, n_steps, seeds, p, t, c, n, d, out);
+}
+int rtw_render_paths_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_paths, int32_t n_steps, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
+                         const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, double *out) {
+    return render_host_paths<double>(scene, cams, n_paths, n_steps, seeds, p, t, c, n, d, out);
 }
 int rtw_render_path_guided_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                                    const rtw_temporal_noise_t *n, const rtw_denoise_t *d, float *out) {

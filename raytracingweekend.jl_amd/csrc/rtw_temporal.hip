@@ -1,8 +1,8 @@
 // rtw_temporal.hip -- temporal reprojection (include/rtw_hip.h rtw_temporal_*): the checks that need no device, the host constants of a step,
 // the one launch of its kernel (rtw_temporal.hpp), the step with moments and the noise map (rtw_history_moments_*, rtw_history_noise_device_*), the
 // clamped step (rtw_clamped_step_device_*: the checks of its clamp and the launch of its own kernel, rtw_temporal_clamp.hpp) and the
-// device-resident entry points.
-// (The host-buffer entry points, rtw_temporal_*, rtw_history_moments_*, rtw_clamped_step_*, rtw_render_sequence_* and rtw_render_path_*, live with the other
+// device-resident entry points; the batched forms of all three (rtw_reproject_*: n_paths paths in each launch, the table of their camera constants).
+// (The host-buffer entry points, rtw_temporal_*, rtw_history_moments_*, rtw_clamped_step_*, rtw_render_sequence_*, rtw_render_path_* and rtw_render_paths_*, live with the other
 // cached-context paths in rtw_render_host.hip.)
 #include "rtw_host.hpp"
 #include "rtw_temporal.hpp"
@@ -57,29 +57,52 @@ int validate_temporal_noise(const rtw_temporal_noise_t *n, int32_t width, int32_
     return 0;
 }
 
-// Enqueue one step on `stream` of the current device (validate_temporal has accepted the call).  cam_prev and d_state_prev are both null
-// (the first frame) or both given.  d_moment_next non-null: the step with moments (rtw_history_moments_*), d_moment_prev null exactly when
+// The camera constants of one path (include/rtw_hip.h rtw_reproject_table_*: 32 elements, the head of rtw::TpParams): the current camera's fields,
+// the previous camera's and the projection's constants -- binary64 from the previous camera's fields, every dot product (x + y) + z, each
+// rounded to T once.  cam_prev null (the first frame): elements 12..28 are 0.  The ONE copy of this arithmetic: launch_temporal's own
+// constants and rtw_reproject_table_* both come from here.
+template <typename T, typename CamT>
+void temporal_table_entry(const CamT *cam, const CamT *cam_prev, T *e) {
+    for (int k = 0; k < 32; ++k) e[k] = T(0);
+    for (int k = 0; k < 3; ++k) { e[k] = cam->origin[k]; e[3 + k] = cam->lower_left_corner[k]; e[6 + k] = cam->horizontal[k]; e[9 + k] = cam->vertical[k]; }
+    if (!cam_prev) return;
+    double q[3], w[3], h[3], v[3];
+    for (int k = 0; k < 3; ++k) {
+        e[12 + k] = cam_prev->origin[k]; e[15 + k] = cam_prev->w[k]; e[18 + k] = cam_prev->horizontal[k]; e[21 + k] = cam_prev->vertical[k];
+        q[k] = (double)cam_prev->lower_left_corner[k] - (double)cam_prev->origin[k];
+        w[k] = cam_prev->w[k]; h[k] = cam_prev->horizontal[k]; v[k] = cam_prev->vertical[k];
+    }
+    auto dot = [](const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+    e[24] = (T)dot(q, w); e[25] = (T)dot(q, h); e[26] = (T)dot(q, v);
+    e[27] = (T)(1.0 / dot(h, h)); e[28] = (T)(1.0 / dot(v, v));
+}
+
+// the path dimensions of a batched launch's grid: the path index is blockIdx.z * gridDim.y + blockIdx.y (rtw_temporal.hpp TpPaths)
+static dim3 paths_grid(unsigned blocks, int32_t n_paths) {
+    const unsigned np = (unsigned)n_paths;
+    return dim3(blocks, np < rtw::TP_PATHS_Y ? np : rtw::TP_PATHS_Y, (np + rtw::TP_PATHS_Y - 1) / rtw::TP_PATHS_Y);
+}
+
+// Enqueue one step on `stream` of the current device (validate_temporal has accepted the call).  n_paths == 0: the step of ONE path -- cam_prev
+// and d_state_prev are both null (the first frame) or both given.  n_paths >= 1 (rtw_reproject_batch_device_*): the step of that many paths in
+// the SAME single launch -- cam and cam_prev are unused, the constants of path s are entry s of the device table d_table, every buffer holds
+// the paths one behind the other (states and moment planes at their byte sizes), d_state_prev null: every path's first frame.
+// d_moment_next non-null: the step with moments (rtw_history_moments_*), d_moment_prev null exactly when
 // d_state_prev is.  `c` non-null (validate_temporal_clamp has accepted it): the clamped step -- its own kernel (rtw_temporal_clamp.hpp), one workgroup per
 // tile, whenever there is a previous state; the first frame is the plain step's.
 template <typename T, typename CamT>
-int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features,
-                    const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev, void *d_moment_next, const rtw_temporal_clamp_t *c) {
+int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_prev, int32_t n_paths, const void *d_table, int32_t width, int32_t height, const void *d_image,
+                    const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev, void *d_moment_next,
+                    const rtw_temporal_clamp_t *c) {
     using V = typename rtw::DnVec<T>::type;
     const long long n_pix = (long long)width * height;
     rtw::TpParams<T> U;
     memset(&U, 0, sizeof U);
-    for (int k = 0; k < 3; ++k) { U.o[k] = cam->origin[k]; U.llc[k] = cam->lower_left_corner[k]; U.hor[k] = cam->horizontal[k]; U.ver[k] = cam->vertical[k]; }
-    if (cam_prev) {
-        // the projection's constants: binary64 from the previous camera's fields, every dot product (x + y) + z, each rounded to T once
-        double q[3], w[3], h[3], v[3];
-        for (int k = 0; k < 3; ++k) {
-            U.po[k] = cam_prev->origin[k]; U.pw[k] = cam_prev->w[k]; U.ph[k] = cam_prev->horizontal[k]; U.pv[k] = cam_prev->vertical[k];
-            q[k] = (double)cam_prev->lower_left_corner[k] - (double)cam_prev->origin[k];
-            w[k] = cam_prev->w[k]; h[k] = cam_prev->horizontal[k]; v[k] = cam_prev->vertical[k];
-        }
-        auto dot = [](const double *a, const double *b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
-        U.Kw = (T)dot(q, w); U.Qh = (T)dot(q, h); U.Qv = (T)dot(q, v);
-        U.ih = (T)(1.0 / dot(h, h)); U.iv = (T)(1.0 / dot(v, v));
+    static_assert(offsetof(rtw::TpParams<T>, inv_sz) == 29 * sizeof(T), "a table entry is the head of TpParams");
+    if (!n_paths) {
+        T e[32];
+        temporal_table_entry<T>(cam, cam_prev, e);
+        memcpy(&U, e, 29 * sizeof(T));
     }
     U.inv_sz = (T)(1.0 / (t->sigma_depth * t->sigma_depth));
     U.w_min = (T)t->min_weight; U.n_max = (T)t->history_max;
@@ -90,6 +113,7 @@ int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
     const char *sp = (const char *)d_state_prev;
     char *sn = (char *)d_state_next;
     const unsigned grid = (unsigned)((n_pix + 255) / 256);
+    const rtw::TpPaths<T, true> B = {(const T *)d_table, state_bytes(width, height, sizeof(T)), moment_bytes(width, height, sizeof(T)), (unsigned)n_paths};
     // (measurement aid, tools/gpu_temporal.py: events around the kernel, reported on stderr -- this one blocks)
     static const bool profile = aid_flag("RTW_TEMPORAL_PROFILE");
     struct Events { hipEvent_t e[2] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
@@ -97,6 +121,9 @@ int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
     (void)hipGetLastError();
     const T *mp = (const T *)d_moment_prev;
     T *mn = (T *)d_moment_next;
+    // the previous state's planes (the first frame: null, its instances read none) and the next state's
+    const V *ep = sp ? (const V *)sp : nullptr, *gp = sp ? (const V *)(sp + pb) : nullptr;
+    const T *lp = sp ? (const T *)(sp + 2 * pb) : nullptr;
     if (c && sp) {
         // the tile grid: fewer tiles than the frame rule's 8 x 8 ones, so one 32-bit grid dimension holds them
         rtw::TpClampParams<T> K;
@@ -104,39 +131,46 @@ int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
         K.ks = (T)c->sigma; K.ls = (T)c->len_scale; K.r = c->radius;
         K.tiles_i = (unsigned)((height + rtw::TP_TI - 1) / rtw::TP_TI);
         const unsigned tiles = K.tiles_i * (unsigned)((width + rtw::TP_TJ - 1) / rtw::TP_TJ);
+        auto go = [&](auto mo, auto gd) {
+            if (n_paths) hipLaunchKernelGGL((rtw::tp_step_clamped<T, decltype(mo)::value, decltype(gd)::value, true>), paths_grid(tiles, n_paths), dim3(256), 0, stream, U, K, (const T *)d_image,
+                                            (const V *)d_features, ep, gp, lp, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn, B);
+            else hipLaunchKernelGGL((rtw::tp_step_clamped<T, decltype(mo)::value, decltype(gd)::value, false>), dim3(tiles), dim3(256), 0, stream, U, K, (const T *)d_image,
+                                    (const V *)d_features, ep, gp, lp, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn, rtw::TpPaths<T, false>());
+        };
         const bool gd = (c->flags & RTW_CLAMP_GUIDES) != 0;
-#define RTW_TP_CLAMPED(MO, GD) hipLaunchKernelGGL((rtw::tp_step_clamped<T, MO, GD>), dim3(tiles), dim3(256), 0, stream, U, K, (const T *)d_image, (const V *)d_features, (const V *)sp, \
-                                                  (const V *)(sp + pb), (const T *)(sp + 2 * pb), (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn)
-        if (mn) { if (gd) RTW_TP_CLAMPED(true, true); else RTW_TP_CLAMPED(true, false); }
-        else { if (gd) RTW_TP_CLAMPED(false, true); else RTW_TP_CLAMPED(false, false); }
-#undef RTW_TP_CLAMPED
-    } else if (mn) {
-        if (sp) hipLaunchKernelGGL((rtw::tp_step<T, true, true>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, (const V *)sp, (const V *)(sp + pb),
-                                   (const T *)(sp + 2 * pb), (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn);
-        else hipLaunchKernelGGL((rtw::tp_step<T, false, true>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, (const V *)nullptr, (const V *)nullptr,
-                                (const T *)nullptr, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, (const T *)nullptr, mn);
-    } else if (sp) hipLaunchKernelGGL((rtw::tp_step<T, true>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, (const V *)sp, (const V *)(sp + pb),
-                                      (const T *)(sp + 2 * pb), (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, (const T *)nullptr, (T *)nullptr);
-    else hipLaunchKernelGGL((rtw::tp_step<T, false>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, (const V *)nullptr, (const V *)nullptr,
-                            (const T *)nullptr, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, (const T *)nullptr, (T *)nullptr);
+        if (mn) { if (gd) go(std::true_type(), std::true_type()); else go(std::true_type(), std::false_type()); }
+        else { if (gd) go(std::false_type(), std::true_type()); else go(std::false_type(), std::false_type()); }
+    } else {
+        auto go = [&](auto hp, auto mo) {
+            if (n_paths) hipLaunchKernelGGL((rtw::tp_step<T, decltype(hp)::value, decltype(mo)::value, true>), paths_grid(grid, n_paths), dim3(256), 0, stream, U, (const T *)d_image,
+                                            (const V *)d_features, ep, gp, lp, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn, B);
+            else hipLaunchKernelGGL((rtw::tp_step<T, decltype(hp)::value, decltype(mo)::value, false>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, ep,
+                                    gp, lp, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn, rtw::TpPaths<T, false>());
+        };
+        if (mn) { if (sp) go(std::true_type(), std::true_type()); else go(std::false_type(), std::true_type()); }
+        else { if (sp) go(std::true_type(), std::false_type()); else go(std::false_type(), std::false_type()); }
+    }
     HIP_TRY(hipGetLastError());
     if (profile) {
         float ms = 0;
         HIP_TRY(hipEventRecord(events.e[1], stream));
         HIP_TRY(hipEventSynchronize(events.e[1]));
         HIP_TRY(hipEventElapsedTime(&ms, events.e[0], events.e[1]));
-        if (c && sp) fprintf(stderr, "[rtw temporal] %s %dx%d %s r=%d guides=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, mn ? "clamped+moments" : "clamped", c->radius, c->flags & RTW_CLAMP_GUIDES, ms);
-        else fprintf(stderr, "[rtw temporal] %s %dx%d %s prev=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, mn ? "step+moments" : "step", sp ? 1 : 0, ms);
+        if (c && sp) fprintf(stderr, "[rtw temporal] %s %dx%d %s r=%d guides=%d paths=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, mn ? "clamped+moments" : "clamped", c->radius, c->flags & RTW_CLAMP_GUIDES, n_paths, ms);
+        else fprintf(stderr, "[rtw temporal] %s %dx%d %s prev=%d paths=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, mn ? "step+moments" : "step", sp ? 1 : 0, n_paths, ms);
     }
     return 0;
 }
 
-int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn, const rtw_temporal_clamp_t *c) { return launch_temporal<float>(t, cam, cam_prev, w, h, img, feat, sp, sn, out, st, mp, mn, c); }
-int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn, const rtw_temporal_clamp_t *c) { return launch_temporal<double>(t, cam, cam_prev, w, h, img, feat, sp, sn, out, st, mp, mn, c); }
+int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn, const rtw_temporal_clamp_t *c) { return launch_temporal<float>(t, cam, cam_prev, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, c); }
+int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn, const rtw_temporal_clamp_t *c) { return launch_temporal<double>(t, cam, cam_prev, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, c); }
+void temporal_table_f32(const rtw_camera_f32 *cams, const rtw_camera_f32 *cams_prev, int64_t n, float *table) { for (int64_t s = 0; s < n; ++s) temporal_table_entry<float>(cams + s, cams_prev ? cams_prev + s : nullptr, table + 32 * s); }
+void temporal_table_f64(const rtw_camera_f64 *cams, const rtw_camera_f64 *cams_prev, int64_t n, double *table) { for (int64_t s = 0; s < n; ++s) temporal_table_entry<double>(cams + s, cams_prev ? cams_prev + s : nullptr, table + 32 * s); }
 
 // Enqueue the noise map of a state and its moment plane on `stream` of the current device (validate_temporal_noise has accepted the call): ONE launch.
+// n_paths >= 1 (rtw_reproject_noise_batch_device_*): the maps of that many states and planes, one behind the other, in the same single launch.
 template <typename T>
-int launch_temporal_noise(const rtw_temporal_noise_t *n, int32_t width, int32_t height, const void *d_state, const void *d_moment, void *d_noise, hipStream_t stream) {
+int launch_temporal_noise(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int32_t n_paths, const void *d_state, const void *d_moment, void *d_noise, hipStream_t stream) {
     using V = typename rtw::DnVec<T>::type;
     const long long n_pix = (long long)width * height;
     rtw::TpNoiseParams<T> U;
@@ -153,20 +187,23 @@ int launch_temporal_noise(const rtw_temporal_noise_t *n, int32_t width, int32_t 
     struct Events { hipEvent_t e[2] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
     if (profile) { for (hipEvent_t &x : events.e) HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventRecord(events.e[0], stream)); }
     (void)hipGetLastError();
-    hipLaunchKernelGGL((rtw::tp_noise<T>), dim3(grid), dim3(256), 0, stream, U, (const V *)sp, (const V *)(sp + pb), (const T *)(sp + 2 * pb), (const T *)d_moment, (T *)d_noise);
+    if (n_paths) hipLaunchKernelGGL((rtw::tp_noise<T, true>), paths_grid(grid, n_paths), dim3(256), 0, stream, U, (const V *)sp, (const V *)(sp + pb), (const T *)(sp + 2 * pb), (const T *)d_moment,
+                                    (T *)d_noise, rtw::TpPaths<T, true>{nullptr, state_bytes(width, height, sizeof(T)), moment_bytes(width, height, sizeof(T)), (unsigned)n_paths});
+    else hipLaunchKernelGGL((rtw::tp_noise<T, false>), dim3(grid), dim3(256), 0, stream, U, (const V *)sp, (const V *)(sp + pb), (const T *)(sp + 2 * pb), (const T *)d_moment, (T *)d_noise,
+                            rtw::TpPaths<T, false>());
     HIP_TRY(hipGetLastError());
     if (profile) {
         float ms = 0;
         HIP_TRY(hipEventRecord(events.e[1], stream));
         HIP_TRY(hipEventSynchronize(events.e[1]));
         HIP_TRY(hipEventElapsedTime(&ms, events.e[0], events.e[1]));
-        fprintf(stderr, "[rtw temporal] %s %dx%d noise r=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, n->radius, ms);
+        fprintf(stderr, "[rtw temporal] %s %dx%d noise r=%d paths=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, n->radius, n_paths, ms);
     }
     return 0;
 }
 
-int launch_temporal_noise_f32(const rtw_temporal_noise_t *n, int32_t w, int32_t h, const void *st, const void *mo, void *noise, hipStream_t s) { return launch_temporal_noise<float>(n, w, h, st, mo, noise, s); }
-int launch_temporal_noise_f64(const rtw_temporal_noise_t *n, int32_t w, int32_t h, const void *st, const void *mo, void *noise, hipStream_t s) { return launch_temporal_noise<double>(n, w, h, st, mo, noise, s); }
+int launch_temporal_noise_f32(const rtw_temporal_noise_t *n, int32_t w, int32_t h, int32_t np, const void *st, const void *mo, void *noise, hipStream_t s) { return launch_temporal_noise<float>(n, w, h, np, st, mo, noise, s); }
+int launch_temporal_noise_f64(const rtw_temporal_noise_t *n, int32_t w, int32_t h, int32_t np, const void *st, const void *mo, void *noise, hipStream_t s) { return launch_temporal_noise<double>(n, w, h, np, st, mo, noise, s); }
 
 // The device-resident entry points of a step: nulls, the parameters, then the pointers' alignment and aliasing.  `moments`:
 // rtw_history_moments_device_*, the same with the two moment planes (d_moment_prev null exactly when d_state_prev is).  `clamped`:
@@ -201,8 +238,68 @@ int temporal_device(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
     }
     DeviceGuard guard;
     if (t->device >= 0) HIP_TRY(hipSetDevice(t->device));
-    return launch_temporal<T>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, (hipStream_t)stream_v, moments ? d_moment_prev : nullptr,
+    return launch_temporal<T>(t, cam, cam_prev, 0, nullptr, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, (hipStream_t)stream_v, moments ? d_moment_prev : nullptr,
                               moments ? d_moment_next : nullptr, clamped ? c : nullptr);
+}
+
+// the batch's own size rule: the batched filter's frame rule on (width, height, number of frames)
+static int check_paths_size(int32_t width, int32_t height, int32_t n_paths) {
+    if ((double)width * (double)height * (double)n_paths >= (double)(1ll << 39)) return fail(-5, "batch too large for one call: %d paths of %d x %d pixels", n_paths, width, height);
+    return 0;
+}
+
+// The device-resident entry point of a batched step (rtw_reproject_batch_device_*): nulls, the count, the parameters, the batch's size, then
+// the pointers' pairing, alignment and aliasing over the extents of all n_paths paths.  `c` null: plain steps; both moment pointers null: no moments.
+template <typename T>
+int temporal_batch_device(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, int32_t n_paths, const void *d_table, int32_t width, int32_t height, const void *d_images,
+                          const void *d_features, const void *d_states_prev, const void *d_moments_prev, void *d_states_next, void *d_moments_next, void *d_out, void *stream_v) {
+    const bool moments = d_moments_prev || d_moments_next;
+    if (!t || !d_table || !d_images || !d_features || !d_states_next || !d_out || (moments && !d_moments_next)) return fail(-1, "null argument");
+    if (n_paths < 1) return fail(-2, "n_paths must be >= 1 (got %d)", n_paths);
+    if (int rc = validate_temporal(t, width, height, (int)sizeof(T))) return rc;
+    if (c) if (int rc = validate_temporal_clamp(c)) return rc;
+    if (int rc = check_paths_size(width, height, n_paths)) return rc;
+    if (moments && (d_moments_prev == nullptr) != (d_states_prev == nullptr)) return fail(-2, "d_moments_prev and d_states_prev must both be given or both be null (the first frame)");
+    if (((uintptr_t)d_table & 15u) || ((uintptr_t)d_features & 15u) || ((uintptr_t)d_states_prev & 15u) || ((uintptr_t)d_states_next & 15u) || ((uintptr_t)d_moments_prev & 15u) ||
+        ((uintptr_t)d_moments_next & 15u))
+        return fail(-2, "the table, the feature buffer, the states and the moment planes must be 16-byte aligned");
+    if (((uintptr_t)d_images & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
+    const size_t np = (size_t)n_paths, n_pix = (size_t)width * (size_t)height * np;
+    // every output against the outputs behind it and against every input that is there
+    const void *outs[3] = {d_out, d_states_next, d_moments_next}, *ins[5] = {d_images, d_features, d_states_prev, d_moments_prev, d_table};
+    const size_t st_b = (size_t)state_bytes(width, height, sizeof(T)) * np, mo_b = (size_t)moment_bytes(width, height, sizeof(T)) * np;
+    const size_t out_b[3] = {n_pix * 3 * sizeof(T), st_b, mo_b}, in_b[5] = {n_pix * 3 * sizeof(T), n_pix * 8 * sizeof(T), st_b, mo_b, np * 32 * sizeof(T)};
+    static const char *const names[3] = {"d_out", "d_states_next", "d_moments_next"};
+    for (int a = 0; a < 3; ++a) {
+        if (!outs[a]) continue;
+        for (int b = a + 1; b < 3; ++b)
+            if (outs[b] && ranges_overlap(outs[a], out_b[a], outs[b], out_b[b])) return fail(-2, "%s and %s may not alias each other", names[a], names[b]);
+        for (int b = 0; b < 5; ++b)
+            if (ins[b] && ranges_overlap(outs[a], out_b[a], ins[b], in_b[b])) return fail(-2, "%s may not alias an input", names[a]);
+    }
+    DeviceGuard guard;
+    if (t->device >= 0) HIP_TRY(hipSetDevice(t->device));
+    using CamT = std::conditional_t<sizeof(T) == 8, rtw_camera_f64, rtw_camera_f32>;
+    return launch_temporal<T, CamT>(t, nullptr, nullptr, n_paths, d_table, width, height, d_images, d_features, d_states_prev, d_states_next, d_out, (hipStream_t)stream_v,
+                                              d_moments_prev, d_moments_next, c);
+}
+
+// ... and of the batched noise map (rtw_reproject_noise_batch_device_*)
+template <typename T>
+int temporal_noise_batch_device(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int32_t n_paths, const void *d_states, const void *d_moments, void *d_noise, void *stream_v) {
+    if (!n || !d_states || !d_moments || !d_noise) return fail(-1, "null argument");
+    if (n_paths < 1) return fail(-2, "n_paths must be >= 1 (got %d)", n_paths);
+    if (int rc = validate_temporal_noise(n, width, height, (int)sizeof(T))) return rc;
+    if (int rc = check_paths_size(width, height, n_paths)) return rc;
+    if (((uintptr_t)d_states & 15u) || ((uintptr_t)d_moments & 15u)) return fail(-2, "the states and the moment planes must be 16-byte aligned");
+    if ((uintptr_t)d_noise & (sizeof(T) - 1)) return fail(-2, "the noise maps must be aligned to their element type");
+    const size_t np = (size_t)n_paths, noise_b = (size_t)width * (size_t)height * np * sizeof(T);
+    if (ranges_overlap(d_noise, noise_b, d_states, (size_t)state_bytes(width, height, sizeof(T)) * np) ||
+        ranges_overlap(d_noise, noise_b, d_moments, (size_t)moment_bytes(width, height, sizeof(T)) * np))
+        return fail(-2, "d_noise may not alias an input");
+    DeviceGuard guard;
+    if (n->device >= 0) HIP_TRY(hipSetDevice(n->device));
+    return launch_temporal_noise<T>(n, width, height, n_paths, d_states, d_moments, d_noise, (hipStream_t)stream_v);
 }
 
 // The device-resident entry point of the noise map: nulls, the parameters, then the pointers' alignment and aliasing.
@@ -218,7 +315,7 @@ int temporal_noise_device(const rtw_temporal_noise_t *n, int32_t width, int32_t 
         return fail(-2, "d_noise may not alias an input");
     DeviceGuard guard;
     if (n->device >= 0) HIP_TRY(hipSetDevice(n->device));
-    return launch_temporal_noise<T>(n, width, height, d_state, d_moment, d_noise, (hipStream_t)stream_v);
+    return launch_temporal_noise<T>(n, width, height, 0, d_state, d_moment, d_noise, (hipStream_t)stream_v);
 }
 
 }  // namespace rtwh
@@ -268,6 +365,39 @@ int rtw_history_noise_device_f32(const rtw_temporal_noise_t *n, int32_t width, i
 }
 int rtw_history_noise_device_f64(const rtw_temporal_noise_t *n, int32_t width, int32_t height, const void *d_state, const void *d_moment, void *d_noise, void *hip_stream) {
     return temporal_noise_device<double>(n, width, height, d_state, d_moment, d_noise, hip_stream);
+}
+int64_t rtw_reproject_table_bytes(int32_t n_paths, int32_t elem_bytes) {
+    if (elem_bytes != 4 && elem_bytes != 8) return fail(-2, "elem_bytes must be 4 or 8 (got %d)", elem_bytes);
+    if (n_paths < 1) return fail(-2, "n_paths must be >= 1 (got %d)", n_paths);
+    return (int64_t)n_paths * 32 * elem_bytes;
+}
+int rtw_reproject_table_f32(const rtw_camera_f32 *cams, const rtw_camera_f32 *cams_prev, int32_t n_paths, void *table) {
+    if (!cams || !table) return fail(-1, "null argument");
+    if (n_paths < 1) return fail(-2, "n_paths must be >= 1 (got %d)", n_paths);
+    temporal_table_f32(cams, cams_prev, n_paths, (float *)table);
+    return 0;
+}
+int rtw_reproject_table_f64(const rtw_camera_f64 *cams, const rtw_camera_f64 *cams_prev, int32_t n_paths, void *table) {
+    if (!cams || !table) return fail(-1, "null argument");
+    if (n_paths < 1) return fail(-2, "n_paths must be >= 1 (got %d)", n_paths);
+    temporal_table_f64(cams, cams_prev, n_paths, (double *)table);
+    return 0;
+}
+int rtw_reproject_batch_device_f32(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, int32_t n_paths, const void *d_table, int32_t width, int32_t height, const void *d_images,
+                                   const void *d_features, const void *d_states_prev, const void *d_moments_prev, void *d_states_next, void *d_moments_next, void *d_out, void *hip_stream) {
+    return temporal_batch_device<float>(t, c, n_paths, d_table, width, height, d_images, d_features, d_states_prev, d_moments_prev, d_states_next, d_moments_next, d_out, hip_stream);
+}
+int rtw_reproject_batch_device_f64(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, int32_t n_paths, const void *d_table, int32_t width, int32_t height, const void *d_images,
+                                   const void *d_features, const void *d_states_prev, const void *d_moments_prev, void *d_states_next, void *d_moments_next, void *d_out, void *hip_stream) {
+    return temporal_batch_device<double>(t, c, n_paths, d_table, width, height, d_images, d_features, d_states_prev, d_moments_prev, d_states_next, d_moments_next, d_out, hip_stream);
+}
+int rtw_reproject_noise_batch_device_f32(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int32_t n_paths, const void *d_states, const void *d_moments, void *d_noise,
+                                         void *hip_stream) {
+    return temporal_noise_batch_device<float>(n, width, height, n_paths, d_states, d_moments, d_noise, hip_stream);
+}
+int rtw_reproject_noise_batch_device_f64(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int32_t n_paths, const void *d_states, const void *d_moments, void *d_noise,
+                                         void *hip_stream) {
+    return temporal_noise_batch_device<double>(n, width, height, n_paths, d_states, d_moments, d_noise, hip_stream);
 }
 
 }  // extern "C"

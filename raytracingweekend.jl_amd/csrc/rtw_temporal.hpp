@@ -13,6 +13,8 @@
 //                  i.  A pixel whose history is at least min_len long divides its temporal variance M - Lm^2 by len; any other pixel estimates
 //                  the variance over its (2r+1)^2 window under tp_tap's weights (sb = 1, zexp = z_p), taps from global memory: the E and the G
 //                  slot, one element of M (Lm_q comes from the E slot) -- two 16-byte slots and one element per tap; len is the centre's alone.
+//   PATHS          true (rtw_reproject_*_batch_device_*): n_paths paths in one launch, TpPaths below; false: the instance is the single form's,
+//                  instruction for instruction (the flag only adds code under `if constexpr`).
 // No LDS, no atomics, no cross-lane operation; the trip count over the 4 taps is uniform, skipped taps are dropped by selects, as in dn_tap.
 // (tp_noise: lanes with a long history skip the window by a branch of their own; the window's trip count is the radius', uniform.)
 // Every operation is rounded once (the Makefile's -ffp-contract=off -fno-fast-math); divisions and sqrt are the compiler's IEEE ones.
@@ -34,6 +36,16 @@ template <typename T> struct TpParams {
 __device__ __forceinline__ float tp_floor(float x) { return __builtin_floorf(x); }
 __device__ __forceinline__ double tp_floor(double x) { return __builtin_floor(x); }
 template <typename T> __device__ __forceinline__ T tp_dot(T ax, T ay, T az, const T *b) { return (ax * b[0] + ay * b[1]) + az * b[2]; }
+
+// the camera constants of a path from its table entry (include/rtw_hip.h rtw_reproject_table_*: TpParams' head o .. iv, element for element)
+template <typename T> __device__ __forceinline__ void tp_load_cameras(TpParams<T> &U, const T *__restrict__ e) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        U.o[k] = e[k]; U.llc[k] = e[3 + k]; U.hor[k] = e[6 + k]; U.ver[k] = e[9 + k];
+        U.po[k] = e[12 + k]; U.pw[k] = e[15 + k]; U.ph[k] = e[18 + k]; U.pv[k] = e[21 + k];
+    }
+    U.Kw = e[24]; U.Qh = e[25]; U.Qv = e[26]; U.ih = e[27]; U.iv = e[28];
+}
 
 template <typename T> struct TpSum { T w, e0, e1, e2, l; };
 
@@ -61,13 +73,42 @@ __device__ __forceinline__ T tp_tap(TpSum<T> &a, const V &g, bool hasP, T zexp, 
     return w;
 }
 
+// The trailing argument of the three kernels.  PATHS = false (one path): empty.  PATHS = true (rtw_reproject_batch_device_*,
+// rtw_reproject_noise_batch_device_*): n_paths independent paths in one launch, the path index s = blockIdx.z * gridDim.y + blockIdx.y uniform over
+// a workgroup; blockIdx.x numbers the blocks (tiles) of ONE path as in the single form.  Path s reads its camera constants from elements
+// [32 s, 32 s + 29) of `table` -- the head of TpParams, o .. iv, in this order (uniform addresses: scalar loads) -- and finds its image, features,
+// states and moment planes s strides behind the base pointers; then the body runs unchanged: it indexes relative to its base pointers and
+// bounds every tap by W and H, which keeps a tap inside its own path.
+constexpr unsigned TP_PATHS_Y = 65535;     // paths per grid row: what one 16-bit grid dimension holds
+template <typename T, bool PATHS> struct TpPaths {};
+template <typename T> struct TpPaths<T, true> {
+    const T *table;                     // 32 elements per path (tp_noise: unused)
+    long long st_stride, mo_stride;     // BYTES from one path's state / moment plane to the next (rtw_temporal_state_bytes, rtw_history_moment_bytes)
+    unsigned n_paths;
+};
+template <typename T> __device__ __forceinline__ const T *tp_adv(const T *p, long long bytes) { return (const T *)((const char *)p + bytes); }
+template <typename T> __device__ __forceinline__ T *tp_adv(T *p, long long bytes) { return (T *)((char *)p + bytes); }
+
 // lane = flat pixel P = j*H + i
-template <typename T, bool HAS_PREV, bool MOMENTS = false>
+template <typename T, bool HAS_PREV, bool MOMENTS = false, bool PATHS = false>
 __global__ __launch_bounds__(256) void tp_step(TpParams<T> U, const T *__restrict__ image, const typename DnVec<T>::type *__restrict__ feat,
                                                const typename DnVec<T>::type *__restrict__ Ep, const typename DnVec<T>::type *__restrict__ Gp, const T *__restrict__ Lp,
                                                typename DnVec<T>::type *__restrict__ En, typename DnVec<T>::type *__restrict__ Gn, T *__restrict__ Ln, T *__restrict__ out,
-                                               const T *__restrict__ Mp, T *__restrict__ Mn) {
+                                               const T *__restrict__ Mp, T *__restrict__ Mn, [[maybe_unused]] TpPaths<T, PATHS> B) {
     using V = typename DnVec<T>::type;
+    if constexpr (PATHS) {
+        const long long s = (long long)blockIdx.z * gridDim.y + blockIdx.y;
+        if (s >= B.n_paths) return;
+        const long long fr = (long long)U.W * U.H * (long long)sizeof(T);         // bytes of one plane of one element per pixel
+        image = tp_adv(image, s * fr * 3); out = tp_adv(out, s * fr * 3); feat = tp_adv(feat, s * fr * 8);
+        En = tp_adv(En, s * B.st_stride); Gn = tp_adv(Gn, s * B.st_stride); Ln = tp_adv(Ln, s * B.st_stride);
+        if constexpr (MOMENTS) Mn = tp_adv(Mn, s * B.mo_stride);
+        if constexpr (HAS_PREV) {
+            Ep = tp_adv(Ep, s * B.st_stride); Gp = tp_adv(Gp, s * B.st_stride); Lp = tp_adv(Lp, s * B.st_stride);
+            if constexpr (MOMENTS) Mp = tp_adv(Mp, s * B.mo_stride);
+            tp_load_cameras(U, B.table + s * 32);
+        }
+    }
     const long long H = U.H, W = U.W, n_pix = W * H;
     const long long P = (long long)blockIdx.x * 256 + threadIdx.x;
     if (P >= n_pix) return;
@@ -190,10 +231,17 @@ template <typename T> struct TpNoiseParams {
 };
 
 // lane = flat pixel P = j*H + i of the state (E, G, L) and the moment plane M -> noise[P]
-template <typename T>
+template <typename T, bool PATHS = false>
 __global__ __launch_bounds__(256) void tp_noise(TpNoiseParams<T> U, const typename DnVec<T>::type *__restrict__ E, const typename DnVec<T>::type *__restrict__ G, const T *__restrict__ L,
-                                                const T *__restrict__ M, T *__restrict__ noise) {
+                                                const T *__restrict__ M, T *__restrict__ noise, [[maybe_unused]] TpPaths<T, PATHS> B) {
     using V = typename DnVec<T>::type;
+    if constexpr (PATHS) {
+        const long long s = (long long)blockIdx.z * gridDim.y + blockIdx.y;
+        if (s >= B.n_paths) return;
+        E = tp_adv(E, s * B.st_stride); G = tp_adv(G, s * B.st_stride); L = tp_adv(L, s * B.st_stride);
+        M = tp_adv(M, s * B.mo_stride);
+        noise = tp_adv(noise, s * ((long long)U.W * U.H * (long long)sizeof(T)));
+    }
     const long long H = U.H, W = U.W, n_pix = W * H;
     const long long P = (long long)blockIdx.x * 256 + threadIdx.x;
     if (P >= n_pix) return;

@@ -30,13 +30,25 @@ template <typename T> struct TpClampParams {
 };
 
 // block = tile (tile column tJ, tile row tI) = blockIdx.x / tiles_i, blockIdx.x % tiles_i; lane = (tj, ti) = threadIdx.x / 32, threadIdx.x % 32
-template <typename T, bool MOMENTS, bool GUIDES>
+// PATHS (rtw_temporal.hpp TpPaths): blockIdx.x numbers the tiles of ONE path; the path comes from blockIdx.y / .z, so a whole workgroup leaves
+// together before the barrier when its path index is past the last one.
+template <typename T, bool MOMENTS, bool GUIDES, bool PATHS = false>
 __global__ __launch_bounds__(256) void tp_step_clamped(TpParams<T> U, TpClampParams<T> C, const T *__restrict__ image, const typename DnVec<T>::type *__restrict__ feat,
                                                        const typename DnVec<T>::type *__restrict__ Ep, const typename DnVec<T>::type *__restrict__ Gp, const T *__restrict__ Lp,
                                                        typename DnVec<T>::type *__restrict__ En, typename DnVec<T>::type *__restrict__ Gn, T *__restrict__ Ln, T *__restrict__ out,
-                                                       const T *__restrict__ Mp, T *__restrict__ Mn) {
+                                                       const T *__restrict__ Mp, T *__restrict__ Mn, [[maybe_unused]] TpPaths<T, PATHS> B) {
     using V = typename DnVec<T>::type;
     __shared__ V sE[TP_SLOTS], sG[TP_SLOTS];
+    if constexpr (PATHS) {
+        const long long s = (long long)blockIdx.z * gridDim.y + blockIdx.y;
+        if (s >= B.n_paths) return;
+        const long long fr = (long long)U.W * U.H * (long long)sizeof(T);         // bytes of one plane of one element per pixel
+        image = tp_adv(image, s * fr * 3); out = tp_adv(out, s * fr * 3); feat = tp_adv(feat, s * fr * 8);
+        Ep = tp_adv(Ep, s * B.st_stride); Gp = tp_adv(Gp, s * B.st_stride); Lp = tp_adv(Lp, s * B.st_stride);
+        En = tp_adv(En, s * B.st_stride); Gn = tp_adv(Gn, s * B.st_stride); Ln = tp_adv(Ln, s * B.st_stride);
+        if constexpr (MOMENTS) { Mp = tp_adv(Mp, s * B.mo_stride); Mn = tp_adv(Mn, s * B.mo_stride); }
+        tp_load_cameras(U, B.table + s * 32);
+    }
     const long long H = U.H, W = U.W;
     const int r = C.r, SI = TP_TI + 2 * r, n_stage = SI * (TP_TJ + 2 * r);
     const unsigned tJ = blockIdx.x / C.tiles_i, tI = blockIdx.x - tJ * C.tiles_i;

@@ -20,6 +20,11 @@ standard deviations of the current frame's window before it blends, and shorten 
 ``temporal_step_clamped``, ``temporal_step_clamped_into``, ``TemporalAccumulator(clamp=...)``, ``render_sequence(..., clamp=...)``; witness:
 tests/temporal_clamp_ref.py).  Its defaults ``radius=1, guides=False, sigma=1, len_scale=1`` are UNTUNED.  Omitting
 ``clamp`` is the plain step, call for call.
+
+Batched steps (``rtw_reproject_*``, ``rtw_render_paths_*``): several independent camera paths over one scene (a stereo pair, orbiting
+cameras) advance in EACH launch -- no new arithmetic, path s is the single call of path s on the bits; the per-path camera constants travel
+in a device table (``temporal_path_table``, ``temporal_step_batch_into``, ``temporal_noise_batch_into``, ``TemporalBatchAccumulator``,
+``render_sequences``; witness: tests/paths_ref.py, the single witnesses side by side; what it saves: DESIGN.md section 7.22).
 """
 import ctypes as C
 
@@ -98,17 +103,22 @@ def _host_step(name, image, features, cam, state, moment, cam_prev, params, *, c
     return np.swapaxes(out, 0, 1), nxt, mom, np.swapaxes(rho, 0, 1) if noise_map else None
 
 
-def _enqueue_step(name, cam, cam_prev, image_width, image_height, elem_type, stream, params, clamp, *ptrs):
+def _enqueue_step(name, cam, cam_prev, image_width, image_height, elem_type, stream, params, clamp, *ptrs, paths=None):
     """A device-resident step: the cameras, ``make_temporal(**params)``, with ``clamp`` its parameters behind them, the frame, the DEVICE
-    pointers in the entry point's order (None: a null pointer) and the stream -> ``name`` + the element type's suffix."""
+    pointers in the entry point's order (None: a null pointer) and the stream -> ``name`` + the element type's suffix.  ``paths``
+    ``(n_paths, d_table_ptr)``: a batched step (rtw_reproject_batch_device_*) -- the count and the device table stand in the cameras' place
+    and the clamp's slot is always there (None: plain steps)."""
     T = np.dtype(elem_type).type
-    Cm = _camera_arg(cam, T, "cam")
-    Cp = C.byref(_camera_arg(cam_prev, T, "cam_prev")) if cam_prev is not None else None
     heads = [C.byref(make_temporal(**params))]
     if clamp is not None:
         heads.append(C.byref(make_temporal_clamp(**_clamp_arg(clamp))))
+    if paths is not None:
+        heads += ([None] if clamp is None else []) + [int(paths[0]), C.c_void_p(int(paths[1]))]
+    else:
+        Cm = _camera_arg(cam, T, "cam")
+        heads += [C.byref(Cm), C.byref(_camera_arg(cam_prev, T, "cam_prev")) if cam_prev is not None else None]
     fn = getattr(_capi.lib(), name + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(*heads, C.byref(Cm), Cp, int(image_width), int(image_height), *(C.c_void_p(int(q)) if q is not None else None for q in ptrs), C.c_void_p(int(stream))))
+    _capi.check(fn(*heads, int(image_width), int(image_height), *(C.c_void_p(int(q)) if q is not None else None for q in ptrs), C.c_void_p(int(stream))))
 
 
 def temporal_step(image, features, cam, state=None, cam_prev=None, **params):
@@ -184,15 +194,20 @@ def temporal_step_moments_into(d_out_ptr, d_state_next_ptr, d_moment_next_ptr, d
                   d_moment_prev_ptr, d_state_next_ptr, d_moment_next_ptr, d_out_ptr)
 
 
+def _enqueue_noise(name, n_paths, d_noise_ptr, d_state_ptr, d_moment_ptr, image_width, image_height, elem_type, stream, noise):
+    """A device-resident noise map through ``name`` + the element type's suffix; ``n_paths`` not None: the batched entry point's count"""
+    tn = make_temporal_noise(**noise)
+    T = np.dtype(elem_type).type
+    fn = getattr(_capi.lib(), name + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(C.byref(tn), int(image_width), int(image_height), *([int(n_paths)] if n_paths is not None else []), C.c_void_p(int(d_state_ptr)),
+                   C.c_void_p(int(d_moment_ptr)), C.c_void_p(int(d_noise_ptr)), C.c_void_p(int(stream))))
+
+
 def temporal_noise_into(d_noise_ptr, d_state_ptr, d_moment_ptr, image_width, image_height, *, elem_type=np.float32, stream=0, **noise):
     """The device-resident noise map (rtw_history_noise_device_*): enqueue the map of a state and its moment plane on ``stream``.  All are
     DEVICE pointers; the map is H*W elements, pixel (i, j) at j*H + i -- what ``guided_filter``'s device forms read.  Keywords:
     ``make_temporal_noise`` (the defaults are untuned)."""
-    tn = make_temporal_noise(**noise)
-    T = np.dtype(elem_type).type
-    fn = getattr(_capi.lib(), "rtw_history_noise_device_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(tn), int(image_width), int(image_height), C.c_void_p(int(d_state_ptr)), C.c_void_p(int(d_moment_ptr)), C.c_void_p(int(d_noise_ptr)),
-                   C.c_void_p(int(stream))))
+    _enqueue_noise("rtw_history_noise_device_", None, d_noise_ptr, d_state_ptr, d_moment_ptr, image_width, image_height, elem_type, stream, noise)
 
 
 _CLAMP_KEYS = ("radius", "guides", "sigma", "len_scale")
@@ -333,6 +348,15 @@ def render_sequence(scene, cams, image_width=400, n_samples=1, *, seeds=None, de
     rtw_render_path_clamped_*): the steps behind view 0 are clamped steps, in any of the three forms above; the clamp's defaults are untuned.
     ``gamma`` is applied once, by the last stage.  Returns ``img[v, i, j, :]``; ``last_stats()`` reports the render.
     ``seeds``: a sequence of ``len(cams)`` ints (None: ``seed`` for every view).  The temporal defaults are untuned (see the module's docstring)."""
+    return _render_frames(scene, cams, 0, image_width, n_samples, seeds=seeds, denoise=denoise, guided=guided, clamp=clamp, depth=depth, seed=seed, n_chunks=n_chunks,
+                          device=device, gamma=gamma, group_cull=group_cull, scan_valu=scan_valu, numerics=numerics, normal_power_log2=normal_power_log2,
+                          sigma_depth=sigma_depth, min_weight=min_weight, history_max=history_max, demodulate=demodulate)
+
+
+def _render_frames(scene, cams, n_paths, image_width, n_samples, *, seeds=None, denoise=None, guided=None, clamp=None, depth=16, seed=1, n_chunks=0, device=-1, gamma=True,
+                   group_cull=False, scan_valu=False, numerics=None, normal_power_log2=1, sigma_depth=0.1, min_weight=0.25, history_max=16.0, demodulate=True):
+    """The one marshalling of the sequence calls.  ``n_paths == 0``: ``render_sequence``'s entry points over the path ``cams``; ``n_paths >= 1``:
+    rtw_render_paths_* over ``cams`` and ``seeds`` in STEP-major order (path s at step k: entry ``k*n_paths + s``).  -> ``img[frame, i, j, :]``"""
     from .structs import flatten_scene
     cams, T = _batch_cameras(cams)
     n = len(cams)
@@ -362,7 +386,12 @@ def render_sequence(scene, cams, image_width=400, n_samples=1, *, seeds=None, de
                           (_capi.FLAG_GROUP_CULL if group_cull else 0) | (_capi.FLAG_SCAN_VALU if scan_valu else 0), numerics=numerics)
     out = np.empty(n * height * int(image_width) * 3, dtype=T)
     sfx = "f64" if _capi.is_f64(T) else "f32"
-    if clamp:
+    if n_paths:
+        K = make_temporal_clamp(**_clamp_arg(clamp)) if clamp else None
+        _capi.check(getattr(L, "rtw_render_paths_" + sfx)(C.byref(S), _capi.make_cameras(cams, T), int(n_paths), n // int(n_paths), sd, C.byref(P), C.byref(tp),
+                                                          C.byref(K) if K is not None else None, C.byref(N) if N is not None else None,
+                                                          C.byref(D) if D is not None else None, out.ctypes.data_as(C.c_void_p)))
+    elif clamp:
         K = make_temporal_clamp(**_clamp_arg(clamp))
         _capi.check(getattr(L, "rtw_render_path_clamped_" + sfx)(C.byref(S), _capi.make_cameras(cams, T), n, sd, C.byref(P), C.byref(tp), C.byref(K),
                                                                  C.byref(N) if N is not None else None, C.byref(D) if D is not None else None,
@@ -376,3 +405,143 @@ def render_sequence(scene, cams, image_width=400, n_samples=1, *, seeds=None, de
     del keep
     _record_stats(L)
     return out.reshape(n, int(image_width), height, 3).transpose(0, 2, 1, 3)
+
+
+# ---- batched steps: n_paths independent camera paths advance in each launch (include/rtw_hip.h rtw_reproject_*, rtw_render_paths_*) ----
+
+def temporal_path_table(cams, cams_prev=None, elem_type=None):
+    """The camera constants of ``len(cams)`` paths (rtw_reproject_table_*): -> a host array ``(n_paths, 32)`` in the header's public layout --
+    the current camera's origin, lower_left_corner, horizontal, vertical; the previous camera's origin, w, horizontal, vertical; Kw, Qh, Qv,
+    ih, iv; three zeros.  ``cams_prev`` None (first frames): elements 12..28 are 0.  ``elem_type``: None takes the cameras'.  The caller
+    uploads it; a batched step reads it on the device."""
+    cams, T = _batch_cameras(cams)
+    if elem_type is not None:
+        T = np.dtype(elem_type).type
+    n = len(cams)
+    Cp = None
+    if cams_prev is not None:
+        cams_prev = list(cams_prev)
+        if len(cams_prev) != n:
+            raise ValueError(f"{len(cams_prev)} previous cameras for {n} paths")
+        for c in cams_prev:
+            _camera_arg(c, T, "cams_prev")                          # (the type and the element type, checked)
+        Cp = _capi.make_cameras(cams_prev, T)
+    for c in cams:
+        _camera_arg(c, T, "cams")
+    table = np.zeros((n, 32), dtype=T)
+    fn = getattr(_capi.lib(), "rtw_reproject_table_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(_capi.make_cameras(cams, T), Cp, n, table.ctypes.data_as(C.c_void_p)))
+    return table
+
+
+def temporal_step_batch_into(d_out_ptr, d_states_next_ptr, d_images_ptr, d_features_ptr, d_table_ptr, n_paths, image_width, image_height, *, clamp=None,
+                             d_states_prev_ptr=None, d_moments_prev_ptr=None, d_moments_next_ptr=None, elem_type=np.float32, stream=0, **params):
+    """The device-resident batched step (rtw_reproject_batch_device_*): ``n_paths`` paths advance in ONE launch on ``stream``; path s is, on the
+    bits, ``temporal_step_into`` / ``temporal_step_moments_into`` / ``temporal_step_clamped_into`` of path s.  All are DEVICE pointers; every
+    buffer holds the paths one behind the other (states at ``temporal_state_bytes``, moment planes at ``temporal_moment_bytes``);
+    ``d_table_ptr``: the uploaded ``temporal_path_table``.  ``clamp`` None: plain steps; no moment pointer: no moments;
+    ``d_states_prev_ptr`` None: every path's first frame.  Other keywords: ``make_temporal``."""
+    _enqueue_step("rtw_reproject_batch_device_", None, None, image_width, image_height, elem_type, stream, params, clamp if clamp else None, d_images_ptr, d_features_ptr,
+                  d_states_prev_ptr, d_moments_prev_ptr, d_states_next_ptr, d_moments_next_ptr, d_out_ptr, paths=(n_paths, d_table_ptr))
+
+
+def temporal_noise_batch_into(d_noise_ptr, d_states_ptr, d_moments_ptr, n_paths, image_width, image_height, *, elem_type=np.float32, stream=0, **noise):
+    """The device-resident batched noise map (rtw_reproject_noise_batch_device_*): the maps of ``n_paths`` states and their moment planes, one
+    behind the other (``n_paths * H * W`` elements), in ONE launch on ``stream``.  Keywords: ``make_temporal_noise``."""
+    _enqueue_noise("rtw_reproject_noise_batch_device_", n_paths, d_noise_ptr, d_states_ptr, d_moments_ptr, image_width, image_height, elem_type, stream, noise)
+
+
+class TemporalBatchAccumulator:
+    """The histories of ``n_paths`` camera paths of one frame size on one device: two SETS of device states (with ``moments=True`` of moment
+    planes too), the device table of the paths' camera constants and the previous step's cameras.  ``step`` uploads the table on ``stream``
+    (ordered before the launch), enqueues ONE ``temporal_step_batch_into`` for all paths and swaps the sets; ``reset`` forgets every history.
+    All paths step together: there is no path that joins or resets alone.  ``clamp`` / ``moments`` / keywords: as ``TemporalAccumulator``."""
+
+    def __init__(self, n_paths, image_width, image_height, *, elem_type=np.float32, device=0, moments=False, clamp=None, **params):
+        import torch
+        make_temporal(**params)                                    # (the keywords, checked now)
+        self.clamp = _clamp_arg(clamp) if clamp else None
+        if self.clamp is not None:
+            make_temporal_clamp(**self.clamp)
+        self.n_paths, self.width, self.height, self.elem_type = int(n_paths), int(image_width), int(image_height), np.dtype(elem_type).type
+        if self.n_paths < 1:
+            raise ValueError(f"n_paths must be >= 1, got {self.n_paths}")
+        if self.width < 1 or self.height < 1:
+            raise ValueError(f"empty frame {self.width} x {self.height}")
+        self.params = dict(params, device=int(device))
+        self.moments = bool(moments)
+        item = np.dtype(self.elem_type).itemsize
+        self._n_state = temporal_state_bytes(self.width, self.height, self.elem_type) // item
+        self._n_mom = temporal_moment_bytes(self.width, self.height, self.elem_type) // item
+        dt = torch.float64 if _capi.is_f64(self.elem_type) else torch.float32
+        dev = f"cuda:{int(device)}"
+        self._states = [torch.zeros(self.n_paths * self._n_state, dtype=dt, device=dev) for _ in range(2)]
+        self._moments = [torch.zeros(self.n_paths * self._n_mom, dtype=dt, device=dev) for _ in range(2)] if self.moments else None
+        self._table = torch.zeros(self.n_paths * 32, dtype=dt, device=dev)
+        torch.cuda.synchronize(int(device))
+        self._cur = 0                                              # the set the NEXT step writes
+        self._cams_prev = None
+        self.frames = 0
+
+    def reset(self):
+        self._cams_prev = None
+        self.frames = 0
+
+    def state(self, s):
+        """the torch tensor (a view) that holds the state the last step left for path ``s`` (None before the first step or after ``reset``)"""
+        if self._cams_prev is None:
+            return None
+        return self._states[self._cur ^ 1][int(s) * self._n_state:(int(s) + 1) * self._n_state]
+
+    def moment(self, s):
+        """... and its moment plane (None without ``moments=True``)"""
+        if self._cams_prev is None or not self.moments:
+            return None
+        return self._moments[self._cur ^ 1][int(s) * self._n_mom:(int(s) + 1) * self._n_mom]
+
+    def step(self, cams, d_images_ptr, d_features_ptr, d_out_ptr, stream=0):
+        import torch
+        cams = list(cams)
+        if len(cams) != self.n_paths:
+            raise ValueError(f"{len(cams)} cameras for {self.n_paths} paths")
+        table = torch.from_numpy(temporal_path_table(cams, self._cams_prev, self.elem_type).reshape(-1))
+        # (from pageable memory: the copy has left the host array when copy_ returns, and runs on `stream` in front of the launch)
+        with torch.cuda.stream(torch.cuda.ExternalStream(int(stream), device=self._table.device) if int(stream) else torch.cuda.default_stream(self._table.device)):
+            self._table.copy_(table, non_blocking=True)
+        first = self._cams_prev is None
+        temporal_step_batch_into(d_out_ptr, self._states[self._cur].data_ptr(), d_images_ptr, d_features_ptr, self._table.data_ptr(), self.n_paths, self.width, self.height,
+                                 clamp=self.clamp, d_states_prev_ptr=None if first else self._states[self._cur ^ 1].data_ptr(),
+                                 d_moments_prev_ptr=None if first or not self.moments else self._moments[self._cur ^ 1].data_ptr(),
+                                 d_moments_next_ptr=self._moments[self._cur].data_ptr() if self.moments else None, elem_type=self.elem_type, stream=stream, **self.params)
+        self._cur ^= 1
+        self._cams_prev = cams
+        self.frames += 1
+
+    def noise_into(self, d_noise_ptr, stream=0, **noise):
+        """enqueue the ``n_paths`` noise maps (``temporal_noise_batch_into``) of the states and moments the last step left"""
+        if not self.moments:
+            raise ValueError("noise_into needs an accumulator made with moments=True")
+        if self._cams_prev is None:
+            raise ValueError("noise_into before the first step: there is no state yet")
+        temporal_noise_batch_into(d_noise_ptr, self._states[self._cur ^ 1].data_ptr(), self._moments[self._cur ^ 1].data_ptr(), self.n_paths, self.width, self.height,
+                                  elem_type=self.elem_type, stream=stream, device=self.params["device"], **noise)
+
+
+def render_sequences(scene, paths, image_width=400, n_samples=1, *, seeds=None, **kw):
+    """``S = len(paths)`` camera paths of equal length N over one scene, each with its own history, in ONE call on the device
+    (rtw_render_paths_*): one batched render and one feature pass over all S*N views, N batched step launches (every launch advances all
+    S paths), with ``guided`` N batched noise launches, with ``denoise`` one batched filter pass.  ``paths``: a list of S equally long lists
+    of cameras; ``seeds``: None (``seed`` for every view) or S sequences of N ints.  Everything else: ``render_sequence``'s keywords, and
+    path s of the result equals ``render_sequence(scene, paths[s], ..., seeds=seeds[s])`` on the bits.  Returns ``img[s, k, i, j, :]``
+    (path, step).  The transposition to the library's step-major order happens here and nowhere else."""
+    paths = [list(p) for p in paths]
+    if not paths or not paths[0] or any(len(p) != len(paths[0]) for p in paths):
+        raise ValueError("paths must be a non-empty list of equally long, non-empty camera lists")
+    S, N = len(paths), len(paths[0])
+    if seeds is not None:
+        seeds = [list(sd) for sd in seeds]
+        if len(seeds) != S or any(len(sd) != N for sd in seeds):
+            raise ValueError(f"seeds must be {S} sequences of {N} ints")
+        seeds = [seeds[s][k] for k in range(N) for s in range(S)]
+    out = _render_frames(scene, [paths[s][k] for k in range(N) for s in range(S)], S, image_width, n_samples, seeds=seeds, **kw)
+    return out.reshape((N, S) + out.shape[1:]).swapaxes(0, 1)

@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_TBS = 6.3
-TP_LINE = re.compile(r"^\[rtw temporal\] (f32|f64) (\d+)x(\d+) step prev=([01]) ms=([0-9.]+)$")
+TP_LINE = re.compile(r"^\[rtw temporal\] (f32|f64) (\d+)x(\d+) step prev=([01]) paths=0 ms=([0-9.]+)$")
 DN_LINE = re.compile(r"^\[rtw denoise\] (f32|f64) (\d+)x(\d+) level step=1 final=0 ms=([0-9.]+)$")
 WIDTHS = (96, 480, 1920)
 

@@ -26,8 +26,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 HBM_TBS = 6.3
-STEP_LINE = re.compile(r"^\[rtw temporal\] (f32|f64) (\d+)x(\d+) (step|step\+moments) prev=1 ms=([0-9.]+)$")
-CLAMP_LINE = re.compile(r"^\[rtw temporal\] (f32|f64) (\d+)x(\d+) (clamped|clamped\+moments) r=(\d) guides=(\d) ms=([0-9.]+)$")
+STEP_LINE = re.compile(r"^\[rtw temporal\] (f32|f64) (\d+)x(\d+) (step|step\+moments) prev=1 paths=0 ms=([0-9.]+)$")
+CLAMP_LINE = re.compile(r"^\[rtw temporal\] (f32|f64) (\d+)x(\d+) (clamped|clamped\+moments) r=(\d) guides=(\d) paths=0 ms=([0-9.]+)$")
 WIDTHS = (96, 480, 1920)
 RADII = (1, 2, 3)
 
