@@ -834,7 +834,8 @@ int rtw_render_upsampled_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_
  * d_state_prev (state_prev) null -> -2; a frame of 2^31 8x8 tiles or more (the denoiser's frame rule) -> -5; the sequence call additionally
  * refuses everything rtw_render_filtered_batch_* refuses for its arguments (with `d` NULL: everything a batched feature render refuses).
  *   Left out on purpose: accumulators or the upsampler as the step's input,
- * device lists, moving spheres (the scene is static: there are no motion vectors beyond the camera's), a variance-guided alpha.
+ * device lists, a variance-guided alpha.  (Spheres that move between the frames: the rtw_first_hit_motion_* block further down; the steps of
+ * this block know no motion but the camera's.)
  * (Neighbourhood colour clamping: the rtw_clamped_step_* block further down.  A per-pixel noise map from the history's second moments, and the sequence call that feeds it to the
  * noise-guided filter: the block behind these declarations.)  Additive to ABI 4: detected by symbol lookup. */
 #define RTW_TEMPORAL_DEMODULATE 1  /* accumulate image / albedo, multiply the current albedo back at the end */
@@ -1087,6 +1088,89 @@ int rtw_render_paths_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams,
 int rtw_render_paths_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_paths, int32_t n_steps, const uint64_t *seeds, const rtw_params *p,
                          const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* may be NULL */, const rtw_temporal_noise_t *n /* may be NULL */,
                          const rtw_denoise_t *d /* may be NULL */, double *out);
+
+/* Temporal reuse over moving spheres: a first-hit motion pass and the step that reads it.  The steps above reproject a pixel's first-hit
+ * point as if the world stood still; where a sphere moved between two frames they gather the history of the wrong place (a reset, or a
+ * ghost).  One new pass says, per pixel, which sphere the pixel sees and how far that sphere moved since the previous frame; the step
+ * subtracts that displacement from the world point before it projects.  Everything behind the projection -- taps, weights, blend, clamp,
+ * moments, the noise map and the filters -- is what the blocks above define.
+ * (The entry points are named rtw_motion_table_*, rtw_first_hit_motion_* and rtw_animated_step_*: the names of the blocks above are closed sets.)
+ *
+ * The definition.  Arithmetic is in T, every operation is rounded once, there is no FMA beyond what a numerics mode of hit(::Sphere)
+ * itself contracts, quotients and sqrt are the correctly rounded IEEE ones.
+ *   Motion plane.  H*W slots of 4 elements of T, each slot 16-byte aligned; pixel (i, j) at slot j*H + i holds (m.x, m.y, m.z, id):
+ * m is the world-space displacement, since the previous frame, of the surface the pixel sees; id is the caller's index of the sphere
+ * seen, as a value of T, or -1 for the sky.
+ *   Motion table.  n slots of 4 elements in the caller's sphere order: (dx, dy, dz, 0).  rtw_motion_table_*(scene_prev, scene, table) is
+ * pure host code like rtw_reproject_table_*: per component d = c_cur - c_prev, ONE subtraction in T; a sphere with k >= n_prev, or whose
+ * radius differs bitwise from the previous scene's, is new or changed and gets three quiet NaNs, so that its pixels reset.  `table`
+ * receives scene->n * 4 elements; the caller uploads it.
+ *   The motion pass, per pixel.  The ray is the STEP's own ray, not a sample of the trace kernel: su, tv, D and nD exactly as in the
+ * rtw_temporal_* block; origin = cam.origin, direction = nD, the lens is ignored.  Its first hit is what a scan of all n spheres finds
+ * with hit(::Sphere) in the evaluation order of the numerics mode p->flags selects (RTW_FLAG_NUMERICS_*), tmin = 1e-4, tmax = +inf: the
+ * smallest root t wins, and among equal roots the LOWER caller's index.  (The trace kernel's scans keep the reference's loop, in which the
+ * later of two equal roots wins; the roots, and so the surface, are the same.)  A hit of sphere k gives the slot (table[k].xyz, T(k)); a miss
+ * gives (0, 0, 0, -1); with a NULL table m = 0 and the pass is an id (picking) buffer.
+ *   The motion step.  The plain step (rtw_temporal_device_*, rtw_history_moments_device_*) or the clamped one (rtw_clamped_step_device_*)
+ * with ONE change: for a `has` pixel  d = ((origin + z*nD) - m) - origin_prev  per component, in this order; a sky pixel is unchanged.
+ * A non-finite m makes d NaN, inr fails and the pixel resets: there is no extra rule.  The slot's fourth element has no effect on the
+ * step.  With m = 0 everywhere the step is the step of the blocks above on the bits (x - 0 == x).
+ * (tests/motion_ref.py restates all of this on the CPU and the device agrees on the bits.)
+ *
+ * rtw_first_hit_motion_device_*: ONE launch, asynchronous on `hip_stream` of the scene's device; of `p` the frame (width, height), the
+ * device and the numerics bits are read -- RTW_FLAG_SCAN_VALU and RTW_FLAG_GROUP_CULL are accepted and change nothing; spp, max_depth, seed
+ * and the chunks are not looked at.  `d_table` (scene n * 4 elements, may be NULL) and `d_motion` (H*W*4 elements) are 16-byte aligned
+ * DEVICE pointers that do not overlap.  rtw_stats() is left alone.
+ *   rtw_first_hit_motion_*: the host-buffer form, blocking, through the cached per-device context like rtw_render_features_f32 (the scene
+ * is uploaded, or reused when its bytes are the same); `table` may be NULL.  rtw_stats() is left alone.
+ *   rtw_animated_step_device_*: one step over a moving scene, ONE launch.  `c` NULL: no clamp; d_moment_prev and d_moment_next both NULL:
+ * no moments -- the pointer rule of rtw_clamped_step_device_*.  cam_prev, d_state_prev and d_motion are NULL together: the first frame,
+ * which runs the first-frame instance of the blocks above.  d_motion is 16-byte aligned and aliases no output.
+ *   rtw_animated_step_*: the host-buffer form, blocking, through the one host path of rtw_temporal_f32; `motion` as d_motion.
+ *   rtw_render_animation_*: n_frames frames of a scene that changes from frame to frame in one blocking call -- rtw_render_sequence_* /
+ * rtw_render_path_clamped_* with a scene per frame.  `scenes` and `cams` hold n_frames entries (the spheres of all scenes in one order:
+ * rtw_motion_table_* pairs them by index), `seeds` n_frames seeds (NULL: p->seed for every frame).  Per frame, on one stream of the cached
+ * per-device context: the scene's upload (skipped while its bytes are those of the frame before), the render of `p` with gamma 0, the
+ * feature pass over all of its chunks, from frame 1 on the motion table against the frame before and the motion pass (of p->flags it gets
+ * the scan-mode and numerics bits), then the step -- frame 0 is a first frame; `c` non-NULL: clamped steps; no moments.  With `d`, ONE
+ * batched filter pass (rtw_filter_batch_*'s launches) over the accumulated frames and their features follows.  ONE D2H of n_frames frames
+ * into `out`; p->gamma is applied once, by the last stage that runs.  Frame v equals, on the bits, the chain of the single calls
+ * (rtw_render_*, rtw_render_features_*, rtw_motion_table_*, rtw_first_hit_motion_*, rtw_animated_step_*, rtw_filter_batch_*), and with
+ * n_frames identical scenes the call is rtw_render_sequence_* / rtw_render_path_clamped_* (n NULL) with the same arguments.  rtw_stats()
+ * reports the counters of all frames' renders summed and the times of the slowest.
+ *   Refusals, all decided before any HIP call: a null argument that is not optional -> -1; everything the step of the blocks above refuses,
+ * with its code; exactly one of d_motion / d_state_prev (motion / state_prev) null, a motion plane or a table that is not 16-byte aligned,
+ * a plane that overlaps the table or an output, width or height < 1, device < -1, flag bits other than the scan-mode and numerics ones, both
+ * numerics bits -> -2; a scene (handle) of the other precision, p->device that is not the handle's -> -4; the frame rule -> -5.
+ * rtw_render_animation_*: n_frames < 1, a negative sphere count -> -2; a null array of a scene that has spheres -> -1; everything
+ * rtw_render_sequence_* / rtw_render_path_clamped_* refuses for n_frames views, with its code.
+ *   Left out on purpose: batched paths with motion (rtw_reproject_batch_device_* has no motion planes),
+ * motion blur inside a frame, guided-filter and upsampler one-call forms, accumulators, device lists, the Julia shim.
+ * Additive to ABI 4: detected by symbol lookup. */
+int rtw_motion_table_f32(const rtw_scene_f32 *scene_prev, const rtw_scene_f32 *scene, void *table /* host */);
+int rtw_motion_table_f64(const rtw_scene_f64 *scene_prev, const rtw_scene_f64 *scene, void *table /* host */);
+int rtw_first_hit_motion_device_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const void *d_table /* may be NULL */,
+                                    void *d_motion, void *hip_stream);
+int rtw_first_hit_motion_device_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const void *d_table /* may be NULL */,
+                                    void *d_motion, void *hip_stream);
+int rtw_first_hit_motion_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const float *table /* may be NULL */, float *motion);
+int rtw_first_hit_motion_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const double *table /* may be NULL */, double *motion);
+int rtw_animated_step_device_f32(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* NULL: no clamp */, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev,
+                                 int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_motion, const void *d_state_prev,
+                                 void *d_state_next, const void *d_moment_prev, void *d_moment_next /* both NULL: no moments */, void *d_out, void *hip_stream);
+int rtw_animated_step_device_f64(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* NULL: no clamp */, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev,
+                                 int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_motion, const void *d_state_prev,
+                                 void *d_state_next, const void *d_moment_prev, void *d_moment_next /* both NULL: no moments */, void *d_out, void *hip_stream);
+int rtw_animated_step_f32(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* NULL: no clamp */, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev,
+                          int32_t width, int32_t height, const float *image, const float *features, const float *motion, const void *state_prev, void *state_next,
+                          const void *moment_prev, void *moment_next /* both NULL: no moments */, float *out);
+int rtw_animated_step_f64(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* NULL: no clamp */, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev,
+                          int32_t width, int32_t height, const double *image, const double *features, const double *motion, const void *state_prev, void *state_next,
+                          const void *moment_prev, void *moment_next /* both NULL: no moments */, double *out);
+int rtw_render_animation_f32(const rtw_scene_f32 *scenes, const rtw_camera_f32 *cams, int32_t n_frames, const uint64_t *seeds /* may be NULL */, const rtw_params *p,
+                             const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* may be NULL */, const rtw_denoise_t *d /* may be NULL */, float *out);
+int rtw_render_animation_f64(const rtw_scene_f64 *scenes, const rtw_camera_f64 *cams, int32_t n_frames, const uint64_t *seeds /* may be NULL */, const rtw_params *p,
+                             const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* may be NULL */, const rtw_denoise_t *d /* may be NULL */, double *out);
 
 /* Present stage: display-ready 8-bit frames from the device.  Every pipeline above ends in T elements in the column-major layout of the
  * render entry points; a window, a PNG or a video encoder wants 8-bit rows.  One kernel clips, rounds, packs and transposes in HBM, and the

@@ -38,6 +38,7 @@ from .temporal import (  # noqa: F401
     TemporalAccumulator, make_temporal, make_temporal_noise, render_sequence, temporal_moment_bytes, temporal_noise_into, temporal_state_bytes, temporal_step,
     temporal_step_into, temporal_step_moments, temporal_step_moments_into, make_temporal_clamp, temporal_step_clamped, temporal_step_clamped_into,
     temporal_path_table, temporal_step_batch_into, temporal_noise_batch_into, TemporalBatchAccumulator, render_sequences,
+    motion_table, first_hit_motion, first_hit_motion_into, temporal_step_animated, temporal_step_animated_into, render_animation,
 )
 from .present import (  # noqa: F401
     make_present, present, present_batch_into, present_bytes, present_into, render_presented, render_presented_batch,
@@ -63,5 +64,6 @@ __all__ = [
     "make_temporal_noise", "temporal_moment_bytes", "temporal_step_moments", "temporal_step_moments_into", "temporal_noise_into",
     "make_temporal_clamp", "temporal_step_clamped", "temporal_step_clamped_into",
     "temporal_path_table", "temporal_step_batch_into", "temporal_noise_batch_into", "TemporalBatchAccumulator", "render_sequences",
+    "motion_table", "first_hit_motion", "first_hit_motion_into", "temporal_step_animated", "temporal_step_animated_into", "render_animation",
     "make_present", "present_bytes", "present", "present_into", "present_batch_into", "render_presented", "render_presented_batch",
 ]

@@ -40,6 +40,9 @@ SYMBOLS = [
     "rtw_render_path_clamped_f32", "rtw_render_path_clamped_f64",
     "rtw_reproject_table_bytes", "rtw_reproject_table_f32", "rtw_reproject_table_f64", "rtw_reproject_batch_device_f32", "rtw_reproject_batch_device_f64",
     "rtw_reproject_noise_batch_device_f32", "rtw_reproject_noise_batch_device_f64", "rtw_render_paths_f32", "rtw_render_paths_f64",
+    "rtw_motion_table_f32", "rtw_motion_table_f64", "rtw_first_hit_motion_device_f32", "rtw_first_hit_motion_device_f64", "rtw_first_hit_motion_f32",
+    "rtw_first_hit_motion_f64", "rtw_animated_step_device_f32", "rtw_animated_step_device_f64", "rtw_animated_step_f32", "rtw_animated_step_f64",
+    "rtw_render_animation_f32", "rtw_render_animation_f64",
     "rtw_present_bytes", "rtw_present_device_f32", "rtw_present_device_f64", "rtw_present_batch_device_f32", "rtw_present_batch_device_f64",
     "rtw_present_f32", "rtw_present_f64", "rtw_render_presented_f32", "rtw_render_presented_f64", "rtw_render_presented_batch_f32",
     "rtw_render_presented_batch_f64",
@@ -236,6 +239,12 @@ def lib():
         getattr(L, "rtw_reproject_batch_device_" + sfx).argtypes = [tp, tc, i32, ptr, i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_reproject_noise_batch_device_" + sfx).argtypes = [tn, i32, i32, i32, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_render_paths_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, i32, seeds, C.POINTER(Params), tp, tc, tn, C.POINTER(Denoise), ptr]
+        getattr(L, "rtw_motion_table_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(SceneT), ptr]
+        getattr(L, "rtw_first_hit_motion_device_" + sfx).argtypes = [ptr, C.POINTER(CamT), C.POINTER(Params), ptr, ptr, ptr]
+        getattr(L, "rtw_first_hit_motion_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), C.POINTER(Params), ptr, ptr]
+        getattr(L, "rtw_animated_step_device_" + sfx).argtypes = [tp, tc, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_animated_step_" + sfx).argtypes = [tp, tc, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_render_animation_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), tp, tc, C.POINTER(Denoise), ptr]
         pr, dn = C.POINTER(Present), C.POINTER(Denoise)
         getattr(L, "rtw_present_device_" + sfx).argtypes = [pr, i32, i32, ptr, ptr, ptr]
         getattr(L, "rtw_present_batch_device_" + sfx).argtypes = [pr, i32, i32, i32, ptr, ptr, ptr]

@@ -15,6 +15,7 @@
 //   rtw_denoise.hip      the feature-guided denoiser: its checks, the launch sequence of its kernels (rtw_denoise.hpp) for one frame or a batch of frames, the device-resident entry points
 //   rtw_upsample.hip     the feature-guided upsampler: its checks, the launch sequence (the denoiser's prepare and level kernels at the small size, then rtw_upsample.hpp at the full size), the device-resident entry points
 //   rtw_temporal.hip     temporal reprojection: its checks, the host constants and the one launch of a step for one path or a batch of paths (rtw_temporal.hpp; clamped: rtw_temporal_clamp.hpp), the device-resident entry points
+//   rtw_motion.hip       the first-hit motion pass over moving spheres: its checks, the motion table, the one launch of its kernel (rtw_motion.hpp), the device-resident entry points
 //   rtw_present.hip      the present stage: its checks, the one launch of its kernel (rtw_present.hpp) for one frame or a batch, the device-resident entry points
 //   (rtw_scene_view.hpp: what both launch functions derive from their arguments; rtw_instances.hpp: the one table of the trace kernel's instances)
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
@@ -32,6 +33,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -354,10 +356,10 @@ int validate_temporal(const rtw_temporal_t *t, int32_t width, int32_t height, in
 // (rtw_history_moments_*), planes of rtw_history_moment_bytes bytes, d_moment_prev null exactly when d_state_prev is.  `c` non-null (accepted by
 // validate_temporal_clamp: every check of a clamp, none needs a device): the clamped step (rtw_clamped_step_*), still one launch.
 int validate_temporal_clamp(const rtw_temporal_clamp_t *c);
-int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t n_paths, const void *d_table, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr, const rtw_temporal_clamp_t *c = nullptr);
-int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t n_paths, const void *d_table, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr, const rtw_temporal_clamp_t *c = nullptr);
-inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f32 *c, const rtw_camera_f32 *cp, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp = nullptr, void *mn = nullptr, const rtw_temporal_clamp_t *cl = nullptr) { return launch_temporal_f32(t, c, cp, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, cl); }
-inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f64 *c, const rtw_camera_f64 *cp, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp = nullptr, void *mn = nullptr, const rtw_temporal_clamp_t *cl = nullptr) { return launch_temporal_f64(t, c, cp, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, cl); }
+int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t n_paths, const void *d_table, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr, const rtw_temporal_clamp_t *c = nullptr, const void *d_motion = nullptr);
+int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t n_paths, const void *d_table, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr, const rtw_temporal_clamp_t *c = nullptr, const void *d_motion = nullptr);
+inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f32 *c, const rtw_camera_f32 *cp, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp = nullptr, void *mn = nullptr, const rtw_temporal_clamp_t *cl = nullptr, const void *mv = nullptr) { return launch_temporal_f32(t, c, cp, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, cl, mv); }
+inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f64 *c, const rtw_camera_f64 *cp, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp = nullptr, void *mn = nullptr, const rtw_temporal_clamp_t *cl = nullptr, const void *mv = nullptr) { return launch_temporal_f64(t, c, cp, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, cl, mv); }
 // temporal_table_*: the camera constants of n paths into a HOST table, 32 elements per path (include/rtw_hip.h rtw_reproject_table_*; cams_prev null: first
 // frames) -- the one copy of that arithmetic, launch_temporal's own constants included.
 void temporal_table_f32(const rtw_camera_f32 *cams, const rtw_camera_f32 *cams_prev, int64_t n, float *table);
@@ -372,6 +374,16 @@ int launch_temporal_noise_f32(const rtw_temporal_noise_t *n, int32_t width, int3
 int launch_temporal_noise_f64(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int32_t n_paths, const void *d_state, const void *d_moment, void *d_noise, hipStream_t stream);
 inline int launch_temporal_noise_t(const rtw_temporal_noise_t *n, int32_t w, int32_t h, int32_t np, const void *st, const void *mo, float *noise, hipStream_t s) { return launch_temporal_noise_f32(n, w, h, np, st, mo, noise, s); }
 inline int launch_temporal_noise_t(const rtw_temporal_noise_t *n, int32_t w, int32_t h, int32_t np, const void *st, const void *mo, double *noise, hipStream_t s) { return launch_temporal_noise_f64(n, w, h, np, st, mo, noise, s); }
+
+// rtw_motion.hip -- the first-hit motion pass (include/rtw_hip.h rtw_first_hit_motion_*).  validate_motion: every check of a pass that needs
+// neither a device nor a pointer (of `p`: the frame, the device, the flag bits).  launch_motion: enqueue the pass (ONE launch, no record) on
+// `stream` of the scene's device, which must be current; d_table (scene->n rows of 4 elements, or null: m = 0) and d_motion (width*height
+// slots of 4 elements) are 16-byte aligned DEVICE pointers.
+int validate_motion(const rtw_params *p, int elem_bytes);
+int launch_motion_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const void *d_table, void *d_motion, hipStream_t stream);
+int launch_motion_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const void *d_table, void *d_motion, hipStream_t stream);
+inline int launch_motion_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, const void *tab, void *mo, hipStream_t st) { return launch_motion_f32(s, c, p, tab, mo, st); }
+inline int launch_motion_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, const void *tab, void *mo, hipStream_t st) { return launch_motion_f64(s, c, p, tab, mo, st); }
 
 // rtw_present.hip -- the present stage (include/rtw_hip.h rtw_present_*).  validate_present: every check of a call that needs neither a device
 // nor a pointer -- the parameters, the frame, n_views (0: one frame; a batch's count through batch_views) and the size of the launch.

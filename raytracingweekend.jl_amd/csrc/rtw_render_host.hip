@@ -81,9 +81,11 @@ int acquire_host(int device, const std::vector<unsigned char> &key, HostLease *o
     return 0;
 }
 
+// `keep` non-null (render_host_animation): the upload this one replaces may still be read by launches on the stream -- it is handed over, not freed
 template <typename T, typename SceneT>
-int ensure_scene(HostCtx *hc, const SceneT *scene, const std::vector<unsigned char> &key) {
+int ensure_scene(HostCtx *hc, const SceneT *scene, const std::vector<unsigned char> &key, std::vector<ScenePtr> *keep = nullptr) {
     if (hc->scene && hc->scene_key == key) return 0;
+    if (hc->scene && keep) { keep->emplace_back(hc->scene); hc->scene = nullptr; hc->scene_key.clear(); }
     if (hc->scene) { rtw_scene_free(hc->scene); hc->scene = nullptr; hc->scene_key.clear(); }
     if (int rc = upload_scene_t(scene, hc->device, &hc->scene)) return rc;
     hc->scene_key = key;
@@ -342,6 +344,39 @@ int render_host_features(const SceneT *scene, const CamT *cams, int32_t n_views,
     });
 }
 
+// The first-hit motion pass on host buffers (rtw_first_hit_motion_*): a leased context of the device with the scene uploaded (the cached one
+// when its bytes are the same) and a device buffer that holds the motion plane and, behind it, the motion table (`table`: scene->n rows of 4
+// elements, or null: m = 0 -- an id buffer); at most one H2D, ONE launch, ONE D2H.  The pass has no record: this thread's last render
+// (rtw_stats) is not touched.  (Not through render_one_device: that path resolves a record.)
+template <typename T, typename SceneT, typename CamT>
+int render_host_motion(const SceneT *scene, const CamT *cam, const rtw_params *p, const T *table, T *motion) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !cam || !motion) return fail(-1, "null argument");
+    if (int rc = validate_motion(p, (int)sizeof(T))) return rc;
+    if (scene->n < 0) return fail(-2, "negative sphere count");
+    if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
+    const size_t mo_b = (size_t)p->width * (size_t)p->height * 4 * sizeof(T), tab_b = (size_t)scene->n * 4 * sizeof(T);
+    if (table && ranges_overlap(motion, mo_b, table, tab_b)) return fail(-2, "motion may not alias the table");
+    DeviceGuard guard;
+    std::vector<unsigned char> key;
+    scene_key_of(scene, sizeof(T) == 8, key);
+    HostLease L;
+    if (int rc = acquire_host(p->device, key, &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_scene<T>(hc, scene, key)) return rc;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, mo_b + tab_b)) return rc;
+    rtw_params q = *p;
+    q.device = hc->device;
+    char *base = (char *)hc->d_img;
+    const bool up = table && tab_b;
+    int rc = 0;
+    if (up) if (hipError_t e = hipMemcpyAsync(base + mo_b, table, tab_b, hipMemcpyHostToDevice, hc->stream); e != hipSuccess) rc = fail((int)e, "upload of the motion table failed: %s", hipGetErrorString(e));
+    if (!rc) rc = launch_motion_t(hc->scene, cam, &q, up ? base + mo_b : nullptr, base, hc->stream);
+    if (!rc) rc = copy_out(hc, base, motion, mo_b);
+    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    return rc;
+}
+
 // The denoiser's regions inside a context's device buffer: image, features, output, workspace -- each starts on a 16-byte boundary and holds
 // the frames of a batch one behind the other.
 template <typename T> struct DenoiseRegions {
@@ -596,10 +631,12 @@ template <typename T> struct MomentRegions : TemporalRegions<T> {
 // filter_host's, two to four H2D, the step's launch (`c`: a clamped step) and, with `n`, the launch of the noise map of what it leaves, then
 // two to four D2H (the next state, its moments, the map; the image last).  The moment planes take part when either is given; moment_next
 // must then be.  `form_args`: what the entry point requires beyond that (n, moment_next and noise; or c) is there.  This thread's last
-// render (rtw_stats) is not touched.
+// render (rtw_stats) is not touched.  `animated` (rtw_animated_step_*): the step over a moving scene -- `motion`, the plane of
+// rtw_first_hit_motion_* (width*height slots of 4 elements), is there exactly when the previous state is and goes up behind the other inputs.
 template <typename T, typename CamT>
 int temporal_step_host(bool form_args, const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const CamT *cam, const CamT *cam_prev, int32_t width,
-                       int32_t height, const T *image, const T *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, T *out, T *noise) {
+                       int32_t height, const T *image, const T *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, T *out, T *noise,
+                       bool animated = false, const T *motion = nullptr) {
     const bool moments = moment_prev || moment_next;
     if (!form_args || !t || !cam || !image || !features || !state_next || !out || (moments && !moment_next)) return fail(-1, "null argument");
     if (int rc = validate_temporal(t, width, height, (int)sizeof(T))) return rc;
@@ -607,32 +644,35 @@ int temporal_step_host(bool form_args, const rtw_temporal_t *t, const rtw_tempor
     if (c) if (int rc = validate_temporal_clamp(c)) return rc;
     if ((cam_prev == nullptr) != (state_prev == nullptr)) return fail(-2, "cam_prev and state_prev must both be given or both be null (the first frame)");
     if (moments && (moment_prev == nullptr) != (state_prev == nullptr)) return fail(-2, "moment_prev and state_prev must both be given or both be null (the first frame)");
+    if (animated && (motion == nullptr) != (state_prev == nullptr)) return fail(-2, "motion and state_prev must both be given or both be null (the first frame)");
     const MomentRegions<T> R(width, height, 1, false);
+    const size_t motion_b = (size_t)width * (size_t)height * 4 * sizeof(T), off_motion = (R.total_m + 15) & ~(size_t)15;      // (behind every other region)
     // the outputs that are there against each other and against every input that is
-    const void *outs[4] = {out, state_next, moment_next, noise}, *ins[4] = {image, features, state_prev, moment_prev};
-    const size_t out_b[4] = {R.img_b, R.st_b, R.mo_b, R.noise_b}, in_b[4] = {R.img_b, R.feat_b, R.st_b, R.mo_b};
+    const void *outs[4] = {out, state_next, moment_next, noise}, *ins[5] = {image, features, state_prev, moment_prev, motion};
+    const size_t out_b[4] = {R.img_b, R.st_b, R.mo_b, R.noise_b}, in_b[5] = {R.img_b, R.feat_b, R.st_b, R.mo_b, motion_b};
     static const char *const names[4] = {"out", "state_next", "moment_next", "noise"};
     for (int a = 0; a < 4; ++a) {
         if (!outs[a]) continue;
         for (int b = a + 1; b < 4; ++b)
             if (outs[b] && ranges_overlap(outs[a], out_b[a], outs[b], out_b[b])) return fail(-2, "%s and %s may not alias each other", names[a], names[b]);
-        for (int b = 0; b < 4; ++b)
+        for (int b = 0; b < 5; ++b)
             if (ins[b] && ranges_overlap(outs[a], out_b[a], ins[b], in_b[b])) return fail(-2, "%s may not alias an input", names[a]);
     }
     DeviceGuard guard;
     HostLease L;
     if (int rc = acquire_host(t->device, std::vector<unsigned char>(), &L)) return rc;
     HostCtx *hc = L.hc;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total_m)) return rc;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, motion ? off_motion + motion_b : R.total_m)) return rc;
     char *base = (char *)hc->d_img;
     int rc = 0;
     hipError_t e = hipMemcpyAsync(base, image, R.img_b, hipMemcpyHostToDevice, hc->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_feat, features, R.feat_b, hipMemcpyHostToDevice, hc->stream);
     if (e == hipSuccess && state_prev) e = hipMemcpyAsync(base + R.off_st[0], state_prev, R.st_b, hipMemcpyHostToDevice, hc->stream);
     if (e == hipSuccess && moment_prev) e = hipMemcpyAsync(base + R.off_mo[0], moment_prev, R.mo_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess && motion) e = hipMemcpyAsync(base + off_motion, motion, motion_b, hipMemcpyHostToDevice, hc->stream);
     if (e != hipSuccess) rc = fail((int)e, "upload of the temporal step's inputs failed: %s", hipGetErrorString(e));
     if (!rc) rc = launch_temporal_t(t, cam, cam_prev, 0, nullptr, width, height, base, base + R.off_feat, state_prev ? base + R.off_st[0] : nullptr, base + R.off_st[1], base + R.off_acc, hc->stream,
-                                    moment_prev ? base + R.off_mo[0] : nullptr, moments ? base + R.off_mo[1] : nullptr, c);
+                                    moment_prev ? base + R.off_mo[0] : nullptr, moments ? base + R.off_mo[1] : nullptr, c, motion ? base + off_motion : nullptr);
     if (!rc && n) {
         rtw_temporal_noise_t nn = *n;
         nn.device = hc->device;
@@ -748,6 +788,105 @@ int render_host_sequence_clamped(const SceneT *scene, const CamT *cams, int32_t 
     if (!c) return fail(-1, "null temporal clamp parameters");
     if (n && !d) return fail(-2, "a noise map (n) guides the filter: d is required with it");
     return render_host_sequence<T>(scene, cams, n_views, seeds, p, t, n, d, out, c, n != nullptr);
+}
+
+inline int motion_table_t(const rtw_scene_f32 *prev, const rtw_scene_f32 *cur, float *tab) { return rtw_motion_table_f32(prev, cur, tab); }
+inline int motion_table_t(const rtw_scene_f64 *prev, const rtw_scene_f64 *cur, double *tab) { return rtw_motion_table_f64(prev, cur, tab); }
+
+// n_frames scenes and cameras with history reuse across the spheres' motion (rtw_render_animation_*): the sequence above for a scene that
+// changes from frame to frame, so what it batches over one scene runs per frame here, all on the leased context's stream: the frame's
+// scene uploaded (reused while its bytes are those of the frame before; an upload it replaces is kept until the stream has drained, since
+// the launches behind it may still read it), the render with gamma 0 and seeds[v] (null: p->seed), the feature pass over all chunks, from
+// frame 1 on the motion table against the frame before (host arithmetic into the context's pinned staging buffer, every frame's table at
+// its own offset, one H2D each) and the motion pass, then the step (two states ping-pong; `c`: clamped steps) -- 3 launches for frame 0, 4 for
+// every other.  The device buffer holds the sequence's regions, ONE motion plane and ONE table behind them (stream order lets every frame
+// reuse both).  With `d` ONE batched filter pass over all frames, then ONE D2H.  p->gamma is applied by the last stage that runs.
+// rtw_stats(): the counters of all frames' renders summed, the times of the slowest.
+// (Not through render_one_device: that path uploads one scene and resolves one record.)
+template <typename T, typename SceneT, typename CamT>
+int render_host_animation(const SceneT *scenes, const CamT *cams, int32_t n_frames, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t, const rtw_temporal_clamp_t *c,
+                          const rtw_denoise_t *d, T *out) {
+    if (!p) return fail(-1, "null params");
+    if (!scenes || !cams || !t || !out) return fail(-1, "null argument");
+    if (n_frames < 1) return fail(-2, "n_frames must be >= 1 (got %d)", n_frames);
+    int nch, cs;
+    if (int rc = validate_features_batch(cams, n_frames, p, 0, 1, out, &nch, &cs)) return rc;
+    if (d) if (int rc = validate_filter_batch(d, p->width, p->height, n_frames)) return rc;
+    if (int rc = validate_temporal(t, p->width, p->height, (int)sizeof(T))) return rc;
+    if (c) if (int rc = validate_temporal_clamp(c)) return rc;
+    rtw_params pm = *p;                                       // the motion pass reads the frame, the device and the numerics bits
+    pm.flags &= RTW_FLAG_GROUP_CULL | RTW_FLAG_SCAN_VALU | RTW_FLAG_NUMERICS_CONTRACT | RTW_FLAG_NUMERICS_REFERENCE_FMA2;
+    if (int rc = validate_motion(&pm, (int)sizeof(T))) return rc;
+    auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
+    size_t tab_max = 0, tab_sum = 0;
+    for (int v = 0; v < n_frames; ++v) {
+        if (scenes[v].n < 0) return fail(-2, "negative sphere count (frame %d)", v);
+        if (s_has_bad_scene(&scenes[v])) return fail(-1, "null scene array (frame %d)", v);
+        const size_t b = up((size_t)scenes[v].n * 4 * sizeof(T));
+        if (v) { tab_max = std::max(tab_max, b); tab_sum += b; }
+    }
+    DeviceGuard guard;
+    release_last();
+    const TemporalRegions<T> R(p->width, p->height, (size_t)n_frames, d != nullptr);
+    const size_t mo_b = (size_t)p->width * (size_t)p->height * 4 * sizeof(T), off_mo = up(R.total), off_tab = off_mo + mo_b, feat_frame_b = R.feat_b / (size_t)n_frames;
+    std::vector<unsigned char> key;
+    scene_key_of(&scenes[0], sizeof(T) == 8, key);
+    std::vector<ScenePtr> replaced;                           // (declared before the lease: the stream has drained when these are freed)
+    HostLease L;
+    if (int rc = acquire_host(p->device, key, &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, off_tab + tab_max)) return rc;
+    if (hc->stage_cap < tab_sum) {
+        if (hc->h_stage) { HIP_IGNORE(hipHostFree(hc->h_stage)); hc->h_stage = nullptr; hc->stage_cap = 0; }
+        HIP_TRY(hipHostMalloc(&hc->h_stage, tab_sum, hipHostMallocDefault));
+        hc->stage_cap = tab_sum;
+    }
+    char *base = (char *)hc->d_img;
+    rtw_params q = *p;
+    q.device = hc->device; q.n_devices = 0; q.device_ids = nullptr; q.gamma = 0;
+    pm.device = hc->device;
+    rtw_temporal_t tt = *t;
+    tt.gamma = d ? 0 : (p->gamma != 0); tt.device = hc->device;
+    std::vector<RenderRec *> recs((size_t)n_frames, nullptr), frecs((size_t)n_frames, nullptr);
+    std::vector<CtxPtr> rctx((size_t)n_frames), fctx((size_t)n_frames);
+    int rc = 0;
+    size_t stage_off = 0;
+    for (int v = 0; v < n_frames && !rc; ++v) {
+        const SceneT *scene = scenes + v;
+        if (v) scene_key_of(scene, sizeof(T) == 8, key);
+        if ((rc = ensure_scene<T>(hc, scene, key, &replaced))) break;
+        if (seeds) q.seed = seeds[v];
+        char *img = base + (size_t)v * R.frame_b, *feat = base + R.off_feat + (size_t)v * feat_frame_b;
+        rc = launch_render_t(hc->scene, cams + v, 0, nullptr, &q, img, hc->stream, &recs[v], &rctx[v]);
+        if (!rc) rc = launch_features_t(hc->scene, cams + v, 0, nullptr, &q, 0, nch, feat, hc->stream, &frecs[v], &fctx[v]);
+        if (!rc && v) {
+            const size_t tab_b = (size_t)scene->n * 4 * sizeof(T);
+            T *tab = (T *)((char *)hc->h_stage + stage_off);
+            stage_off += up(tab_b);
+            if (tab_b) {
+                rc = motion_table_t(scene - 1, scene, tab);
+                if (!rc) if (hipError_t e = hipMemcpyAsync(base + off_tab, tab, tab_b, hipMemcpyHostToDevice, hc->stream); e != hipSuccess)
+                    rc = fail((int)e, "upload of the motion table failed: %s", hipGetErrorString(e));
+            }
+            if (!rc) rc = launch_motion_t(hc->scene, cams + v, &pm, tab_b ? base + off_tab : nullptr, base + off_mo, hc->stream);
+        }
+        if (!rc) rc = launch_temporal_t(&tt, cams + v, v ? cams + (v - 1) : nullptr, 0, nullptr, p->width, p->height, img, feat, v ? base + R.off_st[(v & 1) ^ 1] : nullptr,
+                                        base + R.off_st[v & 1], base + R.off_acc + (size_t)v * R.frame_b, hc->stream, nullptr, nullptr, c, v ? base + off_mo : nullptr);
+    }
+    if (!rc && d) {
+        rtw_denoise_t dd = *d;
+        dd.gamma = p->gamma != 0; dd.device = hc->device;
+        rc = launch_denoise_t(&dd, p->width, p->height, n_frames, (const T *)(base + R.off_acc), base + R.off_feat, base + R.off_flt, base + R.off_work, hc->stream);
+    }
+    if (!rc) rc = copy_out(hc, base + (d ? R.off_flt : R.off_acc), out, R.img_b);
+    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends or an upload is freed
+    for (int v = 0; v < n_frames; ++v) {
+        if (recs[v]) { if (!rc) rc = resolve_rec(recs[v], &g_last.agg); release_rec(rctx[v], recs[v], rc == 0); }
+        if (frecs[v]) release_rec(fctx[v], frecs[v], true);     // (the stream has drained either way)
+    }
+    if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
+    g_last.resolved = rc == 0;
+    return rc;
 }
 
 // What an accumulator holds, denoised (rtw_accum_filtered_f32/_f64): the gamma-0 resolve (per tile for an adaptive accumulator), the feature
@@ -934,6 +1073,28 @@ int rtw_clamped_step_f32(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c,
 int rtw_clamped_step_f64(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
                              const double *image, const double *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, double *out) {
     return temporal_step_host<double>(c != nullptr, t, c, nullptr, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, nullptr);
+}
+int rtw_animated_step_f32(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height,
+                          const float *image, const float *features, const float *motion, const void *state_prev, void *state_next, const void *moment_prev, void *moment_next, float *out) {
+    return temporal_step_host<float>(true, t, c, nullptr, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, nullptr, true, motion);
+}
+int rtw_animated_step_f64(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
+                          const double *image, const double *features, const double *motion, const void *state_prev, void *state_next, const void *moment_prev, void *moment_next, double *out) {
+    return temporal_step_host<double>(true, t, c, nullptr, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, nullptr, true, motion);
+}
+int rtw_first_hit_motion_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const float *table, float *motion) {
+    return render_host_motion<float>(scene, cam, p, table, motion);
+}
+int rtw_first_hit_motion_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const double *table, double *motion) {
+    return render_host_motion<double>(scene, cam, p, table, motion);
+}
+int rtw_render_animation_f32(const rtw_scene_f32 *scenes, const rtw_camera_f32 *cams, int32_t n_frames, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
+                             const rtw_temporal_clamp_t *c, const rtw_denoise_t *d, float *out) {
+    return render_host_animation<float>(scenes, cams, n_frames, seeds, p, t, c, d, out);
+}
+int rtw_render_animation_f64(const rtw_scene_f64 *scenes, const rtw_camera_f64 *cams, int32_t n_frames, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
+                             const rtw_temporal_clamp_t *c, const rtw_denoise_t *d, double *out) {
+    return render_host_animation<double>(scenes, cams, n_frames, seeds, p, t, c, d, out);
 }
 int rtw_render_path_clamped_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                                  const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, float *out) {

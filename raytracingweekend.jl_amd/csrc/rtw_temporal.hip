@@ -1,7 +1,7 @@
 // rtw_temporal.hip -- temporal reprojection (include/rtw_hip.h rtw_temporal_*): the checks that need no device, the host constants of a step,
 // the one launch of its kernel (rtw_temporal.hpp), the step with moments and the noise map (rtw_history_moments_*, rtw_history_noise_device_*), the
 // clamped step (rtw_clamped_step_device_*: the checks of its clamp and the launch of its own kernel, rtw_temporal_clamp.hpp) and the
-// device-resident entry points; the batched forms of all three (rtw_reproject_*: n_paths paths in each launch, the table of their camera constants).
+// device-resident entry points, the step over a moving scene among them (rtw_animated_step_device_*: the MOTION instances, the plane of rtw_motion.hip); the batched forms of all three (rtw_reproject_*: n_paths paths in each launch, the table of their camera constants).
 // (The host-buffer entry points, rtw_temporal_*, rtw_history_moments_*, rtw_clamped_step_*, rtw_render_sequence_*, rtw_render_path_* and rtw_render_paths_*, live with the other
 // cached-context paths in rtw_render_host.hip.)
 #include "rtw_host.hpp"
@@ -90,11 +90,13 @@ static dim3 paths_grid(unsigned blocks, int32_t n_paths) {
 // d_moment_next non-null: the step with moments (rtw_history_moments_*), d_moment_prev null exactly when
 // d_state_prev is.  `c` non-null (validate_temporal_clamp has accepted it): the clamped step -- its own kernel (rtw_temporal_clamp.hpp), one workgroup per
 // tile, whenever there is a previous state; the first frame is the plain step's.
+// d_motion non-null (rtw_animated_step_device_*; one path, a previous state): the MOTION instance of whichever kernel runs.
 template <typename T, typename CamT>
 int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_prev, int32_t n_paths, const void *d_table, int32_t width, int32_t height, const void *d_image,
                     const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev, void *d_moment_next,
-                    const rtw_temporal_clamp_t *c) {
+                    const rtw_temporal_clamp_t *c, const void *d_motion) {
     using V = typename rtw::DnVec<T>::type;
+    if (d_motion && (n_paths || !d_state_prev)) return fail(-9, "internal: a motion plane goes with one path's step behind the first frame");
     const long long n_pix = (long long)width * height;
     rtw::TpParams<T> U;
     memset(&U, 0, sizeof U);
@@ -113,7 +115,10 @@ int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
     const char *sp = (const char *)d_state_prev;
     char *sn = (char *)d_state_next;
     const unsigned grid = (unsigned)((n_pix + 255) / 256);
-    const rtw::TpPaths<T, true> B = {(const T *)d_table, state_bytes(width, height, sizeof(T)), moment_bytes(width, height, sizeof(T)), (unsigned)n_paths};
+    rtw::TpTail<T, true, false> B;
+    B.table = (const T *)d_table; B.st_stride = state_bytes(width, height, sizeof(T)); B.mo_stride = moment_bytes(width, height, sizeof(T)); B.n_paths = (unsigned)n_paths;
+    rtw::TpTail<T, false, true> Q;
+    Q.plane = (const V *)d_motion;
     // (measurement aid, tools/gpu_temporal.py: events around the kernel, reported on stderr -- this one blocks)
     static const bool profile = aid_flag("RTW_TEMPORAL_PROFILE");
     struct Events { hipEvent_t e[2] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
@@ -134,8 +139,10 @@ int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
         auto go = [&](auto mo, auto gd) {
             if (n_paths) hipLaunchKernelGGL((rtw::tp_step_clamped<T, decltype(mo)::value, decltype(gd)::value, true>), paths_grid(tiles, n_paths), dim3(256), 0, stream, U, K, (const T *)d_image,
                                             (const V *)d_features, ep, gp, lp, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn, B);
+            else if (d_motion) hipLaunchKernelGGL((rtw::tp_step_clamped<T, decltype(mo)::value, decltype(gd)::value, false, true>), dim3(tiles), dim3(256), 0, stream, U, K, (const T *)d_image,
+                                                  (const V *)d_features, ep, gp, lp, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn, Q);
             else hipLaunchKernelGGL((rtw::tp_step_clamped<T, decltype(mo)::value, decltype(gd)::value, false>), dim3(tiles), dim3(256), 0, stream, U, K, (const T *)d_image,
-                                    (const V *)d_features, ep, gp, lp, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn, rtw::TpPaths<T, false>());
+                                    (const V *)d_features, ep, gp, lp, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn, rtw::TpTail<T, false, false>());
         };
         const bool gd = (c->flags & RTW_CLAMP_GUIDES) != 0;
         if (mn) { if (gd) go(std::true_type(), std::true_type()); else go(std::true_type(), std::false_type()); }
@@ -145,9 +152,15 @@ int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
             if (n_paths) hipLaunchKernelGGL((rtw::tp_step<T, decltype(hp)::value, decltype(mo)::value, true>), paths_grid(grid, n_paths), dim3(256), 0, stream, U, (const T *)d_image,
                                             (const V *)d_features, ep, gp, lp, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn, B);
             else hipLaunchKernelGGL((rtw::tp_step<T, decltype(hp)::value, decltype(mo)::value, false>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, ep,
-                                    gp, lp, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn, rtw::TpPaths<T, false>());
+                                    gp, lp, (V *)sn, (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn, rtw::TpTail<T, false, false>());
         };
-        if (mn) { if (sp) go(std::true_type(), std::true_type()); else go(std::false_type(), std::true_type()); }
+        // (the plain step over a moving scene: the two HAS_PREV instances with the motion plane)
+        auto gom = [&](auto mo) {
+            hipLaunchKernelGGL((rtw::tp_step<T, true, decltype(mo)::value, false, true>), dim3(grid), dim3(256), 0, stream, U, (const T *)d_image, (const V *)d_features, ep, gp, lp, (V *)sn,
+                               (V *)(sn + pb), (T *)(sn + 2 * pb), (T *)d_out, mp, mn, Q);
+        };
+        if (d_motion) { if (mn) gom(std::true_type()); else gom(std::false_type()); }
+        else if (mn) { if (sp) go(std::true_type(), std::true_type()); else go(std::false_type(), std::true_type()); }
         else { if (sp) go(std::true_type(), std::false_type()); else go(std::false_type(), std::false_type()); }
     }
     HIP_TRY(hipGetLastError());
@@ -156,14 +169,14 @@ int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
         HIP_TRY(hipEventRecord(events.e[1], stream));
         HIP_TRY(hipEventSynchronize(events.e[1]));
         HIP_TRY(hipEventElapsedTime(&ms, events.e[0], events.e[1]));
-        if (c && sp) fprintf(stderr, "[rtw temporal] %s %dx%d %s r=%d guides=%d paths=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, mn ? "clamped+moments" : "clamped", c->radius, c->flags & RTW_CLAMP_GUIDES, n_paths, ms);
-        else fprintf(stderr, "[rtw temporal] %s %dx%d %s prev=%d paths=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, mn ? "step+moments" : "step", sp ? 1 : 0, n_paths, ms);
+        if (c && sp) fprintf(stderr, "[rtw temporal] %s %dx%d %s r=%d guides=%d paths=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, d_motion ? (mn ? "clamped+moments+motion" : "clamped+motion") : mn ? "clamped+moments" : "clamped", c->radius, c->flags & RTW_CLAMP_GUIDES, n_paths, ms);
+        else fprintf(stderr, "[rtw temporal] %s %dx%d %s prev=%d paths=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, d_motion ? (mn ? "step+moments+motion" : "step+motion") : mn ? "step+moments" : "step", sp ? 1 : 0, n_paths, ms);
     }
     return 0;
 }
 
-int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn, const rtw_temporal_clamp_t *c) { return launch_temporal<float>(t, cam, cam_prev, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, c); }
-int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn, const rtw_temporal_clamp_t *c) { return launch_temporal<double>(t, cam, cam_prev, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, c); }
+int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn, const rtw_temporal_clamp_t *c, const void *mv) { return launch_temporal<float>(t, cam, cam_prev, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, c, mv); }
+int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn, const rtw_temporal_clamp_t *c, const void *mv) { return launch_temporal<double>(t, cam, cam_prev, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, c, mv); }
 void temporal_table_f32(const rtw_camera_f32 *cams, const rtw_camera_f32 *cams_prev, int64_t n, float *table) { for (int64_t s = 0; s < n; ++s) temporal_table_entry<float>(cams + s, cams_prev ? cams_prev + s : nullptr, table + 32 * s); }
 void temporal_table_f64(const rtw_camera_f64 *cams, const rtw_camera_f64 *cams_prev, int64_t n, double *table) { for (int64_t s = 0; s < n; ++s) temporal_table_entry<double>(cams + s, cams_prev ? cams_prev + s : nullptr, table + 32 * s); }
 
@@ -207,17 +220,20 @@ int launch_temporal_noise_f64(const rtw_temporal_noise_t *n, int32_t w, int32_t 
 
 // The device-resident entry points of a step: nulls, the parameters, then the pointers' alignment and aliasing.  `moments`:
 // rtw_history_moments_device_*, the same with the two moment planes (d_moment_prev null exactly when d_state_prev is).  `clamped`:
-// rtw_clamped_step_device_*, either of the two with the clamp `c`.
+// rtw_clamped_step_device_*, either of the two with the clamp `c`.  `animated`: rtw_animated_step_device_*, any of the three over a moving
+// scene -- the motion plane d_motion is there exactly when the previous state is.
 template <typename T, typename CamT>
 int temporal_device(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev,
                     void *d_state_next, void *d_out, void *stream_v, bool moments = false, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr, bool clamped = false,
-                    const rtw_temporal_clamp_t *c = nullptr) {
+                    const rtw_temporal_clamp_t *c = nullptr, bool animated = false, const void *d_motion = nullptr) {
     if (!t || !cam || !d_image || !d_features || !d_state_next || !d_out || (moments && !d_moment_next) || (clamped && !c)) return fail(-1, "null argument");
     if (int rc = validate_temporal(t, width, height, (int)sizeof(T))) return rc;
     if (clamped) if (int rc = validate_temporal_clamp(c)) return rc;
     if ((cam_prev == nullptr) != (d_state_prev == nullptr)) return fail(-2, "cam_prev and d_state_prev must both be given or both be null (the first frame)");
     if (moments && (d_moment_prev == nullptr) != (d_state_prev == nullptr)) return fail(-2, "d_moment_prev and d_state_prev must both be given or both be null (the first frame)");
     if (moments && (((uintptr_t)d_moment_prev & 15u) || ((uintptr_t)d_moment_next & 15u))) return fail(-2, "both moment planes must be 16-byte aligned");
+    if (animated && (d_motion == nullptr) != (d_state_prev == nullptr)) return fail(-2, "d_motion and d_state_prev must both be given or both be null (the first frame)");
+    if ((uintptr_t)d_motion & 15u) return fail(-2, "the motion plane must be 16-byte aligned");
     if (((uintptr_t)d_features & 15u) || ((uintptr_t)d_state_prev & 15u) || ((uintptr_t)d_state_next & 15u)) return fail(-2, "the feature buffer and both states must be 16-byte aligned");
     if (((uintptr_t)d_image & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
     const size_t n_pix = (size_t)width * (size_t)height;
@@ -236,10 +252,16 @@ int temporal_device(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
         if (d_moment_prev && (ranges_overlap(d_moment_prev, mo_b, d_out, img_b) || ranges_overlap(d_moment_prev, mo_b, d_state_next, st_b)))
             return fail(-2, "d_moment_prev may not alias an output");
     }
+    if (d_motion) {
+        const size_t mv_b = n_pix * 4 * sizeof(T);
+        if (ranges_overlap(d_motion, mv_b, d_out, img_b) || ranges_overlap(d_motion, mv_b, d_state_next, st_b) ||
+            (moments && ranges_overlap(d_motion, mv_b, d_moment_next, (size_t)moment_bytes(width, height, sizeof(T)))))
+            return fail(-2, "d_motion may not alias an output");
+    }
     DeviceGuard guard;
     if (t->device >= 0) HIP_TRY(hipSetDevice(t->device));
     return launch_temporal<T>(t, cam, cam_prev, 0, nullptr, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, (hipStream_t)stream_v, moments ? d_moment_prev : nullptr,
-                              moments ? d_moment_next : nullptr, clamped ? c : nullptr);
+                              moments ? d_moment_next : nullptr, clamped ? c : nullptr, d_motion);
 }
 
 // the batch's own size rule: the batched filter's frame rule on (width, height, number of frames)
@@ -281,7 +303,7 @@ int temporal_batch_device(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c
     if (t->device >= 0) HIP_TRY(hipSetDevice(t->device));
     using CamT = std::conditional_t<sizeof(T) == 8, rtw_camera_f64, rtw_camera_f32>;
     return launch_temporal<T, CamT>(t, nullptr, nullptr, n_paths, d_table, width, height, d_images, d_features, d_states_prev, d_states_next, d_out, (hipStream_t)stream_v,
-                                              d_moments_prev, d_moments_next, c);
+                                              d_moments_prev, d_moments_next, c, nullptr);
 }
 
 // ... and of the batched noise map (rtw_reproject_noise_batch_device_*)
@@ -359,6 +381,18 @@ int rtw_clamped_step_device_f64(const rtw_temporal_t *t, const rtw_temporal_clam
                                     void *hip_stream) {
     return temporal_device<double>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, hip_stream, d_moment_prev || d_moment_next, d_moment_prev,
                                    d_moment_next, true, c);
+}
+int rtw_animated_step_device_f32(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height,
+                                 const void *d_image, const void *d_features, const void *d_motion, const void *d_state_prev, void *d_state_next, const void *d_moment_prev,
+                                 void *d_moment_next, void *d_out, void *hip_stream) {
+    return temporal_device<float>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, hip_stream, d_moment_prev || d_moment_next, d_moment_prev,
+                                  d_moment_next, c != nullptr, c, true, d_motion);
+}
+int rtw_animated_step_device_f64(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
+                                 const void *d_image, const void *d_features, const void *d_motion, const void *d_state_prev, void *d_state_next, const void *d_moment_prev,
+                                 void *d_moment_next, void *d_out, void *hip_stream) {
+    return temporal_device<double>(t, cam, cam_prev, width, height, d_image, d_features, d_state_prev, d_state_next, d_out, hip_stream, d_moment_prev || d_moment_next, d_moment_prev,
+                                   d_moment_next, c != nullptr, c, true, d_motion);
 }
 int rtw_history_noise_device_f32(const rtw_temporal_noise_t *n, int32_t width, int32_t height, const void *d_state, const void *d_moment, void *d_noise, void *hip_stream) {
     return temporal_noise_device<float>(n, width, height, d_state, d_moment, d_noise, hip_stream);

@@ -15,6 +15,10 @@
 //                  slot, one element of M (Lm_q comes from the E slot) -- two 16-byte slots and one element per tap; len is the centre's alone.
 //   PATHS          true (rtw_reproject_*_batch_device_*): n_paths paths in one launch, TpPaths below; false: the instance is the single form's,
 //                  instruction for instruction (the flag only adds code under `if constexpr`).
+//   MOTION         true (rtw_animated_step_device_*, HAS_PREV instances only, never with PATHS): the scene moved between the two frames -- the
+//                  pixel's slot of the motion plane (rtw_first_hit_motion_device_*: (m.x, m.y, m.z, id), one 16- or 32-byte load) is
+//                  subtracted from its world point before the previous origin is; false: the instance is the static step's, instruction
+//                  for instruction.
 // No LDS, no atomics, no cross-lane operation; the trip count over the 4 taps is uniform, skipped taps are dropped by selects, as in dn_tap.
 // (tp_noise: lanes with a long history skip the window by a branch of their own; the window's trip count is the radius', uniform.)
 // Every operation is rounded once (the Makefile's -ffp-contract=off -fno-fast-math); divisions and sqrt are the compiler's IEEE ones.
@@ -86,16 +90,21 @@ template <typename T> struct TpPaths<T, true> {
     long long st_stride, mo_stride;     // BYTES from one path's state / moment plane to the next (rtw_temporal_state_bytes, rtw_history_moment_bytes)
     unsigned n_paths;
 };
+// The trailing argument of the two step kernels: TpPaths and, MOTION = true (one path only), the motion plane behind it, pixel P at slot P.
+// MOTION = false adds nothing: the argument has TpPaths' own bytes, so the kernel arguments of those instances lie where they always did.
+template <typename T, bool PATHS, bool MOTION> struct TpTail : TpPaths<T, PATHS> {};
+template <typename T> struct TpTail<T, false, true> : TpPaths<T, false> { const typename DnVec<T>::type *plane; };
 template <typename T> __device__ __forceinline__ const T *tp_adv(const T *p, long long bytes) { return (const T *)((const char *)p + bytes); }
 template <typename T> __device__ __forceinline__ T *tp_adv(T *p, long long bytes) { return (T *)((char *)p + bytes); }
 
 // lane = flat pixel P = j*H + i
-template <typename T, bool HAS_PREV, bool MOMENTS = false, bool PATHS = false>
+template <typename T, bool HAS_PREV, bool MOMENTS = false, bool PATHS = false, bool MOTION = false>
 __global__ __launch_bounds__(256) void tp_step(TpParams<T> U, const T *__restrict__ image, const typename DnVec<T>::type *__restrict__ feat,
                                                const typename DnVec<T>::type *__restrict__ Ep, const typename DnVec<T>::type *__restrict__ Gp, const T *__restrict__ Lp,
                                                typename DnVec<T>::type *__restrict__ En, typename DnVec<T>::type *__restrict__ Gn, T *__restrict__ Ln, T *__restrict__ out,
-                                               const T *__restrict__ Mp, T *__restrict__ Mn, [[maybe_unused]] TpPaths<T, PATHS> B) {
+                                               const T *__restrict__ Mp, T *__restrict__ Mn, [[maybe_unused]] TpTail<T, PATHS, MOTION> B) {
     using V = typename DnVec<T>::type;
+    static_assert(!MOTION || (HAS_PREV && !PATHS), "the motion plane belongs to a single path's step behind the first frame");
     if constexpr (PATHS) {
         const long long s = (long long)blockIdx.z * gridDim.y + blockIdx.y;
         if (s >= B.n_paths) return;
@@ -154,9 +163,18 @@ __global__ __launch_bounds__(256) void tp_step(TpParams<T> U, const T *__restric
         const T sl = dn_sqrt((D0 * D0 + D1 * D1) + D2 * D2);
         const T n0 = D0 / sl, n1 = D1 / sl, n2 = D2 / sl;
         // ---- the point to reproject (a sky pixel: the point at infinity), relative to the previous origin
-        const T d0 = has ? (U.o[0] + z * n0) - U.po[0] : n0;
-        const T d1 = has ? (U.o[1] + z * n1) - U.po[1] : n1;
-        const T d2 = has ? (U.o[2] + z * n2) - U.po[2] : n2;
+        T d0, d1, d2;
+        if constexpr (MOTION) {
+            // where the surface was one frame ago: d = ((origin + z*nD) - m) - origin_prev (a non-finite m: d is NaN, inr fails, the pixel resets)
+            const V mv = B.plane[P];
+            d0 = has ? ((U.o[0] + z * n0) - mv.x) - U.po[0] : n0;
+            d1 = has ? ((U.o[1] + z * n1) - mv.y) - U.po[1] : n1;
+            d2 = has ? ((U.o[2] + z * n2) - mv.z) - U.po[2] : n2;
+        } else {
+            d0 = has ? (U.o[0] + z * n0) - U.po[0] : n0;
+            d1 = has ? (U.o[1] + z * n1) - U.po[1] : n1;
+            d2 = has ? (U.o[2] + z * n2) - U.po[2] : n2;
+        }
         // ---- projection into the previous camera
         const T dw = tp_dot<T>(d0, d1, d2, U.pw);
         const bool front = dw < T(0);

@@ -32,12 +32,14 @@ template <typename T> struct TpClampParams {
 // block = tile (tile column tJ, tile row tI) = blockIdx.x / tiles_i, blockIdx.x % tiles_i; lane = (tj, ti) = threadIdx.x / 32, threadIdx.x % 32
 // PATHS (rtw_temporal.hpp TpPaths): blockIdx.x numbers the tiles of ONE path; the path comes from blockIdx.y / .z, so a whole workgroup leaves
 // together before the barrier when its path index is past the last one.
-template <typename T, bool MOMENTS, bool GUIDES, bool PATHS = false>
+// MOTION (rtw_temporal.hpp TpTail; never with PATHS): the pixel's slot of the motion plane is subtracted from its world point, as in tp_step.
+template <typename T, bool MOMENTS, bool GUIDES, bool PATHS = false, bool MOTION = false>
 __global__ __launch_bounds__(256) void tp_step_clamped(TpParams<T> U, TpClampParams<T> C, const T *__restrict__ image, const typename DnVec<T>::type *__restrict__ feat,
                                                        const typename DnVec<T>::type *__restrict__ Ep, const typename DnVec<T>::type *__restrict__ Gp, const T *__restrict__ Lp,
                                                        typename DnVec<T>::type *__restrict__ En, typename DnVec<T>::type *__restrict__ Gn, T *__restrict__ Ln, T *__restrict__ out,
-                                                       const T *__restrict__ Mp, T *__restrict__ Mn, [[maybe_unused]] TpPaths<T, PATHS> B) {
+                                                       const T *__restrict__ Mp, T *__restrict__ Mn, [[maybe_unused]] TpTail<T, PATHS, MOTION> B) {
     using V = typename DnVec<T>::type;
+    static_assert(!(MOTION && PATHS), "the motion plane belongs to a single path's step");
     __shared__ V sE[TP_SLOTS], sG[TP_SLOTS];
     if constexpr (PATHS) {
         const long long s = (long long)blockIdx.z * gridDim.y + blockIdx.y;
@@ -139,9 +141,18 @@ __global__ __launch_bounds__(256) void tp_step_clamped(TpParams<T> U, TpClampPar
     const T D2 = ((U.llc[2] + su * U.hor[2]) + tv * U.ver[2]) - U.o[2];
     const T sl = dn_sqrt((D0 * D0 + D1 * D1) + D2 * D2);
     const T n0 = D0 / sl, n1 = D1 / sl, n2 = D2 / sl;
-    const T d0 = has ? (U.o[0] + z * n0) - U.po[0] : n0;
-    const T d1 = has ? (U.o[1] + z * n1) - U.po[1] : n1;
-    const T d2 = has ? (U.o[2] + z * n2) - U.po[2] : n2;
+    T d0, d1, d2;
+    if constexpr (MOTION) {
+        // where the surface was one frame ago: d = ((origin + z*nD) - m) - origin_prev (a non-finite m: d is NaN, inr fails, the pixel resets)
+        const V mv = B.plane[P];
+        d0 = has ? ((U.o[0] + z * n0) - mv.x) - U.po[0] : n0;
+        d1 = has ? ((U.o[1] + z * n1) - mv.y) - U.po[1] : n1;
+        d2 = has ? ((U.o[2] + z * n2) - mv.z) - U.po[2] : n2;
+    } else {
+        d0 = has ? (U.o[0] + z * n0) - U.po[0] : n0;
+        d1 = has ? (U.o[1] + z * n1) - U.po[1] : n1;
+        d2 = has ? (U.o[2] + z * n2) - U.po[2] : n2;
+    }
     const T dw = tp_dot<T>(d0, d1, d2, U.pw);
     const bool front = dw < T(0);
     const T lam = U.Kw / dw;

@@ -25,6 +25,13 @@ Batched steps (``rtw_reproject_*``, ``rtw_render_paths_*``): several independent
 cameras) advance in EACH launch -- no new arithmetic, path s is the single call of path s on the bits; the per-path camera constants travel
 in a device table (``temporal_path_table``, ``temporal_step_batch_into``, ``temporal_noise_batch_into``, ``TemporalBatchAccumulator``,
 ``render_sequences``; witness: tests/paths_ref.py, the single witnesses side by side; what it saves: DESIGN.md section 7.22).
+
+Moving spheres (``rtw_motion_table_*``, ``rtw_first_hit_motion_*``, ``rtw_animated_step_*``): the steps above treat the world as static.  The
+motion pass says per pixel which sphere its centre ray sees and how far that sphere moved since the previous frame (``motion_table``,
+``first_hit_motion``, ``first_hit_motion_into``); the animated step subtracts that displacement from the pixel's world point before it
+projects into the previous view (``temporal_step_animated``, ``temporal_step_animated_into``, ``TemporalAccumulator.step(...,
+d_motion_ptr=...)``), and ``render_animation`` (``rtw_render_animation_*``) runs a list of scenes and cameras in one call.  With zero motion the step is
+the static one on the bits.  Witness: tests/motion_ref.py; DESIGN.md section 7.23.
 """
 import ctypes as C
 
@@ -61,11 +68,13 @@ def _camera_arg(cam, T, what):
     return _capi.make_camera(cam, T)
 
 
-def _host_step(name, image, features, cam, state, moment, cam_prev, params, *, check, head=None, planes=True, moments=False, noise_map=False):
+def _host_step(name, image, features, cam, state, moment, cam_prev, params, *, check, head=None, planes=True, moments=False, noise_map=False, motion=False):
     """One step on host arrays through the entry point ``name``: the checks of the arrays, then ``check()`` (the caller's own rule about its
     arguments; it raises), the state's and -- with ``moments`` -- the moment's, the library's layout,
-    ``make_temporal(**params)`` and the struct ``head()`` makes behind it, the call.  ``planes``: the entry point takes the two moment
-    planes (null without ``moments``); ``noise_map``: and the map.  -> ``(out [H, W, 3], next_state, next_moment or None, map [H, W] or None)``."""
+    ``make_temporal(**params)`` and the struct ``head()`` makes behind it (``head`` returning None: a null pointer in its place), the call.
+    ``planes``: the entry point takes the two moment planes (null without ``moments``); ``noise_map``: and the map.  ``motion`` other than
+    False: rtw_animated_step_*'s argument order -- the motion plane [H, W, 4] (None on the first frame) behind the features, each moment
+    plane behind its state.  -> ``(out [H, W, 3], next_state, next_moment or None, map [H, W] or None)``."""
     if isinstance(features, dict):
         features = features["raw"]
     image, features = np.asarray(image), np.asarray(features)
@@ -91,13 +100,23 @@ def _host_step(name, image, features, cam, state, moment, cam_prev, params, *, c
             if moment.dtype != T or moment.shape != (n_mom,):
                 raise ValueError(f"moment must be a flat {T.name} array of {n_mom} elements, got {moment.dtype.name} {moment.shape}")
         Cp = C.byref(_camera_arg(cam_prev, T.type, "cam_prev"))
-    heads = [C.byref(make_temporal(**params))] + ([C.byref(head())] if head else [])
+    hd = head() if head else None
+    heads = [C.byref(make_temporal(**params))] + ([C.byref(hd) if hd is not None else None] if head else [])
     img = np.ascontiguousarray(np.swapaxes(image, 0, 1))             # the library's layout: pixel (i, j) at j*H + i
     feat = np.ascontiguousarray(np.swapaxes(features, 0, 1))
     out, nxt = np.empty((W, H, 3), dtype=T), np.zeros(n_state, dtype=T)
     mom = np.zeros(n_mom, dtype=T) if moments else None
     rho = np.empty((W, H), dtype=T) if noise_map else None
-    arrays = [img, feat, state] + ([moment if moments else None] if planes else []) + [nxt] + ([mom] if planes else []) + [out] + ([rho] if noise_map else [])
+    if motion is not False:
+        mv = None
+        if motion is not None:
+            mv = np.asarray(motion)
+            if mv.dtype != T or mv.shape != (H, W, 4):
+                raise ValueError(f"motion must be a {T.name} array [H, W, 4] = {(H, W, 4)}, got {mv.dtype.name} {mv.shape}")
+            mv = np.ascontiguousarray(np.swapaxes(mv, 0, 1))
+        arrays = [img, feat, mv, state, nxt, moment if moments else None, mom, out]
+    else:
+        arrays = [img, feat, state] + ([moment if moments else None] if planes else []) + [nxt] + ([mom] if planes else []) + [out] + ([rho] if noise_map else [])
     fn = getattr(_capi.lib(), name + ("f64" if _capi.is_f64(T) else "f32"))
     _capi.check(fn(*heads, C.byref(Cm), Cp, W, H, *(a.ctypes.data_as(C.c_void_p) if a is not None else None for a in arrays)))
     return np.swapaxes(out, 0, 1), nxt, mom, np.swapaxes(rho, 0, 1) if noise_map else None
@@ -261,6 +280,149 @@ def temporal_step_clamped_into(d_out_ptr, d_state_next_ptr, d_image_ptr, d_featu
                   d_moment_prev_ptr, d_state_next_ptr, d_moment_next_ptr, d_out_ptr)
 
 
+# ---- moving spheres: the motion table, the first-hit motion pass and the animated step (include/rtw_hip.h rtw_first_hit_motion_*) ----
+
+def _flat_scene(scene, T):
+    from .structs import flatten_scene
+    return scene if isinstance(scene, dict) else flatten_scene(scene, T)
+
+
+def motion_table(scene_prev, scene, elem_type=np.float32):
+    """The motion table of a frame (rtw_motion_table_*, host code): -> an array ``(n, 4)`` of ``elem_type``, row k = ``(dx, dy, dz, 0)`` of
+    sphere k of ``scene`` since ``scene_prev`` -- one subtraction per component; three NaNs for a sphere that is new (``k >= n_prev``) or
+    whose radius changed, so that its pixels reset.  Scenes: HittableLists or the flat dicts of ``flatten_scene``, in the same order."""
+    T = np.dtype(elem_type).type
+    Sp, keep_p = _capi.make_scene(_flat_scene(scene_prev, T), T)
+    Sc, keep_c = _capi.make_scene(_flat_scene(scene, T), T)
+    table = np.zeros((int(Sc.n), 4), dtype=T)
+    fn = getattr(_capi.lib(), "rtw_motion_table_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(C.byref(Sp), C.byref(Sc), table.ctypes.data_as(C.c_void_p)))
+    del keep_p, keep_c
+    return table
+
+
+def _motion_params(image_width, image_height, device, numerics, group_cull, scan_valu):
+    from .structs import image_height as _ih
+    H = int(image_height) if image_height is not None else _ih(image_width)
+    if int(image_width) < 1 or H < 1:
+        raise ValueError(f"empty frame {image_width} x {H}")
+    flags = (_capi.FLAG_GROUP_CULL if group_cull else 0) | (_capi.FLAG_SCAN_VALU if scan_valu else 0)
+    # (spp, depth, seed and chunks are not read by the pass: the render's defaults keep the struct valid)
+    return H, _capi.make_params(int(image_width), H, 1, 16, 1, 0, 0, 1, int(device), 1, flags, numerics=numerics)
+
+
+def first_hit_motion(scene, cam, image_width=400, image_height=None, *, table=None, device=-1, numerics=None, group_cull=False, scan_valu=False):
+    """The first-hit motion pass on host arrays (rtw_first_hit_motion_*): -> ``[H, W, 4]``, per pixel ``(m.x, m.y, m.z, id)`` -- the row of
+    ``table`` (``motion_table``; None: zeros, an id / picking buffer) of the sphere the pixel's centre ray sees first, and that sphere's
+    index in the scene's order as a float (-1: the sky).  The ray is the temporal step's own (no lens, no jitter); among equal hits the
+    lower index wins.  ``image_height`` None: the package's 16:9 height.  ``group_cull`` / ``scan_valu`` are accepted and change nothing.
+    Blocking; ``last_stats()`` is left as it was."""
+    if not isinstance(cam, Camera):
+        raise TypeError("cam must be a Camera")
+    T = np.dtype(cam.elem_type).type
+    H, P = _motion_params(image_width, image_height, device, numerics, group_cull, scan_valu)
+    S, keep = _capi.make_scene(_flat_scene(scene, T), T)
+    tab = None
+    if table is not None:
+        tab = np.ascontiguousarray(table)
+        if tab.dtype != T or tab.shape != (int(S.n), 4):
+            raise ValueError(f"table must be a {np.dtype(T).name} array {(int(S.n), 4)}, got {tab.dtype.name} {tab.shape}")
+    out = np.empty((int(image_width), H, 4), dtype=T)
+    fn = getattr(_capi.lib(), "rtw_first_hit_motion_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(C.byref(S), C.byref(_capi.make_camera(cam, T)), C.byref(P), tab.ctypes.data_as(C.c_void_p) if tab is not None else None, out.ctypes.data_as(C.c_void_p)))
+    del keep
+    return np.swapaxes(out, 0, 1)
+
+
+def first_hit_motion_into(renderer, d_motion_ptr, image_width, image_height=None, *, cam=None, d_table_ptr=None, stream=0, numerics=None, group_cull=False,
+                          scan_valu=False):
+    """The device-resident form (rtw_first_hit_motion_device_*): enqueue the pass of ``renderer``'s scene (a ``DeviceRenderer``) through
+    ``cam`` (None: the renderer's camera) on ``stream``.  ``d_motion_ptr``: H*W*4 elements, pixel (i, j) at slot ``j*H + i``;
+    ``d_table_ptr``: the uploaded ``motion_table`` (None: m = 0); both DEVICE pointers, 16-byte aligned.  Returns H."""
+    T = np.dtype(renderer.T).type
+    H, P = _motion_params(image_width, image_height, -1, numerics, group_cull, scan_valu)
+    Cm = renderer.cam if cam is None else _camera_arg(cam, T, "cam")
+    fn = getattr(renderer.L, "rtw_first_hit_motion_device_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(renderer.handle, C.byref(Cm), C.byref(P), C.c_void_p(int(d_table_ptr)) if d_table_ptr is not None else None, C.c_void_p(int(d_motion_ptr)),
+                   C.c_void_p(int(stream))))
+    return H
+
+
+def temporal_step_animated(image, features, cam, motion=None, state=None, moment=None, cam_prev=None, *, clamp=None, moments=None, **params):
+    """One step over a moving scene on host arrays (rtw_animated_step_*): ``temporal_step`` -- with ``moments`` the step with moments, with
+    ``clamp`` (True, or a dict of ``make_temporal_clamp``'s keywords) the clamped one -- whose world points are moved back by ``motion``, the
+    ``[H, W, 4]`` plane of ``first_hit_motion`` for this frame.  ``motion``, ``state``, ``cam_prev`` (and with moments ``moment``) are None
+    together: the first frame.  -> ``(out [H, W, 3], next_state)`` or, with moments, ``(out, next_state, next_moment)``.  With a plane of
+    zeros the result is the static step's on the bits.  Other keywords: ``make_temporal``.  Blocking."""
+    if moments is None:
+        moments = moment is not None
+    def check():
+        if not ((state is None) == (cam_prev is None) == (motion is None)) or (moment is not None and (not moments or state is None)) or \
+                (moments and state is not None and moment is None):
+            raise ValueError("motion, state, cam_prev and (with moments) moment must all be given or all be None (the first frame)")
+    res = _host_step("rtw_animated_step_", image, features, cam, state, moment, cam_prev, params, check=check,
+                     head=lambda: make_temporal_clamp(**_clamp_arg(clamp)) if clamp else None, moments=moments, motion=motion)
+    return res[:3] if moments else res[:2]
+
+
+def temporal_step_animated_into(d_out_ptr, d_state_next_ptr, d_image_ptr, d_features_ptr, cam, image_width, image_height, *, d_motion_ptr=None, clamp=None,
+                                d_state_prev_ptr=None, d_moment_prev_ptr=None, d_moment_next_ptr=None, cam_prev=None, elem_type=np.float32, stream=0, **params):
+    """The device-resident step over a moving scene (rtw_animated_step_device_*): ``temporal_step_into`` / ``temporal_step_moments_into`` /
+    ``temporal_step_clamped_into`` (by ``clamp`` and the moment pointers) with the motion plane ``d_motion_ptr`` -- H*W*4 elements, 16-byte
+    aligned, what ``first_hit_motion_into`` wrote for this frame.  ``d_motion_ptr``, ``d_state_prev_ptr``, ``cam_prev`` (and with moments
+    ``d_moment_prev_ptr``) all None: the first frame.  One launch.  Other keywords: ``make_temporal``."""
+    if not ((d_state_prev_ptr is None) == (cam_prev is None) == (d_motion_ptr is None)) or (d_moment_prev_ptr is not None and (d_moment_next_ptr is None or d_state_prev_ptr is None)) or \
+            (d_moment_next_ptr is not None and d_state_prev_ptr is not None and d_moment_prev_ptr is None):
+        raise ValueError("d_motion_ptr, d_state_prev_ptr, cam_prev and (with moments) d_moment_prev_ptr must all be given or all be None (the first frame)")
+    T = np.dtype(elem_type).type
+    K = make_temporal_clamp(**_clamp_arg(clamp)) if clamp else None
+    Cm = _camera_arg(cam, T, "cam")
+    ptrs = (d_image_ptr, d_features_ptr, d_motion_ptr, d_state_prev_ptr, d_state_next_ptr, d_moment_prev_ptr, d_moment_next_ptr, d_out_ptr)
+    fn = getattr(_capi.lib(), "rtw_animated_step_device_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(C.byref(make_temporal(**params)), C.byref(K) if K is not None else None, C.byref(Cm),
+                   C.byref(_camera_arg(cam_prev, T, "cam_prev")) if cam_prev is not None else None, int(image_width), int(image_height),
+                   *(C.c_void_p(int(q)) if q is not None else None for q in ptrs), C.c_void_p(int(stream))))
+
+
+def render_animation(scenes, cams, image_width=400, n_samples=1, *, seeds=None, denoise=None, clamp=None, depth=16, seed=1, n_chunks=0, device=-1, gamma=True,
+                     group_cull=False, scan_valu=False, numerics=None, **params):
+    """``len(scenes)`` frames of a scene whose spheres move (and a camera that may), with history reuse across the motion, in one call on
+    the device (rtw_render_animation_*): per frame the scene's upload, a linear render, its feature pass, from frame 1 on the motion table
+    against the previous frame's scene and the motion pass, then the step (frame 0 is a first frame); with ``denoise`` (True, or a dict of
+    ``make_denoise``'s keywords ``levels, normal_power_log2, sigma_color, sigma_depth, demodulate``) one batched filter pass over the
+    accumulated frames; one copy back.  Frame v equals the chain of ``render``, ``render_features``, ``motion_table``, ``first_hit_motion``
+    and ``temporal_step_animated`` (and ``denoise_batch``) on the bits.  ``scenes``: HittableLists (or flat dicts) with the spheres in the
+    same order; ``cams``: as many cameras; ``seeds``: as many ints (None: ``seed``).  ``clamp``: as ``render_sequence``; other keywords:
+    ``make_temporal``'s.  ``gamma`` is applied once, by the last stage.  Returns ``img[v, i, j, :]``; ``last_stats()`` sums the renders."""
+    scenes = list(scenes)
+    cams, T = _batch_cameras(cams)
+    n = len(cams)
+    if len(scenes) != n:
+        raise ValueError(f"{len(scenes)} scenes for {n} cameras")
+    sd = _capi.make_seeds(seed if seeds is None else seeds, n)
+    height = _frame_height(image_width, n_samples)
+    D = None
+    if denoise:
+        dk = {} if denoise is True else dict(denoise)
+        if set(dk) - set(_DENOISE_KEYS):
+            raise ValueError(f"denoise takes the keywords {_DENOISE_KEYS}, got {sorted(set(dk) - set(_DENOISE_KEYS))}")
+        D = make_denoise(gamma=gamma, **dk)
+    tp = make_temporal(gamma=gamma, **params)
+    K = make_temporal_clamp(**_clamp_arg(clamp)) if clamp else None
+    made = [_capi.make_scene(_flat_scene(s, T), T) for s in scenes]
+    S = (type(made[0][0]) * n)(*[m[0] for m in made])
+    P = _capi.make_params(image_width, height, n_samples, depth, seed, n_chunks, 0, 1, device, 1 if gamma else 0,
+                          (_capi.FLAG_GROUP_CULL if group_cull else 0) | (_capi.FLAG_SCAN_VALU if scan_valu else 0), numerics=numerics)
+    out = np.empty(n * height * int(image_width) * 3, dtype=T)
+    L = _capi.lib()
+    fn = getattr(L, "rtw_render_animation_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(S, _capi.make_cameras(cams, T), n, sd, C.byref(P), C.byref(tp), C.byref(K) if K is not None else None, C.byref(D) if D is not None else None,
+                   out.ctypes.data_as(C.c_void_p)))
+    del made
+    _record_stats(L)
+    return out.reshape(n, int(image_width), height, 3).transpose(0, 2, 1, 3)
+
+
 class TemporalAccumulator:
     """The history of one camera path on one device: two device states (torch tensors; torch is the package's plumbing for device memory)
     and the previous frame's camera.  ``step`` enqueues one ``temporal_step_into`` and swaps the states; ``reset`` forgets the history, so
@@ -301,11 +463,19 @@ class TemporalAccumulator:
         self._cam_prev = None
         self.frames = 0
 
-    def step(self, cam, d_image_ptr, d_features_ptr, d_out_ptr, stream=0):
+    def step(self, cam, d_image_ptr, d_features_ptr, d_out_ptr, stream=0, d_motion_ptr=None):
+        """``d_motion_ptr``: the motion plane of this frame (``first_hit_motion_into``) -- the step over a moving scene
+        (``temporal_step_animated_into``); it is ignored on a first frame, which has no history to move.  None: the static steps, call for call."""
         if not isinstance(cam, Camera):
             raise TypeError("cam must be a Camera")
         prev = self._states[self._cur ^ 1].data_ptr() if self._cam_prev is not None else None
-        if self.clamp is not None:
+        if d_motion_ptr is not None:
+            mprev = self._moments[self._cur ^ 1].data_ptr() if self.moments and self._cam_prev is not None else None
+            temporal_step_animated_into(d_out_ptr, self._states[self._cur].data_ptr(), d_image_ptr, d_features_ptr, cam, self.width, self.height,
+                                        d_motion_ptr=d_motion_ptr if prev is not None else None, clamp=self.clamp, d_state_prev_ptr=prev, d_moment_prev_ptr=mprev,
+                                        d_moment_next_ptr=self._moments[self._cur].data_ptr() if self.moments else None, cam_prev=self._cam_prev,
+                                        elem_type=self.elem_type, stream=stream, **self.params)
+        elif self.clamp is not None:
             mprev = self._moments[self._cur ^ 1].data_ptr() if self.moments and self._cam_prev is not None else None
             temporal_step_clamped_into(d_out_ptr, self._states[self._cur].data_ptr(), d_image_ptr, d_features_ptr, cam, self.width, self.height, clamp=self.clamp,
                                        d_state_prev_ptr=prev, d_moment_prev_ptr=mprev, d_moment_next_ptr=self._moments[self._cur].data_ptr() if self.moments else None,

@@ -4,7 +4,7 @@ usage: python tools/kernel_resources.py [--unit NAME.hip ...] [extra hipcc flags
 The instances live in rtw_launch.hip and, the BATCH && ACCUM ones, in rtw_batch_accum_f32.hip / _f64.hip: one table over all three.
 --unit names other translation units instead (rtw_features.hip: the instances of the feature kernel, the batched ones among them; rtw_features_accum_batch_f32.hip /
 _f64.hip: its tiled batched instances; rtw_denoise.hip: the denoiser's kernels and the batched level kernels; rtw_accum_kernels.hip: the accumulator's kernels, the noise map and the
-batched resolve and noise map among them; rtw_temporal.hip: the instances of the temporal step, with and without moments, the temporal noise map and their batched (`paths`) twins; rtw_present.hip: the instances of the present kernel)."""
+batched resolve and noise map among them; rtw_temporal.hip: the instances of the temporal step, with and without moments, the temporal noise map and their batched (`paths`) twins; rtw_present.hip: the instances of the present kernel; rtw_motion.hip: the instances of the first-hit motion pass; `motion`: the step instances that read its plane)."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = ""
@@ -48,17 +48,20 @@ for r in rows:
     elif re.search(r"accum_noise_kernelI([fd])", n):
         label = "accum noise<%s>" % ("f32" if re.search(r"accum_noise_kernelI([fd])", n).group(1) == "f" else "f64")
     elif re.match(r"_ZN3rtw\d+tp_stepI([fd])Lb([01])E", n):
-        m = re.match(r"_ZN3rtw\d+tp_stepI([fd])Lb([01])E(?:Lb([01])E)?(?:Lb([01])E)?", n)
-        label = f"temporal tp_step<{'f32' if m.group(1) == 'f' else 'f64'}{', has_prev' if m.group(2) == '1' else ', first frame'}{', moments' if m.group(3) == '1' else ''}{', paths' if m.group(4) == '1' else ''}>"
+        m = re.match(r"_ZN3rtw\d+tp_stepI([fd])Lb([01])E(?:Lb([01])E)?(?:Lb([01])E)?(?:Lb([01])E)?", n)
+        label = f"temporal tp_step<{'f32' if m.group(1) == 'f' else 'f64'}{', has_prev' if m.group(2) == '1' else ', first frame'}{', moments' if m.group(3) == '1' else ''}{', paths' if m.group(4) == '1' else ''}{', motion' if m.group(5) == '1' else ''}>"
     elif re.match(r"_ZN3rtw\d+tp_step_clampedI([fd])Lb([01])ELb([01])E", n):
-        m = re.match(r"_ZN3rtw\d+tp_step_clampedI([fd])Lb([01])ELb([01])E(?:Lb([01])E)?", n)
-        label = f"temporal tp_step_clamped<{'f32' if m.group(1) == 'f' else 'f64'}{', moments' if m.group(2) == '1' else ''}{', guides' if m.group(3) == '1' else ''}{', paths' if m.group(4) == '1' else ''}>"
+        m = re.match(r"_ZN3rtw\d+tp_step_clampedI([fd])Lb([01])ELb([01])E(?:Lb([01])E)?(?:Lb([01])E)?", n)
+        label = f"temporal tp_step_clamped<{'f32' if m.group(1) == 'f' else 'f64'}{', moments' if m.group(2) == '1' else ''}{', guides' if m.group(3) == '1' else ''}{', paths' if m.group(4) == '1' else ''}{', motion' if m.group(5) == '1' else ''}>"
     elif re.match(r"_ZN3rtw\d+tp_noiseI([fd])", n):
         m = re.match(r"_ZN3rtw\d+tp_noiseI([fd])(?:Lb([01])E)?", n)
         label = f"temporal tp_noise<{'f32' if m.group(1) == 'f' else 'f64'}{', paths' if m.group(2) == '1' else ''}>"
     elif re.match(r"_ZN3rtw\d+pr_presentI([fd])Li([34])ELb([01])E", n):
         m = re.match(r"_ZN3rtw\d+pr_presentI([fd])Li([34])ELb([01])E", n)
         label = f"present pr_present<{'f32' if m.group(1) == 'f' else 'f64'}, C = {m.group(2)}{'' if m.group(2) == '4' else ', aligned rows' if m.group(3) == '1' else ', unaligned rows'}>"
+    elif re.match(r"_ZN3rtw\d+motion_passI([fd])Lb([01])E", n):
+        m = re.match(r"_ZN3rtw\d+motion_passI([fd])Lb([01])E", n)
+        label = f"motion motion_pass<{'f32' if m.group(1) == 'f' else 'f64'}{', lds-scene' if m.group(2) == '1' else ', global-scene'}>"
     elif "unit_kernel" in n:
         label = "unit_kernel<%s>" % ("f32" if "IfE" in n else "f64")
     else:
