@@ -1145,7 +1145,8 @@ int rtw_render_paths_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams,
  * rtw_render_animation_*: n_frames < 1, a negative sphere count -> -2; a null array of a scene that has spheres -> -1; everything
  * rtw_render_sequence_* / rtw_render_path_clamped_* refuses for n_frames views, with its code.
  *   Left out on purpose: batched paths with motion (rtw_reproject_batch_device_* has no motion planes),
- * motion blur inside a frame, guided-filter and upsampler one-call forms, accumulators, device lists, the Julia shim.
+ * a time per ray (true in-frame motion blur: the rtw_velocity_blur_* block below blurs a finished frame along the motion plane instead),
+ * guided-filter and upsampler one-call forms, accumulators, device lists, the Julia shim.
  * Additive to ABI 4: detected by symbol lookup. */
 int rtw_motion_table_f32(const rtw_scene_f32 *scene_prev, const rtw_scene_f32 *scene, void *table /* host */);
 int rtw_motion_table_f64(const rtw_scene_f64 *scene_prev, const rtw_scene_f64 *scene, void *table /* host */);
@@ -1171,6 +1172,89 @@ int rtw_render_animation_f32(const rtw_scene_f32 *scenes, const rtw_camera_f32 *
                              const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* may be NULL */, const rtw_denoise_t *d /* may be NULL */, float *out);
 int rtw_render_animation_f64(const rtw_scene_f64 *scenes, const rtw_camera_f64 *cams, int32_t n_frames, const uint64_t *seeds /* may be NULL */, const rtw_params *p,
                              const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* may be NULL */, const rtw_denoise_t *d /* may be NULL */, double *out);
+
+/* Motion blur: a velocity-guided gather on the motion plane.  The 1-spp animation path renders every moving sphere razor sharp, so it
+ * strobes; the motion plane of the block above says how far every pixel's surface moved.  This stage blurs a finished LINEAR frame along
+ * that motion: a deterministic form of McGuire et al. 2012, "A Reconstruction Filter for Plausible Motion Blur" -- tile max, neighbour
+ * max, a gather along the neighbourhood's dominant velocity with soft depth and velocity-aware weights; no jitter.  It sits between the
+ * last linear stage (the step or the filter) and the present stage; it reads no temporal state and writes none, and its output must never
+ * be fed back into the history.
+ *
+ * The definition.  Everything is computed in T; every operation is rounded once, no FMA; quotients and sqrt are the correctly rounded IEEE
+ * ones; three-term sums are grouped (x + y) + z; a tap that does not take part is dropped by a select.  Pixel (i, j) is slot p = j*H + i.
+ * Inputs: a LINEAR image (H*W*3), the features (H*W*8), the motion plane (H*W*4), `cam`, `cam_prev` and rtw_velocity_blur_t; output: an image
+ * (H*W*3) that aliases no input.  clamp01(x) = x > 0 ? (x < 1 ? x : 1) : +0.
+ *   Prepare.  valid, cov, has and z exactly as in the rtw_temporal_* block; zc = has ? z : +inf.
+ *   Previous position.  Exactly the motion step's, with its host constants: for a `has` pixel d = ((origin + z*nD) - m) - origin_prev, for a
+ * sky pixel d = nD (camera rotation blurs the sky); then dw, front, lam, s, t, x, y as defined there.  moved = valid and front and x and y
+ * both finite;  u = moved ? (T(j) - x, T(i) - y) : (0, 0).
+ *   Half-extent.  h = u * T(shutter/2) (the host rounds the factor once);  l2 = h.x*h.x + h.y*h.y;  if l2 > 256: h = h * (T(16) / sqrt(l2))
+ * (one quotient, two products) and l2 is recomputed from the scaled h;  l = sqrt(l2).  The BLUR PLANE holds, at slot p, (h.x, h.y, zc, l) --
+ * 16 or 32 bytes; zc is NaN for a pixel that is not valid.
+ *   Tile max.  Tile (a, b) covers rows 16a .. 16a+15 and columns 16b .. 16b+15, clipped to the frame; TH = ceil(H/16), TW = ceil(W/16); its
+ * index is b*TH + a.  Its value is the (h.x, h.y, l) of its pixel with the greatest l; among equals the lowest slot p wins (the rule is
+ * associative: any reduction tree gives the same answer).  The TILE PLANE holds (h.x, h.y, l, 0) at slot b*TH + a.
+ *   Neighbour max.  Over the up to nine tiles around a tile that lie in the frame: the greatest l, ties to the lowest tile index.  The
+ * NEIGHBOUR PLANE holds (vN.x, vN.y, lN, 0) at slot b*TH + a.
+ *   Gather, per valid pixel X = (i, j) with colour c, in tile (i/16, j/16).  If not lN >= T(0.5): out = c.  Otherwise lX = max(l_X, T(0.5)),
+ * w0 = 1/lX, wsum = w0, sum[k] = c[k]*w0, and for n = 0 .. taps-1 except the middle one, n = (taps-1)/2:
+ *       tt = T(2(n+1) - (taps+1)) / T(taps+1)
+ *       qj = rint(T(j) + vN.x*tt);  qi = rint(T(i) + vN.y*tt)         (ties to even)
+ *       a tap outside the frame or on a pixel that is not valid is skipped
+ *       dist = sqrt(T(qj-j)*T(qj-j) + T(qi-i)*T(qi-i));  lY = max(l_q, T(0.5));  ext = T(depth_extent)
+ *       soft depth compare of zc_q against zc_X: equal (both +inf included): f = b = 1; both finite: f = clamp01(1 - (zc_q - zc_X)/ext),
+ *           b = clamp01(1 - (zc_X - zc_q)/ext); exactly one infinite: the finite one is in front -- zc_q finite: f = 1, b = 0, else f = 0,
+ *           b = 1 -- decided by selects, never by arithmetic on an infinity
+ *       cone(dist, l) = clamp01(1 - dist/l);  cyl(dist, l) = 1 - (x*x)*(3 - 2*x) with x = clamp01((dist - T(0.95)*l) / (T(0.1)*l))
+ *       a = (f*cone(dist, lY) + b*cone(dist, lX)) + (cyl(dist, lY)*cyl(dist, lX))*2
+ *       wsum = wsum + a;  sum[k] = sum[k] + a*c_q[k]
+ * out[k] = sum[k] / wsum.  Then sqrt per channel if gamma = 1 (the pass-through pixels too).  A pixel that is not valid is a quiet NaN in
+ * all three channels.  (tests/motion_blur_ref.py restates all of this on the CPU, twice, and the device agrees on the bits.)
+ *   Workspace.  Caller-owned, rtw_velocity_blur_work_bytes(width, height, elem_bytes) bytes (monotone in the size; < 0: an error code), 16-byte
+ * aligned: the blur plane at byte 0, the tile plane at byte 4*W*H*sizeof(T), the neighbour plane TH*TW slots behind it.  The layout is
+ * public, like the state's.
+ *
+ * rtw_velocity_blur_device_*: THREE launches (velocity and tile max: a workgroup per tile; neighbour max; gather), asynchronous on
+ * `hip_stream` of the device b->device (-1: the current one); rtw_stats() is left alone.  d_features, d_motion and d_work are 16-byte
+ * aligned, d_image and d_out aligned to T; d_out and d_work alias neither each other nor any input.
+ *   rtw_velocity_blur_*: the host-buffer form, blocking, through the cached per-device context like rtw_animated_step_f32.
+ *   rtw_render_blurred_*: rtw_render_animation_* with the blur behind its last linear stage -- the same launches with gamma 0 up
+ * to and including the steps (with `d`: the filter pass), one motion plane per frame kept, then for every frame from 1 on the three
+ * launches above on (frame v, its features, its motion plane, cams[v], cams[v-1]) with gamma = p->gamma (b->gamma and b->device are
+ * replaced); frame 0 has no previous camera and passes through with p->gamma applied (one launch).  ONE D2H as before.  Frame v equals, on
+ * the bits, rtw_render_animation_* with p->gamma = 0 followed by rtw_velocity_blur_* on frame v.
+ *   Refusals, all decided before any HIP call: a null argument -> -1; taps even or outside 3..31, unknown flags, gamma other than 0 or 1,
+ * reserved != 0, device < -1, shutter outside (0, 1] or not finite, depth_extent not finite and positive, width or height < 1, elem_bytes
+ * other than 4 or 8, misaligned or aliasing pointers -> -2; the denoiser's frame rule -> -5; the animation call additionally everything
+ * rtw_render_animation_* refuses, with its code.
+ *   Left out on purpose: batched views, upsampler and present one-call forms (the device stages compose on the
+ * caller's stream), device lists, the Julia shim, jittered taps, lens-aware velocities, a time per ray.
+ * Additive to ABI 4: detected by symbol lookup. */
+#define RTW_VELOCITY_BLUR_TILE 16    /* the tile's edge and the largest half-extent of a blur, in pixels */
+typedef struct {
+    int32_t taps;               /* odd, 3..31: taps along the dominant velocity, the centre one is the pixel itself (default 15) */
+    int32_t flags;              /* 0 */
+    int32_t gamma;              /* 1 = sqrt per channel at the very end, 0 = linear */
+    int32_t device;             /* -1 = current */
+    int32_t reserved[2];        /* 0 */
+    double  shutter;            /* in (0, 1]: the fraction of the frame interval the shutter is open, centred on the frame's time */
+    double  depth_extent;       /* > 0, finite, world units: the softness of the depth compare (default 0.5) */
+} rtw_velocity_blur_t;            /* 40 bytes */
+int64_t rtw_velocity_blur_work_bytes(int32_t width, int32_t height, int32_t elem_bytes);
+int rtw_velocity_blur_device_f32(const rtw_velocity_blur_t *b, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height,
+                               const void *d_image, const void *d_features, const void *d_motion, void *d_work, void *d_out, void *hip_stream);
+int rtw_velocity_blur_device_f64(const rtw_velocity_blur_t *b, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
+                               const void *d_image, const void *d_features, const void *d_motion, void *d_work, void *d_out, void *hip_stream);
+int rtw_velocity_blur_f32(const rtw_velocity_blur_t *b, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height,
+                        const float *image, const float *features, const float *motion, float *out);
+int rtw_velocity_blur_f64(const rtw_velocity_blur_t *b, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
+                        const double *image, const double *features, const double *motion, double *out);
+int rtw_render_blurred_f32(const rtw_scene_f32 *scenes, const rtw_camera_f32 *cams, int32_t n_frames, const uint64_t *seeds /* may be NULL */, const rtw_params *p,
+                                     const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* may be NULL */, const rtw_denoise_t *d /* may be NULL */,
+                                     const rtw_velocity_blur_t *b, float *out);
+int rtw_render_blurred_f64(const rtw_scene_f64 *scenes, const rtw_camera_f64 *cams, int32_t n_frames, const uint64_t *seeds /* may be NULL */, const rtw_params *p,
+                                     const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* may be NULL */, const rtw_denoise_t *d /* may be NULL */,
+                                     const rtw_velocity_blur_t *b, double *out);
 
 /* Present stage: display-ready 8-bit frames from the device.  Every pipeline above ends in T elements in the column-major layout of the
  * render entry points; a window, a PNG or a video encoder wants 8-bit rows.  One kernel clips, rounds, packs and transposes in HBM, and the

@@ -40,6 +40,7 @@ from .temporal import (  # noqa: F401
     temporal_path_table, temporal_step_batch_into, temporal_noise_batch_into, TemporalBatchAccumulator, render_sequences,
     motion_table, first_hit_motion, first_hit_motion_into, temporal_step_animated, temporal_step_animated_into, render_animation,
 )
+from .motion_blur import make_motion_blur, motion_blur, motion_blur_into, motion_blur_work_bytes  # noqa: F401
 from .present import (  # noqa: F401
     make_present, present, present_batch_into, present_bytes, present_into, render_presented, render_presented_batch,
 )
@@ -65,5 +66,6 @@ __all__ = [
     "make_temporal_clamp", "temporal_step_clamped", "temporal_step_clamped_into",
     "temporal_path_table", "temporal_step_batch_into", "temporal_noise_batch_into", "TemporalBatchAccumulator", "render_sequences",
     "motion_table", "first_hit_motion", "first_hit_motion_into", "temporal_step_animated", "temporal_step_animated_into", "render_animation",
+    "make_motion_blur", "motion_blur_work_bytes", "motion_blur", "motion_blur_into",
     "make_present", "present_bytes", "present", "present_into", "present_batch_into", "render_presented", "render_presented_batch",
 ]

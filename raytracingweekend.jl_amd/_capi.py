@@ -43,6 +43,8 @@ SYMBOLS = [
     "rtw_motion_table_f32", "rtw_motion_table_f64", "rtw_first_hit_motion_device_f32", "rtw_first_hit_motion_device_f64", "rtw_first_hit_motion_f32",
     "rtw_first_hit_motion_f64", "rtw_animated_step_device_f32", "rtw_animated_step_device_f64", "rtw_animated_step_f32", "rtw_animated_step_f64",
     "rtw_render_animation_f32", "rtw_render_animation_f64",
+    "rtw_velocity_blur_work_bytes", "rtw_velocity_blur_device_f32", "rtw_velocity_blur_device_f64", "rtw_velocity_blur_f32", "rtw_velocity_blur_f64",
+    "rtw_render_blurred_f32", "rtw_render_blurred_f64",
     "rtw_present_bytes", "rtw_present_device_f32", "rtw_present_device_f64", "rtw_present_batch_device_f32", "rtw_present_batch_device_f64",
     "rtw_present_f32", "rtw_present_f64", "rtw_render_presented_f32", "rtw_render_presented_f64", "rtw_render_presented_batch_f32",
     "rtw_render_presented_batch_f64",
@@ -133,6 +135,14 @@ class TemporalClamp(C.Structure):
 
 
 assert C.sizeof(TemporalClamp) == 32
+
+
+class VelocityBlur(C.Structure):
+    """rtw_velocity_blur_t"""
+    _fields_ = [(k, C.c_int32) for k in ("taps", "flags", "gamma", "device")] + [("reserved", C.c_int32 * 2), ("shutter", C.c_double), ("depth_extent", C.c_double)]
+
+
+assert C.sizeof(VelocityBlur) == 40
 
 
 class Present(C.Structure):
@@ -245,6 +255,9 @@ def lib():
         getattr(L, "rtw_animated_step_device_" + sfx).argtypes = [tp, tc, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_animated_step_" + sfx).argtypes = [tp, tc, C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_render_animation_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), tp, tc, C.POINTER(Denoise), ptr]
+        getattr(L, "rtw_velocity_blur_device_" + sfx).argtypes = [C.POINTER(VelocityBlur), C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_velocity_blur_" + sfx).argtypes = [C.POINTER(VelocityBlur), C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_render_blurred_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), tp, tc, C.POINTER(Denoise), C.POINTER(VelocityBlur), ptr]
         pr, dn = C.POINTER(Present), C.POINTER(Denoise)
         getattr(L, "rtw_present_device_" + sfx).argtypes = [pr, i32, i32, ptr, ptr, ptr]
         getattr(L, "rtw_present_batch_device_" + sfx).argtypes = [pr, i32, i32, i32, ptr, ptr, ptr]
@@ -255,6 +268,8 @@ def lib():
     L.rtw_present_bytes.restype = C.c_int64
     L.rtw_temporal_state_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_temporal_state_bytes.restype = C.c_int64
+    L.rtw_velocity_blur_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.rtw_velocity_blur_work_bytes.restype = C.c_int64
     L.rtw_history_moment_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_history_moment_bytes.restype = C.c_int64
     L.rtw_reproject_table_bytes.argtypes = [C.c_int32, C.c_int32]

@@ -16,6 +16,7 @@
 //   rtw_upsample.hip     the feature-guided upsampler: its checks, the launch sequence (the denoiser's prepare and level kernels at the small size, then rtw_upsample.hpp at the full size), the device-resident entry points
 //   rtw_temporal.hip     temporal reprojection: its checks, the host constants and the one launch of a step for one path or a batch of paths (rtw_temporal.hpp; clamped: rtw_temporal_clamp.hpp), the device-resident entry points
 //   rtw_motion.hip       the first-hit motion pass over moving spheres: its checks, the motion table, the one launch of its kernel (rtw_motion.hpp), the device-resident entry points
+//   rtw_motion_blur.hip  the motion-blur stage on the motion plane: its checks, the workspace, the three launches of its kernels (rtw_motion_blur.hpp), the device-resident entry points
 //   rtw_present.hip      the present stage: its checks, the one launch of its kernel (rtw_present.hpp) for one frame or a batch, the device-resident entry points
 //   (rtw_scene_view.hpp: what both launch functions derive from their arguments; rtw_instances.hpp: the one table of the trace kernel's instances)
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
@@ -384,6 +385,16 @@ int launch_motion_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const r
 int launch_motion_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const void *d_table, void *d_motion, hipStream_t stream);
 inline int launch_motion_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, const void *tab, void *mo, hipStream_t st) { return launch_motion_f32(s, c, p, tab, mo, st); }
 inline int launch_motion_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, const void *tab, void *mo, hipStream_t st) { return launch_motion_f64(s, c, p, tab, mo, st); }
+
+// rtw_motion_blur.hip -- the motion-blur stage (include/rtw_hip.h rtw_velocity_blur_*).  validate_motion_blur: every check of a blur that needs
+// neither a device nor a pointer.  launch_motion_blur: enqueue the stage (THREE launches, no record) on `stream` of the current device; d_work:
+// rtw_velocity_blur_work_bytes bytes.  cam_prev null (frame 0 of rtw_render_blurred_*): ONE launch, the image passes through with the
+// gamma applied; d_motion and d_work are not looked at.
+int validate_motion_blur(const rtw_velocity_blur_t *b, int32_t width, int32_t height, int elem_bytes);
+int launch_motion_blur_f32(const rtw_velocity_blur_t *b, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_motion, void *d_work, void *d_out, hipStream_t stream);
+int launch_motion_blur_f64(const rtw_velocity_blur_t *b, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_motion, void *d_work, void *d_out, hipStream_t stream);
+inline int launch_motion_blur_t(const rtw_velocity_blur_t *b, const rtw_camera_f32 *c, const rtw_camera_f32 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *mo, void *work, void *out, hipStream_t st) { return launch_motion_blur_f32(b, c, cp, w, h, img, feat, mo, work, out, st); }
+inline int launch_motion_blur_t(const rtw_velocity_blur_t *b, const rtw_camera_f64 *c, const rtw_camera_f64 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *mo, void *work, void *out, hipStream_t st) { return launch_motion_blur_f64(b, c, cp, w, h, img, feat, mo, work, out, st); }
 
 // rtw_present.hip -- the present stage (include/rtw_hip.h rtw_present_*).  validate_present: every check of a call that needs neither a device
 // nor a pointer -- the parameters, the frame, n_views (0: one frame; a batch's count through batch_views) and the size of the launch.

@@ -689,6 +689,38 @@ int temporal_step_host(bool form_args, const rtw_temporal_t *t, const rtw_tempor
     return rc;
 }
 
+// The motion-blur stage on host buffers (rtw_velocity_blur_*): a leased context of the device like temporal_step_host's, three H2D (the image,
+// the features, the motion plane), the stage's three launches, ONE D2H.  The device buffer holds the three inputs, the output and the
+// workspace, each on a 16-byte boundary.  This thread's last render (rtw_stats) is not touched.
+template <typename T, typename CamT>
+int motion_blur_host(const rtw_velocity_blur_t *b, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const T *image, const T *features, const T *motion, T *out) {
+    if (!b || !cam || !cam_prev || !image || !features || !motion || !out) return fail(-1, "null argument");
+    if (int rc = validate_motion_blur(b, width, height, (int)sizeof(T))) return rc;
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t n_pix = (size_t)width * (size_t)height;
+    const size_t img_b = n_pix * 3 * sizeof(T), feat_b = n_pix * RTW_FEATURE_CHANNELS * sizeof(T), mo_b = n_pix * 4 * sizeof(T);
+    const size_t work_b = (size_t)rtw_velocity_blur_work_bytes(width, height, (int32_t)sizeof(T));
+    const size_t off_feat = up(img_b), off_mo = off_feat + up(feat_b), off_out = off_mo + mo_b, off_work = off_out + up(img_b), total = off_work + work_b;
+    if (ranges_overlap(out, img_b, image, img_b) || ranges_overlap(out, img_b, features, feat_b) || ranges_overlap(out, img_b, motion, mo_b)) return fail(-2, "out may not alias an input");
+    DeviceGuard guard;
+    HostLease L;
+    if (int rc = acquire_host(b->device, std::vector<unsigned char>(), &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, total)) return rc;
+    char *base = (char *)hc->d_img;
+    int rc = 0;
+    hipError_t e = hipMemcpyAsync(base, image, img_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + off_feat, features, feat_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + off_mo, motion, mo_b, hipMemcpyHostToDevice, hc->stream);
+    if (e != hipSuccess) rc = fail((int)e, "upload of the motion blur's inputs failed: %s", hipGetErrorString(e));
+    rtw_velocity_blur_t bb = *b;
+    bb.device = hc->device;
+    if (!rc) rc = launch_motion_blur_t(&bb, cam, cam_prev, width, height, base, base + off_feat, base + off_mo, base + off_work, base + off_out, hc->stream);
+    if (!rc) rc = copy_out(hc, base + off_out, out, img_b);
+    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    return rc;
+}
+
 // N cameras along a path with history reuse (rtw_render_sequence_*): the one-device path above with a device buffer that holds the linear images
 // (ONE batched render with gamma 0), the features (ONE batched pass over all chunks), the accumulated images (n_views temporal steps in view
 // order, two states ping-pong) and, with `d`, the filtered images and the filter's workspace (ONE batched filter pass); 2 + n_views (+ 1 + levels)
@@ -802,18 +834,23 @@ inline int motion_table_t(const rtw_scene_f64 *prev, const rtw_scene_f64 *cur, d
 // every other.  The device buffer holds the sequence's regions, ONE motion plane and ONE table behind them (stream order lets every frame
 // reuse both).  With `d` ONE batched filter pass over all frames, then ONE D2H.  p->gamma is applied by the last stage that runs.
 // rtw_stats(): the counters of all frames' renders summed, the times of the slowest.
+// `b` non-null (rtw_render_blurred_*; `blurred` says only that the ENTRY POINT requires it): every stage above runs with gamma 0,
+// every frame keeps a motion plane of its own, and behind the last of them the motion-blur stage runs per frame with p->gamma -- three
+// launches for every frame from 1 on, the one pass-through launch for frame 0 -- into a region of n_frames frames behind the table, with ONE
+// workspace (stream order lets every frame reuse it); the D2H reads that region.  Without `b` the buffer and the launches are what they were.
 // (Not through render_one_device: that path uploads one scene and resolves one record.)
 template <typename T, typename SceneT, typename CamT>
 int render_host_animation(const SceneT *scenes, const CamT *cams, int32_t n_frames, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t, const rtw_temporal_clamp_t *c,
-                          const rtw_denoise_t *d, T *out) {
+                          const rtw_denoise_t *d, T *out, const rtw_velocity_blur_t *b = nullptr, bool blurred = false) {
     if (!p) return fail(-1, "null params");
-    if (!scenes || !cams || !t || !out) return fail(-1, "null argument");
+    if (!scenes || !cams || !t || !out || (blurred && !b)) return fail(-1, "null argument");
     if (n_frames < 1) return fail(-2, "n_frames must be >= 1 (got %d)", n_frames);
     int nch, cs;
     if (int rc = validate_features_batch(cams, n_frames, p, 0, 1, out, &nch, &cs)) return rc;
     if (d) if (int rc = validate_filter_batch(d, p->width, p->height, n_frames)) return rc;
     if (int rc = validate_temporal(t, p->width, p->height, (int)sizeof(T))) return rc;
     if (c) if (int rc = validate_temporal_clamp(c)) return rc;
+    if (b) if (int rc = validate_motion_blur(b, p->width, p->height, (int)sizeof(T))) return rc;
     rtw_params pm = *p;                                       // the motion pass reads the frame, the device and the numerics bits
     pm.flags &= RTW_FLAG_GROUP_CULL | RTW_FLAG_SCAN_VALU | RTW_FLAG_NUMERICS_CONTRACT | RTW_FLAG_NUMERICS_REFERENCE_FMA2;
     if (int rc = validate_motion(&pm, (int)sizeof(T))) return rc;
@@ -828,14 +865,16 @@ int render_host_animation(const SceneT *scenes, const CamT *cams, int32_t n_fram
     DeviceGuard guard;
     release_last();
     const TemporalRegions<T> R(p->width, p->height, (size_t)n_frames, d != nullptr);
-    const size_t mo_b = (size_t)p->width * (size_t)p->height * 4 * sizeof(T), off_mo = up(R.total), off_tab = off_mo + mo_b, feat_frame_b = R.feat_b / (size_t)n_frames;
+    const size_t mo_b = (size_t)p->width * (size_t)p->height * 4 * sizeof(T), off_mo = up(R.total), off_tab = off_mo + mo_b * (b ? (size_t)n_frames : 1), feat_frame_b = R.feat_b / (size_t)n_frames;
+    const size_t off_blur = up(off_tab + tab_max), off_bwork = off_blur + up(R.img_b);
+    const size_t total = b ? off_bwork + (size_t)rtw_velocity_blur_work_bytes(p->width, p->height, (int32_t)sizeof(T)) : off_tab + tab_max;
     std::vector<unsigned char> key;
     scene_key_of(&scenes[0], sizeof(T) == 8, key);
     std::vector<ScenePtr> replaced;                           // (declared before the lease: the stream has drained when these are freed)
     HostLease L;
     if (int rc = acquire_host(p->device, key, &L)) return rc;
     HostCtx *hc = L.hc;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, off_tab + tab_max)) return rc;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, total)) return rc;
     if (hc->stage_cap < tab_sum) {
         if (hc->h_stage) { HIP_IGNORE(hipHostFree(hc->h_stage)); hc->h_stage = nullptr; hc->stage_cap = 0; }
         HIP_TRY(hipHostMalloc(&hc->h_stage, tab_sum, hipHostMallocDefault));
@@ -846,7 +885,7 @@ int render_host_animation(const SceneT *scenes, const CamT *cams, int32_t n_fram
     q.device = hc->device; q.n_devices = 0; q.device_ids = nullptr; q.gamma = 0;
     pm.device = hc->device;
     rtw_temporal_t tt = *t;
-    tt.gamma = d ? 0 : (p->gamma != 0); tt.device = hc->device;
+    tt.gamma = (d || b) ? 0 : (p->gamma != 0); tt.device = hc->device;
     std::vector<RenderRec *> recs((size_t)n_frames, nullptr), frecs((size_t)n_frames, nullptr);
     std::vector<CtxPtr> rctx((size_t)n_frames), fctx((size_t)n_frames);
     int rc = 0;
@@ -856,7 +895,7 @@ int render_host_animation(const SceneT *scenes, const CamT *cams, int32_t n_fram
         if (v) scene_key_of(scene, sizeof(T) == 8, key);
         if ((rc = ensure_scene<T>(hc, scene, key, &replaced))) break;
         if (seeds) q.seed = seeds[v];
-        char *img = base + (size_t)v * R.frame_b, *feat = base + R.off_feat + (size_t)v * feat_frame_b;
+        char *img = base + (size_t)v * R.frame_b, *feat = base + R.off_feat + (size_t)v * feat_frame_b, *plane = base + off_mo + (b ? (size_t)v * mo_b : 0);
         rc = launch_render_t(hc->scene, cams + v, 0, nullptr, &q, img, hc->stream, &recs[v], &rctx[v]);
         if (!rc) rc = launch_features_t(hc->scene, cams + v, 0, nullptr, &q, 0, nch, feat, hc->stream, &frecs[v], &fctx[v]);
         if (!rc && v) {
@@ -868,17 +907,24 @@ int render_host_animation(const SceneT *scenes, const CamT *cams, int32_t n_fram
                 if (!rc) if (hipError_t e = hipMemcpyAsync(base + off_tab, tab, tab_b, hipMemcpyHostToDevice, hc->stream); e != hipSuccess)
                     rc = fail((int)e, "upload of the motion table failed: %s", hipGetErrorString(e));
             }
-            if (!rc) rc = launch_motion_t(hc->scene, cams + v, &pm, tab_b ? base + off_tab : nullptr, base + off_mo, hc->stream);
+            if (!rc) rc = launch_motion_t(hc->scene, cams + v, &pm, tab_b ? base + off_tab : nullptr, plane, hc->stream);
         }
         if (!rc) rc = launch_temporal_t(&tt, cams + v, v ? cams + (v - 1) : nullptr, 0, nullptr, p->width, p->height, img, feat, v ? base + R.off_st[(v & 1) ^ 1] : nullptr,
-                                        base + R.off_st[v & 1], base + R.off_acc + (size_t)v * R.frame_b, hc->stream, nullptr, nullptr, c, v ? base + off_mo : nullptr);
+                                        base + R.off_st[v & 1], base + R.off_acc + (size_t)v * R.frame_b, hc->stream, nullptr, nullptr, c, v ? plane : nullptr);
     }
     if (!rc && d) {
         rtw_denoise_t dd = *d;
-        dd.gamma = p->gamma != 0; dd.device = hc->device;
+        dd.gamma = b ? 0 : (p->gamma != 0); dd.device = hc->device;
         rc = launch_denoise_t(&dd, p->width, p->height, n_frames, (const T *)(base + R.off_acc), base + R.off_feat, base + R.off_flt, base + R.off_work, hc->stream);
     }
-    if (!rc) rc = copy_out(hc, base + (d ? R.off_flt : R.off_acc), out, R.img_b);
+    if (b) {
+        rtw_velocity_blur_t bb = *b;
+        bb.gamma = p->gamma != 0; bb.device = hc->device;
+        for (int v = 0; v < n_frames && !rc; ++v)
+            rc = launch_motion_blur_t(&bb, cams + v, v ? cams + (v - 1) : nullptr, p->width, p->height, base + (d ? R.off_flt : R.off_acc) + (size_t)v * R.frame_b,
+                                      base + R.off_feat + (size_t)v * feat_frame_b, base + off_mo + (size_t)v * mo_b, base + off_bwork, base + off_blur + (size_t)v * R.frame_b, hc->stream);
+    }
+    if (!rc) rc = copy_out(hc, base + (b ? off_blur : d ? R.off_flt : R.off_acc), out, R.img_b);
     if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends or an upload is freed
     for (int v = 0; v < n_frames; ++v) {
         if (recs[v]) { if (!rc) rc = resolve_rec(recs[v], &g_last.agg); release_rec(rctx[v], recs[v], rc == 0); }
@@ -1095,6 +1141,22 @@ int rtw_render_animation_f32(const rtw_scene_f32 *scenes, const rtw_camera_f32 *
 int rtw_render_animation_f64(const rtw_scene_f64 *scenes, const rtw_camera_f64 *cams, int32_t n_frames, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                              const rtw_temporal_clamp_t *c, const rtw_denoise_t *d, double *out) {
     return render_host_animation<double>(scenes, cams, n_frames, seeds, p, t, c, d, out);
+}
+int rtw_render_blurred_f32(const rtw_scene_f32 *scenes, const rtw_camera_f32 *cams, int32_t n_frames, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
+                                     const rtw_temporal_clamp_t *c, const rtw_denoise_t *d, const rtw_velocity_blur_t *b, float *out) {
+    return render_host_animation<float>(scenes, cams, n_frames, seeds, p, t, c, d, out, b, true);
+}
+int rtw_render_blurred_f64(const rtw_scene_f64 *scenes, const rtw_camera_f64 *cams, int32_t n_frames, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
+                                     const rtw_temporal_clamp_t *c, const rtw_denoise_t *d, const rtw_velocity_blur_t *b, double *out) {
+    return render_host_animation<double>(scenes, cams, n_frames, seeds, p, t, c, d, out, b, true);
+}
+int rtw_velocity_blur_f32(const rtw_velocity_blur_t *b, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height, const float *image, const float *features,
+                        const float *motion, float *out) {
+    return motion_blur_host<float>(b, cam, cam_prev, width, height, image, features, motion, out);
+}
+int rtw_velocity_blur_f64(const rtw_velocity_blur_t *b, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const double *image, const double *features,
+                        const double *motion, double *out) {
+    return motion_blur_host<double>(b, cam, cam_prev, width, height, image, features, motion, out);
 }
 int rtw_render_path_clamped_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                                  const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, float *out) {

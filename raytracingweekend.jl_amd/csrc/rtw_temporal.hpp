@@ -19,6 +19,8 @@
 //                  pixel's slot of the motion plane (rtw_first_hit_motion_device_*: (m.x, m.y, m.z, id), one 16- or 32-byte load) is
 //                  subtracted from its world point before the previous origin is; false: the instance is the static step's, instruction
 //                  for instruction.
+// (The pixel's own ray, the point to reproject and its projection are the text of rtw_temporal_project.inc, which tp_step_clamped and the motion
+// blur's velocity kernel include too: one copy of that arithmetic, and the instances keep their instructions.)
 // No LDS, no atomics, no cross-lane operation; the trip count over the 4 taps is uniform, skipped taps are dropped by selects, as in dn_tap.
 // (tp_noise: lanes with a long history skip the window by a branch of their own; the window's trip count is the radius', uniform.)
 // Every operation is rounded once (the Makefile's -ffp-contract=off -fno-fast-math); divisions and sqrt are the compiler's IEEE ones.
@@ -154,35 +156,7 @@ __global__ __launch_bounds__(256) void tp_step(TpParams<T> U, const T *__restric
         y2 = y * y; mom = y2;
     }
     if constexpr (HAS_PREV) {
-        // ---- the pixel's own ray in the current camera (the centre of the trace kernel's samples; the lens is ignored)
-        const T su = (T((int)j) + T(1.5)) / T((int)W);
-        const T tv = (T((int)(H - i)) - T(0.5)) / T((int)H);
-        const T D0 = ((U.llc[0] + su * U.hor[0]) + tv * U.ver[0]) - U.o[0];
-        const T D1 = ((U.llc[1] + su * U.hor[1]) + tv * U.ver[1]) - U.o[1];
-        const T D2 = ((U.llc[2] + su * U.hor[2]) + tv * U.ver[2]) - U.o[2];
-        const T sl = dn_sqrt((D0 * D0 + D1 * D1) + D2 * D2);
-        const T n0 = D0 / sl, n1 = D1 / sl, n2 = D2 / sl;
-        // ---- the point to reproject (a sky pixel: the point at infinity), relative to the previous origin
-        T d0, d1, d2;
-        if constexpr (MOTION) {
-            // where the surface was one frame ago: d = ((origin + z*nD) - m) - origin_prev (a non-finite m: d is NaN, inr fails, the pixel resets)
-            const V mv = B.plane[P];
-            d0 = has ? ((U.o[0] + z * n0) - mv.x) - U.po[0] : n0;
-            d1 = has ? ((U.o[1] + z * n1) - mv.y) - U.po[1] : n1;
-            d2 = has ? ((U.o[2] + z * n2) - mv.z) - U.po[2] : n2;
-        } else {
-            d0 = has ? (U.o[0] + z * n0) - U.po[0] : n0;
-            d1 = has ? (U.o[1] + z * n1) - U.po[1] : n1;
-            d2 = has ? (U.o[2] + z * n2) - U.po[2] : n2;
-        }
-        // ---- projection into the previous camera
-        const T dw = tp_dot<T>(d0, d1, d2, U.pw);
-        const bool front = dw < T(0);
-        const T lam = U.Kw / dw;
-        const T s = (lam * tp_dot<T>(d0, d1, d2, U.ph) - U.Qh) * U.ih;
-        const T t = (lam * tp_dot<T>(d0, d1, d2, U.pv) - U.Qv) * U.iv;
-        const T x = s * T((int)W) - T(1.5);
-        const T y = (T((int)H) - T(0.5)) - t * T((int)H);
+#include "rtw_temporal_project.inc"
         const bool inr = x > T(-1) && x < T((int)W) && y > T(-1) && y < T((int)H);       // (a NaN fails)
         // (a position that is not in range decides nothing: its taps are gathered around (0, 0) and thrown away)
         const T xs = inr ? x : T(0), ys = inr ? y : T(0);

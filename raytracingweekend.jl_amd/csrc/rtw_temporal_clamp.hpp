@@ -134,32 +134,7 @@ __global__ __launch_bounds__(256) void tp_step_clamped(TpParams<T> U, TpClampPar
     const T lo0 = mu0 - d0_, lo1 = mu1 - d1_, lo2 = mu2 - d2_;
     const T hi0 = mu0 + d0_, hi1 = mu1 + d1_, hi2 = mu2 + d2_;
     // ---- the pixel's own ray in the current camera, the point to reproject, the projection: tp_step's
-    const T su = (T((int)j) + T(1.5)) / T((int)W);
-    const T tv = (T((int)(H - i)) - T(0.5)) / T((int)H);
-    const T D0 = ((U.llc[0] + su * U.hor[0]) + tv * U.ver[0]) - U.o[0];
-    const T D1 = ((U.llc[1] + su * U.hor[1]) + tv * U.ver[1]) - U.o[1];
-    const T D2 = ((U.llc[2] + su * U.hor[2]) + tv * U.ver[2]) - U.o[2];
-    const T sl = dn_sqrt((D0 * D0 + D1 * D1) + D2 * D2);
-    const T n0 = D0 / sl, n1 = D1 / sl, n2 = D2 / sl;
-    T d0, d1, d2;
-    if constexpr (MOTION) {
-        // where the surface was one frame ago: d = ((origin + z*nD) - m) - origin_prev (a non-finite m: d is NaN, inr fails, the pixel resets)
-        const V mv = B.plane[P];
-        d0 = has ? ((U.o[0] + z * n0) - mv.x) - U.po[0] : n0;
-        d1 = has ? ((U.o[1] + z * n1) - mv.y) - U.po[1] : n1;
-        d2 = has ? ((U.o[2] + z * n2) - mv.z) - U.po[2] : n2;
-    } else {
-        d0 = has ? (U.o[0] + z * n0) - U.po[0] : n0;
-        d1 = has ? (U.o[1] + z * n1) - U.po[1] : n1;
-        d2 = has ? (U.o[2] + z * n2) - U.po[2] : n2;
-    }
-    const T dw = tp_dot<T>(d0, d1, d2, U.pw);
-    const bool front = dw < T(0);
-    const T lam = U.Kw / dw;
-    const T s = (lam * tp_dot<T>(d0, d1, d2, U.ph) - U.Qh) * U.ih;
-    const T t = (lam * tp_dot<T>(d0, d1, d2, U.pv) - U.Qv) * U.iv;
-    const T x = s * T((int)W) - T(1.5);
-    const T y = (T((int)H) - T(0.5)) - t * T((int)H);
+#include "rtw_temporal_project.inc"
     const bool inr = x > T(-1) && x < T((int)W) && y > T(-1) && y < T((int)H);       // (a NaN fails)
     const T xs = inr ? x : T(0), ys = inr ? y : T(0);
     const T xf = tp_floor(xs), yf = tp_floor(ys);

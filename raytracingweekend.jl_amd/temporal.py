@@ -384,7 +384,7 @@ def temporal_step_animated_into(d_out_ptr, d_state_next_ptr, d_image_ptr, d_feat
                    *(C.c_void_p(int(q)) if q is not None else None for q in ptrs), C.c_void_p(int(stream))))
 
 
-def render_animation(scenes, cams, image_width=400, n_samples=1, *, seeds=None, denoise=None, clamp=None, depth=16, seed=1, n_chunks=0, device=-1, gamma=True,
+def render_animation(scenes, cams, image_width=400, n_samples=1, *, seeds=None, denoise=None, clamp=None, blur=None, depth=16, seed=1, n_chunks=0, device=-1, gamma=True,
                      group_cull=False, scan_valu=False, numerics=None, **params):
     """``len(scenes)`` frames of a scene whose spheres move (and a camera that may), with history reuse across the motion, in one call on
     the device (rtw_render_animation_*): per frame the scene's upload, a linear render, its feature pass, from frame 1 on the motion table
@@ -393,7 +393,10 @@ def render_animation(scenes, cams, image_width=400, n_samples=1, *, seeds=None, 
     accumulated frames; one copy back.  Frame v equals the chain of ``render``, ``render_features``, ``motion_table``, ``first_hit_motion``
     and ``temporal_step_animated`` (and ``denoise_batch``) on the bits.  ``scenes``: HittableLists (or flat dicts) with the spheres in the
     same order; ``cams``: as many cameras; ``seeds``: as many ints (None: ``seed``).  ``clamp``: as ``render_sequence``; other keywords:
-    ``make_temporal``'s.  ``gamma`` is applied once, by the last stage.  Returns ``img[v, i, j, :]``; ``last_stats()`` sums the renders."""
+    ``make_temporal``'s.  ``gamma`` is applied once, by the last stage.  Returns ``img[v, i, j, :]``; ``last_stats()`` sums the renders.
+    ``blur`` (True, or a dict of ``make_motion_blur``'s keywords ``taps, shutter, depth_extent``): the motion-blur stage behind the last linear
+    stage of every frame from 1 on (rtw_render_blurred_*; frame 0 has no previous camera and passes through) -- frame v is then
+    ``motion_blur`` of frame v of the same call with ``gamma=False``, on the bits."""
     scenes = list(scenes)
     cams, T = _batch_cameras(cams)
     n = len(cams)
@@ -415,9 +418,17 @@ def render_animation(scenes, cams, image_width=400, n_samples=1, *, seeds=None, 
                           (_capi.FLAG_GROUP_CULL if group_cull else 0) | (_capi.FLAG_SCAN_VALU if scan_valu else 0), numerics=numerics)
     out = np.empty(n * height * int(image_width) * 3, dtype=T)
     L = _capi.lib()
-    fn = getattr(L, "rtw_render_animation_" + ("f64" if _capi.is_f64(T) else "f32"))
+    tail = []
+    if blur:
+        from .motion_blur import _BLUR_KEYS, make_motion_blur
+        bk = {} if blur is True else dict(blur)
+        if set(bk) - set(_BLUR_KEYS):
+            raise ValueError(f"blur takes the keywords {_BLUR_KEYS}, got {sorted(set(bk) - set(_BLUR_KEYS))}")
+        B = make_motion_blur(gamma=gamma, **bk)
+        tail = [C.byref(B)]
+    fn = getattr(L, ("rtw_render_blurred_" if blur else "rtw_render_animation_") + ("f64" if _capi.is_f64(T) else "f32"))
     _capi.check(fn(S, _capi.make_cameras(cams, T), n, sd, C.byref(P), C.byref(tp), C.byref(K) if K is not None else None, C.byref(D) if D is not None else None,
-                   out.ctypes.data_as(C.c_void_p)))
+                   *tail, out.ctypes.data_as(C.c_void_p)))
     del made
     _record_stats(L)
     return out.reshape(n, int(image_width), height, 3).transpose(0, 2, 1, 3)
