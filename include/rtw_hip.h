@@ -1256,6 +1256,91 @@ int rtw_render_blurred_f64(const rtw_scene_f64 *scenes, const rtw_camera_f64 *ca
                                      const rtw_temporal_t *t, const rtw_temporal_clamp_t *c /* may be NULL */, const rtw_denoise_t *d /* may be NULL */,
                                      const rtw_velocity_blur_t *b, double *out);
 
+/* Depth of field: a gather on a finished pinhole frame.  Every stage behind the trace kernel takes its guides from the centre ray of a
+ * pinhole camera; with a real aperture a low-sample frame is noisy exactly where it is out of focus, and there the guides no longer describe
+ * the picture.  So: render through the pinhole, filter and accumulate on that frame, and apply the lens afterwards as a gather on the
+ * finished LINEAR frame, driven by the depth the feature pass already wrote.  The stage is the sibling of the rtw_velocity_blur_* block: the
+ * same place in the chain (behind the last linear stage, in front of the present stage), a caller-owned workspace with a public layout; its
+ * guide is the feature buffer's depth plane.  The focus plane and the aperture become parameters of a cheap pass.
+ *
+ * The definition.  Everything is computed in T; every operation is rounded once, no FMA; quotients and sqrt are the correctly rounded IEEE
+ * ones; three-term sums are grouped (x + y) + z; a tap that does not take part is dropped by a select.  Pixel (i, j) is slot p = j*H + i.
+ * Inputs: a LINEAR image (H*W*3), the features (H*W*8), `cam` and rtw_defocus_t; output: an image (H*W*3) that aliases no input.
+ * clamp01(x) = x > 0 ? (x < 1 ? x : 1) : +0;  min(a, b) = a < b ? a : b;  max(a, b) = a > b ? a : b  (in this argument order: a NaN on the
+ * left gives b).
+ *   Host constants, in binary64 over the camera's fields converted to binary64, each operation rounded once, then rounded once to T:
+ * focus = ((o - llc).w) (per component o - llc, the dot product grouped as above), or focus_dist when that is > 0;  F = T(focus);
+ * K = T((lens_radius * W) / sqrt(hor.hor)), the radius in pixels of the circle of confusion of a point at infinity;  Rm = T(max_radius).
+ * The camera's own lens_radius is not read.  K is measured on the camera's OWN focus plane and does not move with focus_dist: an override f'
+ * with lens radius r equals a camera rebuilt with its focus plane at f' (horizontal and vertical scaled by f'/f) and lens radius r*f'/f.
+ *   Prepare.  valid, cov, has, z, su, tv, D and nD exactly as in the rtw_temporal_* block.  ca = -((nD.x*w.x + nD.y*w.y) + nD.z*w.z) with the
+ * camera's w;  zax = z*ca, the depth along the optical axis.  A `has` pixel with zax > 0:  R = min(K * (|zax - F| / zax), Rm) -- one
+ * difference, one abs, one quotient, one product, one min.  Every other valid pixel (sky; a surface at or behind the eye plane):
+ * R = min(K, Rm).  zc = has ? z : +inf.  Rh = max(R, T(0.5));  w = 1 / (Rh*Rh).  The COC PLANE holds (R, zc, w, 0) at slot p -- 16 or 32
+ * bytes; a pixel that is not valid holds (-1, NaN, 0, 0).
+ *   Tile max.  Tile (a, b) covers rows 16a .. 16a+15 and columns 16b .. 16b+15, clipped to the frame; TH = ceil(H/16), TW = ceil(W/16); its
+ * index is b*TH + a (the tiles of the rtw_velocity_blur_* block).  The TILE PLANE holds ONE element per tile: the greatest R of the tile's
+ * pixels, -1 if none is valid.  A plain maximum: any reduction tree gives the same answer.
+ *   Gather, per valid pixel X = (i, j) with colour c.  RN = the maximum of the tile plane over the up to nine tiles around X's tile that lie in
+ * the frame.  If not RN >= T(0.5): out = c.  Otherwise m = ceil(RN + T(0.5)) - 1 as an integer (at most max_radius), wsum = +0,
+ * sum = (+0, +0, +0), and for dj = -m .. m (outer, ascending), di = -m .. m (inner, ascending), the centre included, the tap q = (i+di, j+dj):
+ *       a tap outside the frame or on a pixel that is not valid is skipped
+ *       dist = sqrt(T(di*di + dj*dj))
+ *       back = zc_q > zc_X                         (a comparison only: no arithmetic is done on an infinity)
+ *       Rh_q = max(R_q, T(0.5));  Rh_X = max(R_X, T(0.5))
+ *       lim = back and Rh_X < Rh_q                 (a tap BEHIND X never spreads further than X's own circle: background does not bleed
+ *                                                   over sharp foreground)
+ *       Re = lim ? Rh_X : Rh_q;  we = lim ? w_X : w_q
+ *       cover = clamp01((Re + T(0.5)) - dist);  a tap with cover not > 0 is skipped
+ *       a = cover*we;  wsum = wsum + a;  sum[k] = sum[k] + a*c_q[k]
+ * out[k] = sum[k] / wsum (the centre tap always has cover = 1, so wsum > 0).  Then sqrt per channel if gamma = 1 (the pass-through pixels
+ * too).  A pixel that is not valid is a quiet NaN in all three channels.  (tests/defocus_ref.py restates all of this on the CPU, twice, and
+ * the device agrees on the bits.)
+ *   Workspace.  Caller-owned, rtw_defocus_work_bytes(width, height, elem_bytes) bytes (monotone in the size; < 0: an error code), 16-byte
+ * aligned: the CoC plane at byte 0, the tile plane at byte 4*W*H*sizeof(T), TH*TW elements rounded up to a multiple of four.  The layout
+ * is public, like the state's.
+ *
+ * rtw_defocus_device_*: TWO launches (prepare and tile max: a workgroup per tile; the gather: a workgroup per tile over a window staged once
+ * in LDS), asynchronous on `hip_stream` of the device b->device (-1: the current one); rtw_stats() is left alone.  d_features and d_work
+ * are 16-byte aligned, d_image and d_out aligned to T; d_out and d_work alias neither each other nor any input.
+ *   rtw_defocus_*: the host-buffer form, blocking, through the cached per-device context like rtw_velocity_blur_f32.
+ *   rtw_render_defocused_*: the scene, the camera AS THE USER BUILT IT (with its aperture), the render's params, an optional filter and the
+ * defocus: the render and the feature pass over all effective chunks run through a copy of the camera with lens_radius = 0, the filter (if
+ * `d` is not NULL) follows, all with gamma 0; then the two launches above with gamma = p->gamma (b->gamma and b->device are replaced by
+ * p's); ONE D2H.  Here and only here b->lens_radius == -1 means "the camera's own".  The result equals, on the bits, the chain of the
+ * single calls on the pinhole copy -- rtw_render_* (or rtw_render_denoised_*) with gamma 0 and rtw_render_features_* -- followed by
+ * rtw_defocus_*.  rtw_stats() afterwards reports the render's record.
+ *   Refusals, all decided before any HIP call: a null argument -> -1 (`d` may be NULL); max_radius outside 1..8, unknown flags, gamma other
+ * than 0 or 1, reserved != 0, device < -1, a lens_radius that is negative or not finite, a focus_dist that is negative or not finite, a
+ * camera whose hor.hor or whose focus in use is not finite and positive, width or height < 1, elem_bytes other than 4 or 8, misaligned or
+ * aliasing pointers -> -2; the denoiser's frame rule -> -5; the one-call form additionally everything rtw_render_features_* (and, with `d`,
+ * rtw_denoise_*) refuses for its arguments, with its code.
+ *   Left out on purpose: batched views; sequence, animation, upsampler and present one-call forms (the device stages
+ * compose on the caller's stream); device lists; the Julia shim; radii beyond 8 px (a half-resolution pass); bokeh shapes; jittered taps.
+ * Additive to ABI 4: detected by symbol lookup. */
+#define RTW_DEFOCUS_MAX_RADIUS 8     /* the largest circle of confusion, in pixels */
+#define RTW_DEFOCUS_TILE 16          /* the tile's edge, in pixels */
+typedef struct {
+    int32_t max_radius;         /* 1..8: where the circle of confusion is clamped, in pixels (default 8) */
+    int32_t flags;              /* 0 */
+    int32_t gamma;              /* 1 = sqrt per channel at the very end, 0 = linear */
+    int32_t device;             /* -1 = current */
+    int32_t reserved[2];        /* 0 */
+    double  lens_radius;        /* >= 0, finite, world units: half the aperture (rtw_render_defocused_* only: -1 = the camera's own) */
+    double  focus_dist;         /* 0 = the camera's own focus plane; > 0, finite: an override */
+} rtw_defocus_t;                /* 40 bytes */
+int64_t rtw_defocus_work_bytes(int32_t width, int32_t height, int32_t elem_bytes);
+int rtw_defocus_device_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features,
+                           void *d_work, void *d_out, void *hip_stream);
+int rtw_defocus_device_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features,
+                           void *d_work, void *d_out, void *hip_stream);
+int rtw_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const float *image, const float *features, float *out);
+int rtw_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const double *image, const double *features, double *out);
+int rtw_render_defocused_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d /* may be NULL */,
+                             const rtw_defocus_t *b, float *out);
+int rtw_render_defocused_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d /* may be NULL */,
+                             const rtw_defocus_t *b, double *out);
+
 /* Present stage: display-ready 8-bit frames from the device.  Every pipeline above ends in T elements in the column-major layout of the
  * render entry points; a window, a PNG or a video encoder wants 8-bit rows.  One kernel clips, rounds, packs and transposes in HBM, and the
  * D2H behind it moves 3 or 4 bytes per pixel instead of 12 or 24.

@@ -41,6 +41,7 @@ from .temporal import (  # noqa: F401
     motion_table, first_hit_motion, first_hit_motion_into, temporal_step_animated, temporal_step_animated_into, render_animation,
 )
 from .motion_blur import make_motion_blur, motion_blur, motion_blur_into, motion_blur_work_bytes  # noqa: F401
+from .defocus import defocus, defocus_into, defocus_work_bytes, make_defocus, render_defocused  # noqa: F401
 from .present import (  # noqa: F401
     make_present, present, present_batch_into, present_bytes, present_into, render_presented, render_presented_batch,
 )
@@ -67,5 +68,6 @@ __all__ = [
     "temporal_path_table", "temporal_step_batch_into", "temporal_noise_batch_into", "TemporalBatchAccumulator", "render_sequences",
     "motion_table", "first_hit_motion", "first_hit_motion_into", "temporal_step_animated", "temporal_step_animated_into", "render_animation",
     "make_motion_blur", "motion_blur_work_bytes", "motion_blur", "motion_blur_into",
+    "make_defocus", "defocus_work_bytes", "defocus", "defocus_into", "render_defocused",
     "make_present", "present_bytes", "present", "present_into", "present_batch_into", "render_presented", "render_presented_batch",
 ]

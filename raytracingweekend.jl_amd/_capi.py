@@ -45,6 +45,8 @@ SYMBOLS = [
     "rtw_render_animation_f32", "rtw_render_animation_f64",
     "rtw_velocity_blur_work_bytes", "rtw_velocity_blur_device_f32", "rtw_velocity_blur_device_f64", "rtw_velocity_blur_f32", "rtw_velocity_blur_f64",
     "rtw_render_blurred_f32", "rtw_render_blurred_f64",
+    "rtw_defocus_work_bytes", "rtw_defocus_device_f32", "rtw_defocus_device_f64", "rtw_defocus_f32", "rtw_defocus_f64",
+    "rtw_render_defocused_f32", "rtw_render_defocused_f64",
     "rtw_present_bytes", "rtw_present_device_f32", "rtw_present_device_f64", "rtw_present_batch_device_f32", "rtw_present_batch_device_f64",
     "rtw_present_f32", "rtw_present_f64", "rtw_render_presented_f32", "rtw_render_presented_f64", "rtw_render_presented_batch_f32",
     "rtw_render_presented_batch_f64",
@@ -143,6 +145,14 @@ class VelocityBlur(C.Structure):
 
 
 assert C.sizeof(VelocityBlur) == 40
+
+
+class Defocus(C.Structure):
+    """rtw_defocus_t"""
+    _fields_ = [(k, C.c_int32) for k in ("max_radius", "flags", "gamma", "device")] + [("reserved", C.c_int32 * 2), ("lens_radius", C.c_double), ("focus_dist", C.c_double)]
+
+
+assert C.sizeof(Defocus) == 40
 
 
 class Present(C.Structure):
@@ -258,6 +268,10 @@ def lib():
         getattr(L, "rtw_velocity_blur_device_" + sfx).argtypes = [C.POINTER(VelocityBlur), C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_velocity_blur_" + sfx).argtypes = [C.POINTER(VelocityBlur), C.POINTER(CamT), C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_render_blurred_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), tp, tc, C.POINTER(Denoise), C.POINTER(VelocityBlur), ptr]
+        df = C.POINTER(Defocus)
+        getattr(L, "rtw_defocus_device_" + sfx).argtypes = [df, C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_defocus_" + sfx).argtypes = [df, C.POINTER(CamT), i32, i32, ptr, ptr, ptr]
+        getattr(L, "rtw_render_defocused_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), C.POINTER(Params), C.POINTER(Denoise), df, ptr]
         pr, dn = C.POINTER(Present), C.POINTER(Denoise)
         getattr(L, "rtw_present_device_" + sfx).argtypes = [pr, i32, i32, ptr, ptr, ptr]
         getattr(L, "rtw_present_batch_device_" + sfx).argtypes = [pr, i32, i32, i32, ptr, ptr, ptr]
@@ -270,6 +284,8 @@ def lib():
     L.rtw_temporal_state_bytes.restype = C.c_int64
     L.rtw_velocity_blur_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_velocity_blur_work_bytes.restype = C.c_int64
+    L.rtw_defocus_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.rtw_defocus_work_bytes.restype = C.c_int64
     L.rtw_history_moment_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_history_moment_bytes.restype = C.c_int64
     L.rtw_reproject_table_bytes.argtypes = [C.c_int32, C.c_int32]

@@ -1,0 +1,128 @@
+// rtw_defocus.hip -- the defocus stage (include/rtw_hip.h rtw_defocus_*): the checks that need no device, the host constants, the workspace's
+// layout, the two launches of its kernels (rtw_defocus.hpp) and the device-resident entry points.
+// (The host-buffer entry points, rtw_defocus_* and rtw_render_defocused_*, live with the other cached-context paths in rtw_render_host.hip.)
+#include "rtw_host.hpp"
+#include "rtw_defocus.hpp"
+
+namespace rtwh {
+
+// the host constants of the definition in binary64, every operation rounded once: the focus distance in use and the circle-of-confusion radius,
+// in pixels, of a point at infinity
+template <typename CamT>
+static void defocus_constants(const rtw_defocus_t *b, const CamT *cam, int32_t width, double *hh, double *focus, double *K) {
+    double q[3], w[3], h[3];
+    for (int k = 0; k < 3; ++k) { q[k] = (double)cam->origin[k] - (double)cam->lower_left_corner[k]; w[k] = cam->w[k]; h[k] = cam->horizontal[k]; }
+    *hh = (h[0] * h[0] + h[1] * h[1]) + h[2] * h[2];
+    *focus = b->focus_dist > 0 ? b->focus_dist : (q[0] * w[0] + q[1] * w[1]) + q[2] * w[2];
+    *K = (b->lens_radius * (double)width) / std::sqrt(*hh);
+}
+
+// Everything about a defocus that is decided without a device and without a pointer.
+template <typename CamT>
+int validate_defocus_t(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, int elem_bytes) {
+    if (!b || !cam) return fail(-1, "null defocus parameters or camera");
+    if (b->max_radius < 1 || b->max_radius > RTW_DEFOCUS_MAX_RADIUS) return fail(-2, "max_radius must be in 1..%d (got %d)", RTW_DEFOCUS_MAX_RADIUS, b->max_radius);
+    if (b->flags != 0) return fail(-2, "unknown defocus flags 0x%x", b->flags);
+    if (b->gamma != 0 && b->gamma != 1) return fail(-2, "gamma must be 0 or 1 (got %d)", b->gamma);
+    if (b->device < -1) return fail(-2, "bad device %d", b->device);
+    if (b->reserved[0] != 0 || b->reserved[1] != 0) return fail(-2, "reserved must be 0");
+    if (!(b->lens_radius >= 0) || !std::isfinite(b->lens_radius)) return fail(-2, "lens_radius must be finite and >= 0");
+    if (!(b->focus_dist >= 0) || !std::isfinite(b->focus_dist)) return fail(-2, "focus_dist must be finite and >= 0 (0: the camera's own focus plane)");
+    if (width < 1 || height < 1) return fail(-2, "width/height must be positive (got %d x %d)", width, height);
+    if (const int64_t rc = rtw_denoise_work_bytes(width, height, elem_bytes); rc < 0) return (int)rc;         // (elem_bytes; the denoiser's frame rule)
+    double hh, focus, K;
+    defocus_constants(b, cam, width, &hh, &focus, &K);
+    if (!(hh > 0) || !std::isfinite(hh)) return fail(-2, "the camera's horizontal vector must have a finite, positive length");
+    if (!(focus > 0) || !std::isfinite(focus)) return fail(-2, "the camera's focus distance (origin - lower_left_corner).w must be finite and positive");
+    return 0;
+}
+int validate_defocus(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height) { return validate_defocus_t(b, cam, width, height, 4); }
+int validate_defocus(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height) { return validate_defocus_t(b, cam, width, height, 8); }
+
+// the workspace: the CoC plane (a 4-element slot per pixel) and the tile plane (one element per tile, rounded up to a 16-byte multiple)
+static long long tiles_of(int32_t width, int32_t height) {
+    return (long long)((height + rtw::DF_TILE - 1) / rtw::DF_TILE) * ((width + rtw::DF_TILE - 1) / rtw::DF_TILE);
+}
+static long long work_bytes(int32_t width, int32_t height, int elem_bytes) { return ((long long)width * height * 4 + ((tiles_of(width, height) + 3) & ~3ll)) * elem_bytes; }
+
+// Enqueue the stage on `stream` of the current device (validate_defocus has accepted the call): TWO launches, no record.
+template <typename T, typename CamT>
+int launch_defocus(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream) {
+    using V = typename rtw::DnVec<T>::type;
+    const unsigned tiles = (unsigned)tiles_of(width, height);                 // (fewer than the frame rule's 8 x 8 ones: one 32-bit grid dimension holds them)
+    double hh, focus, K;
+    defocus_constants(b, cam, width, &hh, &focus, &K);
+    rtw::TpParams<T> U;
+    memset(&U, 0, sizeof U);
+    {
+        T e[32];
+        temporal_table_t(cam, cam, 1, e);             // (the camera as its own previous one: U.pw is its w)
+        memcpy(&U, e, 29 * sizeof(T));
+    }
+    U.W = width; U.H = height;
+    rtw::DfDist<T> tab;
+    for (int dj = 0; dj <= rtw::DF_MAX_RADIUS; ++dj)
+        for (int di = 0; di <= rtw::DF_MAX_RADIUS; ++di) tab.d[dj * (rtw::DF_MAX_RADIUS + 1) + di] = std::sqrt((T)(di * di + dj * dj));
+    const size_t lds = (size_t)(rtw::DF_TILE + 2 * b->max_radius) * rtw::DF_COL * sizeof(T);      // (at most 32 columns: 24 / 48 KB)
+    V *coc = (V *)d_work;
+    T *tile = (T *)(coc + (size_t)width * (size_t)height);
+    // (measurement aid, tools/gpu_defocus.py: events around every launch, reported on stderr -- this one blocks)
+    static const bool profile = aid_flag("RTW_TEMPORAL_PROFILE");
+    struct Events { hipEvent_t e[3] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
+    if (profile) { for (hipEvent_t &x : events.e) HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventRecord(events.e[0], stream)); }
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((rtw::df_prepare<T>), dim3(tiles), dim3(256), 0, stream, U, (T)focus, (T)K, (T)b->max_radius, (const T *)d_image, (const V *)d_features, coc, tile);
+    HIP_TRY(hipGetLastError());
+    if (profile) HIP_TRY(hipEventRecord(events.e[1], stream));
+    hipLaunchKernelGGL((rtw::df_gather<T>), dim3(tiles), dim3(256), lds, stream, width, height, b->max_radius, b->gamma, tab, (const T *)d_image, (const V *)coc, (const T *)tile, (T *)d_out);
+    HIP_TRY(hipGetLastError());
+    if (profile) {
+        float ms[2] = {0, 0};
+        HIP_TRY(hipEventRecord(events.e[2], stream));
+        HIP_TRY(hipEventSynchronize(events.e[2]));
+        for (int k = 0; k < 2; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], events.e[k], events.e[k + 1]));
+        fprintf(stderr, "[rtw defocus] %s %dx%d max_radius=%d prepare_ms=%.5f gather_ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, b->max_radius, ms[0], ms[1]);
+    }
+    return 0;
+}
+
+int launch_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_defocus<float>(b, cam, w, h, img, feat, work, out, st); }
+int launch_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_defocus<double>(b, cam, w, h, img, feat, work, out, st); }
+
+// The device-resident entry point: nulls, the parameters, then the pointers' alignment and aliasing.
+template <typename T, typename CamT>
+int defocus_device(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, void *stream_v) {
+    if (!b || !cam || !d_image || !d_features || !d_work || !d_out) return fail(-1, "null argument");
+    if (int rc = validate_defocus(b, cam, width, height)) return rc;
+    if (((uintptr_t)d_features & 15u) || ((uintptr_t)d_work & 15u)) return fail(-2, "the feature buffer and the workspace must be 16-byte aligned");
+    if (((uintptr_t)d_image & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
+    const size_t n_pix = (size_t)width * (size_t)height;
+    const size_t img_b = n_pix * 3 * sizeof(T), feat_b = n_pix * 8 * sizeof(T), work_b = (size_t)work_bytes(width, height, sizeof(T));
+    if (ranges_overlap(d_out, img_b, d_work, work_b)) return fail(-2, "d_out and d_work may not alias each other");
+    if (ranges_overlap(d_out, img_b, d_image, img_b) || ranges_overlap(d_out, img_b, d_features, feat_b)) return fail(-2, "d_out may not alias an input");
+    if (ranges_overlap(d_work, work_b, d_image, img_b) || ranges_overlap(d_work, work_b, d_features, feat_b)) return fail(-2, "d_work may not alias an input");
+    DeviceGuard guard;
+    if (b->device >= 0) HIP_TRY(hipSetDevice(b->device));
+    return launch_defocus<T>(b, cam, width, height, d_image, d_features, d_work, d_out, (hipStream_t)stream_v);
+}
+
+}  // namespace rtwh
+
+using namespace rtwh;
+
+extern "C" {
+
+int64_t rtw_defocus_work_bytes(int32_t width, int32_t height, int32_t elem_bytes) {
+    if (const int64_t rc = rtw_denoise_work_bytes(width, height, elem_bytes); rc < 0) return rc;             // (elem_bytes, the sizes, the denoiser's frame rule)
+    return work_bytes(width, height, elem_bytes);
+}
+int rtw_defocus_device_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out,
+                           void *hip_stream) {
+    return defocus_device<float>(b, cam, width, height, d_image, d_features, d_work, d_out, hip_stream);
+}
+int rtw_defocus_device_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out,
+                           void *hip_stream) {
+    return defocus_device<double>(b, cam, width, height, d_image, d_features, d_work, d_out, hip_stream);
+}
+
+}  // extern "C"

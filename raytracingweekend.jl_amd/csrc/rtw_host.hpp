@@ -17,6 +17,7 @@
 //   rtw_temporal.hip     temporal reprojection: its checks, the host constants and the one launch of a step for one path or a batch of paths (rtw_temporal.hpp; clamped: rtw_temporal_clamp.hpp), the device-resident entry points
 //   rtw_motion.hip       the first-hit motion pass over moving spheres: its checks, the motion table, the one launch of its kernel (rtw_motion.hpp), the device-resident entry points
 //   rtw_motion_blur.hip  the motion-blur stage on the motion plane: its checks, the workspace, the three launches of its kernels (rtw_motion_blur.hpp), the device-resident entry points
+//   rtw_defocus.hip      the defocus stage (depth of field on the depth plane): its checks, the host constants, the workspace, the two launches of its kernels (rtw_defocus.hpp), the device-resident entry points
 //   rtw_present.hip      the present stage: its checks, the one launch of its kernel (rtw_present.hpp) for one frame or a batch, the device-resident entry points
 //   (rtw_scene_view.hpp: what both launch functions derive from their arguments; rtw_instances.hpp: the one table of the trace kernel's instances)
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
@@ -395,6 +396,16 @@ int launch_motion_blur_f32(const rtw_velocity_blur_t *b, const rtw_camera_f32 *c
 int launch_motion_blur_f64(const rtw_velocity_blur_t *b, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_motion, void *d_work, void *d_out, hipStream_t stream);
 inline int launch_motion_blur_t(const rtw_velocity_blur_t *b, const rtw_camera_f32 *c, const rtw_camera_f32 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *mo, void *work, void *out, hipStream_t st) { return launch_motion_blur_f32(b, c, cp, w, h, img, feat, mo, work, out, st); }
 inline int launch_motion_blur_t(const rtw_velocity_blur_t *b, const rtw_camera_f64 *c, const rtw_camera_f64 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *mo, void *work, void *out, hipStream_t st) { return launch_motion_blur_f64(b, c, cp, w, h, img, feat, mo, work, out, st); }
+
+// rtw_defocus.hip -- the defocus stage (include/rtw_hip.h rtw_defocus_*).  validate_defocus: every check of a defocus that needs neither a device
+// nor a pointer (the camera's focus plane and horizontal extent among them).  launch_defocus: enqueue the stage (TWO launches, no record) on
+// `stream` of the current device; d_work: rtw_defocus_work_bytes bytes.  The camera's lens_radius is not read: the aperture is b->lens_radius.
+int validate_defocus(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height);
+int validate_defocus(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height);
+int launch_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream);
+int launch_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream);
+inline int launch_defocus_t(const rtw_defocus_t *b, const rtw_camera_f32 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_defocus_f32(b, c, w, h, img, feat, work, out, st); }
+inline int launch_defocus_t(const rtw_defocus_t *b, const rtw_camera_f64 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_defocus_f64(b, c, w, h, img, feat, work, out, st); }
 
 // rtw_present.hip -- the present stage (include/rtw_hip.h rtw_present_*).  validate_present: every check of a call that needs neither a device
 // nor a pointer -- the parameters, the frame, n_views (0: one frame; a batch's count through batch_views) and the size of the launch.

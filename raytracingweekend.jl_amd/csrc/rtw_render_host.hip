@@ -721,6 +721,80 @@ int motion_blur_host(const rtw_velocity_blur_t *b, const CamT *cam, const CamT *
     return rc;
 }
 
+// The defocus stage on host buffers (rtw_defocus_*): a leased context of the device like motion_blur_host's, two H2D (the image, the features),
+// the stage's two launches, ONE D2H.  The device buffer holds the two inputs, the output and the workspace, each on a 16-byte boundary.
+// This thread's last render (rtw_stats) is not touched.
+template <typename T, typename CamT>
+int defocus_host(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, const T *image, const T *features, T *out) {
+    if (!b || !cam || !image || !features || !out) return fail(-1, "null argument");
+    if (int rc = validate_defocus(b, cam, width, height)) return rc;
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t n_pix = (size_t)width * (size_t)height;
+    const size_t img_b = n_pix * 3 * sizeof(T), feat_b = n_pix * RTW_FEATURE_CHANNELS * sizeof(T);
+    const size_t work_b = (size_t)rtw_defocus_work_bytes(width, height, (int32_t)sizeof(T));
+    const size_t off_feat = up(img_b), off_out = off_feat + up(feat_b), off_work = off_out + up(img_b), total = off_work + work_b;
+    if (ranges_overlap(out, img_b, image, img_b) || ranges_overlap(out, img_b, features, feat_b)) return fail(-2, "out may not alias an input");
+    DeviceGuard guard;
+    HostLease L;
+    if (int rc = acquire_host(b->device, std::vector<unsigned char>(), &L)) return rc;
+    HostCtx *hc = L.hc;
+    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, total)) return rc;
+    char *base = (char *)hc->d_img;
+    int rc = 0;
+    hipError_t e = hipMemcpyAsync(base, image, img_b, hipMemcpyHostToDevice, hc->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(base + off_feat, features, feat_b, hipMemcpyHostToDevice, hc->stream);
+    if (e != hipSuccess) rc = fail((int)e, "upload of the defocus stage's inputs failed: %s", hipGetErrorString(e));
+    rtw_defocus_t bb = *b;
+    bb.device = hc->device;
+    if (!rc) rc = launch_defocus_t(&bb, cam, width, height, base, base + off_feat, base + off_work, base + off_out, hc->stream);
+    if (!rc) rc = copy_out(hc, base + off_out, out, img_b);
+    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    return rc;
+}
+
+// Render through the pinhole and defocus in one call (rtw_render_defocused_*): the one-device path above.  The render (gamma 0) and the feature
+// pass over all chunks run through a COPY of the camera with lens_radius = 0; with `d` the filter runs with gamma 0 (launch_filtered), without it
+// render and feature pass are enqueued here; then the stage's two launches with p->gamma and the user's aperture (b->lens_radius == -1: the
+// camera's own) into a region behind the denoiser's, ONE D2H.  rtw_stats() reports the render's record.
+template <typename T, typename SceneT, typename CamT>
+int render_host_defocused(const SceneT *scene, const CamT *cam, const rtw_params *p, const rtw_denoise_t *d, const rtw_defocus_t *b, T *out) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !cam || !b || !out) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = validate_features(p, 0, 1, &nch, &cs)) return rc;
+    if (scene->n < 0) return fail(-2, "negative sphere count");
+    if (d) if (int rc = validate_denoise(d, p->width, p->height)) return rc;
+    rtw_defocus_t bb = *b;
+    if (bb.lens_radius == -1) bb.lens_radius = (double)cam->lens_radius;      // (here and only here: the camera's own aperture)
+    if (int rc = validate_defocus(&bb, cam, p->width, p->height)) return rc;
+    bb.gamma = p->gamma != 0;                                                  // (b's gamma and device are judged, then replaced by p's)
+    CamT pin = *cam;
+    pin.lens_radius = 0;
+    DeviceGuard guard;
+    release_last();
+    const DenoiseRegions<T> R(p->width, p->height, 0);
+    const size_t off_df = (R.total + 15) & ~(size_t)15, off_work = off_df + ((R.img_b + 15) & ~(size_t)15);
+    const size_t total = off_work + (size_t)rtw_defocus_work_bytes(p->width, p->height, (int32_t)sizeof(T));
+    RenderRec *frec = nullptr;
+    CtxPtr fctx;
+    const int rc = render_one_device(p->device, scene, p, total, off_df, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+        char *base = (char *)hc->d_img;
+        int rc;
+        if (d) {
+            rc = launch_filtered(hc, q, &pin, 0, nullptr, 0, d, nch, R, rec, rctx, &frec, &fctx);
+        } else {
+            q.gamma = 0;
+            rc = launch_render_t(hc->scene, &pin, 0, nullptr, &q, base, hc->stream, rec, rctx);
+            if (!rc) rc = launch_features_t(hc->scene, &pin, 0, nullptr, &q, 0, nch, base + R.off_feat, hc->stream, &frec, &fctx);
+        }
+        bb.device = hc->device;
+        if (!rc) rc = launch_defocus_t(&bb, &pin, p->width, p->height, base + (d ? R.off_out : 0), base + R.off_feat, base + off_work, base + off_df, hc->stream);
+        return rc;
+    });
+    if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
+    return rc;
+}
+
 // N cameras along a path with history reuse (rtw_render_sequence_*): the one-device path above with a device buffer that holds the linear images
 // (ONE batched render with gamma 0), the features (ONE batched pass over all chunks), the accumulated images (n_views temporal steps in view
 // order, two states ping-pong) and, with `d`, the filtered images and the filter's workspace (ONE batched filter pass); 2 + n_views (+ 1 + levels)
@@ -1157,6 +1231,18 @@ int rtw_velocity_blur_f32(const rtw_velocity_blur_t *b, const rtw_camera_f32 *ca
 int rtw_velocity_blur_f64(const rtw_velocity_blur_t *b, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const double *image, const double *features,
                         const double *motion, double *out) {
     return motion_blur_host<double>(b, cam, cam_prev, width, height, image, features, motion, out);
+}
+int rtw_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const float *image, const float *features, float *out) {
+    return defocus_host<float>(b, cam, width, height, image, features, out);
+}
+int rtw_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const double *image, const double *features, double *out) {
+    return defocus_host<double>(b, cam, width, height, image, features, out);
+}
+int rtw_render_defocused_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, const rtw_defocus_t *b, float *out) {
+    return render_host_defocused<float>(scene, cam, p, d, b, out);
+}
+int rtw_render_defocused_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, const rtw_defocus_t *b, double *out) {
+    return render_host_defocused<double>(scene, cam, p, d, b, out);
 }
 int rtw_render_path_clamped_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                                  const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, float *out) {
