@@ -1476,7 +1476,13 @@ int rtw_stats_devices(int32_t capacity, int32_t *count, int32_t *devices, double
  *          and width * height * 8 raw words.  With E = width * height * 3 (30) or width * height (31): out = per view the E value slots of the
  *          single kernel of op 23 / op 25, launched view by view; then the n_views * E value slots of ONE launch of the batch kernel, view v
  *          at v * E.  tests/test_gpu_accum_filter_batch.py
- *   bits 8-9 of `op`: the numerics mode of the ray-sphere test for ops 0, 8 - 11, 13, 14, 17 - 20, 26, 27 (0 reference, 1 contract, 3 reference_fma2; 2 is rejected)  */
+ *   Ops 32 - 35 are the candidate sinks 17 - 20 with a flush counter (scenes of at most 512 spheres; per item like ops 17 - 20: the scans of ops 10,
+ *          11, 13, 14 in turn).  in: o[3], d[3], tmin, tmax.  out: the 18 slots of the sink and one raw uint64 of four 16-bit counts: how often a
+ *          full candidate list was resolved early during this ray's scan -- bits 0-15 A (the block loop of the matrix-pipe scan), 16-31 B (its
+ *          in-lane filter class, group cull), 32-47 C (the explode loop of its pass 2): ops 34 and 35; bits 48-63 D (the all-VALU scan, op 32)
+ *          or E (the all-VALU cull scan, op 33: the lane's own count; A - D are the wave's, in every live row alike).  36 is the first number
+ *          behind the last op.  tests/test_gpu_list_caps.py
+ *   bits 8-9 of `op`: the numerics mode of the ray-sphere test for ops 0, 8 - 11, 13, 14, 17 - 20, 26, 27, 32 - 35 (0 reference, 1 contract, 3 reference_fma2; 2 is rejected)  */
 int rtw_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene,
                  const rtw_camera_f32 *cam);
 int rtw_unit_f64(int op, int count, const void *in, void *out, const rtw_scene_f64 *scene,

@@ -73,6 +73,13 @@ struct NoClock { static constexpr bool on() { return false; } __device__ __force
 //   caller's index) was listed for pass 2 / tested by the lane itself.  `lane` is the lane whose ray it is (hit_world_mfma: the owner).
 //   blocks(lane, base, v0, v1)   group cull on the matrix pipe: the vote of the group of 32 blocks that starts at block `base` -- v0 / v1: the
 //   sets the first / second half wave voted for (bit b: block base + b); every lane calls it once per group, right behind the vote.
+//   flush(lane, kind)   a full candidate list is being resolved early, in the middle of the scan (kind: RTW_FLUSH_*): every lane of the wave calls it
+//   for itself right in front of the resolve -- hit_world_cull (E) excepted, where the resolve is the lane's own and only that lane calls.
+#define RTW_FLUSH_A 0       // hit_world_mfma, block loop: total + 64 > WaveScratch::cap when a block records
+#define RTW_FLUSH_B 1       // hit_world_mfma, in-lane filter class (group cull): the same condition when a member records
+#define RTW_FLUSH_C 2       // resolve_pairs_impl, explode loop: total + 64 > WaveScratch::cap2 in front of a bit iteration
+#define RTW_FLUSH_D 3       // hit_world: some lane's list holds RTW_LIST_CAP entries while candidates are still waiting
+#define RTW_FLUSH_E 3       // hit_world_cull: the lane's own list holds RTW_LIST_CAP entries at a push (D and E never meet in one scan)
 struct NoSink {
     static constexpr bool on() { return false; }
     unsigned self = 0;
@@ -80,6 +87,7 @@ struct NoSink {
     __device__ __forceinline__ void cand(unsigned, int) {}
     __device__ __forceinline__ void inlane(unsigned, int) {}
     __device__ __forceinline__ void blocks(unsigned, int, unsigned, unsigned) {}
+    __device__ __forceinline__ void flush(unsigned, int) {}
 };
 
 // src/hit.jl:38-50 -- closest hit by linear scan over ALL spheres; `closest` shrinks; a later
@@ -258,6 +266,7 @@ __device__ __forceinline__ int hit_world(const DevScene<T> &w, SRC src, V3<T> o,
             while (__any(m != 0u)) {
                 if (__any(cnt >= RTW_LIST_CAP)) {     // some lane's list is full: resolve all lists now
                     clk.lap(4);
+                    if constexpr (SINK::on()) sink.flush(sink.self, RTW_FLUSH_D);
                     resolve_candidates<T, STRIDE>(w.numerics, src, w.mat0, o, d, tmin, closest, idx, list, cnt);
                     cnt = 0;
                     clk.lap(5);

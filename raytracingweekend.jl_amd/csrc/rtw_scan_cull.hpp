@@ -105,6 +105,7 @@ __device__ __forceinline__ int hit_world_cull(const CullScene<T> &w, SRC src, OR
     int idx = -1, cnt = 0;
     auto push = [&](int i) {                       // lane-local: may run in divergent code
         if (cnt >= RTW_LIST_CAP) {
+            if constexpr (SINK::on()) sink.flush(sink.self, RTW_FLUSH_E);
             resolve_candidates_anyorder<T, STRIDE>(w.numerics, src, w.mat0, orig, o, d, tmin, closest, idx, list, cnt);
             cnt = 0;
         }

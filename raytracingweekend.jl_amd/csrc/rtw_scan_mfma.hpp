@@ -211,6 +211,7 @@ __device__ __forceinline__ void resolve_pairs_impl(int num, SRC src, [[maybe_unu
             if (prof) prof[2] += 1u;                                   // (phase-profile build: iterations of this loop)
             if (!act) break;
             if (total + 64u > ws.cap2) {
+                if constexpr (SINK::on()) sink.flush(lane, RTW_FLUSH_C);
                 __builtin_amdgcn_wave_barrier();
                 test_singles<T, WITH_R>(num, src, rad, o, d, tmin, ws, singles, total, lane, orig, prof, sink);
                 __builtin_amdgcn_wave_barrier();
@@ -447,7 +448,7 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
             const bool cand = has_ray && !(disc_ < T(0));
             const unsigned long long cm = __ballot(cand);
             if (cm) {
-                if (total + 64u > ws.cap) { resolve_pairs<T>(w.numerics, src, rad, o, d, tmin, ws, total, lane, orig, nullptr, sink); total = 0; }
+                if (total + 64u > ws.cap) { if constexpr (SINK::on()) sink.flush(lane, RTW_FLUSH_B); resolve_pairs<T>(w.numerics, src, rad, o, d, tmin, ws, total, lane, orig, nullptr, sink); total = 0; }
                 if (cand) {
                     // the entry a recording lane (H, j) would write for ray j + 32 half and sphere 32 block + 16 H + register: H, block, register from
                     // the sphere, j and the half from this lane
@@ -597,6 +598,7 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
         clk.count(27, 1u);                                                             // blocks that record entries
         if (total + 64u > ws.cap) {
             clk.lap(4);
+            if constexpr (SINK::on()) sink.flush(lane, RTW_FLUSH_A);
             { unsigned pr[3] = {0u, 0u, 0u}; resolve_pairs<T>(w.numerics, src, rad, o, d, tmin, ws, total, lane, orig, clk.on() ? pr : nullptr, sink); clk.count(13, total); clk.count(14, pr[0]); clk.count(15, pr[1]); clk.count(28, pr[2]); }
             total = 0;
             clk.lap(5);

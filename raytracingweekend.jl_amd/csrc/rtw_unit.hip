@@ -1,7 +1,9 @@
 // rtw_unit.hip -- the T0 unit entry points (rtw_unit_f32/_f64): host slots -> device -> unit_kernel (rtw_units.hpp) -> host slots
 // Per-item ops with a scene: 8 - 11, 13, 14, 26 (scans and the bounce), 17 - 20 (candidate sinks, rows of RTW_SINK_SLOTS slots, scenes of at most
 // RTW_SINK_SPHERES spheres), 27 (op 20's sink plus the block vote: rows of RTW_VOTE_SLOTS slots), 28 (the cull layout: item p = device position p;
-// the caller's index or -1, in-lane, positions, blocks).  24 and 29 are not ops.
+// the caller's index or -1, in-lane, positions, blocks), 32 - 35 (ops 17 - 20 plus a flush counter: rows of RTW_FLUSH_SLOTS slots, the last one a raw
+// uint64 of four 16-bit counts of early resolves -- bits 0-15 A, 16-31 B, 32-47 C of hit_world_mfma (ops 34, 35), bits 48-63 D of hit_world (op 32) or E
+// of hit_world_cull (op 33); RTW_FLUSH_* in rtw_scan.hpp).  24 and 29 are not ops; 36 is the first number behind the last op.
 #include "rtw_scene_view.hpp"
 #include "rtw_units.hpp"
 
@@ -17,6 +19,7 @@ int run_unit(int op_arg, int count, const void *in, void *out, const SceneT *sce
     if (count < 0 || (count > 0 && (!in || !out))) return fail(-1, "null argument");
     if (count == 0) return 0;
     const bool sink = rtw::unit_is_sink(op);
+    const int sop = rtw::unit_sink_of(op);       // (a flush op runs its sink op's scan on the same buffers)
     const bool needs_scene = op == rtw::U_HIT_WORLD || op == rtw::U_RAY_COLOR || op == rtw::U_HIT_WORLD_LDS || op == rtw::U_HIT_WORLD_CULL || op == rtw::U_HIT_WORLD_MFMA || op == rtw::U_HIT_WORLD_MFMA_CULL || op == rtw::U_SHADE || op == rtw::U_CULL_LAYOUT || sink;
     if (needs_scene && !scene) return fail(-1, "op %d needs a scene", op);
     if (sink && scene->n > RTW_SINK_SPHERES) return fail(-5, "unit op %d: the candidate sets hold %d spheres, the scene has %d", op, RTW_SINK_SPHERES, scene->n);
@@ -44,10 +47,10 @@ int run_unit(int op_arg, int count, const void *in, void *out, const SceneT *sce
     if (cam) C = device_camera<T>(*cam);
     using V4 = typename rtw::Vec4<T>::type;
     size_t lds_bytes = 0;
-    if (op == rtw::U_HIT_WORLD_LDS || op == rtw::U_HIT_WORLD_MFMA || op == rtw::U_SINK_LDS || op == rtw::U_SINK_MFMA) lds_bytes = (size_t)rtw::scene_geom_alloc(S.n, S.n_pad) * sizeof(V4);
-    if ((op == rtw::U_HIT_WORLD_MFMA || op == rtw::U_SINK_MFMA) && !S.mf_ops) return fail(-5, "the scene has no matrix-pipe scan operands (unit op %d)", op);
-    if ((op == rtw::U_HIT_WORLD_MFMA_CULL || op == rtw::U_SINK_MFMA_CULL || op == rtw::U_SINK_MFMA_CULL_VOTE || op == rtw::U_CULL_LAYOUT) && !CS.mf_ops) return fail(-5, "the scene has no matrix-pipe cull operands (unit op %d)", op);
-    if (op == rtw::U_HIT_WORLD_CULL || op == rtw::U_HIT_WORLD_MFMA_CULL || op == rtw::U_SINK_CULL || op == rtw::U_SINK_MFMA_CULL || op == rtw::U_SINK_MFMA_CULL_VOTE) {
+    if (op == rtw::U_HIT_WORLD_LDS || op == rtw::U_HIT_WORLD_MFMA || sop == rtw::U_SINK_LDS || sop == rtw::U_SINK_MFMA) lds_bytes = (size_t)rtw::scene_geom_alloc(S.n, S.n_pad) * sizeof(V4);
+    if ((op == rtw::U_HIT_WORLD_MFMA || sop == rtw::U_SINK_MFMA) && !S.mf_ops) return fail(-5, "the scene has no matrix-pipe scan operands (unit op %d)", op);
+    if ((op == rtw::U_HIT_WORLD_MFMA_CULL || sop == rtw::U_SINK_MFMA_CULL || op == rtw::U_SINK_MFMA_CULL_VOTE || op == rtw::U_CULL_LAYOUT) && !CS.mf_ops) return fail(-5, "the scene has no matrix-pipe cull operands (unit op %d)", op);
+    if (op == rtw::U_HIT_WORLD_CULL || op == rtw::U_HIT_WORLD_MFMA_CULL || sop == rtw::U_SINK_CULL || sop == rtw::U_SINK_MFMA_CULL || op == rtw::U_SINK_MFMA_CULL_VOTE) {
         const size_t n_cull = (size_t)rtw::cull_exact_count(CS);
         lds_bytes = n_cull * sizeof(V4) + ((n_cull * sizeof(unsigned short) + 15) / 16) * 16;
     }

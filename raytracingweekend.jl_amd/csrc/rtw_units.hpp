@@ -2,6 +2,9 @@
 // one reference function on one input, using exactly the device functions the trace kernel
 // uses.  All I/O is in 8-byte slots: doubles for real values (exact for binary32 inputs),
 // raw uint64 for RNG state words.  Slot layouts are documented in tests/test_gpu_units.py.
+// Ops 32-35 (U_FLUSH_*): the candidate sinks of ops 17-20 with one more raw-uint64 slot per ray, four 16-bit counts of the early resolves of
+// a full candidate list during that ray's scan -- bits 0-15 A, 16-31 B, 32-47 C (hit_world_mfma: ops 34, 35), bits 48-63 D (hit_world: op 32)
+// or E (hit_world_cull: op 33); the kinds are RTW_FLUSH_* of rtw_scan.hpp.  36 is the first number behind the last op; 24 and 29 are no ops.
 #pragma once
 #include "rtw_device.hpp"
 
@@ -17,7 +20,7 @@ enum UnitOp {
     U_HIT_WORLD_MFMA_CULL = 14,   // hit_world_mfma with block culling (RTW_FLAG_GROUP_CULL on the matrix pipe), cull layout staged in LDS
     U_NEAR_ZERO = 15,        // near_zero(v) (src/vec.jl:20): squared length against the Float64 literal 1e-5
     U_EXACT_MATH = 16,       // t_sqrt / t_rcp against the compiler's IEEE sqrt / division on a RANGE of binary32 bit patterns (Float32 only)
-    // pass-1 candidate sinks: the scans of ops 10, 11, 13, 14 with a CandSink -- per ray what pass 2 was handed instead of the hit (scenes of <= 512 spheres)
+    // pass-1 candidate sinks (and ops 32-35, below: the same with a count of the early resolves): the scans of ops 10, 11, 13, 14 with a CandSink -- per ray what pass 2 was handed instead of the hit (scenes of <= 512 spheres)
     U_SINK_LDS = 17, U_SINK_CULL = 18, U_SINK_MFMA = 19, U_SINK_MFMA_CULL = 20,
     // the accumulator's tile kernels on hand-made words (rtw_accum_kernels.hip accum_unit; whole-call layouts, not per item: include/rtw_hip.h): the
     // stopping rule's two check kernels, the two compactions, the per-tile resolve.  rtw_unit.hip hands them over before its per-item path.
@@ -36,15 +39,22 @@ enum UnitOp {
     // (29 is not an op either: the first number behind op 28 stays the unknown one callers probe)
     // the batched per-tile resolve and the batched noise map on hand-made words and C_t, N views in ONE launch next to the single kernels view by view (rtw_accum_kernels.hip accum_unit)
     U_ACCUM_RESOLVE_BATCH = 30, U_ACCUM_NOISE_BATCH = 31,
-    U_NUM_OPS = 32
+    // the sinks of ops 17-20 with a flush counter: RTW_SINK_SLOTS slots as there, then one raw uint64 of four 16-bit counts -- how often a full candidate
+    // list was resolved early during this ray's scan (NoSink::flush, rtw_scan.hpp), field RTW_FLUSH_*: bits 0-15 A, 16-31 B, 32-47 C (ops 34, 35), bits
+    // 48-63 D (op 32) or E (op 33).  A - D are the wave's and stand in every live row alike; E is the lane's own.
+    U_FLUSH_LDS = 32, U_FLUSH_CULL = 33, U_FLUSH_MFMA = 34, U_FLUSH_MFMA_CULL = 35,
+    U_NUM_OPS = 36
 };
 __host__ __device__ inline bool unit_is_accum(int op) {
     return (op >= U_ACCUM_TILE_CHECK && op <= U_ACCUM_RESOLVE_TILES) || op == U_ACCUM_NOISE || op == U_ACCUM_RESOLVE_BATCH || op == U_ACCUM_NOISE_BATCH;
 }
-__host__ __device__ inline bool unit_is_sink(int op) { return (op >= U_SINK_LDS && op <= U_SINK_MFMA_CULL) || op == U_SINK_MFMA_CULL_VOTE; }
+__host__ __device__ inline bool unit_is_flush(int op) { return op >= U_FLUSH_LDS && op <= U_FLUSH_MFMA_CULL; }
+__host__ __device__ inline bool unit_is_sink(int op) { return (op >= U_SINK_LDS && op <= U_SINK_MFMA_CULL) || op == U_SINK_MFMA_CULL_VOTE || unit_is_flush(op); }
+__host__ __device__ inline int unit_sink_of(int op) { return unit_is_flush(op) ? op - U_FLUSH_LDS + U_SINK_LDS : op; }      // the sink op whose scan a flush op runs
 #define RTW_SINK_SPHERES 512
 #define RTW_SINK_SLOTS 18
 #define RTW_VOTE_SLOTS (RTW_SINK_SLOTS + 1)
+#define RTW_FLUSH_SLOTS (RTW_SINK_SLOTS + 1)
 
 __host__ __device__ inline int unit_in_slots(int op) {
     switch (op) {
@@ -60,6 +70,7 @@ __host__ __device__ inline int unit_in_slots(int op) {
         case U_EXACT_MATH: return 2;    // first bit pattern, number of consecutive patterns
         case U_HIT_WORLD: case U_HIT_WORLD_LDS: case U_HIT_WORLD_CULL: case U_HIT_WORLD_MFMA: case U_HIT_WORLD_MFMA_CULL: return 8;     // o[3], d[3], tmin, tmax
         case U_SINK_LDS: case U_SINK_CULL: case U_SINK_MFMA: case U_SINK_MFMA_CULL: case U_SINK_MFMA_CULL_VOTE: return 8;             // (the same)
+        case U_FLUSH_LDS: case U_FLUSH_CULL: case U_FLUSH_MFMA: case U_FLUSH_MFMA_CULL: return 8;                                    // (the same)
         case U_CULL_LAYOUT: return 1;   // (ignored)
         case U_RAY_COLOR: return 9;     // state[2], o[3], d[3], depth
         case U_FX_SUM: return 8;        // 8 binary64 values
@@ -82,6 +93,7 @@ __host__ __device__ inline int unit_out_slots(int op) {
         case U_HIT_WORLD: case U_HIT_WORLD_LDS: case U_HIT_WORLD_CULL: case U_HIT_WORLD_MFMA: case U_HIT_WORLD_MFMA_CULL: return 9;     // idx, t, p[3], n[3], front
         case U_SINK_LDS: case U_SINK_CULL: case U_SINK_MFMA: case U_SINK_MFMA_CULL: return RTW_SINK_SLOTS;   // ok, mf_sc, cand bits[8], in-lane bits[8] (raw uint64)
         case U_SINK_MFMA_CULL_VOTE: return RTW_VOTE_SLOTS;   // op 20's slots, voted blocks (raw uint64)
+        case U_FLUSH_LDS: case U_FLUSH_CULL: case U_FLUSH_MFMA: case U_FLUSH_MFMA_CULL: return RTW_FLUSH_SLOTS;   // the sink's slots, early resolves (raw uint64: 4 x 16 bits)
         case U_CULL_LAYOUT: return 4;   // the caller's index or -1, in-lane, positions, blocks
         case U_RAY_COLOR: return 6;     // state[2], colour[3], segments
         case U_FX_SUM: return 2;        // sum, poisoned
@@ -102,7 +114,9 @@ __device__ __forceinline__ double as_f64(uint64_t u) { return __longlong_as_doub
 // the lane that runs a candidate's exact test is not its owner): global atomic ORs.
 // Op 27 (SLOTS = RTW_VOTE_SLOTS): the same rows with one more slot, the blocks the ray's half wave voted for (blocks(): every lane records into its
 // OWN row what its half of the wave-uniform vote words says).
-template <int SLOTS>
+// Ops 32-35 (SLOTS = RTW_FLUSH_SLOTS, FLUSH_SLOT = RTW_SINK_SLOTS): the same rows with one more slot, four 16-bit counts of early resolves (flush():
+// the lane adds 1 to field `kind` of its OWN row; the other sinks count nothing).
+template <int SLOTS, int FLUSH_SLOT = -1>
 struct CandSinkT {
     double *rows;          // the wave's first row
     unsigned n_live;       // rows of the wave (lanes beyond have no ray and no row)
@@ -118,14 +132,20 @@ struct CandSinkT {
     __device__ void cand(unsigned lane, int i) { bit(lane, 2, i); }
     __device__ void inlane(unsigned lane, int i) { bit(lane, 10, i); }
     __device__ void blocks(unsigned lane, int base, unsigned v0, unsigned v1) {
-        if constexpr (SLOTS > RTW_SINK_SLOTS) {
+        if constexpr (SLOTS > RTW_SINK_SLOTS && FLUSH_SLOT < 0) {
             if (lane < n_live && (unsigned)base < 64u)
                 atomicOr(reinterpret_cast<unsigned long long *>(rows + lane * SLOTS + RTW_SINK_SLOTS), (unsigned long long)(lane < 32u ? v0 : v1) << base);
+        }
+    }
+    __device__ void flush(unsigned lane, int kind) {
+        if constexpr (FLUSH_SLOT >= 0) {
+            if (lane < n_live) atomicAdd(reinterpret_cast<unsigned long long *>(rows + lane * SLOTS + FLUSH_SLOT), 1ull << (16 * kind));
         }
     }
 };
 using CandSink = CandSinkT<RTW_SINK_SLOTS>;
 using VoteSink = CandSinkT<RTW_VOTE_SLOTS>;
+using FlushSink = CandSinkT<RTW_FLUSH_SLOTS, RTW_SINK_SLOTS>;
 
 template <typename T>
 __global__ void unit_kernel(int op, int count, const double *__restrict__ in, double *__restrict__ out,
@@ -142,6 +162,7 @@ __global__ void unit_kernel(int op, int count, const double *__restrict__ in, do
     const int wave0 = gid - (int)(threadIdx.x & 63u);
     const CandSink sink = {out + (size_t)wave0 * RTW_SINK_SLOTS, (unsigned)(count - wave0 < 64 ? count - wave0 : 64), threadIdx.x & 63u};   // (ops 17-20)
     const VoteSink vsink = {out + (size_t)wave0 * RTW_VOTE_SLOTS, sink.n_live, sink.self};                                                   // (op 27)
+    const FlushSink fsink = {out + (size_t)wave0 * RTW_FLUSH_SLOTS, sink.n_live, sink.self};                                                 // (ops 32-35)
     if (!coop && !live) return;
     switch (op) {
         case U_HIT_SPHERE: {
@@ -301,26 +322,31 @@ __global__ void unit_kernel(int op, int count, const double *__restrict__ in, do
                 y[1] = (double)rec.t; st3(y + 2, rec.p); st3(y + 5, rec.n); y[8] = rec.front ? 1.0 : 0.0;
             }
         } break;
-        case U_SINK_LDS: case U_SINK_CULL: {
+        case U_SINK_LDS: case U_SINK_CULL: case U_FLUSH_LDS: case U_FLUSH_CULL: {
             V4 *lds_geom = reinterpret_cast<V4 *>(u_smem);
-            unsigned short *lds_orig = reinterpret_cast<unsigned short *>(lds_geom + (op == U_SINK_CULL ? cull_exact_count(cull) : 0));
-            if (op == U_SINK_CULL) stage_cull_scene<T>(cull, lds_geom, lds_orig); else stage_scene<T>(scene, lds_geom);
+            const bool culled = unit_sink_of(op) == U_SINK_CULL;
+            unsigned short *lds_orig = reinterpret_cast<unsigned short *>(lds_geom + (culled ? cull_exact_count(cull) : 0));
+            if (culled) stage_cull_scene<T>(cull, lds_geom, lds_orig); else stage_scene<T>(scene, lds_geom);
             __syncthreads();
             V3<T> o = {0, 0, 0}, d = {0, 0, 1};
             T tmn = 0, tmx = 0;
             if (live) { o = ld3<T>(x); d = ld3<T>(x + 3); tmn = (T)x[6]; tmx = (T)x[7]; }
             T t_hit;
-            if (op == U_SINK_CULL)
+            if (op == U_FLUSH_CULL)
+                hit_world_cull<T, 64>(cull, (const V4 *)lds_geom, (const unsigned short *)lds_orig, o, d, tmn, tmx, t_hit, my_list, NoClock(), fsink);
+            else if (op == U_FLUSH_LDS)
+                hit_world<T, 64>(scene, (const V4 *)lds_geom, o, d, tmn, tmx, t_hit, my_list, NoClock(), fsink);
+            else if (op == U_SINK_CULL)
                 hit_world_cull<T, 64>(cull, (const V4 *)lds_geom, (const unsigned short *)lds_orig, o, d, tmn, tmx, t_hit, my_list, NoClock(), sink);
             else
                 hit_world<T, 64>(scene, (const V4 *)lds_geom, o, d, tmn, tmx, t_hit, my_list, NoClock(), sink);
         } break;
-        case U_SINK_MFMA: case U_SINK_MFMA_CULL: case U_SINK_MFMA_CULL_VOTE: {
+        case U_SINK_MFMA: case U_SINK_MFMA_CULL: case U_SINK_MFMA_CULL_VOTE: case U_FLUSH_MFMA: case U_FLUSH_MFMA_CULL: {
             __shared__ __attribute__((aligned(8))) unsigned k_pairs[RTW_PAIR_CAP];
             __shared__ unsigned long long k_keys[64];
             __shared__ unsigned k_kidx[64];
             V4 *lds_geom = reinterpret_cast<V4 *>(u_smem);
-            const bool culled = op != U_SINK_MFMA;
+            const bool culled = unit_sink_of(op) != U_SINK_MFMA;
             unsigned short *lds_orig = reinterpret_cast<unsigned short *>(lds_geom + (culled ? cull_exact_count(cull) : 0));
             if (culled) stage_cull_scene<T>(cull, lds_geom, lds_orig); else stage_scene<T>(scene, lds_geom);
             __syncthreads();
@@ -329,7 +355,12 @@ __global__ void unit_kernel(int op, int count, const double *__restrict__ in, do
             const T tmn = (T)in[6];
             T t_hit;
             const WaveScratch ws = {k_pairs, k_keys, k_kidx};
-            if (op == U_SINK_MFMA_CULL_VOTE) {
+            if (op == U_FLUSH_MFMA_CULL) {
+                const MfmaCull mc = mfma_cull_of(cull);
+                hit_world_mfma<T>(scene, (const V4 *)lds_geom, o, d, live, tmn, t_hit, ws, threadIdx.x & 63u, NoClock(), &mc, (const unsigned short *)lds_orig, fsink);
+            } else if (op == U_FLUSH_MFMA) {
+                hit_world_mfma<T>(scene, (const V4 *)lds_geom, o, d, live, tmn, t_hit, ws, threadIdx.x & 63u, NoClock(), nullptr, NoOrig(), fsink);
+            } else if (op == U_SINK_MFMA_CULL_VOTE) {
                 const MfmaCull mc = mfma_cull_of(cull);
                 hit_world_mfma<T>(scene, (const V4 *)lds_geom, o, d, live, tmn, t_hit, ws, threadIdx.x & 63u, NoClock(), &mc, (const unsigned short *)lds_orig, vsink);
             } else if (op == U_SINK_MFMA_CULL) {

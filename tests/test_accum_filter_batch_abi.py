@@ -192,8 +192,8 @@ def test_c_example_compiles_and_links(tmp_path):
 
 
 def test_unit_ops_30_and_31_validate_before_any_hip_call(lib):
-    """the layouts of ops 30 / 31 (include/rtw_hip.h): nulls -> -1; a size or value they do not hold -> -2; 29 stays unknown, 32 is the first
-    number behind the last op"""
+    """the layouts of ops 30 / 31 (include/rtw_hip.h): nulls -> -1; a size or value they do not hold -> -2; 29 stays unknown, 36 is the first
+    number behind the last op (32 - 35: the sinks with a flush counter, tests/test_gpu_list_caps.py)"""
     out = np.zeros(256, np.float64)
     head = np.zeros(8 + 2 * (1 + 8), np.float64)
 
@@ -215,7 +215,7 @@ def test_unit_ops_30_and_31_validate_before_any_hip_call(lib):
             assert call(op, **bad) == -2 and call(op, f32=True, **bad) == -2, (op, bad)
     assert call(30, slot4=2) == -2 and call(30, slot4=0.5) == -2 and call(31, slot4=float("inf")) == -2
     assert unit(29, 1, head, out) == -2 and b"unknown unit op" in lib.rtw_last_error()
-    assert unit(32, 1, head, out) == -2 and b"unknown unit op" in lib.rtw_last_error()
+    assert unit(36, 1, head, out) == -2 and b"unknown unit op" in lib.rtw_last_error()
     if not _has_gpu():
         for rc in (call(30), call(31), call(30, f32=True), call(31, f32=True)):
             assert rc > 0 or rc in (-21, -22), rc

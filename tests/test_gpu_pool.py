@@ -132,3 +132,18 @@ def test_ray_pool_identical_at_1080p(rtw):
     assert sa["segments"] == sb["segments"] and sa["samples"] == sb["samples"] == 1920 * 1080 * 100
     assert bool(torch.equal(a, b)), int((a != b).sum())
     dr.close()
+
+
+@needs_pool
+@all_numerics
+@pytest.mark.parametrize("glass", [False, True], ids=["lambertian", "dielectric"])
+def test_ray_pool_nest_of_200_candidates(oracle, rtw, glass):
+    """the nest of tests/test_gpu_list_caps.py: every ray has ~200 candidates and three exact copies of its closest sphere.  The pool kernel
+    gives a wave half the list area (80 entries, 96 singles), so its lists are resolved early about twice as often."""
+    from test_gpu_list_caps import DEPTH, H, SPP, W, nest, nest_camera
+    T = np.float32
+    scene, cam = nest(rtw, T, glass), nest_camera(rtw, T)
+    ref, ost = oracle.render(rtw.flatten_scene(scene, T), cam, W, H, SPP, T=T, max_depth=DEPTH, seed=3)
+    img = rtw.render(scene, cam, W, SPP, depth=DEPTH, seed=3, ray_pool=True)          # (the pool kernel runs the plain matrix-pipe scan only)
+    assert rtw.last_stats()["block_threads"] == 1024
+    assert np.array_equal(img, ref) and rtw.last_stats()["segments"] == ost["segments"]

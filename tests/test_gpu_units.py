@@ -22,6 +22,12 @@ Slot layouts (8-byte slots: doubles for reals, raw uint64 for RNG state words), 
   op 28 cull layout in (ignored)                           out idx inlane positions blocks
                    (item p = device position p, block p / 32: the caller's index of the sphere there or -1, whether the position is
                    in the in-lane list, the layout's number of positions and of blocks)
+  ops 32-35 flush  in  o[3] d[3] tmin tmax                 out ok mf_sc cand[8] inlane[8] flushes
+                   (the scans and the 18 slots of the candidate sinks 17-20 -- ops 10, 11, 13, 14 in turn -- plus one raw uint64 of four
+                   16-bit counts: how often a full candidate list was resolved early during this ray's scan.  Bits 0-15 A (block loop of
+                   hit_world_mfma), 16-31 B (its in-lane filter class), 32-47 C (the explode loop of its pass 2): ops 34, 35; bits 48-63 D
+                   (hit_world, op 32) or E (hit_world_cull, op 33: the lane's own count; A - D are the wave's and stand in every live
+                   row) -- tests/test_gpu_list_caps.py.  36 is the first number behind the last op.)
 """
 import ctypes as C
 
