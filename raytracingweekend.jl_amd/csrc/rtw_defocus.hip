@@ -1,6 +1,7 @@
 // rtw_defocus.hip -- the defocus stage (include/rtw_hip.h rtw_defocus_*): the checks that need no device, the host constants, the workspace's
 // layout, the two launches of its kernels (rtw_defocus.hpp) and the device-resident entry points.
-// (The host-buffer entry points, rtw_defocus_* and rtw_render_defocused_*, live with the other cached-context paths in rtw_render_host.hip.)
+// (The host-buffer entry points live with the other cached-context paths: rtw_defocus_* in rtw_stage_host.hip, rtw_render_defocused_* in
+// rtw_render_host.hip.)
 #include "rtw_host.hpp"
 #include "rtw_defocus.hpp"
 
@@ -98,9 +99,7 @@ int defocus_device(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32
     if (((uintptr_t)d_image & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
     const size_t n_pix = (size_t)width * (size_t)height;
     const size_t img_b = n_pix * 3 * sizeof(T), feat_b = n_pix * 8 * sizeof(T), work_b = (size_t)work_bytes(width, height, sizeof(T));
-    if (ranges_overlap(d_out, img_b, d_work, work_b)) return fail(-2, "d_out and d_work may not alias each other");
-    if (ranges_overlap(d_out, img_b, d_image, img_b) || ranges_overlap(d_out, img_b, d_features, feat_b)) return fail(-2, "d_out may not alias an input");
-    if (ranges_overlap(d_work, work_b, d_image, img_b) || ranges_overlap(d_work, work_b, d_features, feat_b)) return fail(-2, "d_work may not alias an input");
+    if (int rc = check_alias({{"d_out", d_out, img_b}, {"d_work", d_work, work_b}}, {{"d_image", d_image, img_b}, {"d_features", d_features, feat_b}})) return rc;
     DeviceGuard guard;
     if (b->device >= 0) HIP_TRY(hipSetDevice(b->device));
     return launch_defocus<T>(b, cam, width, height, d_image, d_features, d_work, d_out, (hipStream_t)stream_v);

@@ -1,7 +1,7 @@
 // rtw_denoise.hip -- the feature-guided denoiser (include/rtw_hip.h rtw_denoise_*): the checks that need no device, the launch sequence of
 // its kernels (rtw_denoise.hpp: prepare, then the level kernel once per a-trous pass, the last one writing the image) and the device-resident
 // entry points.  n_views == 0 is one frame; n_views >= 1 (rtw_filter_batch_*) the same sequence once for that many frames (the batched level
-// kernel).  (The host-buffer entry points, rtw_render_denoised_* and rtw_render_filtered_batch_* live with the other cached-context paths in rtw_render_host.hip.)
+// kernel).  (The host-buffer entry points live with the other cached-context paths: rtw_denoise_* and rtw_filter_batch_* in rtw_stage_host.hip, rtw_render_denoised_* and rtw_render_filtered_batch_* in rtw_render_host.hip.)
 #include "rtw_host.hpp"
 #include "rtw_denoise.hpp"
 

@@ -3,8 +3,11 @@
 //                        records behind rtw_stats(): begin_record / run_record, the one sequence around every launch that has a record
 //   rtw_scene.hip        scene upload: SoA rows, kd split of the group-cull layout, the f16-split operands of the matrix-pipe filter
 //   rtw_launch.hip       one render = one launch of the trace kernel (rtw_kernels.hpp / rtw_pool.hpp): geometry, occupancy, job shape, views
-//   rtw_render_host.hip  every host-buffer entry point: cached per-device context (scene, stream, buffer), ONE one-device path (render_one_device) behind render,
-//                        batch, feature, render + filter, render + upsample and render + present calls, the filter, the upsampler and the present stage on host buffers, or a device list
+//   rtw_render_host.hip  the host-buffer entry points that render: the pool of cached per-device contexts (scene, stream, buffer), ONE one-device path (render_one_device)
+//                        behind render, batch, feature and the composite render + stage calls, the motion pass, the accumulator's filtered call, or a device list
+//   rtw_stage_host.hip   the pure stages on host buffers (filter, present, upsampler, temporal step, motion blur, defocus): ONE path (stage_one_device) behind all of them
+//                        (rtw_host_ctx.hpp: what the two share -- the lease of a context, that path and render_one_device on top of it, the regions of the device buffer;
+//                        rtw_layout.hpp: the regions' byte arithmetic and the alias check, plain C++)
 //   rtw_multi.hip        what a device list needs: peer access, the on-demand RCCL binding, the un-tile kernel
 //   rtw_batch_accum_f32.hip / _f64.hip  the BATCH && ACCUM instances of the trace kernel (rtw_instances.hpp: the kernel-instance table), a unit per precision
 //   rtw_features_accum_batch_f32.hip / _f64.hip  the TILED && BATCH instances of the feature kernel (rtw_features.hpp), a unit per precision
@@ -32,9 +35,12 @@
 #include <atomic>
 #include <cmath>
 #include <cstdarg>
+#include <cstddef>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <limits>
 #include <map>
 #include <memory>
@@ -45,6 +51,8 @@
 #include <vector>
 
 #pragma GCC visibility push(hidden)
+
+#include "rtw_layout.hpp"
 
 namespace rtw { struct DevCounters; }      // rtw_kernels.hpp (device side); the host keeps one per render record
 
@@ -263,9 +271,15 @@ int validate_batch(const void *cams, int32_t n_views, const rtw_params *p, const
 // Below the C ABI n_views == 0 is the single-view call and n_views >= 1 a batch of that many.  A batched entry point hands its caller's count
 // down through batch_views: a count that is no batch stays one the batch's validation refuses (-2) and never selects the single-view path.
 inline int32_t batch_views(int32_t n_views) { return n_views < 1 ? -1 : n_views; }
-// do the byte ranges [a, a + na) and [b, b + nb) share a byte?
-inline bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; }
-// (rtw_render_host.hip defines the host-buffer entry points of the C ABI itself: nothing of it is declared here)
+// The alias check of an entry point (rtw_layout.hpp first_alias: the outputs against each other, then against the inputs; absent ranges
+// skipped): the first offending pair is refused with -2.  `input_word`: what an input is called where the call has exactly one.
+inline int check_alias(std::initializer_list<ByteRange> outs, std::initializer_list<ByteRange> ins, const char *input_word = "an input") {
+    const AliasPair hit = first_alias(outs.begin(), (int)outs.size(), ins.begin(), (int)ins.size());
+    if (hit.out < 0) return 0;
+    const char *name = outs.begin()[hit.out].name;
+    return hit.input ? fail(-2, "%s may not alias %s", name, input_word) : fail(-2, "%s and %s may not alias each other", name, outs.begin()[hit.other].name);
+}
+// (rtw_render_host.hip and rtw_stage_host.hip define the host-buffer entry points of the C ABI themselves: nothing of them is declared here)
 
 // rtw_multi.hip
 int ensure_peer(const CtxPtr &ctx, int dev, int root, bool *direct);

@@ -1,0 +1,101 @@
+// rtw_layout.hpp -- byte arithmetic of the host paths, plain C++ (no HIP: a host compiler builds it alone, tests/test_host_layout.py does):
+// the regions of a context's device buffer (DevLayout and the four layouts built with it) and the one alias check over named byte ranges.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace rtwh {
+
+// do the byte ranges [a, a + na) and [b, b + nb) share a byte?
+inline bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) { return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na; }
+
+// Regions of one buffer, one behind the other, each on a 16-byte boundary: add() rounds `total` up to 16, returns that offset and advances
+// `total` past the region.  add(0): the rounded end.  (DevLayout{n}: regions behind the first n bytes.)
+struct DevLayout {
+    size_t total = 0;
+    size_t add(size_t bytes) {
+        const size_t off = (total + 15) & ~(size_t)15;
+        total = off + bytes;
+        return off;
+    }
+};
+
+// ---- the alias check ---------------------------------------------------------------------------------------------
+struct ByteRange { const char *name; const void *ptr; size_t bytes; };      // ptr null: absent, skipped
+// The first offending pair, in this precedence: the outputs in order, each against the outputs behind it, then against the inputs in
+// order.  out < 0: none.  `input`: `other` indexes `ins` (else `outs`).
+struct AliasPair { int out = -1, other = -1; bool input = false; };
+inline AliasPair first_alias(const ByteRange *outs, int n_out, const ByteRange *ins, int n_in) {
+    for (int a = 0; a < n_out; ++a) {
+        if (!outs[a].ptr) continue;
+        for (int b = a + 1; b < n_out; ++b)
+            if (outs[b].ptr && ranges_overlap(outs[a].ptr, outs[a].bytes, outs[b].ptr, outs[b].bytes)) return {a, b, false};
+        for (int b = 0; b < n_in; ++b)
+            if (ins[b].ptr && ranges_overlap(outs[a].ptr, outs[a].bytes, ins[b].ptr, ins[b].bytes)) return {a, b, true};
+    }
+    return {};
+}
+
+// ---- the regions of the stages (`elem`: bytes of an element; the workspace, state and moment sizes are the callers': rtw_*_bytes) ------
+constexpr size_t LAYOUT_FEATURE_CHANNELS = 8;         // RTW_FEATURE_CHANNELS (rtw_host_ctx.hpp asserts it)
+
+// The denoiser's regions: image, features, output, workspace (work_b per frame) -- each holds the frames of a batch one behind the other.
+struct DenoiseLayout {
+    size_t img_b, feat_b, off_feat, off_out, off_work, total;
+    DenoiseLayout(size_t elem, int32_t width, int32_t height, int32_t n_views, size_t work_b) {
+        const size_t frames = n_views ? (size_t)n_views : 1, n = (size_t)width * (size_t)height * frames;
+        img_b = n * 3 * elem; feat_b = n * LAYOUT_FEATURE_CHANNELS * elem;
+        DevLayout L;
+        L.add(img_b); off_feat = L.add(feat_b); off_out = L.add(img_b); off_work = L.add(work_b * frames);
+        total = L.total;
+    }
+};
+
+// The upsampler's regions: small image, small features, full features, output, workspace (work_b per frame) -- frames as above.
+struct UpsampleLayout {
+    size_t img_b, flo_b, fhi_b, out_b, off_flo, off_fhi, off_out, off_work, total;
+    UpsampleLayout(size_t elem, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, size_t work_b) {
+        const size_t frames = n_views ? (size_t)n_views : 1, n_lo = (size_t)lo_width * (size_t)lo_height * frames, n_hi = (size_t)width * (size_t)height * frames;
+        img_b = n_lo * 3 * elem; flo_b = n_lo * LAYOUT_FEATURE_CHANNELS * elem; fhi_b = n_hi * LAYOUT_FEATURE_CHANNELS * elem; out_b = n_hi * 3 * elem;
+        DevLayout L;
+        L.add(img_b); off_flo = L.add(flo_b); off_fhi = L.add(fhi_b); off_out = L.add(out_b); off_work = L.add(work_b * frames);
+        total = L.total;
+    }
+};
+
+// The regions of the temporal paths: the linear images and the features of `frames` views, the accumulated images, (filter: the filtered
+// images,) two states, (filter: the denoiser's workspace, work_b per frame).  `paths` >= 1 (rtw_render_paths_*): each of the two states
+// (state_b bytes per path) is a SET of that many, one behind the other.  Without `filter` off_flt and off_work are where those regions would start.
+struct TemporalLayout {
+    size_t frame_b, img_b, feat_b, st_b, off_feat, off_acc, off_flt, off_st[2], off_work, total;
+    TemporalLayout(size_t elem, int32_t width, int32_t height, size_t frames, bool filter, size_t paths, size_t state_b, size_t work_b) {
+        const size_t n = (size_t)width * (size_t)height;
+        frame_b = n * 3 * elem; img_b = frame_b * frames; feat_b = n * LAYOUT_FEATURE_CHANNELS * elem * frames;
+        st_b = state_b * paths;
+        DevLayout L;
+        L.add(img_b); off_feat = L.add(feat_b); off_acc = L.add(img_b); off_flt = L.add(filter ? img_b : 0);
+        off_st[0] = L.add(st_b); off_st[1] = L.add(st_b); off_work = L.add(filter ? work_b * frames : 0);
+        total = L.total;
+    }
+};
+
+// The regions of the temporal paths with moments: TemporalLayout, then two moment planes (moment_b bytes per path; sets of `paths`) and the
+// noise maps of `frames` views: total_m bytes.  The table of the `frames` steps' camera constants (rtw_reproject_table_*) lies behind
+// everything else: total_p bytes, with `moments`' regions or without them.
+struct MomentLayout : TemporalLayout {
+    size_t mo_b, noise_b, off_mo[2], off_noise, total_m, tab_b, off_tab, total_p;
+    MomentLayout(size_t elem, int32_t width, int32_t height, size_t frames, bool filter, size_t paths, bool moments, size_t state_b, size_t work_b, size_t moment_b)
+        : TemporalLayout(elem, width, height, frames, filter, paths, state_b, work_b) {
+        mo_b = moment_b * paths;
+        noise_b = (size_t)width * (size_t)height * elem;
+        DevLayout L{total};
+        off_mo[0] = L.add(mo_b); off_mo[1] = L.add(mo_b); off_noise = L.add(noise_b * frames);
+        total_m = L.add(0);
+        tab_b = frames * 32 * elem;
+        DevLayout P{moments ? total_m : total};
+        off_tab = P.add(tab_b);
+        total_p = P.total;
+    }
+};
+
+}  // namespace rtwh

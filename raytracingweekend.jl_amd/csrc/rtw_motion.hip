@@ -1,7 +1,7 @@
 // rtw_motion.hip -- the first-hit motion pass (include/rtw_hip.h rtw_first_hit_motion_*, rtw_motion_table_*): the checks that need no device,
 // the motion table (pure host code), the one launch of the pass's kernel (rtw_motion.hpp) and the device-resident entry points.
-// (The step that reads the plane, rtw_animated_step_device_*, lives with the other steps in rtw_temporal.hip; the host-buffer entry points,
-// rtw_first_hit_motion_* and rtw_animated_step_*, with the other cached-context paths in rtw_render_host.hip.)
+// (The step that reads the plane, rtw_animated_step_device_*, lives with the other steps in rtw_temporal.hip; the host-buffer entry points
+// live with the other cached-context paths: rtw_first_hit_motion_* in rtw_render_host.hip, rtw_animated_step_* in rtw_stage_host.hip.)
 #include "rtw_scene_view.hpp"
 #include "rtw_motion.hpp"
 

@@ -1,6 +1,6 @@
 // rtw_motion_blur.hip -- the motion-blur stage (include/rtw_hip.h rtw_velocity_blur_*): the checks that need no device, the workspace's layout,
 // the three launches of its kernels (rtw_motion_blur.hpp) and the device-resident entry points.
-// (The host-buffer entry points, rtw_velocity_blur_* and rtw_render_blurred_*, live with the other cached-context paths in
+// (The host-buffer entry points live with the other cached-context paths: rtw_velocity_blur_* in rtw_stage_host.hip, rtw_render_blurred_* in
 // rtw_render_host.hip.)
 #include "rtw_host.hpp"
 #include "rtw_motion_blur.hpp"
@@ -90,10 +90,7 @@ int motion_blur_device(const rtw_velocity_blur_t *b, const CamT *cam, const CamT
     if (((uintptr_t)d_image & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
     const size_t n_pix = (size_t)width * (size_t)height;
     const size_t img_b = n_pix * 3 * sizeof(T), feat_b = n_pix * 8 * sizeof(T), mo_b = n_pix * 4 * sizeof(T), work_b = (size_t)work_bytes(width, height, sizeof(T));
-    if (ranges_overlap(d_out, img_b, d_work, work_b)) return fail(-2, "d_out and d_work may not alias each other");
-    if (ranges_overlap(d_out, img_b, d_image, img_b) || ranges_overlap(d_out, img_b, d_features, feat_b) || ranges_overlap(d_out, img_b, d_motion, mo_b)) return fail(-2, "d_out may not alias an input");
-    if (ranges_overlap(d_work, work_b, d_image, img_b) || ranges_overlap(d_work, work_b, d_features, feat_b) || ranges_overlap(d_work, work_b, d_motion, mo_b))
-        return fail(-2, "d_work may not alias an input");
+    if (int rc = check_alias({{"d_out", d_out, img_b}, {"d_work", d_work, work_b}}, {{"d_image", d_image, img_b}, {"d_features", d_features, feat_b}, {"d_motion", d_motion, mo_b}})) return rc;
     DeviceGuard guard;
     if (b->device >= 0) HIP_TRY(hipSetDevice(b->device));
     return launch_motion_blur<T>(b, cam, cam_prev, width, height, d_image, d_features, d_motion, d_work, d_out, (hipStream_t)stream_v);

@@ -1,7 +1,7 @@
 // rtw_present.hip -- the present stage (include/rtw_hip.h rtw_present_*): the checks that need no device, the one launch of its kernel
 // (rtw_present.hpp) for one frame or a batch of frames and the device-resident entry points.  n_views == 0 is one frame; n_views >= 1
 // (rtw_present_batch_device_*) that many frames in the same launch.
-// (The host-buffer entry points, rtw_present_* and rtw_render_presented_*, live with the other cached-context paths in rtw_render_host.hip.)
+// (The host-buffer entry points live with the other cached-context paths: rtw_present_* in rtw_stage_host.hip, rtw_render_presented_* in rtw_render_host.hip.)
 #include "rtw_host.hpp"
 #include "rtw_present.hpp"
 

@@ -1,8 +1,9 @@
-// rtw_render_host.hip -- the host-buffer entry points of the C ABI (rtw_render_f32/_f64 is what the Julia ccall binds; replaces src/render.jl:8-44):
-// a cached per-device context (uploaded scene, stream, device buffer), one device (render_one_device: the path the plain, the batched, the
+// rtw_render_host.hip -- the host-buffer entry points of the C ABI that render (rtw_render_f32/_f64 is what the Julia ccall binds; replaces src/render.jl:8-44):
+// the pool of cached per-device contexts (uploaded scene, stream, device buffer), one device (rtw_host_ctx.hpp render_one_device: the path the plain, the batched, the
 // feature, the render + filter, the render + upsample, the sequence and the render + present entry points share) or a device list (tiles dealt round-robin, shards gathered on the first device by peer
 // copies or ONE RCCL reduce: rtw_multi.hip), one D2H of the result.  The single and the batched form of a call share one body (n_views == 0: single).
-#include "rtw_host.hpp"
+// (The pure stages on host buffers: rtw_stage_host.hip.)
+#include "rtw_host_ctx.hpp"
 
 namespace rtwh {
 
@@ -16,33 +17,6 @@ HostCtx::~HostCtx() {
     if (done_ev) HIP_IGNORE(hipEventDestroy(done_ev));
     if (stream) HIP_IGNORE(hipStreamDestroy(stream));
 }
-
-template <typename SceneT>
-void scene_key_of(const SceneT *s, bool f64, std::vector<unsigned char> &key) {
-    using T = typename std::remove_cv<typename std::remove_pointer<decltype(s->cx)>::type>::type;
-    const size_t n = (size_t)(s->n > 0 ? s->n : 0);
-    key.clear();
-    key.reserve(16 + n * (8 * sizeof(T) + sizeof(int32_t)));
-    auto put = [&](const void *p, size_t b) { const unsigned char *q = (const unsigned char *)p; key.insert(key.end(), q, q + b); };
-    const int32_t head[2] = {f64 ? 1 : 0, s->n};
-    put(head, sizeof head);
-    if (n == 0) return;
-    const T *arrs[8] = {s->cx, s->cy, s->cz, s->r, s->ar, s->ag, s->ab, s->param};
-    for (const T *a : arrs) put(a, n * sizeof(T));
-    put(s->kind, n * sizeof(int32_t));
-}
-
-// the caller holds a HostCtx exclusively between acquire and release
-struct HostLease {
-    CtxPtr ctx;
-    HostCtx *hc = nullptr;
-    bool pooled = false;
-    ~HostLease() {
-        if (!hc) return;
-        if (pooled) { std::lock_guard<std::mutex> lk(ctx->mu); hc->busy = false; }
-        else delete hc;                               // more concurrent host renders than pool entries: a temporary
-    }
-};
 
 int acquire_host(int device, const std::vector<unsigned char> &key, HostLease *out) {
     int dev;
@@ -81,22 +55,19 @@ int acquire_host(int device, const std::vector<unsigned char> &key, HostLease *o
     return 0;
 }
 
-// `keep` non-null (render_host_animation): the upload this one replaces may still be read by launches on the stream -- it is handed over, not freed
-template <typename T, typename SceneT>
-int ensure_scene(HostCtx *hc, const SceneT *scene, const std::vector<unsigned char> &key, std::vector<ScenePtr> *keep = nullptr) {
-    if (hc->scene && hc->scene_key == key) return 0;
-    if (hc->scene && keep) { keep->emplace_back(hc->scene); hc->scene = nullptr; hc->scene_key.clear(); }
-    if (hc->scene) { rtw_scene_free(hc->scene); hc->scene = nullptr; hc->scene_key.clear(); }
-    if (int rc = upload_scene_t(scene, hc->device, &hc->scene)) return rc;
-    hc->scene_key = key;
-    return 0;
-}
-
 int ensure_dev(void **p, size_t *cap, size_t bytes) {
     if (*cap >= bytes && *p) return 0;
     if (*p) { HIP_IGNORE(hipFree(*p)); *p = nullptr; *cap = 0; }
     HIP_TRY(hipMalloc(p, bytes));
     *cap = bytes;
+    return 0;
+}
+
+int ensure_stage(HostCtx *hc, size_t bytes) {
+    if (hc->stage_cap >= bytes) return 0;
+    if (hc->h_stage) { HIP_IGNORE(hipHostFree(hc->h_stage)); hc->h_stage = nullptr; hc->stage_cap = 0; }
+    HIP_TRY(hipHostMalloc(&hc->h_stage, bytes, hipHostMallocDefault));
+    hc->stage_cap = bytes;
     return 0;
 }
 
@@ -110,36 +81,8 @@ int copy_out(HostCtx *hc, const void *d_src, void *out, size_t bytes) {
     return 0;
 }
 
-
-// The one-device host path of every host-buffer entry point that renders: a leased context of `device` (negative: the current device) with the
-// scene uploaded and `dev_bytes` bytes of device buffer, ONE launch sequence -- launch(hc, q, &rec, &ctx) enqueues it on hc->stream into
-// hc->d_img, q: the caller's params bound to the lease's device --, ONE D2H of the `out_bytes` bytes at `out_off` into `out`, the counters of
-// `rec` into this thread's last render.  The stream has drained when it returns, on success and on an error.
-// (dev_bytes == 0, render_host's alone: a compact shard that owns no tile)
-template <typename T, typename SceneT, typename Launch>
-int render_one_device(int device, const SceneT *scene, const rtw_params *p, size_t dev_bytes, size_t out_off, size_t out_bytes, T *out, Launch launch) {
-    if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
-    std::vector<unsigned char> key;
-    scene_key_of(scene, sizeof(T) == 8, key);
-    HostLease L;
-    if (int rc = acquire_host(device, key, &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_scene<T>(hc, scene, key)) return rc;
-    rtw_params q = *p;
-    q.device = hc->device; q.n_devices = 0; q.device_ids = nullptr;
-    if (dev_bytes == 0) { g_last.resolved = true; return 0; }
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, dev_bytes)) return rc;
-    RenderRec *rec = nullptr;
-    CtxPtr rctx;
-    int rc = launch(hc, q, &rec, &rctx);
-    if (!rc) rc = copy_out(hc, (const char *)hc->d_img + out_off, out, out_bytes);
-    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
-    if (!rc) rc = resolve_rec(rec, &g_last.agg);
-    if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
-    if (rec) release_rec(rctx, rec, rc == 0);
-    g_last.resolved = rc == 0;
-    return rc;
-}
+// the record of a pass beside the render's own (a feature pass), handed back when the call returns: the stream has drained by then, either way
+struct SideRec { RenderRec *rec = nullptr; CtxPtr ctx; ~SideRec() { if (rec) release_rec(ctx, rec, true); } };
 
 template <typename T, typename SceneT, typename CamT>
 int render_host(const SceneT *scene, const CamT *cam, const rtw_params *p, T *out) {
@@ -256,12 +199,8 @@ int render_host(const SceneT *scene, const CamT *cam, const rtw_params *p, T *ou
                 // the documented fallback: through this shard's pinned staging buffer
                 gather_path |= RTW_GATHER_HOST_STAGED;
                 staged = true;
-                if (hc->stage_cap < my_bytes) {
-                    if (hc->h_stage) { HIP_IGNORE(hipHostFree(hc->h_stage)); hc->h_stage = nullptr; hc->stage_cap = 0; }
-                    e = hipHostMalloc(&hc->h_stage, my_bytes, hipHostMallocDefault);
-                    if (e == hipSuccess) hc->stage_cap = my_bytes;
-                }
-                if (e == hipSuccess) e = hipMemcpyAsync(hc->h_stage, d_out, my_bytes, hipMemcpyDeviceToHost, hc->stream);
+                if ((rc = ensure_stage(hc, my_bytes))) { rc = fail(rc, "device %d (shard %d of %d): gather failed: %s", hc->device, r, N, std::string(g_err).c_str()); break; }
+                e = hipMemcpyAsync(hc->h_stage, d_out, my_bytes, hipMemcpyDeviceToHost, hc->stream);
             }
         } else if (hc != root) {
             gather_path |= RTW_GATHER_SAME_DEVICE;
@@ -344,10 +283,10 @@ int render_host_features(const SceneT *scene, const CamT *cams, int32_t n_views,
     });
 }
 
-// The first-hit motion pass on host buffers (rtw_first_hit_motion_*): a leased context of the device with the scene uploaded (the cached one
-// when its bytes are the same) and a device buffer that holds the motion plane and, behind it, the motion table (`table`: scene->n rows of 4
-// elements, or null: m = 0 -- an id buffer); at most one H2D, ONE launch, ONE D2H.  The pass has no record: this thread's last render
-// (rtw_stats) is not touched.  (Not through render_one_device: that path resolves a record.)
+// The first-hit motion pass on host buffers (rtw_first_hit_motion_*): the stage path (stage_one_device) with the scene -- a leased context of
+// the device with the scene uploaded (the cached one when its bytes are the same) and a device buffer that holds the motion plane and, behind
+// it, the motion table (`table`: scene->n rows of 4 elements, or null: m = 0 -- an id buffer); at most one H2D, ONE launch, ONE D2H.  The pass
+// has no record: this thread's last render (rtw_stats) is not touched.
 template <typename T, typename SceneT, typename CamT>
 int render_host_motion(const SceneT *scene, const CamT *cam, const rtw_params *p, const T *table, T *motion) {
     if (!p) return fail(-1, "null params");
@@ -356,66 +295,16 @@ int render_host_motion(const SceneT *scene, const CamT *cam, const rtw_params *p
     if (scene->n < 0) return fail(-2, "negative sphere count");
     if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
     const size_t mo_b = (size_t)p->width * (size_t)p->height * 4 * sizeof(T), tab_b = (size_t)scene->n * 4 * sizeof(T);
-    if (table && ranges_overlap(motion, mo_b, table, tab_b)) return fail(-2, "motion may not alias the table");
-    DeviceGuard guard;
-    std::vector<unsigned char> key;
-    scene_key_of(scene, sizeof(T) == 8, key);
-    HostLease L;
-    if (int rc = acquire_host(p->device, key, &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_scene<T>(hc, scene, key)) return rc;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, mo_b + tab_b)) return rc;
-    rtw_params q = *p;
-    q.device = hc->device;
-    char *base = (char *)hc->d_img;
-    const bool up = table && tab_b;
-    int rc = 0;
-    if (up) if (hipError_t e = hipMemcpyAsync(base + mo_b, table, tab_b, hipMemcpyHostToDevice, hc->stream); e != hipSuccess) rc = fail((int)e, "upload of the motion table failed: %s", hipGetErrorString(e));
-    if (!rc) rc = launch_motion_t(hc->scene, cam, &q, up ? base + mo_b : nullptr, base, hc->stream);
-    if (!rc) rc = copy_out(hc, base, motion, mo_b);
-    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
-    return rc;
-}
-
-// The denoiser's regions inside a context's device buffer: image, features, output, workspace -- each starts on a 16-byte boundary and holds
-// the frames of a batch one behind the other.
-template <typename T> struct DenoiseRegions {
-    size_t img_b, feat_b, off_feat, off_out, off_work, total;
-    DenoiseRegions(int32_t width, int32_t height, int32_t n_views) {
-        const size_t frames = n_views ? (size_t)n_views : 1, n = (size_t)width * (size_t)height * frames;
-        auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        img_b = n * 3 * sizeof(T); feat_b = n * RTW_FEATURE_CHANNELS * sizeof(T);
-        off_feat = up(img_b); off_out = off_feat + up(feat_b); off_work = off_out + up(img_b);
-        total = off_work + (size_t)rtw_denoise_work_bytes(width, height, (int32_t)sizeof(T)) * frames;
-    }
-    // the filter over the regions of `base`, on `stream`
-    int launch(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, char *base, hipStream_t stream, const void *d_noise = nullptr) const {
-        return launch_denoise_t(d, width, height, n_views, (const T *)base, base + off_feat, base + off_out, base + off_work, stream, d_noise);
-    }
-};
-
-// The filter on host buffers (rtw_denoise_* / rtw_filter_batch_*): a leased context of the device (its stream and buffer; the scene it may hold
-// is left alone), two H2D, prepare + `levels` launches for any number of frames, ONE D2H.  This thread's last render (rtw_stats) is not touched.
-template <typename T>
-int filter_host(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const T *images, const T *features, T *out) {
-    if (!d || !images || !features || !out) return fail(-1, "null argument");
-    if (int rc = n_views ? validate_filter_batch(d, width, height, n_views) : validate_denoise(d, width, height)) return rc;
-    const DenoiseRegions<T> R(width, height, n_views);
-    if (ranges_overlap(out, R.img_b, images, R.img_b) || ranges_overlap(out, R.img_b, features, R.feat_b)) return fail(-2, "out may not alias an input");
-    DeviceGuard guard;
-    HostLease L;
-    if (int rc = acquire_host(d->device, std::vector<unsigned char>(), &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total)) return rc;
-    char *base = (char *)hc->d_img;
-    int rc = 0;
-    hipError_t e = hipMemcpyAsync(base, images, R.img_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_feat, features, R.feat_b, hipMemcpyHostToDevice, hc->stream);
-    if (e != hipSuccess) rc = fail((int)e, "upload of the %s's inputs failed: %s", n_views ? "filter" : "denoiser", hipGetErrorString(e));
-    if (!rc) rc = R.launch(d, width, height, n_views, base, hc->stream);
-    if (!rc) rc = copy_out(hc, base + R.off_out, out, R.img_b);
-    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
-    return rc;
+    DevLayout L{mo_b};
+    const size_t off_tab = L.add(tab_b);
+    if (int rc = check_alias({{"motion", motion, mo_b}}, {{"table", table, tab_b}}, "the table")) return rc;
+    return stage_one_device<T>(p->device, scene, L.total, "the motion table", {{off_tab, table, tab_b}},
+        [&](HostCtx *hc, char *base) {
+            rtw_params q = *p;
+            q.device = hc->device;
+            return launch_motion_t(hc->scene, cam, &q, table && tab_b ? base + off_tab : nullptr, base, hc->stream);
+        },
+        {0, motion, mo_b});
 }
 
 // The launch sequence of render + feature pass + filter on a leased context (render_host_filtered, render_host_presented): the linear image, the
@@ -423,13 +312,13 @@ int filter_host(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n
 // to the lease's device; rec / frec: the render's and the feature pass's records.
 template <typename T, typename CamT>
 int launch_filtered(HostCtx *hc, rtw_params &q, const CamT *cams, int32_t n_views, const uint64_t *seeds, int32_t gamma, const rtw_denoise_t *d, int nch, const DenoiseRegions<T> &R,
-                    RenderRec **rec, CtxPtr *rctx, RenderRec **frec, CtxPtr *fctx) {
+                    RenderRec **rec, CtxPtr *rctx, SideRec &frec) {
     char *base = (char *)hc->d_img;
     q.gamma = 0;
     rtw_denoise_t dd = *d;
     dd.gamma = gamma != 0; dd.device = hc->device;
     int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
-    if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, frec, fctx);
+    if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec.rec, &frec.ctx);
     if (!rc) rc = R.launch(&dd, q.width, q.height, n_views, base, hc->stream);
     return rc;
 }
@@ -447,36 +336,10 @@ int render_host_filtered(const SceneT *scene, const CamT *cams, int32_t n_views,
     DeviceGuard guard;
     release_last();
     const DenoiseRegions<T> R(p->width, p->height, n_views);
-    RenderRec *frec = nullptr;
-    CtxPtr fctx;
-    const int rc = render_one_device(p->device, scene, p, R.total, R.off_out, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
-        return launch_filtered(hc, q, cams, n_views, seeds, p->gamma, d, nch, R, rec, rctx, &frec, &fctx);
+    SideRec frec;                                             // (the feature pass's record)
+    return render_one_device(p->device, scene, p, R.total, R.off_out, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+        return launch_filtered(hc, q, cams, n_views, seeds, p->gamma, d, nch, R, rec, rctx, frec);
     });
-    if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
-    return rc;
-}
-
-// The present stage on a host buffer (rtw_present_*): a leased context of the device (its stream and buffer; the scene it may hold is left
-// alone), one H2D of the frame, ONE launch, ONE D2H of the bytes.  This thread's last render (rtw_stats) is not touched.
-template <typename T>
-int present_host(const rtw_present_t *p, int32_t width, int32_t height, const T *image, uint8_t *out) {
-    if (!p || !image || !out) return fail(-1, "null argument");
-    if (int rc = validate_present(p, width, height, 0)) return rc;
-    const size_t n_pix = (size_t)width * (size_t)height, img_b = n_pix * 3 * sizeof(T), out_b = n_pix * (size_t)p->channels, off_out = (img_b + 15) & ~(size_t)15;
-    if (ranges_overlap(out, out_b, image, img_b)) return fail(-2, "out may not alias the input");
-    DeviceGuard guard;
-    HostLease L;
-    if (int rc = acquire_host(p->device, std::vector<unsigned char>(), &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, off_out + out_b)) return rc;
-    char *base = (char *)hc->d_img;
-    int rc = 0;
-    const hipError_t e = hipMemcpyAsync(base, image, img_b, hipMemcpyHostToDevice, hc->stream);
-    if (e != hipSuccess) rc = fail((int)e, "upload of the frame failed: %s", hipGetErrorString(e));
-    if (!rc) rc = launch_present_t(p, width, height, 0, (const T *)base, base + off_out, hc->stream);
-    if (!rc) rc = copy_out(hc, base + off_out, out, out_b);
-    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
-    return rc;
 }
 
 // Render and present in one call (rtw_render_presented_* / rtw_render_presented_batch_*): the one-device path above.  d null: the render with
@@ -494,66 +357,20 @@ int render_host_presented(const SceneT *scene, const CamT *cams, int32_t n_views
     DeviceGuard guard;
     release_last();
     const DenoiseRegions<T> R(p->width, p->height, n_views);
-    const size_t off_img = d ? R.off_out : 0, off_pres = d ? R.total : (R.img_b + 15) & ~(size_t)15;       // (R.total is a multiple of 16)
     const size_t pres_b = (size_t)rtw_present_bytes(p->width, p->height, pr->channels, n_views);
-    RenderRec *frec = nullptr;
-    CtxPtr fctx;
+    DevLayout L{d ? R.total : R.img_b};                       // (the bytes: behind the filter's regions, or behind the image alone)
+    const size_t off_img = d ? R.off_out : 0, off_pres = L.add(pres_b);
+    SideRec frec;                                             // (the feature pass's record)
     // (render_one_device takes its precision from the type of `out` and hands the pointer to the D2H untyped: the bytes go out as they are)
-    const int rc = render_one_device(p->device, scene, p, off_pres + pres_b, off_pres, pres_b, reinterpret_cast<T *>(out), [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+    return render_one_device(p->device, scene, p, L.total, off_pres, pres_b, reinterpret_cast<T *>(out), [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
         char *base = (char *)hc->d_img;
         rtw_present_t pp = *pr;
         pp.device = hc->device;
-        int rc = d ? launch_filtered(hc, q, cams, n_views, seeds, p->gamma, d, nch, R, rec, rctx, &frec, &fctx)
+        int rc = d ? launch_filtered(hc, q, cams, n_views, seeds, p->gamma, d, nch, R, rec, rctx, frec)
                    : launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
         if (!rc) rc = launch_present_t(&pp, p->width, p->height, n_views, (const T *)(base + off_img), base + off_pres, hc->stream);
         return rc;
     });
-    if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
-    return rc;
-}
-
-// The upsampler's regions inside a context's device buffer: small image, small features, full features, output, workspace -- each starts on a
-// 16-byte boundary and holds the frames of a batch one behind the other.
-template <typename T> struct UpsampleRegions {
-    size_t img_b, flo_b, fhi_b, out_b, off_flo, off_fhi, off_out, off_work, total;
-    UpsampleRegions(int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views) {
-        const size_t frames = n_views ? (size_t)n_views : 1, n_lo = (size_t)lo_width * (size_t)lo_height * frames, n_hi = (size_t)width * (size_t)height * frames;
-        auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        img_b = n_lo * 3 * sizeof(T); flo_b = n_lo * RTW_FEATURE_CHANNELS * sizeof(T); fhi_b = n_hi * RTW_FEATURE_CHANNELS * sizeof(T); out_b = n_hi * 3 * sizeof(T);
-        off_flo = up(img_b); off_fhi = off_flo + up(flo_b); off_out = off_fhi + up(fhi_b); off_work = off_out + up(out_b);
-        total = off_work + (size_t)rtw_upsample_work_bytes(lo_width, lo_height, (int32_t)sizeof(T)) * frames;
-    }
-    // the upsampler over the regions of `base`, on `stream`
-    int launch(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, char *base, hipStream_t stream) const {
-        return launch_upsample_t(u, lo_width, lo_height, width, height, n_views, (const T *)base, base + off_flo, base + off_fhi, base + off_out, base + off_work, stream);
-    }
-};
-
-// The upsampler on host buffers (rtw_upsample_* / rtw_upsample_batch_*): a leased context of the device like filter_host's, three H2D,
-// prepare + `levels` + 1 launches for any number of views, ONE D2H.  This thread's last render (rtw_stats) is not touched.
-template <typename T>
-int upsample_host(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, const T *images_lo, const T *features_lo,
-                  const T *features_hi, T *out) {
-    if (!u || !images_lo || !features_lo || !features_hi || !out) return fail(-1, "null argument");
-    if (int rc = validate_upsample(u, lo_width, lo_height, width, height, n_views, (int)sizeof(T))) return rc;
-    const UpsampleRegions<T> R(lo_width, lo_height, width, height, n_views);
-    if (ranges_overlap(out, R.out_b, images_lo, R.img_b) || ranges_overlap(out, R.out_b, features_lo, R.flo_b) || ranges_overlap(out, R.out_b, features_hi, R.fhi_b))
-        return fail(-2, "out may not alias an input");
-    DeviceGuard guard;
-    HostLease L;
-    if (int rc = acquire_host(u->device, std::vector<unsigned char>(), &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, R.total)) return rc;
-    char *base = (char *)hc->d_img;
-    int rc = 0;
-    hipError_t e = hipMemcpyAsync(base, images_lo, R.img_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_flo, features_lo, R.flo_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_fhi, features_hi, R.fhi_b, hipMemcpyHostToDevice, hc->stream);
-    if (e != hipSuccess) rc = fail((int)e, "upload of the upsampler's inputs failed: %s", hipGetErrorString(e));
-    if (!rc) rc = R.launch(u, lo_width, lo_height, width, height, n_views, base, hc->stream);
-    if (!rc) rc = copy_out(hc, base + R.off_out, out, R.out_b);
-    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
-    return rc;
 }
 
 // A small render, its feature pass, the full-size feature pass and the upsampler in one call (rtw_render_upsampled_* / rtw_render_upsampled_batch_*):
@@ -576,180 +393,19 @@ int render_host_upsampled(const SceneT *scene, const CamT *cams, int32_t n_views
     DeviceGuard guard;
     release_last();
     const UpsampleRegions<T> R(lo_width, lo_height, p->width, p->height, n_views);
-    RenderRec *frec[2] = {nullptr, nullptr};
-    CtxPtr fctx[2];
-    const int rc = render_one_device(p->device, scene, p, R.total, R.off_out, R.out_b, out, [&](HostCtx *hc, rtw_params &pd, RenderRec **rec, CtxPtr *rctx) {
+    SideRec frec[2];                                          // (the two feature passes' records)
+    return render_one_device(p->device, scene, p, R.total, R.off_out, R.out_b, out, [&](HostCtx *hc, rtw_params &pd, RenderRec **rec, CtxPtr *rctx) {
         char *base = (char *)hc->d_img;
         rtw_params qd = pd;
         qd.width = lo_width; qd.height = lo_height; qd.gamma = 0;
         rtw_upsample_t uu = *u;
         uu.gamma = p->gamma != 0; uu.device = hc->device;
         int rc = launch_render_t(hc->scene, cams, n_views, seeds, &qd, base, hc->stream, rec, rctx);
-        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &qd, 0, nch_q, base + R.off_flo, hc->stream, &frec[0], &fctx[0]);
-        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &pd, 0, hi_chunks, base + R.off_fhi, hc->stream, &frec[1], &fctx[1]);
+        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &qd, 0, nch_q, base + R.off_flo, hc->stream, &frec[0].rec, &frec[0].ctx);
+        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &pd, 0, hi_chunks, base + R.off_fhi, hc->stream, &frec[1].rec, &frec[1].ctx);
         if (!rc) rc = R.launch(&uu, lo_width, lo_height, p->width, p->height, n_views, base, hc->stream);
         return rc;
     });
-    for (int k = 0; k < 2; ++k) if (frec[k]) release_rec(fctx[k], frec[k], true);        // (the stream has drained either way)
-    return rc;
-}
-
-// The regions of the temporal paths inside a context's device buffer: the linear images and the features of `frames` views, the accumulated
-// images, (filter: the filtered images,) two states, (filter: the denoiser's workspace) -- each starts on a 16-byte boundary.  `paths` >= 1
-// (rtw_render_paths_*): each of the two states is a SET of that many, one behind the other.
-template <typename T> struct TemporalRegions {
-    size_t frame_b, img_b, feat_b, st_b, off_feat, off_acc, off_flt, off_st[2], off_work, total;
-    TemporalRegions(int32_t width, int32_t height, size_t frames, bool filter, size_t paths = 1) {
-        const size_t n = (size_t)width * (size_t)height;
-        auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        frame_b = n * 3 * sizeof(T); img_b = frame_b * frames; feat_b = n * RTW_FEATURE_CHANNELS * sizeof(T) * frames;
-        st_b = (size_t)rtw_temporal_state_bytes(width, height, (int32_t)sizeof(T)) * paths;
-        off_feat = up(img_b); off_acc = off_feat + up(feat_b); off_flt = off_acc + up(img_b);
-        off_st[0] = off_flt + (filter ? up(img_b) : 0); off_st[1] = off_st[0] + st_b; off_work = off_st[1] + st_b;
-        total = off_work + (filter ? (size_t)rtw_denoise_work_bytes(width, height, (int32_t)sizeof(T)) * frames : 0);
-    }
-};
-
-// The regions of the temporal paths with moments: TemporalRegions (always with the filter's regions when `filter`), then two moment planes and
-// the noise maps of `frames` views -- each starts on a 16-byte boundary.  `paths` >= 1: each of the two moment planes is a set of that many, and
-// the table of the `frames` steps' camera constants (rtw_reproject_table_*) lies behind everything else: total_p bytes with `moments`' regions
-// or without them.
-template <typename T> struct MomentRegions : TemporalRegions<T> {
-    size_t mo_b, noise_b, off_mo[2], off_noise, total_m, tab_b, off_tab, total_p;
-    MomentRegions(int32_t width, int32_t height, size_t frames, bool filter, size_t paths = 1, bool moments = true) : TemporalRegions<T>(width, height, frames, filter, paths) {
-        auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-        mo_b = (size_t)rtw_history_moment_bytes(width, height, (int32_t)sizeof(T)) * paths;
-        noise_b = (size_t)width * (size_t)height * sizeof(T);
-        off_mo[0] = up(this->total); off_mo[1] = off_mo[0] + mo_b; off_noise = off_mo[1] + mo_b;
-        total_m = off_noise + up(noise_b * frames);
-        tab_b = frames * 32 * sizeof(T);
-        off_tab = moments ? total_m : up(this->total); total_p = off_tab + tab_b;
-    }
-};
-
-// One temporal step on host buffers (rtw_temporal_*, rtw_history_moments_*, rtw_clamped_step_*): a leased context of the device like
-// filter_host's, two to four H2D, the step's launch (`c`: a clamped step) and, with `n`, the launch of the noise map of what it leaves, then
-// two to four D2H (the next state, its moments, the map; the image last).  The moment planes take part when either is given; moment_next
-// must then be.  `form_args`: what the entry point requires beyond that (n, moment_next and noise; or c) is there.  This thread's last
-// render (rtw_stats) is not touched.  `animated` (rtw_animated_step_*): the step over a moving scene -- `motion`, the plane of
-// rtw_first_hit_motion_* (width*height slots of 4 elements), is there exactly when the previous state is and goes up behind the other inputs.
-template <typename T, typename CamT>
-int temporal_step_host(bool form_args, const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const CamT *cam, const CamT *cam_prev, int32_t width,
-                       int32_t height, const T *image, const T *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, T *out, T *noise,
-                       bool animated = false, const T *motion = nullptr) {
-    const bool moments = moment_prev || moment_next;
-    if (!form_args || !t || !cam || !image || !features || !state_next || !out || (moments && !moment_next)) return fail(-1, "null argument");
-    if (int rc = validate_temporal(t, width, height, (int)sizeof(T))) return rc;
-    if (n) if (int rc = validate_temporal_noise(n, width, height, (int)sizeof(T))) return rc;
-    if (c) if (int rc = validate_temporal_clamp(c)) return rc;
-    if ((cam_prev == nullptr) != (state_prev == nullptr)) return fail(-2, "cam_prev and state_prev must both be given or both be null (the first frame)");
-    if (moments && (moment_prev == nullptr) != (state_prev == nullptr)) return fail(-2, "moment_prev and state_prev must both be given or both be null (the first frame)");
-    if (animated && (motion == nullptr) != (state_prev == nullptr)) return fail(-2, "motion and state_prev must both be given or both be null (the first frame)");
-    const MomentRegions<T> R(width, height, 1, false);
-    const size_t motion_b = (size_t)width * (size_t)height * 4 * sizeof(T), off_motion = (R.total_m + 15) & ~(size_t)15;      // (behind every other region)
-    // the outputs that are there against each other and against every input that is
-    const void *outs[4] = {out, state_next, moment_next, noise}, *ins[5] = {image, features, state_prev, moment_prev, motion};
-    const size_t out_b[4] = {R.img_b, R.st_b, R.mo_b, R.noise_b}, in_b[5] = {R.img_b, R.feat_b, R.st_b, R.mo_b, motion_b};
-    static const char *const names[4] = {"out", "state_next", "moment_next", "noise"};
-    for (int a = 0; a < 4; ++a) {
-        if (!outs[a]) continue;
-        for (int b = a + 1; b < 4; ++b)
-            if (outs[b] && ranges_overlap(outs[a], out_b[a], outs[b], out_b[b])) return fail(-2, "%s and %s may not alias each other", names[a], names[b]);
-        for (int b = 0; b < 5; ++b)
-            if (ins[b] && ranges_overlap(outs[a], out_b[a], ins[b], in_b[b])) return fail(-2, "%s may not alias an input", names[a]);
-    }
-    DeviceGuard guard;
-    HostLease L;
-    if (int rc = acquire_host(t->device, std::vector<unsigned char>(), &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, motion ? off_motion + motion_b : R.total_m)) return rc;
-    char *base = (char *)hc->d_img;
-    int rc = 0;
-    hipError_t e = hipMemcpyAsync(base, image, R.img_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + R.off_feat, features, R.feat_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess && state_prev) e = hipMemcpyAsync(base + R.off_st[0], state_prev, R.st_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess && moment_prev) e = hipMemcpyAsync(base + R.off_mo[0], moment_prev, R.mo_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess && motion) e = hipMemcpyAsync(base + off_motion, motion, motion_b, hipMemcpyHostToDevice, hc->stream);
-    if (e != hipSuccess) rc = fail((int)e, "upload of the temporal step's inputs failed: %s", hipGetErrorString(e));
-    if (!rc) rc = launch_temporal_t(t, cam, cam_prev, 0, nullptr, width, height, base, base + R.off_feat, state_prev ? base + R.off_st[0] : nullptr, base + R.off_st[1], base + R.off_acc, hc->stream,
-                                    moment_prev ? base + R.off_mo[0] : nullptr, moments ? base + R.off_mo[1] : nullptr, c, motion ? base + off_motion : nullptr);
-    if (!rc && n) {
-        rtw_temporal_noise_t nn = *n;
-        nn.device = hc->device;
-        rc = launch_temporal_noise_t(&nn, width, height, 0, base + R.off_st[1], base + R.off_mo[1], (T *)(base + R.off_noise), hc->stream);
-    }
-    if (!rc) {
-        e = hipMemcpyAsync(state_next, base + R.off_st[1], R.st_b, hipMemcpyDeviceToHost, hc->stream);
-        if (e == hipSuccess && moments) e = hipMemcpyAsync(moment_next, base + R.off_mo[1], R.mo_b, hipMemcpyDeviceToHost, hc->stream);
-        if (e == hipSuccess && n) e = hipMemcpyAsync(noise, base + R.off_noise, R.noise_b, hipMemcpyDeviceToHost, hc->stream);
-        if (e != hipSuccess) rc = fail((int)e, "download of the next state, its moments or the noise map failed: %s", hipGetErrorString(e));
-    }
-    if (!rc) rc = copy_out(hc, base + R.off_acc, out, R.img_b);
-    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
-    return rc;
-}
-
-// The motion-blur stage on host buffers (rtw_velocity_blur_*): a leased context of the device like temporal_step_host's, three H2D (the image,
-// the features, the motion plane), the stage's three launches, ONE D2H.  The device buffer holds the three inputs, the output and the
-// workspace, each on a 16-byte boundary.  This thread's last render (rtw_stats) is not touched.
-template <typename T, typename CamT>
-int motion_blur_host(const rtw_velocity_blur_t *b, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const T *image, const T *features, const T *motion, T *out) {
-    if (!b || !cam || !cam_prev || !image || !features || !motion || !out) return fail(-1, "null argument");
-    if (int rc = validate_motion_blur(b, width, height, (int)sizeof(T))) return rc;
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t n_pix = (size_t)width * (size_t)height;
-    const size_t img_b = n_pix * 3 * sizeof(T), feat_b = n_pix * RTW_FEATURE_CHANNELS * sizeof(T), mo_b = n_pix * 4 * sizeof(T);
-    const size_t work_b = (size_t)rtw_velocity_blur_work_bytes(width, height, (int32_t)sizeof(T));
-    const size_t off_feat = up(img_b), off_mo = off_feat + up(feat_b), off_out = off_mo + mo_b, off_work = off_out + up(img_b), total = off_work + work_b;
-    if (ranges_overlap(out, img_b, image, img_b) || ranges_overlap(out, img_b, features, feat_b) || ranges_overlap(out, img_b, motion, mo_b)) return fail(-2, "out may not alias an input");
-    DeviceGuard guard;
-    HostLease L;
-    if (int rc = acquire_host(b->device, std::vector<unsigned char>(), &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, total)) return rc;
-    char *base = (char *)hc->d_img;
-    int rc = 0;
-    hipError_t e = hipMemcpyAsync(base, image, img_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + off_feat, features, feat_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + off_mo, motion, mo_b, hipMemcpyHostToDevice, hc->stream);
-    if (e != hipSuccess) rc = fail((int)e, "upload of the motion blur's inputs failed: %s", hipGetErrorString(e));
-    rtw_velocity_blur_t bb = *b;
-    bb.device = hc->device;
-    if (!rc) rc = launch_motion_blur_t(&bb, cam, cam_prev, width, height, base, base + off_feat, base + off_mo, base + off_work, base + off_out, hc->stream);
-    if (!rc) rc = copy_out(hc, base + off_out, out, img_b);
-    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
-    return rc;
-}
-
-// The defocus stage on host buffers (rtw_defocus_*): a leased context of the device like motion_blur_host's, two H2D (the image, the features),
-// the stage's two launches, ONE D2H.  The device buffer holds the two inputs, the output and the workspace, each on a 16-byte boundary.
-// This thread's last render (rtw_stats) is not touched.
-template <typename T, typename CamT>
-int defocus_host(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, const T *image, const T *features, T *out) {
-    if (!b || !cam || !image || !features || !out) return fail(-1, "null argument");
-    if (int rc = validate_defocus(b, cam, width, height)) return rc;
-    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t n_pix = (size_t)width * (size_t)height;
-    const size_t img_b = n_pix * 3 * sizeof(T), feat_b = n_pix * RTW_FEATURE_CHANNELS * sizeof(T);
-    const size_t work_b = (size_t)rtw_defocus_work_bytes(width, height, (int32_t)sizeof(T));
-    const size_t off_feat = up(img_b), off_out = off_feat + up(feat_b), off_work = off_out + up(img_b), total = off_work + work_b;
-    if (ranges_overlap(out, img_b, image, img_b) || ranges_overlap(out, img_b, features, feat_b)) return fail(-2, "out may not alias an input");
-    DeviceGuard guard;
-    HostLease L;
-    if (int rc = acquire_host(b->device, std::vector<unsigned char>(), &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, total)) return rc;
-    char *base = (char *)hc->d_img;
-    int rc = 0;
-    hipError_t e = hipMemcpyAsync(base, image, img_b, hipMemcpyHostToDevice, hc->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(base + off_feat, features, feat_b, hipMemcpyHostToDevice, hc->stream);
-    if (e != hipSuccess) rc = fail((int)e, "upload of the defocus stage's inputs failed: %s", hipGetErrorString(e));
-    rtw_defocus_t bb = *b;
-    bb.device = hc->device;
-    if (!rc) rc = launch_defocus_t(&bb, cam, width, height, base, base + off_feat, base + off_work, base + off_out, hc->stream);
-    if (!rc) rc = copy_out(hc, base + off_out, out, img_b);
-    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
-    return rc;
 }
 
 // Render through the pinhole and defocus in one call (rtw_render_defocused_*): the one-device path above.  The render (gamma 0) and the feature
@@ -773,26 +429,23 @@ int render_host_defocused(const SceneT *scene, const CamT *cam, const rtw_params
     DeviceGuard guard;
     release_last();
     const DenoiseRegions<T> R(p->width, p->height, 0);
-    const size_t off_df = (R.total + 15) & ~(size_t)15, off_work = off_df + ((R.img_b + 15) & ~(size_t)15);
-    const size_t total = off_work + (size_t)rtw_defocus_work_bytes(p->width, p->height, (int32_t)sizeof(T));
-    RenderRec *frec = nullptr;
-    CtxPtr fctx;
-    const int rc = render_one_device(p->device, scene, p, total, off_df, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+    DevLayout L{R.total};
+    const size_t off_df = L.add(R.img_b), off_work = L.add((size_t)rtw_defocus_work_bytes(p->width, p->height, (int32_t)sizeof(T)));
+    SideRec frec;                                             // (the feature pass's record)
+    return render_one_device(p->device, scene, p, L.total, off_df, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
         char *base = (char *)hc->d_img;
         int rc;
         if (d) {
-            rc = launch_filtered(hc, q, &pin, 0, nullptr, 0, d, nch, R, rec, rctx, &frec, &fctx);
+            rc = launch_filtered(hc, q, &pin, 0, nullptr, 0, d, nch, R, rec, rctx, frec);
         } else {
             q.gamma = 0;
             rc = launch_render_t(hc->scene, &pin, 0, nullptr, &q, base, hc->stream, rec, rctx);
-            if (!rc) rc = launch_features_t(hc->scene, &pin, 0, nullptr, &q, 0, nch, base + R.off_feat, hc->stream, &frec, &fctx);
+            if (!rc) rc = launch_features_t(hc->scene, &pin, 0, nullptr, &q, 0, nch, base + R.off_feat, hc->stream, &frec.rec, &frec.ctx);
         }
         bb.device = hc->device;
         if (!rc) rc = launch_defocus_t(&bb, &pin, p->width, p->height, base + (d ? R.off_out : 0), base + R.off_feat, base + off_work, base + off_df, hc->stream);
         return rc;
     });
-    if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
-    return rc;
 }
 
 // N cameras along a path with history reuse (rtw_render_sequence_*): the one-device path above with a device buffer that holds the linear images
@@ -830,24 +483,17 @@ int render_host_sequence(const SceneT *scene, const CamT *cams, int32_t n_views,
     const int32_t n_steps = n_paths ? n_views / n_paths : n_views;
     const MomentRegions<T> R(p->width, p->height, (size_t)n_views, d != nullptr, np, n != nullptr);
     const size_t dev_b = n_paths ? R.total_p : n ? R.total_m : R.total;
-    RenderRec *frec = nullptr;
-    CtxPtr fctx;
-    const int rc = render_one_device(p->device, scene, p, dev_b, d ? R.off_flt : R.off_acc, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+    SideRec frec;                                             // (the feature pass's record)
+    return render_one_device(p->device, scene, p, dev_b, d ? R.off_flt : R.off_acc, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
         char *base = (char *)hc->d_img;
         q.gamma = 0;
         rtw_temporal_t tt = *t;
         tt.gamma = d ? 0 : (p->gamma != 0); tt.device = hc->device;
-        rtw_temporal_noise_t nn = n ? *n : rtw_temporal_noise_t();
-        nn.device = hc->device;
         int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
-        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec, &fctx);
+        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec.rec, &frec.ctx);
         if (!rc && n_paths) {
             // the whole table: step 0's entries are first frames', step k's previous cameras are step k-1's
-            if (hc->stage_cap < R.tab_b) {
-                if (hc->h_stage) { HIP_IGNORE(hipHostFree(hc->h_stage)); hc->h_stage = nullptr; hc->stage_cap = 0; }
-                HIP_TRY(hipHostMalloc(&hc->h_stage, R.tab_b, hipHostMallocDefault));
-                hc->stage_cap = R.tab_b;
-            }
+            if ((rc = ensure_stage(hc, R.tab_b))) return rc;
             T *tab = (T *)hc->h_stage;
             temporal_table_t(cams, nullptr, n_paths, tab);
             if (n_steps > 1) temporal_table_t(cams + n_paths, cams, (int64_t)(n_steps - 1) * n_paths, tab + 32 * np);
@@ -859,7 +505,7 @@ int render_host_sequence(const SceneT *scene, const CamT *cams, int32_t n_views,
             rc = launch_temporal_t(&tt, n_paths ? nullptr : cams + v, n_paths || !v ? nullptr : cams + (v - 1), n_paths, n_paths ? base + R.off_tab + f * 32 * sizeof(T) : nullptr, p->width,
                                    p->height, base + f * R.frame_b, base + R.off_feat + f * feat_frame_b, v ? base + R.off_st[(v & 1) ^ 1] : nullptr, base + R.off_st[v & 1],
                                    base + R.off_acc + f * R.frame_b, hc->stream, n && v ? base + R.off_mo[(v & 1) ^ 1] : nullptr, n ? base + R.off_mo[v & 1] : nullptr, c);
-            if (!rc && n) rc = launch_temporal_noise_t(&nn, p->width, p->height, n_paths, base + R.off_st[v & 1], base + R.off_mo[v & 1], (T *)(base + R.off_noise + f * R.noise_b), hc->stream);
+            if (!rc && n) rc = launch_temporal_noise_t(n, p->width, p->height, n_paths, base + R.off_st[v & 1], base + R.off_mo[v & 1], (T *)(base + R.off_noise + f * R.noise_b), hc->stream);
         }
         if (!rc && d) {
             rtw_denoise_t dd = *d;
@@ -869,8 +515,6 @@ int render_host_sequence(const SceneT *scene, const CamT *cams, int32_t n_views,
         }
         return rc;
     });
-    if (frec) release_rec(fctx, frec, true);                  // (the stream has drained either way)
-    return rc;
 }
 
 // rtw_render_paths_*: n_paths paths x n_steps steps, step-major, in any of the sequence's forms -- c null: plain steps; n (d is then required): the
@@ -912,7 +556,7 @@ inline int motion_table_t(const rtw_scene_f64 *prev, const rtw_scene_f64 *cur, d
 // every frame keeps a motion plane of its own, and behind the last of them the motion-blur stage runs per frame with p->gamma -- three
 // launches for every frame from 1 on, the one pass-through launch for frame 0 -- into a region of n_frames frames behind the table, with ONE
 // workspace (stream order lets every frame reuse it); the D2H reads that region.  Without `b` the buffer and the launches are what they were.
-// (Not through render_one_device: that path uploads one scene and resolves one record.)
+// (The stage path with frame 0's scene; not render_one_device: that uploads one scene and resolves one record.)
 template <typename T, typename SceneT, typename CamT>
 int render_host_animation(const SceneT *scenes, const CamT *cams, int32_t n_frames, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t, const rtw_temporal_clamp_t *c,
                           const rtw_denoise_t *d, T *out, const rtw_velocity_blur_t *b = nullptr, bool blurred = false) {
@@ -928,83 +572,73 @@ int render_host_animation(const SceneT *scenes, const CamT *cams, int32_t n_fram
     rtw_params pm = *p;                                       // the motion pass reads the frame, the device and the numerics bits
     pm.flags &= RTW_FLAG_GROUP_CULL | RTW_FLAG_SCAN_VALU | RTW_FLAG_NUMERICS_CONTRACT | RTW_FLAG_NUMERICS_REFERENCE_FMA2;
     if (int rc = validate_motion(&pm, (int)sizeof(T))) return rc;
-    auto up = [](size_t b) { return (b + 15) & ~(size_t)15; };
-    size_t tab_max = 0, tab_sum = 0;
+    size_t tab_max = 0, tab_sum = 0;                          // (a table's bytes are a multiple of 16: the frames' tables lie one behind the other in the staging buffer)
     for (int v = 0; v < n_frames; ++v) {
         if (scenes[v].n < 0) return fail(-2, "negative sphere count (frame %d)", v);
         if (s_has_bad_scene(&scenes[v])) return fail(-1, "null scene array (frame %d)", v);
-        const size_t b = up((size_t)scenes[v].n * 4 * sizeof(T));
-        if (v) { tab_max = std::max(tab_max, b); tab_sum += b; }
+        const size_t tab_b = (size_t)scenes[v].n * 4 * sizeof(T);
+        if (v) { tab_max = std::max(tab_max, tab_b); tab_sum += tab_b; }
     }
     DeviceGuard guard;
     release_last();
     const TemporalRegions<T> R(p->width, p->height, (size_t)n_frames, d != nullptr);
-    const size_t mo_b = (size_t)p->width * (size_t)p->height * 4 * sizeof(T), off_mo = up(R.total), off_tab = off_mo + mo_b * (b ? (size_t)n_frames : 1), feat_frame_b = R.feat_b / (size_t)n_frames;
-    const size_t off_blur = up(off_tab + tab_max), off_bwork = off_blur + up(R.img_b);
-    const size_t total = b ? off_bwork + (size_t)rtw_velocity_blur_work_bytes(p->width, p->height, (int32_t)sizeof(T)) : off_tab + tab_max;
-    std::vector<unsigned char> key;
-    scene_key_of(&scenes[0], sizeof(T) == 8, key);
-    std::vector<ScenePtr> replaced;                           // (declared before the lease: the stream has drained when these are freed)
-    HostLease L;
-    if (int rc = acquire_host(p->device, key, &L)) return rc;
-    HostCtx *hc = L.hc;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, total)) return rc;
-    if (hc->stage_cap < tab_sum) {
-        if (hc->h_stage) { HIP_IGNORE(hipHostFree(hc->h_stage)); hc->h_stage = nullptr; hc->stage_cap = 0; }
-        HIP_TRY(hipHostMalloc(&hc->h_stage, tab_sum, hipHostMallocDefault));
-        hc->stage_cap = tab_sum;
-    }
-    char *base = (char *)hc->d_img;
+    const size_t mo_b = (size_t)p->width * (size_t)p->height * 4 * sizeof(T), feat_frame_b = R.feat_b / (size_t)n_frames;
+    DevLayout B{R.total};                                     // (behind the sequence's regions: the motion planes, the table, with b the blurred frames and the blur's workspace)
+    const size_t off_mo = B.add(mo_b * (b ? (size_t)n_frames : 1)), off_tab = B.add(tab_max);
+    const size_t off_blur = b ? B.add(R.img_b) : 0, off_bwork = b ? B.add((size_t)rtw_velocity_blur_work_bytes(p->width, p->height, (int32_t)sizeof(T))) : 0;
+    std::vector<ScenePtr> replaced;                           // (outlives the lease: the stream has drained when these are freed)
+    std::vector<RenderRec *> recs((size_t)n_frames, nullptr);
+    std::vector<CtxPtr> rctx((size_t)n_frames);
+    std::vector<SideRec> frecs((size_t)n_frames);
     rtw_params q = *p;
-    q.device = hc->device; q.n_devices = 0; q.device_ids = nullptr; q.gamma = 0;
-    pm.device = hc->device;
-    rtw_temporal_t tt = *t;
-    tt.gamma = (d || b) ? 0 : (p->gamma != 0); tt.device = hc->device;
-    std::vector<RenderRec *> recs((size_t)n_frames, nullptr), frecs((size_t)n_frames, nullptr);
-    std::vector<CtxPtr> rctx((size_t)n_frames), fctx((size_t)n_frames);
-    int rc = 0;
-    size_t stage_off = 0;
-    for (int v = 0; v < n_frames && !rc; ++v) {
-        const SceneT *scene = scenes + v;
-        if (v) scene_key_of(scene, sizeof(T) == 8, key);
-        if ((rc = ensure_scene<T>(hc, scene, key, &replaced))) break;
-        if (seeds) q.seed = seeds[v];
-        char *img = base + (size_t)v * R.frame_b, *feat = base + R.off_feat + (size_t)v * feat_frame_b, *plane = base + off_mo + (b ? (size_t)v * mo_b : 0);
-        rc = launch_render_t(hc->scene, cams + v, 0, nullptr, &q, img, hc->stream, &recs[v], &rctx[v]);
-        if (!rc) rc = launch_features_t(hc->scene, cams + v, 0, nullptr, &q, 0, nch, feat, hc->stream, &frecs[v], &fctx[v]);
-        if (!rc && v) {
-            const size_t tab_b = (size_t)scene->n * 4 * sizeof(T);
-            T *tab = (T *)((char *)hc->h_stage + stage_off);
-            stage_off += up(tab_b);
-            if (tab_b) {
-                rc = motion_table_t(scene - 1, scene, tab);
-                if (!rc) if (hipError_t e = hipMemcpyAsync(base + off_tab, tab, tab_b, hipMemcpyHostToDevice, hc->stream); e != hipSuccess)
-                    rc = fail((int)e, "upload of the motion table failed: %s", hipGetErrorString(e));
+    q.n_devices = 0; q.device_ids = nullptr; q.gamma = 0;
+    int rc = stage_one_device<T>(p->device, &scenes[0], B.total, "", {}, [&](HostCtx *hc, char *base) {
+        if (int rc = ensure_stage(hc, tab_sum)) return rc;
+        q.device = pm.device = hc->device;
+        rtw_temporal_t tt = *t;
+        tt.gamma = (d || b) ? 0 : (p->gamma != 0); tt.device = hc->device;
+        std::vector<unsigned char> key;
+        int rc = 0;
+        size_t stage_off = 0;
+        for (int v = 0; v < n_frames && !rc; ++v) {
+            const SceneT *scene = scenes + v;                     // (frame 0's is the lease's)
+            if (v) scene_key_of(scene, sizeof(T) == 8, key);
+            if (v && (rc = ensure_scene<T>(hc, scene, key, &replaced))) break;
+            if (seeds) q.seed = seeds[v];
+            char *img = base + (size_t)v * R.frame_b, *feat = base + R.off_feat + (size_t)v * feat_frame_b, *plane = base + off_mo + (b ? (size_t)v * mo_b : 0);
+            rc = launch_render_t(hc->scene, cams + v, 0, nullptr, &q, img, hc->stream, &recs[v], &rctx[v]);
+            if (!rc) rc = launch_features_t(hc->scene, cams + v, 0, nullptr, &q, 0, nch, feat, hc->stream, &frecs[v].rec, &frecs[v].ctx);
+            if (!rc && v) {
+                const size_t tab_b = (size_t)scene->n * 4 * sizeof(T);
+                T *tab = (T *)((char *)hc->h_stage + stage_off);
+                stage_off += tab_b;
+                if (tab_b) {
+                    rc = motion_table_t(scene - 1, scene, tab);
+                    if (!rc) if (hipError_t e = hipMemcpyAsync(base + off_tab, tab, tab_b, hipMemcpyHostToDevice, hc->stream); e != hipSuccess)
+                        rc = fail((int)e, "upload of the motion table failed: %s", hipGetErrorString(e));
+                }
+                if (!rc) rc = launch_motion_t(hc->scene, cams + v, &pm, tab_b ? base + off_tab : nullptr, plane, hc->stream);
             }
-            if (!rc) rc = launch_motion_t(hc->scene, cams + v, &pm, tab_b ? base + off_tab : nullptr, plane, hc->stream);
+            if (!rc) rc = launch_temporal_t(&tt, cams + v, v ? cams + (v - 1) : nullptr, 0, nullptr, p->width, p->height, img, feat, v ? base + R.off_st[(v & 1) ^ 1] : nullptr,
+                                            base + R.off_st[v & 1], base + R.off_acc + (size_t)v * R.frame_b, hc->stream, nullptr, nullptr, c, v ? plane : nullptr);
         }
-        if (!rc) rc = launch_temporal_t(&tt, cams + v, v ? cams + (v - 1) : nullptr, 0, nullptr, p->width, p->height, img, feat, v ? base + R.off_st[(v & 1) ^ 1] : nullptr,
-                                        base + R.off_st[v & 1], base + R.off_acc + (size_t)v * R.frame_b, hc->stream, nullptr, nullptr, c, v ? plane : nullptr);
-    }
-    if (!rc && d) {
-        rtw_denoise_t dd = *d;
-        dd.gamma = b ? 0 : (p->gamma != 0); dd.device = hc->device;
-        rc = launch_denoise_t(&dd, p->width, p->height, n_frames, (const T *)(base + R.off_acc), base + R.off_feat, base + R.off_flt, base + R.off_work, hc->stream);
-    }
-    if (b) {
-        rtw_velocity_blur_t bb = *b;
-        bb.gamma = p->gamma != 0; bb.device = hc->device;
-        for (int v = 0; v < n_frames && !rc; ++v)
-            rc = launch_motion_blur_t(&bb, cams + v, v ? cams + (v - 1) : nullptr, p->width, p->height, base + (d ? R.off_flt : R.off_acc) + (size_t)v * R.frame_b,
-                                      base + R.off_feat + (size_t)v * feat_frame_b, base + off_mo + (size_t)v * mo_b, base + off_bwork, base + off_blur + (size_t)v * R.frame_b, hc->stream);
-    }
-    if (!rc) rc = copy_out(hc, base + (b ? off_blur : d ? R.off_flt : R.off_acc), out, R.img_b);
-    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends or an upload is freed
-    for (int v = 0; v < n_frames; ++v) {
+        if (!rc && d) {
+            rtw_denoise_t dd = *d;
+            dd.gamma = b ? 0 : (p->gamma != 0); dd.device = hc->device;
+            rc = launch_denoise_t(&dd, p->width, p->height, n_frames, (const T *)(base + R.off_acc), base + R.off_feat, base + R.off_flt, base + R.off_work, hc->stream);
+        }
+        if (b) {
+            rtw_velocity_blur_t bb = *b;
+            bb.gamma = p->gamma != 0; bb.device = hc->device;
+            for (int v = 0; v < n_frames && !rc; ++v)
+                rc = launch_motion_blur_t(&bb, cams + v, v ? cams + (v - 1) : nullptr, p->width, p->height, base + (d ? R.off_flt : R.off_acc) + (size_t)v * R.frame_b,
+                                          base + R.off_feat + (size_t)v * feat_frame_b, base + off_mo + (size_t)v * mo_b, base + off_bwork, base + off_blur + (size_t)v * R.frame_b, hc->stream);
+        }
+        return rc;
+    }, {b ? off_blur : d ? R.off_flt : R.off_acc, out, R.img_b});
+    for (int v = 0; v < n_frames; ++v)
         if (recs[v]) { if (!rc) rc = resolve_rec(recs[v], &g_last.agg); release_rec(rctx[v], recs[v], rc == 0); }
-        if (frecs[v]) release_rec(fctx[v], frecs[v], true);     // (the stream has drained either way)
-    }
-    if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
+    if (!rc) g_last.per_device.emplace_back(q.device, g_last.agg.kernel_ms);
     g_last.resolved = rc == 0;
     return rc;
 }
@@ -1012,7 +646,7 @@ int render_host_animation(const SceneT *scenes, const CamT *cams, int32_t n_fram
 // What an accumulator holds, denoised (rtw_accum_filtered_f32/_f64): the gamma-0 resolve (per tile for an adaptive accumulator), the feature
 // pass over exactly the samples it holds, with `guided` its noise map and the noise-guided filter (else the plain one), all on the
 // accumulator's device in a leased context's buffer and stream, ONE D2H.  The accumulator is only read; every step orders itself behind
-// its event.  rtw_stats() reports the feature pass's record.  (Not through render_one_device: its lease has no scene to upload.)
+// its event.  rtw_stats() reports the feature pass's record.  (The stage path with the record resolved behind it: the lease has no scene to upload.)
 // n_views != 0 (rtw_accum_filtered_batch_*): the same for the n_views accumulators behind `accums` with cams[v] / seeds[v] -- ONE batched
 // resolve, ONE batched feature launch, ONE batched noise launch and the batched filter, 4 + levels launches and ONE D2H for any number of views.
 template <typename T, typename CamT>
@@ -1032,32 +666,29 @@ int accum_filtered_host(rtw_scene_handle scene, const CamT *cams, int32_t n_view
     if (guided) if (int rc = n_views ? validate_accum_noise_batch(accums, n_views, f64) : validate_accum_noise(accums[0], f64)) return rc;
     DeviceGuard guard;
     release_last();
-    HostLease L;
-    if (int rc = acquire_host(accum_device_of(accums[0]), std::vector<unsigned char>(), &L)) return rc;
-    HostCtx *hc = L.hc;
     const DenoiseRegions<T> R(p->width, p->height, n_views);
-    const size_t off_noise = (R.total + 15) & ~(size_t)15;
-    if (int rc = ensure_dev(&hc->d_img, &hc->d_cap, off_noise + (size_t)std::max(n_views, 1) * (size_t)p->width * (size_t)p->height * sizeof(T))) return rc;
-    char *base = (char *)hc->d_img;
-    rtw_denoise_t dd = *d;
-    dd.gamma = p->gamma != 0; dd.device = hc->device;
+    DevLayout B{R.total};                                     // (the noise maps: behind the filter's regions)
+    const size_t off_noise = B.add((size_t)std::max(n_views, 1) * (size_t)p->width * (size_t)p->height * sizeof(T));
     RenderRec *frec = nullptr;
     CtxPtr fctx;
-    int rc;
-    if (n_views) {
-        rc = enqueue_accum_resolve_batch(accums, n_views, f64, 0, base, hc->stream);
-        if (!rc) rc = enqueue_accum_features_batch(scene, cams, n_views, seeds, p, accums, base + R.off_feat, hc->stream, &frec, &fctx);
-        if (!rc && guided) rc = enqueue_accum_noise_batch(accums, n_views, f64, base + off_noise, hc->stream);
-    } else {
-        rc = enqueue_accum_resolve(accums[0], f64, 0, base, hc->stream);
-        if (!rc) rc = enqueue_accum_features(scene, cams, p, accums[0], base + R.off_feat, hc->stream, &frec, &fctx);
-        if (!rc && guided) rc = enqueue_accum_noise(accums[0], f64, base + off_noise, hc->stream);
-    }
-    if (!rc) rc = R.launch(&dd, p->width, p->height, n_views, base, hc->stream, guided ? base + off_noise : nullptr);
-    if (!rc) rc = copy_out(hc, base + R.off_out, out, R.img_b);
-    if (rc) (void)hipStreamSynchronize(hc->stream);           // nothing of this call may still be in flight when the lease ends
+    int rc = stage_one_device<T>(accum_device_of(accums[0]), nullptr, B.total, "", {}, [&](HostCtx *hc, char *base) {
+        rtw_denoise_t dd = *d;
+        dd.gamma = p->gamma != 0; dd.device = hc->device;
+        int rc;
+        if (n_views) {
+            rc = enqueue_accum_resolve_batch(accums, n_views, f64, 0, base, hc->stream);
+            if (!rc) rc = enqueue_accum_features_batch(scene, cams, n_views, seeds, p, accums, base + R.off_feat, hc->stream, &frec, &fctx);
+            if (!rc && guided) rc = enqueue_accum_noise_batch(accums, n_views, f64, base + off_noise, hc->stream);
+        } else {
+            rc = enqueue_accum_resolve(accums[0], f64, 0, base, hc->stream);
+            if (!rc) rc = enqueue_accum_features(scene, cams, p, accums[0], base + R.off_feat, hc->stream, &frec, &fctx);
+            if (!rc && guided) rc = enqueue_accum_noise(accums[0], f64, base + off_noise, hc->stream);
+        }
+        if (!rc) rc = R.launch(&dd, p->width, p->height, n_views, base, hc->stream, guided ? base + off_noise : nullptr);
+        return rc;
+    }, {R.off_out, out, R.img_b});
     if (!rc) rc = resolve_rec(frec, &g_last.agg);
-    if (!rc) g_last.per_device.emplace_back(hc->device, g_last.agg.kernel_ms);
+    if (!rc) g_last.per_device.emplace_back(frec->device, g_last.agg.kernel_ms);
     if (frec) release_rec(fctx, frec, rc == 0);
     g_last.resolved = rc == 0;
     return rc;
@@ -1094,18 +725,6 @@ int rtw_render_features_batch_f64(const rtw_scene_f64 *s, const rtw_camera_f64 *
     return render_host_features<double>(s, cams, batch_views(n_views), seeds, p, chunk_begin, chunk_count, out);
 }
 
-int rtw_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, const float *image, const float *features, float *out) {
-    return filter_host<float>(d, width, height, 0, image, features, out);
-}
-int rtw_denoise_f64(const rtw_denoise_t *d, int32_t width, int32_t height, const double *image, const double *features, double *out) {
-    return filter_host<double>(d, width, height, 0, image, features, out);
-}
-int rtw_filter_batch_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const float *images, const float *features, float *out) {
-    return filter_host<float>(d, width, height, batch_views(n_views), images, features, out);
-}
-int rtw_filter_batch_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const double *images, const double *features, double *out) {
-    return filter_host<double>(d, width, height, batch_views(n_views), images, features, out);
-}
 
 int rtw_render_denoised_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, float *out) {
     return render_host_filtered<float>(scene, cam, 0, nullptr, p, d, out);
@@ -1122,8 +741,6 @@ int rtw_render_filtered_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f
     return render_host_filtered<double>(scene, cams, batch_views(n_views), seeds, p, d, out);
 }
 
-int rtw_present_f32(const rtw_present_t *p, int32_t width, int32_t height, const float *image, uint8_t *out) { return present_host<float>(p, width, height, image, out); }
-int rtw_present_f64(const rtw_present_t *p, int32_t width, int32_t height, const double *image, uint8_t *out) { return present_host<double>(p, width, height, image, out); }
 int rtw_render_presented_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *params, const rtw_denoise_t *d, const rtw_present_t *p, uint8_t *out) {
     return render_host_presented<float>(scene, cam, 0, nullptr, params, d, p, out);
 }
@@ -1139,22 +756,6 @@ int rtw_render_presented_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_
     return render_host_presented<double>(scene, cams, batch_views(n_views), seeds, params, d, p, out);
 }
 
-int rtw_upsample_f32(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, const float *image_lo, const float *features_lo,
-                     const float *features_hi, float *out) {
-    return upsample_host<float>(u, lo_width, lo_height, width, height, 0, image_lo, features_lo, features_hi, out);
-}
-int rtw_upsample_f64(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, const double *image_lo, const double *features_lo,
-                     const double *features_hi, double *out) {
-    return upsample_host<double>(u, lo_width, lo_height, width, height, 0, image_lo, features_lo, features_hi, out);
-}
-int rtw_upsample_batch_f32(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, const float *images_lo,
-                           const float *features_lo, const float *features_hi, float *out) {
-    return upsample_host<float>(u, lo_width, lo_height, width, height, batch_views(n_views), images_lo, features_lo, features_hi, out);
-}
-int rtw_upsample_batch_f64(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, const double *images_lo,
-                           const double *features_lo, const double *features_hi, double *out) {
-    return upsample_host<double>(u, lo_width, lo_height, width, height, batch_views(n_views), images_lo, features_lo, features_hi, out);
-}
 int rtw_render_upsampled_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, int32_t lo_width, int32_t lo_height, const rtw_upsample_t *u, float *out) {
     return render_host_upsampled<float>(scene, cam, 0, nullptr, p, lo_width, lo_height, u, out);
 }
@@ -1170,38 +771,6 @@ int rtw_render_upsampled_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_
     return render_host_upsampled<double>(scene, cams, batch_views(n_views), seeds, p, lo_width, lo_height, u, out);
 }
 
-int rtw_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height, const float *image, const float *features,
-                     const void *state_prev, void *state_next, float *out) {
-    return temporal_step_host<float>(true, t, nullptr, nullptr, cam, cam_prev, width, height, image, features, state_prev, nullptr, state_next, nullptr, out, nullptr);
-}
-int rtw_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const double *image, const double *features,
-                     const void *state_prev, void *state_next, double *out) {
-    return temporal_step_host<double>(true, t, nullptr, nullptr, cam, cam_prev, width, height, image, features, state_prev, nullptr, state_next, nullptr, out, nullptr);
-}
-int rtw_history_moments_f32(const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height,
-                             const float *image, const float *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, float *out, float *noise) {
-    return temporal_step_host<float>(n && moment_next && noise, t, nullptr, n, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, noise);
-}
-int rtw_history_moments_f64(const rtw_temporal_t *t, const rtw_temporal_noise_t *n, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
-                             const double *image, const double *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, double *out, double *noise) {
-    return temporal_step_host<double>(n && moment_next && noise, t, nullptr, n, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, noise);
-}
-int rtw_clamped_step_f32(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height,
-                             const float *image, const float *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, float *out) {
-    return temporal_step_host<float>(c != nullptr, t, c, nullptr, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, nullptr);
-}
-int rtw_clamped_step_f64(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
-                             const double *image, const double *features, const void *state_prev, const void *moment_prev, void *state_next, void *moment_next, double *out) {
-    return temporal_step_host<double>(c != nullptr, t, c, nullptr, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, nullptr);
-}
-int rtw_animated_step_f32(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height,
-                          const float *image, const float *features, const float *motion, const void *state_prev, void *state_next, const void *moment_prev, void *moment_next, float *out) {
-    return temporal_step_host<float>(true, t, c, nullptr, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, nullptr, true, motion);
-}
-int rtw_animated_step_f64(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height,
-                          const double *image, const double *features, const double *motion, const void *state_prev, void *state_next, const void *moment_prev, void *moment_next, double *out) {
-    return temporal_step_host<double>(true, t, c, nullptr, cam, cam_prev, width, height, image, features, state_prev, moment_prev, state_next, moment_next, out, nullptr, true, motion);
-}
 int rtw_first_hit_motion_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const float *table, float *motion) {
     return render_host_motion<float>(scene, cam, p, table, motion);
 }
@@ -1223,20 +792,6 @@ int rtw_render_blurred_f32(const rtw_scene_f32 *scenes, const rtw_camera_f32 *ca
 int rtw_render_blurred_f64(const rtw_scene_f64 *scenes, const rtw_camera_f64 *cams, int32_t n_frames, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                                      const rtw_temporal_clamp_t *c, const rtw_denoise_t *d, const rtw_velocity_blur_t *b, double *out) {
     return render_host_animation<double>(scenes, cams, n_frames, seeds, p, t, c, d, out, b, true);
-}
-int rtw_velocity_blur_f32(const rtw_velocity_blur_t *b, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height, const float *image, const float *features,
-                        const float *motion, float *out) {
-    return motion_blur_host<float>(b, cam, cam_prev, width, height, image, features, motion, out);
-}
-int rtw_velocity_blur_f64(const rtw_velocity_blur_t *b, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const double *image, const double *features,
-                        const double *motion, double *out) {
-    return motion_blur_host<double>(b, cam, cam_prev, width, height, image, features, motion, out);
-}
-int rtw_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const float *image, const float *features, float *out) {
-    return defocus_host<float>(b, cam, width, height, image, features, out);
-}
-int rtw_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const double *image, const double *features, double *out) {
-    return defocus_host<double>(b, cam, width, height, image, features, out);
 }
 int rtw_render_defocused_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, const rtw_defocus_t *b, float *out) {
     return render_host_defocused<float>(scene, cam, p, d, b, out);

@@ -2,8 +2,8 @@
 // the one launch of its kernel (rtw_temporal.hpp), the step with moments and the noise map (rtw_history_moments_*, rtw_history_noise_device_*), the
 // clamped step (rtw_clamped_step_device_*: the checks of its clamp and the launch of its own kernel, rtw_temporal_clamp.hpp) and the
 // device-resident entry points, the step over a moving scene among them (rtw_animated_step_device_*: the MOTION instances, the plane of rtw_motion.hip); the batched forms of all three (rtw_reproject_*: n_paths paths in each launch, the table of their camera constants).
-// (The host-buffer entry points, rtw_temporal_*, rtw_history_moments_*, rtw_clamped_step_*, rtw_render_sequence_*, rtw_render_path_* and rtw_render_paths_*, live with the other
-// cached-context paths in rtw_render_host.hip.)
+// (The host-buffer entry points live with the other cached-context paths: rtw_temporal_*, rtw_history_moments_* and rtw_clamped_step_* in rtw_stage_host.hip,
+// rtw_render_sequence_*, rtw_render_path_* and rtw_render_paths_* in rtw_render_host.hip.)
 #include "rtw_host.hpp"
 #include "rtw_temporal.hpp"
 #include "rtw_temporal_clamp.hpp"
@@ -288,17 +288,11 @@ int temporal_batch_device(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c
     if (((uintptr_t)d_images & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
     const size_t np = (size_t)n_paths, n_pix = (size_t)width * (size_t)height * np;
     // every output against the outputs behind it and against every input that is there
-    const void *outs[3] = {d_out, d_states_next, d_moments_next}, *ins[5] = {d_images, d_features, d_states_prev, d_moments_prev, d_table};
-    const size_t st_b = (size_t)state_bytes(width, height, sizeof(T)) * np, mo_b = (size_t)moment_bytes(width, height, sizeof(T)) * np;
-    const size_t out_b[3] = {n_pix * 3 * sizeof(T), st_b, mo_b}, in_b[5] = {n_pix * 3 * sizeof(T), n_pix * 8 * sizeof(T), st_b, mo_b, np * 32 * sizeof(T)};
-    static const char *const names[3] = {"d_out", "d_states_next", "d_moments_next"};
-    for (int a = 0; a < 3; ++a) {
-        if (!outs[a]) continue;
-        for (int b = a + 1; b < 3; ++b)
-            if (outs[b] && ranges_overlap(outs[a], out_b[a], outs[b], out_b[b])) return fail(-2, "%s and %s may not alias each other", names[a], names[b]);
-        for (int b = 0; b < 5; ++b)
-            if (ins[b] && ranges_overlap(outs[a], out_b[a], ins[b], in_b[b])) return fail(-2, "%s may not alias an input", names[a]);
-    }
+    const size_t img_b = n_pix * 3 * sizeof(T), st_b = (size_t)state_bytes(width, height, sizeof(T)) * np, mo_b = (size_t)moment_bytes(width, height, sizeof(T)) * np;
+    if (int rc = check_alias({{"d_out", d_out, img_b}, {"d_states_next", d_states_next, st_b}, {"d_moments_next", d_moments_next, mo_b}},
+                             {{"d_images", d_images, img_b}, {"d_features", d_features, n_pix * 8 * sizeof(T)}, {"d_states_prev", d_states_prev, st_b}, {"d_moments_prev", d_moments_prev, mo_b},
+                              {"d_table", d_table, np * 32 * sizeof(T)}}))
+        return rc;
     DeviceGuard guard;
     if (t->device >= 0) HIP_TRY(hipSetDevice(t->device));
     using CamT = std::conditional_t<sizeof(T) == 8, rtw_camera_f64, rtw_camera_f32>;
@@ -316,9 +310,8 @@ int temporal_noise_batch_device(const rtw_temporal_noise_t *n, int32_t width, in
     if (((uintptr_t)d_states & 15u) || ((uintptr_t)d_moments & 15u)) return fail(-2, "the states and the moment planes must be 16-byte aligned");
     if ((uintptr_t)d_noise & (sizeof(T) - 1)) return fail(-2, "the noise maps must be aligned to their element type");
     const size_t np = (size_t)n_paths, noise_b = (size_t)width * (size_t)height * np * sizeof(T);
-    if (ranges_overlap(d_noise, noise_b, d_states, (size_t)state_bytes(width, height, sizeof(T)) * np) ||
-        ranges_overlap(d_noise, noise_b, d_moments, (size_t)moment_bytes(width, height, sizeof(T)) * np))
-        return fail(-2, "d_noise may not alias an input");
+    if (int rc = check_alias({{"d_noise", d_noise, noise_b}}, {{"d_states", d_states, (size_t)state_bytes(width, height, sizeof(T)) * np}, {"d_moments", d_moments, (size_t)moment_bytes(width, height, sizeof(T)) * np}}))
+        return rc;
     DeviceGuard guard;
     if (n->device >= 0) HIP_TRY(hipSetDevice(n->device));
     return launch_temporal_noise<T>(n, width, height, n_paths, d_states, d_moments, d_noise, (hipStream_t)stream_v);
@@ -332,9 +325,8 @@ int temporal_noise_device(const rtw_temporal_noise_t *n, int32_t width, int32_t 
     if (((uintptr_t)d_state & 15u) || ((uintptr_t)d_moment & 15u)) return fail(-2, "the state and the moment plane must be 16-byte aligned");
     if ((uintptr_t)d_noise & (sizeof(T) - 1)) return fail(-2, "the noise map must be aligned to its element type");
     const size_t n_pix = (size_t)width * (size_t)height;
-    if (ranges_overlap(d_noise, n_pix * sizeof(T), d_state, (size_t)state_bytes(width, height, sizeof(T))) ||
-        ranges_overlap(d_noise, n_pix * sizeof(T), d_moment, (size_t)moment_bytes(width, height, sizeof(T))))
-        return fail(-2, "d_noise may not alias an input");
+    if (int rc = check_alias({{"d_noise", d_noise, n_pix * sizeof(T)}}, {{"d_state", d_state, (size_t)state_bytes(width, height, sizeof(T))}, {"d_moment", d_moment, (size_t)moment_bytes(width, height, sizeof(T))}}))
+        return rc;
     DeviceGuard guard;
     if (n->device >= 0) HIP_TRY(hipSetDevice(n->device));
     return launch_temporal_noise<T>(n, width, height, 0, d_state, d_moment, d_noise, (hipStream_t)stream_v);

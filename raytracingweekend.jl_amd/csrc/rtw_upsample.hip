@@ -2,7 +2,7 @@
 // the denoiser's prepare and `levels` of its level kernel at the small size (rtw_denoise.hpp, launched as they are; no pass is a final one),
 // then the upsampling kernel (rtw_upsample.hpp) at the full size -- and the device-resident entry points.  n_views == 0 is one frame;
 // n_views >= 1 (rtw_upsample_batch_*) the same sequence once for that many views (the batched kernels).
-// (The host-buffer entry points, rtw_render_upsampled_* and rtw_render_upsampled_batch_* live with the other cached-context paths in rtw_render_host.hip.)
+// (The host-buffer entry points live with the other cached-context paths: rtw_upsample_* and rtw_upsample_batch_* in rtw_stage_host.hip, rtw_render_upsampled_* and rtw_render_upsampled_batch_* in rtw_render_host.hip.)
 #include "rtw_host.hpp"
 #include "rtw_upsample.hpp"
 
