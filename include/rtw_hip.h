@@ -1341,6 +1341,93 @@ int rtw_render_defocused_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *c
 int rtw_render_defocused_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d /* may be NULL */,
                              const rtw_defocus_t *b, double *out);
 
+/* Wide aperture: circles of confusion up to 32 px.  The block above clamps every circle of confusion at 8 px, and at the headline frame
+ * size the headline camera sits at that clamp: lookfrom (13, 2, 3), vfov 20, focus 10, aperture 0.1 at 1920 x 1080 has K = 15.3 px.  This
+ * stage is the standard remedy beside it: the frame is reduced by s = 2 or 4, the reduced copy is gathered by the SAME gather (a radius of
+ * 32 px is 8 small pixels), and the result is blended back by the radius, so that what is nearly sharp keeps the full-resolution gather.
+ * The existing entry points do not move: they keep refusing max_radius > 8.
+ *
+ * The definition, with the conventions of the block above: everything in T, every operation rounded once, no FMA, the correctly rounded
+ * IEEE quotients and sqrt, what does not take part dropped by a select; clamp01, min and max as above.  Inputs and output are those of the
+ * block above; rtw_wide_aperture_t has the fields of its struct with max_radius in 1..32.
+ *   1. Scale.  s = 1 for max_radius <= 8: the call IS the one of the block above on the bits -- the same launches, the same workspace --
+ * and nothing below applies.  s = 2 for 9..16, s = 4 for 17..32.  The small frame is h = ceil(H/s) rows by w = ceil(W/s) columns; small
+ * pixel (a, b) is slot b*h + a.
+ *   2. The narrow frame N: exactly the output of the block above with max_radius = 8 and gamma = 0 on the same inputs (its CoC plane and
+ * tile plane are left in the head of the workspace).
+ *   3. The wide CoC plane: Prepare and Tile max of the block above with Rm = T(max_radius).  A pixel with R < 8 carries the same R in both
+ * planes on the bits.
+ *   4. Reduce.  Small pixel (a, b) covers rows s*a .. s*a+s-1 and columns s*b .. s*b+s-1, clipped to the frame, visited with the column
+ * outer and the row inner, both ascending.  Over the block's VALID pixels (their colour c from the input image, R and zc from the wide
+ * plane), n of them:  csum[k] = csum[k] + c[k] and Rsum = Rsum + R, both from +0 in that order;  zmin = zc < zmin ? zc : zmin from +inf (a
+ * comparison only; +inf stays when every valid pixel is sky);  c_s[k] = csum[k] / T(n);  R_s = (Rsum / T(n)) * T(1/s);  zc_s = zmin;
+ * Rh_s = max(R_s, T(0.5));  w_s = 1 / (Rh_s*Rh_s).  The SMALL COLOUR holds c_s (3 elements per small pixel), the SMALL COC PLANE holds
+ * (R_s, zc_s, w_s, 0).  A block with no valid pixel is not valid: its slot is (-1, NaN, 0, 0) and its colour (+0, +0, +0).  The SMALL TILE
+ * PLANE holds the greatest R_s per 16 x 16 small tile (-1 if none is valid), index b'*th + a' with th = ceil(h/16): a plain maximum.
+ * The sums are of at most 16 values, each <= Rm, and every k*Rm is a small integer: by monotone rounding every partial sum is <= k*Rm, the
+ * mean is <= Rm and R_s <= Rm/s <= 8, so the window of the small gather is never exceeded.
+ *   5. The small gather: Gather of the block above on the small frame -- the small colour as the image, the small CoC and tile planes --
+ * with gamma = 0; every m there is at most ceil(max_radius / s).  Its output is the small image O (NaN where the small pixel is not valid).
+ *   6. Compose, per valid pixel X = (i, j).  Rows: u = 2i + 1 - s;  a0 = floor(u / 2s) (floor division: -1 for the first rows);
+ * fy = T(u - 2s*a0) / T(2s), an odd multiple of 1/2s, exact;  the taps are the small rows clamp(a0, 0, h-1) with weight 1 - fy and
+ * clamp(a0+1, 0, h-1) with weight fy (both may be the same row).  Columns the same with v = 2j + 1 - s, b0, fx, w.  The four tap weights
+ * are the products row weight * column weight (exact), visited in the order (row tap 0, column tap 0), (1, 0), (0, 1), (1, 1).  A tap on
+ * a small pixel that is not valid is skipped;  ws = ws + wt,  acc[k] = acc[k] + wt*O_q[k], from +0;  U[k] = acc[k] / ws.  X's own block
+ * holds X, so it is valid, and it is always one of the taps, with a positive weight: ws > 0.
+ *       t = clamp01((R_X - T(4)) * T(0.25))        (R_X from the wide plane)
+ *       out[k] = t <= 0 ? N[k] : (t >= 1 ? U[k] : N[k] + t*(U[k] - N[k]))
+ * Then sqrt per channel if gamma = 1.  A pixel that is not valid is a quiet NaN in all three channels.  (tests/wide_aperture_ref.py
+ * restates all of this on the CPU, twice, and the device agrees on the bits.)  A pixel with R < 4 is the narrow stage's on the bits; sharp
+ * foreground in front of a wide background stays as sharp as the block above leaves it.
+ *   Workspace.  Caller-owned, rtw_wide_aperture_work_bytes(width, height, elem_bytes, max_radius) bytes (monotone in the frame size; < 0:
+ * an error code; for max_radius <= 8 what the block above reports), 16-byte aligned.  With r4(n) = n rounded up to a multiple of four,
+ * t = TH*TW and t' = th*tw, the regions follow each other in this order, each beginning on a multiple of four ELEMENTS:
+ *       the narrow stage's workspace    4*W*H + r4(t)      its CoC plane (Rm = 8) and tile plane
+ *       the wide CoC plane              4*W*H
+ *       the wide tile plane             r4(t)
+ *       N                               r4(3*W*H)
+ *       the small colour                r4(3*w*h)
+ *       the small CoC plane             4*w*h
+ *       the small tile plane            r4(t')
+ *       O                               r4(3*w*h)
+ * The layout is public, like the state's.
+ *
+ * rtw_wide_aperture_device_*: SIX launches for max_radius > 8 (prepare and gather of the block above with max_radius 8; prepare with
+ * Rm = max_radius; reduce; the gather on the small frame; compose), TWO otherwise, asynchronous on `hip_stream` of the device b->device
+ * (-1: the current one); rtw_stats() is left alone.  Alignment and aliasing as in the block above.
+ *   rtw_wide_aperture_*: the host-buffer form, blocking, through the cached per-device context.
+ *   rtw_render_wide_aperture_*: the one-call form of the block above with this stage at its end, argument for argument; here and only
+ * here b->lens_radius == -1 means "the camera's own".  On the bits the chain of the single calls on the pinhole copy followed by
+ * rtw_wide_aperture_*.
+ *   Refusals, all decided before any HIP call: those of the block above with the same codes, max_radius outside 1..32 in place of 1..8;
+ * rtw_wide_aperture_work_bytes refuses such a max_radius with -2 as well.
+ *   Left out on purpose: batched views; sequence, animation, upsampler and present one-call forms; device lists;
+ * the Julia shim; bokeh shapes; jittered taps; skipping the narrow gather on tiles that lie wholly at t >= 1 (no bit would change, but the
+ * gather kernel would).  Additive to ABI 4: detected by symbol lookup. */
+#define RTW_WIDE_APERTURE_MAX_RADIUS 32     /* the largest circle of confusion, in pixels */
+typedef struct {
+    int32_t max_radius;         /* 1..32: where the circle of confusion is clamped, in pixels; <= 8: the defocus stage itself */
+    int32_t flags;              /* 0 */
+    int32_t gamma;              /* 1 = sqrt per channel at the very end, 0 = linear */
+    int32_t device;             /* -1 = current */
+    int32_t reserved[2];        /* 0 */
+    double  lens_radius;        /* >= 0, finite, world units: half the aperture (rtw_render_wide_aperture_* only: -1 = the camera's own) */
+    double  focus_dist;         /* 0 = the camera's own focus plane; > 0, finite: an override */
+} rtw_wide_aperture_t;          /* 40 bytes */
+int64_t rtw_wide_aperture_work_bytes(int32_t width, int32_t height, int32_t elem_bytes, int32_t max_radius);
+int rtw_wide_aperture_device_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image,
+                                 const void *d_features, void *d_work, void *d_out, void *hip_stream);
+int rtw_wide_aperture_device_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image,
+                                 const void *d_features, void *d_work, void *d_out, void *hip_stream);
+int rtw_wide_aperture_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const float *image, const float *features,
+                          float *out);
+int rtw_wide_aperture_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const double *image, const double *features,
+                          double *out);
+int rtw_render_wide_aperture_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d /* may be NULL */,
+                                 const rtw_wide_aperture_t *b, float *out);
+int rtw_render_wide_aperture_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d /* may be NULL */,
+                                 const rtw_wide_aperture_t *b, double *out);
+
 /* Present stage: display-ready 8-bit frames from the device.  Every pipeline above ends in T elements in the column-major layout of the
  * render entry points; a window, a PNG or a video encoder wants 8-bit rows.  One kernel clips, rounds, packs and transposes in HBM, and the
  * D2H behind it moves 3 or 4 bytes per pixel instead of 12 or 24.

@@ -42,6 +42,7 @@ from .temporal import (  # noqa: F401
 )
 from .motion_blur import make_motion_blur, motion_blur, motion_blur_into, motion_blur_work_bytes  # noqa: F401
 from .defocus import defocus, defocus_into, defocus_work_bytes, make_defocus, render_defocused  # noqa: F401
+from .wide_aperture import make_wide_aperture, render_wide_aperture, wide_aperture, wide_aperture_into, wide_aperture_work_bytes  # noqa: F401
 from .present import (  # noqa: F401
     make_present, present, present_batch_into, present_bytes, present_into, render_presented, render_presented_batch,
 )
@@ -69,5 +70,6 @@ __all__ = [
     "motion_table", "first_hit_motion", "first_hit_motion_into", "temporal_step_animated", "temporal_step_animated_into", "render_animation",
     "make_motion_blur", "motion_blur_work_bytes", "motion_blur", "motion_blur_into",
     "make_defocus", "defocus_work_bytes", "defocus", "defocus_into", "render_defocused",
+    "make_wide_aperture", "wide_aperture_work_bytes", "wide_aperture", "wide_aperture_into", "render_wide_aperture",
     "make_present", "present_bytes", "present", "present_into", "present_batch_into", "render_presented", "render_presented_batch",
 ]

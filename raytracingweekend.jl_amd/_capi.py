@@ -47,6 +47,8 @@ SYMBOLS = [
     "rtw_render_blurred_f32", "rtw_render_blurred_f64",
     "rtw_defocus_work_bytes", "rtw_defocus_device_f32", "rtw_defocus_device_f64", "rtw_defocus_f32", "rtw_defocus_f64",
     "rtw_render_defocused_f32", "rtw_render_defocused_f64",
+    "rtw_wide_aperture_work_bytes", "rtw_wide_aperture_device_f32", "rtw_wide_aperture_device_f64", "rtw_wide_aperture_f32", "rtw_wide_aperture_f64",
+    "rtw_render_wide_aperture_f32", "rtw_render_wide_aperture_f64",
     "rtw_present_bytes", "rtw_present_device_f32", "rtw_present_device_f64", "rtw_present_batch_device_f32", "rtw_present_batch_device_f64",
     "rtw_present_f32", "rtw_present_f64", "rtw_render_presented_f32", "rtw_render_presented_f64", "rtw_render_presented_batch_f32",
     "rtw_render_presented_batch_f64",
@@ -153,6 +155,14 @@ class Defocus(C.Structure):
 
 
 assert C.sizeof(Defocus) == 40
+
+
+class WideAperture(C.Structure):
+    """rtw_wide_aperture_t"""
+    _fields_ = list(Defocus._fields_)
+
+
+assert C.sizeof(WideAperture) == 40
 
 
 class Present(C.Structure):
@@ -272,6 +282,10 @@ def lib():
         getattr(L, "rtw_defocus_device_" + sfx).argtypes = [df, C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_defocus_" + sfx).argtypes = [df, C.POINTER(CamT), i32, i32, ptr, ptr, ptr]
         getattr(L, "rtw_render_defocused_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), C.POINTER(Params), C.POINTER(Denoise), df, ptr]
+        wa = C.POINTER(WideAperture)
+        getattr(L, "rtw_wide_aperture_device_" + sfx).argtypes = [wa, C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_wide_aperture_" + sfx).argtypes = [wa, C.POINTER(CamT), i32, i32, ptr, ptr, ptr]
+        getattr(L, "rtw_render_wide_aperture_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), C.POINTER(Params), C.POINTER(Denoise), wa, ptr]
         pr, dn = C.POINTER(Present), C.POINTER(Denoise)
         getattr(L, "rtw_present_device_" + sfx).argtypes = [pr, i32, i32, ptr, ptr, ptr]
         getattr(L, "rtw_present_batch_device_" + sfx).argtypes = [pr, i32, i32, i32, ptr, ptr, ptr]
@@ -286,6 +300,8 @@ def lib():
     L.rtw_velocity_blur_work_bytes.restype = C.c_int64
     L.rtw_defocus_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_defocus_work_bytes.restype = C.c_int64
+    L.rtw_wide_aperture_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.rtw_wide_aperture_work_bytes.restype = C.c_int64
     L.rtw_history_moment_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_history_moment_bytes.restype = C.c_int64
     L.rtw_reproject_table_bytes.argtypes = [C.c_int32, C.c_int32]

@@ -20,9 +20,9 @@ static void defocus_constants(const rtw_defocus_t *b, const CamT *cam, int32_t w
 
 // Everything about a defocus that is decided without a device and without a pointer.
 template <typename CamT>
-int validate_defocus_t(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, int elem_bytes) {
+int validate_defocus_t(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, int elem_bytes, int top = RTW_DEFOCUS_MAX_RADIUS) {
     if (!b || !cam) return fail(-1, "null defocus parameters or camera");
-    if (b->max_radius < 1 || b->max_radius > RTW_DEFOCUS_MAX_RADIUS) return fail(-2, "max_radius must be in 1..%d (got %d)", RTW_DEFOCUS_MAX_RADIUS, b->max_radius);
+    if (b->max_radius < 1 || b->max_radius > top) return fail(-2, "max_radius must be in 1..%d (got %d)", top, b->max_radius);
     if (b->flags != 0) return fail(-2, "unknown defocus flags 0x%x", b->flags);
     if (b->gamma != 0 && b->gamma != 1) return fail(-2, "gamma must be 0 or 1 (got %d)", b->gamma);
     if (b->device < -1) return fail(-2, "bad device %d", b->device);
@@ -39,6 +39,8 @@ int validate_defocus_t(const rtw_defocus_t *b, const CamT *cam, int32_t width, i
 }
 int validate_defocus(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height) { return validate_defocus_t(b, cam, width, height, 4); }
 int validate_defocus(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height) { return validate_defocus_t(b, cam, width, height, 8); }
+int validate_defocus_top(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, int top) { return validate_defocus_t(b, cam, width, height, 4, top); }
+int validate_defocus_top(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, int top) { return validate_defocus_t(b, cam, width, height, 8, top); }
 
 // the workspace: the CoC plane (a 4-element slot per pixel) and the tile plane (one element per tile, rounded up to a 16-byte multiple)
 static long long tiles_of(int32_t width, int32_t height) {
@@ -46,9 +48,10 @@ static long long tiles_of(int32_t width, int32_t height) {
 }
 static long long work_bytes(int32_t width, int32_t height, int elem_bytes) { return ((long long)width * height * 4 + ((tiles_of(width, height) + 3) & ~3ll)) * elem_bytes; }
 
-// Enqueue the stage on `stream` of the current device (validate_defocus has accepted the call): TWO launches, no record.
+// The stage's two launches one by one (launch_defocus below; rtw_wide_aperture.hip composes them): the prepare launch with the clamp `rm`
+// over the image and the features into a CoC plane and its tile plane ...
 template <typename T, typename CamT>
-int launch_defocus(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream) {
+int launch_prepare(const rtw_defocus_t *b, int rm, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream) {
     using V = typename rtw::DnVec<T>::type;
     const unsigned tiles = (unsigned)tiles_of(width, height);                 // (fewer than the frame rule's 8 x 8 ones: one 32-bit grid dimension holds them)
     double hh, focus, K;
@@ -61,22 +64,43 @@ int launch_defocus(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32
         memcpy(&U, e, 29 * sizeof(T));
     }
     U.W = width; U.H = height;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((rtw::df_prepare<T>), dim3(tiles), dim3(256), 0, stream, U, (T)focus, (T)K, (T)rm, (const T *)d_image, (const V *)d_features, (V *)d_coc, (T *)d_tile);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+// ... and the gather of a frame of any size over its image, CoC plane and tile plane; mmax >= every radius of the plane, at most 8
+template <typename T>
+int launch_gather(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream) {
+    using V = typename rtw::DnVec<T>::type;
+    const unsigned tiles = (unsigned)tiles_of(width, height);
     rtw::DfDist<T> tab;
     for (int dj = 0; dj <= rtw::DF_MAX_RADIUS; ++dj)
         for (int di = 0; di <= rtw::DF_MAX_RADIUS; ++di) tab.d[dj * (rtw::DF_MAX_RADIUS + 1) + di] = std::sqrt((T)(di * di + dj * dj));
-    const size_t lds = (size_t)(rtw::DF_TILE + 2 * b->max_radius) * rtw::DF_COL * sizeof(T);      // (at most 32 columns: 24 / 48 KB)
+    const size_t lds = (size_t)(rtw::DF_TILE + 2 * mmax) * rtw::DF_COL * sizeof(T);      // (at most 32 columns: 24 / 48 KB)
+    (void)hipGetLastError();
+    hipLaunchKernelGGL((rtw::df_gather<T>), dim3(tiles), dim3(256), lds, stream, width, height, mmax, gamma, tab, (const T *)d_image, (const V *)d_coc, (const T *)d_tile, (T *)d_out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+int launch_defocus_prepare_f32(const rtw_defocus_t *b, int rm, const rtw_camera_f32 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st) { return launch_prepare<float>(b, rm, cam, w, h, img, feat, coc, tile, st); }
+int launch_defocus_prepare_f64(const rtw_defocus_t *b, int rm, const rtw_camera_f64 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st) { return launch_prepare<double>(b, rm, cam, w, h, img, feat, coc, tile, st); }
+int launch_defocus_gather_f32(int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st) { return launch_gather<float>(w, h, mmax, gamma, img, coc, tile, out, st); }
+int launch_defocus_gather_f64(int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st) { return launch_gather<double>(w, h, mmax, gamma, img, coc, tile, out, st); }
+
+// Enqueue the stage on `stream` of the current device (validate_defocus has accepted the call): TWO launches, no record.
+template <typename T, typename CamT>
+int launch_defocus(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream) {
+    using V = typename rtw::DnVec<T>::type;
     V *coc = (V *)d_work;
     T *tile = (T *)(coc + (size_t)width * (size_t)height);
     // (measurement aid, tools/gpu_defocus.py: events around every launch, reported on stderr -- this one blocks)
     static const bool profile = aid_flag("RTW_TEMPORAL_PROFILE");
     struct Events { hipEvent_t e[3] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
     if (profile) { for (hipEvent_t &x : events.e) HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventRecord(events.e[0], stream)); }
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((rtw::df_prepare<T>), dim3(tiles), dim3(256), 0, stream, U, (T)focus, (T)K, (T)b->max_radius, (const T *)d_image, (const V *)d_features, coc, tile);
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch_prepare<T>(b, b->max_radius, cam, width, height, d_image, d_features, coc, tile, stream)) return rc;
     if (profile) HIP_TRY(hipEventRecord(events.e[1], stream));
-    hipLaunchKernelGGL((rtw::df_gather<T>), dim3(tiles), dim3(256), lds, stream, width, height, b->max_radius, b->gamma, tab, (const T *)d_image, (const V *)coc, (const T *)tile, (T *)d_out);
-    HIP_TRY(hipGetLastError());
+    if (int rc = launch_gather<T>(width, height, b->max_radius, b->gamma, d_image, coc, tile, d_out, stream)) return rc;
     if (profile) {
         float ms[2] = {0, 0};
         HIP_TRY(hipEventRecord(events.e[2], stream));

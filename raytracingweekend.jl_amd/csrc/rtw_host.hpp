@@ -21,6 +21,7 @@
 //   rtw_motion.hip       the first-hit motion pass over moving spheres: its checks, the motion table, the one launch of its kernel (rtw_motion.hpp), the device-resident entry points
 //   rtw_motion_blur.hip  the motion-blur stage on the motion plane: its checks, the workspace, the three launches of its kernels (rtw_motion_blur.hpp), the device-resident entry points
 //   rtw_defocus.hip      the defocus stage (depth of field on the depth plane): its checks, the host constants, the workspace, the two launches of its kernels (rtw_defocus.hpp), the device-resident entry points
+//   rtw_wide_aperture.hip  the wide-aperture stage (circles of confusion up to 32 px): its checks, the workspace, the six launches (the defocus stage's kernels at two sizes, rtw_wide_aperture.hpp between and behind them), the device-resident entry points
 //   rtw_present.hip      the present stage: its checks, the one launch of its kernel (rtw_present.hpp) for one frame or a batch, the device-resident entry points
 //   (rtw_scene_view.hpp: what both launch functions derive from their arguments; rtw_instances.hpp: the one table of the trace kernel's instances)
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
@@ -420,6 +421,26 @@ int launch_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_
 int launch_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream);
 inline int launch_defocus_t(const rtw_defocus_t *b, const rtw_camera_f32 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_defocus_f32(b, c, w, h, img, feat, work, out, st); }
 inline int launch_defocus_t(const rtw_defocus_t *b, const rtw_camera_f64 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_defocus_f64(b, c, w, h, img, feat, work, out, st); }
+// Its two launches one by one, for the wide-aperture stage: validate_defocus_top is validate_defocus with max_radius in 1..top;
+// launch_defocus_prepare_* is the prepare launch with the clamp `rm` (b->max_radius is not read) into a CoC plane and its tile plane;
+// launch_defocus_gather_* is the gather of a frame of any size over an image, a CoC plane and a tile plane, mmax (1..8) >= every radius there.
+int validate_defocus_top(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, int top);
+int validate_defocus_top(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, int top);
+int launch_defocus_prepare_f32(const rtw_defocus_t *b, int rm, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream);
+int launch_defocus_prepare_f64(const rtw_defocus_t *b, int rm, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream);
+int launch_defocus_gather_f32(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream);
+int launch_defocus_gather_f64(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream);
+
+// rtw_wide_aperture.hip -- the wide-aperture stage (include/rtw_hip.h rtw_wide_aperture_*): circles of confusion up to 32 px through a reduced
+// copy of the frame.  validate_wide_aperture: every check that needs neither a device nor a pointer (the defocus stage's, max_radius in 1..32).
+// launch_wide_aperture: enqueue the stage (SIX launches, or the defocus stage's two when max_radius <= 8; no record) on `stream` of the
+// current device; d_work: rtw_wide_aperture_work_bytes bytes.
+int validate_wide_aperture(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height);
+int validate_wide_aperture(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height);
+int launch_wide_aperture_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream);
+int launch_wide_aperture_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream);
+inline int launch_wide_aperture_t(const rtw_wide_aperture_t *b, const rtw_camera_f32 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_wide_aperture_f32(b, c, w, h, img, feat, work, out, st); }
+inline int launch_wide_aperture_t(const rtw_wide_aperture_t *b, const rtw_camera_f64 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_wide_aperture_f64(b, c, w, h, img, feat, work, out, st); }
 
 // rtw_present.hip -- the present stage (include/rtw_hip.h rtw_present_*).  validate_present: every check of a call that needs neither a device
 // nor a pointer -- the parameters, the frame, n_views (0: one frame; a batch's count through batch_views) and the size of the launch.

@@ -98,4 +98,24 @@ struct MomentLayout : TemporalLayout {
     }
 };
 
+// The workspace of the wide-aperture stage (include/rtw_hip.h rtw_wide_aperture_*), in ELEMENTS: every region begins on a multiple of four.
+// scale 1 (max_radius <= 8): the defocus stage's workspace alone -- the CoC plane and the tile plane; everything else is empty.
+struct WideApertureLayout {
+    int scale, lo_width, lo_height, lo_mmax;
+    size_t narrow, off_coc, off_tile, off_n, off_lo_img, off_lo_coc, off_lo_tile, off_lo_out, total;
+    static size_t r4(size_t n) { return (n + 3) & ~(size_t)3; }
+    static size_t tiles(size_t width, size_t height) { return ((height + 15) / 16) * ((width + 15) / 16); }
+    WideApertureLayout(int32_t width, int32_t height, int32_t max_radius) {
+        scale = max_radius <= 8 ? 1 : (max_radius <= 16 ? 2 : 4);
+        lo_width = (width + scale - 1) / scale; lo_height = (height + scale - 1) / scale;
+        lo_mmax = (max_radius + scale - 1) / scale;
+        const size_t n = (size_t)width * (size_t)height, n_lo = (size_t)lo_width * (size_t)lo_height;
+        narrow = n * 4 + r4(tiles(width, height));
+        off_coc = narrow; off_tile = off_coc + n * 4; off_n = off_tile + r4(tiles(width, height));
+        off_lo_img = off_n + r4(n * 3); off_lo_coc = off_lo_img + r4(n_lo * 3); off_lo_tile = off_lo_coc + n_lo * 4;
+        off_lo_out = off_lo_tile + r4(tiles(lo_width, lo_height));
+        total = scale == 1 ? narrow : off_lo_out + r4(n_lo * 3);
+    }
+};
+
 }  // namespace rtwh

@@ -448,6 +448,44 @@ int render_host_defocused(const SceneT *scene, const CamT *cam, const rtw_params
     });
 }
 
+// Render through the pinhole and apply a wide aperture in one call (rtw_render_wide_aperture_*): render_host_defocused above with the
+// wide-aperture stage's launches (six, or two when max_radius <= 8) and workspace in place of the defocus stage's.
+template <typename T, typename SceneT, typename CamT>
+int render_host_wide_aperture(const SceneT *scene, const CamT *cam, const rtw_params *p, const rtw_denoise_t *d, const rtw_wide_aperture_t *b, T *out) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !cam || !b || !out) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = validate_features(p, 0, 1, &nch, &cs)) return rc;
+    if (scene->n < 0) return fail(-2, "negative sphere count");
+    if (d) if (int rc = validate_denoise(d, p->width, p->height)) return rc;
+    rtw_wide_aperture_t bb = *b;
+    if (bb.lens_radius == -1) bb.lens_radius = (double)cam->lens_radius;      // (here and only here: the camera's own aperture)
+    if (int rc = validate_wide_aperture(&bb, cam, p->width, p->height)) return rc;
+    bb.gamma = p->gamma != 0;                                                  // (b's gamma and device are judged, then replaced by p's)
+    CamT pin = *cam;
+    pin.lens_radius = 0;
+    DeviceGuard guard;
+    release_last();
+    const DenoiseRegions<T> R(p->width, p->height, 0);
+    DevLayout L{R.total};
+    const size_t off_wa = L.add(R.img_b), off_work = L.add(WideApertureLayout(p->width, p->height, bb.max_radius).total * sizeof(T));
+    SideRec frec;                                             // (the feature pass's record)
+    return render_one_device(p->device, scene, p, L.total, off_wa, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+        char *base = (char *)hc->d_img;
+        int rc;
+        if (d) {
+            rc = launch_filtered(hc, q, &pin, 0, nullptr, 0, d, nch, R, rec, rctx, frec);
+        } else {
+            q.gamma = 0;
+            rc = launch_render_t(hc->scene, &pin, 0, nullptr, &q, base, hc->stream, rec, rctx);
+            if (!rc) rc = launch_features_t(hc->scene, &pin, 0, nullptr, &q, 0, nch, base + R.off_feat, hc->stream, &frec.rec, &frec.ctx);
+        }
+        bb.device = hc->device;
+        if (!rc) rc = launch_wide_aperture_t(&bb, &pin, p->width, p->height, base + (d ? R.off_out : 0), base + R.off_feat, base + off_work, base + off_wa, hc->stream);
+        return rc;
+    });
+}
+
 // N cameras along a path with history reuse (rtw_render_sequence_*): the one-device path above with a device buffer that holds the linear images
 // (ONE batched render with gamma 0), the features (ONE batched pass over all chunks), the accumulated images (n_views temporal steps in view
 // order, two states ping-pong) and, with `d`, the filtered images and the filter's workspace (ONE batched filter pass); 2 + n_views (+ 1 + levels)
@@ -798,6 +836,12 @@ int rtw_render_defocused_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *c
 }
 int rtw_render_defocused_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, const rtw_defocus_t *b, double *out) {
     return render_host_defocused<double>(scene, cam, p, d, b, out);
+}
+int rtw_render_wide_aperture_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, const rtw_wide_aperture_t *b, float *out) {
+    return render_host_wide_aperture<float>(scene, cam, p, d, b, out);
+}
+int rtw_render_wide_aperture_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, const rtw_wide_aperture_t *b, double *out) {
+    return render_host_wide_aperture<double>(scene, cam, p, d, b, out);
 }
 int rtw_render_path_clamped_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                                  const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, float *out) {

@@ -1,5 +1,5 @@
 // rtw_stage_host.hip -- the pure stages on host buffers (rtw_denoise_* / rtw_filter_batch_*, rtw_present_*, rtw_upsample_*, the temporal
-// steps, rtw_velocity_blur_*, rtw_defocus_*): each is its null checks, the stage's validate_*, a layout of the device buffer, the alias
+// steps, rtw_velocity_blur_*, rtw_defocus_*, rtw_wide_aperture_*): each is its null checks, the stage's validate_*, a layout of the device buffer, the alias
 // check of its host buffers and ONE call of stage_one_device (rtw_host_ctx.hpp) with the stage's launch.  A leased context's scene is
 // left alone and this thread's last render (rtw_stats) is not touched.  n_views == 0 is the single-frame entry point, n_views != 0 the
 // batched one (rtw_host.hpp batch_views).
@@ -108,6 +108,19 @@ int defocus_host(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t
         {R.off_out, out, R.img_b});
 }
 
+// The wide-aperture stage (rtw_wide_aperture_*): two H2D (the image, the features), the stage's six launches (two when max_radius <= 8), ONE
+// D2H.  The device buffer is the defocus stage's with this stage's workspace.
+template <typename T, typename CamT>
+int wide_aperture_host(const rtw_wide_aperture_t *b, const CamT *cam, int32_t width, int32_t height, const T *image, const T *features, T *out) {
+    if (!b || !cam || !image || !features || !out) return fail(-1, "null argument");
+    if (int rc = validate_wide_aperture(b, cam, width, height)) return rc;
+    const DenoiseLayout R(sizeof(T), width, height, 0, WideApertureLayout(width, height, b->max_radius).total * sizeof(T));
+    if (int rc = check_alias({{"out", out, R.img_b}}, {{"image", image, R.img_b}, {"features", features, R.feat_b}})) return rc;
+    return stage_one_device<T>(b->device, nullptr, R.total, "the wide-aperture stage's inputs", {{0, image, R.img_b}, {R.off_feat, features, R.feat_b}},
+        [&](HostCtx *hc, char *base) { return launch_wide_aperture_t(b, cam, width, height, base, base + R.off_feat, base + R.off_work, base + R.off_out, hc->stream); },
+        {R.off_out, out, R.img_b});
+}
+
 }  // namespace rtwh
 
 using namespace rtwh;
@@ -193,6 +206,12 @@ int rtw_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t w
 }
 int rtw_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const double *image, const double *features, double *out) {
     return defocus_host<double>(b, cam, width, height, image, features, out);
+}
+int rtw_wide_aperture_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const float *image, const float *features, float *out) {
+    return wide_aperture_host<float>(b, cam, width, height, image, features, out);
+}
+int rtw_wide_aperture_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const double *image, const double *features, double *out) {
+    return wide_aperture_host<double>(b, cam, width, height, image, features, out);
 }
 
 }  // extern "C"

@@ -1,0 +1,98 @@
+"""Wide apertures (include/rtw_hip.h ``rtw_wide_aperture_*``): depth of field with circles of confusion up to 32 px.  The defocus stage
+(``defocus.py``) clamps every circle at 8 px; at 1920 x 1080 the headline camera's far field is 15 px wide.  This stage runs that stage
+as it is for what is nearly sharp, gathers a copy of the frame reduced by 2 (``max_radius`` 9..16) or 4 (17..32) with the same gather for
+what is wide, and blends the two by the radius (from 4 px, the narrow result alone, to 8 px, the wide one alone).  With ``max_radius <= 8``
+it IS the defocus stage, on the bits.  The definition is in the header; tests/wide_aperture_ref.py restates it on the CPU, twice, and the
+device agrees on the bits.  All compute happens in librtw_hip.so; there is no CPU fallback.
+
+Defaults: ``max_radius=32, focus_dist=0`` (the camera's own focus plane), ``gamma=True``; what they buy on the CPU witness: DESIGN.md section 7.27.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _capi
+from .defocus import _DENOISE_KEYS, _camera_arg
+from .denoise import make_denoise
+from .render import _frame_height, _record_stats
+from .structs import Camera, flatten_scene
+
+_STAGE_KEYS = ("lens_radius", "focus_dist", "max_radius")
+
+
+def make_wide_aperture(lens_radius, focus_dist=0.0, max_radius=32, gamma=True, device=-1):
+    """-> the ``rtw_wide_aperture_t`` of these keywords: those of ``make_defocus`` with ``max_radius`` in 1..32"""
+    return _capi.WideAperture(int(max_radius), 0, 1 if gamma else 0, int(device), (C.c_int32 * 2)(0, 0), float(lens_radius), float(focus_dist))
+
+
+def wide_aperture_work_bytes(image_width, image_height, elem_type=np.float32, max_radius=32):
+    """bytes of the caller-owned workspace (the header lists its regions); for ``max_radius <= 8`` what ``defocus_work_bytes`` reports"""
+    n = _capi.lib().rtw_wide_aperture_work_bytes(int(image_width), int(image_height), np.dtype(elem_type).itemsize, int(max_radius))
+    if n < 0:
+        _capi.check(int(n))
+    return int(n)
+
+
+def wide_aperture(image, features, cam, **params):
+    """The stage on host arrays (rtw_wide_aperture_*): ``image`` [H, W, 3] (linear, rendered through the pinhole) and ``features`` [H, W, 8]
+    -- or the dict ``render_features`` returns -- of the frame seen through ``cam``, whose own ``lens_radius`` is not read: the aperture is
+    the keyword.  -> the image [H, W, 3]; a pixel that is not valid is NaN.  Keywords: ``make_wide_aperture``.  Blocking."""
+    if isinstance(features, dict):
+        features = features["raw"]
+    image, features = np.asarray(image), np.asarray(features)
+    T = image.dtype
+    if T not in (np.dtype(np.float32), np.dtype(np.float64)) or features.dtype != T:
+        raise TypeError("image and features must both be float32 or both float64")
+    if image.ndim != 3 or image.shape[-1] != 3 or features.shape != image.shape[:-1] + (8,):
+        raise ValueError(f"expected image [H, W, 3] and features [H, W, 8], got {image.shape} and {features.shape}")
+    if 0 in image.shape:
+        raise ValueError("empty image")
+    H, W = image.shape[:2]
+    Cm = _camera_arg(cam, T.type, "cam")
+    img, feat = (np.ascontiguousarray(np.swapaxes(a, 0, 1)) for a in (image, features))      # the library's layout: pixel (i, j) at j*H + i
+    out = np.empty((W, H, 3), dtype=T)
+    fn = getattr(_capi.lib(), "rtw_wide_aperture_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(C.byref(make_wide_aperture(**params)), C.byref(Cm), W, H, *(a.ctypes.data_as(C.c_void_p) for a in (img, feat, out))))
+    return np.swapaxes(out, 0, 1)
+
+
+def wide_aperture_into(d_out_ptr, d_work_ptr, d_image_ptr, d_features_ptr, cam, image_width, image_height, *, elem_type=np.float32, stream=0, **params):
+    """The device-resident stage (rtw_wide_aperture_device_*): six launches on ``stream`` (two when ``max_radius <= 8``).  DEVICE pointers in
+    the library's layout (pixel (i, j) at slot ``j*H + i``): the linear image and the features; ``d_work_ptr``: ``wide_aperture_work_bytes``
+    bytes for the same ``max_radius``, 16-byte aligned, which afterwards hold the regions the header lists; ``d_out_ptr`` aliases nothing.
+    Keywords: ``make_wide_aperture``."""
+    T = np.dtype(elem_type).type
+    Cm = _camera_arg(cam, T, "cam")
+    fn = getattr(_capi.lib(), "rtw_wide_aperture_device_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(C.byref(make_wide_aperture(**params)), C.byref(Cm), int(image_width), int(image_height),
+                   *(C.c_void_p(int(q)) for q in (d_image_ptr, d_features_ptr, d_work_ptr, d_out_ptr)), C.c_void_p(int(stream))))
+
+
+def render_wide_aperture(scene, cam, image_width=400, n_samples=1, *, depth=16, seed=1, n_chunks=0, device=-1, gamma=True, denoise=None, wide_aperture=None):
+    """Render through the pinhole and apply the lens afterwards, in one call on the device (rtw_render_wide_aperture_*): ``render_defocused``
+    with this stage at the end of the chain.  ``wide_aperture``: None, or a dict of ``make_wide_aperture``'s keywords ``lens_radius``
+    (default: the camera's own), ``focus_dist``, ``max_radius``.  Returns ``img[i, j, :]`` -- on the bits the chain of the single calls on the
+    pinhole copy followed by ``wide_aperture``; ``last_stats()`` reports the render."""
+    if not isinstance(cam, Camera):
+        raise TypeError("cam must be a Camera")
+    T = cam.elem_type
+    dk = {} if denoise in (None, False, True) else dict(denoise)
+    if set(dk) - set(_DENOISE_KEYS):
+        raise ValueError(f"denoise takes the keywords {_DENOISE_KEYS}, got {sorted(set(dk) - set(_DENOISE_KEYS))}")
+    bk = {} if wide_aperture is None else dict(wide_aperture)
+    if set(bk) - set(_STAGE_KEYS):
+        raise ValueError(f"wide_aperture takes the keywords {_STAGE_KEYS}, got {sorted(set(bk) - set(_STAGE_KEYS))}")
+    bk.setdefault("lens_radius", -1.0)                       # (the one-call form alone: the camera's own)
+    height = _frame_height(image_width, n_samples)
+    L = _capi.lib()
+    flat = scene if isinstance(scene, dict) else flatten_scene(scene, T)
+    S, keep = _capi.make_scene(flat, T)
+    P = _capi.make_params(image_width, height, n_samples, depth, seed, n_chunks, 0, 1, device, 1 if gamma else 0, 0)
+    D = make_denoise(gamma=gamma, **dk) if denoise else None
+    B = make_wide_aperture(gamma=gamma, **bk)
+    out = np.empty(height * int(image_width) * 3, dtype=T)
+    fn = getattr(L, "rtw_render_wide_aperture_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(C.byref(S), C.byref(_capi.make_camera(cam, T)), C.byref(P), C.byref(D) if D is not None else None, C.byref(B), out.ctypes.data_as(C.c_void_p)))
+    del keep
+    _record_stats(L)
+    return out.reshape(int(image_width), height, 3).transpose(1, 0, 2)
