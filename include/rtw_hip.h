@@ -1315,8 +1315,9 @@ int rtw_render_blurred_f64(const rtw_scene_f64 *scenes, const rtw_camera_f64 *ca
  * camera whose hor.hor or whose focus in use is not finite and positive, width or height < 1, elem_bytes other than 4 or 8, misaligned or
  * aliasing pointers -> -2; the denoiser's frame rule -> -5; the one-call form additionally everything rtw_render_features_* (and, with `d`,
  * rtw_denoise_*) refuses for its arguments, with its code.
- *   Left out on purpose: batched views; sequence, animation, upsampler and present one-call forms (the device stages
- * compose on the caller's stream); device lists; the Julia shim; radii beyond 8 px (a half-resolution pass); bokeh shapes; jittered taps.
+ *   Left out on purpose: sequence, animation, upsampler and present one-call forms (the device stages compose on the
+ * caller's stream); device lists; the Julia shim; radii beyond 8 px (a half-resolution pass); bokeh shapes; jittered taps.  (No longer left
+ * out: batched views -- rtw_lens_batch_* below with max_radius <= 8.)
  * Additive to ABI 4: detected by symbol lookup. */
 #define RTW_DEFOCUS_MAX_RADIUS 8     /* the largest circle of confusion, in pixels */
 #define RTW_DEFOCUS_TILE 16          /* the tile's edge, in pixels */
@@ -1401,8 +1402,8 @@ int rtw_render_defocused_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *c
  * rtw_wide_aperture_*.
  *   Refusals, all decided before any HIP call: those of the block above with the same codes, max_radius outside 1..32 in place of 1..8;
  * rtw_wide_aperture_work_bytes refuses such a max_radius with -2 as well.
- *   Left out on purpose: batched views; sequence, animation, upsampler and present one-call forms; device lists;
- * the Julia shim; bokeh shapes; jittered taps; skipping the narrow gather on tiles that lie wholly at t >= 1 (no bit would change, but the
+ *   Left out on purpose: sequence, animation, upsampler and present one-call forms; device lists;
+ * the Julia shim (batched views no longer: rtw_lens_batch_* below); bokeh shapes; jittered taps; skipping the narrow gather on tiles that lie wholly at t >= 1 (no bit would change, but the
  * gather kernel would).  Additive to ABI 4: detected by symbol lookup. */
 #define RTW_WIDE_APERTURE_MAX_RADIUS 32     /* the largest circle of confusion, in pixels */
 typedef struct {
@@ -1427,6 +1428,66 @@ int rtw_render_wide_aperture_f32(const rtw_scene_f32 *scene, const rtw_camera_f3
                                  const rtw_wide_aperture_t *b, float *out);
 int rtw_render_wide_aperture_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d /* may be NULL */,
                                  const rtw_wide_aperture_t *b, double *out);
+
+/* Batched lens stages: N views, or ONE frame under N lens settings, in each launch.  A stereo pair, a grid of previews or N candidate
+ * cameras go through one batched render, one batched feature pass and one batched filter; the block above then costs N x 6 launches.  And
+ * the first thing a user does with a lens that is a parameter of a cheap pass is a focus pull or an aperture bracket: one rendered frame
+ * under N lenses.  Both are the batch below: n_views views in the SIX launches of the block above (TWO for max_radius <= 8, where the batch
+ * is the batched defocus stage -- there is one family of names, rtw_lens_*, for both stages), whatever n_views is.  There is no new
+ * arithmetic.
+ *
+ * The definition.  View v of the batch is, bit for bit, rtw_wide_aperture_device_* with cams[v], lens_radii[v], focus_dists[v] and b's
+ * max_radius and gamma on frame v: the image and every region of the workspace.
+ *   The lens table.  rtw_lens_table_* (pure host code) writes 32 elements of T per view into the HOST buffer `table`
+ * (rtw_lens_table_bytes(n_views, elem_bytes) = 32*n_views*elem_bytes bytes); the caller uploads it.  Elements 0..28 are the entry
+ * rtw_reproject_table_* writes for cams[v] as its own previous camera; element 29 is F = T(focus) and element 30 is
+ * K = T((lens_radius*W) / sqrt(hor.hor)) -- the host constants of the rtw_defocus_* block, computed in binary64 and rounded to T once, with
+ * focus = focus_dists[v] if > 0, else the camera's own; element 31 is 0.  lens_radii NULL: b->lens_radius for every view; focus_dists NULL:
+ * b->focus_dist for every view.  Every view passes the checks of the single stage; the first offending view is named in rtw_last_error.
+ *   Layout.  Views follow each other in the arrays: the output of view v at v*W*H*3 elements; the workspace of view v at byte
+ * v * rtw_wide_aperture_work_bytes(W, H, elem_bytes, max_radius), with the single stage's public layout inside (that size is a multiple of
+ * 16 bytes); rtw_lens_batch_work_bytes is n_views times the single value.  n_frames is n_views -- image and features of view v
+ * at v*W*H*3 and v*W*H*8 elements -- or 1: every view reads frame 0, the focus or aperture bracket.  Outputs and workspaces are per view
+ * either way.
+ *
+ * rtw_lens_batch_device_*: SIX launches for max_radius > 8, TWO otherwise, asynchronous on `hip_stream` of the device b->device;
+ * no hidden copy, no allocation; rtw_stats() is left alone.  Of `b` only max_radius, gamma, device, flags and reserved are read: the
+ * per-view lens lives in the DEVICE table d_table.  d_table, d_features and d_work are 16-byte aligned, d_images and d_out aligned to T.
+ *   rtw_lens_batch_*: the host-buffer form, blocking, through the cached per-device context: one H2D per input and of the table
+ * (built inside), the launches, ONE D2H.
+ *   rtw_render_lens_batch_*: ONE batched render of the pinhole copies with gamma 0, ONE batched feature pass over all effective
+ * chunks, with `d` ONE batched filter pass, ONE H2D of the table, the batched stage with gamma = p->gamma (b's gamma and device replaced
+ * by p's), ONE D2H.  Here and only here a lens_radii[v] -- or b->lens_radius when the array is NULL -- of -1 means "cams[v]'s own".  View
+ * v equals, on the bits, rtw_render_wide_aperture_* with cams[v] and p->seed = seeds[v] (seeds NULL: p->seed).  rtw_stats() reports the
+ * render's record.
+ *   Refusals, all decided before any HIP call: a null argument that is not optional -> -1; n_views < 1, n_frames other than 1 or n_views,
+ * everything the single stage refuses (with its code), a table, feature buffer or workspace that is not 16-byte aligned, images or out
+ * not aligned to T, outputs that alias each other or an input over the FULL batch extents (inputs counted once when n_frames == 1), a
+ * lens_radii or focus_dists entry the single stage would refuse -> -2; width*height*n_views >= 2^39 (the batched filter's rule) -> -5; the
+ * one-call form additionally everything rtw_render_features_batch_* and rtw_filter_batch_* refuse for its arguments, with their codes.
+ *   Left out on purpose: views of different sizes or different max_radius / gamma in one launch; a batched motion
+ * blur (no batched motion pass exists to feed it); sequence, animation, upsampler and present one-call forms; device lists; the Julia shim.
+ * Additive to ABI 4: detected by symbol lookup. */
+int64_t rtw_lens_table_bytes(int32_t n_views, int32_t elem_bytes);
+int rtw_lens_table_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cams, int32_t n_views, int32_t width, int32_t height,
+                       const double *lens_radii /* may be NULL */, const double *focus_dists /* may be NULL */, void *table);
+int rtw_lens_table_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cams, int32_t n_views, int32_t width, int32_t height,
+                       const double *lens_radii /* may be NULL */, const double *focus_dists /* may be NULL */, void *table);
+int64_t rtw_lens_batch_work_bytes(int32_t width, int32_t height, int32_t elem_bytes, int32_t max_radius, int32_t n_views);
+int rtw_lens_batch_device_f32(const rtw_wide_aperture_t *b, int32_t n_views, int32_t n_frames, const void *d_table, int32_t width, int32_t height,
+                                       const void *d_images, const void *d_features, void *d_work, void *d_out, void *hip_stream);
+int rtw_lens_batch_device_f64(const rtw_wide_aperture_t *b, int32_t n_views, int32_t n_frames, const void *d_table, int32_t width, int32_t height,
+                                       const void *d_images, const void *d_features, void *d_work, void *d_out, void *hip_stream);
+int rtw_lens_batch_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cams, int32_t n_views, int32_t n_frames, const double *lens_radii /* may be NULL */,
+                                const double *focus_dists /* may be NULL */, int32_t width, int32_t height, const float *images, const float *features, float *out);
+int rtw_lens_batch_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cams, int32_t n_views, int32_t n_frames, const double *lens_radii /* may be NULL */,
+                                const double *focus_dists /* may be NULL */, int32_t width, int32_t height, const double *images, const double *features, double *out);
+int rtw_render_lens_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds /* may be NULL */, const rtw_params *p,
+                                       const rtw_denoise_t *d /* may be NULL */, const rtw_wide_aperture_t *b, const double *lens_radii /* may be NULL */,
+                                       const double *focus_dists /* may be NULL */, float *out);
+int rtw_render_lens_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds /* may be NULL */, const rtw_params *p,
+                                       const rtw_denoise_t *d /* may be NULL */, const rtw_wide_aperture_t *b, const double *lens_radii /* may be NULL */,
+                                       const double *focus_dists /* may be NULL */, double *out);
 
 /* Present stage: display-ready 8-bit frames from the device.  Every pipeline above ends in T elements in the column-major layout of the
  * render entry points; a window, a PNG or a video encoder wants 8-bit rows.  One kernel clips, rounds, packs and transposes in HBM, and the

@@ -42,7 +42,10 @@ from .temporal import (  # noqa: F401
 )
 from .motion_blur import make_motion_blur, motion_blur, motion_blur_into, motion_blur_work_bytes  # noqa: F401
 from .defocus import defocus, defocus_into, defocus_work_bytes, make_defocus, render_defocused  # noqa: F401
-from .wide_aperture import make_wide_aperture, render_wide_aperture, wide_aperture, wide_aperture_into, wide_aperture_work_bytes  # noqa: F401
+from .wide_aperture import (  # noqa: F401
+    focus_bracket, lens_table, make_wide_aperture, render_wide_aperture, render_wide_aperture_batch, wide_aperture, wide_aperture_batch, wide_aperture_batch_into,
+    wide_aperture_batch_work_bytes, wide_aperture_into, wide_aperture_work_bytes,
+)
 from .present import (  # noqa: F401
     make_present, present, present_batch_into, present_bytes, present_into, render_presented, render_presented_batch,
 )
@@ -71,5 +74,6 @@ __all__ = [
     "make_motion_blur", "motion_blur_work_bytes", "motion_blur", "motion_blur_into",
     "make_defocus", "defocus_work_bytes", "defocus", "defocus_into", "render_defocused",
     "make_wide_aperture", "wide_aperture_work_bytes", "wide_aperture", "wide_aperture_into", "render_wide_aperture",
+    "lens_table", "wide_aperture_batch_work_bytes", "wide_aperture_batch", "wide_aperture_batch_into", "focus_bracket", "render_wide_aperture_batch",
     "make_present", "present_bytes", "present", "present_into", "present_batch_into", "render_presented", "render_presented_batch",
 ]

@@ -49,6 +49,9 @@ SYMBOLS = [
     "rtw_render_defocused_f32", "rtw_render_defocused_f64",
     "rtw_wide_aperture_work_bytes", "rtw_wide_aperture_device_f32", "rtw_wide_aperture_device_f64", "rtw_wide_aperture_f32", "rtw_wide_aperture_f64",
     "rtw_render_wide_aperture_f32", "rtw_render_wide_aperture_f64",
+    "rtw_lens_table_bytes", "rtw_lens_table_f32", "rtw_lens_table_f64", "rtw_lens_batch_work_bytes", "rtw_lens_batch_device_f32",
+    "rtw_lens_batch_device_f64", "rtw_lens_batch_f32", "rtw_lens_batch_f64", "rtw_render_lens_batch_f32",
+    "rtw_render_lens_batch_f64",
     "rtw_present_bytes", "rtw_present_device_f32", "rtw_present_device_f64", "rtw_present_batch_device_f32", "rtw_present_batch_device_f64",
     "rtw_present_f32", "rtw_present_f64", "rtw_render_presented_f32", "rtw_render_presented_f64", "rtw_render_presented_batch_f32",
     "rtw_render_presented_batch_f64",
@@ -286,6 +289,12 @@ def lib():
         getattr(L, "rtw_wide_aperture_device_" + sfx).argtypes = [wa, C.POINTER(CamT), i32, i32, ptr, ptr, ptr, ptr, ptr]
         getattr(L, "rtw_wide_aperture_" + sfx).argtypes = [wa, C.POINTER(CamT), i32, i32, ptr, ptr, ptr]
         getattr(L, "rtw_render_wide_aperture_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), C.POINTER(Params), C.POINTER(Denoise), wa, ptr]
+        f64p = C.POINTER(C.c_double)
+        getattr(L, "rtw_lens_table_" + sfx).argtypes = [wa, C.POINTER(CamT), i32, i32, i32, f64p, f64p, ptr]
+        getattr(L, "rtw_lens_batch_device_" + sfx).argtypes = [wa, i32, i32, ptr, i32, i32, ptr, ptr, ptr, ptr, ptr]
+        getattr(L, "rtw_lens_batch_" + sfx).argtypes = [wa, C.POINTER(CamT), i32, i32, f64p, f64p, i32, i32, ptr, ptr, ptr]
+        getattr(L, "rtw_render_lens_batch_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, C.POINTER(C.c_uint64), C.POINTER(Params), C.POINTER(Denoise), wa,
+                                                                          f64p, f64p, ptr]
         pr, dn = C.POINTER(Present), C.POINTER(Denoise)
         getattr(L, "rtw_present_device_" + sfx).argtypes = [pr, i32, i32, ptr, ptr, ptr]
         getattr(L, "rtw_present_batch_device_" + sfx).argtypes = [pr, i32, i32, i32, ptr, ptr, ptr]
@@ -302,6 +311,10 @@ def lib():
     L.rtw_defocus_work_bytes.restype = C.c_int64
     L.rtw_wide_aperture_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.rtw_wide_aperture_work_bytes.restype = C.c_int64
+    L.rtw_lens_table_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.rtw_lens_table_bytes.restype = C.c_int64
+    L.rtw_lens_batch_work_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.rtw_lens_batch_work_bytes.restype = C.c_int64
     L.rtw_history_moment_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.rtw_history_moment_bytes.restype = C.c_int64
     L.rtw_reproject_table_bytes.argtypes = [C.c_int32, C.c_int32]

@@ -18,6 +18,19 @@ static void defocus_constants(const rtw_defocus_t *b, const CamT *cam, int32_t w
     *K = (b->lens_radius * (double)width) / std::sqrt(*hh);
 }
 
+// One view's entry of the lens table (include/rtw_hip.h rtw_lens_table_*: 32 elements): [0, 29) the reprojection table's entry of the camera
+// as its own previous one (so that element 15.. is its w), 29: F = T(focus), 30: K rounded to T, 31: 0.  The ONE copy of this arithmetic:
+// launch_prepare's own constants and rtw_lens_table_* both come from here.
+template <typename T, typename CamT>
+void lens_table_entry(const rtw_defocus_t *b, const CamT *cam, int32_t width, T *e) {
+    double hh, focus, K;
+    defocus_constants(b, cam, width, &hh, &focus, &K);
+    temporal_table_t(cam, cam, 1, e);
+    e[29] = (T)focus; e[30] = (T)K; e[31] = T(0);
+}
+void lens_table_entry_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, float *e) { lens_table_entry<float>(b, cam, width, e); }
+void lens_table_entry_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, double *e) { lens_table_entry<double>(b, cam, width, e); }
+
 // Everything about a defocus that is decided without a device and without a pointer.
 template <typename CamT>
 int validate_defocus_t(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, int elem_bytes, int top = RTW_DEFOCUS_MAX_RADIUS) {
@@ -48,30 +61,51 @@ static long long tiles_of(int32_t width, int32_t height) {
 }
 static long long work_bytes(int32_t width, int32_t height, int elem_bytes) { return ((long long)width * height * 4 + ((tiles_of(width, height) + 3) & ~3ll)) * elem_bytes; }
 
+// the view dimensions of a batched launch's grid: the view index is blockIdx.z * gridDim.y + blockIdx.y (rtw_defocus.hpp DfViews)
+dim3 lens_views_grid(unsigned tiles, int32_t n_views) {
+    const unsigned nv = (unsigned)n_views;
+    return dim3(tiles, nv < rtw::DF_VIEWS_Y ? nv : rtw::DF_VIEWS_Y, (nv + rtw::DF_VIEWS_Y - 1) / rtw::DF_VIEWS_Y);
+}
+
 // The stage's two launches one by one (launch_defocus below; rtw_wide_aperture.hip composes them): the prepare launch with the clamp `rm`
 // over the image and the features into a CoC plane and its tile plane ...
+// n_views == 0: ONE view, the constants from b and cam.  n_views >= 1 (rtw_lens_batch_device_*): that many views in the SAME single
+// launch -- b and cam are unused, view v takes its constants from entry v of the DEVICE table d_table (lens_table_*) and finds its image,
+// features, CoC plane and tile plane v * strides[0..3] bytes behind the pointers.
 template <typename T, typename CamT>
-int launch_prepare(const rtw_defocus_t *b, int rm, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream) {
+int launch_prepare(const rtw_defocus_t *b, int rm, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream,
+                   int32_t n_views, const void *d_table, const long long *strides) {
     using V = typename rtw::DnVec<T>::type;
     const unsigned tiles = (unsigned)tiles_of(width, height);                 // (fewer than the frame rule's 8 x 8 ones: one 32-bit grid dimension holds them)
-    double hh, focus, K;
-    defocus_constants(b, cam, width, &hh, &focus, &K);
     rtw::TpParams<T> U;
     memset(&U, 0, sizeof U);
-    {
+    T FK[2] = {T(0), T(0)};
+    if (!n_views) {
         T e[32];
-        temporal_table_t(cam, cam, 1, e);             // (the camera as its own previous one: U.pw is its w)
+        lens_table_entry<T>(b, cam, width, e);
         memcpy(&U, e, 29 * sizeof(T));
+        FK[0] = e[29]; FK[1] = e[30];
     }
     U.W = width; U.H = height;
     (void)hipGetLastError();
-    hipLaunchKernelGGL((rtw::df_prepare<T>), dim3(tiles), dim3(256), 0, stream, U, (T)focus, (T)K, (T)rm, (const T *)d_image, (const V *)d_features, (V *)d_coc, (T *)d_tile);
+    if (n_views) {
+        rtw::DfLens<T, true> B;
+        for (int k = 0; k < 4; ++k) B.stride[k] = strides[k];
+        B.n_views = (unsigned)n_views; B.table = (const T *)d_table;
+        hipLaunchKernelGGL((rtw::df_prepare<T, true>), lens_views_grid(tiles, n_views), dim3(256), 0, stream, U, FK[0], FK[1], (T)rm, (const T *)d_image, (const V *)d_features, (V *)d_coc,
+                           (T *)d_tile, B);
+    } else {
+        hipLaunchKernelGGL((rtw::df_prepare<T, false>), dim3(tiles), dim3(256), 0, stream, U, FK[0], FK[1], (T)rm, (const T *)d_image, (const V *)d_features, (V *)d_coc, (T *)d_tile,
+                           rtw::DfLens<T, false>());
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }
-// ... and the gather of a frame of any size over its image, CoC plane and tile plane; mmax >= every radius of the plane, at most 8
+// ... and the gather of a frame of any size over its image, CoC plane and tile plane; mmax >= every radius of the plane, at most 8.
+// n_views >= 1: that many frames in the same single launch, image, CoC plane, tile plane and output of view v at v * strides[0..3] bytes.
 template <typename T>
-int launch_gather(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream) {
+int launch_gather(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream, int32_t n_views,
+                  const long long *strides) {
     using V = typename rtw::DnVec<T>::type;
     const unsigned tiles = (unsigned)tiles_of(width, height);
     rtw::DfDist<T> tab;
@@ -79,40 +113,57 @@ int launch_gather(int32_t width, int32_t height, int mmax, int gamma, const void
         for (int di = 0; di <= rtw::DF_MAX_RADIUS; ++di) tab.d[dj * (rtw::DF_MAX_RADIUS + 1) + di] = std::sqrt((T)(di * di + dj * dj));
     const size_t lds = (size_t)(rtw::DF_TILE + 2 * mmax) * rtw::DF_COL * sizeof(T);      // (at most 32 columns: 24 / 48 KB)
     (void)hipGetLastError();
-    hipLaunchKernelGGL((rtw::df_gather<T>), dim3(tiles), dim3(256), lds, stream, width, height, mmax, gamma, tab, (const T *)d_image, (const V *)d_coc, (const T *)d_tile, (T *)d_out);
+    if (n_views) {
+        rtw::DfViews<T, true, 4> B;
+        for (int k = 0; k < 4; ++k) B.stride[k] = strides[k];
+        B.n_views = (unsigned)n_views;
+        hipLaunchKernelGGL((rtw::df_gather<T, true>), lens_views_grid(tiles, n_views), dim3(256), lds, stream, width, height, mmax, gamma, tab, (const T *)d_image, (const V *)d_coc,
+                           (const T *)d_tile, (T *)d_out, B);
+    } else {
+        hipLaunchKernelGGL((rtw::df_gather<T, false>), dim3(tiles), dim3(256), lds, stream, width, height, mmax, gamma, tab, (const T *)d_image, (const V *)d_coc, (const T *)d_tile, (T *)d_out,
+                           rtw::DfViews<T, false, 4>());
+    }
     HIP_TRY(hipGetLastError());
     return 0;
 }
-int launch_defocus_prepare_f32(const rtw_defocus_t *b, int rm, const rtw_camera_f32 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st) { return launch_prepare<float>(b, rm, cam, w, h, img, feat, coc, tile, st); }
-int launch_defocus_prepare_f64(const rtw_defocus_t *b, int rm, const rtw_camera_f64 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st) { return launch_prepare<double>(b, rm, cam, w, h, img, feat, coc, tile, st); }
-int launch_defocus_gather_f32(int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st) { return launch_gather<float>(w, h, mmax, gamma, img, coc, tile, out, st); }
-int launch_defocus_gather_f64(int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st) { return launch_gather<double>(w, h, mmax, gamma, img, coc, tile, out, st); }
+int launch_defocus_prepare_f32(const rtw_defocus_t *b, int rm, const rtw_camera_f32 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st, int32_t nv, const void *tab, const long long *strides) { return launch_prepare<float>(b, rm, cam, w, h, img, feat, coc, tile, st, nv, tab, strides); }
+int launch_defocus_prepare_f64(const rtw_defocus_t *b, int rm, const rtw_camera_f64 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st, int32_t nv, const void *tab, const long long *strides) { return launch_prepare<double>(b, rm, cam, w, h, img, feat, coc, tile, st, nv, tab, strides); }
+int launch_defocus_gather_f32(int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st, int32_t nv, const long long *strides) { return launch_gather<float>(w, h, mmax, gamma, img, coc, tile, out, st, nv, strides); }
+int launch_defocus_gather_f64(int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st, int32_t nv, const long long *strides) { return launch_gather<double>(w, h, mmax, gamma, img, coc, tile, out, st, nv, strides); }
 
 // Enqueue the stage on `stream` of the current device (validate_defocus has accepted the call): TWO launches, no record.
+// vb null: one view.  vb given (rtw_lens_batch_device_* with max_radius <= 8): vb->n_views views in the same two launches -- cam and
+// b's lens are unused (the table), the buffers hold the views at vb's strides.
 template <typename T, typename CamT>
-int launch_defocus(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream) {
+int launch_defocus(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream,
+                   const LensViews *vb) {
     using V = typename rtw::DnVec<T>::type;
     V *coc = (V *)d_work;
     T *tile = (T *)(coc + (size_t)width * (size_t)height);
+    const int32_t nv = vb ? vb->n_views : 0;
+    const long long sp[4] = {vb ? vb->img_stride : 0, vb ? vb->feat_stride : 0, vb ? vb->work_stride : 0, vb ? vb->work_stride : 0};
+    const long long sg[4] = {sp[0], sp[2], sp[2], vb ? vb->out_stride : 0};
     // (measurement aid, tools/gpu_defocus.py: events around every launch, reported on stderr -- this one blocks)
     static const bool profile = aid_flag("RTW_TEMPORAL_PROFILE");
     struct Events { hipEvent_t e[3] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
     if (profile) { for (hipEvent_t &x : events.e) HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventRecord(events.e[0], stream)); }
-    if (int rc = launch_prepare<T>(b, b->max_radius, cam, width, height, d_image, d_features, coc, tile, stream)) return rc;
+    if (int rc = launch_prepare<T>(b, b->max_radius, cam, width, height, d_image, d_features, coc, tile, stream, nv, vb ? vb->d_table : nullptr, sp)) return rc;
     if (profile) HIP_TRY(hipEventRecord(events.e[1], stream));
-    if (int rc = launch_gather<T>(width, height, b->max_radius, b->gamma, d_image, coc, tile, d_out, stream)) return rc;
+    if (int rc = launch_gather<T>(width, height, b->max_radius, b->gamma, d_image, coc, tile, d_out, stream, nv, sg)) return rc;
     if (profile) {
         float ms[2] = {0, 0};
+        char views[32] = "";
+        if (nv) snprintf(views, sizeof views, " n_views=%d", nv);
         HIP_TRY(hipEventRecord(events.e[2], stream));
         HIP_TRY(hipEventSynchronize(events.e[2]));
         for (int k = 0; k < 2; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], events.e[k], events.e[k + 1]));
-        fprintf(stderr, "[rtw defocus] %s %dx%d max_radius=%d prepare_ms=%.5f gather_ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, b->max_radius, ms[0], ms[1]);
+        fprintf(stderr, "[rtw defocus] %s %dx%d max_radius=%d%s prepare_ms=%.5f gather_ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, b->max_radius, views, ms[0], ms[1]);
     }
     return 0;
 }
 
-int launch_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_defocus<float>(b, cam, w, h, img, feat, work, out, st); }
-int launch_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_defocus<double>(b, cam, w, h, img, feat, work, out, st); }
+int launch_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb) { return launch_defocus<float>(b, cam, w, h, img, feat, work, out, st, vb); }
+int launch_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb) { return launch_defocus<double>(b, cam, w, h, img, feat, work, out, st, vb); }
 
 // The device-resident entry point: nulls, the parameters, then the pointers' alignment and aliasing.
 template <typename T, typename CamT>
@@ -126,7 +177,7 @@ int defocus_device(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32
     if (int rc = check_alias({{"d_out", d_out, img_b}, {"d_work", d_work, work_b}}, {{"d_image", d_image, img_b}, {"d_features", d_features, feat_b}})) return rc;
     DeviceGuard guard;
     if (b->device >= 0) HIP_TRY(hipSetDevice(b->device));
-    return launch_defocus<T>(b, cam, width, height, d_image, d_features, d_work, d_out, (hipStream_t)stream_v);
+    return launch_defocus<T>(b, cam, width, height, d_image, d_features, d_work, d_out, (hipStream_t)stream_v, nullptr);
 }
 
 }  // namespace rtwh

@@ -18,6 +18,8 @@
 //                  32 different elements modulo 32, so ds_read_b32 (bank = dword mod 32) and ds_read_b64 (bank = dword mod 64, two per lane)
 //                  are conflict-free at every tap offset; a plain pitch of 32 would be 2-way for both.  The staging writes go a column of 32
 //                  rows per half wave: 32 consecutive elements, conflict-free.  
+//   VIEWS          true (rtw_lens_batch_device_*): n_views views in one launch, DfViews below; false: the instance is the single
+//                  form's, instruction for instruction (the flag only adds code under `if constexpr`).
 // Every operation is rounded once (the Makefile's -ffp-contract=off -fno-fast-math); divisions and sqrt are the compiler's IEEE ones; taps that
 // do not take part are dropped by selects.
 #pragma once
@@ -53,13 +55,39 @@ __device__ __forceinline__ void df_ray(const TpParams<T> &U, long long i, long l
     n0_ = n0; n1_ = n1; n2_ = n2;
 }
 
+// The trailing argument of the lens kernels (df_prepare, df_gather; wa_reduce, wa_compose of rtw_wide_aperture.hpp).  VIEWS = false (one
+// view): empty, so the kernel arguments of those instances lie where they always did.  VIEWS = true: n_views independent views in one launch,
+// the view index v = blockIdx.z * gridDim.y + blockIdx.y uniform over a workgroup (df_view); blockIdx.x numbers the tiles of ONE view as in the
+// single form.  View v finds pointer k of the kernel's N pointers, in the order of its arguments, v * stride[k] BYTES behind the base (a stride
+// of 0: every view reads the same frame); then the body runs unchanged: it indexes relative to its base pointers and bounds every tap by W
+// and H, which keeps a tap inside its own view.  A workgroup with v >= n_views (the last grid row) leaves before its first barrier.
+constexpr unsigned DF_VIEWS_Y = 65535;      // views per grid row: what one 16-bit grid dimension holds
+template <typename T, bool VIEWS, int N> struct DfViews {};
+template <typename T, int N> struct DfViews<T, true, N> {
+    long long stride[N];
+    unsigned n_views;
+};
+// df_prepare's: the strides and the lens table -- 32 elements per view: [0, 29) the head of TpParams, o .. iv (rtw_reproject_table_* of the
+// view's camera as its own previous one), 29: F, 30: K, 31: 0 -- read at uniform addresses (scalar loads, like tp_load_cameras)
+template <typename T, bool VIEWS> struct DfLens : DfViews<T, VIEWS, 4> {};
+template <typename T> struct DfLens<T, true> : DfViews<T, true, 4> { const T *table; };
+__device__ __forceinline__ long long df_view() { return (long long)blockIdx.z * gridDim.y + blockIdx.y; }
+
 // U: the camera's fields and W, H (the head of a step's TpParams built with cam_prev = cam, so that U.pw is the camera's w; nothing else of the
 // previous camera is read); F, K, Rm: the host constants of the definition
-template <typename T>
+template <typename T, bool VIEWS = false>
 __global__ __launch_bounds__(256) void df_prepare(TpParams<T> U, T F, T K, T Rm, const T *__restrict__ image, const typename DnVec<T>::type *__restrict__ feat,
-                                                  typename DnVec<T>::type *__restrict__ coc, T *__restrict__ tile) {
+                                                  typename DnVec<T>::type *__restrict__ coc, T *__restrict__ tile, [[maybe_unused]] DfLens<T, VIEWS> B) {
     using V = typename DnVec<T>::type;
     __shared__ T s_r[4];
+    if constexpr (VIEWS) {
+        const long long v = df_view();
+        if (v >= B.n_views) return;
+        image = tp_adv(image, v * B.stride[0]); feat = tp_adv(feat, v * B.stride[1]); coc = tp_adv(coc, v * B.stride[2]); tile = tp_adv(tile, v * B.stride[3]);
+        const T *__restrict__ e = B.table + v * 32;
+        tp_load_cameras(U, e);
+        F = e[29]; K = e[30];
+    }
     const long long H = U.H, W = U.W;
     const unsigned TH = (unsigned)((H + DF_TILE - 1) / DF_TILE);
     const unsigned tb = blockIdx.x / TH, ta = blockIdx.x - tb * TH;
@@ -101,12 +129,17 @@ __global__ __launch_bounds__(256) void df_prepare(TpParams<T> U, T F, T K, T Rm,
 }
 
 // mmax: max_radius, what the launch's dynamic LDS holds -- (16 + 2*mmax) window columns of DF_COL elements
-template <typename T>
+template <typename T, bool VIEWS = false>
 __global__ __launch_bounds__(256) void df_gather(int W_, int H_, int mmax, int gamma, DfDist<T> tab, const T *__restrict__ image, const typename DnVec<T>::type *__restrict__ coc,
-                                                 const T *__restrict__ tile, T *__restrict__ out) {
+                                                 const T *__restrict__ tile, T *__restrict__ out, [[maybe_unused]] DfViews<T, VIEWS, 4> B) {
     using V = typename DnVec<T>::type;
     extern __shared__ __align__(16) unsigned char df_lds[];
     T *win = reinterpret_cast<T *>(df_lds);
+    if constexpr (VIEWS) {
+        const long long v = df_view();
+        if (v >= B.n_views) return;
+        image = tp_adv(image, v * B.stride[0]); coc = tp_adv(coc, v * B.stride[1]); tile = tp_adv(tile, v * B.stride[2]); out = tp_adv(out, v * B.stride[3]);
+    }
     const int H = H_, W = W_;
     const int TH = (H + DF_TILE - 1) / DF_TILE, TW = (W + DF_TILE - 1) / DF_TILE;
     const int tb = (int)(blockIdx.x / (unsigned)TH), ta = (int)blockIdx.x - tb * TH;

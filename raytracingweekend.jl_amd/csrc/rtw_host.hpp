@@ -20,8 +20,8 @@
 //   rtw_temporal.hip     temporal reprojection: its checks, the host constants and the one launch of a step for one path or a batch of paths (rtw_temporal.hpp; clamped: rtw_temporal_clamp.hpp), the device-resident entry points
 //   rtw_motion.hip       the first-hit motion pass over moving spheres: its checks, the motion table, the one launch of its kernel (rtw_motion.hpp), the device-resident entry points
 //   rtw_motion_blur.hip  the motion-blur stage on the motion plane: its checks, the workspace, the three launches of its kernels (rtw_motion_blur.hpp), the device-resident entry points
-//   rtw_defocus.hip      the defocus stage (depth of field on the depth plane): its checks, the host constants, the workspace, the two launches of its kernels (rtw_defocus.hpp), the device-resident entry points
-//   rtw_wide_aperture.hip  the wide-aperture stage (circles of confusion up to 32 px): its checks, the workspace, the six launches (the defocus stage's kernels at two sizes, rtw_wide_aperture.hpp between and behind them), the device-resident entry points
+//   rtw_defocus.hip      the defocus stage (depth of field on the depth plane): its checks, the host constants (one view's entry of the lens table), the workspace, the two launches of its kernels (rtw_defocus.hpp) for one view or a batch of views, the device-resident entry points
+//   rtw_wide_aperture.hip  the wide-aperture stage (circles of confusion up to 32 px): its checks, the workspace, the six launches (the defocus stage's kernels at two sizes, rtw_wide_aperture.hpp between and behind them) for one view or a batch of views, the lens table, the device-resident entry points
 //   rtw_present.hip      the present stage: its checks, the one launch of its kernel (rtw_present.hpp) for one frame or a batch, the device-resident entry points
 //   (rtw_scene_view.hpp: what both launch functions derive from their arguments; rtw_instances.hpp: the one table of the trace kernel's instances)
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
@@ -417,30 +417,53 @@ inline int launch_motion_blur_t(const rtw_velocity_blur_t *b, const rtw_camera_f
 // `stream` of the current device; d_work: rtw_defocus_work_bytes bytes.  The camera's lens_radius is not read: the aperture is b->lens_radius.
 int validate_defocus(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height);
 int validate_defocus(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height);
-int launch_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream);
-int launch_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream);
-inline int launch_defocus_t(const rtw_defocus_t *b, const rtw_camera_f32 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_defocus_f32(b, c, w, h, img, feat, work, out, st); }
-inline int launch_defocus_t(const rtw_defocus_t *b, const rtw_camera_f64 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_defocus_f64(b, c, w, h, img, feat, work, out, st); }
+// A batch of views for the lens stages (rtw_lens_batch_*; rtw_layout.hpp LensBatchLayout has the arithmetic): n_views >= 1 views in each
+// launch, view v's lens in entry v of the DEVICE table d_table (lens_table_entry_*), its image, features, workspace and output v strides (BYTES)
+// behind the pointers; an input stride of 0: every view reads the one frame.  Below the ABI a null LensViews is the single call.
+struct LensViews { int32_t n_views; const void *d_table; long long img_stride, feat_stride, work_stride, out_stride; };
+int launch_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream, const LensViews *vb = nullptr);
+int launch_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream, const LensViews *vb = nullptr);
+inline int launch_defocus_t(const rtw_defocus_t *b, const rtw_camera_f32 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb = nullptr) { return launch_defocus_f32(b, c, w, h, img, feat, work, out, st, vb); }
+inline int launch_defocus_t(const rtw_defocus_t *b, const rtw_camera_f64 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb = nullptr) { return launch_defocus_f64(b, c, w, h, img, feat, work, out, st, vb); }
 // Its two launches one by one, for the wide-aperture stage: validate_defocus_top is validate_defocus with max_radius in 1..top;
 // launch_defocus_prepare_* is the prepare launch with the clamp `rm` (b->max_radius is not read) into a CoC plane and its tile plane;
 // launch_defocus_gather_* is the gather of a frame of any size over an image, a CoC plane and a tile plane, mmax (1..8) >= every radius there.
+// n_views == 0: one view.  n_views >= 1: that many views in the same ONE launch; `strides`: four byte strides from one view to the next, one
+// per pointer in the order of the arguments; the prepare launch then reads neither b nor cam but entry v of the device table d_table.
 int validate_defocus_top(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, int top);
 int validate_defocus_top(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, int top);
-int launch_defocus_prepare_f32(const rtw_defocus_t *b, int rm, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream);
-int launch_defocus_prepare_f64(const rtw_defocus_t *b, int rm, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream);
-int launch_defocus_gather_f32(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream);
-int launch_defocus_gather_f64(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream);
+int launch_defocus_prepare_f32(const rtw_defocus_t *b, int rm, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream, int32_t n_views = 0, const void *d_table = nullptr, const long long *strides = nullptr);
+int launch_defocus_prepare_f64(const rtw_defocus_t *b, int rm, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream, int32_t n_views = 0, const void *d_table = nullptr, const long long *strides = nullptr);
+int launch_defocus_gather_f32(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream, int32_t n_views = 0, const long long *strides = nullptr);
+int launch_defocus_gather_f64(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream, int32_t n_views = 0, const long long *strides = nullptr);
+dim3 lens_views_grid(unsigned tiles, int32_t n_views);       // the grid of a batched lens launch: the tiles of one view in x, the views over y and z
+// one view's entry of the lens table (include/rtw_hip.h rtw_lens_table_*; b: lens_radius and focus_dist alone are read): the one copy of that arithmetic
+void lens_table_entry_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, float *e);
+void lens_table_entry_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, double *e);
 
 // rtw_wide_aperture.hip -- the wide-aperture stage (include/rtw_hip.h rtw_wide_aperture_*): circles of confusion up to 32 px through a reduced
 // copy of the frame.  validate_wide_aperture: every check that needs neither a device nor a pointer (the defocus stage's, max_radius in 1..32).
 // launch_wide_aperture: enqueue the stage (SIX launches, or the defocus stage's two when max_radius <= 8; no record) on `stream` of the
-// current device; d_work: rtw_wide_aperture_work_bytes bytes.
+// current device; d_work: rtw_wide_aperture_work_bytes bytes.  vb non-null (rtw_lens_batch_*): vb->n_views views in the same launches.
 int validate_wide_aperture(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height);
 int validate_wide_aperture(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height);
-int launch_wide_aperture_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream);
-int launch_wide_aperture_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream);
-inline int launch_wide_aperture_t(const rtw_wide_aperture_t *b, const rtw_camera_f32 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_wide_aperture_f32(b, c, w, h, img, feat, work, out, st); }
-inline int launch_wide_aperture_t(const rtw_wide_aperture_t *b, const rtw_camera_f64 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_wide_aperture_f64(b, c, w, h, img, feat, work, out, st); }
+int launch_wide_aperture_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream, const LensViews *vb = nullptr);
+int launch_wide_aperture_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream, const LensViews *vb = nullptr);
+inline int launch_wide_aperture_t(const rtw_wide_aperture_t *b, const rtw_camera_f32 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb = nullptr) { return launch_wide_aperture_f32(b, c, w, h, img, feat, work, out, st, vb); }
+inline int launch_wide_aperture_t(const rtw_wide_aperture_t *b, const rtw_camera_f64 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb = nullptr) { return launch_wide_aperture_f64(b, c, w, h, img, feat, work, out, st, vb); }
+// The batched stage's checks that need neither a device nor a pointer (rtw_lens_batch_*, rtw_lens_table_*): the count, then per view
+// the checks of validate_wide_aperture with lens_radii[v] / focus_dists[v] (null arrays: b's own) -- the first offending view is named --,
+// then the batch's size (-5).  own_lens (rtw_render_lens_batch_* alone): a lens radius of -1 is cams[v]'s own.  `lens_out` non-null:
+// n_views rtw_defocus_t with every view's lens radius and focus distance in place.
+int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, std::vector<rtw_defocus_t> *lens_out);
+int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, std::vector<rtw_defocus_t> *lens_out);
+// the lens table of those views into a HOST table (32 elements per view)
+void lens_table_f32(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f32 *cams, int32_t width, float *table);
+void lens_table_f64(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f64 *cams, int32_t width, double *table);
+inline void lens_table_t(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f32 *cams, int32_t width, float *table) { lens_table_f32(lens, cams, width, table); }
+inline void lens_table_t(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f64 *cams, int32_t width, double *table) { lens_table_f64(lens, cams, width, table); }
+// what the batched device entry point checks of its frame and count without a camera (b: max_radius, gamma, device, flags, reserved alone)
+int validate_lens_batch_frame(const rtw_wide_aperture_t *b, int32_t n_views, int32_t n_frames, int32_t width, int32_t height, int elem_bytes);
 
 // rtw_present.hip -- the present stage (include/rtw_hip.h rtw_present_*).  validate_present: every check of a call that needs neither a device
 // nor a pointer -- the parameters, the frame, n_views (0: one frame; a batch's count through batch_views) and the size of the launch.

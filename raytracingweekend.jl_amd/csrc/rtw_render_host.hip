@@ -486,6 +486,54 @@ int render_host_wide_aperture(const SceneT *scene, const CamT *cam, const rtw_pa
     });
 }
 
+// N views through their pinholes and N lenses in one call (rtw_render_lens_batch_*): the one-device path above with the batched launch
+// sequences that exist -- ONE batched render (gamma 0) and ONE batched feature pass over all chunks through copies of the cameras with
+// lens_radius = 0, with `d` ONE batched filter pass (launch_filtered, gamma 0) --, ONE H2D of the lens table (built here: view v's lens is
+// lens_radii[v] / focus_dists[v], null arrays: b's; a lens radius of -1: cams[v]'s own), the batched stage with p->gamma into a region behind the
+// denoiser's, ONE D2H.  rtw_stats() reports the render's record.
+template <typename T, typename SceneT, typename CamT>
+int render_host_wide_aperture_batch(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, const rtw_wide_aperture_t *b,
+                                    const double *lens_radii, const double *focus_dists, T *out) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !cams || !b || !out) return fail(-1, "null argument");
+    int nch, cs;
+    if (int rc = validate_features_batch(cams, n_views, p, 0, 1, out, &nch, &cs)) return rc;
+    if (scene->n < 0) return fail(-2, "negative sphere count");
+    if (d) if (int rc = validate_filter_batch(d, p->width, p->height, n_views)) return rc;
+    std::vector<rtw_defocus_t> lens;
+    if (int rc = validate_lens_batch(b, cams, n_views, p->width, p->height, lens_radii, focus_dists, true, &lens)) return rc;
+    rtw_wide_aperture_t bb = *b;
+    bb.lens_radius = 0; bb.focus_dist = 0;                                     // (the lens lives in the table)
+    bb.gamma = p->gamma != 0;                                                  // (b's gamma and device are judged, then replaced by p's)
+    std::vector<CamT> pins(cams, cams + n_views);
+    for (CamT &c : pins) c.lens_radius = 0;
+    std::vector<T> table((size_t)n_views * 32);
+    lens_table_t(lens, pins.data(), p->width, table.data());
+    DeviceGuard guard;
+    release_last();
+    const DenoiseRegions<T> R(p->width, p->height, n_views);
+    const LensBatchLayout B(sizeof(T), p->width, p->height, bb.max_radius, n_views, n_views);
+    DevLayout L{R.total};
+    const size_t off_wa = L.add(B.out_b), off_work = L.add(B.work_b), off_tab = L.add(B.tab_b);
+    SideRec frec;                                             // (the feature pass's record)
+    return render_one_device(p->device, scene, p, L.total, off_wa, B.out_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+        char *base = (char *)hc->d_img;
+        int rc;
+        if (d) {
+            rc = launch_filtered(hc, q, pins.data(), n_views, seeds, 0, d, nch, R, rec, rctx, frec);
+        } else {
+            q.gamma = 0;
+            rc = launch_render_t(hc->scene, pins.data(), n_views, seeds, &q, base, hc->stream, rec, rctx);
+            if (!rc) rc = launch_features_t(hc->scene, pins.data(), n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec.rec, &frec.ctx);
+        }
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(base + off_tab, table.data(), B.tab_b, hipMemcpyHostToDevice, hc->stream));
+        bb.device = hc->device;
+        const LensViews vb = {n_views, base + off_tab, (long long)B.img_stride, (long long)B.feat_stride, (long long)B.work_stride, (long long)B.out_stride};
+        return launch_wide_aperture_t(&bb, (const CamT *)nullptr, p->width, p->height, base + (d ? R.off_out : 0), base + R.off_feat, base + off_work, base + off_wa, hc->stream, &vb);
+    });
+}
+
 // N cameras along a path with history reuse (rtw_render_sequence_*): the one-device path above with a device buffer that holds the linear images
 // (ONE batched render with gamma 0), the features (ONE batched pass over all chunks), the accumulated images (n_views temporal steps in view
 // order, two states ping-pong) and, with `d`, the filtered images and the filter's workspace (ONE batched filter pass); 2 + n_views (+ 1 + levels)
@@ -842,6 +890,14 @@ int rtw_render_wide_aperture_f32(const rtw_scene_f32 *scene, const rtw_camera_f3
 }
 int rtw_render_wide_aperture_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, const rtw_wide_aperture_t *b, double *out) {
     return render_host_wide_aperture<double>(scene, cam, p, d, b, out);
+}
+int rtw_render_lens_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d,
+                                       const rtw_wide_aperture_t *b, const double *lens_radii, const double *focus_dists, float *out) {
+    return render_host_wide_aperture_batch<float>(scene, cams, batch_views(n_views), seeds, p, d, b, lens_radii, focus_dists, out);
+}
+int rtw_render_lens_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d,
+                                       const rtw_wide_aperture_t *b, const double *lens_radii, const double *focus_dists, double *out) {
+    return render_host_wide_aperture_batch<double>(scene, cams, batch_views(n_views), seeds, p, d, b, lens_radii, focus_dists, out);
 }
 int rtw_render_path_clamped_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                                  const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, float *out) {

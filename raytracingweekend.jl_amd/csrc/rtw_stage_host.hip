@@ -1,5 +1,5 @@
 // rtw_stage_host.hip -- the pure stages on host buffers (rtw_denoise_* / rtw_filter_batch_*, rtw_present_*, rtw_upsample_*, the temporal
-// steps, rtw_velocity_blur_*, rtw_defocus_*, rtw_wide_aperture_*): each is its null checks, the stage's validate_*, a layout of the device buffer, the alias
+// steps, rtw_velocity_blur_*, rtw_defocus_*, rtw_wide_aperture_*, rtw_lens_batch_*): each is its null checks, the stage's validate_*, a layout of the device buffer, the alias
 // check of its host buffers and ONE call of stage_one_device (rtw_host_ctx.hpp) with the stage's launch.  A leased context's scene is
 // left alone and this thread's last render (rtw_stats) is not touched.  n_views == 0 is the single-frame entry point, n_views != 0 the
 // batched one (rtw_host.hpp batch_views).
@@ -121,6 +121,28 @@ int wide_aperture_host(const rtw_wide_aperture_t *b, const CamT *cam, int32_t wi
         {R.off_out, out, R.img_b});
 }
 
+// The batched wide-aperture stage (rtw_lens_batch_*): n_views views of n_frames (n_views or 1) input frames.  Three H2D (the images,
+// the features, the lens table built here), the stage's six launches (two when max_radius <= 8) for any number of views, ONE D2H of all
+// outputs.  The device buffer: rtw_layout.hpp LensBatchLayout.
+template <typename T, typename CamT>
+int wide_aperture_batch_host(const rtw_wide_aperture_t *b, const CamT *cams, int32_t n_views, int32_t n_frames, const double *lens_radii, const double *focus_dists, int32_t width,
+                             int32_t height, const T *images, const T *features, T *out) {
+    if (!b || !cams || !images || !features || !out) return fail(-1, "null argument");
+    if (int rc = validate_lens_batch_frame(b, n_views, n_frames, width, height, (int)sizeof(T))) return rc;
+    std::vector<rtw_defocus_t> lens;
+    if (int rc = validate_lens_batch(b, cams, n_views, width, height, lens_radii, focus_dists, false, &lens)) return rc;
+    const LensBatchLayout R(sizeof(T), width, height, b->max_radius, n_views, n_frames);
+    if (int rc = check_alias({{"out", out, R.out_b}}, {{"images", images, R.img_b}, {"features", features, R.feat_b}})) return rc;
+    std::vector<T> table((size_t)n_views * 32);
+    lens_table_t(lens, cams, width, table.data());
+    return stage_one_device<T>(b->device, nullptr, R.total, "the batched wide-aperture stage's inputs", {{0, images, R.img_b}, {R.off_feat, features, R.feat_b}, {R.off_tab, table.data(), R.tab_b}},
+        [&](HostCtx *hc, char *base) {
+            const LensViews vb = {n_views, base + R.off_tab, (long long)R.img_stride, (long long)R.feat_stride, (long long)R.work_stride, (long long)R.out_stride};
+            return launch_wide_aperture_t(b, (const CamT *)nullptr, width, height, base, base + R.off_feat, base + R.off_work, base + R.off_out, hc->stream, &vb);
+        },
+        {R.off_out, out, R.out_b});
+}
+
 }  // namespace rtwh
 
 using namespace rtwh;
@@ -212,6 +234,14 @@ int rtw_wide_aperture_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *ca
 }
 int rtw_wide_aperture_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const double *image, const double *features, double *out) {
     return wide_aperture_host<double>(b, cam, width, height, image, features, out);
+}
+int rtw_lens_batch_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cams, int32_t n_views, int32_t n_frames, const double *lens_radii, const double *focus_dists,
+                                int32_t width, int32_t height, const float *images, const float *features, float *out) {
+    return wide_aperture_batch_host<float>(b, cams, n_views, n_frames, lens_radii, focus_dists, width, height, images, features, out);
+}
+int rtw_lens_batch_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cams, int32_t n_views, int32_t n_frames, const double *lens_radii, const double *focus_dists,
+                                int32_t width, int32_t height, const double *images, const double *features, double *out) {
+    return wide_aperture_batch_host<double>(b, cams, n_views, n_frames, lens_radii, focus_dists, width, height, images, features, out);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // rtw_wide_aperture.hip -- the wide-aperture stage (include/rtw_hip.h rtw_wide_aperture_*): the checks that need no device, the workspace's
 // layout (rtw_layout.hpp WideApertureLayout), the six launches -- the defocus stage's two kernels as rtw_defocus.hip launches them, at the full
-// and at the reduced size, and the two kernels of rtw_wide_aperture.hpp -- and the device-resident entry points.
+// and at the reduced size, and the two kernels of rtw_wide_aperture.hpp --, for one view or a batch of views (rtw_lens_batch_*: the
+// lens table, the batch's checks), and the device-resident entry points.
 // (The host-buffer entry points live with the other cached-context paths: rtw_wide_aperture_* in rtw_stage_host.hip,
 // rtw_render_wide_aperture_* in rtw_render_host.hip.)
 #include "rtw_host.hpp"
@@ -28,14 +29,17 @@ static int validate_t(const rtw_wide_aperture_t *b, const CamT *cam, int32_t wid
 int validate_wide_aperture(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height) { return validate_t(b, cam, width, height); }
 int validate_wide_aperture(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height) { return validate_t(b, cam, width, height); }
 
-static int prepare_t(const rtw_defocus_t *b, int rm, const rtw_camera_f32 *c, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st) { return launch_defocus_prepare_f32(b, rm, c, w, h, img, feat, coc, tile, st); }
-static int prepare_t(const rtw_defocus_t *b, int rm, const rtw_camera_f64 *c, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st) { return launch_defocus_prepare_f64(b, rm, c, w, h, img, feat, coc, tile, st); }
-static int gather_t(float, int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st) { return launch_defocus_gather_f32(w, h, mmax, gamma, img, coc, tile, out, st); }
-static int gather_t(double, int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st) { return launch_defocus_gather_f64(w, h, mmax, gamma, img, coc, tile, out, st); }
+static int prepare_t(const rtw_defocus_t *b, int rm, const rtw_camera_f32 *c, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st, int32_t nv, const void *tab, const long long *sb) { return launch_defocus_prepare_f32(b, rm, c, w, h, img, feat, coc, tile, st, nv, tab, sb); }
+static int prepare_t(const rtw_defocus_t *b, int rm, const rtw_camera_f64 *c, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st, int32_t nv, const void *tab, const long long *sb) { return launch_defocus_prepare_f64(b, rm, c, w, h, img, feat, coc, tile, st, nv, tab, sb); }
+static int gather_t(float, int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st, int32_t nv, const long long *sb) { return launch_defocus_gather_f32(w, h, mmax, gamma, img, coc, tile, out, st, nv, sb); }
+static int gather_t(double, int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st, int32_t nv, const long long *sb) { return launch_defocus_gather_f64(w, h, mmax, gamma, img, coc, tile, out, st, nv, sb); }
 
 // Enqueue the stage on `stream` of the current device (validate_wide_aperture has accepted the call): SIX launches, no record.
+// vb null: one view.  vb given: vb->n_views views in the same six launches -- cam and d's lens are unused (the table); every region of the
+// workspace lies at the single stage's offset inside its view's workspace, so one stride serves all of them.
 template <typename T, int S, typename CamT>
-static int launch_scaled(const rtw_defocus_t *d, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream) {
+static int launch_scaled(const rtw_defocus_t *d, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream,
+                         const LensViews *vb) {
     using V = typename rtw::DnVec<T>::type;
     const WideApertureLayout L(width, height, d->max_radius);
     T *work = (T *)d_work;
@@ -43,6 +47,10 @@ static int launch_scaled(const rtw_defocus_t *d, const CamT *cam, int32_t width,
     T *coc = work + L.off_coc, *tile = work + L.off_tile, *narrow = work + L.off_n;
     T *lo_img = work + L.off_lo_img, *lo_coc = work + L.off_lo_coc, *lo_tile = work + L.off_lo_tile, *lo_out = work + L.off_lo_out;
     const unsigned tiles = (unsigned)WideApertureLayout::tiles(width, height), lo_tiles = (unsigned)WideApertureLayout::tiles(L.lo_width, L.lo_height);
+    const int32_t nv = vb ? vb->n_views : 0;
+    const void *tab = vb ? vb->d_table : nullptr;
+    const long long si = vb ? vb->img_stride : 0, sf = vb ? vb->feat_stride : 0, sw = vb ? vb->work_stride : 0, so = vb ? vb->out_stride : 0;
+    const long long s_prepare[4] = {si, sf, sw, sw}, s_gather[4] = {si, sw, sw, sw}, s_small[4] = {sw, sw, sw, sw};
     // (measurement aid, tools/gpu_wide_aperture.py: events around every launch, reported on stderr -- this one blocks)
     static const bool profile = aid_flag("RTW_TEMPORAL_PROFILE");
     struct Events { hipEvent_t e[7] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
@@ -51,46 +59,133 @@ static int launch_scaled(const rtw_defocus_t *d, const CamT *cam, int32_t width,
     if (profile) for (hipEvent_t &x : events.e) HIP_TRY(hipEventCreate(&x));
     if (int rc = mark()) return rc;
     // 1, 2: the narrow frame N -- the defocus stage with max_radius 8, linear
-    if (int rc = prepare_t(d, RTW_DEFOCUS_MAX_RADIUS, cam, width, height, d_image, d_features, n_coc, n_tile, stream)) return rc;
+    if (int rc = prepare_t(d, RTW_DEFOCUS_MAX_RADIUS, cam, width, height, d_image, d_features, n_coc, n_tile, stream, nv, tab, s_prepare)) return rc;
     if (int rc = mark()) return rc;
-    if (int rc = gather_t(T(), width, height, RTW_DEFOCUS_MAX_RADIUS, 0, d_image, n_coc, n_tile, narrow, stream)) return rc;
+    if (int rc = gather_t(T(), width, height, RTW_DEFOCUS_MAX_RADIUS, 0, d_image, n_coc, n_tile, narrow, stream, nv, s_gather)) return rc;
     if (int rc = mark()) return rc;
     // 3: the wide CoC plane
-    if (int rc = prepare_t(d, d->max_radius, cam, width, height, d_image, d_features, coc, tile, stream)) return rc;
+    if (int rc = prepare_t(d, d->max_radius, cam, width, height, d_image, d_features, coc, tile, stream, nv, tab, s_prepare)) return rc;
     if (int rc = mark()) return rc;
     // 4: the reduced frame
     (void)hipGetLastError();
-    hipLaunchKernelGGL((rtw::wa_reduce<T, S>), dim3(lo_tiles), dim3(256), 0, stream, width, height, (const T *)d_image, (const V *)coc, lo_img, (V *)lo_coc, lo_tile);
+    if (nv) hipLaunchKernelGGL((rtw::wa_reduce<T, S, true>), lens_views_grid(lo_tiles, nv), dim3(256), 0, stream, width, height, (const T *)d_image, (const V *)coc, lo_img, (V *)lo_coc, lo_tile,
+                               rtw::DfViews<T, true, 5>{{si, sw, sw, sw, sw}, (unsigned)nv});
+    else hipLaunchKernelGGL((rtw::wa_reduce<T, S, false>), dim3(lo_tiles), dim3(256), 0, stream, width, height, (const T *)d_image, (const V *)coc, lo_img, (V *)lo_coc, lo_tile,
+                            rtw::DfViews<T, false, 5>());
     HIP_TRY(hipGetLastError());
     if (int rc = mark()) return rc;
     // 5: the small gather
-    if (int rc = gather_t(T(), L.lo_width, L.lo_height, L.lo_mmax, 0, lo_img, lo_coc, lo_tile, lo_out, stream)) return rc;
+    if (int rc = gather_t(T(), L.lo_width, L.lo_height, L.lo_mmax, 0, lo_img, lo_coc, lo_tile, lo_out, stream, nv, s_small)) return rc;
     if (int rc = mark()) return rc;
     // 6: the blend by radius
     (void)hipGetLastError();
-    hipLaunchKernelGGL((rtw::wa_compose<T, S>), dim3(tiles), dim3(256), 0, stream, width, height, d->gamma, (const V *)coc, (const T *)narrow, (const V *)lo_coc, (const T *)lo_out, (T *)d_out);
+    if (nv) hipLaunchKernelGGL((rtw::wa_compose<T, S, true>), lens_views_grid(tiles, nv), dim3(256), 0, stream, width, height, d->gamma, (const V *)coc, (const T *)narrow, (const V *)lo_coc,
+                               (const T *)lo_out, (T *)d_out, rtw::DfViews<T, true, 5>{{sw, sw, sw, sw, so}, (unsigned)nv});
+    else hipLaunchKernelGGL((rtw::wa_compose<T, S, false>), dim3(tiles), dim3(256), 0, stream, width, height, d->gamma, (const V *)coc, (const T *)narrow, (const V *)lo_coc, (const T *)lo_out,
+                            (T *)d_out, rtw::DfViews<T, false, 5>());
     HIP_TRY(hipGetLastError());
     if (int rc = mark()) return rc;
     if (profile) {
         float ms[6] = {0, 0, 0, 0, 0, 0};
+        char views[32] = "";
+        if (nv) snprintf(views, sizeof views, " n_views=%d", nv);
         HIP_TRY(hipEventSynchronize(events.e[6]));
         for (int q = 0; q < 6; ++q) HIP_TRY(hipEventElapsedTime(&ms[q], events.e[q], events.e[q + 1]));
-        fprintf(stderr, "[rtw wide_aperture] %s %dx%d max_radius=%d prepare_ms=%.5f gather_ms=%.5f wide_prepare_ms=%.5f reduce_ms=%.5f small_gather_ms=%.5f compose_ms=%.5f\n",
-                sizeof(T) == 8 ? "f64" : "f32", width, height, d->max_radius, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
+        fprintf(stderr, "[rtw wide_aperture] %s %dx%d max_radius=%d%s prepare_ms=%.5f gather_ms=%.5f wide_prepare_ms=%.5f reduce_ms=%.5f small_gather_ms=%.5f compose_ms=%.5f\n",
+                sizeof(T) == 8 ? "f64" : "f32", width, height, d->max_radius, views, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
     }
     return 0;
 }
 
 template <typename T, typename CamT>
-static int launch_wide_aperture(const rtw_wide_aperture_t *b, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream) {
+static int launch_wide_aperture(const rtw_wide_aperture_t *b, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream,
+                                const LensViews *vb) {
     const rtw_defocus_t d = as_defocus(b);
-    if (d.max_radius <= RTW_DEFOCUS_MAX_RADIUS) return launch_defocus_t(&d, cam, width, height, d_image, d_features, d_work, d_out, stream);     // (scale 1: the defocus stage itself)
-    if (d.max_radius <= 16) return launch_scaled<T, 2>(&d, cam, width, height, d_image, d_features, d_work, d_out, stream);
-    return launch_scaled<T, 4>(&d, cam, width, height, d_image, d_features, d_work, d_out, stream);
+    if (d.max_radius <= RTW_DEFOCUS_MAX_RADIUS) return launch_defocus_t(&d, cam, width, height, d_image, d_features, d_work, d_out, stream, vb);     // (scale 1: the defocus stage itself)
+    if (d.max_radius <= 16) return launch_scaled<T, 2>(&d, cam, width, height, d_image, d_features, d_work, d_out, stream, vb);
+    return launch_scaled<T, 4>(&d, cam, width, height, d_image, d_features, d_work, d_out, stream, vb);
 }
 
-int launch_wide_aperture_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_wide_aperture<float>(b, cam, w, h, img, feat, work, out, st); }
-int launch_wide_aperture_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st) { return launch_wide_aperture<double>(b, cam, w, h, img, feat, work, out, st); }
+int launch_wide_aperture_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb) { return launch_wide_aperture<float>(b, cam, w, h, img, feat, work, out, st, vb); }
+int launch_wide_aperture_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb) { return launch_wide_aperture<double>(b, cam, w, h, img, feat, work, out, st, vb); }
+
+// ---- the batch (rtw_lens_batch_*, rtw_lens_table_*) -----------------------------------------------------------------------------
+// the batch's own size rule: the batched filter's frame rule on (width, height, number of views)
+static int check_views_size(int32_t width, int32_t height, int32_t n_views) {
+    if ((double)width * (double)height * (double)n_views >= (double)(1ll << 39)) return fail(-5, "batch too large for one call: %d views of %d x %d pixels", n_views, width, height);
+    return 0;
+}
+
+template <typename CamT>
+static int validate_lens_batch_t(const rtw_wide_aperture_t *b, const CamT *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens,
+                                 std::vector<rtw_defocus_t> *lens_out) {
+    if (!b || !cams) return fail(-1, "null wide-aperture parameters or cameras");
+    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
+    if (lens_out) lens_out->clear();
+    for (int32_t v = 0; v < n_views; ++v) {
+        rtw_wide_aperture_t bv = *b;
+        if (lens_radii) bv.lens_radius = lens_radii[v];
+        if (focus_dists) bv.focus_dist = focus_dists[v];
+        if (own_lens && bv.lens_radius == -1) bv.lens_radius = (double)cams[v].lens_radius;       // (the one-call form alone: the camera's own aperture)
+        if (int rc = validate_wide_aperture(&bv, cams + v, width, height)) {
+            if (n_views > 1 || lens_radii || focus_dists) {
+                const std::string why = g_err;
+                return fail(rc, "view %d: %s", v, why.c_str());
+            }
+            return rc;
+        }
+        if (lens_out) lens_out->push_back(as_defocus(&bv));
+    }
+    return check_views_size(width, height, n_views);
+}
+int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, std::vector<rtw_defocus_t> *lens_out) { return validate_lens_batch_t(b, cams, n_views, width, height, lens_radii, focus_dists, own_lens, lens_out); }
+int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, std::vector<rtw_defocus_t> *lens_out) { return validate_lens_batch_t(b, cams, n_views, width, height, lens_radii, focus_dists, own_lens, lens_out); }
+void lens_table_f32(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f32 *cams, int32_t width, float *table) { for (size_t v = 0; v < lens.size(); ++v) lens_table_entry_f32(&lens[v], cams + v, width, table + 32 * v); }
+void lens_table_f64(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f64 *cams, int32_t width, double *table) { for (size_t v = 0; v < lens.size(); ++v) lens_table_entry_f64(&lens[v], cams + v, width, table + 32 * v); }
+
+// What the batched device entry point checks of its count and frame: it has no camera and reads no lens, so of validate_defocus's checks
+// those on max_radius, flags, gamma, device, reserved and the frame remain, with its codes.
+int validate_lens_batch_frame(const rtw_wide_aperture_t *b, int32_t n_views, int32_t n_frames, int32_t width, int32_t height, int elem_bytes) {
+    if (!b) return fail(-1, "null wide-aperture parameters");
+    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
+    if (n_frames != 1 && n_frames != n_views) return fail(-2, "n_frames must be 1 (every view reads one frame) or n_views (got %d for %d views)", n_frames, n_views);
+    if (b->max_radius < 1 || b->max_radius > RTW_WIDE_APERTURE_MAX_RADIUS) return fail(-2, "max_radius must be in 1..%d (got %d)", RTW_WIDE_APERTURE_MAX_RADIUS, b->max_radius);
+    if (b->flags != 0) return fail(-2, "unknown defocus flags 0x%x", b->flags);
+    if (b->gamma != 0 && b->gamma != 1) return fail(-2, "gamma must be 0 or 1 (got %d)", b->gamma);
+    if (b->device < -1) return fail(-2, "bad device %d", b->device);
+    if (b->reserved[0] != 0 || b->reserved[1] != 0) return fail(-2, "reserved must be 0");
+    if (width < 1 || height < 1) return fail(-2, "width/height must be positive (got %d x %d)", width, height);
+    if (const int64_t rc = rtw_denoise_work_bytes(width, height, elem_bytes); rc < 0) return (int)rc;         // (elem_bytes; the denoiser's frame rule)
+    return check_views_size(width, height, n_views);
+}
+
+// The device-resident entry point of the batch: nulls, the count and the frame, then the pointers' alignment and aliasing over the extents
+// of the whole batch (the inputs counted once when n_frames == 1).
+template <typename T>
+static int wide_aperture_batch_device(const rtw_wide_aperture_t *b, int32_t n_views, int32_t n_frames, const void *d_table, int32_t width, int32_t height, const void *d_images,
+                                      const void *d_features, void *d_work, void *d_out, void *stream_v) {
+    if (!b || !d_table || !d_images || !d_features || !d_work || !d_out) return fail(-1, "null argument");
+    if (int rc = validate_lens_batch_frame(b, n_views, n_frames, width, height, (int)sizeof(T))) return rc;
+    if (((uintptr_t)d_table & 15u) || ((uintptr_t)d_features & 15u) || ((uintptr_t)d_work & 15u)) return fail(-2, "the table, the feature buffer and the workspace must be 16-byte aligned");
+    if (((uintptr_t)d_images & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
+    const LensBatchLayout R(sizeof(T), width, height, b->max_radius, n_views, n_frames);
+    if (int rc = check_alias({{"d_out", d_out, R.out_b}, {"d_work", d_work, R.work_b}}, {{"d_images", d_images, R.img_b}, {"d_features", d_features, R.feat_b}, {"d_table", d_table, R.tab_b}})) return rc;
+    DeviceGuard guard;
+    if (b->device >= 0) HIP_TRY(hipSetDevice(b->device));
+    const LensViews vb = {n_views, d_table, (long long)R.img_stride, (long long)R.feat_stride, (long long)R.work_stride, (long long)R.out_stride};
+    using CamT = std::conditional_t<sizeof(T) == 8, rtw_camera_f64, rtw_camera_f32>;
+    return launch_wide_aperture<T, CamT>(b, nullptr, width, height, d_images, d_features, d_work, d_out, (hipStream_t)stream_v, &vb);
+}
+
+// rtw_lens_table_*: pure host code
+template <typename T, typename CamT>
+static int lens_table_host(const rtw_wide_aperture_t *b, const CamT *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, void *table) {
+    if (!b || !cams || !table) return fail(-1, "null argument");
+    std::vector<rtw_defocus_t> lens;
+    if (int rc = validate_lens_batch(b, cams, n_views, width, height, lens_radii, focus_dists, false, &lens)) return rc;
+    lens_table_t(lens, cams, width, (T *)table);
+    return 0;
+}
 
 // The device-resident entry point: nulls, the parameters, then the pointers' alignment and aliasing.
 template <typename T, typename CamT>
@@ -104,7 +199,7 @@ static int wide_aperture_device(const rtw_wide_aperture_t *b, const CamT *cam, i
     if (int rc = check_alias({{"d_out", d_out, img_b}, {"d_work", d_work, work_b}}, {{"d_image", d_image, img_b}, {"d_features", d_features, feat_b}})) return rc;
     DeviceGuard guard;
     if (b->device >= 0) HIP_TRY(hipSetDevice(b->device));
-    return launch_wide_aperture<T>(b, cam, width, height, d_image, d_features, d_work, d_out, (hipStream_t)stream_v);
+    return launch_wide_aperture<T>(b, cam, width, height, d_image, d_features, d_work, d_out, (hipStream_t)stream_v, nullptr);
 }
 
 }  // namespace rtwh
@@ -125,6 +220,33 @@ int rtw_wide_aperture_device_f32(const rtw_wide_aperture_t *b, const rtw_camera_
 int rtw_wide_aperture_device_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work,
                                  void *d_out, void *hip_stream) {
     return wide_aperture_device<double>(b, cam, width, height, d_image, d_features, d_work, d_out, hip_stream);
+}
+
+int64_t rtw_lens_table_bytes(int32_t n_views, int32_t elem_bytes) {
+    if (elem_bytes != 4 && elem_bytes != 8) return fail(-2, "elem_bytes must be 4 or 8 (got %d)", elem_bytes);
+    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
+    return (int64_t)n_views * 32 * elem_bytes;
+}
+int rtw_lens_table_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, void *table) {
+    return lens_table_host<float>(b, cams, n_views, width, height, lens_radii, focus_dists, table);
+}
+int rtw_lens_table_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, void *table) {
+    return lens_table_host<double>(b, cams, n_views, width, height, lens_radii, focus_dists, table);
+}
+int64_t rtw_lens_batch_work_bytes(int32_t width, int32_t height, int32_t elem_bytes, int32_t max_radius, int32_t n_views) {
+    const int64_t one = rtw_wide_aperture_work_bytes(width, height, elem_bytes, max_radius);
+    if (one < 0) return one;
+    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
+    if (int rc = check_views_size(width, height, n_views)) return rc;
+    return one * n_views;
+}
+int rtw_lens_batch_device_f32(const rtw_wide_aperture_t *b, int32_t n_views, int32_t n_frames, const void *d_table, int32_t width, int32_t height, const void *d_images,
+                                       const void *d_features, void *d_work, void *d_out, void *hip_stream) {
+    return wide_aperture_batch_device<float>(b, n_views, n_frames, d_table, width, height, d_images, d_features, d_work, d_out, hip_stream);
+}
+int rtw_lens_batch_device_f64(const rtw_wide_aperture_t *b, int32_t n_views, int32_t n_frames, const void *d_table, int32_t width, int32_t height, const void *d_images,
+                                       const void *d_features, void *d_work, void *d_out, void *hip_stream) {
+    return wide_aperture_batch_device<double>(b, n_views, n_frames, d_table, width, height, d_images, d_features, d_work, d_out, hip_stream);
 }
 
 }  // extern "C"

@@ -9,6 +9,8 @@
 //   wa_compose<T, S>  one full-size pixel per lane, the 16 x 16 tile mapping.  The four bilinear taps are read from global memory: the S x S
 //                     pixels of a block share them, so a wave's 64 pixels touch at most (16/S + 1) * (4/S + 1) small pixels, and the small
 //                     planes (1/4 or 1/16 of the frame) stay in L2.  No LDS, no barrier.
+//   VIEWS             true (rtw_lens_batch_device_*): n_views views in one launch, rtw_defocus.hpp DfViews with one stride per pointer;
+//                     false: the instance is the single form's, instruction for instruction.
 // Every operation is rounded once (the Makefile's -ffp-contract=off -fno-fast-math); divisions and sqrt are the compiler's IEEE ones; what does not
 // take part is dropped by selects.  A block's pixels outside the frame are not loaded.
 #pragma once
@@ -18,11 +20,17 @@ namespace rtw {
 
 constexpr int WA_MAX_RADIUS = 32;       // RTW_WIDE_APERTURE_MAX_RADIUS
 
-template <typename T, int S>
+template <typename T, int S, bool VIEWS = false>
 __global__ __launch_bounds__(256) void wa_reduce(int W_, int H_, const T *__restrict__ image, const typename DnVec<T>::type *__restrict__ coc, T *__restrict__ lo_image,
-                                                 typename DnVec<T>::type *__restrict__ lo_coc, T *__restrict__ lo_tile) {
+                                                 typename DnVec<T>::type *__restrict__ lo_coc, T *__restrict__ lo_tile, [[maybe_unused]] DfViews<T, VIEWS, 5> B) {
     using V = typename DnVec<T>::type;
     __shared__ T s_r[4];
+    if constexpr (VIEWS) {
+        const long long v = df_view();
+        if (v >= B.n_views) return;
+        image = tp_adv(image, v * B.stride[0]); coc = tp_adv(coc, v * B.stride[1]); lo_image = tp_adv(lo_image, v * B.stride[2]);
+        lo_coc = tp_adv(lo_coc, v * B.stride[3]); lo_tile = tp_adv(lo_tile, v * B.stride[4]);
+    }
     const int H = H_, W = W_;
     const int h = (H + S - 1) / S, w = (W + S - 1) / S;
     const int th = (h + DF_TILE - 1) / DF_TILE;
@@ -76,10 +84,17 @@ __global__ __launch_bounds__(256) void wa_reduce(int W_, int H_, const T *__rest
 }
 
 // coc: the WIDE CoC plane; narrow: N, the defocus stage's output with max_radius 8, linear; lo_coc, lo_out: the small CoC plane and the small gather's image O
-template <typename T, int S>
+template <typename T, int S, bool VIEWS = false>
 __global__ __launch_bounds__(256) void wa_compose(int W_, int H_, int gamma, const typename DnVec<T>::type *__restrict__ coc, const T *__restrict__ narrow,
-                                                  const typename DnVec<T>::type *__restrict__ lo_coc, const T *__restrict__ lo_out, T *__restrict__ out) {
+                                                  const typename DnVec<T>::type *__restrict__ lo_coc, const T *__restrict__ lo_out, T *__restrict__ out,
+                                                  [[maybe_unused]] DfViews<T, VIEWS, 5> B) {
     using V = typename DnVec<T>::type;
+    if constexpr (VIEWS) {
+        const long long v = df_view();
+        if (v >= B.n_views) return;
+        coc = tp_adv(coc, v * B.stride[0]); narrow = tp_adv(narrow, v * B.stride[1]); lo_coc = tp_adv(lo_coc, v * B.stride[2]);
+        lo_out = tp_adv(lo_out, v * B.stride[3]); out = tp_adv(out, v * B.stride[4]);
+    }
     constexpr int LOG2 = S == 2 ? 2 : 3;            // 2S = 1 << LOG2
     const int H = H_, W = W_;
     const int h = (H + S - 1) / S, w = (W + S - 1) / S;

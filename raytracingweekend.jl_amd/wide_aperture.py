@@ -5,6 +5,9 @@ what is wide, and blends the two by the radius (from 4 px, the narrow result alo
 it IS the defocus stage, on the bits.  The definition is in the header; tests/wide_aperture_ref.py restates it on the CPU, twice, and the
 device agrees on the bits.  All compute happens in librtw_hip.so; there is no CPU fallback.
 
+Batches (``rtw_lens_batch_*``): ``wide_aperture_batch`` runs N views, ``focus_bracket`` ONE frame under N lenses, in the same six
+launches; ``render_wide_aperture_batch`` is the one-call form for N cameras.  View ``v`` is the single call on the bits.
+
 Defaults: ``max_radius=32, focus_dist=0`` (the camera's own focus plane), ``gamma=True``; what they buy on the CPU witness: DESIGN.md section 7.27.
 """
 import ctypes as C
@@ -14,7 +17,7 @@ import numpy as np
 from . import _capi
 from .defocus import _DENOISE_KEYS, _camera_arg
 from .denoise import make_denoise
-from .render import _frame_height, _record_stats
+from .render import _batch_cameras, _frame_height, _record_stats
 from .structs import Camera, flatten_scene
 
 _STAGE_KEYS = ("lens_radius", "focus_dist", "max_radius")
@@ -96,3 +99,138 @@ def render_wide_aperture(scene, cam, image_width=400, n_samples=1, *, depth=16, 
     del keep
     _record_stats(L)
     return out.reshape(int(image_width), height, 3).transpose(1, 0, 2)
+
+
+# ---- batched views and brackets (include/rtw_hip.h rtw_lens_batch_*): N views, or one frame under N lenses, in each launch ----------
+
+def _lens_arrays(lens_radii, focus_dists, n):
+    """per-view arrays (None: the keyword for every view) -> two ctypes arrays of n doubles, or None"""
+    out = []
+    for name, a in (("lens_radii", lens_radii), ("focus_dists", focus_dists)):
+        if a is None:
+            out.append(None)
+            continue
+        a = [float(x) for x in a]
+        if len(a) != n:
+            raise ValueError(f"{len(a)} {name} for {n} views")
+        out.append((C.c_double * n)(*a))
+    return out
+
+
+def lens_table(cams, image_width, image_height, *, lens_radii=None, focus_dists=None, **params):
+    """The HOST table of a batch's lenses (rtw_lens_table_*): [N, 32] elements of the cameras' type, row ``v`` the constants of ``cams[v]`` with
+    ``lens_radii[v]`` and ``focus_dists[v]`` (None: the keywords ``lens_radius`` / ``focus_dist`` for every view).  The caller uploads it for
+    ``wide_aperture_batch_into``.  Keywords: ``make_wide_aperture``."""
+    cams, T = _batch_cameras(cams)
+    n = len(cams)
+    lr, fd = _lens_arrays(lens_radii, focus_dists, n)
+    params.setdefault("lens_radius", 0.0)
+    table = np.zeros((n, 32), dtype=T)
+    fn = getattr(_capi.lib(), "rtw_lens_table_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(C.byref(make_wide_aperture(**params)), _capi.make_cameras(cams, T), n, int(image_width), int(image_height), lr, fd, table.ctypes.data_as(C.c_void_p)))
+    return table
+
+
+def wide_aperture_batch_work_bytes(image_width, image_height, n_views, elem_type=np.float32, max_radius=32):
+    """bytes of the batch's workspace: ``n_views`` single-stage workspaces one behind the other, each with the single stage's layout"""
+    n = _capi.lib().rtw_lens_batch_work_bytes(int(image_width), int(image_height), np.dtype(elem_type).itemsize, int(max_radius), int(n_views))
+    if n < 0:
+        _capi.check(int(n))
+    return int(n)
+
+
+def _batch_host(images, features, cams, n_frames, lens_radii, focus_dists, params):
+    if isinstance(features, dict):
+        features = features["raw"]
+    images, features = np.asarray(images), np.asarray(features)
+    T = images.dtype
+    if T not in (np.dtype(np.float32), np.dtype(np.float64)) or features.dtype != T:
+        raise TypeError("images and features must both be float32 or both float64")
+    if images.ndim != 4 or images.shape[-1] != 3 or features.shape != images.shape[:-1] + (8,):
+        raise ValueError(f"expected images [N, H, W, 3] and features [N, H, W, 8], got {images.shape} and {features.shape}")
+    if 0 in images.shape:
+        raise ValueError("empty images")
+    cams, Tc = _batch_cameras(cams)
+    if np.dtype(Tc) != T:
+        raise TypeError(f"the cameras have element type {np.dtype(Tc).name}, the frames {T.name}")
+    n = len(cams)
+    if images.shape[0] != n_frames:
+        raise ValueError(f"{images.shape[0]} frames where {n_frames} are expected for {n} views")
+    H, W = images.shape[1:3]
+    lr, fd = _lens_arrays(lens_radii, focus_dists, n)
+    params.setdefault("lens_radius", 0.0)
+    img, feat = (np.ascontiguousarray(np.swapaxes(a, 1, 2)) for a in (images, features))      # the library's layout: pixel (i, j) of view v at v*W*H + j*H + i
+    out = np.empty((n, W, H, 3), dtype=T)
+    fn = getattr(_capi.lib(), "rtw_lens_batch_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(C.byref(make_wide_aperture(**params)), _capi.make_cameras(cams, T.type), n, n_frames, lr, fd, W, H, *(a.ctypes.data_as(C.c_void_p) for a in (img, feat, out))))
+    return np.swapaxes(out, 1, 2)
+
+
+def wide_aperture_batch(images, features, cams, *, lens_radii=None, focus_dists=None, **params):
+    """``images`` [N, H, W, 3] and ``features`` [N, H, W, 8] -- or the dict ``render_features_batch`` returns -- of N views seen through
+    ``cams`` -> the N images [N, H, W, 3] in six launches for all views, two when ``max_radius <= 8`` (rtw_lens_batch_*).
+    ``lens_radii`` / ``focus_dists``: per-view sequences (None: the keywords ``lens_radius`` / ``focus_dist`` for every view).  View ``v`` is
+    bit for bit ``wide_aperture(images[v], features[v], cams[v], lens_radius=lens_radii[v], focus_dist=focus_dists[v], ...)``.  Keywords:
+    ``make_wide_aperture``.  Blocking; ``last_stats()`` is left as it was."""
+    cams = list(cams)
+    return _batch_host(images, features, cams, len(cams), lens_radii, focus_dists, params)
+
+
+def focus_bracket(image, features, cam, *, focus_dists=None, lens_radii=None, **params):
+    """ONE frame under N lenses in one call (rtw_lens_batch_* with ``n_frames == 1``): ``image`` [H, W, 3] and ``features``
+    [H, W, 8] of the frame seen through ``cam``; ``focus_dists`` and/or ``lens_radii``: sequences of N values (one of them may be None: the
+    keyword ``focus_dist`` / ``lens_radius`` for every lens) -> [N, H, W, 3].  Lens ``v`` is bit for bit ``wide_aperture(image, features, cam,
+    lens_radius=lens_radii[v], focus_dist=focus_dists[v], ...)``.  Keywords: ``make_wide_aperture``.  Blocking."""
+    if focus_dists is None and lens_radii is None:
+        raise ValueError("a bracket needs focus_dists, lens_radii or both")
+    n = len(list(focus_dists if focus_dists is not None else lens_radii))
+    if n < 1:
+        raise ValueError("a bracket needs at least one lens")
+    if isinstance(features, dict):
+        features = features["raw"]
+    return _batch_host(np.asarray(image)[None], np.asarray(features)[None], [cam] * n, 1, lens_radii, focus_dists, params)
+
+
+def wide_aperture_batch_into(d_out_ptr, d_work_ptr, d_images_ptr, d_features_ptr, d_table_ptr, image_width, image_height, n_views, *, n_frames=None, elem_type=np.float32,
+                             stream=0, max_radius=32, gamma=True, device=-1):
+    """The device-resident batched stage (rtw_lens_batch_device_*): six launches on ``stream`` (two when ``max_radius <= 8``) for
+    ``n_views`` views.  DEVICE pointers: ``d_table_ptr`` the uploaded ``lens_table`` (16-byte aligned; the per-view lens lives there), the
+    images and features of ``n_frames`` frames (``n_views``, the default, or 1: every view reads frame 0), ``d_work_ptr`` of
+    ``wide_aperture_batch_work_bytes`` bytes and ``d_out_ptr`` of ``n_views`` frames, views one behind the other."""
+    T = np.dtype(elem_type).type
+    fn = getattr(_capi.lib(), "rtw_lens_batch_device_" + ("f64" if _capi.is_f64(T) else "f32"))
+    B = make_wide_aperture(0.0, 0.0, max_radius, gamma, device)
+    _capi.check(fn(C.byref(B), int(n_views), int(n_views if n_frames is None else n_frames), C.c_void_p(int(d_table_ptr)), int(image_width), int(image_height),
+                   *(C.c_void_p(int(q)) for q in (d_images_ptr, d_features_ptr, d_work_ptr, d_out_ptr)), C.c_void_p(int(stream))))
+
+
+def render_wide_aperture_batch(scene, cams, image_width=400, n_samples=1, *, seeds=None, depth=16, seed=1, n_chunks=0, device=-1, gamma=True, denoise=None, wide_aperture=None,
+                               lens_radii=None, focus_dists=None):
+    """``render_wide_aperture`` for N cameras in one call (rtw_render_lens_batch_*): one batched render and one batched feature
+    pass through the pinhole copies, with ``denoise`` one batched filter pass, then the batched lens stage; the result comes back once.
+    Returns ``img[v, i, j, :]``; view ``v`` is bit for bit ``render_wide_aperture(scene, cams[v], ..., seed=seeds[v])`` with
+    ``lens_radii[v]`` (default: the camera's own) and ``focus_dists[v]``.  ``last_stats()`` reports the render."""
+    cams, T = _batch_cameras(cams)
+    n = len(cams)
+    dk = {} if denoise in (None, False, True) else dict(denoise)
+    if set(dk) - set(_DENOISE_KEYS):
+        raise ValueError(f"denoise takes the keywords {_DENOISE_KEYS}, got {sorted(set(dk) - set(_DENOISE_KEYS))}")
+    bk = {} if wide_aperture is None else dict(wide_aperture)
+    if set(bk) - set(_STAGE_KEYS):
+        raise ValueError(f"wide_aperture takes the keywords {_STAGE_KEYS}, got {sorted(set(bk) - set(_STAGE_KEYS))}")
+    bk.setdefault("lens_radius", -1.0)                       # (the one-call form alone: the camera's own)
+    lr, fd = _lens_arrays(lens_radii, focus_dists, n)
+    sd = _capi.make_seeds(seed if seeds is None else seeds, n)
+    height = _frame_height(image_width, n_samples)
+    L = _capi.lib()
+    flat = scene if isinstance(scene, dict) else flatten_scene(scene, T)
+    S, keep = _capi.make_scene(flat, T)
+    P = _capi.make_params(image_width, height, n_samples, depth, seed, n_chunks, 0, 1, device, 1 if gamma else 0, 0)
+    D = make_denoise(gamma=gamma, **dk) if denoise else None
+    B = make_wide_aperture(gamma=gamma, **bk)
+    out = np.empty(n * height * int(image_width) * 3, dtype=T)
+    fn = getattr(L, "rtw_render_lens_batch_" + ("f64" if _capi.is_f64(T) else "f32"))
+    _capi.check(fn(C.byref(S), _capi.make_cameras(cams, T), n, sd, C.byref(P), C.byref(D) if D is not None else None, C.byref(B), lr, fd, out.ctypes.data_as(C.c_void_p)))
+    del keep
+    _record_stats(L)
+    return out.reshape(n, int(image_width), height, 3).transpose(0, 2, 1, 3)
