@@ -1,7 +1,8 @@
-// rtw_defocus.hip -- the defocus stage (include/rtw_hip.h rtw_defocus_*): the checks that need no device, the host constants, the workspace's
-// layout, the two launches of its kernels (rtw_defocus.hpp) and the device-resident entry points.
-// (The host-buffer entry points live with the other cached-context paths: rtw_defocus_* in rtw_stage_host.hip, rtw_render_defocused_* in
-// rtw_render_host.hip.)
+// rtw_defocus.hip -- the defocus stage (include/rtw_hip.h rtw_defocus_*) and what the whole lens family takes from it: the checks of one
+// view that need no device, in their four parts (validate_lens), the host constants (one view's entry of the lens table) and the two
+// launches of its kernels (rtw_defocus.hpp).  The workspace's size comes from rtw_layout.hpp WideApertureLayout.
+// (The entry points of the family share one body per tier: lens_device in rtw_wide_aperture.hip behind rtw_defocus_device_*, lens_host in
+// rtw_stage_host.hip behind rtw_defocus_*, render_host_lens in rtw_render_host.hip behind rtw_render_defocused_*.)
 #include "rtw_host.hpp"
 #include "rtw_defocus.hpp"
 
@@ -31,35 +32,50 @@ void lens_table_entry(const rtw_defocus_t *b, const CamT *cam, int32_t width, T 
 void lens_table_entry_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, float *e) { lens_table_entry<float>(b, cam, width, e); }
 void lens_table_entry_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, double *e) { lens_table_entry<double>(b, cam, width, e); }
 
-// Everything about a defocus that is decided without a device and without a pointer.
-template <typename CamT>
-int validate_defocus_t(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, int elem_bytes, int top = RTW_DEFOCUS_MAX_RADIUS) {
-    if (!b || !cam) return fail(-1, "null defocus parameters or camera");
+// Everything about a lens stage that is decided without a device and without a pointer, in four parts, in the order every entry point of
+// the family applies them.  1: the parameters -- max_radius against the stage's `top` (8: the defocus stage, 32: the wide-aperture stage and
+// the batch), flags, gamma, device, reserved.
+int check_lens_params(const rtw_defocus_t *b, int top) {
     if (b->max_radius < 1 || b->max_radius > top) return fail(-2, "max_radius must be in 1..%d (got %d)", top, b->max_radius);
     if (b->flags != 0) return fail(-2, "unknown defocus flags 0x%x", b->flags);
     if (b->gamma != 0 && b->gamma != 1) return fail(-2, "gamma must be 0 or 1 (got %d)", b->gamma);
     if (b->device < -1) return fail(-2, "bad device %d", b->device);
     if (b->reserved[0] != 0 || b->reserved[1] != 0) return fail(-2, "reserved must be 0");
+    return 0;
+}
+// 2: the lens
+static int check_lens_values(const rtw_defocus_t *b) {
     if (!(b->lens_radius >= 0) || !std::isfinite(b->lens_radius)) return fail(-2, "lens_radius must be finite and >= 0");
     if (!(b->focus_dist >= 0) || !std::isfinite(b->focus_dist)) return fail(-2, "focus_dist must be finite and >= 0 (0: the camera's own focus plane)");
+    return 0;
+}
+// 3: the frame -- the sizes, then elem_bytes and the denoiser's frame rule
+int check_lens_frame(int32_t width, int32_t height, int elem_bytes) {
     if (width < 1 || height < 1) return fail(-2, "width/height must be positive (got %d x %d)", width, height);
-    if (const int64_t rc = rtw_denoise_work_bytes(width, height, elem_bytes); rc < 0) return (int)rc;         // (elem_bytes; the denoiser's frame rule)
+    if (const int64_t rc = rtw_denoise_work_bytes(width, height, elem_bytes); rc < 0) return (int)rc;
+    return 0;
+}
+// 4: the camera
+template <typename CamT>
+static int check_lens_camera(const rtw_defocus_t *b, const CamT *cam, int32_t width) {
     double hh, focus, K;
     defocus_constants(b, cam, width, &hh, &focus, &K);
     if (!(hh > 0) || !std::isfinite(hh)) return fail(-2, "the camera's horizontal vector must have a finite, positive length");
     if (!(focus > 0) || !std::isfinite(focus)) return fail(-2, "the camera's focus distance (origin - lower_left_corner).w must be finite and positive");
     return 0;
 }
-int validate_defocus(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height) { return validate_defocus_t(b, cam, width, height, 4); }
-int validate_defocus(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height) { return validate_defocus_t(b, cam, width, height, 8); }
-int validate_defocus_top(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, int top) { return validate_defocus_t(b, cam, width, height, 4, top); }
-int validate_defocus_top(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, int top) { return validate_defocus_t(b, cam, width, height, 8, top); }
-
-// the workspace: the CoC plane (a 4-element slot per pixel) and the tile plane (one element per tile, rounded up to a 16-byte multiple)
-static long long tiles_of(int32_t width, int32_t height) {
-    return (long long)((height + rtw::DF_TILE - 1) / rtw::DF_TILE) * ((width + rtw::DF_TILE - 1) / rtw::DF_TILE);
+template <typename CamT>
+static int validate_lens_t(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, int elem_bytes, int top) {
+    if (!b || !cam) return fail(-1, "null lens parameters or camera");
+    if (int rc = check_lens_params(b, top)) return rc;
+    if (int rc = check_lens_values(b)) return rc;
+    if (int rc = check_lens_frame(width, height, elem_bytes)) return rc;
+    return check_lens_camera(b, cam, width);
 }
-static long long work_bytes(int32_t width, int32_t height, int elem_bytes) { return ((long long)width * height * 4 + ((tiles_of(width, height) + 3) & ~3ll)) * elem_bytes; }
+int validate_lens(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, int top) { return validate_lens_t(b, cam, width, height, 4, top); }
+int validate_lens(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, int top) { return validate_lens_t(b, cam, width, height, 8, top); }
+
+static_assert(rtw::DF_TILE == 16, "rtw_layout.hpp WideApertureLayout::tiles counts the kernels' 16 x 16 tiles");
 
 // the view dimensions of a batched launch's grid: the view index is blockIdx.z * gridDim.y + blockIdx.y (rtw_defocus.hpp DfViews)
 dim3 lens_views_grid(unsigned tiles, int32_t n_views) {
@@ -76,7 +92,7 @@ template <typename T, typename CamT>
 int launch_prepare(const rtw_defocus_t *b, int rm, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream,
                    int32_t n_views, const void *d_table, const long long *strides) {
     using V = typename rtw::DnVec<T>::type;
-    const unsigned tiles = (unsigned)tiles_of(width, height);                 // (fewer than the frame rule's 8 x 8 ones: one 32-bit grid dimension holds them)
+    const unsigned tiles = (unsigned)WideApertureLayout::tiles(width, height);                 // (fewer than the frame rule's 8 x 8 ones: one 32-bit grid dimension holds them)
     rtw::TpParams<T> U;
     memset(&U, 0, sizeof U);
     T FK[2] = {T(0), T(0)};
@@ -107,7 +123,7 @@ template <typename T>
 int launch_gather(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream, int32_t n_views,
                   const long long *strides) {
     using V = typename rtw::DnVec<T>::type;
-    const unsigned tiles = (unsigned)tiles_of(width, height);
+    const unsigned tiles = (unsigned)WideApertureLayout::tiles(width, height);
     rtw::DfDist<T> tab;
     for (int dj = 0; dj <= rtw::DF_MAX_RADIUS; ++dj)
         for (int di = 0; di <= rtw::DF_MAX_RADIUS; ++di) tab.d[dj * (rtw::DF_MAX_RADIUS + 1) + di] = std::sqrt((T)(di * di + dj * dj));
@@ -131,7 +147,7 @@ int launch_defocus_prepare_f64(const rtw_defocus_t *b, int rm, const rtw_camera_
 int launch_defocus_gather_f32(int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st, int32_t nv, const long long *strides) { return launch_gather<float>(w, h, mmax, gamma, img, coc, tile, out, st, nv, strides); }
 int launch_defocus_gather_f64(int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st, int32_t nv, const long long *strides) { return launch_gather<double>(w, h, mmax, gamma, img, coc, tile, out, st, nv, strides); }
 
-// Enqueue the stage on `stream` of the current device (validate_defocus has accepted the call): TWO launches, no record.
+// Enqueue the stage on `stream` of the current device (validate_lens has accepted the call): TWO launches, no record.
 // vb null: one view.  vb given (rtw_lens_batch_device_* with max_radius <= 8): vb->n_views views in the same two launches -- cam and
 // b's lens are unused (the table), the buffers hold the views at vb's strides.
 template <typename T, typename CamT>
@@ -165,21 +181,6 @@ int launch_defocus(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32
 int launch_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb) { return launch_defocus<float>(b, cam, w, h, img, feat, work, out, st, vb); }
 int launch_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb) { return launch_defocus<double>(b, cam, w, h, img, feat, work, out, st, vb); }
 
-// The device-resident entry point: nulls, the parameters, then the pointers' alignment and aliasing.
-template <typename T, typename CamT>
-int defocus_device(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, void *stream_v) {
-    if (!b || !cam || !d_image || !d_features || !d_work || !d_out) return fail(-1, "null argument");
-    if (int rc = validate_defocus(b, cam, width, height)) return rc;
-    if (((uintptr_t)d_features & 15u) || ((uintptr_t)d_work & 15u)) return fail(-2, "the feature buffer and the workspace must be 16-byte aligned");
-    if (((uintptr_t)d_image & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
-    const size_t n_pix = (size_t)width * (size_t)height;
-    const size_t img_b = n_pix * 3 * sizeof(T), feat_b = n_pix * 8 * sizeof(T), work_b = (size_t)work_bytes(width, height, sizeof(T));
-    if (int rc = check_alias({{"d_out", d_out, img_b}, {"d_work", d_work, work_b}}, {{"d_image", d_image, img_b}, {"d_features", d_features, feat_b}})) return rc;
-    DeviceGuard guard;
-    if (b->device >= 0) HIP_TRY(hipSetDevice(b->device));
-    return launch_defocus<T>(b, cam, width, height, d_image, d_features, d_work, d_out, (hipStream_t)stream_v, nullptr);
-}
-
 }  // namespace rtwh
 
 using namespace rtwh;
@@ -188,15 +189,7 @@ extern "C" {
 
 int64_t rtw_defocus_work_bytes(int32_t width, int32_t height, int32_t elem_bytes) {
     if (const int64_t rc = rtw_denoise_work_bytes(width, height, elem_bytes); rc < 0) return rc;             // (elem_bytes, the sizes, the denoiser's frame rule)
-    return work_bytes(width, height, elem_bytes);
-}
-int rtw_defocus_device_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out,
-                           void *hip_stream) {
-    return defocus_device<float>(b, cam, width, height, d_image, d_features, d_work, d_out, hip_stream);
-}
-int rtw_defocus_device_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out,
-                           void *hip_stream) {
-    return defocus_device<double>(b, cam, width, height, d_image, d_features, d_work, d_out, hip_stream);
+    return (int64_t)(WideApertureLayout(width, height, RTW_DEFOCUS_MAX_RADIUS).narrow * (size_t)elem_bytes);
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 //   rtw_launch.hip       one render = one launch of the trace kernel (rtw_kernels.hpp / rtw_pool.hpp): geometry, occupancy, job shape, views
 //   rtw_render_host.hip  the host-buffer entry points that render: the pool of cached per-device contexts (scene, stream, buffer), ONE one-device path (render_one_device)
 //                        behind render, batch, feature and the composite render + stage calls, the motion pass, the accumulator's filtered call, or a device list
-//   rtw_stage_host.hip   the pure stages on host buffers (filter, present, upsampler, temporal step, motion blur, defocus): ONE path (stage_one_device) behind all of them
+//   rtw_stage_host.hip   the pure stages on host buffers (filter, present, upsampler, temporal step, motion blur, the lens stages): ONE path (stage_one_device) behind all of them
 //                        (rtw_host_ctx.hpp: what the two share -- the lease of a context, that path and render_one_device on top of it, the regions of the device buffer;
 //                        rtw_layout.hpp: the regions' byte arithmetic and the alias check, plain C++)
 //   rtw_multi.hip        what a device list needs: peer access, the on-demand RCCL binding, the un-tile kernel
@@ -20,8 +20,8 @@
 //   rtw_temporal.hip     temporal reprojection: its checks, the host constants and the one launch of a step for one path or a batch of paths (rtw_temporal.hpp; clamped: rtw_temporal_clamp.hpp), the device-resident entry points
 //   rtw_motion.hip       the first-hit motion pass over moving spheres: its checks, the motion table, the one launch of its kernel (rtw_motion.hpp), the device-resident entry points
 //   rtw_motion_blur.hip  the motion-blur stage on the motion plane: its checks, the workspace, the three launches of its kernels (rtw_motion_blur.hpp), the device-resident entry points
-//   rtw_defocus.hip      the defocus stage (depth of field on the depth plane): its checks, the host constants (one view's entry of the lens table), the workspace, the two launches of its kernels (rtw_defocus.hpp) for one view or a batch of views, the device-resident entry points
-//   rtw_wide_aperture.hip  the wide-aperture stage (circles of confusion up to 32 px): its checks, the workspace, the six launches (the defocus stage's kernels at two sizes, rtw_wide_aperture.hpp between and behind them) for one view or a batch of views, the lens table, the device-resident entry points
+//   rtw_defocus.hip      the defocus stage (depth of field on the depth plane) and the lens family's checks of one view in their four parts, the host constants (one view's entry of the lens table), the two launches of its kernels (rtw_defocus.hpp) for one view or a batch of views
+//   rtw_wide_aperture.hip  the wide-aperture stage (circles of confusion up to 32 px): the six launches (the defocus stage's kernels at two sizes, rtw_wide_aperture.hpp between and behind them) for one view or a batch of views, the checks of N views, the lens table, ONE device-resident entry point (lens_device) behind the defocus, wide-aperture and batched ones
 //   rtw_present.hip      the present stage: its checks, the one launch of its kernel (rtw_present.hpp) for one frame or a batch, the device-resident entry points
 //   (rtw_scene_view.hpp: what both launch functions derive from their arguments; rtw_instances.hpp: the one table of the trace kernel's instances)
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
@@ -412,26 +412,48 @@ int launch_motion_blur_f64(const rtw_velocity_blur_t *b, const rtw_camera_f64 *c
 inline int launch_motion_blur_t(const rtw_velocity_blur_t *b, const rtw_camera_f32 *c, const rtw_camera_f32 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *mo, void *work, void *out, hipStream_t st) { return launch_motion_blur_f32(b, c, cp, w, h, img, feat, mo, work, out, st); }
 inline int launch_motion_blur_t(const rtw_velocity_blur_t *b, const rtw_camera_f64 *c, const rtw_camera_f64 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *mo, void *work, void *out, hipStream_t st) { return launch_motion_blur_f64(b, c, cp, w, h, img, feat, mo, work, out, st); }
 
-// rtw_defocus.hip -- the defocus stage (include/rtw_hip.h rtw_defocus_*).  validate_defocus: every check of a defocus that needs neither a device
-// nor a pointer (the camera's focus plane and horizontal extent among them).  launch_defocus: enqueue the stage (TWO launches, no record) on
-// `stream` of the current device; d_work: rtw_defocus_work_bytes bytes.  The camera's lens_radius is not read: the aperture is b->lens_radius.
-int validate_defocus(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height);
-int validate_defocus(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height);
+// ---- the lens family: rtw_defocus_*, rtw_wide_aperture_*, rtw_lens_batch_* (include/rtw_hip.h) -----------------------------------------
+// The three stages are one: the wide-aperture stage with max_radius <= 8 IS the defocus stage, and the batch runs the same launches over N
+// views.  Each tier of entry points has ONE body -- lens_device (rtw_wide_aperture.hip), lens_host (rtw_stage_host.hip), render_host_lens
+// (rtw_render_host.hip) -- that takes `top`, the stage's largest max_radius (8 or 32), and n_views: 0 for the single forms, which then run
+// without a table and with a null LensViews.  The bodies take rtw_wide_aperture_t; the two stages' parameter structs have the same fields in
+// the same order, and an rtw_defocus_* entry point hands its own over through this copy (null stays null).
+static_assert(sizeof(rtw_wide_aperture_t) == sizeof(rtw_defocus_t) && sizeof(rtw_wide_aperture_t) == 40, "the two stages' parameters have the same fields");
+struct AsWideAperture {
+    rtw_wide_aperture_t copy;
+    const rtw_wide_aperture_t *ptr;
+    explicit AsWideAperture(const rtw_defocus_t *b) : ptr(b ? &copy : nullptr) { if (b) memcpy(&copy, b, sizeof copy); }
+};
+// rtw_lens_batch_* and rtw_lens_batch_device_* NAME the count they refuse, so batch_views' -1 will not do for them: they hand their
+// caller's count down as it is but for 0 -- below the ABI the single form --, which goes down as LENS_NO_VIEWS and is refused and named
+// as the 0 it was (validate_lens_batch_frame).
+constexpr int32_t LENS_NO_VIEWS = std::numeric_limits<int32_t>::min();
+inline int32_t lens_batch_views(int32_t n_views) { return n_views ? n_views : LENS_NO_VIEWS; }
+
+// rtw_defocus.hip -- the defocus stage and the family's checks of ONE view.  validate_lens: every check that needs neither a device nor a
+// pointer, in four parts in this order -- the parameters (check_lens_params: max_radius in 1..top, flags, gamma, device, reserved), the
+// lens (lens_radius, focus_dist), the frame (check_lens_frame: the sizes, then the denoiser's frame rule) and the camera (its horizontal
+// extent and focus plane).  launch_defocus: enqueue the stage (TWO launches, no record) on `stream` of the current device; d_work:
+// rtw_defocus_work_bytes bytes.  The camera's lens_radius is not read: the aperture is b->lens_radius.
+int validate_lens(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, int top);
+int validate_lens(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, int top);
+int check_lens_params(const rtw_defocus_t *b, int top);
+int check_lens_frame(int32_t width, int32_t height, int elem_bytes);
 // A batch of views for the lens stages (rtw_lens_batch_*; rtw_layout.hpp LensBatchLayout has the arithmetic): n_views >= 1 views in each
 // launch, view v's lens in entry v of the DEVICE table d_table (lens_table_entry_*), its image, features, workspace and output v strides (BYTES)
 // behind the pointers; an input stride of 0: every view reads the one frame.  Below the ABI a null LensViews is the single call.
 struct LensViews { int32_t n_views; const void *d_table; long long img_stride, feat_stride, work_stride, out_stride; };
+inline LensViews lens_views(const LensBatchLayout &R, int32_t n_views, const void *d_table) {
+    return {n_views, d_table, (long long)R.img_stride, (long long)R.feat_stride, (long long)R.work_stride, (long long)R.out_stride};
+}
 int launch_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream, const LensViews *vb = nullptr);
 int launch_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream, const LensViews *vb = nullptr);
 inline int launch_defocus_t(const rtw_defocus_t *b, const rtw_camera_f32 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb = nullptr) { return launch_defocus_f32(b, c, w, h, img, feat, work, out, st, vb); }
 inline int launch_defocus_t(const rtw_defocus_t *b, const rtw_camera_f64 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb = nullptr) { return launch_defocus_f64(b, c, w, h, img, feat, work, out, st, vb); }
-// Its two launches one by one, for the wide-aperture stage: validate_defocus_top is validate_defocus with max_radius in 1..top;
-// launch_defocus_prepare_* is the prepare launch with the clamp `rm` (b->max_radius is not read) into a CoC plane and its tile plane;
+// Its two launches one by one, for the wide-aperture stage: launch_defocus_prepare_* is the prepare launch with the clamp `rm` (b->max_radius is not read) into a CoC plane and its tile plane;
 // launch_defocus_gather_* is the gather of a frame of any size over an image, a CoC plane and a tile plane, mmax (1..8) >= every radius there.
 // n_views == 0: one view.  n_views >= 1: that many views in the same ONE launch; `strides`: four byte strides from one view to the next, one
 // per pointer in the order of the arguments; the prepare launch then reads neither b nor cam but entry v of the device table d_table.
-int validate_defocus_top(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, int top);
-int validate_defocus_top(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, int top);
 int launch_defocus_prepare_f32(const rtw_defocus_t *b, int rm, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream, int32_t n_views = 0, const void *d_table = nullptr, const long long *strides = nullptr);
 int launch_defocus_prepare_f64(const rtw_defocus_t *b, int rm, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream, int32_t n_views = 0, const void *d_table = nullptr, const long long *strides = nullptr);
 int launch_defocus_gather_f32(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream, int32_t n_views = 0, const long long *strides = nullptr);
@@ -442,27 +464,26 @@ void lens_table_entry_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int
 void lens_table_entry_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, double *e);
 
 // rtw_wide_aperture.hip -- the wide-aperture stage (include/rtw_hip.h rtw_wide_aperture_*): circles of confusion up to 32 px through a reduced
-// copy of the frame.  validate_wide_aperture: every check that needs neither a device nor a pointer (the defocus stage's, max_radius in 1..32).
-// launch_wide_aperture: enqueue the stage (SIX launches, or the defocus stage's two when max_radius <= 8; no record) on `stream` of the
+// copy of the frame.  launch_wide_aperture: enqueue the stage (SIX launches, or the defocus stage's two when max_radius <= 8 -- what the
+// defocus stage's own entry points run; no record) on `stream` of the
 // current device; d_work: rtw_wide_aperture_work_bytes bytes.  vb non-null (rtw_lens_batch_*): vb->n_views views in the same launches.
-int validate_wide_aperture(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height);
-int validate_wide_aperture(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height);
 int launch_wide_aperture_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream, const LensViews *vb = nullptr);
 int launch_wide_aperture_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream, const LensViews *vb = nullptr);
 inline int launch_wide_aperture_t(const rtw_wide_aperture_t *b, const rtw_camera_f32 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb = nullptr) { return launch_wide_aperture_f32(b, c, w, h, img, feat, work, out, st, vb); }
 inline int launch_wide_aperture_t(const rtw_wide_aperture_t *b, const rtw_camera_f64 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb = nullptr) { return launch_wide_aperture_f64(b, c, w, h, img, feat, work, out, st, vb); }
-// The batched stage's checks that need neither a device nor a pointer (rtw_lens_batch_*, rtw_lens_table_*): the count, then per view
-// the checks of validate_wide_aperture with lens_radii[v] / focus_dists[v] (null arrays: b's own) -- the first offending view is named --,
-// then the batch's size (-5).  own_lens (rtw_render_lens_batch_* alone): a lens radius of -1 is cams[v]'s own.  `lens_out` non-null:
-// n_views rtw_defocus_t with every view's lens radius and focus distance in place.
-int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, std::vector<rtw_defocus_t> *lens_out);
-int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, std::vector<rtw_defocus_t> *lens_out);
+// The checks of n_views >= 1 views that need neither a device nor a pointer (every entry point of the family but the batched device
+// form; a single form: ONE view without arrays): the count, then per view validate_lens with lens_radii[v] / focus_dists[v] (null arrays:
+// b's own) and max_radius in 1..top -- the first offending view is named, unless it is one view without arrays --, then the batch's size
+// (-5; one view never reaches it: the frame rule is the narrower).  own_lens (the one-call forms alone): a lens radius of -1 is cams[v]'s
+// own.  `lens_out` non-null: n_views rtw_defocus_t with every view's lens radius and focus distance in place.
+int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, int top, std::vector<rtw_defocus_t> *lens_out);
+int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, int top, std::vector<rtw_defocus_t> *lens_out);
 // the lens table of those views into a HOST table (32 elements per view)
 void lens_table_f32(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f32 *cams, int32_t width, float *table);
 void lens_table_f64(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f64 *cams, int32_t width, double *table);
 inline void lens_table_t(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f32 *cams, int32_t width, float *table) { lens_table_f32(lens, cams, width, table); }
 inline void lens_table_t(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f64 *cams, int32_t width, double *table) { lens_table_f64(lens, cams, width, table); }
-// what the batched device entry point checks of its frame and count without a camera (b: max_radius, gamma, device, flags, reserved alone)
+// what a batched entry point checks of its counts and frame without a camera: the counts, check_lens_params with top 32, check_lens_frame, the batch's size
 int validate_lens_batch_frame(const rtw_wide_aperture_t *b, int32_t n_views, int32_t n_frames, int32_t width, int32_t height, int elem_bytes);
 
 // rtw_present.hip -- the present stage (include/rtw_hip.h rtw_present_*).  validate_present: every check of a call that needs neither a device

@@ -119,20 +119,22 @@ struct WideApertureLayout {
     }
 };
 
-// The batched lens stage (include/rtw_hip.h rtw_lens_batch_*), in BYTES: n_views views of one size, each with its own output frame and
-// its own workspace (the single stage's layout above, work_stride bytes: a multiple of 16); n_frames == n_views: view v reads frame v of the
-// images and the features; n_frames == 1: every view reads frame 0, the input strides are 0 and the inputs' extents one frame's.
-// *_stride: from one view to the next; *_b: the extent of the whole batch; off_*, total: the regions of a context's device buffer for the
+// The lens stages (include/rtw_hip.h rtw_defocus_*, rtw_wide_aperture_*, rtw_lens_batch_*), in BYTES.  n_views >= 1: a batch of that many
+// views of one size, each with its own output frame and its own workspace (the single stage's layout above, work_stride bytes: a multiple
+// of 16); n_frames == n_views: view v reads frame v of the images and the features; n_frames == 1: every view reads frame 0, the input
+// strides are 0 and the inputs' extents one frame's.  n_views == 0: the SINGLE call -- one frame in, one out, one workspace, NO table
+// (tab_b == 0: its region is empty and `total` ends behind the workspace); n_frames is not read.
+// *_stride: from one view to the next; *_b: the extent of the whole call; off_*, total: the regions of a context's device buffer for the
 // host-buffer form -- images at 0, features, outputs, workspaces, the lens table (32 elements per view).
 struct LensBatchLayout {
     size_t frame_b, img_stride, feat_stride, out_stride, work_stride, img_b, feat_b, out_b, work_b, tab_b, off_feat, off_out, off_work, off_tab, total;
     LensBatchLayout(size_t elem, int32_t width, int32_t height, int32_t max_radius, int32_t n_views, int32_t n_frames) {
-        const size_t n = (size_t)width * (size_t)height, views = (size_t)n_views, frames = (size_t)n_frames;
+        const size_t n = (size_t)width * (size_t)height, views = n_views ? (size_t)n_views : 1, frames = n_views ? (size_t)n_frames : 1;
         frame_b = n * 3 * elem;
         img_stride = frames > 1 ? frame_b : 0; feat_stride = frames > 1 ? n * LAYOUT_FEATURE_CHANNELS * elem : 0;
         out_stride = frame_b; work_stride = WideApertureLayout(width, height, max_radius).total * elem;
         img_b = frame_b * frames; feat_b = n * LAYOUT_FEATURE_CHANNELS * elem * frames;
-        out_b = out_stride * views; work_b = work_stride * views; tab_b = views * 32 * elem;
+        out_b = out_stride * views; work_b = work_stride * views; tab_b = n_views ? views * 32 * elem : 0;
         DevLayout L;
         L.add(img_b); off_feat = L.add(feat_b); off_out = L.add(out_b); off_work = L.add(work_b); off_tab = L.add(tab_b);
         total = L.total;

@@ -1,7 +1,8 @@
 // rtw_render_host.hip -- the host-buffer entry points of the C ABI that render (rtw_render_f32/_f64 is what the Julia ccall binds; replaces src/render.jl:8-44):
 // the pool of cached per-device contexts (uploaded scene, stream, device buffer), one device (rtw_host_ctx.hpp render_one_device: the path the plain, the batched, the
 // feature, the render + filter, the render + upsample, the sequence and the render + present entry points share) or a device list (tiles dealt round-robin, shards gathered on the first device by peer
-// copies or ONE RCCL reduce: rtw_multi.hip), one D2H of the result.  The single and the batched form of a call share one body (n_views == 0: single).
+// copies or ONE RCCL reduce: rtw_multi.hip), one D2H of the result.  The single and the batched form of a call share one body (n_views == 0: single);
+// the three render + lens calls (defocused, wide aperture, lens batch) share render_host_lens.
 // (The pure stages on host buffers: rtw_stage_host.hip.)
 #include "rtw_host_ctx.hpp"
 
@@ -408,115 +409,40 @@ int render_host_upsampled(const SceneT *scene, const CamT *cams, int32_t n_views
     });
 }
 
-// Render through the pinhole and defocus in one call (rtw_render_defocused_*): the one-device path above.  The render (gamma 0) and the feature
-// pass over all chunks run through a COPY of the camera with lens_radius = 0; with `d` the filter runs with gamma 0 (launch_filtered), without it
-// render and feature pass are enqueued here; then the stage's two launches with p->gamma and the user's aperture (b->lens_radius == -1: the
-// camera's own) into a region behind the denoiser's, ONE D2H.  rtw_stats() reports the render's record.
+// Render through the pinhole and apply the lens afterwards in one call: the one-device path above.  n_views == 0 (rtw_render_defocused_*: top 8,
+// rtw_render_wide_aperture_*: top 32): one view; n_views >= 1 (rtw_render_lens_batch_*): that many views through the batched launch sequences
+// that exist.  ONE render (gamma 0) and ONE feature pass over all chunks run through COPIES of the cameras with lens_radius = 0; with `d` ONE
+// filter pass with gamma 0 (launch_filtered).  A batch alone then has ONE H2D of the lens table (built here: view v's lens is lens_radii[v] /
+// focus_dists[v], null arrays: b's); a single call passes its constants as kernel arguments and has no table.  Then the stage -- six
+// launches, two when max_radius <= 8 -- with p->gamma into a region behind the denoiser's, ONE D2H.  A lens radius of -1 is the camera's own
+// (validate_lens_batch).  rtw_stats() reports the render's record.
 template <typename T, typename SceneT, typename CamT>
-int render_host_defocused(const SceneT *scene, const CamT *cam, const rtw_params *p, const rtw_denoise_t *d, const rtw_defocus_t *b, T *out) {
-    if (!p) return fail(-1, "null params");
-    if (!scene || !cam || !b || !out) return fail(-1, "null argument");
-    int nch, cs;
-    if (int rc = validate_features(p, 0, 1, &nch, &cs)) return rc;
-    if (scene->n < 0) return fail(-2, "negative sphere count");
-    if (d) if (int rc = validate_denoise(d, p->width, p->height)) return rc;
-    rtw_defocus_t bb = *b;
-    if (bb.lens_radius == -1) bb.lens_radius = (double)cam->lens_radius;      // (here and only here: the camera's own aperture)
-    if (int rc = validate_defocus(&bb, cam, p->width, p->height)) return rc;
-    bb.gamma = p->gamma != 0;                                                  // (b's gamma and device are judged, then replaced by p's)
-    CamT pin = *cam;
-    pin.lens_radius = 0;
-    DeviceGuard guard;
-    release_last();
-    const DenoiseRegions<T> R(p->width, p->height, 0);
-    DevLayout L{R.total};
-    const size_t off_df = L.add(R.img_b), off_work = L.add((size_t)rtw_defocus_work_bytes(p->width, p->height, (int32_t)sizeof(T)));
-    SideRec frec;                                             // (the feature pass's record)
-    return render_one_device(p->device, scene, p, L.total, off_df, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
-        char *base = (char *)hc->d_img;
-        int rc;
-        if (d) {
-            rc = launch_filtered(hc, q, &pin, 0, nullptr, 0, d, nch, R, rec, rctx, frec);
-        } else {
-            q.gamma = 0;
-            rc = launch_render_t(hc->scene, &pin, 0, nullptr, &q, base, hc->stream, rec, rctx);
-            if (!rc) rc = launch_features_t(hc->scene, &pin, 0, nullptr, &q, 0, nch, base + R.off_feat, hc->stream, &frec.rec, &frec.ctx);
-        }
-        bb.device = hc->device;
-        if (!rc) rc = launch_defocus_t(&bb, &pin, p->width, p->height, base + (d ? R.off_out : 0), base + R.off_feat, base + off_work, base + off_df, hc->stream);
-        return rc;
-    });
-}
-
-// Render through the pinhole and apply a wide aperture in one call (rtw_render_wide_aperture_*): render_host_defocused above with the
-// wide-aperture stage's launches (six, or two when max_radius <= 8) and workspace in place of the defocus stage's.
-template <typename T, typename SceneT, typename CamT>
-int render_host_wide_aperture(const SceneT *scene, const CamT *cam, const rtw_params *p, const rtw_denoise_t *d, const rtw_wide_aperture_t *b, T *out) {
-    if (!p) return fail(-1, "null params");
-    if (!scene || !cam || !b || !out) return fail(-1, "null argument");
-    int nch, cs;
-    if (int rc = validate_features(p, 0, 1, &nch, &cs)) return rc;
-    if (scene->n < 0) return fail(-2, "negative sphere count");
-    if (d) if (int rc = validate_denoise(d, p->width, p->height)) return rc;
-    rtw_wide_aperture_t bb = *b;
-    if (bb.lens_radius == -1) bb.lens_radius = (double)cam->lens_radius;      // (here and only here: the camera's own aperture)
-    if (int rc = validate_wide_aperture(&bb, cam, p->width, p->height)) return rc;
-    bb.gamma = p->gamma != 0;                                                  // (b's gamma and device are judged, then replaced by p's)
-    CamT pin = *cam;
-    pin.lens_radius = 0;
-    DeviceGuard guard;
-    release_last();
-    const DenoiseRegions<T> R(p->width, p->height, 0);
-    DevLayout L{R.total};
-    const size_t off_wa = L.add(R.img_b), off_work = L.add(WideApertureLayout(p->width, p->height, bb.max_radius).total * sizeof(T));
-    SideRec frec;                                             // (the feature pass's record)
-    return render_one_device(p->device, scene, p, L.total, off_wa, R.img_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
-        char *base = (char *)hc->d_img;
-        int rc;
-        if (d) {
-            rc = launch_filtered(hc, q, &pin, 0, nullptr, 0, d, nch, R, rec, rctx, frec);
-        } else {
-            q.gamma = 0;
-            rc = launch_render_t(hc->scene, &pin, 0, nullptr, &q, base, hc->stream, rec, rctx);
-            if (!rc) rc = launch_features_t(hc->scene, &pin, 0, nullptr, &q, 0, nch, base + R.off_feat, hc->stream, &frec.rec, &frec.ctx);
-        }
-        bb.device = hc->device;
-        if (!rc) rc = launch_wide_aperture_t(&bb, &pin, p->width, p->height, base + (d ? R.off_out : 0), base + R.off_feat, base + off_work, base + off_wa, hc->stream);
-        return rc;
-    });
-}
-
-// N views through their pinholes and N lenses in one call (rtw_render_lens_batch_*): the one-device path above with the batched launch
-// sequences that exist -- ONE batched render (gamma 0) and ONE batched feature pass over all chunks through copies of the cameras with
-// lens_radius = 0, with `d` ONE batched filter pass (launch_filtered, gamma 0) --, ONE H2D of the lens table (built here: view v's lens is
-// lens_radii[v] / focus_dists[v], null arrays: b's; a lens radius of -1: cams[v]'s own), the batched stage with p->gamma into a region behind the
-// denoiser's, ONE D2H.  rtw_stats() reports the render's record.
-template <typename T, typename SceneT, typename CamT>
-int render_host_wide_aperture_batch(const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, const rtw_wide_aperture_t *b,
-                                    const double *lens_radii, const double *focus_dists, T *out) {
+int render_host_lens(int top, const SceneT *scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d, const rtw_wide_aperture_t *b,
+                     const double *lens_radii, const double *focus_dists, T *out) {
     if (!p) return fail(-1, "null params");
     if (!scene || !cams || !b || !out) return fail(-1, "null argument");
     int nch, cs;
-    if (int rc = validate_features_batch(cams, n_views, p, 0, 1, out, &nch, &cs)) return rc;
+    if (int rc = n_views ? validate_features_batch(cams, n_views, p, 0, 1, out, &nch, &cs) : validate_features(p, 0, 1, &nch, &cs)) return rc;
     if (scene->n < 0) return fail(-2, "negative sphere count");
-    if (d) if (int rc = validate_filter_batch(d, p->width, p->height, n_views)) return rc;
+    if (d) if (int rc = n_views ? validate_filter_batch(d, p->width, p->height, n_views) : validate_denoise(d, p->width, p->height)) return rc;
+    const int32_t views = n_views ? n_views : 1;
     std::vector<rtw_defocus_t> lens;
-    if (int rc = validate_lens_batch(b, cams, n_views, p->width, p->height, lens_radii, focus_dists, true, &lens)) return rc;
+    if (int rc = validate_lens_batch(b, cams, views, p->width, p->height, lens_radii, focus_dists, true, top, &lens)) return rc;
     rtw_wide_aperture_t bb = *b;
-    bb.lens_radius = 0; bb.focus_dist = 0;                                     // (the lens lives in the table)
+    bb.lens_radius = lens[0].lens_radius;                                      // (a single call's lens with the -1 resolved; a batch's lives in the table and this one is not read)
     bb.gamma = p->gamma != 0;                                                  // (b's gamma and device are judged, then replaced by p's)
-    std::vector<CamT> pins(cams, cams + n_views);
+    std::vector<CamT> pins(cams, cams + views);
     for (CamT &c : pins) c.lens_radius = 0;
-    std::vector<T> table((size_t)n_views * 32);
-    lens_table_t(lens, pins.data(), p->width, table.data());
+    std::vector<T> table;
+    if (n_views) { table.resize((size_t)n_views * 32); lens_table_t(lens, pins.data(), p->width, table.data()); }
     DeviceGuard guard;
     release_last();
     const DenoiseRegions<T> R(p->width, p->height, n_views);
     const LensBatchLayout B(sizeof(T), p->width, p->height, bb.max_radius, n_views, n_views);
     DevLayout L{R.total};
-    const size_t off_wa = L.add(B.out_b), off_work = L.add(B.work_b), off_tab = L.add(B.tab_b);
+    const size_t off_lens = L.add(B.out_b), off_work = L.add(B.work_b), off_tab = L.add(B.tab_b);
     SideRec frec;                                             // (the feature pass's record)
-    return render_one_device(p->device, scene, p, L.total, off_wa, B.out_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
+    return render_one_device(p->device, scene, p, L.total, off_lens, B.out_b, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
         char *base = (char *)hc->d_img;
         int rc;
         if (d) {
@@ -527,10 +453,10 @@ int render_host_wide_aperture_batch(const SceneT *scene, const CamT *cams, int32
             if (!rc) rc = launch_features_t(hc->scene, pins.data(), n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec.rec, &frec.ctx);
         }
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(base + off_tab, table.data(), B.tab_b, hipMemcpyHostToDevice, hc->stream));
+        if (n_views) HIP_TRY(hipMemcpyAsync(base + off_tab, table.data(), B.tab_b, hipMemcpyHostToDevice, hc->stream));
         bb.device = hc->device;
-        const LensViews vb = {n_views, base + off_tab, (long long)B.img_stride, (long long)B.feat_stride, (long long)B.work_stride, (long long)B.out_stride};
-        return launch_wide_aperture_t(&bb, (const CamT *)nullptr, p->width, p->height, base + (d ? R.off_out : 0), base + R.off_feat, base + off_work, base + off_wa, hc->stream, &vb);
+        const LensViews vb = lens_views(B, n_views, base + off_tab);
+        return launch_wide_aperture_t(&bb, pins.data(), p->width, p->height, base + (d ? R.off_out : 0), base + R.off_feat, base + off_work, base + off_lens, hc->stream, n_views ? &vb : nullptr);
     });
 }
 
@@ -880,24 +806,24 @@ int rtw_render_blurred_f64(const rtw_scene_f64 *scenes, const rtw_camera_f64 *ca
     return render_host_animation<double>(scenes, cams, n_frames, seeds, p, t, c, d, out, b, true);
 }
 int rtw_render_defocused_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, const rtw_defocus_t *b, float *out) {
-    return render_host_defocused<float>(scene, cam, p, d, b, out);
+    return render_host_lens<float>(RTW_DEFOCUS_MAX_RADIUS, scene, cam, 0, nullptr, p, d, AsWideAperture(b).ptr, nullptr, nullptr, out);
 }
 int rtw_render_defocused_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, const rtw_defocus_t *b, double *out) {
-    return render_host_defocused<double>(scene, cam, p, d, b, out);
+    return render_host_lens<double>(RTW_DEFOCUS_MAX_RADIUS, scene, cam, 0, nullptr, p, d, AsWideAperture(b).ptr, nullptr, nullptr, out);
 }
 int rtw_render_wide_aperture_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cam, const rtw_params *p, const rtw_denoise_t *d, const rtw_wide_aperture_t *b, float *out) {
-    return render_host_wide_aperture<float>(scene, cam, p, d, b, out);
+    return render_host_lens<float>(RTW_WIDE_APERTURE_MAX_RADIUS, scene, cam, 0, nullptr, p, d, b, nullptr, nullptr, out);
 }
 int rtw_render_wide_aperture_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const rtw_denoise_t *d, const rtw_wide_aperture_t *b, double *out) {
-    return render_host_wide_aperture<double>(scene, cam, p, d, b, out);
+    return render_host_lens<double>(RTW_WIDE_APERTURE_MAX_RADIUS, scene, cam, 0, nullptr, p, d, b, nullptr, nullptr, out);
 }
 int rtw_render_lens_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d,
                                        const rtw_wide_aperture_t *b, const double *lens_radii, const double *focus_dists, float *out) {
-    return render_host_wide_aperture_batch<float>(scene, cams, batch_views(n_views), seeds, p, d, b, lens_radii, focus_dists, out);
+    return render_host_lens<float>(RTW_WIDE_APERTURE_MAX_RADIUS, scene, cams, batch_views(n_views), seeds, p, d, b, lens_radii, focus_dists, out);
 }
 int rtw_render_lens_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_denoise_t *d,
                                        const rtw_wide_aperture_t *b, const double *lens_radii, const double *focus_dists, double *out) {
-    return render_host_wide_aperture_batch<double>(scene, cams, batch_views(n_views), seeds, p, d, b, lens_radii, focus_dists, out);
+    return render_host_lens<double>(RTW_WIDE_APERTURE_MAX_RADIUS, scene, cams, batch_views(n_views), seeds, p, d, b, lens_radii, focus_dists, out);
 }
 int rtw_render_path_clamped_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                                  const rtw_temporal_clamp_t *c, const rtw_temporal_noise_t *n, const rtw_denoise_t *d, float *out) {

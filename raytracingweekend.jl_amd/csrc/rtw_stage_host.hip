@@ -2,7 +2,7 @@
 // steps, rtw_velocity_blur_*, rtw_defocus_*, rtw_wide_aperture_*, rtw_lens_batch_*): each is its null checks, the stage's validate_*, a layout of the device buffer, the alias
 // check of its host buffers and ONE call of stage_one_device (rtw_host_ctx.hpp) with the stage's launch.  A leased context's scene is
 // left alone and this thread's last render (rtw_stats) is not touched.  n_views == 0 is the single-frame entry point, n_views != 0 the
-// batched one (rtw_host.hpp batch_views).
+// batched one (rtw_host.hpp batch_views; the lens stages, all three behind lens_host: lens_batch_views).
 #include "rtw_host_ctx.hpp"
 
 namespace rtwh {
@@ -95,50 +95,25 @@ int motion_blur_host(const rtw_velocity_blur_t *b, const CamT *cam, const CamT *
         {off_out, out, img_b});
 }
 
-// The defocus stage (rtw_defocus_*): two H2D (the image, the features), the stage's two launches, ONE D2H.  The device buffer holds the
-// two inputs, the output and the workspace: the denoiser's regions of one frame with this stage's workspace.
+// The lens stages (rtw_defocus_*, rtw_wide_aperture_*: n_views == 0, one view with max_radius in 1..top; rtw_lens_batch_*: n_views views
+// of n_frames -- n_views or 1 -- input frames, top 32).  Two H2D (the images, the features) and, for a batch alone, a third (the lens table,
+// built here), the stage's six launches (two when max_radius <= 8) for any number of views, ONE D2H of all outputs.  The device buffer:
+// rtw_layout.hpp LensBatchLayout -- the inputs, the outputs, the workspaces and, for a batch alone, the table.  `what`: the inputs' words.
 template <typename T, typename CamT>
-int defocus_host(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, const T *image, const T *features, T *out) {
-    if (!b || !cam || !image || !features || !out) return fail(-1, "null argument");
-    if (int rc = validate_defocus(b, cam, width, height)) return rc;
-    const DenoiseLayout R(sizeof(T), width, height, 0, (size_t)rtw_defocus_work_bytes(width, height, (int32_t)sizeof(T)));
-    if (int rc = check_alias({{"out", out, R.img_b}}, {{"image", image, R.img_b}, {"features", features, R.feat_b}})) return rc;
-    return stage_one_device<T>(b->device, nullptr, R.total, "the defocus stage's inputs", {{0, image, R.img_b}, {R.off_feat, features, R.feat_b}},
-        [&](HostCtx *hc, char *base) { return launch_defocus_t(b, cam, width, height, base, base + R.off_feat, base + R.off_work, base + R.off_out, hc->stream); },
-        {R.off_out, out, R.img_b});
-}
-
-// The wide-aperture stage (rtw_wide_aperture_*): two H2D (the image, the features), the stage's six launches (two when max_radius <= 8), ONE
-// D2H.  The device buffer is the defocus stage's with this stage's workspace.
-template <typename T, typename CamT>
-int wide_aperture_host(const rtw_wide_aperture_t *b, const CamT *cam, int32_t width, int32_t height, const T *image, const T *features, T *out) {
-    if (!b || !cam || !image || !features || !out) return fail(-1, "null argument");
-    if (int rc = validate_wide_aperture(b, cam, width, height)) return rc;
-    const DenoiseLayout R(sizeof(T), width, height, 0, WideApertureLayout(width, height, b->max_radius).total * sizeof(T));
-    if (int rc = check_alias({{"out", out, R.img_b}}, {{"image", image, R.img_b}, {"features", features, R.feat_b}})) return rc;
-    return stage_one_device<T>(b->device, nullptr, R.total, "the wide-aperture stage's inputs", {{0, image, R.img_b}, {R.off_feat, features, R.feat_b}},
-        [&](HostCtx *hc, char *base) { return launch_wide_aperture_t(b, cam, width, height, base, base + R.off_feat, base + R.off_work, base + R.off_out, hc->stream); },
-        {R.off_out, out, R.img_b});
-}
-
-// The batched wide-aperture stage (rtw_lens_batch_*): n_views views of n_frames (n_views or 1) input frames.  Three H2D (the images,
-// the features, the lens table built here), the stage's six launches (two when max_radius <= 8) for any number of views, ONE D2H of all
-// outputs.  The device buffer: rtw_layout.hpp LensBatchLayout.
-template <typename T, typename CamT>
-int wide_aperture_batch_host(const rtw_wide_aperture_t *b, const CamT *cams, int32_t n_views, int32_t n_frames, const double *lens_radii, const double *focus_dists, int32_t width,
-                             int32_t height, const T *images, const T *features, T *out) {
+int lens_host(int top, const char *what, const rtw_wide_aperture_t *b, const CamT *cams, int32_t n_views, int32_t n_frames, const double *lens_radii, const double *focus_dists,
+              int32_t width, int32_t height, const T *images, const T *features, T *out) {
     if (!b || !cams || !images || !features || !out) return fail(-1, "null argument");
-    if (int rc = validate_lens_batch_frame(b, n_views, n_frames, width, height, (int)sizeof(T))) return rc;
+    if (n_views) if (int rc = validate_lens_batch_frame(b, n_views, n_frames, width, height, (int)sizeof(T))) return rc;
     std::vector<rtw_defocus_t> lens;
-    if (int rc = validate_lens_batch(b, cams, n_views, width, height, lens_radii, focus_dists, false, &lens)) return rc;
+    if (int rc = validate_lens_batch(b, cams, n_views ? n_views : 1, width, height, lens_radii, focus_dists, false, top, &lens)) return rc;
     const LensBatchLayout R(sizeof(T), width, height, b->max_radius, n_views, n_frames);
-    if (int rc = check_alias({{"out", out, R.out_b}}, {{"images", images, R.img_b}, {"features", features, R.feat_b}})) return rc;
-    std::vector<T> table((size_t)n_views * 32);
-    lens_table_t(lens, cams, width, table.data());
-    return stage_one_device<T>(b->device, nullptr, R.total, "the batched wide-aperture stage's inputs", {{0, images, R.img_b}, {R.off_feat, features, R.feat_b}, {R.off_tab, table.data(), R.tab_b}},
+    if (int rc = check_alias({{"out", out, R.out_b}}, {{n_views ? "images" : "image", images, R.img_b}, {"features", features, R.feat_b}})) return rc;
+    std::vector<T> table;                                      // (a batch's alone: R.tab_b == 0 for one view, and nothing goes up)
+    if (n_views) { table.resize((size_t)n_views * 32); lens_table_t(lens, cams, width, table.data()); }
+    return stage_one_device<T>(b->device, nullptr, R.total, what, {{0, images, R.img_b}, {R.off_feat, features, R.feat_b}, {R.off_tab, table.data(), R.tab_b}},
         [&](HostCtx *hc, char *base) {
-            const LensViews vb = {n_views, base + R.off_tab, (long long)R.img_stride, (long long)R.feat_stride, (long long)R.work_stride, (long long)R.out_stride};
-            return launch_wide_aperture_t(b, (const CamT *)nullptr, width, height, base, base + R.off_feat, base + R.off_work, base + R.off_out, hc->stream, &vb);
+            const LensViews vb = lens_views(R, n_views, base + R.off_tab);
+            return launch_wide_aperture_t(b, cams, width, height, base, base + R.off_feat, base + R.off_work, base + R.off_out, hc->stream, n_views ? &vb : nullptr);
         },
         {R.off_out, out, R.out_b});
 }
@@ -224,24 +199,24 @@ int rtw_velocity_blur_f64(const rtw_velocity_blur_t *b, const rtw_camera_f64 *ca
     return motion_blur_host<double>(b, cam, cam_prev, width, height, image, features, motion, out);
 }
 int rtw_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const float *image, const float *features, float *out) {
-    return defocus_host<float>(b, cam, width, height, image, features, out);
+    return lens_host<float>(RTW_DEFOCUS_MAX_RADIUS, "the defocus stage's inputs", AsWideAperture(b).ptr, cam, 0, 0, nullptr, nullptr, width, height, image, features, out);
 }
 int rtw_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const double *image, const double *features, double *out) {
-    return defocus_host<double>(b, cam, width, height, image, features, out);
+    return lens_host<double>(RTW_DEFOCUS_MAX_RADIUS, "the defocus stage's inputs", AsWideAperture(b).ptr, cam, 0, 0, nullptr, nullptr, width, height, image, features, out);
 }
 int rtw_wide_aperture_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const float *image, const float *features, float *out) {
-    return wide_aperture_host<float>(b, cam, width, height, image, features, out);
+    return lens_host<float>(RTW_WIDE_APERTURE_MAX_RADIUS, "the wide-aperture stage's inputs", b, cam, 0, 0, nullptr, nullptr, width, height, image, features, out);
 }
 int rtw_wide_aperture_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const double *image, const double *features, double *out) {
-    return wide_aperture_host<double>(b, cam, width, height, image, features, out);
+    return lens_host<double>(RTW_WIDE_APERTURE_MAX_RADIUS, "the wide-aperture stage's inputs", b, cam, 0, 0, nullptr, nullptr, width, height, image, features, out);
 }
 int rtw_lens_batch_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cams, int32_t n_views, int32_t n_frames, const double *lens_radii, const double *focus_dists,
                                 int32_t width, int32_t height, const float *images, const float *features, float *out) {
-    return wide_aperture_batch_host<float>(b, cams, n_views, n_frames, lens_radii, focus_dists, width, height, images, features, out);
+    return lens_host<float>(RTW_WIDE_APERTURE_MAX_RADIUS, "the batched wide-aperture stage's inputs", b, cams, lens_batch_views(n_views), n_frames, lens_radii, focus_dists, width, height, images, features, out);
 }
 int rtw_lens_batch_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cams, int32_t n_views, int32_t n_frames, const double *lens_radii, const double *focus_dists,
                                 int32_t width, int32_t height, const double *images, const double *features, double *out) {
-    return wide_aperture_batch_host<double>(b, cams, n_views, n_frames, lens_radii, focus_dists, width, height, images, features, out);
+    return lens_host<double>(RTW_WIDE_APERTURE_MAX_RADIUS, "the batched wide-aperture stage's inputs", b, cams, lens_batch_views(n_views), n_frames, lens_radii, focus_dists, width, height, images, features, out);
 }
 
 }  // extern "C"

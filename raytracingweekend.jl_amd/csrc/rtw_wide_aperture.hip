@@ -1,40 +1,30 @@
-// rtw_wide_aperture.hip -- the wide-aperture stage (include/rtw_hip.h rtw_wide_aperture_*): the checks that need no device, the workspace's
-// layout (rtw_layout.hpp WideApertureLayout), the six launches -- the defocus stage's two kernels as rtw_defocus.hip launches them, at the full
-// and at the reduced size, and the two kernels of rtw_wide_aperture.hpp --, for one view or a batch of views (rtw_lens_batch_*: the
-// lens table, the batch's checks), and the device-resident entry points.
-// (The host-buffer entry points live with the other cached-context paths: rtw_wide_aperture_* in rtw_stage_host.hip,
-// rtw_render_wide_aperture_* in rtw_render_host.hip.)
+// rtw_wide_aperture.hip -- the wide-aperture stage (include/rtw_hip.h rtw_wide_aperture_*) and the lens family's batch: the six launches --
+// the defocus stage's two kernels as rtw_defocus.hip launches them, at the full and at the reduced size, and the two kernels of
+// rtw_wide_aperture.hpp --, for one view or a batch of views; the checks of N views and of a batch's frame (built from validate_lens and
+// its parts in rtw_defocus.hip), the lens table, and lens_device: the ONE device-resident entry point behind rtw_defocus_device_*,
+// rtw_wide_aperture_device_* and rtw_lens_batch_device_*.  Byte arithmetic: rtw_layout.hpp WideApertureLayout, LensBatchLayout.
+// (The host-buffer entry points live with the other cached-context paths: lens_host in rtw_stage_host.hip, render_host_lens in
+// rtw_render_host.hip.)
 #include "rtw_host.hpp"
-#include "rtw_layout.hpp"
 #include "rtw_wide_aperture.hpp"
 
 namespace rtwh {
 
-static_assert(sizeof(rtw_wide_aperture_t) == sizeof(rtw_defocus_t) && sizeof(rtw_wide_aperture_t) == 40, "the two stages' parameters have the same fields");
 static_assert(rtw::WA_MAX_RADIUS == RTW_WIDE_APERTURE_MAX_RADIUS, "the header's bound");
 
-// the stage's parameters as the defocus stage's (the same fields in the same order)
+// the stage's parameters as the defocus stage's (the same fields in the same order: rtw_host.hpp AsWideAperture is the way back)
 static rtw_defocus_t as_defocus(const rtw_wide_aperture_t *b) {
     rtw_defocus_t d;
     memcpy(&d, b, sizeof d);
     return d;
 }
 
-template <typename CamT>
-static int validate_t(const rtw_wide_aperture_t *b, const CamT *cam, int32_t width, int32_t height) {
-    if (!b || !cam) return fail(-1, "null wide-aperture parameters or camera");
-    const rtw_defocus_t d = as_defocus(b);
-    return validate_defocus_top(&d, cam, width, height, RTW_WIDE_APERTURE_MAX_RADIUS);
-}
-int validate_wide_aperture(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height) { return validate_t(b, cam, width, height); }
-int validate_wide_aperture(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height) { return validate_t(b, cam, width, height); }
-
 static int prepare_t(const rtw_defocus_t *b, int rm, const rtw_camera_f32 *c, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st, int32_t nv, const void *tab, const long long *sb) { return launch_defocus_prepare_f32(b, rm, c, w, h, img, feat, coc, tile, st, nv, tab, sb); }
 static int prepare_t(const rtw_defocus_t *b, int rm, const rtw_camera_f64 *c, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st, int32_t nv, const void *tab, const long long *sb) { return launch_defocus_prepare_f64(b, rm, c, w, h, img, feat, coc, tile, st, nv, tab, sb); }
 static int gather_t(float, int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st, int32_t nv, const long long *sb) { return launch_defocus_gather_f32(w, h, mmax, gamma, img, coc, tile, out, st, nv, sb); }
 static int gather_t(double, int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st, int32_t nv, const long long *sb) { return launch_defocus_gather_f64(w, h, mmax, gamma, img, coc, tile, out, st, nv, sb); }
 
-// Enqueue the stage on `stream` of the current device (validate_wide_aperture has accepted the call): SIX launches, no record.
+// Enqueue the stage on `stream` of the current device (validate_lens has accepted the call): SIX launches, no record.
 // vb null: one view.  vb given: vb->n_views views in the same six launches -- cam and d's lens are unused (the table); every region of the
 // workspace lies at the single stage's offset inside its view's workspace, so one stride serves all of them.
 template <typename T, int S, typename CamT>
@@ -118,63 +108,62 @@ static int check_views_size(int32_t width, int32_t height, int32_t n_views) {
 
 template <typename CamT>
 static int validate_lens_batch_t(const rtw_wide_aperture_t *b, const CamT *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens,
-                                 std::vector<rtw_defocus_t> *lens_out) {
-    if (!b || !cams) return fail(-1, "null wide-aperture parameters or cameras");
+                                 int top, std::vector<rtw_defocus_t> *lens_out) {
+    if (!b || !cams) return fail(-1, "null lens parameters or cameras");
     if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
     if (lens_out) lens_out->clear();
     for (int32_t v = 0; v < n_views; ++v) {
-        rtw_wide_aperture_t bv = *b;
+        rtw_defocus_t bv = as_defocus(b);
         if (lens_radii) bv.lens_radius = lens_radii[v];
         if (focus_dists) bv.focus_dist = focus_dists[v];
-        if (own_lens && bv.lens_radius == -1) bv.lens_radius = (double)cams[v].lens_radius;       // (the one-call form alone: the camera's own aperture)
-        if (int rc = validate_wide_aperture(&bv, cams + v, width, height)) {
+        if (own_lens && bv.lens_radius == -1) bv.lens_radius = (double)cams[v].lens_radius;       // (the one-call forms alone, here and only here: the camera's own aperture)
+        if (int rc = validate_lens(&bv, cams + v, width, height, top)) {
             if (n_views > 1 || lens_radii || focus_dists) {
                 const std::string why = g_err;
                 return fail(rc, "view %d: %s", v, why.c_str());
             }
             return rc;
         }
-        if (lens_out) lens_out->push_back(as_defocus(&bv));
+        if (lens_out) lens_out->push_back(bv);
     }
     return check_views_size(width, height, n_views);
 }
-int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, std::vector<rtw_defocus_t> *lens_out) { return validate_lens_batch_t(b, cams, n_views, width, height, lens_radii, focus_dists, own_lens, lens_out); }
-int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, std::vector<rtw_defocus_t> *lens_out) { return validate_lens_batch_t(b, cams, n_views, width, height, lens_radii, focus_dists, own_lens, lens_out); }
+int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, int top, std::vector<rtw_defocus_t> *lens_out) { return validate_lens_batch_t(b, cams, n_views, width, height, lens_radii, focus_dists, own_lens, top, lens_out); }
+int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, int top, std::vector<rtw_defocus_t> *lens_out) { return validate_lens_batch_t(b, cams, n_views, width, height, lens_radii, focus_dists, own_lens, top, lens_out); }
 void lens_table_f32(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f32 *cams, int32_t width, float *table) { for (size_t v = 0; v < lens.size(); ++v) lens_table_entry_f32(&lens[v], cams + v, width, table + 32 * v); }
 void lens_table_f64(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f64 *cams, int32_t width, double *table) { for (size_t v = 0; v < lens.size(); ++v) lens_table_entry_f64(&lens[v], cams + v, width, table + 32 * v); }
 
-// What the batched device entry point checks of its count and frame: it has no camera and reads no lens, so of validate_defocus's checks
-// those on max_radius, flags, gamma, device, reserved and the frame remain, with its codes.
+// What a batched entry point checks of its counts and frame before it looks at a view.  The device form stops here: it has no camera and
+// reads no lens, so of validate_lens's four parts the parameters and the frame remain, with their codes.
 int validate_lens_batch_frame(const rtw_wide_aperture_t *b, int32_t n_views, int32_t n_frames, int32_t width, int32_t height, int elem_bytes) {
-    if (!b) return fail(-1, "null wide-aperture parameters");
-    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
+    if (!b) return fail(-1, "null lens parameters");
+    if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views == LENS_NO_VIEWS ? 0 : n_views);     // (lens_batch_views: the caller's 0)
     if (n_frames != 1 && n_frames != n_views) return fail(-2, "n_frames must be 1 (every view reads one frame) or n_views (got %d for %d views)", n_frames, n_views);
-    if (b->max_radius < 1 || b->max_radius > RTW_WIDE_APERTURE_MAX_RADIUS) return fail(-2, "max_radius must be in 1..%d (got %d)", RTW_WIDE_APERTURE_MAX_RADIUS, b->max_radius);
-    if (b->flags != 0) return fail(-2, "unknown defocus flags 0x%x", b->flags);
-    if (b->gamma != 0 && b->gamma != 1) return fail(-2, "gamma must be 0 or 1 (got %d)", b->gamma);
-    if (b->device < -1) return fail(-2, "bad device %d", b->device);
-    if (b->reserved[0] != 0 || b->reserved[1] != 0) return fail(-2, "reserved must be 0");
-    if (width < 1 || height < 1) return fail(-2, "width/height must be positive (got %d x %d)", width, height);
-    if (const int64_t rc = rtw_denoise_work_bytes(width, height, elem_bytes); rc < 0) return (int)rc;         // (elem_bytes; the denoiser's frame rule)
+    const rtw_defocus_t d = as_defocus(b);
+    if (int rc = check_lens_params(&d, RTW_WIDE_APERTURE_MAX_RADIUS)) return rc;
+    if (int rc = check_lens_frame(width, height, elem_bytes)) return rc;
     return check_views_size(width, height, n_views);
 }
 
-// The device-resident entry point of the batch: nulls, the count and the frame, then the pointers' alignment and aliasing over the extents
-// of the whole batch (the inputs counted once when n_frames == 1).
-template <typename T>
-static int wide_aperture_batch_device(const rtw_wide_aperture_t *b, int32_t n_views, int32_t n_frames, const void *d_table, int32_t width, int32_t height, const void *d_images,
-                                      const void *d_features, void *d_work, void *d_out, void *stream_v) {
-    if (!b || !d_table || !d_images || !d_features || !d_work || !d_out) return fail(-1, "null argument");
-    if (int rc = validate_lens_batch_frame(b, n_views, n_frames, width, height, (int)sizeof(T))) return rc;
-    if (((uintptr_t)d_table & 15u) || ((uintptr_t)d_features & 15u) || ((uintptr_t)d_work & 15u)) return fail(-2, "the table, the feature buffer and the workspace must be 16-byte aligned");
-    if (((uintptr_t)d_images & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
+// The device-resident entry point of the family (rtw_defocus_device_*, rtw_wide_aperture_device_*: n_views == 0, one view of `cam` with
+// max_radius in 1..top and no table; rtw_lens_batch_device_*: n_views views, their lenses in d_table, no camera): nulls, the
+// parameters -- a batch's counts and frame --, then the pointers' alignment and their aliasing over the extents of the whole call (a batch's
+// inputs counted once when n_frames == 1), then the launches.
+template <typename T, typename CamT>
+static int lens_device(int top, const rtw_wide_aperture_t *b, const CamT *cam, int32_t n_views, int32_t n_frames, const void *d_table, int32_t width, int32_t height, const void *d_image,
+                       const void *d_features, void *d_work, void *d_out, void *stream_v) {
+    if (!b || (n_views ? !d_table : !cam) || !d_image || !d_features || !d_work || !d_out) return fail(-1, "null argument");
+    if (int rc = n_views ? validate_lens_batch_frame(b, n_views, n_frames, width, height, (int)sizeof(T)) : validate_lens_batch(b, cam, 1, width, height, nullptr, nullptr, false, top, nullptr)) return rc;
+    if (((uintptr_t)d_table & 15u) || ((uintptr_t)d_features & 15u) || ((uintptr_t)d_work & 15u))
+        return fail(-2, "%s must be 16-byte aligned", n_views ? "the table, the feature buffer and the workspace" : "the feature buffer and the workspace");
+    if (((uintptr_t)d_image & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
     const LensBatchLayout R(sizeof(T), width, height, b->max_radius, n_views, n_frames);
-    if (int rc = check_alias({{"d_out", d_out, R.out_b}, {"d_work", d_work, R.work_b}}, {{"d_images", d_images, R.img_b}, {"d_features", d_features, R.feat_b}, {"d_table", d_table, R.tab_b}})) return rc;
+    if (int rc = check_alias({{"d_out", d_out, R.out_b}, {"d_work", d_work, R.work_b}},
+                             {{n_views ? "d_images" : "d_image", d_image, R.img_b}, {"d_features", d_features, R.feat_b}, {"d_table", d_table, R.tab_b}})) return rc;
     DeviceGuard guard;
     if (b->device >= 0) HIP_TRY(hipSetDevice(b->device));
-    const LensViews vb = {n_views, d_table, (long long)R.img_stride, (long long)R.feat_stride, (long long)R.work_stride, (long long)R.out_stride};
-    using CamT = std::conditional_t<sizeof(T) == 8, rtw_camera_f64, rtw_camera_f32>;
-    return launch_wide_aperture<T, CamT>(b, nullptr, width, height, d_images, d_features, d_work, d_out, (hipStream_t)stream_v, &vb);
+    const LensViews vb = lens_views(R, n_views, d_table);
+    return launch_wide_aperture<T>(b, cam, width, height, d_image, d_features, d_work, d_out, (hipStream_t)stream_v, n_views ? &vb : nullptr);
 }
 
 // rtw_lens_table_*: pure host code
@@ -182,24 +171,9 @@ template <typename T, typename CamT>
 static int lens_table_host(const rtw_wide_aperture_t *b, const CamT *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, void *table) {
     if (!b || !cams || !table) return fail(-1, "null argument");
     std::vector<rtw_defocus_t> lens;
-    if (int rc = validate_lens_batch(b, cams, n_views, width, height, lens_radii, focus_dists, false, &lens)) return rc;
+    if (int rc = validate_lens_batch(b, cams, n_views, width, height, lens_radii, focus_dists, false, RTW_WIDE_APERTURE_MAX_RADIUS, &lens)) return rc;
     lens_table_t(lens, cams, width, (T *)table);
     return 0;
-}
-
-// The device-resident entry point: nulls, the parameters, then the pointers' alignment and aliasing.
-template <typename T, typename CamT>
-static int wide_aperture_device(const rtw_wide_aperture_t *b, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, void *stream_v) {
-    if (!b || !cam || !d_image || !d_features || !d_work || !d_out) return fail(-1, "null argument");
-    if (int rc = validate_wide_aperture(b, cam, width, height)) return rc;
-    if (((uintptr_t)d_features & 15u) || ((uintptr_t)d_work & 15u)) return fail(-2, "the feature buffer and the workspace must be 16-byte aligned");
-    if (((uintptr_t)d_image & (sizeof(T) - 1)) || ((uintptr_t)d_out & (sizeof(T) - 1))) return fail(-2, "the image buffers must be aligned to their element type");
-    const size_t n_pix = (size_t)width * (size_t)height;
-    const size_t img_b = n_pix * 3 * sizeof(T), feat_b = n_pix * 8 * sizeof(T), work_b = WideApertureLayout(width, height, b->max_radius).total * sizeof(T);
-    if (int rc = check_alias({{"d_out", d_out, img_b}, {"d_work", d_work, work_b}}, {{"d_image", d_image, img_b}, {"d_features", d_features, feat_b}})) return rc;
-    DeviceGuard guard;
-    if (b->device >= 0) HIP_TRY(hipSetDevice(b->device));
-    return launch_wide_aperture<T>(b, cam, width, height, d_image, d_features, d_work, d_out, (hipStream_t)stream_v, nullptr);
 }
 
 }  // namespace rtwh
@@ -213,13 +187,21 @@ int64_t rtw_wide_aperture_work_bytes(int32_t width, int32_t height, int32_t elem
     if (max_radius < 1 || max_radius > RTW_WIDE_APERTURE_MAX_RADIUS) return fail(-2, "max_radius must be in 1..%d (got %d)", RTW_WIDE_APERTURE_MAX_RADIUS, max_radius);
     return (int64_t)(WideApertureLayout(width, height, max_radius).total * (size_t)elem_bytes);
 }
+int rtw_defocus_device_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out,
+                           void *hip_stream) {
+    return lens_device<float>(RTW_DEFOCUS_MAX_RADIUS, AsWideAperture(b).ptr, cam, 0, 0, nullptr, width, height, d_image, d_features, d_work, d_out, hip_stream);
+}
+int rtw_defocus_device_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out,
+                           void *hip_stream) {
+    return lens_device<double>(RTW_DEFOCUS_MAX_RADIUS, AsWideAperture(b).ptr, cam, 0, 0, nullptr, width, height, d_image, d_features, d_work, d_out, hip_stream);
+}
 int rtw_wide_aperture_device_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work,
                                  void *d_out, void *hip_stream) {
-    return wide_aperture_device<float>(b, cam, width, height, d_image, d_features, d_work, d_out, hip_stream);
+    return lens_device<float>(RTW_WIDE_APERTURE_MAX_RADIUS, b, cam, 0, 0, nullptr, width, height, d_image, d_features, d_work, d_out, hip_stream);
 }
 int rtw_wide_aperture_device_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work,
                                  void *d_out, void *hip_stream) {
-    return wide_aperture_device<double>(b, cam, width, height, d_image, d_features, d_work, d_out, hip_stream);
+    return lens_device<double>(RTW_WIDE_APERTURE_MAX_RADIUS, b, cam, 0, 0, nullptr, width, height, d_image, d_features, d_work, d_out, hip_stream);
 }
 
 int64_t rtw_lens_table_bytes(int32_t n_views, int32_t elem_bytes) {
@@ -242,11 +224,11 @@ int64_t rtw_lens_batch_work_bytes(int32_t width, int32_t height, int32_t elem_by
 }
 int rtw_lens_batch_device_f32(const rtw_wide_aperture_t *b, int32_t n_views, int32_t n_frames, const void *d_table, int32_t width, int32_t height, const void *d_images,
                                        const void *d_features, void *d_work, void *d_out, void *hip_stream) {
-    return wide_aperture_batch_device<float>(b, n_views, n_frames, d_table, width, height, d_images, d_features, d_work, d_out, hip_stream);
+    return lens_device<float>(RTW_WIDE_APERTURE_MAX_RADIUS, b, (const rtw_camera_f32 *)nullptr, lens_batch_views(n_views), n_frames, d_table, width, height, d_images, d_features, d_work, d_out, hip_stream);
 }
 int rtw_lens_batch_device_f64(const rtw_wide_aperture_t *b, int32_t n_views, int32_t n_frames, const void *d_table, int32_t width, int32_t height, const void *d_images,
                                        const void *d_features, void *d_work, void *d_out, void *hip_stream) {
-    return wide_aperture_batch_device<double>(b, n_views, n_frames, d_table, width, height, d_images, d_features, d_work, d_out, hip_stream);
+    return lens_device<double>(RTW_WIDE_APERTURE_MAX_RADIUS, b, (const rtw_camera_f64 *)nullptr, lens_batch_views(n_views), n_frames, d_table, width, height, d_images, d_features, d_work, d_out, hip_stream);
 }
 
 }  // extern "C"

@@ -14,7 +14,7 @@ import numpy as np
 
 from . import _capi
 from .denoise import make_denoise
-from .render import _frame_height, _record_stats
+from .render import _batch_cameras, _frame_height, _record_stats
 from .structs import Camera, flatten_scene
 
 _DEFOCUS_KEYS = ("lens_radius", "focus_dist", "max_radius")
@@ -46,38 +46,112 @@ def _camera_arg(cam, T, what):
     return _capi.make_camera(cam, T)
 
 
-def defocus(image, features, cam, **params):
-    """The stage on host arrays (rtw_defocus_*): ``image`` [H, W, 3] (linear, rendered through the pinhole) and ``features`` [H, W, 8] -- or
-    the dict ``render_features`` returns -- of the frame seen through ``cam``, whose own ``lens_radius`` is not read: the aperture is the
-    keyword.  -> the defocused image [H, W, 3]; a pixel that is not valid is NaN.  Keywords: ``make_defocus``.  Blocking."""
+# ---- what the lens stages share (this module, wide_aperture.py): the array checks, the device-resident call, the one-call body --------
+
+def _entry(name, T):
+    return getattr(_capi.lib(), name + ("f64" if _capi.is_f64(T) else "f32"))
+
+
+def _host_arrays(image, features, batch=False):
+    """the checks of a lens stage's host arrays -- ``image`` [H, W, 3] and ``features`` [H, W, 8] (or the dict a feature pass returns); ``batch``:
+    [N, H, W, 3] and [N, H, W, 8] -- and their transposition -> (dtype, image, features) in the library's layout: pixel (i, j) (of view v) at
+    (v*W*H +) j*H + i"""
     if isinstance(features, dict):
         features = features["raw"]
     image, features = np.asarray(image), np.asarray(features)
     T = image.dtype
+    name, lead = ("images", "N, ") if batch else ("image", "")
     if T not in (np.dtype(np.float32), np.dtype(np.float64)) or features.dtype != T:
-        raise TypeError("image and features must both be float32 or both float64")
-    if image.ndim != 3 or image.shape[-1] != 3 or features.shape != image.shape[:-1] + (8,):
-        raise ValueError(f"expected image [H, W, 3] and features [H, W, 8], got {image.shape} and {features.shape}")
+        raise TypeError(f"{name} and features must both be float32 or both float64")
+    if image.ndim != (4 if batch else 3) or image.shape[-1] != 3 or features.shape != image.shape[:-1] + (8,):
+        raise ValueError(f"expected {name} [{lead}H, W, 3] and features [{lead}H, W, 8], got {image.shape} and {features.shape}")
     if 0 in image.shape:
-        raise ValueError("empty image")
-    H, W = image.shape[:2]
+        raise ValueError(f"empty {name}")
+    return (T,) + tuple(np.ascontiguousarray(np.swapaxes(a, -3, -2)) for a in (image, features))
+
+
+def _lens_arrays(lens_radii, focus_dists, n):
+    """per-view arrays (None: the keyword for every view) -> two ctypes arrays of n doubles, or None"""
+    out = []
+    for name, a in (("lens_radii", lens_radii), ("focus_dists", focus_dists)):
+        if a is None:
+            out.append(None)
+            continue
+        a = [float(x) for x in a]
+        if len(a) != n:
+            raise ValueError(f"{len(a)} {name} for {n} views")
+        out.append((C.c_double * n)(*a))
+    return out
+
+
+def _stage_host(entry, make, image, features, cam, params):
+    """one view on host arrays through ``entry`` (rtw_defocus_ / rtw_wide_aperture_) with the parameters ``make(**params)``"""
+    T, img, feat = _host_arrays(image, features)
+    W, H = img.shape[:2]
     Cm = _camera_arg(cam, T.type, "cam")
-    img, feat = (np.ascontiguousarray(np.swapaxes(a, 0, 1)) for a in (image, features))      # the library's layout: pixel (i, j) at j*H + i
     out = np.empty((W, H, 3), dtype=T)
-    fn = getattr(_capi.lib(), "rtw_defocus_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(make_defocus(**params)), C.byref(Cm), W, H, *(a.ctypes.data_as(C.c_void_p) for a in (img, feat, out))))
+    _capi.check(_entry(entry, T)(C.byref(make(**params)), C.byref(Cm), W, H, *(a.ctypes.data_as(C.c_void_p) for a in (img, feat, out))))
     return np.swapaxes(out, 0, 1)
+
+
+def _stage_into(entry, make, d_out_ptr, d_work_ptr, d_image_ptr, d_features_ptr, cam, image_width, image_height, elem_type, stream, params):
+    """one view on device pointers through ``entry`` (rtw_defocus_device_ / rtw_wide_aperture_device_)"""
+    T = np.dtype(elem_type).type
+    Cm = _camera_arg(cam, T, "cam")
+    _capi.check(_entry(entry, T)(C.byref(make(**params)), C.byref(Cm), int(image_width), int(image_height),
+                                 *(C.c_void_p(int(q)) for q in (d_image_ptr, d_features_ptr, d_work_ptr, d_out_ptr)), C.c_void_p(int(stream))))
+
+
+def _render_lens(entry, make, word, stage, scene, cams, image_width, n_samples, depth, seed, n_chunks, device, gamma, denoise, batch=None):
+    """the one-call body through ``entry`` (rtw_render_defocused_ / rtw_render_wide_aperture_ / rtw_render_lens_batch_): the checks of the
+    ``denoise`` and the stage's keywords (``stage``: the dict, ``word``: its name in messages), scene, params, call, stats, reshape.
+    ``batch``: None -- ``cams`` is ONE Camera, -> img[i, j, :]; (seeds, lens_radii, focus_dists) -- N cameras, -> img[v, i, j, :]"""
+    if batch is None:
+        if not isinstance(cams, Camera):
+            raise TypeError("cam must be a Camera")
+        T = cams.elem_type
+    else:
+        cams, T = _batch_cameras(cams)
+    n = 1 if batch is None else len(cams)
+    dk = {} if denoise in (None, False, True) else dict(denoise)
+    if set(dk) - set(_DENOISE_KEYS):
+        raise ValueError(f"denoise takes the keywords {_DENOISE_KEYS}, got {sorted(set(dk) - set(_DENOISE_KEYS))}")
+    bk = {} if stage is None else dict(stage)
+    if set(bk) - set(_DEFOCUS_KEYS):
+        raise ValueError(f"{word} takes the keywords {_DEFOCUS_KEYS}, got {sorted(set(bk) - set(_DEFOCUS_KEYS))}")
+    bk.setdefault("lens_radius", -1.0)                       # (the one-call forms alone: the camera's own)
+    if batch is None:
+        views, lenses = (C.byref(_capi.make_camera(cams, T)),), ()
+    else:
+        lenses = tuple(_lens_arrays(batch[1], batch[2], n))
+        views = (_capi.make_cameras(cams, T), n, _capi.make_seeds(seed if batch[0] is None else batch[0], n))
+    height = _frame_height(image_width, n_samples)
+    L = _capi.lib()
+    flat = scene if isinstance(scene, dict) else flatten_scene(scene, T)
+    S, keep = _capi.make_scene(flat, T)
+    P = _capi.make_params(image_width, height, n_samples, depth, seed, n_chunks, 0, 1, device, 1 if gamma else 0, 0)
+    D = make_denoise(gamma=gamma, **dk) if denoise else None
+    B = make(gamma=gamma, **bk)
+    out = np.empty(n * height * int(image_width) * 3, dtype=T)
+    _capi.check(_entry(entry, T)(C.byref(S), *views, C.byref(P), C.byref(D) if D is not None else None, C.byref(B), *lenses, out.ctypes.data_as(C.c_void_p)))
+    del keep
+    _record_stats(L)
+    img = out.reshape(n, int(image_width), height, 3).transpose(0, 2, 1, 3)
+    return img[0] if batch is None else img
+
+
+def defocus(image, features, cam, **params):
+    """The stage on host arrays (rtw_defocus_*): ``image`` [H, W, 3] (linear, rendered through the pinhole) and ``features`` [H, W, 8] -- or
+    the dict ``render_features`` returns -- of the frame seen through ``cam``, whose own ``lens_radius`` is not read: the aperture is the
+    keyword.  -> the defocused image [H, W, 3]; a pixel that is not valid is NaN.  Keywords: ``make_defocus``.  Blocking."""
+    return _stage_host("rtw_defocus_", make_defocus, image, features, cam, params)
 
 
 def defocus_into(d_out_ptr, d_work_ptr, d_image_ptr, d_features_ptr, cam, image_width, image_height, *, elem_type=np.float32, stream=0, **params):
     """The device-resident stage (rtw_defocus_device_*): two launches on ``stream``.  DEVICE pointers in the library's layout (pixel (i, j) at
     slot ``j*H + i``): the linear image and the features; ``d_work_ptr``: ``defocus_work_bytes`` bytes, 16-byte aligned, which afterwards hold
     the CoC plane and the tile plane; ``d_out_ptr`` aliases nothing.  Keywords: ``make_defocus``."""
-    T = np.dtype(elem_type).type
-    Cm = _camera_arg(cam, T, "cam")
-    fn = getattr(_capi.lib(), "rtw_defocus_device_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(make_defocus(**params)), C.byref(Cm), int(image_width), int(image_height),
-                   *(C.c_void_p(int(q)) for q in (d_image_ptr, d_features_ptr, d_work_ptr, d_out_ptr)), C.c_void_p(int(stream))))
+    _stage_into("rtw_defocus_device_", make_defocus, d_out_ptr, d_work_ptr, d_image_ptr, d_features_ptr, cam, image_width, image_height, elem_type, stream, params)
 
 
 def render_defocused(scene, cam, image_width=400, n_samples=1, *, depth=16, seed=1, n_chunks=0, device=-1, gamma=True, denoise=None, defocus=None):
@@ -87,26 +161,4 @@ def render_defocused(scene, cam, image_width=400, n_samples=1, *, depth=16, seed
     defocus stage ends the chain; ``defocus``: None, or a dict of ``make_defocus``'s keywords ``lens_radius`` (default: the camera's own),
     ``focus_dist``, ``max_radius``.  Returns ``img[i, j, :]`` -- on the bits the chain of the single calls on the pinhole copy followed by
     ``defocus``; ``last_stats()`` reports the render."""
-    if not isinstance(cam, Camera):
-        raise TypeError("cam must be a Camera")
-    T = cam.elem_type
-    dk = {} if denoise in (None, False, True) else dict(denoise)
-    if set(dk) - set(_DENOISE_KEYS):
-        raise ValueError(f"denoise takes the keywords {_DENOISE_KEYS}, got {sorted(set(dk) - set(_DENOISE_KEYS))}")
-    bk = {} if defocus is None else dict(defocus)
-    if set(bk) - set(_DEFOCUS_KEYS):
-        raise ValueError(f"defocus takes the keywords {_DEFOCUS_KEYS}, got {sorted(set(bk) - set(_DEFOCUS_KEYS))}")
-    bk.setdefault("lens_radius", -1.0)                       # (the one-call form alone: the camera's own)
-    height = _frame_height(image_width, n_samples)
-    L = _capi.lib()
-    flat = scene if isinstance(scene, dict) else flatten_scene(scene, T)
-    S, keep = _capi.make_scene(flat, T)
-    P = _capi.make_params(image_width, height, n_samples, depth, seed, n_chunks, 0, 1, device, 1 if gamma else 0, 0)
-    D = make_denoise(gamma=gamma, **dk) if denoise else None
-    B = make_defocus(gamma=gamma, **bk)
-    out = np.empty(height * int(image_width) * 3, dtype=T)
-    fn = getattr(L, "rtw_render_defocused_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(S), C.byref(_capi.make_camera(cam, T)), C.byref(P), C.byref(D) if D is not None else None, C.byref(B), out.ctypes.data_as(C.c_void_p)))
-    del keep
-    _record_stats(L)
-    return out.reshape(int(image_width), height, 3).transpose(1, 0, 2)
+    return _render_lens("rtw_render_defocused_", make_defocus, "defocus", defocus, scene, cam, image_width, n_samples, depth, seed, n_chunks, device, gamma, denoise)

@@ -15,12 +15,8 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from .defocus import _DENOISE_KEYS, _camera_arg
-from .denoise import make_denoise
-from .render import _batch_cameras, _frame_height, _record_stats
-from .structs import Camera, flatten_scene
-
-_STAGE_KEYS = ("lens_radius", "focus_dist", "max_radius")
+from .defocus import _entry, _host_arrays, _lens_arrays, _render_lens, _stage_host, _stage_into
+from .render import _batch_cameras
 
 
 def make_wide_aperture(lens_radius, focus_dist=0.0, max_radius=32, gamma=True, device=-1):
@@ -40,23 +36,7 @@ def wide_aperture(image, features, cam, **params):
     """The stage on host arrays (rtw_wide_aperture_*): ``image`` [H, W, 3] (linear, rendered through the pinhole) and ``features`` [H, W, 8]
     -- or the dict ``render_features`` returns -- of the frame seen through ``cam``, whose own ``lens_radius`` is not read: the aperture is
     the keyword.  -> the image [H, W, 3]; a pixel that is not valid is NaN.  Keywords: ``make_wide_aperture``.  Blocking."""
-    if isinstance(features, dict):
-        features = features["raw"]
-    image, features = np.asarray(image), np.asarray(features)
-    T = image.dtype
-    if T not in (np.dtype(np.float32), np.dtype(np.float64)) or features.dtype != T:
-        raise TypeError("image and features must both be float32 or both float64")
-    if image.ndim != 3 or image.shape[-1] != 3 or features.shape != image.shape[:-1] + (8,):
-        raise ValueError(f"expected image [H, W, 3] and features [H, W, 8], got {image.shape} and {features.shape}")
-    if 0 in image.shape:
-        raise ValueError("empty image")
-    H, W = image.shape[:2]
-    Cm = _camera_arg(cam, T.type, "cam")
-    img, feat = (np.ascontiguousarray(np.swapaxes(a, 0, 1)) for a in (image, features))      # the library's layout: pixel (i, j) at j*H + i
-    out = np.empty((W, H, 3), dtype=T)
-    fn = getattr(_capi.lib(), "rtw_wide_aperture_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(make_wide_aperture(**params)), C.byref(Cm), W, H, *(a.ctypes.data_as(C.c_void_p) for a in (img, feat, out))))
-    return np.swapaxes(out, 0, 1)
+    return _stage_host("rtw_wide_aperture_", make_wide_aperture, image, features, cam, params)
 
 
 def wide_aperture_into(d_out_ptr, d_work_ptr, d_image_ptr, d_features_ptr, cam, image_width, image_height, *, elem_type=np.float32, stream=0, **params):
@@ -64,11 +44,7 @@ def wide_aperture_into(d_out_ptr, d_work_ptr, d_image_ptr, d_features_ptr, cam, 
     the library's layout (pixel (i, j) at slot ``j*H + i``): the linear image and the features; ``d_work_ptr``: ``wide_aperture_work_bytes``
     bytes for the same ``max_radius``, 16-byte aligned, which afterwards hold the regions the header lists; ``d_out_ptr`` aliases nothing.
     Keywords: ``make_wide_aperture``."""
-    T = np.dtype(elem_type).type
-    Cm = _camera_arg(cam, T, "cam")
-    fn = getattr(_capi.lib(), "rtw_wide_aperture_device_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(make_wide_aperture(**params)), C.byref(Cm), int(image_width), int(image_height),
-                   *(C.c_void_p(int(q)) for q in (d_image_ptr, d_features_ptr, d_work_ptr, d_out_ptr)), C.c_void_p(int(stream))))
+    _stage_into("rtw_wide_aperture_device_", make_wide_aperture, d_out_ptr, d_work_ptr, d_image_ptr, d_features_ptr, cam, image_width, image_height, elem_type, stream, params)
 
 
 def render_wide_aperture(scene, cam, image_width=400, n_samples=1, *, depth=16, seed=1, n_chunks=0, device=-1, gamma=True, denoise=None, wide_aperture=None):
@@ -76,46 +52,10 @@ def render_wide_aperture(scene, cam, image_width=400, n_samples=1, *, depth=16, 
     with this stage at the end of the chain.  ``wide_aperture``: None, or a dict of ``make_wide_aperture``'s keywords ``lens_radius``
     (default: the camera's own), ``focus_dist``, ``max_radius``.  Returns ``img[i, j, :]`` -- on the bits the chain of the single calls on the
     pinhole copy followed by ``wide_aperture``; ``last_stats()`` reports the render."""
-    if not isinstance(cam, Camera):
-        raise TypeError("cam must be a Camera")
-    T = cam.elem_type
-    dk = {} if denoise in (None, False, True) else dict(denoise)
-    if set(dk) - set(_DENOISE_KEYS):
-        raise ValueError(f"denoise takes the keywords {_DENOISE_KEYS}, got {sorted(set(dk) - set(_DENOISE_KEYS))}")
-    bk = {} if wide_aperture is None else dict(wide_aperture)
-    if set(bk) - set(_STAGE_KEYS):
-        raise ValueError(f"wide_aperture takes the keywords {_STAGE_KEYS}, got {sorted(set(bk) - set(_STAGE_KEYS))}")
-    bk.setdefault("lens_radius", -1.0)                       # (the one-call form alone: the camera's own)
-    height = _frame_height(image_width, n_samples)
-    L = _capi.lib()
-    flat = scene if isinstance(scene, dict) else flatten_scene(scene, T)
-    S, keep = _capi.make_scene(flat, T)
-    P = _capi.make_params(image_width, height, n_samples, depth, seed, n_chunks, 0, 1, device, 1 if gamma else 0, 0)
-    D = make_denoise(gamma=gamma, **dk) if denoise else None
-    B = make_wide_aperture(gamma=gamma, **bk)
-    out = np.empty(height * int(image_width) * 3, dtype=T)
-    fn = getattr(L, "rtw_render_wide_aperture_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(S), C.byref(_capi.make_camera(cam, T)), C.byref(P), C.byref(D) if D is not None else None, C.byref(B), out.ctypes.data_as(C.c_void_p)))
-    del keep
-    _record_stats(L)
-    return out.reshape(int(image_width), height, 3).transpose(1, 0, 2)
+    return _render_lens("rtw_render_wide_aperture_", make_wide_aperture, "wide_aperture", wide_aperture, scene, cam, image_width, n_samples, depth, seed, n_chunks, device, gamma, denoise)
 
 
 # ---- batched views and brackets (include/rtw_hip.h rtw_lens_batch_*): N views, or one frame under N lenses, in each launch ----------
-
-def _lens_arrays(lens_radii, focus_dists, n):
-    """per-view arrays (None: the keyword for every view) -> two ctypes arrays of n doubles, or None"""
-    out = []
-    for name, a in (("lens_radii", lens_radii), ("focus_dists", focus_dists)):
-        if a is None:
-            out.append(None)
-            continue
-        a = [float(x) for x in a]
-        if len(a) != n:
-            raise ValueError(f"{len(a)} {name} for {n} views")
-        out.append((C.c_double * n)(*a))
-    return out
-
 
 def lens_table(cams, image_width, image_height, *, lens_radii=None, focus_dists=None, **params):
     """The HOST table of a batch's lenses (rtw_lens_table_*): [N, 32] elements of the cameras' type, row ``v`` the constants of ``cams[v]`` with
@@ -126,7 +66,7 @@ def lens_table(cams, image_width, image_height, *, lens_radii=None, focus_dists=
     lr, fd = _lens_arrays(lens_radii, focus_dists, n)
     params.setdefault("lens_radius", 0.0)
     table = np.zeros((n, 32), dtype=T)
-    fn = getattr(_capi.lib(), "rtw_lens_table_" + ("f64" if _capi.is_f64(T) else "f32"))
+    fn = _entry("rtw_lens_table_", T)
     _capi.check(fn(C.byref(make_wide_aperture(**params)), _capi.make_cameras(cams, T), n, int(image_width), int(image_height), lr, fd, table.ctypes.data_as(C.c_void_p)))
     return table
 
@@ -140,29 +80,19 @@ def wide_aperture_batch_work_bytes(image_width, image_height, n_views, elem_type
 
 
 def _batch_host(images, features, cams, n_frames, lens_radii, focus_dists, params):
-    if isinstance(features, dict):
-        features = features["raw"]
-    images, features = np.asarray(images), np.asarray(features)
-    T = images.dtype
-    if T not in (np.dtype(np.float32), np.dtype(np.float64)) or features.dtype != T:
-        raise TypeError("images and features must both be float32 or both float64")
-    if images.ndim != 4 or images.shape[-1] != 3 or features.shape != images.shape[:-1] + (8,):
-        raise ValueError(f"expected images [N, H, W, 3] and features [N, H, W, 8], got {images.shape} and {features.shape}")
-    if 0 in images.shape:
-        raise ValueError("empty images")
+    T, img, feat = _host_arrays(images, features, batch=True)
     cams, Tc = _batch_cameras(cams)
     if np.dtype(Tc) != T:
         raise TypeError(f"the cameras have element type {np.dtype(Tc).name}, the frames {T.name}")
     n = len(cams)
-    if images.shape[0] != n_frames:
-        raise ValueError(f"{images.shape[0]} frames where {n_frames} are expected for {n} views")
-    H, W = images.shape[1:3]
+    if img.shape[0] != n_frames:
+        raise ValueError(f"{img.shape[0]} frames where {n_frames} are expected for {n} views")
+    W, H = img.shape[1:3]
     lr, fd = _lens_arrays(lens_radii, focus_dists, n)
     params.setdefault("lens_radius", 0.0)
-    img, feat = (np.ascontiguousarray(np.swapaxes(a, 1, 2)) for a in (images, features))      # the library's layout: pixel (i, j) of view v at v*W*H + j*H + i
     out = np.empty((n, W, H, 3), dtype=T)
-    fn = getattr(_capi.lib(), "rtw_lens_batch_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(make_wide_aperture(**params)), _capi.make_cameras(cams, T.type), n, n_frames, lr, fd, W, H, *(a.ctypes.data_as(C.c_void_p) for a in (img, feat, out))))
+    _capi.check(_entry("rtw_lens_batch_", T)(C.byref(make_wide_aperture(**params)), _capi.make_cameras(cams, T.type), n, n_frames, lr, fd, W, H,
+                                             *(a.ctypes.data_as(C.c_void_p) for a in (img, feat, out))))
     return np.swapaxes(out, 1, 2)
 
 
@@ -198,7 +128,7 @@ def wide_aperture_batch_into(d_out_ptr, d_work_ptr, d_images_ptr, d_features_ptr
     images and features of ``n_frames`` frames (``n_views``, the default, or 1: every view reads frame 0), ``d_work_ptr`` of
     ``wide_aperture_batch_work_bytes`` bytes and ``d_out_ptr`` of ``n_views`` frames, views one behind the other."""
     T = np.dtype(elem_type).type
-    fn = getattr(_capi.lib(), "rtw_lens_batch_device_" + ("f64" if _capi.is_f64(T) else "f32"))
+    fn = _entry("rtw_lens_batch_device_", T)
     B = make_wide_aperture(0.0, 0.0, max_radius, gamma, device)
     _capi.check(fn(C.byref(B), int(n_views), int(n_views if n_frames is None else n_frames), C.c_void_p(int(d_table_ptr)), int(image_width), int(image_height),
                    *(C.c_void_p(int(q)) for q in (d_images_ptr, d_features_ptr, d_work_ptr, d_out_ptr)), C.c_void_p(int(stream))))
@@ -210,27 +140,5 @@ def render_wide_aperture_batch(scene, cams, image_width=400, n_samples=1, *, see
     pass through the pinhole copies, with ``denoise`` one batched filter pass, then the batched lens stage; the result comes back once.
     Returns ``img[v, i, j, :]``; view ``v`` is bit for bit ``render_wide_aperture(scene, cams[v], ..., seed=seeds[v])`` with
     ``lens_radii[v]`` (default: the camera's own) and ``focus_dists[v]``.  ``last_stats()`` reports the render."""
-    cams, T = _batch_cameras(cams)
-    n = len(cams)
-    dk = {} if denoise in (None, False, True) else dict(denoise)
-    if set(dk) - set(_DENOISE_KEYS):
-        raise ValueError(f"denoise takes the keywords {_DENOISE_KEYS}, got {sorted(set(dk) - set(_DENOISE_KEYS))}")
-    bk = {} if wide_aperture is None else dict(wide_aperture)
-    if set(bk) - set(_STAGE_KEYS):
-        raise ValueError(f"wide_aperture takes the keywords {_STAGE_KEYS}, got {sorted(set(bk) - set(_STAGE_KEYS))}")
-    bk.setdefault("lens_radius", -1.0)                       # (the one-call form alone: the camera's own)
-    lr, fd = _lens_arrays(lens_radii, focus_dists, n)
-    sd = _capi.make_seeds(seed if seeds is None else seeds, n)
-    height = _frame_height(image_width, n_samples)
-    L = _capi.lib()
-    flat = scene if isinstance(scene, dict) else flatten_scene(scene, T)
-    S, keep = _capi.make_scene(flat, T)
-    P = _capi.make_params(image_width, height, n_samples, depth, seed, n_chunks, 0, 1, device, 1 if gamma else 0, 0)
-    D = make_denoise(gamma=gamma, **dk) if denoise else None
-    B = make_wide_aperture(gamma=gamma, **bk)
-    out = np.empty(n * height * int(image_width) * 3, dtype=T)
-    fn = getattr(L, "rtw_render_lens_batch_" + ("f64" if _capi.is_f64(T) else "f32"))
-    _capi.check(fn(C.byref(S), _capi.make_cameras(cams, T), n, sd, C.byref(P), C.byref(D) if D is not None else None, C.byref(B), lr, fd, out.ctypes.data_as(C.c_void_p)))
-    del keep
-    _record_stats(L)
-    return out.reshape(n, int(image_width), height, 3).transpose(0, 2, 1, 3)
+    return _render_lens("rtw_render_lens_batch_", make_wide_aperture, "wide_aperture", wide_aperture, scene, cams, image_width, n_samples, depth, seed, n_chunks, device, gamma, denoise,
+                        batch=(seeds, lens_radii, focus_dists))

@@ -68,6 +68,38 @@ int main() {
                         for (unsigned char c : buf) { once += c == 1; more += c > 1; }
                         CHECK(more == 0 && once == L.img_b + L.feat_b + L.out_b + L.work_b + L.tab_b);
                     }
+    // n_views == 0, the SINGLE call: one frame in, one out, one workspace and NO table -- the regions are the denoiser's of one frame with
+    // this stage's workspace (what the single host forms used before they shared this layout), whatever n_frames says; a batch of one
+    // view has the same strides, extents and offsets and the table behind them
+    for (const auto &sz : sizes)
+        for (size_t elem : {(size_t)4, (size_t)8})
+            for (int mr : radii)
+                for (int nf : {0, 1, 5}) {
+                    const size_t W = (size_t)sz[0], H = (size_t)sz[1];
+                    const LensBatchLayout L(elem, sz[0], sz[1], mr, 0, nf), B(elem, sz[0], sz[1], mr, 1, 1);
+                    const size_t frame = W * H * 3 * elem, feat = W * H * 8 * elem, work = work_elems(W, H, mr) * elem;
+                    const DenoiseLayout D(elem, sz[0], sz[1], 0, work);
+                    CHECK(L.frame_b == frame && L.img_b == frame && L.out_b == frame && L.feat_b == feat && L.work_b == work && L.work_stride == work && L.out_stride == frame);
+                    CHECK(L.img_stride == 0 && L.feat_stride == 0);
+                    CHECK(L.tab_b == 0 && L.total == L.off_work + L.work_b && L.off_tab == L.total);
+                    CHECK(L.off_feat == D.off_feat && L.off_out == D.off_out && L.off_work == D.off_work && L.total == D.total && L.img_b == D.img_b && L.feat_b == D.feat_b);
+                    CHECK(L.off_feat == B.off_feat && L.off_out == B.off_out && L.off_work == B.off_work && L.off_tab == B.off_tab && B.total == L.total + 32 * elem);
+                    CHECK(L.img_b == B.img_b && L.feat_b == B.feat_b && L.out_b == B.out_b && L.work_b == B.work_b && L.img_stride == B.img_stride && L.feat_stride == B.feat_stride);
+                    std::vector<unsigned char> buf(L.total, 0);
+                    for (size_t k = 0; k < L.img_b; ++k) ++buf[k];
+                    for (size_t k = 0; k < L.feat_b; ++k) ++buf[L.off_feat + k];
+                    for (size_t k = 0; k < L.out_b; ++k) ++buf[L.off_out + k];
+                    for (size_t k = 0; k < L.work_b; ++k) ++buf[L.off_work + k];
+                    size_t once = 0, more = 0;
+                    for (unsigned char c : buf) { once += c == 1; more += c > 1; }
+                    CHECK(more == 0 && once == L.img_b + L.feat_b + L.out_b + L.work_b);
+                }
+    // the defocus stage's workspace is the narrow part of the wide-aperture stage's, and all of it up to max_radius 8
+    for (const auto &sz : sizes) {
+        const size_t W = (size_t)sz[0], H = (size_t)sz[1];
+        CHECK(WideApertureLayout(sz[0], sz[1], 8).narrow == 4 * W * H + r4(tiles(W, H)) && WideApertureLayout(sz[0], sz[1], 8).total == WideApertureLayout(sz[0], sz[1], 32).narrow);
+        CHECK(WideApertureLayout::tiles(W, H) == tiles(W, H));
+    }
     // the extents the alias check sees: with n_frames == 1 an output one frame behind the images' start is free, with n_frames == n_views it is not
     {
         const LensBatchLayout one(4, 10, 6, 16, 3, 1), all(4, 10, 6, 16, 3, 3);

@@ -174,3 +174,24 @@ def test_the_one_call_form_is_the_chain_of_the_single_calls(rtw, T, denoise, gam
         _assert_same(out.cpu().numpy().reshape(W, H, 3).transpose(1, 0, 2), wit_out, "wide_aperture_into")
         for name, a in WA.unpack_work(work.cpu().numpy(), H, W, mr).items():
             _assert_same(a, wit_work[name], f"wide_aperture_into: the workspace's {name}")
+
+
+@pytest.mark.parametrize("gamma", [False, True], ids=["linear", "gamma"])
+@pytest.mark.parametrize("denoise", [None, DENOISE], ids=["plain", "filtered"])
+@pytest.mark.parametrize("T", PRECISIONS)
+def test_the_one_call_forms_agree_up_to_max_radius_8(rtw, T, denoise, gamma):
+    """rtw_render_defocused_* and rtw_render_wide_aperture_* with the same max_radius <= 8 return the same bits (the header: with
+    max_radius <= 8 the wide-aperture call IS the defocus call): scene_2_spheres through the camera with its aperture, 96 x 54 at 2 spp,
+    with and without the filter, gamma off (max_radius 5) and on (max_radius 8).  The lens is the camera's own: a point at infinity has a
+    circle of K = lens_radius * W / |horizontal|, about 13 px, so both clamps bind and the frame differs from the closed aperture's."""
+    cam, _ = _cameras(rtw, T)
+    scene = rtw.scene_2_spheres(elem_type=T)
+    W, spp, seed, mr = 96, 2, 11, 8 if gamma else 5
+    assert float(cam.lens_radius) * W / float(np.linalg.norm(np.asarray(cam.horizontal, np.float64))) > 8
+    kw = dict(seed=seed, denoise=denoise, device=0, gamma=gamma)
+    narrow = rtw.render_defocused(scene, cam, W, spp, defocus=dict(max_radius=mr), **kw)
+    wide = rtw.render_wide_aperture(scene, cam, W, spp, wide_aperture=dict(max_radius=mr), **kw)
+    assert narrow.shape == wide.shape == (54, 96, 3) and narrow.dtype == wide.dtype == T
+    _assert_same(wide, narrow, f"render_wide_aperture against render_defocused, max_radius {mr}")
+    closed = rtw.render_defocused(scene, cam, W, spp, defocus=dict(max_radius=mr, lens_radius=0.0), **kw)
+    assert not FO.same_bits(narrow, closed)

@@ -214,6 +214,21 @@ def test_the_one_call_form_is_refused_without_a_device(lib, rtw, T):
     del keep, keep2
 
 
+@pytest.mark.parametrize("T", [np.float32, np.float64])
+def test_the_one_call_form_refuses_a_radius_beyond_its_own_bound_and_names_no_view(lib, rtw, T):
+    """rtw_render_wide_aperture_* with max_radius = 33: -2 with this stage's bound, 1..32; a single call names no view"""
+    from rtw_amd import _capi
+    fn = getattr(lib, "rtw_render_wide_aperture_" + ("f64" if T is np.float64 else "f32"))
+    W, H = 10, 6
+    S, keep = _capi.make_scene(rtw.flatten_scene(rtw.scene_2_spheres(elem_type=T), T), T)
+    cam = _capi.make_camera(rtw.t_cam1(elem_type=T), T)
+    out = np.zeros(W * H * 3, T)
+    assert fn(C.byref(S), C.byref(cam), C.byref(_capi.make_params(W, H, 2)), None, C.byref(_b(max_radius=33)), out.ctypes.data_as(C.c_void_p)) == -2
+    err = lib.rtw_last_error()
+    assert b"1..32" in err and b"view" not in err, err
+    del keep
+
+
 def test_the_python_layer_checks_its_arguments(rtw):
     T = np.float32
     cam = rtw.t_default_cam(elem_type=T)
