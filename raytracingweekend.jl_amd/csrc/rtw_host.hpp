@@ -68,7 +68,7 @@ struct rtw_scene_dev {
     // pass 1 on the matrix pipe (hit_world_mfma): A operands per block of 32 spheres, scales and the ray's share of the margin
     void *mf_ops;    // null: the scene's extent is outside what the f16 split covers (the VALU scan is used)
     int mf_blocks;
-    float mf_sc, mf_sigma2, mf_oo_keep, mf_o1_coef, mf_o_max;
+    float mf_sc, mf_sigma2, mf_oo_keep, mf_o1_coef, mf_o_max, mf_mr;
     int n_huge, huge[2];   // spheres that pass the filter for nearly every ray (a ground sphere): tested exactly by every lane, their filter rows disabled
     // the plain matrix-pipe scan of the trace kernel runs over its OWN order (rtw_plain_layout.hpp: spatially sorted, evenly filled blocks; the
     // huge spheres behind the blocks): operands, geom / mat0 / mat1 rows and the caller's index of every row.  Set whenever mf_ops is.

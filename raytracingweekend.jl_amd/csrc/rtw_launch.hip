@@ -336,7 +336,7 @@ int resolve_rec(RenderRec *r, rtw_stats_t *agg) {
             fprintf(stderr, "[rtw phase counts] per wave-iteration:");
             static const char *nm[32] = {0, 0, 0, 0, 0, 0, "blocks_without_candidate", "blocks", "iterations", "lanes_with_ray", "iterations_without_ray", "takers_pool_short", "takers_unserved",
                                          "list_entries", "exact_test_rounds", "exact_tests", "reject_trials", "R_executed", "H1_executed", "H1_rounds", "A_executed", "jobs_stored", "batches_set_up",
-                                         "H2_executed", "B_executed", "F_normalize_executed", "sign_collections", "blocks_recording", "explode_iterations", "reject_trials_3_draws", 0, 0};
+                                         "H2_executed", "B_executed", "F_normalize_executed", "sign_collections", "blocks_recording", "explode_iterations", "reject_trials_3_draws", "half_blocks", "half_blocks_settled_coarse"};
             for (int k = 6; k < 32; ++k) if (nm[k]) fprintf(stderr, " %s=%.4f", nm[k], (double)c.phase[k] / (double)c.phase[8]);
             fprintf(stderr, "\n");
         }

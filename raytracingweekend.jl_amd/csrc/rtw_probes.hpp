@@ -3,6 +3,7 @@
 // this is in librtw_hip.so.  A probe's body refers to the local variables of the one site that uses it.
 //   -DRTW_DUP_OPERANDS       the ray-operand build of hit_world_mfma (features, f16 splits, word assembly, lane exchange) a second time
 //   -DRTW_DUP_MFMA[=k]       every MFMA pair k more times, same result      -DRTW_PROBE_NO_MFMA   a constant "no candidate" instead (WRONG image)
+//                            (both act on the back-to-back pair: the group cull, or the plain scan built with -DRTW_TWO_STAGE=0)
 //   -DRTW_DUP_EVAL           the sign collection twice                      -DRTW_DUP_EXTRACT     the extraction loop twice
 //   -DRTW_DUP_RESOLVE_PAIRS  the final resolve twice (idempotent)           -DRTW_DUP_REJECT      the rejection loop twice (on a copy of the generator)
 //   -DRTW_PROBE_REJ_CAP=n    the rejection loop stops after n trials (WRONG image)
@@ -26,11 +27,12 @@
         for (int k = 0; k < 6; ++k) sq_[k] = split_f16(fq_[k]);                                                                             \
         for (int k = 0; k < 3; ++k) sp_[k] = split_f16(fp_[k]);                                                                             \
         const float tx_ = ok ? tq_ : tx;                                                                                                    \
-        const _Float16 t1_ = (_Float16)(tx_ * (1.0f / 32768.0f));                                                                           \
-        const unsigned x23_ = split_f16((tx_ - 32768.0f * (float)t1_) * (1.0f / 16.0f));                                                    \
-        const unsigned a0[8] = {dup(sq_[0]), cat(sq_[0], sq_[1]), sq_[1], dup(sq_[2]), sq_[5], dup(sp_[0]), cat(sp_[0], sp_[1]), sp_[1]};   \
-        const unsigned a1[8] = {cat(sq_[2], sq_[3]), sq_[3], dup(sq_[4]), cat(sq_[4], sq_[5]), dup(sp_[2]), cat(sp_[2], sb),                \
-                                ss | ((unsigned)__builtin_bit_cast(unsigned short, t1_) << 16), x23_};                                      \
+        const float txm_ = tx_ + (ok ? __builtin_fmaf(oo_, w.mf_mr, 0x1p-9f) : 0.0f);                                                       \
+        const _Float16 t1_ = (_Float16)(txm_ * (1.0f / 32768.0f));                                                                          \
+        const unsigned x23_ = split_f16(__builtin_fmaf(-32768.0f, (float)t1_, tx_) * (1.0f / 16.0f));                                       \
+        const unsigned a0[8] = {lead(sq_[0], sq_[1]), lead(sq_[2], sq_[3]), lead(sq_[4], sq_[5]), dup(sp_[1]), sq_[0], sq_[1], sq_[2], sq_[3]};\
+        const unsigned a1[8] = {sp_[0], sp_[2], lead(sp_[0], sp_[2]), sb | ((unsigned)__builtin_bit_cast(unsigned short, t1_) << 16),       \
+                                sq_[4], sq_[5], cat(sp_[1], ss), x23_};                                                                     \
         for (int k = 0; k < 8; ++k) {                                                                                                       \
             const auto sw2 = __builtin_amdgcn_permlane32_swap(a0[k], a1[k], false, false);                                                  \
             __asm__ volatile("" :: "v"(sw2[0]), "v"(sw2[1]));                                                                               \

@@ -37,6 +37,7 @@ template <typename T> struct DevScene {
     float mf_oo_keep;       // 1 - (the ray's share of the relative margin)
     float mf_o1_coef;       // absolute margin per unit of |o|_1
     float mf_o_max;         // rays with a larger |o_k| (or non-unit, non-finite ones) take every sphere as a candidate
+    float mf_mr;            // the ray's share of the COARSE margin per unit of |o|^2, scaled (Mr s^2 = mf_mr |o|^2 + 2^-9: two-stage evaluation, rtw_scan_mfma.hpp)
     int n_huge, huge[2];    // spheres tested exactly by every lane instead of through the filter (a ground sphere: candidate of nearly every ray)
     int numerics;           // NUM_*: the deciding arithmetic of sphere_disc for this render (set per launch, not per upload)
     const unsigned short *orig;   // the plain matrix-pipe scan of the trace kernel (its own sphere order: geom / mat0 / mat1 / mf_ops / huge above are

@@ -15,7 +15,8 @@ namespace rtw {
 // distinct products -- so ONE K = 32 contraction gives the whole filter value
 //     W = [2dx^2 2dy^2 2dz^2 4dxdy 4dxdz 4dydz | 2p | 1 | q^2 - oo'] . [cx^2 cy^2 cz^2 cxcy cxcz cycz (x 1/2) | c | k' | 1]
 // (k' = r^2 - |c|^2 + Gs, oo' = |o|^2 - Gr: the sphere's and the ray's shares of the error margin), computed by two chained
-// v_mfma_f32_32x32x16_f16 (the second accumulates onto the first) for 32 spheres x 32 rays.  The VALU is left with ONE
+// v_mfma_f32_32x32x16_f16 (the second accumulates onto the first; the plain scan issues it only where the first leaves a half block
+// undecided: "Two stages" below) for 32 spheres x 32 rays.  The VALU is left with ONE
 // instruction per (ray, sphere) -- the v_alignbit that collects the sign -- instead of the 11 instructions of hit_world's
 // pass 1 (round 2 formed W = P1^2 + P2 from two separate products: one v_fma_f32 more per test, 22 % of the kernel's VALU
 // instructions, and 16 more result registers).  An MFMA and VALU instructions do not overlap on a SIMD, whichever wave they
@@ -34,11 +35,14 @@ namespace rtw {
 // scales so that no small piece lands in the f16 subnormal range:
 //     k' s^2  = 2^15 k1 + 2^4 k2                     against the ray-side constants (2^15, 2^4)  (0 for a ray that is not ok)
 //     (q^2 - oo') s^2 = 2^15 t1 + 2^4 (t2 + t3)       against the sphere-side constants (2^15, 2^4, 2^4)
-// 18 + 9 + 2 + 3 = 32 slots:
-//     slot  0-7   (MFMA 1, lanes 0-31)   xx xx xx yy yy yy zz zz        ray pieces (1 1 2 | 1 1 2 | 1 1)   sphere pieces (1 2 1 | 1 2 1 | 1 2)
-//     slot  8-15  (MFMA 1, lanes 32-63)  zz xy xy xy xz xz xz yz        (2 | 1 1 2 | 1 1 2 | 1)            (1 | 1 2 1 | 1 2 1 | 1)
-//     slot 16-23  (MFMA 2, lanes 0-31)   yz yz px px px py py py        (1 2 | 1 1 2 | 1 1 2)              (2 1 | 1 2 1 | 1 2 1)
-//     slot 24-31  (MFMA 2, lanes 32-63)  pz pz pz k k T T T             (1 1 2 | 2^15 2^4 | t1 t2 t3)      (1 2 1 | k1 k2 | 2^15 2^4 2^4)
+// 18 + 9 + 2 + 3 = 32 slots = 11 LEADING products (piece 1 x piece 1 of the nine features, 2^15 k1, 2^15 t1) + 21 CORRECTIONS (18 cross terms,
+// 2^4 k2, 2^4 t2, 2^4 t3).  MFMA 1 holds the leading products and five corrections, MFMA 2 the other sixteen (why these five: "Two stages" below):
+//     slot  0-7   (MFMA 1, lanes 0-31)   xx yy zz xy xz yz py py        ray pieces (1 1 1 1 1 1 | 1 1)            sphere pieces (1 1 1 1 1 1 | 1 2)
+//     slot  8-15  (MFMA 1, lanes 32-63)  px px pz pz px pz k  T         (1 2 | 1 2 | 1 1 | 2^15 t1)               (2 1 | 2 1 | 1 1 | k1 2^15)
+//     slot 16-23  (MFMA 2, lanes 0-31)   xx xx yy yy zz zz xy xy        (1 2 | 1 2 | 1 2 | 1 2)                   (2 1 | 2 1 | 2 1 | 2 1)
+//     slot 24-31  (MFMA 2, lanes 32-63)  xz xz yz yz py k  T  T         (1 2 | 1 2 | 2 2^4 | t2 t3)               (2 1 | 2 1 | 1 k2 | 2^4 2^4)
+// (a feature's own split word (1, 2) is a ray operand word as it stands: 7 word-assembly instructions per scan, 11 in the old slot order;
+//  the sphere side is built on the host: rtw_mfma_operands.hpp, which also mirrors the ray side for tests/two_stage_check.cpp)
 // Error budget in unscaled units, in multiples of 2^-22 (u = 2^-24 = 0.25, |d|^2 <= 1.001, S = (|o| + |c|)^2, |p| <= |o|):
 //     splits of the quadratic features (3.01 x sum |terms| <= 1.001 |c|^2)             3.02 |c|^2
 //     splits of the linear features (3.01 x 2 |p| |c|)                                 6.03 |o| |c|
@@ -60,6 +64,39 @@ namespace rtw {
 // 2^-22: the round-2 constants, kept although this formulation needs only 36 / 29 / 5 of the 76 / 64 / 12 they provide -- no
 // error is amplified by a squaring any more) and the ray subtracts  oo' = |o|^2 (1 - 1.02 x 2^-16) - 9.18 phi_c |o|_1
 // (mf_oo_keep, mf_o1_coef), so that  deciding discriminant >= 0 (any numerics mode)  =>  W > 0: sign bit clear.
+// Two stages.  The first MFMA alone gives a COARSE value P1' that the second only refines, and 78 % of the half-block evaluations of the
+// headline scene end without a candidate in any lane: the plain scan tests the 16 coarse values of a half block first and issues the second
+// MFMA only where some lane's is not negative (RTW_TWO_STAGE; the group cull visits a third of the blocks, most of which record: it issues the
+// pair back to back).  For that, a margin Mc = Ms(sphere) + Mr(ray) is folded into the pair through the constants' own pieces -- there is no
+// spare slot: MFMA 1 computes P1' = (its products, +Mc) and MFMA 2 adds (its products, -Mc); W = P1' + P2' is the same sum as before.
+//   sphere, host:    k1 = the smallest f16 with 2^15 k1 >= (k' + Ms) s^2;  k2 = RU16((k' s^2 - 2^15 k1) / 16): negative, rounded UP as before
+//   ray, prologue:   t1 = RN16((tx + Mr s^2) / 2^15), tx = (q^2 - oo') s^2;  trem = fma(-2^15, t1, tx);  (t2, t3) = split_f16(trem / 16)
+// Which five corrections join the leading products: in the worst case the six cross terms of 2 p.c dominate the rest by far -- each is up to
+// 2^-11 x 2 |p_k| |c_k| with |p| <= |o| up to 32 x the scene's extent, 2^6 x the bound 2^-11 |c|^2 of a cross term of (d.c)^2 -- and k2, t2, t3
+// must stay in MFMA 2, where they hand the margin back.  So five of the six linear cross terms go to MFMA 1; the sixth, (py piece 2) x (cy
+// piece 1), stays behind: no axis is special in the bound, and y is the flat axis of the reference's scenes.  What MFMA 2 then holds besides the
+// constants (|x2| <= 2^-11 |x|, |x1| <= (1 + 2^-11) |x| + 2^-25; S = scaled units):
+//     twelve cross terms of the quadratic features     <= 2 x 2^-11 (1 + 2^-11) sum |2 m d_i d_j| |c_i c_j / 2| s^2 = 2^-10 x 1.002 (sum |d_i| |c_i|)^2 s^2 <= 2^-10 x 1.002 |c|^2 s^2
+//     py2 x cy1                                        <= 2^-11 x 1.001 x 2 |p_y| |c_y| s^2 <= 2^-11 x 1.002 (|o|^2 + |c|^2) s^2          (|p| <= |o| (1 + 2^-20))
+//     floors (a first piece that is an f16 subnormal)  <= 6 x 2^-21 + 2^-20.5 < 2^-17  [S]
+// and MFMA 1's own accumulation error is E1 <= 2^-20 x sum |its terms| <= 2^-20 (3.1 |c|^2 + 1.1 r^2 + 2.1 |o|^2) s^2 (leading products 1.002 |c|^2 +
+// 2.002 |o| |c|, |2^15 k1| <= 1.01 (r^2 + |c|^2), |2^15 t1| <= 1.01 |o|^2, the five cross terms 2^-9 |o| |c|).  The margin separates like Gs / oo':
+//     Ms s^2 = 1.01 [(1.506 x 2^-10 + 3.1 x 2^-20) |c|^2 + 1.1 x 2^-20 r^2] s^2 + 2^-19        (RTW_MF_MS_*; the 2^-19: k2 rounded up inside the f16 subnormals)
+//     Mr s^2 = 1.01 (0.502 x 2^-10 + 1.003 x 2^-11 + 2.1 x 2^-20) |o|^2 s^2 + 2^-9             (mf_mr |o|^2 + 2^-9: one v_fma_f32, a select and an add per scan)
+// Mr also pays for the rounding of t1 itself, which the ray cannot direct upwards: |2^15 t1 - (tx + Mr s^2)| <= 2^-11 (1.002 |o|^2 s^2 + Mr s^2 +
+// 2^-7) or 2^-10 where t1 is an f16 subnormal -- the 1.003 x 2^-11 term and half of the 2^-9.  The roundings of the fold: k2 rounded up takes
+// at most 2^-10 of the remainder back (inside the 1.01); trem is no longer exact in binary32 -- |trem| <= Mr s^2 + 2^-11 |tx + Mr s^2| <= 2^-9.4
+// |o|^2 s^2, one rounding of 2^-24 |trem| -- and t2 + t3 leave 2^-22 |trem| + 2^-21: together 2^-21.4 |trem| <= 0.002 x 2^-22 |o|^2 s^2, and the two
+// MFMAs sum 2 Mc s^2 more in |terms|: 0.01 x 2^-22 (|c|^2 + |o|^2).  The budget above becomes 36.0 / 28.8 / 5 of the 76 / 64 / 12 that Gs,
+// mf_oo_keep and mf_o1_coef provide: they stay as they are, and so do the bands of tests/exact_filters.py.  f16 ranges: |trem / 16| <= 2^-9.4 x
+// 3 x 2^26 / 16 = 2^14.2 and |k2| <= (Ms s^2 + 2^-10 |k' s^2|) / 16 < 2^6 at the limits |o_k| s = 2^13, |c_k| s = 2^8.
+// Hence, with C^ = P1' + e1 (|e1| <= E1) the value the pre-check sees and W^ = C^ + P2' + e2 the final one:
+//     -P2' >= Mc s^2 (1 - 2^-10) - (what MFMA 2 holds besides the constants) - 2^-19 - 2^-9 / 2 >= E1,  so  C^ >= W_exact (the 32 exact products)
+// and for every ray that uses the filter and every sphere, in every numerics mode:
+//     deciding discriminant >= 0  =>  W_exact >= E1 + E2 (the budget above)  =>  P1' >= E1 and C^ >= 0: sign bit clear, the half block stays open,  and W^ > 0.
+// tests/two_stage_check.cpp evaluates both sums of given pairs in exact integer arithmetic and asserts -P2' >= E1 pair by pair.
+// Special rows and rays mean the same in the coarse value: a ray that is not ok has all features 0, both constants of k 0 and t1 = +-60000
+// (no margin, no remainder): P1' = W = +-2^15 x 60000 exactly; a padding row has k1 = -2^15 and k2 = 0 against |2^15 t1| <= 1.01 x 3 x 2^26: P1' < 0.
 // Rays that are not (nearly) unit (the reference does not renormalise dielectric reflections), not finite, or farther
 // than 2^13 / s from the origin take EVERY sphere as a candidate (all features 0, t1 = 60000); lanes without a ray take none
 // (t1 = -60000).  Padding spheres carry k' s^2 = -2^30.
@@ -141,6 +178,10 @@ __device__ __forceinline__ double lane_get(double v, unsigned src_lane) {
 #endif
 #ifndef RTW_PRECHECK_GROUPS
 #define RTW_PRECHECK_GROUPS 1   // groups per half block whose sign collection is skipped separately (hit_world_mfma): 1, 2 or 4
+#endif
+#ifndef RTW_TWO_STAGE
+#define RTW_TWO_STAGE 1      // plain scan (no block vote): the second MFMA of a half block runs only where some lane's coarse value is not negative
+                             // (0: both MFMAs back to back, as the group cull always issues them -- same operands, same W; the A/B of the skip alone)
 #endif
 #ifndef RTW_SCAN_SKIP
 #define RTW_SCAN_SKIP 1      // wave-level early-out per half block (hit_world_mfma): 372.2 vs 376.3 ms.  (Left to the compiler it is
@@ -250,6 +291,7 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
                                               const MfmaCull *mc = nullptr, ORIG orig = ORIG(), SINK sink = SINK()) {
     constexpr bool HAS_ORIG = !__is_same(ORIG, NoOrig);      // device order != the caller's order: ties go by orig[]
     constexpr bool CULLED = VOTE;                            // the group cull: operands, tables and the in-lane list of `mc`, the block vote
+    constexpr bool TWO_STAGE = RTW_TWO_STAGE != 0 && !VOTE;  // the plain scan decides most half blocks after the first MFMA of the pair
     static_assert(HAS_ORIG || !VOTE, "the group cull's order comes with its index array");
     // radii (mat0[i].x) in the order of `src`: read by NUM_REFERENCE_FMA2 only -- fetched from the kernel arguments where that mode needs them, not held across the scan
     auto rad = [&]() -> const typename Vec4<T>::type * { if constexpr (CULLED) return (const typename Vec4<T>::type *)mc->mat0; else return w.mat0; };
@@ -358,6 +400,13 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
         __asm__("" : "+s"(q));
         A1 = __builtin_bit_cast(uint4, q[(size_t)lane]); A2 = __builtin_bit_cast(uint4, q[(size_t)lane + 64u]);
     };
+    // (two-stage evaluation: the two rows on their own -- A1 is free once the second half's coarse MFMA is issued, A2 only when that half is decided)
+    [[maybe_unused]] auto fetch_row = [&](int b, uint4 &A, unsigned row) {
+        typedef unsigned u4 __attribute__((ext_vector_type(4)));
+        const __attribute__((address_space(1))) u4 *q = (const __attribute__((address_space(1))) u4 *)pa_of(b);
+        __asm__("" : "+s"(q));
+        A = __builtin_bit_cast(uint4, q[(size_t)lane + row]);
+    };
     if constexpr (!CULLED) fetch(0);
     // Lane (H, j) supplies slots 8H .. 8H + 7 of both MFMAs for ray j (first half wave: h = 0) / ray 32 + j (h = 1).  Every
     // lane makes, for ITS ray, the operand words of both lane groups; one v_permlane32_swap per word then hands each lane
@@ -371,17 +420,21 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
     for (int k = 0; k < 6; ++k) sq[k] = split_f16(fq[k]);
 #pragma unroll
     for (int k = 0; k < 3; ++k) sp[k] = split_f16(fp[k]);
-    const _Float16 t1 = (_Float16)(tx * (1.0f / 32768.0f));
-    const float trem = tx - 32768.0f * (float)t1;                         // exact
+    // t1 carries the ray's share Mr of the coarse margin ("Two stages" above): rounded from tx + Mr s^2, and the remainder -- taken from tx
+    // itself, so the pair's sum is unchanged -- hands the margin back through t2, t3 in the second MFMA.  (A ray that is not ok: t1 = +-60000, no remainder.)
+    const float txm = tx + (ok ? __builtin_fmaf(oo, w.mf_mr, 0x1p-9f) : 0.0f);
+    const _Float16 t1 = (_Float16)(txm * (1.0f / 32768.0f));
+    const float trem = __builtin_fmaf(-32768.0f, (float)t1, tx);         // |trem| <= 2^-9.4 |o|^2 s^2: one rounding of 2^-24 |trem|, in the budget
     const unsigned x23 = split_f16(trem * (1.0f / 16.0f));               // (t2, t3)
     const unsigned sb = ok ? 0x7800u : 0u, ss = ok ? 0x4c00u : 0u;        // the ray's constants 2^15, 2^4 as f16 (0: not ok)
     auto dup = [](unsigned v) { return __builtin_amdgcn_perm(v, v, 0x01000100u); };                 // (piece 1, piece 1)
     auto cat = [](unsigned a, unsigned b) { return __builtin_amdgcn_alignbit(b, a, 16); };        // (piece 2 of a, piece 1 of b)
-    // words 0-3: MFMA 1 (slots 0-7 | 8-15), words 4-7: MFMA 2 (slots 16-23 | 24-31)
-    const unsigned g0[8] = {dup(sq[0]), cat(sq[0], sq[1]), sq[1], dup(sq[2]),                       // xx xx | xx yy | yy yy | zz zz
-                            sq[5], dup(sp[0]), cat(sp[0], sp[1]), sp[1]};                            // yz yz | px px | px py | py py
-    const unsigned g1[8] = {cat(sq[2], sq[3]), sq[3], dup(sq[4]), cat(sq[4], sq[5]),                // zz xy | xy xy | xz xz | xz yz
-                            dup(sp[2]), cat(sp[2], sb), ss | ((unsigned)__builtin_bit_cast(unsigned short, t1) << 16), x23};   // pz pz | pz k | k T | T T
+    auto lead = [](unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x05040100u); };    // (piece 1 of a, piece 1 of b)
+    // words 0-3: MFMA 1 (slots 0-7 | 8-15), words 4-7: MFMA 2 (slots 16-23 | 24-31); a feature's own word (1, 2) meets the sphere's (2, 1)
+    const unsigned g0[8] = {lead(sq[0], sq[1]), lead(sq[2], sq[3]), lead(sq[4], sq[5]), dup(sp[1]),  // xx yy | zz xy | xz yz | py py
+                            sq[0], sq[1], sq[2], sq[3]};                                             // xx xx | yy yy | zz zz | xy xy
+    const unsigned g1[8] = {sp[0], sp[2], lead(sp[0], sp[2]), sb | ((unsigned)__builtin_bit_cast(unsigned short, t1) << 16),   // px px | pz pz | px pz | k T
+                            sq[4], sq[5], cat(sp[1], ss), x23};                                      // xz xz | yz yz | py k | T T
     unsigned h0[8], h1[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -555,7 +608,56 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
         // The two ray halves of the block.  Each shifts its 16 sign bits into `bits` and keeps the lanes that made it do so (group cull: a half
         // that the vote skips is a half that did not collect).
         unsigned long long some0 = 0ull, some1 = 0ull;
+        if constexpr (TWO_STAGE) {
+        // Two stages ("Two stages" in the comment at the top): the first MFMA alone gives the coarse value P1' >= W + (MFMA 1's error bound), so a
+        // half block whose 16 coarse values are negative in every lane is settled -- one MFMA, the 9-instruction pre-check and its branch; it leaves
+        // nothing behind, like a half that does not collect.  Otherwise the second MFMA accumulates onto the coarse values (same registers) and
+        // the half goes on as before.  Plain if / else, the evaluating side first.  The next block's A1 is fetched once the second half's
+        // coarse MFMA is issued, its A2 behind that half's conditional second MFMA: neither path copies operand registers.
+        auto coarse = [&](const uint4 &a1, const rtw_h8 &b1) -> rtw_f16v {
+            clk.count(30, 1u);                                                         // half blocks evaluated
+            return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(rtw_h8, a1), b1, zero, 0, 0, 0);
+        };
+        auto undecided = [&](const rtw_f16v &Wv) -> unsigned long long {             // the pre-check of collect() on the coarse values
+            unsigned t = __builtin_amdgcn_bitop3_b32(__float_as_uint(Wv[0]), __float_as_uint(Wv[1]), __float_as_uint(Wv[2]), 0x80);
+#pragma unroll
+            for (int r = 3; r < 15; r += 2) t = __builtin_amdgcn_bitop3_b32(t, __float_as_uint(Wv[r]), __float_as_uint(Wv[r + 1]), 0x80);
+            t &= __float_as_uint(Wv[15]);
+            return __ballot((int)t >= 0);
+        };
+        {
+            rtw_f16v Wv = coarse(A1, B1[0]);
+            if (undecided(Wv)) {
+                __asm__ volatile("" : "+v"(Wv));             // (fenced like the sign collection: never if-converted)
+                Wv = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(rtw_h8, A2), B2[0], Wv, 0, 0, 0);
+                some0 = collect(Wv, bits);
+            } else {
+                clk.count(31, 1u);                                                     // ... of which the coarse test settled
+            }
+        }
+        {
+            rtw_f16v Wv = coarse(A1, B1[1]);
+            __builtin_amdgcn_sched_barrier(0);
+            fetch_row(blk, A1, 0u);
+            __builtin_amdgcn_sched_barrier(0);
+            unsigned long long open1 = undecided(Wv);
+            if (open1) {
+                __asm__ volatile("" : "+v"(Wv));
+                Wv = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(rtw_h8, A2), B2[1], Wv, 0, 0, 0);
+            } else {
+                clk.count(31, 1u);
+            }
+            // (ONE fetch of A2, behind its conditional last use, and the collection under a second test of the same scalar: with the fetch on both
+            //  sides of one branch the structurized loop routes the settled side through a flow block and copies `bits` twice per block)
+            __builtin_amdgcn_sched_barrier(0);
+            fetch_row(blk, A2, 64u);
+            __builtin_amdgcn_sched_barrier(0);
+            __asm__ volatile("" : "+s"(open1));
+            if (open1) some1 = collect(Wv, bits);
+        }
+        } else {
         if (!CULLED || do_half0) {
+            clk.count(30, 1u);
             rtw_f16v Wv = filter_pair(A1, A2, B1[0], B2[0]);
             RTW_PROBE_EVAL_TWICE(Wv);
             some0 = collect(Wv, bits);
@@ -567,6 +669,7 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
         // (two copies of the prefetch: with ONE behind an `if (run) Wv = ...` the skipped side zeroes all 16 result registers -- 16 v_mov per
         //  skipped ray half in the group cull, measured in the ISA)
         if (!CULLED || do_half1) {
+            clk.count(30, 1u);
             rtw_f16v Wv = filter_pair(A1, A2, B1[1], B2[1]);
             __builtin_amdgcn_sched_barrier(0);
             fetch(blk);
@@ -575,6 +678,7 @@ __device__ __forceinline__ int hit_world_mfma(const DevScene<T> &w, SRC src, V3<
             some1 = collect(Wv, bits);
         } else {
             fetch(blk);
+        }
         }
         // The block's candidates m: bit 31 - b, b = ray half << 4 | result register, set where the filter value is NOT negative.  `bits` is all ones
         // when a block starts, each collecting half shifts its 16 signs in, and a half that is skipped does nothing at all:

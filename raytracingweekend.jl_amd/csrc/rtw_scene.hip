@@ -4,6 +4,7 @@
 #include "rtw_scene_view.hpp"
 #include "rtw_cull_tables.hpp"
 #include "rtw_plain_layout.hpp"
+#include "rtw_mfma_operands.hpp"
 
 namespace rtwh {
 
@@ -224,76 +225,29 @@ int build_mfma_operands(const std::vector<V4> &geom, int n, rtw_scene_dev *h, vo
         emax = std::max(emax, std::max(std::max(std::fabs((double)(float)geom[i].x), std::fabs((double)(float)geom[i].y)),
                                        std::max(std::fabs((double)(float)geom[i].z), r)));
     }
-    if (!(emax > 0) || !std::isfinite(emax)) return 0;
-    int ex = 0;
-    (void)std::frexp(emax, &ex);                         // emax <= 2^ex
-    if (ex > 40 || ex < -40) return 0;                   // outside what the scaled f16 pieces cover: VALU scan
-    // lengths x s: sphere coordinates and radii use 2^8 of the f16 range (their products, halved: 2^15), ray origins may use
-    // 2^13 -- rays up to 32 x the scene's extent away still take the filter (2 |p_k| s <= 2 x 2.74 x 2^13 < 65504).
-    // phi_c: a coordinate's second f16 piece is a subnormal below 2^-3 (absolute error 2^-25 scaled); phi_k: the same floor for
-    // the 2^4-scaled pieces of k' and of the ray's constant and for the second pieces of the quadratic features.
-    const double sc = std::ldexp(1.0, 8 - ex), sig2 = sc * sc;
-    const double phi_c = std::ldexp(1.0, -25) / sc, phi_k = std::ldexp(1.0, -20) / sig2;
-    const double A_S = std::ldexp(1.0, -17), A_r = std::ldexp(12.0, -22);
-    auto split = [](double x, unsigned &p1, unsigned &p2) {            // the f16 pieces of (float)x
-        const float xf = (float)x;
-        const _Float16 h1 = (_Float16)xf;
-        const _Float16 h2 = (_Float16)(xf - (float)h1);
-        unsigned short b1, b2;
-        memcpy(&b1, &h1, 2); memcpy(&b2, &h2, 2);
-        p1 = b1; p2 = b2;
-    };
+    // the scales, the margin constants and the rows' words: rtw_mfma_operands.hpp (plain C++, checked on the CPU by tests/two_stage_check.cpp)
+    MfmaScales S;
+    if (!mfma_scales(emax, &S)) return 0;                // outside what the scaled f16 pieces cover: VALU scan
     const int nb = (n_rows + 31) / 32;
     std::vector<uint4> ops((size_t)(nb + 1) * 128);
     for (int blk = 0; blk <= nb; ++blk)
         for (int lane = 0; lane < 64; ++lane) {
             const int i = lane & 31, H = lane >> 5;
             const int sph = blk * 32 + 16 * ((i >> 2) & 1) + (((i >> 3) << 2) | (i & 3));
-            double fq[6] = {0, 0, 0, 0, 0, 0}, fl[3] = {0, 0, 0};
-            double kx = -1073741824.0;                                        // padding sphere: k' s^2 = -2^30: W = -2^30 + (q^2 - oo') s^2 < 0
-            if (in_filter(sph)) {
-                const double cx = (double)(float)geom[sph].x, cy = (double)(float)geom[sph].y, cz = (double)(float)geom[sph].z;
-                const double r2 = (double)geom[sph].w, c2 = cx * cx + cy * cy + cz * cz;
-                const double Gs = 1.02 * ((2 * A_S + A_r) * c2 + A_r * r2 + 9 * phi_c * (std::fabs(cx) + std::fabs(cy) + std::fabs(cz)) + 1.5 * phi_k);
-                kx = (r2 - c2 + Gs) * sig2;
-                const double hs = 0.5 * sig2;
-                fq[0] = cx * cx * hs; fq[1] = cy * cy * hs; fq[2] = cz * cz * hs; fq[3] = cx * cy * hs; fq[4] = cx * cz * hs; fq[5] = cy * cz * hs;
-                fl[0] = cx * sc; fl[1] = cy * sc; fl[2] = cz * sc;
-            }
-            unsigned q1[6], q2[6], l1[3], l2[3];
-            for (int k = 0; k < 6; ++k) split(fq[k], q1[k], q2[k]);
-            for (int k = 0; k < 3; ++k) split(fl[k], l1[k], l2[k]);
-            // k' s^2 = 2^15 k1 + 2^4 k2, the remainder rounded UP (a larger k' only widens the filter)
-            const _Float16 k1 = (_Float16)(float)(kx / 32768.0);
-            const double rem = (kx - 32768.0 * (double)(float)k1) / 16.0;
-            _Float16 k2 = (_Float16)(float)rem;
-            if ((double)(float)k2 < rem) { unsigned short b; memcpy(&b, &k2, 2); b = (unsigned short)((float)k2 >= 0.0f ? b + 1 : b - 1); memcpy(&k2, &b, 2); }
-            unsigned short kb1, kb2;
-            memcpy(&kb1, &k1, 2); memcpy(&kb2, &k2, 2);
-            auto pk = [](unsigned lo, unsigned hi) { return (lo & 0xffffu) | (hi << 16); };
-            // sphere pieces per slot (rtw_device.hpp): a feature's three slots are (1, 2, 1) against the ray's (1, 1, 2)
-            uint4 m1, m2;
-            if (H == 0) {
-                m1 = uint4{pk(q1[0], q2[0]), pk(q1[0], q1[1]), pk(q2[1], q1[1]), pk(q1[2], q2[2])};      // xx xx | xx yy | yy yy | zz zz
-                m2 = uint4{pk(q2[5], q1[5]), pk(l1[0], l2[0]), pk(l1[0], l1[1]), pk(l2[1], l1[1])};      // yz yz | px px | px py | py py
-            } else {
-                m1 = uint4{pk(q1[2], q1[3]), pk(q2[3], q1[3]), pk(q1[4], q2[4]), pk(q1[4], q1[5])};      // zz xy | xy xy | xz xz | xz yz
-                m2 = uint4{pk(l1[2], l2[2]), pk(l1[2], kb1), pk(kb2, 0x7800u), 0x4c004c00u};             // pz pz | pz k | k T | T T
-            }
+            MfmaSphereRow row;
+            if (in_filter(sph)) mfma_sphere_row(true, (double)(float)geom[sph].x, (double)(float)geom[sph].y, (double)(float)geom[sph].z, (double)geom[sph].w, S, &row);
+            else mfma_sphere_row(false, 0, 0, 0, 0, S, &row);
+            uint32_t w1[4], w2[4];
+            mfma_sphere_words(row, H, w1, w2);
+            const uint4 m1 = {w1[0], w1[1], w1[2], w1[3]}, m2 = {w2[0], w2[1], w2[2], w2[3]};
             ops[(size_t)blk * 128 + lane] = m1;
             ops[(size_t)blk * 128 + 64 + lane] = m2;
         }
     HIP_TRY(hipMalloc(ops_out, ops.size() * sizeof(uint4)));
     HIP_TRY(hipMemcpy(*ops_out, ops.data(), ops.size() * sizeof(uint4), hipMemcpyHostToDevice));
     *blocks_out = nb;
-    h->mf_sc = (float)sc; h->mf_sigma2 = (float)sig2;
-    float keep = (float)(1.0 - 1.02 * 2 * A_S);
-    if ((double)keep > 1.0 - 1.02 * 2 * A_S) keep = std::nextafter(keep, 0.0f);
-    h->mf_oo_keep = keep;
-    float coef = (float)(1.02 * 9 * phi_c);
-    if ((double)coef < 1.02 * 9 * phi_c) coef = std::nextafter(coef, INFINITY);
-    h->mf_o1_coef = coef;
-    h->mf_o_max = (float)(std::ldexp(1.0, 13) / sc);
+    h->mf_sc = (float)S.sc; h->mf_sigma2 = (float)S.sig2;
+    h->mf_oo_keep = S.keep; h->mf_o1_coef = S.coef; h->mf_o_max = S.o_max; h->mf_mr = S.mr;
     return 0;
 }
 

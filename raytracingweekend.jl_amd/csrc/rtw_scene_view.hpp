@@ -33,7 +33,7 @@ rtw::DevScene<T> dev_scene_of(const rtw_scene_dev *h) {
     S.scan = (const float *)(h->scan ? h->scan : h->geom);
     S.n = h->n; S.n_pad = h->n_pad;
     S.mf_ops = (const uint4 *)h->mf_ops; S.mf_blocks = h->mf_blocks;
-    S.mf_sc = h->mf_sc; S.mf_sigma2 = h->mf_sigma2; S.mf_oo_keep = h->mf_oo_keep; S.mf_o1_coef = h->mf_o1_coef; S.mf_o_max = h->mf_o_max;
+    S.mf_sc = h->mf_sc; S.mf_sigma2 = h->mf_sigma2; S.mf_oo_keep = h->mf_oo_keep; S.mf_o1_coef = h->mf_o1_coef; S.mf_o_max = h->mf_o_max; S.mf_mr = h->mf_mr;
     S.n_huge = h->mf_ops ? h->n_huge : 0; S.huge[0] = h->huge[0]; S.huge[1] = h->huge[1];
     return S;
 }

@@ -10,7 +10,9 @@ per wave-iteration (the event counters of the phase-profile build), against the 
   comments); blocks that show only inlined helper code (rtw_path.hpp: generator, reject_trial, normalize ...) inherit the phase of the block
   before them in layout order.  Exec-masked code counts in full (a VALU instruction issues whatever its mask); blocks behind an
   s_cbranch_execz are counted as executed -- the budget is an upper estimate where a whole wave skips a branch.
-* counts.txt: the `[rtw phase counts]` line of a run with RTW_ENABLE_TEST_AIDS=1 RTW_PHASE_PROFILE=1 (tools/gpu_valu_budget.sh writes it)."""
+* counts.txt: the `[rtw phase counts]` line of a run with RTW_ENABLE_TEST_AIDS=1 RTW_PHASE_PROFILE=1 (tools/gpu_valu_budget.sh writes it).
+Counters the table does not multiply by, printed on the same line: half_blocks (cell 30: half blocks evaluated, two per visited block in the plain scan)
+and half_blocks_settled_coarse (cell 31: those the first MFMA of the pair settled -- the two-stage evaluation of rtw_scan_mfma.hpp; their ratio is its f)."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "raytracingweekend.jl_amd", "csrc")
