@@ -179,7 +179,7 @@ int validate_batch(const void *cams, int32_t n_views, const rtw_params *p, const
     return 0;
 }
 
-template <typename CamT>
+template <typename T, typename CamT>
 int render_device_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, void *stream_v) {
     if (int rc = validate_batch(cams, n_views, p, d_out)) return rc;
     if (!scene) return fail(-1, "null scene handle");
@@ -187,19 +187,19 @@ int render_device_batch(rtw_scene_handle scene, const CamT *cams, int32_t n_view
     RenderRec *rec = nullptr;
     CtxPtr ctx;
     release_last();
-    int rc = launch_render_t(scene, cams, n_views, seeds, p, d_out, (hipStream_t)stream_v, &rec, &ctx);
+    int rc = launch_render<T>(scene, cams, n_views, seeds, p, d_out, (hipStream_t)stream_v, &rec, &ctx);
     hold_last(rec, ctx);               // (also on a late error: released by the next call)
     return rc;
 }
 
-template <typename CamT>
+template <typename T, typename CamT>
 int render_device(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, void *d_out, void *stream_v) {
     DeviceGuard guard;
     if (p && p->n_devices > 1) return fail(-2, "the device-resident entry point renders on the scene's device only (n_devices = %d)", p->n_devices);
     RenderRec *rec = nullptr;
     CtxPtr ctx;
     release_last();
-    int rc = launch_render_t(scene, cam, 0, nullptr, p, d_out, (hipStream_t)stream_v, &rec, &ctx);
+    int rc = launch_render<T>(scene, cam, 0, nullptr, p, d_out, (hipStream_t)stream_v, &rec, &ctx);
     hold_last(rec, ctx);               // (also on a late error: released by the next call)
     return rc;
 }
@@ -223,8 +223,8 @@ int rtw_device_count(int *count) {
 
 const char *rtw_last_error(void) { return g_err; }
 
-int rtw_scene_upload_f32(const rtw_scene_f32 *s, int device, rtw_scene_handle *out) { return upload_scene_f32(s, device, out); }
-int rtw_scene_upload_f64(const rtw_scene_f64 *s, int device, rtw_scene_handle *out) { return upload_scene_f64(s, device, out); }
+int rtw_scene_upload_f32(const rtw_scene_f32 *s, int device, rtw_scene_handle *out) { return upload_scene<float>(s, device, out); }
+int rtw_scene_upload_f64(const rtw_scene_f64 *s, int device, rtw_scene_handle *out) { return upload_scene<double>(s, device, out); }
 
 int rtw_scene_free(rtw_scene_handle h) {
     if (!h) return 0;
@@ -239,16 +239,16 @@ int rtw_scene_free(rtw_scene_handle h) {
 }
 
 int rtw_render_device_f32(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, void *d_out, void *stream) {
-    return render_device(s, c, p, d_out, stream);
+    return render_device<float>(s, c, p, d_out, stream);
 }
 int rtw_render_device_f64(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, void *d_out, void *stream) {
-    return render_device(s, c, p, d_out, stream);
+    return render_device<double>(s, c, p, d_out, stream);
 }
 int rtw_render_batch_device_f32(rtw_scene_handle s, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, void *stream) {
-    return render_device_batch(s, cams, n_views, seeds, p, d_out, stream);
+    return render_device_batch<float>(s, cams, n_views, seeds, p, d_out, stream);
 }
 int rtw_render_batch_device_f64(rtw_scene_handle s, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, void *stream) {
-    return render_device_batch(s, cams, n_views, seeds, p, d_out, stream);
+    return render_device_batch<double>(s, cams, n_views, seeds, p, d_out, stream);
 }
 
 int rtw_stats(rtw_stats_t *out) {
@@ -285,10 +285,10 @@ int rtw_stats_devices(int32_t capacity, int32_t *count, int32_t *devices, double
 }
 
 int rtw_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene, const rtw_camera_f32 *cam) {
-    return run_unit_f32(op, count, in, out, scene, cam);
+    return run_unit<float>(op, count, in, out, scene, cam);
 }
 int rtw_unit_f64(int op, int count, const void *in, void *out, const rtw_scene_f64 *scene, const rtw_camera_f64 *cam) {
-    return run_unit_f64(op, count, in, out, scene, cam);
+    return run_unit<double>(op, count, in, out, scene, cam);
 }
 
 int rtw_shutdown(void) {

@@ -198,7 +198,7 @@ int accum_pass(bool single, rtw_scene_handle scene, const CamT *cams, int32_t n_
     RenderRec *rec = nullptr;
     CtxPtr ctx;
     release_last();
-    int rc = launch_render_t(scene, cams, single ? 0 : n_views, seeds, p, d_out, stream, &rec, &ctx, &pass);
+    int rc = launch_render<CamElem<CamT>>(scene, cams, single ? 0 : n_views, seeds, p, d_out, stream, &rec, &ctx, &pass);
     hold_last(rec, ctx);               // (also on a late error: released by the next call)
     if (rc) return rc;
     for (int32_t v = 0; v < n_views; ++v) {
@@ -331,7 +331,7 @@ int adaptive_loop(bool single, rtw_scene_handle scene, const CamT *cams, int32_t
         AccumPass ps;
         ps.words = single ? a0->words : nullptr; ps.chunk_begin = begin; ps.chunk_count = count; ps.samples = 1;
         ps.adapt = true; ps.tile_list = list; ps.list_tiles = n_list; ps.views = single ? nullptr : views.data();
-        int rc = launch_render_t(scene, cams, single ? 0 : n_views, seeds, p, nullptr, stream, &rec, &ctx, &ps);
+        int rc = launch_render<CamElem<CamT>>(scene, cams, single ? 0 : n_views, seeds, p, nullptr, stream, &rec, &ctx, &ps);
         if (rc) { hold_last(rec, ctx); rec = nullptr; return rc; }     // (released by the next call)
         (void)hipGetLastError();
         if (single) launch_tile_advance(stream, list, n_list, a0->d_tiles, count);
@@ -536,8 +536,8 @@ int enqueue_accum_features(rtw_scene_handle scene, const CamT *cam, const rtw_pa
     HIP_TRY(hipSetDevice(a->device));
     if (int rc = wait_for(a, stream)) return rc;
     int rc;
-    if (a->adaptive) rc = launch_features_t(scene, cam, 0, nullptr, p, 0, 1, d_out, stream, rec, ctx, a->d_tiles);
-    else rc = launch_features_t(scene, cam, 0, nullptr, p, a->ranges[0].first, a->ranges[0].second - a->ranges[0].first, d_out, stream, rec, ctx);
+    if (a->adaptive) rc = launch_features<CamElem<CamT>>(scene, cam, 0, nullptr, p, 0, 1, d_out, stream, rec, ctx, a->d_tiles);
+    else rc = launch_features<CamElem<CamT>>(scene, cam, 0, nullptr, p, a->ranges[0].first, a->ranges[0].second - a->ranges[0].first, d_out, stream, rec, ctx);
     if (rc) return rc;
     return mark(a, stream);
 }
@@ -691,8 +691,8 @@ int enqueue_accum_features_batch(rtw_scene_handle scene, const CamT *cams, int32
     if (a0->adaptive) {
         std::vector<const int *> tiles((size_t)n_views);
         for (int32_t v = 0; v < n_views; ++v) tiles[(size_t)v] = accums[v]->d_tiles;
-        rc = launch_features_t(scene, cams, n_views, seeds, p, 0, 1, d_out, stream, rec, ctx, nullptr, tiles.data());
-    } else rc = launch_features_t(scene, cams, n_views, seeds, p, a0->ranges[0].first, a0->ranges[0].second - a0->ranges[0].first, d_out, stream, rec, ctx);
+        rc = launch_features<CamElem<CamT>>(scene, cams, n_views, seeds, p, 0, 1, d_out, stream, rec, ctx, nullptr, tiles.data());
+    } else rc = launch_features<CamElem<CamT>>(scene, cams, n_views, seeds, p, a0->ranges[0].first, a0->ranges[0].second - a0->ranges[0].first, d_out, stream, rec, ctx);
     if (rc) return rc;
     return mark_all(accums, n_views, stream);
 }

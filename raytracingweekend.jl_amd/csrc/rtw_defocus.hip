@@ -21,16 +21,14 @@ static void defocus_constants(const rtw_defocus_t *b, const CamT *cam, int32_t w
 
 // One view's entry of the lens table (include/rtw_hip.h rtw_lens_table_*: 32 elements): [0, 29) the reprojection table's entry of the camera
 // as its own previous one (so that element 15.. is its w), 29: F = T(focus), 30: K rounded to T, 31: 0.  The ONE copy of this arithmetic:
-// launch_prepare's own constants and rtw_lens_table_* both come from here.
+// launch_defocus_prepare's own constants and rtw_lens_table_* both come from here.
 template <typename T, typename CamT>
 void lens_table_entry(const rtw_defocus_t *b, const CamT *cam, int32_t width, T *e) {
     double hh, focus, K;
     defocus_constants(b, cam, width, &hh, &focus, &K);
-    temporal_table_t(cam, cam, 1, e);
+    temporal_table<T>(cam, cam, 1, e);
     e[29] = (T)focus; e[30] = (T)K; e[31] = T(0);
 }
-void lens_table_entry_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, float *e) { lens_table_entry<float>(b, cam, width, e); }
-void lens_table_entry_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, double *e) { lens_table_entry<double>(b, cam, width, e); }
 
 // Everything about a lens stage that is decided without a device and without a pointer, in four parts, in the order every entry point of
 // the family applies them.  1: the parameters -- max_radius against the stage's `top` (8: the defocus stage, 32: the wide-aperture stage and
@@ -65,15 +63,13 @@ static int check_lens_camera(const rtw_defocus_t *b, const CamT *cam, int32_t wi
     return 0;
 }
 template <typename CamT>
-static int validate_lens_t(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, int elem_bytes, int top) {
+int validate_lens(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, int top) {
     if (!b || !cam) return fail(-1, "null lens parameters or camera");
     if (int rc = check_lens_params(b, top)) return rc;
     if (int rc = check_lens_values(b)) return rc;
-    if (int rc = check_lens_frame(width, height, elem_bytes)) return rc;
+    if (int rc = check_lens_frame(width, height, (int)sizeof(cam->origin[0]))) return rc;
     return check_lens_camera(b, cam, width);
 }
-int validate_lens(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, int top) { return validate_lens_t(b, cam, width, height, 4, top); }
-int validate_lens(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, int top) { return validate_lens_t(b, cam, width, height, 8, top); }
 
 static_assert(rtw::DF_TILE == 16, "rtw_layout.hpp WideApertureLayout::tiles counts the kernels' 16 x 16 tiles");
 
@@ -83,14 +79,14 @@ dim3 lens_views_grid(unsigned tiles, int32_t n_views) {
     return dim3(tiles, nv < rtw::DF_VIEWS_Y ? nv : rtw::DF_VIEWS_Y, (nv + rtw::DF_VIEWS_Y - 1) / rtw::DF_VIEWS_Y);
 }
 
-// The stage's two launches one by one (launch_defocus below; rtw_wide_aperture.hip composes them): the prepare launch with the clamp `rm`
+// The stage's two launches one by one (launch_defocus below; rtw_wide_aperture.hip composes them): launch_defocus_prepare, the prepare launch with the clamp `rm`
 // over the image and the features into a CoC plane and its tile plane ...
 // n_views == 0: ONE view, the constants from b and cam.  n_views >= 1 (rtw_lens_batch_device_*): that many views in the SAME single
-// launch -- b and cam are unused, view v takes its constants from entry v of the DEVICE table d_table (lens_table_*) and finds its image,
+// launch -- b and cam are unused, view v takes its constants from entry v of the DEVICE table d_table (lens_table) and finds its image,
 // features, CoC plane and tile plane v * strides[0..3] bytes behind the pointers.
 template <typename T, typename CamT>
-int launch_prepare(const rtw_defocus_t *b, int rm, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream,
-                   int32_t n_views, const void *d_table, const long long *strides) {
+int launch_defocus_prepare(const rtw_defocus_t *b, int rm, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream,
+                           int32_t n_views, const void *d_table, const long long *strides) {
     using V = typename rtw::DnVec<T>::type;
     const unsigned tiles = (unsigned)WideApertureLayout::tiles(width, height);                 // (fewer than the frame rule's 8 x 8 ones: one 32-bit grid dimension holds them)
     rtw::TpParams<T> U;
@@ -117,11 +113,11 @@ int launch_prepare(const rtw_defocus_t *b, int rm, const CamT *cam, int32_t widt
     HIP_TRY(hipGetLastError());
     return 0;
 }
-// ... and the gather of a frame of any size over its image, CoC plane and tile plane; mmax >= every radius of the plane, at most 8.
+// ... and launch_defocus_gather, the gather of a frame of any size over its image, CoC plane and tile plane; mmax >= every radius of the plane, at most 8.
 // n_views >= 1: that many frames in the same single launch, image, CoC plane, tile plane and output of view v at v * strides[0..3] bytes.
 template <typename T>
-int launch_gather(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream, int32_t n_views,
-                  const long long *strides) {
+int launch_defocus_gather(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream, int32_t n_views,
+                          const long long *strides) {
     using V = typename rtw::DnVec<T>::type;
     const unsigned tiles = (unsigned)WideApertureLayout::tiles(width, height);
     rtw::DfDist<T> tab;
@@ -142,10 +138,6 @@ int launch_gather(int32_t width, int32_t height, int mmax, int gamma, const void
     HIP_TRY(hipGetLastError());
     return 0;
 }
-int launch_defocus_prepare_f32(const rtw_defocus_t *b, int rm, const rtw_camera_f32 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st, int32_t nv, const void *tab, const long long *strides) { return launch_prepare<float>(b, rm, cam, w, h, img, feat, coc, tile, st, nv, tab, strides); }
-int launch_defocus_prepare_f64(const rtw_defocus_t *b, int rm, const rtw_camera_f64 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st, int32_t nv, const void *tab, const long long *strides) { return launch_prepare<double>(b, rm, cam, w, h, img, feat, coc, tile, st, nv, tab, strides); }
-int launch_defocus_gather_f32(int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st, int32_t nv, const long long *strides) { return launch_gather<float>(w, h, mmax, gamma, img, coc, tile, out, st, nv, strides); }
-int launch_defocus_gather_f64(int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st, int32_t nv, const long long *strides) { return launch_gather<double>(w, h, mmax, gamma, img, coc, tile, out, st, nv, strides); }
 
 // Enqueue the stage on `stream` of the current device (validate_lens has accepted the call): TWO launches, no record.
 // vb null: one view.  vb given (rtw_lens_batch_device_* with max_radius <= 8): vb->n_views views in the same two launches -- cam and
@@ -161,25 +153,32 @@ int launch_defocus(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32
     const long long sg[4] = {sp[0], sp[2], sp[2], vb ? vb->out_stride : 0};
     // (measurement aid, tools/gpu_defocus.py: events around every launch, reported on stderr -- this one blocks)
     static const bool profile = aid_flag("RTW_TEMPORAL_PROFILE");
-    struct Events { hipEvent_t e[3] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
-    if (profile) { for (hipEvent_t &x : events.e) HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventRecord(events.e[0], stream)); }
-    if (int rc = launch_prepare<T>(b, b->max_radius, cam, width, height, d_image, d_features, coc, tile, stream, nv, vb ? vb->d_table : nullptr, sp)) return rc;
-    if (profile) HIP_TRY(hipEventRecord(events.e[1], stream));
-    if (int rc = launch_gather<T>(width, height, b->max_radius, b->gamma, d_image, coc, tile, d_out, stream, nv, sg)) return rc;
+    StageMarks marks(profile, stream);
+    HIP_TRY(marks.mark());
+    if (int rc = launch_defocus_prepare<T>(b, b->max_radius, cam, width, height, d_image, d_features, coc, tile, stream, nv, vb ? vb->d_table : nullptr, sp)) return rc;
+    HIP_TRY(marks.mark());
+    if (int rc = launch_defocus_gather<T>(width, height, b->max_radius, b->gamma, d_image, coc, tile, d_out, stream, nv, sg)) return rc;
     if (profile) {
-        float ms[2] = {0, 0};
+        const float *ms = marks.ms;
         char views[32] = "";
         if (nv) snprintf(views, sizeof views, " n_views=%d", nv);
-        HIP_TRY(hipEventRecord(events.e[2], stream));
-        HIP_TRY(hipEventSynchronize(events.e[2]));
-        for (int k = 0; k < 2; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], events.e[k], events.e[k + 1]));
+        HIP_TRY(marks.mark());
+        HIP_TRY(marks.measure());
         fprintf(stderr, "[rtw defocus] %s %dx%d max_radius=%d%s prepare_ms=%.5f gather_ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, b->max_radius, views, ms[0], ms[1]);
     }
     return 0;
 }
 
-int launch_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb) { return launch_defocus<float>(b, cam, w, h, img, feat, work, out, st, vb); }
-int launch_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb) { return launch_defocus<double>(b, cam, w, h, img, feat, work, out, st, vb); }
+template void lens_table_entry<float>(const rtw_defocus_t *, const rtw_camera_f32 *, int32_t, float *);
+template void lens_table_entry<double>(const rtw_defocus_t *, const rtw_camera_f64 *, int32_t, double *);
+template int validate_lens(const rtw_defocus_t *, const rtw_camera_f32 *, int32_t, int32_t, int);
+template int validate_lens(const rtw_defocus_t *, const rtw_camera_f64 *, int32_t, int32_t, int);
+template int launch_defocus_prepare<float>(const rtw_defocus_t *, int, const rtw_camera_f32 *, int32_t, int32_t, const void *, const void *, void *, void *, hipStream_t, int32_t, const void *, const long long *);
+template int launch_defocus_prepare<double>(const rtw_defocus_t *, int, const rtw_camera_f64 *, int32_t, int32_t, const void *, const void *, void *, void *, hipStream_t, int32_t, const void *, const long long *);
+template int launch_defocus_gather<float>(int32_t, int32_t, int, int, const void *, const void *, const void *, void *, hipStream_t, int32_t, const long long *);
+template int launch_defocus_gather<double>(int32_t, int32_t, int, int, const void *, const void *, const void *, void *, hipStream_t, int32_t, const long long *);
+template int launch_defocus<float>(const rtw_defocus_t *, const rtw_camera_f32 *, int32_t, int32_t, const void *, const void *, void *, void *, hipStream_t, const LensViews *);
+template int launch_defocus<double>(const rtw_defocus_t *, const rtw_camera_f64 *, int32_t, int32_t, const void *, const void *, void *, void *, hipStream_t, const LensViews *);
 
 }  // namespace rtwh
 

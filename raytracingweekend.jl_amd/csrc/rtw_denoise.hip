@@ -51,16 +51,14 @@ int launch_denoise(const rtw_denoise_t *d, int32_t width, int32_t height, int n_
     const unsigned grid = (unsigned)((n_pix + 255) / 256);
     // (measurement aid, tools/gpu_denoise.py: events around every kernel, reported on stderr -- this one blocks)
     static const bool profile = aid_flag("RTW_DENOISE_PROFILE");
-    struct Events { hipEvent_t e[10] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
-    hipEvent_t *ev = events.e;
-    if (profile) for (int k = 0; k <= d->levels + 1; ++k) HIP_TRY(hipEventCreate(&ev[k]));
-    if (profile) HIP_TRY(hipEventRecord(ev[0], stream));
+    StageMarks marks(profile, stream);
+    HIP_TRY(marks.mark());
     (void)hipGetLastError();
     const bool guided = d_noise != nullptr;
     if (guided) hipLaunchKernelGGL((rtw::dn_prepare<T, true>), dim3(grid), dim3(256), 0, stream, (const T *)d_image, (const V *)d_features, E[0], G, A, n_pix, demod ? 1 : 0, (const T *)d_noise);
     else hipLaunchKernelGGL((rtw::dn_prepare<T, false>), dim3(grid), dim3(256), 0, stream, (const T *)d_image, (const V *)d_features, E[0], G, A, n_pix, demod ? 1 : 0, (const T *)nullptr);
     HIP_TRY(hipGetLastError());
-    if (profile) HIP_TRY(hipEventRecord(ev[1], stream));
+    HIP_TRY(marks.mark());
     for (int k = 0; k < d->levels; ++k) {
         rtw::DnLevel<T> L;
         const double sc = d->sigma_color * std::ldexp(1.0, -k);
@@ -79,29 +77,22 @@ int launch_denoise(const rtw_denoise_t *d, int32_t width, int32_t height, int n_
         } else if (guided) hipLaunchKernelGGL((rtw::dn_level<T, true>), dim3(grid), dim3(256), 0, stream, L, in, (const V *)G, (const V *)A, next, (T *)d_out);
         else hipLaunchKernelGGL((rtw::dn_level<T, false>), dim3(grid), dim3(256), 0, stream, L, in, (const V *)G, (const V *)A, next, (T *)d_out);
         HIP_TRY(hipGetLastError());
-        if (profile) HIP_TRY(hipEventRecord(ev[k + 2], stream));
+        HIP_TRY(marks.mark());
     }
     if (profile) {
         const char *tag = guided ? "rtw denoise guided" : "rtw denoise";       // (tools/gpu_accum_denoise.py tells the two forms apart by it)
         char views[32] = "";                                                    // (a batched filter: " views=N" behind the frame's size)
         if (batch) snprintf(views, sizeof views, " views=%d", n_views);
-        HIP_TRY(hipEventSynchronize(ev[d->levels + 1]));
+        HIP_TRY(marks.measure());
         for (int k = 0; k <= d->levels; ++k) {
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-            if (k == 0) fprintf(stderr, "[%s] %s %dx%d%s prepare ms=%.5f\n", tag, sizeof(T) == 8 ? "f64" : "f32", width, height, views, ms);
+            if (k == 0) fprintf(stderr, "[%s] %s %dx%d%s prepare ms=%.5f\n", tag, sizeof(T) == 8 ? "f64" : "f32", width, height, views, marks.ms[k]);
             else fprintf(stderr, "[%s] %s %dx%d%s level step=%d final=%d ms=%.5f\n", tag, sizeof(T) == 8 ? "f64" : "f32", width, height, views, 1 << (k - 1),
-                         (int)(k == d->levels), ms);
+                         (int)(k == d->levels), marks.ms[k]);
         }
-        float all_ms = 0;
-        HIP_TRY(hipEventElapsedTime(&all_ms, ev[0], ev[d->levels + 1]));
-        fprintf(stderr, "[%s] %s %dx%d%s total levels=%d ms=%.5f\n", tag, sizeof(T) == 8 ? "f64" : "f32", width, height, views, d->levels, all_ms);
+        fprintf(stderr, "[%s] %s %dx%d%s total levels=%d ms=%.5f\n", tag, sizeof(T) == 8 ? "f64" : "f32", width, height, views, d->levels, marks.total_ms);
     }
     return 0;
 }
-
-int launch_denoise_f32(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t n_views, const void *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise) { return launch_denoise<float>(d, w, h, n_views, img, feat, out, work, st, noise); }
-int launch_denoise_f64(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t n_views, const void *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise) { return launch_denoise<double>(d, w, h, n_views, img, feat, out, work, st, noise); }
 
 // A batched filter call (rtw_filter_batch_*): validate_denoise for the frame, and a batch whose pixels the launches can number (256 per workgroup)
 int validate_filter_batch(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views) {
@@ -134,6 +125,9 @@ int denoise_device(const rtw_denoise_t *d, int32_t width, int32_t height, int32_
     if (d->device >= 0) HIP_TRY(hipSetDevice(d->device));
     return launch_denoise<T>(d, width, height, n_views, d_image, d_features, d_out, d_work, (hipStream_t)stream_v, guided ? d_noise : nullptr);
 }
+
+template int launch_denoise<float>(const rtw_denoise_t *, int32_t, int32_t, int32_t, const void *, const void *, void *, void *, hipStream_t, const void *);
+template int launch_denoise<double>(const rtw_denoise_t *, int32_t, int32_t, int32_t, const void *, const void *, void *, void *, hipStream_t, const void *);
 
 }  // namespace rtwh
 

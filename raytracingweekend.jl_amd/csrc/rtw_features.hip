@@ -48,8 +48,6 @@ int validate_features_batch(const void *cams, int32_t n_views, const rtw_params 
 // points to, `seeds` (null: p->seed for every view) and n_views buffers behind d_out; the views go up with the record (upload_views).
 // view_tiles non-null (n_views >= 1 only; rtw_accum_features_batch_* on adaptive accumulators): a HOST array of n_views device pointers, the
 // accumulators' tile-chunk arrays -- ONE launch of a TILED && BATCH instance (rtw_features_accum_batch_f32.hip / _f64.hip), the table goes up with the views.
-inline int upload_views_t(RenderRec *r, const rtw_camera_f32 *c, int n, const uint64_t *sd, uint64_t s, hipStream_t st, const void **dc, const unsigned long long **ds, const int *const *t, const int *const **dt) { return upload_views_f32(r, c, n, sd, s, st, dc, ds, t, dt); }
-inline int upload_views_t(RenderRec *r, const rtw_camera_f64 *c, int n, const uint64_t *sd, uint64_t s, hipStream_t st, const void **dc, const unsigned long long **ds, const int *const *t, const int *const **dt) { return upload_views_f64(r, c, n, sd, s, st, dc, ds, t, dt); }
 template <typename T> const void *features_tiled_batch_kernel(bool mfma, bool lds_scene, bool fixed);
 template <> const void *features_tiled_batch_kernel<float>(bool mfma, bool lds_scene, bool fixed) { return features_tiled_batch_kernel_f32(mfma, lds_scene, fixed); }
 template <> const void *features_tiled_batch_kernel<double>(bool mfma, bool lds_scene, bool fixed) { return features_tiled_batch_kernel_f64(mfma, lds_scene, fixed); }
@@ -122,7 +120,7 @@ int launch_features(rtw_scene_handle scene, const CamT *cam, int n_views, const 
     memset(&FV, 0, sizeof FV);
     if (batch) {
         const void *d_cams = nullptr;
-        if (int rc = upload_views_t(*rec_out, cam, n_views, seeds, p->seed, stream, &d_cams, &FV.seeds, view_tiles, &FV.chunks)) return rc;
+        if (int rc = upload_views<T>(*rec_out, cam, n_views, seeds, p->seed, stream, &d_cams, &FV.seeds, view_tiles, &FV.chunks)) return rc;
         FV.cams = (const rtw::Camera<T> *)d_cams;
         FV.total_tiles = total_tiles;
         FV.view_elems = (unsigned long long)p->width * (unsigned long long)p->height * RTW_FEATURE_CHANNELS;
@@ -132,17 +130,8 @@ int launch_features(rtw_scene_handle scene, const CamT *cam, int n_views, const 
     return run_record(*rec_out, stream, [&] { (void)hipLaunchKernel(kern, dim3(grid), dim3(64 * RTW_FEATURE_WAVES), args, lds_bytes, stream); });
 }
 
-int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out,
-                        hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks, const int *const *view_tiles) {
-    return launch_features<float>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks, view_tiles);
-}
-int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out,
-                        hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks, const int *const *view_tiles) {
-    return launch_features<double>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, stream, rec_out, ctx_out, d_tile_chunks, view_tiles);
-}
-
 // The device-resident entry points rtw_render_features_device_* (n_views == 0) and rtw_render_features_batch_device_* (n_views != 0).
-template <typename CamT>
+template <typename T, typename CamT>
 int features_device(rtw_scene_handle scene, const CamT *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out,
                     void *stream_v) {
     if (!p) return fail(-1, "null params");
@@ -154,10 +143,13 @@ int features_device(rtw_scene_handle scene, const CamT *cams, int32_t n_views, c
     RenderRec *rec = nullptr;
     CtxPtr ctx;
     release_last();
-    int rc = launch_features_t(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, (hipStream_t)stream_v, &rec, &ctx);
+    int rc = launch_features<T>(scene, cams, n_views, seeds, p, chunk_begin, chunk_count, d_out, (hipStream_t)stream_v, &rec, &ctx);
     hold_last(rec, ctx);               // (also on a late error: released by the next call)
     return rc;
 }
+
+template int launch_features<float>(rtw_scene_handle, const rtw_camera_f32 *, int, const uint64_t *, const rtw_params *, int32_t, int32_t, void *, hipStream_t, RenderRec **, CtxPtr *, const int *, const int *const *);
+template int launch_features<double>(rtw_scene_handle, const rtw_camera_f64 *, int, const uint64_t *, const rtw_params *, int32_t, int32_t, void *, hipStream_t, RenderRec **, CtxPtr *, const int *, const int *const *);
 
 }  // namespace rtwh
 
@@ -166,18 +158,18 @@ using namespace rtwh;
 extern "C" {
 
 int rtw_render_features_device_f32(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, void *stream) {
-    return features_device(s, c, 0, nullptr, p, chunk_begin, chunk_count, d_out, stream);
+    return features_device<float>(s, c, 0, nullptr, p, chunk_begin, chunk_count, d_out, stream);
 }
 int rtw_render_features_device_f64(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, void *stream) {
-    return features_device(s, c, 0, nullptr, p, chunk_begin, chunk_count, d_out, stream);
+    return features_device<double>(s, c, 0, nullptr, p, chunk_begin, chunk_count, d_out, stream);
 }
 int rtw_render_features_batch_device_f32(rtw_scene_handle s, const rtw_camera_f32 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin,
                                          int32_t chunk_count, void *d_out, void *stream) {
-    return features_device(s, cams, batch_views(n_views), seeds, p, chunk_begin, chunk_count, d_out, stream);
+    return features_device<float>(s, cams, batch_views(n_views), seeds, p, chunk_begin, chunk_count, d_out, stream);
 }
 int rtw_render_features_batch_device_f64(rtw_scene_handle s, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin,
                                          int32_t chunk_count, void *d_out, void *stream) {
-    return features_device(s, cams, batch_views(n_views), seeds, p, chunk_begin, chunk_count, d_out, stream);
+    return features_device<double>(s, cams, batch_views(n_views), seeds, p, chunk_begin, chunk_count, d_out, stream);
 }
 
 }  // extern "C"

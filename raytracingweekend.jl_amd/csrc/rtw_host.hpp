@@ -24,6 +24,16 @@
 //   rtw_wide_aperture.hip  the wide-aperture stage (circles of confusion up to 32 px): the six launches (the defocus stage's kernels at two sizes, rtw_wide_aperture.hpp between and behind them) for one view or a batch of views, the checks of N views, the lens table, ONE device-resident entry point (lens_device) behind the defocus, wide-aperture and batched ones
 //   rtw_present.hip      the present stage: its checks, the one launch of its kernel (rtw_present.hpp) for one frame or a batch, the device-resident entry points
 //   (rtw_scene_view.hpp: what both launch functions derive from their arguments; rtw_instances.hpp: the one table of the trace kernel's instances)
+// A function that exists once per precision and crosses units is declared here ONCE, as a template under its own name, and the unit that
+// defines it ends with its two explicit instantiations (float with rtw_camera_f32 / rtw_scene_f32, double with the _f64 structs); a caller
+// names the precision it has -- launch_temporal<T>(...) -- and the struct types are deduced.  Declared in this form:
+//   rtw_scene.hip upload_scene; rtw_launch.hip launch_render, upload_views; rtw_features.hip launch_features; rtw_denoise.hip launch_denoise;
+//   rtw_upsample.hip launch_upsample; rtw_temporal.hip launch_temporal, temporal_table, launch_temporal_noise; rtw_motion.hip launch_motion,
+//   motion_table; rtw_motion_blur.hip launch_motion_blur; rtw_defocus.hip validate_lens, launch_defocus, launch_defocus_prepare,
+//   launch_defocus_gather, lens_table_entry; rtw_wide_aperture.hip launch_wide_aperture, validate_lens_batch, lens_table; rtw_present.hip
+//   launch_present; rtw_unit.hip run_unit; rtw_accum.hip validate_ / enqueue_accum_features and their _batch forms (on the camera alone).
+// Not in this form: batch_accum_kernel_f32 / _f64 and features_tiled_batch_kernel_f32 / _f64, each half in a unit of its own so that the heavy
+// trace instances compile in parallel.  StageMarks (below) is the one measurement aid of the stages' launch functions.
 // Everything is in namespace rtwh with hidden visibility; the library exports the C ABI only.
 #pragma once
 #pragma GCC visibility push(default)
@@ -118,6 +128,36 @@ bool aid_flag(const char *name);
             (void)hipGetLastError();            /* do not leave it for a later hipGetLastError() check */ \
         }                                                                                     \
     } while (0)
+
+// The measurement aid of the stages (tools/gpu_*.py; RTW_DENOISE_PROFILE, RTW_TEMPORAL_PROFILE, RTW_PRESENT_PROFILE, each read once per
+// process by the launch function that owns the `static const bool` it hands in): events around every launch of a stage.  Off -- the
+// production path -- mark() does nothing and no event is ever created, recorded or destroyed.  On: mark() puts an event on the stream
+// (one in front of the first launch, one behind every launch; at most MAX: the upsampler's `levels` + 3), measure() blocks until the last
+// one has happened and fills ms[k], the time between marks k and k + 1, and total_ms, from the first mark to the last; the launch function
+// prints them.  The events are destroyed on every return path.
+struct StageMarks {
+    static constexpr int MAX = 11;
+    const bool on;
+    const hipStream_t stream;
+    hipEvent_t e[MAX] = {};
+    int n = 0;
+    float ms[MAX - 1] = {}, total_ms = 0;
+    StageMarks(bool on_, hipStream_t stream_) : on(on_), stream(stream_) {}
+    StageMarks(const StageMarks &) = delete;
+    ~StageMarks() { for (int k = 0; k < n; ++k) HIP_IGNORE(hipEventDestroy(e[k])); }
+    hipError_t mark() {
+        if (!on) return hipSuccess;
+        if (n == MAX) return hipErrorInvalidValue;
+        if (hipError_t rc = hipEventCreate(&e[n])) return rc;
+        return hipEventRecord(e[n++], stream);          // (counted before it is recorded: the destructor destroys it either way)
+    }
+    hipError_t measure() {
+        if (n < 2) return hipErrorInvalidValue;
+        if (hipError_t rc = hipEventSynchronize(e[n - 1])) return rc;
+        for (int k = 0; k + 1 < n; ++k) if (hipError_t rc = hipEventElapsedTime(&ms[k], e[k], e[k + 1])) return rc;
+        return hipEventElapsedTime(&total_ms, e[0], e[n - 1]);
+    }
+};
 
 // restores the caller's current device when an entry point returns
 struct DeviceGuard {
@@ -229,14 +269,14 @@ template <typename SceneT> bool s_has_bad_scene(const SceneT *s) {
     return s->n > 0 && (!s->cx || !s->cy || !s->cz || !s->r || !s->kind || !s->ar || !s->ag || !s->ab || !s->param);
 }
 
+// the element type of a camera struct (rtw_camera_f32 / _f64), for a caller that is a template on the camera alone (rtw_accum.hip)
+template <typename CamT> using CamElem = std::remove_extent_t<decltype(CamT::origin)>;
+
 struct SceneDeleter { void operator()(rtw_scene_dev *h) const { rtw_scene_free(h); } };
 using ScenePtr = std::unique_ptr<rtw_scene_dev, SceneDeleter>;
 
 // rtw_scene.hip
-int upload_scene_f32(const rtw_scene_f32 *s, int device, rtw_scene_handle *out);
-int upload_scene_f64(const rtw_scene_f64 *s, int device, rtw_scene_handle *out);
-inline int upload_scene_t(const rtw_scene_f32 *s, int device, rtw_scene_handle *out) { return upload_scene_f32(s, device, out); }
-inline int upload_scene_t(const rtw_scene_f64 *s, int device, rtw_scene_handle *out) { return upload_scene_f64(s, device, out); }
+template <typename T, typename SceneT> int upload_scene(const SceneT *s, int device, rtw_scene_handle *out);
 
 // rtw_launch.hip -- enqueue one render (this shard's tiles) on `stream`; `rec` receives the counters and the kernel's events.
 // n_views == 0: one render of the camera `cams` points to.  n_views >= 1: a batch of that many views (validate_batch first): `cams` /
@@ -249,17 +289,14 @@ inline int upload_scene_t(const rtw_scene_f64 *s, int device, rtw_scene_handle *
 // pass itself are unused), `tile_list` numbers the tiles batch-globally, v * n_tiles + t
 struct AccumViewPass { unsigned long long *words; int samples; };
 struct AccumPass { unsigned long long *words; int chunk_begin, chunk_count, samples; bool adapt = false; const int *tile_list = nullptr; int list_tiles = 0; const AccumViewPass *views = nullptr; };
-int launch_render_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const AccumPass *pass = nullptr);
-int launch_render_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const AccumPass *pass = nullptr);
-inline int launch_render_t(rtw_scene_handle s, const rtw_camera_f32 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const AccumPass *a = nullptr) { return launch_render_f32(s, c, n, sd, p, d, st, r, x, a); }
-inline int launch_render_t(rtw_scene_handle s, const rtw_camera_f64 *c, int n, const uint64_t *sd, const rtw_params *p, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const AccumPass *a = nullptr) { return launch_render_f64(s, c, n, sd, p, d, st, r, x, a); }
+template <typename T, typename CamT>
+int launch_render(rtw_scene_handle scene, const CamT *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const AccumPass *pass = nullptr);
 // a batch's cameras and seeds (null: `seed` for every view) into the record's pinned buffer and, by ONE asynchronous H2D on `stream`, into its
 // device buffer (the upload of launch_render's batches): *d_cams receives the device array of n_views rtw::Camera<T>, *d_seeds that of the seeds.
 // `tiles` non-null: n_views device pointers (the tile-chunk arrays of adaptive accumulators) travel behind them, *d_tiles receives the table's device address
-int upload_views_f32(RenderRec *rec, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds,
-                     const int *const *tiles = nullptr, const int *const **d_tiles = nullptr);
-int upload_views_f64(RenderRec *rec, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds,
-                     const int *const *tiles = nullptr, const int *const **d_tiles = nullptr);
+template <typename T, typename CamT>
+int upload_views(RenderRec *rec, const CamT *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds,
+                 const int *const *tiles = nullptr, const int *const **d_tiles = nullptr);
 int resolve_rec(RenderRec *r, rtw_stats_t *agg);            // wait for a record's kernel and add its counters to `agg`
 // what the kernel-instance table answers (rtw_instances.hpp): the kernel, and whether it has the default numerics mode compiled in
 struct TraceInstance { const void *kern; bool fixed; };
@@ -329,10 +366,8 @@ int validate_features_batch(const void *cams, int32_t n_views, const rtw_params 
 // (device memory, the accumulator's C_t array), the call's own range is validated and otherwise unused.
 // view_tiles non-null (n_views >= 1 only): the same pass for a batch of adaptive accumulators in ONE launch of a TILED && BATCH instance -- a HOST
 // array of n_views such device arrays, tile t of view v gets the chunks [0, view_tiles[v][t]).
-int launch_features_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks = nullptr, const int *const *view_tiles = nullptr);
-int launch_features_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks = nullptr, const int *const *view_tiles = nullptr);
-inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f32 *c, int nv, const uint64_t *sd, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const int *tc = nullptr, const int *const *vt = nullptr) { return launch_features_f32(s, c, nv, sd, p, b, n, d, st, r, x, tc, vt); }
-inline int launch_features_t(rtw_scene_handle s, const rtw_camera_f64 *c, int nv, const uint64_t *sd, const rtw_params *p, int32_t b, int32_t n, void *d, hipStream_t st, RenderRec **r, CtxPtr *x, const int *tc = nullptr, const int *const *vt = nullptr) { return launch_features_f64(s, c, nv, sd, p, b, n, d, st, r, x, tc, vt); }
+template <typename T, typename CamT>
+int launch_features(rtw_scene_handle scene, const CamT *cams, int n_views, const uint64_t *seeds, const rtw_params *p, int32_t chunk_begin, int32_t chunk_count, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out, const int *d_tile_chunks = nullptr, const int *const *view_tiles = nullptr);
 // rtw_features_accum_batch_f32.hip / _f64.hip: the TILED && BATCH instance of the feature kernel for a scan variant, as launch_features chooses
 // among the other instances (`fixed`: the headline variant with the default numerics mode compiled in)
 const void *features_tiled_batch_kernel_f32(bool mfma, bool lds_scene, bool fixed);
@@ -346,10 +381,8 @@ int validate_filter_batch(const rtw_denoise_t *d, int32_t width, int32_t height,
 // (16-byte aligned); d_noise non-null: the noise-guided form (rtw_guided_filter_device_*), H*W elements of T, the per-pixel relative noise.
 // n_views >= 1: that many frames of one size in prepare + `levels` launches; every buffer (d_noise: n_views*H*W elements) and every plane of the
 // workspace (n_views * rtw_denoise_work_bytes bytes) holds the views one behind the other.
-int launch_denoise_f32(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream, const void *d_noise = nullptr);
-int launch_denoise_f64(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream, const void *d_noise = nullptr);
-inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t nv, const float *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise = nullptr) { return launch_denoise_f32(d, w, h, nv, img, feat, out, work, st, noise); }
-inline int launch_denoise_t(const rtw_denoise_t *d, int32_t w, int32_t h, int32_t nv, const double *img, const void *feat, void *out, void *work, hipStream_t st, const void *noise = nullptr) { return launch_denoise_f64(d, w, h, nv, img, feat, out, work, st, noise); }
+template <typename T>
+int launch_denoise(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, const void *d_image, const void *d_features, void *d_out, void *d_work, hipStream_t stream, const void *d_noise = nullptr);
 
 // rtw_upsample.hip -- the feature-guided upsampler (include/rtw_hip.h rtw_upsample_*).  validate_upsample: every check of a call that needs no
 // device -- the parameters, both frame sizes, n_views (0: one frame) and the batch's size.
@@ -357,10 +390,8 @@ int validate_upsample(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_heig
 // launch_upsample: enqueue prepare + `levels` level passes at the small size and the upsampling kernel at the full size on `stream` of the current
 // device.  n_views == 0: one frame, d_work of rtw_upsample_work_bytes bytes (16-byte aligned); n_views >= 1: that many views in the same number
 // of launches, every buffer and every plane of the workspace (n_views times the bytes) holds the views one behind the other, each at its own size.
-int launch_upsample_f32(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, const void *d_image_lo, const void *d_features_lo, const void *d_features_hi, void *d_out, void *d_work, hipStream_t stream);
-int launch_upsample_f64(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, const void *d_image_lo, const void *d_features_lo, const void *d_features_hi, void *d_out, void *d_work, hipStream_t stream);
-inline int launch_upsample_t(const rtw_upsample_t *u, int32_t lw, int32_t lh, int32_t w, int32_t h, int32_t nv, const float *img, const void *flo, const void *fhi, void *out, void *work, hipStream_t st) { return launch_upsample_f32(u, lw, lh, w, h, nv, img, flo, fhi, out, work, st); }
-inline int launch_upsample_t(const rtw_upsample_t *u, int32_t lw, int32_t lh, int32_t w, int32_t h, int32_t nv, const double *img, const void *flo, const void *fhi, void *out, void *work, hipStream_t st) { return launch_upsample_f64(u, lw, lh, w, h, nv, img, flo, fhi, out, work, st); }
+template <typename T>
+int launch_upsample(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, const void *d_image_lo, const void *d_features_lo, const void *d_features_hi, void *d_out, void *d_work, hipStream_t stream);
 
 // rtw_temporal.hip -- temporal reprojection (include/rtw_hip.h rtw_temporal_*).  validate_temporal: every check of a step that needs neither a
 // device nor a pointer -- the parameters and the frame.
@@ -368,49 +399,38 @@ int validate_temporal(const rtw_temporal_t *t, int32_t width, int32_t height, in
 // launch_temporal: enqueue ONE step (one launch) on `stream` of the current device.  n_paths == 0: ONE path -- cam_prev and d_state_prev are
 // both null (the first frame) or both given; the states hold rtw_temporal_state_bytes bytes each (16-byte aligned).  n_paths >= 1
 // (rtw_reproject_batch_device_*): that many paths in the same ONE launch -- cam / cam_prev are unused, path s takes its constants from entry s of
-// the DEVICE table d_table (temporal_table_*: 32 elements of T per path) and every buffer holds the paths one behind the other; d_state_prev
+// the DEVICE table d_table (temporal_table: 32 elements of T per path) and every buffer holds the paths one behind the other; d_state_prev
 // null: every path's first frame.  d_moment_next non-null: the step with moments
 // (rtw_history_moments_*), planes of rtw_history_moment_bytes bytes, d_moment_prev null exactly when d_state_prev is.  `c` non-null (accepted by
 // validate_temporal_clamp: every check of a clamp, none needs a device): the clamped step (rtw_clamped_step_*), still one launch.
 int validate_temporal_clamp(const rtw_temporal_clamp_t *c);
-int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t n_paths, const void *d_table, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr, const rtw_temporal_clamp_t *c = nullptr, const void *d_motion = nullptr);
-int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t n_paths, const void *d_table, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr, const rtw_temporal_clamp_t *c = nullptr, const void *d_motion = nullptr);
-inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f32 *c, const rtw_camera_f32 *cp, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp = nullptr, void *mn = nullptr, const rtw_temporal_clamp_t *cl = nullptr, const void *mv = nullptr) { return launch_temporal_f32(t, c, cp, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, cl, mv); }
-inline int launch_temporal_t(const rtw_temporal_t *t, const rtw_camera_f64 *c, const rtw_camera_f64 *cp, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp = nullptr, void *mn = nullptr, const rtw_temporal_clamp_t *cl = nullptr, const void *mv = nullptr) { return launch_temporal_f64(t, c, cp, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, cl, mv); }
-// temporal_table_*: the camera constants of n paths into a HOST table, 32 elements per path (include/rtw_hip.h rtw_reproject_table_*; cams_prev null: first
+template <typename T, typename CamT>
+int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_prev, int32_t n_paths, const void *d_table, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_state_prev, void *d_state_next, void *d_out, hipStream_t stream, const void *d_moment_prev = nullptr, void *d_moment_next = nullptr, const rtw_temporal_clamp_t *c = nullptr, const void *d_motion = nullptr);
+// temporal_table: the camera constants of n paths into a HOST table, 32 elements per path (include/rtw_hip.h rtw_reproject_table_*; cams_prev null: first
 // frames) -- the one copy of that arithmetic, launch_temporal's own constants included.
-void temporal_table_f32(const rtw_camera_f32 *cams, const rtw_camera_f32 *cams_prev, int64_t n, float *table);
-void temporal_table_f64(const rtw_camera_f64 *cams, const rtw_camera_f64 *cams_prev, int64_t n, double *table);
-inline void temporal_table_t(const rtw_camera_f32 *c, const rtw_camera_f32 *cp, int64_t n, float *tab) { temporal_table_f32(c, cp, n, tab); }
-inline void temporal_table_t(const rtw_camera_f64 *c, const rtw_camera_f64 *cp, int64_t n, double *tab) { temporal_table_f64(c, cp, n, tab); }
+template <typename T, typename CamT> void temporal_table(const CamT *cams, const CamT *cams_prev, int64_t n, T *table);
 // validate_temporal_noise: every check of a noise map (rtw_history_noise_device_*) that needs neither a device nor a pointer.  launch_temporal_noise:
 // enqueue the map (ONE launch) of a state and its moment plane on `stream` of the current device; d_noise: width*height elements of T.
 // n_paths >= 1 (rtw_reproject_noise_batch_device_*): the maps of that many states and planes, one behind the other, in the same ONE launch.
 int validate_temporal_noise(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int elem_bytes);
-int launch_temporal_noise_f32(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int32_t n_paths, const void *d_state, const void *d_moment, void *d_noise, hipStream_t stream);
-int launch_temporal_noise_f64(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int32_t n_paths, const void *d_state, const void *d_moment, void *d_noise, hipStream_t stream);
-inline int launch_temporal_noise_t(const rtw_temporal_noise_t *n, int32_t w, int32_t h, int32_t np, const void *st, const void *mo, float *noise, hipStream_t s) { return launch_temporal_noise_f32(n, w, h, np, st, mo, noise, s); }
-inline int launch_temporal_noise_t(const rtw_temporal_noise_t *n, int32_t w, int32_t h, int32_t np, const void *st, const void *mo, double *noise, hipStream_t s) { return launch_temporal_noise_f64(n, w, h, np, st, mo, noise, s); }
+template <typename T> int launch_temporal_noise(const rtw_temporal_noise_t *n, int32_t width, int32_t height, int32_t n_paths, const void *d_state, const void *d_moment, void *d_noise, hipStream_t stream);
 
 // rtw_motion.hip -- the first-hit motion pass (include/rtw_hip.h rtw_first_hit_motion_*).  validate_motion: every check of a pass that needs
 // neither a device nor a pointer (of `p`: the frame, the device, the flag bits).  launch_motion: enqueue the pass (ONE launch, no record) on
 // `stream` of the scene's device, which must be current; d_table (scene->n rows of 4 elements, or null: m = 0) and d_motion (width*height
 // slots of 4 elements) are 16-byte aligned DEVICE pointers.
 int validate_motion(const rtw_params *p, int elem_bytes);
-int launch_motion_f32(rtw_scene_handle scene, const rtw_camera_f32 *cam, const rtw_params *p, const void *d_table, void *d_motion, hipStream_t stream);
-int launch_motion_f64(rtw_scene_handle scene, const rtw_camera_f64 *cam, const rtw_params *p, const void *d_table, void *d_motion, hipStream_t stream);
-inline int launch_motion_t(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, const void *tab, void *mo, hipStream_t st) { return launch_motion_f32(s, c, p, tab, mo, st); }
-inline int launch_motion_t(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, const void *tab, void *mo, hipStream_t st) { return launch_motion_f64(s, c, p, tab, mo, st); }
+template <typename T, typename CamT> int launch_motion(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, const void *d_table, void *d_motion, hipStream_t stream);
+// motion_table: the body of rtw_motion_table_* (include/rtw_hip.h), a frame's table into HOST memory
+template <typename T, typename SceneT> int motion_table(const SceneT *prev, const SceneT *cur, T *table);
 
 // rtw_motion_blur.hip -- the motion-blur stage (include/rtw_hip.h rtw_velocity_blur_*).  validate_motion_blur: every check of a blur that needs
 // neither a device nor a pointer.  launch_motion_blur: enqueue the stage (THREE launches, no record) on `stream` of the current device; d_work:
 // rtw_velocity_blur_work_bytes bytes.  cam_prev null (frame 0 of rtw_render_blurred_*): ONE launch, the image passes through with the
 // gamma applied; d_motion and d_work are not looked at.
 int validate_motion_blur(const rtw_velocity_blur_t *b, int32_t width, int32_t height, int elem_bytes);
-int launch_motion_blur_f32(const rtw_velocity_blur_t *b, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_motion, void *d_work, void *d_out, hipStream_t stream);
-int launch_motion_blur_f64(const rtw_velocity_blur_t *b, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_motion, void *d_work, void *d_out, hipStream_t stream);
-inline int launch_motion_blur_t(const rtw_velocity_blur_t *b, const rtw_camera_f32 *c, const rtw_camera_f32 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *mo, void *work, void *out, hipStream_t st) { return launch_motion_blur_f32(b, c, cp, w, h, img, feat, mo, work, out, st); }
-inline int launch_motion_blur_t(const rtw_velocity_blur_t *b, const rtw_camera_f64 *c, const rtw_camera_f64 *cp, int32_t w, int32_t h, const void *img, const void *feat, const void *mo, void *work, void *out, hipStream_t st) { return launch_motion_blur_f64(b, c, cp, w, h, img, feat, mo, work, out, st); }
+template <typename T, typename CamT>
+int launch_motion_blur(const rtw_velocity_blur_t *b, const CamT *cam, const CamT *cam_prev, int32_t width, int32_t height, const void *d_image, const void *d_features, const void *d_motion, void *d_work, void *d_out, hipStream_t stream);
 
 // ---- the lens family: rtw_defocus_*, rtw_wide_aperture_*, rtw_lens_batch_* (include/rtw_hip.h) -----------------------------------------
 // The three stages are one: the wide-aperture stage with max_radius <= 8 IS the defocus stage, and the batch runs the same launches over N
@@ -435,54 +455,45 @@ inline int32_t lens_batch_views(int32_t n_views) { return n_views ? n_views : LE
 // lens (lens_radius, focus_dist), the frame (check_lens_frame: the sizes, then the denoiser's frame rule) and the camera (its horizontal
 // extent and focus plane).  launch_defocus: enqueue the stage (TWO launches, no record) on `stream` of the current device; d_work:
 // rtw_defocus_work_bytes bytes.  The camera's lens_radius is not read: the aperture is b->lens_radius.
-int validate_lens(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, int top);
-int validate_lens(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, int top);
+template <typename CamT> int validate_lens(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, int top);
 int check_lens_params(const rtw_defocus_t *b, int top);
 int check_lens_frame(int32_t width, int32_t height, int elem_bytes);
 // A batch of views for the lens stages (rtw_lens_batch_*; rtw_layout.hpp LensBatchLayout has the arithmetic): n_views >= 1 views in each
-// launch, view v's lens in entry v of the DEVICE table d_table (lens_table_entry_*), its image, features, workspace and output v strides (BYTES)
+// launch, view v's lens in entry v of the DEVICE table d_table (lens_table_entry), its image, features, workspace and output v strides (BYTES)
 // behind the pointers; an input stride of 0: every view reads the one frame.  Below the ABI a null LensViews is the single call.
 struct LensViews { int32_t n_views; const void *d_table; long long img_stride, feat_stride, work_stride, out_stride; };
 inline LensViews lens_views(const LensBatchLayout &R, int32_t n_views, const void *d_table) {
     return {n_views, d_table, (long long)R.img_stride, (long long)R.feat_stride, (long long)R.work_stride, (long long)R.out_stride};
 }
-int launch_defocus_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream, const LensViews *vb = nullptr);
-int launch_defocus_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream, const LensViews *vb = nullptr);
-inline int launch_defocus_t(const rtw_defocus_t *b, const rtw_camera_f32 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb = nullptr) { return launch_defocus_f32(b, c, w, h, img, feat, work, out, st, vb); }
-inline int launch_defocus_t(const rtw_defocus_t *b, const rtw_camera_f64 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb = nullptr) { return launch_defocus_f64(b, c, w, h, img, feat, work, out, st, vb); }
-// Its two launches one by one, for the wide-aperture stage: launch_defocus_prepare_* is the prepare launch with the clamp `rm` (b->max_radius is not read) into a CoC plane and its tile plane;
-// launch_defocus_gather_* is the gather of a frame of any size over an image, a CoC plane and a tile plane, mmax (1..8) >= every radius there.
+template <typename T, typename CamT>
+int launch_defocus(const rtw_defocus_t *b, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream, const LensViews *vb = nullptr);
+// Its two launches one by one, for the wide-aperture stage: launch_defocus_prepare is the prepare launch with the clamp `rm` (b->max_radius is not read) into a CoC plane and its tile plane;
+// launch_defocus_gather is the gather of a frame of any size over an image, a CoC plane and a tile plane, mmax (1..8) >= every radius there.
 // n_views == 0: one view.  n_views >= 1: that many views in the same ONE launch; `strides`: four byte strides from one view to the next, one
 // per pointer in the order of the arguments; the prepare launch then reads neither b nor cam but entry v of the device table d_table.
-int launch_defocus_prepare_f32(const rtw_defocus_t *b, int rm, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream, int32_t n_views = 0, const void *d_table = nullptr, const long long *strides = nullptr);
-int launch_defocus_prepare_f64(const rtw_defocus_t *b, int rm, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream, int32_t n_views = 0, const void *d_table = nullptr, const long long *strides = nullptr);
-int launch_defocus_gather_f32(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream, int32_t n_views = 0, const long long *strides = nullptr);
-int launch_defocus_gather_f64(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream, int32_t n_views = 0, const long long *strides = nullptr);
+template <typename T, typename CamT>
+int launch_defocus_prepare(const rtw_defocus_t *b, int rm, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_coc, void *d_tile, hipStream_t stream, int32_t n_views = 0, const void *d_table = nullptr, const long long *strides = nullptr);
+template <typename T>
+int launch_defocus_gather(int32_t width, int32_t height, int mmax, int gamma, const void *d_image, const void *d_coc, const void *d_tile, void *d_out, hipStream_t stream, int32_t n_views = 0, const long long *strides = nullptr);
 dim3 lens_views_grid(unsigned tiles, int32_t n_views);       // the grid of a batched lens launch: the tiles of one view in x, the views over y and z
 // one view's entry of the lens table (include/rtw_hip.h rtw_lens_table_*; b: lens_radius and focus_dist alone are read): the one copy of that arithmetic
-void lens_table_entry_f32(const rtw_defocus_t *b, const rtw_camera_f32 *cam, int32_t width, float *e);
-void lens_table_entry_f64(const rtw_defocus_t *b, const rtw_camera_f64 *cam, int32_t width, double *e);
+template <typename T, typename CamT> void lens_table_entry(const rtw_defocus_t *b, const CamT *cam, int32_t width, T *e);
 
 // rtw_wide_aperture.hip -- the wide-aperture stage (include/rtw_hip.h rtw_wide_aperture_*): circles of confusion up to 32 px through a reduced
 // copy of the frame.  launch_wide_aperture: enqueue the stage (SIX launches, or the defocus stage's two when max_radius <= 8 -- what the
 // defocus stage's own entry points run; no record) on `stream` of the
 // current device; d_work: rtw_wide_aperture_work_bytes bytes.  vb non-null (rtw_lens_batch_*): vb->n_views views in the same launches.
-int launch_wide_aperture_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream, const LensViews *vb = nullptr);
-int launch_wide_aperture_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream, const LensViews *vb = nullptr);
-inline int launch_wide_aperture_t(const rtw_wide_aperture_t *b, const rtw_camera_f32 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb = nullptr) { return launch_wide_aperture_f32(b, c, w, h, img, feat, work, out, st, vb); }
-inline int launch_wide_aperture_t(const rtw_wide_aperture_t *b, const rtw_camera_f64 *c, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb = nullptr) { return launch_wide_aperture_f64(b, c, w, h, img, feat, work, out, st, vb); }
+template <typename T, typename CamT>
+int launch_wide_aperture(const rtw_wide_aperture_t *b, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream, const LensViews *vb = nullptr);
 // The checks of n_views >= 1 views that need neither a device nor a pointer (every entry point of the family but the batched device
 // form; a single form: ONE view without arrays): the count, then per view validate_lens with lens_radii[v] / focus_dists[v] (null arrays:
 // b's own) and max_radius in 1..top -- the first offending view is named, unless it is one view without arrays --, then the batch's size
 // (-5; one view never reaches it: the frame rule is the narrower).  own_lens (the one-call forms alone): a lens radius of -1 is cams[v]'s
 // own.  `lens_out` non-null: n_views rtw_defocus_t with every view's lens radius and focus distance in place.
-int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, int top, std::vector<rtw_defocus_t> *lens_out);
-int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, int top, std::vector<rtw_defocus_t> *lens_out);
+template <typename CamT>
+int validate_lens_batch(const rtw_wide_aperture_t *b, const CamT *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, int top, std::vector<rtw_defocus_t> *lens_out);
 // the lens table of those views into a HOST table (32 elements per view)
-void lens_table_f32(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f32 *cams, int32_t width, float *table);
-void lens_table_f64(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f64 *cams, int32_t width, double *table);
-inline void lens_table_t(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f32 *cams, int32_t width, float *table) { lens_table_f32(lens, cams, width, table); }
-inline void lens_table_t(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f64 *cams, int32_t width, double *table) { lens_table_f64(lens, cams, width, table); }
+template <typename T, typename CamT> void lens_table(const std::vector<rtw_defocus_t> &lens, const CamT *cams, int32_t width, T *table);
 // what a batched entry point checks of its counts and frame without a camera: the counts, check_lens_params with top 32, check_lens_frame, the batch's size
 int validate_lens_batch_frame(const rtw_wide_aperture_t *b, int32_t n_views, int32_t n_frames, int32_t width, int32_t height, int elem_bytes);
 
@@ -491,14 +502,10 @@ int validate_lens_batch_frame(const rtw_wide_aperture_t *b, int32_t n_views, int
 int validate_present(const rtw_present_t *p, int32_t width, int32_t height, int32_t n_views);
 // launch_present: enqueue ONE launch on `stream` of the current device.  n_views == 0: one frame of width*height*3 elements into
 // width*height*channels bytes (d_out 4-byte aligned); n_views >= 1: that many frames one behind the other in both buffers.
-int launch_present_f32(const rtw_present_t *p, int32_t width, int32_t height, int32_t n_views, const void *d_images, void *d_out, hipStream_t stream);
-int launch_present_f64(const rtw_present_t *p, int32_t width, int32_t height, int32_t n_views, const void *d_images, void *d_out, hipStream_t stream);
-inline int launch_present_t(const rtw_present_t *p, int32_t w, int32_t h, int32_t nv, const float *img, void *out, hipStream_t st) { return launch_present_f32(p, w, h, nv, img, out, st); }
-inline int launch_present_t(const rtw_present_t *p, int32_t w, int32_t h, int32_t nv, const double *img, void *out, hipStream_t st) { return launch_present_f64(p, w, h, nv, img, out, st); }
+template <typename T> int launch_present(const rtw_present_t *p, int32_t width, int32_t height, int32_t n_views, const void *d_images, void *d_out, hipStream_t stream);
 
 // rtw_unit.hip
-int run_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene, const rtw_camera_f32 *cam);
-int run_unit_f64(int op, int count, const void *in, void *out, const rtw_scene_f64 *scene, const rtw_camera_f64 *cam);
+template <typename T, typename SceneT, typename CamT> int run_unit(int op, int count, const void *in, void *out, const SceneT *scene, const CamT *cam);
 
 }  // namespace rtwh
 

@@ -48,7 +48,7 @@ int ensure_scene(HostCtx *hc, const SceneT *scene, const std::vector<unsigned ch
     if (hc->scene && hc->scene_key == key) return 0;
     if (hc->scene && keep) { keep->emplace_back(hc->scene); hc->scene = nullptr; hc->scene_key.clear(); }
     if (hc->scene) { rtw_scene_free(hc->scene); hc->scene = nullptr; hc->scene_key.clear(); }
-    if (int rc = upload_scene_t(scene, hc->device, &hc->scene)) return rc;
+    if (int rc = upload_scene<T>(scene, hc->device, &hc->scene)) return rc;
     hc->scene_key = key;
     return 0;
 }
@@ -115,7 +115,7 @@ template <typename T> struct DenoiseRegions : DenoiseLayout {
     DenoiseRegions(int32_t width, int32_t height, int32_t n_views) : DenoiseLayout(sizeof(T), width, height, n_views, (size_t)rtw_denoise_work_bytes(width, height, (int32_t)sizeof(T))) {}
     // the filter over the regions of `base`, on `stream`
     int launch(const rtw_denoise_t *d, int32_t width, int32_t height, int32_t n_views, char *base, hipStream_t stream, const void *d_noise = nullptr) const {
-        return launch_denoise_t(d, width, height, n_views, (const T *)base, base + off_feat, base + off_out, base + off_work, stream, d_noise);
+        return launch_denoise<T>(d, width, height, n_views, base, base + off_feat, base + off_out, base + off_work, stream, d_noise);
     }
 };
 
@@ -124,7 +124,7 @@ template <typename T> struct UpsampleRegions : UpsampleLayout {
         : UpsampleLayout(sizeof(T), lo_width, lo_height, width, height, n_views, (size_t)rtw_upsample_work_bytes(lo_width, lo_height, (int32_t)sizeof(T))) {}
     // the upsampler over the regions of `base`, on `stream`
     int launch(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height, int32_t width, int32_t height, int32_t n_views, char *base, hipStream_t stream) const {
-        return launch_upsample_t(u, lo_width, lo_height, width, height, n_views, (const T *)base, base + off_flo, base + off_fhi, base + off_out, base + off_work, stream);
+        return launch_upsample<T>(u, lo_width, lo_height, width, height, n_views, base, base + off_flo, base + off_fhi, base + off_out, base + off_work, stream);
     }
 };
 

@@ -105,7 +105,7 @@ static int job_shape(int nch, long long n_local, int tiles_i, int tiles_j, int s
 // (a batched pass: behind them the views' accumulators and divisors, rtw::AccumView; the batched feature pass over adaptive accumulators:
 //  behind them `tiles`, the n_views device pointers of the accumulators' tile-chunk arrays -- *d_tiles receives the table's device address)
 template <typename T, typename CamT>
-static int upload_views(RenderRec *rec, const CamT *cam, int n_views, const uint64_t *seeds, uint64_t seed, const AccumPass *pass, hipStream_t stream, rtw::BatchArgs<T> *B, rtw::AccumArgs *A,
+static int upload_batch(RenderRec *rec, const CamT *cam, int n_views, const uint64_t *seeds, uint64_t seed, const AccumPass *pass, hipStream_t stream, rtw::BatchArgs<T> *B, rtw::AccumArgs *A,
                         const int *const *tiles = nullptr, const int *const **d_tiles = nullptr) {
     const size_t cam_bytes = (size_t)n_views * sizeof(rtw::Camera<T>), seed_bytes = (size_t)n_views * sizeof(unsigned long long);
     static_assert(sizeof(rtw::Camera<T>) % 8 == 0, "the seeds and the view table behind the cameras are 8-byte aligned");
@@ -140,21 +140,13 @@ static int upload_views(RenderRec *rec, const CamT *cam, int n_views, const uint
 // the same upload for a launch that is not the trace kernel's (the batched feature pass, rtw_features.hip): the device arrays of the
 // cameras and of the seeds in the record's buffer
 template <typename T, typename CamT>
-static int upload_views_plain(RenderRec *rec, const CamT *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds,
-                              const int *const *tiles, const int *const **d_tiles) {
+int upload_views(RenderRec *rec, const CamT *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds,
+                 const int *const *tiles, const int *const **d_tiles) {
     rtw::BatchArgs<T> B;
     memset(&B, 0, sizeof B);
-    if (int rc = upload_views<T>(rec, cams, n_views, seeds, seed, nullptr, stream, &B, nullptr, tiles, d_tiles)) return rc;
+    if (int rc = upload_batch<T>(rec, cams, n_views, seeds, seed, nullptr, stream, &B, nullptr, tiles, d_tiles)) return rc;
     *d_cams = B.cams; *d_seeds = B.seeds;
     return 0;
-}
-int upload_views_f32(RenderRec *rec, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds,
-                     const int *const *tiles, const int *const **d_tiles) {
-    return upload_views_plain<float>(rec, cams, n_views, seeds, seed, stream, d_cams, d_seeds, tiles, d_tiles);
-}
-int upload_views_f64(RenderRec *rec, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, uint64_t seed, hipStream_t stream, const void **d_cams, const unsigned long long **d_seeds,
-                     const int *const *tiles, const int *const **d_tiles) {
-    return upload_views_plain<double>(rec, cams, n_views, seeds, seed, stream, d_cams, d_seeds, tiles, d_tiles);
 }
 
 // Enqueue one render (this shard's tiles) on `stream`; `rec` receives the counters and the kernel's events.
@@ -170,7 +162,7 @@ int upload_views_f64(RenderRec *rec, const rtw_camera_f64 *cams, int n_views, co
 // pass->views holds every view's accumulator and divisor, a tile list numbers the tiles batch-globally (v * n_tiles + t).
 template <typename T, typename CamT>
 int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
-                  RenderRec **rec_out, CtxPtr *ctx_out, const AccumPass *pass = nullptr) {
+                  RenderRec **rec_out, CtxPtr *ctx_out, const AccumPass *pass) {
     if (!scene || !cam || (!d_out && !pass)) return fail(-1, "null argument");
     if (scene->is_f64 != (sizeof(T) == 8)) return fail(-4, "scene handle precision does not match the call");
     int nch, cs;
@@ -279,7 +271,7 @@ int launch_render(rtw_scene_handle scene, const CamT *cam, int n_views, const ui
     RenderRec *rec = *rec_out;
     if (drain_profile) HIP_TRY(hipMemsetAsync(&rec->ctr->t_first, 0xff, sizeof(unsigned long long), stream));
     // ---- views ----
-    if (batch) if (int rc = upload_views<T>(rec, cam, n_views, seeds, p->seed, pass, stream, &B, &A)) return rc;
+    if (batch) if (int rc = upload_batch<T>(rec, cam, n_views, seeds, p->seed, pass, stream, &B, &A)) return rc;
     // pixels of other shards read 0 in the full-frame layout (the sum over the shards is the image)
     if (K.out_layout == 0 && p->shard_count > 1 && d_out)
         HIP_TRY(hipMemsetAsync(d_out, 0, (size_t)p->width * p->height * 3 * sizeof(T), stream));
@@ -373,13 +365,9 @@ int resolve_rec(RenderRec *r, rtw_stats_t *agg) {
     return 0;
 }
 
-int launch_render_f32(rtw_scene_handle scene, const rtw_camera_f32 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
-                      RenderRec **rec_out, CtxPtr *ctx_out, const AccumPass *pass) {
-    return launch_render<float>(scene, cams, n_views, seeds, p, d_out, stream, rec_out, ctx_out, pass);
-}
-int launch_render_f64(rtw_scene_handle scene, const rtw_camera_f64 *cams, int n_views, const uint64_t *seeds, const rtw_params *p, void *d_out, hipStream_t stream,
-                      RenderRec **rec_out, CtxPtr *ctx_out, const AccumPass *pass) {
-    return launch_render<double>(scene, cams, n_views, seeds, p, d_out, stream, rec_out, ctx_out, pass);
-}
+template int upload_views<float>(RenderRec *, const rtw_camera_f32 *, int, const uint64_t *, uint64_t, hipStream_t, const void **, const unsigned long long **, const int *const *, const int *const **);
+template int upload_views<double>(RenderRec *, const rtw_camera_f64 *, int, const uint64_t *, uint64_t, hipStream_t, const void **, const unsigned long long **, const int *const *, const int *const **);
+template int launch_render<float>(rtw_scene_handle, const rtw_camera_f32 *, int, const uint64_t *, const rtw_params *, void *, hipStream_t, RenderRec **, CtxPtr *, const AccumPass *);
+template int launch_render<double>(rtw_scene_handle, const rtw_camera_f64 *, int, const uint64_t *, const rtw_params *, void *, hipStream_t, RenderRec **, CtxPtr *, const AccumPass *);
 
 }  // namespace rtwh

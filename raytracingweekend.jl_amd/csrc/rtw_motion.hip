@@ -55,24 +55,19 @@ int launch_motion(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, 
     const unsigned grid = (unsigned)((n_pix + 255) / 256);
     // (measurement aid, tools/gpu_animation.py: events around the kernel, reported on stderr -- this one blocks)
     static const bool profile = aid_flag("RTW_TEMPORAL_PROFILE");
-    struct Events { hipEvent_t e[2] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
-    if (profile) { for (hipEvent_t &x : events.e) HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventRecord(events.e[0], stream)); }
+    StageMarks marks(profile, stream);
+    HIP_TRY(marks.mark());
     (void)hipGetLastError();
     if (S.lds_scene) hipLaunchKernelGGL((rtw::motion_pass<T, true>), dim3(grid), dim3(256), S.scene_bytes, stream, U, S.scene, (const V *)d_table, (V *)d_motion);
     else hipLaunchKernelGGL((rtw::motion_pass<T, false>), dim3(grid), dim3(256), 0, stream, U, S.scene, (const V *)d_table, (V *)d_motion);
     HIP_TRY(hipGetLastError());
     if (profile) {
-        float ms = 0;
-        HIP_TRY(hipEventRecord(events.e[1], stream));
-        HIP_TRY(hipEventSynchronize(events.e[1]));
-        HIP_TRY(hipEventElapsedTime(&ms, events.e[0], events.e[1]));
-        fprintf(stderr, "[rtw motion] %s %dx%d spheres=%d lds_scene=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", p->width, p->height, scene->n, (int)S.lds_scene, ms);
+        HIP_TRY(marks.mark());
+        HIP_TRY(marks.measure());
+        fprintf(stderr, "[rtw motion] %s %dx%d spheres=%d lds_scene=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", p->width, p->height, scene->n, (int)S.lds_scene, marks.ms[0]);
     }
     return 0;
 }
-
-int launch_motion_f32(rtw_scene_handle s, const rtw_camera_f32 *c, const rtw_params *p, const void *tab, void *mo, hipStream_t st) { return launch_motion<float>(s, c, p, tab, mo, st); }
-int launch_motion_f64(rtw_scene_handle s, const rtw_camera_f64 *c, const rtw_params *p, const void *tab, void *mo, hipStream_t st) { return launch_motion<double>(s, c, p, tab, mo, st); }
 
 // The device-resident entry point: nulls, the parameters, the pointers' alignment, then the handle and what needs it (the table's extent).
 template <typename T, typename CamT>
@@ -89,6 +84,11 @@ int motion_device(rtw_scene_handle scene, const CamT *cam, const rtw_params *p, 
     HIP_TRY(hipSetDevice(scene->device));
     return launch_motion<T>(scene, cam, p, d_table, d_motion, (hipStream_t)stream_v);
 }
+
+template int motion_table<float>(const rtw_scene_f32 *, const rtw_scene_f32 *, float *);
+template int motion_table<double>(const rtw_scene_f64 *, const rtw_scene_f64 *, double *);
+template int launch_motion<float>(rtw_scene_handle, const rtw_camera_f32 *, const rtw_params *, const void *, void *, hipStream_t);
+template int launch_motion<double>(rtw_scene_handle, const rtw_camera_f64 *, const rtw_params *, const void *, void *, hipStream_t);
 
 }  // namespace rtwh
 

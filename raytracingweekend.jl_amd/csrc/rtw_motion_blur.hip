@@ -40,8 +40,8 @@ int launch_motion_blur(const rtw_velocity_blur_t *b, const CamT *cam, const CamT
     const T ext = (T)b->depth_extent;
     // (measurement aid, tools/gpu_motion_blur.py: events around every launch, reported on stderr -- this one blocks)
     static const bool profile = aid_flag("RTW_TEMPORAL_PROFILE");
-    struct Events { hipEvent_t e[4] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
-    if (profile) { for (hipEvent_t &x : events.e) HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventRecord(events.e[0], stream)); }
+    StageMarks marks(profile, stream);
+    HIP_TRY(marks.mark());
     (void)hipGetLastError();
     if (!cam_prev) {
         hipLaunchKernelGGL((rtw::mb_gather<T, true>), dim3(tiles), dim3(256), 0, stream, width, height, b->taps, b->gamma, ext, (const T *)d_image, (const V *)d_features,
@@ -53,32 +53,28 @@ int launch_motion_blur(const rtw_velocity_blur_t *b, const CamT *cam, const CamT
     memset(&U, 0, sizeof U);
     {
         T e[32];
-        temporal_table_t(cam, cam_prev, 1, e);
+        temporal_table<T>(cam, cam_prev, 1, e);
         memcpy(&U, e, 29 * sizeof(T));
     }
     U.W = width; U.H = height;
     V *blur = (V *)d_work, *tile = blur + (size_t)width * (size_t)height, *nb = tile + tiles;
     hipLaunchKernelGGL((rtw::mb_velocity<T>), dim3(tiles), dim3(256), 0, stream, U, (T)(b->shutter / 2), (const T *)d_image, (const V *)d_features, (const V *)d_motion, blur, tile);
     HIP_TRY(hipGetLastError());
-    if (profile) HIP_TRY(hipEventRecord(events.e[1], stream));
+    HIP_TRY(marks.mark());
     hipLaunchKernelGGL((rtw::mb_neighbour<T>), dim3((tiles + 255) / 256), dim3(256), 0, stream, TH, TW, (const V *)tile, nb);
     HIP_TRY(hipGetLastError());
-    if (profile) HIP_TRY(hipEventRecord(events.e[2], stream));
+    HIP_TRY(marks.mark());
     hipLaunchKernelGGL((rtw::mb_gather<T, false>), dim3(tiles), dim3(256), 0, stream, width, height, b->taps, b->gamma, ext, (const T *)d_image, (const V *)nullptr, (const V *)blur,
                        (const V *)nb, (T *)d_out);
     HIP_TRY(hipGetLastError());
     if (profile) {
-        float ms[3] = {0, 0, 0};
-        HIP_TRY(hipEventRecord(events.e[3], stream));
-        HIP_TRY(hipEventSynchronize(events.e[3]));
-        for (int k = 0; k < 3; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], events.e[k], events.e[k + 1]));
+        const float *ms = marks.ms;
+        HIP_TRY(marks.mark());
+        HIP_TRY(marks.measure());
         fprintf(stderr, "[rtw motion blur] %s %dx%d taps=%d velocity_ms=%.5f neighbour_ms=%.5f gather_ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, b->taps, ms[0], ms[1], ms[2]);
     }
     return 0;
 }
-
-int launch_motion_blur_f32(const rtw_velocity_blur_t *b, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t w, int32_t h, const void *img, const void *feat, const void *mo, void *work, void *out, hipStream_t st) { return launch_motion_blur<float>(b, cam, cam_prev, w, h, img, feat, mo, work, out, st); }
-int launch_motion_blur_f64(const rtw_velocity_blur_t *b, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t w, int32_t h, const void *img, const void *feat, const void *mo, void *work, void *out, hipStream_t st) { return launch_motion_blur<double>(b, cam, cam_prev, w, h, img, feat, mo, work, out, st); }
 
 // The device-resident entry point: nulls, the parameters, then the pointers' alignment and aliasing.
 template <typename T, typename CamT>
@@ -95,6 +91,9 @@ int motion_blur_device(const rtw_velocity_blur_t *b, const CamT *cam, const CamT
     if (b->device >= 0) HIP_TRY(hipSetDevice(b->device));
     return launch_motion_blur<T>(b, cam, cam_prev, width, height, d_image, d_features, d_motion, d_work, d_out, (hipStream_t)stream_v);
 }
+
+template int launch_motion_blur<float>(const rtw_velocity_blur_t *, const rtw_camera_f32 *, const rtw_camera_f32 *, int32_t, int32_t, const void *, const void *, const void *, void *, void *, hipStream_t);
+template int launch_motion_blur<double>(const rtw_velocity_blur_t *, const rtw_camera_f64 *, const rtw_camera_f64 *, int32_t, int32_t, const void *, const void *, const void *, void *, void *, hipStream_t);
 
 }  // namespace rtwh
 

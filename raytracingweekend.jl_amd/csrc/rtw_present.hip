@@ -44,8 +44,8 @@ int launch_present(const rtw_present_t *p, int32_t width, int32_t height, int32_
     const unsigned grid = (unsigned)(tiles_of(width, height) * (n_views ? n_views : 1));
     // (measurement aid, tools/gpu_present.py: events around the kernel, reported on stderr -- this one blocks)
     static const bool profile = aid_flag("RTW_PRESENT_PROFILE");
-    struct Events { hipEvent_t e[2] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
-    if (profile) { for (hipEvent_t &x : events.e) HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventRecord(events.e[0], stream)); }
+    StageMarks marks(profile, stream);
+    HIP_TRY(marks.mark());
     (void)hipGetLastError();
     const T *in = (const T *)d_images;
     unsigned char *out = (unsigned char *)d_out;
@@ -55,18 +55,13 @@ int launch_present(const rtw_present_t *p, int32_t width, int32_t height, int32_
     else hipLaunchKernelGGL((rtw::pr_present<T, 3, false>), dim3(grid), dim3(256), 0, stream, U, in, out);
     HIP_TRY(hipGetLastError());
     if (profile) {
-        float ms = 0;
-        HIP_TRY(hipEventRecord(events.e[1], stream));
-        HIP_TRY(hipEventSynchronize(events.e[1]));
-        HIP_TRY(hipEventElapsedTime(&ms, events.e[0], events.e[1]));
+        HIP_TRY(marks.mark());
+        HIP_TRY(marks.measure());
         fprintf(stderr, "[rtw present] %s %dx%d views=%d C=%d %s ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, n_views ? n_views : 1, p->channels,
-                p->channels == 4 ? "dword" : aligned ? "aligned" : "unaligned", ms);
+                p->channels == 4 ? "dword" : aligned ? "aligned" : "unaligned", marks.ms[0]);
     }
     return 0;
 }
-
-int launch_present_f32(const rtw_present_t *p, int32_t w, int32_t h, int32_t nv, const void *img, void *out, hipStream_t st) { return launch_present<float>(p, w, h, nv, img, out, st); }
-int launch_present_f64(const rtw_present_t *p, int32_t w, int32_t h, int32_t nv, const void *img, void *out, hipStream_t st) { return launch_present<double>(p, w, h, nv, img, out, st); }
 
 // The device-resident entry points: nulls, the parameters, then the pointers' alignment and aliasing over the extents of all frames.
 template <typename T>
@@ -81,6 +76,9 @@ int present_device(const rtw_present_t *p, int32_t width, int32_t height, int32_
     if (p->device >= 0) HIP_TRY(hipSetDevice(p->device));
     return launch_present<T>(p, width, height, n_views, d_images, d_out, (hipStream_t)stream_v);
 }
+
+template int launch_present<float>(const rtw_present_t *, int32_t, int32_t, int32_t, const void *, void *, hipStream_t);
+template int launch_present<double>(const rtw_present_t *, int32_t, int32_t, int32_t, const void *, void *, hipStream_t);
 
 }  // namespace rtwh
 

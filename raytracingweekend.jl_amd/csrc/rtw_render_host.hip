@@ -112,7 +112,7 @@ int render_host(const SceneT *scene, const CamT *cam, const rtw_params *p, T *ou
         const size_t bytes = ((p->flags & RTW_FLAG_COMPACT_TILES) ? (size_t)local_tiles(p) * 64 * 3 : (size_t)p->width * (size_t)p->height * 3) * sizeof(T);
         return render_one_device(devs.size() == 1 ? devs[0] : p->device, scene, p, bytes, 0, bytes, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
             q.flags &= ~RTW_FLAG_RCCL_REDUCE;              // (one device: nothing to reduce)
-            return launch_render_t(hc->scene, cam, 0, nullptr, &q, hc->d_img, hc->stream, rec, rctx);
+            return launch_render<T>(hc->scene, cam, 0, nullptr, &q, hc->d_img, hc->stream, rec, rctx);
         });
     }
     if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
@@ -171,7 +171,7 @@ int render_host(const SceneT *scene, const CamT *cam, const rtw_params *p, T *ou
         if (use_rccl) {
             // this shard's tiles in the full-frame layout, zero elsewhere (launch_render clears the frame of a sharded render first)
             if ((rc = ensure_dev(&hc->d_img, &hc->d_cap, frame_bytes))) break;
-            rc = launch_render_t(hc->scene, cam, 0, nullptr, &q, hc->d_img, hc->stream, &recs[r], &rctx[r]);
+            rc = launch_render<T>(hc->scene, cam, 0, nullptr, &q, hc->d_img, hc->stream, &recs[r], &rctx[r]);
             continue;
         }
         q.flags |= RTW_FLAG_COMPACT_TILES;
@@ -184,7 +184,7 @@ int render_host(const SceneT *scene, const CamT *cam, const rtw_params *p, T *ou
             if ((rc = ensure_dev(&hc->d_img, &hc->d_cap, my_bytes))) break;        // (the shard buffer belongs to ITS device)
             d_out = hc->d_img;
         }
-        if ((rc = launch_render_t(hc->scene, cam, 0, nullptr, &q, d_out, hc->stream, &recs[r], &rctx[r]))) break;
+        if ((rc = launch_render<T>(hc->scene, cam, 0, nullptr, &q, d_out, hc->stream, &recs[r], &rctx[r]))) break;
         hipError_t e = hipSuccess;
         bool staged = false;
         if (remote) {
@@ -261,7 +261,7 @@ int render_host_batch(const SceneT *scene, const CamT *cams, int32_t n_views, co
     release_last();
     const size_t bytes = (size_t)n_views * (size_t)p->width * (size_t)p->height * 3 * sizeof(T);
     return render_one_device(p->device, scene, p, bytes, 0, bytes, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
-        return launch_render_t(hc->scene, cams, n_views, seeds, &q, hc->d_img, hc->stream, rec, rctx);
+        return launch_render<T>(hc->scene, cams, n_views, seeds, &q, hc->d_img, hc->stream, rec, rctx);
     });
 }
 
@@ -280,7 +280,7 @@ int render_host_features(const SceneT *scene, const CamT *cams, int32_t n_views,
     release_last();
     const size_t bytes = (size_t)(n_views ? n_views : 1) * (size_t)p->width * (size_t)p->height * RTW_FEATURE_CHANNELS * sizeof(T);
     return render_one_device(p->device, scene, p, bytes, 0, bytes, out, [&](HostCtx *hc, rtw_params &q, RenderRec **rec, CtxPtr *rctx) {
-        return launch_features_t(hc->scene, cams, n_views, seeds, &q, chunk_begin, chunk_count, hc->d_img, hc->stream, rec, rctx);
+        return launch_features<T>(hc->scene, cams, n_views, seeds, &q, chunk_begin, chunk_count, hc->d_img, hc->stream, rec, rctx);
     });
 }
 
@@ -303,7 +303,7 @@ int render_host_motion(const SceneT *scene, const CamT *cam, const rtw_params *p
         [&](HostCtx *hc, char *base) {
             rtw_params q = *p;
             q.device = hc->device;
-            return launch_motion_t(hc->scene, cam, &q, table && tab_b ? base + off_tab : nullptr, base, hc->stream);
+            return launch_motion<T>(hc->scene, cam, &q, table && tab_b ? base + off_tab : nullptr, base, hc->stream);
         },
         {0, motion, mo_b});
 }
@@ -318,8 +318,8 @@ int launch_filtered(HostCtx *hc, rtw_params &q, const CamT *cams, int32_t n_view
     q.gamma = 0;
     rtw_denoise_t dd = *d;
     dd.gamma = gamma != 0; dd.device = hc->device;
-    int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
-    if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec.rec, &frec.ctx);
+    int rc = launch_render<T>(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
+    if (!rc) rc = launch_features<T>(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec.rec, &frec.ctx);
     if (!rc) rc = R.launch(&dd, q.width, q.height, n_views, base, hc->stream);
     return rc;
 }
@@ -368,8 +368,8 @@ int render_host_presented(const SceneT *scene, const CamT *cams, int32_t n_views
         rtw_present_t pp = *pr;
         pp.device = hc->device;
         int rc = d ? launch_filtered(hc, q, cams, n_views, seeds, p->gamma, d, nch, R, rec, rctx, frec)
-                   : launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
-        if (!rc) rc = launch_present_t(&pp, p->width, p->height, n_views, (const T *)(base + off_img), base + off_pres, hc->stream);
+                   : launch_render<T>(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
+        if (!rc) rc = launch_present<T>(&pp, p->width, p->height, n_views, base + off_img, base + off_pres, hc->stream);
         return rc;
     });
 }
@@ -401,9 +401,9 @@ int render_host_upsampled(const SceneT *scene, const CamT *cams, int32_t n_views
         qd.width = lo_width; qd.height = lo_height; qd.gamma = 0;
         rtw_upsample_t uu = *u;
         uu.gamma = p->gamma != 0; uu.device = hc->device;
-        int rc = launch_render_t(hc->scene, cams, n_views, seeds, &qd, base, hc->stream, rec, rctx);
-        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &qd, 0, nch_q, base + R.off_flo, hc->stream, &frec[0].rec, &frec[0].ctx);
-        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &pd, 0, hi_chunks, base + R.off_fhi, hc->stream, &frec[1].rec, &frec[1].ctx);
+        int rc = launch_render<T>(hc->scene, cams, n_views, seeds, &qd, base, hc->stream, rec, rctx);
+        if (!rc) rc = launch_features<T>(hc->scene, cams, n_views, seeds, &qd, 0, nch_q, base + R.off_flo, hc->stream, &frec[0].rec, &frec[0].ctx);
+        if (!rc) rc = launch_features<T>(hc->scene, cams, n_views, seeds, &pd, 0, hi_chunks, base + R.off_fhi, hc->stream, &frec[1].rec, &frec[1].ctx);
         if (!rc) rc = R.launch(&uu, lo_width, lo_height, p->width, p->height, n_views, base, hc->stream);
         return rc;
     });
@@ -434,7 +434,7 @@ int render_host_lens(int top, const SceneT *scene, const CamT *cams, int32_t n_v
     std::vector<CamT> pins(cams, cams + views);
     for (CamT &c : pins) c.lens_radius = 0;
     std::vector<T> table;
-    if (n_views) { table.resize((size_t)n_views * 32); lens_table_t(lens, pins.data(), p->width, table.data()); }
+    if (n_views) { table.resize((size_t)n_views * 32); lens_table<T>(lens, pins.data(), p->width, table.data()); }
     DeviceGuard guard;
     release_last();
     const DenoiseRegions<T> R(p->width, p->height, n_views);
@@ -449,14 +449,14 @@ int render_host_lens(int top, const SceneT *scene, const CamT *cams, int32_t n_v
             rc = launch_filtered(hc, q, pins.data(), n_views, seeds, 0, d, nch, R, rec, rctx, frec);
         } else {
             q.gamma = 0;
-            rc = launch_render_t(hc->scene, pins.data(), n_views, seeds, &q, base, hc->stream, rec, rctx);
-            if (!rc) rc = launch_features_t(hc->scene, pins.data(), n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec.rec, &frec.ctx);
+            rc = launch_render<T>(hc->scene, pins.data(), n_views, seeds, &q, base, hc->stream, rec, rctx);
+            if (!rc) rc = launch_features<T>(hc->scene, pins.data(), n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec.rec, &frec.ctx);
         }
         if (rc) return rc;
         if (n_views) HIP_TRY(hipMemcpyAsync(base + off_tab, table.data(), B.tab_b, hipMemcpyHostToDevice, hc->stream));
         bb.device = hc->device;
         const LensViews vb = lens_views(B, n_views, base + off_tab);
-        return launch_wide_aperture_t(&bb, pins.data(), p->width, p->height, base + (d ? R.off_out : 0), base + R.off_feat, base + off_work, base + off_lens, hc->stream, n_views ? &vb : nullptr);
+        return launch_wide_aperture<T>(&bb, pins.data(), p->width, p->height, base + (d ? R.off_out : 0), base + R.off_feat, base + off_work, base + off_lens, hc->stream, n_views ? &vb : nullptr);
     });
 }
 
@@ -471,7 +471,7 @@ int render_host_lens(int top, const SceneT *scene, const CamT *cams, int32_t n_v
 // `c` non-null (rtw_render_path_clamped_*): the steps behind view 0 are clamped steps, launch for launch.
 // n_paths >= 1 (rtw_render_paths_*): n_views = n_steps * n_paths frames, step-major -- path s at step k is view k*n_paths + s of cams, seeds and
 // out.  Still ONE render, ONE feature pass and ONE filter pass over all n_views frames; the table of all n_views camera constants
-// (temporal_table_t: step k's previous cameras are step k-1's) goes up by ONE H2D from the context's pinned staging buffer, then n_steps
+// (temporal_table: step k's previous cameras are step k-1's) goes up by ONE H2D from the context's pinned staging buffer, then n_steps
 // BATCHED step launches (step k reads the table's entries [k*n_paths, (k+1)*n_paths); two sets of n_paths states -- with n, of moment planes
 // -- ping-pong) and, with n, one batched noise launch behind each.  n_paths == 0 is the one path above, call for call.
 template <typename T, typename SceneT, typename CamT>
@@ -501,29 +501,29 @@ int render_host_sequence(const SceneT *scene, const CamT *cams, int32_t n_views,
         q.gamma = 0;
         rtw_temporal_t tt = *t;
         tt.gamma = d ? 0 : (p->gamma != 0); tt.device = hc->device;
-        int rc = launch_render_t(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
-        if (!rc) rc = launch_features_t(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec.rec, &frec.ctx);
+        int rc = launch_render<T>(hc->scene, cams, n_views, seeds, &q, base, hc->stream, rec, rctx);
+        if (!rc) rc = launch_features<T>(hc->scene, cams, n_views, seeds, &q, 0, nch, base + R.off_feat, hc->stream, &frec.rec, &frec.ctx);
         if (!rc && n_paths) {
             // the whole table: step 0's entries are first frames', step k's previous cameras are step k-1's
             if ((rc = ensure_stage(hc, R.tab_b))) return rc;
             T *tab = (T *)hc->h_stage;
-            temporal_table_t(cams, nullptr, n_paths, tab);
-            if (n_steps > 1) temporal_table_t(cams + n_paths, cams, (int64_t)(n_steps - 1) * n_paths, tab + 32 * np);
+            temporal_table<T, CamT>(cams, nullptr, n_paths, tab);
+            if (n_steps > 1) temporal_table<T>(cams + n_paths, cams, (int64_t)(n_steps - 1) * n_paths, tab + 32 * np);
             HIP_TRY(hipMemcpyAsync(base + R.off_tab, tab, R.tab_b, hipMemcpyHostToDevice, hc->stream));
         }
         const size_t feat_frame_b = R.feat_b / (size_t)n_views;
         for (int v = 0; v < n_steps && !rc; ++v) {
             const size_t f = (size_t)v * np;                  // the step's first frame
-            rc = launch_temporal_t(&tt, n_paths ? nullptr : cams + v, n_paths || !v ? nullptr : cams + (v - 1), n_paths, n_paths ? base + R.off_tab + f * 32 * sizeof(T) : nullptr, p->width,
-                                   p->height, base + f * R.frame_b, base + R.off_feat + f * feat_frame_b, v ? base + R.off_st[(v & 1) ^ 1] : nullptr, base + R.off_st[v & 1],
-                                   base + R.off_acc + f * R.frame_b, hc->stream, n && v ? base + R.off_mo[(v & 1) ^ 1] : nullptr, n ? base + R.off_mo[v & 1] : nullptr, c);
-            if (!rc && n) rc = launch_temporal_noise_t(n, p->width, p->height, n_paths, base + R.off_st[v & 1], base + R.off_mo[v & 1], (T *)(base + R.off_noise + f * R.noise_b), hc->stream);
+            rc = launch_temporal<T>(&tt, n_paths ? nullptr : cams + v, n_paths || !v ? nullptr : cams + (v - 1), n_paths, n_paths ? base + R.off_tab + f * 32 * sizeof(T) : nullptr, p->width,
+                                    p->height, base + f * R.frame_b, base + R.off_feat + f * feat_frame_b, v ? base + R.off_st[(v & 1) ^ 1] : nullptr, base + R.off_st[v & 1],
+                                    base + R.off_acc + f * R.frame_b, hc->stream, n && v ? base + R.off_mo[(v & 1) ^ 1] : nullptr, n ? base + R.off_mo[v & 1] : nullptr, c);
+            if (!rc && n) rc = launch_temporal_noise<T>(n, p->width, p->height, n_paths, base + R.off_st[v & 1], base + R.off_mo[v & 1], base + R.off_noise + f * R.noise_b, hc->stream);
         }
         if (!rc && d) {
             rtw_denoise_t dd = *d;
             dd.gamma = p->gamma != 0; dd.device = hc->device;
-            rc = launch_denoise_t(&dd, p->width, p->height, n_views, (const T *)(base + R.off_acc), base + R.off_feat, base + R.off_flt, base + R.off_work, hc->stream,
-                                  n ? base + R.off_noise : nullptr);
+            rc = launch_denoise<T>(&dd, p->width, p->height, n_views, base + R.off_acc, base + R.off_feat, base + R.off_flt, base + R.off_work, hc->stream,
+                                   n ? base + R.off_noise : nullptr);
         }
         return rc;
     });
@@ -552,8 +552,6 @@ int render_host_sequence_clamped(const SceneT *scene, const CamT *cams, int32_t 
     return render_host_sequence<T>(scene, cams, n_views, seeds, p, t, n, d, out, c, n != nullptr);
 }
 
-inline int motion_table_t(const rtw_scene_f32 *prev, const rtw_scene_f32 *cur, float *tab) { return rtw_motion_table_f32(prev, cur, tab); }
-inline int motion_table_t(const rtw_scene_f64 *prev, const rtw_scene_f64 *cur, double *tab) { return rtw_motion_table_f64(prev, cur, tab); }
 
 // n_frames scenes and cameras with history reuse across the spheres' motion (rtw_render_animation_*): the sequence above for a scene that
 // changes from frame to frame, so what it batches over one scene runs per frame here, all on the leased context's stream: the frame's
@@ -618,33 +616,33 @@ int render_host_animation(const SceneT *scenes, const CamT *cams, int32_t n_fram
             if (v && (rc = ensure_scene<T>(hc, scene, key, &replaced))) break;
             if (seeds) q.seed = seeds[v];
             char *img = base + (size_t)v * R.frame_b, *feat = base + R.off_feat + (size_t)v * feat_frame_b, *plane = base + off_mo + (b ? (size_t)v * mo_b : 0);
-            rc = launch_render_t(hc->scene, cams + v, 0, nullptr, &q, img, hc->stream, &recs[v], &rctx[v]);
-            if (!rc) rc = launch_features_t(hc->scene, cams + v, 0, nullptr, &q, 0, nch, feat, hc->stream, &frecs[v].rec, &frecs[v].ctx);
+            rc = launch_render<T>(hc->scene, cams + v, 0, nullptr, &q, img, hc->stream, &recs[v], &rctx[v]);
+            if (!rc) rc = launch_features<T>(hc->scene, cams + v, 0, nullptr, &q, 0, nch, feat, hc->stream, &frecs[v].rec, &frecs[v].ctx);
             if (!rc && v) {
                 const size_t tab_b = (size_t)scene->n * 4 * sizeof(T);
                 T *tab = (T *)((char *)hc->h_stage + stage_off);
                 stage_off += tab_b;
                 if (tab_b) {
-                    rc = motion_table_t(scene - 1, scene, tab);
+                    rc = motion_table<T>(scene - 1, scene, tab);
                     if (!rc) if (hipError_t e = hipMemcpyAsync(base + off_tab, tab, tab_b, hipMemcpyHostToDevice, hc->stream); e != hipSuccess)
                         rc = fail((int)e, "upload of the motion table failed: %s", hipGetErrorString(e));
                 }
-                if (!rc) rc = launch_motion_t(hc->scene, cams + v, &pm, tab_b ? base + off_tab : nullptr, plane, hc->stream);
+                if (!rc) rc = launch_motion<T>(hc->scene, cams + v, &pm, tab_b ? base + off_tab : nullptr, plane, hc->stream);
             }
-            if (!rc) rc = launch_temporal_t(&tt, cams + v, v ? cams + (v - 1) : nullptr, 0, nullptr, p->width, p->height, img, feat, v ? base + R.off_st[(v & 1) ^ 1] : nullptr,
-                                            base + R.off_st[v & 1], base + R.off_acc + (size_t)v * R.frame_b, hc->stream, nullptr, nullptr, c, v ? plane : nullptr);
+            if (!rc) rc = launch_temporal<T>(&tt, cams + v, v ? cams + (v - 1) : nullptr, 0, nullptr, p->width, p->height, img, feat, v ? base + R.off_st[(v & 1) ^ 1] : nullptr,
+                                             base + R.off_st[v & 1], base + R.off_acc + (size_t)v * R.frame_b, hc->stream, nullptr, nullptr, c, v ? plane : nullptr);
         }
         if (!rc && d) {
             rtw_denoise_t dd = *d;
             dd.gamma = b ? 0 : (p->gamma != 0); dd.device = hc->device;
-            rc = launch_denoise_t(&dd, p->width, p->height, n_frames, (const T *)(base + R.off_acc), base + R.off_feat, base + R.off_flt, base + R.off_work, hc->stream);
+            rc = launch_denoise<T>(&dd, p->width, p->height, n_frames, base + R.off_acc, base + R.off_feat, base + R.off_flt, base + R.off_work, hc->stream);
         }
         if (b) {
             rtw_velocity_blur_t bb = *b;
             bb.gamma = p->gamma != 0; bb.device = hc->device;
             for (int v = 0; v < n_frames && !rc; ++v)
-                rc = launch_motion_blur_t(&bb, cams + v, v ? cams + (v - 1) : nullptr, p->width, p->height, base + (d ? R.off_flt : R.off_acc) + (size_t)v * R.frame_b,
-                                          base + R.off_feat + (size_t)v * feat_frame_b, base + off_mo + (size_t)v * mo_b, base + off_bwork, base + off_blur + (size_t)v * R.frame_b, hc->stream);
+                rc = launch_motion_blur<T>(&bb, cams + v, v ? cams + (v - 1) : nullptr, p->width, p->height, base + (d ? R.off_flt : R.off_acc) + (size_t)v * R.frame_b,
+                                           base + R.off_feat + (size_t)v * feat_frame_b, base + off_mo + (size_t)v * mo_b, base + off_bwork, base + off_blur + (size_t)v * R.frame_b, hc->stream);
         }
         return rc;
     }, {b ? off_blur : d ? R.off_flt : R.off_acc, out, R.img_b});

@@ -409,7 +409,7 @@ int upload_scene(const SceneT *s, int device, rtw_scene_handle *out) {
     return 0;
 }
 
-int upload_scene_f32(const rtw_scene_f32 *s, int device, rtw_scene_handle *out) { return upload_scene<float>(s, device, out); }
-int upload_scene_f64(const rtw_scene_f64 *s, int device, rtw_scene_handle *out) { return upload_scene<double>(s, device, out); }
+template int upload_scene<float>(const rtw_scene_f32 *, int, rtw_scene_handle *);
+template int upload_scene<double>(const rtw_scene_f64 *, int, rtw_scene_handle *);
 
 }  // namespace rtwh

@@ -28,7 +28,7 @@ int present_host(const rtw_present_t *p, int32_t width, int32_t height, const T 
     const size_t off_out = L.add(out_b);
     if (int rc = check_alias({{"out", out, out_b}}, {{"image", image, img_b}}, "the input")) return rc;
     return stage_one_device<T>(p->device, nullptr, L.total, "the frame", {{0, image, img_b}},
-                               [&](HostCtx *hc, char *base) { return launch_present_t(p, width, height, 0, (const T *)base, base + off_out, hc->stream); }, {off_out, out, out_b});
+                               [&](HostCtx *hc, char *base) { return launch_present<T>(p, width, height, 0, base, base + off_out, hc->stream); }, {off_out, out, out_b});
 }
 
 // The upsampler (rtw_upsample_* / rtw_upsample_batch_*): three H2D, prepare + `levels` + 1 launches for any number of views, ONE D2H.
@@ -70,9 +70,9 @@ int temporal_step_host(bool form_args, const rtw_temporal_t *t, const rtw_tempor
     return stage_one_device<T>(t->device, nullptr, motion ? L.total : R.total_m, "the temporal step's inputs",
         {{0, image, R.img_b}, {R.off_feat, features, R.feat_b}, {R.off_st[0], state_prev, R.st_b}, {R.off_mo[0], moment_prev, R.mo_b}, {off_motion, motion, motion_b}},
         [&](HostCtx *hc, char *base) {
-            int rc = launch_temporal_t(t, cam, cam_prev, 0, nullptr, width, height, base, base + R.off_feat, state_prev ? base + R.off_st[0] : nullptr, base + R.off_st[1], base + R.off_acc,
-                                       hc->stream, moment_prev ? base + R.off_mo[0] : nullptr, moments ? base + R.off_mo[1] : nullptr, c, motion ? base + off_motion : nullptr);
-            if (!rc && n) rc = launch_temporal_noise_t(n, width, height, 0, base + R.off_st[1], base + R.off_mo[1], (T *)(base + R.off_noise), hc->stream);
+            int rc = launch_temporal<T>(t, cam, cam_prev, 0, nullptr, width, height, base, base + R.off_feat, state_prev ? base + R.off_st[0] : nullptr, base + R.off_st[1], base + R.off_acc,
+                                        hc->stream, moment_prev ? base + R.off_mo[0] : nullptr, moments ? base + R.off_mo[1] : nullptr, c, motion ? base + off_motion : nullptr);
+            if (!rc && n) rc = launch_temporal_noise<T>(n, width, height, 0, base + R.off_st[1], base + R.off_mo[1], base + R.off_noise, hc->stream);
             return rc;
         },
         {R.off_acc, out, R.img_b}, {{R.off_st[1], state_next, R.st_b}, {R.off_mo[1], moment_next, R.mo_b}, {R.off_noise, n ? noise : nullptr, R.noise_b}},
@@ -91,7 +91,7 @@ int motion_blur_host(const rtw_velocity_blur_t *b, const CamT *cam, const CamT *
     const size_t off_feat = L.add(feat_b), off_mo = L.add(mo_b), off_out = L.add(img_b), off_work = L.add((size_t)rtw_velocity_blur_work_bytes(width, height, (int32_t)sizeof(T)));
     if (int rc = check_alias({{"out", out, img_b}}, {{"image", image, img_b}, {"features", features, feat_b}, {"motion", motion, mo_b}})) return rc;
     return stage_one_device<T>(b->device, nullptr, L.total, "the motion blur's inputs", {{0, image, img_b}, {off_feat, features, feat_b}, {off_mo, motion, mo_b}},
-        [&](HostCtx *hc, char *base) { return launch_motion_blur_t(b, cam, cam_prev, width, height, base, base + off_feat, base + off_mo, base + off_work, base + off_out, hc->stream); },
+        [&](HostCtx *hc, char *base) { return launch_motion_blur<T>(b, cam, cam_prev, width, height, base, base + off_feat, base + off_mo, base + off_work, base + off_out, hc->stream); },
         {off_out, out, img_b});
 }
 
@@ -109,11 +109,11 @@ int lens_host(int top, const char *what, const rtw_wide_aperture_t *b, const Cam
     const LensBatchLayout R(sizeof(T), width, height, b->max_radius, n_views, n_frames);
     if (int rc = check_alias({{"out", out, R.out_b}}, {{n_views ? "images" : "image", images, R.img_b}, {"features", features, R.feat_b}})) return rc;
     std::vector<T> table;                                      // (a batch's alone: R.tab_b == 0 for one view, and nothing goes up)
-    if (n_views) { table.resize((size_t)n_views * 32); lens_table_t(lens, cams, width, table.data()); }
+    if (n_views) { table.resize((size_t)n_views * 32); lens_table<T>(lens, cams, width, table.data()); }
     return stage_one_device<T>(b->device, nullptr, R.total, what, {{0, images, R.img_b}, {R.off_feat, features, R.feat_b}, {R.off_tab, table.data(), R.tab_b}},
         [&](HostCtx *hc, char *base) {
             const LensViews vb = lens_views(R, n_views, base + R.off_tab);
-            return launch_wide_aperture_t(b, cams, width, height, base, base + R.off_feat, base + R.off_work, base + R.off_out, hc->stream, n_views ? &vb : nullptr);
+            return launch_wide_aperture<T>(b, cams, width, height, base, base + R.off_feat, base + R.off_work, base + R.off_out, hc->stream, n_views ? &vb : nullptr);
         },
         {R.off_out, out, R.out_b});
 }

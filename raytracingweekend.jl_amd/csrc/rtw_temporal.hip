@@ -121,8 +121,8 @@ int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
     Q.plane = (const V *)d_motion;
     // (measurement aid, tools/gpu_temporal.py: events around the kernel, reported on stderr -- this one blocks)
     static const bool profile = aid_flag("RTW_TEMPORAL_PROFILE");
-    struct Events { hipEvent_t e[2] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
-    if (profile) { for (hipEvent_t &x : events.e) HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventRecord(events.e[0], stream)); }
+    StageMarks marks(profile, stream);
+    HIP_TRY(marks.mark());
     (void)hipGetLastError();
     const T *mp = (const T *)d_moment_prev;
     T *mn = (T *)d_moment_next;
@@ -165,20 +165,19 @@ int launch_temporal(const rtw_temporal_t *t, const CamT *cam, const CamT *cam_pr
     }
     HIP_TRY(hipGetLastError());
     if (profile) {
-        float ms = 0;
-        HIP_TRY(hipEventRecord(events.e[1], stream));
-        HIP_TRY(hipEventSynchronize(events.e[1]));
-        HIP_TRY(hipEventElapsedTime(&ms, events.e[0], events.e[1]));
+        HIP_TRY(marks.mark());
+        HIP_TRY(marks.measure());
+        const float ms = marks.ms[0];
         if (c && sp) fprintf(stderr, "[rtw temporal] %s %dx%d %s r=%d guides=%d paths=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, d_motion ? (mn ? "clamped+moments+motion" : "clamped+motion") : mn ? "clamped+moments" : "clamped", c->radius, c->flags & RTW_CLAMP_GUIDES, n_paths, ms);
         else fprintf(stderr, "[rtw temporal] %s %dx%d %s prev=%d paths=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, d_motion ? (mn ? "step+moments+motion" : "step+motion") : mn ? "step+moments" : "step", sp ? 1 : 0, n_paths, ms);
     }
     return 0;
 }
 
-int launch_temporal_f32(const rtw_temporal_t *t, const rtw_camera_f32 *cam, const rtw_camera_f32 *cam_prev, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn, const rtw_temporal_clamp_t *c, const void *mv) { return launch_temporal<float>(t, cam, cam_prev, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, c, mv); }
-int launch_temporal_f64(const rtw_temporal_t *t, const rtw_camera_f64 *cam, const rtw_camera_f64 *cam_prev, int32_t np, const void *tab, int32_t w, int32_t h, const void *img, const void *feat, const void *sp, void *sn, void *out, hipStream_t st, const void *mp, void *mn, const rtw_temporal_clamp_t *c, const void *mv) { return launch_temporal<double>(t, cam, cam_prev, np, tab, w, h, img, feat, sp, sn, out, st, mp, mn, c, mv); }
-void temporal_table_f32(const rtw_camera_f32 *cams, const rtw_camera_f32 *cams_prev, int64_t n, float *table) { for (int64_t s = 0; s < n; ++s) temporal_table_entry<float>(cams + s, cams_prev ? cams_prev + s : nullptr, table + 32 * s); }
-void temporal_table_f64(const rtw_camera_f64 *cams, const rtw_camera_f64 *cams_prev, int64_t n, double *table) { for (int64_t s = 0; s < n; ++s) temporal_table_entry<double>(cams + s, cams_prev ? cams_prev + s : nullptr, table + 32 * s); }
+template <typename T, typename CamT>
+void temporal_table(const CamT *cams, const CamT *cams_prev, int64_t n, T *table) {
+    for (int64_t s = 0; s < n; ++s) temporal_table_entry<T>(cams + s, cams_prev ? cams_prev + s : nullptr, table + 32 * s);
+}
 
 // Enqueue the noise map of a state and its moment plane on `stream` of the current device (validate_temporal_noise has accepted the call): ONE launch.
 // n_paths >= 1 (rtw_reproject_noise_batch_device_*): the maps of that many states and planes, one behind the other, in the same single launch.
@@ -197,8 +196,8 @@ int launch_temporal_noise(const rtw_temporal_noise_t *n, int32_t width, int32_t 
     const unsigned grid = (unsigned)((n_pix + 255) / 256);
     // (measurement aid, tools/gpu_temporal_noise.py: events around the kernel, reported on stderr -- this one blocks)
     static const bool profile = aid_flag("RTW_TEMPORAL_PROFILE");
-    struct Events { hipEvent_t e[2] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
-    if (profile) { for (hipEvent_t &x : events.e) HIP_TRY(hipEventCreate(&x)); HIP_TRY(hipEventRecord(events.e[0], stream)); }
+    StageMarks marks(profile, stream);
+    HIP_TRY(marks.mark());
     (void)hipGetLastError();
     if (n_paths) hipLaunchKernelGGL((rtw::tp_noise<T, true>), paths_grid(grid, n_paths), dim3(256), 0, stream, U, (const V *)sp, (const V *)(sp + pb), (const T *)(sp + 2 * pb), (const T *)d_moment,
                                     (T *)d_noise, rtw::TpPaths<T, true>{nullptr, state_bytes(width, height, sizeof(T)), moment_bytes(width, height, sizeof(T)), (unsigned)n_paths});
@@ -206,17 +205,13 @@ int launch_temporal_noise(const rtw_temporal_noise_t *n, int32_t width, int32_t 
                             rtw::TpPaths<T, false>());
     HIP_TRY(hipGetLastError());
     if (profile) {
-        float ms = 0;
-        HIP_TRY(hipEventRecord(events.e[1], stream));
-        HIP_TRY(hipEventSynchronize(events.e[1]));
-        HIP_TRY(hipEventElapsedTime(&ms, events.e[0], events.e[1]));
+        HIP_TRY(marks.mark());
+        HIP_TRY(marks.measure());
+        const float ms = marks.ms[0];
         fprintf(stderr, "[rtw temporal] %s %dx%d noise r=%d paths=%d ms=%.5f\n", sizeof(T) == 8 ? "f64" : "f32", width, height, n->radius, n_paths, ms);
     }
     return 0;
 }
-
-int launch_temporal_noise_f32(const rtw_temporal_noise_t *n, int32_t w, int32_t h, int32_t np, const void *st, const void *mo, void *noise, hipStream_t s) { return launch_temporal_noise<float>(n, w, h, np, st, mo, noise, s); }
-int launch_temporal_noise_f64(const rtw_temporal_noise_t *n, int32_t w, int32_t h, int32_t np, const void *st, const void *mo, void *noise, hipStream_t s) { return launch_temporal_noise<double>(n, w, h, np, st, mo, noise, s); }
 
 // The device-resident entry points of a step: nulls, the parameters, then the pointers' alignment and aliasing.  `moments`:
 // rtw_history_moments_device_*, the same with the two moment planes (d_moment_prev null exactly when d_state_prev is).  `clamped`:
@@ -332,6 +327,13 @@ int temporal_noise_device(const rtw_temporal_noise_t *n, int32_t width, int32_t 
     return launch_temporal_noise<T>(n, width, height, 0, d_state, d_moment, d_noise, (hipStream_t)stream_v);
 }
 
+template int launch_temporal<float>(const rtw_temporal_t *, const rtw_camera_f32 *, const rtw_camera_f32 *, int32_t, const void *, int32_t, int32_t, const void *, const void *, const void *, void *, void *, hipStream_t, const void *, void *, const rtw_temporal_clamp_t *, const void *);
+template int launch_temporal<double>(const rtw_temporal_t *, const rtw_camera_f64 *, const rtw_camera_f64 *, int32_t, const void *, int32_t, int32_t, const void *, const void *, const void *, void *, void *, hipStream_t, const void *, void *, const rtw_temporal_clamp_t *, const void *);
+template void temporal_table<float>(const rtw_camera_f32 *, const rtw_camera_f32 *, int64_t, float *);
+template void temporal_table<double>(const rtw_camera_f64 *, const rtw_camera_f64 *, int64_t, double *);
+template int launch_temporal_noise<float>(const rtw_temporal_noise_t *, int32_t, int32_t, int32_t, const void *, const void *, void *, hipStream_t);
+template int launch_temporal_noise<double>(const rtw_temporal_noise_t *, int32_t, int32_t, int32_t, const void *, const void *, void *, hipStream_t);
+
 }  // namespace rtwh
 
 using namespace rtwh;
@@ -400,13 +402,13 @@ int64_t rtw_reproject_table_bytes(int32_t n_paths, int32_t elem_bytes) {
 int rtw_reproject_table_f32(const rtw_camera_f32 *cams, const rtw_camera_f32 *cams_prev, int32_t n_paths, void *table) {
     if (!cams || !table) return fail(-1, "null argument");
     if (n_paths < 1) return fail(-2, "n_paths must be >= 1 (got %d)", n_paths);
-    temporal_table_f32(cams, cams_prev, n_paths, (float *)table);
+    temporal_table<float>(cams, cams_prev, n_paths, (float *)table);
     return 0;
 }
 int rtw_reproject_table_f64(const rtw_camera_f64 *cams, const rtw_camera_f64 *cams_prev, int32_t n_paths, void *table) {
     if (!cams || !table) return fail(-1, "null argument");
     if (n_paths < 1) return fail(-2, "n_paths must be >= 1 (got %d)", n_paths);
-    temporal_table_f64(cams, cams_prev, n_paths, (double *)table);
+    temporal_table<double>(cams, cams_prev, n_paths, (double *)table);
     return 0;
 }
 int rtw_reproject_batch_device_f32(const rtw_temporal_t *t, const rtw_temporal_clamp_t *c, int32_t n_paths, const void *d_table, int32_t width, int32_t height, const void *d_images,

@@ -35,7 +35,7 @@ int run_unit(int op_arg, int count, const void *in, void *out, const SceneT *sce
     rtw::CullScene<T> CS;
     memset(&CS, 0, sizeof CS);
     if (needs_scene) {
-        if (int rc = upload_scene_t(scene, dev, &h_raw)) return rc;
+        if (int rc = upload_scene<T>(scene, dev, &h_raw)) return rc;
         S = dev_scene_of<T>(h_raw);
         CS = cull_scene_of<T>(h_raw);
     }
@@ -73,7 +73,7 @@ int run_unit(int op_arg, int count, const void *in, void *out, const SceneT *sce
     return rc;
 }
 
-int run_unit_f32(int op, int count, const void *in, void *out, const rtw_scene_f32 *scene, const rtw_camera_f32 *cam) { return run_unit<float>(op, count, in, out, scene, cam); }
-int run_unit_f64(int op, int count, const void *in, void *out, const rtw_scene_f64 *scene, const rtw_camera_f64 *cam) { return run_unit<double>(op, count, in, out, scene, cam); }
+template int run_unit<float>(int, int, const void *, void *, const rtw_scene_f32 *, const rtw_camera_f32 *);
+template int run_unit<double>(int, int, const void *, void *, const rtw_scene_f64 *, const rtw_camera_f64 *);
 
 }  // namespace rtwh

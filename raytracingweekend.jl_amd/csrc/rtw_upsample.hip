@@ -48,15 +48,12 @@ int launch_upsample(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height
     const unsigned grid_lo = (unsigned)((n_lo + 255) / 256), grid_hi = (unsigned)((n_hi + 255) / 256);
     // (measurement aid, tools/gpu_upsample.py: events around every kernel, reported on stderr -- this one blocks)
     static const bool profile = aid_flag("RTW_DENOISE_PROFILE");
-    struct Events { hipEvent_t e[11] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
-    hipEvent_t *ev = events.e;
-    const int n_ev = u->levels + 3;                    // before prepare, behind prepare, behind every level, behind the upsampling
-    if (profile) for (int k = 0; k < n_ev; ++k) HIP_TRY(hipEventCreate(&ev[k]));
-    if (profile) HIP_TRY(hipEventRecord(ev[0], stream));
+    StageMarks marks(profile, stream);                 // before prepare, behind prepare, behind every level, behind the upsampling
+    HIP_TRY(marks.mark());
     (void)hipGetLastError();
     hipLaunchKernelGGL((rtw::dn_prepare<T, false>), dim3(grid_lo), dim3(256), 0, stream, (const T *)d_image_lo, (const V *)d_features_lo, E[0], G, A, n_lo, demod ? 1 : 0, (const T *)nullptr);
     HIP_TRY(hipGetLastError());
-    if (profile) HIP_TRY(hipEventRecord(ev[1], stream));
+    HIP_TRY(marks.mark());
     const T inv_sz = (T)(1.0 / (u->sigma_depth * u->sigma_depth));
     for (int k = 0; k < u->levels; ++k) {
         rtw::DnLevel<T> L;
@@ -74,7 +71,7 @@ int launch_upsample(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height
             hipLaunchKernelGGL((rtw::dn_level_batch<T, false>), dim3(grid_lo), dim3(256), 0, stream, LB, in, (const V *)G, (const V *)A, next, (T *)nullptr);
         } else hipLaunchKernelGGL((rtw::dn_level<T, false>), dim3(grid_lo), dim3(256), 0, stream, L, in, (const V *)G, (const V *)A, next, (T *)nullptr);
         HIP_TRY(hipGetLastError());
-        if (profile) HIP_TRY(hipEventRecord(ev[k + 2], stream));
+        HIP_TRY(marks.mark());
     }
     rtw::UpParamsBatch<T> B;
     B.U.inv_sa = (T)(1.0 / (u->sigma_albedo * u->sigma_albedo));
@@ -88,28 +85,21 @@ int launch_upsample(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height
     else hipLaunchKernelGGL((rtw::up_sample<T, false>), dim3(grid_hi), dim3(256), 0, stream, B, Ef, (const V *)G, (const V *)A, (const V *)d_features_hi, (T *)d_out);
     HIP_TRY(hipGetLastError());
     if (profile) {
-        HIP_TRY(hipEventRecord(ev[n_ev - 1], stream));
+        HIP_TRY(marks.mark());
         const char *ts = sizeof(T) == 8 ? "f64" : "f32";
         char size[96];                                                          // (a batch: " views=N" behind the sizes)
         if (batch) snprintf(size, sizeof size, "%dx%d->%dx%d views=%d", lo_width, lo_height, width, height, n_views);
         else snprintf(size, sizeof size, "%dx%d->%dx%d", lo_width, lo_height, width, height);
-        HIP_TRY(hipEventSynchronize(ev[n_ev - 1]));
-        for (int k = 0; k + 1 < n_ev; ++k) {
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-            if (k == 0) fprintf(stderr, "[rtw upsample] %s %s prepare ms=%.5f\n", ts, size, ms);
-            else if (k <= u->levels) fprintf(stderr, "[rtw upsample] %s %s level step=%d ms=%.5f\n", ts, size, 1 << (k - 1), ms);
-            else fprintf(stderr, "[rtw upsample] %s %s upsample ms=%.5f\n", ts, size, ms);
+        HIP_TRY(marks.measure());
+        for (int k = 0; k + 1 < marks.n; ++k) {
+            if (k == 0) fprintf(stderr, "[rtw upsample] %s %s prepare ms=%.5f\n", ts, size, marks.ms[k]);
+            else if (k <= u->levels) fprintf(stderr, "[rtw upsample] %s %s level step=%d ms=%.5f\n", ts, size, 1 << (k - 1), marks.ms[k]);
+            else fprintf(stderr, "[rtw upsample] %s %s upsample ms=%.5f\n", ts, size, marks.ms[k]);
         }
-        float all_ms = 0;
-        HIP_TRY(hipEventElapsedTime(&all_ms, ev[0], ev[n_ev - 1]));
-        fprintf(stderr, "[rtw upsample] %s %s total levels=%d ms=%.5f\n", ts, size, u->levels, all_ms);
+        fprintf(stderr, "[rtw upsample] %s %s total levels=%d ms=%.5f\n", ts, size, u->levels, marks.total_ms);
     }
     return 0;
 }
-
-int launch_upsample_f32(const rtw_upsample_t *u, int32_t lw, int32_t lh, int32_t w, int32_t h, int32_t n_views, const void *img, const void *flo, const void *fhi, void *out, void *work, hipStream_t st) { return launch_upsample<float>(u, lw, lh, w, h, n_views, img, flo, fhi, out, work, st); }
-int launch_upsample_f64(const rtw_upsample_t *u, int32_t lw, int32_t lh, int32_t w, int32_t h, int32_t n_views, const void *img, const void *flo, const void *fhi, void *out, void *work, hipStream_t st) { return launch_upsample<double>(u, lw, lh, w, h, n_views, img, flo, fhi, out, work, st); }
 
 // The device-resident entry points.  n_views == 0: rtw_upsample_device_*; n_views != 0: rtw_upsample_batch_device_*.  The alignment and aliasing
 // checks cover the extents of all frames.
@@ -131,6 +121,9 @@ int upsample_device(const rtw_upsample_t *u, int32_t lo_width, int32_t lo_height
     if (u->device >= 0) HIP_TRY(hipSetDevice(u->device));
     return launch_upsample<T>(u, lo_width, lo_height, width, height, n_views, d_image_lo, d_features_lo, d_features_hi, d_out, d_work, (hipStream_t)stream_v);
 }
+
+template int launch_upsample<float>(const rtw_upsample_t *, int32_t, int32_t, int32_t, int32_t, int32_t, const void *, const void *, const void *, void *, void *, hipStream_t);
+template int launch_upsample<double>(const rtw_upsample_t *, int32_t, int32_t, int32_t, int32_t, int32_t, const void *, const void *, const void *, void *, void *, hipStream_t);
 
 }  // namespace rtwh
 

@@ -19,11 +19,6 @@ static rtw_defocus_t as_defocus(const rtw_wide_aperture_t *b) {
     return d;
 }
 
-static int prepare_t(const rtw_defocus_t *b, int rm, const rtw_camera_f32 *c, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st, int32_t nv, const void *tab, const long long *sb) { return launch_defocus_prepare_f32(b, rm, c, w, h, img, feat, coc, tile, st, nv, tab, sb); }
-static int prepare_t(const rtw_defocus_t *b, int rm, const rtw_camera_f64 *c, int32_t w, int32_t h, const void *img, const void *feat, void *coc, void *tile, hipStream_t st, int32_t nv, const void *tab, const long long *sb) { return launch_defocus_prepare_f64(b, rm, c, w, h, img, feat, coc, tile, st, nv, tab, sb); }
-static int gather_t(float, int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st, int32_t nv, const long long *sb) { return launch_defocus_gather_f32(w, h, mmax, gamma, img, coc, tile, out, st, nv, sb); }
-static int gather_t(double, int32_t w, int32_t h, int mmax, int gamma, const void *img, const void *coc, const void *tile, void *out, hipStream_t st, int32_t nv, const long long *sb) { return launch_defocus_gather_f64(w, h, mmax, gamma, img, coc, tile, out, st, nv, sb); }
-
 // Enqueue the stage on `stream` of the current device (validate_lens has accepted the call): SIX launches, no record.
 // vb null: one view.  vb given: vb->n_views views in the same six launches -- cam and d's lens are unused (the table); every region of the
 // workspace lies at the single stage's offset inside its view's workspace, so one stride serves all of them.
@@ -43,19 +38,16 @@ static int launch_scaled(const rtw_defocus_t *d, const CamT *cam, int32_t width,
     const long long s_prepare[4] = {si, sf, sw, sw}, s_gather[4] = {si, sw, sw, sw}, s_small[4] = {sw, sw, sw, sw};
     // (measurement aid, tools/gpu_wide_aperture.py: events around every launch, reported on stderr -- this one blocks)
     static const bool profile = aid_flag("RTW_TEMPORAL_PROFILE");
-    struct Events { hipEvent_t e[7] = {}; ~Events() { for (hipEvent_t x : e) if (x) HIP_IGNORE(hipEventDestroy(x)); } } events;
-    int k = 0;
-    auto mark = [&]() -> int { if (profile) HIP_TRY(hipEventRecord(events.e[k++], stream)); return 0; };
-    if (profile) for (hipEvent_t &x : events.e) HIP_TRY(hipEventCreate(&x));
-    if (int rc = mark()) return rc;
+    StageMarks marks(profile, stream);
+    HIP_TRY(marks.mark());
     // 1, 2: the narrow frame N -- the defocus stage with max_radius 8, linear
-    if (int rc = prepare_t(d, RTW_DEFOCUS_MAX_RADIUS, cam, width, height, d_image, d_features, n_coc, n_tile, stream, nv, tab, s_prepare)) return rc;
-    if (int rc = mark()) return rc;
-    if (int rc = gather_t(T(), width, height, RTW_DEFOCUS_MAX_RADIUS, 0, d_image, n_coc, n_tile, narrow, stream, nv, s_gather)) return rc;
-    if (int rc = mark()) return rc;
+    if (int rc = launch_defocus_prepare<T>(d, RTW_DEFOCUS_MAX_RADIUS, cam, width, height, d_image, d_features, n_coc, n_tile, stream, nv, tab, s_prepare)) return rc;
+    HIP_TRY(marks.mark());
+    if (int rc = launch_defocus_gather<T>(width, height, RTW_DEFOCUS_MAX_RADIUS, 0, d_image, n_coc, n_tile, narrow, stream, nv, s_gather)) return rc;
+    HIP_TRY(marks.mark());
     // 3: the wide CoC plane
-    if (int rc = prepare_t(d, d->max_radius, cam, width, height, d_image, d_features, coc, tile, stream, nv, tab, s_prepare)) return rc;
-    if (int rc = mark()) return rc;
+    if (int rc = launch_defocus_prepare<T>(d, d->max_radius, cam, width, height, d_image, d_features, coc, tile, stream, nv, tab, s_prepare)) return rc;
+    HIP_TRY(marks.mark());
     // 4: the reduced frame
     (void)hipGetLastError();
     if (nv) hipLaunchKernelGGL((rtw::wa_reduce<T, S, true>), lens_views_grid(lo_tiles, nv), dim3(256), 0, stream, width, height, (const T *)d_image, (const V *)coc, lo_img, (V *)lo_coc, lo_tile,
@@ -63,10 +55,10 @@ static int launch_scaled(const rtw_defocus_t *d, const CamT *cam, int32_t width,
     else hipLaunchKernelGGL((rtw::wa_reduce<T, S, false>), dim3(lo_tiles), dim3(256), 0, stream, width, height, (const T *)d_image, (const V *)coc, lo_img, (V *)lo_coc, lo_tile,
                             rtw::DfViews<T, false, 5>());
     HIP_TRY(hipGetLastError());
-    if (int rc = mark()) return rc;
+    HIP_TRY(marks.mark());
     // 5: the small gather
-    if (int rc = gather_t(T(), L.lo_width, L.lo_height, L.lo_mmax, 0, lo_img, lo_coc, lo_tile, lo_out, stream, nv, s_small)) return rc;
-    if (int rc = mark()) return rc;
+    if (int rc = launch_defocus_gather<T>(L.lo_width, L.lo_height, L.lo_mmax, 0, lo_img, lo_coc, lo_tile, lo_out, stream, nv, s_small)) return rc;
+    HIP_TRY(marks.mark());
     // 6: the blend by radius
     (void)hipGetLastError();
     if (nv) hipLaunchKernelGGL((rtw::wa_compose<T, S, true>), lens_views_grid(tiles, nv), dim3(256), 0, stream, width, height, d->gamma, (const V *)coc, (const T *)narrow, (const V *)lo_coc,
@@ -74,13 +66,12 @@ static int launch_scaled(const rtw_defocus_t *d, const CamT *cam, int32_t width,
     else hipLaunchKernelGGL((rtw::wa_compose<T, S, false>), dim3(tiles), dim3(256), 0, stream, width, height, d->gamma, (const V *)coc, (const T *)narrow, (const V *)lo_coc, (const T *)lo_out,
                             (T *)d_out, rtw::DfViews<T, false, 5>());
     HIP_TRY(hipGetLastError());
-    if (int rc = mark()) return rc;
+    HIP_TRY(marks.mark());
     if (profile) {
-        float ms[6] = {0, 0, 0, 0, 0, 0};
+        const float *ms = marks.ms;
         char views[32] = "";
         if (nv) snprintf(views, sizeof views, " n_views=%d", nv);
-        HIP_TRY(hipEventSynchronize(events.e[6]));
-        for (int q = 0; q < 6; ++q) HIP_TRY(hipEventElapsedTime(&ms[q], events.e[q], events.e[q + 1]));
+        HIP_TRY(marks.measure());
         fprintf(stderr, "[rtw wide_aperture] %s %dx%d max_radius=%d%s prepare_ms=%.5f gather_ms=%.5f wide_prepare_ms=%.5f reduce_ms=%.5f small_gather_ms=%.5f compose_ms=%.5f\n",
                 sizeof(T) == 8 ? "f64" : "f32", width, height, d->max_radius, views, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5]);
     }
@@ -88,16 +79,13 @@ static int launch_scaled(const rtw_defocus_t *d, const CamT *cam, int32_t width,
 }
 
 template <typename T, typename CamT>
-static int launch_wide_aperture(const rtw_wide_aperture_t *b, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream,
+int launch_wide_aperture(const rtw_wide_aperture_t *b, const CamT *cam, int32_t width, int32_t height, const void *d_image, const void *d_features, void *d_work, void *d_out, hipStream_t stream,
                                 const LensViews *vb) {
     const rtw_defocus_t d = as_defocus(b);
-    if (d.max_radius <= RTW_DEFOCUS_MAX_RADIUS) return launch_defocus_t(&d, cam, width, height, d_image, d_features, d_work, d_out, stream, vb);     // (scale 1: the defocus stage itself)
+    if (d.max_radius <= RTW_DEFOCUS_MAX_RADIUS) return launch_defocus<T>(&d, cam, width, height, d_image, d_features, d_work, d_out, stream, vb);     // (scale 1: the defocus stage itself)
     if (d.max_radius <= 16) return launch_scaled<T, 2>(&d, cam, width, height, d_image, d_features, d_work, d_out, stream, vb);
     return launch_scaled<T, 4>(&d, cam, width, height, d_image, d_features, d_work, d_out, stream, vb);
 }
-
-int launch_wide_aperture_f32(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb) { return launch_wide_aperture<float>(b, cam, w, h, img, feat, work, out, st, vb); }
-int launch_wide_aperture_f64(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cam, int32_t w, int32_t h, const void *img, const void *feat, void *work, void *out, hipStream_t st, const LensViews *vb) { return launch_wide_aperture<double>(b, cam, w, h, img, feat, work, out, st, vb); }
 
 // ---- the batch (rtw_lens_batch_*, rtw_lens_table_*) -----------------------------------------------------------------------------
 // the batch's own size rule: the batched filter's frame rule on (width, height, number of views)
@@ -107,8 +95,8 @@ static int check_views_size(int32_t width, int32_t height, int32_t n_views) {
 }
 
 template <typename CamT>
-static int validate_lens_batch_t(const rtw_wide_aperture_t *b, const CamT *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens,
-                                 int top, std::vector<rtw_defocus_t> *lens_out) {
+int validate_lens_batch(const rtw_wide_aperture_t *b, const CamT *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, int top,
+                        std::vector<rtw_defocus_t> *lens_out) {
     if (!b || !cams) return fail(-1, "null lens parameters or cameras");
     if (n_views < 1) return fail(-2, "n_views must be >= 1 (got %d)", n_views);
     if (lens_out) lens_out->clear();
@@ -128,10 +116,10 @@ static int validate_lens_batch_t(const rtw_wide_aperture_t *b, const CamT *cams,
     }
     return check_views_size(width, height, n_views);
 }
-int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f32 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, int top, std::vector<rtw_defocus_t> *lens_out) { return validate_lens_batch_t(b, cams, n_views, width, height, lens_radii, focus_dists, own_lens, top, lens_out); }
-int validate_lens_batch(const rtw_wide_aperture_t *b, const rtw_camera_f64 *cams, int32_t n_views, int32_t width, int32_t height, const double *lens_radii, const double *focus_dists, bool own_lens, int top, std::vector<rtw_defocus_t> *lens_out) { return validate_lens_batch_t(b, cams, n_views, width, height, lens_radii, focus_dists, own_lens, top, lens_out); }
-void lens_table_f32(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f32 *cams, int32_t width, float *table) { for (size_t v = 0; v < lens.size(); ++v) lens_table_entry_f32(&lens[v], cams + v, width, table + 32 * v); }
-void lens_table_f64(const std::vector<rtw_defocus_t> &lens, const rtw_camera_f64 *cams, int32_t width, double *table) { for (size_t v = 0; v < lens.size(); ++v) lens_table_entry_f64(&lens[v], cams + v, width, table + 32 * v); }
+template <typename T, typename CamT>
+void lens_table(const std::vector<rtw_defocus_t> &lens, const CamT *cams, int32_t width, T *table) {
+    for (size_t v = 0; v < lens.size(); ++v) lens_table_entry<T>(&lens[v], cams + v, width, table + 32 * v);
+}
 
 // What a batched entry point checks of its counts and frame before it looks at a view.  The device form stops here: it has no camera and
 // reads no lens, so of validate_lens's four parts the parameters and the frame remain, with their codes.
@@ -172,9 +160,16 @@ static int lens_table_host(const rtw_wide_aperture_t *b, const CamT *cams, int32
     if (!b || !cams || !table) return fail(-1, "null argument");
     std::vector<rtw_defocus_t> lens;
     if (int rc = validate_lens_batch(b, cams, n_views, width, height, lens_radii, focus_dists, false, RTW_WIDE_APERTURE_MAX_RADIUS, &lens)) return rc;
-    lens_table_t(lens, cams, width, (T *)table);
+    lens_table<T>(lens, cams, width, (T *)table);
     return 0;
 }
+
+template int launch_wide_aperture<float>(const rtw_wide_aperture_t *, const rtw_camera_f32 *, int32_t, int32_t, const void *, const void *, void *, void *, hipStream_t, const LensViews *);
+template int launch_wide_aperture<double>(const rtw_wide_aperture_t *, const rtw_camera_f64 *, int32_t, int32_t, const void *, const void *, void *, void *, hipStream_t, const LensViews *);
+template int validate_lens_batch(const rtw_wide_aperture_t *, const rtw_camera_f32 *, int32_t, int32_t, int32_t, const double *, const double *, bool, int, std::vector<rtw_defocus_t> *);
+template int validate_lens_batch(const rtw_wide_aperture_t *, const rtw_camera_f64 *, int32_t, int32_t, int32_t, const double *, const double *, bool, int, std::vector<rtw_defocus_t> *);
+template void lens_table<float>(const std::vector<rtw_defocus_t> &, const rtw_camera_f32 *, int32_t, float *);
+template void lens_table<double>(const std::vector<rtw_defocus_t> &, const rtw_camera_f64 *, int32_t, double *);
 
 }  // namespace rtwh
 
