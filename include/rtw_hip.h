@@ -1564,6 +1564,55 @@ int rtw_render_presented_batch_f32(const rtw_scene_f32 *scene, const rtw_camera_
 int rtw_render_presented_batch_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cams, int32_t n_views, const uint64_t *seeds,
                                    const rtw_params *params, const rtw_denoise_t *d /* may be NULL */, const rtw_present_t *p, uint8_t *out);
 
+/* Ray queries: the closest hit of caller-supplied rays against the whole sphere list.  Everything above reaches the intersection routine
+ * through pixels; this block hands it out as it is -- for picking under a position that is no pixel centre, visibility and shadow tests
+ * between points, collision and line-of-sight queries, light baking, or an integrator of the caller's own on the host.
+ *
+ * The definition.  Arithmetic is in T; nothing is normalised.
+ *   A ray is 8 elements of T, rays one behind the other: ox, oy, oz, dx, dy, dz, tmax, tag.  `tag` is the caller's (a pixel index, a
+ * payload) and is never read.  Directions are expected to be of unit length to rounding, as every ray of the reference is (its hit()
+ * drops `a`); the result is nevertheless DEFINED for every finite ray as what the formula gives, without a normalisation.  tmax = +inf
+ * is legal; other non-finite elements are outside the contract.
+ *   The result for ray i is idx[i] (int32_t) and, where asked for, 8 elements of T at rec[8 i]: t, px, py, pz, nx, ny, nz, front.
+ * idx[i] is the sphere's 0-based index in the CALLER's list, or -1; front is 1 or 0; the record is all +0 on a miss.
+ *   The values are those of the reference's hit(::HittableList) with (tmin, tmax_i), in the numerics mode of the call's flags
+ * (RTW_FLAG_NUMERICS_*), on the bits: the spheres are tested in the caller's order, `closest` starts at tmax_i, a root is rejected when
+ * root < tmin || closest < root -- so the LATER of two spheres with the same root wins (the reference's rule, not the motion pass's) --
+ * and the record is p = o + t d, n_out = (p - c) / r, front = d.n_out < 0, n = front ? n_out : -n_out, each operation rounded once.
+ * tmin is one value per call; tmax lives in the ray.
+ *
+ * rtw_rays_params.  flags: RTW_FLAG_SCAN_VALU and the two RTW_FLAG_NUMERICS_* bits (they exclude each other); RTW_FLAG_GROUP_CULL is
+ * accepted and runs the same scans, as the feature pass does; any other bit -> -2.  device: as in rtw_params.  max_workgroups: 0 =
+ * automatic, otherwise >= 1, a cap on the kernel's persistent grid -- scheduling only, the words are identical for every value.
+ * reserved: 0.  tmin: finite and >= 0, converted to T once; 1e-4 is the reference's.
+ *
+ * rtw_cast_rays_device_*: ONE launch, asynchronous on `hip_stream` of the scene's device, re-entrant like rtw_render_features_device_*.
+ * `d_rays` (n * 8 elements) and `d_rec` (n * 8 elements, may be NULL: indices only) are 16-byte aligned DEVICE pointers, `d_idx` (n
+ * int32_t) is 4-byte aligned; nothing beyond ray n - 1 is read or written.  rtw_stats() afterwards reports samples = segments = n,
+ * sphere_tests = n x spheres and the kernel time.
+ *   rtw_cast_rays_*: the host-buffer form, blocking, through the cached per-device context like rtw_render_features_f32 (the scene is
+ * uploaded, or reused when its bytes are the same): one H2D of the rays, one launch, one D2H of `idx` and, where asked for, one of `rec`.
+ *   Refusals, all decided before any HIP call: a null argument other than rec -> -1; n < 0, a flag bit that is not named above, both
+ * numerics bits, reserved != 0, device < -1, max_workgroups < 0, a tmin that is not finite or is negative, d_rays or d_rec not 16-byte
+ * aligned, d_idx not 4-byte aligned, host buffers that overlap -> -2; a handle of the other precision or of another device -> -4;
+ * n >= 2^31 -> -5.  n == 0 -> 0 with nothing enqueued (rtw_stats() is left alone).
+ *   Left out on purpose: an early-exit any-hit mode (rec == NULL is the occlusion query today, and it pays the full
+ * scan), the group cull on caller rays, a tmin per ray, scatter and shading of the hits, device lists, the Julia shim.
+ * Additive to ABI 4: detected by symbol lookup. */
+typedef struct {
+    int32_t flags;            /* RTW_FLAG_SCAN_VALU, RTW_FLAG_GROUP_CULL, RTW_FLAG_NUMERICS_*                    */
+    int32_t device;           /* HIP ordinal, or -1 = the current device (device form: the handle's)         */
+    int32_t max_workgroups;   /* 0 = automatic, else a cap on the persistent grid (scheduling only)          */
+    int32_t reserved;         /* 0                                                                           */
+    double tmin;              /* finite, >= 0; converted to T once (the reference's: 1e-4)                   */
+} rtw_rays_params;            /* 24 bytes */
+int rtw_cast_rays_device_f32(rtw_scene_handle scene, const void *d_rays, int64_t n, const rtw_rays_params *p, void *d_idx, void *d_rec /* may be NULL */,
+                             void *hip_stream);
+int rtw_cast_rays_device_f64(rtw_scene_handle scene, const void *d_rays, int64_t n, const rtw_rays_params *p, void *d_idx, void *d_rec /* may be NULL */,
+                             void *hip_stream);
+int rtw_cast_rays_f32(const rtw_scene_f32 *scene, const float *rays, int64_t n, const rtw_rays_params *p, int32_t *idx, float *rec /* may be NULL */);
+int rtw_cast_rays_f64(const rtw_scene_f64 *scene, const double *rays, int64_t n, const rtw_rays_params *p, int32_t *idx, double *rec /* may be NULL */);
+
 /* Counters/timings of the last render issued from this thread (waits for it to finish). */
 int rtw_stats(rtw_stats_t *out);
 

@@ -49,6 +49,7 @@ from .wide_aperture import (  # noqa: F401
 from .present import (  # noqa: F401
     make_present, present, present_batch_into, present_bytes, present_into, render_presented, render_presented_batch,
 )
+from .rays import cast_rays, cast_rays_into, make_rays_params  # noqa: F401
 from . import imageio  # noqa: F401
 
 __all__ = [
@@ -76,4 +77,5 @@ __all__ = [
     "make_wide_aperture", "wide_aperture_work_bytes", "wide_aperture", "wide_aperture_into", "render_wide_aperture",
     "lens_table", "wide_aperture_batch_work_bytes", "wide_aperture_batch", "wide_aperture_batch_into", "focus_bracket", "render_wide_aperture_batch",
     "make_present", "present_bytes", "present", "present_into", "present_batch_into", "render_presented", "render_presented_batch",
+    "cast_rays", "cast_rays_into", "make_rays_params",
 ]

@@ -55,6 +55,7 @@ SYMBOLS = [
     "rtw_present_bytes", "rtw_present_device_f32", "rtw_present_device_f64", "rtw_present_batch_device_f32", "rtw_present_batch_device_f64",
     "rtw_present_f32", "rtw_present_f64", "rtw_render_presented_f32", "rtw_render_presented_f64", "rtw_render_presented_batch_f32",
     "rtw_render_presented_batch_f64",
+    "rtw_cast_rays_device_f32", "rtw_cast_rays_device_f64", "rtw_cast_rays_f32", "rtw_cast_rays_f64",
 ]
 
 
@@ -175,6 +176,14 @@ class Present(C.Structure):
 
 
 assert C.sizeof(Present) == 32
+
+
+class RaysParams(C.Structure):
+    """rtw_rays_params"""
+    _fields_ = [(k, C.c_int32) for k in ("flags", "device", "max_workgroups", "reserved")] + [("tmin", C.c_double)]
+
+
+assert C.sizeof(RaysParams) == 24
 
 _lib = None
 
@@ -301,6 +310,8 @@ def lib():
         getattr(L, "rtw_present_" + sfx).argtypes = [pr, i32, i32, ptr, ptr]
         getattr(L, "rtw_render_presented_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), C.POINTER(Params), dn, pr, ptr]
         getattr(L, "rtw_render_presented_batch_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), dn, pr, ptr]
+        getattr(L, "rtw_cast_rays_device_" + sfx).argtypes = [ptr, ptr, C.c_int64, C.POINTER(RaysParams), ptr, ptr, ptr]
+        getattr(L, "rtw_cast_rays_" + sfx).argtypes = [C.POINTER(SceneT), ptr, C.c_int64, C.POINTER(RaysParams), ptr, ptr]
     L.rtw_present_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.rtw_present_bytes.restype = C.c_int64
     L.rtw_temporal_state_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]

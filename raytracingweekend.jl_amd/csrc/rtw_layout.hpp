@@ -141,4 +141,27 @@ struct LensBatchLayout {
     }
 };
 
+// Ray queries (include/rtw_hip.h rtw_cast_rays_*), in BYTES: n rays of 8 elements, n indices of 4 bytes, n records of 8 elements (records
+// false: none -- the region is empty).  off_*, total: the regions of a context's device buffer for the host-buffer form -- the indices at
+// 0 (what the one-device path copies out last), the records, the rays.
+struct RaysLayout {
+    size_t rays_b, idx_b, rec_b, off_rec, off_rays, total;
+    RaysLayout(size_t elem, int64_t n, bool records) {
+        const size_t rays = n > 0 ? (size_t)n : 0;
+        rays_b = rays * 8 * elem; idx_b = rays * sizeof(int32_t); rec_b = records ? rays * 8 * elem : 0;
+        DevLayout L;
+        L.add(idx_b); off_rec = L.add(rec_b); off_rays = L.add(rays_b);
+        total = L.total;
+    }
+};
+// The persistent grid of the ray kernel: workgroups of 256 lanes, min(ceil(n / 256), CUs x resident workgroups per CU), capped by
+// max_workgroups when that is not 0; at least 1.  (n < 2^31, so the result fits an int whatever the device reports.)
+inline int rays_grid(int64_t n, int num_cus, int blocks_per_cu, int32_t max_workgroups) {
+    int64_t g = (n + 255) / 256;
+    const int64_t resident = (int64_t)(num_cus > 0 ? num_cus : 1) * (blocks_per_cu > 0 ? blocks_per_cu : 1);
+    if (g > resident) g = resident;
+    if (max_workgroups > 0 && g > max_workgroups) g = max_workgroups;
+    return g < 1 ? 1 : (int)g;
+}
+
 }  // namespace rtwh

@@ -308,6 +308,38 @@ int render_host_motion(const SceneT *scene, const CamT *cam, const rtw_params *p
         {0, motion, mo_b});
 }
 
+// Ray queries on host buffers (rtw_cast_rays_*): the stage path (stage_one_device) WITH the scene and a record, as render_one_device runs
+// it -- a leased context of the device with the scene uploaded (the cached one when its bytes are the same) and a device buffer that holds
+// the indices, the records and the rays (RaysLayout); ONE H2D of the rays, ONE launch, ONE D2H of the records where asked for and ONE of
+// the indices, then the counters of the record into this thread's last render.
+template <typename T, typename SceneT>
+int cast_rays_host(const SceneT *scene, const T *rays, int64_t n, const rtw_rays_params *p, int32_t *idx, T *rec) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !rays || !idx) return fail(-1, "null argument");
+    if (int rc = validate_rays(p, n)) return rc;
+    if (scene->n < 0) return fail(-2, "negative sphere count");
+    if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
+    const RaysLayout R(sizeof(T), n, rec != nullptr);
+    if (int rc = check_alias({{"idx", idx, R.idx_b}, {"rec", rec, R.rec_b}}, {{"rays", rays, R.rays_b}}, "the rays")) return rc;
+    if (n == 0) return 0;               // nothing enqueued; this thread's last render is left alone
+    DeviceGuard guard;
+    release_last();
+    RenderRec *rrec = nullptr;
+    CtxPtr rctx;
+    rtw_rays_params q = *p;
+    int rc = stage_one_device<T>(p->device, scene, R.total, "the rays", {{R.off_rays, rays, R.rays_b}},
+        [&](HostCtx *hc, char *base) {
+            q.device = hc->device;
+            return launch_rays<T>(hc->scene, base + R.off_rays, n, &q, base, rec ? base + R.off_rec : nullptr, hc->stream, &rrec, &rctx);
+        },
+        {0, idx, R.idx_b}, {{R.off_rec, rec, R.rec_b}}, "the records");
+    if (!rc) rc = resolve_rec(rrec, &g_last.agg);
+    if (!rc) g_last.per_device.emplace_back(q.device, g_last.agg.kernel_ms);
+    if (rrec) release_rec(rctx, rrec, rc == 0);
+    g_last.resolved = rc == 0;
+    return rc;
+}
+
 // The launch sequence of render + feature pass + filter on a leased context (render_host_filtered, render_host_presented): the linear image, the
 // features over all `nch` effective chunks and the filter with the caller's gamma into the regions R of hc->d_img.  `q`: the caller's params bound
 // to the lease's device; rec / frec: the render's and the feature pass's records.
@@ -786,6 +818,12 @@ int rtw_first_hit_motion_f32(const rtw_scene_f32 *scene, const rtw_camera_f32 *c
 }
 int rtw_first_hit_motion_f64(const rtw_scene_f64 *scene, const rtw_camera_f64 *cam, const rtw_params *p, const double *table, double *motion) {
     return render_host_motion<double>(scene, cam, p, table, motion);
+}
+int rtw_cast_rays_f32(const rtw_scene_f32 *scene, const float *rays, int64_t n, const rtw_rays_params *p, int32_t *idx, float *rec) {
+    return cast_rays_host<float>(scene, rays, n, p, idx, rec);
+}
+int rtw_cast_rays_f64(const rtw_scene_f64 *scene, const double *rays, int64_t n, const rtw_rays_params *p, int32_t *idx, double *rec) {
+    return cast_rays_host<double>(scene, rays, n, p, idx, rec);
 }
 int rtw_render_animation_f32(const rtw_scene_f32 *scenes, const rtw_camera_f32 *cams, int32_t n_frames, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                              const rtw_temporal_clamp_t *c, const rtw_denoise_t *d, float *out) {

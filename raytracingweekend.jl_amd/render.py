@@ -192,6 +192,13 @@ class DeviceRenderer:
         from .features import features_into
         return features_into(self, d_out_ptr, image_width, n_samples, **kw)
 
+    def cast_rays_into(self, d_rays_ptr, n, d_idx_ptr, d_rec_ptr=0, **kw):
+        """Enqueue a ray query (rtw_cast_rays_device_f32/_f64) of this scene: the closest hits of the ``n`` rays at ``d_rays_ptr`` (n * 8
+        elements, 16-byte aligned) into ``d_idx_ptr`` (n int32) and ``d_rec_ptr`` (n * 8 elements; 0: no records).  The camera is not
+        used.  Keywords: ``rays.cast_rays_into``."""
+        from .rays import cast_rays_into
+        return cast_rays_into(self.handle, d_rays_ptr, n, d_idx_ptr, d_rec_ptr, T=self.T, **kw)
+
     def features_batch_into(self, d_out_ptr, cams, image_width, n_samples, **kw):
         """Enqueue ONE feature launch (rtw_render_features_batch_device_f32/_f64) of this scene through ``cams`` into device memory at
         ``d_out_ptr``: len(cams) consecutive buffers of H*W*8 elements, 16-byte aligned.  Keywords: ``features.features_batch_into``."""
