@@ -1613,6 +1613,66 @@ int rtw_cast_rays_device_f64(rtw_scene_handle scene, const void *d_rays, int64_t
 int rtw_cast_rays_f32(const rtw_scene_f32 *scene, const float *rays, int64_t n, const rtw_rays_params *p, int32_t *idx, float *rec /* may be NULL */);
 int rtw_cast_rays_f64(const rtw_scene_f64 *scene, const double *rays, int64_t n, const rtw_rays_params *p, int32_t *idx, double *rec /* may be NULL */);
 
+/* Radiance queries: ray_color along caller-supplied rays.  The ray queries above stop at the hit; this block runs the whole Monte Carlo
+ * estimate the renders are built around -- scan, scatter, sky, bounce by bounce -- on rays that belong to no pixel and no camera: light
+ * and irradiance probes, light baking at surface points, reflection captures, radiance along the rays of a caller's own camera model
+ * (fisheye, orthographic, panoramas), the continuation of paths a caller started itself.
+ *
+ * The definition.  Arithmetic is in T, colour in binary64; nothing is normalised.
+ *   The input is the ray list of the ray queries as it stands: n rays of 8 elements of T, ox oy oz dx dy dz tmax tag, so one buffer serves
+ * both calls.  Elements 6 and 7 are not read: ray_color scans with tmin = T(1e-4) and tmax = +inf.
+ *   Sample s in [0, spp) of ray i is the reference's ray_color(scene, o_i, d_i, max_depth) (src/ray_color.jl:14-38; the product of the
+ * attenuations formed front to back, as every render here forms it) on a FRESH stream: the stream rule of the renders (DESIGN.md
+ * section 5) with seed, p = first_stream + i in the place of the pixel and c = first_sample + s in the place of the chunk.  One stream
+ * per SAMPLE, on purpose: the result does not depend on how samples are dealt to lanes, waves or launches.  No camera draw happens: the
+ * first draw of a stream belongs to the first scatter.
+ *   The result for ray i is three binary64 values at out[3 i]: the three channel sums of its spp radiances in 64.64 fixed point (the
+ * pixel's exact sum), each rounded once to binary64 and divided by (double)spp.  They are linear -- no gamma, no conversion to T: a caller
+ * weights and sums them further.  `out` is n x 3 binary64 in both precisions.
+ *   Poisoning: a sample radiance that is NaN, infinite or >= 2^31 makes all three values of that ray NaN (the pixel's rule).
+ *   Every finite ray has a defined result; non-finite rays are outside the contract.  Directions longer than 1.0009 and far origins take
+ * the scan's slow path, unchanged.
+ *   Two consequences.  A list traced in two calls, the second with first_stream advanced by the first call's n, gives the words of the
+ * one call.  A ray placed twice in a list gets two independent estimates (and that is how one ray gets more lanes than one today).
+ * Another seed, first_stream or first_sample moves the words of a ray whose path draws a direction and reaches the sky (a first hit on
+ * a Lambertian sphere, say); it need not move a ray that misses at once (sky(d) on every stream), one that starts inside an opaque
+ * sphere (black on every stream) or one that meets only glass and polished metal (a stream decides a choice there, not a direction).
+ *
+ * rtw_trace_params.  flags: RTW_FLAG_SCAN_VALU and the two RTW_FLAG_NUMERICS_* bits (they exclude each other); RTW_FLAG_GROUP_CULL is
+ * accepted and runs the plain scans, as in the ray queries; any other bit -> -2.  device: as in rtw_params.  max_workgroups: 0 =
+ * automatic, otherwise >= 1, a cap on the launch grid -- scheduling only, the words are identical for every value.  spp >= 1.  max_depth:
+ * the range rtw_params.max_depth has, [0, 2^22) (0: every sample is black).  reserved: 0.  seed, first_stream, first_sample: above.
+ *
+ * The device form (suffix _device_f32 / _device_f64): ONE launch, asynchronous on `hip_stream` of the scene's device, re-entrant like the
+ * device form of the ray queries.  `d_rays` (n * 8 elements) is a 16-byte aligned DEVICE pointer, `d_out` (n * 3 binary64) an 8-byte
+ * aligned one; nothing beyond ray n - 1 is read or written.  rtw_stats() afterwards reports samples = n x spp, segments = the scans with
+ * a live ray (the reference's count), sphere_tests = segments x spheres and the kernel time.
+ *   The host-buffer form (suffix _f32 / _f64): blocking, through the cached per-device context like the host form of the ray queries: one
+ * H2D of the rays, one launch, one D2H of `out`.
+ *   Refusals, all decided before any HIP call: a null argument -> -1; n < 0, a flag bit that is not named above, both numerics bits,
+ * reserved != 0, device < -1, max_workgroups < 0, spp < 1, max_depth outside its range, first_stream + n or first_sample + spp beyond
+ * 2^64 - 1, d_rays not 16-byte aligned, d_out not 8-byte aligned, host buffers that overlap -> -2; a handle of the other precision or of
+ * another device -> -4; n >= 2^31 -> -5.  n == 0 -> 0 with nothing enqueued (rtw_stats() is left alone).
+ *   Left out on purpose: one ray's samples split across lanes (few rays x very many samples: repeat the ray in the
+ * list, with first_sample apart), the group cull on caller rays, tmin or tmax per ray, the exact sums as an output (resumable passes),
+ * device lists, the Julia shim.
+ * Additive to ABI 4: detected by symbol lookup. */
+typedef struct {
+    int32_t flags;            /* RTW_FLAG_SCAN_VALU, RTW_FLAG_GROUP_CULL, RTW_FLAG_NUMERICS_*                    */
+    int32_t device;           /* HIP ordinal, or -1 = the current device (device form: the handle's)         */
+    int32_t max_workgroups;   /* 0 = automatic, else a cap on the launch grid (scheduling only)              */
+    int32_t spp;              /* samples per ray, >= 1                                                       */
+    int32_t max_depth;        /* ray_color's depth, [0, 2^22) (the reference's default: 16)                  */
+    int32_t reserved;         /* 0                                                                           */
+    uint64_t seed;            /* the stream seed                                                             */
+    uint64_t first_stream;    /* stream index of ray 0: ray i draws from stream first_stream + i             */
+    uint64_t first_sample;    /* index of the first sample: sample s is chunk first_sample + s of the stream */
+} rtw_trace_params;           /* 48 bytes */
+int rtw_trace_rays_device_f32(rtw_scene_handle scene, const void *d_rays, int64_t n, const rtw_trace_params *p, void *d_out, void *hip_stream);
+int rtw_trace_rays_device_f64(rtw_scene_handle scene, const void *d_rays, int64_t n, const rtw_trace_params *p, void *d_out, void *hip_stream);
+int rtw_trace_rays_f32(const rtw_scene_f32 *scene, const float *rays, int64_t n, const rtw_trace_params *p, double *out);
+int rtw_trace_rays_f64(const rtw_scene_f64 *scene, const double *rays, int64_t n, const rtw_trace_params *p, double *out);
+
 /* Counters/timings of the last render issued from this thread (waits for it to finish). */
 int rtw_stats(rtw_stats_t *out);
 

@@ -50,6 +50,7 @@ from .present import (  # noqa: F401
     make_present, present, present_batch_into, present_bytes, present_into, render_presented, render_presented_batch,
 )
 from .rays import cast_rays, cast_rays_into, make_rays_params  # noqa: F401
+from .trace_rays import make_trace_params, trace_rays, trace_rays_into  # noqa: F401
 from . import imageio  # noqa: F401
 
 __all__ = [
@@ -78,4 +79,5 @@ __all__ = [
     "lens_table", "wide_aperture_batch_work_bytes", "wide_aperture_batch", "wide_aperture_batch_into", "focus_bracket", "render_wide_aperture_batch",
     "make_present", "present_bytes", "present", "present_into", "present_batch_into", "render_presented", "render_presented_batch",
     "cast_rays", "cast_rays_into", "make_rays_params",
+    "trace_rays", "trace_rays_into", "make_trace_params",
 ]

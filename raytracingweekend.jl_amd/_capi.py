@@ -56,6 +56,7 @@ SYMBOLS = [
     "rtw_present_f32", "rtw_present_f64", "rtw_render_presented_f32", "rtw_render_presented_f64", "rtw_render_presented_batch_f32",
     "rtw_render_presented_batch_f64",
     "rtw_cast_rays_device_f32", "rtw_cast_rays_device_f64", "rtw_cast_rays_f32", "rtw_cast_rays_f64",
+    "rtw_trace_rays_device_f32", "rtw_trace_rays_device_f64", "rtw_trace_rays_f32", "rtw_trace_rays_f64",
 ]
 
 
@@ -185,6 +186,15 @@ class RaysParams(C.Structure):
 
 assert C.sizeof(RaysParams) == 24
 
+
+class TraceParams(C.Structure):
+    """rtw_trace_params"""
+    _fields_ = ([(k, C.c_int32) for k in ("flags", "device", "max_workgroups", "spp", "max_depth", "reserved")]
+                + [(k, C.c_uint64) for k in ("seed", "first_stream", "first_sample")])
+
+
+assert C.sizeof(TraceParams) == 48
+
 _lib = None
 
 
@@ -312,6 +322,8 @@ def lib():
         getattr(L, "rtw_render_presented_batch_" + sfx).argtypes = [C.POINTER(SceneT), C.POINTER(CamT), i32, seeds, C.POINTER(Params), dn, pr, ptr]
         getattr(L, "rtw_cast_rays_device_" + sfx).argtypes = [ptr, ptr, C.c_int64, C.POINTER(RaysParams), ptr, ptr, ptr]
         getattr(L, "rtw_cast_rays_" + sfx).argtypes = [C.POINTER(SceneT), ptr, C.c_int64, C.POINTER(RaysParams), ptr, ptr]
+        getattr(L, "rtw_trace_rays_device_" + sfx).argtypes = [ptr, ptr, C.c_int64, C.POINTER(TraceParams), ptr, ptr]
+        getattr(L, "rtw_trace_rays_" + sfx).argtypes = [C.POINTER(SceneT), ptr, C.c_int64, C.POINTER(TraceParams), ptr]
     L.rtw_present_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32]
     L.rtw_present_bytes.restype = C.c_int64
     L.rtw_temporal_state_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]

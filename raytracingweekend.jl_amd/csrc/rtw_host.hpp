@@ -16,6 +16,7 @@
 //   rtw_unit.hip         the T0 unit entry points (rtw_units.hpp)
 //   rtw_features.hip     first-hit feature buffers: one launch of the feature kernel (rtw_features.hpp) for one view or a batch of views, the device-resident entry points
 //   rtw_rays.hip         ray queries: closest hits of caller-supplied rays -- their checks, one launch of the ray kernel (rtw_rays.hpp), the device-resident entry points
+//   rtw_trace_rays.hip   radiance queries: ray_color of caller-supplied rays -- their checks, one launch of the radiance kernel (rtw_trace_rays.hpp), the device-resident entry points
 //   rtw_denoise.hip      the feature-guided denoiser: its checks, the launch sequence of its kernels (rtw_denoise.hpp) for one frame or a batch of frames, the device-resident entry points
 //   rtw_upsample.hip     the feature-guided upsampler: its checks, the launch sequence (the denoiser's prepare and level kernels at the small size, then rtw_upsample.hpp at the full size), the device-resident entry points
 //   rtw_temporal.hip     temporal reprojection: its checks, the host constants and the one launch of a step for one path or a batch of paths (rtw_temporal.hpp; clamped: rtw_temporal_clamp.hpp), the device-resident entry points
@@ -28,7 +29,7 @@
 // A function that exists once per precision and crosses units is declared here ONCE, as a template under its own name, and the unit that
 // defines it ends with its two explicit instantiations (float with rtw_camera_f32 / rtw_scene_f32, double with the _f64 structs); a caller
 // names the precision it has -- launch_temporal<T>(...) -- and the struct types are deduced.  Declared in this form:
-//   rtw_scene.hip upload_scene; rtw_launch.hip launch_render, upload_views; rtw_features.hip launch_features; rtw_rays.hip launch_rays; rtw_denoise.hip launch_denoise;
+//   rtw_scene.hip upload_scene; rtw_launch.hip launch_render, upload_views; rtw_features.hip launch_features; rtw_rays.hip launch_rays; rtw_trace_rays.hip launch_trace_rays; rtw_denoise.hip launch_denoise;
 //   rtw_upsample.hip launch_upsample; rtw_temporal.hip launch_temporal, temporal_table, launch_temporal_noise; rtw_motion.hip launch_motion,
 //   motion_table; rtw_motion_blur.hip launch_motion_blur; rtw_defocus.hip validate_lens, launch_defocus, launch_defocus_prepare,
 //   launch_defocus_gather, lens_table_entry; rtw_wide_aperture.hip launch_wide_aperture, validate_lens_batch, lens_table; rtw_present.hip
@@ -381,6 +382,14 @@ const void *features_tiled_batch_kernel_f64(bool mfma, bool lds_scene, bool fixe
 int validate_rays(const rtw_rays_params *p, int64_t n);
 template <typename T>
 int launch_rays(rtw_scene_handle scene, const void *d_rays, int64_t n, const rtw_rays_params *p, void *d_idx, void *d_rec, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
+
+// rtw_trace_rays.hip -- radiance queries (include/rtw_hip.h rtw_trace_rays_*).  validate_trace_rays: every check of a call that needs neither
+// a device nor a pointer -- the parameters, the count and the two 64-bit ranges (n == 0 passes: the caller returns 0 without a launch).
+// launch_trace_rays: enqueue the radiance kernel (ONE launch) for n >= 1 rays on `stream`, `rec` receives the counters and the kernel's
+// events like a render's; d_rays 16-byte, d_out (n x 3 binary64) 8-byte aligned DEVICE pointers.
+int validate_trace_rays(const rtw_trace_params *p, int64_t n);
+template <typename T>
+int launch_trace_rays(rtw_scene_handle scene, const void *d_rays, int64_t n, const rtw_trace_params *p, void *d_out, hipStream_t stream, RenderRec **rec_out, CtxPtr *ctx_out);
 
 // rtw_denoise.hip -- the feature-guided denoiser (include/rtw_hip.h rtw_denoise_*, rtw_filter_batch_*).  validate_denoise: the checks of one
 // frame that need no device; validate_filter_batch: those, n_views and the batch's size.

@@ -164,4 +164,25 @@ inline int rays_grid(int64_t n, int num_cus, int blocks_per_cu, int32_t max_work
     return g < 1 ? 1 : (int)g;
 }
 
+// Radiance queries (include/rtw_hip.h rtw_trace_rays_*), in BYTES: n rays of 8 elements, n results of 3 binary64 whatever the element is.
+// off_rays, total: the regions of a context's device buffer for the host-buffer form -- the results at 0 (what the one-device path copies
+// out), the rays behind them.
+struct TraceRaysLayout {
+    size_t rays_b, out_b, off_rays, total;
+    TraceRaysLayout(size_t elem, int64_t n) {
+        const size_t rays = n > 0 ? (size_t)n : 0;
+        rays_b = rays * 8 * elem; out_b = rays * 3 * sizeof(double);
+        DevLayout L;
+        L.add(out_b); off_rays = L.add(rays_b);
+        total = L.total;
+    }
+};
+// does first + count leave the unsigned 64-bit range?  (the streams first_stream + i of n rays, the samples first_sample + s of spp)
+inline bool u64_range_wraps(uint64_t first, uint64_t count) { return first > UINT64_MAX - count; }
+// The grid of the radiance kernel: the ray kernel's -- ceil(n / 256) workgroups, capped by the resident ones and by max_workgroups, at
+// least 1.  Its waves CLAIM batches of 64 rays from a counter, so every grid >= 1 walks every batch exactly once.
+inline int trace_rays_grid(int64_t n, int num_cus, int blocks_per_cu, int32_t max_workgroups) { return rays_grid(n, num_cus, blocks_per_cu, max_workgroups); }
+// batches of 64 rays in a list of n (n < 2^31)
+inline unsigned trace_rays_batches(int64_t n) { return n > 0 ? (unsigned)((n + 63) / 64) : 0u; }
+
 }  // namespace rtwh

@@ -340,6 +340,37 @@ int cast_rays_host(const SceneT *scene, const T *rays, int64_t n, const rtw_rays
     return rc;
 }
 
+// Radiance queries on host buffers (rtw_trace_rays_*): cast_rays_host's path with the radiance kernel -- a device buffer that holds the
+// results and the rays (TraceRaysLayout); ONE H2D of the rays, ONE launch, ONE D2H of the results, then the counters of the record into
+// this thread's last render.
+template <typename T, typename SceneT>
+int trace_rays_host(const SceneT *scene, const T *rays, int64_t n, const rtw_trace_params *p, double *out) {
+    if (!p) return fail(-1, "null params");
+    if (!scene || !rays || !out) return fail(-1, "null argument");
+    if (int rc = validate_trace_rays(p, n)) return rc;
+    if (scene->n < 0) return fail(-2, "negative sphere count");
+    if (s_has_bad_scene(scene)) return fail(-1, "null scene array");
+    const TraceRaysLayout R(sizeof(T), n);
+    if (int rc = check_alias({{"out", out, R.out_b}}, {{"rays", rays, R.rays_b}}, "the rays")) return rc;
+    if (n == 0) return 0;               // nothing enqueued; this thread's last render is left alone
+    DeviceGuard guard;
+    release_last();
+    RenderRec *rrec = nullptr;
+    CtxPtr rctx;
+    rtw_trace_params q = *p;
+    int rc = stage_one_device<T>(p->device, scene, R.total, "the rays", {{R.off_rays, rays, R.rays_b}},
+        [&](HostCtx *hc, char *base) {
+            q.device = hc->device;
+            return launch_trace_rays<T>(hc->scene, base + R.off_rays, n, &q, base, hc->stream, &rrec, &rctx);
+        },
+        {0, out, R.out_b});
+    if (!rc) rc = resolve_rec(rrec, &g_last.agg);
+    if (!rc) g_last.per_device.emplace_back(q.device, g_last.agg.kernel_ms);
+    if (rrec) release_rec(rctx, rrec, rc == 0);
+    g_last.resolved = rc == 0;
+    return rc;
+}
+
 // The launch sequence of render + feature pass + filter on a leased context (render_host_filtered, render_host_presented): the linear image, the
 // features over all `nch` effective chunks and the filter with the caller's gamma into the regions R of hc->d_img.  `q`: the caller's params bound
 // to the lease's device; rec / frec: the render's and the feature pass's records.
@@ -824,6 +855,12 @@ int rtw_cast_rays_f32(const rtw_scene_f32 *scene, const float *rays, int64_t n, 
 }
 int rtw_cast_rays_f64(const rtw_scene_f64 *scene, const double *rays, int64_t n, const rtw_rays_params *p, int32_t *idx, double *rec) {
     return cast_rays_host<double>(scene, rays, n, p, idx, rec);
+}
+int rtw_trace_rays_f32(const rtw_scene_f32 *scene, const float *rays, int64_t n, const rtw_trace_params *p, double *out) {
+    return trace_rays_host<float>(scene, rays, n, p, out);
+}
+int rtw_trace_rays_f64(const rtw_scene_f64 *scene, const double *rays, int64_t n, const rtw_trace_params *p, double *out) {
+    return trace_rays_host<double>(scene, rays, n, p, out);
 }
 int rtw_render_animation_f32(const rtw_scene_f32 *scenes, const rtw_camera_f32 *cams, int32_t n_frames, const uint64_t *seeds, const rtw_params *p, const rtw_temporal_t *t,
                              const rtw_temporal_clamp_t *c, const rtw_denoise_t *d, float *out) {

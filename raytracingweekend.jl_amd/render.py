@@ -199,6 +199,13 @@ class DeviceRenderer:
         from .rays import cast_rays_into
         return cast_rays_into(self.handle, d_rays_ptr, n, d_idx_ptr, d_rec_ptr, T=self.T, **kw)
 
+    def trace_rays_into(self, d_rays_ptr, n, d_out_ptr, **kw):
+        """Enqueue a radiance query (rtw_trace_rays_device_f32/_f64) of this scene: ray_color along the ``n`` rays at ``d_rays_ptr`` (n * 8
+        elements, 16-byte aligned), ``spp`` samples each, into ``d_out_ptr`` (n * 3 float64, linear).  The camera is not used.
+        Keywords: ``trace_rays.trace_rays_into``."""
+        from .trace_rays import trace_rays_into
+        return trace_rays_into(self.handle, d_rays_ptr, n, d_out_ptr, T=self.T, **kw)
+
     def features_batch_into(self, d_out_ptr, cams, image_width, n_samples, **kw):
         """Enqueue ONE feature launch (rtw_render_features_batch_device_f32/_f64) of this scene through ``cams`` into device memory at
         ``d_out_ptr``: len(cams) consecutive buffers of H*W*8 elements, 16-byte aligned.  Keywords: ``features.features_batch_into``."""

@@ -4,7 +4,7 @@ usage: python tools/kernel_resources.py [--unit NAME.hip ...] [extra hipcc flags
 The instances live in rtw_launch.hip and, the BATCH && ACCUM ones, in rtw_batch_accum_f32.hip / _f64.hip: one table over all three.
 --unit names other translation units instead (rtw_features.hip: the instances of the feature kernel, the batched ones among them; rtw_features_accum_batch_f32.hip /
 _f64.hip: its tiled batched instances; rtw_denoise.hip: the denoiser's kernels and the batched level kernels; rtw_accum_kernels.hip: the accumulator's kernels, the noise map and the
-batched resolve and noise map among them; rtw_temporal.hip: the instances of the temporal step, with and without moments, the temporal noise map and their batched (`paths`) twins; rtw_present.hip: the instances of the present kernel; rtw_motion.hip: the instances of the first-hit motion pass; rtw_rays.hip: the eight instances of the ray-query kernel (its LDS is dynamic: 11 KB + the scene copy, not in the table); rtw_motion_blur.hip: the three kernels of the motion-blur stage; rtw_defocus.hip: the two kernels of the defocus stage (the gather's LDS is dynamic: (16 + 2*max_radius) * 192 elements, not in the table); rtw_wide_aperture.hip: the two kernels the wide-aperture stage adds, at both scales; both units: with their batched (`views`) twins; `motion`: the step instances that read its plane)."""
+batched resolve and noise map among them; rtw_temporal.hip: the instances of the temporal step, with and without moments, the temporal noise map and their batched (`paths`) twins; rtw_present.hip: the instances of the present kernel; rtw_motion.hip: the instances of the first-hit motion pass; rtw_rays.hip: the eight instances of the ray-query kernel (its LDS is dynamic: 11 KB + the scene copy, not in the table); rtw_trace_rays.hip: the eight instances of the radiance-query kernel (the same dynamic LDS); rtw_motion_blur.hip: the three kernels of the motion-blur stage; rtw_defocus.hip: the two kernels of the defocus stage (the gather's LDS is dynamic: (16 + 2*max_radius) * 192 elements, not in the table); rtw_wide_aperture.hip: the two kernels the wide-aperture stage adds, at both scales; both units: with their batched (`views`) twins; `motion`: the step instances that read its plane)."""
 import os, re, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 out = ""
@@ -77,6 +77,9 @@ for r in rows:
     elif re.match(r"_ZN3rtw\d+cast_rays_kernelI([fd])Lb([01])ELb([01])E", n):
         m = re.match(r"_ZN3rtw\d+cast_rays_kernelI([fd])Lb([01])ELb([01])E", n)
         label = f"rays cast_rays<{'f32' if m.group(1) == 'f' else 'f64'}{', mfma' if m.group(2) == '1' else ', valu'}{', lds-scene' if m.group(3) == '1' else ', global-scene'}>"
+    elif re.match(r"_ZN3rtw\d+trace_rays_kernelI([fd])Lb([01])ELb([01])E", n):
+        m = re.match(r"_ZN3rtw\d+trace_rays_kernelI([fd])Lb([01])ELb([01])E", n)
+        label = f"radiance trace_rays<{'f32' if m.group(1) == 'f' else 'f64'}{', mfma' if m.group(2) == '1' else ', valu'}{', lds-scene' if m.group(3) == '1' else ', global-scene'}>"
     elif "unit_kernel" in n:
         label = "unit_kernel<%s>" % ("f32" if "IfE" in n else "f64")
     else:
